@@ -2,7 +2,9 @@
 """Throughput of the keyword-spotting hot path on MI355X: 1 s / 16 kHz clips per second, end to end
 (device-resident int16 PCM -> MFCC -> DS-CNN -> logits + label), BASELINE.json's metric.
 
-    python bench.py                                   # 1 GPU, defaults that finish within minutes
+    python bench.py                                   # 1 GPU, the headline alone: set up, warm up, time, one line
+    python bench.py --full                            # + CPU baseline, parity, bf16 triple, every other configuration
+    python bench.py --dump-outputs DIR                # + the last timed step's outputs as DIR/<name>.npy (float32)
     python bench.py --gpus 8                          # launches its own 8 ranks (one process per GPU)
     python bench.py --gpus 8 --total-batch 8192       # BASELINE configs[3] as written: 8 x 1024, strong scaling
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -20,9 +22,15 @@ With --gpus N > 1 and no WORLD_SIZE in the environment the script is its own lau
 touches the GPU starts N children (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set), relays
 rank 0's line and exits with the worst child code -- no exec of a process that has initialised HIP.
 
-At N = 1 the line also carries, under "configs", one short measurement of every other BASELINE.json configuration
-(each with its own clock spin-up): configs[1] MFCC only, configs[2] read literally (cnn-trad-fpool3, build-defined),
-configs[3]'s per-GPU shape (DS-CNN, 1024 clips), configs[4] streaming (64 streams, p50 / p99 per 10 ms hop).
+A plain run measures the headline and nothing else.  With --full the line also carries what takes work of its own after
+the timed region: the golden-clip parity, the bf16 triple timed on the same context, the CPU baseline and, at N = 1,
+under "configs", one short measurement of every other BASELINE.json configuration (each with its own clock spin-up):
+configs[1] MFCC only, configs[2] read literally (cnn-trad-fpool3, build-defined), configs[3]'s per-GPU shape (DS-CNN,
+1024 clips), configs[4] streaming (64 streams, p50 / p99 per 10 ms hop).
+
+--dump-outputs DIR writes what the timed path returned in its last step (logits and labels; features for
+--model mfcc-only) as float32 DIR/<name>.npy.  Inputs and weights are seeded, so two builds run with the same
+arguments can be compared output for output.
 
 Before the W warm-up steps the step runs `--spinup` more untimed times (default 60): from idle the GPU needs ~30 steps
 for its clocks to settle, and the timed K steps should see the steady state whatever W the caller picked.
@@ -60,6 +68,7 @@ CNNTRAD_FLOP_PER_CLIP = CNNTRAD_CONV_FLOP_PER_CLIP + 2 * (19008 * 32 + 32 * 128 
 CNNTRAD_CONV_EXECUTED_BF16_FLOP_PER_CLIP = (33 * 2 * 10 + 10 * 2 * 160) * 6 * 32 * 32 * 16 * 2
 GOLDEN = os.path.join(ROOT, "tests", "golden", "e2e_golden.npz")
 LAUNCH_TIMEOUT_S = 1800                        # self-launched N > 1 runs: the parent gives its children this long
+DUMP_LIMIT_BYTES = 64 << 20                    # --dump-outputs: at most this much in all (over every rank)
 
 
 # ------------------------------------------------------------------------------------------ host-only helpers
@@ -82,6 +91,28 @@ def timed_steps(step_fn, steps: int, barrier, device_sync, all_reduce_max):
     dt = time.perf_counter() - t0  # this rank's K steps; the clock is read BEFORE the closing barrier (a gloo round trip is not step time)
     barrier()
     return all_reduce_max(dt)
+
+
+def dump_outputs(out_dir: str, arrays: dict, rank: int = 0, world: int = 1, limit: int = DUMP_LIMIT_BYTES):
+    """--dump-outputs: one float32 DIR/<name>.npy per array (labels are small integers, exact in float32), suffixed
+    .rank<r> when N > 1.  Every array has one row per clip; if they exceed this rank's share of `limit`, the same fixed,
+    seeded sample of rows is written from each and the sampled row indices go to DIR/rows.npy.  Returns the paths."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes // max(len(a), 1) for a in arrays.values())
+    budget = limit // world
+    if n * row_bytes > budget:
+        k = max(1, budget // (row_bytes + 8))
+        rows = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    suffix = "" if world == 1 else f".rank{rank}"
+    paths = []
+    for name, a in arrays.items():
+        paths.append(os.path.join(out_dir, f"{name}{suffix}.npy"))
+        np.save(paths[-1], a)
+    return paths
 
 
 def pmc_traffic(kernel: str, workload: str = "ds-cnn"):
@@ -976,6 +1007,15 @@ def worker(args) -> int:
     d_ms, d_n = ctx.prof_read(_native.KWS_K_CNNTRAD_DENSE)
     ctx.prof_enable(False)
 
+    if args.dump_outputs:  # the last timed step's results, before anything after the timed region touches the buffers
+        if args.ingest == "host":
+            outs = {"logits": host_logits, "labels": host_labels}
+        elif args.model == "mfcc-only":
+            outs = {"features": feat_out.cpu().numpy()}
+        else:
+            outs = {"logits": logits.cpu().numpy(), "labels": labels.cpu().numpy()}
+        dump_outputs(args.dump_outputs, outs, rank, world)
+
     if rank == 0:
         value = total * args.steps / elapsed
         dscnn_ms, mfcc_ms = k_ms / max(k_n, 1), m_ms / max(m_n, 1)
@@ -996,7 +1036,7 @@ def worker(args) -> int:
                    "config": {"workload": f"configs[1]: batch={B}/GPU synthetic uniform int16 1s/16kHz clips, device-resident, "
                                           "MFCC(400/160/512, 26 mel, 10 cep) -> float32 [B,1,99,10]", **cfg},
                    "roofline": hbm_roofline(_native, mfcc_kid, m_n, mfcc_ms, B, "mfcc-only"), **multi}
-            if world == 1 and args.cpu_sample > 0:
+            if args.full and world == 1 and args.cpu_sample > 0:
                 from oracle import psf_mfcc as o_mfcc
 
                 n = min(args.cpu_sample, B, 512)
@@ -1060,7 +1100,7 @@ def worker(args) -> int:
                 out["frontend_refinement"] = refine_report(_native, ctx, B, stats0, args.steps)
             lab = labels.cpu().numpy()
             out["labels_seen"] = {"n_classes": int(len(np.unique(lab))), "logit_std_across_clips": float(logits.std(dim=0).mean().item())}
-            if golden is not None and not args.no_parity:  # the 48 diverse golden clips against the imported reference model's logits (data file)
+            if args.full and golden is not None and not args.no_parity:  # the 48 diverse golden clips against the imported reference model's logits (data file)
                 gw = torch.from_numpy(np.ascontiguousarray(golden["clips"])).to(dev)
                 gl = torch.empty((gw.shape[0], NUM_CLASSES), dtype=torch.float32, device=dev)
                 gy = torch.empty((gw.shape[0],), dtype=torch.int32, device=dev)
@@ -1071,7 +1111,7 @@ def worker(args) -> int:
                     "labels_identical": bool(np.array_equal(gy.cpu().numpy(), golden["he.label"][8:])),
                     "n_classes": int(len(set(golden["he.label"][8:].tolist()))), "clips": int(gw.shape[0]),
                     "source": "tests/golden/e2e_golden.npz: imported reference DS-CNN on the oracle's MFCC of 48 diverse clips"}
-            if world == 1 and not args.no_parity and ctx is not None:
+            if args.full and world == 1 and not args.no_parity and ctx is not None:
                 # the same step on the exact three-way bf16 split (six MFMAs per f32 k-block), same context, after the timed region
                 pair_logits = logits.clone()
                 ctx.set_pointwise_math(_native.PW_SPLIT_BF16)
@@ -1096,12 +1136,12 @@ def worker(args) -> int:
                     "note": "kws_set_pointwise_math(KWS_PW_SPLIT_BF16): the arithmetic of rounds 1-2, every f32 operand as three bf16 pieces"}
                 ctx.infer_i16(wav, logits, labels)  # leave the default arithmetic's results in the buffers
                 ctx.sync()
-            if world == 1 and args.cpu_sample > 0:
+            if args.full and world == 1 and args.cpu_sample > 0:
                 n = min(args.cpu_sample, B)
                 base, cpu_logits = cpu_baseline(clips[:n], blob)
                 out["cpu_baseline"] = base
                 out["parity_vs_cpu_max_abs_logit_err"] = float(np.abs(logits[:n].cpu().numpy() - cpu_logits).max())
-            if world == 1 and args.configs == "all":
+            if args.full and world == 1 and args.configs == "all":
                 ctx.close()
                 ctx = None
                 cpu_n = args.cpu_sample
@@ -1137,7 +1177,13 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=4096, help="clips per GPU per step (weak scaling)")
     ap.add_argument("--total-batch", type=int, default=0,
                     help="strong scaling: one batch of this many clips sharded over the GPUs (8192 = BASELINE configs[3] as written)")
-    ap.add_argument("--cpu-sample", type=int, default=2048, help="clips timed on the CPU baseline (0 = skip every CPU leg)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need, after the timed region: golden-clip parity, the "
+                         "bf16 triple on the same context, the CPU baseline and (N = 1) every other BASELINE configuration under `configs`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's outputs (logits and labels; features for --model mfcc-only) as float32 "
+                         "DIR/<name>.npy, at most 64 MB in all (a fixed, seeded sample of rows beyond that)")
+    ap.add_argument("--cpu-sample", type=int, default=2048, help="clips timed on the CPU baseline with --full (0 = skip every CPU leg)")
     ap.add_argument("--model", choices=["ds-cnn", "cnn-trad-fpool3", "mfcc-only"], default="ds-cnn",
                     help="ds-cnn: the reference's model (the driver's line); cnn-trad-fpool3: the build-defined model "
                          "BASELINE.json configs[2] names (parity unpinned against the reference, DESIGN.md 4.5); "
@@ -1146,7 +1192,7 @@ def parse_args(argv=None):
                     help="DS-CNN GEMM arithmetic of the timed steps: pair = KWS_PW_PAIR_F16 (the library's default), triple = KWS_PW_SPLIT_BF16 "
                          "(rounds 1-2; for counter passes and A/B runs -- the JSON line says which)")
     ap.add_argument("--configs", choices=["all", "none"], default="all",
-                    help="all: at N = 1 the ds-cnn line also measures the other BASELINE configurations under `configs`")
+                    help="all: with --full at N = 1 the ds-cnn line also measures the other BASELINE configurations under `configs`")
     ap.add_argument("--config-steps", type=int, default=100, help="timed steps of each side configuration")
     ap.add_argument("--stream-hops", type=int, default=340, help="pushes per mode of the streaming configuration (first 40 untimed)")
     ap.add_argument("--dist-backend", choices=["gloo", "nccl"], default="gloo",
@@ -1158,12 +1204,16 @@ def parse_args(argv=None):
                     help="device: inputs resident in HBM when the timed region starts (the contract's `value`); host: the timed step is "
                          "kws_infer_host_i16 on pageable host memory (PCIe inclusive), each rank pinned to its GPU's NUMA node")
     ap.add_argument("--no-parity", action="store_true",
-                    help="skip the extra launch on the golden clips after the timed region (profile runs: exact launch counts)")
+                    help="with --full, skip the extra launches on the golden clips and the bf16 triple after the timed region "
+                         "(profile runs: exact launch counts)")
     ap.add_argument("--prof-every", type=int, default=8,
                     help="HIP events around every n-th launch of each kernel inside the timed region (roofline.avg_kernel_ms); "
                          "a pair per launch costs the stream ~7 us = 2 %% of a 4096-clip step (tools/prof_overhead.py)")
     ap.add_argument("--selftest-cpu", action="store_true", help=argparse.SUPPRESS)  # launcher rehearsal on CPU (gloo), tests only
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0 or args.spinup < 0:
+        ap.error("--steps must be at least 1, --warmup and --spinup at least 0")
+    return args
 
 
 def main(argv=None) -> int:

@@ -12,7 +12,7 @@ WORKLOADS=${*:-"ds-cnn mfcc-only cnn-trad-fpool3 ds-cnn-1024 stream"}
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
-cd "$REPO" && timeout -k 10 500 python bench.py > "$OUT/${TAG}_bench_default.json" 2> "$OUT/bench_default.err" || { tail -5 "$OUT/bench_default.err"; exit 1; }
+cd "$REPO" && timeout -k 10 500 python bench.py --full > "$OUT/${TAG}_bench_default.json" 2> "$OUT/bench_default.err" || { tail -5 "$OUT/bench_default.err"; exit 1; }
 cd /tmp && export TMPDIR=/tmp
 SPIN=60; WARM=20
 for W in $WORKLOADS; do

@@ -8,9 +8,9 @@ timed on the host cores of the same box (core count stated)".
     python tools/scale_sweep.py --out profiles/r03_scale_sweep.json
 
 Every point is `python bench.py --gpus N ...` started as a FRESH child process before anything touches a GPU (bench.py is
-its own launcher for N > 1: one child interpreter per GPU, no exec after HIP init).  The N = 1 weak point is the plain
-bench line, so the sweep checks itself against it.  The sweep never computes an efficiency the driver would also
-compute -- it prints the absolute numbers and the ratio to N = 1 for the reader.  Points whose ranks share a GPU (a
+its own launcher for N > 1: one child interpreter per GPU, no exec after HIP init).  The N = 1 weak point is the bench
+line with --full (it carries the CPU baseline), so the sweep checks itself against it.  The sweep never computes an
+efficiency the caller of the benchmark would also compute -- it prints the absolute numbers and the ratio to N = 1 for the reader.  Points whose ranks share a GPU (a
 rehearsal on a smaller box) are kept and marked invalid.  Imports neither torch nor the HIP library."""
 from __future__ import annotations
 
@@ -104,8 +104,8 @@ def main(argv=None) -> int:
         common.append("--selftest-cpu")
     rows = []
     for n in counts:
-        # the CPU baseline and the side configurations ride on the N = 1 weak point only (the plain bench line)
-        extra = common + ([] if n == 1 else ["--cpu-sample", "0", "--configs", "none"])
+        # the CPU baseline and the side configurations ride on the N = 1 weak point only (the bench's --full line)
+        extra = common + (["--full"] if n == 1 else ["--cpu-sample", "0", "--configs", "none"])
         line, dt, err = run_point(n, extra, args.timeout)
         rows.append(row_of("weak (4096 clips/GPU)", n, line, dt, err))
         print(f"[scale_sweep] weak N={n}: {rows[-1].get('clips_per_s', rows[-1].get('error'))}", file=sys.stderr, flush=True)
