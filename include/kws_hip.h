@@ -160,6 +160,21 @@ int kws_forward_map_f32(kws_ctx* ctx, const float* d_feat, int B, int T, int F, 
 int kws_forward_map_debug_f32(kws_ctx* ctx, const float* d_feat, int B, int T, int F, float* d_logits, int32_t* d_label,
                               float* d_layers);
 
+/* ---- training ------------------------------------------------------------------------------ */
+
+/* Training: gradient of a scalar loss through DepthwiseSeparableConv.forward (models.py:160-183) for the model loaded by
+ * kws_load_dscnn, given d_dlogits = dloss/dlogits float32 [B, num_classes].  d_feat float32 [B, C, T, F] as for
+ * kws_forward_map_f32.  d_grad: float32 [n_floats] in the kws_load_dscnn blob layout (state_dict order), overwritten.
+ * Replaces loss.backward() of train.py:48 / kws/libs/training.py:296 for this model.
+ * The forward activations are recomputed by the composed fp32 path of kws_forward_map_f32 (nothing is saved by the
+ * forward); the arithmetic is fp32, the two 64 x 64 GEMMs of each pointwise layer on the f32-input matrix cores.  The
+ * gradients are deterministic: per-workgroup partials over a fixed clip ownership and a fixed-order reduction, so the same
+ * inputs and B give bit-identical d_grad.  The ReLU convention is torch's (no gradient where an output is exactly 0).
+ * Any B >= 1 (the workspace is bounded in chunks of at most 16384 clips), any map kws_forward_map_f32 accepts.
+ * input_channels must be 1 (KWS_EUNSUPPORTED otherwise); no model loaded: KWS_ESTATE.  Asynchronous on the context
+ * stream; the context keeps a workspace of about 1 MB per clip of the largest chunk (99 x 10). */
+int kws_dscnn_backward_f32(kws_ctx* ctx, const float* d_feat, int B, int T, int F, const float* d_dlogits, float* d_grad);
+
 /* One depthwise-separable block on an arbitrary map -- replaces DepthwiseSeparableConvBlock.forward
  * (kws/libs/models.py:108-119) used on its own: depthwise Conv2d(C_in, C_in, kernel_size, stride, padding, groups=C_in)
  * + bias, then pointwise Conv2d(C_in, C_out, 1, padding=padding) + bias, then ReLU.  d_x float32 [B,C_in,H,W]; d_dw_w

@@ -236,6 +236,7 @@ void kws_destroy(kws_ctx* c) {
     if (c->d_model) (void)hipFree(c->d_model);
     if (c->d_cnntrad) (void)hipFree(c->d_cnntrad);
     if (c->d_conv_ws) (void)hipFree(c->d_conv_ws);
+    if (c->d_train_ws) (void)hipFree(c->d_train_ws);
     if (c->d_feat_ws) (void)hipFree(c->d_feat_ws);
     stream_free_fwd(c);  // rings, hop counter, captured graph, smoothing and endpointer history
     ingest_free(c);      // staging rings, copy streams, pack threads

@@ -47,6 +47,9 @@ struct kws_ctx {
     int cnntrad_math = KWS_CT_F16_PAIR;
     float* d_conv_ws = nullptr;
     size_t conv_ws_floats = 0;
+    // training (kws_dscnn_backward_f32, kws_dscnn_bwd.hip): recomputed activations, gradients, per-workgroup partials
+    float* d_train_ws = nullptr;
+    size_t train_ws_floats = 0;
 
     // workspace (MFCC features between the two kernels of kws_infer_i16)
     float* d_feat_ws = nullptr;

@@ -55,6 +55,7 @@ SIGNATURES = {
     "kws_forward_map_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _i32p]),
     "kws_forward_map_debug_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, _f32p]),
     "kws_infer_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, _f32p, _i32p]),
+    "kws_dscnn_backward_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _f32p]),
     "kws_dsblock_forward_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int,
                                           C.c_int, C.c_int, _f32p]),
     "kws_infer_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, _f32p, _i32p]),
@@ -233,6 +234,13 @@ class Context:
             self._check(self._lib.kws_forward_map_f32(self._h, _ptr(feat), B, T, F, _ptr(logits), lab), ModelError)
         else:
             self._check(self._lib.kws_forward_map_debug_f32(self._h, _ptr(feat), B, T, F, _ptr(logits), lab, _ptr(layers)), ModelError)
+
+    def dscnn_backward_f32(self, feat, T, F, dlogits, grad):
+        """Gradient of a scalar loss with respect to the loaded DS-CNN's 20 state_dict tensors (``kws_dscnn_backward_f32``):
+        ``feat`` float32 [B, C, T, F] and ``dlogits`` = dloss/dlogits float32 [B, num_classes] on the device; ``grad`` float32
+        [n_floats] (the kws_load_dscnn blob layout) is overwritten.  Asynchronous on the context's stream."""
+        self._check(self._lib.kws_dscnn_backward_f32(self._h, _ptr(feat), int(feat.shape[0]), int(T), int(F), _ptr(dlogits), _ptr(grad)),
+                    ModelError)
 
     def load_cnn_trad(self, blob: np.ndarray, num_classes: int):
         blob = np.ascontiguousarray(blob, dtype=np.float32)

@@ -6,7 +6,10 @@ Drop-in for the reference's ``kws/libs/models.py``: ``KeywordSpottingModel`` (``
 names, shapes and initialisation, so reference checkpoints (bare ``state_dict`` or the trainer's
 ``{"model_state_dict": ...}``) load unchanged.  The modules only *hold* parameters; the arithmetic of
 ``forward`` is ``kws_forward_f32`` (include/kws_hip.h): LDS-resident activations, depthwise 3x3 on the
-VALU, pointwise 1x1 and conv1 on the matrix cores.  Inference only -- no autograd graph is built.
+VALU, pointwise 1x1 and conv1 on the matrix cores.  ``DepthwiseSeparableConv`` also trains: after ``model.train()`` (which
+the reference trainers call every epoch), with grad mode on and a parameter that requires grad, its forward is a
+``torch.autograd.Function`` whose backward is ``kws_dscnn_backward_f32``, so the trainer's ``loss.backward()`` /
+``optimizer.step()`` work unchanged.  The other models are inference only.
 """
 from __future__ import annotations
 
@@ -56,7 +59,8 @@ class DepthwiseSeparableConvBlock(nn.Module):
     """One block: kxk depthwise + 1x1 pointwise + ReLU (the pointwise keeps the reference's ``padding=padding`` --
     the relu(bias) ring, ``models.py:104-106``).  Inside ``DepthwiseSeparableConv`` the four blocks run fused in the
     DS-CNN kernel and this module only holds their parameters; called on its own, ``forward`` is the general-shape
-    operator ``kws_dsblock_forward_f32`` (any ``[B, C_in, H, W]``, kernel size, stride and padding)."""
+    operator ``kws_dsblock_forward_f32`` (any ``[B, C_in, H, W]``, kernel size, stride and padding).  Called on its own it is
+    inference only: the output has no ``grad_fn`` (the block's gradients exist only through ``DepthwiseSeparableConv``)."""
 
     def __init__(self, in_channels: int, out_channels: int, kernel_size: int = 3, stride: int = 1, padding: int = 1):
         super().__init__()
@@ -103,7 +107,17 @@ class DepthwiseSeparableConvBlock(nn.Module):
 
 
 class DepthwiseSeparableConv(KeywordSpottingModel):
-    """DS-CNN: conv1 (1->64, 10x10, s2, p2) + 4 depthwise-separable blocks + global pool + Linear."""
+    """DS-CNN: conv1 (1->64, 10x10, s2, p2) + 4 depthwise-separable blocks + global pool + Linear.
+
+    Trainable: after an explicit ``model.train()`` (the reference trainers call it at the start of every epoch,
+    ``kws/libs/training.py:275``, ``train.py:32``), when ``torch.is_grad_enabled()`` and some parameter requires grad,
+    ``forward`` runs through ``_DscnnTrainFunction`` -- the same forward kernels (logits and labels are bit-identical to a call under
+    ``torch.no_grad()``) with a backward that recomputes the activations and computes all 20 parameter gradients in HIP
+    (``kws_dscnn_backward_f32``, fp32, deterministic).  Each gradient lands on its parameter's device.  No gradient with
+    respect to the input features is provided (an input that requires grad raises ``ModelError`` in backward), and
+    ``input_channels > 1`` cannot be trained (backward raises ``ModelError``).  Otherwise -- a model never switched with
+    ``train()``, or switched back with ``eval()``, ``torch.no_grad()``, frozen parameters -- no autograd graph is built and
+    the logits are plain tensors, as for inference."""
 
     def __init__(self, num_classes: int = 12, input_channels: int = 1):
         super().__init__(num_classes)
@@ -119,6 +133,14 @@ class DepthwiseSeparableConv(KeywordSpottingModel):
         self._initialize_weights()
         self._ctx = None
         self._uploaded = None  # fingerprint of the parameters currently on the device
+        self._autograd = False  # set by an explicit train(), cleared by eval() / train(False)
+
+    def train(self, mode: bool = True):
+        """``nn.Module.train``; an explicit ``train()`` also switches ``forward`` to the autograd path (see the class
+        docstring), ``eval()`` / ``train(False)`` switches it back."""
+        super().train(mode)
+        self._autograd = bool(mode)
+        return self
 
     def _initialize_weights(self):
         # same scheme as the reference (:149-158)
@@ -133,8 +155,12 @@ class DepthwiseSeparableConv(KeywordSpottingModel):
 
     # ------------------------------------------------------------------ device plumbing
     def packed_weights(self) -> np.ndarray:
-        """The 20 ``state_dict`` tensors, in order, as one float32 vector (``kws_load_dscnn`` layout)."""
-        return np.concatenate([v.detach().to("cpu", torch.float32).reshape(-1).numpy() for v in self.state_dict().values()])
+        """The 20 ``state_dict`` tensors, in order, as one float32 vector (``kws_load_dscnn`` layout): concatenated on the
+        parameters' device and copied to the host once (it runs again after every optimizer step)."""
+        vals = [v.detach() for v in self.state_dict().values()]
+        dev = vals[0].device
+        flat = torch.cat([v.to(dev, torch.float32).reshape(-1) for v in vals])
+        return flat.cpu().numpy()
 
     def sync_weights(self) -> None:
         """Force a re-upload of the parameters at the next forward.  The device copy is refreshed automatically when
@@ -163,10 +189,20 @@ class DepthwiseSeparableConv(KeywordSpottingModel):
     def forward(self, x: torch.Tensor, return_labels: bool = False):
         """``float32[B,C,T,F]`` on the GPU -> logits ``float32[B,num_classes]`` (and argmax labels).  Any ``T x F`` the
         reference's forward accepts (``models.py:160-183``: the pooling is adaptive): 99 x 10 runs the fused LDS-resident
-        kernel, any other map the composed path (``kws_forward_map_f32``)."""
+        kernel, any other map the composed path (``kws_forward_map_f32``).  After ``train()``, under grad mode with
+        trainable parameters, the logits carry a ``grad_fn`` (see the class docstring)."""
         self._check_input(x, "DepthwiseSeparableConv.forward")
         if x.dim() != 4 or x.shape[1] != self.input_channels:
             raise ModelError(f"expected input [B,{self.input_channels},T,F], got {tuple(x.shape)}")
+        params = tuple(self.parameters())
+        if self._autograd and torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            logits, labels = _DscnnTrainFunction.apply(self, x, *params)
+        else:
+            logits, labels = self._forward_native(x)
+        return (logits, labels) if return_labels else logits
+
+    def _forward_native(self, x: torch.Tensor):
+        """The forward kernels on ``x`` (checked by the caller) -> (logits, labels); no autograd graph."""
         ctx = self._context(x.device.index or 0)
         x = x.detach().to(torch.float32).contiguous()
         logits = torch.empty((x.shape[0], self.num_classes), dtype=torch.float32, device=x.device)
@@ -175,7 +211,7 @@ class DepthwiseSeparableConv(KeywordSpottingModel):
             ctx.forward_f32(x, logits, labels)
         else:
             ctx.forward_map_f32(x, logits, labels)
-        return (logits, labels) if return_labels else logits
+        return logits, labels
 
     def infer_pcm16(self, wav: torch.Tensor):
         """Fused path: ``int16[B,16000]`` PCM on the GPU -> (logits, labels); MFCC + DS-CNN back to back
@@ -193,13 +229,52 @@ class DepthwiseSeparableConv(KeywordSpottingModel):
         return logits, labels
 
 
+class _DscnnTrainFunction(torch.autograd.Function):
+    """``DepthwiseSeparableConv.forward`` with a HIP backward.  Forward: exactly the inference call (the fused kernel at
+    99 x 10, the composed path otherwise); the input and the parameters are saved with ``save_for_backward``, so torch's
+    version counter rejects a parameter modified in place between forward and backward.  Backward:
+    ``kws_dscnn_backward_f32`` on the device weights (re-uploaded only if they changed), the flat gradient split into
+    views shaped like the parameters and moved to each parameter's device."""
+
+    @staticmethod
+    def forward(fctx, model, x, *params):
+        logits, labels = model._forward_native(x)
+        fctx.model = model
+        fctx.save_for_backward(x, *params)
+        fctx.mark_non_differentiable(labels)
+        return logits, labels
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, dlogits, _dlabels):
+        x, *params = fctx.saved_tensors
+        if fctx.needs_input_grad[1]:
+            raise ModelError("DepthwiseSeparableConv: the gradient with respect to the input features is not provided "
+                             "(kws_dscnn_backward_f32 computes parameter gradients only); detach the input")
+        model = fctx.model
+        ctx = model._context(x.device.index or 0)
+        x = x.detach().to(torch.float32).contiguous()
+        dl = dlogits.detach().to(x.device, torch.float32).contiguous()
+        grad = torch.empty(sum(p.numel() for p in params), dtype=torch.float32, device=x.device)
+        ctx.dscnn_backward_f32(x, x.shape[2], x.shape[3], dl, grad)
+        on_dev = {}
+        out, off = [], 0
+        for p in params:
+            if p.device not in on_dev:
+                on_dev[p.device] = grad.to(p.device)
+            out.append(on_dev[p.device][off:off + p.numel()].view(p.shape).to(p.dtype))
+            off += p.numel()
+        return (None, None, *out)
+
+
 class DepthwiseSeparableConvBN(KeywordSpottingModel):
     """Build-defined model-zoo member (the reference has no BatchNorm): the same DS-CNN
     with an inference-mode BatchNorm2d after conv1, after every depthwise and after every pointwise convolution
     (conv -> BN -> ReLU where the plain model has conv -> ReLU).  ``fold()`` folds every BatchNorm into the
     convolution before it -- w' = w * g / sqrt(var + eps), b' = (b - mean) * g / sqrt(var + eps) + beta -- which
     yields an ordinary ``DepthwiseSeparableConv`` whose forward is the fused kernel.  The relu(bias) ring of the
-    padded 1x1 convolutions stays exact: a BatchNorm acts per channel, ring included.  Inference only."""
+    padded 1x1 convolutions stays exact: a BatchNorm acts per channel, ring included.  Inference only: the fold is
+    detached, so no gradient reaches this model's parameters (training covers the plain ``DepthwiseSeparableConv``)."""
 
     def __init__(self, num_classes: int = 12, eps: float = 1e-5):
         super().__init__(num_classes)
@@ -258,7 +333,8 @@ class CnnTradFpool3(KeywordSpottingModel):
     ``[1,99,10]`` MFCC map with SAME padding -- conv 64x(20x8)+ReLU, max-pool 1x3 over frequency, conv 64x(10x4)+ReLU,
     flatten, Linear 32, Linear 128+ReLU, Linear C.  The modules hold parameters; ``forward`` is
     ``kws_forward_cnn_trad_f32`` (both convolutions as implicit GEMMs on the bf16 matrix pipe with the exact
-    three-way split, the dense tail batched on the VALU).  Inference only."""
+    three-way split, the dense tail batched on the VALU).  Inference only: no autograd graph is built (there is no
+    backward for this model; training covers ``DepthwiseSeparableConv``)."""
 
     def __init__(self, num_classes: int = 12):
         super().__init__(num_classes)
