@@ -157,7 +157,11 @@ class DepthwiseSeparableConv(KeywordSpottingModel):
     def packed_weights(self) -> np.ndarray:
         """The 20 ``state_dict`` tensors, in order, as one float32 vector (``kws_load_dscnn`` layout): concatenated on the
         parameters' device and copied to the host once (it runs again after every optimizer step)."""
-        vals = [v.detach() for v in self.state_dict().values()]
+        return self._pack(self.state_dict().values())
+
+    @staticmethod
+    def _pack(tensors) -> np.ndarray:
+        vals = [v.detach() for v in tensors]
         dev = vals[0].device
         flat = torch.cat([v.to(dev, torch.float32).reshape(-1) for v in vals])
         return flat.cpu().numpy()
@@ -169,15 +173,18 @@ class DepthwiseSeparableConv(KeywordSpottingModel):
         ``p.data.clamp_()``) do not, and need this call."""
         self._uploaded = None
 
-    def _context(self, device_index: int):
+    def _context(self, device_index: int, params=None):
+        """The model's context on ``device_index`` holding ``params`` (default: the current parameters, in ``parameters()``
+        order); uploaded only when they differ from the tensors (and versions) uploaded last."""
         from kws import _native
 
         if self._ctx is None or self._ctx.device != device_index:
             self._ctx = _native.Context(device_index, ModelError)
             self._uploaded = None
-        fp = tuple((p.data_ptr(), p._version) for p in self.parameters())
+        params = tuple(self.parameters()) if params is None else tuple(params)
+        fp = tuple((p.data_ptr(), p._version) for p in params)
         if fp != self._uploaded:
-            self._ctx.load_dscnn(self.packed_weights(), self.num_classes, self.input_channels)
+            self._ctx.load_dscnn(self._pack(params), self.num_classes, self.input_channels)
             self._uploaded = fp
         self._ctx.use_torch_stream()
         return self._ctx
@@ -233,7 +240,8 @@ class _DscnnTrainFunction(torch.autograd.Function):
     """``DepthwiseSeparableConv.forward`` with a HIP backward.  Forward: exactly the inference call (the fused kernel at
     99 x 10, the composed path otherwise); the input and the parameters are saved with ``save_for_backward``, so torch's
     version counter rejects a parameter modified in place between forward and backward.  Backward:
-    ``kws_dscnn_backward_f32`` on the device weights (re-uploaded only if they changed), the flat gradient split into
+    ``kws_dscnn_backward_f32`` at the saved parameters -- the weights the forward saw, also when a module attribute was
+    replaced by a new ``nn.Parameter`` in between (uploaded only if they are not the device copy), the flat gradient split into
     views shaped like the parameters and moved to each parameter's device."""
 
     @staticmethod
@@ -252,7 +260,9 @@ class _DscnnTrainFunction(torch.autograd.Function):
             raise ModelError("DepthwiseSeparableConv: the gradient with respect to the input features is not provided "
                              "(kws_dscnn_backward_f32 computes parameter gradients only); detach the input")
         model = fctx.model
-        ctx = model._context(x.device.index or 0)
+        # the weights the forward saw: the saved parameters, even if the module's attribute was replaced since (a new
+        # nn.Parameter bumps no version of the saved one); equal to the current ones in a normal step, so no re-upload
+        ctx = model._context(x.device.index or 0, params)
         x = x.detach().to(torch.float32).contiguous()
         dl = dlogits.detach().to(x.device, torch.float32).contiguous()
         grad = torch.empty(sum(p.numel() for p in params), dtype=torch.float32, device=x.device)

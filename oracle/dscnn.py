@@ -57,16 +57,33 @@ def random_state(seed: int, std: float = 0.1, num_classes: int = 12) -> "Ordered
     return out
 
 
-def forward(state: dict, x: torch.Tensor, return_layers: bool = False):
-    """x [B,1,T,F] -> logits [B,num_classes]; dtype follows ``x`` (params are cast)."""
+MASKED = ["conv1"] + [f"dsconv{i}" for i in range(1, N_BLOCKS + 1)]  # the five ReLU outputs (block outputs: ring included)
+
+
+def forward(state: dict, x: torch.Tensor, return_layers: bool = False, masks: dict = None):
+    """x [B,1,T,F] -> logits [B,num_classes]; dtype follows ``x`` (params are cast).
+
+    ``masks`` pins the ReLU decisions: ``{name: bool tensor shaped like layers[name]}`` for every name of ``MASKED``; each
+    ``relu(z)`` becomes ``where(mask, z, 0)``, so its gradient is ``mask * upstream``.  With masks taken from another
+    computation (the GPU's own stage outputs, ``stage > 0``), a comparison measures arithmetic error only: a pre-activation
+    within rounding of zero cannot switch a unit on one side and off on the other."""
     p = {k: v.to(dtype=x.dtype) for k, v in state.items()}
     layers = OrderedDict()
-    h = F.relu(F.conv2d(x, p["conv1.weight"], p["conv1.bias"], stride=2, padding=2))
+
+    def relu(z, name):
+        if masks is None:
+            return F.relu(z)
+        m = masks[name]
+        if m.shape != z.shape:
+            raise ValueError(f"mask {name}: shape {tuple(m.shape)}, pre-activation {tuple(z.shape)}")
+        return torch.where(m.to(torch.bool), z, z.new_zeros(()))
+
+    h = relu(F.conv2d(x, p["conv1.weight"], p["conv1.bias"], stride=2, padding=2), "conv1")
     layers["conv1"] = h
     for i in range(1, N_BLOCKS + 1):
         h = F.conv2d(h, p[f"dsconv{i}.depthwise.weight"], p[f"dsconv{i}.depthwise.bias"], stride=1, padding=1, groups=CHANNELS)
         layers[f"dsconv{i}.depthwise"] = h
-        h = F.relu(F.conv2d(h, p[f"dsconv{i}.pointwise.weight"], p[f"dsconv{i}.pointwise.bias"], stride=1, padding=1))
+        h = relu(F.conv2d(h, p[f"dsconv{i}.pointwise.weight"], p[f"dsconv{i}.pointwise.bias"], stride=1, padding=1), f"dsconv{i}")
         layers[f"dsconv{i}"] = h
     h = F.adaptive_avg_pool2d(h, (1, 1)).reshape(h.shape[0], -1)
     layers["pool"] = h
@@ -74,6 +91,20 @@ def forward(state: dict, x: torch.Tensor, return_layers: bool = False):
     if return_layers:
         return logits, layers
     return logits
+
+
+def relu_masks(layers: dict) -> dict:
+    """The ReLU decisions of a forward: ``{name: layers[name] > 0}`` for every name of ``MASKED``.  ``layers`` holds the five
+    ReLU outputs (as ``forward(..., return_layers=True)`` returns them, or the GPU's stage outputs)."""
+    return {k: torch.as_tensor(layers[k]) > 0 for k in MASKED}
+
+
+def grads(state: dict, x: torch.Tensor, dlogits: torch.Tensor, dtype=torch.float64, masks: dict = None) -> dict:
+    """Gradient of ``sum(logits * dlogits)`` with respect to every ``state`` tensor, computed by torch autograd in ``dtype``
+    (float64: the answer; float32: the yardstick of torch-f32's own error), ReLU decisions pinned by ``masks`` if given."""
+    st = {k: v.detach().to(dtype).requires_grad_(True) for k, v in state.items()}
+    forward(st, x.to(dtype), masks=masks).backward(dlogits.to(dtype))
+    return {k: st[k].grad.detach().to(torch.float64).numpy() for k in STATE_KEYS}
 
 
 def block_forward(params: dict, x: torch.Tensor, kernel_size: int = 3, stride: int = 1, padding: int = 1) -> torch.Tensor:

@@ -68,3 +68,34 @@ def test_training_forward_without_gpu_still_fails_loudly():
     assert torch.is_grad_enabled() and all(p.requires_grad for p in m.parameters())
     with pytest.raises(ModelError, match="no CPU fallback"):
         m(torch.zeros(2, 1, 99, 10))
+
+
+@pytest.mark.parametrize("T,F,C", [(99, 10, 12), (20, 8, 35), (7, 7, 1)])
+def test_pinned_relu_oracle_equals_the_unpinned_one(T, F, C):
+    """The float64 oracle with its ReLU decisions pinned to those of its own forward gives the same logits, stage outputs
+    and gradients, bit for bit; a mask taken from elsewhere is honoured (a unit switched off passes nothing)."""
+    from oracle import dscnn as o_dscnn
+
+    torch.set_num_threads(min(16, os.cpu_count() or 1))
+    gen = torch.Generator().manual_seed(T * F + C)
+    state = o_dscnn.random_state(9, num_classes=C)
+    x = torch.randn(5, 1, T, F, generator=gen, dtype=torch.float64)
+    x[1] = 0.0  # all-zero clip: conv1 is its bias everywhere
+    dl = torch.randn(5, C, generator=gen, dtype=torch.float64)
+    logits, layers = o_dscnn.forward(state, x, return_layers=True)
+    masks = o_dscnn.relu_masks(layers)
+    assert all(0 < int(m.sum()) < m.numel() for m in masks.values())
+    pl, players = o_dscnn.forward(state, x, return_layers=True, masks=masks)
+    assert torch.equal(pl, logits)
+    for k in layers:
+        assert torch.equal(players[k], layers[k]), k
+    g, gp = o_dscnn.grads(state, x, dl), o_dscnn.grads(state, x, dl, masks=masks)
+    for k in o_dscnn.STATE_KEYS:
+        assert np.array_equal(g[k], gp[k]), k
+    # the masks decide: switch every unit of block 2 off -> blocks 3, 4 see only their biases and nothing flows below
+    off = dict(masks, dsconv2=torch.zeros_like(masks["dsconv2"]))
+    gd = o_dscnn.grads(state, x, dl, masks=off)
+    for k in ("conv1.weight", "conv1.bias", "dsconv1.depthwise.weight", "dsconv2.pointwise.weight", "dsconv2.pointwise.bias"):
+        assert not gd[k].any(), k
+    with pytest.raises(ValueError, match="mask conv1"):
+        o_dscnn.forward(state, x, masks=dict(masks, conv1=masks["conv1"][:, :, 1:]))
