@@ -175,6 +175,27 @@ int kws_forward_map_debug_f32(kws_ctx* ctx, const float* d_feat, int B, int T, i
  * stream; the context keeps a workspace of about 1 MB per clip of the largest chunk (99 x 10). */
 int kws_dscnn_backward_f32(kws_ctx* ctx, const float* d_feat, int B, int T, int F, const float* d_dlogits, float* d_grad);
 
+/* Training: gradient of a scalar loss through cnn-trad-fpool3's forward (kws_forward_cnn_trad_f32) for the model loaded by
+ * kws_load_cnn_trad or kws_load_cnn_trad_device, given d_dlogits = dloss/dlogits float32 [B, num_classes] and the features
+ * d_feat float32 [B, 1, 99, 10].  d_grad: float32 [786720 + 129 num_classes] in the kws_load_cnn_trad blob layout (the ten
+ * state_dict tensors in order), overwritten.  Replaces loss.backward() of train.py:48 / kws/libs/training.py:296 for this model.
+ * The activations are recomputed by the call's own f32 forward (conv2 and lin on the f32-input matrix cores), so the gradients do
+ * not depend on kws_set_cnn_trad_math; the pool routes each gradient to the first maximum of its window (torch's max_pool2d), and
+ * the ReLU convention is torch's (no gradient where an output is exactly 0).  Deterministic: per-workgroup partials over a fixed
+ * clip ownership and fixed-order reductions, no float atomics, so the same inputs and B give bit-identical d_grad.  Any B >= 1:
+ * batches are cut into chunks of at most 8192 clips whose results add onto d_grad in chunk order; the context keeps a workspace of
+ * about 324 KB per clip of the largest chunk.  No model loaded: KWS_ESTATE; a NULL pointer or B <= 0: KWS_EINVAL.  Asynchronous on
+ * the context stream.  The gradient with respect to the features is not computed. */
+int kws_cnn_trad_backward_f32(kws_ctx* ctx, const float* d_feat, int B, const float* d_dlogits, float* d_grad);
+
+/* Parity aid of kws_cnn_trad_backward_f32: runs exactly its recompute launches on d_feat float32 [B, 1, 99, 10] and writes their
+ * stages (device pointers): d_conv1 float32 [B, 64, 99, 10] (conv1 after ReLU), d_winner int32 [B, 64, 99, 3] (the pool's
+ * winner 0..2 within each window of three bins), d_conv2 float32 [B, 64, 99, 3] (conv2 after ReLU), d_hidden float32 [B, 160]
+ * (h = lin(.) [32], then d = relu(dnn(h)) [128]).  Tests pin the float64 oracle's ReLU and max-pool decisions to these (the role
+ * kws_forward_map_debug_f32 plays for the DS-CNN).  Errors as kws_cnn_trad_backward_f32. */
+int kws_cnn_trad_train_debug_f32(kws_ctx* ctx, const float* d_feat, int B, float* d_conv1, int32_t* d_winner, float* d_conv2,
+                                 float* d_hidden);
+
 /* One depthwise-separable block on an arbitrary map -- replaces DepthwiseSeparableConvBlock.forward
  * (kws/libs/models.py:108-119) used on its own: depthwise Conv2d(C_in, C_in, kernel_size, stride, padding, groups=C_in)
  * + bias, then pointwise Conv2d(C_in, C_out, 1, padding=padding) + bias, then ReLU.  d_x float32 [B,C_in,H,W]; d_dw_w
@@ -314,6 +335,12 @@ int kws_stream_vad_f32(kws_ctx* ctx, float log_energy_threshold, int on_window, 
  * [64,64,10,4], conv2.bias [64], lin.weight [32,19008], lin.bias [32], dnn.weight [128,32], dnn.bias [128],
  * fc.weight [C,128], fc.bias [C] (host pointer, copied). */
 int kws_load_cnn_trad(kws_ctx* ctx, const float* blob, size_t n_floats, int num_classes);
+/* kws_load_cnn_trad from a DEVICE-resident blob (same layout, same argument checks) -- the weight refresh of a training step
+ * (the reference re-reads its parameters after every optimizer.step(), train.py:49): the pre-split images are packed by a kernel
+ * and the weight statistics computed on the device in the host's order, and the handful of floats the model carries by value is
+ * read back (the call waits for the context stream).  The resulting forward is bit-identical to a kws_load_cnn_trad of the same
+ * values.  The image is rebuilt in place when the class count is unchanged. */
+int kws_load_cnn_trad_device(kws_ctx* ctx, const float* d_blob, size_t n_floats, int num_classes);
 /* float32 [B,1,99,10] features -> logits float32 [B,C] and labels int32 [B] (d_label may be NULL).  The
  * convolution output (76 KB per clip) goes through a context workspace that grows on demand. */
 int kws_forward_cnn_trad_f32(kws_ctx* ctx, const float* d_feat, int B, float* d_logits, int32_t* d_label);

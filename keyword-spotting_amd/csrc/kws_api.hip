@@ -235,6 +235,7 @@ void kws_destroy(kws_ctx* c) {
     if (c->d_refine) (void)hipFree(c->d_refine);
     if (c->d_model) (void)hipFree(c->d_model);
     if (c->d_cnntrad) (void)hipFree(c->d_cnntrad);
+    if (c->d_ct_stats) (void)hipFree(c->d_ct_stats);
     if (c->d_conv_ws) (void)hipFree(c->d_conv_ws);
     if (c->d_train_ws) (void)hipFree(c->d_train_ws);
     if (c->d_feat_ws) (void)hipFree(c->d_feat_ws);
@@ -1157,29 +1158,85 @@ static float max_row_abs_sum(const float* w, int rows, size_t row_len) {
     return (float)(best * 1.0000002);  // rounded up
 }
 
+// The device image of a cnn-trad-fpool3 blob (units: 32-bit words): c1_split | c2_split | c1_b | c2_b | lin_split | lin_b | dnn_w |
+// dnn_b | fc_w | fc_b, the f16-pair images (two pieces, 16-byte aligned), then the blob itself as float32 (16-byte aligned; the
+// weights of kws_cnn_trad_backward_f32).
+struct CtLayout {
+    size_t n_c1, n_c2, n_lin, n_dnn, n_fc, n_floats;
+    size_t o_c1s, o_c2s, o_c1b, o_c2b, o_lin, o_linb, o_dnn, o_dnnb, o_fc, o_fcb, o_c1h, o_c2h, o_linh, o_raw, total;
+    explicit CtLayout(int num_classes) {
+        const size_t FLAT = 64 * 297;
+        n_c1 = 64 * 160, n_c2 = 64 * 64 * 40, n_lin = 32 * FLAT, n_dnn = 128 * 32, n_fc = (size_t)num_classes * 128;
+        n_floats = n_c1 + 64 + n_c2 + 64 + n_lin + 32 + n_dnn + 128 + n_fc + num_classes;
+        o_c1s = 0, o_c2s = o_c1s + 10 * 2 * 3 * 64 * 4, o_c1b = o_c2s + (size_t)40 * 4 * 2 * 3 * 64 * 4, o_c2b = o_c1b + 64, o_lin = o_c2b + 64,
+        o_linb = o_lin + (size_t)(FLAT / 16) * 3 * 64 * 4, o_dnn = o_linb + 32, o_dnnb = o_dnn + n_dnn, o_fc = o_dnnb + 128, o_fcb = o_fc + n_fc,
+        o_c1h = (o_fcb + num_classes + 3) / 4 * 4, o_c2h = o_c1h + 10 * 2 * 2 * 64 * 4, o_linh = o_c2h + (size_t)40 * 4 * 2 * 2 * 64 * 4,
+        o_raw = o_linh + (size_t)(FLAT / 16) * 2 * 64 * 4, total = o_raw + (n_floats + 3) / 4 * 4;
+    }
+};
+
+// the power of two s with m * s < 2^15 for m = max|w| of a layer (pow2_weight_scale)
+static float pow2_scale_of_max(float m) {
+    if (!(m > 0.f) || !std::isfinite(m)) return 1.f;
+    int e;
+    (void)std::frexp(m, &e);  // m = f * 2^e, f in [0.5, 1): m < 2^e
+    return std::ldexp(1.f, std::max(-100, std::min(100, 15 - e)));
+}
+
+// Point the context at a complete device image d (layout L) and set the values CnnTradWeights carries by value.
+static void install_cnntrad(kws_ctx* c, uint32_t* d, const CtLayout& L, int num_classes, float sw1, float sw2, float swl, float w1_abs,
+                            float w2_abs, float b1_max, float b2_max) {
+    if (c->d_cnntrad && c->d_cnntrad != d) (void)hipFree(c->d_cnntrad);
+    c->d_cnntrad = d;
+    c->ct_image_words = L.total;
+    const float* df = reinterpret_cast<const float*>(d);
+    c->tw.c1_split = d + L.o_c1s;
+    c->tw.c2_split = d + L.o_c2s;
+    c->tw.c1_b = df + L.o_c1b;
+    c->tw.c2_b = df + L.o_c2b;
+    c->tw.lin_split = d + L.o_lin;
+    c->tw.lin_b = df + L.o_linb;
+    c->tw.dnn_w = df + L.o_dnn;
+    c->tw.dnn_b = df + L.o_dnnb;
+    c->tw.fc_w = df + L.o_fc;
+    c->tw.fc_b = df + L.o_fcb;
+    c->tw.num_classes = num_classes;
+    c->tw.c1_h2 = d + L.o_c1h;
+    c->tw.c2_h2 = d + L.o_c2h;
+    c->tw.lin_h2 = d + L.o_linh;
+    c->tw.inv_sw1 = 1.f / sw1;
+    c->tw.inv_sw2 = 1.f / sw2;
+    c->tw.inv_swl = 1.f / swl;
+    c->tw.w1_abs = w1_abs;
+    c->tw.w2_abs = w2_abs;
+    c->tw.b1_max = b1_max;
+    c->tw.b2_max = b2_max;
+    c->ct_raw = df + L.o_raw;
+    c->cnntrad_ready = true;
+}
+
+static int check_cnntrad_blob(kws_ctx* c, const char* fn, size_t n_floats, int num_classes) {
+    if (num_classes < 1 || num_classes > MAX_CLASSES) return fail(c, KWS_EUNSUPPORTED, std::string(fn) + ": num_classes must be in [1, 64]");
+    const size_t expect = CtLayout(num_classes).n_floats;
+    if (n_floats != expect) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "%s: expected %zu floats for %d classes, got %zu", fn, expect, num_classes, n_floats);
+        return fail(c, KWS_EINVAL, msg);
+    }
+    return KWS_OK;
+}
+
 int kws_load_cnn_trad(kws_ctx* c, const float* blob, size_t n_floats, int num_classes) {
     KWS_GUARD_BEGIN
     if (!c) return KWS_EINVAL;
     if (!blob) return fail(c, KWS_EINVAL, "kws_load_cnn_trad: blob is NULL");
-    if (num_classes < 1 || num_classes > MAX_CLASSES) return fail(c, KWS_EUNSUPPORTED, "kws_load_cnn_trad: num_classes must be in [1, 64]");
-    const size_t FLAT = 64 * 297;
-    const size_t n_c1 = 64 * 160, n_c2 = 64 * 64 * 40, n_lin = 32 * FLAT, n_dnn = 128 * 32, n_fc = (size_t)num_classes * 128;
-    const size_t expect = n_c1 + 64 + n_c2 + 64 + n_lin + 32 + n_dnn + 128 + n_fc + num_classes;
-    if (n_floats != expect) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "kws_load_cnn_trad: expected %zu floats for %d classes, got %zu", expect, num_classes, n_floats);
-        return fail(c, KWS_EINVAL, msg);
-    }
+    int rc = check_cnntrad_blob(c, "kws_load_cnn_trad", n_floats, num_classes);
+    if (rc) return rc;
+    const CtLayout L(num_classes);
+    const size_t FLAT = 64 * 297, n_c1 = L.n_c1, n_c2 = L.n_c2, n_lin = L.n_lin, n_dnn = L.n_dnn, n_fc = L.n_fc;
     const float *w1 = blob, *b1 = w1 + n_c1, *w2 = b1 + 64, *b2 = w2 + n_c2, *wl = b2 + 64, *bl = wl + n_lin, *wd = bl + 32,
                 *bd = wd + n_dnn, *wf = bd + 128, *bf = wf + n_fc;
-    // device image (units: 32-bit words): c1_split | c2_split | c1_b | c2_b | lin_split | lin_b | dnn_w | dnn_b | fc_w | fc_b
-    const size_t o_c1s = 0, o_c2s = o_c1s + 10 * 2 * 3 * 64 * 4, o_c1b = o_c2s + (size_t)40 * 4 * 2 * 3 * 64 * 4, o_c2b = o_c1b + 64,
-                 o_lin = o_c2b + 64, o_linb = o_lin + (size_t)(FLAT / 16) * 3 * 64 * 4, o_dnn = o_linb + 32, o_dnnb = o_dnn + n_dnn, o_fc = o_dnnb + 128,
-                 o_fcb = o_fc + n_fc,
-                 // f16-pair images (two pieces), 16-byte aligned
-                 o_c1h = (o_fcb + num_classes + 3) / 4 * 4, o_c2h = o_c1h + 10 * 2 * 2 * 64 * 4, o_linh = o_c2h + (size_t)40 * 4 * 2 * 2 * 64 * 4,
-                 total = o_linh + (size_t)(FLAT / 16) * 2 * 64 * 4;
-    std::vector<uint32_t> h(total, 0u);
+    std::vector<uint32_t> h(L.total, 0u);
     const float sw1 = pow2_weight_scale(w1, n_c1), sw2 = pow2_weight_scale(w2, n_c2), swl = pow2_weight_scale(wl, n_lin);
     auto put = [&](size_t off, const float* src, size_t n) { memcpy(&h[off], src, n * sizeof(float)); };
     // conv1: lane l of (kb, ct): cout = 32ct + (l&31), kernel row 2kb + (l>>5), kernel columns j = 0..7
@@ -1189,9 +1246,9 @@ int kws_load_cnn_trad(kws_ctx* c, const float* blob, size_t n_floats, int num_cl
                 float v[8];
                 const int co = 32 * ct + (l & 31), kh = 2 * kb + (l >> 5);
                 for (int j = 0; j < 8; ++j) v[j] = w1[(co * 20 + kh) * 8 + j];
-                uint32_t* base = &h[o_c1s + ((size_t)(kb * 2 + ct) * 3 * 64 + l) * 4];
+                uint32_t* base = &h[L.o_c1s + ((size_t)(kb * 2 + ct) * 3 * 64 + l) * 4];
                 pack_split8(v, base, base + 64 * 4, base + 2 * 64 * 4);
-                uint32_t* b2 = &h[o_c1h + ((size_t)(kb * 2 + ct) * 2 * 64 + l) * 4];
+                uint32_t* b2 = &h[L.o_c1h + ((size_t)(kb * 2 + ct) * 2 * 64 + l) * 4];
                 pack_pair8(v, sw1, b2, b2 + 64 * 4);
             }
     // conv2: lane l of (kk = kh*4 + kw, cb, ct): cout = 32ct + (l&31), input channels 16cb + 8(l>>5) + j
@@ -1202,70 +1259,200 @@ int kws_load_cnn_trad(kws_ctx* c, const float* blob, size_t n_floats, int num_cl
                     float v[8];
                     const int co = 32 * ct + (l & 31), kh = kk >> 2, kw = kk & 3;
                     for (int j = 0; j < 8; ++j) v[j] = w2[((co * 64 + 16 * cb + 8 * (l >> 5) + j) * 10 + kh) * 4 + kw];
-                    uint32_t* base = &h[o_c2s + ((((size_t)kk * 4 + cb) * 2 + ct) * 3 * 64 + l) * 4];
+                    uint32_t* base = &h[L.o_c2s + ((((size_t)kk * 4 + cb) * 2 + ct) * 3 * 64 + l) * 4];
                     pack_split8(v, base, base + 64 * 4, base + 2 * 64 * 4);
-                    uint32_t* b2 = &h[o_c2h + ((((size_t)kk * 4 + cb) * 2 + ct) * 2 * 64 + l) * 4];
+                    uint32_t* b2 = &h[L.o_c2h + ((((size_t)kk * 4 + cb) * 2 + ct) * 2 * 64 + l) * 4];
                     pack_pair8(v, sw2, b2, b2 + 64 * 4);
                 }
-    put(o_c1b, b1, 64);
-    put(o_c2b, b2, 64);
+    put(L.o_c1b, b1, 64);
+    put(L.o_c2b, b2, 64);
     // first dense layer as MFMA B operands (32x32x16): lane l of k-block kb: output l&31, inputs 16kb + 8(l>>5) + j
     for (size_t kb = 0; kb < FLAT / 16; ++kb)
         for (int l = 0; l < 64; ++l) {
             float v[8];
             for (int j = 0; j < 8; ++j) v[j] = wl[(size_t)(l & 31) * FLAT + 16 * kb + 8 * (l >> 5) + j];
-            uint32_t* base = &h[o_lin + (kb * 3 * 64 + l) * 4];
+            uint32_t* base = &h[L.o_lin + (kb * 3 * 64 + l) * 4];
             pack_split8(v, base, base + 64 * 4, base + 2 * 64 * 4);
-            uint32_t* b2 = &h[o_linh + (kb * 2 * 64 + l) * 4];
+            uint32_t* b2 = &h[L.o_linh + (kb * 2 * 64 + l) * 4];
             pack_pair8(v, swl, b2, b2 + 64 * 4);
         }
-    put(o_linb, bl, 32);
-    put(o_dnn, wd, n_dnn);
-    put(o_dnnb, bd, 128);
-    put(o_fc, wf, n_fc);
-    put(o_fcb, bf, num_classes);
+    put(L.o_linb, bl, 32);
+    put(L.o_dnn, wd, n_dnn);
+    put(L.o_dnnb, bd, 128);
+    put(L.o_fc, wf, n_fc);
+    put(L.o_fcb, bf, num_classes);
+    put(L.o_raw, blob, n_floats);
 
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     uint32_t* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), total * sizeof(uint32_t)) != hipSuccess)
+    if (hipMalloc(reinterpret_cast<void**>(&d), L.total * sizeof(uint32_t)) != hipSuccess)
         return fail(c, KWS_ENOMEM, "kws_load_cnn_trad: device allocation failed");
-    hipError_t e = hipMemcpy(d, h.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice);
+    hipError_t e = hipMemcpy(d, h.data(), L.total * sizeof(uint32_t), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         (void)hipFree(d);
         return fail_hip(c, e, "kws_load_cnn_trad: hipMemcpy");
     }
-    if (c->d_cnntrad) (void)hipFree(c->d_cnntrad);
-    c->d_cnntrad = d;
-    const float* df = reinterpret_cast<const float*>(d);
-    c->tw.c1_split = d + o_c1s;
-    c->tw.c2_split = d + o_c2s;
-    c->tw.c1_b = df + o_c1b;
-    c->tw.c2_b = df + o_c2b;
-    c->tw.lin_split = d + o_lin;
-    c->tw.lin_b = df + o_linb;
-    c->tw.dnn_w = df + o_dnn;
-    c->tw.dnn_b = df + o_dnnb;
-    c->tw.fc_w = df + o_fc;
-    c->tw.fc_b = df + o_fcb;
-    c->tw.num_classes = num_classes;
-    c->tw.c1_h2 = d + o_c1h;
-    c->tw.c2_h2 = d + o_c2h;
-    c->tw.lin_h2 = d + o_linh;
-    c->tw.inv_sw1 = 1.f / sw1;
-    c->tw.inv_sw2 = 1.f / sw2;
-    c->tw.inv_swl = 1.f / swl;
-    c->tw.w1_abs = max_row_abs_sum(w1, 64, 160);
-    c->tw.w2_abs = max_row_abs_sum(w2, 64, 2560);
-    c->tw.b1_max = 0.f;
-    c->tw.b2_max = 0.f;
+    float b1_max = 0.f, b2_max = 0.f;
     for (int i = 0; i < 64; ++i) {
-        c->tw.b1_max = std::max(c->tw.b1_max, std::fabs(b1[i]));
-        c->tw.b2_max = std::max(c->tw.b2_max, std::fabs(b2[i]));
+        b1_max = std::max(b1_max, std::fabs(b1[i]));
+        b2_max = std::max(b2_max, std::fabs(b2[i]));
     }
-    c->cnntrad_ready = true;
+    install_cnntrad(c, d, L, num_classes, sw1, sw2, swl, max_row_abs_sum(w1, 64, 160), max_row_abs_sum(w2, 64, 2560), b1_max, b2_max);
     return KWS_OK;
     KWS_GUARD_END(c, "kws_load_cnn_trad")
+}
+
+// ---- kws_load_cnn_trad_device: the same image built on the device from a device-resident blob ----------------------------------
+// Statistics in the host's arithmetic: maxima of |w| (exact in any order; fmaxf drops NaN as std::max does there), the row sums of
+// max_row_abs_sum as ONE sequential float64 chain per row, in the host's order.  st: float [5] = max|w1|, max|w2|, max|wl|, max|b1|,
+// max|b2|, then (8-byte aligned) double [2] = the largest row sums of w1 and w2.
+__global__ __launch_bounds__(1024) void kws_ct_load_stats_kernel(const float* __restrict__ blob, float* __restrict__ st) {
+    __shared__ float s_m[1024];
+    __shared__ double s_r[128];
+    const int tid = threadIdx.x, q = blockIdx.x;
+    if (q < 5) {  // one maximum per workgroup
+        const size_t off[5] = {0, 64 * 160 + 64, 64 * 160 + 64 + 163840 + 64, 64 * 160, 64 * 160 + 64 + 163840};
+        const size_t len[5] = {64 * 160, 163840, (size_t)32 * 19008, 64, 64};
+        float m = 0.f;
+        for (size_t i = tid; i < len[q]; i += 1024) m = fmaxf(m, fabsf(blob[off[q] + i]));
+        s_m[tid] = m;
+        __syncthreads();
+        for (int w = 512; w > 0; w >>= 1) {
+            if (tid < w) s_m[tid] = fmaxf(s_m[tid], s_m[tid + w]);
+            __syncthreads();
+        }
+        if (tid == 0) st[q] = s_m[0];
+        return;
+    }
+    // q == 5: row sums (thread r < 64: w1 row r; 64 <= r < 128: w2 row r - 64)
+    if (tid < 128) {
+        const bool c2 = tid >= 64;
+        const int r = tid & 63;
+        const size_t len = c2 ? 2560 : 160;
+        const float* w = blob + (c2 ? 64 * 160 + 64 : 0) + (size_t)r * len;
+        double a = 0.0;
+        for (size_t i = 0; i < len; ++i) a += fabs((double)w[i]);
+        s_r[tid] = a;
+    }
+    __syncthreads();
+    if (tid < 2) {
+        double best = 0.0;
+        for (int r = 0; r < 64; ++r) best = fmax(best, s_r[tid * 64 + r]);
+        reinterpret_cast<double*>(st + 6)[tid] = best;
+    }
+}
+
+// one thread per 8-value fragment of the three GEMM layers (same fragment orders as kws_load_cnn_trad), bit for bit the host packing
+__device__ void ct_pack_frag(const float (&v)[8], uint32_t* img, size_t o3, size_t o2, float scale) {
+    uint32_t w3[3][4] = {}, w2[2][4] = {};
+    for (int j = 0; j < 8; ++j) {
+        float r = v[j];
+        for (int pc = 0; pc < 3; ++pc) {
+            const uint32_t u = __builtin_bit_cast(uint32_t, r) & 0xffff0000u;
+            r -= __builtin_bit_cast(float, u);
+            w3[pc][j >> 1] |= (u >> 16) << (16 * (j & 1));
+        }
+        const float x = v[j] * scale;
+        const _Float16 hh = (_Float16)x;
+        const _Float16 ll = (_Float16)((x - (float)hh) * 2048.f);
+        w2[0][j >> 1] |= (uint32_t)__builtin_bit_cast(uint16_t, hh) << (16 * (j & 1));
+        w2[1][j >> 1] |= (uint32_t)__builtin_bit_cast(uint16_t, ll) << (16 * (j & 1));
+    }
+    for (int pc = 0; pc < 3; ++pc)
+        for (int i = 0; i < 4; ++i) img[o3 + pc * 64 * 4 + i] = w3[pc][i];
+    for (int pc = 0; pc < 2; ++pc)
+        for (int i = 0; i < 4; ++i) img[o2 + pc * 64 * 4 + i] = w2[pc][i];
+}
+struct CtPackArgs {
+    size_t o_c1s, o_c2s, o_lin, o_c1h, o_c2h, o_linh;
+    float sw1, sw2, swl;
+};
+__global__ __launch_bounds__(256) void kws_ct_load_pack_kernel(const float* __restrict__ blob, CtPackArgs a, uint32_t* __restrict__ img) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const float* w1 = blob;
+    const float* w2 = blob + 64 * 160 + 64;
+    const float* wl = w2 + 163840 + 64;
+    const size_t FLAT = 64 * 297;
+    float v[8];
+    const int l = i & 63;
+    if (i < 10 * 2 * 64) {  // conv1 (kb, ct, l)
+        const int kb = i / 128, ct = (i / 64) & 1, co = 32 * ct + (l & 31), kh = 2 * kb + (l >> 5);
+        for (int j = 0; j < 8; ++j) v[j] = w1[(co * 20 + kh) * 8 + j];
+        ct_pack_frag(v, img, a.o_c1s + ((size_t)(kb * 2 + ct) * 3 * 64 + l) * 4, a.o_c1h + ((size_t)(kb * 2 + ct) * 2 * 64 + l) * 4, a.sw1);
+        return;
+    }
+    int k = i - 10 * 2 * 64;
+    if (k < 40 * 4 * 2 * 64) {  // conv2 (kk, cb, ct, l)
+        const int kk = k / 512, cb = (k / 128) & 3, ct = (k / 64) & 1, co = 32 * ct + (l & 31), kh = kk >> 2, kw = kk & 3;
+        for (int j = 0; j < 8; ++j) v[j] = w2[((co * 64 + 16 * cb + 8 * (l >> 5) + j) * 10 + kh) * 4 + kw];
+        const size_t f = ((size_t)kk * 4 + cb) * 2 + ct;
+        ct_pack_frag(v, img, a.o_c2s + (f * 3 * 64 + l) * 4, a.o_c2h + (f * 2 * 64 + l) * 4, a.sw2);
+        return;
+    }
+    k -= 40 * 4 * 2 * 64;
+    if (k < (int)(FLAT / 16) * 64) {  // lin (kb, l)
+        const size_t kb = k / 64;
+        for (int j = 0; j < 8; ++j) v[j] = wl[(size_t)(l & 31) * FLAT + 16 * kb + 8 * (l >> 5) + j];
+        ct_pack_frag(v, img, a.o_lin + (kb * 3 * 64 + l) * 4, a.o_linh + (kb * 2 * 64 + l) * 4, a.swl);
+    }
+}
+// The f32 sections (biases, dnn, fc), the alignment padding (zero) and the raw blob.
+struct CtCopyArgs {
+    size_t o_c1b, o_c2b, o_linb, o_dnn, o_raw, n_floats;
+    size_t pad1, n_pad1, pad2, n_pad2;  // padding words in front of the f16-pair images and behind the blob
+};
+__global__ __launch_bounds__(256) void kws_ct_load_copy_kernel(const float* __restrict__ blob, CtCopyArgs a, uint32_t* __restrict__ img) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n_floats) return;
+    const uint32_t u = __builtin_bit_cast(uint32_t, blob[i]);
+    img[a.o_raw + i] = u;
+    const size_t o_b1 = 64 * 160, o_b2 = o_b1 + 64 + 163840, o_bl = o_b2 + 64 + (size_t)32 * 19008, o_dnn = o_bl + 32;
+    if (i >= o_b1 && i < o_b1 + 64) img[a.o_c1b + i - o_b1] = u;
+    if (i >= o_b2 && i < o_b2 + 64) img[a.o_c2b + i - o_b2] = u;
+    if (i >= o_bl && i < o_bl + 32) img[a.o_linb + i - o_bl] = u;
+    if (i >= o_dnn) img[a.o_dnn + i - o_dnn] = u;  // dnn_w | dnn_b | fc_w | fc_b: contiguous in both
+    if (i < a.n_pad1) img[a.pad1 + i] = 0u;
+    if (i < a.n_pad2) img[a.pad2 + i] = 0u;
+}
+
+int kws_load_cnn_trad_device(kws_ctx* c, const float* d_blob, size_t n_floats, int num_classes) {
+    static const char* fn = "kws_load_cnn_trad_device";
+    KWS_GUARD_BEGIN
+    if (!c) return KWS_EINVAL;
+    if (!d_blob) return fail(c, KWS_EINVAL, std::string(fn) + ": blob is NULL");
+    int rc = check_cnntrad_blob(c, fn, n_floats, num_classes);
+    if (rc) return rc;
+    const CtLayout L(num_classes);
+    HIP_TRY(c, hipSetDevice(c->device));
+    uint32_t* d = static_cast<uint32_t*>(c->d_cnntrad);
+    if (!d || c->ct_image_words != L.total) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        d = nullptr;
+        if (hipMalloc(reinterpret_cast<void**>(&d), L.total * sizeof(uint32_t)) != hipSuccess)
+            return fail(c, KWS_ENOMEM, std::string(fn) + ": device allocation failed");
+    }
+    if (!c->d_ct_stats) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_ct_stats), 16 * sizeof(float)));
+    hipStream_t s = c->stream;
+    hipLaunchKernelGGL(kws_ct_load_stats_kernel, dim3(6), dim3(1024), 0, s, d_blob, c->d_ct_stats);
+    HIP_TRY(c, hipGetLastError());
+    float st[10];
+    HIP_TRY(c, hipMemcpyAsync(st, c->d_ct_stats, sizeof st, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    double rows[2];
+    memcpy(rows, st + 6, sizeof rows);
+    const float sw1 = pow2_scale_of_max(st[0]), sw2 = pow2_scale_of_max(st[1]), swl = pow2_scale_of_max(st[2]);
+    CtPackArgs pa{L.o_c1s, L.o_c2s, L.o_lin, L.o_c1h, L.o_c2h, L.o_linh, sw1, sw2, swl};
+    const int n_frag = 10 * 2 * 64 + 40 * 4 * 2 * 64 + (64 * 297 / 16) * 64;
+    hipLaunchKernelGGL(kws_ct_load_pack_kernel, dim3((n_frag + 255) / 256), dim3(256), 0, s, d_blob, pa, d);
+    HIP_TRY(c, hipGetLastError());
+    CtCopyArgs ca{L.o_c1b, L.o_c2b, L.o_linb, L.o_dnn, L.o_raw, n_floats, L.o_fcb + num_classes, L.o_c1h - (L.o_fcb + num_classes),
+                  L.o_raw + n_floats, L.total - (L.o_raw + n_floats)};
+    hipLaunchKernelGGL(kws_ct_load_copy_kernel, dim3((unsigned)((n_floats + 255) / 256)), dim3(256), 0, s, d_blob, ca, d);
+    HIP_TRY(c, hipGetLastError());
+    install_cnntrad(c, d, L, num_classes, sw1, sw2, swl, (float)(rows[0] * 1.0000002), (float)(rows[1] * 1.0000002), st[3], st[4]);
+    return KWS_OK;
+    KWS_GUARD_END(c, "kws_load_cnn_trad_device")
 }
 
 // Grow the context's float scratch (convolution outputs between two kernels of one call) to at least `need` floats.

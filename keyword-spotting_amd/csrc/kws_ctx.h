@@ -45,9 +45,12 @@ struct kws_ctx {
     CnnTradWeights tw{};
     bool cnntrad_ready = false;
     int cnntrad_math = KWS_CT_F16_PAIR;
+    const float* ct_raw = nullptr;  // the loaded blob as float32 (state_dict layouts), inside d_cnntrad: kws_cnn_trad_backward_f32's weights
+    size_t ct_image_words = 0;      // size of d_cnntrad (kws_load_cnn_trad_device refreshes it in place when the size matches)
+    float* d_ct_stats = nullptr;    // kws_load_cnn_trad_device: the weight statistics read back to the host
     float* d_conv_ws = nullptr;
     size_t conv_ws_floats = 0;
-    // training (kws_dscnn_backward_f32, kws_dscnn_bwd.hip): recomputed activations, gradients, per-workgroup partials
+    // training (kws_dscnn_backward_f32, kws_dscnn_bwd.hip; kws_cnn_trad_backward_f32, kws_cnntrad_bwd.hip): recomputed activations, gradients, per-workgroup partials
     float* d_train_ws = nullptr;
     size_t train_ws_floats = 0;
 

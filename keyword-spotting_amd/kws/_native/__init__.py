@@ -76,6 +76,9 @@ SIGNATURES = {
     "kws_stream_state": (C.c_int, [_c_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
     "kws_stream_copy_features": (C.c_int, [_c_ctx, _f32p]),
     "kws_load_cnn_trad": (C.c_int, [_c_ctx, C.POINTER(C.c_float), C.c_size_t, C.c_int]),
+    "kws_load_cnn_trad_device": (C.c_int, [_c_ctx, _f32p, C.c_size_t, C.c_int]),
+    "kws_cnn_trad_backward_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, _f32p, _f32p]),
+    "kws_cnn_trad_train_debug_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, _f32p, _i32p, _f32p, _f32p]),
     "kws_stream_vad_f32": (C.c_int, [_c_ctx, C.c_float, C.c_int, C.c_int, _i32p]),
     "kws_forward_cnn_trad_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, _f32p, _i32p]),
     "kws_set_cnn_trad_math": (C.c_int, [_c_ctx, C.c_int]),
@@ -246,6 +249,23 @@ class Context:
         blob = np.ascontiguousarray(blob, dtype=np.float32)
         self._check(self._lib.kws_load_cnn_trad(self._h, blob.ctypes.data_as(C.POINTER(C.c_float)), blob.size, int(num_classes)),
                     ModelError)
+
+    def load_cnn_trad_device(self, blob, num_classes: int):
+        """``kws_load_cnn_trad_device``: ``blob`` float32 [n_floats] on this context's device (the ten state_dict tensors in
+        order); same image and forward as ``load_cnn_trad`` of the same values, packed on the device."""
+        self._check(self._lib.kws_load_cnn_trad_device(self._h, _ptr(blob), int(blob.numel()), int(num_classes)), ModelError)
+
+    def cnn_trad_backward_f32(self, feat, dlogits, grad):
+        """Gradient of a scalar loss with respect to the loaded cnn-trad-fpool3's ten state_dict tensors
+        (``kws_cnn_trad_backward_f32``): ``feat`` float32 [B, 1, 99, 10] and ``dlogits`` float32 [B, num_classes] on the device;
+        ``grad`` float32 [n_floats] (the kws_load_cnn_trad blob layout) is overwritten.  Asynchronous on the context's stream."""
+        self._check(self._lib.kws_cnn_trad_backward_f32(self._h, _ptr(feat), int(feat.shape[0]), _ptr(dlogits), _ptr(grad)), ModelError)
+
+    def cnn_trad_train_debug_f32(self, feat, conv1, winner, conv2, hidden):
+        """The recompute stages of ``cnn_trad_backward_f32`` (``kws_cnn_trad_train_debug_f32``): conv1 after ReLU float32
+        [B, 64, 99, 10], the pool winner int32 [B, 64, 99, 3], conv2 after ReLU float32 [B, 64, 99, 3], [h | d] float32 [B, 160]."""
+        self._check(self._lib.kws_cnn_trad_train_debug_f32(self._h, _ptr(feat), int(feat.shape[0]), _ptr(conv1), _ptr(winner), _ptr(conv2),
+                                                           _ptr(hidden)), ModelError)
 
     def set_cnn_trad_math(self, math: int):
         """KWS_CT_F16_PAIR (0, default) or KWS_CT_BF16_TRIPLE (1): arithmetic of cnn-trad-fpool3's GEMM layers."""

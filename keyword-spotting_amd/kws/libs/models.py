@@ -9,7 +9,8 @@ names, shapes and initialisation, so reference checkpoints (bare ``state_dict`` 
 VALU, pointwise 1x1 and conv1 on the matrix cores.  ``DepthwiseSeparableConv`` also trains: after ``model.train()`` (which
 the reference trainers call every epoch), with grad mode on and a parameter that requires grad, its forward is a
 ``torch.autograd.Function`` whose backward is ``kws_dscnn_backward_f32``, so the trainer's ``loss.backward()`` /
-``optimizer.step()`` work unchanged.  The other models are inference only.
+``optimizer.step()`` work unchanged.  ``CnnTradFpool3`` trains the same way (``kws_cnn_trad_backward_f32``); the other models
+are inference only.
 """
 from __future__ import annotations
 
@@ -343,8 +344,16 @@ class CnnTradFpool3(KeywordSpottingModel):
     ``[1,99,10]`` MFCC map with SAME padding -- conv 64x(20x8)+ReLU, max-pool 1x3 over frequency, conv 64x(10x4)+ReLU,
     flatten, Linear 32, Linear 128+ReLU, Linear C.  The modules hold parameters; ``forward`` is
     ``kws_forward_cnn_trad_f32`` (both convolutions as implicit GEMMs on the bf16 matrix pipe with the exact
-    three-way split, the dense tail batched on the VALU).  Inference only: no autograd graph is built (there is no
-    backward for this model; training covers ``DepthwiseSeparableConv``)."""
+    three-way split, the dense tail batched on the VALU).
+
+    Trainable like ``DepthwiseSeparableConv``: after an explicit ``model.train()``, when ``torch.is_grad_enabled()`` and some
+    parameter requires grad, ``forward`` runs through ``_CnnTradTrainFunction`` -- the same inference call (logits and labels
+    bit-identical to a call under ``torch.no_grad()``) with a backward that recomputes the activations in f32 and computes all
+    ten parameter gradients in HIP (``kws_cnn_trad_backward_f32``, deterministic, independent of ``kws_set_cnn_trad_math``).
+    Each gradient lands on its parameter's device.  No gradient with respect to the input features is provided (an input that
+    requires grad raises ``ModelError`` in backward).  Otherwise -- no ``train()``, ``eval()``, ``torch.no_grad()``, frozen
+    parameters -- no autograd graph is built.  Parameters on the GPU are re-uploaded after an optimizer step without leaving
+    the device (``kws_load_cnn_trad_device``); CPU-resident parameters go through the host load."""
 
     def __init__(self, num_classes: int = 12):
         super().__init__(num_classes)
@@ -355,6 +364,14 @@ class CnnTradFpool3(KeywordSpottingModel):
         self.fc = nn.Linear(128, num_classes)
         self._ctx = None
         self._uploaded = None
+        self._autograd = False  # set by an explicit train(), cleared by eval() / train(False)
+
+    def train(self, mode: bool = True):
+        """``nn.Module.train``; an explicit ``train()`` also switches ``forward`` to the autograd path (see the class
+        docstring), ``eval()`` / ``train(False)`` switches it back."""
+        super().train(mode)
+        self._autograd = bool(mode)
+        return self
 
     def packed_weights(self) -> np.ndarray:
         return np.concatenate([v.detach().to("cpu", torch.float32).reshape(-1).numpy() for v in self.state_dict().values()])
@@ -364,15 +381,26 @@ class CnnTradFpool3(KeywordSpottingModel):
         ``p._version``; see ``DepthwiseSeparableConv.sync_weights``)."""
         self._uploaded = None
 
-    def _context(self, device_index: int):
+    def _context(self, device_index: int, params=None):
+        """The model's context on ``device_index`` holding ``params`` (default: the current parameters, in ``parameters()``
+        order); uploaded only when they differ from the tensors (and versions) uploaded last.  Parameters that all live on
+        that GPU are concatenated there and loaded with ``kws_load_cnn_trad_device``; otherwise through the host."""
         from kws import _native
 
         if self._ctx is None or self._ctx.device != device_index:
             self._ctx = _native.Context(device_index, ModelError)
             self._uploaded = None
-        fp = tuple((p.data_ptr(), p._version) for p in self.parameters())
+        params = tuple(self.parameters()) if params is None else tuple(params)
+        fp = tuple((p.data_ptr(), p._version) for p in params)
         if fp != self._uploaded:
-            self._ctx.load_cnn_trad(self.packed_weights(), self.num_classes)
+            dev = torch.device("cuda", device_index)
+            if all(p.device == dev for p in params):
+                self._ctx.use_torch_stream()
+                blob = torch.cat([p.detach().to(torch.float32).reshape(-1) for p in params])
+                self._ctx.load_cnn_trad_device(blob, self.num_classes)
+            else:
+                self._ctx.load_cnn_trad(np.concatenate([p.detach().to("cpu", torch.float32).reshape(-1).numpy() for p in params]),
+                                        self.num_classes)
             self._uploaded = fp
         self._ctx.use_torch_stream()
         return self._ctx
@@ -382,12 +410,21 @@ class CnnTradFpool3(KeywordSpottingModel):
             raise ModelError("CnnTradFpool3.forward needs a CUDA/ROCm tensor: the forward is a HIP kernel and has no CPU fallback")
         if x.dim() != 4 or tuple(x.shape[1:]) != FEATURE_SHAPE:
             raise ModelError(f"expected input [B,1,99,10], got {tuple(x.shape)}")
+        params = tuple(self.parameters())
+        if self._autograd and torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            logits, labels = _CnnTradTrainFunction.apply(self, x, *params)
+        else:
+            logits, labels = self._forward_native(x)
+        return (logits, labels) if return_labels else logits
+
+    def _forward_native(self, x: torch.Tensor):
+        """The inference kernels on ``x`` (checked by the caller) -> (logits, labels); no autograd graph."""
         ctx = self._context(x.device.index or 0)
         x = x.detach().to(torch.float32).contiguous()
         logits = torch.empty((x.shape[0], self.num_classes), dtype=torch.float32, device=x.device)
         labels = torch.empty((x.shape[0],), dtype=torch.int32, device=x.device)
         ctx.forward_cnn_trad_f32(x, logits, labels)
-        return (logits, labels) if return_labels else logits
+        return logits, labels
 
     def infer_pcm16(self, wav: torch.Tensor):
         """Fused path (BASELINE.json configs[2]): ``int16[B,16000]`` PCM on the GPU -> (logits, labels); MFCC +
@@ -402,3 +439,40 @@ class CnnTradFpool3(KeywordSpottingModel):
         labels = torch.empty((wav.shape[0],), dtype=torch.int32, device=wav.device)
         ctx.infer_cnn_trad_i16(wav, logits, labels)
         return logits, labels
+
+
+class _CnnTradTrainFunction(torch.autograd.Function):
+    """``CnnTradFpool3.forward`` with a HIP backward.  Forward: exactly the inference call; the input and the parameters are
+    saved with ``save_for_backward``, so torch's version counter rejects a parameter modified in place between forward and
+    backward.  Backward: ``kws_cnn_trad_backward_f32`` at the saved parameters (uploaded only if they are not the device copy),
+    the flat gradient split into views shaped like the parameters and moved to each parameter's device."""
+
+    @staticmethod
+    def forward(fctx, model, x, *params):
+        logits, labels = model._forward_native(x)
+        fctx.model = model
+        fctx.save_for_backward(x, *params)
+        fctx.mark_non_differentiable(labels)
+        return logits, labels
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, dlogits, _dlabels):
+        x, *params = fctx.saved_tensors
+        if fctx.needs_input_grad[1]:
+            raise ModelError("CnnTradFpool3: the gradient with respect to the input features is not provided "
+                             "(kws_cnn_trad_backward_f32 computes parameter gradients only); detach the input")
+        model = fctx.model
+        ctx = model._context(x.device.index or 0, params)
+        x = x.detach().to(torch.float32).contiguous()
+        dl = dlogits.detach().to(x.device, torch.float32).contiguous()
+        grad = torch.empty(sum(p.numel() for p in params), dtype=torch.float32, device=x.device)
+        ctx.cnn_trad_backward_f32(x, dl, grad)
+        on_dev = {}
+        out, off = [], 0
+        for p in params:
+            if p.device not in on_dev:
+                on_dev[p.device] = grad.to(p.device)
+            out.append(on_dev[p.device][off:off + p.numel()].view(p.shape).to(p.dtype))
+            off += p.numel()
+        return (None, None, *out)

@@ -1,0 +1,143 @@
+"""CPU tests of cnn-trad-fpool3 training (kws_cnn_trad_backward_f32): the backward unit is hazard-free at the ISA level and runs on
+the matrix cores, the C ABI declares, binds and exports the three entries, the pinned float64 restatement equals torch autograd of
+the oracle (ties of the max-pool included), the model keeps its CPU contract, and bench_train counts the model's FLOPs."""
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import REPO
+
+sys.path.insert(0, os.path.join(REPO, "tools"))
+sys.path.insert(0, os.path.join(REPO, "tests"))
+import isa_hazard_lint as lint  # noqa: E402
+
+UNIT = os.path.join(REPO, "keyword-spotting_amd", "csrc", "kws_cnntrad_bwd.hip")
+KERNELS = ("kws_ct_bwd_prep_kernel", "kws_ct_bwd_conv1_kernel", "kws_ct_bwd_conv2_fwd_kernel", "kws_ct_bwd_lin_fwd_kernel",
+           "kws_ct_bwd_tail_kernel", "kws_ct_bwd_lin_kernel", "kws_ct_bwd_conv2_wgrad_kernel", "kws_ct_bwd_conv2_dgrad_kernel",
+           "kws_ct_bwd_conv1_wgrad_kernel", "kws_ct_bwd_reduce_kernel")
+PROTOS = {
+    "kws_cnn_trad_backward_f32":
+        "int kws_cnn_trad_backward_f32(kws_ctx* ctx, const float* d_feat, int B, const float* d_dlogits, float* d_grad);",
+    "kws_cnn_trad_train_debug_f32":
+        "int kws_cnn_trad_train_debug_f32(kws_ctx* ctx, const float* d_feat, int B, float* d_conv1, int32_t* d_winner, "
+        "float* d_conv2, float* d_hidden);",
+    "kws_load_cnn_trad_device":
+        "int kws_load_cnn_trad_device(kws_ctx* ctx, const float* d_blob, size_t n_floats, int num_classes);",
+}
+
+
+@pytest.mark.skipif(not os.path.exists(lint.HIPCC), reason="hipcc not installed")
+def test_backward_unit_is_hazard_free_and_uses_the_matrix_cores():
+    findings, _, isa = lint.lint_file(UNIT)
+    flat = [(fn[:60], line, rule, msg) for fn, fs in findings.items() for line, rule, msg in fs]
+    assert not flat, flat[:5]
+    body = open(isa).read()
+    assert re.search(r"v_mfma_f32_\w+", body), "conv2's GEMMs and lin's products must run on a matrix instruction"
+    for k in KERNELS:
+        assert k in body, f"kernel {k} missing (rocprofv3 attributes time by these names)"
+
+
+def test_header_declares_the_three_entries():
+    text = re.sub(r"\s+", " ", open(os.path.join(REPO, "include", "kws_hip.h")).read())
+    for name, proto in PROTOS.items():
+        assert proto in text, name
+    assert "#define KWS_ABI_VERSION 1" in text
+
+
+def test_entries_are_bound_and_exported():
+    native = pytest.importorskip("kws._native")
+    for name in PROTOS:
+        assert name in native.SIGNATURES, name
+    for meth in ("cnn_trad_backward_f32", "cnn_trad_train_debug_f32", "load_cnn_trad_device"):
+        assert hasattr(native.Context, meth), meth
+    if os.path.exists(native.LIB_PATH):
+        lib = native.lib()
+        for name in PROTOS:
+            assert hasattr(lib, name), name
+
+
+def _state(kind, C):
+    from oracle import cnn_trad as o_ct
+
+    if kind == "random":
+        return o_ct.random_state(5, num_classes=C)
+    from kws.libs.models import CnnTradFpool3
+
+    torch.manual_seed(C)
+    return {k: v.detach().clone() for k, v in CnnTradFpool3(C).state_dict().items()}
+
+
+@pytest.mark.parametrize("kind,C,inp", [("random", 12, "randn"), ("default", 12, "randn"), ("random", 3, "const"),
+                                        ("default", 12, "const"), ("random", 12, "zero")])
+def test_pinned_oracle_equals_torch_autograd(kind, C, inp):
+    """Pinned to its own float64 decisions, the restatement gives torch autograd's logits and gradients of
+    oracle.cnn_trad.forward -- also on constant maps, where bins 3, 4, 5 of rows 9..88 see only in-range taps and pooled column 1
+    is an exact three-way tie: torch routes it to the first maximum, and so does the restatement."""
+    import _cnntrad_grad as cg
+    from oracle import cnn_trad as o_ct
+
+    torch.set_num_threads(min(16, os.cpu_count() or 1))
+    gen = torch.Generator().manual_seed(17 + C)
+    state = {k: v.to(torch.float64) for k, v in _state(kind, C).items()}
+    x = torch.randn(3, 1, 99, 10, generator=gen, dtype=torch.float64)
+    if inp == "const":
+        x = torch.tensor([0.7, -1.3, 2.0], dtype=torch.float64).reshape(3, 1, 1, 1).expand(3, 1, 99, 10).contiguous()
+    elif inp == "zero":
+        x.zero_()
+    dl = torch.randn(3, C, generator=gen, dtype=torch.float64)
+    pins = cg.own_pins(state, x)
+    if inp == "const":  # the tie is real: the three bins of pooled column 1 are equal on rows 9..88
+        z1 = cg._z1(state, x)[:, :, 9:89]
+        assert torch.equal(z1[..., 3], z1[..., 4]) and torch.equal(z1[..., 4], z1[..., 5])
+        assert bool((pins["winner"][:, :, 9:89, 1] == 0).all())
+    logits, _ = cg.forward(state, x, pins)
+    st = {k: v.clone().requires_grad_(True) for k, v in state.items()}
+    want = o_ct.forward(st, x)
+    assert torch.equal(logits, want.detach())
+    (want * dl).sum().backward()
+    g = cg.grads(state, x, dl, pins)
+    for k in cg.keys(C):
+        ref = st[k].grad.numpy()
+        assert np.allclose(g[k], ref, rtol=1e-12, atol=1e-14 * max(1.0, float(np.abs(ref).max()))), k
+
+
+def test_pinned_decisions_are_honoured():
+    """A mask taken from elsewhere is honoured: with conv2 switched off, nothing reaches lin, conv2 or conv1."""
+    import _cnntrad_grad as cg
+    from oracle import cnn_trad as o_ct
+
+    state = {k: v.to(torch.float64) for k, v in o_ct.random_state(2).items()}
+    x = torch.randn(2, 1, 99, 10, dtype=torch.float64, generator=torch.Generator().manual_seed(4))
+    pins = cg.own_pins(state, x)
+    pins["m2"] = torch.zeros_like(pins["m2"])
+    g = cg.grads(state, x, torch.ones(2, 12, dtype=torch.float64), pins)
+    for k in ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias", "lin.weight"):
+        assert not g[k].any(), k
+    assert g["lin.bias"].any() and g["fc.weight"].any()
+
+
+def test_training_forward_without_gpu_still_fails_loudly():
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    from kws.common.errors import ModelError
+    from kws.libs.models import CnnTradFpool3
+
+    m = CnnTradFpool3().train()
+    assert m._autograd and torch.is_grad_enabled() and all(p.requires_grad for p in m.parameters())
+    with pytest.raises(ModelError, match="no CPU fallback"):
+        m(torch.zeros(2, 1, 99, 10))
+    assert not CnnTradFpool3().train().eval()._autograd
+
+
+def test_bench_train_counts_the_cnntrad_flops():
+    import bench_train
+
+    assert bench_train.cnntrad_forward_macs(12) == 59_411_968  # 59.4 M multiply-adds per clip, 82 % in conv2
+    assert abs(64 * 297 * 2560 / bench_train.cnntrad_forward_macs(12) - 0.82) < 0.005
+    # recompute + backward at B = 1024: 330 GFLOP (345 if conv1's weight gradient ran over all 990 positions, not the 297 winners)
+    g = bench_train.cnntrad_backward_flops(1024, 12) / 1e9
+    assert 325 < g < 335, g

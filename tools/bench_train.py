@@ -6,6 +6,8 @@ zero_grad -> forward -> CrossEntropyLoss -> loss.backward() -> Adam(lr=1e-3) (tr
 
     python tools/bench_train.py [--batches 1028,4096] [--steps 60] [--warmup 10] [--out FILE]
     python tools/bench_train.py --backward-only --batches 1028     # only the kws_dscnn_backward_f32 loop (for rocprofv3)
+    python tools/bench_train.py --model cnn-trad-fpool3 [--batches 1024,4096]   # the same step on CnnTradFpool3
+                                   (oracle.cnn_trad.forward for torch eager; kws_cnn_trad_backward_f32; --backward-only as above)
 
 Prints one JSON line.  Per batch size B:
   hip.step_ms            device-event time of a whole step (median, p10, p90 over --steps steps), clips/s at the median
@@ -19,6 +21,9 @@ Prints one JSON line.  Per batch size B:
   backward_tflops, backward_peak_frac   backward_gflop over backward_call_ms, and that over the 157.3 TF f32 matrix peak
   torch_eager.step_ms    the eager step (median, p10, p90), clips/s
   speedup                torch eager median / HIP median
+With --model cnn-trad-fpool3 the result also carries the model name, hip.refresh_host_ms (the same refresh through the host
+load kws_load_cnn_trad, device events around the call, median: what the refresh cost before kws_load_cnn_trad_device) and
+backward_bf16_split_floor_ms (backward_gflop at the 2.5 PF dense bf16 rate over the six products of the exact split).
 """
 import argparse
 import json
@@ -49,6 +54,20 @@ def backward_flops(B, T=T_IN, F=F_IN, num_classes=C):
            + sum(2 * (2 * 64 * 9 * p) for p in pk)         # depthwise: g_w, dX_in
            + 2 * 64 * 100 * p0)                            # conv1: g_w
     return B * (fwd + bwd)
+
+
+def cnntrad_forward_macs(num_classes=C):
+    """Multiply-adds of one cnn-trad-fpool3 forward per clip: conv1, conv2, lin, dnn, fc."""
+    return 64 * 990 * 160 + 64 * 297 * 2560 + 19008 * 32 + 32 * 128 + 128 * num_classes
+
+
+def cnntrad_backward_flops(B, num_classes=C):
+    """Algorithmic FLOPs of kws_cnn_trad_backward_f32 for B clips: the recompute (the forward without fc) and the backward --
+    fc and dnn (input and weight gradients), lin (dy2 and g_lin.w), conv2 (weight and input gradients), conv1's weight gradient
+    over the 297 pool winners per channel -- 2 FLOP per multiply-add."""
+    rec = cnntrad_forward_macs(num_classes) - 128 * num_classes
+    bwd = 2 * 128 * num_classes + 2 * 32 * 128 + 2 * 19008 * 32 + 2 * 64 * 297 * 2560 + 64 * 297 * 160
+    return 2 * B * (rec + bwd)
 
 
 def stats(xs):
@@ -153,9 +172,116 @@ def run(B, steps, warmup, dev, backward_only=False):
     }
 
 
+BF16_MATRIX_PEAK_TF = 2516.6
+
+
+def run_cnntrad(B, steps, warmup, dev, backward_only=False):
+    from kws.libs.models import CnnTradFpool3
+    from oracle import cnn_trad as o_ct
+
+    torch.manual_seed(0)
+    model = CnnTradFpool3().to(dev).train()
+    init = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    gen = torch.Generator().manual_seed(B)
+    x = torch.randn(B, 1, T_IN, F_IN, generator=gen).to(dev)
+    y = torch.randint(0, C, (B,), generator=gen).to(dev)
+    crit = torch.nn.CrossEntropyLoss()
+    opt = torch.optim.Adam(model.parameters(), lr=1e-3)
+    st = {k: v.clone().requires_grad_(True) for k, v in init.items()}
+    opt_t = torch.optim.Adam(list(st.values()), lr=1e-3)
+
+    def ev():
+        return torch.cuda.Event(enable_timing=True)
+
+    def calls(ctx, dl, grad, n):
+        evs = []
+        for _ in range(n):
+            a, b = ev(), ev()
+            a.record()
+            ctx.cnn_trad_backward_f32(x, dl, grad)
+            b.record()
+            evs.append((a, b))
+        torch.cuda.synchronize()
+        return [a.elapsed_time(b) for a, b in evs]
+
+    gflop = cnntrad_backward_flops(B) / 1e9
+    ctx = model._context(dev.index or 0)
+    dl = torch.randn(B, C, generator=gen).to(dev) / B
+    grad = torch.empty(sum(p.numel() for p in model.parameters()), dtype=torch.float32, device=dev)
+    if backward_only:
+        calls(ctx, dl, grad, warmup)
+        return {"B": B, "backward_call_ms": stats(calls(ctx, dl, grad, steps)), "backward_gflop": round(gflop, 3)}
+
+    def hip_step():
+        e = [ev() for _ in range(5)]
+        e[0].record()
+        opt.zero_grad()
+        model._context(dev.index or 0)   # refresh: the device load of the parameters the last optimizer step changed
+        e[1].record()
+        logits = model(x)
+        e[2].record()
+        crit(logits, y).backward()
+        e[3].record()
+        opt.step()
+        e[4].record()
+        return e
+
+    def torch_step():
+        e = [ev(), ev()]
+        e[0].record()
+        opt_t.zero_grad()
+        crit(o_ct.forward(st, x), y).backward()
+        opt_t.step()
+        e[1].record()
+        return e
+
+    for _ in range(warmup):
+        hip_step()
+        torch_step()
+    torch.cuda.synchronize()
+    hip_ev, t_ev = [], []
+    for _ in range(steps):
+        hip_ev.append(hip_step())
+        t_ev.append(torch_step())
+    torch.cuda.synchronize()
+    step = [e[0].elapsed_time(e[4]) for e in hip_ev]
+    split = {name: stats([e[i].elapsed_time(e[i + 1]) for e in hip_ev])["median"]
+             for i, name in enumerate(["refresh", "forward", "backward", "optimizer"])}
+    t_step = [e[0].elapsed_time(e[1]) for e in t_ev]
+    # the refresh through the host load, as before kws_load_cnn_trad_device
+    host = []
+    for _ in range(max(10, steps // 5)):
+        a, b = ev(), ev()
+        a.record()
+        ctx.load_cnn_trad(model.packed_weights(), C)
+        b.record()
+        torch.cuda.synchronize()
+        host.append(a.elapsed_time(b))
+    model.sync_weights()
+    ctx = model._context(dev.index or 0)
+    calls(ctx, dl, grad, warmup)
+    call_ms = stats(calls(ctx, dl, grad, steps))
+    tflops = gflop / call_ms["median"]
+    hs, ts = stats(step), stats(t_step)
+    return {
+        "B": B,
+        "hip": {"step_ms": hs, "clips_per_s": round(B / hs["median"] * 1e3), "split_ms": split,
+                "refresh_host_ms": stats(host)["median"]},
+        "backward_call_ms": call_ms,
+        "backward_gflop": round(gflop, 3),
+        "backward_tflops": round(tflops, 3),
+        "backward_peak_frac": round(tflops / F32_MATRIX_PEAK_TF, 4),
+        "backward_f32_floor_ms": round(gflop / F32_MATRIX_PEAK_TF, 3),
+        "backward_bf16_split_floor_ms": round(6 * gflop / BF16_MATRIX_PEAK_TF, 3),
+        "torch_eager": {"step_ms": ts, "clips_per_s": round(B / ts["median"] * 1e3)},
+        "speedup": round(ts["median"] / hs["median"], 3),
+    }
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--batches", default="1028,4096")
+    ap.add_argument("--model", default="ds-cnn", choices=["ds-cnn", "cnn-trad-fpool3"])
+    ap.add_argument("--batches", default=None, help="comma-separated batch sizes (default 1028,4096; cnn-trad-fpool3: 1024,4096)")
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
@@ -166,9 +292,14 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("bench_train.py needs a GPU (there is no CPU fallback to time)")
     dev = torch.device("cuda", 0)
+    cnntrad = args.model == "cnn-trad-fpool3"
+    batches = args.batches or ("1024,4096" if cnntrad else "1028,4096")
+    fn = run_cnntrad if cnntrad else run
     res = {"tool": "bench_train", "device": torch.cuda.get_device_name(0), "features": [1, T_IN, F_IN], "num_classes": C,
-           "steps": args.steps, "warmup": args.warmup, "f32_matrix_peak_tf": F32_MATRIX_PEAK_TF,
-           "results": [run(int(b), args.steps, args.warmup, dev, args.backward_only) for b in args.batches.split(",")]}
+           "steps": args.steps, "warmup": args.warmup, "f32_matrix_peak_tf": F32_MATRIX_PEAK_TF}
+    if cnntrad:
+        res = {"tool": "bench_train", "model": args.model, **{k: v for k, v in res.items() if k != "tool"}}
+    res["results"] = [fn(int(b), args.steps, args.warmup, dev, args.backward_only) for b in batches.split(",")]
     line = json.dumps(res)
     print(line)
     if args.out:
