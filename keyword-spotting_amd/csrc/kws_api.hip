@@ -203,6 +203,11 @@ int kws_create(kws_ctx** out, int device_id) {
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = dscnn_init_device();
     if (e == hipSuccess) e = cnntrad_init_device();
+    if (e == hipSuccess) {
+        hipDeviceProp_t prop;
+        e = hipGetDeviceProperties(&prop, device_id);
+        if (e == hipSuccess) c->n_cu = prop.multiProcessorCount;
+    }
     if (e != hipSuccess) {
         int rc = fail_hip(nullptr, e, "kws_create");
         if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -804,7 +809,7 @@ static int forward_impl(kws_ctx* c, const float* d_feat, int B, float* d_logits,
         return KWS_OK;
     }
     ProfScope ps(c, KWS_K_DSCNN);
-    HIP_TRY(c, launch_dscnn(c->stream, c->mw, d_feat, B, d_logits, d_label, d_act, mode, d_stamps));
+    HIP_TRY(c, launch_dscnn(c->stream, c->mw, d_feat, B, d_logits, d_label, d_act, mode, d_stamps, nullptr, false, 3, c->n_cu));
     return KWS_OK;
 }
 

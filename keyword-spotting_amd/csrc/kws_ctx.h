@@ -14,6 +14,7 @@ using kws::FrontendParams; using kws::FrontendTables; using kws::DscnnWeights; u
 
 struct kws_ctx {
     int device = 0;
+    int n_cu = 0;                   // compute units of the device (hipDeviceProp_t::multiProcessorCount): the persistent DS-CNN grid
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     hipEvent_t order_ev = nullptr;  // orders the new stream behind the old one in kws_set_stream

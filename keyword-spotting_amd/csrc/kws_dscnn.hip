@@ -125,6 +125,19 @@ struct Leftover {
 static_assert(Blk<1>::TILES == 5 && Blk<2>::TILES == 9, "the leftover tiles are the fifth of block 1 and the ninth of block 2");
 static_assert(4 * CH * Leftover<1>::NP <= 38784 - OFF_Z2 && OFF_Z0 + 4 * CH * Leftover<2>::NP <= OFF_FEAT, "partial sums fit their dead planes");
 
+// Persistent batched launch (PERSIST, kws_dscnn_fwd_kernel): a workgroup carries clips g, g + grid, ... one after another and
+// the next clip is staged in block 4's tail.  Block 4 reads only Z3 and the odd table buffer, so the Z2 plane is dead from
+// block 3's barrier until block 2 of the next clip: the next clip's padded features and this clip's pool partials go there.
+// Both are dead again before block 1 writes its leftover partials over them (Leftover<1>::OFF_PART = OFF_Z2): the features
+// after conv1, the pool partials once the pool / fc wavefront has read them, which it does before conv1's barrier.
+constexpr int OFF_FEAT_P = OFF_Z2;                            // [103][14] features of the NEXT clip
+constexpr int OFF_POOLBUF_P = OFF_FEAT_P + 1456;              // [NW][64]  block 4's pool partials of THIS clip
+constexpr int STAGE_WAVES = 4;                                // wavefronts 0-3 stage the next clip (they finish block 4 first)
+static_assert(OFF_FEAT_P >= OFF_Z3 + Blk<3>::SOUT * CH, "the next clip's features must not overlap block 4's input");
+static_assert(OFF_FEAT_P + FEAT_H * FEAT_W <= OFF_POOLBUF_P && OFF_POOLBUF_P % 4 == 0, "features and pool partials are disjoint");
+static_assert(OFF_POOLBUF_P + NW * CH <= OFF_Z2 + Blk<2>::SOUT * CH && OFF_Z2 + Blk<2>::SOUT * CH <= OFF_DWTAB,
+              "pool partials stay inside the Z2 plane, clear of the table buffers the next clip's block 1 rewrites");
+
 // Depthwise 3x3 (+bias) at this lane's column from its three own-column inputs: nine multiply-adds and two
 // fused DPP multiply-adds that pull the neighbouring lanes' column sums across the wavefront (0 shifted in at the
 // ends).  Written as one asm block so that (a) the shift and the multiply-add are one instruction each
@@ -503,8 +516,8 @@ constexpr int OFF_C1P2 = OFF_C1W8 + 2 * C1W_ROWS * 3 * 4;          // [2][103][3
 static_assert(OFF_C1P2 + 2 * C1W_ROWS * 3 <= OFF_Z0, "conv1's operand windows live where block 1's output goes later");
 static_assert(2 * (C1_W - 1) + 9 < FEAT_W && 2 * (C1_H - 1) + 9 < FEAT_H, "window reach inside the padded map");
 
-__device__ __forceinline__ void conv1_build_windows(float* lds, int tid, float sx) {
-    const float* featp = lds + OFF_FEAT;
+__device__ __forceinline__ void conv1_build_windows(float* lds, int tid, float sx, int off_feat = OFF_FEAT) {
+    const float* featp = lds + off_feat;
     uint32_t* w8 = reinterpret_cast<uint32_t*>(lds + OFF_C1W8);
     uint32_t* p2 = reinterpret_cast<uint32_t*>(lds + OFF_C1P2);
     for (int i = tid; i < C1W_ROWS * 3; i += NT) {
@@ -613,9 +626,9 @@ struct PosRange {
 
 template <bool RANGED, int NP>
 __device__ __forceinline__ void conv1_phase_split(const DscnnWeights& w, float* lds, int tid, const uintx4 (&c1f)[7][NP],
-                                                  PosRange rg, float sx = 1.f, float sig0 = 1.f) {
+                                                  PosRange rg, float sx = 1.f, float sig0 = 1.f, int off_feat = OFF_FEAT) {
     static_assert(P0 > 4 * 32 && P0 <= 5 * 32 && NW >= 6, "conv1 work split: four dual tiles + one tile in two halves");
-    const float* featp = lds + OFF_FEAT;
+    const float* featp = lds + off_feat;
     float* z0 = lds + OFF_Z0;
     const int lane = tid & 63, wv = tid >> 6;
     float mx = 0.f;
@@ -745,7 +758,8 @@ __device__ __forceinline__ void leftover_combine(float* lds, int tid) {
 // RANGED: only the positions rg.lo .. rg.hi - 1 (whole rows) are computed -- one time tile of a workgroup cluster.
 template <int N, int MODE, bool RANGED = false>
 __device__ __forceinline__ void block_phase(const DscnnWeights& w, float* lds, int tid, PwOperands<MODE>& pwo,
-                                            float* __restrict__ act4 = nullptr, PosRange rg = PosRange{0, 0}, PairCtx pc = PairCtx{}) {
+                                            float* __restrict__ act4 = nullptr, PosRange rg = PosRange{0, 0}, PairCtx pc = PairCtx{},
+                                            int off_poolbuf = OFF_POOLBUF) {
     using G = Blk<N>;
     constexpr bool PAIR = MODE == 5;          // f16 pairs: three products per k-block, activations in per-clip scaled units
     constexpr int NP = PAIR ? 2 : 3;
@@ -767,7 +781,7 @@ __device__ __forceinline__ void block_phase(const DscnnWeights& w, float* lds, i
     float* zout = lds + G::OFF_OUT;
     const float* dwtab = lds + OFF_DWTAB + G::BUF * 768;
     const float* pwb = lds + OFF_PWB + G::BUF * 64;
-    float* poolbuf = lds + OFF_POOLBUF;
+    float* poolbuf = lds + off_poolbuf;  // block 4's pool partials (PERSIST: OFF_POOLBUF_P)
 
     // The other table buffer is idle during this block: the next block's tables are fetched now and
     // stored after the units.  Ring and zero slots of the output planes.  No barrier needed before the
@@ -1184,6 +1198,115 @@ __device__ __forceinline__ void block_phase(const DscnnWeights& w, float* lds, i
     (void)bias4;
 }
 
+// conv1's pre-split A operands of channel tile wv & 1, all seven k-blocks (split paths)
+template <int NP>
+__device__ __forceinline__ void load_conv1_frags(const DscnnWeights& w, int wv, int lane, uintx4 (&c1f)[7][NP]) {
+    const uintx4* src = reinterpret_cast<const uintx4*>(NP == 2 ? w.c1_pair : w.c1_split) + (size_t)(wv & 1) * (7 * NP * 64) + lane;
+#pragma unroll
+    for (int kb = 0; kb < 7; ++kb)
+#pragma unroll
+        for (int p = 0; p < NP; ++p) c1f[kb][p] = src[(kb * NP + p) * 64];
+}
+
+// Argmax over lanes 0 .. C-1 of a wavefront, first maximum wins: wave maximum by DPP (no LDS round trips; six dependent
+// __shfl_xor rounds through ds_bpermute were 1.4 k of the 2.6 k cycles the classifier tail took), then the lowest lane that
+// holds it.  v = -inf in lanes >= C.
+__device__ __forceinline__ int wave_argmax_first(float v, int lane, int C) {
+    float m = v;
+    m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, m), __builtin_bit_cast(int, m), 0x111, 0xf, 0xf, false)));
+    m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, m), __builtin_bit_cast(int, m), 0x112, 0xf, 0xf, false)));
+    m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, m), __builtin_bit_cast(int, m), 0x114, 0xf, 0xf, false)));
+    m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, m), __builtin_bit_cast(int, m), 0x118, 0xf, 0xf, false)));
+    m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, m), __builtin_bit_cast(int, m), 0x142, 0xa, 0xf, false)));
+    m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, m), __builtin_bit_cast(int, m), 0x143, 0xc, 0xf, false)));
+    const float vmax = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, m), 63));
+    const unsigned long long holders = __ballot(lane < C && v == vmax);
+    return holders ? __ffsll(holders) - 1 : 0;  // all-NaN logits: label 0
+}
+
+// PERSIST: the kernel's weight argument read again for every clip, through a kernel-argument pointer the compiler cannot see
+// through.  Every weight load of the body is clip-invariant: hoisted out of the clip loop, the loads (and the ~50 argument
+// dwords) would stay live for the workgroup's whole life and spill.  The argument is the kernel's first: offset 0.
+__device__ __forceinline__ DscnnWeights weights_for_this_clip() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    using KArg = const __attribute__((address_space(4))) DscnnWeights*;
+    KArg p = (KArg)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *p;
+#else
+    return DscnnWeights{};
+#endif
+}
+
+// PERSIST, block 4's tail: wavefronts 0 .. STAGE_WAVES-1 stage the padded feature map of `clip` at OFF_FEAT_P (the loads,
+// the zero pad, the scatter) and, for f16 pairs, publish its largest |feature| to stage-maxima set 0 -- the slots of the other
+// wavefronts are zeroed, so read_stage_max sees this clip alone (set 0 was last read before block 3).
+template <bool PAIR>
+__device__ __forceinline__ void stage_features_persist(float* lds, const float* __restrict__ feat, int clip, int tid) {
+    constexpr int ST = STAGE_WAVES * 64;
+    constexpr int FV = (IN_T * IN_F + ST - 1) / ST;
+    static_assert(2 * STAGE_WAVES == NW, "each staging wavefront zeroes the maximum slot of one other wavefront");
+    const int lane = tid & 63, wv = tid >> 6;
+    const float* f = feat + (size_t)clip * (IN_T * IN_F);
+    float fv[FV];
+#pragma unroll
+    for (int k = 0; k < FV; ++k) {
+        const int i = tid + k * ST;
+        fv[k] = i < IN_T * IN_F ? f[i] : 0.f;
+    }
+    float* featp = lds + OFF_FEAT_P;
+    for (int i = tid; i < FEAT_H * FEAT_W; i += ST) {  // the zero fill touches only the padding, the scatter only the interior
+        const int r = i / FEAT_W - 2, c = i % FEAT_W - 2;
+        if (!((unsigned)r < (unsigned)IN_T && (unsigned)c < (unsigned)IN_F)) featp[i] = 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < FV; ++k) {
+        const int i = tid + k * ST;
+        if (i < IN_T * IN_F) featp[(i / IN_F + 2) * FEAT_W + (i % IN_F) + 2] = fv[k];
+    }
+    if constexpr (PAIR) {
+        float m = 0.f;
+#pragma unroll
+        for (int k = 0; k < FV; ++k) m = fmaxf(m, fabsf(fv[k]));
+        publish_wave_max(lds, 0, wv, lane, m);
+        if (lane == 63) lds[OFF_WMAX + wv + STAGE_WAVES] = 0.f;
+    }
+}
+
+// PERSIST: global average pool + Linear(64 -> C) + argmax of a finished clip on ONE wavefront (NW - 1, which has no conv1 unit),
+// while the others run the next clip's conv1.  Same sums in the same order as the one-clip tail of kws_dscnn_fwd_kernel: lane c
+// adds the NW partials of channel c, then the ring term; the classifier row of lane j takes the 64 pooled values in channel
+// order, broadcast from their lanes (v_readlane) instead of through LDS.
+__device__ __forceinline__ void pool_fc_wave(const DscnnWeights& w, const float* lds, int lane, int clip, float* __restrict__ logits,
+                                             int32_t* __restrict__ label, float* __restrict__ a_pool) {
+    const int C = w.num_classes;
+    float4 fcw[CH / 4];
+    float fcb = 0.f;
+    const float4* wr = reinterpret_cast<const float4*>(w.fc_w + (lane < C ? lane : 0) * CH);
+#pragma unroll
+    for (int c = 0; c < CH / 4; ++c) fcw[c] = wr[c];
+    if (lane < C) fcb = w.fc_b[lane];
+    const float ring_b = w.pw_b[3 * CH + lane];
+    constexpr float RING_N = 55.f * 11.f - 53.f * 9.f;  // 128
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < NW; ++k) s += lds[OFF_POOLBUF_P + k * CH + lane];
+    s = fmaf(RING_N, relu(ring_b), s) * (1.0f / (55.f * 11.f));
+    if (a_pool) a_pool[lane] = s;
+    float acc = fcb;  // every lane runs the chain (rows >= C are row 0 again): the broadcasts stay outside divergent code
+#pragma unroll
+    for (int c = 0; c < CH / 4; ++c) {
+        const float4 a4 = fcw[c];
+        acc = fmaf(a4.x, __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, s), 4 * c + 0)), acc);
+        acc = fmaf(a4.y, __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, s), 4 * c + 1)), acc);
+        acc = fmaf(a4.z, __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, s), 4 * c + 2)), acc);
+        acc = fmaf(a4.w, __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, s), 4 * c + 3)), acc);
+    }
+    if (lane < C) logits[(size_t)clip * C + lane] = acc;
+    const int idx = wave_argmax_first(lane < C ? acc : -INFINITY, lane, C);
+    if (label && lane == 0) label[clip] = idx;
+}
+
 
 // DIAG = false: the product instantiation -- no activation dump, no stamps (their pointers and loops cost
 // registers and 5 KB of code even when unused).
@@ -1199,13 +1322,19 @@ __device__ __forceinline__ void block_phase(const DscnnWeights& w, float* lds, i
 // everything stays LDS-resident per tile.  Only the LAST tile needs the window's newest row, so only its wavefront 0 runs
 // the one-frame front end.  The tiles' pooled partial sums meet in global memory; the workgroup that arrives last (a
 // counter per stream) adds them in tile order, adds the ring term and runs fc + argmax.
-template <int MODE, bool DIAG = true, bool PRECONV = false, bool STREAM = false, bool CLUSTER = false>
-__global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w, const float* __restrict__ feat, int B,
+// PERSIST (batched product paths, launch_dscnn with B above the CU count): grid = CU count, workgroup g carries clips g,
+// g + grid, ... and overlaps consecutive ones.  Wavefronts 0-3, which finish block 4 first, stage the next clip's features
+// (OFF_FEAT_P) while 4-7 finish their units; one barrier closes both.  The pool + fc + argmax of the finished clip then runs
+// on wavefront NW - 1 beside the next clip's conv1, in which it has no unit.  Same units, orders and sums as one clip per
+// workgroup: the results are bit-identical.
+template <int MODE, bool DIAG = true, bool PRECONV = false, bool STREAM = false, bool CLUSTER = false, bool PERSIST = false>
+__global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, const float* __restrict__ feat, int B,
                                                            float* __restrict__ logits, int32_t* __restrict__ label,
                                                            float* __restrict__ act_arg,
                                                            unsigned long long* __restrict__ stamps_arg,
                                                            const int* __restrict__ ring_hops, StreamPush sp) {
     static_assert(!STREAM || (MODE >= 4 && !DIAG && !PRECONV), "the fused push exists for the product paths only");
+    static_assert(!PERSIST || ((MODE == 4 || MODE == 5) && !PRECONV && !STREAM), "persistent workgroups: batched product paths only");
     constexpr bool PAIR = MODE == 5;   // f16-pair arithmetic (kws_split_mfma.h): activations live in LDS in per-clip scaled units
     constexpr int NP = PAIR ? 2 : 3;
     BlockTables t1_pre{};              // PRECONV: block 1's tables between their fetch and their (PAIR: scaled) store
@@ -1214,13 +1343,13 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w, const
     unsigned long long* const stamps = DIAG ? stamps_arg : nullptr;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr bool MFMA = MODE != 0;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wv = tid >> 6;
+    const int tid_k = threadIdx.x;
+    const int lane_k = tid_k & 63, wv_k = tid_k >> 6;
 
-    // One clip per workgroup (no persistent loop: hoisting the ~400 weight addresses out of a clip
-    // loop costs more registers than the relaunch saves).
+    // One clip per workgroup, or (PERSIST) one workgroup per CU that loops over its clips: the loop body sees the weights and
+    // the thread index through opaque values once per clip, so nothing clip-invariant is hoisted into registers.
     const int cl_n = CLUSTER ? sp.cluster : 1;
-    const int clip = CLUSTER ? (int)blockIdx.x / cl_n : (int)blockIdx.x;
+    int clip = CLUSTER ? (int)blockIdx.x / cl_n : (int)blockIdx.x;  // PERSIST: the running clip
     const int cl_tile = CLUSTER ? (int)blockIdx.x - clip * cl_n : 0;
     if (clip >= B) return;
     // Rows of each stage this workgroup computes (CLUSTER; otherwise everything).  Block 4's output rows [j0, j1) need block
@@ -1235,19 +1364,69 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w, const
     // phase boundaries, KWS_DSCNN_STAMPS per clip; [14] and [15] carry the 100 MHz real-time counter
     int n_stamp = 0;
     auto stamp = [&]() {
-        if (stamps && tid == KWS_X_DSCNN_STAMP_TID) stamps[(size_t)clip * KWS_DSCNN_STAMPS + n_stamp] = __builtin_amdgcn_s_memtime();
+        if (stamps && tid_k == KWS_X_DSCNN_STAMP_TID) stamps[(size_t)clip * KWS_DSCNN_STAMPS + n_stamp] = __builtin_amdgcn_s_memtime();
         ++n_stamp;
     };
-    if (stamps && tid == KWS_X_DSCNN_STAMP_TID) stamps[(size_t)clip * KWS_DSCNN_STAMPS + KWS_DSCNN_STAMPS - 2] = __builtin_amdgcn_s_memrealtime();
-    stamp();  // 0: start
 
     constexpr bool SPLIT = MODE >= 4;
+    // PERSIST: block 1's tables are the same for every clip (3 registers for the whole loop); conv1's operands are reloaded in
+    // every block-4 tail, after the pool sums have left the registers.  The first clip is staged here.
+    BlockTables t1p{};
+    uintx4 c1p[PERSIST ? 7 : 1][NP];
+    int prev_clip = -1;         // PERSIST: the clip whose pool + fc is still to run (on wavefront NW - 1)
+    float* a_prev = nullptr;    // its pooled-means slot in the activation dump (diagnostics)
+    if constexpr (PERSIST) {
+        fetch_block_tables(w_arg, 1, tid_k, t1p);
+        if (wv_k < STAGE_WAVES) stage_features_persist<PAIR>(lds, feat, clip, tid_k);
+        load_conv1_frags(w_arg, wv_k, lane_k, c1p);
+        __syncthreads();
+    }
+    for (;;) {  // one pass unless PERSIST (the body keeps its one-clip indentation)
+    // PERSIST: every weight load of the body is clip-invariant; hoisted out of the loop they would pin hundreds of registers
+    // for the workgroup's whole life (spills).  Opaque weight pointers per clip keep each load where it is.
+    const DscnnWeights w = PERSIST ? weights_for_this_clip() : w_arg;
+    int tid = tid_k;
+    if constexpr (PERSIST) {
+        // the same for the thread index: every LDS address and mask is derived from it, and hoisted they spill.  The wavefront
+        // index stays a wave-uniform scalar: tid = 64 wv + lane with wv from a readfirstlane and lane < 64 visible.
+        int wv_l = __builtin_amdgcn_readfirstlane(wv_k), lane_l = lane_k;
+        asm volatile("" : "+s"(wv_l), "+v"(lane_l));
+        tid = (wv_l << 6) | (lane_l & 63);
+    }
+    const int lane = tid & 63, wv = tid >> 6;
+    if constexpr (PERSIST) n_stamp = 0;
+    if (stamps && tid == KWS_X_DSCNN_STAMP_TID) stamps[(size_t)clip * KWS_DSCNN_STAMPS + KWS_DSCNN_STAMPS - 2] = __builtin_amdgcn_s_memrealtime();
+    stamp();  // 0: start (PERSIST: features already staged)
+
     PwOperands<MODE> wa;            // pointwise operands of the running block
     int hops_before = 0;            // STREAM: pushes before this one
     // PAIR: exponents of the clip's scales.  kx: features; ky[n]: block n's depthwise output (true units) * 2^ky[n] < 2^15;
     // sg[n]: the units stage n's accumulators and stored output are in (sg[0]: conv1), = ky[n] + the layer's weight exponent
     int kx = 0, ky[5] = {0, 0, 0, 0, 0}, sg[5] = {0, 0, 0, 0, 0};
-    if constexpr (PRECONV) {
+    if constexpr (PERSIST) {
+        // the features were staged behind the previous barrier (block 4's tail of the previous clip, or the prologue)
+        if constexpr (PAIR) {  // scales of conv1 and block 1 exactly as below
+            const float mxf = read_stage_max(lds, 0, 1);
+            kx = pow2_exp_for(mxf);
+            const float bz0 = (w.c1_abs * mxf + w.c1_bmax) * 1.001f;
+            cap_units(kx, sg[0], w.k_c1, bz0);
+            const float by1 = (w.dw_abs[0] * bz0 + w.dw_bmax[0]) * 1.001f;
+            ky[1] = pow2_exp_for(by1);
+            cap_units(ky[1], sg[1], w.k_pw[0], (w.pw_abs[0] * by1 + w.pw_bmax[0]) * 1.001f);
+            store_block_tables(lds, 1, tid, t1p, pow2f(ky[1]), pow2f(sg[1]), pow2f(ky[1] - sg[0]));
+            conv1_build_windows(lds, tid, pow2f(kx), OFF_FEAT_P);
+            __syncthreads();
+        } else {
+            store_block_tables(lds, 1, tid, t1p);  // (read in block 1, behind conv1's barrier)
+        }
+        stamp();  // 1: scales and conv1 windows ready
+        conv1_phase_split<false, NP>(w, lds, tid, c1p, rg0, pow2f(kx), pow2f(sg[0]), OFF_FEAT_P);
+        if (wv == NW - 1 && prev_clip >= 0) {
+            pool_fc_wave(w, lds, lane, prev_clip, logits, label, a_prev);
+            if (stamps && lane == 0) stamps[(size_t)prev_clip * KWS_DSCNN_STAMPS + 13] = __builtin_amdgcn_s_memtime();
+        }
+        load_afrag(w, 1, wv >= 4 ? wv - 4 : 0, lane, wa.ring[0]);  // wavefronts 4-7: their k-block of block 1's leftover tile
+    } else if constexpr (PRECONV) {
         static_assert(!PRECONV || MODE >= 4, "the pre-convolved entry exists for the product (split) path only");
         const float* z = feat + (size_t)clip * (CH * P0);
         fetch_block_tables(w, 1, tid, t1_pre);
@@ -1307,11 +1486,7 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w, const
     float a1[SPLIT ? 1 : 50];       // conv1 weights of this wave's output-channel tile (f32 MFMA A operands)
     uintx4 c1f[SPLIT ? 7 : 1][NP];  // the same as bf16 pieces / f16 pairs (split paths)
     if constexpr (SPLIT) {
-        const uintx4* src = reinterpret_cast<const uintx4*>(PAIR ? w.c1_pair : w.c1_split) + (size_t)(wv & 1) * (7 * NP * 64) + lane;
-#pragma unroll
-        for (int kb = 0; kb < 7; ++kb)
-#pragma unroll
-            for (int p = 0; p < NP; ++p) c1f[kb][p] = src[(kb * NP + p) * 64];
+        load_conv1_frags(w, wv, lane, c1f);
     } else if constexpr (MFMA) {
         const int half = lane >> 5, col = lane & 31, ct = wv & 1;
 #pragma unroll
@@ -1490,8 +1665,27 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w, const
     if constexpr (PAIR) {
         pc.inv_out = pow2f(-sg[4]);
     }
-    block_phase<4, MODE, CLUSTER>(w, lds, tid, wa, a ? a + CH : nullptr, rg4, pc);  // block 4's output follows the pooled means
+    block_phase<4, MODE, CLUSTER>(w, lds, tid, wa, a ? a + CH : nullptr, rg4, pc,  // block 4's output follows the pooled means
+                                  PERSIST ? OFF_POOLBUF_P : OFF_POOLBUF);
     stamp();  // 10
+    if constexpr (PERSIST) {
+        // block 4's tail: the pool partials are stored; wavefronts 0-3 stage the next clip while 4-7 finish their units, and
+        // everyone requests conv1's operands (the pool sums have left the registers).  One barrier closes block 4 of this clip
+        // and the staging of the next; this clip's pool + fc runs behind it, beside the next clip's conv1.
+        const int next = clip + (int)gridDim.x;
+        __builtin_amdgcn_sched_barrier(0);
+        if (wv < STAGE_WAVES && next < B) stage_features_persist<PAIR>(lds, feat, next, tid);
+        stamp();  // 11: next clip staged (wavefront 0)
+        load_conv1_frags(w, wv, lane, c1p);  // (unconditional: a conditional reload keeps the old copy live through the whole loop)
+        __syncthreads();
+        stamp();  // 12: block 4 barrier
+        if (stamps && tid == KWS_X_DSCNN_STAMP_TID) stamps[(size_t)clip * KWS_DSCNN_STAMPS + KWS_DSCNN_STAMPS - 1] = __builtin_amdgcn_s_memrealtime();
+        prev_clip = clip;
+        a_prev = a;
+        clip = next;
+        if (clip >= B) break;
+        continue;
+    }
     // The classifier row of lane c (wavefront 0) and the ring bias of channel tid are requested BEFORE the barrier:
     // their L2 round trips pass while the workgroup waits for its slowest wavefront, instead of sitting exposed at
     // the very end of the clip (the CU cannot take its next clip before this wavefront is done).
@@ -1577,18 +1771,7 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w, const
             }
             v = acc;
         }
-        // argmax, first maximum wins: wave maximum by DPP (no LDS round trips; six dependent __shfl_xor rounds through
-        // ds_bpermute were 1.4 k of the 2.6 k cycles this tail took), then the lowest lane that holds it
-        float m = v;
-        m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, m), __builtin_bit_cast(int, m), 0x111, 0xf, 0xf, false)));
-        m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, m), __builtin_bit_cast(int, m), 0x112, 0xf, 0xf, false)));
-        m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, m), __builtin_bit_cast(int, m), 0x114, 0xf, 0xf, false)));
-        m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, m), __builtin_bit_cast(int, m), 0x118, 0xf, 0xf, false)));
-        m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, m), __builtin_bit_cast(int, m), 0x142, 0xa, 0xf, false)));
-        m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, m), __builtin_bit_cast(int, m), 0x143, 0xc, 0xf, false)));
-        const float vmax = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, m), 63));
-        const unsigned long long holders = __ballot(lane < C && v == vmax);
-        const int idx = holders ? __ffsll(holders) - 1 : 0;  // all-NaN logits: label 0
+        const int idx = wave_argmax_first(v, lane, C);
         if (label && lane == 0) label[clip] = idx;
         if constexpr (STREAM) {
             if (sp.h_label && lane == 0) __hip_atomic_store(sp.h_label + clip, idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1616,6 +1799,14 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w, const
     }
     stamp();  // 12: pool + fc + argmax done
     if (stamps && tid == KWS_X_DSCNN_STAMP_TID) stamps[(size_t)clip * KWS_DSCNN_STAMPS + KWS_DSCNN_STAMPS - 1] = __builtin_amdgcn_s_memrealtime();
+    break;
+    }
+    if constexpr (PERSIST) {  // the last clip's pool + fc (its partials are behind the loop's last barrier)
+        if (wv_k == NW - 1) {
+            pool_fc_wave(w_arg, lds, lane_k, prev_clip, logits, label, a_prev);
+            if (stamps && lane_k == 0) stamps[(size_t)prev_clip * KWS_DSCNN_STAMPS + 13] = __builtin_amdgcn_s_memtime();
+        }
+    }
 }
 
 }  // namespace
@@ -1633,7 +1824,11 @@ hipError_t dscnn_init_device() {
                              reinterpret_cast<const void*>(kws_dscnn_fwd_kernel<5>), reinterpret_cast<const void*>(kws_dscnn_fwd_kernel<5, false>),
                              reinterpret_cast<const void*>(kws_dscnn_fwd_kernel<5, false, true>),
                              reinterpret_cast<const void*>(kws_dscnn_fwd_kernel<5, false, false, true>),
-                             reinterpret_cast<const void*>(kws_dscnn_fwd_kernel<5, false, false, true, true>)};
+                             reinterpret_cast<const void*>(kws_dscnn_fwd_kernel<5, false, false, true, true>),
+                             reinterpret_cast<const void*>(kws_dscnn_fwd_kernel<4, true, false, false, false, true>),
+                             reinterpret_cast<const void*>(kws_dscnn_fwd_kernel<4, false, false, false, false, true>),
+                             reinterpret_cast<const void*>(kws_dscnn_fwd_kernel<5, true, false, false, false, true>),
+                             reinterpret_cast<const void*>(kws_dscnn_fwd_kernel<5, false, false, false, false, true>)};
     for (const void* k : kernels) {
         hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (e != hipSuccess) return e;
@@ -1712,11 +1907,25 @@ hipError_t launch_dscnn_stream(hipStream_t s, const DscnnWeights& w, const Strea
 
 hipError_t launch_dscnn(hipStream_t s, const DscnnWeights& w, const float* d_feat, int B, float* d_logits,
                         int32_t* d_label, float* d_act, int mode, unsigned long long* d_stamps, const int* d_ring_hops,
-                        bool preconv, int frames_lag) {
+                        bool preconv, int frames_lag, int n_cu) {
     const size_t lds = LDS_FLOATS * sizeof(float);
     StreamPush lag{};  // the two-launch streaming route: only the hops-per-frame count travels (the window's first row)
     lag.frames_lag = frames_lag;
     const int grid = B;  // one clip per workgroup; one workgroup per CU (160 KiB LDS)
+    // More clips than CUs on a product path: persistent workgroups, one per CU, each carrying its clips one after another
+    // (kws_dscnn_fwd_kernel, PERSIST).  The streaming route (d_ring_hops) and the pre-convolved entry keep one clip per workgroup.
+    if (n_cu > 0 && B > n_cu && !preconv && !d_ring_hops && (mode == 4 || mode == 5)) {
+        const bool diag = d_act || d_stamps;
+        if (mode == 5 && diag)
+            hipLaunchKernelGGL((kws_dscnn_fwd_kernel<5, true, false, false, false, true>), dim3(n_cu), dim3(NT), lds, s, w, d_feat, B, d_logits, d_label, d_act, d_stamps, nullptr, lag);
+        else if (mode == 5)
+            hipLaunchKernelGGL((kws_dscnn_fwd_kernel<5, false, false, false, false, true>), dim3(n_cu), dim3(NT), lds, s, w, d_feat, B, d_logits, d_label, nullptr, nullptr, nullptr, lag);
+        else if (diag)
+            hipLaunchKernelGGL((kws_dscnn_fwd_kernel<4, true, false, false, false, true>), dim3(n_cu), dim3(NT), lds, s, w, d_feat, B, d_logits, d_label, d_act, d_stamps, nullptr, lag);
+        else
+            hipLaunchKernelGGL((kws_dscnn_fwd_kernel<4, false, false, false, false, true>), dim3(n_cu), dim3(NT), lds, s, w, d_feat, B, d_logits, d_label, nullptr, nullptr, nullptr, lag);
+        return hipGetLastError();
+    }
     if (preconv) {  // d_feat = conv1 output of a multi-channel model (kws_conv1_general_kernel): product paths only
         if (mode == 5)
             hipLaunchKernelGGL((kws_dscnn_fwd_kernel<5, false, true>), dim3(grid), dim3(NT), lds, s, w, d_feat, B, d_logits, d_label, nullptr, nullptr, nullptr, StreamPush{});

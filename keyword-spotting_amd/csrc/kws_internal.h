@@ -185,7 +185,7 @@ hipError_t launch_dscnn_stream(hipStream_t s, const DscnnWeights& w, const Strea
                                float* d_logits, int32_t* d_label, bool pair);
 hipError_t launch_dscnn(hipStream_t s, const DscnnWeights& w, const float* d_feat, int B, float* d_logits,
                         int32_t* d_label, float* d_act, int mode, unsigned long long* d_stamps = nullptr,
-                        const int* d_ring_hops = nullptr, bool preconv = false, int frames_lag = 3);
+                        const int* d_ring_hops = nullptr, bool preconv = false, int frames_lag = 3, int n_cu = 0);
 // conv1 of a model with input_channels > 1: x [B][C_in][99][10] -> relu(conv1) [B][64][141]; d_wt = weights as [ci][tap][co]
 hipError_t launch_conv1_general(hipStream_t s, const float* d_x, int B, int C_in, const float* d_wt, const float* d_bias, float* d_out);
 

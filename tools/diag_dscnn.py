@@ -20,6 +20,11 @@ from kws import _native  # noqa: E402
 
 NAMES = ["stage features", "conv1 units", "conv1 barrier", "block1 units", "block1 barrier", "block2 units",
          "block2 barrier", "block3 units", "block3 barrier", "block4 units", "block4 barrier", "pool+fc"]
+# persistent workgroups (B above the CU count): the clip's features were staged in the previous clip's block-4 tail; stamp 1
+# follows the scales and conv1 windows, 11 the next clip's staging (wavefront 0), 12 the block-4 barrier; the clip's pool + fc
+# runs on the last wavefront beside the next clip's conv1 and stamps [13] when it is done
+NAMES_PERSIST = ["scales + windows", "conv1 units", "conv1 barrier", "block1 units", "block1 barrier", "block2 units",
+                 "block2 barrier", "block3 units", "block3 barrier", "block4 units", "stage next clip", "block4 barrier"]
 
 
 def main():
@@ -51,8 +56,12 @@ def main():
         clock_ghz = np.median(total / np.maximum(rt, 1)) * 0.1
         print(f"mode {mode} ({label[mode]})  B={B}  kernel {t0.elapsed_time(t1) / 5:.3f} ms  median clip lifetime "
               f"{np.median(total):.0f} cycles  clock ~{clock_ghz:.2f} GHz = {np.median(total) / clock_ghz / 1e3:.1f} us per clip per CU")
-        for i, n in enumerate(NAMES):
+        persist = bool((st[:, 13] != 0).all())
+        for i, n in enumerate(NAMES_PERSIST if persist else NAMES):
             print(f"  {n:16s} {np.median(d[:, i]):9.0f} cyc  {100 * np.median(d[:, i]) / np.median(total):5.1f} %")
+        if persist:
+            print(f"  (overlapped) pool+fc done {np.median(st[:, 13] - st[:, 12]):.0f} cyc after the block4 barrier, "
+                  f"on the last wavefront during the next clip's conv1")
     ctx.close()
 
 
