@@ -378,6 +378,53 @@ int kws_stream_smooth_f32(kws_ctx* ctx, const float* d_logits, int C, int window
 int kws_augment_i16(kws_ctx* ctx, const int16_t* d_wav, int B, const int32_t* d_shift, const float* d_bg, int bg_len,
                     const int32_t* d_bg_off, const float* d_bg_vol, const uint8_t* d_silence, float* d_out);
 
+/* ---- resident training loader: draws and features on the device ------------------------------------------
+ * Together the two entries replace the reference's per-sample transform inside DataLoader workers
+ * (kws/libs/data_loader.py:96-105 under train.py:108-121) for a split whose PCM lives in device memory. */
+
+/* The label of a silence clip (kws/common/types.py: LabelIndex.SILENCE_INDEX). */
+#define KWS_SILENCE_INDEX 0
+
+/* The four random draws of the training transform (kws/libs/audio_processor.py:151-159, 172-233) for the B dataset
+ * indices d_index int32 [B]: time shift, background file, offset inside it, volume.
+ *   Generator: Philox4x32-10, key = seed (low word, high word), counter = (dataset index, epoch, 0, 0); one call gives
+ *   a clip's four words.  A clip's draws are therefore a pure function of (seed, epoch, dataset index): they do not
+ *   depend on B, on the other clips of the batch or on the order inside it.
+ *   Word -> integer in [0, m): (uint64(u) * m) >> 32.  Word -> float in [0, 1): (u >> 8) * 2^-24.
+ *   word 0: shift uniform on the integers [-time_shift, time_shift) (0 when time_shift is 0);
+ *   word 1: file k uniform on [0, K);  word 2: offset = d_bg_start[k] + uniform on [0, d_bg_len[k] - n_samples)
+ *           (d_bg_start / d_bg_len int32 [K]: where the pool's files, already tiled beyond n_samples, begin and how long
+ *           they are);
+ *   word 3: u.  A silence clip (d_label[index] == KWS_SILENCE_INDEX; d_label int32 [N] or NULL: no silence clips) gets
+ *           volume u, uniform on [0, 1).  Any other clip gets (u / bg_frequency) * bg_volume when u < bg_frequency -- given
+ *           that, u / bg_frequency is uniform on [0, 1) again, so the volume is uniform on [0, bg_volume) with probability
+ *           bg_frequency -- else 0 (two float32 roundings: the divide, the multiply).
+ *   use_background == 0 mixes noise into silence clips only (audio_processor.py:158); such a clip's other draws, and
+ *   every clip's when K == 0, are offset 0 and volume 0.  The distributions are the reference's; its stream of numbers
+ *   (NumPy's global state per worker) is not reproducible and is not reproduced.
+ * Outputs d_shift int32 [B], d_bg_off int32 [B], d_bg_vol float32 [B], d_silence uint8 [B] have exactly the meaning of
+ * kws_augment_i16's arguments.  An index outside [0, N) reads no label.  B <= 0, a NULL index or output pointer, K > 0
+ * without its tables, time_shift < 0: KWS_EINVAL.  Asynchronous on the context stream. */
+int kws_augment_draw(kws_ctx* ctx, uint64_t seed, uint32_t epoch, const int32_t* d_index, int B, const int32_t* d_label, int N,
+                     int time_shift, const int32_t* d_bg_start, const int32_t* d_bg_len, int K, float bg_volume,
+                     float bg_frequency, int use_background, int n_samples, int32_t* d_shift, int32_t* d_bg_off,
+                     float* d_bg_vol, uint8_t* d_silence);
+
+/* Gather + augment + MFCC in one launch (plus the refinement launch): batch row b is clip d_index[b] of the resident
+ * split d_pcm int16 [N, n_samples], augmented as kws_augment_i16 would with the b-th entries of d_shift / d_bg_off /
+ * d_bg_vol / d_silence (same NULL conventions), and transformed to d_out float32 [B, 1, num_frames, numcep].  No
+ * intermediate signal reaches memory.  The result is bit-identical to gathering the rows, kws_augment_i16 and
+ * kws_mfcc_f32, refinement and kws_frontend_stats included.
+ *   Scope: KWS_FE_F32 at a geometry the wavefront-resident int16 kernel covers (the reference's: frames of 385..448
+ *   samples, n_samples and 4 * frame_step multiples of 8, d_pcm 16-byte aligned).  Anything else, KWS_FE_F64 included:
+ *   KWS_EUNSUPPORTED -- compose the three calls instead.  B <= 0, N <= 0, a NULL d_pcm / d_index / d_out, a pool without
+ *   length, offsets and volumes: KWS_EINVAL.
+ *   An index outside [0, N) is never dereferenced: row 0 is read instead and that batch row's output is unspecified.
+ * Asynchronous on the context stream. */
+int kws_mfcc_augment_i16(kws_ctx* ctx, const int16_t* d_pcm, int N, const int32_t* d_index, int B, const int32_t* d_shift,
+                         const float* d_bg, int bg_len, const int32_t* d_bg_off, const float* d_bg_vol,
+                         const uint8_t* d_silence, float* d_out);
+
 /* Diagnostics: the same forward with per-clip shader-clock stamps (s_memtime of thread 0) at the phase
  * boundaries of the DS-CNN kernel, uint64 [B, KWS_DSCNN_STAMPS]: 0 start, 1 features staged, 2/3 conv1
  * done / barrier, 4/5 .. 10/11 blocks 1..4 done / barrier, 12 end; [14], [15] = 100 MHz real-time

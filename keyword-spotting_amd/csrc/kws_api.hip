@@ -1725,6 +1725,58 @@ int kws_augment_i16(kws_ctx* c, const int16_t* d_wav, int B, const int32_t* d_sh
     return KWS_OK;
 }
 
+// ---- resident training loader -----------------------------------------------------------------------
+int kws_augment_draw(kws_ctx* c, uint64_t seed, uint32_t epoch, const int32_t* d_index, int B, const int32_t* d_label, int N,
+                     int time_shift, const int32_t* d_bg_start, const int32_t* d_bg_len, int K, float bg_volume,
+                     float bg_frequency, int use_background, int n_samples, int32_t* d_shift, int32_t* d_bg_off,
+                     float* d_bg_vol, uint8_t* d_silence) {
+    int rc = check_batch(c, d_index, B, "kws_augment_draw");
+    if (rc) return rc;
+    if (!d_shift || !d_bg_off || !d_bg_vol || !d_silence) return fail(c, KWS_EINVAL, "kws_augment_draw: an output pointer is NULL");
+    if (K < 0 || (K > 0 && (!d_bg_start || !d_bg_len))) return fail(c, KWS_EINVAL, "kws_augment_draw: K files need their start and length tables");
+    if (time_shift < 0 || time_shift > (1 << 30)) return fail(c, KWS_EINVAL, "kws_augment_draw: time_shift must be in [0, 2^30]");
+    if (N < 0 || n_samples < 0) return fail(c, KWS_EINVAL, "kws_augment_draw: N and n_samples must not be negative");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const kws::DrawArgs d = {seed, epoch, d_index, d_label, N, time_shift, d_bg_start, d_bg_len, K, bg_volume, bg_frequency,
+                             use_background, n_samples, d_shift, d_bg_off, d_bg_vol, d_silence};
+    HIP_TRY(c, kws::launch_augment_draw(c->stream, d, B));
+    return KWS_OK;
+}
+
+int kws_mfcc_augment_i16(kws_ctx* c, const int16_t* d_pcm, int N, const int32_t* d_index, int B, const int32_t* d_shift,
+                         const float* d_bg, int bg_len, const int32_t* d_bg_off, const float* d_bg_vol,
+                         const uint8_t* d_silence, float* d_out) {
+    int rc = check_batch(c, d_pcm, B, "kws_mfcc_augment_i16");
+    if (rc) return rc;
+    if (!d_index || !d_out) return fail(c, KWS_EINVAL, "kws_mfcc_augment_i16: d_index or d_out is NULL");
+    if (N <= 0) return fail(c, KWS_EINVAL, "kws_mfcc_augment_i16: N must be positive");
+    if (d_bg && (bg_len <= 0 || !d_bg_off || !d_bg_vol)) return fail(c, KWS_EINVAL, "kws_mfcc_augment_i16: background pool needs length, offsets and volumes");
+    if (!c->fe_ready) return fail(c, KWS_ESTATE, "kws_mfcc_augment_i16: front end not configured");
+    FrontendParams p = c->fp;
+    if ((reinterpret_cast<uintptr_t>(d_pcm) & 15) != 0) p.vec_ok = 0;
+    if (c->fe_math == KWS_FE_F64 || !c->fe_fast_ok || !kws::mfcc_wave_resident_ok(p))
+        return fail(c, KWS_EUNSUPPORTED, "kws_mfcc_augment_i16: needs KWS_FE_F32 at a geometry of the wavefront-resident kernel and 16-byte "
+                                         "aligned PCM; compose kws_augment_i16 and kws_mfcc_f32 instead");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const kws::AugmentArgs a = {d_pcm, d_index, N, d_shift, d_bg, bg_len, d_bg_off, d_bg_vol, d_silence};
+    c->frames_seen += (unsigned long long)B * p.num_frames;
+    kws::RefineList rl{};
+    if (p.refine_span > 0.f) {
+        rc = ensure_refine(c, B);
+        if (rc) return rc;
+        rl = {c->d_refine, c->d_refine + 8, c->refine_cap, 0};
+    }
+    {
+        ProfScope ps(c, KWS_K_MFCC);
+        HIP_TRY(c, kws::launch_mfcc_augment_flag(c->stream, p, c->ft, a, B, d_out, rl));
+    }
+    if (p.refine_span > 0.f) {
+        ProfScope ps(c, KWS_K_MFCC_REFINE);
+        HIP_TRY(c, kws::launch_mfcc_refine_augment(c->stream, p, c->ft, a, d_out, rl, B));
+    }
+    return KWS_OK;
+}
+
 // ---- sigproc operators --------------------------------------------------------------------------
 int kws_preemphasis_f32(kws_ctx* c, const float* d_signal, int n, float coeff, float* d_out) {
     int rc = check_batch(c, d_signal, n, "kws_preemphasis_f32");

@@ -121,6 +121,43 @@ hipError_t launch_stream_frame(hipStream_t s, const FrontendParams& p, const Fro
 hipError_t launch_augment(hipStream_t s, const int16_t* d_wav, int B, int n, const int32_t* d_shift, const float* d_bg,
                           int bg_len, const int32_t* d_bg_off, const float* d_bg_vol, const uint8_t* d_silence,
                           float* d_out);
+// The resident training loader (kws_augment_draw, kws_mfcc_augment_i16): batch row b is clip index[b] of the split,
+// augmented with the b-th draws -- the arguments of launch_augment, gathered.
+struct AugmentArgs {
+    const int16_t* pcm;       // [n_rows][n_samples]  the resident split
+    const int32_t* index;     // [B]  dataset indices
+    int n_rows;
+    const int32_t* shift;     // [B] or nullptr
+    const float* bg;          // [bg_len] background pool or nullptr
+    int bg_len;
+    const int32_t* bg_off;    // [B]
+    const float* bg_vol;      // [B]
+    const uint8_t* silence;   // [B] or nullptr
+};
+struct DrawArgs {
+    unsigned long long seed;
+    unsigned epoch;
+    const int32_t* index;     // [B]
+    const int32_t* label;     // [n_rows] or nullptr
+    int n_rows, time_shift;
+    const int32_t* bg_start;  // [n_files]
+    const int32_t* bg_len;    // [n_files]
+    int n_files;
+    float bg_volume, bg_frequency;
+    int use_background, n_samples;
+    int32_t* shift;           // [B]
+    int32_t* bg_off;          // [B]
+    float* bg_vol;            // [B]
+    uint8_t* silence;         // [B]
+};
+hipError_t launch_augment_draw(hipStream_t s, const DrawArgs& d, int B);
+// true: launch_mfcc_flag picks the wavefront-resident kernel for this geometry (the fused kernel is a variant of it)
+bool mfcc_wave_resident_ok(const FrontendParams& p);
+// gather + augment + float32 MFCC in one launch (wavefront-resident geometry only), and the refinement of its flagged frames
+hipError_t launch_mfcc_augment_flag(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const AugmentArgs& a, int B,
+                                    float* d_out, const RefineList& rl);
+hipError_t launch_mfcc_refine_augment(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const AugmentArgs& a,
+                                      float* d_out, const RefineList& rl, int B);
 hipError_t launch_preemphasis(hipStream_t s, const float* d_in, int n, float coeff, float* d_out);
 hipError_t launch_framesig(hipStream_t s, const float* d_in, int n, int frame_len, int frame_step,
                            int num_frames, const float* d_window, float* d_frames);

@@ -24,6 +24,7 @@
 // (tolerance 1e-4 on MFCC, see tests/test_gpu_parity.py).
 #include <cstdlib>
 
+#include "kws_augment_dev.h"
 #include "kws_internal.h"
 #include "kws_mfcc_dev.h"
 
@@ -212,13 +213,73 @@ constexpr int WR_PAIRS = 2, WR_FRAMES = 2 * WR_PAIRS;   // frames per chunk
 constexpr int WR_SPAN = 1024;                            // floats of LDS per wavefront for the chunk's span (two uint4 of PCM per lane)
 constexpr int WR_WAVE_BYTES = WR_SPAN * 4 + SCR_BYTES;
 
+// Eight consecutive augmented samples n0 .. n0 + 7 (n0 a multiple of 8) of a clip of the resident split, the values aug_sample
+// gives one by one.  The source run starts at j0 = n0 - shift, aligned to 2 bytes only: the two ALIGNED 16-byte vectors that
+// hold it are read -- each lies wholly inside the clip's own row or is replaced by zeros (n_samples % 8 == 0), so nothing
+// outside the row is touched and positions outside [0, n) contribute zeros -- and funnelled by j0 mod 8 half-words.  That
+// amount is wave-uniform (every n0 of a wavefront is a multiple of 8), so the word selects take scalar conditions.  The
+// background term is a float32 stream at 4-byte alignment: two 16-byte loads when the eight samples lie inside the pool.
+typedef float float4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+__device__ __forceinline__ void aug_vec8(const AugClip& c, int n0, int n, float (&a)[8]) {
+    if (n0 + 8 > n) {  // past the clip: the caller zeroes the pre-emphasised samples
+#pragma unroll
+        for (int i = 0; i < 8; ++i) a[i] = 0.f;
+        return;
+    }
+    const int r = uniform_i(-c.shift & 7);  // = (n0 - shift) mod 8
+    const int base = n0 - c.shift - r;      // a multiple of 8, possibly negative
+    uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
+    if (!c.silence) {
+        if (base >= 0 && base + 8 <= n) lo = *reinterpret_cast<const uint4*>(c.x + base);
+        if (base + 8 >= 0 && base + 16 <= n) hi = *reinterpret_cast<const uint4*>(c.x + base + 8);
+    }
+    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    // word shift by r / 2 as two levels of bit selects under scalar masks (ternaries on the words turn into one dynamically
+    // indexed array in private memory with this compiler)
+    const uint32_t m2 = (r & 4) ? ~0u : 0u, m1 = (r & 2) ? ~0u : 0u;
+    uint32_t u[6], v[5];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) u[k] = (w[k + 2] & m2) | (w[k] & ~m2);
+#pragma unroll
+    for (int k = 0; k < 5; ++k) v[k] = (u[k + 1] & m1) | (u[k] & ~m1);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t wd = (r & 1) ? __builtin_amdgcn_alignbyte(v[k + 1], v[k], 2) : v[k];
+        a[2 * k] = pcm_unit((int16_t)(wd & 0xffffu));
+        a[2 * k + 1] = pcm_unit((int16_t)(wd >> 16));
+    }
+    if (c.bg) {
+        const int k0 = c.off + n0;
+        float g[8];
+        if (k0 >= 0 && k0 + 8 <= c.bg_len) {
+            const float4_a4 g0 = *reinterpret_cast<const float4_a4*>(c.bg + k0);
+            const float4_a4 g1 = *reinterpret_cast<const float4_a4*>(c.bg + k0 + 4);
+            g[0] = g0.x, g[1] = g0.y, g[2] = g0.z, g[3] = g0.w, g[4] = g1.x, g[5] = g1.y, g[6] = g1.z, g[7] = g1.w;
+        } else {  // an offset that leaves the pool (never one of kws_augment_draw's): zeros outside it, as kws_augment_i16 reads them
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int k = c.off + n0 + i;
+                g[i] = (k >= 0 && k < c.bg_len) ? c.bg[k] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) a[i] = __fadd_rn(a[i], __fmul_rn(g[i], c.vol));
+    }
+}
+
 __host__ __device__ inline size_t mfcc_wr_lds_bytes(const FrontendParams& p) {
     const int nfp = (p.nfilt + 3) & ~3;
     return sizeof(float) * (size_t)(((p.numcep * nfp + 3) & ~3) + 2 * 64) + (size_t)MFCC_WAVES * WR_WAVE_BYTES;
 }
 
-__global__ __launch_bounds__(MFCC_THREADS) __attribute__((amdgpu_waves_per_eu(KWS_MFCC_EU, KWS_MFCC_EU))) void kws_mfcc_i16_kernel(
-    FrontendParams p, FrontendTables t, const int16_t* __restrict__ wav, float* __restrict__ out, RefineList rl, int B, int chunks_per_wave) {
+// The body of the wavefront-resident kernels.  AUG (kws_mfcc_augment_i16_kernel, the resident training loader): the same run of
+// chunks, LDS map and mfcc_pair; only the way a chunk's samples reach the registers differs -- see aug_vec8 above.  Every AUG
+// branch is an if constexpr: the plain instantiation keeps the instruction sequence kws_mfcc_i16_kernel had as a kernel of
+// its own (register names apart).
+template <bool AUG>
+__device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t, const int16_t* __restrict__ wav,
+                                             float* __restrict__ out, RefineList rl, int B, int chunks_per_wave,
+                                             AugmentArgs aug) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int nfp = (p.nfilt + 3) & ~3;
     float* dctb = reinterpret_cast<float*>(smem);
@@ -245,7 +306,9 @@ __global__ __launch_bounds__(MFCC_THREADS) __attribute__((amdgpu_waves_per_eu(KW
     int c = part * chunks_per_wave;
     const int c_end = min(n_chunks, c + chunks_per_wave);
     const bool active = clip < B && c < c_end;  // wave-uniform
-    const int16_t* __restrict__ x = wav + (size_t)(active ? clip : 0) * p.n_samples;
+    const int16_t* __restrict__ x = AUG ? nullptr : wav + (size_t)(active ? clip : 0) * p.n_samples;
+    AugClip ac{};
+    if constexpr (AUG) ac = aug_clip(aug, active ? clip : 0, p.n_samples);  // wave-uniform: scalar registers
     const int chunk_step = WR_FRAMES * p.frame_step;  // samples from one chunk's span to the next (a multiple of 8: checked by the launcher)
 
     // two 16-byte vectors of PCM per lane cover the span; a vector is inside the clip or past its end (n_samples % 8 == 0)
@@ -258,8 +321,9 @@ __global__ __launch_bounds__(MFCC_THREADS) __attribute__((amdgpu_waves_per_eu(KW
         v1 = n1 + 8 <= p.n_samples ? *reinterpret_cast<const uint4*>(x + n1) : make_uint4(0, 0, 0, 0);
         before = s0 > 0 ? x[s0 - 1] : (int16_t)0;
     };
+    (void)fetch;
 #ifdef KWS_X_MFCC_PREFETCH
-    if (active) fetch(c);
+    if (!AUG && active) fetch(c);
 #endif
     __syncthreads();  // the only workgroup barrier: the shared tables are in place
     if (!active) return;
@@ -289,10 +353,38 @@ __global__ __launch_bounds__(MFCC_THREADS) __attribute__((amdgpu_waves_per_eu(KW
     }
     for (; c < c_end; ++c) {
 #ifndef KWS_X_MFCC_PREFETCH
-        fetch(c);
+        if constexpr (!AUG) fetch(c);
 #endif
         // ---- registers -> float32, pre-emphasised, into this wavefront's span buffer -----------------------
-        {
+        if constexpr (AUG) {
+            const int s0 = c * chunk_step;
+            float a0[8], a1[8];
+            aug_vec8(ac, s0 + 8 * lane, p.n_samples, a0);
+            aug_vec8(ac, s0 + 512 + 8 * lane, p.n_samples, a1);
+            // the sample before a lane's vector is an AUGMENTED sample too: the neighbouring lane's last one (wave_shr:1), lane 63's
+            // first vector for lane 0's second, the clip's sample s0 - 1 for lane 0's first
+            const float w0 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a0[7]), 0x138, 0xf, 0xf, false));
+            const float w1 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a1[7]), 0x138, 0xf, 0xf, false));
+            const float last0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a0[7]), 63));
+            const float before_a = s0 > 0 ? aug_sample(ac, s0 - 1, p.n_samples) : 0.f;
+            auto emphasise = [&](const float (&a)[8], float prev, int n, float* dst) {
+                float y[8];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    y[i] = __fsub_rn(a[i], __fmul_rn(pre, prev));
+                    prev = a[i];
+                }
+                if (n == 0) y[0] = a[0];       // the clip's first sample is not pre-emphasised
+                if (n + 8 > p.n_samples) {     // past the clip: psf pads the PRE-EMPHASISED signal with zeros
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) y[i] = 0.f;
+                }
+                reinterpret_cast<float4*>(dst)[0] = make_float4(y[0], y[1], y[2], y[3]);
+                reinterpret_cast<float4*>(dst)[1] = make_float4(y[4], y[5], y[6], y[7]);
+            };
+            emphasise(a0, lane == 0 ? before_a : w0, s0 + 8 * lane, ybuf + 8 * lane);
+            emphasise(a1, lane == 0 ? last0 : w1, s0 + 512 + 8 * lane, ybuf + 512 + 8 * lane);
+        } else {
             const int s0 = c * chunk_step;
             // the sample before a lane's vector: the last half-word of the neighbouring lane's vector (wave_shr:1), of lane 63's
             // first vector for lane 0's second, of the clip for lane 0's first
@@ -323,7 +415,7 @@ __global__ __launch_bounds__(MFCC_THREADS) __attribute__((amdgpu_waves_per_eu(KW
         }
         wave_lds_order();
 #ifdef KWS_X_MFCC_PREFETCH  // (experiment, see the header comment: the prefetched vectors spill under the 128-register cap)
-        if (c + 1 < c_end) fetch(c + 1);
+        if (!AUG && c + 1 < c_end) fetch(c + 1);
 #endif
 #pragma unroll 1
         for (int pr = 0; pr < WR_PAIRS; ++pr) {
@@ -368,6 +460,18 @@ __global__ __launch_bounds__(MFCC_THREADS) __attribute__((amdgpu_waves_per_eu(KW
     }
     KWS_FLUSH_FLAGS()
 #undef KWS_FLUSH_FLAGS
+}
+
+__global__ __launch_bounds__(MFCC_THREADS) __attribute__((amdgpu_waves_per_eu(KWS_MFCC_EU, KWS_MFCC_EU))) void kws_mfcc_i16_kernel(
+    FrontendParams p, FrontendTables t, const int16_t* __restrict__ wav, float* __restrict__ out, RefineList rl, int B, int chunks_per_wave) {
+    mfcc_wr_body<false>(p, t, wav, out, rl, B, chunks_per_wave, AugmentArgs{});
+}
+#ifndef KWS_MFCC_AUG_EU
+#define KWS_MFCC_AUG_EU 4
+#endif
+__global__ __launch_bounds__(MFCC_THREADS) __attribute__((amdgpu_waves_per_eu(KWS_MFCC_AUG_EU, KWS_MFCC_AUG_EU))) void kws_mfcc_augment_i16_kernel(
+    FrontendParams p, FrontendTables t, AugmentArgs aug, float* __restrict__ out, RefineList rl, int B, int chunks_per_wave) {
+    mfcc_wr_body<true>(p, t, nullptr, out, rl, B, chunks_per_wave, aug);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -480,7 +584,59 @@ __global__ void kws_augment_i16_kernel(const int16_t* __restrict__ wav, int B, i
     }
 }
 
+// The four random draws of the training transform (kws/libs/audio_processor.py:172-233) for a batch of dataset indices, made
+// on the device.  Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11), key = the 64-bit seed,
+// counter = (dataset index, epoch, 0, 0): one call yields the four words of a clip, so a clip's draws are a pure function of
+// (seed, epoch, dataset index) -- whatever the batch size, the other clips of the batch or the order inside it.
+__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+        c[0] = n0, c[1] = lo1, c[2] = n2, c[3] = lo0;
+        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+    }
+}
+// word -> integer in [0, m): (u * m) >> 32; word -> float in [0, 1): (u >> 8) * 2^-24, exact in float32
+__device__ __forceinline__ int draw_below(uint32_t u, int m) { return (int)(((unsigned long long)u * (unsigned)m) >> 32); }
+__device__ __forceinline__ float draw_unit(uint32_t u) { return (float)(u >> 8) * (1.0f / 16777216.0f); }
+
+__global__ void kws_augment_draw_kernel(DrawArgs d, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int idx = d.index[b];
+    uint32_t w[4] = {(uint32_t)idx, d.epoch, 0u, 0u};
+    philox4x32_10(w, (uint32_t)d.seed, (uint32_t)(d.seed >> 32));
+    const bool in_split = (unsigned)idx < (unsigned)d.n_rows;  // a label outside the split is never read
+    const bool sil = d.label && in_split && d.label[idx] == KWS_SILENCE_INDEX;
+    // time shift: uniform on the integers [-S, S) (np.random.randint(-S, S), :174)
+    d.shift[b] = d.time_shift > 0 ? draw_below(w[0], 2 * d.time_shift) - d.time_shift : 0;
+    int off = 0;
+    float vol = 0.f;
+    if (d.n_files > 0 && (d.use_background || sil)) {  // (:158: without use_background_noise only silence clips get noise)
+        const int k = draw_below(w[1], d.n_files);       // random.choice(background_data), :205
+        const int room = d.bg_len[k] - d.n_samples;      // np.random.randint(0, len - n), :214 (the pool's files are tiled beyond n)
+        off = d.bg_start[k] + (room > 0 ? draw_below(w[2], room) : 0);
+        // the reference draws a Bernoulli(background_frequency) variable and then the volume (:218-223); the one word left serves
+        // both: u < frequency decides, and given that, u / frequency is again uniform on [0, 1)
+        const float u = draw_unit(w[3]);
+        if (sil)
+            vol = u;
+        else if (u < d.bg_frequency)
+            vol = __fmul_rn(__fdiv_rn(u, d.bg_frequency), d.bg_volume);
+    }
+    d.bg_off[b] = off;
+    d.bg_vol[b] = vol;
+    d.silence[b] = sil ? 1 : 0;
+}
+
 }  // namespace
+
+hipError_t launch_augment_draw(hipStream_t s, const DrawArgs& d, int B) {
+    hipLaunchKernelGGL(kws_augment_draw_kernel, dim3((B + 255) / 256), dim3(256), 0, s, d, B);
+    return hipGetLastError();
+}
 
 // ------------------------------------------------------------------------------------------------
 size_t mfcc_lds_bytes(const FrontendParams& p) {
@@ -509,30 +665,41 @@ static hipError_t launch_mfcc_t(K kernel, hipStream_t s, const FrontendParams& p
     return hipGetLastError();
 }
 
+// the wavefront-resident kernel: 16-byte PCM vectors (aligned clips and chunk starts), a chunk's span within two vectors per lane
+bool mfcc_wave_resident_ok(const FrontendParams& p) {
+    const bool tail6 = p.frame_len > 384 && p.frame_len <= 448;
+    return tail6 && p.vec_ok && (WR_FRAMES * p.frame_step) % 8 == 0 && (WR_FRAMES - 1) * p.frame_step + 448 <= WR_SPAN;
+}
+
+// Chunks per wavefront of the wavefront-resident kernels for a launch of nb clips.
+// ~5 chunks (20 frames) per wavefront, split evenly (99 frames = 25 chunks = 5 x 5): measured on 4096 clips, 1 / 5 / 25
+// chunks per wavefront take 0.219 / 0.183 / 0.201 ms -- short-lived wavefronts keep the CUs' phases mixed and the tail
+// short, an uneven split (6 + 6 + 6 + 6 + 1: 0.209 ms) wastes a wavefront's set-up on one chunk.  Small batches spread
+// a clip over more wavefronts, down to one chunk each, so that even one clip uses 25 wavefronts.
+static int mfcc_wr_chunks_per_wave(int nb, int n_chunks) {
+    int wpc = (n_chunks + 2) / 5;
+    wpc = wpc < 1 ? 1 : wpc;
+    int cpw = (n_chunks + wpc - 1) / wpc;
+    const int fill = (int)(((long)nb * n_chunks + 4095) / 4096);  // chunks per wavefront that still fill 256 CUs x 16 wavefronts
+    cpw = cpw > fill ? (fill < 1 ? 1 : fill) : cpw;
+    static const int cpw_env = [] {  // experiment hook, read once (profiles/r03_mfcc_ab.txt: the chunks-per-wavefront scan)
+        const char* e = getenv("KWS_X_MFCC_CPW");
+        return e ? atoi(e) : 0;
+    }();
+    if (cpw_env > 0) cpw = cpw_env > 16 ? 16 : cpw_env;
+    return cpw;
+}
+
 hipError_t launch_mfcc_flag(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_wav, int B,
                             float* d_out, const RefineList& rl) {
     const bool tail6 = p.frame_len > 384 && p.frame_len <= 448;
 #ifndef KWS_X_MFCC_TILE_KERNEL  // (A/B switch: the round-2 tile kernel for every geometry)
-    // the wavefront-resident kernel: 16-byte PCM vectors (aligned clips and chunk starts), a chunk's span within two vectors per lane
-    if (tail6 && p.vec_ok && (WR_FRAMES * p.frame_step) % 8 == 0 && (WR_FRAMES - 1) * p.frame_step + 448 <= WR_SPAN) {
+    if (mfcc_wave_resident_ok(p)) {
         const size_t lds = mfcc_wr_lds_bytes(p);
         const int n_chunks = (p.num_frames + WR_FRAMES - 1) / WR_FRAMES;
         for (int b0 = 0; b0 < B; b0 += (1 << 20)) {  // (grid.x limit: 2^31 workgroups; a million clips per launch keeps indices in 32 bits)
             const int nb = B - b0 < (1 << 20) ? B - b0 : (1 << 20);
-            // ~5 chunks (20 frames) per wavefront, split evenly (99 frames = 25 chunks = 5 x 5): measured on 4096 clips, 1 / 5 / 25
-            // chunks per wavefront take 0.219 / 0.183 / 0.201 ms -- short-lived wavefronts keep the CUs' phases mixed and the tail
-            // short, an uneven split (6 + 6 + 6 + 6 + 1: 0.209 ms) wastes a wavefront's set-up on one chunk.  Small batches spread
-            // a clip over more wavefronts, down to one chunk each, so that even one clip uses 25 wavefronts.
-            int wpc = (n_chunks + 2) / 5;
-            wpc = wpc < 1 ? 1 : wpc;
-            int cpw = (n_chunks + wpc - 1) / wpc;
-            const int fill = (int)(((long)nb * n_chunks + 4095) / 4096);  // chunks per wavefront that still fill 256 CUs x 16 wavefronts
-            cpw = cpw > fill ? (fill < 1 ? 1 : fill) : cpw;
-            static const int cpw_env = [] {  // experiment hook, read once (profiles/r03_mfcc_ab.txt: the chunks-per-wavefront scan)
-                const char* e = getenv("KWS_X_MFCC_CPW");
-                return e ? atoi(e) : 0;
-            }();
-            if (cpw_env > 0) cpw = cpw_env > 16 ? 16 : cpw_env;
+            const int cpw = mfcc_wr_chunks_per_wave(nb, n_chunks);
             const int waves_per_clip = (n_chunks + cpw - 1) / cpw;
             const long waves = (long)nb * waves_per_clip;
             RefineList r = rl;
@@ -544,6 +711,31 @@ hipError_t launch_mfcc_flag(hipStream_t s, const FrontendParams& p, const Fronte
     }
 #endif
     return launch_mfcc_t(tail6 ? kws_mfcc_i16_tile_kernel : kws_mfcc_i16_any_kernel, s, p, t, d_wav, B, d_out, rl);
+}
+
+// The fused loader kernel: the same launch shape as kws_mfcc_i16_kernel; the per-clip arrays advance with the launch's first clip.
+hipError_t launch_mfcc_augment_flag(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const AugmentArgs& a, int B,
+                                    float* d_out, const RefineList& rl) {
+    if (!mfcc_wave_resident_ok(p)) return hipErrorInvalidValue;  // refused by kws_mfcc_augment_i16 before it gets here
+    const size_t lds = mfcc_wr_lds_bytes(p);
+    const int n_chunks = (p.num_frames + WR_FRAMES - 1) / WR_FRAMES;
+    for (int b0 = 0; b0 < B; b0 += (1 << 20)) {
+        const int nb = B - b0 < (1 << 20) ? B - b0 : (1 << 20);
+        const int cpw = mfcc_wr_chunks_per_wave(nb, n_chunks);
+        const int waves_per_clip = (n_chunks + cpw - 1) / cpw;
+        const long waves = (long)nb * waves_per_clip;
+        RefineList r = rl;
+        r.clip0 = b0;
+        AugmentArgs ab = a;
+        ab.index += b0;
+        if (ab.shift) ab.shift += b0;
+        if (ab.bg_off) ab.bg_off += b0;
+        if (ab.bg_vol) ab.bg_vol += b0;
+        if (ab.silence) ab.silence += b0;
+        hipLaunchKernelGGL(kws_mfcc_augment_i16_kernel, dim3((unsigned)((waves + MFCC_WAVES - 1) / MFCC_WAVES)), dim3(MFCC_THREADS), lds, s, p,
+                           t, ab, d_out + (size_t)b0 * p.num_frames * p.numcep, r, nb, cpw);
+    }
+    return hipGetLastError();
 }
 hipError_t launch_mfcc_f32_flag(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, int B,
                                 float* d_out, const RefineList& rl) {

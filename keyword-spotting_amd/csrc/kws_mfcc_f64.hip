@@ -17,6 +17,9 @@
 //   any other nfft (<= 2048):       direct DFT, each lane a bin, twiddles W^(n k mod nfft) from an LDS copy of the table
 // then |X|^2/nfft, frame energy, the triangular mel filters evaluated from psf's bin edges (weights formed in float64
 // exactly as psf's get_filterbanks does), eps floors, log, DCT-II(ortho) x lifter from a float64 table, c0 = log(energy).
+#include <type_traits>
+
+#include "kws_augment_dev.h"
 #include "kws_internal.h"
 #include "kws_mfcc_f64_dev.h"
 
@@ -125,9 +128,12 @@ __global__ __launch_bounds__(F64_MAX_WAVES * 64) void kws_mfcc_f64_kernel(Fronte
 #define KWS_X_REFINE_WAVES 12
 #endif
 constexpr int REFINE_WAVES = KWS_X_REFINE_WAVES;  // wavefronts per workgroup of the refinement kernel
-template <typename T>
-__global__ __launch_bounds__(REFINE_WAVES * 64) void kws_mfcc_refine_kernel(FrontendParams p, FrontendTables t, const T* __restrict__ wav,
-                                                                         float* __restrict__ out, RefineList rl) {
+// SrcOf: batch row -> the source of that clip's samples.  A pointer to them (int16 PCM or float32: the kernels of kws_mfcc_i16 /
+// kws_mfcc_f32), or the augmented view of a clip of the resident split (kws_mfcc_augment_i16): the refinement then re-creates
+// the float32 samples the fused kernel transformed through the same per-sample function, aug_sample.
+template <typename SrcOf>
+__device__ __forceinline__ void mfcc_refine_body(const FrontendParams& p, const FrontendTables& t, float* __restrict__ out,
+                                                 const RefineList& rl, SrcOf src_of) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem64[];
     constexpr int NCT = 512;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -154,9 +160,18 @@ __global__ __launch_bounds__(REFINE_WAVES * 64) void kws_mfcc_refine_kernel(Fron
 #ifdef KWS_X_REFINE_SINGLE
             has_b = false;  // timing experiment: wrong rows for frame b
 #endif
-            const T* __restrict__ x = wav + (size_t)clip * p.n_samples;
+            const auto x = src_of(clip);
             const long sa = (long)fa * p.frame_step;
-            f64_load_pair<T, NCT>(p, x, sa, x, sa + p.frame_step, has_b, X, NCT, n_used, lane, nza, nzb);
+            if constexpr (std::is_pointer<decltype(x)>::value) {
+                f64_load_pair<typename std::remove_cv<typename std::remove_pointer<decltype(x)>::type>::type, NCT>(
+                    p, x, sa, x, sa + p.frame_step, has_b, X, NCT, n_used, lane, nza, nzb);
+            } else {
+                nza = nzb = false;
+                f64_fill_pair<NCT>(p, x, sa, x, sa + p.frame_step, has_b, X, NCT, n_used, lane, nza, nzb);
+                nza = __any(nza);
+                nzb = __any(nzb);
+                wave_order();
+            }
         };
 #ifndef KWS_X_REFINE_LATE_FETCH
         if (e < n) fetch();
@@ -195,6 +210,16 @@ __global__ __launch_bounds__(REFINE_WAVES * 64) void kws_mfcc_refine_kernel(Fron
         rl.ctr[1] = 0;
         rl.ctr[0] = 0;
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(REFINE_WAVES * 64) void kws_mfcc_refine_kernel(FrontendParams p, FrontendTables t, const T* __restrict__ wav,
+                                                                         float* __restrict__ out, RefineList rl) {
+    mfcc_refine_body(p, t, out, rl, [&](int clip) -> const T* { return wav + (size_t)clip * p.n_samples; });
+}
+__global__ __launch_bounds__(REFINE_WAVES * 64) void kws_mfcc_refine_augment_kernel(FrontendParams p, FrontendTables t, AugmentArgs aug,
+                                                                                 float* __restrict__ out, RefineList rl) {
+    mfcc_refine_body(p, t, out, rl, [&](int clip) { return aug_clip(aug, clip, p.n_samples); });
 }
 
 // magspec / powspec for any NFFT (kws/libs/speech_features/sigproc.py:55-90): frames float32 [num_frames][frame_len]
@@ -276,11 +301,10 @@ hipError_t launch_mfcc_f64_t(hipStream_t s, const FrontendParams& p, const Front
 #define KWS_X_REFINE_GRID 256
 #endif
 constexpr int REFINE_GRID = KWS_X_REFINE_GRID;
-template <typename T>
-hipError_t launch_mfcc_refine_t(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const T* d_wav, float* d_out,
+template <typename K, typename In>
+hipError_t launch_mfcc_refine_t(K kernel, hipStream_t s, const FrontendParams& p, const FrontendTables& t, const In& d_wav, float* d_out,
                                 const RefineList& rl, int B) {
     const size_t lds = f64_layout(512, true, true, p.nfilt, p.numcep, REFINE_WAVES).total;
-    auto kernel = kws_mfcc_refine_kernel<T>;
     hipError_t e = raise_lds_limit(kernel, lds);
     if (e != hipSuccess) return e;
     // workgroups cost time even when they leave at once (~3.5 us per 256 of them): a small batch, whose list is short in
@@ -295,11 +319,15 @@ hipError_t launch_mfcc_refine_t(hipStream_t s, const FrontendParams& p, const Fr
 
 hipError_t launch_mfcc_refine(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_wav, float* d_out,
                               const RefineList& rl, int B) {
-    return launch_mfcc_refine_t(s, p, t, d_wav, d_out, rl, B);
+    return launch_mfcc_refine_t(kws_mfcc_refine_kernel<int16_t>, s, p, t, d_wav, d_out, rl, B);
 }
 hipError_t launch_mfcc_refine_f32in(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, float* d_out,
                                     const RefineList& rl, int B) {
-    return launch_mfcc_refine_t(s, p, t, d_wav, d_out, rl, B);
+    return launch_mfcc_refine_t(kws_mfcc_refine_kernel<float>, s, p, t, d_wav, d_out, rl, B);
+}
+hipError_t launch_mfcc_refine_augment(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const AugmentArgs& a,
+                                      float* d_out, const RefineList& rl, int B) {
+    return launch_mfcc_refine_t(kws_mfcc_refine_augment_kernel, s, p, t, a, d_out, rl, B);
 }
 
 hipError_t launch_mfcc_f64(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_wav, int B, float* d_out) {

@@ -220,6 +220,23 @@ __device__ __forceinline__ void spectrum_pair(d2* X, d2* P, const d2* tw_lds, in
 }
 
 
+// One sample per lane and step: the route of every source without 16-byte PCM vectors.  Src is anything preemph_sample takes:
+// a pointer to the clip's samples, or the augmented view of a resident clip (kws_augment_dev.h: AugClip).
+template <int NCT, typename Src>
+__device__ __forceinline__ void f64_fill_pair(const FrontendParams& p, const Src& xa, long sa, const Src& xb, long sb, bool has_b, d2* X,
+                                              int nfft, int n_used, int lane, bool& nza, bool& nzb) {
+    lane_loop<NCT>(lane, nfft, [&](int n) {
+        double a = 0.0, b = 0.0;
+        if (n < n_used) {
+            a = (double)preemph_sample(xa, sa + n, p.n_samples, p.preemph);
+            if (has_b) b = (double)preemph_sample(xb, sb + n, p.n_samples, p.preemph);
+        }
+        nza |= a != 0.0;
+        nzb |= b != 0.0;
+        X[NCT == 512 ? sw512(n) : n] = d2{a, b};
+    });
+}
+
 // Samples of the frame pair (frame a = samples [sa, sa + frame_len) of clip xa, frame b likewise; pre-emphasised in float32
 // as NumPy does, zero beyond the frame and the clip) -> X[n] = (a[n], b[n]), n < nfft.  Returns through nza / nzb whether
 // the frames hold any non-zero sample.
@@ -260,16 +277,7 @@ __device__ __forceinline__ void f64_load_pair(const FrontendParams& p, const T* 
             }
         }
     } else {
-        lane_loop<NCT>(lane, nfft, [&](int n) {
-            double a = 0.0, b = 0.0;
-            if (n < n_used) {
-                a = (double)preemph_sample(xa, sa + n, p.n_samples, p.preemph);
-                if (has_b) b = (double)preemph_sample(xb, sb + n, p.n_samples, p.preemph);
-            }
-            nza |= a != 0.0;
-            nzb |= b != 0.0;
-            X[NCT == 512 ? sw512(n) : n] = d2{a, b};
-        });
+        f64_fill_pair<NCT>(p, xa, sa, xb, sb, has_b, X, nfft, n_used, lane, nza, nzb);
     }
     nza = __any(nza);
     nzb = __any(nzb);

@@ -86,6 +86,10 @@ SIGNATURES = {
     "kws_softmax_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, _f32p]),
     "kws_stream_smooth_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, _f32p, _i32p]),
     "kws_augment_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, C.c_void_p, _f32p, C.c_int, C.c_void_p, _f32p, C.c_void_p, _f32p]),
+    "kws_augment_draw": (C.c_int, [_c_ctx, C.c_uint64, C.c_uint32, _i32p, C.c_int, _i32p, C.c_int, C.c_int, _i32p, _i32p, C.c_int, C.c_float,
+                                   C.c_float, C.c_int, C.c_int, _i32p, _i32p, _f32p, C.c_void_p]),
+    "kws_mfcc_augment_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, _i32p, C.c_int, C.c_void_p, _f32p, C.c_int, C.c_void_p, _f32p, C.c_void_p,
+                                       _f32p]),
     "kws_forward_stamps_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, _f32p, C.c_void_p, C.c_int]),
     "kws_preemphasis_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_float, _f32p]),
     "kws_framesig_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _f32p]),
@@ -424,6 +428,29 @@ class Context:
                                       p(bg_off), p(bg_vol), p(silence), _ptr(out)),
             AudioProcessingError,
         )
+
+    def augment_draw(self, seed, epoch, index, shift, bg_off, bg_vol, silence, labels=None, time_shift=0, bg_start=None, bg_len=None,
+                     bg_volume=0.0, bg_frequency=0.0, use_background=True, n_samples=16000):
+        """The training transform's random draws for the dataset indices ``index`` (int32, device), made on the device."""
+        p = lambda t: _ptr(t) if t is not None else None
+        self._check(
+            self._lib.kws_augment_draw(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF, _ptr(index), int(index.numel()),
+                                       p(labels), int(labels.numel()) if labels is not None else 0, int(time_shift), p(bg_start),
+                                       p(bg_len), int(bg_start.numel()) if bg_start is not None else 0, float(bg_volume),
+                                       float(bg_frequency), int(bool(use_background)), int(n_samples), _ptr(shift), _ptr(bg_off),
+                                       _ptr(bg_vol), _ptr(silence)),
+            AudioProcessingError,
+        )
+
+    def mfcc_augment_i16(self, pcm, index, out, shift=None, bg=None, bg_off=None, bg_vol=None, silence=None) -> int:
+        """Gather + augment + MFCC in one launch.  Returns ``KWS_OK``, or ``KWS_EUNSUPPORTED`` when the configured front end
+        has no fused kernel (the caller composes ``augment_i16`` and ``mfcc_f32``); every other code raises."""
+        p = lambda t: _ptr(t) if t is not None else None
+        rc = self._lib.kws_mfcc_augment_i16(self._h, _ptr(pcm), int(pcm.shape[0]), _ptr(index), int(index.numel()), p(shift), p(bg),
+                                            int(bg.numel()) if bg is not None else 0, p(bg_off), p(bg_vol), p(silence), _ptr(out))
+        if rc != KWS_EUNSUPPORTED:
+            self._check(rc, AudioProcessingError)
+        return rc
 
     def reserve(self, max_batch: int):
         self._check(self._lib.kws_reserve(self._h, int(max_batch)))

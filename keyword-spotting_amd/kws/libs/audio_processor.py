@@ -276,6 +276,13 @@ class AudioProcessor:
             x = torch.from_numpy(np.ascontiguousarray(sig, dtype=np.float32)).to(dev)[None]
         return self.extract_features_batch(x, _ctx=ctx)[0, 0].double().cpu().numpy()
 
+    def background_pool(self, n: int):
+        """The background clips as one float32 array, each tiled beyond ``n`` samples by the reference's rule (``:212-213``):
+        ``(pool, starts, lengths)`` -- what ``transform_batch`` and the resident loader mix from."""
+        clips = [np.tile(b, int(np.ceil(n / len(b))) + 1) if len(b) <= n else b for b in self.background_data]
+        starts = np.cumsum([0] + [len(b) for b in clips[:-1]])
+        return np.concatenate(clips).astype(np.float32), starts, [len(b) for b in clips]
+
     def transform_batch(self, pcm, labels):
         """Batched, on-device version of ``transform`` for clips already decoded to ``int16[B, n]``:
         silence zeroing, random time shift, background mix (``kws_augment_i16``) and MFCC (``kws_mfcc_f32``).
@@ -298,10 +305,8 @@ class AudioProcessor:
         if self.background_data and (c.use_background_noise or silence.any()):
             pool, starts = getattr(self, "_bg_pool", None), getattr(self, "_bg_starts", None)
             if pool is None:
-                clips = [np.tile(b, int(np.ceil(n / len(b))) + 1) if len(b) <= n else b for b in self.background_data]
-                starts = np.cumsum([0] + [len(b) for b in clips[:-1]])
-                pool = torch.from_numpy(np.concatenate(clips).astype(np.float32)).to(dev)
-                self._bg_pool, self._bg_starts, self._bg_lens = pool, starts, [len(b) for b in clips]
+                pool, starts, lens = self.background_pool(n)
+                self._bg_pool, self._bg_starts, self._bg_lens = torch.from_numpy(pool).to(dev), starts, lens
             off, vol = np.zeros(B, np.int32), np.zeros(B, np.float32)
             for i in range(B):
                 if not (c.use_background_noise or silence[i]):
