@@ -482,6 +482,17 @@ int kws_host_mel_dense(int nfilt, int nfft, int sample_rate, float* fb_out);
 int kws_host_mel_layout(int nfilt, int nfft, int sample_rate, int* first_lane_out, int* n_lanes_out, int* lanes_used, int* row_safe);
 /* float32 [numcep, nfilt] DCT-II(ortho) x lifter table the kernel uses. */
 int kws_host_dct_lifter(int nfilt, int numcep, int ceplifter, float* out);
+/* The device image of a model as 32-bit words, exactly as kws_load_dscnn_ex / kws_load_cnn_trad upload it for the same
+ * blob, built on the host alone.  *need_words (may be NULL) receives the image's size; out_words == NULL only asks for
+ * that size, a cap_words below it is KWS_EINVAL; the blob is checked as by the loaders.  scalars (may be NULL) receives
+ * the values the context keeps by value:
+ *   kws_host_dscnn_image    float[23]: k_c1, k_pw[4] (the weight-scale exponents), c1_abs, c1_bmax, dw_abs[4], dw_bmax[4],
+ *                           pw_abs[4], pw_bmax[4] (the bounds behind the per-clip activation scales)
+ *   kws_host_cnn_trad_image float[7]:  1/sw of conv1, conv2, lin; w1_abs, b1_max, w2_abs, b2_max */
+int kws_host_dscnn_image(const float* blob, size_t n_floats, int num_classes, int input_channels, uint32_t* out_words,
+                         size_t cap_words, size_t* need_words, float* scalars);
+int kws_host_cnn_trad_image(const float* blob, size_t n_floats, int num_classes, uint32_t* out_words, size_t cap_words,
+                            size_t* need_words, float* scalars);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
-// C ABI of libkws_hip.so (declared in include/kws_hip.h): context, host-side table construction,
-// weight repacking, workspace and per-kernel event timing.  No torch types, no exceptions across the
-// boundary, no CPU fallback.
+// C ABI of libkws_hip.so (declared in include/kws_hip.h): context, the front-end, forward and streaming entry points, workspace
+// and per-kernel event timing.  The front-end tables are built in kws_tables.hip, the weight images in kws_weights.hip.  No torch
+// types, no exceptions across the boundary, no CPU fallback.
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -9,140 +9,13 @@
 #include <new>
 
 #include "kws_ctx.h"
+#include "kws_tables.h"
 
 namespace kws {
 
 const char* const kKernelNames[KWS_K_COUNT] = {"kws_mfcc_i16_kernel", "kws_dscnn_fwd_kernel", "kws_cnntrad_conv_kernel",
                                                "kws_cnntrad_dense_kernel", "kws_stream_frame_kernel", "kws_mfcc_f64_kernel",
                                                "kws_mfcc_refine_kernel"};
-
-// ------------------------------------------------------------------------------------------------
-// Host tables (double precision, then rounded once to float32).
-
-static double hz2mel(double hz) { return 2595.0 * std::log10(1.0 + hz / 700.0); }
-static double mel2hz(double mel) { return 700.0 * (std::pow(10.0, mel / 2595.0) - 1.0); }
-
-// psf get_filterbanks: nfilt+2 points equally spaced in mel (numpy.linspace arithmetic: i*step + start,
-// last point = stop), converted to FFT bins by floor((nfft+1)*hz/samplerate).
-static void mel_edges(int nfilt, int nfft, int sample_rate, std::vector<int>& edges) {
-    const double lowmel = hz2mel(0.0), highmel = hz2mel(sample_rate / 2.0);
-    const int num = nfilt + 2;
-    const double step = (highmel - lowmel) / (double)(num - 1);
-    edges.resize(num);
-    for (int i = 0; i < num; ++i) {
-        volatile double prod = (double)i * step;  // two roundings, as numpy does (no fused multiply-add)
-        double mel = prod + lowmel;
-        if (i == num - 1) mel = highmel;
-        edges[i] = (int)std::floor((nfft + 1) * mel2hz(mel) / sample_rate);
-    }
-}
-
-bool build_mel_host(int nfilt, int nfft, int sample_rate, MelHost& out, std::string& err) {
-    if (nfilt < 1 || nfilt > MAX_NFILT) {
-        err = "nfilt must be in [1, 64]";
-        return false;
-    }
-    mel_edges(nfilt, nfft, sample_rate, out.edges);
-    for (int i = 0; i + 1 < (int)out.edges.size(); ++i) {
-        if (out.edges[i + 1] < out.edges[i] || out.edges[i] < 0 || out.edges[i + 1] > nfft / 2) {
-            err = "mel edges are not monotone inside [0, nfft/2]";
-            return false;
-        }
-    }
-    out.k0.assign(64, nfft / 2);
-    out.rw.assign(MEL_CHUNK * 64, 0.f);
-    out.fw.assign(MEL_CHUNK * 64, 0.f);
-    out.gather.assign(64, 0u);
-    out.slot.assign(nfft / 2, 0);
-    std::vector<int> seg_first(nfilt + 2, 0), seg_count(nfilt + 2, 0);
-    // segment s = bins [edge_s, edge_s+1): rising side of filter s (s < nfilt), falling side of filter s-1 (s >= 1);
-    // it is cut into chunks of MEL_CHUNK bins, one chunk per lane, the chunks of a segment on adjacent lanes.
-    int dense_lanes = 0;
-    for (int s = 0; s <= nfilt; ++s) {
-        seg_count[s] = (out.edges[s + 1] - out.edges[s] + MEL_CHUNK - 1) / MEL_CHUNK;
-        dense_lanes += seg_count[s];
-    }
-    if (dense_lanes > 64) {
-        err = "mel filterbank needs more than 64 chunks of 8 bins";
-        return false;
-    }
-    // Lane layout: no segment straddles a 16-lane DPP row (idle lanes pad the rows), so the segmented sums can shift
-    // with row_shl:1/2/4 fused into v_fmac_f32_dpp.  Every filterbank that fits 64 dense chunks at nfft = 512 and
-    // the sample rates tried also fits this way (many filters = short segments); one that does not is refused.
-    {
-        int cursor = 0;
-        for (int s = 0; s <= nfilt; ++s) {
-            if (cursor % 16 + seg_count[s] > 16) cursor = (cursor + 15) / 16 * 16;
-            seg_first[s] = cursor;
-            cursor += seg_count[s];
-            if (seg_count[s] > 8 || cursor > 64) {
-                err = "mel filterbank does not fit 64 lanes with every segment (<= 8 chunks) inside one 16-lane row";
-                return false;
-            }
-        }
-    }
-    int nchunks = 0;  // lanes in use (idle padding lanes included)
-    for (int s = 0; s <= nfilt; ++s) {
-        const int lo = out.edges[s], hi = out.edges[s + 1];
-        int c = seg_first[s];
-        for (int k0 = lo; k0 < hi; k0 += MEL_CHUNK, ++c) {
-            out.k0[c] = k0;
-            for (int i = 0; i < MEL_CHUNK && k0 + i < hi; ++i) out.slot[k0 + i] = MEL_STRIDE * c + i;
-            for (int i = 0; i < MEL_CHUNK && k0 + i < hi; ++i) {
-                const double k = k0 + i, width = (double)(hi - lo);
-                if (s < nfilt) out.rw[i * 64 + c] = (float)((k - lo) / width);
-                if (s >= 1) out.fw[i * 64 + c] = (float)((hi - k) / width);
-            }
-        }
-        nchunks = std::max(nchunks, c);
-    }
-    // which neighbours (chunk + 1, + 2, + 4) share a chunk's segment: drives the in-register segmented sums
-    out.seg.assign(64, 0);
-    bool deep = false;
-    for (int s = 0; s <= nfilt; ++s) {
-        if (seg_count[s] > 8) {
-            err = "a mel segment spans more than 8 chunks of 8 bins";
-            return false;
-        }
-        deep = deep || seg_count[s] > 4;
-        for (int i = 0; i < seg_count[s]; ++i)
-            for (int d = 0; d < 3; ++d)
-                if (i + (1 << d) < seg_count[s]) out.seg[seg_first[s] + i] |= 1 << d;
-    }
-    for (int c = 0; c < 64; ++c) out.seg[c] |= (deep ? 128 : 0) | 64;  // bit 6: row-safe layout (always)
-    for (int j = 0; j < nfilt; ++j) {
-        if (seg_count[j] > 255 || seg_count[j + 1] > 255) {
-            err = "mel segment too long";
-            return false;
-        }
-        out.gather[j] = (uint32_t)seg_first[j] | ((uint32_t)seg_count[j] << 8) | ((uint32_t)seg_first[j + 1] << 16) |
-                        ((uint32_t)seg_count[j + 1] << 24);
-    }
-    out.n_chunks = nchunks;
-    return true;
-}
-
-void build_dct_lifter_host(int nfilt, int numcep, int ceplifter, std::vector<float>& out) {
-    out.assign((size_t)numcep * nfilt, 0.f);
-    const double pi = 3.14159265358979323846;
-    for (int i = 0; i < numcep; ++i) {
-        const double lift = ceplifter > 0 ? 1.0 + (ceplifter / 2.0) * std::sin(pi * i / ceplifter) : 1.0;
-        for (int j = 0; j < nfilt; ++j) {
-            const double d = (i == 0) ? std::sqrt(1.0 / nfilt)
-                                      : std::sqrt(2.0 / nfilt) * std::cos(pi * i * (2 * j + 1) / (2.0 * nfilt));
-            out[(size_t)i * nfilt + j] = (float)(lift * d);
-        }
-    }
-}
-
-void build_twiddle_host(std::vector<float2>& out) {
-    out.resize(NFFT);
-    const double pi = 3.14159265358979323846;
-    for (int k = 0; k < NFFT; ++k) {
-        const double a = 2.0 * pi * k / NFFT;
-        out[k] = make_float2((float)std::cos(a), (float)(-std::sin(a)));
-    }
-}
 
 }  // namespace kws
 
@@ -176,7 +49,6 @@ struct ProfScope {
 };
 
 static void stream_free_fwd(kws_ctx* c);
-static void drop_stream_graph(kws_ctx* c);
 
 #pragma GCC visibility push(default)
 extern "C" {
@@ -290,110 +162,16 @@ int kws_set_frontend(kws_ctx* c, int sample_rate, int n_samples, int frame_len, 
         for (int v = nfft; v > 1; v >>= 1) ++log2n;
     if (nfft > 4096 || (log2n == 0 && nfft > 2048) || (log2n > 0 && nfft < 64))
         return fail(c, KWS_EUNSUPPORTED, "kws_set_frontend: nfft must be a power of two in [64, 4096] or any value in [2, 2048]");
-    std::vector<int> edges;
-    mel_edges(nfilt, nfft, sample_rate, edges);
-    for (size_t i = 0; i + 1 < edges.size(); ++i)
-        if (edges[i + 1] < edges[i] || edges[i] < 0 || edges[i + 1] > nfft / 2)
-            return fail(c, KWS_EUNSUPPORTED, "kws_set_frontend: mel edges are not monotone inside [0, nfft/2]");
-    // The float32 kernel is built for nfft = 512, frames of at most 512 samples and filterbanks its sparse lane layout can
-    // hold; every other geometry runs on the float64 kernel (kws_mfcc_f64.hip).
-    MelHost mel;
-    std::string err;
-    bool fast = nfft == NFFT && frame_len <= NFFT && build_mel_host(nfilt, nfft, sample_rate, mel, err) &&
-                mel.edges.front() == 0 && mel.edges.back() == nfft / 2;
-    if (!fast) {
-        mel = MelHost();
-        mel.k0.assign(64, 0);
-        mel.rw.assign(MEL_CHUNK * 64, 0.f);
-        mel.fw.assign(MEL_CHUNK * 64, 0.f);
-        mel.gather.assign(64, 0u);
-        mel.slot.assign(NFFT / 2, 0);
-        mel.seg.assign(64, 0);
-    }
-    std::vector<float> dct;
-    build_dct_lifter_host(nfilt, numcep, ceplifter, dct);
-    std::vector<float2> tw;
-    build_twiddle_host(tw);
-    // float64 tables: twiddles (cos, -sin)(2 pi k / nfft), DCT-II(ortho) x lifter
-    const double pi = 3.14159265358979323846;
-    std::vector<double> tw64(2 * (size_t)nfft), dct64((size_t)numcep * nfilt);
-    for (int k = 0; k < nfft; ++k) {
-        const double a = 2.0 * pi * k / nfft;
-        tw64[2 * k] = std::cos(a);
-        tw64[2 * k + 1] = -std::sin(a);
-    }
-    for (int i = 0; i < numcep; ++i) {
-        const double lift = ceplifter > 0 ? 1.0 + (ceplifter / 2.0) * std::sin(pi * i / ceplifter) : 1.0;
-        for (int j = 0; j < nfilt; ++j)
-            dct64[(size_t)i * nfilt + j] = lift * (i == 0 ? std::sqrt(1.0 / nfilt) : std::sqrt(2.0 / nfilt) * std::cos(pi * i * (2 * j + 1) / (2.0 * nfilt)));
-    }
-
-    // per-bin mel weights exactly as psf's get_filterbanks forms them (float64 divisions): bin i in [e_j, e_j+1) rises in
-    // filter j with (i - e_j)/(e_j+1 - e_j) and falls in filter j-1 with (e_j+1 - i)/(e_j+1 - e_j)
-    const int nb64 = nfft / 2 + 1;
-    std::vector<double> melw(2 * (size_t)nb64, 0.0);
-    for (int j = 0; j <= nfilt; ++j)
-        for (int i = edges[j]; i < edges[j + 1]; ++i) {
-            const double width = (double)(edges[j + 1] - edges[j]);
-            melw[i] = (double)(i - edges[j]) / width;
-            melw[(size_t)nb64 + i] = (double)(edges[j + 1] - i) / width;
-        }
-
-    const int nfp = (nfilt + 3) & ~3;
-    std::vector<float> dct_pad(((size_t)numcep * nfp + 3) & ~(size_t)3, 0.f);
-    for (int i = 0; i < numcep; ++i)
-        for (int j = 0; j < nfilt; ++j) dct_pad[(size_t)i * nfp + j] = dct[(size_t)i * nfilt + j];
-
-    // one device allocation, every table 256-byte aligned
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_tw = 0, o_k0 = al(o_tw + sizeof(float2) * NFFT), o_rw = al(o_k0 + sizeof(int) * 64),
-                 o_fw = al(o_rw + sizeof(float) * MEL_CHUNK * 64), o_g = al(o_fw + sizeof(float) * MEL_CHUNK * 64),
-                 o_dct = al(o_g + sizeof(uint32_t) * 64), o_slot = al(o_dct + sizeof(float) * dct.size()),
-                 o_seg = al(o_slot + sizeof(int) * (NFFT / 2)), o_tw64 = al(o_seg + sizeof(int) * 64),
-                 o_edges = al(o_tw64 + sizeof(double) * tw64.size()), o_dct64 = al(o_edges + sizeof(int) * edges.size()),
-                 o_melw = al(o_dct64 + sizeof(double) * dct64.size()), o_dctp = al(o_melw + sizeof(double) * melw.size()),
-                 total = al(o_dctp + sizeof(float) * dct_pad.size());
-    std::vector<unsigned char> host(total, 0);
-    memcpy(&host[o_tw], tw.data(), sizeof(float2) * NFFT);
-    memcpy(&host[o_k0], mel.k0.data(), sizeof(int) * 64);
-    memcpy(&host[o_rw], mel.rw.data(), sizeof(float) * MEL_CHUNK * 64);
-    memcpy(&host[o_fw], mel.fw.data(), sizeof(float) * MEL_CHUNK * 64);
-    memcpy(&host[o_g], mel.gather.data(), sizeof(uint32_t) * 64);
-    memcpy(&host[o_dct], dct.data(), sizeof(float) * dct.size());
-    memcpy(&host[o_slot], mel.slot.data(), sizeof(int) * (NFFT / 2));
-    memcpy(&host[o_seg], mel.seg.data(), sizeof(int) * 64);
-    memcpy(&host[o_tw64], tw64.data(), sizeof(double) * tw64.size());
-    memcpy(&host[o_edges], edges.data(), sizeof(int) * edges.size());
-    memcpy(&host[o_dct64], dct64.data(), sizeof(double) * dct64.size());
-    memcpy(&host[o_melw], melw.data(), sizeof(double) * melw.size());
-    memcpy(&host[o_dctp], dct_pad.data(), sizeof(float) * dct_pad.size());
+    FrontendImage im;
+    if (!build_frontend_image(sample_rate, frame_len, nfft, nfilt, numcep, ceplifter, im))
+        return fail(c, KWS_EUNSUPPORTED, "kws_set_frontend: mel edges are not monotone inside [0, nfft/2]");
 
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // tables of the previous configuration may be in use
     if (c->n_streams) stream_free_fwd(c);         // ring geometry depends on the front end
-    void* d = nullptr;
-    if (hipMalloc(&d, total) != hipSuccess) return fail(c, KWS_ENOMEM, "kws_set_frontend: device allocation failed");
-    hipError_t e = hipMemcpy(d, host.data(), total, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return fail_hip(c, e, "kws_set_frontend: hipMemcpy");
-    }
-    if (c->d_fe) (void)hipFree(c->d_fe);
-    c->d_fe = d;
-    unsigned char* b = static_cast<unsigned char*>(d);
-    c->ft.twiddle = reinterpret_cast<const float2*>(b + o_tw);
-    c->ft.mel_k0 = reinterpret_cast<const int*>(b + o_k0);
-    c->ft.mel_rw = reinterpret_cast<const float*>(b + o_rw);
-    c->ft.mel_fw = reinterpret_cast<const float*>(b + o_fw);
-    c->ft.mel_gather = reinterpret_cast<const uint32_t*>(b + o_g);
-    c->ft.dct = reinterpret_cast<const float*>(b + o_dct);
-    c->ft.mel_slot = reinterpret_cast<const int*>(b + o_slot);
-    c->ft.mel_seg = reinterpret_cast<const int*>(b + o_seg);
-    c->ft.tw64 = reinterpret_cast<const double*>(b + o_tw64);
-    c->ft.mel_edges = reinterpret_cast<const int*>(b + o_edges);
-    c->ft.dct64 = reinterpret_cast<const double*>(b + o_dct64);
-    c->ft.mel_w64 = reinterpret_cast<const double*>(b + o_melw);
-    c->ft.dct_pad = reinterpret_cast<const float*>(b + o_dctp);
+    int rc = replace_device_image(c, c->d_fe, im.bytes.data(), im.bytes.size(), "kws_set_frontend");
+    if (rc) return rc;
+    c->ft = im.tables(c->d_fe);
 
     FrontendParams& p = c->fp;
     p.n_samples = n_samples;
@@ -414,7 +192,7 @@ int kws_set_frontend(kws_ctx* c, int sample_rate, int n_samples, int frame_len, 
     c->sample_rate = sample_rate;
     c->nfft = nfft;
     c->ceplifter = ceplifter;
-    c->fe_fast_ok = fast;
+    c->fe_fast_ok = im.fast;
     c->fe_ready = true;
     return KWS_OK;
     KWS_GUARD_END(c, "kws_set_frontend")
@@ -464,220 +242,6 @@ int kws_frontend_shape(kws_ctx* c, int* num_frames, int* numcep) {
     return KWS_OK;
 }
 
-int kws_load_dscnn(kws_ctx* c, const float* blob, size_t n_floats, int num_classes) {
-    return kws_load_dscnn_ex(c, blob, n_floats, num_classes, 1);
-}
-
-static float pow2_weight_scale(const float* w, size_t n);
-static float max_row_abs_sum(const float* w, int rows, size_t row_len);
-// PLAIN f16-pair pieces of one weight already multiplied by its layer's scale: hi = f16(x), lo = f16(x - hi) (kws_split_mfma.h)
-static void pair_plain(float x, uint16_t& hb, uint16_t& lb) {
-    const _Float16 h = (_Float16)x;
-    const _Float16 l = (_Float16)(x - (float)h);
-    memcpy(&hb, &h, 2);
-    memcpy(&lb, &l, 2);
-}
-
-int kws_load_dscnn_ex(kws_ctx* c, const float* blob, size_t n_floats, int num_classes, int input_channels) {
-    KWS_GUARD_BEGIN
-    if (!c) return KWS_EINVAL;
-    if (!blob) return fail(c, KWS_EINVAL, "kws_load_dscnn: blob is NULL");
-    if (num_classes < 1 || num_classes > MAX_CLASSES) return fail(c, KWS_EUNSUPPORTED, "kws_load_dscnn: num_classes must be in [1, 64]");
-    if (input_channels < 1 || input_channels > 64) return fail(c, KWS_EUNSUPPORTED, "kws_load_dscnn: input_channels must be in [1, 64]");
-    const size_t c1_floats = (size_t)6400 * input_channels;
-    const size_t expect = c1_floats + 64 + 4 * (576 + 64 + 4096 + 64) + (size_t)num_classes * 64 + num_classes;
-    if (n_floats != expect) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "kws_load_dscnn: expected %zu floats for %d classes and %d input channel(s), got %zu", expect,
-                 num_classes, input_channels, n_floats);
-        return fail(c, KWS_EINVAL, msg);
-    }
-    // repack: c1_w [100][64] | c1_b [64] | dw [4][64][12] | pw_w [4][cin][cout] | pw_b [4][64] | fc_w | fc_b | splits |
-    // (input_channels > 1) conv1 as [ci][tap][cout] for kws_conv1_general_kernel
-    const size_t o_c1w = 0, o_c1b = o_c1w + 6400, o_dw = o_c1b + 64, o_pww = o_dw + 4 * 64 * 12, o_pwb = o_pww + 4 * 4096,
-                 o_fcw = o_pwb + 4 * 64, o_fcb = o_fcw + (size_t)num_classes * 64,
-                 o_split = (o_fcb + num_classes + 3) & ~(size_t)3, o_c1s = o_split + 4 * 2 * 4 * 3 * 64 * 4,
-                 o_c1g = o_c1s + 2 * 7 * 3 * 64 * 4, o_raw = o_c1g + c1_floats,
-                 o_pwp = (o_raw + n_floats + 3) & ~(size_t)3, o_c1p = o_pwp + 4 * 2 * 4 * 2 * 64 * 4, total = o_c1p + 2 * 7 * 2 * 64 * 4;
-    std::vector<float> h(total, 0.f);
-    const float* src = blob;
-    memcpy(&h[o_raw], blob, n_floats * sizeof(float));  // torch layouts, for the composed any-map path (kws_forward_map_f32)
-    // conv1.weight [64][C][10][10] -> [ci][tap][cout] (kws_conv1_general_kernel for C > 1, kws_conv1_any_kernel for any map)
-    {
-        for (int co = 0; co < 64; ++co)
-            for (int ci = 0; ci < input_channels; ++ci)
-                for (int k = 0; k < 100; ++k) h[o_c1g + ((size_t)ci * 100 + k) * 64 + co] = src[((size_t)co * input_channels + ci) * 100 + k];
-    }
-    for (int co = 0; co < 64 && input_channels == 1; ++co)  // conv1.weight [64][1][10][10] -> [k][cout]
-        for (int k = 0; k < 100; ++k) h[o_c1w + (size_t)k * 64 + co] = src[co * 100 + k];
-    if (input_channels == 1) {
-        // conv1 as bf16x3 MFMA A operands (32x32x16).  The 100 taps are split between the half-waves: lanes
-        // 32..63 take kernel rows 5..9, so both halves walk the same 50 (+6 zero) offsets f = 10*(kh%5) + kw and
-        // their LDS addresses differ by a constant.  Lane l of (ct, kb): cout = 32ct + (l&31), f = 8kb + j.
-        uint32_t* sp = reinterpret_cast<uint32_t*>(&h[o_c1s]);
-        for (int ct = 0; ct < 2; ++ct)
-            for (int kb = 0; kb < 7; ++kb)
-                for (int l = 0; l < 64; ++l)
-                    for (int j = 0; j < 8; ++j) {
-                        const int co = 32 * ct + (l & 31), f = 8 * kb + j;
-                        float r = f < 50 ? src[co * 100 + (f / 10 + 5 * (l >> 5)) * 10 + f % 10] : 0.f;
-                        for (int p = 0; p < 3; ++p) {
-                            uint32_t u;
-                            memcpy(&u, &r, 4);
-                            u &= 0xffff0000u;
-                            float t;
-                            memcpy(&t, &u, 4);
-                            r -= t;
-                            sp[(((size_t)(ct * 7 + kb) * 3 + p) * 64 + l) * 4 + (j >> 1)] |= (u >> 16) << (16 * (j & 1));
-                        }
-                    }
-    }
-    // the f16-pair images and the bounds behind the per-clip activation scales (kws_dscnn.hip, KWS_PW_PAIR_F16)
-    DscnnWeights mw{};  // (a local: the context keeps its old model if the upload below fails)
-    if (input_channels == 1) {
-        const float sw = pow2_weight_scale(src, 6400);
-        int ke;
-        (void)std::frexp(sw, &ke);
-        mw.k_c1 = ke - 1;  // sw = 2^(ke - 1)
-        uint32_t* sp = reinterpret_cast<uint32_t*>(&h[o_c1p]);
-        for (int ct = 0; ct < 2; ++ct)
-            for (int kb = 0; kb < 7; ++kb)
-                for (int l = 0; l < 64; ++l)
-                    for (int j = 0; j < 8; ++j) {
-                        // K order of the pre-split windows (kws_dscnn.hip, conv1_unit_pairwin): half-wave h = l >> 5 takes kernel
-                        // rows 5h .. 5h + 4; kb < 5: kernel row 5h + kb, taps kw = j; kb = 5: taps kw = 8 + (j & 1) of kernel row
-                        // 5h + (j >> 1); kb = 6: taps kw = 8 + j (j < 2) of kernel row 5h + 4, then zeros
-                        const int co = 32 * ct + (l & 31), h5 = 5 * (l >> 5);
-                        int kh = -1, kw = 0;
-                        if (kb < 5) {
-                            kh = h5 + kb;
-                            kw = j;
-                        } else if (kb == 5) {
-                            kh = h5 + (j >> 1);
-                            kw = 8 + (j & 1);
-                        } else if (j < 2) {
-                            kh = h5 + 4;
-                            kw = 8 + j;
-                        }
-                        const float v = kh >= 0 ? src[co * 100 + kh * 10 + kw] : 0.f;
-                        uint16_t hb, lb;
-                        pair_plain(v * sw, hb, lb);
-                        sp[(((size_t)(ct * 7 + kb) * 2 + 0) * 64 + l) * 4 + (j >> 1)] |= (uint32_t)hb << (16 * (j & 1));
-                        sp[(((size_t)(ct * 7 + kb) * 2 + 1) * 64 + l) * 4 + (j >> 1)] |= (uint32_t)lb << (16 * (j & 1));
-                    }
-        mw.c1_abs = max_row_abs_sum(src, 64, 100);
-        mw.c1_bmax = 0.f;
-        for (int i = 0; i < 64; ++i) mw.c1_bmax = std::max(mw.c1_bmax, std::fabs(src[6400 + i]));
-    } else {
-        mw.k_c1 = 0;
-        mw.c1_abs = mw.c1_bmax = 0.f;
-    }
-    src += c1_floats;
-    memcpy(&h[o_c1b], src, 64 * sizeof(float));
-    src += 64;
-    for (int b = 0; b < 4; ++b) {
-        const float *dw_w = src, *dw_b = src + 576, *pw_w = src + 640, *pw_b = src + 640 + 4096;
-        for (int ch = 0; ch < 64; ++ch) {  // channel PAIRS interleaved, 24 floats per pair: (tap t of ch, of ch + 1) at 2t, the biases at 18, 19
-            float* q = &h[o_dw + ((size_t)b * 32 + ch / 2) * 24 + (ch & 1)];
-            for (int t = 0; t < 9; ++t) q[2 * t] = dw_w[ch * 9 + t];
-            q[18] = dw_b[ch];
-        }
-        for (int co = 0; co < 64; ++co)  // pointwise.weight [cout][cin][1][1] -> [cin][cout]
-            for (int ci = 0; ci < 64; ++ci) h[o_pww + (size_t)b * 4096 + (size_t)ci * 64 + co] = pw_w[co * 64 + ci];
-        memcpy(&h[o_pwb + (size_t)b * 64], pw_b, 64 * sizeof(float));
-        // the same weights as bf16x3 MFMA A operands (32x32x16): lane l of (ct, m) holds cin = 16m + 8(l>>5) + j,
-        // j = 0..7, of cout = 32ct + (l&31); piece 0/1/2 = top 16 bits of the value / first / second remainder
-        uint32_t* sp = reinterpret_cast<uint32_t*>(&h[o_split]) + (size_t)b * (2 * 4 * 3 * 64 * 4);
-        for (int ct = 0; ct < 2; ++ct)
-            for (int m = 0; m < 4; ++m)
-                for (int l = 0; l < 64; ++l)
-                    for (int j = 0; j < 8; ++j) {
-                        const int co = 32 * ct + (l & 31), ci = 16 * m + 8 * (l >> 5) + j;
-                        float r = pw_w[co * 64 + ci];
-                        for (int p = 0; p < 3; ++p) {
-                            uint32_t u;
-                            memcpy(&u, &r, 4);
-                            u &= 0xffff0000u;
-                            float t;
-                            memcpy(&t, &u, 4);
-                            r -= t;
-                            uint32_t& dst = sp[(((size_t)(ct * 4 + m) * 3 + p) * 64 + l) * 4 + (j >> 1)];
-                            dst |= (u >> 16) << (16 * (j & 1));
-                        }
-                    }
-        {
-            const float sw = pow2_weight_scale(pw_w, 4096);
-            int ke;
-            (void)std::frexp(sw, &ke);
-            mw.k_pw[b] = ke - 1;
-            uint32_t* pp = reinterpret_cast<uint32_t*>(&h[o_pwp]) + (size_t)b * (2 * 4 * 2 * 64 * 4);
-            for (int ct = 0; ct < 2; ++ct)
-                for (int m = 0; m < 4; ++m)
-                    for (int l = 0; l < 64; ++l)
-                        for (int j = 0; j < 8; ++j) {
-                            const int co = 32 * ct + (l & 31), ci = 16 * m + 8 * (l >> 5) + j;
-                            uint16_t hb, lb;
-                            pair_plain(pw_w[co * 64 + ci] * sw, hb, lb);
-                            pp[(((size_t)(ct * 4 + m) * 2 + 0) * 64 + l) * 4 + (j >> 1)] |= (uint32_t)hb << (16 * (j & 1));
-                            pp[(((size_t)(ct * 4 + m) * 2 + 1) * 64 + l) * 4 + (j >> 1)] |= (uint32_t)lb << (16 * (j & 1));
-                        }
-            mw.dw_abs[b] = max_row_abs_sum(dw_w, 64, 9);
-            mw.pw_abs[b] = max_row_abs_sum(pw_w, 64, 64);
-            mw.dw_bmax[b] = mw.pw_bmax[b] = 0.f;
-            for (int i = 0; i < 64; ++i) {
-                mw.dw_bmax[b] = std::max(mw.dw_bmax[b], std::fabs(dw_b[i]));
-                mw.pw_bmax[b] = std::max(mw.pw_bmax[b], std::fabs(pw_b[i]));
-            }
-        }
-        src += 576 + 64 + 4096 + 64;
-    }
-    memcpy(&h[o_fcw], src, (size_t)num_classes * 64 * sizeof(float));
-    src += (size_t)num_classes * 64;
-    memcpy(&h[o_fcb], src, (size_t)num_classes * sizeof(float));
-
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    float* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), total * sizeof(float)) != hipSuccess)
-        return fail(c, KWS_ENOMEM, "kws_load_dscnn: device allocation failed");
-    hipError_t e = hipMemcpy(d, h.data(), total * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return fail_hip(c, e, "kws_load_dscnn: hipMemcpy");
-    }
-    drop_stream_graph(c);  // a captured push holds the old weight pointers by value
-    if (c->d_model) (void)hipFree(c->d_model);
-    c->d_model = d;
-    c->mw.c1_w = d + o_c1w;
-    c->mw.c1_b = d + o_c1b;
-    c->mw.dw_w = d + o_dw;
-    c->mw.pw_w = d + o_pww;
-    c->mw.pw_b = d + o_pwb;
-    c->mw.pw_split = reinterpret_cast<const uint32_t*>(d + o_split);
-    c->mw.c1_split = reinterpret_cast<const uint32_t*>(d + o_c1s);
-    c->mw.pw_pair = reinterpret_cast<const uint32_t*>(d + o_pwp);
-    c->mw.c1_pair = reinterpret_cast<const uint32_t*>(d + o_c1p);
-    c->mw.k_c1 = mw.k_c1;
-    c->mw.c1_abs = mw.c1_abs;
-    c->mw.c1_bmax = mw.c1_bmax;
-    for (int b = 0; b < 4; ++b) {
-        c->mw.k_pw[b] = mw.k_pw[b];
-        c->mw.dw_abs[b] = mw.dw_abs[b];
-        c->mw.dw_bmax[b] = mw.dw_bmax[b];
-        c->mw.pw_abs[b] = mw.pw_abs[b];
-        c->mw.pw_bmax[b] = mw.pw_bmax[b];
-    }
-    c->mw.fc_w = d + o_fcw;
-    c->mw.fc_b = d + o_fcb;
-    c->mw.num_classes = num_classes;
-    c->mw.in_channels = input_channels;
-    c->mw.c1_general = d + o_c1g;
-    c->mw.raw = d + o_raw;
-    c->model_ready = true;
-    return KWS_OK;
-    KWS_GUARD_END(c, "kws_load_dscnn")
-}
-
 // Worklist of the selective refinement for batches of up to B clips: int[8] counters + one entry per frame.  The counters
 // (running totals included) move to the new allocation.
 static int ensure_refine(kws_ctx* c, int B) {
@@ -710,14 +274,7 @@ int kws_reserve(kws_ctx* c, int max_batch) {
     const size_t need = (size_t)max_batch * c->fp.num_frames * c->fp.numcep;
     if (need <= c->feat_ws_floats) return KWS_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    float* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), need * sizeof(float)) != hipSuccess)
-        return fail(c, KWS_ENOMEM, "kws_reserve: device allocation failed");
-    if (c->d_feat_ws) (void)hipFree(c->d_feat_ws);
-    c->d_feat_ws = d;
-    c->feat_ws_floats = need;
-    return KWS_OK;
+    return grow_device_buffer(c, c->d_feat_ws, c->feat_ws_floats, need, "kws_reserve", "device");
 }
 
 static int check_batch(kws_ctx* c, const void* in, int B, const char* fn) {
@@ -946,12 +503,6 @@ static void vad_free(kws_ctx* c) {
     c->vad_on = c->vad_off = 0;
 }
 
-static void drop_stream_graph(kws_ctx* c) {
-    if (c->stream_graph) (void)hipGraphExecDestroy(c->stream_graph);
-    c->stream_graph = nullptr;
-    c->graph_key[0] = c->graph_key[1] = c->graph_key[2] = nullptr;
-}
-
 static void host_results_free(kws_ctx* c) {
     if (c->h_stream_logits) (void)hipHostFree(c->h_stream_logits);
     if (c->h_stream_label) (void)hipHostFree(c->h_stream_label);
@@ -1113,364 +664,9 @@ int kws_stream_cluster(kws_ctx* c, int workgroups_per_stream) {
     return KWS_OK;
 }
 
-// Exact bf16 hi/mid/lo pieces of eight weights, OR-ed into four dwords per piece (MFMA operand fragment of one lane).
-static void pack_split8(const float (&v)[8], uint32_t* hi, uint32_t* mid, uint32_t* lo) {
-    uint32_t* dst[3] = {hi, mid, lo};
-    for (int j = 0; j < 8; ++j) {
-        float r = v[j];
-        for (int p = 0; p < 3; ++p) {
-            uint32_t u;
-            memcpy(&u, &r, 4);
-            u &= 0xffff0000u;
-            float t;
-            memcpy(&t, &u, 4);
-            r -= t;
-            dst[p][j >> 1] |= (u >> 16) << (16 * (j & 1));
-        }
-    }
-}
-
-// f16-pair pieces of eight weights already multiplied by the layer's power-of-two scale: hi = f16(v) (round to nearest),
-// lo' = f16((v - hi) * 2^11); OR-ed into four dwords per piece like pack_split8 (kws_cnntrad.hip, split_pair).
-static void pack_pair8(const float (&v)[8], float scale, uint32_t* hi, uint32_t* lo) {
-    for (int j = 0; j < 8; ++j) {
-        const float x = v[j] * scale;
-        const _Float16 h = (_Float16)x;
-        const _Float16 l = (_Float16)((x - (float)h) * 2048.f);
-        uint16_t hb, lb;
-        memcpy(&hb, &h, 2);
-        memcpy(&lb, &l, 2);
-        hi[j >> 1] |= (uint32_t)hb << (16 * (j & 1));
-        lo[j >> 1] |= (uint32_t)lb << (16 * (j & 1));
-    }
-}
-// the power of two s with max|w| * s < 2^15, and the layer's bound terms
-static float pow2_weight_scale(const float* w, size_t n) {
-    float m = 0.f;
-    for (size_t i = 0; i < n; ++i) m = std::max(m, std::fabs(w[i]));
-    if (!(m > 0.f) || !std::isfinite(m)) return 1.f;
-    int e;
-    (void)std::frexp(m, &e);  // m = f * 2^e, f in [0.5, 1): m < 2^e
-    return std::ldexp(1.f, std::max(-100, std::min(100, 15 - e)));
-}
-static float max_row_abs_sum(const float* w, int rows, size_t row_len) {
-    double best = 0.0;
-    for (int r = 0; r < rows; ++r) {
-        double a = 0.0;
-        for (size_t i = 0; i < row_len; ++i) a += std::fabs((double)w[(size_t)r * row_len + i]);
-        best = std::max(best, a);
-    }
-    return (float)(best * 1.0000002);  // rounded up
-}
-
-// The device image of a cnn-trad-fpool3 blob (units: 32-bit words): c1_split | c2_split | c1_b | c2_b | lin_split | lin_b | dnn_w |
-// dnn_b | fc_w | fc_b, the f16-pair images (two pieces, 16-byte aligned), then the blob itself as float32 (16-byte aligned; the
-// weights of kws_cnn_trad_backward_f32).
-struct CtLayout {
-    size_t n_c1, n_c2, n_lin, n_dnn, n_fc, n_floats;
-    size_t o_c1s, o_c2s, o_c1b, o_c2b, o_lin, o_linb, o_dnn, o_dnnb, o_fc, o_fcb, o_c1h, o_c2h, o_linh, o_raw, total;
-    explicit CtLayout(int num_classes) {
-        const size_t FLAT = 64 * 297;
-        n_c1 = 64 * 160, n_c2 = 64 * 64 * 40, n_lin = 32 * FLAT, n_dnn = 128 * 32, n_fc = (size_t)num_classes * 128;
-        n_floats = n_c1 + 64 + n_c2 + 64 + n_lin + 32 + n_dnn + 128 + n_fc + num_classes;
-        o_c1s = 0, o_c2s = o_c1s + 10 * 2 * 3 * 64 * 4, o_c1b = o_c2s + (size_t)40 * 4 * 2 * 3 * 64 * 4, o_c2b = o_c1b + 64, o_lin = o_c2b + 64,
-        o_linb = o_lin + (size_t)(FLAT / 16) * 3 * 64 * 4, o_dnn = o_linb + 32, o_dnnb = o_dnn + n_dnn, o_fc = o_dnnb + 128, o_fcb = o_fc + n_fc,
-        o_c1h = (o_fcb + num_classes + 3) / 4 * 4, o_c2h = o_c1h + 10 * 2 * 2 * 64 * 4, o_linh = o_c2h + (size_t)40 * 4 * 2 * 2 * 64 * 4,
-        o_raw = o_linh + (size_t)(FLAT / 16) * 2 * 64 * 4, total = o_raw + (n_floats + 3) / 4 * 4;
-    }
-};
-
-// the power of two s with m * s < 2^15 for m = max|w| of a layer (pow2_weight_scale)
-static float pow2_scale_of_max(float m) {
-    if (!(m > 0.f) || !std::isfinite(m)) return 1.f;
-    int e;
-    (void)std::frexp(m, &e);  // m = f * 2^e, f in [0.5, 1): m < 2^e
-    return std::ldexp(1.f, std::max(-100, std::min(100, 15 - e)));
-}
-
-// Point the context at a complete device image d (layout L) and set the values CnnTradWeights carries by value.
-static void install_cnntrad(kws_ctx* c, uint32_t* d, const CtLayout& L, int num_classes, float sw1, float sw2, float swl, float w1_abs,
-                            float w2_abs, float b1_max, float b2_max) {
-    if (c->d_cnntrad && c->d_cnntrad != d) (void)hipFree(c->d_cnntrad);
-    c->d_cnntrad = d;
-    c->ct_image_words = L.total;
-    const float* df = reinterpret_cast<const float*>(d);
-    c->tw.c1_split = d + L.o_c1s;
-    c->tw.c2_split = d + L.o_c2s;
-    c->tw.c1_b = df + L.o_c1b;
-    c->tw.c2_b = df + L.o_c2b;
-    c->tw.lin_split = d + L.o_lin;
-    c->tw.lin_b = df + L.o_linb;
-    c->tw.dnn_w = df + L.o_dnn;
-    c->tw.dnn_b = df + L.o_dnnb;
-    c->tw.fc_w = df + L.o_fc;
-    c->tw.fc_b = df + L.o_fcb;
-    c->tw.num_classes = num_classes;
-    c->tw.c1_h2 = d + L.o_c1h;
-    c->tw.c2_h2 = d + L.o_c2h;
-    c->tw.lin_h2 = d + L.o_linh;
-    c->tw.inv_sw1 = 1.f / sw1;
-    c->tw.inv_sw2 = 1.f / sw2;
-    c->tw.inv_swl = 1.f / swl;
-    c->tw.w1_abs = w1_abs;
-    c->tw.w2_abs = w2_abs;
-    c->tw.b1_max = b1_max;
-    c->tw.b2_max = b2_max;
-    c->ct_raw = df + L.o_raw;
-    c->cnntrad_ready = true;
-}
-
-static int check_cnntrad_blob(kws_ctx* c, const char* fn, size_t n_floats, int num_classes) {
-    if (num_classes < 1 || num_classes > MAX_CLASSES) return fail(c, KWS_EUNSUPPORTED, std::string(fn) + ": num_classes must be in [1, 64]");
-    const size_t expect = CtLayout(num_classes).n_floats;
-    if (n_floats != expect) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "%s: expected %zu floats for %d classes, got %zu", fn, expect, num_classes, n_floats);
-        return fail(c, KWS_EINVAL, msg);
-    }
-    return KWS_OK;
-}
-
-int kws_load_cnn_trad(kws_ctx* c, const float* blob, size_t n_floats, int num_classes) {
-    KWS_GUARD_BEGIN
-    if (!c) return KWS_EINVAL;
-    if (!blob) return fail(c, KWS_EINVAL, "kws_load_cnn_trad: blob is NULL");
-    int rc = check_cnntrad_blob(c, "kws_load_cnn_trad", n_floats, num_classes);
-    if (rc) return rc;
-    const CtLayout L(num_classes);
-    const size_t FLAT = 64 * 297, n_c1 = L.n_c1, n_c2 = L.n_c2, n_lin = L.n_lin, n_dnn = L.n_dnn, n_fc = L.n_fc;
-    const float *w1 = blob, *b1 = w1 + n_c1, *w2 = b1 + 64, *b2 = w2 + n_c2, *wl = b2 + 64, *bl = wl + n_lin, *wd = bl + 32,
-                *bd = wd + n_dnn, *wf = bd + 128, *bf = wf + n_fc;
-    std::vector<uint32_t> h(L.total, 0u);
-    const float sw1 = pow2_weight_scale(w1, n_c1), sw2 = pow2_weight_scale(w2, n_c2), swl = pow2_weight_scale(wl, n_lin);
-    auto put = [&](size_t off, const float* src, size_t n) { memcpy(&h[off], src, n * sizeof(float)); };
-    // conv1: lane l of (kb, ct): cout = 32ct + (l&31), kernel row 2kb + (l>>5), kernel columns j = 0..7
-    for (int kb = 0; kb < 10; ++kb)
-        for (int ct = 0; ct < 2; ++ct)
-            for (int l = 0; l < 64; ++l) {
-                float v[8];
-                const int co = 32 * ct + (l & 31), kh = 2 * kb + (l >> 5);
-                for (int j = 0; j < 8; ++j) v[j] = w1[(co * 20 + kh) * 8 + j];
-                uint32_t* base = &h[L.o_c1s + ((size_t)(kb * 2 + ct) * 3 * 64 + l) * 4];
-                pack_split8(v, base, base + 64 * 4, base + 2 * 64 * 4);
-                uint32_t* b2 = &h[L.o_c1h + ((size_t)(kb * 2 + ct) * 2 * 64 + l) * 4];
-                pack_pair8(v, sw1, b2, b2 + 64 * 4);
-            }
-    // conv2: lane l of (kk = kh*4 + kw, cb, ct): cout = 32ct + (l&31), input channels 16cb + 8(l>>5) + j
-    for (int kk = 0; kk < 40; ++kk)
-        for (int cb = 0; cb < 4; ++cb)
-            for (int ct = 0; ct < 2; ++ct)
-                for (int l = 0; l < 64; ++l) {
-                    float v[8];
-                    const int co = 32 * ct + (l & 31), kh = kk >> 2, kw = kk & 3;
-                    for (int j = 0; j < 8; ++j) v[j] = w2[((co * 64 + 16 * cb + 8 * (l >> 5) + j) * 10 + kh) * 4 + kw];
-                    uint32_t* base = &h[L.o_c2s + ((((size_t)kk * 4 + cb) * 2 + ct) * 3 * 64 + l) * 4];
-                    pack_split8(v, base, base + 64 * 4, base + 2 * 64 * 4);
-                    uint32_t* b2 = &h[L.o_c2h + ((((size_t)kk * 4 + cb) * 2 + ct) * 2 * 64 + l) * 4];
-                    pack_pair8(v, sw2, b2, b2 + 64 * 4);
-                }
-    put(L.o_c1b, b1, 64);
-    put(L.o_c2b, b2, 64);
-    // first dense layer as MFMA B operands (32x32x16): lane l of k-block kb: output l&31, inputs 16kb + 8(l>>5) + j
-    for (size_t kb = 0; kb < FLAT / 16; ++kb)
-        for (int l = 0; l < 64; ++l) {
-            float v[8];
-            for (int j = 0; j < 8; ++j) v[j] = wl[(size_t)(l & 31) * FLAT + 16 * kb + 8 * (l >> 5) + j];
-            uint32_t* base = &h[L.o_lin + (kb * 3 * 64 + l) * 4];
-            pack_split8(v, base, base + 64 * 4, base + 2 * 64 * 4);
-            uint32_t* b2 = &h[L.o_linh + (kb * 2 * 64 + l) * 4];
-            pack_pair8(v, swl, b2, b2 + 64 * 4);
-        }
-    put(L.o_linb, bl, 32);
-    put(L.o_dnn, wd, n_dnn);
-    put(L.o_dnnb, bd, 128);
-    put(L.o_fc, wf, n_fc);
-    put(L.o_fcb, bf, num_classes);
-    put(L.o_raw, blob, n_floats);
-
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    uint32_t* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), L.total * sizeof(uint32_t)) != hipSuccess)
-        return fail(c, KWS_ENOMEM, "kws_load_cnn_trad: device allocation failed");
-    hipError_t e = hipMemcpy(d, h.data(), L.total * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return fail_hip(c, e, "kws_load_cnn_trad: hipMemcpy");
-    }
-    float b1_max = 0.f, b2_max = 0.f;
-    for (int i = 0; i < 64; ++i) {
-        b1_max = std::max(b1_max, std::fabs(b1[i]));
-        b2_max = std::max(b2_max, std::fabs(b2[i]));
-    }
-    install_cnntrad(c, d, L, num_classes, sw1, sw2, swl, max_row_abs_sum(w1, 64, 160), max_row_abs_sum(w2, 64, 2560), b1_max, b2_max);
-    return KWS_OK;
-    KWS_GUARD_END(c, "kws_load_cnn_trad")
-}
-
-// ---- kws_load_cnn_trad_device: the same image built on the device from a device-resident blob ----------------------------------
-// Statistics in the host's arithmetic: maxima of |w| (exact in any order; fmaxf drops NaN as std::max does there), the row sums of
-// max_row_abs_sum as ONE sequential float64 chain per row, in the host's order.  st: float [5] = max|w1|, max|w2|, max|wl|, max|b1|,
-// max|b2|, then (8-byte aligned) double [2] = the largest row sums of w1 and w2.
-__global__ __launch_bounds__(1024) void kws_ct_load_stats_kernel(const float* __restrict__ blob, float* __restrict__ st) {
-    __shared__ float s_m[1024];
-    __shared__ double s_r[128];
-    const int tid = threadIdx.x, q = blockIdx.x;
-    if (q < 5) {  // one maximum per workgroup
-        const size_t off[5] = {0, 64 * 160 + 64, 64 * 160 + 64 + 163840 + 64, 64 * 160, 64 * 160 + 64 + 163840};
-        const size_t len[5] = {64 * 160, 163840, (size_t)32 * 19008, 64, 64};
-        float m = 0.f;
-        for (size_t i = tid; i < len[q]; i += 1024) m = fmaxf(m, fabsf(blob[off[q] + i]));
-        s_m[tid] = m;
-        __syncthreads();
-        for (int w = 512; w > 0; w >>= 1) {
-            if (tid < w) s_m[tid] = fmaxf(s_m[tid], s_m[tid + w]);
-            __syncthreads();
-        }
-        if (tid == 0) st[q] = s_m[0];
-        return;
-    }
-    // q == 5: row sums (thread r < 64: w1 row r; 64 <= r < 128: w2 row r - 64)
-    if (tid < 128) {
-        const bool c2 = tid >= 64;
-        const int r = tid & 63;
-        const size_t len = c2 ? 2560 : 160;
-        const float* w = blob + (c2 ? 64 * 160 + 64 : 0) + (size_t)r * len;
-        double a = 0.0;
-        for (size_t i = 0; i < len; ++i) a += fabs((double)w[i]);
-        s_r[tid] = a;
-    }
-    __syncthreads();
-    if (tid < 2) {
-        double best = 0.0;
-        for (int r = 0; r < 64; ++r) best = fmax(best, s_r[tid * 64 + r]);
-        reinterpret_cast<double*>(st + 6)[tid] = best;
-    }
-}
-
-// one thread per 8-value fragment of the three GEMM layers (same fragment orders as kws_load_cnn_trad), bit for bit the host packing
-__device__ void ct_pack_frag(const float (&v)[8], uint32_t* img, size_t o3, size_t o2, float scale) {
-    uint32_t w3[3][4] = {}, w2[2][4] = {};
-    for (int j = 0; j < 8; ++j) {
-        float r = v[j];
-        for (int pc = 0; pc < 3; ++pc) {
-            const uint32_t u = __builtin_bit_cast(uint32_t, r) & 0xffff0000u;
-            r -= __builtin_bit_cast(float, u);
-            w3[pc][j >> 1] |= (u >> 16) << (16 * (j & 1));
-        }
-        const float x = v[j] * scale;
-        const _Float16 hh = (_Float16)x;
-        const _Float16 ll = (_Float16)((x - (float)hh) * 2048.f);
-        w2[0][j >> 1] |= (uint32_t)__builtin_bit_cast(uint16_t, hh) << (16 * (j & 1));
-        w2[1][j >> 1] |= (uint32_t)__builtin_bit_cast(uint16_t, ll) << (16 * (j & 1));
-    }
-    for (int pc = 0; pc < 3; ++pc)
-        for (int i = 0; i < 4; ++i) img[o3 + pc * 64 * 4 + i] = w3[pc][i];
-    for (int pc = 0; pc < 2; ++pc)
-        for (int i = 0; i < 4; ++i) img[o2 + pc * 64 * 4 + i] = w2[pc][i];
-}
-struct CtPackArgs {
-    size_t o_c1s, o_c2s, o_lin, o_c1h, o_c2h, o_linh;
-    float sw1, sw2, swl;
-};
-__global__ __launch_bounds__(256) void kws_ct_load_pack_kernel(const float* __restrict__ blob, CtPackArgs a, uint32_t* __restrict__ img) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const float* w1 = blob;
-    const float* w2 = blob + 64 * 160 + 64;
-    const float* wl = w2 + 163840 + 64;
-    const size_t FLAT = 64 * 297;
-    float v[8];
-    const int l = i & 63;
-    if (i < 10 * 2 * 64) {  // conv1 (kb, ct, l)
-        const int kb = i / 128, ct = (i / 64) & 1, co = 32 * ct + (l & 31), kh = 2 * kb + (l >> 5);
-        for (int j = 0; j < 8; ++j) v[j] = w1[(co * 20 + kh) * 8 + j];
-        ct_pack_frag(v, img, a.o_c1s + ((size_t)(kb * 2 + ct) * 3 * 64 + l) * 4, a.o_c1h + ((size_t)(kb * 2 + ct) * 2 * 64 + l) * 4, a.sw1);
-        return;
-    }
-    int k = i - 10 * 2 * 64;
-    if (k < 40 * 4 * 2 * 64) {  // conv2 (kk, cb, ct, l)
-        const int kk = k / 512, cb = (k / 128) & 3, ct = (k / 64) & 1, co = 32 * ct + (l & 31), kh = kk >> 2, kw = kk & 3;
-        for (int j = 0; j < 8; ++j) v[j] = w2[((co * 64 + 16 * cb + 8 * (l >> 5) + j) * 10 + kh) * 4 + kw];
-        const size_t f = ((size_t)kk * 4 + cb) * 2 + ct;
-        ct_pack_frag(v, img, a.o_c2s + (f * 3 * 64 + l) * 4, a.o_c2h + (f * 2 * 64 + l) * 4, a.sw2);
-        return;
-    }
-    k -= 40 * 4 * 2 * 64;
-    if (k < (int)(FLAT / 16) * 64) {  // lin (kb, l)
-        const size_t kb = k / 64;
-        for (int j = 0; j < 8; ++j) v[j] = wl[(size_t)(l & 31) * FLAT + 16 * kb + 8 * (l >> 5) + j];
-        ct_pack_frag(v, img, a.o_lin + (kb * 3 * 64 + l) * 4, a.o_linh + (kb * 2 * 64 + l) * 4, a.swl);
-    }
-}
-// The f32 sections (biases, dnn, fc), the alignment padding (zero) and the raw blob.
-struct CtCopyArgs {
-    size_t o_c1b, o_c2b, o_linb, o_dnn, o_raw, n_floats;
-    size_t pad1, n_pad1, pad2, n_pad2;  // padding words in front of the f16-pair images and behind the blob
-};
-__global__ __launch_bounds__(256) void kws_ct_load_copy_kernel(const float* __restrict__ blob, CtCopyArgs a, uint32_t* __restrict__ img) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= a.n_floats) return;
-    const uint32_t u = __builtin_bit_cast(uint32_t, blob[i]);
-    img[a.o_raw + i] = u;
-    const size_t o_b1 = 64 * 160, o_b2 = o_b1 + 64 + 163840, o_bl = o_b2 + 64 + (size_t)32 * 19008, o_dnn = o_bl + 32;
-    if (i >= o_b1 && i < o_b1 + 64) img[a.o_c1b + i - o_b1] = u;
-    if (i >= o_b2 && i < o_b2 + 64) img[a.o_c2b + i - o_b2] = u;
-    if (i >= o_bl && i < o_bl + 32) img[a.o_linb + i - o_bl] = u;
-    if (i >= o_dnn) img[a.o_dnn + i - o_dnn] = u;  // dnn_w | dnn_b | fc_w | fc_b: contiguous in both
-    if (i < a.n_pad1) img[a.pad1 + i] = 0u;
-    if (i < a.n_pad2) img[a.pad2 + i] = 0u;
-}
-
-int kws_load_cnn_trad_device(kws_ctx* c, const float* d_blob, size_t n_floats, int num_classes) {
-    static const char* fn = "kws_load_cnn_trad_device";
-    KWS_GUARD_BEGIN
-    if (!c) return KWS_EINVAL;
-    if (!d_blob) return fail(c, KWS_EINVAL, std::string(fn) + ": blob is NULL");
-    int rc = check_cnntrad_blob(c, fn, n_floats, num_classes);
-    if (rc) return rc;
-    const CtLayout L(num_classes);
-    HIP_TRY(c, hipSetDevice(c->device));
-    uint32_t* d = static_cast<uint32_t*>(c->d_cnntrad);
-    if (!d || c->ct_image_words != L.total) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        d = nullptr;
-        if (hipMalloc(reinterpret_cast<void**>(&d), L.total * sizeof(uint32_t)) != hipSuccess)
-            return fail(c, KWS_ENOMEM, std::string(fn) + ": device allocation failed");
-    }
-    if (!c->d_ct_stats) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_ct_stats), 16 * sizeof(float)));
-    hipStream_t s = c->stream;
-    hipLaunchKernelGGL(kws_ct_load_stats_kernel, dim3(6), dim3(1024), 0, s, d_blob, c->d_ct_stats);
-    HIP_TRY(c, hipGetLastError());
-    float st[10];
-    HIP_TRY(c, hipMemcpyAsync(st, c->d_ct_stats, sizeof st, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    double rows[2];
-    memcpy(rows, st + 6, sizeof rows);
-    const float sw1 = pow2_scale_of_max(st[0]), sw2 = pow2_scale_of_max(st[1]), swl = pow2_scale_of_max(st[2]);
-    CtPackArgs pa{L.o_c1s, L.o_c2s, L.o_lin, L.o_c1h, L.o_c2h, L.o_linh, sw1, sw2, swl};
-    const int n_frag = 10 * 2 * 64 + 40 * 4 * 2 * 64 + (64 * 297 / 16) * 64;
-    hipLaunchKernelGGL(kws_ct_load_pack_kernel, dim3((n_frag + 255) / 256), dim3(256), 0, s, d_blob, pa, d);
-    HIP_TRY(c, hipGetLastError());
-    CtCopyArgs ca{L.o_c1b, L.o_c2b, L.o_linb, L.o_dnn, L.o_raw, n_floats, L.o_fcb + num_classes, L.o_c1h - (L.o_fcb + num_classes),
-                  L.o_raw + n_floats, L.total - (L.o_raw + n_floats)};
-    hipLaunchKernelGGL(kws_ct_load_copy_kernel, dim3((unsigned)((n_floats + 255) / 256)), dim3(256), 0, s, d_blob, ca, d);
-    HIP_TRY(c, hipGetLastError());
-    install_cnntrad(c, d, L, num_classes, sw1, sw2, swl, (float)(rows[0] * 1.0000002), (float)(rows[1] * 1.0000002), st[3], st[4]);
-    return KWS_OK;
-    KWS_GUARD_END(c, "kws_load_cnn_trad_device")
-}
-
 // Grow the context's float scratch (convolution outputs between two kernels of one call) to at least `need` floats.
 static int grow_conv_ws(kws_ctx* c, size_t need, const std::string& fn) {
-    if (need <= c->conv_ws_floats) return KWS_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    float* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), need * sizeof(float)) != hipSuccess)
-        return fail(c, KWS_ENOMEM, fn + ": workspace allocation failed");
-    if (c->d_conv_ws) (void)hipFree(c->d_conv_ws);
-    c->d_conv_ws = d;
-    c->conv_ws_floats = need;
-    return KWS_OK;
+    return grow_device_buffer(c, c->d_conv_ws, c->conv_ws_floats, need, fn.c_str(), "workspace");
 }
 
 int kws_dsblock_forward_f32(kws_ctx* c, const float* d_x, int B, int C_in, int H, int W, const float* d_dw_w, const float* d_dw_b,
@@ -1820,23 +1016,9 @@ int kws_spec_f32(kws_ctx* c, const float* d_frames, int num_frames, int frame_le
         return fail(c, KWS_EUNSUPPORTED, "kws_spec_f32: NFFT must be a power of two in [64, 4096] or any value in [2, 2048]");
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->spec_nfft != nfft) {  // float64 twiddles of this transform length, kept until another length is asked for
-        std::vector<double> tw(2 * (size_t)nfft);
-        const double pi = 3.14159265358979323846;
-        for (int k = 0; k < nfft; ++k) {
-            tw[2 * k] = std::cos(2.0 * pi * k / nfft);
-            tw[2 * k + 1] = -std::sin(2.0 * pi * k / nfft);
-        }
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        double* d = nullptr;
-        if (hipMalloc(reinterpret_cast<void**>(&d), sizeof(double) * tw.size()) != hipSuccess)
-            return fail(c, KWS_ENOMEM, "kws_spec_f32: device allocation failed");
-        hipError_t e = hipMemcpy(d, tw.data(), sizeof(double) * tw.size(), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(d);
-            return fail_hip(c, e, "kws_spec_f32: hipMemcpy");
-        }
-        if (c->d_spec_tw64) (void)hipFree(c->d_spec_tw64);
-        c->d_spec_tw64 = d;
+        const std::vector<double> tw = build_twiddle64(nfft);
+        rc = replace_device_image(c, c->d_spec_tw64, tw.data(), sizeof(double) * tw.size(), "kws_spec_f32");
+        if (rc) return rc;
         c->spec_nfft = nfft;
     }
     HIP_TRY(c, launch_spec_f64(c->stream, c->d_spec_tw64, d_frames, num_frames, frame_len, nfft, log2n, power, d_spec));
@@ -1886,66 +1068,6 @@ int kws_prof_read(kws_ctx* c, int kernel_id, double* total_ms, int* launches) {
     if (rc) return rc;
     if (total_ms) *total_ms = c->ms_total[kernel_id];
     if (launches) *launches = (int)c->launches[kernel_id];
-    return KWS_OK;
-}
-
-// ---- host-only helpers -----------------------------------------------------------------------------
-int kws_host_mel_edges(int nfilt, int nfft, int sample_rate, int* edges_out) {
-    if (!edges_out || nfilt < 1 || nfft < 2 || sample_rate < 1) return KWS_EINVAL;
-    std::vector<int> e;
-    mel_edges(nfilt, nfft, sample_rate, e);
-    memcpy(edges_out, e.data(), sizeof(int) * e.size());
-    return KWS_OK;
-}
-
-int kws_host_mel_dense(int nfilt, int nfft, int sample_rate, float* fb_out) {
-    if (!fb_out) return KWS_EINVAL;
-    MelHost mel;
-    std::string err;
-    if (!build_mel_host(nfilt, nfft, sample_rate, mel, err)) return KWS_EUNSUPPORTED;
-    const int nb = nfft / 2 + 1;
-    std::fill(fb_out, fb_out + (size_t)nfilt * nb, 0.f);
-    // expand exactly what the kernel evaluates: filter j = rising weights of its chunks + falling weights
-    // of the next segment's chunks
-    for (int j = 0; j < nfilt; ++j) {
-        const uint32_t g = mel.gather[j];
-        const int r0 = g & 255, nr = (g >> 8) & 255, q0 = (g >> 16) & 255, nq = g >> 24;
-        for (int c = r0; c < r0 + nr; ++c)
-            for (int i = 0; i < MEL_CHUNK; ++i) {
-                const int k = mel.k0[c] + i;
-                if (k < nb) fb_out[(size_t)j * nb + k] += mel.rw[i * 64 + c];
-            }
-        for (int c = q0; c < q0 + nq; ++c)
-            for (int i = 0; i < MEL_CHUNK; ++i) {
-                const int k = mel.k0[c] + i;
-                if (k < nb) fb_out[(size_t)j * nb + k] += mel.fw[i * 64 + c];
-            }
-    }
-    return KWS_OK;
-}
-
-int kws_host_mel_layout(int nfilt, int nfft, int sample_rate, int* first_lane_out, int* n_lanes_out, int* lanes_used, int* row_safe) {
-    if (!first_lane_out || !n_lanes_out) return KWS_EINVAL;
-    MelHost mel;
-    std::string err;
-    if (!build_mel_host(nfilt, nfft, sample_rate, mel, err)) return KWS_EUNSUPPORTED;
-    // segment s = filter s's rising side; the last segment is the falling side of the last filter
-    for (int j = 0; j < nfilt; ++j) {
-        first_lane_out[j] = (int)(mel.gather[j] & 255);
-        n_lanes_out[j] = (int)((mel.gather[j] >> 8) & 255);
-    }
-    first_lane_out[nfilt] = (int)((mel.gather[nfilt - 1] >> 16) & 255);
-    n_lanes_out[nfilt] = (int)(mel.gather[nfilt - 1] >> 24);
-    if (lanes_used) *lanes_used = mel.n_chunks;
-    if (row_safe) *row_safe = (mel.seg[0] & 64) ? 1 : 0;
-    return KWS_OK;
-}
-
-int kws_host_dct_lifter(int nfilt, int numcep, int ceplifter, float* out) {
-    if (!out || nfilt < 1 || numcep < 1) return KWS_EINVAL;
-    std::vector<float> t;
-    build_dct_lifter_host(nfilt, numcep, ceplifter, t);
-    memcpy(out, t.data(), sizeof(float) * t.size());
     return KWS_OK;
 }
 

@@ -601,19 +601,6 @@ hipError_t set_lds_limits() {
     return hipSuccess;
 }
 
-// Grow the context's training workspace (shared with kws_dscnn_backward_f32) to at least `need` floats.
-int grow_ws(kws_ctx* c, size_t need, const char* fn) {
-    if (need <= c->train_ws_floats) return KWS_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    float* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), need * sizeof(float)) != hipSuccess)
-        return fail(c, KWS_ENOMEM, std::string(fn) + ": workspace allocation failed");
-    if (c->d_train_ws) (void)hipFree(c->d_train_ws);
-    c->d_train_ws = d;
-    c->train_ws_floats = need;
-    return KWS_OK;
-}
-
 // The recompute (and, with d_dl, the backward) in chunks of at most MAX_CHUNK clips.  Debug mode (d_dl == NULL): conv2's output
 // goes to dbg_conv2 and [h | d] to dbg_hidden instead of the workspace, conv1's output and the winners to dbg_conv1 / dbg_win.
 int run(kws_ctx* c, const char* fn, const float* d_feat, int B, const float* d_dl, float* d_grad, float* dbg_conv1, int32_t* dbg_win,
@@ -625,7 +612,9 @@ int run(kws_ctx* c, const char* fn, const float* d_feat, int B, const float* d_d
     const size_t per_clip = 4 * (size_t)CT_FLAT + CT_FLAT / 4 + 160 + 32;  // yp, y2, dz2, dz1 | winners (bytes) | h, d | dh
     const int g_conv = std::min(chunk, CONV_GROUPS), g_tail = (chunk + TAIL_CPG - 1) / TAIL_CPG;
     const size_t part_n = std::max({(size_t)g_conv * C2W_PART, (size_t)g_tail * tail_part_floats(C), (size_t)g_conv * C1W_PART});
-    int rc = grow_ws(c, (size_t)chunk * per_clip + 2 * (size_t)W2_N + part_n, fn);
+    // the training workspace is shared with kws_dscnn_backward_f32
+    int rc = grow_device_buffer(c, c->d_train_ws, c->train_ws_floats, (size_t)chunk * per_clip + 2 * (size_t)W2_N + part_n,
+                                fn, "workspace");
     if (rc) return rc;
     float* ws = c->d_train_ws;
     auto take = [&](size_t n) {

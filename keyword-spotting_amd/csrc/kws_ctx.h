@@ -1,5 +1,5 @@
-// The context behind the C ABI (include/kws_hip.h) and the error plumbing shared by the translation units that
-// implement it (kws_api.hip, kws_ingest.hip).
+// The context behind the C ABI (include/kws_hip.h), the error plumbing and the device-memory helpers shared by the translation
+// units that implement it (kws_api.hip, kws_weights.hip, kws_ingest.hip, kws_*_bwd.hip).
 #pragma once
 #include <new>
 
@@ -131,3 +131,41 @@ inline int fail_hip(kws_ctx* c, hipError_t e, const char* what) {
         if (_e != hipSuccess) return fail_hip(c, _e, #expr); \
     } while (0)
 
+// Retire the captured streaming push (it holds table and weight pointers by value); the caller has drained the stream.
+inline void drop_stream_graph(kws_ctx* c) {
+    if (c->stream_graph) (void)hipGraphExecDestroy(c->stream_graph);
+    c->stream_graph = nullptr;
+    c->graph_key[0] = c->graph_key[1] = c->graph_key[2] = nullptr;
+}
+
+// Swap a device allocation for a fresh copy of `bytes` host bytes: drain the stream (kernels may be reading the old one),
+// allocate, copy, free the old allocation, store the pointer.  On failure the context keeps what it had.
+template <class T>
+int replace_device_image(kws_ctx* c, T*& slot, const void* host, size_t bytes, const char* fn) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    void* d = nullptr;
+    if (hipMalloc(&d, bytes) != hipSuccess) return fail(c, KWS_ENOMEM, std::string(fn) + ": device allocation failed");
+    hipError_t e = hipMemcpy(d, host, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return fail_hip(c, e, (std::string(fn) + ": hipMemcpy").c_str());
+    }
+    if (slot) (void)hipFree(slot);
+    slot = static_cast<T*>(d);
+    return KWS_OK;
+}
+
+// Grow a workspace to at least `need` elements (contents are not kept): nothing when it is large enough, else drain the
+// stream, allocate, free the old one, store pointer and capacity.  KWS_ENOMEM reads "<fn>: <what> allocation failed".
+template <class T>
+int grow_device_buffer(kws_ctx* c, T*& buf, size_t& cap, size_t need, const char* fn, const char* what) {
+    if (need <= cap) return KWS_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    T* d = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d), need * sizeof(T)) != hipSuccess)
+        return fail(c, KWS_ENOMEM, std::string(fn) + ": " + what + " allocation failed");
+    if (buf) (void)hipFree(buf);
+    buf = d;
+    cap = need;
+    return KWS_OK;
+}

@@ -336,19 +336,6 @@ hipError_t reduce(hipStream_t s, const float* part, int G, int n, float* out, bo
     return hipGetLastError();
 }
 
-// Grow the context's training workspace to at least `need` floats.
-int grow_train_ws(kws_ctx* c, size_t need) {
-    if (need <= c->train_ws_floats) return KWS_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    float* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), need * sizeof(float)) != hipSuccess)
-        return fail(c, KWS_ENOMEM, "kws_dscnn_backward_f32: workspace allocation failed");
-    if (c->d_train_ws) (void)hipFree(c->d_train_ws);
-    c->d_train_ws = d;
-    c->train_ws_floats = need;
-    return KWS_OK;
-}
-
 }  // namespace
 }  // namespace kws
 
@@ -386,7 +373,8 @@ int kws_dscnn_backward_f32(kws_ctx* c, const float* d_feat, int B, int T, int F,
     const size_t by_budget = std::max<size_t>(1, ((size_t)1 << 31) / per_clip);
     const int chunk = (int)std::min<size_t>({(size_t)B, 16384, by_budget});
     const int g_max = std::min(chunk, BWD_MAX_GROUPS);  // partial rows: G = ceil(nb / ceil(nb / 1024)) <= min(nb, 1024)
-    int rc = grow_train_ws(c, (size_t)chunk * per_clip + (size_t)g_max * C1_PART);
+    int rc = grow_device_buffer(c, c->d_train_ws, c->train_ws_floats, (size_t)chunk * per_clip + (size_t)g_max * C1_PART,
+                                fn, "workspace");
     if (rc) return rc;
     float* ws = c->d_train_ws;
     float* a0 = ws;

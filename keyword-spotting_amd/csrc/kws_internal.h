@@ -78,20 +78,6 @@ struct FrontendTables {
     const double* dct64;       // [numcep][nfilt]  DCT-II ortho x lifter
 };
 
-// Host-side construction of the sparse mel decomposition (also used by the host-only ABI helpers).
-struct MelHost {
-    std::vector<int> edges;            // nfilt+2
-    std::vector<int> k0;               // 64
-    std::vector<float> rw, fw;         // 8*64 each, [i][lane]
-    std::vector<uint32_t> gather;      // 64
-    std::vector<int> slot;             // nfft/2 (bin 256 belongs to no filter)
-    std::vector<int> seg;              // 64
-    int n_chunks = 0;
-};
-bool build_mel_host(int nfilt, int nfft, int sample_rate, MelHost& out, std::string& err);
-void build_dct_lifter_host(int nfilt, int numcep, int ceplifter, std::vector<float>& out);
-void build_twiddle_host(std::vector<float2>& out);
-
 hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTables& t,
                        const int16_t* d_wav, int B, float* d_out);
 hipError_t launch_mfcc_f32(hipStream_t s, const FrontendParams& p, const FrontendTables& t,

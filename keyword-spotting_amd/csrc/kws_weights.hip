@@ -1,0 +1,421 @@
+// Model weights: the device images of the DS-CNN and of cnn-trad-fpool3 (layouts: kws_internal.h), built on the host by pure
+// functions of the state_dict blob, the upload / install behind the kws_load_* entries, cnn-trad-fpool3's device-side loader and
+// the host-only image exports.  Every weight bit comes from kws_pack.h.
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+
+#include "kws_ctx.h"
+#include "kws_pack.h"
+
+using namespace kws;
+
+static float max_abs(const float* w, size_t n) {
+    float m = 0.f;
+    for (size_t i = 0; i < n; ++i) m = std::max(m, std::fabs(w[i]));
+    return m;
+}
+// The bound terms the per-clip activation scales are derived from: max|b| and max over rows of sum |w| (one float64 chain per
+// row), rounded up.
+static double max_row_sum(const float* w, int rows, size_t row_len) {
+    double best = 0.0;
+    for (int r = 0; r < rows; ++r) {
+        double a = 0.0;
+        for (size_t i = 0; i < row_len; ++i) a += std::fabs((double)w[(size_t)r * row_len + i]);
+        best = std::max(best, a);
+    }
+    return best;
+}
+static float bound_of_row_sum(double best) { return (float)(best * 1.0000002); }  // rounded up
+static float max_row_abs_sum(const float* w, int rows, size_t row_len) { return bound_of_row_sum(max_row_sum(w, rows, row_len)); }
+
+// The device image of a DS-CNN blob (units: floats): c1_w [100][64] | c1_b [64] | dw [4][32][24] | pw_w [4][cin][cout] | pw_b [4][64] |
+// fc_w | fc_b | splits | conv1 as [ci][tap][cout] | the blob itself | the f16-pair images.
+struct DscnnLayout {
+    size_t c1_floats, n_floats;
+    size_t o_c1w, o_c1b, o_dw, o_pww, o_pwb, o_fcw, o_fcb, o_split, o_c1s, o_c1g, o_raw, o_pwp, o_c1p, total;
+    DscnnLayout(int num_classes, int input_channels) {
+        c1_floats = (size_t)6400 * input_channels;
+        n_floats = c1_floats + 64 + 4 * (576 + 64 + 4096 + 64) + (size_t)num_classes * 64 + num_classes;
+        o_c1w = 0, o_c1b = o_c1w + 6400, o_dw = o_c1b + 64, o_pww = o_dw + 4 * 64 * 12, o_pwb = o_pww + 4 * 4096, o_fcw = o_pwb + 4 * 64,
+        o_fcb = o_fcw + (size_t)num_classes * 64, o_split = (o_fcb + num_classes + 3) & ~(size_t)3, o_c1s = o_split + 4 * 2 * 4 * 3 * 64 * 4,
+        o_c1g = o_c1s + 2 * 7 * 3 * 64 * 4, o_raw = o_c1g + c1_floats, o_pwp = (o_raw + n_floats + 3) & ~(size_t)3,
+        o_c1p = o_pwp + 4 * 2 * 4 * 2 * 64 * 4, total = o_c1p + 2 * 7 * 2 * 64 * 4;
+    }
+};
+
+static int check_dscnn_blob(kws_ctx* c, const char* fn, size_t n_floats, int num_classes, int input_channels) {
+    if (num_classes < 1 || num_classes > MAX_CLASSES) return fail(c, KWS_EUNSUPPORTED, std::string(fn) + ": num_classes must be in [1, 64]");
+    if (input_channels < 1 || input_channels > 64) return fail(c, KWS_EUNSUPPORTED, std::string(fn) + ": input_channels must be in [1, 64]");
+    const size_t expect = DscnnLayout(num_classes, input_channels).n_floats;
+    if (n_floats != expect) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "%s: expected %zu floats for %d classes and %d input channel(s), got %zu", fn, expect, num_classes,
+                 input_channels, n_floats);
+        return fail(c, KWS_EINVAL, msg);
+    }
+    return KWS_OK;
+}
+
+// The host image h of a checked blob and the members DscnnWeights carries by value (its pointers stay null).
+static void build_dscnn_image(const float* blob, const DscnnLayout& L, int num_classes, int input_channels, std::vector<float>& h,
+                              DscnnWeights& mw) {
+    mw = DscnnWeights{};
+    mw.num_classes = num_classes;
+    mw.in_channels = input_channels;
+    h.assign(L.total, 0.f);
+    uint32_t* const img = reinterpret_cast<uint32_t*>(h.data());
+    const float* src = blob;
+    memcpy(&h[L.o_raw], blob, L.n_floats * sizeof(float));  // torch layouts, for the composed any-map path (kws_forward_map_f32)
+    // conv1.weight [64][C][10][10] -> [ci][tap][cout] (kws_conv1_general_kernel for C > 1, kws_conv1_any_kernel for any map)
+    for (int co = 0; co < 64; ++co)
+        for (int ci = 0; ci < input_channels; ++ci)
+            for (int k = 0; k < 100; ++k) h[L.o_c1g + ((size_t)ci * 100 + k) * 64 + co] = src[((size_t)co * input_channels + ci) * 100 + k];
+    if (input_channels == 1) {
+        for (int co = 0; co < 64; ++co)  // conv1.weight [64][1][10][10] -> [k][cout]
+            for (int k = 0; k < 100; ++k) h[L.o_c1w + (size_t)k * 64 + co] = src[co * 100 + k];
+        // conv1 as MFMA A operands (32x32x16), lane l of (ct, kb): cout = 32ct + (l&31); half-wave l >> 5 takes kernel rows
+        // 5(l>>5) .. + 4, i.e. 50 consecutive taps w[0..49], in two K orders:
+        //   bf16 image: w[8kb + j], zeros from 50 on -- both halves walk the same offsets 10*(kh%5) + kw, so their LDS addresses differ
+        //               by a constant
+        //   f16 image (the pre-split windows, kws_dscnn.hip, conv1_unit_pairwin): kb < 5: row kb, taps kw = j; kb = 5: taps
+        //               kw = 8 + (j & 1) of row j >> 1; kb = 6: taps kw = 8 + j (j < 2) of row 4, then zeros
+        const float sw = pow2_scale_of_max(max_abs(src, 6400));
+        int ke;
+        (void)std::frexp(sw, &ke);
+        mw.k_c1 = ke - 1;  // sw = 2^(ke - 1)
+        for (int ct = 0; ct < 2; ++ct)
+            for (int kb = 0; kb < 7; ++kb)
+                for (int l = 0; l < 64; ++l) {
+                    const float* w = src + (32 * ct + (l & 31)) * 100 + 50 * (l >> 5);
+                    float v3[8], v2[8];
+                    for (int j = 0; j < 8; ++j) {
+                        const int t = kb < 5 ? 10 * kb + j : kb == 5 ? 10 * (j >> 1) + 8 + (j & 1) : j < 2 ? 48 + j : -1;
+                        v3[j] = 8 * kb + j < 50 ? w[8 * kb + j] : 0.f;
+                        v2[j] = t >= 0 ? w[t] : 0.f;
+                    }
+                    pack_bf16_triple(v3, img + L.o_c1s + ((size_t)(ct * 7 + kb) * 3 * 64 + l) * 4);
+                    pack_f16_pair(v2, sw, 1.f, img + L.o_c1p + ((size_t)(ct * 7 + kb) * 2 * 64 + l) * 4);
+                }
+        mw.c1_abs = max_row_abs_sum(src, 64, 100);
+        mw.c1_bmax = max_abs(src + 6400, 64);
+    }
+    src += L.c1_floats;
+    memcpy(&h[L.o_c1b], src, 64 * sizeof(float));
+    src += 64;
+    for (int b = 0; b < 4; ++b) {
+        const float *dw_w = src, *dw_b = src + 576, *pw_w = src + 640, *pw_b = src + 640 + 4096;
+        for (int ch = 0; ch < 64; ++ch) {  // channel PAIRS interleaved, 24 floats per pair: (tap t of ch, of ch + 1) at 2t, the biases at 18, 19
+            float* q = &h[L.o_dw + ((size_t)b * 32 + ch / 2) * 24 + (ch & 1)];
+            for (int t = 0; t < 9; ++t) q[2 * t] = dw_w[ch * 9 + t];
+            q[18] = dw_b[ch];
+        }
+        for (int co = 0; co < 64; ++co)  // pointwise.weight [cout][cin][1][1] -> [cin][cout]
+            for (int ci = 0; ci < 64; ++ci) h[L.o_pww + (size_t)b * 4096 + (size_t)ci * 64 + co] = pw_w[co * 64 + ci];
+        memcpy(&h[L.o_pwb + (size_t)b * 64], pw_b, 64 * sizeof(float));
+        // the same weights as MFMA A operands (32x32x16): lane l of (ct, m) holds cin = 16m + 8(l>>5) + j, j = 0..7, of
+        // cout = 32ct + (l&31)
+        const float sw = pow2_scale_of_max(max_abs(pw_w, 4096));
+        int ke;
+        (void)std::frexp(sw, &ke);
+        mw.k_pw[b] = ke - 1;
+        for (int ct = 0; ct < 2; ++ct)
+            for (int m = 0; m < 4; ++m)
+                for (int l = 0; l < 64; ++l) {
+                    float v[8];
+                    for (int j = 0; j < 8; ++j) v[j] = pw_w[(32 * ct + (l & 31)) * 64 + 16 * m + 8 * (l >> 5) + j];
+                    const size_t f = (size_t)(b * 2 + ct) * 4 + m;
+                    pack_bf16_triple(v, img + L.o_split + (f * 3 * 64 + l) * 4);
+                    pack_f16_pair(v, sw, 1.f, img + L.o_pwp + (f * 2 * 64 + l) * 4);
+                }
+        mw.dw_abs[b] = max_row_abs_sum(dw_w, 64, 9);
+        mw.pw_abs[b] = max_row_abs_sum(pw_w, 64, 64);
+        mw.dw_bmax[b] = max_abs(dw_b, 64);
+        mw.pw_bmax[b] = max_abs(pw_b, 64);
+        src += 576 + 64 + 4096 + 64;
+    }
+    memcpy(&h[L.o_fcw], src, (size_t)num_classes * 64 * sizeof(float));
+    src += (size_t)num_classes * 64;
+    memcpy(&h[L.o_fcb], src, (size_t)num_classes * sizeof(float));
+}
+
+static int check_cnntrad_blob(kws_ctx* c, const char* fn, size_t n_floats, int num_classes) {
+    if (num_classes < 1 || num_classes > MAX_CLASSES) return fail(c, KWS_EUNSUPPORTED, std::string(fn) + ": num_classes must be in [1, 64]");
+    const size_t expect = CtLayout(num_classes).n_floats;
+    if (n_floats != expect) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "%s: expected %zu floats for %d classes, got %zu", fn, expect, num_classes, n_floats);
+        return fail(c, KWS_EINVAL, msg);
+    }
+    return KWS_OK;
+}
+
+// The members CnnTradWeights carries by value (its pointers stay null) from the layers' statistics, for the host and the device
+// loader alike: the scales, the largest row sums of |w1|, |w2| and max|b1|, max|b2|.
+static CnnTradWeights ct_scalars(int num_classes, float sw1, float sw2, float swl, double row1, double row2, float b1_max, float b2_max) {
+    CnnTradWeights w{};
+    w.num_classes = num_classes;
+    w.inv_sw1 = 1.f / sw1;
+    w.inv_sw2 = 1.f / sw2;
+    w.inv_swl = 1.f / swl;
+    w.w1_abs = bound_of_row_sum(row1);
+    w.w2_abs = bound_of_row_sum(row2);
+    w.b1_max = b1_max;
+    w.b2_max = b2_max;
+    return w;
+}
+
+// The host image h of a checked blob and the members CnnTradWeights carries by value (its pointers stay null).
+static void build_cnntrad_image(const float* blob, const CtLayout& L, int num_classes, std::vector<uint32_t>& h, CnnTradWeights& w) {
+    h.assign(L.total, 0u);
+    const float sw1 = pow2_scale_of_max(max_abs(blob + L.b_w1, L.n_c1)), sw2 = pow2_scale_of_max(max_abs(blob + L.b_w2, L.n_c2)),
+                swl = pow2_scale_of_max(max_abs(blob + L.b_wl, L.n_lin));
+    for (size_t i = 0; i < CtLayout::N_FRAG; ++i) ct_pack_fragment(L, blob, i, sw1, sw2, swl, h.data());
+    auto put = [&](size_t off, size_t src, size_t n) { memcpy(&h[off], blob + src, n * sizeof(float)); };
+    put(L.o_c1b, L.b_b1, CtLayout::CO);
+    put(L.o_c2b, L.b_b2, CtLayout::CO);
+    put(L.o_linb, L.b_bl, 32);
+    put(L.o_dnn, L.b_wd, L.n_floats - L.b_wd);  // dnn_w | dnn_b | fc_w | fc_b: contiguous in both
+    put(L.o_raw, 0, L.n_floats);
+    w = ct_scalars(num_classes, sw1, sw2, swl, max_row_sum(blob + L.b_w1, CtLayout::CO, L.n_c1 / CtLayout::CO),
+                   max_row_sum(blob + L.b_w2, CtLayout::CO, L.n_c2 / CtLayout::CO), max_abs(blob + L.b_b1, CtLayout::CO),
+                   max_abs(blob + L.b_b2, CtLayout::CO));
+}
+
+// Point the context at a complete device image d (layout L); w holds the values CnnTradWeights carries by value.
+static void install_cnntrad(kws_ctx* c, uint32_t* d, const CtLayout& L, const CnnTradWeights& w) {
+    if (c->d_cnntrad && c->d_cnntrad != d) (void)hipFree(c->d_cnntrad);
+    c->d_cnntrad = d;
+    c->ct_image_words = L.total;
+    const float* df = reinterpret_cast<const float*>(d);
+    c->tw = w;
+    c->tw.c1_split = d + L.o_c1s;
+    c->tw.c2_split = d + L.o_c2s;
+    c->tw.c1_b = df + L.o_c1b;
+    c->tw.c2_b = df + L.o_c2b;
+    c->tw.lin_split = d + L.o_lin;
+    c->tw.lin_b = df + L.o_linb;
+    c->tw.dnn_w = df + L.o_dnn;
+    c->tw.dnn_b = df + L.o_dnnb;
+    c->tw.fc_w = df + L.o_fc;
+    c->tw.fc_b = df + L.o_fcb;
+    c->tw.c1_h2 = d + L.o_c1h;
+    c->tw.c2_h2 = d + L.o_c2h;
+    c->tw.lin_h2 = d + L.o_linh;
+    c->ct_raw = df + L.o_raw;
+    c->cnntrad_ready = true;
+}
+
+// ---- kws_load_cnn_trad_device: the same image built on the device from a device-resident blob ----------------------------------
+// Statistics in the host's arithmetic: maxima of |w| (exact in any order; fmaxf drops NaN as std::max does there), the row sums of
+// max_row_abs_sum as ONE sequential float64 chain per row, in the host's order.  st: float [5] = max|w1|, max|w2|, max|wl|, max|b1|,
+// max|b2|, then (8-byte aligned) double [2] = the largest row sums of w1 and w2.  (extern "C": profilers show the plain names.)
+extern "C" __global__ __launch_bounds__(1024) void kws_ct_load_stats_kernel(const float* __restrict__ blob, CtLayout L, float* __restrict__ st) {
+    __shared__ float s_m[1024];
+    __shared__ double s_r[2 * CtLayout::CO];
+    const int tid = threadIdx.x, q = blockIdx.x;
+    if (q < 5) {  // one maximum per workgroup
+        const size_t off = q == 0 ? L.b_w1 : q == 1 ? L.b_w2 : q == 2 ? L.b_wl : q == 3 ? L.b_b1 : L.b_b2;
+        const size_t len = q == 0 ? L.n_c1 : q == 1 ? L.n_c2 : q == 2 ? L.n_lin : CtLayout::CO;
+        float m = 0.f;
+        for (size_t i = tid; i < len; i += 1024) m = fmaxf(m, fabsf(blob[off + i]));
+        s_m[tid] = m;
+        __syncthreads();
+        for (int w = 512; w > 0; w >>= 1) {
+            if (tid < w) s_m[tid] = fmaxf(s_m[tid], s_m[tid + w]);
+            __syncthreads();
+        }
+        if (tid == 0) st[q] = s_m[0];
+        return;
+    }
+    // q == 5: row sums (thread r < CO: w1 row r; CO <= r < 2 CO: w2 row r - CO)
+    constexpr int CO = (int)CtLayout::CO;
+    if (tid < 2 * CO) {
+        const bool c2 = tid >= CO;
+        const size_t len = (c2 ? L.n_c2 : L.n_c1) / CO;
+        const float* w = blob + (c2 ? L.b_w2 : L.b_w1) + (size_t)(tid % CO) * len;
+        double a = 0.0;
+        for (size_t i = 0; i < len; ++i) a += fabs((double)w[i]);
+        s_r[tid] = a;
+    }
+    __syncthreads();
+    if (tid < 2) {
+        double best = 0.0;
+        for (int r = 0; r < CO; ++r) best = fmax(best, s_r[tid * CO + r]);
+        reinterpret_cast<double*>(st + 6)[tid] = best;
+    }
+}
+
+// one thread per 8-value fragment of the three GEMM layers: the host loader's loop body, compiled for the device
+extern "C" __global__ __launch_bounds__(256) void kws_ct_load_pack_kernel(const float* __restrict__ blob, CtLayout L, float sw1, float sw2, float swl,
+                                                               uint32_t* __restrict__ img) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < CtLayout::N_FRAG) ct_pack_fragment(L, blob, i, sw1, sw2, swl, img);
+}
+// The f32 sections (biases, dnn, fc), the alignment padding (zero) in front of the f16-pair images and behind the blob, and the blob.
+extern "C" __global__ __launch_bounds__(256) void kws_ct_load_copy_kernel(const float* __restrict__ blob, CtLayout L, uint32_t* __restrict__ img) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= L.n_floats) return;
+    const uint32_t u = __builtin_bit_cast(uint32_t, blob[i]);
+    img[L.o_raw + i] = u;
+    if (i >= L.b_b1 && i < L.b_w2) img[L.o_c1b + i - L.b_b1] = u;
+    if (i >= L.b_b2 && i < L.b_wl) img[L.o_c2b + i - L.b_b2] = u;
+    if (i >= L.b_bl && i < L.b_wd) img[L.o_linb + i - L.b_bl] = u;
+    if (i >= L.b_wd) img[L.o_dnn + i - L.b_wd] = u;  // dnn_w | dnn_b | fc_w | fc_b: contiguous in both
+    const size_t pad1 = L.o_dnn + L.n_floats - L.b_wd, pad2 = L.o_raw + L.n_floats;
+    if (i < L.o_c1h - pad1) img[pad1 + i] = 0u;
+    if (i < L.total - pad2) img[pad2 + i] = 0u;
+}
+
+// Shared tail of the host-only image exports: report the size, and say whether out can take the image.
+static int export_room(size_t total, const uint32_t* out_words, size_t cap_words, size_t* need_words) {
+    if (need_words) *need_words = total;
+    return out_words && cap_words < total ? KWS_EINVAL : KWS_OK;
+}
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int kws_load_dscnn(kws_ctx* c, const float* blob, size_t n_floats, int num_classes) {
+    return kws_load_dscnn_ex(c, blob, n_floats, num_classes, 1);
+}
+
+int kws_load_dscnn_ex(kws_ctx* c, const float* blob, size_t n_floats, int num_classes, int input_channels) {
+    KWS_GUARD_BEGIN
+    if (!c) return KWS_EINVAL;
+    if (!blob) return fail(c, KWS_EINVAL, "kws_load_dscnn: blob is NULL");
+    int rc = check_dscnn_blob(c, "kws_load_dscnn", n_floats, num_classes, input_channels);
+    if (rc) return rc;
+    const DscnnLayout L(num_classes, input_channels);
+    std::vector<float> h;
+    DscnnWeights mw;  // (a local: the context keeps its old model if the upload below fails)
+    build_dscnn_image(blob, L, num_classes, input_channels, h, mw);
+
+    HIP_TRY(c, hipSetDevice(c->device));
+    rc = replace_device_image(c, c->d_model, h.data(), L.total * sizeof(float), "kws_load_dscnn");
+    if (rc) return rc;
+    drop_stream_graph(c);  // a captured push holds the old weight pointers by value
+    const float* d = c->d_model;
+    mw.c1_w = d + L.o_c1w;
+    mw.c1_b = d + L.o_c1b;
+    mw.dw_w = d + L.o_dw;
+    mw.pw_w = d + L.o_pww;
+    mw.pw_b = d + L.o_pwb;
+    mw.pw_split = reinterpret_cast<const uint32_t*>(d + L.o_split);
+    mw.c1_split = reinterpret_cast<const uint32_t*>(d + L.o_c1s);
+    mw.pw_pair = reinterpret_cast<const uint32_t*>(d + L.o_pwp);
+    mw.c1_pair = reinterpret_cast<const uint32_t*>(d + L.o_c1p);
+    mw.fc_w = d + L.o_fcw;
+    mw.fc_b = d + L.o_fcb;
+    mw.c1_general = d + L.o_c1g;
+    mw.raw = d + L.o_raw;
+    c->mw = mw;
+    c->model_ready = true;
+    return KWS_OK;
+    KWS_GUARD_END(c, "kws_load_dscnn")
+}
+
+int kws_load_cnn_trad(kws_ctx* c, const float* blob, size_t n_floats, int num_classes) {
+    KWS_GUARD_BEGIN
+    if (!c) return KWS_EINVAL;
+    if (!blob) return fail(c, KWS_EINVAL, "kws_load_cnn_trad: blob is NULL");
+    int rc = check_cnntrad_blob(c, "kws_load_cnn_trad", n_floats, num_classes);
+    if (rc) return rc;
+    const CtLayout L(num_classes);
+    std::vector<uint32_t> h;
+    CnnTradWeights w;
+    build_cnntrad_image(blob, L, num_classes, h, w);
+
+    HIP_TRY(c, hipSetDevice(c->device));
+    rc = replace_device_image(c, c->d_cnntrad, h.data(), L.total * sizeof(uint32_t), "kws_load_cnn_trad");
+    if (rc) return rc;
+    install_cnntrad(c, static_cast<uint32_t*>(c->d_cnntrad), L, w);
+    return KWS_OK;
+    KWS_GUARD_END(c, "kws_load_cnn_trad")
+}
+
+int kws_load_cnn_trad_device(kws_ctx* c, const float* d_blob, size_t n_floats, int num_classes) {
+    static const char* fn = "kws_load_cnn_trad_device";
+    KWS_GUARD_BEGIN
+    if (!c) return KWS_EINVAL;
+    if (!d_blob) return fail(c, KWS_EINVAL, std::string(fn) + ": blob is NULL");
+    int rc = check_cnntrad_blob(c, fn, n_floats, num_classes);
+    if (rc) return rc;
+    const CtLayout L(num_classes);
+    HIP_TRY(c, hipSetDevice(c->device));
+    uint32_t* d = static_cast<uint32_t*>(c->d_cnntrad);
+    if (!d || c->ct_image_words != L.total) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        d = nullptr;
+        if (hipMalloc(reinterpret_cast<void**>(&d), L.total * sizeof(uint32_t)) != hipSuccess)
+            return fail(c, KWS_ENOMEM, std::string(fn) + ": device allocation failed");
+    }
+    if (!c->d_ct_stats) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_ct_stats), 16 * sizeof(float)));
+    hipStream_t s = c->stream;
+    hipLaunchKernelGGL(kws_ct_load_stats_kernel, dim3(6), dim3(1024), 0, s, d_blob, L, c->d_ct_stats);
+    HIP_TRY(c, hipGetLastError());
+    float st[10];
+    HIP_TRY(c, hipMemcpyAsync(st, c->d_ct_stats, sizeof st, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    double rows[2];
+    memcpy(rows, st + 6, sizeof rows);
+    const float sw1 = pow2_scale_of_max(st[0]), sw2 = pow2_scale_of_max(st[1]), swl = pow2_scale_of_max(st[2]);
+    hipLaunchKernelGGL(kws_ct_load_pack_kernel, dim3((unsigned)((CtLayout::N_FRAG + 255) / 256)), dim3(256), 0, s, d_blob, L, sw1, sw2, swl, d);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(kws_ct_load_copy_kernel, dim3((unsigned)((n_floats + 255) / 256)), dim3(256), 0, s, d_blob, L, d);
+    HIP_TRY(c, hipGetLastError());
+    install_cnntrad(c, d, L, ct_scalars(num_classes, sw1, sw2, swl, rows[0], rows[1], st[3], st[4]));
+    return KWS_OK;
+    KWS_GUARD_END(c, "kws_load_cnn_trad_device")
+}
+
+// ---- host-only image exports ---------------------------------------------------------------------------------------------------
+int kws_host_dscnn_image(const float* blob, size_t n_floats, int num_classes, int input_channels, uint32_t* out_words, size_t cap_words,
+                         size_t* need_words, float* scalars) {
+    KWS_GUARD_BEGIN
+    if (!blob) return fail(nullptr, KWS_EINVAL, "kws_host_dscnn_image: blob is NULL");
+    int rc = check_dscnn_blob(nullptr, "kws_host_dscnn_image", n_floats, num_classes, input_channels);
+    if (rc) return rc;
+    const DscnnLayout L(num_classes, input_channels);
+    rc = export_room(L.total, out_words, cap_words, need_words);
+    if (rc || !out_words) return rc;
+    std::vector<float> h;
+    DscnnWeights mw;
+    build_dscnn_image(blob, L, num_classes, input_channels, h, mw);
+    memcpy(out_words, h.data(), L.total * sizeof(float));
+    if (scalars) {
+        *scalars++ = (float)mw.k_c1;
+        for (int b = 0; b < 4; ++b) *scalars++ = (float)mw.k_pw[b];
+        *scalars++ = mw.c1_abs;
+        *scalars++ = mw.c1_bmax;
+        const float* const bounds[4] = {mw.dw_abs, mw.dw_bmax, mw.pw_abs, mw.pw_bmax};
+        for (const float* p : bounds)
+            for (int b = 0; b < 4; ++b) *scalars++ = p[b];
+    }
+    return KWS_OK;
+    KWS_GUARD_END(nullptr, "kws_host_dscnn_image")
+}
+
+int kws_host_cnn_trad_image(const float* blob, size_t n_floats, int num_classes, uint32_t* out_words, size_t cap_words,
+                            size_t* need_words, float* scalars) {
+    KWS_GUARD_BEGIN
+    if (!blob) return fail(nullptr, KWS_EINVAL, "kws_host_cnn_trad_image: blob is NULL");
+    int rc = check_cnntrad_blob(nullptr, "kws_host_cnn_trad_image", n_floats, num_classes);
+    if (rc) return rc;
+    const CtLayout L(num_classes);
+    rc = export_room(L.total, out_words, cap_words, need_words);
+    if (rc || !out_words) return rc;
+    std::vector<uint32_t> h;
+    CnnTradWeights w;
+    build_cnntrad_image(blob, L, num_classes, h, w);
+    memcpy(out_words, h.data(), L.total * sizeof(uint32_t));
+    if (scalars) {
+        const float s[7] = {w.inv_sw1, w.inv_sw2, w.inv_swl, w.w1_abs, w.b1_max, w.w2_abs, w.b2_max};
+        memcpy(scalars, s, sizeof s);
+    }
+    return KWS_OK;
+    KWS_GUARD_END(nullptr, "kws_host_cnn_trad_image")
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

@@ -103,6 +103,10 @@ SIGNATURES = {
     "kws_host_mel_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                       C.POINTER(C.c_int)]),
     "kws_host_dct_lifter": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "kws_host_dscnn_image": (C.c_int, [C.POINTER(C.c_float), C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_size_t,
+                                       C.POINTER(C.c_size_t), C.POINTER(C.c_float)]),
+    "kws_host_cnn_trad_image": (C.c_int, [C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_uint32), C.c_size_t,
+                                          C.POINTER(C.c_size_t), C.POINTER(C.c_float)]),
 }
 
 _lib = None
@@ -530,6 +534,32 @@ def host_dct_lifter(nfilt=26, numcep=10, ceplifter=22) -> np.ndarray:
     if rc != KWS_OK:
         raise KWSError(f"kws_host_dct_lifter failed ({rc})")
     return out
+
+
+def _host_image(fn, n_scalars, blob, *dims):
+    blob = np.ascontiguousarray(blob, dtype=np.float32)
+    bp, need = blob.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(0)
+    rc = fn(bp, blob.size, *dims, None, 0, C.byref(need), None)
+    if rc != KWS_OK:
+        raise ModelError(f"{lib().kws_last_error(None).decode()} (code {rc})")
+    words, scalars = np.empty(need.value, np.uint32), np.empty(n_scalars, np.float32)
+    rc = fn(bp, blob.size, *dims, words.ctypes.data_as(C.POINTER(C.c_uint32)), words.size, None,
+            scalars.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != KWS_OK:
+        raise ModelError(f"{lib().kws_last_error(None).decode()} (code {rc})")
+    return words, scalars
+
+
+def host_dscnn_image(blob: np.ndarray, num_classes: int, input_channels: int = 1):
+    """(words uint32, scalars float32[23]): the device image ``Context.load_dscnn`` uploads for this blob and the values the context
+    keeps by value -- k_c1, k_pw[4], c1_abs, c1_bmax, dw_abs[4], dw_bmax[4], pw_abs[4], pw_bmax[4] (``kws_host_dscnn_image``)."""
+    return _host_image(lib().kws_host_dscnn_image, 23, blob, int(num_classes), int(input_channels))
+
+
+def host_cnn_trad_image(blob: np.ndarray, num_classes: int):
+    """(words uint32, scalars float32[7]): the device image ``Context.load_cnn_trad`` uploads for this blob and 1/sw of conv1,
+    conv2, lin, w1_abs, b1_max, w2_abs, b2_max (``kws_host_cnn_trad_image``)."""
+    return _host_image(lib().kws_host_cnn_trad_image, 7, blob, int(num_classes))
 
 
 _contexts: dict = {}

@@ -47,12 +47,12 @@ def state_shapes(num_classes: int = 12, input_channels: int = 1) -> "OrderedDict
     return shapes
 
 
-def random_state(seed: int, std: float = 0.1, num_classes: int = 12) -> "OrderedDict[str, torch.Tensor]":
+def random_state(seed: int, std: float = 0.1, num_classes: int = 12, input_channels: int = 1) -> "OrderedDict[str, torch.Tensor]":
     """Every parameter (biases too) ~ N(0, std): non-zero biases expose the
     relu(bias) ring, which the reference's default init (zero biases) hides."""
     rs = np.random.RandomState(seed)
     out = OrderedDict()
-    for k, shp in state_shapes(num_classes).items():
+    for k, shp in state_shapes(num_classes, input_channels).items():
         out[k] = torch.from_numpy((rs.standard_normal(shp) * std).astype(np.float32))
     return out
 
