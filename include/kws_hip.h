@@ -141,6 +141,20 @@ int kws_load_dscnn(kws_ctx* ctx, const float* blob, size_t n_floats, int num_cla
  * kws_forward_f32 takes d_feat float32 [B, input_channels, 99, 10]: conv1 runs in a general kernel and the fused kernel
  * starts at block 1.  The wav -> label entry points need input_channels == 1 (an MFCC map has one channel). */
 int kws_load_dscnn_ex(kws_ctx* ctx, const float* blob, size_t n_floats, int num_classes, int input_channels);
+/* kws_load_dscnn_ex from a DEVICE-resident blob (d_blob: float32 [n_floats] on the context's device, same layout, same argument
+ * checks and codes) -- the weight refresh of a training step (the reference re-reads its parameters after every optimizer.step(),
+ * train.py:49) without a device-to-host copy: the image is built by kernels on the context stream (the fragment gather is the host
+ * loader's source, kws_pack.h), the weight statistics are computed on the device in the host's arithmetic and order, and the 128
+ * bytes of them are read back for the scalars the forward kernels take as launch arguments (the call waits for the context
+ * stream).  For a finite blob every word of the image and all 23 scalars equal kws_host_dscnn_image of the same values, so every
+ * forward is bit-identical to one after kws_load_dscnn_ex.  An image of the same size (same num_classes and input_channels) is
+ * rewritten in place, without allocation; a captured streaming push is retired as by the host load.  If a launch fails after the
+ * context's own image has been touched, the context has no model until the next successful load (KWS_ESTATE). */
+int kws_load_dscnn_device(kws_ctx* ctx, const float* d_blob, size_t n_floats, int num_classes, int input_channels);
+/* The context's current DS-CNN image and the 23 scalars, copied to the host, with the size protocol and the scalar order of
+ * kws_host_dscnn_image: *need_words (may be NULL) is always set (0 when there is no model), out_words == NULL only asks for the
+ * size, a cap_words below it is KWS_EINVAL.  No model loaded: KWS_ESTATE.  Waits for the context stream. */
+int kws_dscnn_image_read(kws_ctx* ctx, uint32_t* out_words, size_t cap_words, size_t* need_words, float* scalars);
 
 /* Forward on precomputed features.  d_feat: float32 [B,1,99,10]; d_logits: float32
  * [B,num_classes]; d_label: int32 [B] = argmax (first maximum wins, torch.max semantics,
@@ -461,7 +475,9 @@ int kws_spec_f32(kws_ctx* ctx, const float* d_frames, int num_frames, int frame_
  * kws_prof_reset.  The kernels of an eager kws_stream_push_i16 are timed
  * too (KWS_K_DSCNN for the one-launch push; KWS_K_STREAM_FRAME + KWS_K_DSCNN for the two-launch routes); a push replayed
  * as a hipGraph is not (events cannot bracket a node). */
-enum { KWS_K_MFCC = 0, KWS_K_DSCNN = 1, KWS_K_CNNTRAD_CONV = 2, KWS_K_CNNTRAD_DENSE = 3, KWS_K_STREAM_FRAME = 4, KWS_K_MFCC_F64 = 5, KWS_K_MFCC_REFINE = 6, KWS_K_COUNT = 7 };
+enum { KWS_K_MFCC = 0, KWS_K_DSCNN = 1, KWS_K_CNNTRAD_CONV = 2, KWS_K_CNNTRAD_DENSE = 3, KWS_K_STREAM_FRAME = 4, KWS_K_MFCC_F64 = 5, KWS_K_MFCC_REFINE = 6,
+       KWS_K_DSCNN_LOAD_STATS = 7, KWS_K_DSCNN_LOAD_PACK = 8, KWS_K_DSCNN_LOAD_FILL = 9, /* the launches of kws_load_dscnn_device */
+       KWS_K_COUNT = 10 };
 int kws_prof_enable(kws_ctx* ctx, int on);
 int kws_prof_reset(kws_ctx* ctx);
 int kws_prof_read(kws_ctx* ctx, int kernel_id, double* total_ms, int* launches);

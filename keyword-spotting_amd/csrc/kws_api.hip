@@ -15,7 +15,8 @@ namespace kws {
 
 const char* const kKernelNames[KWS_K_COUNT] = {"kws_mfcc_i16_kernel", "kws_dscnn_fwd_kernel", "kws_cnntrad_conv_kernel",
                                                "kws_cnntrad_dense_kernel", "kws_stream_frame_kernel", "kws_mfcc_f64_kernel",
-                                               "kws_mfcc_refine_kernel"};
+                                               "kws_mfcc_refine_kernel", "kws_ds_load_stats_kernel", "kws_ds_load_pack_kernel",
+                                               "kws_ds_load_fill_kernel"};
 
 }  // namespace kws
 
@@ -25,28 +26,6 @@ static int frames_for(int n_samples, int frame_len, int frame_step) {
     if (n_samples <= frame_len) return 1;
     return 1 + (n_samples - frame_len + frame_step - 1) / frame_step;  // 1 + ceil((n - L)/step)
 }
-
-// Bracket a kernel launch with events when profiling is on.
-struct ProfScope {
-    kws_ctx* c;
-    int id;
-    hipEvent_t stop = nullptr;
-    ProfScope(kws_ctx* c_, int id_) : c(c_), id(id_) {
-        if (!c->prof) return;
-        if (c->prof_seen[id]++ % (unsigned)c->prof_every != 0) return;  // sampling: events around every launch cost ~7 us of stream time each
-        if (c->ev_used[id] == c->ev[id].size()) {
-            kws_ctx::EvPair p{};
-            if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) return;
-            c->ev[id].push_back(p);
-        }
-        kws_ctx::EvPair& p = c->ev[id][c->ev_used[id]++];
-        (void)hipEventRecord(p.a, c->stream);
-        stop = p.b;
-    }
-    ~ProfScope() {
-        if (stop) (void)hipEventRecord(stop, c->stream);
-    }
-};
 
 static void stream_free_fwd(kws_ctx* c);
 
@@ -113,6 +92,7 @@ void kws_destroy(kws_ctx* c) {
     if (c->d_model) (void)hipFree(c->d_model);
     if (c->d_cnntrad) (void)hipFree(c->d_cnntrad);
     if (c->d_ct_stats) (void)hipFree(c->d_ct_stats);
+    if (c->d_ds_stats) (void)hipFree(c->d_ds_stats);
     if (c->d_conv_ws) (void)hipFree(c->d_conv_ws);
     if (c->d_train_ws) (void)hipFree(c->d_train_ws);
     if (c->d_feat_ws) (void)hipFree(c->d_feat_ws);

@@ -1,5 +1,5 @@
 // The context behind the C ABI (include/kws_hip.h), the error plumbing and the device-memory helpers shared by the translation
-// units that implement it (kws_api.hip, kws_weights.hip, kws_ingest.hip, kws_*_bwd.hip).
+// units that implement it (kws_api.hip, kws_weights.hip, kws_ingest.hip, kws_*_bwd.hip), and the event bracket of a timed launch.
 #pragma once
 #include <new>
 
@@ -40,6 +40,8 @@ struct kws_ctx {
     float* d_model = nullptr;
     DscnnWeights mw{};
     bool model_ready = false;
+    size_t ds_image_words = 0;        // size of d_model (kws_load_dscnn_device refreshes it in place when the size matches)
+    void* d_ds_stats = nullptr;       // kws_load_dscnn_device: the weight statistics read back to the host
     int pw_math = KWS_PW_PAIR_F16;    // kernel variant of the product entry points
     // cnn-trad-fpool3
     void* d_cnntrad = nullptr;
@@ -130,6 +132,28 @@ inline int fail_hip(kws_ctx* c, hipError_t e, const char* what) {
         hipError_t _e = (expr);                            \
         if (_e != hipSuccess) return fail_hip(c, _e, #expr); \
     } while (0)
+
+// Bracket a kernel launch with events when profiling is on.
+struct ProfScope {
+    kws_ctx* c;
+    int id;
+    hipEvent_t stop = nullptr;
+    ProfScope(kws_ctx* c_, int id_) : c(c_), id(id_) {
+        if (!c->prof) return;
+        if (c->prof_seen[id]++ % (unsigned)c->prof_every != 0) return;  // sampling: events around every launch cost ~7 us of stream time each
+        if (c->ev_used[id] == c->ev[id].size()) {
+            kws_ctx::EvPair p{};
+            if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) return;
+            c->ev[id].push_back(p);
+        }
+        kws_ctx::EvPair& p = c->ev[id][c->ev_used[id]++];
+        (void)hipEventRecord(p.a, c->stream);
+        stop = p.b;
+    }
+    ~ProfScope() {
+        if (stop) (void)hipEventRecord(stop, c->stream);
+    }
+};
 
 // Retire the captured streaming push (it holds table and weight pointers by value); the caller has drained the stream.
 inline void drop_stream_graph(kws_ctx* c) {

@@ -1,6 +1,7 @@
 // The arithmetic that decides, bit for bit, what the MFMA kernels read as weights -- one copy for the host loaders
-// (kws_weights.hip) and for the device loader's kernels: the two exact splits of eight weights into one lane's operand
-// fragment, the power-of-two layer scale, and cnn-trad-fpool3's blob / image layout with its fragment order.
+// (kws_weights.hip) and for the device loaders' kernels: the two exact splits of eight weights into one lane's operand
+// fragment, the power-of-two layer scale, and the blob / image layouts of the DS-CNN and of cnn-trad-fpool3 with their fragment
+// orders.
 // Compiled with -ffp-contract=off on both sides: the expressions below must stay as they are.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -52,6 +53,67 @@ __host__ __device__ inline float pow2_scale_of_max(float m) {
     int e;
     (void)std::frexp(m, &e);  // m = f * 2^e, f in [0.5, 1): m < 2^e
     return std::ldexp(1.f, std::max(-100, std::min(100, 15 - e)));
+}
+
+// DS-CNN.  The blob (b_*: floats) is the 20 state_dict tensors in order: conv1.weight [64][C_in][10][10] | conv1.bias [64] | four
+// blocks of BLK floats (depthwise.weight [64][9] | depthwise.bias [64] | pointwise.weight [64][64] | pointwise.bias [64]) | fc.weight
+// | fc.bias.  The device image (o_*, total: 32-bit words): c1_w [100][64] | c1_b [64] | dw [4][32][24] | pw_w [4][cin][cout] |
+// pw_b [4][64] | fc_w | fc_b | the bf16-triple fragments of the pointwise layers and of conv1 (16-byte aligned) | conv1 as
+// [ci][tap][cout] | the blob itself | the f16-pair fragments (16-byte aligned).
+struct DscnnLayout {
+    static constexpr size_t BLK = 576 + 64 + 4096 + 64, B_DWB = 576, B_PWW = 640, B_PWB = 640 + 4096;  // a block and its tensors
+    // 8-value fragments: pointwise [b 4][ct 2][m 4][lane], then (one input channel only) conv1 [ct 2][kb 7][lane]
+    static constexpr size_t F_PW = 4 * 2 * 4 * 64, F_C1 = 2 * 7 * 64;
+    size_t c1_floats, n_floats, b_blk, b_fcw, b_fcb, n_frag;
+    size_t o_c1w, o_c1b, o_dw, o_pww, o_pwb, o_fcw, o_fcb, o_split, o_c1s, o_c1g, o_raw, o_pwp, o_c1p, total;
+    int num_classes, in_channels;
+    __host__ __device__ DscnnLayout(int num_classes_, int input_channels) : num_classes(num_classes_), in_channels(input_channels) {
+        c1_floats = (size_t)6400 * input_channels;
+        b_blk = c1_floats + 64, b_fcw = b_blk + 4 * BLK, b_fcb = b_fcw + (size_t)num_classes * 64, n_floats = b_fcb + num_classes;
+        n_frag = F_PW + (input_channels == 1 ? F_C1 : 0);
+        o_c1w = 0, o_c1b = o_c1w + 6400, o_dw = o_c1b + 64, o_pww = o_dw + 4 * 64 * 12, o_pwb = o_pww + 4 * 4096, o_fcw = o_pwb + 4 * 64,
+        o_fcb = o_fcw + (size_t)num_classes * 64, o_split = (o_fcb + num_classes + 3) & ~(size_t)3, o_c1s = o_split + F_PW * 3 * 4,
+        o_c1g = o_c1s + F_C1 * 3 * 4, o_raw = o_c1g + c1_floats, o_pwp = (o_raw + n_floats + 3) & ~(size_t)3,
+        o_c1p = o_pwp + F_PW * 2 * 4, total = o_c1p + F_C1 * 2 * 4;
+    }
+};
+
+// The layers' power-of-two weight scales of the f16-pair images (pow2_scale_of_max of max|w|): conv1, the four pointwise layers.
+struct DscnnScales {
+    float c1, pw[4];
+};
+
+// Both images of fragment i < L.n_frag of the DS-CNN (MFMA A operands, 32x32x16), from the blob into the image.  Lane l = i & 63
+// holds cout = 32ct + (l&31).
+//   i < F_PW, block (b, ct, m): cin = 16m + 8(l>>5) + j, j = 0..7, of pointwise layer b.
+//   then conv1, block (ct, kb): half-wave l >> 5 takes kernel rows 5(l>>5) .. + 4, i.e. 50 consecutive taps w[0..49], in two K orders:
+//     bf16 image: w[8kb + j], zeros from 50 on -- both halves walk the same offsets 10*(kh%5) + kw, so their LDS addresses differ by
+//                 a constant
+//     f16 image (the pre-split windows, kws_dscnn.hip, conv1_unit_pairwin): kb < 5: row kb, taps kw = j; kb = 5: taps
+//                 kw = 8 + (j & 1) of row j >> 1; kb = 6: taps kw = 8 + j (j < 2) of row 4, then zeros
+__host__ __device__ inline void ds_pack_fragment(const DscnnLayout& L, const float* blob, size_t i, const DscnnScales& sw, uint32_t* img) {
+    const size_t l = i & 63, row = l & 31, half = l >> 5;
+    size_t f = i >> 6;  // fragment block
+    if (i < DscnnLayout::F_PW) {
+        const size_t b = f >> 3, ct = (f >> 2) & 1, m = f & 3;
+        const float* w = blob + L.b_blk + b * DscnnLayout::BLK + DscnnLayout::B_PWW + (32 * ct + row) * 64 + 16 * m + 8 * half;
+        float v[8];
+        for (int j = 0; j < 8; ++j) v[j] = w[j];
+        pack_bf16_triple(v, img + L.o_split + (f * 3 * 64 + l) * 4);
+        pack_f16_pair(v, sw.pw[b], 1.f, img + L.o_pwp + (f * 2 * 64 + l) * 4);
+        return;
+    }
+    f -= DscnnLayout::F_PW / 64;
+    const int ct = (int)(f / 7), kb = (int)(f % 7);
+    const float* w = blob + (32 * ct + row) * 100 + 50 * half;
+    float v3[8], v2[8];
+    for (int j = 0; j < 8; ++j) {
+        const int t = kb < 5 ? 10 * kb + j : kb == 5 ? 10 * (j >> 1) + 8 + (j & 1) : j < 2 ? 48 + j : -1;
+        v3[j] = 8 * kb + j < 50 ? w[8 * kb + j] : 0.f;
+        v2[j] = t >= 0 ? w[t] : 0.f;
+    }
+    pack_bf16_triple(v3, img + L.o_c1s + (f * 3 * 64 + l) * 4);
+    pack_f16_pair(v2, sw.c1, 1.f, img + L.o_c1p + (f * 2 * 64 + l) * 4);
 }
 
 // cnn-trad-fpool3.  The blob (b_*, n_*: floats) is the ten state_dict tensors in order.  The device image (o_*, total: 32-bit

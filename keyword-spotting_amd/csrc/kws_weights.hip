@@ -1,6 +1,6 @@
 // Model weights: the device images of the DS-CNN and of cnn-trad-fpool3 (layouts: kws_internal.h), built on the host by pure
-// functions of the state_dict blob, the upload / install behind the kws_load_* entries, cnn-trad-fpool3's device-side loader and
-// the host-only image exports.  Every weight bit comes from kws_pack.h.
+// functions of the state_dict blob, the upload / install behind the kws_load_* entries, the device-side loaders of both models
+// (the same image from a device-resident blob) and the image exports.  Every weight bit comes from kws_pack.h.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -27,22 +27,6 @@ static double max_row_sum(const float* w, int rows, size_t row_len) {
     return best;
 }
 static float bound_of_row_sum(double best) { return (float)(best * 1.0000002); }  // rounded up
-static float max_row_abs_sum(const float* w, int rows, size_t row_len) { return bound_of_row_sum(max_row_sum(w, rows, row_len)); }
-
-// The device image of a DS-CNN blob (units: floats): c1_w [100][64] | c1_b [64] | dw [4][32][24] | pw_w [4][cin][cout] | pw_b [4][64] |
-// fc_w | fc_b | splits | conv1 as [ci][tap][cout] | the blob itself | the f16-pair images.
-struct DscnnLayout {
-    size_t c1_floats, n_floats;
-    size_t o_c1w, o_c1b, o_dw, o_pww, o_pwb, o_fcw, o_fcb, o_split, o_c1s, o_c1g, o_raw, o_pwp, o_c1p, total;
-    DscnnLayout(int num_classes, int input_channels) {
-        c1_floats = (size_t)6400 * input_channels;
-        n_floats = c1_floats + 64 + 4 * (576 + 64 + 4096 + 64) + (size_t)num_classes * 64 + num_classes;
-        o_c1w = 0, o_c1b = o_c1w + 6400, o_dw = o_c1b + 64, o_pww = o_dw + 4 * 64 * 12, o_pwb = o_pww + 4 * 4096, o_fcw = o_pwb + 4 * 64,
-        o_fcb = o_fcw + (size_t)num_classes * 64, o_split = (o_fcb + num_classes + 3) & ~(size_t)3, o_c1s = o_split + 4 * 2 * 4 * 3 * 64 * 4,
-        o_c1g = o_c1s + 2 * 7 * 3 * 64 * 4, o_raw = o_c1g + c1_floats, o_pwp = (o_raw + n_floats + 3) & ~(size_t)3,
-        o_c1p = o_pwp + 4 * 2 * 4 * 2 * 64 * 4, total = o_c1p + 2 * 7 * 2 * 64 * 4;
-    }
-};
 
 static int check_dscnn_blob(kws_ctx* c, const char* fn, size_t n_floats, int num_classes, int input_channels) {
     if (num_classes < 1 || num_classes > MAX_CLASSES) return fail(c, KWS_EUNSUPPORTED, std::string(fn) + ": num_classes must be in [1, 64]");
@@ -57,54 +41,95 @@ static int check_dscnn_blob(kws_ctx* c, const char* fn, size_t n_floats, int num
     return KWS_OK;
 }
 
+// The statistics of a DS-CNN blob the members DscnnWeights carries by value derive from; kws_ds_load_stats_kernel writes exactly
+// this.  m: max|w| of conv1.weight, max|conv1.bias|, then per block b max|pointwise.weight| [2 + b], max|depthwise.bias| [6 + b],
+// max|pointwise.bias| [10 + b].  r: the largest row sum of |w| of conv1 [0], of depthwise b [1 + b], of pointwise b [5 + b].  The
+// conv1 entries are 0 for more than one input channel (no fused conv1, no bounds).
+struct DscnnStats {
+    float m[14];
+    double r[9];
+};
+static_assert(sizeof(DscnnStats) == 14 * sizeof(float) + 9 * sizeof(double), "DscnnStats: the read-back is exactly the statistics");
+
+static DscnnStats dscnn_host_stats(const float* blob, const DscnnLayout& L) {
+    DscnnStats st{};
+    if (L.in_channels == 1) {
+        st.m[0] = max_abs(blob, 6400);
+        st.m[1] = max_abs(blob + 6400, 64);
+        st.r[0] = max_row_sum(blob, 64, 100);
+    }
+    for (int b = 0; b < 4; ++b) {
+        const float* blk = blob + L.b_blk + b * DscnnLayout::BLK;
+        st.m[2 + b] = max_abs(blk + DscnnLayout::B_PWW, 4096);
+        st.m[6 + b] = max_abs(blk + DscnnLayout::B_DWB, 64);
+        st.m[10 + b] = max_abs(blk + DscnnLayout::B_PWB, 64);
+        st.r[1 + b] = max_row_sum(blk, 64, 9);
+        st.r[5 + b] = max_row_sum(blk + DscnnLayout::B_PWW, 64, 64);
+    }
+    return st;
+}
+
+static int exponent_of_scale(float sw) {  // sw = 2^(ke - 1)
+    int ke;
+    (void)std::frexp(sw, &ke);
+    return ke - 1;
+}
+
+// The members DscnnWeights carries by value (its pointers stay null) and the scales of the f16-pair images, from the statistics:
+// for the host and the device loader alike.
+static DscnnWeights ds_scalars(const DscnnStats& st, const DscnnLayout& L, DscnnScales& sw) {
+    DscnnWeights mw{};
+    mw.num_classes = L.num_classes;
+    mw.in_channels = L.in_channels;
+    sw.c1 = 1.f;
+    if (L.in_channels == 1) {
+        sw.c1 = pow2_scale_of_max(st.m[0]);
+        mw.k_c1 = exponent_of_scale(sw.c1);
+        mw.c1_abs = bound_of_row_sum(st.r[0]);
+        mw.c1_bmax = st.m[1];
+    }
+    for (int b = 0; b < 4; ++b) {
+        sw.pw[b] = pow2_scale_of_max(st.m[2 + b]);
+        mw.k_pw[b] = exponent_of_scale(sw.pw[b]);
+        mw.dw_abs[b] = bound_of_row_sum(st.r[1 + b]);
+        mw.pw_abs[b] = bound_of_row_sum(st.r[5 + b]);
+        mw.dw_bmax[b] = st.m[6 + b];
+        mw.pw_bmax[b] = st.m[10 + b];
+    }
+    return mw;
+}
+
+// The 23 scalars of the image exports (kws_host_dscnn_image, kws_dscnn_image_read).
+static void dscnn_scalars_out(const DscnnWeights& mw, float* scalars) {
+    *scalars++ = (float)mw.k_c1;
+    for (int b = 0; b < 4; ++b) *scalars++ = (float)mw.k_pw[b];
+    *scalars++ = mw.c1_abs;
+    *scalars++ = mw.c1_bmax;
+    const float* const bounds[4] = {mw.dw_abs, mw.dw_bmax, mw.pw_abs, mw.pw_bmax};
+    for (const float* p : bounds)
+        for (int b = 0; b < 4; ++b) *scalars++ = p[b];
+}
+
 // The host image h of a checked blob and the members DscnnWeights carries by value (its pointers stay null).
-static void build_dscnn_image(const float* blob, const DscnnLayout& L, int num_classes, int input_channels, std::vector<float>& h,
-                              DscnnWeights& mw) {
-    mw = DscnnWeights{};
-    mw.num_classes = num_classes;
-    mw.in_channels = input_channels;
+static void build_dscnn_image(const float* blob, const DscnnLayout& L, std::vector<float>& h, DscnnWeights& mw) {
+    const int input_channels = L.in_channels;
+    DscnnScales sw;
+    mw = ds_scalars(dscnn_host_stats(blob, L), L, sw);
     h.assign(L.total, 0.f);
-    uint32_t* const img = reinterpret_cast<uint32_t*>(h.data());
     const float* src = blob;
     memcpy(&h[L.o_raw], blob, L.n_floats * sizeof(float));  // torch layouts, for the composed any-map path (kws_forward_map_f32)
     // conv1.weight [64][C][10][10] -> [ci][tap][cout] (kws_conv1_general_kernel for C > 1, kws_conv1_any_kernel for any map)
     for (int co = 0; co < 64; ++co)
         for (int ci = 0; ci < input_channels; ++ci)
             for (int k = 0; k < 100; ++k) h[L.o_c1g + ((size_t)ci * 100 + k) * 64 + co] = src[((size_t)co * input_channels + ci) * 100 + k];
-    if (input_channels == 1) {
+    if (input_channels == 1)
         for (int co = 0; co < 64; ++co)  // conv1.weight [64][1][10][10] -> [k][cout]
             for (int k = 0; k < 100; ++k) h[L.o_c1w + (size_t)k * 64 + co] = src[co * 100 + k];
-        // conv1 as MFMA A operands (32x32x16), lane l of (ct, kb): cout = 32ct + (l&31); half-wave l >> 5 takes kernel rows
-        // 5(l>>5) .. + 4, i.e. 50 consecutive taps w[0..49], in two K orders:
-        //   bf16 image: w[8kb + j], zeros from 50 on -- both halves walk the same offsets 10*(kh%5) + kw, so their LDS addresses differ
-        //               by a constant
-        //   f16 image (the pre-split windows, kws_dscnn.hip, conv1_unit_pairwin): kb < 5: row kb, taps kw = j; kb = 5: taps
-        //               kw = 8 + (j & 1) of row j >> 1; kb = 6: taps kw = 8 + j (j < 2) of row 4, then zeros
-        const float sw = pow2_scale_of_max(max_abs(src, 6400));
-        int ke;
-        (void)std::frexp(sw, &ke);
-        mw.k_c1 = ke - 1;  // sw = 2^(ke - 1)
-        for (int ct = 0; ct < 2; ++ct)
-            for (int kb = 0; kb < 7; ++kb)
-                for (int l = 0; l < 64; ++l) {
-                    const float* w = src + (32 * ct + (l & 31)) * 100 + 50 * (l >> 5);
-                    float v3[8], v2[8];
-                    for (int j = 0; j < 8; ++j) {
-                        const int t = kb < 5 ? 10 * kb + j : kb == 5 ? 10 * (j >> 1) + 8 + (j & 1) : j < 2 ? 48 + j : -1;
-                        v3[j] = 8 * kb + j < 50 ? w[8 * kb + j] : 0.f;
-                        v2[j] = t >= 0 ? w[t] : 0.f;
-                    }
-                    pack_bf16_triple(v3, img + L.o_c1s + ((size_t)(ct * 7 + kb) * 3 * 64 + l) * 4);
-                    pack_f16_pair(v2, sw, 1.f, img + L.o_c1p + ((size_t)(ct * 7 + kb) * 2 * 64 + l) * 4);
-                }
-        mw.c1_abs = max_row_abs_sum(src, 64, 100);
-        mw.c1_bmax = max_abs(src + 6400, 64);
-    }
     src += L.c1_floats;
     memcpy(&h[L.o_c1b], src, 64 * sizeof(float));
     src += 64;
     for (int b = 0; b < 4; ++b) {
-        const float *dw_w = src, *dw_b = src + 576, *pw_w = src + 640, *pw_b = src + 640 + 4096;
+        const float *dw_w = src, *dw_b = src + DscnnLayout::B_DWB, *pw_w = src + DscnnLayout::B_PWW, *pw_b = src + DscnnLayout::B_PWB;
         for (int ch = 0; ch < 64; ++ch) {  // channel PAIRS interleaved, 24 floats per pair: (tap t of ch, of ch + 1) at 2t, the biases at 18, 19
             float* q = &h[L.o_dw + ((size_t)b * 32 + ch / 2) * 24 + (ch & 1)];
             for (int t = 0; t < 9; ++t) q[2 * t] = dw_w[ch * 9 + t];
@@ -113,30 +138,131 @@ static void build_dscnn_image(const float* blob, const DscnnLayout& L, int num_c
         for (int co = 0; co < 64; ++co)  // pointwise.weight [cout][cin][1][1] -> [cin][cout]
             for (int ci = 0; ci < 64; ++ci) h[L.o_pww + (size_t)b * 4096 + (size_t)ci * 64 + co] = pw_w[co * 64 + ci];
         memcpy(&h[L.o_pwb + (size_t)b * 64], pw_b, 64 * sizeof(float));
-        // the same weights as MFMA A operands (32x32x16): lane l of (ct, m) holds cin = 16m + 8(l>>5) + j, j = 0..7, of
-        // cout = 32ct + (l&31)
-        const float sw = pow2_scale_of_max(max_abs(pw_w, 4096));
-        int ke;
-        (void)std::frexp(sw, &ke);
-        mw.k_pw[b] = ke - 1;
-        for (int ct = 0; ct < 2; ++ct)
-            for (int m = 0; m < 4; ++m)
-                for (int l = 0; l < 64; ++l) {
-                    float v[8];
-                    for (int j = 0; j < 8; ++j) v[j] = pw_w[(32 * ct + (l & 31)) * 64 + 16 * m + 8 * (l >> 5) + j];
-                    const size_t f = (size_t)(b * 2 + ct) * 4 + m;
-                    pack_bf16_triple(v, img + L.o_split + (f * 3 * 64 + l) * 4);
-                    pack_f16_pair(v, sw, 1.f, img + L.o_pwp + (f * 2 * 64 + l) * 4);
-                }
-        mw.dw_abs[b] = max_row_abs_sum(dw_w, 64, 9);
-        mw.pw_abs[b] = max_row_abs_sum(pw_w, 64, 64);
-        mw.dw_bmax[b] = max_abs(dw_b, 64);
-        mw.pw_bmax[b] = max_abs(pw_b, 64);
-        src += 576 + 64 + 4096 + 64;
+        src += DscnnLayout::BLK;
     }
-    memcpy(&h[L.o_fcw], src, (size_t)num_classes * 64 * sizeof(float));
-    src += (size_t)num_classes * 64;
-    memcpy(&h[L.o_fcb], src, (size_t)num_classes * sizeof(float));
+    memcpy(&h[L.o_fcw], src, (size_t)L.num_classes * 64 * sizeof(float));
+    src += (size_t)L.num_classes * 64;
+    memcpy(&h[L.o_fcb], src, (size_t)L.num_classes * sizeof(float));
+    // conv1 and the pointwise layers as MFMA A operands, both arithmetics (kws_pack.h)
+    uint32_t* const img = reinterpret_cast<uint32_t*>(h.data());
+    for (size_t i = 0; i < L.n_frag; ++i) ds_pack_fragment(L, blob, i, sw, img);
+}
+
+// Point the context at a complete device image d (layout L); mw holds the values DscnnWeights carries by value.
+static void install_dscnn(kws_ctx* c, float* d, const DscnnLayout& L, DscnnWeights mw) {
+    if (c->d_model && c->d_model != d) (void)hipFree(c->d_model);
+    c->d_model = d;
+    c->ds_image_words = L.total;
+    mw.c1_w = d + L.o_c1w;
+    mw.c1_b = d + L.o_c1b;
+    mw.dw_w = d + L.o_dw;
+    mw.pw_w = d + L.o_pww;
+    mw.pw_b = d + L.o_pwb;
+    mw.pw_split = reinterpret_cast<const uint32_t*>(d + L.o_split);
+    mw.c1_split = reinterpret_cast<const uint32_t*>(d + L.o_c1s);
+    mw.pw_pair = reinterpret_cast<const uint32_t*>(d + L.o_pwp);
+    mw.c1_pair = reinterpret_cast<const uint32_t*>(d + L.o_c1p);
+    mw.fc_w = d + L.o_fcw;
+    mw.fc_b = d + L.o_fcb;
+    mw.c1_general = d + L.o_c1g;
+    mw.raw = d + L.o_raw;
+    c->mw = mw;
+    c->model_ready = true;
+}
+
+// ---- kws_load_dscnn_device: the same image built on the device from a device-resident blob ---------------------------------------
+// DscnnStats in the host's arithmetic: maxima of |w| (exact in any order; fmaxf drops NaN as std::max does there), the row sums of
+// max_row_sum as ONE sequential float64 chain per row, in the host's order.  Workgroup q < 14: the maximum m[q]; workgroup 14 + g:
+// the 64 rows behind r[g], one thread each.  (extern "C": profilers show the plain names.)
+extern "C" __global__ __launch_bounds__(256) void kws_ds_load_stats_kernel(const float* __restrict__ blob, DscnnLayout L, DscnnStats* __restrict__ st) {
+    __shared__ float s_m[256];
+    __shared__ double s_r[64];
+    const int tid = threadIdx.x, q = blockIdx.x;
+    const bool one = L.in_channels == 1;
+    if (q < 14) {
+        size_t off = 0, len = one ? 6400 : 0;  // q == 0: conv1.weight
+        if (q == 1) off = 6400, len = one ? 64 : 0;
+        if (q >= 2) {
+            const int kind = (q - 2) >> 2;  // 0 pointwise.weight, 1 depthwise.bias, 2 pointwise.bias
+            off = L.b_blk + (size_t)((q - 2) & 3) * DscnnLayout::BLK + (kind == 0 ? DscnnLayout::B_PWW : kind == 1 ? DscnnLayout::B_DWB : DscnnLayout::B_PWB);
+            len = kind == 0 ? 4096 : 64;
+        }
+        float m = 0.f;
+        for (size_t i = tid; i < len; i += 256) m = fmaxf(m, fabsf(blob[off + i]));
+        s_m[tid] = m;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) {
+            if (tid < w) s_m[tid] = fmaxf(s_m[tid], s_m[tid + w]);
+            __syncthreads();
+        }
+        if (tid == 0) st->m[q] = s_m[0];
+        return;
+    }
+    const int g = q - 14;  // 0: conv1 [64][100]; 1..4: depthwise [64][9]; 5..8: pointwise [64][64]
+    if (tid < 64) {
+        const size_t len = g == 0 ? (one ? 100 : 0) : g < 5 ? 9 : 64;
+        const size_t base = g == 0 ? 0 : L.b_blk + (size_t)((g - 1) & 3) * DscnnLayout::BLK + (g < 5 ? 0 : DscnnLayout::B_PWW);
+        const float* w = blob + base + (size_t)tid * len;
+        double a = 0.0;
+        for (size_t i = 0; i < len; ++i) a += fabs((double)w[i]);
+        s_r[tid] = a;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double best = 0.0;
+        for (int r = 0; r < 64; ++r) best = fmax(best, s_r[r]);
+        st->r[g] = best;
+    }
+}
+
+// one thread per 8-value fragment of conv1 and the pointwise layers: the host loader's loop body, compiled for the device
+extern "C" __global__ __launch_bounds__(256) void kws_ds_load_pack_kernel(const float* __restrict__ blob, DscnnLayout L, DscnnScales sw,
+                                                               uint32_t* __restrict__ img) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < L.n_frag) ds_pack_fragment(L, blob, i, sw, img);
+}
+
+// One thread per image word outside the fragment blocks the pack kernel writes: the transposed, interleaved and copied float32
+// sections of build_dscnn_image, gathered from the blob, and zero wherever the host image keeps its initial zero -- the depthwise
+// pad floats, the alignment padding, and for more than one input channel c1_w and conv1's fragment blocks.
+extern "C" __global__ __launch_bounds__(256) void kws_ds_load_fill_kernel(const float* __restrict__ blob, DscnnLayout L, uint32_t* __restrict__ img) {
+    const size_t w = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (w >= L.total) return;
+    constexpr size_t ZERO = ~(size_t)0;
+    const bool one = L.in_channels == 1;
+    const size_t cin = (size_t)L.in_channels;
+    size_t src = ZERO;
+    if (w < L.o_c1b) {  // conv1.weight [64][1][10][10] -> [k][cout]
+        if (one) src = (w & 63) * 100 + (w >> 6);
+    } else if (w < L.o_dw) {
+        src = L.c1_floats + (w - L.o_c1b);
+    } else if (w < L.o_pww) {  // channel pairs interleaved: (tap t of ch, of ch + 1) at 2t, the biases at 18, 19, four pad floats
+        const size_t u = w - L.o_dw, blk = L.b_blk + u / 768 * DscnnLayout::BLK, e = u % 24, ch = 2 * (u % 768 / 24) + (e & 1);
+        if (e < 18) src = blk + ch * 9 + (e >> 1);
+        else if (e < 20) src = blk + DscnnLayout::B_DWB + ch;
+    } else if (w < L.o_pwb) {  // pointwise.weight [cout][cin] -> [cin][cout]
+        const size_t u = w - L.o_pww;
+        src = L.b_blk + (u >> 12) * DscnnLayout::BLK + DscnnLayout::B_PWW + (u & 63) * 64 + ((u >> 6) & 63);
+    } else if (w < L.o_fcw) {
+        const size_t u = w - L.o_pwb;
+        src = L.b_blk + (u >> 6) * DscnnLayout::BLK + DscnnLayout::B_PWB + (u & 63);
+    } else if (w < L.o_fcb + (size_t)L.num_classes) {  // fc_w | fc_b: contiguous in both
+        src = L.b_fcw + (w - L.o_fcw);
+    } else if (w < L.o_split) {  // alignment
+    } else if (w < L.o_c1s) {
+        return;  // pointwise fragments
+    } else if (w < L.o_c1g) {
+        if (one) return;  // conv1 fragments
+    } else if (w < L.o_raw) {  // conv1.weight [64][C][10][10] -> [ci][tap][cout]
+        const size_t u = w - L.o_c1g;
+        src = ((u & 63) * cin + u / 6400) * 100 + (u % 6400 >> 6);
+    } else if (w < L.o_raw + L.n_floats) {
+        src = w - L.o_raw;
+    } else if (w < L.o_pwp) {  // alignment
+    } else if (w < L.o_c1p || one) {
+        return;  // f16-pair fragments
+    }
+    img[w] = src == ZERO ? 0u : __builtin_bit_cast(uint32_t, blob[src]);
 }
 
 static int check_cnntrad_blob(kws_ctx* c, const char* fn, size_t n_floats, int num_classes) {
@@ -208,7 +334,7 @@ static void install_cnntrad(kws_ctx* c, uint32_t* d, const CtLayout& L, const Cn
 
 // ---- kws_load_cnn_trad_device: the same image built on the device from a device-resident blob ----------------------------------
 // Statistics in the host's arithmetic: maxima of |w| (exact in any order; fmaxf drops NaN as std::max does there), the row sums of
-// max_row_abs_sum as ONE sequential float64 chain per row, in the host's order.  st: float [5] = max|w1|, max|w2|, max|wl|, max|b1|,
+// max_row_sum as ONE sequential float64 chain per row, in the host's order.  st: float [5] = max|w1|, max|w2|, max|wl|, max|b1|,
 // max|b2|, then (8-byte aligned) double [2] = the largest row sums of w1 and w2.  (extern "C": profilers show the plain names.)
 extern "C" __global__ __launch_bounds__(1024) void kws_ct_load_stats_kernel(const float* __restrict__ blob, CtLayout L, float* __restrict__ st) {
     __shared__ float s_m[1024];
@@ -289,30 +415,80 @@ int kws_load_dscnn_ex(kws_ctx* c, const float* blob, size_t n_floats, int num_cl
     const DscnnLayout L(num_classes, input_channels);
     std::vector<float> h;
     DscnnWeights mw;  // (a local: the context keeps its old model if the upload below fails)
-    build_dscnn_image(blob, L, num_classes, input_channels, h, mw);
+    build_dscnn_image(blob, L, h, mw);
 
     HIP_TRY(c, hipSetDevice(c->device));
     rc = replace_device_image(c, c->d_model, h.data(), L.total * sizeof(float), "kws_load_dscnn");
     if (rc) return rc;
     drop_stream_graph(c);  // a captured push holds the old weight pointers by value
-    const float* d = c->d_model;
-    mw.c1_w = d + L.o_c1w;
-    mw.c1_b = d + L.o_c1b;
-    mw.dw_w = d + L.o_dw;
-    mw.pw_w = d + L.o_pww;
-    mw.pw_b = d + L.o_pwb;
-    mw.pw_split = reinterpret_cast<const uint32_t*>(d + L.o_split);
-    mw.c1_split = reinterpret_cast<const uint32_t*>(d + L.o_c1s);
-    mw.pw_pair = reinterpret_cast<const uint32_t*>(d + L.o_pwp);
-    mw.c1_pair = reinterpret_cast<const uint32_t*>(d + L.o_c1p);
-    mw.fc_w = d + L.o_fcw;
-    mw.fc_b = d + L.o_fcb;
-    mw.c1_general = d + L.o_c1g;
-    mw.raw = d + L.o_raw;
-    c->mw = mw;
-    c->model_ready = true;
+    install_dscnn(c, c->d_model, L, mw);
     return KWS_OK;
     KWS_GUARD_END(c, "kws_load_dscnn")
+}
+
+int kws_load_dscnn_device(kws_ctx* c, const float* d_blob, size_t n_floats, int num_classes, int input_channels) {
+    static const char* fn = "kws_load_dscnn_device";
+    KWS_GUARD_BEGIN
+    if (!c) return KWS_EINVAL;
+    if (!d_blob) return fail(c, KWS_EINVAL, std::string(fn) + ": blob is NULL");
+    int rc = check_dscnn_blob(c, fn, n_floats, num_classes, input_channels);
+    if (rc) return rc;
+    const DscnnLayout L(num_classes, input_channels);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->d_ds_stats) HIP_TRY(c, hipMalloc(&c->d_ds_stats, sizeof(DscnnStats)));
+    hipStream_t s = c->stream;
+    {
+        ProfScope ps(c, KWS_K_DSCNN_LOAD_STATS);
+        hipLaunchKernelGGL(kws_ds_load_stats_kernel, dim3(14 + 9), dim3(256), 0, s, d_blob, L, static_cast<DscnnStats*>(c->d_ds_stats));
+    }
+    HIP_TRY(c, hipGetLastError());
+    DscnnStats st;
+    HIP_TRY(c, hipMemcpyAsync(&st, c->d_ds_stats, sizeof st, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    DscnnScales sw;
+    const DscnnWeights mw = ds_scalars(st, L, sw);
+    // the stream has drained: rewrite an image of this size where it lies, else allocate (install_dscnn frees the old one)
+    float* d = c->d_model;
+    const bool in_place = d && c->ds_image_words == L.total;
+    if (!in_place && hipMalloc(reinterpret_cast<void**>(&d), L.total * sizeof(float)) != hipSuccess)
+        return fail(c, KWS_ENOMEM, std::string(fn) + ": device allocation failed");
+    drop_stream_graph(c);  // a captured push holds the old weight pointers and scalars by value
+    uint32_t* img = reinterpret_cast<uint32_t*>(d);
+    hipError_t e;
+    {
+        ProfScope ps(c, KWS_K_DSCNN_LOAD_PACK);
+        hipLaunchKernelGGL(kws_ds_load_pack_kernel, dim3((unsigned)((L.n_frag + 255) / 256)), dim3(256), 0, s, d_blob, L, sw, img);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        ProfScope ps(c, KWS_K_DSCNN_LOAD_FILL);
+        hipLaunchKernelGGL(kws_ds_load_fill_kernel, dim3((unsigned)((L.total + 255) / 256)), dim3(256), 0, s, d_blob, L, img);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {  // no mixed image is served: the context's own image may be half rewritten, a fresh one is dropped
+        if (in_place)
+            c->model_ready = false;
+        else
+            (void)hipFree(d);
+        return fail_hip(c, e, fn);
+    }
+    install_dscnn(c, d, L, mw);
+    return KWS_OK;
+    KWS_GUARD_END(c, "kws_load_dscnn_device")
+}
+
+int kws_dscnn_image_read(kws_ctx* c, uint32_t* out_words, size_t cap_words, size_t* need_words, float* scalars) {
+    if (need_words) *need_words = 0;
+    if (!c) return KWS_EINVAL;
+    if (!c->model_ready) return fail(c, KWS_ESTATE, "kws_dscnn_image_read: no model loaded (kws_load_dscnn)");
+    int rc = export_room(c->ds_image_words, out_words, cap_words, need_words);
+    if (rc) return fail(c, rc, "kws_dscnn_image_read: cap_words is below the image's size");
+    if (!out_words) return KWS_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(out_words, c->d_model, c->ds_image_words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (scalars) dscnn_scalars_out(c->mw, scalars);
+    return KWS_OK;
 }
 
 int kws_load_cnn_trad(kws_ctx* c, const float* blob, size_t n_floats, int num_classes) {
@@ -381,17 +557,9 @@ int kws_host_dscnn_image(const float* blob, size_t n_floats, int num_classes, in
     if (rc || !out_words) return rc;
     std::vector<float> h;
     DscnnWeights mw;
-    build_dscnn_image(blob, L, num_classes, input_channels, h, mw);
+    build_dscnn_image(blob, L, h, mw);
     memcpy(out_words, h.data(), L.total * sizeof(float));
-    if (scalars) {
-        *scalars++ = (float)mw.k_c1;
-        for (int b = 0; b < 4; ++b) *scalars++ = (float)mw.k_pw[b];
-        *scalars++ = mw.c1_abs;
-        *scalars++ = mw.c1_bmax;
-        const float* const bounds[4] = {mw.dw_abs, mw.dw_bmax, mw.pw_abs, mw.pw_bmax};
-        for (const float* p : bounds)
-            for (int b = 0; b < 4; ++b) *scalars++ = p[b];
-    }
+    if (scalars) dscnn_scalars_out(mw, scalars);
     return KWS_OK;
     KWS_GUARD_END(nullptr, "kws_host_dscnn_image")
 }

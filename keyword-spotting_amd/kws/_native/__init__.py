@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("KWS_HIP_LIB") or os.path.join(os.path.dirname(os.path
 KWS_OK, KWS_EINVAL, KWS_ENOMEM, KWS_EHIP, KWS_ESTATE, KWS_EUNSUPPORTED = 0, -1, -2, -3, -4, -5
 KWS_CT_F16_PAIR, KWS_CT_BF16_TRIPLE = 0, 1  # kws_set_cnn_trad_math
 KWS_K_MFCC, KWS_K_DSCNN, KWS_K_CNNTRAD_CONV, KWS_K_CNNTRAD_DENSE, KWS_K_STREAM_FRAME, KWS_K_MFCC_F64, KWS_K_MFCC_REFINE = 0, 1, 2, 3, 4, 5, 6
+KWS_K_DSCNN_LOAD_STATS, KWS_K_DSCNN_LOAD_PACK, KWS_K_DSCNN_LOAD_FILL = 7, 8, 9  # the launches of kws_load_dscnn_device
 FE_REFINE_SPAN_DEFAULT = 10.2  # KWS_FE_REFINE_SPAN_DEFAULT: log(largest bin power / weakest mel band) beyond which a frame is redone in float64
 FE_F32, FE_F64 = 0, 1  # KWS_FE_F32 (default: the fast float32 front end) / KWS_FE_F64 (float64 after framing, as psf)
 ACT_FLOATS_PER_CLIP = 64 * (141 + 141 + 245 + 357) + 64 + 64 * 477  # KWS_ACT_FLOATS_PER_CLIP
@@ -51,6 +52,8 @@ SIGNATURES = {
     "kws_mfcc_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, _f32p]),
     "kws_load_dscnn": (C.c_int, [_c_ctx, C.POINTER(C.c_float), C.c_size_t, C.c_int]),
     "kws_load_dscnn_ex": (C.c_int, [_c_ctx, C.POINTER(C.c_float), C.c_size_t, C.c_int, C.c_int]),
+    "kws_load_dscnn_device": (C.c_int, [_c_ctx, _f32p, C.c_size_t, C.c_int, C.c_int]),
+    "kws_dscnn_image_read": (C.c_int, [_c_ctx, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_float)]),
     "kws_forward_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, _f32p, _i32p]),
     "kws_forward_map_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _i32p]),
     "kws_forward_map_debug_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, _f32p]),
@@ -229,6 +232,23 @@ class Context:
             ModelError,
         )
         self.num_classes = int(num_classes)
+
+    def load_dscnn_device(self, blob, num_classes: int, input_channels: int = 1):
+        """``kws_load_dscnn_device``: ``blob`` float32 [n_floats] on this context's device (the 20 state_dict tensors in order);
+        same image, scalars and forward as ``load_dscnn`` of the same values, built on the device."""
+        self._check(self._lib.kws_load_dscnn_device(self._h, _ptr(blob), int(blob.numel()), int(num_classes), int(input_channels)),
+                    ModelError)
+        self.num_classes = int(num_classes)
+
+    def dscnn_image(self):
+        """(words uint32, scalars float32[23]) of the DS-CNN image this context holds now, in ``host_dscnn_image``'s format
+        (``kws_dscnn_image_read``; waits for the context's stream)."""
+        need = C.c_size_t(0)
+        self._check(self._lib.kws_dscnn_image_read(self._h, None, 0, C.byref(need), None), ModelError)
+        words, scalars = np.empty(need.value, np.uint32), np.empty(23, np.float32)
+        self._check(self._lib.kws_dscnn_image_read(self._h, words.ctypes.data_as(C.POINTER(C.c_uint32)), words.size, None,
+                                                   scalars.ctypes.data_as(C.POINTER(C.c_float))), ModelError)
+        return words, scalars
 
     def forward_f32(self, feat, logits, label=None):
         self._check(

@@ -120,6 +120,10 @@ class DepthwiseSeparableConv(KeywordSpottingModel):
     ``train()``, or switched back with ``eval()``, ``torch.no_grad()``, frozen parameters -- no autograd graph is built and
     the logits are plain tensors, as for inference."""
 
+    # the parameter refresh of ``_context`` for parameters on the GPU: True = on the device (``kws_load_dscnn_device``), False =
+    # through the host as for CPU-resident parameters (an instance sets it to compare the two routes)
+    _device_refresh = True
+
     def __init__(self, num_classes: int = 12, input_channels: int = 1):
         super().__init__(num_classes)
         if not 1 <= input_channels <= 64:
@@ -157,7 +161,8 @@ class DepthwiseSeparableConv(KeywordSpottingModel):
     # ------------------------------------------------------------------ device plumbing
     def packed_weights(self) -> np.ndarray:
         """The 20 ``state_dict`` tensors, in order, as one float32 vector (``kws_load_dscnn`` layout): concatenated on the
-        parameters' device and copied to the host once (it runs again after every optimizer step)."""
+        parameters' device and copied to the host once.  (The refresh after an optimizer step uses it only on the host route:
+        parameters on the GPU are re-loaded there, see ``_context``.)"""
         return self._pack(self.state_dict().values())
 
     @staticmethod
@@ -176,7 +181,9 @@ class DepthwiseSeparableConv(KeywordSpottingModel):
 
     def _context(self, device_index: int, params=None):
         """The model's context on ``device_index`` holding ``params`` (default: the current parameters, in ``parameters()``
-        order); uploaded only when they differ from the tensors (and versions) uploaded last."""
+        order); uploaded only when they differ from the tensors (and versions) uploaded last.  Parameters that all live on
+        that GPU are concatenated there and loaded with ``kws_load_dscnn_device`` (``_device_refresh``); otherwise through
+        the host."""
         from kws import _native
 
         if self._ctx is None or self._ctx.device != device_index:
@@ -185,7 +192,13 @@ class DepthwiseSeparableConv(KeywordSpottingModel):
         params = tuple(self.parameters()) if params is None else tuple(params)
         fp = tuple((p.data_ptr(), p._version) for p in params)
         if fp != self._uploaded:
-            self._ctx.load_dscnn(self._pack(params), self.num_classes, self.input_channels)
+            dev = torch.device("cuda", device_index)
+            if self._device_refresh and all(p.device == dev for p in params):
+                self._ctx.use_torch_stream()
+                blob = torch.cat([p.detach().to(torch.float32).reshape(-1) for p in params])
+                self._ctx.load_dscnn_device(blob, self.num_classes, self.input_channels)
+            else:
+                self._ctx.load_dscnn(self._pack(params), self.num_classes, self.input_channels)
             self._uploaded = fp
         self._ctx.use_torch_stream()
         return self._ctx

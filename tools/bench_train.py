@@ -21,8 +21,11 @@ Prints one JSON line.  Per batch size B:
   backward_tflops, backward_peak_frac   backward_gflop over backward_call_ms, and that over the 157.3 TF f32 matrix peak
   torch_eager.step_ms    the eager step (median, p10, p90), clips/s
   speedup                torch eager median / HIP median
-With --model cnn-trad-fpool3 the result also carries the model name, hip.refresh_host_ms (the same refresh through the host
-load kws_load_cnn_trad, device events around the call, median: what the refresh cost before kws_load_cnn_trad_device) and
+  hip.refresh_host_ms    the same refresh through the host (packed_weights() + the host load, device events around the call,
+                         median), measured in the same run: what the refresh costs without the device-side load
+  hip.host_route         (ds-cnn) step_ms and split_ms of the same steps with the model's refresh switched to the host route
+                         (DepthwiseSeparableConv._device_refresh = False), run after the device-route steps in the same process
+With --model cnn-trad-fpool3 the result also carries the model name and
 backward_bf16_split_floor_ms (backward_gflop at the 2.5 PF dense bf16 rate over the six products of the exact split).
 """
 import argparse
@@ -137,19 +140,37 @@ def run(B, steps, warmup, dev, backward_only=False):
         e[1].record()
         return e
 
-    for _ in range(warmup):
-        hip_step()
-        torch_step()
-    torch.cuda.synchronize()
-    hip_ev, t_ev = [], []
-    for _ in range(steps):  # alternated: both see the same clocks and neighbours
-        hip_ev.append(hip_step())
-        t_ev.append(torch_step())
-    torch.cuda.synchronize()
-    step = [e[0].elapsed_time(e[4]) for e in hip_ev]
-    split = {name: stats([e[i].elapsed_time(e[i + 1]) for e in hip_ev])["median"]
-             for i, name in enumerate(["refresh", "forward", "backward", "optimizer"])}
-    t_step = [e[0].elapsed_time(e[1]) for e in t_ev]
+    names = ["refresh", "forward", "backward", "optimizer"]
+
+    def timed_steps():
+        for _ in range(warmup):
+            hip_step()
+            torch_step()
+        torch.cuda.synchronize()
+        hip_ev, t_ev = [], []
+        for _ in range(steps):  # alternated: both see the same clocks and neighbours
+            hip_ev.append(hip_step())
+            t_ev.append(torch_step())
+        torch.cuda.synchronize()
+        return ([e[0].elapsed_time(e[4]) for e in hip_ev],
+                {name: stats([e[i].elapsed_time(e[i + 1]) for e in hip_ev])["median"] for i, name in enumerate(names)},
+                [e[0].elapsed_time(e[1]) for e in t_ev])
+
+    step, split, t_step = timed_steps()
+    # the same steps with the refresh through the host (packed_weights() + kws_load_dscnn), as before kws_load_dscnn_device
+    model._device_refresh = False
+    host_step, host_split, _ = timed_steps()
+    del model._device_refresh
+    ctx = model._context(dev.index or 0)
+    host = []
+    for _ in range(max(10, steps // 5)):  # and that refresh alone
+        a, b = ev(), ev()
+        a.record()
+        ctx.load_dscnn(model.packed_weights(), C)
+        b.record()
+        torch.cuda.synchronize()
+        host.append(a.elapsed_time(b))
+    model.sync_weights()
 
     # the C call alone, on the same inputs
     ctx = model._context(dev.index or 0)
@@ -162,7 +183,8 @@ def run(B, steps, warmup, dev, backward_only=False):
     hs, ts = stats(step), stats(t_step)
     return {
         "B": B,
-        "hip": {"step_ms": hs, "clips_per_s": round(B / hs["median"] * 1e3), "split_ms": split},
+        "hip": {"step_ms": hs, "clips_per_s": round(B / hs["median"] * 1e3), "split_ms": split,
+                "refresh_host_ms": stats(host)["median"], "host_route": {"step_ms": stats(host_step), "split_ms": host_split}},
         "backward_call_ms": call_ms,
         "backward_gflop": round(gflop, 3),
         "backward_tflops": round(tflops, 3),
