@@ -366,6 +366,14 @@ int kws_forward_cnn_trad_f32(kws_ctx* ctx, const float* d_feat, int B, float* d_
 #define KWS_CT_F16_PAIR 0
 #define KWS_CT_BF16_TRIPLE 1
 int kws_set_cnn_trad_math(kws_ctx* ctx, int math);
+/* Parity aid of kws_forward_cnn_trad_f32: runs exactly its two launches (same code path, under the context's current
+ * kws_set_cnn_trad_math) and then copies what sits in the context workspace between them, device to device on the context's
+ * stream: d_conv2 float32 [B,64,99,3] = conv2 after ReLU, channel-major as the convolution kernel writes it (the dense kernel's
+ * input), and d_clip_scale float32 [B] = the clip's power-of-two scale into f16's range.  d_clip_scale may be NULL; it is
+ * written only under KWS_CT_F16_PAIR and left untouched under KWS_CT_BF16_TRIPLE (that arithmetic has no such scale).  Errors as
+ * kws_forward_cnn_trad_f32, plus KWS_EINVAL for a NULL d_conv2.  (The role kws_forward_debug_f32 plays for the DS-CNN.) */
+int kws_forward_cnn_trad_debug_f32(kws_ctx* ctx, const float* d_feat, int B, float* d_logits, int32_t* d_label, float* d_conv2,
+                                   float* d_clip_scale);
 
 /* Fused wav -> label for this model (BASELINE.json configs[2]): kws_mfcc_i16 into the context workspace, then
  * kws_forward_cnn_trad_f32, on the context's stream.  Same arguments and errors as kws_infer_i16. */

@@ -669,13 +669,15 @@ int kws_dsblock_forward_f32(kws_ctx* c, const float* d_x, int B, int C_in, int H
     return KWS_OK;
 }
 
-int kws_forward_cnn_trad_f32(kws_ctx* c, const float* d_feat, int B, float* d_logits, int32_t* d_label) {
-    int rc = check_batch(c, d_feat, B, "kws_forward_cnn_trad_f32");
+// The two launches of the cnn-trad-fpool3 forward, shared by the product entry and its parity aid (`fn` names the caller in
+// error messages).  Workspace: B * 19008 floats of conv2 output, then one scale per clip (f16-pair arithmetic).
+static int forward_cnn_trad(kws_ctx* c, const float* d_feat, int B, float* d_logits, int32_t* d_label, const std::string& fn) {
+    int rc = check_batch(c, d_feat, B, fn.c_str());
     if (rc) return rc;
-    if (!d_logits) return fail(c, KWS_EINVAL, "kws_forward_cnn_trad_f32: d_logits is NULL");
-    if (!c->cnntrad_ready) return fail(c, KWS_ESTATE, "kws_forward_cnn_trad_f32: no model loaded (kws_load_cnn_trad)");
+    if (!d_logits) return fail(c, KWS_EINVAL, fn + ": d_logits is NULL");
+    if (!c->cnntrad_ready) return fail(c, KWS_ESTATE, fn + ": no model loaded (kws_load_cnn_trad)");
     HIP_TRY(c, hipSetDevice(c->device));
-    rc = grow_conv_ws(c, (size_t)B * 64 * 297 + (size_t)B, "kws_forward_cnn_trad_f32");  // + one scale per clip (f16-pair arithmetic)
+    rc = grow_conv_ws(c, (size_t)B * 64 * 297 + (size_t)B, fn);
     if (rc) return rc;
     const bool pair = c->cnntrad_math == KWS_CT_F16_PAIR;
     {
@@ -686,6 +688,23 @@ int kws_forward_cnn_trad_f32(kws_ctx* c, const float* d_feat, int B, float* d_lo
         ProfScope ps(c, KWS_K_CNNTRAD_DENSE);
         HIP_TRY(c, launch_cnntrad_dense(c->stream, c->tw, c->d_conv_ws, B, d_logits, d_label, pair));
     }
+    return KWS_OK;
+}
+
+int kws_forward_cnn_trad_f32(kws_ctx* c, const float* d_feat, int B, float* d_logits, int32_t* d_label) {
+    return forward_cnn_trad(c, d_feat, B, d_logits, d_label, "kws_forward_cnn_trad_f32");
+}
+
+int kws_forward_cnn_trad_debug_f32(kws_ctx* c, const float* d_feat, int B, float* d_logits, int32_t* d_label, float* d_conv2,
+                                   float* d_clip_scale) {
+    const char* fn = "kws_forward_cnn_trad_debug_f32";
+    if (c && !d_conv2) return fail(c, KWS_EINVAL, std::string(fn) + ": d_conv2 is NULL");
+    int rc = forward_cnn_trad(c, d_feat, B, d_logits, d_label, fn);
+    if (rc) return rc;
+    const size_t n = (size_t)B * 64 * 297;
+    HIP_TRY(c, hipMemcpyAsync(d_conv2, c->d_conv_ws, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
+    if (d_clip_scale && c->cnntrad_math == KWS_CT_F16_PAIR)
+        HIP_TRY(c, hipMemcpyAsync(d_clip_scale, c->d_conv_ws + n, sizeof(float) * (size_t)B, hipMemcpyDeviceToDevice, c->stream));
     return KWS_OK;
 }
 

@@ -84,6 +84,7 @@ SIGNATURES = {
     "kws_cnn_trad_train_debug_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, _f32p, _i32p, _f32p, _f32p]),
     "kws_stream_vad_f32": (C.c_int, [_c_ctx, C.c_float, C.c_int, C.c_int, _i32p]),
     "kws_forward_cnn_trad_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, _f32p, _i32p]),
+    "kws_forward_cnn_trad_debug_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, _f32p, _i32p, _f32p, _f32p]),
     "kws_set_cnn_trad_math": (C.c_int, [_c_ctx, C.c_int]),
     "kws_infer_cnn_trad_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, _f32p, _i32p]),
     "kws_softmax_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, _f32p]),
@@ -302,6 +303,13 @@ class Context:
     def forward_cnn_trad_f32(self, feat, logits, label=None):
         self._check(self._lib.kws_forward_cnn_trad_f32(self._h, _ptr(feat), int(feat.shape[0]), _ptr(logits),
                                                        _ptr(label) if label is not None else None), ModelError)
+
+    def forward_cnn_trad_debug_f32(self, feat, logits, label, conv2, clip_scale=None):
+        """``forward_cnn_trad_f32`` plus what sits between its two kernels (``kws_forward_cnn_trad_debug_f32``): ``conv2`` float32
+        [B, 64, 99, 3] after ReLU and, under KWS_CT_F16_PAIR only, ``clip_scale`` float32 [B] (left untouched otherwise)."""
+        self._check(self._lib.kws_forward_cnn_trad_debug_f32(self._h, _ptr(feat), int(feat.shape[0]), _ptr(logits),
+                                                             _ptr(label) if label is not None else None, _ptr(conv2),
+                                                             _ptr(clip_scale) if clip_scale is not None else None), ModelError)
 
     def infer_cnn_trad_i16(self, wav, logits, label=None):
         self._check(self._lib.kws_infer_cnn_trad_i16(self._h, _ptr(wav), int(wav.shape[0]), _ptr(logits),
