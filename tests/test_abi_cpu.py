@@ -28,6 +28,110 @@ def test_every_declared_symbol_is_exported_and_bound():
     assert native.kernel_name(native.KWS_K_DSCNN) == "kws_dscnn_fwd_kernel"
 
 
+def declared_prototypes():
+    """name -> (return kind, [parameter kinds]) of every kws_* prototype in include/kws_hip.h."""
+    text = open(os.path.join(REPO, "include", "kws_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*", " ", text, flags=re.M)
+    protos = {}
+    for ret, name, params in re.findall(r"\b((?:const\s+)?[A-Za-z_][A-Za-z0-9_]*(?:\s*\*+)?)\s*\b(kws_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        assert name not in protos, f"{name} is declared twice"
+        params = " ".join(params.split())
+        kinds = [] if params in ("", "void") else [_c_kind(p, is_param=True) for p in params.split(",")]
+        protos[name] = (_c_kind(ret, is_param=False), kinds)
+    return protos
+
+
+_C_SCALARS = {"int": "int", "int32_t": "int", "float": "float", "double": "double", "size_t": "u64", "uint64_t": "u64", "uint32_t": "u32"}
+
+
+def _c_kind(decl: str, is_param: bool) -> str:
+    """Kind of one C declarator: 'ptr', 'int', 'float', 'double', 'u64' (size_t / uint64_t), 'u32', 'void' (return only)."""
+    decl = " ".join(decl.replace("*", " * ").split())
+    if "*" in decl:
+        return "ptr"
+    words = [w for w in decl.split() if w != "const"]
+    if is_param:
+        assert len(words) == 2 and re.fullmatch(r"[A-Za-z_][A-Za-z0-9_]*", words[1]), f"cannot parse parameter {decl!r}"
+    else:
+        assert len(words) == 1, f"cannot parse return type {decl!r}"
+        if words[0] == "void":
+            return "void"
+    assert words[0] in _C_SCALARS, f"unknown C type in {decl!r}"
+    return _C_SCALARS[words[0]]
+
+
+def _ctypes_kind(t) -> str:
+    """The same kinds for a ctypes type; size_t and uint64_t are one class on this platform, so they compare by size."""
+    import ctypes as C
+
+    if t is None:
+        return "void"
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+        return "ptr"
+    if t in (C.c_int, C.c_int32):
+        return "int"
+    if t is C.c_float:
+        return "float"
+    if t is C.c_double:
+        return "double"
+    if t in (C.c_size_t, C.c_uint64, C.c_uint32):
+        return {8: "u64", 4: "u32"}[C.sizeof(t)]
+    raise AssertionError(f"ctypes type {t!r} has no C kind here")
+
+
+def _abi_mismatches(signatures, protos):
+    bad = []
+    for name, (ret, kinds) in sorted(protos.items()):
+        if name not in signatures:
+            bad.append(f"{name}: no ctypes signature")
+            continue
+        res, args = signatures[name]
+        if _ctypes_kind(res) != ret:
+            bad.append(f"{name}: returns {ret} in the header, {_ctypes_kind(res)} in ctypes")
+        got = [_ctypes_kind(a) for a in args]
+        if len(got) != len(kinds):
+            bad.append(f"{name}: {len(kinds)} parameters in the header, {len(got)} in ctypes")
+            continue
+        bad += [f"{name}: parameter {i} is {k} in the header, {g} in ctypes" for i, (k, g) in enumerate(zip(kinds, got)) if k != g]
+    return bad
+
+
+def test_ctypes_signatures_match_the_header_prototypes():
+    """Every hand-written parameter list of kws._native.SIGNATURES against the prototype in include/kws_hip.h: equal arity, equal
+    kind (pointer / int / float / double / 64-bit / 32-bit unsigned) at every position, equal return kind.  A parameter dropped
+    from, or changed in, one entry makes ctypes pass garbage or truncate a pointer without any error at the call."""
+    import ctypes as C
+
+    protos = declared_prototypes()
+    assert len(protos) >= 70
+    assert sorted(protos) == declared_symbols() == sorted(native.SIGNATURES)
+    assert all(ret in ("int", "void", "ptr") for ret, _ in protos.values())
+    assert protos["kws_abi_version"] == ("int", []) and protos["kws_destroy"] == ("void", ["ptr"])
+    assert protos["kws_last_error"] == ("ptr", ["ptr"])
+    assert protos["kws_stream_vad_f32"] == ("int", ["ptr", "float", "int", "int", "ptr"])
+    assert protos["kws_augment_draw"][1][:3] == ["ptr", "u64", "u32"] and protos["kws_prof_read"][1] == ["ptr", "int", "ptr", "ptr"]
+    assert _abi_mismatches(native.SIGNATURES, protos) == []
+
+    # the check notices one parameter of one entry dropped, changed in kind, or a changed return type
+    def mutated(name, res=..., args=None):
+        sig = dict(native.SIGNATURES)
+        sig[name] = (sig[name][0] if res is ... else res, list(sig[name][1]) if args is None else args)
+        return sig
+
+    smooth = native.SIGNATURES["kws_stream_smooth_f32"][1]
+    for sig, word in ((mutated("kws_stream_smooth_f32", args=smooth[:-1]), "6 parameters in the header, 5 in ctypes"),
+                      (mutated("kws_stream_smooth_f32", args=smooth[:2] + [C.c_float] + smooth[3:]), "parameter 2 is int in the header, float"),
+                      (mutated("kws_stream_vad_f32", args=[C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p]), "parameter 1 is float"),
+                      (mutated("kws_infer_host_wait", args=[C.c_void_p, C.c_uint32]), "parameter 1 is u64 in the header, u32"),
+                      (mutated("kws_softmax_f32", args=[C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]), "parameter 4 is ptr"),
+                      (mutated("kws_kernel_name", res=C.c_int), "returns ptr in the header, int"),
+                      (mutated("kws_destroy", res=C.c_int), "returns void in the header, int")):
+        bad = _abi_mismatches(sig, protos)
+        assert len(bad) == 1 and word in bad[0], (word, bad)
+
+
 def test_no_gpu_means_loud_failure():
     import torch
 
