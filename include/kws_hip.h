@@ -391,6 +391,59 @@ int kws_softmax_f32(kws_ctx* ctx, const float* d_logits, int B, int C, float* d_
  * wins.  The history lives in the context and is reset by kws_stream_open / a change of window or C. */
 int kws_stream_smooth_f32(kws_ctx* ctx, const float* d_logits, int C, int window, float* d_smoothed, int32_t* d_label);
 
+/* ---- scanning recordings longer than a clip (build-defined: the reference has no such mode; its nearest code is the
+ * record-then-classify loop of kws/inference/inference_local.py:114-192) ------------------------------------------- */
+
+/* Classify every window of R recordings of equal length: ONE MFCC pass over each recording, then the DS-CNN over strided
+ * windows of the frame array -- no window of PCM or of features is ever materialised.
+ *   d_pcm: int16 [R, n_total] (device).  Frames: each recording is ONE clip of n_total samples under the context's own front
+ *   end (kws_set_frontend except its n_samples, kws_set_frontend_math, kws_set_frontend_refine): F_total =
+ *   1 + ceil((n_total - frame_len) / frame_step) frames (1 when n_total <= frame_len), the last one zero-padded as psf does;
+ *   bit-identical, refinement included, to kws_mfcc_i16 with B = R on a context configured with n_samples = n_total, and
+ *   counted by kws_frontend_stats as that call counts them (R * F_total frames through the float32 front end).  The context's
+ *   own n_samples is neither used nor changed.
+ *   Windows: T = the context's num_frames (the model's clip length, kws_frontend_shape).  Window w of recording r is frames
+ *   [w * hop_frames, w * hop_frames + T); W = (F_total - T) / hop_frames + 1, rounded down (kws_host_scan_shape gives both
+ *   counts).  Window w covers samples [w * hop_frames * frame_step, w * hop_frames * frame_step + (T - 1) * frame_step +
+ *   frame_len), clipped to n_total.
+ *   d_logits: float32 [R, W, C].  d_label: int32 [R, W] or NULL, first maximum wins.  d_feat_out: float32 [R, F_total, numcep]
+ *   or NULL; NULL keeps the frames in a context workspace that grows on demand, so the call allocates and is not for stream
+ *   capture.
+ *   A recording of exactly n_samples samples gives W = 1 and the logits and label of kws_infer_i16 on it, bit for bit.  Any
+ *   other window differs from clip-wise inference on the same samples in two places, exactly as the streaming ring does: the
+ *   first sample of its first frame (pre-emphasis continues across the window start) and its last frame (which sees real
+ *   samples where a clip is zero-padded).  Given the frames, a window's logits are bit-identical to kws_forward_f32 on those
+ *   99 rows, wherever the window sits.
+ *   Scope: a 99 x 10 window map (the fused kernel), a one-channel model, KWS_PW_PAIR_F16 or KWS_PW_SPLIT_BF16; anything else
+ *   is KWS_EUNSUPPORTED.  F_total < T, hop_frames < 1, R < 1, n_total < 1 or a NULL d_pcm / d_logits: KWS_EINVAL.  No front end
+ *   or no model: KWS_ESTATE.  Limits (KWS_EUNSUPPORTED beyond): R * F_total <= 2^28 -- the refinement worklist packs
+ *   (recording * ceil(F_total / 2) + frame pair) << 2 into 32 bits, and a recording's F_total * numcep floats are a 32-bit
+ *   stride of the window kernel; R * W <= 2^30 -- the window index and the persistent kernel's next-window index are ints;
+ *   n_total <= 2^30 -- the front-end kernels form sample indices up to a chunk past the end in ints.  The refinement
+ *   worklist grows with R * F_total (a tone flags every frame).
+ *   Timed under KWS_K_MFCC / KWS_K_MFCC_REFINE / KWS_K_MFCC_F64 and KWS_K_DSCNN.  Asynchronous on the context stream. */
+int kws_scan_i16(kws_ctx* ctx, const int16_t* d_pcm, int R, int n_total, int hop_frames, float* d_logits, int32_t* d_label,
+                 float* d_feat_out);
+
+/* Causal decisions over a scan's logits [R, W, C] (C <= 64) -- the decisions a stream would have made at each hop.
+ *   p[r, w, :] = softmax(logits[r, w, :]) as kws_softmax_f32 computes it.
+ *   Smoothing: s[r, w, c] = mean of p[r, v, c] over v = max(0, w - S + 1) .. w, S = smooth_window in [1, 256]: summed in
+ *   float32, oldest first, then divided by the number of terms -- the rule of kws_stream_smooth_f32 (fewer terms while the
+ *   history is shorter), as a direct sum per output (no running sum, no drift).
+ *   Candidates: k = first argmax of s[r, w, :]; window w is a candidate when k >= first_keyword and s[r, w, k] >= threshold
+ *   (first_keyword = 2 skips _silence_ / _unknown_, kws/common/types.py; 0 skips nothing).
+ *   Events: walking w upwards with next = 0, a candidate at w >= next is the event (w, k, s[r, w, k]) and sets
+ *   next = w + refractory (refractory >= 1; 1: every candidate fires).
+ *   d_event_count int32 [R]: the number of events, even beyond max_events.  The first min(count, max_events) events of
+ *   recording r go to d_event_window / d_event_label (int32) and d_event_score (float32), each [R, max_events], in window
+ *   order; slots beyond the count are not written (max_events == 0: the three may be NULL).  d_smoothed: float32 [R, W, C]
+ *   or NULL.  Deterministic: no atomics.  The kernels are not timed; scratch of R * W * (C + 2) floats lives in the context.
+ *   A NULL d_logits / d_event_count, R or W < 1, C outside [1, 64], S outside [1, 256], refractory < 1, first_keyword < 0,
+ *   max_events < 0: KWS_EINVAL.  R * W > 2^30: KWS_EUNSUPPORTED. */
+int kws_scan_detect_f32(kws_ctx* ctx, const float* d_logits, int R, int W, int C, int smooth_window, int first_keyword,
+                        float threshold, int refractory, float* d_smoothed, int32_t* d_event_window, int32_t* d_event_label,
+                        float* d_event_score, int max_events, int32_t* d_event_count);
+
 /* ---- augmentation of the training transform (kws/libs/audio_processor.py:151-159,172-233) ---------- */
 
 /* out[b][i] = (silence[b] ? 0 : wav[b][i - shift[b]] / 32768, 0 outside the clip) + bg_vol[b] * bg[bg_off[b] + i]
@@ -517,6 +570,13 @@ int kws_host_dscnn_image(const float* blob, size_t n_floats, int num_classes, in
                          size_t cap_words, size_t* need_words, float* scalars);
 int kws_host_cnn_trad_image(const float* blob, size_t n_floats, int num_classes, uint32_t* out_words, size_t cap_words,
                             size_t* need_words, float* scalars);
+
+/* Frames of a recording of n_total samples taken as one clip (*frames_total = 1 + ceil((n_total - frame_len) / frame_step),
+ * 1 when n_total <= frame_len) and windows of a scan over it (*n_windows = (frames_total - window_frames) / hop_frames + 1,
+ * rounded down; 0 when the recording is shorter than a window) -- the shapes of kws_scan_i16's outputs.  Either pointer may
+ * be NULL.  Non-positive sizes: KWS_EINVAL. */
+int kws_host_scan_shape(int n_total, int frame_len, int frame_step, int window_frames, int hop_frames, int* frames_total,
+                        int* n_windows);
 
 #ifdef __cplusplus
 }

@@ -22,12 +22,53 @@ const char* const kKernelNames[KWS_K_COUNT] = {"kws_mfcc_i16_kernel", "kws_dscnn
 
 using namespace kws;
 
-static int frames_for(int n_samples, int frame_len, int frame_step) {
+int frames_for(int n_samples, int frame_len, int frame_step) {
     if (n_samples <= frame_len) return 1;
     return 1 + (n_samples - frame_len + frame_step - 1) / frame_step;  // 1 + ceil((n - L)/step)
 }
 
+// What of a front end's launch parameters depends on the clip length (p.frame_len and p.frame_step are set): kws_set_frontend
+// for the context's clips, kws_scan_i16 for a whole recording as one clip.
+void set_clip_length(FrontendParams& p, int n_samples) {
+    p.n_samples = n_samples;
+    p.num_frames = frames_for(n_samples, p.frame_len, p.frame_step);
+    // 16-byte PCM loads: every clip base and every workgroup's first sample must be multiples of 8 samples
+    // (the pointer itself is checked per call; the tail of a clip falls back to guarded scalar loads)
+    p.vec_ok = (n_samples % 8 == 0) && ((MFCC_FRAMES_PER_WG * p.frame_step) % 8 == 0);
+}
+
 static void stream_free_fwd(kws_ctx* c);
+static int ensure_refine(kws_ctx* c, int B, int num_frames);
+
+// The launches of kws_mfcc_i16 for B clips of the geometry p (the context's own, or kws_scan_i16's recording-long clips):
+// float64, or float32 with the flagged frames redone.  refine_clips sizes the refinement's grid: the batch in one-second clips.
+int mfcc_i16_clips(kws_ctx* c, const FrontendParams& geometry, const int16_t* d_wav, int B, float* d_out, int refine_clips) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    FrontendParams p = geometry;
+    if ((reinterpret_cast<uintptr_t>(d_wav) & 15) != 0) p.vec_ok = 0;
+    if (c->fe_math == KWS_FE_F64 || !c->fe_fast_ok) {
+        ProfScope ps(c, KWS_K_MFCC_F64);
+        HIP_TRY(c, launch_mfcc_f64(c->stream, p, c->ft, d_wav, B, d_out));
+        return KWS_OK;
+    }
+    c->frames_seen += (unsigned long long)B * p.num_frames;
+    if (p.refine_span > 0.f) {
+        int rc = ensure_refine(c, B, p.num_frames);
+        if (rc) return rc;
+        const RefineList rl = {c->d_refine, c->d_refine + 8, c->refine_cap, 0};
+        {
+            ProfScope ps(c, KWS_K_MFCC);
+            HIP_TRY(c, launch_mfcc_flag(c->stream, p, c->ft, d_wav, B, d_out, rl));
+        }
+        ProfScope ps(c, KWS_K_MFCC_REFINE);
+        HIP_TRY(c, launch_mfcc_refine(c->stream, p, c->ft, d_wav, d_out, rl, refine_clips));
+        return KWS_OK;
+    }
+    ProfScope ps(c, KWS_K_MFCC);
+    HIP_TRY(c, launch_mfcc(c->stream, p, c->ft, d_wav, B, d_out));
+    return KWS_OK;
+}
+
 
 #pragma GCC visibility push(default)
 extern "C" {
@@ -96,6 +137,7 @@ void kws_destroy(kws_ctx* c) {
     if (c->d_conv_ws) (void)hipFree(c->d_conv_ws);
     if (c->d_train_ws) (void)hipFree(c->d_train_ws);
     if (c->d_feat_ws) (void)hipFree(c->d_feat_ws);
+    if (c->d_scan_ws) (void)hipFree(c->d_scan_ws);
     stream_free_fwd(c);  // rings, hop counter, captured graph, smoothing and endpointer history
     ingest_free(c);      // staging rings, copy streams, pack threads
     if (c->order_ev) (void)hipEventDestroy(c->order_ev);
@@ -154,18 +196,14 @@ int kws_set_frontend(kws_ctx* c, int sample_rate, int n_samples, int frame_len, 
     c->ft = im.tables(c->d_fe);
 
     FrontendParams& p = c->fp;
-    p.n_samples = n_samples;
     p.frame_len = frame_len;
     p.frame_step = frame_step;
-    p.num_frames = frames_for(n_samples, frame_len, frame_step);
+    set_clip_length(p, n_samples);
     p.nfilt = nfilt;
     p.numcep = numcep;
     p.append_energy = 1;
     p.preemph = preemph;
     p.chunk_samples = (MFCC_FRAMES_PER_WG - 1) * frame_step + frame_len;
-    // 16-byte PCM loads: every clip base and every workgroup's first sample must be multiples of 8 samples
-    // (the pointer itself is checked per call; the tail of a clip falls back to guarded scalar loads)
-    p.vec_ok = (n_samples % 8 == 0) && ((MFCC_FRAMES_PER_WG * frame_step) % 8 == 0);
     p.nfft = nfft;
     p.log2_nfft = log2n;
     p.refine_span = c->refine_span;
@@ -222,10 +260,10 @@ int kws_frontend_shape(kws_ctx* c, int* num_frames, int* numcep) {
     return KWS_OK;
 }
 
-// Worklist of the selective refinement for batches of up to B clips: int[8] counters + one entry per frame.  The counters
-// (running totals included) move to the new allocation.
-static int ensure_refine(kws_ctx* c, int B) {
-    const size_t frames = (size_t)B * ((c->fp.num_frames + 1) / 2);  // one entry per frame pair
+// Worklist of the selective refinement for batches of up to B clips of num_frames frames: int[8] counters + one entry per frame
+// pair.  The counters (running totals included) move to the new allocation.
+static int ensure_refine(kws_ctx* c, int B, int num_frames) {
+    const size_t frames = (size_t)B * ((num_frames + 1) / 2);  // one entry per frame pair
     if (frames > 0x1fffffffu) return fail(c, KWS_EUNSUPPORTED, "refinement worklist: more than 2^29 frame pairs in one call");
     if (c->d_refine && (int)frames <= c->refine_cap) return KWS_OK;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -248,7 +286,7 @@ int kws_reserve(kws_ctx* c, int max_batch) {
     if (max_batch <= 0) return fail(c, KWS_EINVAL, "kws_reserve: max_batch must be positive");
     if (!c->fe_ready) return fail(c, KWS_ESTATE, "front end not configured");
     if (c->refine_span > 0.f && c->fe_fast_ok) {
-        int rc = ensure_refine(c, max_batch);
+        int rc = ensure_refine(c, max_batch, c->fp.num_frames);
         if (rc) return rc;
     }
     const size_t need = (size_t)max_batch * c->fp.num_frames * c->fp.numcep;
@@ -269,30 +307,7 @@ int kws_mfcc_i16(kws_ctx* c, const int16_t* d_wav, int B, float* d_out) {
     if (rc) return rc;
     if (!d_out) return fail(c, KWS_EINVAL, "kws_mfcc_i16: d_out is NULL");
     if (!c->fe_ready) return fail(c, KWS_ESTATE, "kws_mfcc_i16: front end not configured");
-    HIP_TRY(c, hipSetDevice(c->device));
-    FrontendParams p = c->fp;
-    if ((reinterpret_cast<uintptr_t>(d_wav) & 15) != 0) p.vec_ok = 0;
-    if (c->fe_math == KWS_FE_F64 || !c->fe_fast_ok) {
-        ProfScope ps(c, KWS_K_MFCC_F64);
-        HIP_TRY(c, launch_mfcc_f64(c->stream, p, c->ft, d_wav, B, d_out));
-        return KWS_OK;
-    }
-    c->frames_seen += (unsigned long long)B * p.num_frames;
-    if (p.refine_span > 0.f) {
-        rc = ensure_refine(c, B);
-        if (rc) return rc;
-        const RefineList rl = {c->d_refine, c->d_refine + 8, c->refine_cap, 0};
-        {
-            ProfScope ps(c, KWS_K_MFCC);
-            HIP_TRY(c, launch_mfcc_flag(c->stream, p, c->ft, d_wav, B, d_out, rl));
-        }
-        ProfScope ps(c, KWS_K_MFCC_REFINE);
-        HIP_TRY(c, launch_mfcc_refine(c->stream, p, c->ft, d_wav, d_out, rl, B));
-        return KWS_OK;
-    }
-    ProfScope ps(c, KWS_K_MFCC);
-    HIP_TRY(c, launch_mfcc(c->stream, p, c->ft, d_wav, B, d_out));
-    return KWS_OK;
+    return mfcc_i16_clips(c, c->fp, d_wav, B, d_out, B);
 }
 
 int kws_mfcc_f32(kws_ctx* c, const float* d_wav, int B, float* d_out) {
@@ -308,7 +323,7 @@ int kws_mfcc_f32(kws_ctx* c, const float* d_wav, int B, float* d_out) {
     }
     c->frames_seen += (unsigned long long)B * c->fp.num_frames;
     if (c->fp.refine_span > 0.f) {
-        rc = ensure_refine(c, B);
+        rc = ensure_refine(c, B, c->fp.num_frames);
         if (rc) return rc;
         const RefineList rl = {c->d_refine, c->d_refine + 8, c->refine_cap, 0};
         {
@@ -545,7 +560,7 @@ int kws_stream_open(kws_ctx* c, int n_streams) {
     c->host_push = 0;
     c->last_push_host = false;
     if (c->refine_span > 0.f) {  // the pushes count the frames they redo in float64 in the refinement counters
-        int rc = ensure_refine(c, 1);
+        int rc = ensure_refine(c, 1, c->fp.num_frames);
         if (rc) return rc;
     }
     HIP_TRY(c, hipMemsetAsync(c->d_pcm_ring, 0, pcm_b, c->stream));
@@ -957,7 +972,7 @@ int kws_mfcc_augment_i16(kws_ctx* c, const int16_t* d_pcm, int N, const int32_t*
     c->frames_seen += (unsigned long long)B * p.num_frames;
     kws::RefineList rl{};
     if (p.refine_span > 0.f) {
-        rc = ensure_refine(c, B);
+        rc = ensure_refine(c, B, c->fp.num_frames);
         if (rc) return rc;
         rl = {c->d_refine, c->d_refine + 8, c->refine_cap, 0};
     }

@@ -60,6 +60,9 @@ struct kws_ctx {
     // workspace (MFCC features between the two kernels of kws_infer_i16)
     float* d_feat_ws = nullptr;
     size_t feat_ws_floats = 0;
+    // kws_scan_i16: a recording's frames when the caller keeps none (kws_scan_detect_f32's scratch is d_conv_ws)
+    float* d_scan_ws = nullptr;
+    size_t scan_ws_floats = 0;
 
     // streaming state (kws_stream_*): per-stream PCM ring, feature ring, hop counter, optional graph
     int n_streams = 0, ring_len = 0;
@@ -107,6 +110,11 @@ struct kws_ctx {
     double ms_total[KWS_K_COUNT] = {};
     long launches[KWS_K_COUNT] = {};
 };
+
+// Front-end pieces kws_api.hip shares with kws_scan.hip
+int frames_for(int n_samples, int frame_len, int frame_step);  // 1 + ceil((n - L) / step), 1 for n <= L (sigproc.py:31-35)
+void set_clip_length(FrontendParams& p, int n_samples);
+int mfcc_i16_clips(kws_ctx* c, const FrontendParams& geometry, const int16_t* d_wav, int B, float* d_out, int refine_clips);
 
 inline thread_local std::string g_create_err;
 

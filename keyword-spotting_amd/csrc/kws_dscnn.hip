@@ -1238,16 +1238,62 @@ __device__ __forceinline__ DscnnWeights weights_for_this_clip() {
 #endif
 }
 
+// The arguments of kws_dscnn_fwd_kernel as they lie in the kernel-argument segment (each at its natural alignment), for reads
+// that must not be hoisted (weights_for_this_clip, scan_windows_now).  FwdKernelFn is the kernel's type with the same members
+// in the same order; a static_assert below the kernel holds its signature to it, so the two cannot drift apart unnoticed.
+using FwdKernelFn = void (*)(DscnnWeights, const float*, int, float*, int32_t*, float*, unsigned long long*, const int*, StreamPush);
+struct FwdKernelArgs {
+    DscnnWeights w;
+    const float* feat;
+    int B;
+    float* logits;
+    int32_t* label;
+    float* act;
+    unsigned long long* stamps;
+    const int* ring_hops;
+    StreamPush sp;
+};
+
+// PERSIST + SCAN: the window strides read again where a clip is staged, as weights_for_this_clip reads the weights: kept in
+// scalar registers across the clip loop they push others out into vector registers, and block 4's tail has none to spare.
+__device__ __forceinline__ ScanWindows scan_windows_now() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    using KArg = const __attribute__((address_space(4))) FwdKernelArgs*;
+    KArg p = (KArg)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p->sp.scan;
+#else
+    return ScanWindows{};
+#endif
+}
+
+// Where the 99 x 10 floats of `clip` start: consecutive clips, or (SCAN) the strided windows of a scan (ScanWindows).
+template <bool SCAN>
+__device__ __forceinline__ const float* clip_features(const float* __restrict__ feat, int clip, const ScanWindows& sw) {
+    if constexpr (SCAN) {
+        // mulhi(i, floor(2^32 / d)) lies in (i / d - 1, i / d]: the quotient or one less
+        unsigned rec = __umulhi((unsigned)clip, sw.wpr_recip), win = (unsigned)clip - rec * sw.wpr;
+        if (win >= sw.wpr) {
+            win -= sw.wpr;
+            ++rec;
+        }
+        return feat + (size_t)rec * sw.row_floats + (size_t)win * sw.win_floats;
+    } else {
+        return feat + (size_t)clip * (IN_T * IN_F);
+    }
+}
+
 // PERSIST, block 4's tail: wavefronts 0 .. STAGE_WAVES-1 stage the padded feature map of `clip` at OFF_FEAT_P (the loads,
 // the zero pad, the scatter) and, for f16 pairs, publish its largest |feature| to stage-maxima set 0 -- the slots of the other
 // wavefronts are zeroed, so read_stage_max sees this clip alone (set 0 was last read before block 3).
-template <bool PAIR>
-__device__ __forceinline__ void stage_features_persist(float* lds, const float* __restrict__ feat, int clip, int tid) {
+template <bool PAIR, bool SCAN = false>
+__device__ __forceinline__ void stage_features_persist(float* lds, const float* __restrict__ feat, int clip, int tid,
+                                                       const ScanWindows& sw = ScanWindows{}) {
     constexpr int ST = STAGE_WAVES * 64;
     constexpr int FV = (IN_T * IN_F + ST - 1) / ST;
     static_assert(2 * STAGE_WAVES == NW, "each staging wavefront zeroes the maximum slot of one other wavefront");
     const int lane = tid & 63, wv = tid >> 6;
-    const float* f = feat + (size_t)clip * (IN_T * IN_F);
+    const float* f = clip_features<SCAN>(feat, clip, sw);
     float fv[FV];
 #pragma unroll
     for (int k = 0; k < FV; ++k) {
@@ -1327,7 +1373,11 @@ __device__ __forceinline__ void pool_fc_wave(const DscnnWeights& w, const float*
 // (OFF_FEAT_P) while 4-7 finish their units; one barrier closes both.  The pool + fc + argmax of the finished clip then runs
 // on wavefront NW - 1 beside the next clip's conv1, in which it has no unit.  Same units, orders and sums as one clip per
 // workgroup: the results are bit-identical.
-template <int MODE, bool DIAG = true, bool PRECONV = false, bool STREAM = false, bool CLUSTER = false, bool PERSIST = false>
+// SCAN (kws_scan_i16, launch_dscnn_scan): "clip" i is a window of a long recording's frame array -- only the address its
+// features are fetched from changes (clip_features); logits and labels stay indexed by i.
+// The parameter list is mirrored by FwdKernelArgs / FwdKernelFn (the persistent kernels read arguments from the segment).
+template <int MODE, bool DIAG = true, bool PRECONV = false, bool STREAM = false, bool CLUSTER = false, bool PERSIST = false,
+          bool SCAN = false>
 __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, const float* __restrict__ feat, int B,
                                                            float* __restrict__ logits, int32_t* __restrict__ label,
                                                            float* __restrict__ act_arg,
@@ -1335,6 +1385,7 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
                                                            const int* __restrict__ ring_hops, StreamPush sp) {
     static_assert(!STREAM || (MODE >= 4 && !DIAG && !PRECONV), "the fused push exists for the product paths only");
     static_assert(!PERSIST || ((MODE == 4 || MODE == 5) && !PRECONV && !STREAM), "persistent workgroups: batched product paths only");
+    static_assert(!SCAN || ((MODE == 4 || MODE == 5) && !DIAG && !PRECONV && !STREAM && !CLUSTER), "strided windows: batched product paths only");
     constexpr bool PAIR = MODE == 5;   // f16-pair arithmetic (kws_split_mfma.h): activations live in LDS in per-clip scaled units
     constexpr int NP = PAIR ? 2 : 3;
     BlockTables t1_pre{};              // PRECONV: block 1's tables between their fetch and their (PAIR: scaled) store
@@ -1377,7 +1428,7 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
     float* a_prev = nullptr;    // its pooled-means slot in the activation dump (diagnostics)
     if constexpr (PERSIST) {
         fetch_block_tables(w_arg, 1, tid_k, t1p);
-        if (wv_k < STAGE_WAVES) stage_features_persist<PAIR>(lds, feat, clip, tid_k);
+        if (wv_k < STAGE_WAVES) stage_features_persist<PAIR, SCAN>(lds, feat, clip, tid_k, sp.scan);
         load_conv1_frags(w_arg, wv_k, lane_k, c1p);
         __syncthreads();
     }
@@ -1456,7 +1507,7 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
     // The feature map and block 1's tables are on the critical path of this phase: their loads are issued first
     // (vector memory returns in order), the conv1 operands behind them.
     float* featp = lds + OFF_FEAT;
-    const float* f = feat + (size_t)clip * (IN_T * IN_F);
+    const float* f = clip_features<SCAN>(feat, clip, sp.scan);
     constexpr int FV = (IN_T * IN_F + NT - 1) / NT;
     float fv[FV];
     // streaming: the feature map is a ring of IN_T frames; after `hops` pushes the newest frame sits in row
@@ -1674,7 +1725,8 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
         // and the staging of the next; this clip's pool + fc runs behind it, beside the next clip's conv1.
         const int next = clip + (int)gridDim.x;
         __builtin_amdgcn_sched_barrier(0);
-        if (wv < STAGE_WAVES && next < B) stage_features_persist<PAIR>(lds, feat, next, tid);
+        const ScanWindows sw_next = SCAN ? scan_windows_now() : ScanWindows{};  // (outside the branch: a uniform scalar read)
+        if (wv < STAGE_WAVES && next < B) stage_features_persist<PAIR, SCAN>(lds, feat, next, tid, sw_next);
         stamp();  // 11: next clip staged (wavefront 0)
         load_conv1_frags(w, wv, lane, c1p);  // (unconditional: a conditional reload keeps the old copy live through the whole loop)
         __syncthreads();
@@ -1809,6 +1861,10 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
     }
 }
 
+// weights_for_this_clip and scan_windows_now read the arguments through FwdKernelArgs: a new or moved argument goes there too
+static_assert(std::is_same_v<decltype(&kws_dscnn_fwd_kernel<5, false, false, false, false, true, true>), FwdKernelFn>,
+              "kws_dscnn_fwd_kernel's parameters and FwdKernelArgs / FwdKernelFn must change together");
+
 }  // namespace
 
 // The kernel needs the CU's whole 160 KiB of LDS as dynamic shared memory: opt in once per device.
@@ -1828,7 +1884,11 @@ hipError_t dscnn_init_device() {
                              reinterpret_cast<const void*>(kws_dscnn_fwd_kernel<4, true, false, false, false, true>),
                              reinterpret_cast<const void*>(kws_dscnn_fwd_kernel<4, false, false, false, false, true>),
                              reinterpret_cast<const void*>(kws_dscnn_fwd_kernel<5, true, false, false, false, true>),
-                             reinterpret_cast<const void*>(kws_dscnn_fwd_kernel<5, false, false, false, false, true>)};
+                             reinterpret_cast<const void*>(kws_dscnn_fwd_kernel<5, false, false, false, false, true>),
+                             reinterpret_cast<const void*>(kws_dscnn_fwd_kernel<4, false, false, false, false, false, true>),
+                             reinterpret_cast<const void*>(kws_dscnn_fwd_kernel<4, false, false, false, false, true, true>),
+                             reinterpret_cast<const void*>(kws_dscnn_fwd_kernel<5, false, false, false, false, false, true>),
+                             reinterpret_cast<const void*>(kws_dscnn_fwd_kernel<5, false, false, false, false, true, true>)};
     for (const void* k : kernels) {
         hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (e != hipSuccess) return e;
@@ -1953,6 +2013,25 @@ hipError_t launch_dscnn(hipStream_t s, const DscnnWeights& w, const float* d_fea
             break;
         case 6: hipLaunchKernelGGL(kws_dscnn_fwd_kernel<6>, dim3(grid), dim3(NT), lds, s, w, d_feat, B, d_logits, d_label, d_act, d_stamps, d_ring_hops, lag); break;
         default: hipLaunchKernelGGL(kws_dscnn_fwd_kernel<1>, dim3(grid), dim3(NT), lds, s, w, d_feat, B, d_logits, d_label, d_act, d_stamps, d_ring_hops, lag); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_dscnn_scan(hipStream_t s, const DscnnWeights& w, const float* d_feat, int B, float* d_logits, int32_t* d_label,
+                             int mode, int n_cu, const ScanWindows& sw) {
+    if (mode != 4 && mode != 5) return hipErrorInvalidValue;  // refused by kws_scan_i16 before it gets here
+    const size_t lds = LDS_FLOATS * sizeof(float);
+    StreamPush sp{};
+    sp.scan = sw;
+    if (n_cu > 0 && B > n_cu) {  // persistent workgroups above the CU count, as launch_dscnn
+        if (mode == 5)
+            hipLaunchKernelGGL((kws_dscnn_fwd_kernel<5, false, false, false, false, true, true>), dim3(n_cu), dim3(NT), lds, s, w, d_feat, B, d_logits, d_label, nullptr, nullptr, nullptr, sp);
+        else
+            hipLaunchKernelGGL((kws_dscnn_fwd_kernel<4, false, false, false, false, true, true>), dim3(n_cu), dim3(NT), lds, s, w, d_feat, B, d_logits, d_label, nullptr, nullptr, nullptr, sp);
+    } else if (mode == 5) {
+        hipLaunchKernelGGL((kws_dscnn_fwd_kernel<5, false, false, false, false, false, true>), dim3(B), dim3(NT), lds, s, w, d_feat, B, d_logits, d_label, nullptr, nullptr, nullptr, sp);
+    } else {
+        hipLaunchKernelGGL((kws_dscnn_fwd_kernel<4, false, false, false, false, false, true>), dim3(B), dim3(NT), lds, s, w, d_feat, B, d_logits, d_label, nullptr, nullptr, nullptr, sp);
     }
     return hipGetLastError();
 }

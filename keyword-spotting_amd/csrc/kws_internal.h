@@ -185,11 +185,25 @@ struct DscnnWeights {
 };
 
 hipError_t dscnn_init_device();
+// Strided windows of a scan (kws_scan_i16; kws_dscnn_fwd_kernel, SCAN): "clip" i of the launch is window i % wpr of recording
+// i / wpr, and its 99 x 10 floats start at feat + (i / wpr) * row_floats + (i % wpr) * win_floats -- 99 consecutive rows of the
+// recording's [F_total][10] frame array.  The kernel forms the offset in 64 bits; each factor fits 32 (R * F_total <= 2^28).
+struct ScanWindows {
+    unsigned wpr;          // windows per recording
+    unsigned wpr_recip;    // floor(2^32 / wpr), 2^32 - 1 for wpr == 1: i / wpr = mulhi(i, wpr_recip), or one more (all scalar, no
+                           // division in the persistent kernel's block-4 tail, where every register is taken)
+    unsigned row_floats;   // one recording's frames: F_total * 10
+    unsigned win_floats;   // from one window to the next: hop_frames * 10
+};
 // The streaming push as ONE launch: every stream's workgroup of the DS-CNN kernel computes that stream's new MFCC frame in
 // its prologue (kws_mfcc_dev.h: stream_frame_wave), appends the hop to the PCM ring, and the last workgroup to finish
 // advances the hop counter.  d_feat_ring: [n_streams][num_frames][numcep]; d_hops: {pushes so far, finished workgroups}.
 struct StreamPush {
-    FrontendParams p;
+    union {
+        FrontendParams p;
+        ScanWindows scan;    // SCAN only (launch_dscnn_scan): where a window's features start; nothing else of this struct is read then.
+                             // Shares p's bytes: the kernel-argument segment of every other instantiation stays as it was
+    };
     FrontendTables t;
     const int16_t* hop;      // [n_streams][frame_step]
     int16_t* pcm_ring;       // [n_streams][ring_len]
@@ -209,6 +223,10 @@ hipError_t launch_dscnn_stream(hipStream_t s, const DscnnWeights& w, const Strea
 hipError_t launch_dscnn(hipStream_t s, const DscnnWeights& w, const float* d_feat, int B, float* d_logits,
                         int32_t* d_label, float* d_act, int mode, unsigned long long* d_stamps = nullptr,
                         const int* d_ring_hops = nullptr, bool preconv = false, int frames_lag = 3, int n_cu = 0);
+// The batched product kernels over the strided windows of a scan: B = R * sw.wpr windows, logits [B][C] and labels [B] in window
+// order; mode 4 or 5 only.  One window per workgroup, or persistent workgroups above n_cu windows, exactly as launch_dscnn chooses.
+hipError_t launch_dscnn_scan(hipStream_t s, const DscnnWeights& w, const float* d_feat, int B, float* d_logits, int32_t* d_label,
+                             int mode, int n_cu, const ScanWindows& sw);
 // conv1 of a model with input_channels > 1: x [B][C_in][99][10] -> relu(conv1) [B][64][141]; d_wt = weights as [ci][tap][co]
 hipError_t launch_conv1_general(hipStream_t s, const float* d_x, int B, int C_in, const float* d_wt, const float* d_bias, float* d_out);
 
@@ -255,6 +273,12 @@ hipError_t launch_pool_fc(hipStream_t s, const float* d_x, int B, int HW, const 
 hipError_t launch_softmax(hipStream_t s, const float* d_logits, int B, int C, float* d_prob);
 hipError_t launch_smooth_posteriors(hipStream_t s, const float* d_logits, int S, int C, int window, float* d_ring,
                                     float* d_sum, int* d_count, float* d_smoothed, int32_t* d_label);
+// Decisions over a scan's logits (kws_scan_detect_f32, kws_scan.hip): smoothed posteriors + candidates per window, then the
+// refractory walk per recording.  d_cand: int32 [R * W] scratch (candidate label or -1), d_score: float32 [R * W] scratch.
+hipError_t launch_scan_detect(hipStream_t s, const float* d_logits, int R, int W, int C, int smooth_window, int first_keyword,
+                              float threshold, int refractory, float* d_smoothed, int32_t* d_cand, float* d_score,
+                              int32_t* d_event_window, int32_t* d_event_label, float* d_event_score, int max_events,
+                              int32_t* d_event_count);
 hipError_t launch_stream_vad(hipStream_t s, const float* d_feat_ring, const int* d_hops, int n_streams, int num_frames, int numcep,
                              int frames_lag, float threshold, int on_window, int off_window, unsigned char* d_flags, int* d_cursor_trig,
                              int32_t* d_state);

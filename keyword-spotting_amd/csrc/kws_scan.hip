@@ -1,0 +1,163 @@
+// Scanning recordings longer than a clip (include/kws_hip.h: kws_scan_i16, kws_scan_detect_f32, kws_host_scan_shape): ONE MFCC
+// pass over each recording as one long clip, the DS-CNN over strided 99-frame windows of the frame array (kws_dscnn_fwd_kernel,
+// SCAN), and the causal decision layer that turns the windows' logits into a short list of events.
+#include "kws_ctx.h"
+
+using namespace kws;
+
+namespace {
+
+// Smoothed posteriors and candidates, one thread per window.  p: softmax rows [R * W][C] (launch_softmax).  s[c] = the sum of
+// p[v][c] over the last min(S, w + 1) windows, oldest first, divided by their number; k = first argmax.  cand[i] = k when k is
+// a keyword at or over the threshold, else -1; score[i] = s[k].
+__global__ __launch_bounds__(256) void kws_scan_smooth_kernel(const float* __restrict__ p, int n, int W, int C, int S, int first_keyword,
+                                                              float threshold, float* __restrict__ smoothed, int32_t* __restrict__ cand,
+                                                              float* __restrict__ score) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;  // r * W + w
+    if (i >= n) return;
+    const int w = i % W;
+    const int terms = w + 1 < S ? w + 1 : S;
+    const float* first = p + (size_t)(i - terms + 1) * C;
+    const float count = (float)terms;
+    float best = -1.f;
+    int arg = 0;
+    for (int c = 0; c < C; ++c) {
+        float a = 0.f;
+        for (int v = 0; v < terms; ++v) a += first[(size_t)v * C + c];
+        a /= count;
+        if (smoothed) smoothed[(size_t)i * C + c] = a;
+        if (a > best) {
+            best = a;
+            arg = c;
+        }
+    }
+    cand[i] = (arg >= first_keyword && best >= threshold) ? arg : -1;
+    score[i] = best;
+}
+
+// The refractory walk, one wavefront per recording, 64 windows per step: the first candidate lane at or after `next` fires,
+// `next` moves `refractory` windows on, and the step repeats until no candidate lane is left.  Everything but the event stores
+// is wave-uniform; events land in window order with no atomics.
+__global__ __launch_bounds__(64) void kws_scan_events_kernel(const int32_t* __restrict__ cand, const float* __restrict__ score, int W,
+                                                             int refractory, int32_t* __restrict__ ev_window, int32_t* __restrict__ ev_label,
+                                                             float* __restrict__ ev_score, int max_events, int32_t* __restrict__ ev_count) {
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const int32_t* cr = cand + (size_t)r * W;
+    const float* sr = score + (size_t)r * W;
+    long long next = 0;
+    int count = 0;
+    for (int w0 = 0; w0 < W; w0 += 64) {
+        const int w = w0 + lane;
+        const int k = w < W ? cr[w] : -1;
+        const float sc = w < W ? sr[w] : 0.f;
+        unsigned long long left = __ballot(k >= 0);
+        while (left) {
+            const int f = __builtin_ctzll(left);
+            left &= left - 1;  // lanes below f are gone already
+            if (w0 + f < next) continue;
+            if (lane == f && count < max_events) {
+                const size_t at = (size_t)r * max_events + count;
+                ev_window[at] = w;
+                ev_label[at] = k;
+                ev_score[at] = sc;
+            }
+            ++count;
+            next = (long long)w0 + f + refractory;
+        }
+    }
+    if (lane == 0) ev_count[r] = count;
+}
+
+}  // namespace
+
+namespace kws {
+
+hipError_t launch_scan_detect(hipStream_t s, const float* d_prob, int R, int W, int C, int smooth_window, int first_keyword,
+                              float threshold, int refractory, float* d_smoothed, int32_t* d_cand, float* d_score,
+                              int32_t* d_event_window, int32_t* d_event_label, float* d_event_score, int max_events,
+                              int32_t* d_event_count) {
+    const int n = R * W;
+    hipLaunchKernelGGL(kws_scan_smooth_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_prob, n, W, C, smooth_window, first_keyword,
+                       threshold, d_smoothed, d_cand, d_score);
+    hipLaunchKernelGGL(kws_scan_events_kernel, dim3(R), dim3(64), 0, s, d_cand, d_score, W, refractory, d_event_window, d_event_label,
+                       d_event_score, max_events, d_event_count);
+    return hipGetLastError();
+}
+
+}  // namespace kws
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int kws_host_scan_shape(int n_total, int frame_len, int frame_step, int window_frames, int hop_frames, int* frames_total,
+                        int* n_windows) {
+    if (n_total <= 0 || frame_len <= 0 || frame_step <= 0 || window_frames <= 0 || hop_frames <= 0) return KWS_EINVAL;
+    const int F = frames_for(n_total, frame_len, frame_step);
+    if (frames_total) *frames_total = F;
+    if (n_windows) *n_windows = F < window_frames ? 0 : (F - window_frames) / hop_frames + 1;
+    return KWS_OK;
+}
+
+int kws_scan_i16(kws_ctx* c, const int16_t* d_pcm, int R, int n_total, int hop_frames, float* d_logits, int32_t* d_label,
+                 float* d_feat_out) {
+    if (!c) return KWS_EINVAL;
+    if (!d_pcm || !d_logits) return fail(c, KWS_EINVAL, "kws_scan_i16: d_pcm / d_logits is NULL");
+    if (R < 1 || n_total < 1 || hop_frames < 1) return fail(c, KWS_EINVAL, "kws_scan_i16: R, n_total and hop_frames must be positive");
+    if (!c->fe_ready || !c->model_ready) return fail(c, KWS_ESTATE, "kws_scan_i16: front end or model not configured");
+    if (c->fp.num_frames != IN_T || c->fp.numcep != IN_F)
+        return fail(c, KWS_EUNSUPPORTED, "kws_scan_i16: the strided DS-CNN kernel is built for windows of 99 x 10 features");
+    if (c->mw.in_channels != 1) return fail(c, KWS_EUNSUPPORTED, "kws_scan_i16: the MFCC front end yields one channel; the model was loaded with more");
+    if (c->pw_math != KWS_PW_PAIR_F16 && c->pw_math != KWS_PW_SPLIT_BF16)
+        return fail(c, KWS_EUNSUPPORTED, "kws_scan_i16: needs KWS_PW_PAIR_F16 or KWS_PW_SPLIT_BF16");
+    if (n_total > (1 << 30)) return fail(c, KWS_EUNSUPPORTED, "kws_scan_i16: more than 2^30 samples per recording");
+    FrontendParams p = c->fp;  // the context's geometry and arithmetic; the recording is one clip of n_total samples
+    set_clip_length(p, n_total);
+    const int T = c->fp.num_frames, F = p.num_frames;
+    if (F < T) return fail(c, KWS_EINVAL, "kws_scan_i16: the recording is shorter than one window");
+    const int W = (F - T) / hop_frames + 1;
+    if ((unsigned long long)R * F > (1ull << 28) || (unsigned long long)R * W > (1ull << 30))
+        return fail(c, KWS_EUNSUPPORTED, "kws_scan_i16: more than 2^28 frames or 2^30 windows in one call");
+    HIP_TRY(c, hipSetDevice(c->device));
+    float* feat = d_feat_out;
+    if (!feat) {
+        int rc = grow_device_buffer(c, c->d_scan_ws, c->scan_ws_floats, (size_t)R * F * p.numcep, "kws_scan_i16", "frame workspace");
+        if (rc) return rc;
+        feat = c->d_scan_ws;
+    }
+    // the refinement's grid: the batch in one-second clips (R * F <= 2^28 was checked above)
+    int rc = mfcc_i16_clips(c, p, d_pcm, R, feat, (int)((unsigned long long)R * F / T + 1));
+    if (rc) return rc;
+    const ScanWindows sw = {(unsigned)W, W == 1 ? 0xffffffffu : (unsigned)((1ull << 32) / (unsigned)W), (unsigned)F * (unsigned)IN_F,
+                            (unsigned)hop_frames * (unsigned)IN_F};
+    ProfScope ps(c, KWS_K_DSCNN);
+    HIP_TRY(c, launch_dscnn_scan(c->stream, c->mw, feat, R * W, d_logits, d_label, c->pw_math, c->n_cu, sw));
+    return KWS_OK;
+}
+
+int kws_scan_detect_f32(kws_ctx* c, const float* d_logits, int R, int W, int C, int smooth_window, int first_keyword, float threshold,
+                        int refractory, float* d_smoothed, int32_t* d_event_window, int32_t* d_event_label, float* d_event_score,
+                        int max_events, int32_t* d_event_count) {
+    if (!c) return KWS_EINVAL;
+    if (!d_logits || !d_event_count) return fail(c, KWS_EINVAL, "kws_scan_detect_f32: d_logits / d_event_count is NULL");
+    if (max_events < 0 || (max_events > 0 && (!d_event_window || !d_event_label || !d_event_score)))
+        return fail(c, KWS_EINVAL, "kws_scan_detect_f32: max_events events need their three arrays");
+    if (R < 1 || W < 1 || C < 1 || C > MAX_CLASSES) return fail(c, KWS_EINVAL, "kws_scan_detect_f32: need R >= 1, W >= 1 and C in [1, 64]");
+    if (smooth_window < 1 || smooth_window > 256) return fail(c, KWS_EINVAL, "kws_scan_detect_f32: smooth_window must be in [1, 256]");
+    if (refractory < 1 || first_keyword < 0) return fail(c, KWS_EINVAL, "kws_scan_detect_f32: need refractory >= 1 and first_keyword >= 0");
+    if ((unsigned long long)R * W > (1ull << 30)) return fail(c, KWS_EUNSUPPORTED, "kws_scan_detect_f32: more than 2^30 windows in one call");
+    HIP_TRY(c, hipSetDevice(c->device));
+    // context scratch: posteriors [R W][C], then per window the candidate label and its score
+    const size_t n = (size_t)R * W;
+    int rc = grow_device_buffer(c, c->d_conv_ws, c->conv_ws_floats, n * C + 2 * n, "kws_scan_detect_f32", "workspace");
+    if (rc) return rc;
+    float* prob = c->d_conv_ws;
+    float* score = prob + n * C;
+    int32_t* cand = reinterpret_cast<int32_t*>(score + n);
+    HIP_TRY(c, launch_softmax(c->stream, d_logits, (int)n, C, prob));
+    HIP_TRY(c, launch_scan_detect(c->stream, prob, R, W, C, smooth_window, first_keyword, threshold, refractory, d_smoothed, cand, score,
+                                  d_event_window, d_event_label, d_event_score, max_events, d_event_count));
+    return KWS_OK;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

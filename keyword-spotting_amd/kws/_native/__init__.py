@@ -89,6 +89,9 @@ SIGNATURES = {
     "kws_infer_cnn_trad_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, _f32p, _i32p]),
     "kws_softmax_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, _f32p]),
     "kws_stream_smooth_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, _f32p, _i32p]),
+    "kws_scan_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, _f32p]),
+    "kws_scan_detect_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _f32p, _i32p, _i32p,
+                                      _f32p, C.c_int, _i32p]),
     "kws_augment_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, C.c_void_p, _f32p, C.c_int, C.c_void_p, _f32p, C.c_void_p, _f32p]),
     "kws_augment_draw": (C.c_int, [_c_ctx, C.c_uint64, C.c_uint32, _i32p, C.c_int, _i32p, C.c_int, C.c_int, _i32p, _i32p, C.c_int, C.c_float,
                                    C.c_float, C.c_int, C.c_int, _i32p, _i32p, _f32p, C.c_void_p]),
@@ -111,6 +114,7 @@ SIGNATURES = {
                                        C.POINTER(C.c_size_t), C.POINTER(C.c_float)]),
     "kws_host_cnn_trad_image": (C.c_int, [C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_uint32), C.c_size_t,
                                           C.POINTER(C.c_size_t), C.POINTER(C.c_float)]),
+    "kws_host_scan_shape": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 
 _lib = None
@@ -397,6 +401,25 @@ class Context:
             ModelError,
         )
 
+    # -- scanning --------------------------------------------------------------------------------
+    def scan_i16(self, pcm, hop_frames, logits, label=None, feat=None):
+        """``kws_scan_i16``: ``pcm`` int16 [R, n_total] on the device -> ``logits`` float32 [R, W, C] (and ``label`` int32 [R, W])
+        for every window of 99 frames, ``hop_frames`` frames apart, of each recording's one MFCC pass; ``feat`` float32
+        [R, F_total, numcep] keeps the frames (``host_scan_shape`` gives F_total and W)."""
+        p = lambda t: _ptr(t) if t is not None else None
+        self._check(self._lib.kws_scan_i16(self._h, _ptr(pcm), int(pcm.shape[0]), int(pcm.shape[1]), int(hop_frames), _ptr(logits),
+                                           p(label), p(feat)), ModelError)
+
+    def scan_detect_f32(self, logits, smooth_window, first_keyword, threshold, refractory, event_count, event_window=None,
+                        event_label=None, event_score=None, max_events=0, smoothed=None):
+        """``kws_scan_detect_f32``: ``logits`` float32 [R, W, C] -> smoothed posteriors, candidates and events with a refractory
+        gap.  ``event_count`` int32 [R]; the three event arrays [R, max_events]; ``smoothed`` float32 [R, W, C] or None."""
+        p = lambda t: _ptr(t) if t is not None else None
+        R, W, Cn = (int(v) for v in logits.shape)
+        self._check(self._lib.kws_scan_detect_f32(self._h, _ptr(logits), R, W, Cn, int(smooth_window), int(first_keyword), float(threshold),
+                                                  int(refractory), p(smoothed), p(event_window), p(event_label), p(event_score),
+                                                  int(max_events), _ptr(event_count)), ModelError)
+
     # -- streaming -------------------------------------------------------------------------------
     def stream_open(self, n_streams: int):
         self._check(self._lib.kws_stream_open(self._h, int(n_streams)), AudioProcessingError)
@@ -562,6 +585,16 @@ def host_dct_lifter(nfilt=26, numcep=10, ceplifter=22) -> np.ndarray:
     if rc != KWS_OK:
         raise KWSError(f"kws_host_dct_lifter failed ({rc})")
     return out
+
+
+def host_scan_shape(n_total, frame_len=400, frame_step=160, window_frames=99, hop_frames=1):
+    """(frames_total, n_windows) of a scan over a recording of ``n_total`` samples (``kws_host_scan_shape``)."""
+    frames, windows = C.c_int(0), C.c_int(0)
+    rc = lib().kws_host_scan_shape(int(n_total), int(frame_len), int(frame_step), int(window_frames), int(hop_frames),
+                                   C.byref(frames), C.byref(windows))
+    if rc != KWS_OK:
+        raise KWSError(f"kws_host_scan_shape failed ({rc}): sizes must be positive")
+    return int(frames.value), int(windows.value)
 
 
 def _host_image(fn, n_scalars, blob, *dims):

@@ -3,17 +3,46 @@
 word), on the fused MI355X path and for whole batches of files."""
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Iterable, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from kws.common.errors import ModelError
+from kws.common.errors import AudioProcessingError, ModelError
 from kws.datasets.speech_commands import DEFAULT_WORDS, SpeechCommandDataset
 from kws.libs.audio_processor import AudioConfig, fix_length, load_audio, load_pcm16
 from kws.libs.models import DepthwiseSeparableConv
 
 WANTED_WORDS = [SpeechCommandDataset.SILENCE_LABEL, SpeechCommandDataset.UNKNOWN_LABEL] + DEFAULT_WORDS
+
+
+WINDOW_FRAMES = 99  # frames per window of a scan: the model's clip length
+
+
+def _round_half_up(x: float) -> int:
+    return int(np.floor(x + 0.5))  # psf's rounding of winlen * samplerate
+
+
+def scan_window_times(n_windows: int, hop_frames: int, frame_len: int = 400, frame_step: int = 160, sample_rate: int = 16000,
+                      window_frames: int = WINDOW_FRAMES, n_total: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """(start_s [W], end_s [W]) of a scan's windows: window w covers samples [w * hop_frames * frame_step,
+    w * hop_frames * frame_step + (window_frames - 1) * frame_step + frame_len), clipped to ``n_total`` when given."""
+    start = np.arange(int(n_windows), dtype=np.int64) * (int(hop_frames) * int(frame_step))
+    end = start + (int(window_frames) - 1) * int(frame_step) + int(frame_len)
+    if n_total is not None:
+        end = np.minimum(end, int(n_total))
+    return start / float(sample_rate), end / float(sample_rate)
+
+
+@dataclass
+class ScanResult:
+    """What ``KeywordSpotter.scan`` returns.  ``events`` is None unless a threshold was given: one list per recording of
+    ``(time_s, index, word, score)``, ``time_s`` being the end of the window that fired."""
+    labels: np.ndarray           # int32 [R, W]
+    logits: np.ndarray           # float32 [R, W, C]
+    window_start_s: np.ndarray   # float64 [W]
+    events: Optional[List[List[Tuple[float, int, str, float]]]] = None
 
 
 class KeywordSpotter:
@@ -106,6 +135,72 @@ class KeywordSpotter:
         labels = torch.empty((x.shape[0],), dtype=torch.int32, device=self.device)
         ctx.infer_f32(x, logits, labels)
         return labels.cpu().numpy(), logits.cpu().numpy()
+
+
+    def scan(self, pcm, hop_frames: int = 1, smooth_window: int = 1, threshold: Optional[float] = None, refractory: int = 50,
+             first_keyword: int = 2, max_events: int = 1024) -> ScanResult:
+        """Where are the keywords in a recording longer than a clip?  ``pcm``: int16 ``[n]`` or ``[R, n]`` (R recordings of
+        equal length), a host array or a device tensor.  One MFCC pass per recording, then the model on every window of 99
+        frames, ``hop_frames`` frames (10 ms each) apart (``kws_scan_i16``).  With a ``threshold`` the windows' posteriors are
+        smoothed over ``smooth_window`` windows and turned into events at least ``refractory`` windows apart, classes below
+        ``first_keyword`` (_silence_, _unknown_) never firing (``kws_scan_detect_f32``); at most ``max_events`` per recording
+        are returned.  A recording shorter than one window raises ``ModelError``."""
+        from kws import _native
+
+        if torch.is_tensor(pcm):
+            if pcm.dtype != torch.int16:
+                raise ModelError(f"scan expects int16 PCM, got {pcm.dtype}")
+            x = pcm
+        else:
+            a = np.asarray(pcm)
+            if a.dtype != np.int16:
+                raise ModelError(f"scan expects int16 PCM, got {a.dtype}")
+            x = torch.from_numpy(np.ascontiguousarray(a))
+        if x.dim() == 1:
+            x = x[None, :]
+        if x.dim() != 2 or x.shape[0] < 1:
+            raise ModelError(f"scan expects int16 [n] or [R, n], got shape {tuple(x.shape)}")
+        if int(hop_frames) < 1:
+            raise ModelError("scan: hop_frames must be at least 1")
+        if threshold is not None:
+            if not 1 <= int(smooth_window) <= 256:
+                raise ModelError("scan: smooth_window must be in [1, 256]")
+            if int(refractory) < 1 or int(first_keyword) < 0 or int(max_events) < 0:
+                raise ModelError("scan: need refractory >= 1, first_keyword >= 0 and max_events >= 0")
+        cfg = self.config
+        frame_len, frame_step = _round_half_up(cfg.frame_length * cfg.sample_rate), _round_half_up(cfg.frame_step * cfg.sample_rate)
+        R, n = int(x.shape[0]), int(x.shape[1])
+        frames, W = (0, 0) if n < 1 else _native.host_scan_shape(n, frame_len, frame_step, WINDOW_FRAMES, int(hop_frames))
+        if W < 1:
+            raise ModelError(f"scan: a recording of {n} samples ({frames} frames) is shorter than one window of {WINDOW_FRAMES} frames")
+        ctx = self.model._context(self.device.index or 0)
+        x = x.to(self.device).contiguous()
+        C = self.model.num_classes
+        logits = torch.empty((R, W, C), dtype=torch.float32, device=self.device)
+        labels = torch.empty((R, W), dtype=torch.int32, device=self.device)
+        ctx.scan_i16(x, int(hop_frames), logits, labels)
+        start_s, end_s = scan_window_times(W, int(hop_frames), frame_len, frame_step, cfg.sample_rate, WINDOW_FRAMES, n)
+        events = None
+        if threshold is not None:
+            m = int(max_events)
+            count = torch.empty((R,), dtype=torch.int32, device=self.device)
+            ev_w = torch.empty((R, m), dtype=torch.int32, device=self.device)
+            ev_k = torch.empty((R, m), dtype=torch.int32, device=self.device)
+            ev_s = torch.empty((R, m), dtype=torch.float32, device=self.device)
+            ctx.scan_detect_f32(logits, smooth_window, first_keyword, threshold, refractory, count,
+                                ev_w if m else None, ev_k if m else None, ev_s if m else None, m)
+            count, ev_w, ev_k, ev_s = count.cpu().numpy(), ev_w.cpu().numpy(), ev_k.cpu().numpy(), ev_s.cpu().numpy()
+            events = [[(float(end_s[ev_w[r, i]]), int(ev_k[r, i]), self.words[int(ev_k[r, i])], float(ev_s[r, i]))
+                       for i in range(min(int(count[r]), m))] for r in range(R)]
+        return ScanResult(labels.cpu().numpy(), logits.cpu().numpy(), start_s, events)
+
+    def scan_file(self, path: str, **kwargs) -> ScanResult:
+        """``scan`` over a whole wav file (no trimming or padding to a clip).  The file must be 16-bit mono PCM at the
+        configured rate: anything else raises ``AudioProcessingError`` with the reason."""
+        x = load_pcm16(path, self.config.sample_rate)
+        if x.ndim == 2:
+            raise AudioProcessingError(f"{path}: {x.shape[1]} channels; scan_file takes mono files")
+        return self.scan(x, **kwargs)
 
 
 _default: Optional[KeywordSpotter] = None
