@@ -37,7 +37,7 @@ void set_clip_length(FrontendParams& p, int n_samples) {
     p.vec_ok = (n_samples % 8 == 0) && ((MFCC_FRAMES_PER_WG * p.frame_step) % 8 == 0);
 }
 
-static void stream_free_fwd(kws_ctx* c);
+static void stream_free(kws_ctx* c);
 static int ensure_refine(kws_ctx* c, int B, int num_frames);
 
 // The launches of kws_mfcc_i16 for B clips of the geometry p (the context's own, or kws_scan_i16's recording-long clips):
@@ -138,7 +138,7 @@ void kws_destroy(kws_ctx* c) {
     if (c->d_train_ws) (void)hipFree(c->d_train_ws);
     if (c->d_feat_ws) (void)hipFree(c->d_feat_ws);
     if (c->d_scan_ws) (void)hipFree(c->d_scan_ws);
-    stream_free_fwd(c);  // rings, hop counter, captured graph, smoothing and endpointer history
+    stream_free(c);      // rings, hop counter, captured graph, smoothing and endpointer history (kws_decide.hip)
     ingest_free(c);      // staging rings, copy streams, pack threads
     if (c->order_ev) (void)hipEventDestroy(c->order_ev);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -190,7 +190,7 @@ int kws_set_frontend(kws_ctx* c, int sample_rate, int n_samples, int frame_len, 
 
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // tables of the previous configuration may be in use
-    if (c->n_streams) stream_free_fwd(c);         // ring geometry depends on the front end
+    if (c->n_streams) stream_free(c);             // ring geometry depends on the front end
     int rc = replace_device_image(c, c->d_fe, im.bytes.data(), im.bytes.size(), "kws_set_frontend");
     if (rc) return rc;
     c->ft = im.tables(c->d_fe);
@@ -293,13 +293,6 @@ int kws_reserve(kws_ctx* c, int max_batch) {
     if (need <= c->feat_ws_floats) return KWS_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     return grow_device_buffer(c, c->d_feat_ws, c->feat_ws_floats, need, "kws_reserve", "device");
-}
-
-static int check_batch(kws_ctx* c, const void* in, int B, const char* fn) {
-    if (!c) return KWS_EINVAL;
-    if (!in) return fail(c, KWS_EINVAL, std::string(fn) + ": input pointer is NULL");
-    if (B <= 0) return fail(c, KWS_EINVAL, std::string(fn) + ": B must be positive");
-    return KWS_OK;
 }
 
 int kws_mfcc_i16(kws_ctx* c, const int16_t* d_wav, int B, float* d_out) {
@@ -481,23 +474,6 @@ int kws_infer_f32(kws_ctx* c, const float* d_wav, int B, float* d_logits, int32_
 }
 
 // ---- streaming ------------------------------------------------------------------------------------
-static void smooth_free(kws_ctx* c) {
-    if (c->d_post_ring) (void)hipFree(c->d_post_ring);
-    if (c->d_post_sum) (void)hipFree(c->d_post_sum);
-    if (c->d_post_count) (void)hipFree(c->d_post_count);
-    c->d_post_ring = c->d_post_sum = nullptr;
-    c->d_post_count = nullptr;
-    c->post_window = c->post_classes = 0;
-}
-
-static void vad_free(kws_ctx* c) {
-    if (c->d_vad_flags) (void)hipFree(c->d_vad_flags);
-    if (c->d_vad_state) (void)hipFree(c->d_vad_state);
-    c->d_vad_flags = nullptr;
-    c->d_vad_state = nullptr;
-    c->vad_on = c->vad_off = 0;
-}
-
 static void host_results_free(kws_ctx* c) {
     if (c->h_stream_logits) (void)hipHostFree(c->h_stream_logits);
     if (c->h_stream_label) (void)hipHostFree(c->h_stream_label);
@@ -742,71 +718,6 @@ int kws_infer_cnn_trad_i16(kws_ctx* c, const int16_t* d_wav, int B, float* d_log
     rc = kws_mfcc_i16(c, d_wav, B, c->d_feat_ws);
     if (rc) return rc;
     return kws_forward_cnn_trad_f32(c, c->d_feat_ws, B, d_logits, d_label);
-}
-
-int kws_stream_vad_f32(kws_ctx* c, float log_energy_threshold, int on_window, int off_window, int32_t* d_state) {
-    if (!c) return KWS_EINVAL;
-    if (!c->n_streams) return fail(c, KWS_ESTATE, "kws_stream_vad_f32: call kws_stream_open first");
-    if (!d_state) return fail(c, KWS_EINVAL, "kws_stream_vad_f32: d_state is NULL");
-    if (on_window < 1 || off_window < on_window || off_window > 1024)
-        return fail(c, KWS_EINVAL, "kws_stream_vad_f32: need 1 <= on_window <= off_window <= 1024");
-    if (!c->fp.append_energy) return fail(c, KWS_EUNSUPPORTED, "kws_stream_vad_f32: needs cepstrum 0 = log frame energy (appendEnergy)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (on_window != c->vad_on || off_window != c->vad_off) {  // (re)start the history
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        vad_free(c);
-        const size_t fb = (size_t)c->n_streams * off_window, sb = sizeof(int) * 2 * (size_t)c->n_streams;
-        if (hipMalloc(reinterpret_cast<void**>(&c->d_vad_flags), fb) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&c->d_vad_state), sb) != hipSuccess) {
-            vad_free(c);
-            return fail(c, KWS_ENOMEM, "kws_stream_vad_f32: device allocation failed");
-        }
-        HIP_TRY(c, hipMemsetAsync(c->d_vad_flags, 0, fb, c->stream));
-        HIP_TRY(c, hipMemsetAsync(c->d_vad_state, 0, sb, c->stream));
-        c->vad_on = on_window;
-        c->vad_off = off_window;
-    }
-    HIP_TRY(c, launch_stream_vad(c->stream, c->d_feat_ring, c->d_hops, c->n_streams, c->fp.num_frames, c->fp.numcep,
-                                 (c->fp.frame_len + c->fp.frame_step - 1) / c->fp.frame_step, log_energy_threshold, on_window, off_window, c->d_vad_flags, c->d_vad_state, d_state));
-    return KWS_OK;
-}
-
-int kws_softmax_f32(kws_ctx* c, const float* d_logits, int B, int C, float* d_prob) {
-    int rc = check_batch(c, d_logits, B, "kws_softmax_f32");
-    if (rc) return rc;
-    if (!d_prob) return fail(c, KWS_EINVAL, "kws_softmax_f32: d_prob is NULL");
-    if (C < 1 || C > MAX_CLASSES) return fail(c, KWS_EUNSUPPORTED, "kws_softmax_f32: C must be in [1, 64]");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, launch_softmax(c->stream, d_logits, B, C, d_prob));
-    return KWS_OK;
-}
-
-int kws_stream_smooth_f32(kws_ctx* c, const float* d_logits, int C, int window, float* d_smoothed, int32_t* d_label) {
-    if (!c) return KWS_EINVAL;
-    if (!c->n_streams) return fail(c, KWS_ESTATE, "kws_stream_smooth_f32: call kws_stream_open first");
-    if (!d_logits || !d_smoothed) return fail(c, KWS_EINVAL, "kws_stream_smooth_f32: d_logits / d_smoothed is NULL");
-    if (C < 1 || C > MAX_CLASSES) return fail(c, KWS_EUNSUPPORTED, "kws_stream_smooth_f32: C must be in [1, 64]");
-    if (window < 1 || window > 4096) return fail(c, KWS_EINVAL, "kws_stream_smooth_f32: window must be in [1, 4096]");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (window != c->post_window || C != c->post_classes) {  // (re)start the history
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        smooth_free(c);
-        const size_t ring_b = sizeof(float) * (size_t)c->n_streams * window * C, sum_b = sizeof(float) * (size_t)c->n_streams * C;
-        if (hipMalloc(reinterpret_cast<void**>(&c->d_post_ring), ring_b) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&c->d_post_sum), sum_b) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&c->d_post_count), 2 * sizeof(int)) != hipSuccess) {
-            smooth_free(c);
-            return fail(c, KWS_ENOMEM, "kws_stream_smooth_f32: device allocation failed");
-        }
-        HIP_TRY(c, hipMemsetAsync(c->d_post_ring, 0, ring_b, c->stream));
-        HIP_TRY(c, hipMemsetAsync(c->d_post_sum, 0, sum_b, c->stream));
-        HIP_TRY(c, hipMemsetAsync(c->d_post_count, 0, 2 * sizeof(int), c->stream));
-        c->post_window = window;
-        c->post_classes = C;
-    }
-    HIP_TRY(c, launch_smooth_posteriors(c->stream, d_logits, c->n_streams, C, window, c->d_post_ring, c->d_post_sum,
-                                        c->d_post_count, d_smoothed, d_label));
-    return KWS_OK;
 }
 
 int kws_stream_close(kws_ctx* c) {
@@ -1087,5 +998,3 @@ int kws_prof_read(kws_ctx* c, int kernel_id, double* total_ms, int* launches) {
 
 }  // extern "C"
 #pragma GCC visibility pop
-
-static void stream_free_fwd(kws_ctx* c) { stream_free(c); }

@@ -1,5 +1,6 @@
 // The context behind the C ABI (include/kws_hip.h), the error plumbing and the device-memory helpers shared by the translation
-// units that implement it (kws_api.hip, kws_weights.hip, kws_ingest.hip, kws_*_bwd.hip), and the event bracket of a timed launch.
+// units that implement it (kws_api.hip, kws_weights.hip, kws_ingest.hip, kws_scan.hip, kws_decide.hip, kws_*_bwd.hip), and the
+// event bracket of a timed launch.
 #pragma once
 #include <new>
 
@@ -8,6 +9,8 @@
 namespace kws {
 struct Ingest;  // host-ingest pipeline state (kws_ingest.hip)
 void ingest_free(kws_ctx* c);
+void smooth_free(kws_ctx* c);  // posterior-smoothing and endpointer histories of the streams (kws_decide.hip)
+void vad_free(kws_ctx* c);
 }  // namespace kws
 
 using kws::FrontendParams; using kws::FrontendTables; using kws::DscnnWeights; using kws::CnnTradWeights; using kws::NFFT;
@@ -127,6 +130,12 @@ inline int fail(kws_ctx* c, int code, const std::string& msg) {
 }
 inline int fail_hip(kws_ctx* c, hipError_t e, const char* what) {
     return fail(c, KWS_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+inline int check_batch(kws_ctx* c, const void* in, int B, const char* fn) {
+    if (!c) return KWS_EINVAL;
+    if (!in) return fail(c, KWS_EINVAL, std::string(fn) + ": input pointer is NULL");
+    if (B <= 0) return fail(c, KWS_EINVAL, std::string(fn) + ": B must be positive");
+    return KWS_OK;
 }
 // No exception may cross the C ABI (ctypes would terminate the process): entry points that allocate host containers or
 // start threads run their body between these two.

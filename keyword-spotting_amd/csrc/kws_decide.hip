@@ -1,0 +1,235 @@
+// The decision layer behind the logits (include/kws_hip.h: kws_softmax_f32, kws_stream_smooth_f32, kws_stream_vad_f32):
+// posteriors, their moving average per stream and the energy endpointer, each kernel with the entry point that drives it and
+// the history it keeps in the context.  (the reference's scripts take argmax of the logits.)
+#include "kws_ctx.h"
+
+namespace kws {
+namespace {
+
+// one thread per clip / stream: C <= 64 values, the work is launch latency, not arithmetic
+__device__ __forceinline__ void softmax_row(const float* __restrict__ z, int C, float* __restrict__ p) {
+    float m = z[0];
+    for (int i = 1; i < C; ++i) m = fmaxf(m, z[i]);
+    float sum = 0.f;
+    for (int i = 0; i < C; ++i) {
+        const float e = expf(z[i] - m);
+        p[i] = e;
+        sum += e;
+    }
+    const float inv = 1.0f / sum;
+    for (int i = 0; i < C; ++i) p[i] *= inv;
+}
+
+__global__ void kws_softmax_f32_kernel(const float* __restrict__ logits, int B, int C, float* __restrict__ prob) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) softmax_row(logits + (size_t)b * C, C, prob + (size_t)b * C);
+}
+
+// Moving average of the last `window` posterior vectors per stream (ring [S][window][C], running sum [S][C]),
+// then argmax of the smoothed vector (first maximum wins).  count = hops smoothed so far, before this one.
+// The running sum is updated incrementally (sum += p - oldest) and REBUILT from the ring every `window` hops (when the
+// write slot wraps to 0), so its float32 rounding error is bounded by one window's worth of updates instead of growing
+// over the life of a stream (10 ms hops = 8.6 M updates a day).
+__global__ void kws_smooth_posteriors_kernel(const float* __restrict__ logits, int S, int C, int window,
+                                             float* __restrict__ ring, float* __restrict__ sum, int* __restrict__ count_ptr,
+                                             float* __restrict__ smoothed, int32_t* __restrict__ label) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    const int count = count_ptr[0];
+    // every workgroup has read the hop count; the one that finishes last advances it (count_ptr[1] = done counter)
+    auto finish = [&]() {
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            __threadfence();
+            if (atomicAdd(&count_ptr[1], 1) == (int)gridDim.x - 1) {
+                count_ptr[1] = 0;
+                count_ptr[0] = count + 1;
+            }
+        }
+    };
+    if (s >= S) {
+        finish();
+        return;
+    }
+    const int slot = count % window;
+    float p[MAX_CLASSES];
+    softmax_row(logits + (size_t)s * C, C, p);
+    float* r = ring + ((size_t)s * window + slot) * C;
+    float* acc = sum + (size_t)s * C;
+    const float inv = 1.0f / (float)((count + 1 < window) ? count + 1 : window);
+    float best = -1.f;
+    int arg = 0;
+    const bool rebuild = count >= window && slot == 0;
+    for (int i = 0; i < C; ++i) {
+        const float old = count >= window ? r[i] : 0.f;
+        r[i] = p[i];
+        float a;
+        if (rebuild) {
+            a = 0.f;
+            for (int k = 0; k < window; ++k) a += ring[((size_t)s * window + k) * C + i];
+        } else {
+            a = acc[i] + (p[i] - old);
+        }
+        acc[i] = a;
+        const float v = a * inv;
+        smoothed[(size_t)s * C + i] = v;
+        if (v > best) {
+            best = v;
+            arg = i;
+        }
+    }
+    if (label) label[s] = arg;
+    finish();
+}
+
+}  // namespace
+
+hipError_t launch_softmax(hipStream_t s, const float* d_logits, int B, int C, float* d_prob) {
+    hipLaunchKernelGGL(kws_softmax_f32_kernel, dim3((B + 255) / 256), dim3(256), 0, s, d_logits, B, C, d_prob);
+    return hipGetLastError();
+}
+
+// Energy endpointer per stream (the gate that replaces webrtcvad in the reference's live loop,
+// kws/inference/inference_local.py:131-166 -- same hysteresis, at hop granularity).  The newest frame's log energy
+// (cepstrum 0 with appendEnergy) above the threshold marks the hop voiced; an utterance OPENS when more than 80 % of the
+// last `on_window` hops are voiced (:151) and CLOSES when more than 90 % of the last `off_window` hops are unvoiced
+// (:161); hops before the stream began count as unvoiced (the reference's rings start as zeros).  One thread per stream.
+// state[s] = triggered | event << 1, event 1 = opened at this hop, 2 = closed at this hop.
+__global__ void kws_stream_vad_kernel(const float* __restrict__ feat_ring, const int* __restrict__ hops_ptr, int n_streams,
+                                      int num_frames, int numcep, int frames_lag, float threshold, int on_window, int off_window,
+                                      unsigned char* __restrict__ flags, int* __restrict__ cursor_trig, int32_t* __restrict__ state) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_streams) return;
+    const int hops = *hops_ptr;  // already advanced by the push this call follows: the newest frame is hops - K (K hops per frame)
+    if (hops < frames_lag) {     // no complete frame yet
+        state[s] = 0;
+        return;
+    }
+    const float c0 = feat_ring[((size_t)s * num_frames + (hops - frames_lag) % num_frames) * numcep];
+    unsigned char* fl = flags + (size_t)s * off_window;
+    const int cur = cursor_trig[2 * s];
+    int trig = cursor_trig[2 * s + 1];
+    fl[cur % off_window] = c0 > threshold ? 1 : 0;
+    int n_on = 0, n_all = 0;
+    for (int k = 0; k < off_window; ++k) {  // k hops back from the newest
+        const int v = k <= cur ? fl[(cur - k) % off_window] : 0;
+        n_all += v;
+        if (k < on_window) n_on += v;
+    }
+    int event = 0;
+    if (!trig) {
+        if (10 * n_on > 8 * on_window) trig = 1, event = 1;
+    } else if (10 * (off_window - n_all) > 9 * off_window) {
+        trig = 0, event = 2;
+    }
+    cursor_trig[2 * s] = cur + 1;
+    cursor_trig[2 * s + 1] = trig;
+    state[s] = trig | (event << 1);
+}
+
+hipError_t launch_stream_vad(hipStream_t s, const float* d_feat_ring, const int* d_hops, int n_streams, int num_frames, int numcep,
+                             int frames_lag, float threshold, int on_window, int off_window, unsigned char* d_flags, int* d_cursor_trig,
+                             int32_t* d_state) {
+    hipLaunchKernelGGL(kws_stream_vad_kernel, dim3((n_streams + 63) / 64), dim3(64), 0, s, d_feat_ring, d_hops, n_streams,
+                       num_frames, numcep, frames_lag, threshold, on_window, off_window, d_flags, d_cursor_trig, d_state);
+    return hipGetLastError();
+}
+
+hipError_t launch_smooth_posteriors(hipStream_t s, const float* d_logits, int S, int C, int window, float* d_ring,
+                                    float* d_sum, int* d_count, float* d_smoothed, int32_t* d_label) {
+    hipLaunchKernelGGL(kws_smooth_posteriors_kernel, dim3((S + 63) / 64), dim3(64), 0, s, d_logits, S, C, window, d_ring, d_sum,
+                       d_count, d_smoothed, d_label);
+    return hipGetLastError();
+}
+
+// The histories of the two streaming entry points below; stream_free (kws_api.hip) drops them with the streams.
+void smooth_free(kws_ctx* c) {
+    if (c->d_post_ring) (void)hipFree(c->d_post_ring);
+    if (c->d_post_sum) (void)hipFree(c->d_post_sum);
+    if (c->d_post_count) (void)hipFree(c->d_post_count);
+    c->d_post_ring = c->d_post_sum = nullptr;
+    c->d_post_count = nullptr;
+    c->post_window = c->post_classes = 0;
+}
+
+void vad_free(kws_ctx* c) {
+    if (c->d_vad_flags) (void)hipFree(c->d_vad_flags);
+    if (c->d_vad_state) (void)hipFree(c->d_vad_state);
+    c->d_vad_flags = nullptr;
+    c->d_vad_state = nullptr;
+    c->vad_on = c->vad_off = 0;
+}
+
+}  // namespace kws
+
+using namespace kws;
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int kws_stream_vad_f32(kws_ctx* c, float log_energy_threshold, int on_window, int off_window, int32_t* d_state) {
+    if (!c) return KWS_EINVAL;
+    if (!c->n_streams) return fail(c, KWS_ESTATE, "kws_stream_vad_f32: call kws_stream_open first");
+    if (!d_state) return fail(c, KWS_EINVAL, "kws_stream_vad_f32: d_state is NULL");
+    if (on_window < 1 || off_window < on_window || off_window > 1024)
+        return fail(c, KWS_EINVAL, "kws_stream_vad_f32: need 1 <= on_window <= off_window <= 1024");
+    if (!c->fp.append_energy) return fail(c, KWS_EUNSUPPORTED, "kws_stream_vad_f32: needs cepstrum 0 = log frame energy (appendEnergy)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (on_window != c->vad_on || off_window != c->vad_off) {  // (re)start the history
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        vad_free(c);
+        const size_t fb = (size_t)c->n_streams * off_window, sb = sizeof(int) * 2 * (size_t)c->n_streams;
+        if (hipMalloc(reinterpret_cast<void**>(&c->d_vad_flags), fb) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&c->d_vad_state), sb) != hipSuccess) {
+            vad_free(c);
+            return fail(c, KWS_ENOMEM, "kws_stream_vad_f32: device allocation failed");
+        }
+        HIP_TRY(c, hipMemsetAsync(c->d_vad_flags, 0, fb, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_vad_state, 0, sb, c->stream));
+        c->vad_on = on_window;
+        c->vad_off = off_window;
+    }
+    HIP_TRY(c, launch_stream_vad(c->stream, c->d_feat_ring, c->d_hops, c->n_streams, c->fp.num_frames, c->fp.numcep,
+                                 (c->fp.frame_len + c->fp.frame_step - 1) / c->fp.frame_step, log_energy_threshold, on_window, off_window, c->d_vad_flags, c->d_vad_state, d_state));
+    return KWS_OK;
+}
+
+int kws_softmax_f32(kws_ctx* c, const float* d_logits, int B, int C, float* d_prob) {
+    int rc = check_batch(c, d_logits, B, "kws_softmax_f32");
+    if (rc) return rc;
+    if (!d_prob) return fail(c, KWS_EINVAL, "kws_softmax_f32: d_prob is NULL");
+    if (C < 1 || C > MAX_CLASSES) return fail(c, KWS_EUNSUPPORTED, "kws_softmax_f32: C must be in [1, 64]");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, launch_softmax(c->stream, d_logits, B, C, d_prob));
+    return KWS_OK;
+}
+
+int kws_stream_smooth_f32(kws_ctx* c, const float* d_logits, int C, int window, float* d_smoothed, int32_t* d_label) {
+    if (!c) return KWS_EINVAL;
+    if (!c->n_streams) return fail(c, KWS_ESTATE, "kws_stream_smooth_f32: call kws_stream_open first");
+    if (!d_logits || !d_smoothed) return fail(c, KWS_EINVAL, "kws_stream_smooth_f32: d_logits / d_smoothed is NULL");
+    if (C < 1 || C > MAX_CLASSES) return fail(c, KWS_EUNSUPPORTED, "kws_stream_smooth_f32: C must be in [1, 64]");
+    if (window < 1 || window > 4096) return fail(c, KWS_EINVAL, "kws_stream_smooth_f32: window must be in [1, 4096]");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (window != c->post_window || C != c->post_classes) {  // (re)start the history
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        smooth_free(c);
+        const size_t ring_b = sizeof(float) * (size_t)c->n_streams * window * C, sum_b = sizeof(float) * (size_t)c->n_streams * C;
+        if (hipMalloc(reinterpret_cast<void**>(&c->d_post_ring), ring_b) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&c->d_post_sum), sum_b) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&c->d_post_count), 2 * sizeof(int)) != hipSuccess) {
+            smooth_free(c);
+            return fail(c, KWS_ENOMEM, "kws_stream_smooth_f32: device allocation failed");
+        }
+        HIP_TRY(c, hipMemsetAsync(c->d_post_ring, 0, ring_b, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_post_sum, 0, sum_b, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_post_count, 0, 2 * sizeof(int), c->stream));
+        c->post_window = window;
+        c->post_classes = C;
+    }
+    HIP_TRY(c, launch_smooth_posteriors(c->stream, d_logits, c->n_streams, C, window, c->d_post_ring, c->d_post_sum,
+                                        c->d_post_count, d_smoothed, d_label));
+    return KWS_OK;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

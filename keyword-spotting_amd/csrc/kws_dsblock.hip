@@ -13,6 +13,7 @@
 //                                  order; ring positions are written by the same kernel (relu(bias), no arithmetic)
 #include <algorithm>
 
+#include "kws_dscnn_geom.h"
 #include "kws_internal.h"
 #include "kws_split_mfma.h"
 
@@ -159,6 +160,47 @@ __global__ __launch_bounds__(256) void kws_conv1_any_kernel(const float* __restr
     }
 }
 
+// conv1 for input_channels > 1 on the 99 x 10 map, in front of the fused kernel's PRECONV entry (kws_dscnn.hip; reference
+// kws/libs/models.py:125,135: Conv2d(input_channels, 64, 10, stride 2, padding 2)):
+// one 512-thread workgroup per clip; thread (co = tid & 63, group g = tid >> 6) owns output channel co at positions
+// g, g + 8, ...; per input channel the zero-padded plane goes through LDS (every lane of a wavefront reads the same
+// address: a broadcast) and the 100 taps come from a [ci][tap][co] weight image (coalesced).  ReLU(bias + sum) -> [64][141].
+__global__ __launch_bounds__(NT) void kws_conv1_general_kernel(const float* __restrict__ x, int C_in, const float* __restrict__ wt,
+                                                               const float* __restrict__ bias, float* __restrict__ out) {
+    __shared__ float plane[FEAT_H * FEAT_W];
+    const int tid = threadIdx.x, co = tid & 63, g = tid >> 6;
+    constexpr int PER = (P0 + NW - 1) / NW;  // positions per thread
+    float acc[PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) acc[k] = 0.f;
+    const float* xc = x + (size_t)blockIdx.x * C_in * (IN_T * IN_F);
+    for (int ci = 0; ci < C_in; ++ci) {
+        __syncthreads();
+        for (int i = tid; i < FEAT_H * FEAT_W; i += NT) {
+            const int r = i / FEAT_W - 2, cidx = i % FEAT_W - 2;
+            plane[i] = ((unsigned)r < (unsigned)IN_T && (unsigned)cidx < (unsigned)IN_F) ? xc[(size_t)ci * (IN_T * IN_F) + r * IN_F + cidx] : 0.f;
+        }
+        __syncthreads();
+        const float* wc = wt + (size_t)ci * (C1_K * C1_K) * CH + co;
+        for (int tap = 0; tap < C1_K * C1_K; ++tap) {
+            const float wv_ = wc[(size_t)tap * CH];
+            const int kh = tap / C1_K, kw = tap % C1_K;
+#pragma unroll
+            for (int k = 0; k < PER; ++k) {
+                const int pos = g + NW * k;
+                if (pos < P0) acc[k] = fmaf(wv_, plane[(2 * (pos / C1_W) + kh) * FEAT_W + 2 * (pos % C1_W) + kw], acc[k]);
+            }
+        }
+    }
+    float* o = out + (size_t)blockIdx.x * (CH * P0) + (size_t)co * P0;
+    const float bv = bias[co];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int pos = g + NW * k;
+        if (pos < P0) o[pos] = relu(acc[k] + bv);
+    }
+}
+
 // F.adaptive_avg_pool2d(x, (1, 1)) + view + fc (models.py:179-181) + argmax, first maximum wins (training.py:371).
 // x: [B][64][HW] (the last block's output, ring included).  One workgroup per clip: four partial sums per channel, fc and
 // argmax on wavefront 0.
@@ -203,6 +245,11 @@ hipError_t launch_conv1_any(hipStream_t s, const float* d_x, int B, int C_in, in
     }
     hipLaunchKernelGGL(kws_conv1_any_kernel, dim3((Ho * Wo + C1A_POS - 1) / C1A_POS, B), dim3(256), lds, s, d_x, C_in, T, F, d_wt, d_bias,
                        Ho, Wo, d_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_conv1_general(hipStream_t s, const float* d_x, int B, int C_in, const float* d_wt, const float* d_bias, float* d_out) {
+    hipLaunchKernelGGL(kws_conv1_general_kernel, dim3(B), dim3(NT), 0, s, d_x, C_in, d_wt, d_bias, d_out);
     return hipGetLastError();
 }
 

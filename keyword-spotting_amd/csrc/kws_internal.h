@@ -166,7 +166,7 @@ struct DscnnWeights {
     const float* pw_w;     // [4][64][64] pointwise transposed: [cin][cout]
     const float* pw_b;     // [4][64]
     const uint32_t* pw_split;  // [4][ct 2][m 4][piece 3][lane 64][4]  pointwise weights as bf16 hi/mid/lo MFMA A operands
-    const uint32_t* c1_split;  // [ct 2][kb 7][piece 3][lane 64][4]    conv1 weights, same format (K order: see kws_dscnn.hip)
+    const uint32_t* c1_split;  // [ct 2][kb 7][piece 3][lane 64][4]    conv1 weights, same format (K order: see kws_dscnn_stages.h)
     const float* fc_w;     // [C][64]
     const float* fc_b;     // [C]
     int num_classes;
@@ -227,7 +227,7 @@ hipError_t launch_dscnn(hipStream_t s, const DscnnWeights& w, const float* d_fea
 // order; mode 4 or 5 only.  One window per workgroup, or persistent workgroups above n_cu windows, exactly as launch_dscnn chooses.
 hipError_t launch_dscnn_scan(hipStream_t s, const DscnnWeights& w, const float* d_feat, int B, float* d_logits, int32_t* d_label,
                              int mode, int n_cu, const ScanWindows& sw);
-// conv1 of a model with input_channels > 1: x [B][C_in][99][10] -> relu(conv1) [B][64][141]; d_wt = weights as [ci][tap][co]
+// conv1 of a model with input_channels > 1 (kws_dsblock.hip): x [B][C_in][99][10] -> relu(conv1) [B][64][141]; d_wt = weights as [ci][tap][co]
 hipError_t launch_conv1_general(hipStream_t s, const float* d_x, int B, int C_in, const float* d_wt, const float* d_bias, float* d_out);
 
 // ------------------------------------------------------------------------------------------------
@@ -270,6 +270,7 @@ hipError_t launch_conv1_any(hipStream_t s, const float* d_x, int B, int C_in, in
 hipError_t launch_pool_fc(hipStream_t s, const float* d_x, int B, int HW, const float* d_fc_w, const float* d_fc_b, int C,
                           float* d_logits, int32_t* d_label);
 
+// The decision layer (kws_decide.hip): posteriors, their moving average per stream, and further down the energy endpointer.
 hipError_t launch_softmax(hipStream_t s, const float* d_logits, int B, int C, float* d_prob);
 hipError_t launch_smooth_posteriors(hipStream_t s, const float* d_logits, int S, int C, int window, float* d_ring,
                                     float* d_sum, int* d_count, float* d_smoothed, int32_t* d_label);

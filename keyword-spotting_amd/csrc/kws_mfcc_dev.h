@@ -1,7 +1,7 @@
 // Device-side building blocks of the MFCC front end for gfx950: the packed 512-point transform, the spectrum split,
 // the sparse mel stage and the log / DCT tail of one frame pair (mfcc_pair), shared by the batched kernels
 // (kws_mfcc.hip) and by the streaming push, whose one-frame front end runs inside the DS-CNN kernel's prologue
-// (kws_dscnn.hip).  Everything lives in an anonymous namespace: each translation unit gets its own inlined copy.
+// (kws_dscnn.hip; its stages, kws_dscnn_stages.h, borrow dpp_shift_add).  Everything lives in an anonymous namespace: each translation unit gets its own inlined copy.
 // See kws_mfcc.hip for the work decomposition and the numerics.
 #pragma once
 #include "kws_internal.h"

@@ -33,7 +33,7 @@ __host__ __device__ inline void pack_bf16_triple(const float (&v)[8], uint32_t* 
 }
 
 // f16-pair pieces of x = v * scale (the layer's power of two): hi = f16(x) (round to nearest), lo = f16((x - hi) * resid).
-// resid = 1: the DS-CNN's PLAIN flavour (kws_dscnn.hip); resid = 2^11: cnn-trad-fpool3's (kws_cnntrad.hip, split_pair).
+// resid = 1: the DS-CNN's PLAIN flavour (kws_dscnn_stages.h); resid = 2^11: cnn-trad-fpool3's (kws_cnntrad.hip, split_pair).
 __host__ __device__ inline void pack_f16_pair(const float (&v)[8], float scale, float resid, uint32_t* dst) {
     uint32_t w[2][4] = {};
     for (int j = 0; j < 8; ++j) {
@@ -89,7 +89,7 @@ struct DscnnScales {
 //   then conv1, block (ct, kb): half-wave l >> 5 takes kernel rows 5(l>>5) .. + 4, i.e. 50 consecutive taps w[0..49], in two K orders:
 //     bf16 image: w[8kb + j], zeros from 50 on -- both halves walk the same offsets 10*(kh%5) + kw, so their LDS addresses differ by
 //                 a constant
-//     f16 image (the pre-split windows, kws_dscnn.hip, conv1_unit_pairwin): kb < 5: row kb, taps kw = j; kb = 5: taps
+//     f16 image (the pre-split windows, kws_dscnn_stages.h, conv1_unit_pairwin): kb < 5: row kb, taps kw = j; kb = 5: taps
 //                 kw = 8 + (j & 1) of row j >> 1; kb = 6: taps kw = 8 + j (j < 2) of row 4, then zeros
 __host__ __device__ inline void ds_pack_fragment(const DscnnLayout& L, const float* blob, size_t i, const DscnnScales& sw, uint32_t* img) {
     const size_t l = i & 63, row = l & 31, half = l >> 5;

@@ -1,4 +1,4 @@
-// Device helpers shared by the matrix-core kernels (kws_dscnn.hip, kws_cnntrad.hip): the exact three-way bf16
+// Device helpers shared by the matrix-core kernels (kws_dscnn.hip through kws_dscnn_stages.h, kws_cnntrad.hip): the exact three-way bf16
 // split of f32 operands, the 32x32x16 bf16 MFMA wrapper, accumulator row mapping, wavefront lane shifts.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -64,7 +64,7 @@ __device__ __forceinline__ floatx16 mfma_bf16(const uintx4& a, const uintx4& b, 
 // f16 SUBNORMAL inputs (tools/mfma_f16_denorm_probe.hip), so hi*hi + hi*lo + lo*hi reproduces the f32 product to 2^-22
 // relative or 2^-25 absolute (in scaled units), whichever is larger: three MFMAs per k-block instead of the six of the
 // three-way bf16 split.  Two flavours of the residual piece: PLAIN lo = f16(x e - hi) goes to the same accumulator as
-// hi*hi (kws_dscnn.hip); SCALED lo' = f16((x e - hi) 2^11) goes to a second accumulator (kws_cnntrad.hip).
+// hi*hi (kws_dscnn_stages.h); SCALED lo' = f16((x e - hi) 2^11) goes to a second accumulator (kws_cnntrad.hip).
 typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
 typedef _Float16 halfx2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ floatx16 mfma_f16(const uintx4& a, const uintx4& b, floatx16 c) {

@@ -452,6 +452,25 @@ def test_argmax_ties_first_maximum_wins(native, ctx, dev, e2e_golden, use_mfma):
             assert (lb == lo).sum() >= 3 and not (lb == hi).any()
 
 
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("mode", [2, 3, 6])
+def test_timing_ablation_variants_run_every_phase(ctx, dev, e2e_golden, mode, B):
+    """kws_forward_stamps_f32 modes 2, 3 and 6 (matrix core only, stencil only, bf16 triple without the stencil) are timing
+    ablations: their logits are wrong by construction, so no oracle applies.  What can be held is what the stamps of the product
+    variants are held to (test_dscnn_persistent_gpu.py): the launch succeeds, every clip's thirteen phase stamps are written and
+    in order, and nothing but [B, 12] logits is written."""
+    ctx.load_dscnn(e2e_golden["he.blob"], 12)
+    x = torch.from_numpy(np.ascontiguousarray(e2e_golden["x_rand"][:B])).to(dev)
+    logits = torch.full((B + 1, 12), float("nan"), device=dev)
+    stamps = torch.zeros((B, 16), dtype=torch.int64, device=dev)
+    ctx.forward_stamps_f32(x, logits[:B], stamps, mode)
+    ctx.sync()
+    st = stamps.cpu().numpy()
+    assert (st[:, :13] > 0).all(), "a phase stamp was not written"
+    assert (np.diff(st[:, :13], axis=1) >= 0).all(), "phase stamps out of order"
+    assert torch.isnan(logits[B]).all(), "logits were written beyond [B, 12]"
+
+
 def test_standalone_block_forward(dev, dsblock_golden):
     """DepthwiseSeparableConvBlock.forward on its own (kws_dsblock_forward_f32) against the imported reference module's
     outputs: four shapes incl. 5x5 / stride 2 / padding 2, padding 0, and channel counts off the kernel's tile sizes;
@@ -1672,6 +1691,46 @@ def test_streaming_time_tile_clusters_agree(native, dev, e2e_golden, use_graph):
     a, b = runs[4]
     assert all(np.array_equal(x[1], y[1]) for x, y in zip(a[0], b[0]))                      # deterministic
     assert all(np.array_equal(x[1], y[1]) for x, y in zip(runs[0][0][0], a[0]))             # automatic == 4 tiles at 64 streams
+
+
+@pytest.mark.parametrize("tiles", [1, 2])
+@pytest.mark.parametrize("S", [1, 3])
+def test_streaming_push_on_the_bf16_triple(native, dev, e2e_golden, S, tiles):
+    """The one-launch push under KWS_PW_SPLIT_BF16 (every other streaming test runs the default f16 pairs), as one workgroup
+    per stream and as two time tiles per stream, at 1 and 3 streams: feature ring and logits within 1e-4 of the oracle and its
+    labels, at a partial window, a full one and across the ring wrap (hop > 99); with a quiet stream."""
+    from kws.inference import StreamingSpotter
+
+    hops = 104
+    model = he_model(e2e_golden)
+    state = {k: v.clone() for k, v in model.state_dict().items()}
+    pcm = np.random.default_rng(71 + S).integers(-20000, 20000, size=(S, hops * 160), dtype=np.int16)
+    pcm[S - 1] //= 40
+    sp = StreamingSpotter(S, model)
+    try:
+        sp._ctx.set_pointwise_math(native.PW_SPLIT_BF16)
+        sp._ctx.stream_cluster(tiles)
+        for t in range(hops):
+            labels, logits = sp.push(pcm[:, t * 160:(t + 1) * 160])
+            if t not in (2, 40, 98, 99, 100, hops - 1):
+                continue
+            feats, pushed = sp.features()
+            assert pushed == t + 1
+            newest = t - 2
+            want = np.zeros((S, 99, 10), np.float32)
+            for s_ in range(S):
+                allf = o_mfcc.mfcc(o_mfcc.pcm16_to_float(pcm[s_, : (t + 1) * 160]), o_mfcc.FrontendSpec(n_samples=(t + 1) * 160))
+                for i in range(99):
+                    f = newest - 98 + i
+                    if 0 <= f <= newest:
+                        want[s_, i] = allf[f]
+            assert np.abs(feats - want).max() <= TOL, f"hop {t}"
+            ref = o_dscnn.forward(state, torch.from_numpy(want)[:, None])
+            err = float(np.abs(logits - ref.numpy()).max())
+            assert err <= TOL, f"hop {t}: {err:.3e}"
+            assert_labels_match(labels, ref, err)
+    finally:
+        sp.close()
 
 
 def test_streaming_host_results_are_the_device_results(native, dev, e2e_golden):

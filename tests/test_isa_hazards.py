@@ -27,7 +27,9 @@ def test_calibration_matches_the_documented_wait_states():
     assert 17 <= waits["v_mfma_f32_32x32x2_f32"] <= 20, waits
 
 
-@pytest.mark.parametrize("unit", ["kws_dscnn.hip", "kws_cnntrad.hip", "kws_mfcc.hip", "kws_mfcc_f64.hip"])
+ASM_UNITS = ["kws_dscnn.hip", "kws_cnntrad.hip", "kws_mfcc.hip", "kws_mfcc_f64.hip"]  # the units with hand-written asm blocks
+# kws_decide.hip and kws_dsblock.hip hold the plain kernels that once shared kws_dscnn.hip's unit: they stay in the lint's view
+@pytest.mark.parametrize("unit", ASM_UNITS + ["kws_decide.hip", "kws_dsblock.hip"])
 def test_no_unprotected_hazard_in_the_product_kernels(unit):
     findings, waits, isa = lint.lint_file(os.path.join(CSRC, unit))
     flat = [(fn[:60], line, rule, msg) for fn, fs in findings.items() for line, rule, msg in fs]
@@ -36,7 +38,8 @@ def test_no_unprotected_hazard_in_the_product_kernels(unit):
     body = open(isa).read()
     if unit in ("kws_dscnn.hip", "kws_cnntrad.hip"):
         assert body.count("v_mfma_f32_32x32x16_bf16") > 100
-    assert "_dpp" in body or "row_shr" in body
+    if unit in ASM_UNITS:
+        assert "_dpp" in body or "row_shr" in body
 
 
 def test_the_lint_fails_when_the_epilogue_wait_is_removed():

@@ -5,8 +5,9 @@ arithmetic as the device code and checked against the oracle:
   * the 8 x 8 x 8 wavefront FFT (register radix-8 passes + two LDS exchanges) and the split of two
     packed real frames                                    (csrc/kws_mfcc.hip: fft512, split_power)
   * the sparse mel decomposition, through the C ABI's host helpers
-  * the ring-slot / zero-slot depthwise addressing        (csrc/kws_dscnn.hip: block_phase)
-  * the im2col addressing of conv1 on the zero-padded MFCC map (conv1_phase)
+  * the ring-slot / zero-slot depthwise addressing        (csrc/kws_dscnn_stages.h: block_phase, over the planes
+    of csrc/kws_dscnn_geom.h: Blk<N>, pidx)
+  * the im2col addressing of conv1 on the zero-padded MFCC map (csrc/kws_dscnn_stages.h: conv1_phase)
 """
 import numpy as np
 import pytest
