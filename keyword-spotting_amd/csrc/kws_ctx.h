@@ -1,6 +1,6 @@
 // The context behind the C ABI (include/kws_hip.h), the error plumbing and the device-memory helpers shared by the translation
-// units that implement it (kws_api.hip, kws_weights.hip, kws_ingest.hip, kws_scan.hip, kws_decide.hip, kws_*_bwd.hip), and the
-// event bracket of a timed launch.
+// units that implement it (kws_api.hip, kws_frontend.hip, kws_weights.hip, kws_ingest.hip, kws_scan.hip, kws_decide.hip,
+// kws_*_bwd.hip), and the event bracket of a timed launch.
 #pragma once
 #include <new>
 
@@ -114,10 +114,14 @@ struct kws_ctx {
     long launches[KWS_K_COUNT] = {};
 };
 
-// Front-end pieces kws_api.hip shares with kws_scan.hip
+// Front-end pieces kws_frontend.hip shares with kws_api.hip and kws_scan.hip
 int frames_for(int n_samples, int frame_len, int frame_step);  // 1 + ceil((n - L) / step), 1 for n <= L (sigproc.py:31-35)
 void set_clip_length(FrontendParams& p, int n_samples);
-int mfcc_i16_clips(kws_ctx* c, const FrontendParams& geometry, const int16_t* d_wav, int B, float* d_out, int refine_clips);
+int ensure_refine(kws_ctx* c, int B, int num_frames);  // the refinement worklist holds B clips of num_frames frames
+void stream_free(kws_ctx* c);                          // kws_api.hip: rings, hop counter, captured graph, smoothing and endpointer history
+// The MFCC launches of B clips read from src (const int16_t*, const float* or kws::AugmentArgs; instantiated in kws_frontend.hip)
+template <typename Src>
+int run_frontend(kws_ctx* c, const FrontendParams& geometry, Src src, int B, float* d_out, int refine_clips);
 
 inline thread_local std::string g_create_err;
 

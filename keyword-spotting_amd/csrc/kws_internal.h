@@ -78,25 +78,33 @@ struct FrontendTables {
     const double* dct64;       // [numcep][nfilt]  DCT-II ortho x lifter
 };
 
-hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTables& t,
-                       const int16_t* d_wav, int B, float* d_out);
-hipError_t launch_mfcc_f32(hipStream_t s, const FrontendParams& p, const FrontendTables& t,
-                           const float* d_wav, int B, float* d_out);
-size_t mfcc_lds_bytes(const FrontendParams& p);
-// The float32 kernels with flagging: frames over p.refine_span are appended to rl (rl.ctr == nullptr: no flagging).
-hipError_t launch_mfcc_flag(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_wav, int B, float* d_out,
-                            const RefineList& rl);
-hipError_t launch_mfcc_f32_flag(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, int B,
-                                float* d_out, const RefineList& rl);
-// Float64 recomputation of the listed frames, in place in d_out (same d_wav / d_out as the float32 launch before it).
+// Opt a kernel in to more than the default 64 KiB of dynamic LDS.
+template <typename K>
+inline hipError_t raise_lds_limit(K kernel, size_t lds) {
+    if (lds <= 64 * 1024) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
+struct AugmentArgs;
+// The float32 MFCC of B clips read from int16 PCM, float32 samples, or the augmented view of a resident split (gather +
+// augment + MFCC in one launch, wavefront-resident geometry only).  Frames over p.refine_span are appended to rl; an empty rl
+// (ctr == nullptr) means no flagging.
+hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_wav, int B, float* d_out,
+                       const RefineList& rl);
+hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, int B, float* d_out,
+                       const RefineList& rl);
+hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const AugmentArgs& a, int B, float* d_out,
+                       const RefineList& rl);
+// Float64 recomputation of the listed frames, in place in d_out (same source / d_out as the float32 launch before it).
 hipError_t launch_mfcc_refine(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_wav, float* d_out,
                               const RefineList& rl, int B);
-hipError_t launch_mfcc_refine_f32in(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, float* d_out,
-                                    const RefineList& rl, int B);
+hipError_t launch_mfcc_refine(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, float* d_out,
+                              const RefineList& rl, int B);
+hipError_t launch_mfcc_refine(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const AugmentArgs& a, float* d_out,
+                              const RefineList& rl, int B);
 // The float64 front end: any nfft (power of two up to 4096: FFT; otherwise up to 2048: direct DFT), any frame length.
 hipError_t launch_mfcc_f64(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_wav, int B, float* d_out);
-hipError_t launch_mfcc_f64_f32in(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, int B,
-                                 float* d_out);
+hipError_t launch_mfcc_f64(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, int B, float* d_out);
 hipError_t launch_spec_f64(hipStream_t s, const double* d_tw64, const float* d_frames, int num_frames, int frame_len, int nfft,
                            int log2n, int power, float* d_spec);
 // Streaming: one hop of frame_step new samples per stream -> one new MFCC frame per stream in the feature ring.
@@ -137,13 +145,8 @@ struct DrawArgs {
     uint8_t* silence;         // [B]
 };
 hipError_t launch_augment_draw(hipStream_t s, const DrawArgs& d, int B);
-// true: launch_mfcc_flag picks the wavefront-resident kernel for this geometry (the fused kernel is a variant of it)
+// true: launch_mfcc picks the wavefront-resident kernel for int16 PCM at this geometry (the fused kernel is a variant of it)
 bool mfcc_wave_resident_ok(const FrontendParams& p);
-// gather + augment + float32 MFCC in one launch (wavefront-resident geometry only), and the refinement of its flagged frames
-hipError_t launch_mfcc_augment_flag(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const AugmentArgs& a, int B,
-                                    float* d_out, const RefineList& rl);
-hipError_t launch_mfcc_refine_augment(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const AugmentArgs& a,
-                                      float* d_out, const RefineList& rl, int B);
 hipError_t launch_preemphasis(hipStream_t s, const float* d_in, int n, float coeff, float* d_out);
 hipError_t launch_framesig(hipStream_t s, const float* d_in, int n, int frame_len, int frame_step,
                            int num_frames, const float* d_window, float* d_frames);

@@ -321,10 +321,6 @@ __device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t,
         v1 = n1 + 8 <= p.n_samples ? *reinterpret_cast<const uint4*>(x + n1) : make_uint4(0, 0, 0, 0);
         before = s0 > 0 ? x[s0 - 1] : (int16_t)0;
     };
-    (void)fetch;
-#ifdef KWS_X_MFCC_PREFETCH
-    if (!AUG && active) fetch(c);
-#endif
     __syncthreads();  // the only workgroup barrier: the shared tables are in place
     if (!active) return;
 
@@ -352,9 +348,7 @@ __device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t,
             rl.list[at] = (int)((((unsigned)(rl.clip0 + clip) * (unsigned)((p.num_frames + 1) / 2) + (unsigned)(pair0 + lane)) << 2) | fk); \
     }
     for (; c < c_end; ++c) {
-#ifndef KWS_X_MFCC_PREFETCH
         if constexpr (!AUG) fetch(c);
-#endif
         // ---- registers -> float32, pre-emphasised, into this wavefront's span buffer -----------------------
         if constexpr (AUG) {
             const int s0 = c * chunk_step;
@@ -414,9 +408,6 @@ __device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t,
             convert(v1, prev1, s0 + 512 + 8 * lane, ybuf + 512 + 8 * lane);
         }
         wave_lds_order();
-#ifdef KWS_X_MFCC_PREFETCH  // (experiment, see the header comment: the prefetched vectors spill under the 128-register cap)
-        if (!AUG && c + 1 < c_end) fetch(c + 1);
-#endif
 #pragma unroll 1
         for (int pr = 0; pr < WR_PAIRS; ++pr) {
             const int fa = WR_FRAMES * c + 2 * pr;
@@ -475,25 +466,7 @@ __global__ __launch_bounds__(MFCC_THREADS) __attribute__((amdgpu_waves_per_eu(KW
 }
 
 // ------------------------------------------------------------------------------------------------
-// sigproc operators (kws/libs/speech_features/sigproc.py), float32 device versions.
-__global__ void kws_preemphasis_f32_kernel(const float* __restrict__ in, int n, float coeff, float* __restrict__ out) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-        out[i] = (i > 0) ? __fsub_rn(in[i], __fmul_rn(coeff, in[i - 1])) : in[i];
-}
-
-__global__ void kws_framesig_f32_kernel(const float* __restrict__ in, int n, int frame_len, int frame_step,
-                                        int num_frames, const float* __restrict__ window,
-                                        float* __restrict__ frames) {
-    const long total = (long)num_frames * frame_len;
-    for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-        const int f = (int)(idx / frame_len), i = (int)(idx % frame_len);
-        const long s = (long)f * frame_step + i;
-        float v = (s < n) ? in[s] : 0.f;
-        if (window) v *= window[i];
-        frames[idx] = v;
-    }
-}
-
+// sigproc operator (kws/libs/speech_features/sigproc.py), float32 device version; the others are in kws_sigproc.hip.
 // magspec / powspec with NFFT = 512: one wavefront per pair of frames.
 __global__ __launch_bounds__(64) void kws_spec512_f32_kernel(FrontendTables t, const float* __restrict__ frames,
                                                              int num_frames, int frame_len, int power,
@@ -560,86 +533,10 @@ __global__ __launch_bounds__(64) void kws_stream_frame_kernel(FrontendParams p, 
     }
 }
 
-// Augmentation of the reference's training transform (kws/libs/audio_processor.py:151-159, 172-233) for a whole
-// batch: out[b][i] = (silence_b ? 0 : x_b[i - shift_b] / 32768, zero outside the clip) + vol_b * bg[off_b + i],
-// float32 with the same two roundings NumPy makes.
-__global__ void kws_augment_i16_kernel(const int16_t* __restrict__ wav, int B, int n, const int32_t* __restrict__ shift,
-                                       const float* __restrict__ bg, int bg_len, const int32_t* __restrict__ bg_off,
-                                       const float* __restrict__ bg_vol, const uint8_t* __restrict__ silence,
-                                       float* __restrict__ out) {
-    const int b = blockIdx.y;
-    const int sh = shift ? shift[b] : 0;
-    const bool sil = silence && silence[b];
-    const float vol = (bg && bg_vol) ? bg_vol[b] : 0.f;
-    const int off = (bg && bg_off) ? bg_off[b] : 0;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const int j = i - sh;
-        float a = (!sil && j >= 0 && j < n) ? to_unit(wav[(size_t)b * n + j]) : 0.f;
-        if (bg) {
-            const int k = off + i;
-            const float g = (k >= 0 && k < bg_len) ? bg[k] : 0.f;
-            a = __fadd_rn(a, __fmul_rn(g, vol));
-        }
-        out[(size_t)b * n + i] = a;
-    }
-}
-
-// The four random draws of the training transform (kws/libs/audio_processor.py:172-233) for a batch of dataset indices, made
-// on the device.  Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11), key = the 64-bit seed,
-// counter = (dataset index, epoch, 0, 0): one call yields the four words of a clip, so a clip's draws are a pure function of
-// (seed, epoch, dataset index) -- whatever the batch size, the other clips of the batch or the order inside it.
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0, c[1] = lo1, c[2] = n2, c[3] = lo0;
-        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-    }
-}
-// word -> integer in [0, m): (u * m) >> 32; word -> float in [0, 1): (u >> 8) * 2^-24, exact in float32
-__device__ __forceinline__ int draw_below(uint32_t u, int m) { return (int)(((unsigned long long)u * (unsigned)m) >> 32); }
-__device__ __forceinline__ float draw_unit(uint32_t u) { return (float)(u >> 8) * (1.0f / 16777216.0f); }
-
-__global__ void kws_augment_draw_kernel(DrawArgs d, int B) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const int idx = d.index[b];
-    uint32_t w[4] = {(uint32_t)idx, d.epoch, 0u, 0u};
-    philox4x32_10(w, (uint32_t)d.seed, (uint32_t)(d.seed >> 32));
-    const bool in_split = (unsigned)idx < (unsigned)d.n_rows;  // a label outside the split is never read
-    const bool sil = d.label && in_split && d.label[idx] == KWS_SILENCE_INDEX;
-    // time shift: uniform on the integers [-S, S) (np.random.randint(-S, S), :174)
-    d.shift[b] = d.time_shift > 0 ? draw_below(w[0], 2 * d.time_shift) - d.time_shift : 0;
-    int off = 0;
-    float vol = 0.f;
-    if (d.n_files > 0 && (d.use_background || sil)) {  // (:158: without use_background_noise only silence clips get noise)
-        const int k = draw_below(w[1], d.n_files);       // random.choice(background_data), :205
-        const int room = d.bg_len[k] - d.n_samples;      // np.random.randint(0, len - n), :214 (the pool's files are tiled beyond n)
-        off = d.bg_start[k] + (room > 0 ? draw_below(w[2], room) : 0);
-        // the reference draws a Bernoulli(background_frequency) variable and then the volume (:218-223); the one word left serves
-        // both: u < frequency decides, and given that, u / frequency is again uniform on [0, 1)
-        const float u = draw_unit(w[3]);
-        if (sil)
-            vol = u;
-        else if (u < d.bg_frequency)
-            vol = __fmul_rn(__fdiv_rn(u, d.bg_frequency), d.bg_volume);
-    }
-    d.bg_off[b] = off;
-    d.bg_vol[b] = vol;
-    d.silence[b] = sil ? 1 : 0;
-}
-
 }  // namespace
 
-hipError_t launch_augment_draw(hipStream_t s, const DrawArgs& d, int B) {
-    hipLaunchKernelGGL(kws_augment_draw_kernel, dim3((B + 255) / 256), dim3(256), 0, s, d, B);
-    return hipGetLastError();
-}
-
 // ------------------------------------------------------------------------------------------------
-size_t mfcc_lds_bytes(const FrontendParams& p) {
+static size_t mfcc_lds_bytes(const FrontendParams& p) {
     const int nfp = (p.nfilt + 3) & ~3;
     return sizeof(float) * (size_t)(((p.numcep * nfp + 3) & ~3) + 2 * 64 + ((p.chunk_samples + 7) & ~7)) +
            (size_t)MFCC_WAVES * SCR_BYTES;
@@ -650,10 +547,8 @@ static hipError_t launch_mfcc_t(K kernel, hipStream_t s, const FrontendParams& p
                                 int B, float* d_out, RefineList rl) {
     dim3 grid((p.num_frames + MFCC_FRAMES_PER_WG - 1) / MFCC_FRAMES_PER_WG, B);
     const size_t lds = mfcc_lds_bytes(p);
-    if (lds > 64 * 1024) {  // geometries (or experiment shapes) beyond the default dynamic-LDS limit opt in per kernel
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    hipError_t e = raise_lds_limit(kernel, lds);  // geometries (or experiment shapes) beyond the default dynamic-LDS limit opt in per kernel
+    if (e != hipSuccess) return e;
     // grid.y is limited to 65535: split very large batches
     for (int b0 = 0; b0 < B; b0 += 65535) {
         const int nb = (B - b0 < 65535) ? (B - b0) : 65535;
@@ -665,10 +560,12 @@ static hipError_t launch_mfcc_t(K kernel, hipStream_t s, const FrontendParams& p
     return hipGetLastError();
 }
 
+// frame lengths of the TAIL6 kernels (see mfcc_body)
+static bool mfcc_tail6(const FrontendParams& p) { return p.frame_len > 384 && p.frame_len <= 448; }
+
 // the wavefront-resident kernel: 16-byte PCM vectors (aligned clips and chunk starts), a chunk's span within two vectors per lane
 bool mfcc_wave_resident_ok(const FrontendParams& p) {
-    const bool tail6 = p.frame_len > 384 && p.frame_len <= 448;
-    return tail6 && p.vec_ok && (WR_FRAMES * p.frame_step) % 8 == 0 && (WR_FRAMES - 1) * p.frame_step + 448 <= WR_SPAN;
+    return mfcc_tail6(p) && p.vec_ok && (WR_FRAMES * p.frame_step) % 8 == 0 && (WR_FRAMES - 1) * p.frame_step + 448 <= WR_SPAN;
 }
 
 // Chunks per wavefront of the wavefront-resident kernels for a launch of nb clips.
@@ -690,65 +587,50 @@ static int mfcc_wr_chunks_per_wave(int nb, int n_chunks) {
     return cpw;
 }
 
-hipError_t launch_mfcc_flag(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_wav, int B,
-                            float* d_out, const RefineList& rl) {
-    const bool tail6 = p.frame_len > 384 && p.frame_len <= 448;
-#ifndef KWS_X_MFCC_TILE_KERNEL  // (A/B switch: the round-2 tile kernel for every geometry)
-    if (mfcc_wave_resident_ok(p)) {
-        const size_t lds = mfcc_wr_lds_bytes(p);
-        const int n_chunks = (p.num_frames + WR_FRAMES - 1) / WR_FRAMES;
-        for (int b0 = 0; b0 < B; b0 += (1 << 20)) {  // (grid.x limit: 2^31 workgroups; a million clips per launch keeps indices in 32 bits)
-            const int nb = B - b0 < (1 << 20) ? B - b0 : (1 << 20);
-            const int cpw = mfcc_wr_chunks_per_wave(nb, n_chunks);
-            const int waves_per_clip = (n_chunks + cpw - 1) / cpw;
-            const long waves = (long)nb * waves_per_clip;
-            RefineList r = rl;
-            r.clip0 = b0;
-            hipLaunchKernelGGL(kws_mfcc_i16_kernel, dim3((unsigned)((waves + MFCC_WAVES - 1) / MFCC_WAVES)), dim3(MFCC_THREADS), lds, s, p, t,
-                               d_wav + (size_t)b0 * p.n_samples, d_out + (size_t)b0 * p.num_frames * p.numcep, r, nb, cpw);
-        }
-        return hipGetLastError();
-    }
-#endif
-    return launch_mfcc_t(tail6 ? kws_mfcc_i16_tile_kernel : kws_mfcc_i16_any_kernel, s, p, t, d_wav, B, d_out, rl);
+// A launch's source from its first clip b0 on: the PCM pointer moves by whole clips, the fused loader's per-clip arrays by b0.
+static const int16_t* clips_from(const int16_t* d_wav, int b0, const FrontendParams& p) { return d_wav + (size_t)b0 * p.n_samples; }
+static AugmentArgs clips_from(AugmentArgs a, int b0, const FrontendParams&) {
+    a.index += b0;
+    if (a.shift) a.shift += b0;
+    if (a.bg_off) a.bg_off += b0;
+    if (a.bg_vol) a.bg_vol += b0;
+    if (a.silence) a.silence += b0;
+    return a;
 }
 
-// The fused loader kernel: the same launch shape as kws_mfcc_i16_kernel; the per-clip arrays advance with the launch's first clip.
-hipError_t launch_mfcc_augment_flag(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const AugmentArgs& a, int B,
-                                    float* d_out, const RefineList& rl) {
-    if (!mfcc_wave_resident_ok(p)) return hipErrorInvalidValue;  // refused by kws_mfcc_augment_i16 before it gets here
+// The launches of a wavefront-resident kernel (kws_mfcc_i16_kernel, or the fused loader kernel: the same launch shape).
+template <typename K, typename Src>
+static hipError_t launch_mfcc_wr(K kernel, hipStream_t s, const FrontendParams& p, const FrontendTables& t, const Src& src, int B,
+                                 float* d_out, RefineList rl) {
     const size_t lds = mfcc_wr_lds_bytes(p);
     const int n_chunks = (p.num_frames + WR_FRAMES - 1) / WR_FRAMES;
-    for (int b0 = 0; b0 < B; b0 += (1 << 20)) {
+    for (int b0 = 0; b0 < B; b0 += (1 << 20)) {  // (grid.x limit: 2^31 workgroups; a million clips per launch keeps indices in 32 bits)
         const int nb = B - b0 < (1 << 20) ? B - b0 : (1 << 20);
         const int cpw = mfcc_wr_chunks_per_wave(nb, n_chunks);
         const int waves_per_clip = (n_chunks + cpw - 1) / cpw;
         const long waves = (long)nb * waves_per_clip;
-        RefineList r = rl;
-        r.clip0 = b0;
-        AugmentArgs ab = a;
-        ab.index += b0;
-        if (ab.shift) ab.shift += b0;
-        if (ab.bg_off) ab.bg_off += b0;
-        if (ab.bg_vol) ab.bg_vol += b0;
-        if (ab.silence) ab.silence += b0;
-        hipLaunchKernelGGL(kws_mfcc_augment_i16_kernel, dim3((unsigned)((waves + MFCC_WAVES - 1) / MFCC_WAVES)), dim3(MFCC_THREADS), lds, s, p,
-                           t, ab, d_out + (size_t)b0 * p.num_frames * p.numcep, r, nb, cpw);
+        rl.clip0 = b0;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((waves + MFCC_WAVES - 1) / MFCC_WAVES)), dim3(MFCC_THREADS), lds, s, p, t,
+                           clips_from(src, b0, p), d_out + (size_t)b0 * p.num_frames * p.numcep, rl, nb, cpw);
     }
     return hipGetLastError();
 }
-hipError_t launch_mfcc_f32_flag(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, int B,
-                                float* d_out, const RefineList& rl) {
-    const bool tail6 = p.frame_len > 384 && p.frame_len <= 448;
-    return launch_mfcc_t(tail6 ? kws_mfcc_f32_kernel : kws_mfcc_f32_any_kernel, s, p, t, d_wav, B, d_out, rl);
+
+hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_wav, int B, float* d_out,
+                       const RefineList& rl) {
+#ifndef KWS_X_MFCC_TILE_KERNEL  // (A/B switch: the round-2 tile kernel for every geometry)
+    if (mfcc_wave_resident_ok(p)) return launch_mfcc_wr(kws_mfcc_i16_kernel, s, p, t, d_wav, B, d_out, rl);
+#endif
+    return launch_mfcc_t(mfcc_tail6(p) ? kws_mfcc_i16_tile_kernel : kws_mfcc_i16_any_kernel, s, p, t, d_wav, B, d_out, rl);
 }
-hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_wav, int B,
-                       float* d_out) {
-    return launch_mfcc_flag(s, p, t, d_wav, B, d_out, RefineList{});
+hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, int B, float* d_out,
+                       const RefineList& rl) {
+    return launch_mfcc_t(mfcc_tail6(p) ? kws_mfcc_f32_kernel : kws_mfcc_f32_any_kernel, s, p, t, d_wav, B, d_out, rl);
 }
-hipError_t launch_mfcc_f32(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, int B,
-                           float* d_out) {
-    return launch_mfcc_f32_flag(s, p, t, d_wav, B, d_out, RefineList{});
+hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const AugmentArgs& a, int B, float* d_out,
+                       const RefineList& rl) {
+    if (!mfcc_wave_resident_ok(p)) return hipErrorInvalidValue;  // refused by kws_mfcc_augment_i16 before it gets here
+    return launch_mfcc_wr(kws_mfcc_augment_i16_kernel, s, p, t, a, B, d_out, rl);
 }
 
 hipError_t launch_stream_frame(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_hop,
@@ -756,36 +638,6 @@ hipError_t launch_stream_frame(hipStream_t s, const FrontendParams& p, const Fro
     const size_t lds = stream_frame_lds_bytes(p);
     hipLaunchKernelGGL(kws_stream_frame_kernel, dim3((n_streams + 1) / 2), dim3(64), lds, s, p, t, d_hop, n_streams,
                        d_pcm_ring, ring_len, d_feat_ring, d_hops, d_refine_ctr);
-    return hipGetLastError();
-}
-
-hipError_t launch_augment(hipStream_t s, const int16_t* d_wav, int B, int n, const int32_t* d_shift, const float* d_bg,
-                          int bg_len, const int32_t* d_bg_off, const float* d_bg_vol, const uint8_t* d_silence,
-                          float* d_out) {
-    int bx = (n + 255) / 256;
-    if (bx > 64) bx = 64;
-    for (int b0 = 0; b0 < B; b0 += 65535) {
-        const int nb = (B - b0 < 65535) ? (B - b0) : 65535;
-        hipLaunchKernelGGL(kws_augment_i16_kernel, dim3(bx, nb), dim3(256), 0, s, d_wav + (size_t)b0 * n, nb, n,
-                           d_shift ? d_shift + b0 : nullptr, d_bg, bg_len, d_bg_off ? d_bg_off + b0 : nullptr,
-                           d_bg_vol ? d_bg_vol + b0 : nullptr, d_silence ? d_silence + b0 : nullptr, d_out + (size_t)b0 * n);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_preemphasis(hipStream_t s, const float* d_in, int n, float coeff, float* d_out) {
-    const int blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(kws_preemphasis_f32_kernel, dim3(blocks < 2048 ? blocks : 2048), dim3(256), 0, s, d_in, n, coeff, d_out);
-    return hipGetLastError();
-}
-
-hipError_t launch_framesig(hipStream_t s, const float* d_in, int n, int frame_len, int frame_step, int num_frames,
-                           const float* d_window, float* d_frames) {
-    const long total = (long)num_frames * frame_len;
-    long blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(kws_framesig_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, s, d_in, n, frame_len, frame_step,
-                       num_frames, d_window, d_frames);
     return hipGetLastError();
 }
 

@@ -222,56 +222,6 @@ __global__ __launch_bounds__(REFINE_WAVES * 64) void kws_mfcc_refine_augment_ker
     mfcc_refine_body(p, t, out, rl, [&](int clip) { return aug_clip(aug, clip, p.n_samples); });
 }
 
-// magspec / powspec for any NFFT (kws/libs/speech_features/sigproc.py:55-90): frames float32 [num_frames][frame_len]
-// (zero-padded to nfft, or truncated), one wavefront per pair of frames, float64 inside, float32 out.
-template <bool POW2>
-__global__ __launch_bounds__(64) void kws_spec_f64_kernel(const float* __restrict__ frames, int num_frames, int frame_len, int nfft,
-                                                         int log2n, int power, const d2* __restrict__ tw, float* __restrict__ spec) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem64[];
-    const int nb = nfft / 2 + 1;
-    d2* X = reinterpret_cast<d2*>(smem64);
-    d2* P = X + nfft;
-    d2* tw_lds = P + nb;
-    const int lane = threadIdx.x;
-    const int fa = 2 * blockIdx.x;
-    const bool has_b = fa + 1 < num_frames;
-    const int n_used = frame_len < nfft ? frame_len : nfft;
-    bool nza = false, nzb = false;
-    for (int n = lane; n < nfft; n += 64) {
-        double a = 0.0, b = 0.0;
-        if (n < n_used) {
-            a = (double)frames[(size_t)fa * frame_len + n];
-            if (has_b) b = (double)frames[(size_t)(fa + 1) * frame_len + n];
-        }
-        nza |= a != 0.0;
-        nzb |= b != 0.0;
-        X[n] = d2{a, b};
-    }
-    nza = __any(nza);
-    nzb = __any(nzb);
-    for (int i = lane; i < (POW2 ? nfft / 2 : nfft); i += 64) tw_lds[i] = tw[i];
-    wave_order();
-    spectrum_pair<POW2, 0>(X, P, tw_lds, nfft, log2n, n_used, power ? 1.0 / (double)nfft : 1.0, lane);
-    for (int k = lane; k < nb; k += 64) {
-        d2 pw = P[k];
-        if (!nza) pw.x = 0.0;  // an all-zero frame has an exactly zero spectrum, whatever shares its transform
-        if (!nzb) pw.y = 0.0;
-        spec[(size_t)fa * nb + k] = (float)(power ? pw.x : sqrt(pw.x));
-        if (has_b) spec[(size_t)(fa + 1) * nb + k] = (float)(power ? pw.y : sqrt(pw.y));
-    }
-}
-
-size_t spec_lds_bytes(int nfft, bool pow2) {
-    const size_t nb = nfft / 2 + 1;
-    return sizeof(d2) * ((size_t)nfft + nb + (pow2 ? (size_t)nfft / 2 : (size_t)nfft));
-}
-
-template <typename K>
-hipError_t raise_lds_limit(K kernel, size_t lds) {
-    if (lds <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
-
 template <typename T>
 hipError_t launch_mfcc_f64_t(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const T* d_wav, int B, float* d_out) {
     const bool pow2 = p.log2_nfft > 0;
@@ -321,33 +271,20 @@ hipError_t launch_mfcc_refine(hipStream_t s, const FrontendParams& p, const Fron
                               const RefineList& rl, int B) {
     return launch_mfcc_refine_t(kws_mfcc_refine_kernel<int16_t>, s, p, t, d_wav, d_out, rl, B);
 }
-hipError_t launch_mfcc_refine_f32in(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, float* d_out,
-                                    const RefineList& rl, int B) {
+hipError_t launch_mfcc_refine(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, float* d_out,
+                              const RefineList& rl, int B) {
     return launch_mfcc_refine_t(kws_mfcc_refine_kernel<float>, s, p, t, d_wav, d_out, rl, B);
 }
-hipError_t launch_mfcc_refine_augment(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const AugmentArgs& a,
-                                      float* d_out, const RefineList& rl, int B) {
+hipError_t launch_mfcc_refine(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const AugmentArgs& a, float* d_out,
+                              const RefineList& rl, int B) {
     return launch_mfcc_refine_t(kws_mfcc_refine_augment_kernel, s, p, t, a, d_out, rl, B);
 }
 
 hipError_t launch_mfcc_f64(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_wav, int B, float* d_out) {
     return launch_mfcc_f64_t(s, p, t, d_wav, B, d_out);
 }
-hipError_t launch_mfcc_f64_f32in(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, int B,
-                                 float* d_out) {
+hipError_t launch_mfcc_f64(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, int B, float* d_out) {
     return launch_mfcc_f64_t(s, p, t, d_wav, B, d_out);
-}
-
-hipError_t launch_spec_f64(hipStream_t s, const double* d_tw64, const float* d_frames, int num_frames, int frame_len, int nfft,
-                           int log2n, int power, float* d_spec) {
-    const bool pow2 = log2n > 0;
-    const size_t lds = spec_lds_bytes(nfft, pow2);
-    auto kernel = pow2 ? kws_spec_f64_kernel<true> : kws_spec_f64_kernel<false>;
-    hipError_t e = raise_lds_limit(kernel, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3((num_frames + 1) / 2), dim3(64), lds, s, d_frames, num_frames, frame_len, nfft, log2n, power,
-                       reinterpret_cast<const d2*>(d_tw64), d_spec);
-    return hipGetLastError();
 }
 
 }  // namespace kws

@@ -125,7 +125,7 @@ int kws_scan_i16(kws_ctx* c, const int16_t* d_pcm, int R, int n_total, int hop_f
         feat = c->d_scan_ws;
     }
     // the refinement's grid: the batch in one-second clips (R * F <= 2^28 was checked above)
-    int rc = mfcc_i16_clips(c, p, d_pcm, R, feat, (int)((unsigned long long)R * F / T + 1));
+    int rc = run_frontend(c, p, d_pcm, R, feat, (int)((unsigned long long)R * F / T + 1));
     if (rc) return rc;
     const ScanWindows sw = {(unsigned)W, W == 1 ? 0xffffffffu : (unsigned)((1ull << 32) / (unsigned)W), (unsigned)F * (unsigned)IN_F,
                             (unsigned)hop_frames * (unsigned)IN_F};

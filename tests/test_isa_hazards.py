@@ -28,8 +28,9 @@ def test_calibration_matches_the_documented_wait_states():
 
 
 ASM_UNITS = ["kws_dscnn.hip", "kws_cnntrad.hip", "kws_mfcc.hip", "kws_mfcc_f64.hip"]  # the units with hand-written asm blocks
-# kws_decide.hip and kws_dsblock.hip hold the plain kernels that once shared kws_dscnn.hip's unit: they stay in the lint's view
-@pytest.mark.parametrize("unit", ASM_UNITS + ["kws_decide.hip", "kws_dsblock.hip"])
+# kws_decide.hip and kws_dsblock.hip hold the plain kernels that once shared kws_dscnn.hip's unit, kws_augment.hip and
+# kws_sigproc.hip those that once shared kws_mfcc.hip's and kws_mfcc_f64.hip's: they stay in the lint's view
+@pytest.mark.parametrize("unit", ASM_UNITS + ["kws_decide.hip", "kws_dsblock.hip", "kws_augment.hip", "kws_sigproc.hip"])
 def test_no_unprotected_hazard_in_the_product_kernels(unit):
     findings, waits, isa = lint.lint_file(os.path.join(CSRC, unit))
     flat = [(fn[:60], line, rule, msg) for fn, fs in findings.items() for line, rule, msg in fs]

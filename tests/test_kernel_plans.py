@@ -3,7 +3,7 @@
 The kernels cannot run here (no GPU), so their *plans* are replayed in NumPy with the same index
 arithmetic as the device code and checked against the oracle:
   * the 8 x 8 x 8 wavefront FFT (register radix-8 passes + two LDS exchanges) and the split of two
-    packed real frames                                    (csrc/kws_mfcc.hip: fft512, split_power)
+    packed real frames                                    (csrc/kws_mfcc_dev.h: fft512, split_power)
   * the sparse mel decomposition, through the C ABI's host helpers
   * the ring-slot / zero-slot depthwise addressing        (csrc/kws_dscnn_stages.h: block_phase, over the planes
     of csrc/kws_dscnn_geom.h: Blk<N>, pidx)

@@ -12,7 +12,8 @@ FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -I$ROOT/include -Wall -Wno-unu
 # the translation units are the Makefile's SRCS: the list lives there alone
 for f in $(make -s -C "$SRC" print-srcs | sed 's/\.hip//g'); do
   # only the translation units a macro can touch are rebuilt per variant; the others are linked from the main build
-  if [ "$f" != kws_api ] && [ -f "$SRC/build/$f.o" ] && ! grep -q "KWS_MFCC_\|KWS_DSCNN_\|KWS_X_\|kws_mfcc_dev.h\|kws_dscnn_geom.h\|kws_dscnn_stages.h" "$SRC/$f.hip"; then cp "$SRC/build/$f.o" "$OBJ/$f.o"; continue; fi
+  # (kws_api and kws_frontend: host code that reads the macros' constants from kws_internal.h)
+  if [ "$f" != kws_api ] && [ "$f" != kws_frontend ] && [ -f "$SRC/build/$f.o" ] && ! grep -q "KWS_MFCC_\|KWS_DSCNN_\|KWS_X_\|kws_mfcc_dev.h\|kws_mfcc_f64_dev.h\|kws_dscnn_geom.h\|kws_dscnn_stages.h" "$SRC/$f.hip"; then cp "$SRC/build/$f.o" "$OBJ/$f.o"; continue; fi
   /opt/rocm/bin/hipcc $FLAGS -c "$SRC/$f.hip" -o "$OBJ/$f.o" &
 done
 wait

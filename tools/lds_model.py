@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """LDS-array cycle model for gfx950 wave64 LDS instructions (lane groups and bank rules as tabulated in
-MI355X_MICROARCH.md, section LDS) applied to the access patterns of kws_mfcc.hip.  Host-only diagnostics.
+MI355X_MICROARCH.md, section LDS) applied to the access patterns of kws_mfcc.hip's kernels (kws_mfcc_dev.h).  Host-only
+diagnostics.
 
     python tools/lds_model.py
 """
