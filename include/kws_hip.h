@@ -444,6 +444,46 @@ int kws_scan_detect_f32(kws_ctx* ctx, const float* d_logits, int R, int W, int C
                         float threshold, int refractory, float* d_smoothed, int32_t* d_event_window, int32_t* d_event_label,
                         float* d_event_score, int max_events, int32_t* d_event_count);
 
+/* ---- evaluation statistics on the device (build-defined: the reference computes them on the host, with a
+ * round trip per batch -- running_loss += loss.item(), torch.max(outputs, 1), (predicted == labels).sum().item() in
+ * train.py:51-54,79-98 and kws/libs/training.py:300-303,347-393 -- and test.py:27-58 derives the per-class report, the
+ * one-vs-rest ROC curves and the false-alarm / false-reject rates from posteriors copied to the host) ------------------------ */
+
+/* The context holds ONE evaluation state: integer accumulators in device memory, updated by any number of batches and read
+ * back once.  kws_eval_open allocates and zeroes it for num_classes C in [1, 64] and n_bins K, a power of two in [2, 1024] or 0
+ * for no histograms (anything else: KWS_EINVAL); a second open replaces the state; kws_destroy frees it.  kws_eval_reset zeroes
+ * it (asynchronous on the context stream); kws_eval_close frees it.  Before an open, reset / update / read return KWS_ESTATE. */
+int kws_eval_open(kws_ctx* ctx, int num_classes, int n_bins);
+int kws_eval_reset(kws_ctx* ctx);
+int kws_eval_close(kws_ctx* ctx);
+
+/* One batch into the statistics: d_logits float32 [B, C], d_truth int32 [B] (device pointers), any B >= 1; asynchronous on the
+ * context stream, two launches, not timed by kws_prof_* (as kws_scan_detect_f32).  Per row b:
+ *   - a truth outside [0, C) makes the row IGNORED: counted in counts[2], nothing else; the label is never used as an index;
+ *   - else a NaN or infinite logit makes the row NON-FINITE: counted in counts[3], nothing else;
+ *   - an ignored or non-finite row gets zeros in d_dlogits and d_loss_rows;
+ *   - every other row: p[c] = the value kws_softmax_f32 writes for the row, bit for bit (the same device function); row loss
+ *     l = logf(sum) + m - z[truth] in float32 with the maximum m and the sum of expf(z - m) of that softmax (the cross-entropy
+ *     of nn.CrossEntropyLoss, train.py:48); pred = first argmax of the logits (torch.max, training.py:371);
+ *     confusion[truth][pred] += 1; counts[1] += (pred == truth); counts[0] += 1; with K > 0, for every class c,
+ *     bin = min(K - 1, (int)(p[c] * K)) (the product is exact) and hist_pos[c][bin] += 1 when truth == c, else
+ *     hist_neg[c][bin] += 1 -- the counts behind roc_curve(y_test[:, c], y_score[:, c]) of test.py:38 at thresholds j / K;
+ *     d_loss_rows[b] = l and d_dlogits[b][c] = (p[c] - (c == truth)) * grad_scale where the pointers are not NULL.
+ *     grad_scale = 1 / B gives the gradient of nn.CrossEntropyLoss() at its default mean reduction: the d_dlogits that
+ *     kws_dscnn_backward_f32 / kws_cnn_trad_backward_f32 take.  grad_scale is only read when d_dlogits is given.
+ * All counters are integers (private 32-bit counters per workgroup in LDS where the 2 C K histogram counters fit, 64-bit atomics
+ * into the accumulators), so they do not depend on the order of execution.  loss_sum is a float64 sum of the float32 row
+ * losses in an order that depends only on B and on the sequence of calls (per-workgroup partials, added in index order; no
+ * float atomics): the same updates after a reset give a bit-identical loss_sum.
+ * NULL d_logits / d_truth or B <= 0: KWS_EINVAL. */
+int kws_eval_update_f32(kws_ctx* ctx, const float* d_logits, const int32_t* d_truth, int B, float grad_scale, float* d_dlogits,
+                        float* d_loss_rows);
+
+/* Waits for the context stream and copies the statistics to HOST memory; any pointer may be NULL.  counts[4] = rows used, rows
+ * correct, rows ignored, rows non-finite; loss_sum: one float64, the sum of the used rows' losses; confusion [C][C], row =
+ * truth, column = prediction; hist_pos and hist_neg [C][K] each (not written when K is 0). */
+int kws_eval_read(kws_ctx* ctx, uint64_t* counts, double* loss_sum, uint64_t* confusion, uint64_t* hist_pos, uint64_t* hist_neg);
+
 /* ---- augmentation of the training transform (kws/libs/audio_processor.py:151-159,172-233) ---------- */
 
 /* out[b][i] = (silence[b] ? 0 : wav[b][i - shift[b]] / 32768, 0 outside the clip) + bg_vol[b] * bg[bg_off[b] + i]

@@ -126,6 +126,7 @@ void kws_destroy(kws_ctx* c) {
     if (c->d_feat_ws) (void)hipFree(c->d_feat_ws);
     if (c->d_scan_ws) (void)hipFree(c->d_scan_ws);
     stream_free(c);      // rings, hop counter, captured graph, smoothing and endpointer history (kws_decide.hip)
+    eval_free(c);        // evaluation accumulators (kws_eval.hip)
     ingest_free(c);      // staging rings, copy streams, pack threads
     if (c->order_ev) (void)hipEventDestroy(c->order_ev);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);

@@ -1,6 +1,6 @@
 // The context behind the C ABI (include/kws_hip.h), the error plumbing and the device-memory helpers shared by the translation
 // units that implement it (kws_api.hip, kws_frontend.hip, kws_weights.hip, kws_ingest.hip, kws_scan.hip, kws_decide.hip,
-// kws_*_bwd.hip), and the event bracket of a timed launch.
+// kws_eval.hip, kws_*_bwd.hip), and the event bracket of a timed launch.
 #pragma once
 #include <new>
 
@@ -11,6 +11,7 @@ struct Ingest;  // host-ingest pipeline state (kws_ingest.hip)
 void ingest_free(kws_ctx* c);
 void smooth_free(kws_ctx* c);  // posterior-smoothing and endpointer histories of the streams (kws_decide.hip)
 void vad_free(kws_ctx* c);
+void eval_free(kws_ctx* c);  // evaluation accumulators (kws_eval.hip)
 }  // namespace kws
 
 using kws::FrontendParams; using kws::FrontendTables; using kws::DscnnWeights; using kws::CnnTradWeights; using kws::NFFT;
@@ -97,6 +98,13 @@ struct kws_ctx {
     unsigned char* d_vad_flags = nullptr;
     int* d_vad_state = nullptr;
     int vad_on = 0, vad_off = 0;
+
+    // evaluation statistics (kws_eval_*, kws_eval.hip): one allocation of 64-bit words -- counts[4], loss_sum (a double),
+    // confusion [C][C], hist_pos [C][K], hist_neg [C][K] -- and the per-workgroup float64 loss partials of one update
+    unsigned long long* d_eval = nullptr;
+    int eval_classes = 0, eval_bins = 0;  // eval_classes > 0: open
+    double* d_eval_part = nullptr;
+    size_t eval_part_cap = 0;
 
     // host ingest (kws_infer_host_i16): staging rings, copy streams, pack threads -- created on first use
     kws::Ingest* ingest = nullptr;

@@ -2,23 +2,10 @@
 // posteriors, their moving average per stream and the energy endpointer, each kernel with the entry point that drives it and
 // the history it keeps in the context.  (the reference's scripts take argmax of the logits.)
 #include "kws_ctx.h"
+#include "kws_softmax_dev.h"  // softmax_row: one thread per clip / stream, shared with kws_eval.hip
 
 namespace kws {
 namespace {
-
-// one thread per clip / stream: C <= 64 values, the work is launch latency, not arithmetic
-__device__ __forceinline__ void softmax_row(const float* __restrict__ z, int C, float* __restrict__ p) {
-    float m = z[0];
-    for (int i = 1; i < C; ++i) m = fmaxf(m, z[i]);
-    float sum = 0.f;
-    for (int i = 0; i < C; ++i) {
-        const float e = expf(z[i] - m);
-        p[i] = e;
-        sum += e;
-    }
-    const float inv = 1.0f / sum;
-    for (int i = 0; i < C; ++i) p[i] *= inv;
-}
 
 __global__ void kws_softmax_f32_kernel(const float* __restrict__ logits, int B, int C, float* __restrict__ prob) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;

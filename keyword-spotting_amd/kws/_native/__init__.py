@@ -92,6 +92,12 @@ SIGNATURES = {
     "kws_scan_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, _f32p]),
     "kws_scan_detect_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _f32p, _i32p, _i32p,
                                       _f32p, C.c_int, _i32p]),
+    "kws_eval_open": (C.c_int, [_c_ctx, C.c_int, C.c_int]),
+    "kws_eval_reset": (C.c_int, [_c_ctx]),
+    "kws_eval_close": (C.c_int, [_c_ctx]),
+    "kws_eval_update_f32": (C.c_int, [_c_ctx, _f32p, _i32p, C.c_int, C.c_float, _f32p, _f32p]),
+    "kws_eval_read": (C.c_int, [_c_ctx, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                C.POINTER(C.c_uint64)]),
     "kws_augment_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, C.c_void_p, _f32p, C.c_int, C.c_void_p, _f32p, C.c_void_p, _f32p]),
     "kws_augment_draw": (C.c_int, [_c_ctx, C.c_uint64, C.c_uint32, _i32p, C.c_int, _i32p, C.c_int, C.c_int, _i32p, _i32p, C.c_int, C.c_float,
                                    C.c_float, C.c_int, C.c_int, _i32p, _i32p, _f32p, C.c_void_p]),
@@ -419,6 +425,43 @@ class Context:
         self._check(self._lib.kws_scan_detect_f32(self._h, _ptr(logits), R, W, Cn, int(smooth_window), int(first_keyword), float(threshold),
                                                   int(refractory), p(smoothed), p(event_window), p(event_label), p(event_score),
                                                   int(max_events), _ptr(event_count)), ModelError)
+
+    # -- evaluation ------------------------------------------------------------------------------
+    def eval_open(self, num_classes: int, n_bins: int = 256):
+        """``kws_eval_open``: allocate and zero the context's evaluation state for ``num_classes`` classes and ``n_bins``
+        posterior bins (a power of two in [2, 1024], or 0: no histograms)."""
+        self._check(self._lib.kws_eval_open(self._h, int(num_classes), int(n_bins)), ModelError)
+        self._eval_shape = (int(num_classes), int(n_bins))
+
+    def eval_reset(self):
+        self._check(self._lib.kws_eval_reset(self._h), ModelError)
+
+    def eval_close(self):
+        self._check(self._lib.kws_eval_close(self._h), ModelError)
+        self._eval_shape = None
+
+    def eval_update_f32(self, logits, truth, grad_scale: float = 0.0, dlogits=None, loss_rows=None):
+        """``kws_eval_update_f32``: ``logits`` float32 [B, C] and ``truth`` int32 [B] on the device into the statistics;
+        ``dlogits`` float32 [B, C] (the cross-entropy gradient times ``grad_scale``) and ``loss_rows`` float32 [B] are optional
+        outputs.  Asynchronous on the context's stream."""
+        p = lambda t: _ptr(t) if t is not None else None
+        self._check(self._lib.kws_eval_update_f32(self._h, _ptr(logits), _ptr(truth), int(logits.shape[0]), float(grad_scale), p(dlogits),
+                                                  p(loss_rows)), ModelError)
+
+    def eval_read(self):
+        """``kws_eval_read``: wait for the stream, then (counts uint64[4], loss_sum float, confusion uint64[C, C], hist_pos
+        uint64[C, K], hist_neg uint64[C, K]) on the host; counts = rows used, correct, ignored, non-finite."""
+        shape = getattr(self, "_eval_shape", None)
+        if shape is None:
+            raise ModelError("eval_read: call eval_open first")
+        Cn, K = shape
+        u64 = C.POINTER(C.c_uint64)
+        counts, loss = np.zeros(4, np.uint64), C.c_double(0.0)
+        confusion = np.zeros((Cn, Cn), np.uint64)
+        pos, neg = np.zeros((Cn, K), np.uint64), np.zeros((Cn, K), np.uint64)
+        self._check(self._lib.kws_eval_read(self._h, counts.ctypes.data_as(u64), C.byref(loss), confusion.ctypes.data_as(u64),
+                                            pos.ctypes.data_as(u64) if K else None, neg.ctypes.data_as(u64) if K else None), ModelError)
+        return counts, float(loss.value), confusion, pos, neg
 
     # -- streaming -------------------------------------------------------------------------------
     def stream_open(self, n_streams: int):
