@@ -444,6 +444,40 @@ int kws_scan_detect_f32(kws_ctx* ctx, const float* d_logits, int R, int W, int C
                         float threshold, int refractory, float* d_smoothed, int32_t* d_event_window, int32_t* d_event_label,
                         float* d_event_score, int max_events, int32_t* d_event_count);
 
+/* ---- sample-rate conversion on the device (replaces the resampling inside librosa.load(path, sr=...),
+ * kws/libs/audio_processor.py:120,145; PARITY UNPINNED against librosa's soxr: what is pinned is the project's own host
+ * definition, scipy.signal.resample_poly(x, up, down, window=("kaiser", 14.0)) with zero padding, in float64) ---------------- */
+
+/* The definition.  g = gcd(rate_in, rate_out), up = rate_out / g, down = rate_in / g, M = max(up, down), half = 10 * M.
+ *   Taps h[j], j = 0 .. 2 * half, float64 = firwin(2 * half + 1, 1 / M, window=("kaiser", 14.0)) * up: with n = j - half,
+ *   h0 = (1 / M) * sinc(n / M) * I0(14 * sqrt(1 - (n / half)^2)) / I0(14) and h = up * h0 / sum(h0).
+ *   A recording of n_valid samples has the natural length n_nat = ceil(n_valid * up / down), and for k < n_nat
+ *     y[k] = sum over m of x[m] * h[half + k * down - m * up],   0 <= m < n_valid, tap index in [0, 2 * half]
+ *   -- at most ceil((2 * half + 1) / up) terms (61 for 48 -> 16 kHz, 56 for 44.1 -> 16 kHz, 21 for 8 -> 16 kHz).
+ * Limits: max(up, down) <= 1024, KWS_EUNSUPPORTED beyond (8 / 11.025 / 22.05 / 32 / 44.1 / 48 / 96 / 192 kHz -> 16 kHz all fit;
+ * the largest table, 640 / 441, holds 12 801 float64 taps, 100 KB); n_in and n_out at most 2^30 and at most 2^31 - 1 workgroups
+ * (R * ceil(n_out / outputs_per_workgroup)) per call, KWS_EUNSUPPORTED beyond.
+ *
+ * kws_resample_i16 / kws_resample_f32: d_in [R, n_in] -> d_out [R, n_out] (device), n_out of the caller's choosing.
+ *   d_len: int32 [R] on the device or NULL.  Recording r has len[r] valid samples, clamped to [0, n_in]; NULL: n_in for all.
+ *   Samples at or beyond len[r] count as zero whatever the row holds there.  Output k < min(n_out, n_nat(r)) is y[k]; output
+ *   k >= n_nat(r) is written as zero.  So n_out = the clip length performs fix_length after resampling, the reference's order
+ *   (audio_processor.py:145,148), and a ragged batch needs one launch; kws_host_resample_len gives the natural length.
+ *   Arithmetic: products and sums in float64 with the float64 taps read from a device table; each output is ONE chain of
+ *   fused multiply-adds over its terms in a fixed order (newest sample first), with zeros where its span leaves [0, len).  An
+ *   output's bits depend on its own input span and the rate pair alone: not on R, n_in, n_out, the row, or where k falls in
+ *   the launch.  _f32 rounds the sum to float32.  _i16 sums in int16 units without scaling, clamps to [-32768, 32767] and rounds
+ *   to nearest, ties to even.  rate_in == rate_out is a copy under the same d_len / n_out rules.
+ *   Design cache: the context designs a pair's table on its first use -- float64 on the host, then an upload -- and keeps the
+ *   eight pairs used last; a first use therefore drains the stream and allocates, and is NOT for stream capture.  kws_destroy
+ *   frees the tables.  The calls need neither a front end nor a model.
+ *   R < 1, n_in < 1, n_out < 1, a rate < 1, a NULL d_in / d_out: KWS_EINVAL.  Timed under KWS_K_RESAMPLE.  Asynchronous on the
+ *   context stream; no atomics, so two runs give the same bits. */
+int kws_resample_i16(kws_ctx* ctx, const int16_t* d_in, int R, int n_in, const int32_t* d_len, int rate_in, int rate_out,
+                     int16_t* d_out, int n_out);
+int kws_resample_f32(kws_ctx* ctx, const float* d_in, int R, int n_in, const int32_t* d_len, int rate_in, int rate_out,
+                     float* d_out, int n_out);
+
 /* ---- evaluation statistics on the device (build-defined: the reference computes them on the host, with a
  * round trip per batch -- running_loss += loss.item(), torch.max(outputs, 1), (predicted == labels).sum().item() in
  * train.py:51-54,79-98 and kws/libs/training.py:300-303,347-393 -- and test.py:27-58 derives the per-class report, the
@@ -578,7 +612,8 @@ int kws_spec_f32(kws_ctx* ctx, const float* d_frames, int num_frames, int frame_
  * as a hipGraph is not (events cannot bracket a node). */
 enum { KWS_K_MFCC = 0, KWS_K_DSCNN = 1, KWS_K_CNNTRAD_CONV = 2, KWS_K_CNNTRAD_DENSE = 3, KWS_K_STREAM_FRAME = 4, KWS_K_MFCC_F64 = 5, KWS_K_MFCC_REFINE = 6,
        KWS_K_DSCNN_LOAD_STATS = 7, KWS_K_DSCNN_LOAD_PACK = 8, KWS_K_DSCNN_LOAD_FILL = 9, /* the launches of kws_load_dscnn_device */
-       KWS_K_COUNT = 10 };
+       KWS_K_RESAMPLE = 10,                                                              /* kws_resample_i16 / kws_resample_f32 */
+       KWS_K_COUNT = 11 };
 int kws_prof_enable(kws_ctx* ctx, int on);
 int kws_prof_reset(kws_ctx* ctx);
 int kws_prof_read(kws_ctx* ctx, int kernel_id, double* total_ms, int* launches);
@@ -617,6 +652,17 @@ int kws_host_cnn_trad_image(const float* blob, size_t n_floats, int num_classes,
  * be NULL.  Non-positive sizes: KWS_EINVAL. */
 int kws_host_scan_shape(int n_total, int frame_len, int frame_step, int window_frames, int hop_frames, int* frames_total,
                         int* n_windows);
+
+/* Host side of kws_resample_* (no GPU).  kws_host_resample_len: *n_out = ceil(n_in * up / down), the natural length of n_in
+ * samples (n_in >= 0).  kws_host_resample_design: the reduced pair, half (the taps number 2 * half + 1), the outputs one
+ * workgroup of the kernel owns -- a recording's outputs are cut into tiles of that many from output 0, so tests can place
+ * lengths on both sides of a tile edge -- and the taps h[0 .. 2 * half] exactly as the device table holds them (which appends
+ * zeros up to a multiple of up).  *need (may be NULL) is always set to the number of taps; taps == NULL only asks for the
+ * sizes, a cap below *need is KWS_EINVAL.  Any other pointer may be NULL.  A rate < 1: KWS_EINVAL; max(up, down) > 1024:
+ * KWS_EUNSUPPORTED. */
+int kws_host_resample_len(int n_in, int rate_in, int rate_out, int* n_out);
+int kws_host_resample_design(int rate_in, int rate_out, int* up, int* down, int* half_len, int* outputs_per_workgroup,
+                             double* taps, size_t cap, size_t* need);
 
 #ifdef __cplusplus
 }

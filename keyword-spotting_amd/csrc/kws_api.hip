@@ -15,7 +15,7 @@ namespace kws {
 const char* const kKernelNames[KWS_K_COUNT] = {"kws_mfcc_i16_kernel", "kws_dscnn_fwd_kernel", "kws_cnntrad_conv_kernel",
                                                "kws_cnntrad_dense_kernel", "kws_stream_frame_kernel", "kws_mfcc_f64_kernel",
                                                "kws_mfcc_refine_kernel", "kws_ds_load_stats_kernel", "kws_ds_load_pack_kernel",
-                                               "kws_ds_load_fill_kernel"};
+                                               "kws_ds_load_fill_kernel", "kws_resample_kernel"};
 
 }  // namespace kws
 
@@ -127,6 +127,7 @@ void kws_destroy(kws_ctx* c) {
     if (c->d_scan_ws) (void)hipFree(c->d_scan_ws);
     stream_free(c);      // rings, hop counter, captured graph, smoothing and endpointer history (kws_decide.hip)
     eval_free(c);        // evaluation accumulators (kws_eval.hip)
+    resample_free(c);    // tap tables of the rate pairs (kws_resample.hip)
     ingest_free(c);      // staging rings, copy streams, pack threads
     if (c->order_ev) (void)hipEventDestroy(c->order_ev);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);

@@ -1,6 +1,6 @@
 // The context behind the C ABI (include/kws_hip.h), the error plumbing and the device-memory helpers shared by the translation
 // units that implement it (kws_api.hip, kws_frontend.hip, kws_weights.hip, kws_ingest.hip, kws_scan.hip, kws_decide.hip,
-// kws_eval.hip, kws_*_bwd.hip), and the event bracket of a timed launch.
+// kws_eval.hip, kws_resample.hip, kws_*_bwd.hip), and the event bracket of a timed launch.
 #pragma once
 #include <new>
 
@@ -12,6 +12,8 @@ void ingest_free(kws_ctx* c);
 void smooth_free(kws_ctx* c);  // posterior-smoothing and endpointer histories of the streams (kws_decide.hip)
 void vad_free(kws_ctx* c);
 void eval_free(kws_ctx* c);  // evaluation accumulators (kws_eval.hip)
+struct ResampleCache;           // rate pairs designed so far and their device tap tables (kws_resample.hip)
+void resample_free(kws_ctx* c);
 }  // namespace kws
 
 using kws::FrontendParams; using kws::FrontendTables; using kws::DscnnWeights; using kws::CnnTradWeights; using kws::NFFT;
@@ -105,6 +107,9 @@ struct kws_ctx {
     int eval_classes = 0, eval_bins = 0;  // eval_classes > 0: open
     double* d_eval_part = nullptr;
     size_t eval_part_cap = 0;
+
+    // sample-rate conversion (kws_resample_*): the tap tables of the rate pairs used so far -- created on first use
+    kws::ResampleCache* resample = nullptr;
 
     // host ingest (kws_infer_host_i16): staging rings, copy streams, pack threads -- created on first use
     kws::Ingest* ingest = nullptr;

@@ -22,6 +22,7 @@ KWS_OK, KWS_EINVAL, KWS_ENOMEM, KWS_EHIP, KWS_ESTATE, KWS_EUNSUPPORTED = 0, -1, 
 KWS_CT_F16_PAIR, KWS_CT_BF16_TRIPLE = 0, 1  # kws_set_cnn_trad_math
 KWS_K_MFCC, KWS_K_DSCNN, KWS_K_CNNTRAD_CONV, KWS_K_CNNTRAD_DENSE, KWS_K_STREAM_FRAME, KWS_K_MFCC_F64, KWS_K_MFCC_REFINE = 0, 1, 2, 3, 4, 5, 6
 KWS_K_DSCNN_LOAD_STATS, KWS_K_DSCNN_LOAD_PACK, KWS_K_DSCNN_LOAD_FILL = 7, 8, 9  # the launches of kws_load_dscnn_device
+KWS_K_RESAMPLE = 10  # kws_resample_i16 / kws_resample_f32
 FE_REFINE_SPAN_DEFAULT = 10.2  # KWS_FE_REFINE_SPAN_DEFAULT: log(largest bin power / weakest mel band) beyond which a frame is redone in float64
 FE_F32, FE_F64 = 0, 1  # KWS_FE_F32 (default: the fast float32 front end) / KWS_FE_F64 (float64 after framing, as psf)
 ACT_FLOATS_PER_CLIP = 64 * (141 + 141 + 245 + 357) + 64 + 64 * 477  # KWS_ACT_FLOATS_PER_CLIP
@@ -92,6 +93,8 @@ SIGNATURES = {
     "kws_scan_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, _f32p]),
     "kws_scan_detect_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _f32p, _i32p, _i32p,
                                       _f32p, C.c_int, _i32p]),
+    "kws_resample_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _i16p, C.c_int]),
+    "kws_resample_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _f32p, C.c_int]),
     "kws_eval_open": (C.c_int, [_c_ctx, C.c_int, C.c_int]),
     "kws_eval_reset": (C.c_int, [_c_ctx]),
     "kws_eval_close": (C.c_int, [_c_ctx]),
@@ -121,6 +124,9 @@ SIGNATURES = {
     "kws_host_cnn_trad_image": (C.c_int, [C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_uint32), C.c_size_t,
                                           C.POINTER(C.c_size_t), C.POINTER(C.c_float)]),
     "kws_host_scan_shape": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "kws_host_resample_len": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "kws_host_resample_design": (C.c_int, [C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4 + [C.POINTER(C.c_double), C.c_size_t,
+                                           C.POINTER(C.c_size_t)]),
 }
 
 _lib = None
@@ -426,6 +432,21 @@ class Context:
                                                   int(refractory), p(smoothed), p(event_window), p(event_label), p(event_score),
                                                   int(max_events), _ptr(event_count)), ModelError)
 
+    # -- sample-rate conversion --------------------------------------------------------------------
+    def _resample(self, fn, x, rate_in, rate_out, out, lengths):
+        self._check(fn(self._h, _ptr(x), int(x.shape[0]), int(x.shape[1]), _ptr(lengths) if lengths is not None else None, int(rate_in),
+                       int(rate_out), _ptr(out), int(out.shape[1])), AudioProcessingError)
+
+    def resample_i16(self, pcm, rate_in, rate_out, out, lengths=None):
+        """``kws_resample_i16``: ``pcm`` int16 [R, n_in] at ``rate_in`` -> ``out`` int16 [R, n_out] at ``rate_out``, both on the
+        device; ``lengths`` int32 [R] (device) gives each row's valid samples.  Outputs beyond a row's natural length
+        (``host_resample_len``) are zeros.  The first use of a rate pair designs and uploads its taps."""
+        self._resample(self._lib.kws_resample_i16, pcm, rate_in, rate_out, out, lengths)
+
+    def resample_f32(self, signal, rate_in, rate_out, out, lengths=None):
+        """``kws_resample_f32``: the same for float32 [R, n_in] -> float32 [R, n_out]."""
+        self._resample(self._lib.kws_resample_f32, signal, rate_in, rate_out, out, lengths)
+
     # -- evaluation ------------------------------------------------------------------------------
     def eval_open(self, num_classes: int, n_bins: int = 256):
         """``kws_eval_open``: allocate and zero the context's evaluation state for ``num_classes`` classes and ``n_bins``
@@ -638,6 +659,29 @@ def host_scan_shape(n_total, frame_len=400, frame_step=160, window_frames=99, ho
     if rc != KWS_OK:
         raise KWSError(f"kws_host_scan_shape failed ({rc}): sizes must be positive")
     return int(frames.value), int(windows.value)
+
+
+def host_resample_len(n_in, rate_in, rate_out) -> int:
+    """ceil(n_in * up / down): the natural length of ``n_in`` samples at ``rate_in`` once at ``rate_out`` (``kws_host_resample_len``)."""
+    n = C.c_int(0)
+    rc = lib().kws_host_resample_len(int(n_in), int(rate_in), int(rate_out), C.byref(n))
+    if rc != KWS_OK:
+        raise AudioProcessingError(f"kws_host_resample_len({n_in}, {rate_in}, {rate_out}) failed (code {rc})")
+    return int(n.value)
+
+
+def host_resample_design(rate_in, rate_out):
+    """(up, down, half_len, outputs_per_workgroup, taps float64 [2 * half_len + 1]) of a rate pair: the taps the device table
+    holds and the tile of the kernel (``kws_host_resample_design``)."""
+    up, down, half, tile, need = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_size_t(0)
+    fn = lib().kws_host_resample_design
+    rc = fn(int(rate_in), int(rate_out), C.byref(up), C.byref(down), C.byref(half), C.byref(tile), None, 0, C.byref(need))
+    if rc == KWS_OK:
+        taps = np.empty(need.value, np.float64)
+        rc = fn(int(rate_in), int(rate_out), None, None, None, None, taps.ctypes.data_as(C.POINTER(C.c_double)), taps.size, None)
+    if rc != KWS_OK:
+        raise AudioProcessingError(f"{lib().kws_last_error(None).decode()} (code {rc})")
+    return int(up.value), int(down.value), int(half.value), int(tile.value), taps
 
 
 def _host_image(fn, n_scalars, blob, *dims):

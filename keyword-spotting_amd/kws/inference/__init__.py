@@ -11,7 +11,7 @@ import torch
 
 from kws.common.errors import AudioProcessingError, ModelError
 from kws.datasets.speech_commands import DEFAULT_WORDS, SpeechCommandDataset
-from kws.libs.audio_processor import AudioConfig, fix_length, load_audio, load_pcm16
+from kws.libs.audio_processor import AudioConfig, fix_length, load_audio, load_pcm16, read_wav
 from kws.libs.models import DepthwiseSeparableConv
 
 WANTED_WORDS = [SpeechCommandDataset.SILENCE_LABEL, SpeechCommandDataset.UNKNOWN_LABEL] + DEFAULT_WORDS
@@ -104,10 +104,15 @@ class KeywordSpotter:
             if pending is not None:  # the consumer stopped early: nothing may stay in flight into freed arrays
                 ctx.infer_host_wait(0)
 
-    def infer_files(self, paths: Sequence[str], resample: bool = False) -> List[Tuple[int, str]]:
+    def infer_files(self, paths: Sequence[str], resample=False) -> List[Tuple[int, str]]:
         """wav files -> (index, word).  16-bit mono files at the configured rate go through the int16 path (the PCM
         itself is the device input); anything else -- other bit depths, float, stereo, and with ``resample=True`` other
-        rates -- is decoded to float32 mono as ``librosa.load`` does and takes the float32 path (``kws_infer_f32``)."""
+        rates -- is decoded to float32 mono as ``librosa.load`` does and takes the float32 path (``kws_infer_f32``).
+        ``resample="device"`` serves any rate on the device instead (``_infer_files_device``)."""
+        if isinstance(resample, str):
+            if resample != "device":
+                raise AudioProcessingError(f"infer_files: resample must be False, True or 'device', got {resample!r}")
+            return self._infer_files_device(paths)
         n = self.config.desired_samples
         clips, all_i16 = [], True
         for p in paths:
@@ -126,6 +131,39 @@ class KeywordSpotter:
             labels, _ = self.infer_f32(f32)
         return [(int(i), self.words[int(i)]) for i in labels]
 
+    def _infer_files_device(self, paths: Sequence[str]) -> List[Tuple[int, str]]:
+        """``infer_files(resample="device")``: every file is decoded at its own rate (``read_wav``: 16-bit mono stays int16,
+        anything else is float32 mono) and the files are grouped by (rate, sample type).  A group is uploaded as one batch padded
+        to its longest file, resampled to the configured rate and cut or zero-padded to a clip in ONE launch
+        (``kws_resample_i16`` / ``kws_resample_f32`` with the true lengths and ``n_out = desired_samples``: ``fix_length`` after
+        resampling, the reference's order) and classified where it lies (``kws_infer_i16`` / ``kws_infer_f32``).  Results come
+        back in the order of ``paths``.  Parity against librosa's soxr resampler is unpinned, as with ``resample=True``."""
+        cfg = self.config
+        decoded = [read_wav(p) for p in paths]
+        groups: dict = {}
+        for i, (x, rate) in enumerate(decoded):
+            groups.setdefault((rate, x.dtype == np.int16), []).append(i)
+        ctx = self.model._context(self.device.index or 0)
+        result = np.empty(len(decoded), np.int32)
+        for (rate, is_i16), members in groups.items():
+            clips = [decoded[i][0] for i in members]
+            batch = np.zeros((len(clips), max(1, max(len(x) for x in clips))), np.int16 if is_i16 else np.float32)
+            for row, x in zip(batch, clips):
+                row[:len(x)] = x
+            x = torch.from_numpy(batch).to(self.device)
+            lengths = torch.tensor([len(c) for c in clips], dtype=torch.int32, device=self.device)
+            y = torch.empty((len(clips), cfg.desired_samples), dtype=x.dtype, device=self.device)
+            logits = torch.empty((len(clips), self.model.num_classes), dtype=torch.float32, device=self.device)
+            labels = torch.empty((len(clips),), dtype=torch.int32, device=self.device)
+            if is_i16:
+                ctx.resample_i16(x, rate, cfg.sample_rate, y, lengths)
+                ctx.infer_i16(y, logits, labels)
+            else:
+                ctx.resample_f32(x, rate, cfg.sample_rate, y, lengths)
+                ctx.infer_f32(y, logits, labels)
+            result[members] = labels.cpu().numpy()
+        return [(int(i), self.words[int(i)]) for i in result]
+
     def infer_f32(self, signals: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
         """``float32[B,n]`` host signals in [-1, 1] -> (labels int32[B], logits float32[B,C]) (``kws_infer_f32``)."""
         x = torch.from_numpy(np.ascontiguousarray(fix_length(np.atleast_2d(np.asarray(signals, dtype=np.float32)),
@@ -138,13 +176,15 @@ class KeywordSpotter:
 
 
     def scan(self, pcm, hop_frames: int = 1, smooth_window: int = 1, threshold: Optional[float] = None, refractory: int = 50,
-             first_keyword: int = 2, max_events: int = 1024) -> ScanResult:
+             first_keyword: int = 2, max_events: int = 1024, sample_rate: Optional[int] = None) -> ScanResult:
         """Where are the keywords in a recording longer than a clip?  ``pcm``: int16 ``[n]`` or ``[R, n]`` (R recordings of
         equal length), a host array or a device tensor.  One MFCC pass per recording, then the model on every window of 99
         frames, ``hop_frames`` frames (10 ms each) apart (``kws_scan_i16``).  With a ``threshold`` the windows' posteriors are
         smoothed over ``smooth_window`` windows and turned into events at least ``refractory`` windows apart, classes below
         ``first_keyword`` (_silence_, _unknown_) never firing (``kws_scan_detect_f32``); at most ``max_events`` per recording
-        are returned.  A recording shorter than one window raises ``ModelError``."""
+        are returned.  A recording shorter than one window raises ``ModelError``.  ``sample_rate``: the rate of ``pcm`` when it
+        is not the configured one; the recordings are then resampled on the device to their natural length at the configured
+        rate (``kws_resample_i16``) and the result is scanned, so window and event times stay in seconds of the recording."""
         from kws import _native
 
         if torch.is_tensor(pcm):
@@ -168,6 +208,13 @@ class KeywordSpotter:
             if int(refractory) < 1 or int(first_keyword) < 0 or int(max_events) < 0:
                 raise ModelError("scan: need refractory >= 1, first_keyword >= 0 and max_events >= 0")
         cfg = self.config
+        if sample_rate is not None and int(sample_rate) != cfg.sample_rate:
+            if x.shape[1] < 1:
+                raise ModelError("scan: the recording is empty")
+            src = x.to(self.device).contiguous()
+            x = torch.empty((src.shape[0], _native.host_resample_len(src.shape[1], sample_rate, cfg.sample_rate)), dtype=torch.int16,
+                            device=self.device)
+            self.model._context(self.device.index or 0).resample_i16(src, sample_rate, cfg.sample_rate, x)
         frame_len, frame_step = _round_half_up(cfg.frame_length * cfg.sample_rate), _round_half_up(cfg.frame_step * cfg.sample_rate)
         R, n = int(x.shape[0]), int(x.shape[1])
         frames, W = (0, 0) if n < 1 else _native.host_scan_shape(n, frame_len, frame_step, WINDOW_FRAMES, int(hop_frames))
@@ -194,9 +241,18 @@ class KeywordSpotter:
                        for i in range(min(int(count[r]), m))] for r in range(R)]
         return ScanResult(labels.cpu().numpy(), logits.cpu().numpy(), start_s, events)
 
-    def scan_file(self, path: str, **kwargs) -> ScanResult:
+    def scan_file(self, path: str, resample: bool = False, **kwargs) -> ScanResult:
         """``scan`` over a whole wav file (no trimming or padding to a clip).  The file must be 16-bit mono PCM at the
-        configured rate: anything else raises ``AudioProcessingError`` with the reason."""
+        configured rate: anything else raises ``AudioProcessingError`` with the reason.  With ``resample=True`` a 16-bit mono
+        file at another rate is uploaded at its own rate and resampled on the device (``scan`` with ``sample_rate``); any other
+        encoding at another rate is still refused -- ``kws_scan_i16`` takes int16 and there is no float32 scan."""
+        if resample:
+            x, rate = read_wav(path)
+            if rate != self.config.sample_rate:
+                if x.dtype != np.int16:
+                    raise AudioProcessingError(f"{path}: sample rate {rate} != {self.config.sample_rate} and the file is not 16-bit mono "
+                                               "PCM; the device resampler of scan_file takes int16 only (there is no float32 scan)")
+                return self.scan(x, sample_rate=rate, **kwargs)
         x = load_pcm16(path, self.config.sample_rate)
         if x.ndim == 2:
             raise AudioProcessingError(f"{path}: {x.shape[1]} channels; scan_file takes mono files")

@@ -7,8 +7,9 @@ delegates to ``python_speech_features.mfcc`` runs in the batched HIP kernel behi
 ``kws_mfcc_f32`` (include/kws_hip.h).  WAV decoding and the random augmentations stay on the host.
 
 Additions for batched use: ``extract_features_batch`` (device tensor in, ``float32[B,1,T,F]`` out --
-the collated batch of the reference's data loader), ``load_pcm16`` (16-bit files as int16, the fast path's input) and
-``load_audio`` (any PCM / float WAV as float32 mono, what ``librosa.load`` returns).
+the collated batch of the reference's data loader), ``load_pcm16`` (16-bit files as int16, the fast path's input),
+``load_audio`` (any PCM / float WAV as float32 mono, what ``librosa.load`` returns) and ``read_wav`` (a file at its own rate, for
+the device resampler ``kws_resample_i16`` / ``kws_resample_f32``).
 """
 from __future__ import annotations
 
@@ -79,15 +80,8 @@ def load_pcm16(path, sample_rate: int = 16000) -> np.ndarray:
     return data
 
 
-def load_audio(path, sample_rate: int = 16000, resample: bool = False) -> np.ndarray:
-    """Decode a WAV file to what ``librosa.load(path, sr=sample_rate)`` hands the reference (``audio_processor.py:145``):
-    float32 mono in [-1, 1).  Integer PCM of 8 / 16 / 24 / 32 bits is scaled like libsndfile does (u8: (v - 128)/128,
-    otherwise v / 2**(bits-1)), IEEE float32 / float64 is taken as is, WAVE_FORMAT_EXTENSIBLE is read through its
-    sub-format; channels are averaged in float32 (``librosa.to_mono``).
-
-    A file at another sample rate is refused unless ``resample=True``: librosa resamples with soxr ('soxr_hq'), which is
-    not available here and cannot be reproduced bit for bit; with ``resample=True`` a Kaiser-windowed polyphase filter
-    (``scipy.signal.resample_poly``) is used instead -- PARITY UNPINNED against the reference for such files."""
+def _decode_wav(path):
+    """(payload bytes, format tag, channels, rate, bits) of a RIFF/WAVE file; WAVE_FORMAT_EXTENSIBLE is read through its sub-format."""
     import struct
 
     with open(str(path), "rb") as f:
@@ -110,6 +104,11 @@ def load_audio(path, sample_rate: int = 16000, resample: bool = False) -> np.nda
         tag = struct.unpack("<H", fmt[24:26])[0]
     if ch < 1:
         raise AudioProcessingError(f"{path}: no channels")
+    return payload, tag, ch, rate, bits
+
+
+def _float_mono(path, payload, tag, ch, bits) -> np.ndarray:
+    """A decoded payload as float32 mono in [-1, 1), scaled as libsndfile does and mixed down as ``librosa.to_mono``."""
     if tag == 1 and bits == 8:
         x = (np.frombuffer(payload, dtype=np.uint8).astype(np.float32) - np.float32(128.0)) / np.float32(128.0)
     elif tag == 1 and bits == 16:
@@ -130,17 +129,47 @@ def load_audio(path, sample_rate: int = 16000, resample: bool = False) -> np.nda
     x = x[: len(x) // ch * ch]
     if ch > 1:
         x = x.reshape(-1, ch).mean(axis=1, dtype=np.float32)
+    return x
+
+
+def read_wav(path):
+    """Decode a WAV file at its own rate: ``(samples, rate)``.  16-bit mono PCM comes back as int16 -- the samples themselves,
+    the input of the int16 device entries -- and every other encoding ``load_audio`` reads as float32 mono in [-1, 1).  No rate
+    check and no resampling: ``kws_resample_i16`` / ``kws_resample_f32`` take it from here."""
+    payload, tag, ch, rate, bits = _decode_wav(path)
+    if tag == 1 and bits == 16 and ch == 1:
+        return np.ascontiguousarray(np.frombuffer(payload[: len(payload) // 2 * 2], dtype="<i2").astype(np.int16)), int(rate)
+    return np.ascontiguousarray(_float_mono(path, payload, tag, ch, bits), dtype=np.float32), int(rate)
+
+
+def load_audio(path, sample_rate: int = 16000, resample: bool = False) -> np.ndarray:
+    """Decode a WAV file to what ``librosa.load(path, sr=sample_rate)`` hands the reference (``audio_processor.py:145``):
+    float32 mono in [-1, 1).  Integer PCM of 8 / 16 / 24 / 32 bits is scaled like libsndfile does (u8: (v - 128)/128,
+    otherwise v / 2**(bits-1)), IEEE float32 / float64 is taken as is, WAVE_FORMAT_EXTENSIBLE is read through its
+    sub-format; channels are averaged in float32 (``librosa.to_mono``).
+
+    A file at another sample rate is refused unless ``resample=True``: librosa resamples with soxr ('soxr_hq'), which is
+    not available here and cannot be reproduced bit for bit; with ``resample=True`` a Kaiser-windowed polyphase filter
+    (``scipy.signal.resample_poly``) is used instead -- PARITY UNPINNED against the reference for such files."""
+    payload, tag, ch, rate, bits = _decode_wav(path)
+    x = _float_mono(path, payload, tag, ch, bits)
     if rate != sample_rate:
         if not resample:
             raise AudioProcessingError(f"{path}: sample rate {rate} != {sample_rate}; pass resample=True for a polyphase "
                                        "resampler (librosa's soxr resampler cannot be reproduced: parity unpinned)")
-        from math import gcd
-
-        from scipy.signal import resample_poly
-
-        g = gcd(int(rate), int(sample_rate))
-        x = resample_poly(x.astype(np.float64), sample_rate // g, rate // g, window=("kaiser", 14.0)).astype(np.float32)
+        x = resample_host(x, rate, sample_rate).astype(np.float32)
     return np.ascontiguousarray(x, dtype=np.float32)
+
+
+def resample_host(x: np.ndarray, rate_in: int, rate_out: int) -> np.ndarray:
+    """The host definition of the project's resampler, float64 in and out: ``scipy.signal.resample_poly`` with
+    ``window=("kaiser", 14.0)`` and zero padding.  ``kws_resample_i16`` / ``kws_resample_f32`` evaluate the same sum on the device."""
+    from math import gcd
+
+    from scipy.signal import resample_poly
+
+    g = gcd(int(rate_in), int(rate_out))
+    return resample_poly(np.asarray(x).astype(np.float64), int(rate_out) // g, int(rate_in) // g, window=("kaiser", 14.0))
 
 
 def _to_float_mono(pcm: np.ndarray) -> np.ndarray:
