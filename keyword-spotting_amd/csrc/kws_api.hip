@@ -200,41 +200,33 @@ static int forward_map_impl(kws_ctx* c, const float* d_feat, int B, int T, int F
     if (!d_logits) return fail(c, KWS_EINVAL, std::string(fn) + ": d_logits is NULL");
     if (!c->model_ready) return fail(c, KWS_ESTATE, std::string(fn) + ": no model loaded (kws_load_dscnn)");
     if (T == IN_T && F == IN_F && !d_layers) return forward_impl(c, d_feat, B, d_logits, d_label, nullptr, c->pw_math, fn);
-    if (T < 6 || F < 6) return fail(c, KWS_EINVAL, std::string(fn) + ": the 10 x 10 first convolution (padding 2) needs T >= 6 and F >= 6");
-    if ((size_t)(T + 4) * (F + 4) * sizeof(float) > 160 * 1024)
-        return fail(c, KWS_EUNSUPPORTED, std::string(fn) + ": the padded feature map must fit 160 KB of LDS ((T + 4) * (F + 4) <= 40960)");
+    rc = check_dscnn_map(c, fn, T, F);
+    if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    const int H1 = (T - 6) / 2 + 1, W1 = (F - 6) / 2 + 1, Cin = c->mw.in_channels, C = c->mw.num_classes;
-    const size_t per_clip_max = (size_t)CH * (H1 + 8) * (W1 + 8);   // block 4's output, ring included
-    const size_t dw_max = (size_t)CH * (H1 + 6) * (W1 + 6);        // block 4's depthwise output
-    const int chunk = B < 16384 ? B : 16384;                        // grid.z of the pointwise kernel, and a bounded workspace
+    const DscnnMap m(T, F);
+    const int Cin = c->mw.in_channels, C = c->mw.num_classes, LAST = N_BLOCKS - 1;
+    const size_t per_clip_max = CH * m.Q(LAST);                            // block 4's output, ring included
+    const size_t dw_max = CH * m.P(LAST);                                  // block 4's depthwise output
+    const int chunk = B < COMPOSED_MAX_CLIPS ? B : COMPOSED_MAX_CLIPS;     // a bounded workspace
     rc = grow_conv_ws(c, (size_t)chunk * (2 * per_clip_max + dw_max), fn);
     if (rc) return rc;
     float* bufs[2] = {c->d_conv_ws, c->d_conv_ws + (size_t)chunk * per_clip_max};
     float* dw_ws = c->d_conv_ws + 2 * (size_t)chunk * per_clip_max;
-    const float* raw = c->mw.raw + (size_t)6400 * Cin + 64;        // first block's parameters in state_dict order
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int nb = B - b0 < chunk ? B - b0 : chunk;
-        HIP_TRY(c, launch_conv1_any(c->stream, d_feat + (size_t)b0 * Cin * T * F, nb, Cin, T, F, c->mw.c1_general, c->mw.c1_b, bufs[0]));
-        int H = H1, W = W1, cur = 0;
+        // the stages ping-pong between the two buffers; the diagnostics entry keeps them in d_layers instead, stage-major with the
+        // batch inside: stage i of this chunk is the run [nb][per_clip] at lo * B + b0 * per_clip, lo = the per-clip floats before it
+        DscnnStages st;
         size_t lo = 0;
-        auto dump = [&](const float* src, size_t per_clip) -> hipError_t {  // diagnostics: stage outputs, stage-major, batch inside
-            if (!d_layers) return hipSuccess;
-            hipError_t e = hipMemcpyAsync(d_layers + lo * B + (size_t)b0 * per_clip, src, sizeof(float) * per_clip * nb, hipMemcpyDeviceToDevice, c->stream);
+        for (int i = 0; i <= N_BLOCKS; ++i) {
+            const size_t per_clip = CH * m.P(i);
+            float*& stage = i ? st.y[i - 1] : st.a0;
+            stage = d_layers ? d_layers + lo * B + (size_t)b0 * per_clip : bufs[i & 1];
+            if (i < N_BLOCKS) st.dw[i] = dw_ws;
             lo += per_clip;
-            return e;
-        };
-        HIP_TRY(c, dump(bufs[0], (size_t)CH * H * W));
-        for (int blk = 0; blk < N_BLOCKS; ++blk) {
-            const float* prm = raw + (size_t)blk * (576 + 64 + 4096 + 64);
-            HIP_TRY(c, launch_dsblock(c->stream, bufs[cur], nb, CH, H, W, prm, prm + 576, prm + 640, prm + 640 + 4096, CH, 3, 1, 1, dw_ws,
-                                      bufs[cur ^ 1]));
-            cur ^= 1;
-            H += 2;
-            W += 2;
-            HIP_TRY(c, dump(bufs[cur], (size_t)CH * H * W));
         }
-        HIP_TRY(c, launch_pool_fc(c->stream, bufs[cur], nb, H * W, c->mw.fc_w, c->mw.fc_b, C, d_logits + (size_t)b0 * C,
+        HIP_TRY(c, launch_dscnn_composed(c->stream, c->mw, d_feat + (size_t)b0 * Cin * T * F, nb, T, F, st));
+        HIP_TRY(c, launch_pool_fc(c->stream, st.y[LAST], nb, (int)m.Q(LAST), c->mw.fc_w, c->mw.fc_b, C, d_logits + (size_t)b0 * C,
                                   d_label ? d_label + b0 : nullptr));
     }
     return KWS_OK;

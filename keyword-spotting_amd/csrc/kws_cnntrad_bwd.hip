@@ -29,44 +29,33 @@
 // in runs of 32.
 //
 // Memory is written with plain vector stores only; there is no inline assembly in this unit.
-#include <algorithm>
-#include <string>
-
-#include "kws_ctx.h"
+#include "kws_train.h"
 
 namespace kws {
 namespace {
 
-constexpr int CT_T = 99, CT_F = 10, CT_P = 297, CT_FLAT = CH * CT_P;  // pooled map: 64 x 99 x 3
-constexpr int XP_H = 118, XP_W = 17;                                  // conv1's zero-padded input (pad 9/10 x 3/4)
-constexpr int W2_N = 64 * 64 * 40;                                    // conv2.weight floats
-// offsets of the state_dict tensors in the kws_load_cnn_trad blob (floats)
-constexpr size_t O_W1 = 0, O_B1 = O_W1 + 64 * 160, O_W2 = O_B1 + 64, O_B2 = O_W2 + W2_N, O_WL = O_B2 + 64, O_BL = O_WL + (size_t)32 * CT_FLAT,
-                 O_WD = O_BL + 32, O_BD = O_WD + 128 * 32, O_WF = O_BD + 128;  // fc.bias at O_WF + 128 C
-constexpr int MAX_CHUNK = 8192;      // clips per chunk (the workspace is about 324 KB per clip)
-constexpr int CONV_GROUPS = 256;     // clip groups of the two weight-gradient kernels
-constexpr int TAIL_CPG = 64;         // clips per group of the tail kernel
-constexpr int RUN = 64;              // positions per run of a weight-gradient sum
-constexpr int C2W_PART = W2_N + 64;  // [kk][co][ci] | conv2.bias
-constexpr int C1W_PART = 64 * 160 + 64;
+using CL = CtLayout;
+constexpr int CT_T = 99, CT_F = 10, CT_P = 297, CT_FLAT = (int)CL::FLAT;  // pooled map: 64 x 99 x 3
+static_assert(CT_FLAT == CH * CT_P, "lin's inputs are the pooled map");
+constexpr int XP_H = 118, XP_W = 17;                                      // conv1's zero-padded input (pad 9/10 x 3/4)
+constexpr int W2_N = CL::N_C2;                                            // conv2.weight floats
+constexpr int MAX_CHUNK = 8192;                // clips per chunk (the workspace is about 324 KB per clip)
+constexpr int CONV_GROUPS = 256;               // clip groups of the two weight-gradient kernels
+constexpr int TAIL_CPG = 64;                   // clips per group of the tail kernel
+constexpr int C2W_PART = W2_N + (int)CL::CO;   // [kk][co][ci] | conv2.bias
+constexpr int C1W_PART = CL::N_C1 + (int)CL::CO;
+constexpr int HD = CL::LIN_OUT + CL::DNN_OUT;  // [h | d] per clip
 constexpr int LIN_TILES = CT_FLAT / 32;  // 594 column tiles of lin.weight
 constexpr int LF_WAVES = 6, LF_BLOCKS = LIN_TILES / LF_WAVES;  // h = lin(y2): 99 blocks of 32 k per wave
 static_assert(LF_BLOCKS * LF_WAVES == LIN_TILES && LF_BLOCKS % 3 == 0, "K of lin must divide among the waves");
-constexpr int tail_part_floats(int C) { return 32 + 128 * 32 + 128 + 128 * C + C; }  // lin.b | dnn.w | dnn.b | fc.w | fc.b
+// the tail's partial row, in the blob's order from lin.bias on: lin.b | dnn.w | dnn.b | fc.w | fc.b
+constexpr int TP_DW = CL::LIN_OUT, TP_DB = TP_DW + CL::N_DNN, TP_FW = TP_DB + CL::DNN_OUT;
+constexpr int tail_part_floats(int C) { return TP_FW + CL::DNN_OUT * C + C; }
 constexpr int CONV2_LDS = CT_FLAT * 4;                           // one map [64][297]
 constexpr int C2W_LDS = 2 * CT_FLAT * 4;                         // dz2 | yp
 constexpr int C1W_X = 2048;                                      // floats reserved for the padded input (118 x 17 = 2006)
 constexpr int C1W_LDS = (C1W_X + CT_FLAT) * 4 + CT_FLAT;         // padded input | dz1 | winners (bytes)
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ void zero16(f32x16& v) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) v[r] = 0.f;
-}
-// D layout of the 32x32 MFMAs: register r of a lane in half-wave `half` is row (r & 3) + 8 (r >> 2) + 4 half, column lane & 31
-__device__ __forceinline__ int drow(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 __device__ __forceinline__ float relu0(float v) { return v > 0.f ? v : 0.f; }
 
 // ---- conv2.weight [co][ci][kk] as A-operand tables ------------------------------------------------------------------------
@@ -87,14 +76,14 @@ __global__ __launch_bounds__(256) void kws_ct_bwd_conv1_kernel(const float* __re
                                                                unsigned char* __restrict__ win, float* __restrict__ dbg_conv1,
                                                                int32_t* __restrict__ dbg_win) {
     __shared__ float s_x[XP_H * XP_W];
-    __shared__ float s_w[64 * 160];
+    __shared__ float s_w[CL::N_C1];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, b = blockIdx.x;
     const float* xb = feat + (size_t)b * (CT_T * CT_F);
     for (int i = tid; i < XP_H * XP_W; i += 256) {
         const int r = i / XP_W - 9, c = i % XP_W - 3;
         s_x[i] = ((unsigned)r < (unsigned)CT_T && (unsigned)c < (unsigned)CT_F) ? xb[r * CT_F + c] : 0.f;
     }
-    for (int i = tid; i < 64 * 160; i += 256) s_w[i] = w1[i];
+    for (int i = tid; i < CL::N_C1; i += 256) s_w[i] = w1[i];
     __syncthreads();
     for (int co = wv; co < 64; co += 4) {
         const float bias = b1[co];
@@ -272,14 +261,14 @@ __global__ __launch_bounds__(LF_WAVES * 64) void kws_ct_bwd_lin_fwd_kernel(const
         for (int w = 0; w < LF_WAVES; ++w) a += s_part[w][s][j];
         a += bl[j];
         s_h[s][j] = a;
-        if (b0 + s < nb) hd[(size_t)(b0 + s) * 160 + j] = a;
+        if (b0 + s < nb) hd[(size_t)(b0 + s) * HD + j] = a;
     }
     __syncthreads();
     for (int i = tid; i < 32 * 128; i += LF_WAVES * 64) {
         const int s = i >> 7, j = i & 127;
         float a = bd[j];
         for (int k = 0; k < 32; ++k) a = fmaf(s_h[s][k], wd[j * 32 + k], a);
-        if (b0 + s < nb) hd[(size_t)(b0 + s) * 160 + 32 + j] = relu0(a);
+        if (b0 + s < nb) hd[(size_t)(b0 + s) * HD + CL::LIN_OUT + j] = relu0(a);
     }
 }
 
@@ -297,10 +286,10 @@ __global__ __launch_bounds__(256) void kws_ct_bwd_tail_kernel(const float* __res
     float acc[PER];
 #pragma unroll
     for (int k = 0; k < PER; ++k) acc[k] = 0.f;
-    const int b_end = min(nb, (g + 1) * TAIL_CPG);
+    const int b_end = group_end(g, TAIL_CPG, nb);
     for (int b = g * TAIL_CPG; b < b_end; ++b) {
-        if (tid < 160) {
-            const float v = hd[(size_t)b * 160 + tid];
+        if (tid < HD) {
+            const float v = hd[(size_t)b * HD + tid];
             if (tid < 32)
                 s_h[tid] = v;
             else
@@ -325,16 +314,16 @@ __global__ __launch_bounds__(256) void kws_ct_bwd_tail_kernel(const float* __res
 #pragma unroll
         for (int k = 0; k < PER; ++k) {
             const int e = tid + 256 * k;
-            if (e < 32)
+            if (e < TP_DW)
                 acc[k] += s_dh[e];
-            else if (e < 32 + 4096)
-                acc[k] = fmaf(s_dd[(e - 32) >> 5], s_h[(e - 32) & 31], acc[k]);
-            else if (e < 4256)
-                acc[k] += s_dd[e - 4128];
-            else if (e < 4256 + 128 * C)
-                acc[k] = fmaf(s_dl[(e - 4256) >> 7], s_d[(e - 4256) & 127], acc[k]);
+            else if (e < TP_DB)
+                acc[k] = fmaf(s_dd[(e - TP_DW) >> 5], s_h[(e - TP_DW) & 31], acc[k]);
+            else if (e < TP_FW)
+                acc[k] += s_dd[e - TP_DB];
+            else if (e < TP_FW + CL::DNN_OUT * C)
+                acc[k] = fmaf(s_dl[(e - TP_FW) >> 7], s_d[(e - TP_FW) & 127], acc[k]);
             else if (e < n_part)
-                acc[k] += s_dl[e - 4256 - 128 * C];
+                acc[k] += s_dl[e - TP_FW - CL::DNN_OUT * C];
         }
         __syncthreads();
     }
@@ -422,7 +411,7 @@ __global__ __launch_bounds__(512) void kws_ct_bwd_conv2_wgrad_kernel(const float
     zero16(grp[0]);
     zero16(grp[1]);
     float bgrp = 0.f;
-    const int b_end = min(nb, (g + 1) * cpg);
+    const int b_end = group_end(g, cpg, nb);
     for (int b = g * cpg; b < b_end; ++b) {
         __syncthreads();
         const float4* s1 = reinterpret_cast<const float4*>(dz2 + (size_t)b * CT_FLAT);
@@ -500,7 +489,7 @@ __global__ __launch_bounds__(512) void kws_ct_bwd_conv1_wgrad_kernel(const float
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int k = 0; k < 8; ++k) grp[i][k] = 0.f;
-    const int b_end = min(nb, (g + 1) * cpg);
+    const int b_end = group_end(g, cpg, nb);
     for (int b = g * cpg; b < b_end; ++b) {
         __syncthreads();
         const float* xb = feat + (size_t)b * (CT_T * CT_F);
@@ -560,25 +549,14 @@ __global__ __launch_bounds__(512) void kws_ct_bwd_conv1_wgrad_kernel(const float
             for (int kw = 0; kw < 8; ++kw) pg[co * 160 + kh * 8 + kw] = grp[i][kw];
         }
     }
-    if (r0 == 0) pg[64 * 160 + co] = bgrp;
+    if (r0 == 0) pg[CL::N_C1 + co] = bgrp;
 }
 
-// out (+)= sum over g < G of part[g]: runs of 32 rows summed in order, the run sums added in order.  perm_c2: the rows are conv2
-// partials ([kk][co][ci] | bias), written to the blob's [co][ci][kk] | bias.
+// out (+)= sum over g < G of part[g], in the fixed order of reduce_partials (kws_train.h).  perm_c2: the rows are conv2 partials
+// ([kk][co][ci] | bias), written to the blob's [co][ci][kk] | bias.
 __global__ __launch_bounds__(256) void kws_ct_bwd_reduce_kernel(const float* __restrict__ part, int G, int n, int perm_c2,
                                                                 float* __restrict__ out, int accumulate) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    float s = 0.f;
-    for (int g0 = 0; g0 < G; g0 += 32) {
-        const int g1 = min(G, g0 + 32);
-        float t = 0.f;
-        for (int g = g0; g < g1; ++g) t += part[(size_t)g * n + i];
-        s += t;
-    }
-    int o = i;
-    if (perm_c2 && i < W2_N) o = ((i >> 6) & 63) * 2560 + (i & 63) * 40 + (i >> 12);
-    out[o] = accumulate ? out[o] + s : s;
+    reduce_partials<true>(part, G, n, perm_c2, out, accumulate);
 }
 
 hipError_t reduce(hipStream_t s, const float* part, int G, int n, bool perm_c2, float* out, bool accumulate) {
@@ -608,65 +586,66 @@ int run(kws_ctx* c, const char* fn, const float* d_feat, int B, const float* d_d
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, set_lds_limits());
     const int C = c->tw.num_classes;
+    const CL L(C);
     const int chunk = std::min(B, MAX_CHUNK);
-    const size_t per_clip = 4 * (size_t)CT_FLAT + CT_FLAT / 4 + 160 + 32;  // yp, y2, dz2, dz1 | winners (bytes) | h, d | dh
     const int g_conv = std::min(chunk, CONV_GROUPS), g_tail = (chunk + TAIL_CPG - 1) / TAIL_CPG;
-    const size_t part_n = std::max({(size_t)g_conv * C2W_PART, (size_t)g_tail * tail_part_floats(C), (size_t)g_conv * C1W_PART});
-    // the training workspace is shared with kws_dscnn_backward_f32
-    int rc = grow_device_buffer(c, c->d_train_ws, c->train_ws_floats, (size_t)chunk * per_clip + 2 * (size_t)W2_N + part_n,
-                                fn, "workspace");
-    if (rc) return rc;
-    float* ws = c->d_train_ws;
-    auto take = [&](size_t n) {
-        float* p = ws;
-        ws += n;
-        return p;
+    float *yp, *y2, *dz2, *dz1, *hd, *dh, *w2t, *w2u, *part;
+    unsigned char* win;
+    auto carve = [&](Carver& w) {
+        yp = w.per(CT_FLAT);
+        y2 = w.per(CT_FLAT);
+        dz2 = w.per(CT_FLAT);
+        dz1 = w.per(CT_FLAT);
+        win = reinterpret_cast<unsigned char*>(w.per(CT_FLAT / 4));  // one byte per pooled position
+        hd = w.per(HD);
+        dh = w.per(CL::LIN_OUT);
+        w2t = w.flat(W2_N);
+        w2u = w.flat(W2_N);
+        part = w.flat(std::max({(size_t)g_conv * C2W_PART, (size_t)g_tail * tail_part_floats(C), (size_t)g_conv * C1W_PART}));
     };
-    float* yp = take((size_t)chunk * CT_FLAT);
-    float* y2 = take((size_t)chunk * CT_FLAT);
-    float* dz2 = take((size_t)chunk * CT_FLAT);
-    float* dz1 = take((size_t)chunk * CT_FLAT);
-    unsigned char* win = reinterpret_cast<unsigned char*>(take((size_t)chunk * CT_FLAT / 4));
-    float* hd = take((size_t)chunk * 160);
-    float* dh = take((size_t)chunk * 32);
-    float* w2t = take(W2_N);
-    float* w2u = take(W2_N);
-    float* part = take(part_n);
+    Carver need(chunk);
+    carve(need);
+    // the training workspace is shared with kws_dscnn_backward_f32
+    int rc = grow_device_buffer(c, c->d_train_ws, c->train_ws_floats, need.floats(), fn, "workspace");
+    if (rc) return rc;
+    Carver ws(chunk, c->d_train_ws);
+    carve(ws);
     const float* raw = c->ct_raw;
     hipStream_t s = c->stream;
-    hipLaunchKernelGGL(kws_ct_bwd_prep_kernel, dim3(W2_N / 256), dim3(256), 0, s, raw + O_W2, w2t, w2u);
+    hipLaunchKernelGGL(kws_ct_bwd_prep_kernel, dim3(W2_N / 256), dim3(256), 0, s, raw + L.b_w2, w2t, w2u);
     HIP_TRY(c, hipGetLastError());
     const bool debug = d_dl == nullptr;
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int nb = std::min(chunk, B - b0);
         const bool acc = b0 > 0;
-        const int cpg = (nb + CONV_GROUPS - 1) / CONV_GROUPS, G = (nb + cpg - 1) / cpg, Gt = (nb + TAIL_CPG - 1) / TAIL_CPG;
+        const auto [cpg, G] = clip_groups(nb, CONV_GROUPS);
+        const int Gt = (nb + TAIL_CPG - 1) / TAIL_CPG;
         const float* feat = d_feat + (size_t)b0 * CT_T * CT_F;
-        hipLaunchKernelGGL(kws_ct_bwd_conv1_kernel, dim3(nb), dim3(256), 0, s, feat, raw + O_W1, raw + O_B1, yp, win,
+        hipLaunchKernelGGL(kws_ct_bwd_conv1_kernel, dim3(nb), dim3(256), 0, s, feat, raw + L.b_w1, raw + L.b_b1, yp, win,
                            dbg_conv1 ? dbg_conv1 + (size_t)b0 * CH * CT_T * CT_F : nullptr, dbg_win ? dbg_win + (size_t)b0 * CT_FLAT : nullptr);
         HIP_TRY(c, hipGetLastError());
         float* y2c = debug ? dbg_conv2 + (size_t)b0 * CT_FLAT : y2;
-        hipLaunchKernelGGL(kws_ct_bwd_conv2_fwd_kernel, dim3(nb), dim3(256), CONV2_LDS, s, yp, w2t, raw + O_B2, y2c);
+        hipLaunchKernelGGL(kws_ct_bwd_conv2_fwd_kernel, dim3(nb), dim3(256), CONV2_LDS, s, yp, w2t, raw + L.b_b2, y2c);
         HIP_TRY(c, hipGetLastError());
-        float* hdc = debug ? dbg_hidden + (size_t)b0 * 160 : hd;
-        hipLaunchKernelGGL(kws_ct_bwd_lin_fwd_kernel, dim3((nb + 31) / 32), dim3(LF_WAVES * 64), 0, s, y2c, raw + O_WL, raw + O_BL,
-                           raw + O_WD, raw + O_BD, nb, hdc);
+        float* hdc = debug ? dbg_hidden + (size_t)b0 * HD : hd;
+        hipLaunchKernelGGL(kws_ct_bwd_lin_fwd_kernel, dim3((nb + 31) / 32), dim3(LF_WAVES * 64), 0, s, y2c, raw + L.b_wl, raw + L.b_bl,
+                           raw + L.b_wd, raw + L.b_bd, nb, hdc);
         HIP_TRY(c, hipGetLastError());
         if (debug) continue;
-        hipLaunchKernelGGL(kws_ct_bwd_tail_kernel, dim3(Gt), dim3(256), 0, s, hd, d_dl + (size_t)b0 * C, raw + O_WD, raw + O_WF, C, nb, dh, part);
+        hipLaunchKernelGGL(kws_ct_bwd_tail_kernel, dim3(Gt), dim3(256), 0, s, hd, d_dl + (size_t)b0 * C, raw + L.b_wd, raw + L.b_wf, C, nb, dh, part);
         HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, reduce(s, part, Gt, tail_part_floats(C), false, d_grad + O_BL, acc));
-        hipLaunchKernelGGL(kws_ct_bwd_lin_kernel, dim3((LIN_TILES + 3) / 4), dim3(256), 0, s, y2, dh, raw + O_WL, nb, acc ? 1 : 0, dz2,
-                           d_grad + O_WL);
+        HIP_TRY(c, reduce(s, part, Gt, tail_part_floats(C), false, d_grad + L.b_bl, acc));
+        hipLaunchKernelGGL(kws_ct_bwd_lin_kernel, dim3((LIN_TILES + 3) / 4), dim3(256), 0, s, y2, dh, raw + L.b_wl, nb, acc ? 1 : 0, dz2,
+                           d_grad + L.b_wl);
         HIP_TRY(c, hipGetLastError());
         hipLaunchKernelGGL(kws_ct_bwd_conv2_wgrad_kernel, dim3(10, G), dim3(512), C2W_LDS, s, dz2, yp, nb, cpg, part);
         HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, reduce(s, part, G, C2W_PART, true, d_grad + O_W2, acc));
+        HIP_TRY(c, reduce(s, part, G, C2W_PART, true, d_grad + L.b_w2, acc));
         hipLaunchKernelGGL(kws_ct_bwd_conv2_dgrad_kernel, dim3(nb), dim3(256), CONV2_LDS, s, dz2, w2u, yp, dz1);
         HIP_TRY(c, hipGetLastError());
         hipLaunchKernelGGL(kws_ct_bwd_conv1_wgrad_kernel, dim3(G), dim3(512), C1W_LDS, s, feat, dz1, win, nb, cpg, part);
         HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, reduce(s, part, G, C1W_PART, false, d_grad + O_W1, acc));
+        HIP_TRY(c, reduce(s, part, G, C1W_PART, false, d_grad + L.b_w1, acc));
     }
     return KWS_OK;
 }
@@ -682,11 +661,8 @@ extern "C" {
 int kws_cnn_trad_backward_f32(kws_ctx* c, const float* d_feat, int B, const float* d_dlogits, float* d_grad) {
     static const char* fn = "kws_cnn_trad_backward_f32";
     KWS_GUARD_BEGIN
-    if (!c) return KWS_EINVAL;
-    if (!d_feat) return fail(c, KWS_EINVAL, std::string(fn) + ": input pointer is NULL");
-    if (B <= 0) return fail(c, KWS_EINVAL, std::string(fn) + ": B must be positive");
-    if (!d_dlogits) return fail(c, KWS_EINVAL, std::string(fn) + ": d_dlogits is NULL");
-    if (!d_grad) return fail(c, KWS_EINVAL, std::string(fn) + ": d_grad is NULL");
+    int rc = check_backward_args(c, d_feat, B, d_dlogits, d_grad, fn);
+    if (rc) return rc;
     if (!c->cnntrad_ready) return fail(c, KWS_ESTATE, std::string(fn) + ": no model loaded (kws_load_cnn_trad)");
     return run(c, fn, d_feat, B, d_dlogits, d_grad, nullptr, nullptr, nullptr, nullptr);
     KWS_GUARD_END(c, "kws_cnn_trad_backward_f32")
@@ -696,9 +672,8 @@ int kws_cnn_trad_train_debug_f32(kws_ctx* c, const float* d_feat, int B, float* 
                                  float* d_hidden) {
     static const char* fn = "kws_cnn_trad_train_debug_f32";
     KWS_GUARD_BEGIN
-    if (!c) return KWS_EINVAL;
-    if (!d_feat) return fail(c, KWS_EINVAL, std::string(fn) + ": input pointer is NULL");
-    if (B <= 0) return fail(c, KWS_EINVAL, std::string(fn) + ": B must be positive");
+    int rc = check_batch(c, d_feat, B, fn);
+    if (rc) return rc;
     if (!d_conv1 || !d_winner || !d_conv2 || !d_hidden) return fail(c, KWS_EINVAL, std::string(fn) + ": an output pointer is NULL");
     if (!c->cnntrad_ready) return fail(c, KWS_ESTATE, std::string(fn) + ": no model loaded (kws_load_cnn_trad)");
     return run(c, fn, d_feat, B, nullptr, nullptr, d_conv1, d_winner, d_conv2, d_hidden);

@@ -13,8 +13,9 @@
 //                                  order; ring positions are written by the same kernel (relu(bias), no arithmetic)
 #include <algorithm>
 
+#include "kws_ctx.h"
 #include "kws_dscnn_geom.h"
-#include "kws_internal.h"
+#include "kws_pack.h"
 #include "kws_split_mfma.h"
 
 namespace kws {
@@ -273,6 +274,25 @@ hipError_t launch_dsblock(hipStream_t s, const float* d_x, int B, int C_in, int 
     hipLaunchKernelGGL(kws_dsblock_pointwise_kernel, dim3((P + TP - 1) / TP, (C_out + TC - 1) / TC, B), dim3(256), 0, s, d_ws, C_in,
                        P, d_pw_w, d_pw_b, C_out, Ho, Wo, pad, d_out);
     return hipGetLastError();
+}
+
+int check_dscnn_map(kws_ctx* c, const char* fn, int T, int F) {
+    if (T < 6 || F < 6) return fail(c, KWS_EINVAL, std::string(fn) + ": the 10 x 10 first convolution (padding 2) needs T >= 6 and F >= 6");
+    if ((size_t)(T + 4) * (F + 4) * sizeof(float) > 160 * 1024)
+        return fail(c, KWS_EUNSUPPORTED, std::string(fn) + ": the padded feature map must fit 160 KB of LDS ((T + 4) * (F + 4) <= 40960)");
+    return KWS_OK;
+}
+
+hipError_t launch_dscnn_composed(hipStream_t s, const DscnnWeights& w, const float* d_feat, int nb, int T, int F, const DscnnStages& st) {
+    const DscnnMap m(T, F);
+    const DscnnLayout L(w.num_classes, w.in_channels);
+    hipError_t e = launch_conv1_any(s, d_feat, nb, w.in_channels, T, F, w.c1_general, w.c1_b, st.a0);
+    for (int k = 0; k < N_BLOCKS && e == hipSuccess; ++k) {
+        const float* prm = w.raw + L.block(k);  // the block's parameters in state_dict order
+        e = launch_dsblock(s, k ? st.y[k - 1] : st.a0, nb, CH, m.H(k), m.W(k), prm, prm + L.B_DWB, prm + L.B_PWW, prm + L.B_PWB, CH, 3, 1,
+                           1, st.dw[k], st.y[k]);
+    }
+    return e;
 }
 
 }  // namespace kws

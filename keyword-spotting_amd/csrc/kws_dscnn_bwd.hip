@@ -23,33 +23,25 @@
 //                              on the VALU; no input gradient
 //   kws_bwd_reduce_kernel      fixed-order sum of the per-workgroup partials into d_grad
 //
-// Deterministic: no float atomics.  A chunk of n clips is split into G contiguous groups of cpg = ceil(n / 1024) clips; the
-// workgroup(s) of group g accumulate its clips in a fixed order and write one partial row, and kws_bwd_reduce_kernel sums the
-// G rows in a fixed order (chunks after the first add onto d_grad in chunk order).  G, cpg and the chunking depend on B and the map
-// only, so the same inputs and B give bit-identical gradients on every call.
+// Deterministic: no float atomics, but the clip groups of kws_train.h with at most 1024 groups per chunk (chunks after the first
+// add onto d_grad in chunk order).  G, cpg and the chunking depend on B and the map only, so the same inputs and B give
+// bit-identical gradients on every call.
 //
 // input_channels > 1 returns KWS_EUNSUPPORTED: conv1's weight gradient is written for one input channel (N = 100 taps).
 //
 // Memory is written with plain vector stores only; there is no inline assembly in this unit.
-#include <algorithm>
-#include <string>
-
-#include "kws_ctx.h"
+#include "kws_train.h"
 
 namespace kws {
 namespace {
 
-constexpr int BWD_MAX_GROUPS = 1024;  // partial rows per stage and chunk
-constexpr int PW_TP = 64;             // interior positions per tile of the pointwise backward
-constexpr int PW_PART = 64 * 64 + 64; // pointwise.weight [co][ci] | pointwise.bias
-constexpr int DW_PART = 64 * 9 + 64;  // depthwise.weight [c][3][3] | depthwise.bias
-constexpr int C1_PART = 64 * 100 + 64;// conv1.weight [co][10][10] | conv1.bias
-// Sums over the positions of a map are taken in runs of RUN terms, each started from zero and added to a running total.
-// One chain per accumulator over block 4's Q / 4 = 2772 positions per wave at 156 x 252 missed the 4x torch-f32 bound on
-// dsconv4.pointwise.bias (2.1x) and, through the pooled mean, on fc.weight (1.1x).
-constexpr int RUN = 64;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using DL = DscnnLayout;
+constexpr int BWD_MAX_GROUPS = 1024;          // partial rows per stage and chunk
+constexpr int PW_TP = 64;                     // interior positions per tile of the pointwise backward
+constexpr int PW_PART = DL::PW_W + DL::CO;    // pointwise.weight [co][ci] | pointwise.bias
+constexpr int DW_PART = DL::DW_W + DL::CO;    // depthwise.weight [c][3][3] | depthwise.bias
+constexpr int C1_PART = DL::C1_W + DL::CO;    // conv1.weight [co][10][10] | conv1.bias
+constexpr int fc_part(int C) { return C * DL::CO + C; }  // fc.weight [C][64] | fc.bias
 
 // ---- global average pool + fc ---------------------------------------------------------------------------------------------
 // One workgroup per clip group.  Per clip: pooled = mean of the block-4 output over its Q4 positions (ring included),
@@ -57,16 +49,16 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 __global__ __launch_bounds__(256) void kws_bwd_fc_kernel(const float* __restrict__ y4, const float* __restrict__ dl,
                                                          const float* __restrict__ fc_w, int Q4, int C, int nb, int cpg,
                                                          float* __restrict__ dy4, float* __restrict__ part) {
-    constexpr int PER = (64 * 64 + 64 + 255) / 256;  // partial entries per thread (C <= 64)
+    constexpr int PER = (fc_part(MAX_CLASSES) + 255) / 256;  // partial entries per thread
     __shared__ float s_sum[4][64];
     __shared__ float s_pool[64];
     __shared__ float s_dl[MAX_CLASSES];
     const int tid = threadIdx.x, c = tid & 63, q0 = tid >> 6, g = blockIdx.x;
-    const int n_part = C * 64 + C;
+    const int n_part = C * DL::CO + C;  // fc_part(C), spelled out: the call moves instructions in this kernel
     float acc[PER];
 #pragma unroll
     for (int k = 0; k < PER; ++k) acc[k] = 0.f;
-    const int b_end = min(nb, (g + 1) * cpg);
+    const int b_end = group_end(g, cpg, nb);
     for (int b = g * cpg; b < b_end; ++b) {
         const float* yp = y4 + ((size_t)b * 64 + c) * Q4;
         float s = 0.f;
@@ -119,18 +111,20 @@ __global__ __launch_bounds__(256) void kws_bwd_pointwise_kernel(const float* __r
     __shared__ float s_b[4][64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = blockIdx.x;
     const int P = H * W, Wq = W + 2, Q = (H + 2) * Wq;
-    for (int e = tid; e < 64 * 64; e += 256) s_w[e >> 6][e & 63] = w[e];
+    for (int e = tid; e < DL::PW_W; e += 256) s_w[e >> 6][e & 63] = w[e];
     __syncthreads();
     const int co0 = 32 * (wv >> 1), ci0 = 32 * (wv & 1), pt0 = 32 * (wv >> 1);
     // A operand of dX_dw = W^T dZ (32x32x2: A[i = l & 31][k = l >> 5]): A[ci][co] = W[co][ci], k-step s covers co 2s, 2s + 1
     float wa[32];
 #pragma unroll
     for (int s = 0; s < 32; ++s) wa[s] = s_w[2 * s + (lane >> 5)][ci0 + (lane & 31)];
+    // the MFMA calls, zero fills and D rows stay spelled out in this kernel: through kws_train.h's mfma32 / zero16 / drow it
+    // took 176 VGPRs for 168
     f32x16 gw;
 #pragma unroll
     for (int r = 0; r < 16; ++r) gw[r] = 0.f;
     float bsum = 0.f;
-    const int b_end = min(nb, (g + 1) * cpg);
+    const int b_end = group_end(g, cpg, nb);
     for (int b = g * cpg; b < b_end; ++b) {
         const float* dyb = dy + (size_t)b * dy_clip;
         const float* yb = y + (size_t)b * 64 * Q;
@@ -195,7 +189,7 @@ __global__ __launch_bounds__(256) void kws_bwd_pointwise_kernel(const float* __r
     for (int r = 0; r < 16; ++r) pg[(co0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 64 + ci0 + (lane & 31)] = gw[r];
     s_b[wv][lane] = bsum;
     __syncthreads();
-    if (tid < 64) pg[4096 + tid] = (s_b[0][tid] + s_b[1][tid]) + (s_b[2][tid] + s_b[3][tid]);
+    if (tid < 64) pg[DL::PW_W + tid] = (s_b[0][tid] + s_b[1][tid]) + (s_b[2][tid] + s_b[3][tid]);
 }
 
 // ---- depthwise 3x3 (padding 1, groups 64) --------------------------------------------------------------------------------
@@ -213,7 +207,7 @@ __global__ __launch_bounds__(256) void kws_bwd_depthwise_kernel(const float* __r
     for (int t = 0; t < 9; ++t) wk[t] = w[c * 9 + t];
 #pragma unroll
     for (int t = 0; t < 10; ++t) gk[t] = 0.f;
-    const int b_end = min(nb, (g + 1) * cpg);
+    const int b_end = group_end(g, cpg, nb);
     for (int b = g * cpg; b < b_end; ++b) {
         const float* dp = dxdw + ((size_t)b * 64 + c) * P;
         const float* xp = xin + ((size_t)b * 64 + c) * P;
@@ -244,7 +238,7 @@ __global__ __launch_bounds__(256) void kws_bwd_depthwise_kernel(const float* __r
         for (int l = 0; l < 64; ++l) s += s_red[wv][lane][l];
         float* pg = part + (size_t)g * DW_PART;
         if (lane < 9) pg[c * 9 + lane] = s;
-        else pg[576 + c] = s;
+        else pg[DL::DW_W + c] = s;
     }
 }
 
@@ -266,7 +260,7 @@ __global__ __launch_bounds__(256) void kws_bwd_conv1_kernel(const float* __restr
 #pragma unroll
         for (int k = 0; k < 10; ++k) acc[i][k] = 0.f;
     float bsum = 0.f;
-    const int b_end = min(nb, (g + 1) * cpg);
+    const int b_end = group_end(g, cpg, nb);
     for (int b = g * cpg; b < b_end; ++b) {
         const float* dab = da + (size_t)b * 64 * P;
         const float* ab = a + (size_t)b * 64 * P;
@@ -307,28 +301,18 @@ __global__ __launch_bounds__(256) void kws_bwd_conv1_kernel(const float* __restr
         const int kh = r0 + 4 * i;
         if (kh < 10) {
 #pragma unroll
-            for (int kw = 0; kw < 10; ++kw) pg[co * 100 + kh * 10 + kw] = acc[i][kw];
+            for (int kw = 0; kw < 10; ++kw) pg[co * DL::C1_TAPS + kh * 10 + kw] = acc[i][kw];
         }
     }
     s_b[r0][co] = bsum;
     __syncthreads();
-    if (tid < 64) pg[6400 + tid] = s_b[0][tid];
+    if (tid < 64) pg[DL::C1_W + tid] = s_b[0][tid];
 }
 
-// out[i] (+)= sum over g = 0 .. G-1 of part[g][i]: runs of 32 rows summed in order, the run sums added in order (chains of
-// at most 32 + 32 additions at G = 1024)
+// out[i] (+)= sum over g = 0 .. G-1 of part[g][i], in the fixed order of reduce_partials (kws_train.h)
 __global__ __launch_bounds__(256) void kws_bwd_reduce_kernel(const float* __restrict__ part, int G, int n, float* __restrict__ out,
                                                              int accumulate) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    float s = 0.f;
-    for (int g0 = 0; g0 < G; g0 += 32) {
-        const int g1 = min(G, g0 + 32);
-        float t = 0.f;
-        for (int g = g0; g < g1; ++g) t += part[(size_t)g * n + i];
-        s += t;
-    }
-    out[i] = accumulate ? out[i] + s : s;
+    reduce_partials<false>(part, G, n, 0, out, accumulate);
 }
 
 hipError_t reduce(hipStream_t s, const float* part, int G, int n, float* out, bool accumulate) {
@@ -347,89 +331,73 @@ extern "C" {
 int kws_dscnn_backward_f32(kws_ctx* c, const float* d_feat, int B, int T, int F, const float* d_dlogits, float* d_grad) {
     static const char* fn = "kws_dscnn_backward_f32";
     KWS_GUARD_BEGIN
-    if (!c) return KWS_EINVAL;
-    if (!d_feat) return fail(c, KWS_EINVAL, std::string(fn) + ": input pointer is NULL");
-    if (B <= 0) return fail(c, KWS_EINVAL, std::string(fn) + ": B must be positive");
-    if (!d_dlogits) return fail(c, KWS_EINVAL, std::string(fn) + ": d_dlogits is NULL");
-    if (!d_grad) return fail(c, KWS_EINVAL, std::string(fn) + ": d_grad is NULL");
+    int rc = check_backward_args(c, d_feat, B, d_dlogits, d_grad, fn);
+    if (rc) return rc;
     if (!c->model_ready) return fail(c, KWS_ESTATE, std::string(fn) + ": no model loaded (kws_load_dscnn)");
     if (c->mw.in_channels != 1)
         return fail(c, KWS_EUNSUPPORTED, std::string(fn) + ": the backward is implemented for input_channels == 1 only");
-    if (T < 6 || F < 6) return fail(c, KWS_EINVAL, std::string(fn) + ": the 10 x 10 first convolution (padding 2) needs T >= 6 and F >= 6");
-    if ((size_t)(T + 4) * (F + 4) * sizeof(float) > 160 * 1024)
-        return fail(c, KWS_EUNSUPPORTED, std::string(fn) + ": the padded feature map must fit 160 KB of LDS ((T + 4) * (F + 4) <= 40960)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int C = c->mw.num_classes;
-    const int H1 = (T - 6) / 2 + 1, W1 = (F - 6) / 2 + 1, P0 = H1 * W1;
-    int Pk[N_BLOCKS], Qk[N_BLOCKS];  // block k: input / depthwise positions, output positions (ring included)
-    size_t per_clip = (size_t)CH * P0 + CH;  // conv1 output, dY4
-    for (int k = 0; k < N_BLOCKS; ++k) {
-        Pk[k] = (H1 + 2 * k) * (W1 + 2 * k);
-        Qk[k] = (H1 + 2 * k + 2) * (W1 + 2 * k + 2);
-        per_clip += (size_t)CH * (Pk[k] + Qk[k]);
-    }
-    per_clip += 2 * (size_t)CH * Pk[N_BLOCKS - 1];  // gradient of a block input, of a depthwise output
-    // clip chunks: at most 16384 clips (as kws_forward_map_f32) and at most 2^31 floats of activations and gradients
-    const size_t by_budget = std::max<size_t>(1, ((size_t)1 << 31) / per_clip);
-    const int chunk = (int)std::min<size_t>({(size_t)B, 16384, by_budget});
-    const int g_max = std::min(chunk, BWD_MAX_GROUPS);  // partial rows: G = ceil(nb / ceil(nb / 1024)) <= min(nb, 1024)
-    int rc = grow_device_buffer(c, c->d_train_ws, c->train_ws_floats, (size_t)chunk * per_clip + (size_t)g_max * C1_PART,
-                                fn, "workspace");
+    rc = check_dscnn_map(c, fn, T, F);
     if (rc) return rc;
-    float* ws = c->d_train_ws;
-    float* a0 = ws;
-    ws += (size_t)chunk * CH * P0;
-    float *xdw[N_BLOCKS], *yk[N_BLOCKS];
-    for (int k = 0; k < N_BLOCKS; ++k) {
-        xdw[k] = ws;
-        ws += (size_t)chunk * CH * Pk[k];
-        yk[k] = ws;
-        ws += (size_t)chunk * CH * Qk[k];
-    }
-    float* gin = ws;  // dloss / d(block input) = dloss / d(previous block's output, or conv1's)
-    ws += (size_t)chunk * CH * Pk[N_BLOCKS - 1];
-    float* gdw = ws;  // dloss / d(depthwise output)
-    ws += (size_t)chunk * CH * Pk[N_BLOCKS - 1];
-    float* dy4 = ws;
-    ws += (size_t)chunk * CH;
-    float* part = ws;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int C = c->mw.num_classes, LAST = N_BLOCKS - 1;
+    const DscnnMap m(T, F);
+    const DL L(C, 1);
+    DscnnStages st;
+    float *gin, *gdw, *dy4, *part;
+    auto carve = [&](Carver& w) {
+        st.a0 = w.per(CH * m.P(0));
+        for (int k = 0; k < N_BLOCKS; ++k) {
+            st.dw[k] = w.per(CH * m.P(k));
+            st.y[k] = w.per(CH * m.Q(k));
+        }
+        gin = w.per(CH * m.P(LAST));  // dloss / d(block input) = dloss / d(previous block's output, or conv1's)
+        gdw = w.per(CH * m.P(LAST));  // dloss / d(depthwise output)
+        dy4 = w.per(CH);
+        // partial rows: G = ceil(nb / ceil(nb / 1024)) <= min(nb, 1024), the widest row is conv1's
+        part = w.flat(std::min<size_t>(w.clips, BWD_MAX_GROUPS) * C1_PART);
+    };
+    Carver per_clip(0);
+    carve(per_clip);
+    // clip chunks: at most as many clips as the composed forward takes and at most 2^31 floats of activations and gradients
+    const size_t by_budget = std::max<size_t>(1, ((size_t)1 << 31) / per_clip.per_clip);
+    const int chunk = (int)std::min<size_t>({(size_t)B, COMPOSED_MAX_CLIPS, by_budget});
+    Carver need(chunk);
+    carve(need);
+    rc = grow_device_buffer(c, c->d_train_ws, c->train_ws_floats, need.floats(), fn, "workspace");
+    if (rc) return rc;
+    Carver ws(chunk, c->d_train_ws);
+    carve(ws);
     const float* raw = c->mw.raw;
-    const size_t o_blk = 6400 + 64, blk_floats = 576 + 64 + 4096 + 64, o_fc = o_blk + N_BLOCKS * blk_floats;
     hipStream_t s = c->stream;
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int nb = std::min(chunk, B - b0);
-        const int cpg = (nb + BWD_MAX_GROUPS - 1) / BWD_MAX_GROUPS, G = (nb + cpg - 1) / cpg;
+        const auto [cpg, G] = clip_groups(nb, BWD_MAX_GROUPS);
         const bool acc = b0 > 0;
         const float* feat = d_feat + (size_t)b0 * T * F;
         // recompute: the composed forward of kws_forward_map_f32, every stage kept
-        HIP_TRY(c, launch_conv1_any(s, feat, nb, 1, T, F, c->mw.c1_general, c->mw.c1_b, a0));
-        for (int k = 0; k < N_BLOCKS; ++k) {
-            const float* prm = raw + o_blk + (size_t)k * blk_floats;
-            HIP_TRY(c, launch_dsblock(s, k ? yk[k - 1] : a0, nb, CH, H1 + 2 * k, W1 + 2 * k, prm, prm + 576, prm + 640, prm + 640 + 4096,
-                                      CH, 3, 1, 1, xdw[k], yk[k]));
-        }
+        HIP_TRY(c, launch_dscnn_composed(s, c->mw, feat, nb, T, F, st));
         // pool + fc
-        hipLaunchKernelGGL(kws_bwd_fc_kernel, dim3(G), dim3(256), 0, s, yk[N_BLOCKS - 1], d_dlogits + (size_t)b0 * C, raw + o_fc,
-                           Qk[N_BLOCKS - 1], C, nb, cpg, dy4, part);
+        hipLaunchKernelGGL(kws_bwd_fc_kernel, dim3(G), dim3(256), 0, s, st.y[LAST], d_dlogits + (size_t)b0 * C, raw + L.b_fcw,
+                           (int)m.Q(LAST), C, nb, cpg, dy4, part);
         HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, reduce(s, part, G, C * 64 + C, d_grad + o_fc, acc));
+        HIP_TRY(c, reduce(s, part, G, fc_part(C), d_grad + L.b_fcw, acc));
         // blocks 4 .. 1
-        for (int k = N_BLOCKS - 1; k >= 0; --k) {
-            const float* prm = raw + o_blk + (size_t)k * blk_floats;
-            float* gk = d_grad + o_blk + (size_t)k * blk_floats;
-            const int H = H1 + 2 * k, W = W1 + 2 * k;
-            const bool last = k == N_BLOCKS - 1;
-            hipLaunchKernelGGL(kws_bwd_pointwise_kernel, dim3(G), dim3(256), 0, s, last ? dy4 : gin, last ? (long)CH : (long)CH * Qk[k],
-                               last ? 1 : Qk[k], last ? 0 : 1, yk[k], xdw[k], prm + 640, H, W, nb, cpg, gdw, part);
+        for (int k = LAST; k >= 0; --k) {
+            const float* prm = raw + L.block(k);
+            float* gk = d_grad + L.block(k);
+            const int Q = (int)m.Q(k);
+            const bool last = k == LAST;
+            hipLaunchKernelGGL(kws_bwd_pointwise_kernel, dim3(G), dim3(256), 0, s, last ? dy4 : gin, last ? (long)CH : (long)CH * Q,
+                               last ? 1 : Q, last ? 0 : 1, st.y[k], st.dw[k], prm + DL::B_PWW, m.H(k), m.W(k), nb, cpg, gdw, part);
             HIP_TRY(c, hipGetLastError());
-            HIP_TRY(c, reduce(s, part, G, PW_PART, gk + 640, acc));
-            hipLaunchKernelGGL(kws_bwd_depthwise_kernel, dim3(CH / 4, G), dim3(256), 0, s, gdw, k ? yk[k - 1] : a0, prm, H, W, nb, cpg,
-                               gin, part);
+            HIP_TRY(c, reduce(s, part, G, PW_PART, gk + DL::B_PWW, acc));
+            hipLaunchKernelGGL(kws_bwd_depthwise_kernel, dim3(CH / 4, G), dim3(256), 0, s, gdw, k ? st.y[k - 1] : st.a0, prm, m.H(k), m.W(k),
+                               nb, cpg, gin, part);
             HIP_TRY(c, hipGetLastError());
             HIP_TRY(c, reduce(s, part, G, DW_PART, gk, acc));
         }
         // conv1
-        hipLaunchKernelGGL(kws_bwd_conv1_kernel, dim3(G), dim3(256), 0, s, gin, a0, feat, T, F, H1, W1, nb, cpg, part);
+        hipLaunchKernelGGL(kws_bwd_conv1_kernel, dim3(G), dim3(256), 0, s, gin, st.a0, feat, T, F, m.H1, m.W1, nb, cpg, part);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, reduce(s, part, G, C1_PART, d_grad, acc));
     }

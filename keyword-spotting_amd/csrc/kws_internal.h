@@ -272,6 +272,28 @@ hipError_t launch_conv1_any(hipStream_t s, const float* d_x, int B, int C_in, in
                             float* d_out);
 hipError_t launch_pool_fc(hipStream_t s, const float* d_x, int B, int HW, const float* d_fc_w, const float* d_fc_b, int C,
                           float* d_logits, int32_t* d_label);
+// The composed path's geometry on a T x F map: conv1's output is H1 x W1; block k (0-based) takes H(k) x W(k) = P(k) positions,
+// its depthwise output has as many, its pointwise output (the relu(bias) ring included) is the next block's input.
+struct DscnnMap {
+    int H1, W1;
+    DscnnMap(int T, int F) : H1((T - 6) / 2 + 1), W1((F - 6) / 2 + 1) {}
+    int H(int k) const { return H1 + 2 * k; }
+    int W(int k) const { return W1 + 2 * k; }
+    size_t P(int k) const { return (size_t)H(k) * W(k); }
+    size_t Q(int k) const { return P(k + 1); }  // block k's output positions
+};
+// The maps the composed path accepts (forward and backward alike); the error is set on c and returned, KWS_OK otherwise.
+int check_dscnn_map(kws_ctx* c, const char* fn, int T, int F);
+// Where the stages of nb clips go, each [nb][64][positions]: conv1's output, and per block its depthwise and its pointwise output.
+// Stages may share memory as far as the data flow allows (a0 -> dw[0] -> y[0] -> dw[1] -> ...).
+struct DscnnStages {
+    float* a0;
+    float* dw[N_BLOCKS];
+    float* y[N_BLOCKS];
+};
+// conv1 + the four depthwise-separable blocks of nb <= 16384 clips (grid.z of the pointwise kernel), at the weights of the blob w.raw.
+hipError_t launch_dscnn_composed(hipStream_t s, const DscnnWeights& w, const float* d_feat, int nb, int T, int F, const DscnnStages& st);
+constexpr int COMPOSED_MAX_CLIPS = 16384;
 
 // The decision layer (kws_decide.hip): posteriors, their moving average per stream, and further down the energy endpointer.
 hipError_t launch_softmax(hipStream_t s, const float* d_logits, int B, int C, float* d_prob);

@@ -61,21 +61,24 @@ __host__ __device__ inline float pow2_scale_of_max(float m) {
 // pw_b [4][64] | fc_w | fc_b | the bf16-triple fragments of the pointwise layers and of conv1 (16-byte aligned) | conv1 as
 // [ci][tap][cout] | the blob itself | the f16-pair fragments (16-byte aligned).
 struct DscnnLayout {
-    static constexpr size_t BLK = 576 + 64 + 4096 + 64, B_DWB = 576, B_PWW = 640, B_PWB = 640 + 4096;  // a block and its tensors
+    // tensor sizes the kernels need at compile time: channels, conv1.weight per input channel, a depthwise and a pointwise weight
+    static constexpr int CO = 64, C1_TAPS = 100, C1_W = CO * C1_TAPS, DW_W = CO * 9, PW_W = CO * CO;
+    static constexpr size_t B_DWB = DW_W, B_PWW = B_DWB + CO, B_PWB = B_PWW + PW_W, BLK = B_PWB + CO;  // a block and its tensors
     // 8-value fragments: pointwise [b 4][ct 2][m 4][lane], then (one input channel only) conv1 [ct 2][kb 7][lane]
     static constexpr size_t F_PW = 4 * 2 * 4 * 64, F_C1 = 2 * 7 * 64;
     size_t c1_floats, n_floats, b_blk, b_fcw, b_fcb, n_frag;
     size_t o_c1w, o_c1b, o_dw, o_pww, o_pwb, o_fcw, o_fcb, o_split, o_c1s, o_c1g, o_raw, o_pwp, o_c1p, total;
     int num_classes, in_channels;
     __host__ __device__ DscnnLayout(int num_classes_, int input_channels) : num_classes(num_classes_), in_channels(input_channels) {
-        c1_floats = (size_t)6400 * input_channels;
-        b_blk = c1_floats + 64, b_fcw = b_blk + 4 * BLK, b_fcb = b_fcw + (size_t)num_classes * 64, n_floats = b_fcb + num_classes;
+        c1_floats = (size_t)C1_W * input_channels;
+        b_blk = c1_floats + CO, b_fcw = b_blk + 4 * BLK, b_fcb = b_fcw + (size_t)num_classes * 64, n_floats = b_fcb + num_classes;
         n_frag = F_PW + (input_channels == 1 ? F_C1 : 0);
         o_c1w = 0, o_c1b = o_c1w + 6400, o_dw = o_c1b + 64, o_pww = o_dw + 4 * 64 * 12, o_pwb = o_pww + 4 * 4096, o_fcw = o_pwb + 4 * 64,
         o_fcb = o_fcw + (size_t)num_classes * 64, o_split = (o_fcb + num_classes + 3) & ~(size_t)3, o_c1s = o_split + F_PW * 3 * 4,
         o_c1g = o_c1s + F_C1 * 3 * 4, o_raw = o_c1g + c1_floats, o_pwp = (o_raw + n_floats + 3) & ~(size_t)3,
         o_c1p = o_pwp + F_PW * 2 * 4, total = o_c1p + F_C1 * 2 * 4;
     }
+    __host__ __device__ size_t block(int k) const { return b_blk + (size_t)k * BLK; }  // blob offset of block k (0-based)
 };
 
 // The layers' power-of-two weight scales of the f16-pair images (pow2_scale_of_max of max|w|): conv1, the four pointwise layers.
@@ -121,15 +124,17 @@ __host__ __device__ inline void ds_pack_fragment(const DscnnLayout& L, const flo
 // 16-byte aligned), then the blob itself as float32 (16-byte aligned; the weights of kws_cnn_trad_backward_f32).
 struct CtLayout {
     static constexpr size_t CO = 64, FLAT = 64 * 297;  // conv channels; inputs of the first dense layer
+    // tensor sizes the kernels need at compile time: conv1.weight, conv2.weight, outputs of lin and dnn, dnn.weight
+    static constexpr int N_C1 = 64 * 160, N_C2 = 64 * 64 * 40, LIN_OUT = 32, DNN_OUT = 128, N_DNN = DNN_OUT * LIN_OUT;
     // 8-value fragments per GEMM layer: conv1 [kb 10][ct 2][lane], conv2 [kk 40][cb 4][ct 2][lane], lin [kb FLAT/16][lane]
     static constexpr size_t F_C1 = 10 * 2 * 64, F_C2 = 40 * 4 * 2 * 64, F_LIN = FLAT / 16 * 64, N_FRAG = F_C1 + F_C2 + F_LIN;
     size_t n_c1, n_c2, n_lin, n_dnn, n_fc, n_floats;
     size_t b_w1, b_b1, b_w2, b_b2, b_wl, b_bl, b_wd, b_bd, b_wf, b_bf;
     size_t o_c1s, o_c2s, o_c1b, o_c2b, o_lin, o_linb, o_dnn, o_dnnb, o_fc, o_fcb, o_c1h, o_c2h, o_linh, o_raw, total;
     __host__ __device__ explicit CtLayout(int num_classes) {
-        n_c1 = CO * 160, n_c2 = CO * 64 * 40, n_lin = 32 * FLAT, n_dnn = 128 * 32, n_fc = (size_t)num_classes * 128;
-        b_w1 = 0, b_b1 = b_w1 + n_c1, b_w2 = b_b1 + CO, b_b2 = b_w2 + n_c2, b_wl = b_b2 + CO, b_bl = b_wl + n_lin, b_wd = b_bl + 32,
-        b_bd = b_wd + n_dnn, b_wf = b_bd + 128, b_bf = b_wf + n_fc, n_floats = b_bf + num_classes;
+        n_c1 = N_C1, n_c2 = N_C2, n_lin = LIN_OUT * FLAT, n_dnn = N_DNN, n_fc = (size_t)num_classes * DNN_OUT;
+        b_w1 = 0, b_b1 = b_w1 + n_c1, b_w2 = b_b1 + CO, b_b2 = b_w2 + n_c2, b_wl = b_b2 + CO, b_bl = b_wl + n_lin, b_wd = b_bl + LIN_OUT,
+        b_bd = b_wd + n_dnn, b_wf = b_bd + DNN_OUT, b_bf = b_wf + n_fc, n_floats = b_bf + num_classes;
         o_c1s = 0, o_c2s = o_c1s + F_C1 * 3 * 4, o_c1b = o_c2s + F_C2 * 3 * 4, o_c2b = o_c1b + CO, o_lin = o_c2b + CO,
         o_linb = o_lin + F_LIN * 3 * 4, o_dnn = o_linb + 32, o_dnnb = o_dnn + n_dnn, o_fc = o_dnnb + 128, o_fcb = o_fc + n_fc,
         o_c1h = (o_fcb + num_classes + 3) / 4 * 4, o_c2h = o_c1h + F_C1 * 2 * 4, o_linh = o_c2h + F_C2 * 2 * 4,

@@ -8,7 +8,7 @@ names, shapes and initialisation, so reference checkpoints (bare ``state_dict`` 
 ``forward`` is ``kws_forward_f32`` (include/kws_hip.h): LDS-resident activations, depthwise 3x3 on the
 VALU, pointwise 1x1 and conv1 on the matrix cores.  ``DepthwiseSeparableConv`` also trains: after ``model.train()`` (which
 the reference trainers call every epoch), with grad mode on and a parameter that requires grad, its forward is a
-``torch.autograd.Function`` whose backward is ``kws_dscnn_backward_f32``, so the trainer's ``loss.backward()`` /
+``torch.autograd.Function`` (``_NativeTrainFunction``) whose backward is ``kws_dscnn_backward_f32``, so the trainer's ``loss.backward()`` /
 ``optimizer.step()`` work unchanged.  ``CnnTradFpool3`` trains the same way (``kws_cnn_trad_backward_f32``); the other models
 are inference only.
 """
@@ -107,35 +107,65 @@ class DepthwiseSeparableConvBlock(nn.Module):
         return out
 
 
-class DepthwiseSeparableConv(KeywordSpottingModel):
-    """DS-CNN: conv1 (1->64, 10x10, s2, p2) + 4 depthwise-separable blocks + global pool + Linear.
+def split_flat_grad(grad: torch.Tensor, params):
+    """The flat gradient of a backward entry (``state_dict`` order) as one piece per parameter: shaped like the parameter, on its
+    device and of its dtype.  ``grad`` is copied once per device."""
+    on_dev = {}
+    out, off = [], 0
+    for p in params:
+        if p.device not in on_dev:
+            on_dev[p.device] = grad.to(p.device)
+        out.append(on_dev[p.device][off:off + p.numel()].view(p.shape).to(p.dtype))
+        off += p.numel()
+    return out
 
-    Trainable: after an explicit ``model.train()`` (the reference trainers call it at the start of every epoch,
-    ``kws/libs/training.py:275``, ``train.py:32``), when ``torch.is_grad_enabled()`` and some parameter requires grad,
-    ``forward`` runs through ``_DscnnTrainFunction`` -- the same forward kernels (logits and labels are bit-identical to a call under
-    ``torch.no_grad()``) with a backward that recomputes the activations and computes all 20 parameter gradients in HIP
-    (``kws_dscnn_backward_f32``, fp32, deterministic).  Each gradient lands on its parameter's device.  No gradient with
-    respect to the input features is provided (an input that requires grad raises ``ModelError`` in backward), and
-    ``input_channels > 1`` cannot be trained (backward raises ``ModelError``).  Otherwise -- a model never switched with
-    ``train()``, or switched back with ``eval()``, ``torch.no_grad()``, frozen parameters -- no autograd graph is built and
-    the logits are plain tensors, as for inference."""
 
-    # the parameter refresh of ``_context`` for parameters on the GPU: True = on the device (``kws_load_dscnn_device``), False =
-    # through the host as for CPU-resident parameters (an instance sets it to compare the two routes)
+class _NativeTrainFunction(torch.autograd.Function):
+    """The forward of a ``_TrainableNative`` model with a HIP backward.  Forward: exactly the inference call; the input and
+    the parameters are saved with ``save_for_backward``, so torch's version counter rejects a parameter modified in place between
+    forward and backward.  Backward: the model's backward entry at the saved parameters -- the weights the forward saw, also when a
+    module attribute was replaced by a new ``nn.Parameter`` in between (a new one bumps no version of the saved one; uploaded only
+    if they are not the device copy, so no re-upload in a normal step), the flat gradient split by ``split_flat_grad``."""
+
+    @staticmethod
+    def forward(fctx, model, x, *params):
+        logits, labels = model._forward_native(x)
+        fctx.model = model
+        fctx.save_for_backward(x, *params)
+        fctx.mark_non_differentiable(labels)
+        return logits, labels
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, dlogits, _dlabels):
+        x, *params = fctx.saved_tensors
+        model = fctx.model
+        if fctx.needs_input_grad[1]:
+            raise ModelError(f"{model._name}: the gradient with respect to the input features is not provided "
+                             f"({model._backward_entry} computes parameter gradients only); detach the input")
+        ctx = model._context(x.device.index or 0, params)
+        x = x.detach().to(torch.float32).contiguous()
+        dl = dlogits.detach().to(x.device, torch.float32).contiguous()
+        grad = torch.empty(sum(p.numel() for p in params), dtype=torch.float32, device=x.device)
+        model._native_backward(ctx, x, dl, grad)
+        return (None, None, *split_flat_grad(grad, params))
+
+
+class _TrainableNative(KeywordSpottingModel):
+    """A model whose forward and backward are HIP entries of a ``_native.Context``: the context with its parameter refresh, the
+    switch between the plain forward and ``_NativeTrainFunction``, the output tensors and the checks of ``infer_pcm16``.  A model
+    supplies ``_name``, ``_backward_entry``, ``_pcm16_is`` and the hooks ``_check_features``, ``_load_host``, ``_load_device``,
+    ``_native_forward``, ``_native_backward``, ``_native_infer_i16``."""
+
+    _name = ""            # the class name in messages
+    _backward_entry = ""  # the C entry behind loss.backward()
+    _pcm16_is = "the forward is a HIP kernel"  # what infer_pcm16 tells a CPU tensor it is
+    # the parameter refresh of ``_context`` for parameters on the GPU: True = on the device (``kws_load_*_device``), False =
+    # through the host as for CPU-resident parameters (an instance of ``DepthwiseSeparableConv`` sets it to compare the routes)
     _device_refresh = True
 
-    def __init__(self, num_classes: int = 12, input_channels: int = 1):
+    def __init__(self, num_classes: int):
         super().__init__(num_classes)
-        if not 1 <= input_channels <= 64:
-            raise ModelError("input_channels must be in [1, 64]")
-        self.input_channels = int(input_channels)
-        self.conv1 = nn.Conv2d(input_channels, 64, kernel_size=10, stride=2, padding=2)
-        self.dsconv1 = DepthwiseSeparableConvBlock(64, 64)
-        self.dsconv2 = DepthwiseSeparableConvBlock(64, 64)
-        self.dsconv3 = DepthwiseSeparableConvBlock(64, 64)
-        self.dsconv4 = DepthwiseSeparableConvBlock(64, 64)
-        self.fc = nn.Linear(64, num_classes)
-        self._initialize_weights()
         self._ctx = None
         self._uploaded = None  # fingerprint of the parameters currently on the device
         self._autograd = False  # set by an explicit train(), cleared by eval() / train(False)
@@ -147,21 +177,9 @@ class DepthwiseSeparableConv(KeywordSpottingModel):
         self._autograd = bool(mode)
         return self
 
-    def _initialize_weights(self):
-        # same scheme as the reference (:149-158)
-        for m in self.modules():
-            if isinstance(m, nn.Conv2d):
-                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
-                if m.bias is not None:
-                    nn.init.constant_(m.bias, 0)
-            elif isinstance(m, nn.Linear):
-                nn.init.normal_(m.weight, 0, 0.01)
-                nn.init.constant_(m.bias, 0)
-
-    # ------------------------------------------------------------------ device plumbing
     def packed_weights(self) -> np.ndarray:
-        """The 20 ``state_dict`` tensors, in order, as one float32 vector (``kws_load_dscnn`` layout): concatenated on the
-        parameters' device and copied to the host once.  (The refresh after an optimizer step uses it only on the host route:
+        """The ``state_dict`` tensors, in order, as one float32 vector (the layout of the model's host load): concatenated on
+        the parameters' device and copied to the host once.  (The refresh after an optimizer step uses it only on the host route:
         parameters on the GPU are re-loaded there, see ``_context``.)"""
         return self._pack(self.state_dict().values())
 
@@ -182,8 +200,8 @@ class DepthwiseSeparableConv(KeywordSpottingModel):
     def _context(self, device_index: int, params=None):
         """The model's context on ``device_index`` holding ``params`` (default: the current parameters, in ``parameters()``
         order); uploaded only when they differ from the tensors (and versions) uploaded last.  Parameters that all live on
-        that GPU are concatenated there and loaded with ``kws_load_dscnn_device`` (``_device_refresh``); otherwise through
-        the host."""
+        that GPU are concatenated there and loaded by the model's device load (``_device_refresh``); otherwise through the
+        host."""
         from kws import _native
 
         if self._ctx is None or self._ctx.device != device_index:
@@ -195,29 +213,26 @@ class DepthwiseSeparableConv(KeywordSpottingModel):
             dev = torch.device("cuda", device_index)
             if self._device_refresh and all(p.device == dev for p in params):
                 self._ctx.use_torch_stream()
-                blob = torch.cat([p.detach().to(torch.float32).reshape(-1) for p in params])
-                self._ctx.load_dscnn_device(blob, self.num_classes, self.input_channels)
+                self._load_device(self._ctx, torch.cat([p.detach().to(torch.float32).reshape(-1) for p in params]))
             else:
-                self._ctx.load_dscnn(self._pack(params), self.num_classes, self.input_channels)
+                self._load_host(self._ctx, self._pack(params))
             self._uploaded = fp
         self._ctx.use_torch_stream()
         return self._ctx
 
-    def _check_input(self, x: torch.Tensor, what: str):
-        if not x.is_cuda:
-            raise ModelError(f"{what} needs a CUDA/ROCm tensor: the forward is a HIP kernel and has no CPU fallback")
+    def _outputs(self, like: torch.Tensor):
+        return (torch.empty((like.shape[0], self.num_classes), dtype=torch.float32, device=like.device),
+                torch.empty((like.shape[0],), dtype=torch.int32, device=like.device))
 
     def forward(self, x: torch.Tensor, return_labels: bool = False):
-        """``float32[B,C,T,F]`` on the GPU -> logits ``float32[B,num_classes]`` (and argmax labels).  Any ``T x F`` the
-        reference's forward accepts (``models.py:160-183``: the pooling is adaptive): 99 x 10 runs the fused LDS-resident
-        kernel, any other map the composed path (``kws_forward_map_f32``).  After ``train()``, under grad mode with
-        trainable parameters, the logits carry a ``grad_fn`` (see the class docstring)."""
-        self._check_input(x, "DepthwiseSeparableConv.forward")
-        if x.dim() != 4 or x.shape[1] != self.input_channels:
-            raise ModelError(f"expected input [B,{self.input_channels},T,F], got {tuple(x.shape)}")
+        """``float32[B,C,T,F]`` on the GPU -> logits ``float32[B,num_classes]`` (and argmax labels).  After ``train()``, under
+        grad mode with trainable parameters, the logits carry a ``grad_fn`` (see the class docstring)."""
+        if not x.is_cuda:
+            raise ModelError(f"{self._name}.forward needs a CUDA/ROCm tensor: the forward is a HIP kernel and has no CPU fallback")
+        self._check_features(x)
         params = tuple(self.parameters())
         if self._autograd and torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            logits, labels = _DscnnTrainFunction.apply(self, x, *params)
+            logits, labels = _NativeTrainFunction.apply(self, x, *params)
         else:
             logits, labels = self._forward_native(x)
         return (logits, labels) if return_labels else logits
@@ -226,69 +241,96 @@ class DepthwiseSeparableConv(KeywordSpottingModel):
         """The forward kernels on ``x`` (checked by the caller) -> (logits, labels); no autograd graph."""
         ctx = self._context(x.device.index or 0)
         x = x.detach().to(torch.float32).contiguous()
-        logits = torch.empty((x.shape[0], self.num_classes), dtype=torch.float32, device=x.device)
-        labels = torch.empty((x.shape[0],), dtype=torch.int32, device=x.device)
-        if tuple(x.shape[2:]) == FEATURE_SHAPE[1:]:
-            ctx.forward_f32(x, logits, labels)
-        else:
-            ctx.forward_map_f32(x, logits, labels)
+        logits, labels = self._outputs(x)
+        self._native_forward(ctx, x, logits, labels)
         return logits, labels
 
+    def _check_pcm16(self):
+        pass
+
     def infer_pcm16(self, wav: torch.Tensor):
-        """Fused path: ``int16[B,16000]`` PCM on the GPU -> (logits, labels); MFCC + DS-CNN back to back
-        on one stream, features never leave the device (``kws_infer_i16``)."""
-        self._check_input(wav, "DepthwiseSeparableConv.infer_pcm16")
-        if self.input_channels != 1:
-            raise ModelError("infer_pcm16 needs input_channels=1: the MFCC front end yields one channel")
+        """Fused path: ``int16[B,16000]`` PCM on the GPU -> (logits, labels); MFCC + the model back to back on one stream,
+        features never leave the device (``kws_infer_i16`` / ``kws_infer_cnn_trad_i16``)."""
+        if not wav.is_cuda:
+            raise ModelError(f"{self._name}.infer_pcm16 needs a CUDA/ROCm tensor: {self._pcm16_is} and has no CPU fallback")
+        self._check_pcm16()
         if wav.dtype != torch.int16 or wav.dim() != 2:
             raise ModelError("infer_pcm16 expects an int16 tensor [B, n_samples]")
         ctx = self._context(wav.device.index or 0)
         wav = wav.contiguous()
-        logits = torch.empty((wav.shape[0], self.num_classes), dtype=torch.float32, device=wav.device)
-        labels = torch.empty((wav.shape[0],), dtype=torch.int32, device=wav.device)
-        ctx.infer_i16(wav, logits, labels)
+        logits, labels = self._outputs(wav)
+        self._native_infer_i16(ctx, wav, logits, labels)
         return logits, labels
 
 
-class _DscnnTrainFunction(torch.autograd.Function):
-    """``DepthwiseSeparableConv.forward`` with a HIP backward.  Forward: exactly the inference call (the fused kernel at
-    99 x 10, the composed path otherwise); the input and the parameters are saved with ``save_for_backward``, so torch's
-    version counter rejects a parameter modified in place between forward and backward.  Backward:
-    ``kws_dscnn_backward_f32`` at the saved parameters -- the weights the forward saw, also when a module attribute was
-    replaced by a new ``nn.Parameter`` in between (uploaded only if they are not the device copy), the flat gradient split into
-    views shaped like the parameters and moved to each parameter's device."""
+class DepthwiseSeparableConv(_TrainableNative):
+    """DS-CNN: conv1 (1->64, 10x10, s2, p2) + 4 depthwise-separable blocks + global pool + Linear.  ``forward`` takes any
+    ``T x F`` the reference's accepts (``models.py:160-183``: the pooling is adaptive): 99 x 10 runs the fused LDS-resident
+    kernel, any other map the composed path (``kws_forward_map_f32``).
 
-    @staticmethod
-    def forward(fctx, model, x, *params):
-        logits, labels = model._forward_native(x)
-        fctx.model = model
-        fctx.save_for_backward(x, *params)
-        fctx.mark_non_differentiable(labels)
-        return logits, labels
+    Trainable: after an explicit ``model.train()`` (the reference trainers call it at the start of every epoch,
+    ``kws/libs/training.py:275``, ``train.py:32``), when ``torch.is_grad_enabled()`` and some parameter requires grad,
+    ``forward`` runs through ``_NativeTrainFunction`` -- the same forward kernels (logits and labels are bit-identical to a call under
+    ``torch.no_grad()``) with a backward that recomputes the activations and computes all 20 parameter gradients in HIP
+    (``kws_dscnn_backward_f32``, fp32, deterministic).  Each gradient lands on its parameter's device.  No gradient with
+    respect to the input features is provided (an input that requires grad raises ``ModelError`` in backward), and
+    ``input_channels > 1`` cannot be trained (backward raises ``ModelError``).  Otherwise -- a model never switched with
+    ``train()``, or switched back with ``eval()``, ``torch.no_grad()``, frozen parameters -- no autograd graph is built and
+    the logits are plain tensors, as for inference."""
 
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(fctx, dlogits, _dlabels):
-        x, *params = fctx.saved_tensors
-        if fctx.needs_input_grad[1]:
-            raise ModelError("DepthwiseSeparableConv: the gradient with respect to the input features is not provided "
-                             "(kws_dscnn_backward_f32 computes parameter gradients only); detach the input")
-        model = fctx.model
-        # the weights the forward saw: the saved parameters, even if the module's attribute was replaced since (a new
-        # nn.Parameter bumps no version of the saved one); equal to the current ones in a normal step, so no re-upload
-        ctx = model._context(x.device.index or 0, params)
-        x = x.detach().to(torch.float32).contiguous()
-        dl = dlogits.detach().to(x.device, torch.float32).contiguous()
-        grad = torch.empty(sum(p.numel() for p in params), dtype=torch.float32, device=x.device)
+    _name = "DepthwiseSeparableConv"
+    _backward_entry = "kws_dscnn_backward_f32"
+
+    def __init__(self, num_classes: int = 12, input_channels: int = 1):
+        super().__init__(num_classes)
+        if not 1 <= input_channels <= 64:
+            raise ModelError("input_channels must be in [1, 64]")
+        self.input_channels = int(input_channels)
+        self.conv1 = nn.Conv2d(input_channels, 64, kernel_size=10, stride=2, padding=2)
+        self.dsconv1 = DepthwiseSeparableConvBlock(64, 64)
+        self.dsconv2 = DepthwiseSeparableConvBlock(64, 64)
+        self.dsconv3 = DepthwiseSeparableConvBlock(64, 64)
+        self.dsconv4 = DepthwiseSeparableConvBlock(64, 64)
+        self.fc = nn.Linear(64, num_classes)
+        self._initialize_weights()
+
+    def _initialize_weights(self):
+        # same scheme as the reference (:149-158)
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+            elif isinstance(m, nn.Linear):
+                nn.init.normal_(m.weight, 0, 0.01)
+                nn.init.constant_(m.bias, 0)
+
+    # ------------------------------------------------------------------ the hooks of _TrainableNative
+    def _load_host(self, ctx, blob):
+        ctx.load_dscnn(blob, self.num_classes, self.input_channels)
+
+    def _load_device(self, ctx, blob):
+        ctx.load_dscnn_device(blob, self.num_classes, self.input_channels)
+
+    def _check_features(self, x):
+        if x.dim() != 4 or x.shape[1] != self.input_channels:
+            raise ModelError(f"expected input [B,{self.input_channels},T,F], got {tuple(x.shape)}")
+
+    def _native_forward(self, ctx, x, logits, labels):
+        if tuple(x.shape[2:]) == FEATURE_SHAPE[1:]:
+            ctx.forward_f32(x, logits, labels)
+        else:
+            ctx.forward_map_f32(x, logits, labels)
+
+    def _native_backward(self, ctx, x, dl, grad):
         ctx.dscnn_backward_f32(x, x.shape[2], x.shape[3], dl, grad)
-        on_dev = {}
-        out, off = [], 0
-        for p in params:
-            if p.device not in on_dev:
-                on_dev[p.device] = grad.to(p.device)
-            out.append(on_dev[p.device][off:off + p.numel()].view(p.shape).to(p.dtype))
-            off += p.numel()
-        return (None, None, *out)
+
+    def _check_pcm16(self):
+        if self.input_channels != 1:
+            raise ModelError("infer_pcm16 needs input_channels=1: the MFCC front end yields one channel")
+
+    def _native_infer_i16(self, ctx, wav, logits, labels):
+        ctx.infer_i16(wav, logits, labels)
 
 
 class DepthwiseSeparableConvBN(KeywordSpottingModel):
@@ -352,7 +394,7 @@ class DepthwiseSeparableConvBN(KeywordSpottingModel):
         return self.fold().infer_pcm16(wav)
 
 
-class CnnTradFpool3(KeywordSpottingModel):
+class CnnTradFpool3(_TrainableNative):
     """Build-defined model-zoo member: Sainath & Parada's cnn-trad-fpool3 on the reference's
     ``[1,99,10]`` MFCC map with SAME padding -- conv 64x(20x8)+ReLU, max-pool 1x3 over frequency, conv 64x(10x4)+ReLU,
     flatten, Linear 32, Linear 128+ReLU, Linear C.  The modules hold parameters; ``forward`` is
@@ -360,13 +402,18 @@ class CnnTradFpool3(KeywordSpottingModel):
     three-way split, the dense tail batched on the VALU).
 
     Trainable like ``DepthwiseSeparableConv``: after an explicit ``model.train()``, when ``torch.is_grad_enabled()`` and some
-    parameter requires grad, ``forward`` runs through ``_CnnTradTrainFunction`` -- the same inference call (logits and labels
+    parameter requires grad, ``forward`` runs through ``_NativeTrainFunction`` -- the same inference call (logits and labels
     bit-identical to a call under ``torch.no_grad()``) with a backward that recomputes the activations in f32 and computes all
     ten parameter gradients in HIP (``kws_cnn_trad_backward_f32``, deterministic, independent of ``kws_set_cnn_trad_math``).
     Each gradient lands on its parameter's device.  No gradient with respect to the input features is provided (an input that
     requires grad raises ``ModelError`` in backward).  Otherwise -- no ``train()``, ``eval()``, ``torch.no_grad()``, frozen
     parameters -- no autograd graph is built.  Parameters on the GPU are re-uploaded after an optimizer step without leaving
-    the device (``kws_load_cnn_trad_device``); CPU-resident parameters go through the host load."""
+    the device (``kws_load_cnn_trad_device``); CPU-resident parameters go through the host load.  ``infer_pcm16`` is
+    BASELINE.json configs[2]."""
+
+    _name = "CnnTradFpool3"
+    _backward_entry = "kws_cnn_trad_backward_f32"
+    _pcm16_is = "the path is HIP kernels"
 
     def __init__(self, num_classes: int = 12):
         super().__init__(num_classes)
@@ -375,117 +422,22 @@ class CnnTradFpool3(KeywordSpottingModel):
         self.lin = nn.Linear(64 * 99 * 3, 32)
         self.dnn = nn.Linear(32, 128)
         self.fc = nn.Linear(128, num_classes)
-        self._ctx = None
-        self._uploaded = None
-        self._autograd = False  # set by an explicit train(), cleared by eval() / train(False)
 
-    def train(self, mode: bool = True):
-        """``nn.Module.train``; an explicit ``train()`` also switches ``forward`` to the autograd path (see the class
-        docstring), ``eval()`` / ``train(False)`` switches it back."""
-        super().train(mode)
-        self._autograd = bool(mode)
-        return self
+    def _load_host(self, ctx, blob):
+        ctx.load_cnn_trad(blob, self.num_classes)
 
-    def packed_weights(self) -> np.ndarray:
-        return np.concatenate([v.detach().to("cpu", torch.float32).reshape(-1).numpy() for v in self.state_dict().values()])
+    def _load_device(self, ctx, blob):
+        ctx.load_cnn_trad_device(blob, self.num_classes)
 
-    def sync_weights(self) -> None:
-        """Force a re-upload at the next forward (needed only after edits through ``p.data``, which do not bump
-        ``p._version``; see ``DepthwiseSeparableConv.sync_weights``)."""
-        self._uploaded = None
-
-    def _context(self, device_index: int, params=None):
-        """The model's context on ``device_index`` holding ``params`` (default: the current parameters, in ``parameters()``
-        order); uploaded only when they differ from the tensors (and versions) uploaded last.  Parameters that all live on
-        that GPU are concatenated there and loaded with ``kws_load_cnn_trad_device``; otherwise through the host."""
-        from kws import _native
-
-        if self._ctx is None or self._ctx.device != device_index:
-            self._ctx = _native.Context(device_index, ModelError)
-            self._uploaded = None
-        params = tuple(self.parameters()) if params is None else tuple(params)
-        fp = tuple((p.data_ptr(), p._version) for p in params)
-        if fp != self._uploaded:
-            dev = torch.device("cuda", device_index)
-            if all(p.device == dev for p in params):
-                self._ctx.use_torch_stream()
-                blob = torch.cat([p.detach().to(torch.float32).reshape(-1) for p in params])
-                self._ctx.load_cnn_trad_device(blob, self.num_classes)
-            else:
-                self._ctx.load_cnn_trad(np.concatenate([p.detach().to("cpu", torch.float32).reshape(-1).numpy() for p in params]),
-                                        self.num_classes)
-            self._uploaded = fp
-        self._ctx.use_torch_stream()
-        return self._ctx
-
-    def forward(self, x: torch.Tensor, return_labels: bool = False):
-        if not x.is_cuda:
-            raise ModelError("CnnTradFpool3.forward needs a CUDA/ROCm tensor: the forward is a HIP kernel and has no CPU fallback")
+    def _check_features(self, x):
         if x.dim() != 4 or tuple(x.shape[1:]) != FEATURE_SHAPE:
             raise ModelError(f"expected input [B,1,99,10], got {tuple(x.shape)}")
-        params = tuple(self.parameters())
-        if self._autograd and torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            logits, labels = _CnnTradTrainFunction.apply(self, x, *params)
-        else:
-            logits, labels = self._forward_native(x)
-        return (logits, labels) if return_labels else logits
 
-    def _forward_native(self, x: torch.Tensor):
-        """The inference kernels on ``x`` (checked by the caller) -> (logits, labels); no autograd graph."""
-        ctx = self._context(x.device.index or 0)
-        x = x.detach().to(torch.float32).contiguous()
-        logits = torch.empty((x.shape[0], self.num_classes), dtype=torch.float32, device=x.device)
-        labels = torch.empty((x.shape[0],), dtype=torch.int32, device=x.device)
+    def _native_forward(self, ctx, x, logits, labels):
         ctx.forward_cnn_trad_f32(x, logits, labels)
-        return logits, labels
 
-    def infer_pcm16(self, wav: torch.Tensor):
-        """Fused path (BASELINE.json configs[2]): ``int16[B,16000]`` PCM on the GPU -> (logits, labels); MFCC +
-        cnn-trad-fpool3 back to back on one stream (``kws_infer_cnn_trad_i16``)."""
-        if not wav.is_cuda:
-            raise ModelError("CnnTradFpool3.infer_pcm16 needs a CUDA/ROCm tensor: the path is HIP kernels and has no CPU fallback")
-        if wav.dtype != torch.int16 or wav.dim() != 2:
-            raise ModelError("infer_pcm16 expects an int16 tensor [B, n_samples]")
-        ctx = self._context(wav.device.index or 0)
-        wav = wav.contiguous()
-        logits = torch.empty((wav.shape[0], self.num_classes), dtype=torch.float32, device=wav.device)
-        labels = torch.empty((wav.shape[0],), dtype=torch.int32, device=wav.device)
-        ctx.infer_cnn_trad_i16(wav, logits, labels)
-        return logits, labels
-
-
-class _CnnTradTrainFunction(torch.autograd.Function):
-    """``CnnTradFpool3.forward`` with a HIP backward.  Forward: exactly the inference call; the input and the parameters are
-    saved with ``save_for_backward``, so torch's version counter rejects a parameter modified in place between forward and
-    backward.  Backward: ``kws_cnn_trad_backward_f32`` at the saved parameters (uploaded only if they are not the device copy),
-    the flat gradient split into views shaped like the parameters and moved to each parameter's device."""
-
-    @staticmethod
-    def forward(fctx, model, x, *params):
-        logits, labels = model._forward_native(x)
-        fctx.model = model
-        fctx.save_for_backward(x, *params)
-        fctx.mark_non_differentiable(labels)
-        return logits, labels
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(fctx, dlogits, _dlabels):
-        x, *params = fctx.saved_tensors
-        if fctx.needs_input_grad[1]:
-            raise ModelError("CnnTradFpool3: the gradient with respect to the input features is not provided "
-                             "(kws_cnn_trad_backward_f32 computes parameter gradients only); detach the input")
-        model = fctx.model
-        ctx = model._context(x.device.index or 0, params)
-        x = x.detach().to(torch.float32).contiguous()
-        dl = dlogits.detach().to(x.device, torch.float32).contiguous()
-        grad = torch.empty(sum(p.numel() for p in params), dtype=torch.float32, device=x.device)
+    def _native_backward(self, ctx, x, dl, grad):
         ctx.cnn_trad_backward_f32(x, dl, grad)
-        on_dev = {}
-        out, off = [], 0
-        for p in params:
-            if p.device not in on_dev:
-                on_dev[p.device] = grad.to(p.device)
-            out.append(on_dev[p.device][off:off + p.numel()].view(p.shape).to(p.dtype))
-            off += p.numel()
-        return (None, None, *out)
+
+    def _native_infer_i16(self, ctx, wav, logits, labels):
+        ctx.infer_cnn_trad_i16(wav, logits, labels)

@@ -128,8 +128,12 @@ def test_training_forward_without_gpu_still_fails_loudly():
 
     m = CnnTradFpool3().train()
     assert m._autograd and torch.is_grad_enabled() and all(p.requires_grad for p in m.parameters())
-    with pytest.raises(ModelError, match="no CPU fallback"):
+    with pytest.raises(ModelError, match=r"CnnTradFpool3\.forward needs a CUDA/ROCm tensor.*no CPU fallback"):
         m(torch.zeros(2, 1, 99, 10))
+    with pytest.raises(ModelError, match="no CPU fallback"):
+        m.eval()(torch.zeros(2, 1, 99, 10))
+    with pytest.raises(ModelError, match=r"CnnTradFpool3\.infer_pcm16 needs a CUDA/ROCm tensor: the path is HIP kernels"):
+        m.infer_pcm16(torch.zeros(2, 16000, dtype=torch.int16))
     assert not CnnTradFpool3().train().eval()._autograd
 
 

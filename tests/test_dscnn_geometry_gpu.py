@@ -383,6 +383,35 @@ def test_depthwise_grid_stride_batch(native):
         c.close()
 
 
+def test_stage_dump_across_the_clip_cap(native, ctx):
+    """16387 clips at 6 x 6, two classes: a chunk of 16384 clips (the cap) and one of 3.  The dumped stages and logits of
+    clips 16380 .. 16386 -- the last four of the first chunk, all of the second -- are those of a debug call on these seven
+    clips alone, bit for bit (no kernel of the composed path mixes clips), and every float of the dump is written."""
+    from oracle import dscnn as o_dscnn
+
+    B, C, T, F, lo = 16387, 2, 6, 6, 16380
+    ctx.load_dscnn(o_dscnn.flatten_state(o_dscnn.random_state(16387, num_classes=C)), C)
+    x = torch.randn(B, 1, T, F, generator=torch.Generator().manual_seed(16387)).to(DEV)
+    sizes = [int(np.prod(s)) for s in _geometry(T, F)]
+
+    def dump(xs):
+        n = xs.shape[0]
+        layers = torch.full((n * sum(sizes),), float("nan"), device=DEV)
+        logits = torch.empty((n, C), device=DEV)
+        labels = torch.empty((n,), dtype=torch.int32, device=DEV)
+        ctx.forward_map_f32(xs, logits, labels, layers=layers)
+        ctx.sync()
+        ends = np.cumsum([n * s for s in sizes])
+        return logits, labels, [layers[e - n * s:e].reshape(n, s) for e, s in zip(ends, sizes)], layers
+
+    logits, labels, stages, layers = dump(x)
+    assert torch.isfinite(layers).all()
+    l7, b7, s7, _ = dump(x[lo:].clone())
+    for k, (a, b) in enumerate(zip(stages, s7)):
+        assert torch.equal(a[lo:], b), f"stage {k}"
+    assert torch.equal(logits[lo:], l7) and torch.equal(labels[lo:], b7)
+
+
 def test_accepted_domain_is_the_same_forward_and_backward(native, ctx):
     from kws.common.errors import ModelError
     from oracle import dscnn as o_dscnn

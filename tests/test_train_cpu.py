@@ -68,6 +68,54 @@ def test_training_forward_without_gpu_still_fails_loudly():
     assert torch.is_grad_enabled() and all(p.requires_grad for p in m.parameters())
     with pytest.raises(ModelError, match="no CPU fallback"):
         m(torch.zeros(2, 1, 99, 10))
+    assert m.train()._autograd  # the autograd dispatch refuses the CPU tensor as the plain one does
+    with pytest.raises(ModelError, match=r"DepthwiseSeparableConv\.forward needs a CUDA/ROCm tensor.*no CPU fallback"):
+        m(torch.zeros(2, 1, 99, 10))
+    with pytest.raises(ModelError, match=r"DepthwiseSeparableConv\.infer_pcm16 needs a CUDA/ROCm tensor.*no CPU fallback"):
+        m.infer_pcm16(torch.zeros(2, 16000, dtype=torch.int16))
+
+
+def test_both_trainable_models_dispatch_to_one_function(monkeypatch):
+    """After train(), under grad mode, the forward of either model hands itself, the input and its parameters to the same
+    torch.autograd.Function -- the only one of the module."""
+    from kws.libs import models
+
+    fns = [v for v in vars(models).values() if isinstance(v, type) and issubclass(v, torch.autograd.Function)]
+    assert fns == [models._NativeTrainFunction]
+
+    class OnGpu:  # what forward looks at before it dispatches
+        is_cuda = True
+        shape = (2, 1, 99, 10)
+
+        def dim(self):
+            return 4
+
+    calls = []
+    monkeypatch.setattr(models._NativeTrainFunction, "apply",
+                        staticmethod(lambda model, x, *params: calls.append((model, x, params)) or ("logits", "labels")))
+    x = OnGpu()
+    for cls in (models.DepthwiseSeparableConv, models.CnnTradFpool3):
+        m = cls().train()
+        assert m(x) == "logits" and m(x, return_labels=True) == ("logits", "labels")
+        model, got, params = calls[-1]
+        mine = list(m.parameters())
+        assert model is m and got is x and len(params) == len(mine) and all(a is b for a, b in zip(params, mine))
+    assert len(calls) == 4
+
+
+def test_split_flat_grad_pieces_are_the_slices():
+    from kws.libs.models import split_flat_grad
+
+    params = [torch.zeros(2, 3), torch.zeros(4, dtype=torch.float64), torch.zeros(1, 1, 2)]
+    flat = torch.arange(12, dtype=torch.float32) * 0.37 - 2.0
+    pieces = split_flat_grad(flat, params)
+    assert len(pieces) == 3
+    off = 0
+    for g, p in zip(pieces, params):
+        assert g.shape == p.shape and g.dtype == p.dtype and g.device == p.device
+        assert torch.equal(g.reshape(-1), flat[off:off + p.numel()].to(p.dtype))
+        off += p.numel()
+    assert off == flat.numel()
 
 
 @pytest.mark.parametrize("T,F,C", [(99, 10, 12), (20, 8, 35), (7, 7, 1)])
