@@ -478,6 +478,55 @@ int kws_resample_i16(kws_ctx* ctx, const int16_t* d_in, int R, int n_in, const i
 int kws_resample_f32(kws_ctx* ctx, const float* d_in, int R, int n_in, const int32_t* d_len, int rate_in, int rate_out,
                      float* d_out, int n_out);
 
+/* ---- streaming sample-rate conversion: the resampler above with state, for live audio that arrives in pieces ----------------
+ * up, down, M, half, the taps h and their device table are those of kws_resample_*; rows = ceil((2 * half + 1) / up).
+ * The definition.  All streams of a context advance in lockstep.  A stream's signal x[m] is zero for m < first_sample and grows
+ *   by n_in samples per push.  For EVERY integer k, negative ones included,
+ *     y[k] = sum over m of x[m] * h[half + k * down - m * up]
+ *   evaluated as kws_resample_* evaluates it: newest sample q = floor((half + k * down) / up) first, `rows` fused float64
+ *   multiply-adds from 0.0 with the taps h[phase + i * up], phase = (half + k * down) - q * up, the table's padded zeros
+ *   included; the division and the remainder round towards minus infinity.
+ *   Delay: d = ceil(half / down) output samples -- 10 whenever down >= up (0.625 ms at 16 kHz), 20 for 8 -> 16 kHz, 15 for 44.1 ->
+ *   64 kHz.  Absolute output j is y[j - d], stored as kws_resample_i16 stores (clamped to int16, rounded to nearest even).  With P
+ *   samples received in all (first_sample counts as received) the outputs j < floor(P * up / down) have been emitted: a push from
+ *   P0 to P1 emits floor(P1 * up / down) - floor(P0 * up / down) samples, a number the host computes -- nothing is read back.
+ *   With this d every emitted output's span lies inside the samples already pushed, so its bits are those kws_resample_i16 gives
+ *   the whole signal at index j - d (front-padded by a multiple of down zeros to reach the pre-ringing before the onset).
+ *   Equal rates are a copy: d = 0 and every push emits n_in samples.
+ *   first_sample must be a multiple of down; the first output index is then the integer first_sample / down * up and the bits
+ *   are those of first_sample = 0.  Positions are kept in 64 bits (first_sample below 2^62): 2^31 samples are 12 hours at 48 kHz.
+ * State: the last H = rows - 1 + ceil((d * down + down - 1 - half) / up) samples per stream (62 at 48 -> 16 kHz, 58 at 44.1 ->
+ *   16 kHz, 20 at 8 -> 16 kHz), which is exactly what the outputs of the next push can reach back to.
+ * Limits: max(up, down) <= 1024 and H + max_in <= 6144 (a workgroup stages history and input in LDS as float64), KWS_EUNSUPPORTED
+ *   beyond; equal rates have no such limit.
+ *
+ * kws_host_stream_resample_plan (no GPU): the reduced pair, d and H; any pointer may be NULL.
+ * kws_host_stream_resample_count (no GPU): *n_out = what a push of n_in >= 0 samples emits after samples_before samples.
+ *   Both: a rate < 1 (or a NULL n_out, n_in < 0): KWS_EINVAL; max(up, down) > 1024: KWS_EUNSUPPORTED.
+ * kws_stream_resample_open: state for n_streams streams and pushes of at most max_in samples; needs neither a front end nor a
+ *   model.  Designs the pair through the design cache of kws_resample_* (drains the stream: NOT for stream capture), zeroes the
+ *   history.  A second open replaces the state; kws_stream_resample_close and kws_destroy free it.  n_streams < 1, max_in < 1, a
+ *   rate < 1, first_sample not a multiple of down: KWS_EINVAL.
+ * kws_stream_resample_i16: d_in [n_streams, n_in] -> d_out [n_streams, out_cap] (row stride out_cap), both on the device and
+ *   not overlapping.  *n_out (host) is set before the launch; out_cap < *n_out is KWS_EINVAL with nothing done.  One launch:
+ *   one workgroup per stream up to 1024 outputs per stream, one per 1024 outputs beyond; the history is double-buffered, so
+ *   no workgroup reads what another writes.  NULL pointers, n_in < 1 or > max_in: KWS_EINVAL; no open: KWS_ESTATE.  Not timed
+ *   by kws_prof_*.  Asynchronous on the context stream; no atomics.
+ * kws_stream_push_rate_i16: resample one push into a hop buffer the context owns, then kws_stream_push_i16(ctx, hop, d_logits,
+ *   d_label, 0).  Needs kws_stream_open with the same n_streams and rate_out == the front end's sample rate (KWS_ESTATE
+ *   otherwise); the push must emit exactly frame_step samples, else KWS_EINVAL with no state touched (48 kHz: 480 in, 44.1 kHz:
+ *   441 in, 8 kHz: 80 in for the default hop of 160).  If the streaming push refuses, the resampler's state steps back.
+ * kws_stream_push_host_rate_i16: the same from host memory -- h_in [n_streams, n_in] is copied into pinned, device-mapped
+ *   memory of n_streams * max_in samples, the resampler reads it from there -- with the results delivered as
+ *   kws_stream_push_host_i16 delivers them (kws_stream_host_results / kws_stream_wait_host). */
+int kws_host_stream_resample_plan(int rate_in, int rate_out, int* up, int* down, int* delay_out, int* history);
+int kws_host_stream_resample_count(int rate_in, int rate_out, uint64_t samples_before, int n_in, int* n_out);
+int kws_stream_resample_open(kws_ctx* ctx, int n_streams, int rate_in, int rate_out, int max_in, uint64_t first_sample);
+int kws_stream_resample_close(kws_ctx* ctx);
+int kws_stream_resample_i16(kws_ctx* ctx, const int16_t* d_in, int n_in, int16_t* d_out, int out_cap, int* n_out);
+int kws_stream_push_rate_i16(kws_ctx* ctx, const int16_t* d_in, int n_in, float* d_logits, int32_t* d_label);
+int kws_stream_push_host_rate_i16(kws_ctx* ctx, const int16_t* h_in, int n_in, const float** h_logits, const int32_t** h_label);
+
 /* ---- evaluation statistics on the device (build-defined: the reference computes them on the host, with a
  * round trip per batch -- running_loss += loss.item(), torch.max(outputs, 1), (predicted == labels).sum().item() in
  * train.py:51-54,79-98 and kws/libs/training.py:300-303,347-393 -- and test.py:27-58 derives the per-class report, the

@@ -14,6 +14,8 @@ void vad_free(kws_ctx* c);
 void eval_free(kws_ctx* c);  // evaluation accumulators (kws_eval.hip)
 struct ResampleCache;           // rate pairs designed so far and their device tap tables (kws_resample.hip)
 void resample_free(kws_ctx* c);
+struct StreamResample;          // the streaming resampler's pair, position and per-stream history (kws_resample.hip)
+void stream_resample_free(kws_ctx* c);
 }  // namespace kws
 
 using kws::FrontendParams; using kws::FrontendTables; using kws::DscnnWeights; using kws::CnnTradWeights; using kws::NFFT;
@@ -110,6 +112,8 @@ struct kws_ctx {
 
     // sample-rate conversion (kws_resample_*): the tap tables of the rate pairs used so far -- created on first use
     kws::ResampleCache* resample = nullptr;
+    // streaming resampler (kws_stream_resample_*, kws_stream_push_rate_i16): created by kws_stream_resample_open
+    kws::StreamResample* stream_resample = nullptr;
 
     // host ingest (kws_infer_host_i16): staging rings, copy streams, pack threads -- created on first use
     kws::Ingest* ingest = nullptr;

@@ -95,6 +95,13 @@ SIGNATURES = {
                                       _f32p, C.c_int, _i32p]),
     "kws_resample_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _i16p, C.c_int]),
     "kws_resample_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _f32p, C.c_int]),
+    "kws_host_stream_resample_plan": (C.c_int, [C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4),
+    "kws_host_stream_resample_count": (C.c_int, [C.c_int, C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_int)]),
+    "kws_stream_resample_open": (C.c_int, [_c_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64]),
+    "kws_stream_resample_close": (C.c_int, [_c_ctx]),
+    "kws_stream_resample_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, _i16p, C.c_int, C.POINTER(C.c_int)]),
+    "kws_stream_push_rate_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, _f32p, _i32p]),
+    "kws_stream_push_host_rate_i16": (C.c_int, [_c_ctx, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "kws_eval_open": (C.c_int, [_c_ctx, C.c_int, C.c_int]),
     "kws_eval_reset": (C.c_int, [_c_ctx]),
     "kws_eval_close": (C.c_int, [_c_ctx]),
@@ -447,6 +454,46 @@ class Context:
         """``kws_resample_f32``: the same for float32 [R, n_in] -> float32 [R, n_out]."""
         self._resample(self._lib.kws_resample_f32, signal, rate_in, rate_out, out, lengths)
 
+    # -- streaming sample-rate conversion ---------------------------------------------------------
+    @staticmethod
+    def host_stream_resample_plan(rate_in, rate_out):
+        return host_stream_resample_plan(rate_in, rate_out)
+
+    @staticmethod
+    def host_stream_resample_count(rate_in, rate_out, samples_before, n_in) -> int:
+        return host_stream_resample_count(rate_in, rate_out, samples_before, n_in)
+
+    def stream_resample_open(self, n_streams: int, rate_in: int, rate_out: int, max_in: int, first_sample: int = 0):
+        """``kws_stream_resample_open``: a stateful resampler for ``n_streams`` streams in lockstep and pushes of at most ``max_in``
+        samples; ``first_sample`` (a multiple of ``down``) is where the streams' signal starts."""
+        self._check(self._lib.kws_stream_resample_open(self._h, int(n_streams), int(rate_in), int(rate_out), int(max_in),
+                                                       C.c_uint64(int(first_sample))), AudioProcessingError)
+
+    def stream_resample_close(self):
+        self._check(self._lib.kws_stream_resample_close(self._h), AudioProcessingError)
+
+    def stream_resample_i16(self, pcm, out) -> int:
+        """``kws_stream_resample_i16``: the next ``pcm`` int16 [S, n_in] of every stream -> ``out`` int16 [S, out_cap], both on the
+        device; returns the samples per stream this push emitted (known before the launch; the call is asynchronous)."""
+        n = C.c_int(0)
+        self._check(self._lib.kws_stream_resample_i16(self._h, _ptr(pcm), int(pcm.shape[1]), _ptr(out), int(out.shape[1]), C.byref(n)),
+                    AudioProcessingError)
+        return n.value
+
+    def stream_push_rate_i16(self, pcm, logits=None, label=None):
+        """``kws_stream_push_rate_i16``: one hop's worth of ``pcm`` int16 [S, n_in] at the resampler's input rate (device) ->
+        resampled into the context's hop buffer -> ``stream_push_i16``."""
+        self._check(self._lib.kws_stream_push_rate_i16(self._h, _ptr(pcm), int(pcm.shape[1]), _ptr(logits) if logits is not None else None,
+                                                       _ptr(label) if label is not None else None), ModelError)
+
+    def stream_push_host_rate_i16(self, pcm: np.ndarray, n_streams: int):
+        """``kws_stream_push_host_rate_i16``: host int16 [S, n_in] at the resampler's input rate -> (logits, labels) host views."""
+        if pcm.dtype != np.int16 or not pcm.flags.c_contiguous or pcm.ndim != 2 or pcm.shape[0] != n_streams:
+            raise ModelError("stream_push_host_rate_i16 expects a C-contiguous int16 array [n_streams, n_in]")
+        pl, py = C.c_void_p(), C.c_void_p()
+        self._check(self._lib.kws_stream_push_host_rate_i16(self._h, pcm.ctypes.data, int(pcm.shape[1]), C.byref(pl), C.byref(py)), ModelError)
+        return self._host_views_of(pl, py, n_streams)
+
     # -- evaluation ------------------------------------------------------------------------------
     def eval_open(self, num_classes: int, n_bins: int = 256):
         """``kws_eval_open``: allocate and zero the context's evaluation state for ``num_classes`` classes and ``n_bins``
@@ -668,6 +715,26 @@ def host_resample_len(n_in, rate_in, rate_out) -> int:
     if rc != KWS_OK:
         raise AudioProcessingError(f"kws_host_resample_len({n_in}, {rate_in}, {rate_out}) failed (code {rc})")
     return int(n.value)
+
+
+def host_stream_resample_plan(rate_in, rate_out):
+    """(up, down, delay, history) of the streaming resampler: the reduced pair, the delay d in output samples and the input
+    samples H a stream keeps (``kws_host_stream_resample_plan``)."""
+    v = [C.c_int(0) for _ in range(4)]
+    rc = lib().kws_host_stream_resample_plan(int(rate_in), int(rate_out), *(C.byref(x) for x in v))
+    if rc != KWS_OK:
+        raise AudioProcessingError(f"kws_host_stream_resample_plan({rate_in}, {rate_out}) failed (code {rc})")
+    return tuple(x.value for x in v)
+
+
+def host_stream_resample_count(rate_in, rate_out, samples_before, n_in) -> int:
+    """floor((P + n_in) up / down) - floor(P up / down): what a push of ``n_in`` samples emits after ``samples_before`` = P
+    samples (``kws_host_stream_resample_count``)."""
+    n = C.c_int(0)
+    rc = lib().kws_host_stream_resample_count(int(rate_in), int(rate_out), C.c_uint64(int(samples_before)), int(n_in), C.byref(n))
+    if rc != KWS_OK:
+        raise AudioProcessingError(f"kws_host_stream_resample_count({rate_in}, {rate_out}, {samples_before}, {n_in}) failed (code {rc})")
+    return n.value
 
 
 def host_resample_design(rate_in, rate_out):

@@ -281,11 +281,22 @@ class StreamingSpotter:
     (``kws/inference/inference_local.py:114-192``).  Here every ``push`` of ``frame_step`` new samples per
     stream adds one MFCC frame to a 99-frame ring on the GPU and re-classifies the last second of every
     stream (``kws_stream_push_i16``); with ``use_graph`` the two launches of a push replay as one hipGraph.
+
+    ``input_rate``: the rate the audio arrives at, when it is not ``config.sample_rate``.  Every ``push`` then takes ``hop_in``
+    samples per stream at that rate (480 at 48 kHz, 441 at 44.1 kHz, 80 at 8 kHz for the default 10 ms hop) and a stateful
+    polyphase resampler on the device turns them into the hop (``kws_stream_push_rate_i16`` /
+    ``kws_stream_push_host_rate_i16``: the bits of ``kws_resample_i16`` over the whole signal, delayed).  ``hop_in = hop * down /
+    up`` must be integral -- 22.05 kHz (220.5) raises ``ModelError``; ``use_graph`` does not apply to these pushes.
+
+    Attributes: ``hop`` -- samples per hop at ``config.sample_rate``; ``hop_in`` -- samples ``push`` takes per stream (``hop``
+    without ``input_rate``); ``delay_samples`` -- the resampler's delay in samples at ``config.sample_rate`` (10 = 0.625 ms for
+    every rate above 16 kHz, 20 for 8 kHz, 0 without ``input_rate``): what the streams hear lags the input by that much.
     """
 
     def __init__(self, n_streams: int, model: Optional[DepthwiseSeparableConv] = None, words: Sequence[str] = WANTED_WORDS,
                  config: Optional[AudioConfig] = None, device: int = 0, use_graph: bool = False, smooth_window: int = 0,
-                 vad_log_energy: Optional[float] = None, vad_windows: Tuple[int, int] = (40, 80), host_results: bool = True):
+                 vad_log_energy: Optional[float] = None, vad_windows: Tuple[int, int] = (40, 80), host_results: bool = True,
+                 input_rate: Optional[int] = None):
         from kws import _native
 
         self.config = config or AudioConfig()
@@ -293,6 +304,15 @@ class StreamingSpotter:
         self.model = model if model is not None else DepthwiseSeparableConv(num_classes=len(self.words))
         self.n_streams = int(n_streams)
         self.hop = int(round(self.config.frame_step * self.config.sample_rate))
+        self.input_rate = int(input_rate) if input_rate is not None else None
+        self._resample = self.input_rate is not None and self.input_rate != self.config.sample_rate
+        self.hop_in, self.delay_samples = self.hop, 0
+        if self._resample:
+            up, down, self.delay_samples, _ = _native.host_stream_resample_plan(self.input_rate, self.config.sample_rate)
+            if (self.hop * down) % up:
+                raise ModelError(f"input_rate {self.input_rate}: a hop of {self.hop} samples at {self.config.sample_rate} Hz is "
+                                 f"{self.hop * down}/{up} = {self.hop * down / up:g} samples at the input rate, not a whole number")
+            self.hop_in = self.hop * down // up
         self.device = torch.device("cuda", device)
         self.use_graph = use_graph
         self._ctx = _native.Context(device, ModelError)
@@ -304,7 +324,9 @@ class StreamingSpotter:
                                    cfg.num_mel_filters, cfg.num_cepstral_coeffs)
         self._ctx.load_dscnn(self.model.packed_weights(), self.model.num_classes)
         self._ctx.stream_open(self.n_streams)
-        self._hop_buf = torch.zeros((self.n_streams, self.hop), dtype=torch.int16, device=self.device)
+        if self._resample:
+            self._ctx.stream_resample_open(self.n_streams, self.input_rate, cfg.sample_rate, self.hop_in)
+        self._hop_buf = torch.zeros((self.n_streams, self.hop_in), dtype=torch.int16, device=self.device)
         self._logits = torch.zeros((self.n_streams, self.model.num_classes), dtype=torch.float32, device=self.device)
         self._labels = torch.zeros((self.n_streams,), dtype=torch.int32, device=self.device)
         # posterior smoothing: softmax of every hop's logits averaged over the last
@@ -334,22 +356,28 @@ class StreamingSpotter:
         self._ctx.load_dscnn(model.packed_weights(), model.num_classes)
 
     def push(self, samples) -> Tuple[np.ndarray, np.ndarray]:
-        """``int16[n_streams, hop]`` (host array or device tensor) -> (labels int32[S], logits float32[S,C]);
+        """``int16[n_streams, hop_in]`` (host array or device tensor) -> (labels int32[S], logits float32[S,C]);
         with ``smooth_window`` > 0 the second array holds the smoothed posteriors and the labels are their argmax."""
         if self._host and not isinstance(samples, torch.Tensor):
             # host samples in, host results out, one call: the kernel reads the hop from pinned host memory and writes the
             # results back there (kws_stream_push_host_i16) -- no H2D copy, no synchronise, no D2H copy
             h = np.ascontiguousarray(samples, dtype=np.int16)
-            if h.shape != (self.n_streams, self.hop):
-                raise ModelError(f"push expects int16 [{self.n_streams}, {self.hop}]")
-            lg, lb = self._ctx.stream_push_host_i16(h, self.n_streams)
+            if h.shape != (self.n_streams, self.hop_in):
+                raise ModelError(f"push expects int16 [{self.n_streams}, {self.hop_in}]")
+            if self._resample:
+                lg, lb = self._ctx.stream_push_host_rate_i16(h, self.n_streams)
+            else:
+                lg, lb = self._ctx.stream_push_host_i16(h, self.n_streams)
             return lb.copy(), lg.copy()
         x = samples if isinstance(samples, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(samples, dtype=np.int16))
-        if tuple(x.shape) != (self.n_streams, self.hop) or x.dtype != torch.int16:
-            raise ModelError(f"push expects int16 [{self.n_streams}, {self.hop}]")
+        if tuple(x.shape) != (self.n_streams, self.hop_in) or x.dtype != torch.int16:
+            raise ModelError(f"push expects int16 [{self.n_streams}, {self.hop_in}]")
         self._hop_buf.copy_(x, non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()  # the context runs on its own stream
-        self._ctx.stream_push_i16(self._hop_buf, self._logits, self._labels, use_graph=self.use_graph)
+        if self._resample:
+            self._ctx.stream_push_rate_i16(self._hop_buf, self._logits, self._labels)
+        else:
+            self._ctx.stream_push_i16(self._hop_buf, self._logits, self._labels, use_graph=self.use_graph)
         if self._host:
             lg, lb = self._ctx.stream_wait_host(self.n_streams)
             return lb.copy(), lg.copy()
