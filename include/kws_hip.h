@@ -72,10 +72,16 @@ const char* kws_last_error(kws_ctx* ctx);
  *   psf.mfcc defaults for preemph / ceplifter / lowfreq 0 / highfreq sr/2 / appendEnergy True /
  *   rectangular window).  frame_len and frame_step are in samples (winlen*sr, winstep*sr rounded
  *   half up, as psf does).  Two kernels serve it:
- *     the float32 kernel (the hot path) for nfft == 512, frame_len <= 512 and a filterbank that spans bins 0..256;
+ *     the float32 kernel (the hot path) for nfft == 512, frame_len <= 512, a filterbank that spans bins 0..256 in at most
+ *     64 chunks of 8 bins (no stretch between two mel edges longer than 64 bins), and a hop whose 24-frame span fits a
+ *     workgroup's LDS: 4 * (23 * frame_step + frame_len) bytes + 21 KB + the DCT table (4 * numcep * nfilt) <= 160 KB, i.e.
+ *     frame_step up to ~1500 samples;
  *     the float64 kernel for every other geometry: nfft a power of two in [64, 4096] or any value in [2, 2048] (the
  *     reference derives nfft = max(fft_size, int(winlen*samplerate)), audio_processor.py:268 -- e.g. 640 for a 40 ms
  *     window), any frame_len (frames longer than nfft are truncated, as numpy.fft.rfft does).
+ *     A geometry the float32 kernel does not cover is no error: kws_set_frontend returns KWS_OK, kws_frontend_math reports
+ *     KWS_FE_F64 and every kws_mfcc_* / kws_scan_i16 call computes it in float64; kws_mfcc_augment_i16 and kws_stream_open
+ *     (float32 only) return KWS_EUNSUPPORTED for it.  No geometry kws_set_frontend accepts fails at call time.
  *   Limits of both: nfilt <= 64, numcep <= min(nfilt, 32); anything else returns KWS_EUNSUPPORTED. */
 int kws_set_frontend(kws_ctx* ctx, int sample_rate, int n_samples, int frame_len, int frame_step,
                      int nfft, int nfilt, int numcep, float preemph, int ceplifter);

@@ -300,7 +300,7 @@ int kws_stream_open(kws_ctx* c, int n_streams) {
     if (n_streams <= 0) return fail(c, KWS_EINVAL, "kws_stream_open: n_streams must be positive");
     if (!c->fe_ready) return fail(c, KWS_ESTATE, "kws_stream_open: front end not configured");
     if (!c->fe_fast_ok)
-        return fail(c, KWS_EUNSUPPORTED, "kws_stream_open: the streaming frame kernel is built for nfft == 512 and frames of at most 512 samples");
+        return fail(c, KWS_EUNSUPPORTED, "kws_stream_open: the streaming frame kernel is float32 only (nfft == 512, frames of at most 512 samples, a filterbank and a hop the float32 kernel covers)");
     if (c->fp.frame_step > 512) return fail(c, KWS_EUNSUPPORTED, "kws_stream_open: hops of more than 512 samples are not supported");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));

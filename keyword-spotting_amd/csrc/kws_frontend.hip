@@ -124,7 +124,9 @@ int kws_set_frontend(kws_ctx* c, int sample_rate, int n_samples, int frame_len, 
     c->sample_rate = sample_rate;
     c->nfft = nfft;
     c->ceplifter = ceplifter;
-    c->fe_fast_ok = im.fast;
+    // a hop so long that the tile kernels' staged span (23 hops + one frame) does not fit the LDS: the float64 kernel, which
+    // reads its frames from global memory, serves the geometry (kws_frontend_math reports it; kws_stream_open refuses)
+    c->fe_fast_ok = im.fast && mfcc_tile_lds_bytes(p) <= MFCC_TILE_LDS_MAX;
     c->fe_ready = true;
     return KWS_OK;
     KWS_GUARD_END(c, "kws_set_frontend")

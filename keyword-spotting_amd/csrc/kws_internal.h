@@ -147,6 +147,10 @@ struct DrawArgs {
 hipError_t launch_augment_draw(hipStream_t s, const DrawArgs& d, int B);
 // true: launch_mfcc picks the wavefront-resident kernel for int16 PCM at this geometry (the fused kernel is a variant of it)
 bool mfcc_wave_resident_ok(const FrontendParams& p);
+// dynamic LDS a tile kernel asks for at this geometry (23 hops + one frame of float32 samples): beyond MFCC_TILE_LDS_MAX the
+// float32 kernels cannot be launched and kws_set_frontend routes the geometry to the float64 kernel
+size_t mfcc_tile_lds_bytes(const FrontendParams& p);
+constexpr size_t MFCC_TILE_LDS_MAX = 160 * 1024;  // the CU's LDS on gfx950
 hipError_t launch_preemphasis(hipStream_t s, const float* d_in, int n, float coeff, float* d_out);
 hipError_t launch_framesig(hipStream_t s, const float* d_in, int n, int frame_len, int frame_step,
                            int num_frames, const float* d_window, float* d_frames);

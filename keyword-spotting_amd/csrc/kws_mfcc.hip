@@ -536,7 +536,8 @@ __global__ __launch_bounds__(64) void kws_stream_frame_kernel(FrontendParams p, 
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
-static size_t mfcc_lds_bytes(const FrontendParams& p) {
+// dynamic LDS of a tile-kernel workgroup: tables, the staged span of its 24 frames, the wavefronts' scratch
+size_t mfcc_tile_lds_bytes(const FrontendParams& p) {
     const int nfp = (p.nfilt + 3) & ~3;
     return sizeof(float) * (size_t)(((p.numcep * nfp + 3) & ~3) + 2 * 64 + ((p.chunk_samples + 7) & ~7)) +
            (size_t)MFCC_WAVES * SCR_BYTES;
@@ -546,7 +547,7 @@ template <typename T, typename K>
 static hipError_t launch_mfcc_t(K kernel, hipStream_t s, const FrontendParams& p, const FrontendTables& t, const T* d_wav,
                                 int B, float* d_out, RefineList rl) {
     dim3 grid((p.num_frames + MFCC_FRAMES_PER_WG - 1) / MFCC_FRAMES_PER_WG, B);
-    const size_t lds = mfcc_lds_bytes(p);
+    const size_t lds = mfcc_tile_lds_bytes(p);
     hipError_t e = raise_lds_limit(kernel, lds);  // geometries (or experiment shapes) beyond the default dynamic-LDS limit opt in per kernel
     if (e != hipSuccess) return e;
     // grid.y is limited to 65535: split very large batches

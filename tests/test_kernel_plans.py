@@ -89,7 +89,12 @@ def test_wavefront_fft_plan_and_real_pair_split():
 native = pytest.importorskip("kws._native")
 
 
-@pytest.mark.parametrize("nfilt,sr", [(26, 16000), (40, 16000), (20, 8000), (13, 22050), (26, 44100)])
+# the filterbanks of tests/test_frontend_geometry_gpu.py section A: deep segments (10, 9 at 16 kHz; 26 at 48 kHz), all 64 lanes (54),
+# the largest fast-path bank (59 at 8 kHz), zero-width segments (32, 39 at 44.1 kHz; 47 at 22.05 kHz)
+SWEEP_BANKS = [(10, 16000), (9, 16000), (54, 16000), (59, 8000), (32, 44100), (39, 44100), (47, 22050), (26, 48000)]
+
+
+@pytest.mark.parametrize("nfilt,sr", [(26, 16000), (40, 16000), (20, 8000), (13, 22050), (26, 44100)] + SWEEP_BANKS)
 def test_host_mel_tables_match_oracle(nfilt, sr):
     edges = native.host_mel_edges(nfilt, 512, sr)
     assert edges.tolist() == o.mel_bin_edges(nfilt, 512, sr).astype(int).tolist()
@@ -99,13 +104,15 @@ def test_host_mel_tables_match_oracle(nfilt, sr):
     assert np.array_equal(fb != 0, ref != 0)  # identical sparsity: 459 non-zeros for the default
 
 
-@pytest.mark.parametrize("nfilt,sr", [(26, 16000), (40, 16000), (20, 8000), (13, 22050), (26, 44100), (54, 16000)])
+@pytest.mark.parametrize("nfilt,sr", [(26, 16000), (40, 16000), (20, 8000), (13, 22050), (26, 44100), (54, 16000)]
+                         + [b for b in SWEEP_BANKS if b != (54, 16000)])
 def test_host_mel_lane_layout(nfilt, sr):
     """Segments sit on adjacent lanes, in order, without overlap, inside the wavefront, and none of them straddles a
     16-lane DPP row (the kernel's segmented sums shift with row_shl); a filterbank that cannot be laid out so is refused."""
     first, count, used, row_safe = native.host_mel_layout(nfilt, 512, sr)
     edges = native.host_mel_edges(nfilt, 512, sr)
-    assert count.tolist() == [-(-int(edges[s + 1] - edges[s]) // 8) for s in range(nfilt + 1)]
+    assert count.tolist() == [-(-int(edges[s + 1] - edges[s]) // 8) for s in range(nfilt + 1)]  # 0 for a zero-width segment
+    assert edges[0] == 0 and edges[-1] == 256 and (np.diff(edges) >= 0).all()  # what the float32 kernel needs besides the layout
     end = 0
     for f, c in zip(first, count):
         assert f >= end  # in order, no overlap (idle lanes may pad)
@@ -117,7 +124,7 @@ def test_host_mel_lane_layout(nfilt, sr):
         native.host_mel_layout(64, 512, 16000)  # 65 segments do not fit 64 lanes
 
 
-@pytest.mark.parametrize("nfilt,numcep,L", [(26, 10, 22), (26, 13, 22), (40, 12, 0)])
+@pytest.mark.parametrize("nfilt,numcep,L", [(26, 10, 22), (26, 13, 22), (40, 12, 0), (32, 32, 22), (10, 10, 0), (25, 10, 1), (54, 32, 40)])
 def test_host_dct_lifter_matches_oracle(nfilt, numcep, L):
     want = o.dct2_ortho_matrix(nfilt, numcep) * o.lifter_vector(numcep, L)[:, None]
     np.testing.assert_allclose(native.host_dct_lifter(nfilt, numcep, L), want, atol=2e-7 * np.abs(want).max())
