@@ -450,6 +450,64 @@ int kws_scan_detect_f32(kws_ctx* ctx, const float* d_logits, int R, int W, int C
                         float threshold, int refractory, float* d_smoothed, int32_t* d_event_window, int32_t* d_event_label,
                         float* d_event_score, int max_events, int32_t* d_event_count);
 
+/* ---- utterances from recordings (the device side of the reference's one live path, kws/inference/inference_local.py:114-192:
+ * an endpointer opens and closes an utterance (:149-166), the captured samples start 600 ms before the trigger (:156,
+ * :176-179), normalize scales them to a peak of 16384 (:102-109) and inference pads or trims to one second and classifies once
+ * (:67-81).  Build-defined where the reference gates on webrtcvad: the voiced decision is the frame's log energy, as
+ * kws_stream_vad_f32) ------------------------------------------------------------------------------------------------ */
+
+/* The MFCC pass of kws_scan_i16 on its own: each of the R recordings is ONE clip of n_total samples under the context's own
+ * front end.  d_pcm: int16 [R, n_total] (device).  d_feat_out: float32 [R, F_total, numcep], F_total = 1 + ceil((n_total -
+ * frame_len) / frame_step), 1 when n_total <= frame_len (kws_host_scan_shape) -- a recording shorter than a window is fine.
+ *   Bit-identical to the d_feat_out of kws_scan_i16 and to kws_mfcc_i16 with B = R on a context configured with n_samples =
+ *   n_total, refinement included, and counted by kws_frontend_stats as those count.  The context's own n_samples is neither
+ *   used nor changed.  Needs a front end (else KWS_ESTATE), no model.  A NULL pointer, R < 1 or n_total < 1: KWS_EINVAL.
+ *   Limits as the scan's (KWS_EUNSUPPORTED beyond): R * F_total <= 2^28, n_total <= 2^30.
+ *   Timed under KWS_K_MFCC / KWS_K_MFCC_REFINE / KWS_K_MFCC_F64.  Asynchronous on the context stream; the refinement worklist
+ *   grows with R * F_total, so the call may allocate and is not for stream capture. */
+int kws_frames_i16(kws_ctx* ctx, const int16_t* d_pcm, int R, int n_total, float* d_feat_out);
+
+/* The endpointer of kws_stream_vad_f32 walked over a whole frame array, with the reference's start point and time-out.
+ *   d_feat: float32 [R, F_total, numcep] (kws_frames_i16, or the d_feat_out of kws_scan_i16); only column 0, the log frame
+ *   energy, is read; the row stride is the context's numcep; frame_len / frame_step are the context's.  n_total: samples per
+ *   recording (it clips an utterance's end).
+ *   Per recording, frames f = 0 .. F_total - 1:  v[f] = feat[f][0] > log_energy_threshold (float32, strict; a NaN is
+ *   unvoiced; frames before 0 are unvoiced).  c_on[f] / c_off[f] = voiced frames among the last on_window / off_window frames
+ *   ending at f.  Walking f upwards with triggered = false, prev_close = -1, count = 0:
+ *     not triggered and 10 c_on[f] > 8 on_window: the utterance opens, open = f (:153); nothing else happens at this frame;
+ *     triggered and 10 (off_window - c_off[f]) > 9 off_window: close at f, reason 0 (:163-164);
+ *     triggered otherwise, max_frames > 0 and f - open + 1 >= max_frames: close at f, reason 1 (build-defined stand-in for
+ *       TimeUse > 10, :164, counted from the open: a recording has no "start of listening" per utterance);
+ *     after these, still triggered at f == F_total - 1: close there, reason 2 (the recording ended).
+ *   A close: start_frame = max(open - pre_roll, prev_close + 1, 0) (the reference starts 20 chunks of 30 ms before the
+ *   trigger, :156; pre_roll is in frames), start_sample = start_frame * frame_step, end_sample = min(n_total, f * frame_step +
+ *   frame_len); if count < max_utts, slot count of d_utt receives (start_sample, end_sample, open, f, reason); then count += 1,
+ *   prev_close = f, triggered = false.
+ *   d_utt: int32 [R, max_utts, 5].  d_count: int32 [R], the full count, even beyond max_utts.  Slots at or beyond the count
+ *   are not written; max_utts == 0 allows a NULL d_utt.  With max_frames == 0 the opens and the reason-0 closes are exactly
+ *   the events of kws_stream_vad_f32 over the same column.
+ *   KWS_EINVAL: outside 1 <= on_window <= off_window <= 1024, pre_roll < 0, max_frames not 0 and below 2, max_utts < 0, R,
+ *   F_total or n_total < 1, a NULL d_feat / d_count (or d_utt with max_utts > 0).  No front end: KWS_ESTATE.  No log energy in
+ *   cepstrum 0: KWS_EUNSUPPORTED (as kws_stream_vad_f32).  R * F_total > 2^28: KWS_EUNSUPPORTED.
+ *   Two launches, asynchronous on the context stream, integers only, no atomics: the same bits run to run.  Scratch of
+ *   4 * R * ceil(F_total / 64) 64-bit words lives in the context and grows on demand (not for stream capture).  Not timed by
+ *   kws_prof_*. */
+int kws_segment_f32(kws_ctx* ctx, const float* d_feat, int R, int F_total, int n_total, float log_energy_threshold, int on_window,
+                    int off_window, int pre_roll, int max_frames, int32_t* d_utt, int max_utts, int32_t* d_count);
+
+/* normalize (:102-109) followed by fix_length (:70) for U spans of samples: d_span int32 [U, 3] = (recording, start, end).
+ *   d_pcm: int16 [R, n_total].  d_clips: int16 [U, n_out]; every element is written.  d_peak: int32 [U] or NULL.
+ *   Per span: start and end are clamped to [0, n_total], len = max(0, end - start).  peak = max |x[i]| over the WHOLE span as
+ *   an int (|-32768| = 32768; 0 for an empty span) -- not over its first n_out samples: the reference normalises before it
+ *   trims.  normalize_to > 0 (the reference's 16384) and peak > 0: times = (double)normalize_to / (double)peak and out[i] =
+ *   (int16) trunc((double)x[start + i] * times) for i < min(len, n_out) -- the float64 divide, multiply and truncation towards
+ *   zero of Python's int(i * times).  peak == 0 writes zeros (the reference raises ZeroDivisionError).  normalize_to == 0 is a
+ *   plain copy.  out[i] = 0 for i >= len.  A recording index outside [0, R) reads nothing: a zero clip and peak = -1.
+ *   KWS_EINVAL: normalize_to outside [0, 32767], U, R, n_total or n_out < 1, a NULL d_pcm / d_span / d_clips.  Needs neither a
+ *   front end nor a model.  One launch, asynchronous on the context stream, deterministic; not timed by kws_prof_*. */
+int kws_cut_i16(kws_ctx* ctx, const int16_t* d_pcm, int R, int n_total, const int32_t* d_span, int U, int normalize_to,
+                int16_t* d_clips, int n_out, int32_t* d_peak);
+
 /* ---- sample-rate conversion on the device (replaces the resampling inside librosa.load(path, sr=...),
  * kws/libs/audio_processor.py:120,145; PARITY UNPINNED against librosa's soxr: what is pinned is the project's own host
  * definition, scipy.signal.resample_poly(x, up, down, window=("kaiser", 14.0)) with zero padding, in float64) ---------------- */

@@ -1,0 +1,245 @@
+// Utterances from recordings (include/kws_hip.h: kws_frames_i16, kws_segment_f32, kws_cut_i16) -- the device side of the
+// reference's record-then-classify loop (kws/inference/inference_local.py:114-192): the MFCC pass of a scan on its own, the
+// energy endpointer walked over a whole frame array with the reference's start point and time-out, and normalize + fix_length
+// for a list of sample spans.  What follows a clip (kws_infer_i16) is elsewhere; nothing here touches another unit's kernels.
+#include "kws_ctx.h"
+
+using namespace kws;
+
+namespace {
+
+constexpr int SEG_THREADS = 256;                 // frames per workgroup of the flag kernel: four ballot words
+constexpr int SEG_WORDS = SEG_THREADS / 64;
+constexpr int SEG_MAX_WINDOW = 1024;             // off_window's limit (as kws_stream_vad_f32)
+constexpr int SEG_BACK_WORDS = SEG_MAX_WINDOW / 64;  // ballot words of history a workgroup can need: ceil((1024 - 1) / 64)
+constexpr int CUT_THREADS = 256;
+
+// Voiced frames among the `window` frames ending at local frame `at` (bit b of words[j] = local frame 64 j + b; at >= window - 1).
+__device__ __forceinline__ int voiced_in_window(const unsigned long long* words, int at, int window) {
+    const int lo = at - window + 1;
+    const int j0 = lo >> 6, j1 = at >> 6;
+    int n = 0;
+    for (int j = j0; j <= j1; ++j) {
+        unsigned long long m = words[j];
+        if (j == j0) m &= ~0ull << (lo & 63);
+        if (j == j1) m &= ~0ull >> (63 - (at & 63));
+        n += __popcll(m);
+    }
+    return n;
+}
+
+// Per frame: may an utterance open here, may one close here?  One thread per frame, 256 frames of one recording per workgroup.
+// The workgroup first packs the voiced flags of its own frames and of the `back` words before them (frames before 0 and past
+// F are unvoiced) into ballot words in LDS -- wavefront v takes words v, v + 4, ... -- then every thread counts its two
+// windows as popcounts over at most 17 words and the wavefront's answers leave as two ballot words:
+//   open_ok[f]  = 10 c_on[f] > 8 on_window,  close_ok[f] = 10 (off_window - c_off[f]) > 9 off_window.
+// ok: [R][2][n_words], n_words = ceil(F / 64); bits at or beyond F are zero.
+__global__ __launch_bounds__(SEG_THREADS) void kws_segment_flags_kernel(const float* __restrict__ feat, int F, int numcep, float threshold,
+                                                                        int on_window, int off_window, int back, int n_words,
+                                                                        int groups_per_rec, unsigned long long* __restrict__ ok) {
+    __shared__ unsigned long long words[SEG_BACK_WORDS + SEG_WORDS];
+    const int r = blockIdx.x / groups_per_rec, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int f0 = (blockIdx.x % groups_per_rec) * SEG_THREADS;
+    const int base = f0 - back * 64;  // the frame of bit 0 of words[0]; may be negative
+    const float* fr = feat + (size_t)r * F * numcep;
+    for (int j = wave; j < back + SEG_WORDS; j += SEG_WORDS) {  // wave-uniform
+        const int g = base + j * 64 + lane;
+        const bool voiced = g >= 0 && g < F && fr[(size_t)g * numcep] > threshold;  // a NaN compares false: unvoiced
+        const unsigned long long b = __ballot(voiced);
+        if (lane == 0) words[j] = b;
+    }
+    __syncthreads();
+    const int f = f0 + threadIdx.x;
+    const int at = back * 64 + threadIdx.x;  // back * 64 >= off_window - 1: both windows start inside words[]
+    const int c_on = voiced_in_window(words, at, on_window);
+    const int c_off = voiced_in_window(words, at, off_window);
+    const unsigned long long open_ok = __ballot(f < F && 10 * c_on > 8 * on_window);
+    const unsigned long long close_ok = __ballot(f < F && 10 * (off_window - c_off) > 9 * off_window);
+    const int w = f0 / 64 + wave;
+    if (lane == 0 && w < n_words) {
+        unsigned long long* o = ok + (size_t)r * 2 * n_words;
+        o[w] = open_ok;
+        o[n_words + w] = close_ok;
+    }
+}
+
+// The walk, one wavefront per recording.  Every lane holds one open_ok and one close_ok word of a chunk of 64 words (4096
+// frames); the walk alternates between "first open_ok at or after f" and "first close_ok after the open, or the time-out at
+// open + max_frames - 1"; words without a bit are passed over through a ballot of the non-empty lanes, so a chunk costs a few
+// steps per utterance, not one per word.  f moves forward in every iteration, so the loop ends for any input.  Everything is
+// wave-uniform; lane 0 stores.  utt: [R][max_utts][5] = (start_sample, end_sample, open, close, reason).
+__global__ __launch_bounds__(64) void kws_segment_walk_kernel(const unsigned long long* __restrict__ ok, int F, int n_words, int n_total,
+                                                              int frame_len, int frame_step, int pre_roll, int max_frames,
+                                                              int32_t* __restrict__ utt, int max_utts, int32_t* __restrict__ count_out) {
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const unsigned long long* o = ok + (size_t)r * 2 * n_words;
+    int32_t* ur = utt + (size_t)r * max_utts * 5;
+    bool triggered = false;
+    int open = 0, prev_close = -1, count = 0;
+    auto close_at = [&](int f, int reason) {
+        long long start = (long long)open - pre_roll;
+        if (start < prev_close + 1) start = prev_close + 1;  // prev_close + 1 >= 0
+        const long long end = (long long)f * frame_step + frame_len;
+        if (lane == 0 && count < max_utts) {
+            int32_t* u = ur + (size_t)count * 5;
+            u[0] = (int32_t)(start * frame_step);
+            u[1] = (int32_t)(end < n_total ? end : n_total);
+            u[2] = open;
+            u[3] = f;
+            u[4] = reason;
+        }
+        ++count;
+        prev_close = f;
+        triggered = false;
+    };
+    int f = 0;
+    for (int w0 = 0; w0 < n_words; w0 += 64) {
+        const int mine = w0 + lane;
+        const unsigned long long open_w = mine < n_words ? o[mine] : 0ull;
+        const unsigned long long close_w = mine < n_words ? o[n_words + mine] : 0ull;
+        const int chunk_end = (w0 + 64 < n_words ? w0 + 64 : n_words) * 64;  // first frame past this chunk's words
+        const unsigned long long open_any = __ballot(open_w != 0), close_any = __ballot(close_w != 0);  // lanes whose word has a bit
+        // the first frame of the next word of this chunk, after word w, that `any` marks; the chunk's end when there is none
+        auto skip_to = [&](unsigned long long any, int w) {
+            const unsigned long long rest = w - w0 < 63 ? any & (~0ull << (w - w0 + 1)) : 0ull;
+            return rest ? (w0 + __builtin_ctzll(rest)) * 64 : chunk_end;
+        };
+        while (f < chunk_end) {  // f == w0 * 64 on entry: no step below passes the chunk's end
+            const int w = f >> 6;
+            const unsigned long long from = ~0ull << (f & 63);
+            const int next_word = (w + 1) * 64;
+            if (!triggered) {
+                const unsigned long long m = __shfl(open_w, w - w0) & from;
+                if (!m) {
+                    f = skip_to(open_any, w);
+                    continue;
+                }
+                open = w * 64 + __builtin_ctzll(m);
+                triggered = true;
+                f = open + 1;  // nothing else happens at the opening frame
+                continue;
+            }
+            const unsigned long long m = __shfl(close_w, w - w0) & from;
+            const long long limit = max_frames > 0 ? (long long)open + max_frames - 1 : (long long)F;  // >= f: max_frames >= 2
+            const int cand = m ? w * 64 + __builtin_ctzll(m) : next_word;
+            if (m && cand <= limit) {
+                close_at(cand, 0);
+                f = cand + 1;
+            } else if (limit < next_word && limit < F) {
+                close_at((int)limit, 1);
+                f = (int)limit + 1;
+            } else {  // neither in this word: on to the next word with a close_ok bit, or to the time-out's word if that comes first
+                int next = skip_to(close_any, w);
+                if (limit < F && (int)(limit >> 6) * 64 < next) next = (int)(limit >> 6) * 64;  // limit >= next_word here: still forward
+                f = next;
+            }
+        }
+    }
+    if (triggered) close_at(F - 1, 2);  // the recording ended inside an utterance
+    if (lane == 0) count_out[r] = count;
+}
+
+// normalize (inference_local.py:102-109) then fix_length (:70) of one span per workgroup: the peak over the WHOLE span (the
+// reference normalises before it trims), then n_out samples, scaled in float64 and truncated towards zero as int(i * times),
+// zero beyond the span.  A span starts at any sample: 2-byte loads.
+__global__ __launch_bounds__(CUT_THREADS) void kws_cut_i16_kernel(const int16_t* __restrict__ pcm, int R, int n_total,
+                                                                  const int32_t* __restrict__ span, int normalize_to,
+                                                                  int16_t* __restrict__ clips, int n_out, int32_t* __restrict__ peak_out) {
+    __shared__ int wave_peak[CUT_THREADS / 64];
+    const int u = blockIdx.x, tid = threadIdx.x;
+    const int r = span[3 * (size_t)u];
+    int start = span[3 * (size_t)u + 1], end = span[3 * (size_t)u + 2];
+    start = start < 0 ? 0 : (start > n_total ? n_total : start);
+    end = end < 0 ? 0 : (end > n_total ? n_total : end);
+    const bool in_range = r >= 0 && r < R;  // workgroup-uniform
+    const int len = in_range && end > start ? end - start : 0;
+    const int16_t* x = pcm + (in_range ? (size_t)r * n_total + start : 0);
+    int16_t* out = clips + (size_t)u * n_out;
+    int peak = 0;
+    for (unsigned i = tid; i < (unsigned)len; i += CUT_THREADS) {
+        const int v = x[i];
+        const int a = v < 0 ? -v : v;  // |-32768| = 32768
+        peak = a > peak ? a : peak;
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        const int other = __shfl_xor(peak, d);
+        peak = other > peak ? other : peak;
+    }
+    if ((tid & 63) == 0) wave_peak[tid >> 6] = peak;
+    __syncthreads();
+    peak = wave_peak[0];
+    for (int k = 1; k < CUT_THREADS / 64; ++k) peak = wave_peak[k] > peak ? wave_peak[k] : peak;
+    if (tid == 0 && peak_out) peak_out[u] = in_range ? peak : -1;
+    const int body = len < n_out ? len : n_out;
+    if (normalize_to > 0) {
+        const double times = peak > 0 ? (double)normalize_to / (double)peak : 0.0;  // peak 0: the span is all zeros anyway
+        for (unsigned i = tid; i < (unsigned)n_out; i += CUT_THREADS) out[i] = i < (unsigned)body ? (int16_t)(int)((double)x[i] * times) : (int16_t)0;
+    } else {
+        for (unsigned i = tid; i < (unsigned)n_out; i += CUT_THREADS) out[i] = i < (unsigned)body ? x[i] : (int16_t)0;
+    }
+}
+
+}  // namespace
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int kws_frames_i16(kws_ctx* c, const int16_t* d_pcm, int R, int n_total, float* d_feat_out) {
+    if (!c) return KWS_EINVAL;
+    if (!d_pcm || !d_feat_out) return fail(c, KWS_EINVAL, "kws_frames_i16: d_pcm / d_feat_out is NULL");
+    if (R < 1 || n_total < 1) return fail(c, KWS_EINVAL, "kws_frames_i16: R and n_total must be positive");
+    if (!c->fe_ready) return fail(c, KWS_ESTATE, "kws_frames_i16: front end not configured");
+    if (n_total > (1 << 30)) return fail(c, KWS_EUNSUPPORTED, "kws_frames_i16: more than 2^30 samples per recording");
+    FrontendParams p = c->fp;  // the context's geometry and arithmetic; the recording is one clip of n_total samples
+    set_clip_length(p, n_total);
+    const int F = p.num_frames;
+    if ((unsigned long long)R * F > (1ull << 28)) return fail(c, KWS_EUNSUPPORTED, "kws_frames_i16: more than 2^28 frames in one call");
+    // the refinement's grid: the batch in clips of the context's own length, as kws_scan_i16 sizes it
+    return run_frontend(c, p, d_pcm, R, d_feat_out, (int)((unsigned long long)R * F / c->fp.num_frames + 1));
+}
+
+int kws_segment_f32(kws_ctx* c, const float* d_feat, int R, int F_total, int n_total, float log_energy_threshold, int on_window,
+                    int off_window, int pre_roll, int max_frames, int32_t* d_utt, int max_utts, int32_t* d_count) {
+    if (!c) return KWS_EINVAL;
+    if (!d_feat || !d_count) return fail(c, KWS_EINVAL, "kws_segment_f32: d_feat / d_count is NULL");
+    if (R < 1 || F_total < 1 || n_total < 1) return fail(c, KWS_EINVAL, "kws_segment_f32: R, F_total and n_total must be positive");
+    if (on_window < 1 || off_window < on_window || off_window > SEG_MAX_WINDOW)
+        return fail(c, KWS_EINVAL, "kws_segment_f32: need 1 <= on_window <= off_window <= 1024");
+    if (pre_roll < 0 || (max_frames != 0 && max_frames < 2))
+        return fail(c, KWS_EINVAL, "kws_segment_f32: need pre_roll >= 0 and max_frames == 0 or >= 2");
+    if (max_utts < 0 || (max_utts > 0 && !d_utt)) return fail(c, KWS_EINVAL, "kws_segment_f32: max_utts utterances need d_utt");
+    if (!c->fe_ready) return fail(c, KWS_ESTATE, "kws_segment_f32: front end not configured");
+    if (!c->fp.append_energy) return fail(c, KWS_EUNSUPPORTED, "kws_segment_f32: needs cepstrum 0 = log frame energy (appendEnergy)");
+    if ((unsigned long long)R * F_total > (1ull << 28)) return fail(c, KWS_EUNSUPPORTED, "kws_segment_f32: more than 2^28 frames in one call");
+    HIP_TRY(c, hipSetDevice(c->device));
+    // context scratch: open_ok and close_ok as ballot words, [R][2][n_words] of 64 bits
+    const int n_words = (F_total + 63) / 64;
+    int rc = grow_device_buffer(c, c->d_conv_ws, c->conv_ws_floats, (size_t)R * 2 * n_words * 2, "kws_segment_f32", "workspace");
+    if (rc) return rc;
+    unsigned long long* ok = reinterpret_cast<unsigned long long*>(c->d_conv_ws);
+    const int back = (off_window - 1 + 63) / 64;  // words of history before a workgroup's first frame: <= 16
+    const int groups_per_rec = (F_total + SEG_THREADS - 1) / SEG_THREADS;  // R * groups_per_rec <= 2^28 / 256 + R workgroups
+    hipLaunchKernelGGL(kws_segment_flags_kernel, dim3((unsigned)R * (unsigned)groups_per_rec), dim3(SEG_THREADS), 0, c->stream, d_feat,
+                       F_total, c->fp.numcep, log_energy_threshold, on_window, off_window, back, n_words, groups_per_rec, ok);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(kws_segment_walk_kernel, dim3(R), dim3(64), 0, c->stream, ok, F_total, n_words, n_total, c->fp.frame_len,
+                       c->fp.frame_step, pre_roll, max_frames, d_utt, max_utts, d_count);
+    HIP_TRY(c, hipGetLastError());
+    return KWS_OK;
+}
+
+int kws_cut_i16(kws_ctx* c, const int16_t* d_pcm, int R, int n_total, const int32_t* d_span, int U, int normalize_to, int16_t* d_clips,
+                int n_out, int32_t* d_peak) {
+    if (!c) return KWS_EINVAL;
+    if (!d_pcm || !d_span || !d_clips) return fail(c, KWS_EINVAL, "kws_cut_i16: d_pcm / d_span / d_clips is NULL");
+    if (U < 1 || R < 1 || n_total < 1 || n_out < 1) return fail(c, KWS_EINVAL, "kws_cut_i16: U, R, n_total and n_out must be positive");
+    if (normalize_to < 0 || normalize_to > 32767) return fail(c, KWS_EINVAL, "kws_cut_i16: normalize_to must be in [0, 32767]");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(kws_cut_i16_kernel, dim3(U), dim3(CUT_THREADS), 0, c->stream, d_pcm, R, n_total, d_span, normalize_to, d_clips,
+                       n_out, d_peak);
+    HIP_TRY(c, hipGetLastError());
+    return KWS_OK;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

@@ -93,6 +93,10 @@ SIGNATURES = {
     "kws_scan_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, _f32p]),
     "kws_scan_detect_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _f32p, _i32p, _i32p,
                                       _f32p, C.c_int, _i32p]),
+    "kws_frames_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, C.c_int, _f32p]),
+    "kws_segment_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, C.c_int,
+                                  _i32p]),
+    "kws_cut_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _i16p, C.c_int, _i32p]),
     "kws_resample_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _i16p, C.c_int]),
     "kws_resample_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _f32p, C.c_int]),
     "kws_host_stream_resample_plan": (C.c_int, [C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4),
@@ -438,6 +442,28 @@ class Context:
         self._check(self._lib.kws_scan_detect_f32(self._h, _ptr(logits), R, W, Cn, int(smooth_window), int(first_keyword), float(threshold),
                                                   int(refractory), p(smoothed), p(event_window), p(event_label), p(event_score),
                                                   int(max_events), _ptr(event_count)), ModelError)
+
+    # -- utterances --------------------------------------------------------------------------------
+    def frames_i16(self, pcm, feat):
+        """``kws_frames_i16``: ``pcm`` int16 [R, n_total] on the device -> ``feat`` float32 [R, F_total, numcep], each recording
+        one clip of the context's front end (``host_scan_shape`` gives F_total)."""
+        self._check(self._lib.kws_frames_i16(self._h, _ptr(pcm), int(pcm.shape[0]), int(pcm.shape[1]), _ptr(feat)), AudioProcessingError)
+
+    def segment_f32(self, feat, n_total, threshold, count, utt=None, max_utts=0, on_window=40, off_window=80, pre_roll=60,
+                    max_frames=1000):
+        """``kws_segment_f32``: the endpointer walked over ``feat`` float32 [R, F_total, numcep] (column 0).  ``count`` int32 [R];
+        ``utt`` int32 [R, max_utts, 5] = (start_sample, end_sample, open, close, reason 0 endpoint / 1 max length / 2 end of
+        recording) or None with ``max_utts`` 0."""
+        self._check(self._lib.kws_segment_f32(self._h, _ptr(feat), int(feat.shape[0]), int(feat.shape[1]), int(n_total), float(threshold),
+                                              int(on_window), int(off_window), int(pre_roll), int(max_frames),
+                                              _ptr(utt) if utt is not None else None, int(max_utts), _ptr(count)), ModelError)
+
+    def cut_i16(self, pcm, span, clips, normalize_to=16384, peak=None):
+        """``kws_cut_i16``: normalize + fix_length of ``span`` int32 [U, 3] = (recording, start, end) over ``pcm`` int16
+        [R, n_total] into ``clips`` int16 [U, n_out]; ``peak`` int32 [U] or None."""
+        self._check(self._lib.kws_cut_i16(self._h, _ptr(pcm), int(pcm.shape[0]), int(pcm.shape[1]), _ptr(span), int(span.shape[0]),
+                                          int(normalize_to), _ptr(clips), int(clips.shape[1]), _ptr(peak) if peak is not None else None),
+                    AudioProcessingError)
 
     # -- sample-rate conversion --------------------------------------------------------------------
     def _resample(self, fn, x, rate_in, rate_out, out, lengths):

@@ -45,6 +45,27 @@ class ScanResult:
     events: Optional[List[List[Tuple[float, int, str, float]]]] = None
 
 
+UTTERANCE_REASONS = ("endpoint", "max_length", "end_of_recording")  # kws_segment_f32's reasons 0, 1, 2
+
+
+@dataclass
+class Utterance:
+    """One utterance ``KeywordSpotter.segment`` found: where it lies in its recording (seconds), why it closed and what the
+    model says about its normalised, one-second clip.  ``start_s`` is ``pre_roll`` frames before ``open_s``, the frame at which
+    the endpointer triggered; ``end_s`` is the end of the closing frame ``close_s`` starts; ``peak`` is the largest sample
+    magnitude of the span before normalisation."""
+    recording: int
+    start_s: float
+    end_s: float
+    open_s: float
+    close_s: float
+    reason: str
+    label: int
+    word: str
+    logits: np.ndarray  # float32 [C]
+    peak: int
+
+
 class KeywordSpotter:
     """Holds a model on one GPU and maps wav files / PCM batches to (index, word)."""
 
@@ -187,19 +208,7 @@ class KeywordSpotter:
         rate (``kws_resample_i16``) and the result is scanned, so window and event times stay in seconds of the recording."""
         from kws import _native
 
-        if torch.is_tensor(pcm):
-            if pcm.dtype != torch.int16:
-                raise ModelError(f"scan expects int16 PCM, got {pcm.dtype}")
-            x = pcm
-        else:
-            a = np.asarray(pcm)
-            if a.dtype != np.int16:
-                raise ModelError(f"scan expects int16 PCM, got {a.dtype}")
-            x = torch.from_numpy(np.ascontiguousarray(a))
-        if x.dim() == 1:
-            x = x[None, :]
-        if x.dim() != 2 or x.shape[0] < 1:
-            raise ModelError(f"scan expects int16 [n] or [R, n], got shape {tuple(x.shape)}")
+        x = self._recordings(pcm, "scan")
         if int(hop_frames) < 1:
             raise ModelError("scan: hop_frames must be at least 1")
         if threshold is not None:
@@ -208,13 +217,7 @@ class KeywordSpotter:
             if int(refractory) < 1 or int(first_keyword) < 0 or int(max_events) < 0:
                 raise ModelError("scan: need refractory >= 1, first_keyword >= 0 and max_events >= 0")
         cfg = self.config
-        if sample_rate is not None and int(sample_rate) != cfg.sample_rate:
-            if x.shape[1] < 1:
-                raise ModelError("scan: the recording is empty")
-            src = x.to(self.device).contiguous()
-            x = torch.empty((src.shape[0], _native.host_resample_len(src.shape[1], sample_rate, cfg.sample_rate)), dtype=torch.int16,
-                            device=self.device)
-            self.model._context(self.device.index or 0).resample_i16(src, sample_rate, cfg.sample_rate, x)
+        x = self._at_configured_rate(x, sample_rate, "scan")
         frame_len, frame_step = _round_half_up(cfg.frame_length * cfg.sample_rate), _round_half_up(cfg.frame_step * cfg.sample_rate)
         R, n = int(x.shape[0]), int(x.shape[1])
         frames, W = (0, 0) if n < 1 else _native.host_scan_shape(n, frame_len, frame_step, WINDOW_FRAMES, int(hop_frames))
@@ -257,6 +260,121 @@ class KeywordSpotter:
         if x.ndim == 2:
             raise AudioProcessingError(f"{path}: {x.shape[1]} channels; scan_file takes mono files")
         return self.scan(x, **kwargs)
+
+    def _recordings(self, pcm, what: str) -> torch.Tensor:
+        """int16 ``[n]`` or ``[R, n]``, host array or device tensor -> an int16 tensor ``[R, n]`` (the checks of ``scan``)."""
+        if torch.is_tensor(pcm):
+            if pcm.dtype != torch.int16:
+                raise ModelError(f"{what} expects int16 PCM, got {pcm.dtype}")
+            x = pcm
+        else:
+            a = np.asarray(pcm)
+            if a.dtype != np.int16:
+                raise ModelError(f"{what} expects int16 PCM, got {a.dtype}")
+            x = torch.from_numpy(np.ascontiguousarray(a))
+        if x.dim() == 1:
+            x = x[None, :]
+        if x.dim() != 2 or x.shape[0] < 1:
+            raise ModelError(f"{what} expects int16 [n] or [R, n], got shape {tuple(x.shape)}")
+        return x
+
+    def _at_configured_rate(self, x: torch.Tensor, sample_rate: Optional[int], what: str) -> torch.Tensor:
+        """Recordings at ``sample_rate`` -> the same at the configured rate, resampled on the device to their natural length
+        (``kws_resample_i16``); ``x`` itself when the rate is the configured one."""
+        from kws import _native
+
+        cfg = self.config
+        if sample_rate is None or int(sample_rate) == cfg.sample_rate:
+            return x
+        if x.shape[1] < 1:
+            raise ModelError(f"{what}: the recording is empty")
+        src = x.to(self.device).contiguous()
+        y = torch.empty((src.shape[0], _native.host_resample_len(src.shape[1], sample_rate, cfg.sample_rate)), dtype=torch.int16,
+                        device=self.device)
+        self.model._context(self.device.index or 0).resample_i16(src, sample_rate, cfg.sample_rate, y)
+        return y
+
+    def segment(self, pcm, threshold: float, on_window: int = 40, off_window: int = 80, pre_roll: int = 60, max_seconds: float = 10.0,
+                normalize: int = 16384, max_utterances: int = 1024, sample_rate: Optional[int] = None,
+                keep_unfinished: bool = True) -> List[List[Utterance]]:
+        """Which utterances are in this audio, and what was said in each?  The reference's live loop
+        (``kws/inference/inference_local.py:114-192``) over recordings: ``pcm`` int16 ``[n]`` or ``[R, n]``, a host array or a
+        device tensor, ``sample_rate`` as in ``scan``.  One list of ``Utterance`` per recording, in time order.
+
+        On the device, in this order: the MFCC frames of each recording as one clip (``kws_frames_i16``); the energy endpointer
+        walked over them (``kws_segment_f32``) -- a frame is voiced when its log energy exceeds ``threshold``, an utterance opens
+        when more than 80 % of the last ``on_window`` frames are voiced and closes when more than 90 % of the last ``off_window``
+        are not (400 / 800 ms by default), after ``max_seconds`` (0: never) or with the recording, and starts ``pre_roll`` frames
+        (600 ms) before it opened; then ONE device-to-host read of the counts and spans -- the only synchronisation before the
+        results, needed because the number of clips sizes what follows; the spans cut, scaled to a peak of ``normalize`` (0: as
+        they are) and padded or trimmed to a clip (``kws_cut_i16``); and the model once per clip (``kws_infer_i16``).  With no
+        utterance nothing further is launched.  At most ``max_utterances`` per recording are returned;
+        ``keep_unfinished=False`` drops those the end of the recording closed."""
+        from kws import _native
+
+        x = self._recordings(pcm, "segment")
+        if not 1 <= int(on_window) <= int(off_window) <= 1024:
+            raise ModelError("segment: need 1 <= on_window <= off_window <= 1024")
+        if int(pre_roll) < 0 or int(max_utterances) < 0 or not 0 <= int(normalize) <= 32767:
+            raise ModelError("segment: need pre_roll >= 0, max_utterances >= 0 and normalize in [0, 32767]")
+        cfg = self.config
+        x = self._at_configured_rate(x, sample_rate, "segment")
+        frame_len, frame_step = _round_half_up(cfg.frame_length * cfg.sample_rate), _round_half_up(cfg.frame_step * cfg.sample_rate)
+        max_frames = int(round(float(max_seconds) * cfg.sample_rate / frame_step))
+        if max_frames == 1 or max_frames < 0:
+            raise ModelError("segment: max_seconds must be 0 (no limit) or at least two frames")
+        R, n = int(x.shape[0]), int(x.shape[1])
+        if n < 1:
+            raise ModelError("segment: the recording is empty")
+        F, _ = _native.host_scan_shape(n, frame_len, frame_step, WINDOW_FRAMES, 1)
+        ctx = self.model._context(self.device.index or 0)
+        x = x.to(self.device).contiguous()
+        m = int(max_utterances)
+        feat = torch.empty((R, F, cfg.num_cepstral_coeffs), dtype=torch.float32, device=self.device)
+        found = torch.empty((R + 5 * R * m,), dtype=torch.int32, device=self.device)  # the counts [R], then the slots [R, m, 5]
+        ctx.frames_i16(x, feat)
+        ctx.segment_f32(feat, n, threshold, found[:R], found[R:] if m else None, m, on_window, off_window, pre_roll, max_frames)
+        host = found.cpu().numpy()  # the one device-to-host read (it waits for the stream): counts and spans together
+        counts, slots = host[:R], host[R:].reshape(R, m, 5)
+        rows = []  # (recording, start, end, open, close, reason): the compact list, in recording and time order
+        for r in range(R):
+            for i in range(min(int(counts[r]), m)):
+                start, end, opened, closed, reason = (int(v) for v in slots[r, i])
+                if reason == 2 and not keep_unfinished:
+                    continue
+                rows.append((r, start, end, opened, closed, reason))
+        out: List[List[Utterance]] = [[] for _ in range(R)]
+        if not rows:
+            return out
+        U, C = len(rows), self.model.num_classes
+        span = torch.tensor([row[:3] for row in rows], dtype=torch.int32).to(self.device)
+        clips = torch.empty((U, cfg.desired_samples), dtype=torch.int16, device=self.device)
+        peak = torch.empty((U,), dtype=torch.int32, device=self.device)
+        logits = torch.empty((U, C), dtype=torch.float32, device=self.device)
+        labels = torch.empty((U,), dtype=torch.int32, device=self.device)
+        ctx.cut_i16(x, span, clips, int(normalize), peak)
+        ctx.infer_i16(clips, logits, labels)
+        logits, labels, peak = logits.cpu().numpy(), labels.cpu().numpy(), peak.cpu().numpy()
+        rate = float(cfg.sample_rate)
+        for u, (r, start, end, opened, closed, reason) in enumerate(rows):
+            out[r].append(Utterance(r, start / rate, end / rate, opened * frame_step / rate, closed * frame_step / rate,
+                                    UTTERANCE_REASONS[reason], int(labels[u]), self.words[int(labels[u])], logits[u].copy(), int(peak[u])))
+        return out
+
+    def segment_file(self, path: str, resample: bool = False, **kwargs) -> List[Utterance]:
+        """``segment`` over a whole wav file; the file's utterances.  The file must be 16-bit mono PCM at the configured rate;
+        with ``resample=True`` a 16-bit mono file at another rate is resampled on the device (as ``scan_file``)."""
+        if resample:
+            x, rate = read_wav(path)
+            if rate != self.config.sample_rate:
+                if x.dtype != np.int16:
+                    raise AudioProcessingError(f"{path}: sample rate {rate} != {self.config.sample_rate} and the file is not 16-bit mono "
+                                               "PCM; the device resampler of segment_file takes int16 only")
+                return self.segment(x, sample_rate=rate, **kwargs)[0]
+        x = load_pcm16(path, self.config.sample_rate)
+        if x.ndim == 2:
+            raise AudioProcessingError(f"{path}: {x.shape[1]} channels; segment_file takes mono files")
+        return self.segment(x, **kwargs)[0]
 
 
 _default: Optional[KeywordSpotter] = None
