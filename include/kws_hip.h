@@ -508,6 +508,82 @@ int kws_segment_f32(kws_ctx* ctx, const float* d_feat, int R, int F_total, int n
 int kws_cut_i16(kws_ctx* ctx, const int16_t* d_pcm, int R, int n_total, const int32_t* d_span, int U, int normalize_to,
                 int16_t* d_clips, int n_out, int32_t* d_peak);
 
+/* ---- live utterances (the same loop, :114-192, for the streams of kws_stream_open: the walk of kws_segment_f32 taken one
+ * frame per hop, a PCM history per stream to cut from, events in a queue the host reads without a copy) ------------------ */
+
+/* Host only: the history a stream needs, in samples.  K = ceil(frame_len / frame_step) hops complete a frame.
+ *   *history_samples = (pre_roll + max_frames - 1 + K + slack_hops) * frame_step: the longest span an utterance can have,
+ *   (pre_roll + max_frames - 1) * frame_step + frame_len, rounded up to whole hops, plus slack_hops hops that may be pushed
+ *   between a close and its cut (kws_stream_utt_cut_i16 refuses a span whose start has left the ring).
+ *   KWS_EINVAL: frame_len or frame_step < 1, pre_roll < 0, max_frames < 2, slack_hops < 0, a NULL pointer, or a result beyond
+ *   INT_MAX. */
+int kws_host_stream_utt_history(int frame_len, int frame_step, int pre_roll, int max_frames, int slack_hops, int* history_samples);
+
+/* Arm the open stream set: from here to kws_stream_utt_close (or kws_stream_open / kws_stream_close / kws_set_frontend, which
+ * drop it with the streams) every push -- kws_stream_push_i16, kws_stream_push_host_i16, kws_stream_push_rate_i16,
+ * kws_stream_push_host_rate_i16 -- enqueues ONE more launch behind its own (with use_graph: behind the replay, outside the
+ * captured graph): the step kernel, one workgroup, one thread per stream.  A push's logits and labels are the bits of an
+ * unarmed push; an unarmed context launches nothing new.
+ *   Stream time counts from this call: sample 0 is the first sample pushed after it, frame f covers samples [f * frame_step,
+ *   f * frame_step + frame_len), and the set's push number h (from 1) completes frame h - K; the first K - 1 pushes append PCM
+ *   and walk nothing (as kws_stream_vad_f32 reports nothing for them).
+ *   The step, per push: (1) APPEND each stream's newest hop to its history ring int16 [n_streams, history_samples] at (hops *
+ *   frame_step) mod history_samples.  The hop is read from the CONTEXT'S OWN PCM ring, not from the caller's pointer: the ring
+ *   is device-resident, the same for all four entries, holds the RESAMPLED hop for the rate pushes (what the front end heard),
+ *   and a step still running when kws_stream_push_host_i16 has returned and its pinned hop slot is being rewritten reads
+ *   nothing of that slot.  (2) WALK one frame with exactly the rules of kws_segment_f32 above: v = c0 > threshold (float32,
+ *   strict, a NaN is unvoiced; c0 = the newest row of the feature ring); the window counts are kept per stream and updated in
+ *   O(1) -- add the new flag, subtract the flag leaving, from a ring of 1024 flag bits; not triggered and 10 c_on > 8
+ *   on_window: open = f, nothing else at this frame; triggered and 10 (off_window - c_off) > 9 off_window: close, reason 0;
+ *   else triggered and f - open + 1 >= max_frames: close, reason 1.  A close: start_frame = max(open - pre_roll, prev_close + 1,
+ *   0), start_sample = start_frame * frame_step, end_sample = f * frame_step + frame_len (never clipped: a walked frame is
+ *   complete), prev_close = f.  (3) EMIT: the streams that closed at this step get consecutive sequence numbers in ascending
+ *   stream order (wavefront ballots and a prefix over the wavefronts; no atomics: the same bits run to run).  A record is
+ *   int64 [6] = (stream, start_sample, end_sample, open_frame, close_frame, reason), written at seq mod max_events to the device
+ *   queue and to its mirror in pinned, device-mapped host memory (system-scope stores; the totals and then a completion count
+ *   are published behind them, as kws_stream_host_results delivers logits).  A queue of max_events records keeps the newest
+ *   max_events; older ones are overwritten.
+ *   Needs an open stream set (else KWS_ESTATE) and the log energy in cepstrum 0 (else KWS_EUNSUPPORTED, as kws_stream_vad_f32).
+ *   KWS_EINVAL: outside 1 <= on_window <= off_window <= 1024; pre_roll < 0; max_frames < 2 (a live ring is bounded: there is no
+ *   "no time-out"); history_samples below kws_host_stream_utt_history(..., slack_hops = 0) for the context's frame geometry or
+ *   not a multiple of frame_step; max_events < n_streams (all streams may close at one step).  n_streams > 1024:
+ *   KWS_EUNSUPPORTED.  Waits for the context stream, allocates; a second call replaces the first.  Independent of
+ *   kws_stream_vad_f32, whose state and results it neither reads nor changes.  No entry below allocates. */
+int kws_stream_utt_open(kws_ctx* ctx, float log_energy_threshold, int on_window, int off_window, int pre_roll, int max_frames,
+                        int history_samples, int max_events);
+/* Waits for the context stream and releases what kws_stream_utt_open allocated; nothing when the context is not armed. */
+int kws_stream_utt_close(kws_ctx* ctx);
+/* The explicit step, for callers with their own front end (and the tests): d_hop int16 [n_streams, frame_step] (device), if
+ * not NULL, is appended; d_energy float32 [n_streams] (device), if not NULL, walks one frame with these energies in place of
+ * the feature ring (append first, then walk).  Both NULL: KWS_EINVAL.  The caller keeps the frame's samples appended before it
+ * walks the frame (K hops for frame 0); kws_stream_utt_cut_i16 refuses a span that ends beyond the appended samples.
+ * KWS_ESTATE: the context is not armed, or a push has stepped this armed set -- and a push is refused (KWS_ESTATE) once this
+ * entry has stepped it: the set has ONE frame counter and ONE hop counter, and the two drivers would let them drift apart. */
+int kws_stream_utt_step_i16(kws_ctx* ctx, const int16_t* d_hop, const float* d_energy);
+/* Close every stream that is inside an utterance at the newest walked frame F - 1, reason 2, prev_close = F - 1 (one launch).
+ * A hop-by-hop run followed by a flush equals kws_segment_f32 over the same F frames with n_total beyond reach, an utterance
+ * that opened at the very last frame included.  The streams go on afterwards.  Not armed: KWS_ESTATE. */
+int kws_stream_utt_flush(kws_ctx* ctx);
+/* Wait until the step of the newest enqueued push, step or flush has landed: spins on the completion count in host memory and
+ * falls back to the stream after ~2 ms (as kws_stream_wait_host).  *total_events: records emitted since kws_stream_utt_open;
+ * *steps: frames walked (either may be NULL).  Not armed: KWS_ESTATE. */
+int kws_stream_utt_poll(kws_ctx* ctx, uint64_t* total_events, uint64_t* steps);
+/* Copy records first_seq .. first_seq + n - 1 out of the host mirror: out_records int64 [n, 6] (host).  Waits for nothing:
+ * sequence numbers at or beyond the total that has landed, and ones no longer in the queue (seq + max_events < total, checked
+ * again after the copy), are KWS_EINVAL, as are n < 1 and a NULL pointer.  Not armed: KWS_ESTATE. */
+int kws_stream_utt_read(kws_ctx* ctx, uint64_t first_seq, int n, int64_t* out_records);
+/* kws_cut_i16 with a ring origin: normalize + fix_length of the spans of U consecutive sequence numbers, one workgroup per
+ * span, each record read from the DEVICE queue (no span list is uploaded).  d_clips int16 [U, n_out] (device), every element
+ * written; d_peak int32 [U] or NULL.  Peak over the whole span (|-32768| = 32768), float64 divide, multiply and truncation
+ * towards zero, zeros beyond the span: on the linear signal the clips and peaks are bit-identical to kws_cut_i16's.  A span
+ * crosses the ring's seam at most once.  A zero clip and peak = -1 (kws_cut_i16's refusal of a recording out of range) for: a
+ * sequence number not emitted yet or already overwritten in the queue (seq + max_events < total); a span whose start is older
+ * than appended - history_samples (cut too late: more than slack_hops hops after the close); a span that ends beyond the
+ * appended samples (explicit steps only).  The launch is ordered on the context stream behind every earlier push, so "appended"
+ * is what was pushed before this call.  KWS_EINVAL: U or n_out < 1, normalize_to outside [0, 32767], a NULL d_clips.  Not armed:
+ * KWS_ESTATE.  Asynchronous, deterministic, not timed by kws_prof_*. */
+int kws_stream_utt_cut_i16(kws_ctx* ctx, uint64_t first_seq, int U, int normalize_to, int16_t* d_clips, int n_out, int32_t* d_peak);
+
 /* ---- sample-rate conversion on the device (replaces the resampling inside librosa.load(path, sr=...),
  * kws/libs/audio_processor.py:120,145; PARITY UNPINNED against librosa's soxr: what is pinned is the project's own host
  * definition, scipy.signal.resample_poly(x, up, down, window=("kaiser", 14.0)) with zero padding, in float64) ---------------- */

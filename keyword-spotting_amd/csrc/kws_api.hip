@@ -41,6 +41,7 @@ static void host_results_free(kws_ctx* c) {
 void stream_free(kws_ctx* c) {
     smooth_free(c);
     vad_free(c);
+    stream_utt_free(c);  // live utterances (kws_live.hip)
     host_results_free(c);
     if (c->stream_graph) (void)hipGraphExecDestroy(c->stream_graph);
     if (c->d_pcm_ring) (void)hipFree(c->d_pcm_ring);
@@ -564,6 +565,7 @@ int kws_stream_push_i16(kws_ctx* c, const int16_t* d_hop, float* d_logits, int32
         if (c->fp.num_frames != IN_T || c->fp.numcep != IN_F)
             return fail(c, KWS_EUNSUPPORTED, "kws_stream_push_i16: the DS-CNN kernel is built for a 99 x 10 feature map");
     }
+    if (int rc = stream_utt_push_check(c, "kws_stream_push_i16")) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     // A push that is ONE kernel launch gains nothing from a graph -- on this stack it loses: hipGraphLaunch of a one-node graph
     // takes 6.9 us of host time against 3.0 us for the plain launch, and completion is observed 8 us later in all
@@ -591,12 +593,12 @@ int kws_stream_push_i16(kws_ctx* c, const int16_t* d_hop, float* d_logits, int32
         }
         HIP_TRY(c, hipGraphLaunch(c->stream_graph, c->stream));
         c->pushes_enqueued += 1;
-        return KWS_OK;
+        return stream_utt_pushed(c);  // armed: the step kernel, behind the replay and outside the graph
     }
     HIP_TRY(c, stream_enqueue(c, d_hop, d_logits, d_label, true));
     c->pushes_enqueued += 1;
     if (c->last_push_host) c->host_push = c->pushes_enqueued;
-    return KWS_OK;
+    return stream_utt_pushed(c);
 }
 
 int kws_stream_state(kws_ctx* c, const float** d_feat_ring, int* hops) {

@@ -1,6 +1,6 @@
 // The context behind the C ABI (include/kws_hip.h), the error plumbing and the device-memory helpers shared by the translation
 // units that implement it (kws_api.hip, kws_frontend.hip, kws_weights.hip, kws_ingest.hip, kws_scan.hip, kws_decide.hip,
-// kws_eval.hip, kws_resample.hip, kws_*_bwd.hip), and the event bracket of a timed launch.
+// kws_eval.hip, kws_resample.hip, kws_live.hip, kws_*_bwd.hip), and the event bracket of a timed launch.
 #pragma once
 #include <new>
 
@@ -16,6 +16,10 @@ struct ResampleCache;           // rate pairs designed so far and their device t
 void resample_free(kws_ctx* c);
 struct StreamResample;          // the streaming resampler's pair, position and per-stream history (kws_resample.hip)
 void stream_resample_free(kws_ctx* c);
+struct StreamUtt;               // live utterances: history ring, walk state, event queue and its host mirror (kws_live.hip)
+void stream_utt_free(kws_ctx* c);
+int stream_utt_push_check(kws_ctx* c, const char* fn);  // a push is refused once kws_stream_utt_step_i16 has stepped the set
+int stream_utt_pushed(kws_ctx* c);                      // the step behind a push's launches; nothing when the context is unarmed
 }  // namespace kws
 
 using kws::FrontendParams; using kws::FrontendTables; using kws::DscnnWeights; using kws::CnnTradWeights; using kws::NFFT;
@@ -114,6 +118,8 @@ struct kws_ctx {
     kws::ResampleCache* resample = nullptr;
     // streaming resampler (kws_stream_resample_*, kws_stream_push_rate_i16): created by kws_stream_resample_open
     kws::StreamResample* stream_resample = nullptr;
+    // live utterances (kws_stream_utt_*): created by kws_stream_utt_open, dropped with the streams
+    kws::StreamUtt* stream_utt = nullptr;
 
     // host ingest (kws_infer_host_i16): staging rings, copy streams, pack threads -- created on first use
     kws::Ingest* ingest = nullptr;

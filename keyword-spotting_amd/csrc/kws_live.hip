@@ -1,0 +1,501 @@
+// Live utterances (include/kws_hip.h: kws_stream_utt_*) -- the reference's one live loop (kws/inference/inference_local.py:
+// 114-192) for the streams of kws_stream_open: a per-stream PCM history ring, the walk of kws_segment_f32 taken one frame per
+// hop with O(1) window counts, an event queue mirrored in pinned host memory, and kws_cut_i16 with a ring origin.  Everything
+// here is new kernels launched BEHIND a push; no other unit's kernel changes, and an unarmed context never gets here.
+#include <atomic>
+#include <chrono>
+#include <climits>
+#include <cstring>
+
+#include "kws_ctx.h"
+
+namespace kws {
+
+constexpr int LIVE_MAX_STREAMS = 1024;  // one workgroup walks every stream: one thread each
+constexpr int LIVE_MAX_WINDOW = 1024;   // off_window's limit (as kws_segment_f32)
+constexpr int LIVE_BIT_WORDS = LIVE_MAX_WINDOW / 64;
+constexpr int LIVE_REC = 6;             // int64 words per record
+constexpr int LIVE_CUT_THREADS = 256;
+
+// Everything kws_stream_utt_open allocates.  Device counters ctr[4] = frames walked, hops appended, events so far, kernels
+// finished; the host mirror h_ctr[3] = events so far, frames walked, kernels finished (the flag kws_stream_utt_poll spins on).
+struct StreamUtt {
+    int n_streams = 0, H = 0, max_events = 0;
+    int on_window = 0, off_window = 0, pre_roll = 0, max_frames = 0;
+    float threshold = 0.f;
+    int16_t* d_hist = nullptr;             // [S][H]
+    unsigned long long* d_bits = nullptr;  // [S][16]: voiced flag of frame f at bit f mod 1024
+    int* d_counts = nullptr;               // [S][4]: c_on, c_off, triggered, unused
+    long long* d_pos = nullptr;            // [S][2]: open, prev_close
+    unsigned long long* d_ctr = nullptr;   // [4]
+    long long* d_queue = nullptr;          // [max_events][6]
+    long long* h_queue = nullptr;          // pinned, device-mapped mirror of d_queue
+    unsigned long long* h_ctr = nullptr;   // pinned, device-mapped [3]
+    unsigned long long ticks_enqueued = 0; // kernels enqueued so far: h_ctr[2] reads this once the newest has landed
+    int mode = 0;                          // 0: not stepped yet, 1: stepped by pushes, 2: stepped by kws_stream_utt_step_i16
+};
+
+namespace {
+
+struct LiveArgs {
+    const int16_t* hop;       // append source (nullptr: no append): stream s at hop + s * hop_stride (+ the ring offset with ctx_hops)
+    long long hop_stride;
+    const int* ctx_hops;      // stepped by a push: the context's hop counter (already advanced); nullptr: explicit step
+    int ring_len;             // of the context's PCM ring
+    const float* energy;      // explicit step: [S] (nullptr: no walk); push: the context's feature ring
+    int num_frames, numcep, K;
+    int S, step, frame_len, H, max_events;
+    int on_window, off_window, pre_roll, max_frames;
+    float threshold;
+    int vec;                  // the hop may be copied 16 bytes at a time
+    int16_t* hist;
+    unsigned long long* bits;
+    int* counts;
+    long long* pos;
+    unsigned long long* ctr;
+    long long* queue;
+    long long* h_queue;
+    unsigned long long* h_ctr;
+};
+
+__device__ __forceinline__ void store_host(long long* p, long long v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// One hop of every stream: append, walk one frame, emit.  ONE workgroup, thread s = stream s (threads at or beyond S only
+// help with the copy, the ballots and the barriers).  FLUSH: no append and no walk -- every stream inside an utterance closes
+// at the newest walked frame with reason 2.
+// Emit: the wavefronts' ballots of "closed at this step" give every closing stream its rank in ascending stream order (popcount
+// of the lower lanes + the counts of the lower wavefronts, through LDS): consecutive sequence numbers, no atomics.  Records go
+// to the device queue and, as system-scope stores, to the pinned host mirror; every wavefront waits for its own stores to be
+// acknowledged (vmcnt 0: they are on their way, in order), and behind the barrier thread 0 publishes the totals and, last, the
+// kernel count the host spins on -- the discipline of the push's zero-copy results (kws_dscnn.hip), in one workgroup.
+template <bool FLUSH>
+__global__ __launch_bounds__(LIVE_MAX_STREAMS) void kws_live_step_kernel(const LiveArgs a) {
+    __shared__ int wave_n[LIVE_MAX_STREAMS / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = (int)blockDim.x >> 6;
+    const unsigned long long frames = a.ctr[0], appended = a.ctr[1], total = a.ctr[2], ticks = a.ctr[3];
+    bool do_append = false, do_walk = false;
+    const int16_t* src = a.hop;
+    const float* energy = a.energy;
+    long long e_stride = 1;
+    if constexpr (!FLUSH) {
+        if (a.ctx_hops) {
+            // push number h left its hop at [((h - 1) step) mod ring_len, + step) of the context's ring (kws_mfcc_dev.h) and
+            // completed the frame of feature row (h - K) mod num_frames; this set's own K - 1 first hops walk nothing
+            const int h = a.ctx_hops[0];  // >= 1 behind a push
+            do_append = h >= 1;
+            do_walk = do_append && appended + 1 >= (unsigned long long)a.K && h >= a.K;
+            if (do_append) src += (int)(((long long)(h - 1) * a.step) % a.ring_len);
+            if (do_walk) energy += (size_t)((h - a.K) % a.num_frames) * a.numcep;
+            e_stride = (long long)a.num_frames * a.numcep;
+        } else {
+            do_append = a.hop != nullptr;
+            do_walk = a.energy != nullptr;
+        }
+    }
+    if (do_append) {  // workgroup-uniform; a hop never straddles the seam: H is a multiple of step
+        const int at = (int)((appended * (unsigned long long)a.step) % (unsigned long long)a.H);
+        if (a.vec) {
+            const int per = a.step >> 3;
+            for (int i = tid; i < a.S * per; i += (int)blockDim.x) {
+                const int s = i / per, j = i - s * per;
+                reinterpret_cast<uint4*>(a.hist + (size_t)s * a.H + at)[j] = reinterpret_cast<const uint4*>(src + (size_t)s * a.hop_stride)[j];
+            }
+        } else {
+            for (int i = tid; i < a.S * a.step; i += (int)blockDim.x) {
+                const int s = i / a.step, j = i - s * a.step;
+                a.hist[(size_t)s * a.H + at + j] = src[(size_t)s * a.hop_stride + j];
+            }
+        }
+    }
+    bool closed = false;
+    long long open = 0, start_frame = 0, close_frame = 0;
+    int reason = 0;
+    if (tid < a.S && (FLUSH || do_walk)) {
+        int* cnt = a.counts + 4 * tid;
+        long long* ps = a.pos + 2 * tid;
+        int trig = cnt[2];
+        open = ps[0];
+        const long long prev_close = ps[1];
+        if constexpr (FLUSH) {
+            if (trig) {
+                closed = true;
+                reason = 2;
+                close_frame = (long long)frames - 1;  // triggered: at least one frame was walked
+            }
+        } else {
+            const long long f = (long long)frames;
+            const int v = energy[(size_t)tid * e_stride] > a.threshold ? 1 : 0;  // float32, strict; a NaN is unvoiced
+            unsigned long long* bw = a.bits + (size_t)tid * LIVE_BIT_WORDS;
+            // the flags leaving the two windows are read BEFORE the new one is stored: with a window of 1024 they share its slot
+            auto flag_at = [&](long long g) -> int { return g < 0 ? 0 : (int)((bw[(g & (LIVE_MAX_WINDOW - 1)) >> 6] >> (g & 63)) & 1ull); };
+            const int c_on = cnt[0] + v - flag_at(f - a.on_window);
+            const int c_off = cnt[1] + v - flag_at(f - a.off_window);
+            const int slot = (int)(f & (LIVE_MAX_WINDOW - 1));
+            bw[slot >> 6] = (bw[slot >> 6] & ~(1ull << (slot & 63))) | ((unsigned long long)v << (slot & 63));
+            cnt[0] = c_on;
+            cnt[1] = c_off;
+            if (!trig) {
+                if (10 * c_on > 8 * a.on_window) {  // the utterance opens; nothing else happens at this frame
+                    trig = 1;
+                    open = f;
+                    ps[0] = f;
+                    cnt[2] = 1;
+                }
+            } else if (10 * (a.off_window - c_off) > 9 * a.off_window) {
+                closed = true;
+                reason = 0;
+                close_frame = f;
+            } else if (f - open + 1 >= a.max_frames) {
+                closed = true;
+                reason = 1;
+                close_frame = f;
+            }
+        }
+        if (closed) {
+            start_frame = open - a.pre_roll;
+            if (start_frame < prev_close + 1) start_frame = prev_close + 1;  // prev_close + 1 >= 0
+            ps[1] = close_frame;
+            cnt[2] = 0;
+        }
+    }
+    const unsigned long long b = __ballot(closed);
+    if (lane == 0) wave_n[wave] = __popcll(b);
+    __syncthreads();
+    int before = 0, all = 0;
+    for (int k = 0; k < n_waves; ++k) {
+        before += k < wave ? wave_n[k] : 0;
+        all += wave_n[k];
+    }
+    if (closed) {
+        const unsigned long long seq = total + (unsigned long long)before + (unsigned long long)__popcll(b & ((1ull << lane) - 1ull));
+        const size_t at = (size_t)(seq % (unsigned long long)a.max_events) * LIVE_REC;
+        const long long rec[LIVE_REC] = {(long long)tid, start_frame * a.step, close_frame * a.step + a.frame_len, open, close_frame, (long long)reason};
+#pragma unroll
+        for (int k = 0; k < LIVE_REC; ++k) {
+            a.queue[at + k] = rec[k];
+            store_host(a.h_queue + at + k, rec[k]);
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wavefront's stores, the host's among them, are acknowledged
+    __syncthreads();                     // ... and so are every other wavefront's; all have read ctr[]
+    if (tid == 0) {
+        const unsigned long long frames_now = frames + (do_walk ? 1 : 0);
+        a.ctr[0] = frames_now;
+        a.ctr[1] = appended + (do_append ? 1 : 0);
+        a.ctr[2] = total + (unsigned long long)all;
+        a.ctr[3] = ticks + 1;
+        store_host(reinterpret_cast<long long*>(a.h_ctr), (long long)(total + (unsigned long long)all));
+        store_host(reinterpret_cast<long long*>(a.h_ctr) + 1, (long long)frames_now);
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+        store_host(reinterpret_cast<long long*>(a.h_ctr) + 2, (long long)(ticks + 1));
+    }
+}
+
+// kws_cut_i16_kernel (kws_segment.hip) with a ring origin: one workgroup per sequence number, the record read from the device
+// queue.  The span [start, end) of stream r lies in the history ring from start mod H on and crosses the seam at most once
+// (end - start <= H): element i is at p0 + i, minus H from the seam on.  Same peak, same float64 divide, multiply and
+// truncation, same zeros beyond the span as the linear kernel.  Refused (zero clip, peak -1): a sequence number not issued yet
+// or already overwritten in the queue, a span whose start has left the ring, a span that ends beyond what was appended.
+__global__ __launch_bounds__(LIVE_CUT_THREADS) void kws_live_cut_kernel(const int16_t* __restrict__ hist, int S, int H, int step,
+                                                                        const long long* __restrict__ queue, int max_events,
+                                                                        const unsigned long long* __restrict__ ctr,
+                                                                        unsigned long long first_seq, int normalize_to,
+                                                                        int16_t* __restrict__ clips, int n_out, int32_t* __restrict__ peak_out) {
+    __shared__ int wave_peak[LIVE_CUT_THREADS / 64];
+    const int u = blockIdx.x, tid = threadIdx.x;
+    const unsigned long long seq = first_seq + (unsigned long long)u, total = ctr[2];
+    const long long have = (long long)(ctr[1] * (unsigned long long)step);  // samples appended so far
+    bool ok = seq < total && seq + (unsigned long long)max_events >= total;  // workgroup-uniform throughout
+    long long r = 0, start = 0, end = 0;
+    if (ok) {
+        const long long* rec = queue + (size_t)(seq % (unsigned long long)max_events) * LIVE_REC;
+        r = rec[0];
+        start = rec[1];
+        end = rec[2];
+        ok = r >= 0 && r < S && start >= 0 && end >= start && end <= have && start + H >= have;
+    }
+    const int len = ok ? (int)(end - start) : 0;  // <= H
+    const int p0 = ok ? (int)(start % H) : 0;
+    const int16_t* x = hist + (ok ? (size_t)r * H : 0);
+    auto at = [&](unsigned i) -> int {
+        int p = p0 + (int)i;
+        p -= p >= H ? H : 0;
+        return x[p];
+    };
+    int16_t* out = clips + (size_t)u * n_out;
+    int peak = 0;
+    for (unsigned i = tid; i < (unsigned)len; i += LIVE_CUT_THREADS) {
+        const int v = at(i);
+        const int m = v < 0 ? -v : v;  // |-32768| = 32768
+        peak = m > peak ? m : peak;
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        const int other = __shfl_xor(peak, d);
+        peak = other > peak ? other : peak;
+    }
+    if ((tid & 63) == 0) wave_peak[tid >> 6] = peak;
+    __syncthreads();
+    peak = wave_peak[0];
+    for (int k = 1; k < LIVE_CUT_THREADS / 64; ++k) peak = wave_peak[k] > peak ? wave_peak[k] : peak;
+    if (tid == 0 && peak_out) peak_out[u] = ok ? peak : -1;
+    const int body = len < n_out ? len : n_out;
+    if (normalize_to > 0) {
+        const double times = peak > 0 ? (double)normalize_to / (double)peak : 0.0;  // peak 0: the span is all zeros anyway
+        for (unsigned i = tid; i < (unsigned)n_out; i += LIVE_CUT_THREADS) out[i] = i < (unsigned)body ? (int16_t)(int)((double)at(i) * times) : (int16_t)0;
+    } else {
+        for (unsigned i = tid; i < (unsigned)n_out; i += LIVE_CUT_THREADS) out[i] = i < (unsigned)body ? (int16_t)at(i) : (int16_t)0;
+    }
+}
+
+int frames_lag(const FrontendParams& p) { return (p.frame_len + p.frame_step - 1) / p.frame_step; }
+
+int history_for(int frame_len, int frame_step, int pre_roll, int max_frames, int slack_hops, long long* out) {
+    if (frame_len < 1 || frame_step < 1 || pre_roll < 0 || max_frames < 2 || slack_hops < 0) return KWS_EINVAL;
+    const long long K = (frame_len + frame_step - 1) / frame_step;
+    *out = ((long long)pre_roll + max_frames - 1 + K + slack_hops) * frame_step;
+    return *out > INT_MAX ? KWS_EINVAL : KWS_OK;
+}
+
+void utt_release(StreamUtt* u) {
+    if (!u) return;
+    if (u->d_hist) (void)hipFree(u->d_hist);
+    if (u->d_bits) (void)hipFree(u->d_bits);
+    if (u->d_counts) (void)hipFree(u->d_counts);
+    if (u->d_pos) (void)hipFree(u->d_pos);
+    if (u->d_ctr) (void)hipFree(u->d_ctr);
+    if (u->d_queue) (void)hipFree(u->d_queue);
+    if (u->h_queue) (void)hipHostFree(u->h_queue);
+    if (u->h_ctr) (void)hipHostFree(u->h_ctr);
+    delete u;
+}
+
+// One launch of the step or flush kernel with the set's state; hop / energy / ctx_hops as LiveArgs describes them.
+template <bool FLUSH>
+int utt_launch(kws_ctx* c, const int16_t* hop, long long hop_stride, const int* ctx_hops, const float* energy) {
+    StreamUtt* u = c->stream_utt;
+    const FrontendParams& p = c->fp;
+    LiveArgs a{};
+    a.hop = hop;
+    a.hop_stride = hop_stride;
+    a.ctx_hops = ctx_hops;
+    a.ring_len = c->ring_len;
+    a.energy = energy;
+    a.num_frames = p.num_frames;
+    a.numcep = p.numcep;
+    a.K = frames_lag(p);
+    a.S = u->n_streams;
+    a.step = p.frame_step;
+    a.frame_len = p.frame_len;
+    a.H = u->H;
+    a.max_events = u->max_events;
+    a.on_window = u->on_window;
+    a.off_window = u->off_window;
+    a.pre_roll = u->pre_roll;
+    a.max_frames = u->max_frames;
+    a.threshold = u->threshold;
+    // 16-byte copies: whole hops of 8 samples, every stream's hop and ring row on a 16-byte boundary (the ring offset and the
+    // ring's write position are multiples of step)
+    a.vec = hop && p.frame_step % 8 == 0 && hop_stride % 8 == 0 && reinterpret_cast<uintptr_t>(hop) % 16 == 0;
+    a.hist = u->d_hist;
+    a.bits = u->d_bits;
+    a.counts = u->d_counts;
+    a.pos = u->d_pos;
+    a.ctr = u->d_ctr;
+    a.queue = u->d_queue;
+    a.h_queue = u->h_queue;
+    a.h_ctr = u->h_ctr;
+    int threads = (u->n_streams + 63) / 64 * 64;
+    if (hop && threads < 256) threads = 256;  // the copy is the workgroup's bulk
+    hipLaunchKernelGGL(kws_live_step_kernel<FLUSH>, dim3(1), dim3(threads), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    u->ticks_enqueued += 1;
+    return KWS_OK;
+}
+
+}  // namespace
+
+void stream_utt_free(kws_ctx* c) {
+    utt_release(c->stream_utt);
+    c->stream_utt = nullptr;
+}
+
+// The push entries' side (kws_api.hip): the check in front of a push's launches, the step behind them.
+int stream_utt_push_check(kws_ctx* c, const char* fn) {
+    if (c->stream_utt && c->stream_utt->mode == 2)
+        return fail(c, KWS_ESTATE, std::string(fn) + ": this utterance set was stepped by kws_stream_utt_step_i16; a push would let its two counters drift apart");
+    return KWS_OK;
+}
+
+int stream_utt_pushed(kws_ctx* c) {
+    if (!c->stream_utt) return KWS_OK;
+    c->stream_utt->mode = 1;
+    return utt_launch<false>(c, c->d_pcm_ring, c->ring_len, c->d_hops, c->d_feat_ring);
+}
+
+}  // namespace kws
+
+using namespace kws;
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int kws_host_stream_utt_history(int frame_len, int frame_step, int pre_roll, int max_frames, int slack_hops, int* history_samples) {
+    long long h = 0;
+    if (!history_samples || history_for(frame_len, frame_step, pre_roll, max_frames, slack_hops, &h) != KWS_OK) return KWS_EINVAL;
+    *history_samples = (int)h;
+    return KWS_OK;
+}
+
+int kws_stream_utt_open(kws_ctx* c, float log_energy_threshold, int on_window, int off_window, int pre_roll, int max_frames,
+                        int history_samples, int max_events) {
+    KWS_GUARD_BEGIN
+    if (!c) return KWS_EINVAL;
+    if (!c->n_streams) return fail(c, KWS_ESTATE, "kws_stream_utt_open: call kws_stream_open first");
+    if (!c->fp.append_energy) return fail(c, KWS_EUNSUPPORTED, "kws_stream_utt_open: needs cepstrum 0 = log frame energy (appendEnergy)");
+    if (on_window < 1 || off_window < on_window || off_window > LIVE_MAX_WINDOW)
+        return fail(c, KWS_EINVAL, "kws_stream_utt_open: need 1 <= on_window <= off_window <= 1024");
+    if (pre_roll < 0 || max_frames < 2)
+        return fail(c, KWS_EINVAL, "kws_stream_utt_open: need pre_roll >= 0 and max_frames >= 2 (a live ring is bounded: there is no \"no time-out\")");
+    long long need = 0;
+    if (history_for(c->fp.frame_len, c->fp.frame_step, pre_roll, max_frames, 0, &need) != KWS_OK)
+        return fail(c, KWS_EINVAL, "kws_stream_utt_open: pre_roll + max_frames is beyond what a ring of int samples holds");
+    if (history_samples < need || history_samples % c->fp.frame_step != 0)
+        return fail(c, KWS_EINVAL, "kws_stream_utt_open: history_samples must be a multiple of frame_step and at least kws_host_stream_utt_history(..., slack_hops = 0)");
+    if (max_events < c->n_streams) return fail(c, KWS_EINVAL, "kws_stream_utt_open: max_events must be at least n_streams (all may close at one step)");
+    if (c->n_streams > LIVE_MAX_STREAMS)
+        return fail(c, KWS_EUNSUPPORTED, "kws_stream_utt_open: more than 1024 streams (one workgroup walks them all)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    stream_utt_free(c);
+    StreamUtt* u = new StreamUtt();
+    const size_t S = (size_t)c->n_streams;
+    u->n_streams = c->n_streams;
+    u->H = history_samples;
+    u->max_events = max_events;
+    u->on_window = on_window;
+    u->off_window = off_window;
+    u->pre_roll = pre_roll;
+    u->max_frames = max_frames;
+    u->threshold = log_energy_threshold;
+    const size_t hist_b = sizeof(int16_t) * S * (size_t)u->H, bits_b = sizeof(unsigned long long) * S * LIVE_BIT_WORDS,
+                 counts_b = sizeof(int) * S * 4, pos_b = sizeof(long long) * S * 2, ctr_b = sizeof(unsigned long long) * 4,
+                 queue_b = sizeof(long long) * (size_t)max_events * LIVE_REC;
+    const unsigned flags = hipHostMallocMapped | hipHostMallocCoherent;  // fine-grained: device stores are visible to the host as they land
+    if (hipMalloc(reinterpret_cast<void**>(&u->d_hist), hist_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&u->d_bits), bits_b) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&u->d_counts), counts_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&u->d_pos), pos_b) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&u->d_ctr), ctr_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&u->d_queue), queue_b) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void**>(&u->h_queue), queue_b, flags) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void**>(&u->h_ctr), 64, flags) != hipSuccess) {
+        utt_release(u);
+        return fail(c, KWS_ENOMEM, "kws_stream_utt_open: allocation failed");
+    }
+    memset(u->h_queue, 0, queue_b);
+    memset(u->h_ctr, 0, 64);
+    hipError_t e = hipMemsetAsync(u->d_hist, 0, hist_b, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(u->d_bits, 0, bits_b, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(u->d_counts, 0, counts_b, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(u->d_pos, 0xFF, pos_b, c->stream);  // open = prev_close = -1
+    if (e == hipSuccess) e = hipMemsetAsync(u->d_ctr, 0, ctr_b, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(u->d_queue, 0, queue_b, c->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        utt_release(u);
+        return fail_hip(c, e, "kws_stream_utt_open: hipMemsetAsync");
+    }
+    c->stream_utt = u;
+    return KWS_OK;
+    KWS_GUARD_END(c, "kws_stream_utt_open")
+}
+
+int kws_stream_utt_close(kws_ctx* c) {
+    if (!c) return KWS_EINVAL;
+    if (!c->stream_utt) return KWS_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    stream_utt_free(c);
+    return KWS_OK;
+}
+
+int kws_stream_utt_step_i16(kws_ctx* c, const int16_t* d_hop, const float* d_energy) {
+    if (!c) return KWS_EINVAL;
+    StreamUtt* u = c->stream_utt;
+    if (!u) return fail(c, KWS_ESTATE, "kws_stream_utt_step_i16: call kws_stream_utt_open first");
+    if (!d_hop && !d_energy) return fail(c, KWS_EINVAL, "kws_stream_utt_step_i16: d_hop and d_energy are both NULL");
+    if (u->mode == 1) return fail(c, KWS_ESTATE, "kws_stream_utt_step_i16: this utterance set is stepped by the pushes");
+    HIP_TRY(c, hipSetDevice(c->device));
+    u->mode = 2;
+    return utt_launch<false>(c, d_hop, c->fp.frame_step, nullptr, d_energy);
+}
+
+int kws_stream_utt_flush(kws_ctx* c) {
+    if (!c) return KWS_EINVAL;
+    if (!c->stream_utt) return fail(c, KWS_ESTATE, "kws_stream_utt_flush: call kws_stream_utt_open first");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return utt_launch<true>(c, nullptr, 0, nullptr, nullptr);
+}
+
+int kws_stream_utt_poll(kws_ctx* c, uint64_t* total_events, uint64_t* steps) {
+    if (!c) return KWS_EINVAL;
+    StreamUtt* u = c->stream_utt;
+    if (!u) return fail(c, KWS_ESTATE, "kws_stream_utt_poll: call kws_stream_utt_open first");
+    // spin on the count of finished kernels; bounded: after ~2 ms without it, fall back to the stream (kws_stream_wait_host)
+    volatile unsigned long long* h = u->h_ctr;
+    const unsigned long long want = u->ticks_enqueued;
+    bool seen = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (long spin = 1;; ++spin) {
+        if (h[2] >= want) {
+            seen = true;
+            break;
+        }
+        __builtin_ia32_pause();
+        if ((spin & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
+    }
+    if (!seen) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (h[2] < want) return fail(c, KWS_EHIP, "kws_stream_utt_poll: the stream drained but the step's flag never arrived");
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    if (total_events) *total_events = h[0];
+    if (steps) *steps = h[1];
+    return KWS_OK;
+}
+
+int kws_stream_utt_read(kws_ctx* c, uint64_t first_seq, int n, int64_t* out_records) {
+    if (!c) return KWS_EINVAL;
+    StreamUtt* u = c->stream_utt;
+    if (!u) return fail(c, KWS_ESTATE, "kws_stream_utt_read: call kws_stream_utt_open first");
+    if (n < 1 || !out_records) return fail(c, KWS_EINVAL, "kws_stream_utt_read: n must be positive and out_records not NULL");
+    volatile unsigned long long* h = u->h_ctr;
+    unsigned long long total = h[0];
+    std::atomic_thread_fence(std::memory_order_acquire);
+    if (first_seq + (unsigned long long)n > total) return fail(c, KWS_EINVAL, "kws_stream_utt_read: sequence numbers beyond the events landed so far");
+    for (int i = 0; i < n; ++i) {
+        const volatile long long* rec = u->h_queue + (size_t)((first_seq + i) % (unsigned long long)u->max_events) * LIVE_REC;
+        for (int k = 0; k < LIVE_REC; ++k) out_records[(size_t)i * LIVE_REC + k] = rec[k];
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    total = h[0];  // again: a step that landed during the copy may have overwritten the oldest
+    if (first_seq + (unsigned long long)u->max_events < total) return fail(c, KWS_EINVAL, "kws_stream_utt_read: the sequence number is no longer in the queue");
+    return KWS_OK;
+}
+
+int kws_stream_utt_cut_i16(kws_ctx* c, uint64_t first_seq, int U, int normalize_to, int16_t* d_clips, int n_out, int32_t* d_peak) {
+    if (!c) return KWS_EINVAL;
+    StreamUtt* u = c->stream_utt;
+    if (!u) return fail(c, KWS_ESTATE, "kws_stream_utt_cut_i16: call kws_stream_utt_open first");
+    if (!d_clips) return fail(c, KWS_EINVAL, "kws_stream_utt_cut_i16: d_clips is NULL");
+    if (U < 1 || n_out < 1) return fail(c, KWS_EINVAL, "kws_stream_utt_cut_i16: U and n_out must be positive");
+    if (normalize_to < 0 || normalize_to > 32767) return fail(c, KWS_EINVAL, "kws_stream_utt_cut_i16: normalize_to must be in [0, 32767]");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(kws_live_cut_kernel, dim3(U), dim3(LIVE_CUT_THREADS), 0, c->stream, u->d_hist, u->n_streams, u->H, c->fp.frame_step,
+                       u->d_queue, u->max_events, u->d_ctr, (unsigned long long)first_seq, normalize_to, d_clips, n_out, d_peak);
+    HIP_TRY(c, hipGetLastError());
+    return KWS_OK;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

@@ -97,6 +97,14 @@ SIGNATURES = {
     "kws_segment_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, C.c_int,
                                   _i32p]),
     "kws_cut_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _i16p, C.c_int, _i32p]),
+    "kws_host_stream_utt_history": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int)]),
+    "kws_stream_utt_open": (C.c_int, [_c_ctx, C.c_float] + [C.c_int] * 6),
+    "kws_stream_utt_close": (C.c_int, [_c_ctx]),
+    "kws_stream_utt_step_i16": (C.c_int, [_c_ctx, _i16p, _f32p]),
+    "kws_stream_utt_flush": (C.c_int, [_c_ctx]),
+    "kws_stream_utt_poll": (C.c_int, [_c_ctx, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kws_stream_utt_read": (C.c_int, [_c_ctx, C.c_uint64, C.c_int, C.POINTER(C.c_int64)]),
+    "kws_stream_utt_cut_i16": (C.c_int, [_c_ctx, C.c_uint64, C.c_int, C.c_int, _i16p, C.c_int, _i32p]),
     "kws_resample_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _i16p, C.c_int]),
     "kws_resample_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _f32p, C.c_int]),
     "kws_host_stream_resample_plan": (C.c_int, [C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4),
@@ -465,6 +473,45 @@ class Context:
                                           int(normalize_to), _ptr(clips), int(clips.shape[1]), _ptr(peak) if peak is not None else None),
                     AudioProcessingError)
 
+    # -- live utterances ---------------------------------------------------------------------------
+    def stream_utt_open(self, threshold, on_window, off_window, pre_roll, max_frames, history_samples, max_events):
+        """``kws_stream_utt_open``: arm the open stream set -- every push then appends its hop to a per-stream history, walks
+        one frame of the endpointer and queues the utterances that close (``host_stream_utt_history`` sizes the history)."""
+        self._check(self._lib.kws_stream_utt_open(self._h, float(threshold), int(on_window), int(off_window), int(pre_roll),
+                                                  int(max_frames), int(history_samples), int(max_events)), ModelError)
+
+    def stream_utt_close(self):
+        self._check(self._lib.kws_stream_utt_close(self._h), ModelError)
+
+    def stream_utt_step_i16(self, hop=None, energy=None):
+        """``kws_stream_utt_step_i16``: the explicit step; ``hop`` int16 [S, frame_step] and / or ``energy`` float32 [S], device
+        tensors or raw device addresses."""
+        p = lambda t: None if t is None else (int(t) if isinstance(t, int) else _ptr(t))
+        self._check(self._lib.kws_stream_utt_step_i16(self._h, p(hop), p(energy)), ModelError)
+
+    def stream_utt_flush(self):
+        self._check(self._lib.kws_stream_utt_flush(self._h), ModelError)
+
+    def stream_utt_poll(self):
+        """``kws_stream_utt_poll``: wait for the newest step; (events so far, frames walked)."""
+        total, steps = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.kws_stream_utt_poll(self._h, C.byref(total), C.byref(steps)), ModelError)
+        return int(total.value), int(steps.value)
+
+    def stream_utt_read(self, first_seq: int, n: int) -> np.ndarray:
+        """``kws_stream_utt_read``: int64 [n, 6] = (stream, start_sample, end_sample, open_frame, close_frame, reason) of the
+        sequence numbers ``first_seq`` .. ``first_seq + n - 1``, from the host mirror of the queue."""
+        out = np.empty((max(int(n), 0), 6), np.int64)
+        self._check(self._lib.kws_stream_utt_read(self._h, C.c_uint64(int(first_seq)), int(n), out.ctypes.data_as(C.POINTER(C.c_int64))),
+                    ModelError)
+        return out
+
+    def stream_utt_cut_i16(self, first_seq: int, clips, normalize_to=16384, peak=None):
+        """``kws_stream_utt_cut_i16``: the spans of ``clips.shape[0]`` consecutive sequence numbers cut from the history rings,
+        normalised and padded or trimmed into ``clips`` int16 [U, n_out]; ``peak`` int32 [U] or None."""
+        self._check(self._lib.kws_stream_utt_cut_i16(self._h, C.c_uint64(int(first_seq)), int(clips.shape[0]), int(normalize_to), _ptr(clips),
+                                                     int(clips.shape[1]), _ptr(peak) if peak is not None else None), AudioProcessingError)
+
     # -- sample-rate conversion --------------------------------------------------------------------
     def _resample(self, fn, x, rate_in, rate_out, out, lengths):
         self._check(fn(self._h, _ptr(x), int(x.shape[0]), int(x.shape[1]), _ptr(lengths) if lengths is not None else None, int(rate_in),
@@ -732,6 +779,16 @@ def host_scan_shape(n_total, frame_len=400, frame_step=160, window_frames=99, ho
     if rc != KWS_OK:
         raise KWSError(f"kws_host_scan_shape failed ({rc}): sizes must be positive")
     return int(frames.value), int(windows.value)
+
+
+def host_stream_utt_history(frame_len=400, frame_step=160, pre_roll=60, max_frames=1000, slack_hops=8) -> int:
+    """(pre_roll + max_frames - 1 + ceil(frame_len / frame_step) + slack_hops) * frame_step: the samples of history a live
+    utterance set keeps per stream (``kws_host_stream_utt_history``)."""
+    n = C.c_int(0)
+    rc = lib().kws_host_stream_utt_history(int(frame_len), int(frame_step), int(pre_roll), int(max_frames), int(slack_hops), C.byref(n))
+    if rc != KWS_OK:
+        raise ModelError(f"kws_host_stream_utt_history({frame_len}, {frame_step}, {pre_roll}, {max_frames}, {slack_hops}) failed (code {rc})")
+    return int(n.value)
 
 
 def host_resample_len(n_in, rate_in, rate_out) -> int:

@@ -66,6 +66,24 @@ class Utterance:
     peak: int
 
 
+@dataclass
+class UtteranceConfig:
+    """``StreamingSpotter(utterances=...)``: the reference's live loop on the streams.  A frame is voiced when its log energy
+    exceeds ``threshold``; an utterance opens when more than 80 % of the last ``on_window`` frames are voiced, closes when more
+    than 90 % of the last ``off_window`` are not or after ``max_seconds`` (a live history is bounded: there is no "never"),
+    starts ``pre_roll`` frames before it opened and is scaled to a peak of ``normalize`` (0: as it is) before the model sees it.
+    ``max_events``: records the device queue keeps (None: ``max(n_streams, 64)``); ``slack_hops``: hops that may be pushed
+    between a close and the ``pop_utterances`` that cuts it."""
+    threshold: float
+    on_window: int = 40
+    off_window: int = 80
+    pre_roll: int = 60
+    max_seconds: float = 10.0
+    normalize: int = 16384
+    max_events: Optional[int] = None
+    slack_hops: int = 8
+
+
 class KeywordSpotter:
     """Holds a model on one GPU and maps wav files / PCM batches to (index, word)."""
 
@@ -406,6 +424,11 @@ class StreamingSpotter:
     ``kws_stream_push_host_rate_i16``: the bits of ``kws_resample_i16`` over the whole signal, delayed).  ``hop_in = hop * down /
     up`` must be integral -- 22.05 kHz (220.5) raises ``ModelError``; ``use_graph`` does not apply to these pushes.
 
+    ``utterances``: an ``UtteranceConfig`` arms the reference's live loop on the device (``kws_stream_utt_open``): every push is
+    followed by one more launch that appends the hop to a per-stream history, walks one frame of the energy endpointer and
+    queues the utterances that closed; ``pop_utterances()`` cuts, normalises and classifies them, ``flush()`` closes what is
+    still open.  ``push`` keeps its signature, its results and its zero-copy path; at most 1024 streams.
+
     Attributes: ``hop`` -- samples per hop at ``config.sample_rate``; ``hop_in`` -- samples ``push`` takes per stream (``hop``
     without ``input_rate``); ``delay_samples`` -- the resampler's delay in samples at ``config.sample_rate`` (10 = 0.625 ms for
     every rate above 16 kHz, 20 for 8 kHz, 0 without ``input_rate``): what the streams hear lags the input by that much.
@@ -414,7 +437,7 @@ class StreamingSpotter:
     def __init__(self, n_streams: int, model: Optional[DepthwiseSeparableConv] = None, words: Sequence[str] = WANTED_WORDS,
                  config: Optional[AudioConfig] = None, device: int = 0, use_graph: bool = False, smooth_window: int = 0,
                  vad_log_energy: Optional[float] = None, vad_windows: Tuple[int, int] = (40, 80), host_results: bool = True,
-                 input_rate: Optional[int] = None):
+                 input_rate: Optional[int] = None, utterances: Optional[UtteranceConfig] = None):
         from kws import _native
 
         self.config = config or AudioConfig()
@@ -463,6 +486,21 @@ class StreamingSpotter:
         self._host = bool(host_results) and self.smooth_window == 0 and self._vad is None
         if self._host:
             self._ctx.stream_host_results(True)
+        # live utterances (kws_stream_utt_*): armed, every push also appends its hop to a per-stream history on the device, walks
+        # one frame of the endpointer and queues the utterances that close; push itself is unchanged, zero-copy path included
+        self.utterances = utterances
+        self._utt_seq = 0  # the next sequence number pop_utterances hands out
+        if utterances is not None:
+            u = utterances
+            max_frames = int(round(float(u.max_seconds) * cfg.sample_rate / self.hop))
+            if max_frames < 2:
+                raise ModelError("utterances: max_seconds must be at least two frames (a live history is bounded: there is no 'never')")
+            if not 0 <= int(u.normalize) <= 32767:
+                raise ModelError("utterances: normalize must be in [0, 32767]")
+            self._utt_frame_len = frame_len
+            self._utt_max_events = int(u.max_events) if u.max_events is not None else max(self.n_streams, 64)
+            history = _native.host_stream_utt_history(frame_len, self.hop, int(u.pre_roll), max_frames, int(u.slack_hops))
+            self._ctx.stream_utt_open(u.threshold, u.on_window, u.off_window, u.pre_roll, max_frames, history, self._utt_max_events)
         torch.cuda.synchronize(self.device)
 
     def load_model(self, model: DepthwiseSeparableConv) -> None:
@@ -527,6 +565,49 @@ class StreamingSpotter:
         head = (hops - k + 1) % t
         return np.roll(host, -head, axis=1), hops
 
+    def pop_utterances(self) -> List[Utterance]:
+        """The utterances that closed since the last call, in the order they closed (ascending stream within a hop).  Waits for
+        the newest push's step (``kws_stream_utt_poll``); with nothing new it returns ``[]`` and launches nothing.  Otherwise, on
+        the device: the spans cut out of the history rings, normalised and padded or trimmed to a clip
+        (``kws_stream_utt_cut_i16``), the model once per clip (``kws_infer_i16``), then ONE read of logits, labels and peaks.
+        ``recording`` is the stream index; times are seconds of the stream since this spotter was armed, at ``config.sample_rate``
+        (with ``input_rate`` that is the resampled timeline, ``delay_samples`` behind the input).  Records the queue has already
+        overwritten (more than ``max_events`` closes between two calls) are skipped; an utterance cut more than ``slack_hops``
+        hops after it closed has left the history and comes back with ``peak`` -1 and a silent clip's logits."""
+        if self.utterances is None:
+            raise ModelError("pop_utterances: this StreamingSpotter was created without utterances=UtteranceConfig(...)")
+        total, _ = self._ctx.stream_utt_poll()
+        first = max(self._utt_seq, total - self._utt_max_events)
+        U = total - first
+        if U <= 0:
+            return []
+        rec = self._ctx.stream_utt_read(first, U)
+        self._utt_seq = total
+        C, n = self.model.num_classes, self.config.desired_samples
+        clips = torch.empty((U, n), dtype=torch.int16, device=self.device)
+        out = torch.empty((U * (C + 2),), dtype=torch.float32, device=self.device)  # logits [U, C], then labels [U] and peaks [U] as int32
+        logits, ints = out[:U * C].view(U, C), out[U * C:].view(torch.int32)
+        torch.cuda.current_stream(self.device).synchronize()  # the context runs on its own stream
+        self._ctx.stream_utt_cut_i16(first, clips, int(self.utterances.normalize), ints[U:])
+        self._ctx.infer_i16(clips, logits, ints[:U])
+        self._ctx.sync()
+        host = out.cpu()  # the one read
+        logits, ints = host[:U * C].view(U, C).numpy(), host[U * C:].view(torch.int32).numpy()
+        rate, step = float(self.config.sample_rate), self.hop
+        return [Utterance(int(s), int(start) / rate, int(end) / rate, int(opened) * step / rate, int(closed) * step / rate,
+                          UTTERANCE_REASONS[int(reason)], int(ints[u]), self.words[int(ints[u])], logits[u].copy(), int(ints[U + u]))
+                for u, (s, start, end, opened, closed, reason) in enumerate(rec)]
+
+    def flush(self) -> List[Utterance]:
+        """Close every utterance that is still open, at the newest frame and with reason ``"end_of_recording"``
+        (``kws_stream_utt_flush``), then what ``pop_utterances`` does.  The streams go on afterwards."""
+        if self.utterances is None:
+            raise ModelError("flush: this StreamingSpotter was created without utterances=UtteranceConfig(...)")
+        self._ctx.stream_utt_flush()
+        return self.pop_utterances()
+
     def close(self):
+        if self.utterances is not None:
+            self._ctx.stream_utt_close()
         self._ctx.stream_close()
         self._ctx.close()
