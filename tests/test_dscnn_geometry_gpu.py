@@ -12,11 +12,15 @@ import numpy as np
 import pytest
 import torch
 
+from _dscnn_forward import DEV, LAYER_RTOL, TOL  # noqa: F401  (the gates of tests/test_gpu_parity.py)
+from _dscnn_forward import check_class_counts as _check_class_counts
+from _dscnn_forward import check_forward as _check_forward
+from _dscnn_forward import fused_case as _fused_case
+from _dscnn_forward import geometry as _geometry
+from _dscnn_forward import gpu_forward as _gpu_forward
+
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda", 0)
-TOL = 1e-4          # logits, as tests/test_gpu_parity.py
-LAYER_RTOL = 2e-5   # stage outputs: max abs error <= LAYER_RTOL * max |float64 stage|, as tests/test_gpu_parity.py
 N_BODY = 6464 + 4 * 4800  # conv1 + four blocks; fc adds 65 C
 
 
@@ -34,31 +38,6 @@ def ctx(native):
     c.use_torch_stream()
     yield c
     c.close()
-
-
-def _geometry(T, F):
-    H1, W1 = (T - 6) // 2 + 1, (F - 6) // 2 + 1
-    return [(64, H1 + 2 * k, W1 + 2 * k) for k in range(5)]
-
-
-def _gpu_forward(ctx, x, C):
-    """kws_forward_map_debug_f32 (the composed path the backward recomputes with) -> logits, labels, {stage: output} on the
-    CPU."""
-    from oracle import dscnn as o_dscnn
-
-    B, _, T, F = x.shape
-    shapes = _geometry(T, F)
-    sizes = [int(np.prod(s)) for s in shapes]
-    layers = torch.full((B * sum(sizes),), float("nan"), device=DEV)
-    logits = torch.empty((B, C), device=DEV)
-    labels = torch.empty((B,), dtype=torch.int32, device=DEV)
-    ctx.forward_map_f32(x, logits, labels, layers=layers)
-    ctx.sync()
-    stages, off = {}, 0
-    for name, shp, n in zip(o_dscnn.MASKED, shapes, sizes):
-        stages[name] = layers[off:off + B * n].reshape(B, *shp).cpu()
-        off += B * n
-    return logits.cpu(), labels.cpu(), stages
 
 
 def _gpu_grad(ctx, x, dl, C):
@@ -169,32 +148,6 @@ def test_backward_and_forward_on_every_map(native, ctx, T, F):
     _check_forward(ctx, state, x, f"{T}x{F}")
 
 
-def _check_forward(ctx, state, x, what):
-    from oracle import dscnn as o_dscnn
-
-    C = state["fc.weight"].shape[0]
-    ctx.load_dscnn(o_dscnn.flatten_state(state), C)
-    logits, labels, stages = _gpu_forward(ctx, x.to(DEV), C)
-    want, layers = o_dscnn.forward(state, x.double(), return_layers=True)
-    for k in o_dscnn.MASKED:
-        w, got = layers[k].numpy(), stages[k].double().numpy()
-        assert got.shape == w.shape, (what, k)
-        assert np.abs(got - w).max() <= LAYER_RTOL * np.abs(w).max(), f"{what} stage {k}"
-        if k != "conv1":  # the ring is relu(bias) exactly
-            assert np.array_equal(got[:, :, 0, :], w[:, :, 0, :]) and np.array_equal(got[:, :, :, -1], w[:, :, :, -1]), (what, k)
-    want = want.numpy()
-    assert np.abs(logits.double().numpy() - want).max() <= TOL, what
-    top = np.sort(want, axis=1)
-    sure = (top[:, -1] - top[:, -2] > TOL) if C > 1 else np.ones(len(want), bool)
-    assert np.array_equal(labels.numpy()[sure], want.argmax(axis=1)[sure]), what
-    # the product entry (no stage dump) gives the same bits
-    l2 = torch.empty((x.shape[0], C), device=DEV)
-    ctx.forward_map_f32(x.to(DEV), l2, None)
-    ctx.sync()
-    if tuple(x.shape[2:]) != (99, 10):  # 99 x 10 takes the fused kernel there (checked in test_fused_kernel_class_counts)
-        assert torch.equal(l2.cpu(), logits), what
-
-
 @pytest.mark.parametrize("C", [1, 2, 35, 64])
 @pytest.mark.parametrize("T,F", [(99, 10), (22, 20)], ids=["99x10", "22x20"])
 def test_backward_class_counts(native, ctx, T, F, C):
@@ -275,38 +228,6 @@ def test_composed_forward_class_counts(native, ctx, T, F, C):
     _check_forward(ctx, o_dscnn.random_state(400 + C, num_classes=C), x, f"{T}x{F} C={C}")
 
 
-def _fused_case(C):
-    """A random model whose fc row c is clip c's centred pooled vector, normalised (bias: minus its product with the mean),
-    so that clip c gets label c: the float64 labels of the clip set cover every 16-lane row of the fused kernel's classifier
-    wavefront below C.  For C > 16, row b in another 16-lane row is an exact copy of row a: a tie the kernel must resolve
-    to a."""
-    from oracle import dscnn as o_dscnn
-
-    gen = torch.Generator().manual_seed(C)
-    x = torch.randn(96, 1, 99, 10, generator=gen)
-    x[C % 96] = 0.0
-    state = o_dscnn.random_state(500 + C, num_classes=C, std=1.0)
-    for k, v in state.items():  # He-scaled weights, small biases: the pooled vectors differ from clip to clip
-        if k.endswith("bias"):
-            state[k] = v * 0.01
-        elif k != "fc.weight":
-            state[k] = v * (2.0 / v[0].numel()) ** 0.5
-    _, layers = o_dscnn.forward(state, x.double(), return_layers=True)
-    pooled = layers["pool"]
-    u = pooled - pooled.mean(dim=0)
-    w = 5.0 * u[:C] / u[:C].norm(dim=1, keepdim=True)
-    state["fc.weight"] = w.float()
-    state["fc.bias"] = -(w @ pooled.mean(dim=0)).float()
-    ties = []
-    if C > 16:
-        ties = [(2, 17)] + ([(20, 33)] if C > 33 else []) + ([(40, 63)] if C > 63 else [])
-        for a, b in ties:
-            state["fc.weight"][b] = state["fc.weight"][a]
-            state["fc.bias"][b] = state["fc.bias"][a]
-    want = o_dscnn.forward(state, x.double()).numpy()
-    return state, x, want, ties
-
-
 @pytest.mark.parametrize("mode", [0, 1, 4, 5])  # VALU cross-check, f32 MFMA, split-bf16 MFMA, f16-pair MFMA
 @pytest.mark.parametrize("C", [1, 2, 35, 64])
 def test_fused_kernel_class_counts(native, ctx, C, mode):
@@ -314,34 +235,7 @@ def test_fused_kernel_class_counts(native, ctx, C, mode):
     16-lane rows and a ballot: labels from every 16-lane row below C, and exact ties across rows."""
     from oracle import dscnn as o_dscnn
 
-    state, x, want, ties = _fused_case(C)
-    B = x.shape[0]
-    cols = [c for c in range(C) if c not in {b for _, b in ties}]  # the copies tie their originals exactly
-    ref = np.asarray(cols)[want[:, cols].argmax(axis=1)]
-    assert set(ref // 16) == set(range((C + 15) // 16)), "the clip set must reach every 16-lane row"
-    for a, _ in ties:
-        assert (ref == a).any(), f"tie row {a} never wins"
-    ctx.load_dscnn(o_dscnn.flatten_state(state), C)
-    logits = torch.empty((B, C), device=DEV)
-    labels = torch.empty((B,), dtype=torch.int32, device=DEV)
-    xd = x.to(DEV)
-    if mode in (4, 5):
-        ctx.set_pointwise_math(mode)
-        ctx.forward_f32(xd, logits, labels)
-        ctx.set_pointwise_math(native.PW_DEFAULT)
-    else:
-        act = torch.zeros((B, native.ACT_FLOATS_PER_CLIP), device=DEV)
-        ctx.forward_debug_f32(xd, logits, labels, act, use_mfma=mode)
-    ctx.sync()
-    lg, lb = logits.cpu().double().numpy(), labels.cpu().numpy()
-    assert np.abs(lg - want).max() <= TOL * max(1.0, float(np.abs(want).max()) / 100), f"C={C} mode {mode}"
-    for a, b in ties:
-        assert np.array_equal(lg[:, a], lg[:, b])
-    top = np.sort(want[:, cols], axis=1) if len(cols) > 1 else None
-    sure = (top[:, -1] - top[:, -2] > TOL) if top is not None else np.ones(B, bool)
-    assert sure.sum() >= B // 2
-    assert np.array_equal(lb[sure], ref[sure]), f"C={C} mode {mode}: {lb[sure][lb[sure] != ref[sure]]} vs {ref[sure][lb[sure] != ref[sure]]}"
-    assert not np.isin(lb, [b for _, b in ties]).any(), "a tie must go to the first maximum"
+    _check_class_counts(native, ctx, C, mode, _fused_case(C))
 
 
 @pytest.mark.parametrize("C", [1, 35, 64])

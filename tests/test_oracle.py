@@ -167,12 +167,13 @@ def test_dscnn_matches_reference(dscnn_golden, tag):
         np.testing.assert_allclose(a[probe][:, :, :, 1], g[f"{tag}.{name}.col1"], atol=tol)
 
 
-def _state_of(blob):
+def _state_of(blob, input_channels=1):
     state, off = {}, 0
-    for k, shp in o_dscnn.state_shapes(12).items():
+    for k, shp in o_dscnn.state_shapes(12, input_channels).items():
         n = int(np.prod(shp))
         state[k] = torch.from_numpy(blob[off:off + n].reshape(shp).copy())
         off += n
+    assert off == blob.size
     return state
 
 
@@ -233,6 +234,24 @@ def test_standalone_block_matches_reference(dsblock_golden):
         if pd:  # the ring of the padded 1x1 convolution is relu(bias)
             ring = np.maximum(g[f"c{i}.pointwise.bias"], 0)
             assert np.array_equal(want[0, :, 0, :], np.broadcast_to(ring[:, None], want[0, :, 0, :].shape))
+
+
+def test_multichannel_oracle_matches_reference():
+    """oracle.dscnn.forward(input_channels=3) in float64 reproduces what the imported reference module recorded
+    (make_golden.py multichannel): the logits of the ten maps and conv1's output on the first two, within 2e-6 of the output's
+    scale -- the generator's own cross-check gate.  The GPU tests of the multi-channel model use this oracle as their truth."""
+    g = np.load(os.path.join(os.path.dirname(__file__), "golden", "multichannel_golden.npz"))
+    state = _state_of(g["blob"], 3)
+    assert tuple(state["conv1.weight"].shape) == (64, 3, 10, 10)
+    logits, layers = o_dscnn.forward(state, torch.from_numpy(g["x"]).double(), return_layers=True)
+    assert logits.dtype == torch.float64 and logits.shape == g["logits"].shape
+    assert np.abs(logits.numpy() - g["logits"]).max() <= 2e-6 * np.abs(g["logits"]).max()
+    conv1 = layers["conv1"][:2].numpy()
+    assert conv1.shape == g["conv1"].shape == (2, 64, 47, 3)
+    assert not g["x"][1].any()  # the second map is all zero: conv1's recorded output there is relu(bias), exactly
+    assert np.array_equal(g["conv1"][1], np.broadcast_to(np.maximum(state["conv1.bias"].numpy(), 0)[:, None, None], (64, 47, 3)))
+    assert np.abs(conv1 - g["conv1"]).max() <= 2e-6 * np.abs(g["conv1"]).max()
+    assert np.array_equal(o_dscnn.predict(torch.from_numpy(g["logits"])).numpy(), g["label"])
 
 
 def test_dscnn_shapes_and_relu_bias_ring():
