@@ -307,7 +307,7 @@ int kws_stream_open(kws_ctx* c, int n_streams) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     stream_free(c);
     const FrontendParams& p = c->fp;
-    c->ring_len = ((p.frame_len + p.frame_step - 1) / p.frame_step + 1) * p.frame_step;
+    c->ring_len = (frames_lag(p) + 1) * p.frame_step;
     const size_t pcm_b = sizeof(int16_t) * (size_t)n_streams * c->ring_len;
     const size_t feat_b = sizeof(float) * (size_t)n_streams * p.num_frames * p.numcep;
     if (hipMalloc(reinterpret_cast<void**>(&c->d_pcm_ring), pcm_b) != hipSuccess ||
@@ -550,7 +550,7 @@ static hipError_t stream_enqueue(kws_ctx* c, const int16_t* d_hop, float* d_logi
         ProfScope ps(c, KWS_K_DSCNN);
         c->prof = was;
         e = launch_dscnn(c->stream, c->mw, c->d_feat_ring, c->n_streams, d_logits, d_label, nullptr, c->pw_math, nullptr, c->d_hops, false,
-                         (c->fp.frame_len + c->fp.frame_step - 1) / c->fp.frame_step);
+                         frames_lag(c->fp));
     }
     return e;
 }

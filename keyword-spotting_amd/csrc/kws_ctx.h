@@ -4,6 +4,7 @@
 #pragma once
 #include <new>
 
+#include "kws_endpoint_dev.h"
 #include "kws_internal.h"
 
 namespace kws {
@@ -102,9 +103,10 @@ struct kws_ctx {
     float* d_post_sum = nullptr;
     int* d_post_count = nullptr;
     int post_window = 0, post_classes = 0;
-    // energy endpointer (kws_stream_vad_f32): voiced flags [n_streams][off_window], (cursor, triggered) [n_streams][2]
-    unsigned char* d_vad_flags = nullptr;
-    int* d_vad_state = nullptr;
+    // energy endpointer (kws_stream_vad_f32): ep_ring_push's state, bits [n_streams][EP_BIT_WORDS] and counts [n_streams][4] =
+    // (c_on, c_off, triggered, cursor)
+    unsigned long long* d_vad_bits = nullptr;
+    int* d_vad_counts = nullptr;
     int vad_on = 0, vad_off = 0;
 
     // evaluation statistics (kws_eval_*, kws_eval.hip): one allocation of 64-bit words -- counts[4], loss_sum (a double),
@@ -164,6 +166,18 @@ inline int check_batch(kws_ctx* c, const void* in, int B, const char* fn) {
     if (B <= 0) return fail(c, KWS_EINVAL, std::string(fn) + ": B must be positive");
     return KWS_OK;
 }
+// The endpointer's argument checks, one text each for the entries that share them (kws_stream_vad_f32, kws_segment_f32,
+// kws_stream_utt_open; kws_cut_i16, kws_stream_utt_cut_i16).
+inline int check_endpoint_windows(kws_ctx* c, const char* fn, int on_window, int off_window) {
+    const bool ok = on_window >= 1 && on_window <= off_window && off_window <= kws::EP_MAX_WINDOW;
+    return ok ? KWS_OK : fail(c, KWS_EINVAL, std::string(fn) + ": need 1 <= on_window <= off_window <= 1024");
+}
+inline int check_append_energy(kws_ctx* c, const char* fn) {
+    return c->fp.append_energy ? KWS_OK : fail(c, KWS_EUNSUPPORTED, std::string(fn) + ": needs cepstrum 0 = log frame energy (appendEnergy)");
+}
+inline int check_normalize_to(kws_ctx* c, const char* fn, int v) {
+    return v >= 0 && v <= 32767 ? KWS_OK : fail(c, KWS_EINVAL, std::string(fn) + ": normalize_to must be in [0, 32767]");
+}
 // No exception may cross the C ABI (ctypes would terminate the process): entry points that allocate host containers or
 // start threads run their body between these two.
 #define KWS_GUARD_BEGIN try {
@@ -176,6 +190,17 @@ inline int check_batch(kws_ctx* c, const void* in, int B, const char* fn) {
         hipError_t _e = (expr);                            \
         if (_e != hipSuccess) return fail_hip(c, _e, #expr); \
     } while (0)
+
+// ep_ring_push's state for S streams, zeroed on the context's stream (history before the first frame is unvoiced).  On an
+// error the caller frees whatever was allocated.
+inline int alloc_endpoint_state(kws_ctx* c, const char* fn, size_t S, unsigned long long*& bits, int*& counts) {
+    const size_t bits_b = sizeof(unsigned long long) * S * kws::EP_BIT_WORDS, counts_b = sizeof(int) * S * 4;
+    if (hipMalloc(reinterpret_cast<void**>(&bits), bits_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&counts), counts_b) != hipSuccess)
+        return fail(c, KWS_ENOMEM, std::string(fn) + ": device allocation failed");
+    hipError_t e = hipMemsetAsync(bits, 0, bits_b, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(counts, 0, counts_b, c->stream);
+    return e == hipSuccess ? KWS_OK : fail_hip(c, e, (std::string(fn) + ": hipMemsetAsync").c_str());
+}
 
 // Bracket a kernel launch with events when profiling is on.
 struct ProfScope {

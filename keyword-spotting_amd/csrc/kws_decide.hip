@@ -79,46 +79,32 @@ hipError_t launch_softmax(hipStream_t s, const float* d_logits, int B, int C, fl
 // kws/inference/inference_local.py:131-166 -- same hysteresis, at hop granularity).  The newest frame's log energy
 // (cepstrum 0 with appendEnergy) above the threshold marks the hop voiced; an utterance OPENS when more than 80 % of the
 // last `on_window` hops are voiced (:151) and CLOSES when more than 90 % of the last `off_window` hops are unvoiced
-// (:161); hops before the stream began count as unvoiced (the reference's rings start as zeros).  One thread per stream.
+// (:161); hops before the stream began count as unvoiced (the reference's rings start as zeros).  One thread per stream, the
+// rules and the O(1) flag ring of kws_endpoint_dev.h; counts[s] = (c_on, c_off, triggered, frames walked so far).
 // state[s] = triggered | event << 1, event 1 = opened at this hop, 2 = closed at this hop.
 __global__ void kws_stream_vad_kernel(const float* __restrict__ feat_ring, const int* __restrict__ hops_ptr, int n_streams,
-                                      int num_frames, int numcep, int frames_lag, float threshold, int on_window, int off_window,
-                                      unsigned char* __restrict__ flags, int* __restrict__ cursor_trig, int32_t* __restrict__ state) {
+                                      int num_frames, int numcep, int lag, float threshold, int on_window, int off_window,
+                                      unsigned long long* __restrict__ bits, int* __restrict__ counts, int32_t* __restrict__ state) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n_streams) return;
-    const int hops = *hops_ptr;  // already advanced by the push this call follows: the newest frame is hops - K (K hops per frame)
-    if (hops < frames_lag) {     // no complete frame yet
+    const int hops = *hops_ptr;  // already advanced by the push this call follows: the newest frame is hops - lag
+    if (hops < lag) {            // no complete frame yet
         state[s] = 0;
         return;
     }
-    const float c0 = feat_ring[((size_t)s * num_frames + (hops - frames_lag) % num_frames) * numcep];
-    unsigned char* fl = flags + (size_t)s * off_window;
-    const int cur = cursor_trig[2 * s];
-    int trig = cursor_trig[2 * s + 1];
-    fl[cur % off_window] = c0 > threshold ? 1 : 0;
-    int n_on = 0, n_all = 0;
-    for (int k = 0; k < off_window; ++k) {  // k hops back from the newest
-        const int v = k <= cur ? fl[(cur - k) % off_window] : 0;
-        n_all += v;
-        if (k < on_window) n_on += v;
-    }
-    int event = 0;
+    const float c0 = feat_ring[((size_t)s * num_frames + (hops - lag) % num_frames) * numcep];
+    int* cnt = counts + 4 * s;
+    const int cur = cnt[3];
+    int trig = cnt[2], event = 0;
+    const EpCounts n = ep_ring_push(bits + (size_t)s * EP_BIT_WORDS, cnt, cur, ep_voiced(c0, threshold) ? 1 : 0, on_window, off_window);
     if (!trig) {
-        if (10 * n_on > 8 * on_window) trig = 1, event = 1;
-    } else if (10 * (off_window - n_all) > 9 * off_window) {
+        if (ep_opens(n.on, on_window)) trig = 1, event = 1;
+    } else if (ep_closes(n.off, off_window)) {
         trig = 0, event = 2;
     }
-    cursor_trig[2 * s] = cur + 1;
-    cursor_trig[2 * s + 1] = trig;
+    cnt[2] = trig;
+    cnt[3] = cur + 1;
     state[s] = trig | (event << 1);
-}
-
-hipError_t launch_stream_vad(hipStream_t s, const float* d_feat_ring, const int* d_hops, int n_streams, int num_frames, int numcep,
-                             int frames_lag, float threshold, int on_window, int off_window, unsigned char* d_flags, int* d_cursor_trig,
-                             int32_t* d_state) {
-    hipLaunchKernelGGL(kws_stream_vad_kernel, dim3((n_streams + 63) / 64), dim3(64), 0, s, d_feat_ring, d_hops, n_streams,
-                       num_frames, numcep, frames_lag, threshold, on_window, off_window, d_flags, d_cursor_trig, d_state);
-    return hipGetLastError();
 }
 
 hipError_t launch_smooth_posteriors(hipStream_t s, const float* d_logits, int S, int C, int window, float* d_ring,
@@ -139,10 +125,10 @@ void smooth_free(kws_ctx* c) {
 }
 
 void vad_free(kws_ctx* c) {
-    if (c->d_vad_flags) (void)hipFree(c->d_vad_flags);
-    if (c->d_vad_state) (void)hipFree(c->d_vad_state);
-    c->d_vad_flags = nullptr;
-    c->d_vad_state = nullptr;
+    if (c->d_vad_bits) (void)hipFree(c->d_vad_bits);
+    if (c->d_vad_counts) (void)hipFree(c->d_vad_counts);
+    c->d_vad_bits = nullptr;
+    c->d_vad_counts = nullptr;
     c->vad_on = c->vad_off = 0;
 }
 
@@ -157,26 +143,24 @@ int kws_stream_vad_f32(kws_ctx* c, float log_energy_threshold, int on_window, in
     if (!c) return KWS_EINVAL;
     if (!c->n_streams) return fail(c, KWS_ESTATE, "kws_stream_vad_f32: call kws_stream_open first");
     if (!d_state) return fail(c, KWS_EINVAL, "kws_stream_vad_f32: d_state is NULL");
-    if (on_window < 1 || off_window < on_window || off_window > 1024)
-        return fail(c, KWS_EINVAL, "kws_stream_vad_f32: need 1 <= on_window <= off_window <= 1024");
-    if (!c->fp.append_energy) return fail(c, KWS_EUNSUPPORTED, "kws_stream_vad_f32: needs cepstrum 0 = log frame energy (appendEnergy)");
+    int rc = check_endpoint_windows(c, "kws_stream_vad_f32", on_window, off_window);
+    if (!rc) rc = check_append_energy(c, "kws_stream_vad_f32");
+    if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     if (on_window != c->vad_on || off_window != c->vad_off) {  // (re)start the history
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         vad_free(c);
-        const size_t fb = (size_t)c->n_streams * off_window, sb = sizeof(int) * 2 * (size_t)c->n_streams;
-        if (hipMalloc(reinterpret_cast<void**>(&c->d_vad_flags), fb) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&c->d_vad_state), sb) != hipSuccess) {
+        if ((rc = alloc_endpoint_state(c, "kws_stream_vad_f32", (size_t)c->n_streams, c->d_vad_bits, c->d_vad_counts))) {
             vad_free(c);
-            return fail(c, KWS_ENOMEM, "kws_stream_vad_f32: device allocation failed");
+            return rc;
         }
-        HIP_TRY(c, hipMemsetAsync(c->d_vad_flags, 0, fb, c->stream));
-        HIP_TRY(c, hipMemsetAsync(c->d_vad_state, 0, sb, c->stream));
         c->vad_on = on_window;
         c->vad_off = off_window;
     }
-    HIP_TRY(c, launch_stream_vad(c->stream, c->d_feat_ring, c->d_hops, c->n_streams, c->fp.num_frames, c->fp.numcep,
-                                 (c->fp.frame_len + c->fp.frame_step - 1) / c->fp.frame_step, log_energy_threshold, on_window, off_window, c->d_vad_flags, c->d_vad_state, d_state));
+    hipLaunchKernelGGL(kws_stream_vad_kernel, dim3((c->n_streams + 63) / 64), dim3(64), 0, c->stream, c->d_feat_ring, c->d_hops, c->n_streams,
+                       c->fp.num_frames, c->fp.numcep, frames_lag(c->fp), log_energy_threshold, on_window, off_window, c->d_vad_bits,
+                       c->d_vad_counts, d_state);
+    HIP_TRY(c, hipGetLastError());
     return KWS_OK;
 }
 

@@ -349,10 +349,10 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
         hops_before = *sp.hops;
         // K = hops a frame spans = ceil(frame_len / frame_step) (3 for 400 / 160): after h pushes the newest frame is h - K
         // and the window starts one row after it; here h = hops_before + 1
-        const int K = (sp.p.frame_len + sp.p.frame_step - 1) / sp.p.frame_step;
+        const int K = frames_lag(sp.p);
         head = (((hops_before + 2 - K) % IN_T) + IN_T) % IN_T;  // what the two-launch path derives from the advanced counter
         const int step = sp.p.frame_step;
-        const long f_start = (long)step * hops_before + step - (long)((sp.p.frame_len + step - 1) / step) * step;
+        const long f_start = (long)step * hops_before + step - (long)K * step;
         if (f_start >= 0) row_new = (int)((((f_start / step) - head) % IN_T + IN_T) % IN_T);
     } else {
         head = ring_hops ? (((*ring_hops + 1 - sp.frames_lag) % IN_T) + IN_T) % IN_T : 0;

@@ -46,6 +46,9 @@ struct FrontendParams {
     int log2_nfft;         // log2(nfft) when nfft is a power of two, else 0 (float64 kernel: FFT vs direct DFT)
     float refine_span;     // float32 kernels: a frame whose weakest mel band lies more than this (log power) below its largest bin is redone in float64 (0: never)
 };
+// Hops a frame spans, ceil(frame_len / frame_step) (3 for 400 / 160): after h pushes the newest complete frame is h - frames_lag.
+__host__ __device__ inline int frames_lag(int frame_len, int frame_step) { return (frame_len + frame_step - 1) / frame_step; }
+__host__ __device__ inline int frames_lag(const FrontendParams& p) { return frames_lag(p.frame_len, p.frame_step); }
 
 // Worklist of the selective float64 refinement: the float32 MFCC kernel appends, per frame pair with a
 // flagged frame, (global pair index << 2 | mask of flagged frames), global pair index = clip * ceil(num_frames / 2) +
@@ -299,7 +302,7 @@ struct DscnnStages {
 hipError_t launch_dscnn_composed(hipStream_t s, const DscnnWeights& w, const float* d_feat, int nb, int T, int F, const DscnnStages& st);
 constexpr int COMPOSED_MAX_CLIPS = 16384;
 
-// The decision layer (kws_decide.hip): posteriors, their moving average per stream, and further down the energy endpointer.
+// The decision layer (kws_decide.hip): posteriors and their moving average per stream.
 hipError_t launch_softmax(hipStream_t s, const float* d_logits, int B, int C, float* d_prob);
 hipError_t launch_smooth_posteriors(hipStream_t s, const float* d_logits, int S, int C, int window, float* d_ring,
                                     float* d_sum, int* d_count, float* d_smoothed, int32_t* d_label);
@@ -309,9 +312,6 @@ hipError_t launch_scan_detect(hipStream_t s, const float* d_logits, int R, int W
                               float threshold, int refractory, float* d_smoothed, int32_t* d_cand, float* d_score,
                               int32_t* d_event_window, int32_t* d_event_label, float* d_event_score, int max_events,
                               int32_t* d_event_count);
-hipError_t launch_stream_vad(hipStream_t s, const float* d_feat_ring, const int* d_hops, int n_streams, int num_frames, int numcep,
-                             int frames_lag, float threshold, int on_window, int off_window, unsigned char* d_flags, int* d_cursor_trig,
-                             int32_t* d_state);
 
 extern const char* const kKernelNames[KWS_K_COUNT];
 

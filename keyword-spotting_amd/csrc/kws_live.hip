@@ -12,31 +12,14 @@
 namespace kws {
 
 constexpr int LIVE_MAX_STREAMS = 1024;  // one workgroup walks every stream: one thread each
-constexpr int LIVE_MAX_WINDOW = 1024;   // off_window's limit (as kws_segment_f32)
-constexpr int LIVE_BIT_WORDS = LIVE_MAX_WINDOW / 64;
 constexpr int LIVE_REC = 6;             // int64 words per record
 constexpr int LIVE_CUT_THREADS = 256;
 
-// Everything kws_stream_utt_open allocates.  Device counters ctr[4] = frames walked, hops appended, events so far, kernels
-// finished; the host mirror h_ctr[3] = events so far, frames walked, kernels finished (the flag kws_stream_utt_poll spins on).
-struct StreamUtt {
-    int n_streams = 0, H = 0, max_events = 0;
-    int on_window = 0, off_window = 0, pre_roll = 0, max_frames = 0;
-    float threshold = 0.f;
-    int16_t* d_hist = nullptr;             // [S][H]
-    unsigned long long* d_bits = nullptr;  // [S][16]: voiced flag of frame f at bit f mod 1024
-    int* d_counts = nullptr;               // [S][4]: c_on, c_off, triggered, unused
-    long long* d_pos = nullptr;            // [S][2]: open, prev_close
-    unsigned long long* d_ctr = nullptr;   // [4]
-    long long* d_queue = nullptr;          // [max_events][6]
-    long long* h_queue = nullptr;          // pinned, device-mapped mirror of d_queue
-    unsigned long long* h_ctr = nullptr;   // pinned, device-mapped [3]
-    unsigned long long ticks_enqueued = 0; // kernels enqueued so far: h_ctr[2] reads this once the newest has landed
-    int mode = 0;                          // 0: not stepped yet, 1: stepped by pushes, 2: stepped by kws_stream_utt_step_i16
-};
-
 namespace {
 
+// What a step reads.  The first group is set per launch (utt_launch); the set's own size, rules and buffers below it are filled
+// once by kws_stream_utt_open.  Device counters ctr[4] = frames walked, hops appended, events so far, kernels finished; the host
+// mirror h_ctr[3] = events so far, frames walked, kernels finished (the flag kws_stream_utt_poll spins on).
 struct LiveArgs {
     const int16_t* hop;       // append source (nullptr: no append): stream s at hop + s * hop_stride (+ the ring offset with ctx_hops)
     long long hop_stride;
@@ -48,15 +31,26 @@ struct LiveArgs {
     int on_window, off_window, pre_roll, max_frames;
     float threshold;
     int vec;                  // the hop may be copied 16 bytes at a time
-    int16_t* hist;
-    unsigned long long* bits;
+    int16_t* hist;            // [S][H]
+    unsigned long long* bits; // [S][EP_BIT_WORDS], counts [S][4] = c_on, c_off, triggered, unused: ep_ring_push's state
     int* counts;
-    long long* pos;
-    unsigned long long* ctr;
-    long long* queue;
-    long long* h_queue;
-    unsigned long long* h_ctr;
+    long long* pos;           // [S][2]: open, prev_close
+    unsigned long long* ctr;  // [4]
+    long long* queue;         // [max_events][6]
+    long long* h_queue;       // pinned, device-mapped mirror of queue
+    unsigned long long* h_ctr;  // pinned, device-mapped [3]
 };
+
+}  // namespace
+
+// Everything kws_stream_utt_open allocates, as the step kernel takes it.
+struct StreamUtt {
+    LiveArgs a{};
+    unsigned long long ticks_enqueued = 0; // kernels enqueued so far: h_ctr[2] reads this once the newest has landed
+    int mode = 0;                          // 0: not stepped yet, 1: stepped by pushes, 2: stepped by kws_stream_utt_step_i16
+};
+
+namespace {
 
 __device__ __forceinline__ void store_host(long long* p, long long v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -126,24 +120,16 @@ __global__ __launch_bounds__(LIVE_MAX_STREAMS) void kws_live_step_kernel(const L
             }
         } else {
             const long long f = (long long)frames;
-            const int v = energy[(size_t)tid * e_stride] > a.threshold ? 1 : 0;  // float32, strict; a NaN is unvoiced
-            unsigned long long* bw = a.bits + (size_t)tid * LIVE_BIT_WORDS;
-            // the flags leaving the two windows are read BEFORE the new one is stored: with a window of 1024 they share its slot
-            auto flag_at = [&](long long g) -> int { return g < 0 ? 0 : (int)((bw[(g & (LIVE_MAX_WINDOW - 1)) >> 6] >> (g & 63)) & 1ull); };
-            const int c_on = cnt[0] + v - flag_at(f - a.on_window);
-            const int c_off = cnt[1] + v - flag_at(f - a.off_window);
-            const int slot = (int)(f & (LIVE_MAX_WINDOW - 1));
-            bw[slot >> 6] = (bw[slot >> 6] & ~(1ull << (slot & 63))) | ((unsigned long long)v << (slot & 63));
-            cnt[0] = c_on;
-            cnt[1] = c_off;
+            const int v = ep_voiced(energy[(size_t)tid * e_stride], a.threshold) ? 1 : 0;
+            const EpCounts n = ep_ring_push(a.bits + (size_t)tid * EP_BIT_WORDS, cnt, f, v, a.on_window, a.off_window);
             if (!trig) {
-                if (10 * c_on > 8 * a.on_window) {  // the utterance opens; nothing else happens at this frame
+                if (ep_opens(n.on, a.on_window)) {  // the utterance opens; nothing else happens at this frame
                     trig = 1;
                     open = f;
                     ps[0] = f;
                     cnt[2] = 1;
                 }
-            } else if (10 * (a.off_window - c_off) > 9 * a.off_window) {
+            } else if (ep_closes(n.off, a.off_window)) {
                 closed = true;
                 reason = 0;
                 close_frame = f;
@@ -154,8 +140,7 @@ __global__ __launch_bounds__(LIVE_MAX_STREAMS) void kws_live_step_kernel(const L
             }
         }
         if (closed) {
-            start_frame = open - a.pre_roll;
-            if (start_frame < prev_close + 1) start_frame = prev_close + 1;  // prev_close + 1 >= 0
+            start_frame = ep_span_start(open, a.pre_roll, prev_close);
             ps[1] = close_frame;
             cnt[2] = 0;
         }
@@ -195,16 +180,15 @@ __global__ __launch_bounds__(LIVE_MAX_STREAMS) void kws_live_step_kernel(const L
 
 // kws_cut_i16_kernel (kws_segment.hip) with a ring origin: one workgroup per sequence number, the record read from the device
 // queue.  The span [start, end) of stream r lies in the history ring from start mod H on and crosses the seam at most once
-// (end - start <= H): element i is at p0 + i, minus H from the seam on.  Same peak, same float64 divide, multiply and
-// truncation, same zeros beyond the span as the linear kernel.  Refused (zero clip, peak -1): a sequence number not issued yet
+// (end - start <= H): element i is at p0 + i, minus H from the seam on.  The cut itself is the linear kernel's (ep_cut_clip).
+// Refused (zero clip, peak -1): a sequence number not issued yet
 // or already overwritten in the queue, a span whose start has left the ring, a span that ends beyond what was appended.
 __global__ __launch_bounds__(LIVE_CUT_THREADS) void kws_live_cut_kernel(const int16_t* __restrict__ hist, int S, int H, int step,
                                                                         const long long* __restrict__ queue, int max_events,
                                                                         const unsigned long long* __restrict__ ctr,
                                                                         unsigned long long first_seq, int normalize_to,
                                                                         int16_t* __restrict__ clips, int n_out, int32_t* __restrict__ peak_out) {
-    __shared__ int wave_peak[LIVE_CUT_THREADS / 64];
-    const int u = blockIdx.x, tid = threadIdx.x;
+    const int u = blockIdx.x;
     const unsigned long long seq = first_seq + (unsigned long long)u, total = ctr[2];
     const long long have = (long long)(ctr[1] * (unsigned long long)step);  // samples appended so far
     bool ok = seq < total && seq + (unsigned long long)max_events >= total;  // workgroup-uniform throughout
@@ -224,50 +208,22 @@ __global__ __launch_bounds__(LIVE_CUT_THREADS) void kws_live_cut_kernel(const in
         p -= p >= H ? H : 0;
         return x[p];
     };
-    int16_t* out = clips + (size_t)u * n_out;
-    int peak = 0;
-    for (unsigned i = tid; i < (unsigned)len; i += LIVE_CUT_THREADS) {
-        const int v = at(i);
-        const int m = v < 0 ? -v : v;  // |-32768| = 32768
-        peak = m > peak ? m : peak;
-    }
-    for (int d = 32; d >= 1; d >>= 1) {
-        const int other = __shfl_xor(peak, d);
-        peak = other > peak ? other : peak;
-    }
-    if ((tid & 63) == 0) wave_peak[tid >> 6] = peak;
-    __syncthreads();
-    peak = wave_peak[0];
-    for (int k = 1; k < LIVE_CUT_THREADS / 64; ++k) peak = wave_peak[k] > peak ? wave_peak[k] : peak;
-    if (tid == 0 && peak_out) peak_out[u] = ok ? peak : -1;
-    const int body = len < n_out ? len : n_out;
-    if (normalize_to > 0) {
-        const double times = peak > 0 ? (double)normalize_to / (double)peak : 0.0;  // peak 0: the span is all zeros anyway
-        for (unsigned i = tid; i < (unsigned)n_out; i += LIVE_CUT_THREADS) out[i] = i < (unsigned)body ? (int16_t)(int)((double)at(i) * times) : (int16_t)0;
-    } else {
-        for (unsigned i = tid; i < (unsigned)n_out; i += LIVE_CUT_THREADS) out[i] = i < (unsigned)body ? (int16_t)at(i) : (int16_t)0;
-    }
+    ep_cut_clip<LIVE_CUT_THREADS>(at, len, ok, normalize_to, clips + (size_t)u * n_out, n_out, peak_out, u);
 }
-
-int frames_lag(const FrontendParams& p) { return (p.frame_len + p.frame_step - 1) / p.frame_step; }
 
 int history_for(int frame_len, int frame_step, int pre_roll, int max_frames, int slack_hops, long long* out) {
     if (frame_len < 1 || frame_step < 1 || pre_roll < 0 || max_frames < 2 || slack_hops < 0) return KWS_EINVAL;
-    const long long K = (frame_len + frame_step - 1) / frame_step;
+    const long long K = frames_lag(frame_len, frame_step);
     *out = ((long long)pre_roll + max_frames - 1 + K + slack_hops) * frame_step;
     return *out > INT_MAX ? KWS_EINVAL : KWS_OK;
 }
 
 void utt_release(StreamUtt* u) {
     if (!u) return;
-    if (u->d_hist) (void)hipFree(u->d_hist);
-    if (u->d_bits) (void)hipFree(u->d_bits);
-    if (u->d_counts) (void)hipFree(u->d_counts);
-    if (u->d_pos) (void)hipFree(u->d_pos);
-    if (u->d_ctr) (void)hipFree(u->d_ctr);
-    if (u->d_queue) (void)hipFree(u->d_queue);
-    if (u->h_queue) (void)hipHostFree(u->h_queue);
-    if (u->h_ctr) (void)hipHostFree(u->h_ctr);
+    for (void* d : {(void*)u->a.hist, (void*)u->a.bits, (void*)u->a.counts, (void*)u->a.pos, (void*)u->a.ctr, (void*)u->a.queue})
+        if (d) (void)hipFree(d);
+    if (u->a.h_queue) (void)hipHostFree(u->a.h_queue);
+    if (u->a.h_ctr) (void)hipHostFree(u->a.h_ctr);
     delete u;
 }
 
@@ -276,7 +232,7 @@ template <bool FLUSH>
 int utt_launch(kws_ctx* c, const int16_t* hop, long long hop_stride, const int* ctx_hops, const float* energy) {
     StreamUtt* u = c->stream_utt;
     const FrontendParams& p = c->fp;
-    LiveArgs a{};
+    LiveArgs a = u->a;
     a.hop = hop;
     a.hop_stride = hop_stride;
     a.ctx_hops = ctx_hops;
@@ -285,28 +241,12 @@ int utt_launch(kws_ctx* c, const int16_t* hop, long long hop_stride, const int* 
     a.num_frames = p.num_frames;
     a.numcep = p.numcep;
     a.K = frames_lag(p);
-    a.S = u->n_streams;
     a.step = p.frame_step;
     a.frame_len = p.frame_len;
-    a.H = u->H;
-    a.max_events = u->max_events;
-    a.on_window = u->on_window;
-    a.off_window = u->off_window;
-    a.pre_roll = u->pre_roll;
-    a.max_frames = u->max_frames;
-    a.threshold = u->threshold;
     // 16-byte copies: whole hops of 8 samples, every stream's hop and ring row on a 16-byte boundary (the ring offset and the
     // ring's write position are multiples of step)
     a.vec = hop && p.frame_step % 8 == 0 && hop_stride % 8 == 0 && reinterpret_cast<uintptr_t>(hop) % 16 == 0;
-    a.hist = u->d_hist;
-    a.bits = u->d_bits;
-    a.counts = u->d_counts;
-    a.pos = u->d_pos;
-    a.ctr = u->d_ctr;
-    a.queue = u->d_queue;
-    a.h_queue = u->h_queue;
-    a.h_ctr = u->h_ctr;
-    int threads = (u->n_streams + 63) / 64 * 64;
+    int threads = (a.S + 63) / 64 * 64;
     if (hop && threads < 256) threads = 256;  // the copy is the workgroup's bulk
     hipLaunchKernelGGL(kws_live_step_kernel<FLUSH>, dim3(1), dim3(threads), 0, c->stream, a);
     HIP_TRY(c, hipGetLastError());
@@ -353,9 +293,9 @@ int kws_stream_utt_open(kws_ctx* c, float log_energy_threshold, int on_window, i
     KWS_GUARD_BEGIN
     if (!c) return KWS_EINVAL;
     if (!c->n_streams) return fail(c, KWS_ESTATE, "kws_stream_utt_open: call kws_stream_open first");
-    if (!c->fp.append_energy) return fail(c, KWS_EUNSUPPORTED, "kws_stream_utt_open: needs cepstrum 0 = log frame energy (appendEnergy)");
-    if (on_window < 1 || off_window < on_window || off_window > LIVE_MAX_WINDOW)
-        return fail(c, KWS_EINVAL, "kws_stream_utt_open: need 1 <= on_window <= off_window <= 1024");
+    int rc = check_append_energy(c, "kws_stream_utt_open");
+    if (!rc) rc = check_endpoint_windows(c, "kws_stream_utt_open", on_window, off_window);
+    if (rc) return rc;
     if (pre_roll < 0 || max_frames < 2)
         return fail(c, KWS_EINVAL, "kws_stream_utt_open: need pre_roll >= 0 and max_frames >= 2 (a live ring is bounded: there is no \"no time-out\")");
     long long need = 0;
@@ -370,40 +310,35 @@ int kws_stream_utt_open(kws_ctx* c, float log_energy_threshold, int on_window, i
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     stream_utt_free(c);
     StreamUtt* u = new StreamUtt();
+    LiveArgs& a = u->a;
     const size_t S = (size_t)c->n_streams;
-    u->n_streams = c->n_streams;
-    u->H = history_samples;
-    u->max_events = max_events;
-    u->on_window = on_window;
-    u->off_window = off_window;
-    u->pre_roll = pre_roll;
-    u->max_frames = max_frames;
-    u->threshold = log_energy_threshold;
-    const size_t hist_b = sizeof(int16_t) * S * (size_t)u->H, bits_b = sizeof(unsigned long long) * S * LIVE_BIT_WORDS,
-                 counts_b = sizeof(int) * S * 4, pos_b = sizeof(long long) * S * 2, ctr_b = sizeof(unsigned long long) * 4,
+    a.S = c->n_streams;
+    a.H = history_samples;
+    a.max_events = max_events;
+    a.on_window = on_window;
+    a.off_window = off_window;
+    a.pre_roll = pre_roll;
+    a.max_frames = max_frames;
+    a.threshold = log_energy_threshold;
+    const size_t hist_b = sizeof(int16_t) * S * (size_t)a.H, pos_b = sizeof(long long) * S * 2, ctr_b = sizeof(unsigned long long) * 4,
                  queue_b = sizeof(long long) * (size_t)max_events * LIVE_REC;
     const unsigned flags = hipHostMallocMapped | hipHostMallocCoherent;  // fine-grained: device stores are visible to the host as they land
-    if (hipMalloc(reinterpret_cast<void**>(&u->d_hist), hist_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&u->d_bits), bits_b) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&u->d_counts), counts_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&u->d_pos), pos_b) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&u->d_ctr), ctr_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&u->d_queue), queue_b) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&u->h_queue), queue_b, flags) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&u->h_ctr), 64, flags) != hipSuccess) {
+    if (hipMalloc(reinterpret_cast<void**>(&a.hist), hist_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&a.pos), pos_b) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&a.ctr), ctr_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&a.queue), queue_b) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void**>(&a.h_queue), queue_b, flags) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void**>(&a.h_ctr), 64, flags) != hipSuccess) {
         utt_release(u);
         return fail(c, KWS_ENOMEM, "kws_stream_utt_open: allocation failed");
     }
-    memset(u->h_queue, 0, queue_b);
-    memset(u->h_ctr, 0, 64);
-    hipError_t e = hipMemsetAsync(u->d_hist, 0, hist_b, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(u->d_bits, 0, bits_b, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(u->d_counts, 0, counts_b, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(u->d_pos, 0xFF, pos_b, c->stream);  // open = prev_close = -1
-    if (e == hipSuccess) e = hipMemsetAsync(u->d_ctr, 0, ctr_b, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(u->d_queue, 0, queue_b, c->stream);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(c->stream);
-        utt_release(u);
-        return fail_hip(c, e, "kws_stream_utt_open: hipMemsetAsync");
-    }
+    memset(a.h_queue, 0, queue_b);
+    memset(a.h_ctr, 0, 64);
+    auto drop = [&](int code) { (void)hipStreamSynchronize(c->stream); utt_release(u); return code; };
+    if ((rc = alloc_endpoint_state(c, "kws_stream_utt_open", S, a.bits, a.counts))) return drop(rc);
+    hipError_t e = hipMemsetAsync(a.hist, 0, hist_b, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(a.pos, 0xFF, pos_b, c->stream);  // open = prev_close = -1
+    if (e == hipSuccess) e = hipMemsetAsync(a.ctr, 0, ctr_b, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(a.queue, 0, queue_b, c->stream);
+    if (e != hipSuccess) return drop(fail_hip(c, e, "kws_stream_utt_open: hipMemsetAsync"));
     c->stream_utt = u;
     return KWS_OK;
     KWS_GUARD_END(c, "kws_stream_utt_open")
@@ -441,7 +376,7 @@ int kws_stream_utt_poll(kws_ctx* c, uint64_t* total_events, uint64_t* steps) {
     StreamUtt* u = c->stream_utt;
     if (!u) return fail(c, KWS_ESTATE, "kws_stream_utt_poll: call kws_stream_utt_open first");
     // spin on the count of finished kernels; bounded: after ~2 ms without it, fall back to the stream (kws_stream_wait_host)
-    volatile unsigned long long* h = u->h_ctr;
+    volatile unsigned long long* h = u->a.h_ctr;
     const unsigned long long want = u->ticks_enqueued;
     bool seen = false;
     const auto t0 = std::chrono::steady_clock::now();
@@ -469,17 +404,17 @@ int kws_stream_utt_read(kws_ctx* c, uint64_t first_seq, int n, int64_t* out_reco
     StreamUtt* u = c->stream_utt;
     if (!u) return fail(c, KWS_ESTATE, "kws_stream_utt_read: call kws_stream_utt_open first");
     if (n < 1 || !out_records) return fail(c, KWS_EINVAL, "kws_stream_utt_read: n must be positive and out_records not NULL");
-    volatile unsigned long long* h = u->h_ctr;
+    volatile unsigned long long* h = u->a.h_ctr;
     unsigned long long total = h[0];
     std::atomic_thread_fence(std::memory_order_acquire);
     if (first_seq + (unsigned long long)n > total) return fail(c, KWS_EINVAL, "kws_stream_utt_read: sequence numbers beyond the events landed so far");
     for (int i = 0; i < n; ++i) {
-        const volatile long long* rec = u->h_queue + (size_t)((first_seq + i) % (unsigned long long)u->max_events) * LIVE_REC;
+        const volatile long long* rec = u->a.h_queue + (size_t)((first_seq + i) % (unsigned long long)u->a.max_events) * LIVE_REC;
         for (int k = 0; k < LIVE_REC; ++k) out_records[(size_t)i * LIVE_REC + k] = rec[k];
     }
     std::atomic_thread_fence(std::memory_order_acquire);
     total = h[0];  // again: a step that landed during the copy may have overwritten the oldest
-    if (first_seq + (unsigned long long)u->max_events < total) return fail(c, KWS_EINVAL, "kws_stream_utt_read: the sequence number is no longer in the queue");
+    if (first_seq + (unsigned long long)u->a.max_events < total) return fail(c, KWS_EINVAL, "kws_stream_utt_read: the sequence number is no longer in the queue");
     return KWS_OK;
 }
 
@@ -489,10 +424,10 @@ int kws_stream_utt_cut_i16(kws_ctx* c, uint64_t first_seq, int U, int normalize_
     if (!u) return fail(c, KWS_ESTATE, "kws_stream_utt_cut_i16: call kws_stream_utt_open first");
     if (!d_clips) return fail(c, KWS_EINVAL, "kws_stream_utt_cut_i16: d_clips is NULL");
     if (U < 1 || n_out < 1) return fail(c, KWS_EINVAL, "kws_stream_utt_cut_i16: U and n_out must be positive");
-    if (normalize_to < 0 || normalize_to > 32767) return fail(c, KWS_EINVAL, "kws_stream_utt_cut_i16: normalize_to must be in [0, 32767]");
+    if (int rc = check_normalize_to(c, "kws_stream_utt_cut_i16", normalize_to)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    hipLaunchKernelGGL(kws_live_cut_kernel, dim3(U), dim3(LIVE_CUT_THREADS), 0, c->stream, u->d_hist, u->n_streams, u->H, c->fp.frame_step,
-                       u->d_queue, u->max_events, u->d_ctr, (unsigned long long)first_seq, normalize_to, d_clips, n_out, d_peak);
+    hipLaunchKernelGGL(kws_live_cut_kernel, dim3(U), dim3(LIVE_CUT_THREADS), 0, c->stream, u->a.hist, u->a.S, u->a.H, c->fp.frame_step,
+                       u->a.queue, u->a.max_events, u->a.ctr, (unsigned long long)first_seq, normalize_to, d_clips, n_out, d_peak);
     HIP_TRY(c, hipGetLastError());
     return KWS_OK;
 }

@@ -2,7 +2,7 @@
 // reference's record-then-classify loop (kws/inference/inference_local.py:114-192): the MFCC pass of a scan on its own, the
 // energy endpointer walked over a whole frame array with the reference's start point and time-out, and normalize + fix_length
 // for a list of sample spans.  What follows a clip (kws_infer_i16) is elsewhere; nothing here touches another unit's kernels.
-#include "kws_ctx.h"
+#include "kws_ctx.h"  // kws_endpoint_dev.h: the endpointer's rules and the clip cut
 
 using namespace kws;
 
@@ -10,8 +10,7 @@ namespace {
 
 constexpr int SEG_THREADS = 256;                 // frames per workgroup of the flag kernel: four ballot words
 constexpr int SEG_WORDS = SEG_THREADS / 64;
-constexpr int SEG_MAX_WINDOW = 1024;             // off_window's limit (as kws_stream_vad_f32)
-constexpr int SEG_BACK_WORDS = SEG_MAX_WINDOW / 64;  // ballot words of history a workgroup can need: ceil((1024 - 1) / 64)
+constexpr int SEG_BACK_WORDS = EP_BIT_WORDS;     // ballot words of history a workgroup can need: ceil((1024 - 1) / 64)
 constexpr int CUT_THREADS = 256;
 
 // Voiced frames among the `window` frames ending at local frame `at` (bit b of words[j] = local frame 64 j + b; at >= window - 1).
@@ -32,7 +31,7 @@ __device__ __forceinline__ int voiced_in_window(const unsigned long long* words,
 // The workgroup first packs the voiced flags of its own frames and of the `back` words before them (frames before 0 and past
 // F are unvoiced) into ballot words in LDS -- wavefront v takes words v, v + 4, ... -- then every thread counts its two
 // windows as popcounts over at most 17 words and the wavefront's answers leave as two ballot words:
-//   open_ok[f]  = 10 c_on[f] > 8 on_window,  close_ok[f] = 10 (off_window - c_off[f]) > 9 off_window.
+//   open_ok[f]  = ep_opens(c_on[f], on_window),  close_ok[f] = ep_closes(c_off[f], off_window).
 // ok: [R][2][n_words], n_words = ceil(F / 64); bits at or beyond F are zero.
 __global__ __launch_bounds__(SEG_THREADS) void kws_segment_flags_kernel(const float* __restrict__ feat, int F, int numcep, float threshold,
                                                                         int on_window, int off_window, int back, int n_words,
@@ -44,7 +43,7 @@ __global__ __launch_bounds__(SEG_THREADS) void kws_segment_flags_kernel(const fl
     const float* fr = feat + (size_t)r * F * numcep;
     for (int j = wave; j < back + SEG_WORDS; j += SEG_WORDS) {  // wave-uniform
         const int g = base + j * 64 + lane;
-        const bool voiced = g >= 0 && g < F && fr[(size_t)g * numcep] > threshold;  // a NaN compares false: unvoiced
+        const bool voiced = g >= 0 && g < F && ep_voiced(fr[(size_t)g * numcep], threshold);
         const unsigned long long b = __ballot(voiced);
         if (lane == 0) words[j] = b;
     }
@@ -53,8 +52,8 @@ __global__ __launch_bounds__(SEG_THREADS) void kws_segment_flags_kernel(const fl
     const int at = back * 64 + threadIdx.x;  // back * 64 >= off_window - 1: both windows start inside words[]
     const int c_on = voiced_in_window(words, at, on_window);
     const int c_off = voiced_in_window(words, at, off_window);
-    const unsigned long long open_ok = __ballot(f < F && 10 * c_on > 8 * on_window);
-    const unsigned long long close_ok = __ballot(f < F && 10 * (off_window - c_off) > 9 * off_window);
+    const unsigned long long open_ok = __ballot(f < F && ep_opens(c_on, on_window));
+    const unsigned long long close_ok = __ballot(f < F && ep_closes(c_off, off_window));
     const int w = f0 / 64 + wave;
     if (lane == 0 && w < n_words) {
         unsigned long long* o = ok + (size_t)r * 2 * n_words;
@@ -77,8 +76,7 @@ __global__ __launch_bounds__(64) void kws_segment_walk_kernel(const unsigned lon
     bool triggered = false;
     int open = 0, prev_close = -1, count = 0;
     auto close_at = [&](int f, int reason) {
-        long long start = (long long)open - pre_roll;
-        if (start < prev_close + 1) start = prev_close + 1;  // prev_close + 1 >= 0
+        const long long start = ep_span_start(open, pre_roll, prev_close);
         const long long end = (long long)f * frame_step + frame_len;
         if (lane == 0 && count < max_utts) {
             int32_t* u = ur + (size_t)count * 5;
@@ -139,14 +137,11 @@ __global__ __launch_bounds__(64) void kws_segment_walk_kernel(const unsigned lon
     if (lane == 0) count_out[r] = count;
 }
 
-// normalize (inference_local.py:102-109) then fix_length (:70) of one span per workgroup: the peak over the WHOLE span (the
-// reference normalises before it trims), then n_out samples, scaled in float64 and truncated towards zero as int(i * times),
-// zero beyond the span.  A span starts at any sample: 2-byte loads.
+// normalize then fix_length (ep_cut_clip) of one span per workgroup.  A span starts at any sample: 2-byte loads.
 __global__ __launch_bounds__(CUT_THREADS) void kws_cut_i16_kernel(const int16_t* __restrict__ pcm, int R, int n_total,
                                                                   const int32_t* __restrict__ span, int normalize_to,
                                                                   int16_t* __restrict__ clips, int n_out, int32_t* __restrict__ peak_out) {
-    __shared__ int wave_peak[CUT_THREADS / 64];
-    const int u = blockIdx.x, tid = threadIdx.x;
+    const int u = blockIdx.x;
     const int r = span[3 * (size_t)u];
     int start = span[3 * (size_t)u + 1], end = span[3 * (size_t)u + 2];
     start = start < 0 ? 0 : (start > n_total ? n_total : start);
@@ -154,29 +149,7 @@ __global__ __launch_bounds__(CUT_THREADS) void kws_cut_i16_kernel(const int16_t*
     const bool in_range = r >= 0 && r < R;  // workgroup-uniform
     const int len = in_range && end > start ? end - start : 0;
     const int16_t* x = pcm + (in_range ? (size_t)r * n_total + start : 0);
-    int16_t* out = clips + (size_t)u * n_out;
-    int peak = 0;
-    for (unsigned i = tid; i < (unsigned)len; i += CUT_THREADS) {
-        const int v = x[i];
-        const int a = v < 0 ? -v : v;  // |-32768| = 32768
-        peak = a > peak ? a : peak;
-    }
-    for (int d = 32; d >= 1; d >>= 1) {
-        const int other = __shfl_xor(peak, d);
-        peak = other > peak ? other : peak;
-    }
-    if ((tid & 63) == 0) wave_peak[tid >> 6] = peak;
-    __syncthreads();
-    peak = wave_peak[0];
-    for (int k = 1; k < CUT_THREADS / 64; ++k) peak = wave_peak[k] > peak ? wave_peak[k] : peak;
-    if (tid == 0 && peak_out) peak_out[u] = in_range ? peak : -1;
-    const int body = len < n_out ? len : n_out;
-    if (normalize_to > 0) {
-        const double times = peak > 0 ? (double)normalize_to / (double)peak : 0.0;  // peak 0: the span is all zeros anyway
-        for (unsigned i = tid; i < (unsigned)n_out; i += CUT_THREADS) out[i] = i < (unsigned)body ? (int16_t)(int)((double)x[i] * times) : (int16_t)0;
-    } else {
-        for (unsigned i = tid; i < (unsigned)n_out; i += CUT_THREADS) out[i] = i < (unsigned)body ? x[i] : (int16_t)0;
-    }
+    ep_cut_clip<CUT_THREADS>([&](unsigned i) -> int { return x[i]; }, len, in_range, normalize_to, clips + (size_t)u * n_out, n_out, peak_out, u);
 }
 
 }  // namespace
@@ -203,18 +176,18 @@ int kws_segment_f32(kws_ctx* c, const float* d_feat, int R, int F_total, int n_t
     if (!c) return KWS_EINVAL;
     if (!d_feat || !d_count) return fail(c, KWS_EINVAL, "kws_segment_f32: d_feat / d_count is NULL");
     if (R < 1 || F_total < 1 || n_total < 1) return fail(c, KWS_EINVAL, "kws_segment_f32: R, F_total and n_total must be positive");
-    if (on_window < 1 || off_window < on_window || off_window > SEG_MAX_WINDOW)
-        return fail(c, KWS_EINVAL, "kws_segment_f32: need 1 <= on_window <= off_window <= 1024");
+    int rc = check_endpoint_windows(c, "kws_segment_f32", on_window, off_window);
+    if (rc) return rc;
     if (pre_roll < 0 || (max_frames != 0 && max_frames < 2))
         return fail(c, KWS_EINVAL, "kws_segment_f32: need pre_roll >= 0 and max_frames == 0 or >= 2");
     if (max_utts < 0 || (max_utts > 0 && !d_utt)) return fail(c, KWS_EINVAL, "kws_segment_f32: max_utts utterances need d_utt");
     if (!c->fe_ready) return fail(c, KWS_ESTATE, "kws_segment_f32: front end not configured");
-    if (!c->fp.append_energy) return fail(c, KWS_EUNSUPPORTED, "kws_segment_f32: needs cepstrum 0 = log frame energy (appendEnergy)");
+    if ((rc = check_append_energy(c, "kws_segment_f32"))) return rc;
     if ((unsigned long long)R * F_total > (1ull << 28)) return fail(c, KWS_EUNSUPPORTED, "kws_segment_f32: more than 2^28 frames in one call");
     HIP_TRY(c, hipSetDevice(c->device));
     // context scratch: open_ok and close_ok as ballot words, [R][2][n_words] of 64 bits
     const int n_words = (F_total + 63) / 64;
-    int rc = grow_device_buffer(c, c->d_conv_ws, c->conv_ws_floats, (size_t)R * 2 * n_words * 2, "kws_segment_f32", "workspace");
+    rc = grow_device_buffer(c, c->d_conv_ws, c->conv_ws_floats, (size_t)R * 2 * n_words * 2, "kws_segment_f32", "workspace");
     if (rc) return rc;
     unsigned long long* ok = reinterpret_cast<unsigned long long*>(c->d_conv_ws);
     const int back = (off_window - 1 + 63) / 64;  // words of history before a workgroup's first frame: <= 16
@@ -233,7 +206,7 @@ int kws_cut_i16(kws_ctx* c, const int16_t* d_pcm, int R, int n_total, const int3
     if (!c) return KWS_EINVAL;
     if (!d_pcm || !d_span || !d_clips) return fail(c, KWS_EINVAL, "kws_cut_i16: d_pcm / d_span / d_clips is NULL");
     if (U < 1 || R < 1 || n_total < 1 || n_out < 1) return fail(c, KWS_EINVAL, "kws_cut_i16: U, R, n_total and n_out must be positive");
-    if (normalize_to < 0 || normalize_to > 32767) return fail(c, KWS_EINVAL, "kws_cut_i16: normalize_to must be in [0, 32767]");
+    if (int rc = check_normalize_to(c, "kws_cut_i16", normalize_to)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     hipLaunchKernelGGL(kws_cut_i16_kernel, dim3(U), dim3(CUT_THREADS), 0, c->stream, d_pcm, R, n_total, d_span, normalize_to, d_clips,
                        n_out, d_peak);

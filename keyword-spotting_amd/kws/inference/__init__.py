@@ -66,6 +66,25 @@ class Utterance:
     peak: int
 
 
+def _classify_spans(ctx, device, words, num_classes: int, clip_samples: int, rate: float, frame_step: int, rows, cut) -> List[Utterance]:
+    """The tail ``segment`` and ``pop_utterances`` share: ``rows`` of ``(recording, start, end, open, close, reason)``, samples
+    and frames; ``cut(clips, peaks)`` launches the cut of row ``u`` into ``clips[u]`` and ``peaks[u]``.  Then the model once per
+    clip and ONE read of logits, labels and peaks."""
+    U, C = len(rows), num_classes
+    clips = torch.empty((U, clip_samples), dtype=torch.int16, device=device)
+    out = torch.empty((U * (C + 2),), dtype=torch.float32, device=device)  # logits [U, C], then labels [U] and peaks [U] as int32
+    logits, ints = out[:U * C].view(U, C), out[U * C:].view(torch.int32)
+    torch.cuda.current_stream(device).synchronize()  # a context may run on its own stream
+    cut(clips, ints[U:])
+    ctx.infer_i16(clips, logits, ints[:U])
+    ctx.sync()
+    host = out.cpu()  # the one read
+    logits, ints = host[:U * C].view(U, C).numpy(), host[U * C:].view(torch.int32).numpy()
+    return [Utterance(int(r), int(start) / rate, int(end) / rate, int(opened) * frame_step / rate, int(closed) * frame_step / rate,
+                      UTTERANCE_REASONS[int(reason)], int(ints[u]), words[int(ints[u])], logits[u].copy(), int(ints[U + u]))
+            for u, (r, start, end, opened, closed, reason) in enumerate(rows)]
+
+
 @dataclass
 class UtteranceConfig:
     """``StreamingSpotter(utterances=...)``: the reference's live loop on the streams.  A frame is voiced when its log energy
@@ -364,19 +383,10 @@ class KeywordSpotter:
         out: List[List[Utterance]] = [[] for _ in range(R)]
         if not rows:
             return out
-        U, C = len(rows), self.model.num_classes
         span = torch.tensor([row[:3] for row in rows], dtype=torch.int32).to(self.device)
-        clips = torch.empty((U, cfg.desired_samples), dtype=torch.int16, device=self.device)
-        peak = torch.empty((U,), dtype=torch.int32, device=self.device)
-        logits = torch.empty((U, C), dtype=torch.float32, device=self.device)
-        labels = torch.empty((U,), dtype=torch.int32, device=self.device)
-        ctx.cut_i16(x, span, clips, int(normalize), peak)
-        ctx.infer_i16(clips, logits, labels)
-        logits, labels, peak = logits.cpu().numpy(), labels.cpu().numpy(), peak.cpu().numpy()
-        rate = float(cfg.sample_rate)
-        for u, (r, start, end, opened, closed, reason) in enumerate(rows):
-            out[r].append(Utterance(r, start / rate, end / rate, opened * frame_step / rate, closed * frame_step / rate,
-                                    UTTERANCE_REASONS[reason], int(labels[u]), self.words[int(labels[u])], logits[u].copy(), int(peak[u])))
+        for utt in _classify_spans(ctx, self.device, self.words, self.model.num_classes, cfg.desired_samples, float(cfg.sample_rate), frame_step,
+                                   rows, lambda clips, peaks: ctx.cut_i16(x, span, clips, int(normalize), peaks)):
+            out[utt.recording].append(utt)
         return out
 
     def segment_file(self, path: str, resample: bool = False, **kwargs) -> List[Utterance]:
@@ -583,20 +593,9 @@ class StreamingSpotter:
             return []
         rec = self._ctx.stream_utt_read(first, U)
         self._utt_seq = total
-        C, n = self.model.num_classes, self.config.desired_samples
-        clips = torch.empty((U, n), dtype=torch.int16, device=self.device)
-        out = torch.empty((U * (C + 2),), dtype=torch.float32, device=self.device)  # logits [U, C], then labels [U] and peaks [U] as int32
-        logits, ints = out[:U * C].view(U, C), out[U * C:].view(torch.int32)
-        torch.cuda.current_stream(self.device).synchronize()  # the context runs on its own stream
-        self._ctx.stream_utt_cut_i16(first, clips, int(self.utterances.normalize), ints[U:])
-        self._ctx.infer_i16(clips, logits, ints[:U])
-        self._ctx.sync()
-        host = out.cpu()  # the one read
-        logits, ints = host[:U * C].view(U, C).numpy(), host[U * C:].view(torch.int32).numpy()
-        rate, step = float(self.config.sample_rate), self.hop
-        return [Utterance(int(s), int(start) / rate, int(end) / rate, int(opened) * step / rate, int(closed) * step / rate,
-                          UTTERANCE_REASONS[int(reason)], int(ints[u]), self.words[int(ints[u])], logits[u].copy(), int(ints[U + u]))
-                for u, (s, start, end, opened, closed, reason) in enumerate(rec)]
+        return _classify_spans(self._ctx, self.device, self.words, self.model.num_classes, self.config.desired_samples,
+                               float(self.config.sample_rate), self.hop, rec,
+                               lambda clips, peaks: self._ctx.stream_utt_cut_i16(first, clips, int(self.utterances.normalize), peaks))
 
     def flush(self) -> List[Utterance]:
         """Close every utterance that is still open, at the newest frame and with reason ``"end_of_recording"``

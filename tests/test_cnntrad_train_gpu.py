@@ -69,6 +69,7 @@ def _load(ctx, state, C):
 
 def _backward(ctx, xd, dld, n):
     grad = torch.full((n,), float("nan"), dtype=torch.float32, device=DEV)
+    torch.cuda.synchronize()  # the fill runs on torch's stream, the context on its own: the fill must land first
     ctx.cnn_trad_backward_f32(xd, dld, grad)
     ctx.sync()
     return grad
@@ -80,6 +81,7 @@ def _debug(ctx, xd):
     win = torch.full((B, 64, 99, 3), -1, dtype=torch.int32, device=DEV)
     conv2 = torch.full((B, 64, 99, 3), float("nan"), device=DEV)
     hidden = torch.full((B, 160), float("nan"), device=DEV)
+    torch.cuda.synchronize()  # as in _backward: the four fills are on torch's stream
     ctx.cnn_trad_train_debug_f32(xd, conv1, win, conv2, hidden)
     ctx.sync()
     return conv1.cpu(), win.cpu(), conv2.cpu(), hidden.cpu()

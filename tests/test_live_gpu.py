@@ -89,6 +89,24 @@ def test_walk_sweep_equals_the_whole_signal_walk(bare, F):
                 assert got == want, (F, on, off, pre_roll, max_frames)
 
 
+def test_walk_at_the_longest_windows_past_one_turn_of_the_flag_ring(bare):
+    """(1024, 1024) over 1100 frames: from frame 1024 on the flag that leaves both windows sits in the slot the new flag takes.
+    Stream 0 (the flag track of test_stream_decisions_gpu.test_endpointer_longest_off_window's second case) has a voiced run, a
+    pause and is voiced from then on: it opens past frame 1024, when frames of the run have left the windows, and the flush
+    closes it.  Stream 1 never opens."""
+    S, F, on, off = 2, 1100, 1024, 1024
+    flags = np.zeros((S, F), np.int64)
+    flags[0, 2:34] = 1
+    flags[0, 250:] = 1
+    flags[1, 2:30] = 1
+    flags[1, 598:601] = 1
+    want = lr.whole_signal_records(flags, on, off, 0, 2000)
+    assert len(want) == 1 and want[0][0] == 0 and want[0][5] == 2 and want[0][3] >= 1024 and flags[0, :want[0][3] - 1023].any()
+    assert want == lr.live_run(flags, on, off, 0, 2000)
+    got, total, steps = _walk(bare, flags, on, off, 0, 2000)
+    assert (total, steps) == (1, F) and got == want
+
+
 def test_threshold_is_strict_and_a_nan_is_unvoiced(bare):
     S, F = 3, 12
     e = np.full((F, S), 5.0, np.float32)

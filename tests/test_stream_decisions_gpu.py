@@ -401,8 +401,8 @@ def _cycles(on, off, hops):
 
 def _oracle_states(pcm, on, off, first_hop=0, last_hop=None):
     """What kws_stream_vad_f32 reports after each of the pushes first_hop .. last_hop - 1 of `pcm` when its history starts empty at
-    first_hop: int [hops, S], and per stream and hop (voiced of the last `on` flags, voiced of all `off` flags, event) as the
-    oracle's flag deque shows them (None while no frame is complete)."""
+    first_hop: int [hops, S], and per stream and hop (voiced of the last `on` flags, voiced of all `off` flags, event, newest
+    flag) as the oracle's flag deque shows them (None while no frame is complete)."""
     S, H = pcm.shape[0], pcm.shape[1] // STEP
     last_hop = H if last_hop is None else last_hop
     want = np.zeros((last_hop - first_hop, S), np.int32)
@@ -418,7 +418,7 @@ def _oracle_states(pcm, on, off, first_hop=0, last_hop=None):
             trig, ev = ref.update(v)
             flags = list(ref.flags)
             want[t - first_hop, s] = int(trig) | (ev << 1)
-            stats[s][t - first_hop] = (sum(flags[-on:]), sum(flags), ev)
+            stats[s][t - first_hop] = (sum(flags[-on:]), sum(flags), ev, flags[-1])
     return want, stats
 
 
@@ -495,7 +495,11 @@ def test_endpointer_longest_off_window(sctx):
     throughout: it opens at once and -- the history before the stream counting as unvoiced -- closes and reopens until more than
     a tenth of the last 1024 flags are voiced (103), then stays open to the end.  Stream 1 has a voiced run and afterwards a single
     voiced hop inside every 1024: by the closing rule (more than 90 % of the last 1024 unvoiced) it cannot stay open, and the
-    device closes it where the oracle does."""
+    device closes it where the oracle does.
+
+    Then (1024, 1024) over the same 1100 hops: a flag leaves BOTH windows through the slot the new one takes.  Stream 0 has a
+    short voiced run, a pause and is voiced from then on, so that it opens only at a frame of 1024 or later, when voiced frames
+    of the run have left the window: a count that never subtracts a leaving flag would open it earlier.  Stream 1 never opens."""
     on, off, H = 10, 1024, 1100
     p = np.zeros((2, H), bool)
     p[0, 4:] = True
@@ -506,6 +510,25 @@ def test_endpointer_longest_off_window(sctx):
     ev0 = _events(want)[0]
     assert want[-1, 0] == 1 and ev0[-1][1] == 1 and stats[0][ev0[-1][0]][1] == 103 and len(ev0) > 3
     assert want[-1, 1] == 0 and len(_events(want)[1]) >= 2
+    sctx.stream_open(2)
+    got = _vad(sctx, _to_hops(pcm), on, off)
+    assert np.array_equal(got, want), np.argwhere(got != want)[:5]
+
+    on = off = 1024
+    p = np.zeros((2, H), bool)
+    p[0, 4:34] = True
+    p[0, 252:] = True
+    p[1, 4:30] = True
+    p[1, 600] = True
+    pcm = _pcm(p, seed=2048)
+    want, stats = _oracle_states(pcm, on, off)
+    ev0, ev1 = _events(want)
+    voiced = [x[3] for x in stats[0] if x is not None]  # the oracle's flag of every frame
+    first_open = ev0[0][0] - (LAG - 1)                  # as a frame index
+    assert ev0[0][1] == 1 and first_open >= 1024 and sum(voiced[:first_open - 1023]) > 0  # voiced frames have left the window
+    never_leaving = next(f for f in range(len(voiced)) if 10 * sum(voiced[:f + 1]) > 8 * on)
+    assert never_leaving != first_open and not ev1
+    sctx.stream_close()
     sctx.stream_open(2)
     got = _vad(sctx, _to_hops(pcm), on, off)
     assert np.array_equal(got, want), np.argwhere(got != want)[:5]
