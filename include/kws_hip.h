@@ -100,6 +100,16 @@ int kws_set_frontend(kws_ctx* ctx, int sample_rate, int n_samples, int frame_len
 int kws_set_frontend_math(kws_ctx* ctx, int math);
 int kws_frontend_math(kws_ctx* ctx);
 
+/* Diagnostics: which float32 kernel int16 PCM at the reference geometry (frames of 400 samples every 160, 26 filters, 10
+ * cepstra) takes.  Both compute the same bits, flags included.
+ *   KWS_FE_ROUTE_AUTO (default): the wavefront-resident kernel compiled for that geometry.
+ *   KWS_FE_ROUTE_GENERIC: the wavefront-resident kernel that reads the geometry at run time, as every other geometry it covers
+ *     does -- for A/B timing and bit comparison inside one process.
+ * Any other value: KWS_EINVAL.  Takes effect from the next call; other geometries, sources and KWS_FE_F64 are unaffected. */
+#define KWS_FE_ROUTE_AUTO 0
+#define KWS_FE_ROUTE_GENERIC 1
+int kws_set_frontend_route(kws_ctx* ctx, int route);
+
 /* Selective float64 refinement of KWS_FE_F32 -- what makes the default front end meet psf's float64 arithmetic
  * (kws/libs/audio_processor.py:270-278) to 1e-4 on every frame.  A float32 transform leaves rounding noise a fixed distance
  * below the frame's strongest spectral component, so the float32 kernel measures, per frame, how far its weakest mel band

@@ -38,6 +38,8 @@ struct kws_ctx {
     FrontendParams fp{};
     bool fe_ready = false;
     bool fe_fast_ok = false;      // the float32 kernel covers this geometry (nfft 512, frame_len <= 512, sparse mel layout fits)
+    bool fe_ref_geometry = false; // frame length, hop, filters and cepstra are the reference's: int16 PCM may take kws_mfcc_i16_ref_kernel
+    int fe_route = KWS_FE_ROUTE_AUTO;  // kws_set_frontend_route (diagnostics): KWS_FE_ROUTE_GENERIC keeps such calls on the generic kernel
     int fe_math = KWS_FE_F32;     // requested arithmetic (kws_set_frontend_math); geometries without a fast kernel run in float64 anyway
     void* d_fe = nullptr;  // one allocation holding all front-end tables
     FrontendTables ft{};

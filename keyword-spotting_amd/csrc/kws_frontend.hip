@@ -62,20 +62,21 @@ int run_frontend(kws_ctx* c, const FrontendParams& geometry, Src src, int B, flo
             return KWS_OK;
         }
     c->frames_seen += (unsigned long long)B * p.num_frames;
+    const bool ref_route = c->fe_ref_geometry && c->fe_route == KWS_FE_ROUTE_AUTO;
     if (p.refine_span > 0.f) {
         int rc = ensure_refine(c, B, p.num_frames);
         if (rc) return rc;
         const RefineList rl = {c->d_refine, c->d_refine + 8, c->refine_cap, 0};
         {
             ProfScope ps(c, KWS_K_MFCC);
-            HIP_TRY(c, launch_mfcc(c->stream, p, c->ft, src, B, d_out, rl));
+            HIP_TRY(c, launch_mfcc(c->stream, p, c->ft, src, B, d_out, rl, ref_route));
         }
         ProfScope ps(c, KWS_K_MFCC_REFINE);
         HIP_TRY(c, launch_mfcc_refine(c->stream, p, c->ft, src, d_out, rl, refine_clips));
         return KWS_OK;
     }
     ProfScope ps(c, KWS_K_MFCC);
-    HIP_TRY(c, launch_mfcc(c->stream, p, c->ft, src, B, d_out, RefineList{}));
+    HIP_TRY(c, launch_mfcc(c->stream, p, c->ft, src, B, d_out, RefineList{}, ref_route));
     return KWS_OK;
 }
 template int run_frontend(kws_ctx*, const FrontendParams&, const int16_t*, int, float*, int);
@@ -127,6 +128,9 @@ int kws_set_frontend(kws_ctx* c, int sample_rate, int n_samples, int frame_len, 
     // a hop so long that the tile kernels' staged span (23 hops + one frame) does not fit the LDS: the float64 kernel, which
     // reads its frames from global memory, serves the geometry (kws_frontend_math reports it; kws_stream_open refuses)
     c->fe_fast_ok = im.fast && mfcc_tile_lds_bytes(p) <= MFCC_TILE_LDS_MAX;
+    // the reference configuration has a wavefront-resident kernel with its constants compiled in (kws_set_frontend_route)
+    // (whether a call's clips suit a wavefront-resident kernel at all -- their length, the pointer -- is asked per launch, as before)
+    c->fe_ref_geometry = c->fe_fast_ok && mfcc_reference_geometry(p);
     c->fe_ready = true;
     return KWS_OK;
     KWS_GUARD_END(c, "kws_set_frontend")
@@ -136,6 +140,14 @@ int kws_set_frontend_math(kws_ctx* c, int math) {
     if (!c) return KWS_EINVAL;
     if (math != KWS_FE_F32 && math != KWS_FE_F64) return fail(c, KWS_EINVAL, "kws_set_frontend_math: math must be KWS_FE_F32 or KWS_FE_F64");
     c->fe_math = math;
+    return KWS_OK;
+}
+
+int kws_set_frontend_route(kws_ctx* c, int route) {
+    if (!c) return KWS_EINVAL;
+    if (route != KWS_FE_ROUTE_AUTO && route != KWS_FE_ROUTE_GENERIC)
+        return fail(c, KWS_EINVAL, "kws_set_frontend_route: route must be KWS_FE_ROUTE_AUTO or KWS_FE_ROUTE_GENERIC");
+    c->fe_route = route;
     return KWS_OK;
 }
 

@@ -91,13 +91,14 @@ inline hipError_t raise_lds_limit(K kernel, size_t lds) {
 struct AugmentArgs;
 // The float32 MFCC of B clips read from int16 PCM, float32 samples, or the augmented view of a resident split (gather +
 // augment + MFCC in one launch, wavefront-resident geometry only).  Frames over p.refine_span are appended to rl; an empty rl
-// (ctr == nullptr) means no flagging.
+// (ctr == nullptr) means no flagging.  ref_route: int16 PCM at the reference geometry takes the kernel compiled for it
+// (kws_mfcc_i16_ref_kernel: the same bits); the other sources have one route and ignore it.
 hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_wav, int B, float* d_out,
-                       const RefineList& rl);
+                       const RefineList& rl, bool ref_route);
 hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, int B, float* d_out,
-                       const RefineList& rl);
+                       const RefineList& rl, bool ref_route);
 hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const AugmentArgs& a, int B, float* d_out,
-                       const RefineList& rl);
+                       const RefineList& rl, bool ref_route);
 // Float64 recomputation of the listed frames, in place in d_out (same source / d_out as the float32 launch before it).
 hipError_t launch_mfcc_refine(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_wav, float* d_out,
                               const RefineList& rl, int B);
@@ -150,6 +151,8 @@ struct DrawArgs {
 hipError_t launch_augment_draw(hipStream_t s, const DrawArgs& d, int B);
 // true: launch_mfcc picks the wavefront-resident kernel for int16 PCM at this geometry (the fused kernel is a variant of it)
 bool mfcc_wave_resident_ok(const FrontendParams& p);
+// true: frame length, hop, filters, cepstra and energy row are the reference's, the constants kws_mfcc_i16_ref_kernel is built for
+bool mfcc_reference_geometry(const FrontendParams& p);
 // dynamic LDS a tile kernel asks for at this geometry (23 hops + one frame of float32 samples): beyond MFCC_TILE_LDS_MAX the
 // float32 kernels cannot be launched and kws_set_frontend routes the geometry to the float64 kernel
 size_t mfcc_tile_lds_bytes(const FrontendParams& p);

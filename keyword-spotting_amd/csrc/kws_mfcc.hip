@@ -276,20 +276,27 @@ __host__ __device__ inline size_t mfcc_wr_lds_bytes(const FrontendParams& p) {
 // chunks, LDS map and mfcc_pair; only the way a chunk's samples reach the registers differs -- see aug_vec8 above.  Every AUG
 // branch is an if constexpr: the plain instantiation keeps the instruction sequence kws_mfcc_i16_kernel had as a kernel of
 // its own (register names apart).
-template <bool AUG>
+// G (kws_mfcc_dev.h): GeomAny reads the geometry from p, as every wavefront-resident kernel did before the type existed; GeomRef
+// is the reference configuration at compile time (kws_mfcc_i16_ref_kernel): the row pointer and the frames' LDS addresses
+// advance by constants, the frame bound is a lane mask, and the worklist code exists only in the instantiation that flags.
+template <bool AUG, class G = GeomAny>
 __device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t, const int16_t* __restrict__ wav,
                                              float* __restrict__ out, RefineList rl, int B, int chunks_per_wave,
                                              AugmentArgs aug) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int nfp = (p.nfilt + 3) & ~3;
+    static_assert(!(AUG && G::REF), "the fused loader keeps the generic geometry");
+    const int nfp = (G::nfilt(p) + 3) & ~3;
+    const int numcep = G::numcep(p), frame_step = G::frame_step(p);
     float* dctb = reinterpret_cast<float*>(smem);
-    cf* tw2 = reinterpret_cast<cf*>(dctb + ((p.numcep * nfp + 3) & ~3));
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    cf* tw2 = reinterpret_cast<cf*>(dctb + ((numcep * nfp + 3) & ~3));
+    // (GeomRef: the wavefront's number as a scalar -- the compiler cannot see that threadIdx.x >> 6 is wave-uniform; with a vector
+    // number the chunk and pair loops are exec-masked vector loops whose counters, pointers and LDS bases take vector registers)
+    const int tid = threadIdx.x, lane = tid & 63, wv = G::REF ? uniform_i(tid >> 6) : tid >> 6;
     unsigned char* mine = reinterpret_cast<unsigned char*>(tw2 + 64) + wv * WR_WAVE_BYTES;
     float* ybuf = reinterpret_cast<float*>(mine);
     unsigned char* scr = mine + WR_SPAN * 4;
 
-    for (int i = tid; i < (p.numcep * nfp + 3) / 4; i += MFCC_THREADS)
+    for (int i = tid; i < (numcep * nfp + 3) / 4; i += MFCC_THREADS)
         reinterpret_cast<float4*>(dctb)[i] = reinterpret_cast<const float4*>(t.dct_pad)[i];
     fill_tw2(t.twiddle, tw2, tid);
     cf t1[8];
@@ -309,12 +316,12 @@ __device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t,
     const int16_t* __restrict__ x = AUG ? nullptr : wav + (size_t)(active ? clip : 0) * p.n_samples;
     AugClip ac{};
     if constexpr (AUG) ac = aug_clip(aug, active ? clip : 0, p.n_samples);  // wave-uniform: scalar registers
-    const int chunk_step = WR_FRAMES * p.frame_step;  // samples from one chunk's span to the next (a multiple of 8: checked by the launcher)
+    const int chunk_step = WR_FRAMES * frame_step;  // samples from one chunk's span to the next (a multiple of 8: checked by the launcher)
 
     // two 16-byte vectors of PCM per lane cover the span; a vector is inside the clip or past its end (n_samples % 8 == 0)
     uint4 v0 = make_uint4(0, 0, 0, 0), v1 = v0;
     int16_t before = 0;
-    auto fetch = [&](int cc) {
+    auto fetch = [&](int cc, int lane) {
         const int s0 = cc * chunk_step;
         const int n0 = s0 + 8 * lane, n1 = n0 + 512;
         v0 = n0 + 8 <= p.n_samples ? *reinterpret_cast<const uint4*>(x + n0) : make_uint4(0, 0, 0, 0);
@@ -334,8 +341,10 @@ __device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t,
     // flagged pair queued up at the counter's L2 line when flags are dense (speech-like clips, 5 % of the frames: 0.194 -> 0.262 ms).
     uint32_t fmask = 0u;
     int pair0 = 2 * c;  // pair index (within the clip) of mask position 0
+    // GeomRef: the row of the run's first frame, advanced by two rows per pair (wave-uniform: scalar registers)
+    float* orow = G::REF ? out + ((size_t)clip * p.num_frames + WR_FRAMES * c) * REF_NUMCEP : nullptr;
 #define KWS_FLUSH_FLAGS()                                                                                                          \
-    if (fmask && rl.ctr) {                                                                                                          \
+    if (fmask && (G::REF || rl.ctr)) {                                                                                              \
         const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); /* (recomputed: the loop's copy would have to be kept in scratch) */ \
         const uint32_t fk = lane < 16 ? (fmask >> (2 * lane)) & 3u : 0u;                                                            \
         const uint32_t has = (uint32_t)__ballot(fk != 0u);                                                                          \
@@ -348,7 +357,7 @@ __device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t,
             rl.list[at] = (int)((((unsigned)(rl.clip0 + clip) * (unsigned)((p.num_frames + 1) / 2) + (unsigned)(pair0 + lane)) << 2) | fk); \
     }
     for (; c < c_end; ++c) {
-        if constexpr (!AUG) fetch(c);
+        if constexpr (!AUG) fetch(c, lane);
         // ---- registers -> float32, pre-emphasised, into this wavefront's span buffer -----------------------
         if constexpr (AUG) {
             const int s0 = c * chunk_step;
@@ -396,10 +405,18 @@ __device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t,
                     y[i] = __fsub_rn(cur, __fmul_rn(pre, prev));
                     prev = cur;
                 }
-                if (n == 0) y[0] = to_unit((int16_t)(wd[0] & 0xffffu));  // the clip's first sample is not pre-emphasised
-                if (n + 8 > p.n_samples) {                                 // past the clip: psf pads the PRE-EMPHASISED signal with zeros
+#ifdef KWS_X_MFCC_NO_BOOKKEEPING  // timing build, wrong results (see mfcc_pair)
+                if constexpr (!G::REF)
+#endif
+                {
+                    if (n == 0) y[0] = to_unit((int16_t)(wd[0] & 0xffffu));  // the clip's first sample is not pre-emphasised
+                    if constexpr (G::REF) {
+                        // past the clip the vector itself is zeros (fetch), so samples 1..7 are 0 - 0.97 * 0 = +0 already: one select, not eight
+                        if (n + 8 > p.n_samples) y[0] = 0.f;
+                    } else if (n + 8 > p.n_samples) {  // past the clip: psf pads the PRE-EMPHASISED signal with zeros
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) y[i] = 0.f;
+                        for (int i = 0; i < 8; ++i) y[i] = 0.f;
+                    }
                 }
                 reinterpret_cast<float4*>(dst)[0] = make_float4(y[0], y[1], y[2], y[3]);
                 reinterpret_cast<float4*>(dst)[1] = make_float4(y[4], y[5], y[6], y[7]);
@@ -408,54 +425,115 @@ __device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t,
             convert(v1, prev1, s0 + 512 + 8 * lane, ybuf + 512 + 8 * lane);
         }
         wave_lds_order();
+        if constexpr (G::REF) {
+            const float* ya = ybuf;  // frame a of the pair; frame b lies REF_FRAME_STEP floats on: an immediate offset of its loads
 #pragma unroll 1
-        for (int pr = 0; pr < WR_PAIRS; ++pr) {
-            const int fa = WR_FRAMES * c + 2 * pr;
-            if (fa >= p.num_frames) break;  // wave-uniform
-            const bool has_b = fa + 1 < p.num_frames;
-            const float* ya = ybuf + (2 * pr) * p.frame_step;
-            const float* yb = ya + p.frame_step;
-            cf v[8];
-            uint32_t ora = 0u, orb = 0u;
+            for (int pr = 0; pr < WR_PAIRS; ++pr, ya += 2 * REF_FRAME_STEP, orow += 2 * REF_NUMCEP) {
+                const int fa = WR_FRAMES * c + 2 * pr;
+                if (fa >= p.num_frames) break;  // wave-uniform
+                const bool has_b = fa + 1 < p.num_frames;
+                [[maybe_unused]] const float* yb = ya + REF_FRAME_STEP;
+                cf v[8];
+#ifdef KWS_X_MFCC_NO_BOOKKEEPING
 #pragma unroll
-            for (int n1 = 0; n1 < 7; ++n1) {  // frame_len in (384, 448]: block 6 is cut by a lane bound, block 7 is zero
-                const int i = 64 * n1 + lane;
-                float a = ya[i], b = yb[i];
-                if (n1 == 6) {
-                    const bool in = i < p.frame_len;
-                    a = in ? a : 0.f, b = in ? b : 0.f;
+                for (int n1 = 0; n1 < 7; ++n1) v[n1] = cf{ya[64 * n1 + lane], yb[64 * n1 + lane]};
+                v[7] = cf{0.f, 0.f};
+                const bool nza = true, nzb = true;
+#else
+                // sample i of frame a and of frame b, one hop on, as ONE ds_read2_b32: the complex value (a, b) arrives in its
+                // register pair (the compiler pairs the loads along a frame instead and regroups with a move per value); the
+                // offsets are in floats and end at 255, hence a base per two blocks
+                static_assert(REF_FRAME_STEP == 160 && REF_FRAME_LEN > 384 && REF_FRAME_LEN <= 448, "the offsets below");
+                {
+                    const uint32_t a0 = lds_addr(ya + lane);
+                    asm volatile(
+                        "ds_read2_b32 %0, %7 offset1:160\n\t"
+                        "ds_read2_b32 %1, %7 offset0:64 offset1:224\n\t"
+                        "ds_read2_b32 %2, %8 offset1:160\n\t"
+                        "ds_read2_b32 %3, %8 offset0:64 offset1:224\n\t"
+                        "ds_read2_b32 %4, %9 offset1:160\n\t"
+                        "ds_read2_b32 %5, %9 offset0:64 offset1:224\n\t"
+                        "ds_read2_b32 %6, %10 offset1:160\n\t"
+                        "s_waitcnt lgkmcnt(0)"
+                        : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6])
+                        : "v"(a0), "v"(a0 + 512u), "v"(a0 + 1024u), "v"(a0 + 1536u)
+                        : "memory");
                 }
-                v[n1] = cf{a, b};
-                ora |= __builtin_bit_cast(uint32_t, a);
-                orb |= __builtin_bit_cast(uint32_t, b);
-            }
-            v[7] = cf{0.f, 0.f};
-            if (!has_b) {  // the clip's last pair only: frame b is past the clip
+                const bool in6 = lane < REF_FRAME_LEN - 384;  // block 6 holds the frame's last 16 samples, block 7 none
+                v[6] = cf{in6 ? v[6].x : 0.f, in6 ? v[6].y : 0.f};
+                v[7] = cf{0.f, 0.f};
+                if (!has_b) {  // the clip's last pair only: frame b is past the clip (wave-uniform: a real branch)
+                    asm volatile("" ::: "memory");
 #pragma unroll
-                for (int n1 = 0; n1 < 7; ++n1) v[n1].y = 0.f;
-                orb = 0u;
+                    for (int n1 = 0; n1 < 7; ++n1) v[n1].y = 0.f;
+                }
+                const bool nza = true, nzb = true;  // mfcc_pair<GeomRef> reads them off the frame energies
+#endif
+                const uint32_t flags = mfcc_pair<G>(v, nza, nzb, has_b, p, sc, t1, ml, lane, orow, orow + REF_NUMCEP, nullptr, t.mel_seg);
+                if constexpr (G::FLAGS) fmask |= flags << (2 * ((fa >> 1) - pair0));  // wave-uniform
+                wave_lds_order();
             }
-            const bool nza = __any((ora << 1) != 0u);
-            const bool nzb = __any((orb << 1) != 0u);
-            const uint32_t flags = mfcc_pair(v, nza, nzb, has_b, p, sc, t1, ml, lane,
-                                             out + ((size_t)clip * p.num_frames + fa) * p.numcep,
-                                             out + ((size_t)clip * p.num_frames + fa + 1) * p.numcep);
-            fmask |= flags << (2 * ((fa >> 1) - pair0));  // wave-uniform
-            wave_lds_order();
+        } else {
+#pragma unroll 1
+            for (int pr = 0; pr < WR_PAIRS; ++pr) {
+                const int fa = WR_FRAMES * c + 2 * pr;
+                if (fa >= p.num_frames) break;  // wave-uniform
+                const bool has_b = fa + 1 < p.num_frames;
+                const float* ya = ybuf + (2 * pr) * p.frame_step;
+                const float* yb = ya + p.frame_step;
+                cf v[8];
+                uint32_t ora = 0u, orb = 0u;
+#pragma unroll
+                for (int n1 = 0; n1 < 7; ++n1) {  // frame_len in (384, 448]: block 6 is cut by a lane bound, block 7 is zero
+                    const int i = 64 * n1 + lane;
+                    float a = ya[i], b = yb[i];
+                    if (n1 == 6) {
+                        const bool in = i < p.frame_len;
+                        a = in ? a : 0.f, b = in ? b : 0.f;
+                    }
+                    v[n1] = cf{a, b};
+                    ora |= __builtin_bit_cast(uint32_t, a);
+                    orb |= __builtin_bit_cast(uint32_t, b);
+                }
+                v[7] = cf{0.f, 0.f};
+                if (!has_b) {  // the clip's last pair only: frame b is past the clip
+#pragma unroll
+                    for (int n1 = 0; n1 < 7; ++n1) v[n1].y = 0.f;
+                    orb = 0u;
+                }
+                const bool nza = __any((ora << 1) != 0u);
+                const bool nzb = __any((orb << 1) != 0u);
+                const uint32_t flags = mfcc_pair(v, nza, nzb, has_b, p, sc, t1, ml, lane,
+                                                 out + ((size_t)clip * p.num_frames + fa) * p.numcep,
+                                                 out + ((size_t)clip * p.num_frames + fa + 1) * p.numcep);
+                fmask |= flags << (2 * ((fa >> 1) - pair0));  // wave-uniform
+                wave_lds_order();
+            }
         }
-        if (2 * (c + 1) - pair0 >= 16) {  // the mask is full (more than 8 chunks per wavefront: tuning runs only)
-            KWS_FLUSH_FLAGS()
-            fmask = 0u;
-            pair0 = 2 * (c + 1);
-        }
+        if constexpr (G::FLAGS)
+            if (2 * (c + 1) - pair0 >= 16) {  // the mask is full (more than 8 chunks per wavefront: tuning runs only)
+                KWS_FLUSH_FLAGS()
+                fmask = 0u;
+                pair0 = 2 * (c + 1);
+            }
     }
-    KWS_FLUSH_FLAGS()
+    if constexpr (G::FLAGS) KWS_FLUSH_FLAGS()
 #undef KWS_FLUSH_FLAGS
 }
 
 __global__ __launch_bounds__(MFCC_THREADS) __attribute__((amdgpu_waves_per_eu(KWS_MFCC_EU, KWS_MFCC_EU))) void kws_mfcc_i16_kernel(
     FrontendParams p, FrontendTables t, const int16_t* __restrict__ wav, float* __restrict__ out, RefineList rl, int B, int chunks_per_wave) {
     mfcc_wr_body<false>(p, t, wav, out, rl, B, chunks_per_wave, AugmentArgs{});
+}
+// The same kernel at the reference geometry (GeomRef), which every shipped configuration uses: with the precision flag and the
+// worklist, and without both for a context whose refinement is off.  Kernels of their own: both bodies in one kernel spill.
+__global__ __launch_bounds__(MFCC_THREADS) __attribute__((amdgpu_waves_per_eu(KWS_MFCC_EU, KWS_MFCC_EU))) void kws_mfcc_i16_ref_kernel(
+    FrontendParams p, FrontendTables t, const int16_t* __restrict__ wav, float* __restrict__ out, RefineList rl, int B, int chunks_per_wave) {
+    mfcc_wr_body<false, GeomRef<true>>(p, t, wav, out, rl, B, chunks_per_wave, AugmentArgs{});
+}
+__global__ __launch_bounds__(MFCC_THREADS) __attribute__((amdgpu_waves_per_eu(KWS_MFCC_EU, KWS_MFCC_EU))) void kws_mfcc_i16_ref_noflag_kernel(
+    FrontendParams p, FrontendTables t, const int16_t* __restrict__ wav, float* __restrict__ out, RefineList rl, int B, int chunks_per_wave) {
+    mfcc_wr_body<false, GeomRef<false>>(p, t, wav, out, rl, B, chunks_per_wave, AugmentArgs{});
 }
 #ifndef KWS_MFCC_AUG_EU
 #define KWS_MFCC_AUG_EU 4
@@ -569,6 +647,12 @@ bool mfcc_wave_resident_ok(const FrontendParams& p) {
     return mfcc_tail6(p) && p.vec_ok && (WR_FRAMES * p.frame_step) % 8 == 0 && (WR_FRAMES - 1) * p.frame_step + 448 <= WR_SPAN;
 }
 
+// the geometry kws_mfcc_i16_ref_kernel is compiled for (GeomRef, kws_mfcc_dev.h); kws_set_frontend asks once per configuration
+bool mfcc_reference_geometry(const FrontendParams& p) {
+    return p.frame_len == REF_FRAME_LEN && p.frame_step == REF_FRAME_STEP && p.nfilt == REF_NFILT && p.numcep == REF_NUMCEP &&
+           p.append_energy != 0;
+}
+
 // Chunks per wavefront of the wavefront-resident kernels for a launch of nb clips.
 // ~5 chunks (20 frames) per wavefront, split evenly (99 frames = 25 chunks = 5 x 5): measured on 4096 clips, 1 / 5 / 25
 // chunks per wavefront take 0.219 / 0.183 / 0.201 ms -- short-lived wavefronts keep the CUs' phases mixed and the tail
@@ -618,18 +702,23 @@ static hipError_t launch_mfcc_wr(K kernel, hipStream_t s, const FrontendParams& 
 }
 
 hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_wav, int B, float* d_out,
-                       const RefineList& rl) {
+                       const RefineList& rl, bool ref_route) {
 #ifndef KWS_X_MFCC_TILE_KERNEL  // (A/B switch: the round-2 tile kernel for every geometry)
-    if (mfcc_wave_resident_ok(p)) return launch_mfcc_wr(kws_mfcc_i16_kernel, s, p, t, d_wav, B, d_out, rl);
+    if (mfcc_wave_resident_ok(p)) {
+        if (ref_route && mfcc_reference_geometry(p))  // (the caller's p may be a copy with another clip length: asked again, five compares)
+            return launch_mfcc_wr(rl.ctr && p.refine_span > 0.f ? kws_mfcc_i16_ref_kernel : kws_mfcc_i16_ref_noflag_kernel, s, p, t,
+                                  d_wav, B, d_out, rl);
+        return launch_mfcc_wr(kws_mfcc_i16_kernel, s, p, t, d_wav, B, d_out, rl);
+    }
 #endif
     return launch_mfcc_t(mfcc_tail6(p) ? kws_mfcc_i16_tile_kernel : kws_mfcc_i16_any_kernel, s, p, t, d_wav, B, d_out, rl);
 }
 hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, int B, float* d_out,
-                       const RefineList& rl) {
+                       const RefineList& rl, bool) {
     return launch_mfcc_t(mfcc_tail6(p) ? kws_mfcc_f32_kernel : kws_mfcc_f32_any_kernel, s, p, t, d_wav, B, d_out, rl);
 }
 hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const AugmentArgs& a, int B, float* d_out,
-                       const RefineList& rl) {
+                       const RefineList& rl, bool) {
     if (!mfcc_wave_resident_ok(p)) return hipErrorInvalidValue;  // refused by kws_mfcc_augment_i16 before it gets here
     return launch_mfcc_wr(kws_mfcc_augment_i16_kernel, s, p, t, a, B, d_out, rl);
 }

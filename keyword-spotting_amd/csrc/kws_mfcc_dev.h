@@ -241,12 +241,16 @@ __device__ __forceinline__ void wave_sum2(float& a, float& b) {
 struct PairLevel {
     float pow_a, pow_b;
 };
-__device__ __forceinline__ PairLevel equalise_levels(cf (&v)[8]) {
+// e_out: where the two frame energies (sums of squares, wave-uniform) go, or nullptr.  NV: blocks of v that hold samples -- the
+// rest are zeros whose squares leave the sums as they are (7 at the reference's frame length).
+template <int NV = 8>
+__device__ __forceinline__ PairLevel equalise_levels(cf (&v)[8], float* e_out = nullptr) {
     cf e2 = {0.f, 0.f};
 #pragma unroll
-    for (int i = 0; i < 8; ++i) asm("v_pk_fma_f32 %0, %1, %1, %0" : "+v"(e2) : "v"(v[i]));
+    for (int i = 0; i < NV; ++i) asm("v_pk_fma_f32 %0, %1, %1, %0" : "+v"(e2) : "v"(v[i]));
     float ea = e2.x, eb = e2.y;
     wave_sum2(ea, eb);  // wave-uniform
+    if (e_out) e_out[0] = ea, e_out[1] = eb;
     auto shift_of = [](float e) -> int {
         const int ex = (int)((__builtin_bit_cast(uint32_t, e) >> 23) & 0xffu);  // biased exponent of the energy
         if (ex == 0 || ex == 255) return 0;                                        // zero / denormal / non-finite: leave as is
@@ -259,7 +263,7 @@ __device__ __forceinline__ PairLevel equalise_levels(cf (&v)[8]) {
     if (sa == sb) return {1.0f, 1.0f};
     const cf down = {__builtin_bit_cast(float, (uint32_t)(127 - sa) << 23), __builtin_bit_cast(float, (uint32_t)(127 - sb) << 23)};
 #pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = v[i] * down;
+    for (int i = 0; i < NV; ++i) v[i] = v[i] * down;
     return {__builtin_bit_cast(float, (uint32_t)(127 + 2 * sa) << 23), __builtin_bit_cast(float, (uint32_t)(127 + 2 * sb) << 23)};
 }
 
@@ -361,6 +365,65 @@ __device__ __forceinline__ void split_power(const cf (&v)[8], cf* zbuf, float2* 
     wave_lds_order();
 }
 
+// split_power for the reference instantiation: powers only, no bin-256 slot, and the pair (|A|^2, |B|^2) of a bin formed as ONE
+// packed value from the start.  With s = z + w = (2 Re A, 2 Re B') and d = z - w = (2 Im B', 2 Im A) -- the two packed additions
+// of the spectrum split -- the powers are s * s + swap(d * d): the same roundings as fmaf(ar, ar, ai * ai) and
+// fmaf(br, br, bi * bi) above, in registers that already are the float2 the power buffer stores (the compiler's own packing
+// of the scalar form pairs values of different bins and pays a dozen moves per pair to regroup them).  An all-zero frame is
+// forced to exactly 0 through its scale factor (a power is finite and >= 0, so power * 0 = +0: the value the select gave)
+// -- no branch, no selects.
+template <bool PEAK>
+__device__ __forceinline__ void split_power_packed(const cf (&v)[8], cf* zbuf, float2* pbuf, int lane, bool nza, bool nzb,
+                                                   const int (&pslot)[4], const PairLevel& lv, float& ea, float& eb,
+                                                   float& pk_a, float& pk_b) {
+    const int k1 = lane >> 3, q = lane & 7;
+#pragma unroll
+    for (int d = 0; d < 8; ++d) zbuf[zswz(k1 + 8 * q + 64 * d)] = v[d];
+    wave_lds_order();
+    cf z[4], w[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int k = lane + 64 * j;
+        z[j] = zbuf[zswz(k)];
+        w[j] = zbuf[zswz((NFFT - k) & (NFFT - 1))];
+    }
+    wave_lds_order();
+    constexpr float scale = 1.0f / (4.0f * NFFT);
+    const cf sc = {nza ? scale * lv.pow_a : 0.f, nzb ? scale * lv.pow_b : 0.f};  // products of powers of two: exact; wave-uniform
+    cf pw[4], e = {0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const cf s = z[j] + w[j], d = z[j] - w[j];
+        const cf t = d * d;
+        cf r;
+        asm("v_pk_fma_f32 %0, %1, %1, %2 op_sel:[0,0,1] op_sel_hi:[1,1,0]" : "=v"(r) : "v"(s), "v"(t));  // (s.x^2 + t.y, s.y^2 + t.x)
+        pw[j] = r * sc;
+    }
+    if constexpr (PEAK) {
+        asm("v_max3_f32 %0, %1, %2, %3" : "=v"(pk_a) : "v"(pw[0].x), "v"(pw[1].x), "v"(pw[2].x));
+        asm("v_max3_f32 %0, %1, %2, %3" : "=v"(pk_b) : "v"(pw[0].y), "v"(pw[1].y), "v"(pw[2].y));
+        asm("v_max_f32 %0, %0, %1" : "+v"(pk_a) : "v"(pw[3].x));
+        asm("v_max_f32 %0, %0, %1" : "+v"(pk_b) : "v"(pw[3].y));
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        pbuf[pslot[j]] = make_float2(pw[j].x, pw[j].y);
+        e = e + pw[j];
+    }
+    if (lane == 0) {  // bin 256 = Z[256]: lane 0, register 4; its own mirror image
+        const cf t = v[4] * 2.f;
+        const cf p = (t * t) * sc;
+        e = e + p;
+        if constexpr (PEAK) {
+            asm("v_max_f32 %0, %0, %1" : "+v"(pk_a) : "v"(p.x));
+            asm("v_max_f32 %0, %0, %1" : "+v"(pk_b) : "v"(p.y));
+        }
+    }
+    ea = e.x;
+    eb = e.y;
+    wave_lds_order();
+}
+
 constexpr float PSF_EPS = 2.220446049250313e-16f;  // numpy.finfo(float).eps, exactly 2^-52
 
 // Sample -> float32 in [-1, 1): int16 PCM is scaled like librosa/soundfile do (x / 32768, exact);
@@ -417,7 +480,11 @@ __device__ __forceinline__ void zero_scratch(unsigned char* scr, int lane) {
 // Segments of up to 8 chunks; the host keeps every segment inside one 16-lane DPP row, so the shifts by 1, 2 and 4
 // lanes are row_shl operands of the multiply-add itself: three instructions per sum (shifting across the whole
 // wavefront takes 1 + 2 + 4 wave_shl:1 moves on top).
-__device__ __forceinline__ void segment_suffix_sums(float& a, float& b, float& c, float& d, const MelLane& m) {
+// M4_FROM_TABLE (the reference instantiation): the row_shl:4 step, which no 16 kHz bank of more than 19 filters takes, reads its
+// mask from the table (seg_tab = FrontendTables::mel_seg) again instead of holding a register for it across the kernel's loops.
+template <bool M4_FROM_TABLE = false>
+__device__ __forceinline__ void segment_suffix_sums(float& a, float& b, float& c, float& d, const MelLane& m,
+                                                    const int* seg_tab = nullptr, int lane = 0) {
     // four independent chains interleaved: three other instructions sit between a write and its DPP read (the VALU ->
     // DPP hazard needs two wait states; inline asm hides it from the compiler, hence the leading s_nop)
     asm("s_nop 1\n\t"
@@ -431,14 +498,16 @@ __device__ __forceinline__ void segment_suffix_sums(float& a, float& b, float& c
         "v_fmac_f32_dpp %3, %3, %5 row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:1"
         : "+v"(a), "+v"(b), "+v"(c), "+v"(d)
         : "v"(m.m1), "v"(m.m2));
-    if (m.deep)
+    if (m.deep) {
+        const float m4 = M4_FROM_TABLE ? ((seg_tab[lane] & 4) ? 1.f : 0.f) : m.m4;
         asm("s_nop 1\n\t"
             "v_fmac_f32_dpp %0, %0, %4 row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
             "v_fmac_f32_dpp %1, %1, %4 row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
             "v_fmac_f32_dpp %2, %2, %4 row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
             "v_fmac_f32_dpp %3, %3, %4 row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:1"
             : "+v"(a), "+v"(b), "+v"(c), "+v"(d)
-            : "v"(m.m4));
+            : "v"(m4));
+    }
 }
 
 // Two sums and two maxima (of non-negative values) over the wavefront at once: four chains alternate, so a register is read by
@@ -518,33 +587,75 @@ __device__ __forceinline__ void peak_over2(float va, float vb, float lim_a, floa
     over_b = (__ballot(b < lim_b) >> 63) & 1ull;
 }
 
+// The geometry of a front end as mfcc_pair and the wavefront-resident body (kws_mfcc.hip) read it.  GeomAny takes every
+// value from FrontendParams at run time: the instruction sequence every caller had before the type existed.  GeomRef is the
+// reference configuration (400 / 160, 26 filters in rows of 28, 10 cepstra, appended energy, both frames through one
+// logarithm) as compile-time constants, with the precision flag on or off as a template argument: products by numcep and
+// frame_step, the DCT's trip count and the refinement tests fold away, and the divergent regions of the DCT tail become
+// selects and one masked store.  The same arithmetic in the same order either way: every output bit and flag agrees.
+struct GeomAny {
+    static constexpr bool REF = false;
+    static constexpr bool FLAGS = true;  // the worklist code is present (and asks rl.ctr at run time)
+    static __device__ __forceinline__ int frame_len(const FrontendParams& p) { return p.frame_len; }
+    static __device__ __forceinline__ int frame_step(const FrontendParams& p) { return p.frame_step; }
+    static __device__ __forceinline__ int nfilt(const FrontendParams& p) { return p.nfilt; }
+    static __device__ __forceinline__ int numcep(const FrontendParams& p) { return p.numcep; }
+    static __device__ __forceinline__ bool append_energy(const FrontendParams& p) { return p.append_energy != 0; }
+    static __device__ __forceinline__ bool refine(const FrontendParams& p) { return p.refine_span > 0.f; }
+};
+constexpr int REF_FRAME_LEN = 400, REF_FRAME_STEP = 160, REF_NFILT = 26, REF_NUMCEP = 10;
+template <bool REFINE>
+struct GeomRef {
+    static constexpr bool REF = true;
+    static constexpr bool FLAGS = REFINE;
+    static __device__ __forceinline__ constexpr int frame_len(const FrontendParams&) { return REF_FRAME_LEN; }
+    static __device__ __forceinline__ constexpr int frame_step(const FrontendParams&) { return REF_FRAME_STEP; }
+    static __device__ __forceinline__ constexpr int nfilt(const FrontendParams&) { return REF_NFILT; }
+    static __device__ __forceinline__ constexpr int numcep(const FrontendParams&) { return REF_NUMCEP; }
+    static __device__ __forceinline__ constexpr bool append_energy(const FrontendParams&) { return true; }
+    static __device__ __forceinline__ constexpr bool refine(const FrontendParams&) { return REFINE; }
+};
+
 // One packed frame pair, from the (pre-emphasised, zero-padded) samples in v to the cepstra in global memory:
 // FFT -> split -> power -> sparse mel -> log -> DCT x lifter, c0 = log(frame energy).
 // out_a / out_b: rows of numcep floats for frame a / b (out_b is not touched when has_b is false).
+// seg_tab: GeomRef only, FrontendTables::mel_seg (see segment_suffix_sums).
 // Returns the precision flags of the pair (wave-uniform): bit 0 = frame a, bit 1 = frame b has a mel band more than p.refine_span
 // (natural-log units of power) below its largest spectral bin.
+template <class G = GeomAny>
 __device__ __forceinline__ uint32_t mfcc_pair(cf (&v)[8], bool nza, bool nzb, bool has_b, const FrontendParams& p,
                                           const PairScratch& sc, const cf (&t1)[8], const MelLane& ml, int lane,
                                           float* __restrict__ out_a, float* __restrict__ out_b,
-                                          float* lds_out_a = nullptr) {
+                                          float* lds_out_a = nullptr, const int* seg_tab = nullptr) {
     cf* xbuf = sc.xbuf;
     float2* pbuf = sc.pbuf;
     float* lbuf = sc.lbuf;
     const float* dctb = sc.dctb;
     const cf* tw2 = sc.tw2;
     const uint32_t gth = ml.gth;
-    const int nfp = sc.nfp;
-    const PairLevel lv = equalise_levels(v);
+    const int nfp = G::REF ? ((REF_NFILT + 3) & ~3) : sc.nfp;
+    const int nfilt = G::nfilt(p);
+    [[maybe_unused]] const int numcep = G::numcep(p);  // (the KWS_X_MFCC_STOP timing builds)
+    // GeomRef: whether a frame has a non-zero sample is read off its energy, which the level equalisation sums anyway, instead
+    // of an OR over the samples' bit patterns (the caller passes nza = nzb = true).  The same truth value: a pre-emphasised
+    // int16 sample is a multiple of 2^-40 below 2, so the square of a non-zero one is a normal float32 and the sum is not 0.
+    float e_pair[2];
+    const PairLevel lv = G::REF ? equalise_levels<(REF_FRAME_LEN + 63) / 64>(v, e_pair) : equalise_levels(v);
+    if constexpr (G::REF) nza = e_pair[0] != 0.f, nzb = e_pair[1] != 0.f;
 #if !defined(KWS_X_MFCC_STOP) || KWS_X_MFCC_STOP >= 1
     fft512(v, xbuf, t1, tw2, lane);
 #endif
 #if defined(KWS_X_MFCC_STOP) && KWS_X_MFCC_STOP <= 1   // counter attribution (tools/pmc_mfcc_variant.sh): stop after the transform; wrong results
-    if (lane < p.numcep) out_a[lane] = v[0].x + v[1].y + v[2].x + v[3].y + v[4].x + v[5].y + v[6].x + v[7].y + lv.pow_a;
+    if (lane < numcep) out_a[lane] = v[0].x + v[1].y + v[2].x + v[3].y + v[4].x + v[5].y + v[6].x + v[7].y + lv.pow_a;
     return 0u;
 #endif
 
     float ea, eb, pka = 0.f, pkb = 0.f;  // frame energies; largest bin power of each frame (the precision flag's reference)
-    if (p.refine_span > 0.f) {  // wave-uniform
+    if constexpr (G::REF) {
+        split_power_packed<G::FLAGS>(v, xbuf, pbuf, lane, nza, nzb, ml.pslot, lv, ea, eb, pka, pkb);
+        if constexpr (G::FLAGS) wave_sum2_max2(ea, eb, pka, pkb);
+        else wave_sum2(ea, eb);
+    } else if (G::refine(p)) {  // wave-uniform
         split_power(v, xbuf, pbuf, lane, 1, nza, nzb, ml.pslot, -1, lv, ea, eb, &pka, &pkb);
         wave_sum2_max2(ea, eb, pka, pkb);
     } else {
@@ -552,14 +663,31 @@ __device__ __forceinline__ uint32_t mfcc_pair(cf (&v)[8], bool nza, bool nzb, bo
         wave_sum2(ea, eb);
     }
 #if defined(KWS_X_MFCC_STOP) && KWS_X_MFCC_STOP == 2    // stop after the power spectrum
-    if (lane < p.numcep) out_a[lane] = ea + eb + pbuf[lane].x;
+    if (lane < numcep) out_a[lane] = ea + eb + pbuf[lane].x;
     return 0u;
 #endif
 
     // sparse mel: this lane's chunk of <= 8 bins is one contiguous 64-byte run of the power buffer (four
     // conflict-free ds_read_b128); slots past the chunk's length hold stale finite values and meet zero weights
     float ra = 0.f, fa_ = 0.f, rb = 0.f, fb_ = 0.f;
-    {
+    if constexpr (G::REF) {
+        // the same sums with the two frames of a bin in one packed multiply-add: weight (one half of a register pair, taken by
+        // both halves of the instruction) x (power of frame a, of frame b) + (ra, rb); per accumulator the same operands in
+        // the same order as below
+        const float4* pc = reinterpret_cast<const float4*>(pbuf + lane * MEL_STRIDE);
+        cf accr = {0.f, 0.f}, accf = {0.f, 0.f};
+#pragma unroll
+        for (int h = 0; h < MEL_CHUNK / 2; ++h) {
+            const float4 pw = pc[h];
+            const cf p0 = {pw.x, pw.y}, p1 = {pw.z, pw.w};
+            const cf rw2 = {ml.rw[2 * h], ml.rw[2 * h + 1]}, fw2 = {ml.fw[2 * h], ml.fw[2 * h + 1]};
+            asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]" : "+v"(accr) : "v"(rw2), "v"(p0));
+            asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]" : "+v"(accf) : "v"(fw2), "v"(p0));
+            asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0]" : "+v"(accr) : "v"(rw2), "v"(p1));
+            asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0]" : "+v"(accf) : "v"(fw2), "v"(p1));
+        }
+        ra = accr.x, rb = accr.y, fa_ = accf.x, fb_ = accf.y;
+    } else {
         const float4* pc = reinterpret_cast<const float4*>(pbuf + lane * MEL_STRIDE);
 #pragma unroll
         for (int h = 0; h < MEL_CHUNK / 2; ++h) {
@@ -577,7 +705,8 @@ __device__ __forceinline__ uint32_t mfcc_pair(cf (&v)[8], bool nza, bool nzb, bo
     // Filter j = rising sum over segment j + falling sum over segment j+1.  The chunks of a segment are adjacent
     // lanes: a suffix sum by doubling (DPP shifts, no LDS) leaves each segment's total in its first chunk, and lane
     // j fetches its two totals through the LDS crossbar (ds_bpermute: no memory, no bank conflicts).
-    segment_suffix_sums(ra, fa_, rb, fb_, ml);
+    if constexpr (G::REF) segment_suffix_sums<true>(ra, fa_, rb, fb_, ml, seg_tab, lane);
+    else segment_suffix_sums(ra, fa_, rb, fb_, ml);
     float ma, mb;
     uint32_t flags = 0u;
     {
@@ -586,26 +715,39 @@ __device__ __forceinline__ uint32_t mfcc_pair(cf (&v)[8], bool nza, bool nzb, bo
         const float grb = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(4 * r0, __builtin_bit_cast(int, rb)));
         const float gfa = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(4 * q0, __builtin_bit_cast(int, fa_)));
         const float gfb = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(4 * q0, __builtin_bit_cast(int, fb_)));
+#ifdef KWS_X_MFCC_NO_BOOKKEEPING  // timing build, wrong results: what the selects of the reference instantiation cost at most
+        const float sa = G::REF ? gra + gfa : (nr ? gra : 0.f) + (nq ? gfa : 0.f);
+        const float sb = G::REF ? grb + gfb : (nr ? grb : 0.f) + (nq ? gfb : 0.f);
+#else
         const float sa = (nr ? gra : 0.f) + (nq ? gfa : 0.f);
         const float sb = (nr ? grb : 0.f) + (nq ? gfb : 0.f);
-        if (p.nfilt <= 32) {
+#endif
+        if (nfilt <= 32) {
             // both frames through ONE log: frame b's filterbank energies move to lanes 32.. (v_permlane32_swap
             // exchanges the upper half of its first operand with the lower half of its second)
             const auto sw = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, sa), __builtin_bit_cast(unsigned, sb), false, false);
             const float s = __builtin_bit_cast(float, (unsigned)sw[0]);
+#ifdef KWS_X_MFCC_NO_BOOKKEEPING
+            const float l = logf(G::REF ? s : (s == 0.f ? PSF_EPS : s));
+#else
             const float l = logf(s == 0.f ? PSF_EPS : s);
+#endif
             // DCT rows k >= 1 are orthogonal to constants: removing the common mode L_0 removes the float32
             // table-rounding error a -36 log-floor would otherwise amplify.
             ma = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, l), 0));
             mb = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, l), 32));
 #if defined(KWS_X_MFCC_STOP) && KWS_X_MFCC_STOP == 3    // stop after mel + log
-            if (lane < p.numcep) out_a[lane] = l + ea + eb;
+            if (lane < numcep) out_a[lane] = l + ea + eb;
             return 0u;
 #endif
             const int f = lane >> 5, j = lane & 31;
-            const float cv = j < p.nfilt ? l - (f ? mb : ma) : 0.f;
+#ifdef KWS_X_MFCC_NO_BOOKKEEPING
+            const float cv = G::REF ? l - (f ? mb : ma) : (j < nfilt ? l - (f ? mb : ma) : 0.f);
+#else
+            const float cv = j < nfilt ? l - (f ? mb : ma) : 0.f;
+#endif
             lbuf[64 * f + j] = cv;
-            if (p.refine_span > 0.f) {  // wave-uniform
+            if (G::refine(p)) {  // wave-uniform
                 // log(peak) - log(mel_0) - threshold per frame, both frames through one hardware logarithm (v_log_f32: a threshold
                 // needs no more; an all-zero frame: log 0 = -inf, never flagged)
                 const float lim = 0.6931471806f * __builtin_amdgcn_logf(f ? pkb : pka) - (f ? mb : ma) - p.refine_span;  // (v_log_f32, bare: a peak power is no subnormal)
@@ -616,10 +758,10 @@ __device__ __forceinline__ uint32_t mfcc_pair(cf (&v)[8], bool nza, bool nzb, bo
             const float la = logf(sa == 0.f ? PSF_EPS : sa), lb = logf(sb == 0.f ? PSF_EPS : sb);
             ma = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, la)));
             mb = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lb)));
-            const float cva = lane < p.nfilt ? la - ma : 0.f, cvb = lane < p.nfilt ? lb - mb : 0.f;
+            const float cva = lane < nfilt ? la - ma : 0.f, cvb = lane < nfilt ? lb - mb : 0.f;
             lbuf[lane] = cva;
             lbuf[64 + lane] = cvb;
-            if (p.refine_span > 0.f) {
+            if (G::refine(p)) {
                 bool oa, ob;
                 peak_over2(cva, cvb, 0.6931471806f * __builtin_amdgcn_logf(pka) - ma - p.refine_span, 0.6931471806f * __builtin_amdgcn_logf(pkb) - mb - p.refine_span, oa, ob);
                 flags = (uint32_t)oa | ((uint32_t)ob << 1);
@@ -629,7 +771,42 @@ __device__ __forceinline__ uint32_t mfcc_pair(cf (&v)[8], bool nza, bool nzb, bo
     wave_lds_order();
 
     // DCT-II(ortho) x lifter: lane -> (frame f = lane>>5, coefficient i = lane&31)
-    {
+    if constexpr (G::REF) {
+        // One region for the row products, the energy row's logarithm by every lane and a select, one masked store (the generic
+        // tail nests the energy row and the store inside the products' region).  The additions of a row are those of the
+        // nfp == 28 branch below, in its order.
+        const int f = lane >> 5, i = lane & 31;
+        const int row = i < REF_NUMCEP ? i : REF_NUMCEP - 1;
+        const float4* L4 = reinterpret_cast<const float4*>(lbuf + 64 * f);
+        const float4* D4 = reinterpret_cast<const float4*>(dctb + row * nfp);
+        float acc = 0.f;
+        if (i < REF_NUMCEP)  // (all 64 lanes forming a row product was measured: the same time, 14 more vector registers)
+#pragma unroll
+        for (int j0 = 0; j0 < 7; j0 += 4) {
+            float4 d[4], l[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (j0 + j < 7) d[j] = D4[j0 + j], l[j] = L4[j0 + j];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (j0 + j < 7) {
+                    acc = fmaf(d[j].x, l[j].x, acc);
+                    acc = fmaf(d[j].y, l[j].y, acc);
+                    acc = fmaf(d[j].z, l[j].z, acc);
+                    acc = fmaf(d[j].w, l[j].w, acc);
+                }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        const float e = f ? eb : ea;
+#ifdef KWS_X_MFCC_NO_BOOKKEEPING
+        acc += logf(e);
+        if (i < REF_NUMCEP && (f == 0 || has_b)) out_a[REF_NUMCEP * f + i] = acc;  // (the store keeps its bounds)
+#else
+        const float le = logf(e == 0.f ? PSF_EPS : e);
+        acc = i == 0 ? le : acc;
+        if (i < REF_NUMCEP && (f == 0 || has_b)) out_a[(unsigned)(REF_NUMCEP * f + i)] = acc;  // out_b = out_a + numcep: consecutive rows
+#endif
+    } else {
         const int f = lane >> 5, i = lane & 31;
         if (i < p.numcep && (f == 0 || has_b)) {
             const float4* L4 = reinterpret_cast<const float4*>(lbuf + 64 * f);

@@ -24,6 +24,7 @@ KWS_K_MFCC, KWS_K_DSCNN, KWS_K_CNNTRAD_CONV, KWS_K_CNNTRAD_DENSE, KWS_K_STREAM_F
 KWS_K_DSCNN_LOAD_STATS, KWS_K_DSCNN_LOAD_PACK, KWS_K_DSCNN_LOAD_FILL = 7, 8, 9  # the launches of kws_load_dscnn_device
 KWS_K_RESAMPLE = 10  # kws_resample_i16 / kws_resample_f32
 FE_REFINE_SPAN_DEFAULT = 10.2  # KWS_FE_REFINE_SPAN_DEFAULT: log(largest bin power / weakest mel band) beyond which a frame is redone in float64
+FE_ROUTE_AUTO, FE_ROUTE_GENERIC = 0, 1  # KWS_FE_ROUTE_*: the kernel compiled for the reference geometry / the generic one (diagnostics)
 FE_F32, FE_F64 = 0, 1  # KWS_FE_F32 (default: the fast float32 front end) / KWS_FE_F64 (float64 after framing, as psf)
 ACT_FLOATS_PER_CLIP = 64 * (141 + 141 + 245 + 357) + 64 + 64 * 477  # KWS_ACT_FLOATS_PER_CLIP
 PW_F32 = 1          # KWS_PW_F32: pointwise convolutions on v_mfma_f32_32x32x2_f32
@@ -45,6 +46,7 @@ SIGNATURES = {
     "kws_set_frontend": (C.c_int, [_c_ctx] + [C.c_int] * 7 + [C.c_float, C.c_int]),
     "kws_set_frontend_math": (C.c_int, [_c_ctx, C.c_int]),
     "kws_frontend_math": (C.c_int, [_c_ctx]),
+    "kws_set_frontend_route": (C.c_int, [_c_ctx, C.c_int]),
     "kws_set_frontend_refine": (C.c_int, [_c_ctx, C.c_float]),
     "kws_frontend_stats": (C.c_int, [_c_ctx, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "kws_spec_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
@@ -233,6 +235,10 @@ class Context:
 
     def set_frontend_math(self, math: int):
         self._check(self._lib.kws_set_frontend_math(self._h, int(math)), AudioProcessingError)
+
+    def set_frontend_route(self, route: int = FE_ROUTE_AUTO):
+        """Diagnostics: FE_ROUTE_GENERIC keeps reference-geometry int16 calls on the generic wavefront-resident kernel (same bits)."""
+        self._check(self._lib.kws_set_frontend_route(self._h, int(route)), AudioProcessingError)
 
     def frontend_math(self) -> int:
         """FE_F32 or FE_F64: the arithmetic kws_mfcc_* actually uses for the configured geometry."""

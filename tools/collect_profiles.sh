@@ -5,7 +5,8 @@
 # its own pass with --kernel-trace only, never combined with sys/hip/hsa tracing).
 #   tools/collect_profiles.sh <round tag, e.g. r03> [workloads...]
 # Writes gpurun_out/prof_<tag>/ ; copy what should be judged into profiles/.  Fails if a kernel-stats file does not
-# hold exactly spinup + warmup + steps calls of the workload's kernels.
+# hold exactly spinup + warmup + steps calls of the workload's kernels (kws_mfcc_i16_: whichever int16 MFCC kernel the
+# geometry routes to -- kws_mfcc_i16_ref_kernel at the reference's).
 set -o pipefail
 TAG=${1:-r03}; shift
 WORKLOADS=${*:-"ds-cnn mfcc-only cnn-trad-fpool3 ds-cnn-1024 stream"}
@@ -17,10 +18,10 @@ cd /tmp && export TMPDIR=/tmp
 SPIN=60; WARM=20
 for W in $WORKLOADS; do
   case $W in
-    ds-cnn)          STEPS=200; CMD="python $REPO/bench.py --steps $STEPS --warmup $WARM --spinup $SPIN --cpu-sample 0 --configs none --no-parity"; KERNELS="kws_mfcc_i16_kernel kws_mfcc_refine_kernel kws_dscnn_fwd_kernel";;
-    mfcc-only)       STEPS=200; CMD="python $REPO/bench.py --model mfcc-only --steps $STEPS --warmup $WARM --spinup $SPIN --cpu-sample 0"; KERNELS="kws_mfcc_i16_kernel kws_mfcc_refine_kernel";;
-    cnn-trad-fpool3) STEPS=100; CMD="python $REPO/bench.py --model cnn-trad-fpool3 --steps $STEPS --warmup $WARM --spinup $SPIN --cpu-sample 0"; KERNELS="kws_mfcc_i16_kernel kws_cnntrad_conv_kernel kws_cnntrad_dense_kernel";;
-    ds-cnn-1024)     STEPS=400; CMD="python $REPO/bench.py --batch 1024 --steps $STEPS --warmup $WARM --spinup $SPIN --cpu-sample 0 --configs none --no-parity"; KERNELS="kws_mfcc_i16_kernel kws_dscnn_fwd_kernel";;
+    ds-cnn)          STEPS=200; CMD="python $REPO/bench.py --steps $STEPS --warmup $WARM --spinup $SPIN --cpu-sample 0 --configs none --no-parity"; KERNELS="kws_mfcc_i16_ kws_mfcc_refine_kernel kws_dscnn_fwd_kernel";;
+    mfcc-only)       STEPS=200; CMD="python $REPO/bench.py --model mfcc-only --steps $STEPS --warmup $WARM --spinup $SPIN --cpu-sample 0"; KERNELS="kws_mfcc_i16_ kws_mfcc_refine_kernel";;
+    cnn-trad-fpool3) STEPS=100; CMD="python $REPO/bench.py --model cnn-trad-fpool3 --steps $STEPS --warmup $WARM --spinup $SPIN --cpu-sample 0"; KERNELS="kws_mfcc_i16_ kws_cnntrad_conv_kernel kws_cnntrad_dense_kernel";;
+    ds-cnn-1024)     STEPS=400; CMD="python $REPO/bench.py --batch 1024 --steps $STEPS --warmup $WARM --spinup $SPIN --cpu-sample 0 --configs none --no-parity"; KERNELS="kws_mfcc_i16_ kws_dscnn_fwd_kernel";;
     stream)          STEPS=300; CMD="python $REPO/tools/bench_stream.py 64 $STEPS eager"; KERNELS="kws_dscnn_fwd_kernel";;
     *) echo "unknown workload $W"; exit 1;;
   esac
@@ -53,7 +54,7 @@ done
 python3 - "$OUT" "$TAG" $WORKLOADS <<'PY'
 import csv, json, sys, collections, os
 out, tag, workloads = sys.argv[1], sys.argv[2], sys.argv[3:]
-KEYS = ("kws_mfcc_i16_kernel", "kws_mfcc_refine_kernel", "kws_dscnn_fwd_kernel", "kws_cnntrad_conv_kernel", "kws_cnntrad_dense_kernel", "kws_stream_frame_kernel")
+KEYS = ("kws_mfcc_i16_", "kws_mfcc_refine_kernel", "kws_dscnn_fwd_kernel", "kws_cnntrad_conv_kernel", "kws_cnntrad_dense_kernel", "kws_stream_frame_kernel")
 def per_kernel(path, counter):
     acc = collections.defaultdict(lambda: collections.defaultdict(float))  # kernel -> dispatch -> sum over instances
     for r in csv.DictReader(open(path)):

@@ -20,7 +20,7 @@ with open(os.path.join(out, "summary.txt"), "w") as fh:
         agg = collections.defaultdict(lambda: collections.defaultdict(float))  # counter -> dispatch -> sum over instances
         for f in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):
             for r in csv.DictReader(open(f)):
-                if "kws_mfcc_i16_kernel" in r["Kernel_Name"]:
+                if "kws_mfcc_i16_" in r["Kernel_Name"]:
                     agg[r["Counter_Name"]][r["Dispatch_Id"]] += float(r["Counter_Value"])
         for c, v in sorted(agg.items()):
             line = f"{os.path.basename(d.rstrip('/')):20s} {c:24s} {sum(v.values())/len(v):16.1f}  per launch (n={len(v)})"

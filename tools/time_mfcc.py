@@ -2,6 +2,8 @@
 """Diagnostics (GPU box): time kws_mfcc_i16 alone for the library selected by KWS_HIP_LIB -- the call as a whole with the
 selective float64 refinement off and on (alternating rounds, so clock drift hits both alike), the per-kernel times of the
 float32 kernel and of the refinement launch (HIP events on the context's stream), and how many frames were refined.
+A second line compares, inside this process, the kernel compiled for the reference geometry with the generic wavefront-resident
+kernel (kws_set_frontend_route; alternating rounds, kernel-only times).
   python tools/time_mfcc.py [uniform|golden|speech]      workload: bench noise (default), the 48 golden clips tiled to
                                                           4096, or 32 speech-like clips tiled to 4096"""
 import os, sys
@@ -53,3 +55,20 @@ print(f"{os.path.basename(name):24s} {kind}: mfcc call {min(res[0.0]):.4f} ms wi
       f"float32 kernel {kern[0.0][0][0] / max(kern[0.0][0][1], 1):.4f} ms without the flag, {kern[1e9][0][0] / max(kern[1e9][0][1], 1):.4f} with, empty refinement launch {kern[1e9][1][0] / max(kern[1e9][1][1], 1):.4f} ms; "
       f"float32 kernel {ms_f32 / max(n_f32, 1):.4f} ms, refinement launch {ms_ref / max(n_ref, 1):.4f} ms, "
       f"{last} of {B * 99} frames refined per call ({100.0 * last / (B * 99):.3f} %)  checksum {float(out.double().sum()):.6f}")
+for span in (_native.FE_REFINE_SPAN_DEFAULT, 0.0):
+    ctx.set_frontend_refine(span)
+    route = {_native.FE_ROUTE_GENERIC: [], _native.FE_ROUTE_AUTO: []}
+    for rnd in range(3):
+        for r in route:
+            ctx.set_frontend_route(r)
+            for _ in range(10): ctx.mfcc_i16(wav, out)
+            ctx.prof_reset(); ctx.prof_enable(2)
+            for _ in range(200): ctx.mfcc_i16(wav, out)
+            ms, n = ctx.prof_read(_native.KWS_K_MFCC)
+            ctx.prof_enable(0)
+            route[r].append(ms / max(n, 1))
+    ctx.set_frontend_route(_native.FE_ROUTE_AUTO)
+    g, a = route[_native.FE_ROUTE_GENERIC], route[_native.FE_ROUTE_AUTO]
+    print(f"{os.path.basename(name):24s} {kind}: float32 kernel by route, refinement {'on' if span else 'off'}, three rounds: generic {' '.join(f'{x:.4f}' for x in g)} ms, "
+          f"reference {' '.join(f'{x:.4f}' for x in a)} ms; medians {sorted(g)[1]:.4f} -> {sorted(a)[1]:.4f} ms ({100.0 * (sorted(a)[1] / sorted(g)[1] - 1.0):+.2f} %)")
+ctx.set_frontend_refine(_native.FE_REFINE_SPAN_DEFAULT)
