@@ -518,6 +518,77 @@ int kws_segment_f32(kws_ctx* ctx, const float* d_feat, int R, int F_total, int n
 int kws_cut_i16(kws_ctx* ctx, const int16_t* d_pcm, int R, int n_total, const int32_t* d_span, int U, int normalize_to,
                 int16_t* d_clips, int n_out, int32_t* d_peak);
 
+/* Cutting the spans of a ragged batch (below) needs no entry of its own: kws_cut_i16 over the whole buffer as ONE recording
+ * (R = 1, n_total = n_pcm, recording index 0), with start[r] added to each span of recording r on the host, gives the clips
+ * and peaks kws_cut_i16 gives on that recording alone -- a span lies inside its recording, so the clamp to [0, n_pcm] never
+ * bites. */
+
+/* ---- batches of recordings of unequal length: the scan, the frames, the decisions and the endpointer above in ONE call for R
+ * recordings that each keep their own length.  Every recording's results are bit-identical to the equal-length entry run on
+ * that recording alone.
+ *   Layout.  PCM: one device buffer d_pcm of n_pcm int16 samples, 16-byte aligned; recording r is samples [start[r], start[r] +
+ *   len[r]).  start (int64 [R]) and len (int32 [R]) are HOST arrays, checked before anything is launched: len[r] >= 1,
+ *   start[r] >= 0, start[r] % 8 == 0, start[r] + len[r] <= n_pcm, else KWS_EINVAL; n_pcm <= 2^30 and R <= 2^20, else
+ *   KWS_EUNSUPPORTED.  That covers a packed buffer (starts rounded up to 8) and the rectangular output of kws_resample_i16 with
+ *   d_len (start[r] = r * n_out, n_out % 8 == 0).  Nothing outside a recording's span is read as part of it -- the one 16-byte
+ *   vector that straddles its end is read sample by sample.
+ *   Frames: one packed array float32 [F_pack, numcep].  Recording r has F_r = 1 + ceil((len[r] - frame_len) / frame_step) rows
+ *   (1 when len[r] <= frame_len) from row frame_off[r]; its row count is rounded up to a multiple of row_multiple and the
+ *   rounding rows are written as zeros; frame_off[R] = F_pack <= 2^28.
+ *   Windows: with row_multiple = hop_frames the packed array is scanned as ONE recording of F_pack frames by the strided DS-CNN
+ *   launch of kws_scan_i16; window w of recording r is packed window win_off[r] + w, win_off[r] = frame_off[r] / hop_frames, W_r =
+ *   0 when F_r < T, else (F_r - T) / hop_frames + 1, and W_pack = 0 when F_pack < T, else (F_pack - T) / hop_frames + 1.  Every
+ *   win_off[r] + w with w < W_r lies below W_pack.  The packed windows that belong to no recording straddle two recordings: they
+ *   are computed and their content is unspecified -- at most ceil((T - 1) / hop_frames) + 1 per recording.
+ *   The plan tables are derived on the host and uploaded into context scratch: the device entries may wait for the stream,
+ *   allocate, and are not for stream capture. */
+
+/* The ragged front end: kws_frames_i16 for every recording of the batch in one launch (plus the refinement of the frames it
+ * flags).  d_feat_out: float32 [F_pack, numcep] as laid out above (kws_host_ragged_plan with hop_frames = row_multiple gives
+ * frame_off and F_pack); every row is written.  Rows frame_off[r] .. frame_off[r] + F_r - 1 equal, word for word,
+ * kws_frames_i16 on recording r alone, selective float64 refinement included; kws_frontend_stats counts sum F_r frames and the
+ * flagged frames of the recordings together.
+ *   Routes: the float32 wavefront-resident kernel at its generic geometry (frame_len in (384, 448], 4 * frame_step a multiple of
+ *   8, 3 * frame_step + 448 <= 1024 -- the reference's 400 / 160 among them), refinement on or off.  KWS_FE_F64 and every other
+ *   geometry: KWS_EUNSUPPORTED.  A NULL pointer, R or n_pcm < 1, row_multiple < 1, d_pcm off a 16-byte boundary, a bad start /
+ *   len: KWS_EINVAL.  No front end: KWS_ESTATE.  F_pack > 2^28: KWS_EUNSUPPORTED.
+ *   Timed under KWS_K_MFCC / KWS_K_MFCC_REFINE.  Asynchronous on the context stream after the tables' upload. */
+int kws_frames_ragged_i16(kws_ctx* ctx, const int16_t* d_pcm, int n_pcm, const int64_t* start, const int32_t* len, int R,
+                          int row_multiple, float* d_feat_out);
+
+/* kws_scan_i16 for a ragged batch: kws_frames_ragged_i16 with row_multiple = hop_frames, then the scan launch over the packed
+ * frame array.  d_logits: float32 [W_pack, C]; d_label: int32 [W_pack] or NULL; d_feat_out: float32 [F_pack, numcep] or NULL
+ * (a context workspace).  Rows win_off[r] + w, w < W_r, equal kws_scan_i16 on recording r alone (window w), bit for bit; the
+ * other rows are unspecified.  A recording shorter than a window is fine (W_r = 0); when every W_r is 0 nothing is launched
+ * after the frames.  Scope, model and state checks as kws_scan_i16; argument checks and limits as kws_frames_ragged_i16, and
+ * W_pack <= 2^30.  Timed under KWS_K_MFCC / KWS_K_MFCC_REFINE and KWS_K_DSCNN. */
+int kws_scan_ragged_i16(kws_ctx* ctx, const int16_t* d_pcm, int n_pcm, const int64_t* start, const int32_t* len, int R, int hop_frames,
+                        float* d_logits, int32_t* d_label, float* d_feat_out);
+
+/* kws_scan_detect_f32 per recording of a ragged scan.  d_logits: float32 [W_pack, C]; win_off, windows: HOST int32 [R]
+ * (kws_host_ragged_plan), win_off ascending with win_off[r] >= win_off[r - 1] + windows[r - 1].  Softmax, smoothing, candidates
+ * and the refractory walk run per recording: the history never crosses a recording's first window, events carry window
+ * indices relative to their own recording, and the packed rows between recordings are never read.  d_event_count int32 [R];
+ * the three event arrays [R, max_events]; d_smoothed float32 [W_pack, C] or NULL (rows of no recording are not written).
+ * Recording r's results equal kws_scan_detect_f32 on its own [1, W_r, C] logits; W_r = 0 gives count 0.
+ *   KWS_EINVAL as kws_scan_detect_f32 (R < 1, C outside [1, 64], ...), a NULL table, a negative count or overlapping windows.
+ *   R > 2^20 or more than 2^30 packed windows: KWS_EUNSUPPORTED.  Not timed; scratch of (C + 2) floats per packed window. */
+int kws_scan_detect_ragged_f32(kws_ctx* ctx, const float* d_logits, const int32_t* win_off, const int32_t* windows, int R, int C,
+                               int smooth_window, int first_keyword, float threshold, int refractory, float* d_smoothed,
+                               int32_t* d_event_window, int32_t* d_event_label, float* d_event_score, int max_events,
+                               int32_t* d_event_count);
+
+/* kws_segment_f32 per recording of a packed frame array.  d_feat: float32 [F_pack, numcep] (kws_frames_ragged_i16, any
+ * row_multiple); frame_off, frames, len: HOST int32 [R] -- the recording's first row, its F_r and its samples (frame_off
+ * ascending, rows not overlapping).  Frames before 0 and at or past F_r are unvoiced, the reason-2 close falls at F_r - 1,
+ * end_sample is clipped to len[r], and spans are in samples relative to the recording's own start.  d_utt: int32 [R, max_utts,
+ * 5]; d_count: int32 [R].  Recording r's results equal kws_segment_f32 on that recording alone.
+ *   KWS_EINVAL / KWS_ESTATE / KWS_EUNSUPPORTED as kws_segment_f32, plus: a NULL table, frames[r] or len[r] < 1 or overlapping
+ *   rows (KWS_EINVAL); R > 2^20 or rows beyond 2^28 (KWS_EUNSUPPORTED).  Two launches; not timed. */
+int kws_segment_ragged_f32(kws_ctx* ctx, const float* d_feat, const int32_t* frame_off, const int32_t* frames, const int32_t* len, int R,
+                           float log_energy_threshold, int on_window, int off_window, int pre_roll, int max_frames, int32_t* d_utt,
+                           int max_utts, int32_t* d_count);
+
 /* ---- live utterances (the same loop, :114-192, for the streams of kws_stream_open: the walk of kws_segment_f32 taken one
  * frame per hop, a PCM history per stream to cut from, events in a queue the host reads without a copy) ------------------ */
 
@@ -851,6 +922,14 @@ int kws_host_cnn_trad_image(const float* blob, size_t n_floats, int num_classes,
  * be NULL.  Non-positive sizes: KWS_EINVAL. */
 int kws_host_scan_shape(int n_total, int frame_len, int frame_step, int window_frames, int hop_frames, int* frames_total,
                         int* n_windows);
+
+/* The plan of a ragged batch (see "batches of recordings of unequal length"): for R recordings of len[r] samples,
+ * frames[r] = F_r and windows[r] = W_r exactly as kws_host_scan_shape gives them per recording; frame_off [R + 1] with each
+ * recording's rows rounded up to a multiple of hop_frames (frame_off[R] = F_pack); win_off[r] = frame_off[r] / hop_frames;
+ * *W_pack = the windows of the packed array scanned as one recording.  Any output pointer may be NULL.  A NULL len, R < 1,
+ * a length < 1, hop_frames < 1 or another non-positive size: KWS_EINVAL.  R > 2^20 or F_pack > 2^28: KWS_EUNSUPPORTED. */
+int kws_host_ragged_plan(const int32_t* len, int R, int frame_len, int frame_step, int window_frames, int hop_frames, int32_t* frames,
+                         int32_t* frame_off, int32_t* windows, int32_t* win_off, int* W_pack);
 
 /* Host side of kws_resample_* (no GPU).  kws_host_resample_len: *n_out = ceil(n_in * up / down), the natural length of n_in
  * samples (n_in >= 0).  kws_host_resample_design: the reduced pair, half (the taps number 2 * half + 1), the outputs one

@@ -126,7 +126,8 @@ void kws_destroy(kws_ctx* c) {
     if (c->d_train_ws) (void)hipFree(c->d_train_ws);
     if (c->d_feat_ws) (void)hipFree(c->d_feat_ws);
     if (c->d_scan_ws) (void)hipFree(c->d_scan_ws);
-    stream_free(c);      // rings, hop counter, captured graph, smoothing and endpointer history (kws_decide.hip)
+    if (c->d_ragged) (void)hipFree(c->d_ragged);
+    stream_free(c);     // rings, hop counter, captured graph, smoothing and endpointer history (kws_decide.hip)
     eval_free(c);        // evaluation accumulators (kws_eval.hip)
     stream_resample_free(c);  // streaming resampler: history, hop buffer, pinned input (kws_resample.hip)
     resample_free(c);    // tap tables of the rate pairs (kws_resample.hip)

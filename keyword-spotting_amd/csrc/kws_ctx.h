@@ -78,6 +78,9 @@ struct kws_ctx {
     // kws_scan_i16: a recording's frames when the caller keeps none (kws_scan_detect_f32's scratch is d_conv_ws)
     float* d_scan_ws = nullptr;
     size_t scan_ws_floats = 0;
+    // the ragged entries' plan tables (records, per-recording offsets and counts), derived on the host per call
+    unsigned char* d_ragged = nullptr;
+    size_t ragged_bytes = 0;
 
     // streaming state (kws_stream_*): per-stream PCM ring, feature ring, hop counter, optional graph
     int n_streams = 0, ring_len = 0;
@@ -203,6 +206,9 @@ inline int alloc_endpoint_state(kws_ctx* c, const char* fn, size_t S, unsigned l
     if (e == hipSuccess) e = hipMemsetAsync(counts, 0, counts_b, c->stream);
     return e == hipSuccess ? KWS_OK : fail_hip(c, e, (std::string(fn) + ": hipMemsetAsync").c_str());
 }
+
+// Host-built plan tables of a ragged call -> context scratch (kws_ragged.hip); may wait for the stream.
+int upload_ragged_tables(kws_ctx* c, const void* host, size_t bytes, const char* fn, const void** d_tables);
 
 // Bracket a kernel launch with events when profiling is on.
 struct ProfScope {

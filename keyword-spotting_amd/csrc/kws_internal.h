@@ -106,6 +106,30 @@ hipError_t launch_mfcc_refine(hipStream_t s, const FrontendParams& p, const Fron
                               const RefineList& rl, int B);
 hipError_t launch_mfcc_refine(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const AugmentArgs& a, float* d_out,
                               const RefineList& rl, int B);
+// Ragged batches (kws_frames_ragged_i16; the entries are in kws_ragged.hip): one record per recording and a closing record R
+// that holds the totals, derived on the host and uploaded into context scratch.  Recording r is samples [start, start + len) of
+// the one PCM buffer, rows [frame_off, frame_off + frames) of the packed frame array and frame pairs [pair_off, ...) of the
+// refinement worklist's numbering; wavefronts [wave_off, next record's wave_off) of the front-end launch walk its chunks, cpw each.
+struct RaggedRec {
+    long long start;
+    int len, frames;
+    int frame_off;     // record R: F_pack (the rows between a recording's last frame and the next record's first are written as zeros)
+    int pair_off;      // record R: the number of pairs
+    int wave_off;      // record R: the number of wavefronts
+    int cpw;
+};
+struct RaggedArgs {
+    const RaggedRec* rec;  // [R + 1]
+    int R;
+};
+// The float32 wavefront-resident kernel (generic geometry) over the recordings of rg, and the float64 redo of the frames it listed.
+hipError_t launch_mfcc_ragged(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_pcm, const RaggedArgs& rg,
+                              int n_waves, float* d_out, const RefineList& rl);
+hipError_t launch_mfcc_refine_ragged(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_pcm,
+                                     const RaggedArgs& rg, float* d_out, const RefineList& rl, int B);
+// Chunks per wavefront of a wavefront-resident launch of total_chunks chunks in all, for a clip of n_chunks of them (host).
+int mfcc_wr_chunks_per_wave(long total_chunks, int n_chunks);
+constexpr int MFCC_WR_FRAMES = 4;  // frames per chunk of the wavefront-resident kernels
 // The float64 front end: any nfft (power of two up to 4096: FFT; otherwise up to 2048: direct DFT), any frame length.
 hipError_t launch_mfcc_f64(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_wav, int B, float* d_out);
 hipError_t launch_mfcc_f64(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, int B, float* d_out);

@@ -212,6 +212,21 @@ __global__ __launch_bounds__(MFCC_THREADS) __attribute__((amdgpu_waves_per_eu(KW
 constexpr int WR_PAIRS = 2, WR_FRAMES = 2 * WR_PAIRS;   // frames per chunk
 constexpr int WR_SPAN = 1024;                            // floats of LDS per wavefront for the chunk's span (two uint4 of PCM per lane)
 constexpr int WR_WAVE_BYTES = WR_SPAN * 4 + SCR_BYTES;
+static_assert(WR_FRAMES == MFCC_WR_FRAMES, "the host's plan of a ragged batch counts chunks of WR_FRAMES frames");
+
+// One 16-byte vector of a recording of a ragged batch (n0 a multiple of 8, x + n0 16-byte aligned): the vector itself when it lies
+// inside the recording, zeros when it lies past it, and the one vector that straddles len sample by sample -- what follows the
+// recording in the buffer (the next recording, or the buffer's end) is never read.
+__device__ __forceinline__ uint4 ragged_vec8(const int16_t* __restrict__ x, int n0, int len) {
+    if (n0 + 8 <= len) return *reinterpret_cast<const uint4*>(x + n0);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    if (n0 < len) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            if (n0 + i < len) w[i >> 1] |= (uint32_t)(uint16_t)x[n0 + i] << (16 * (i & 1));
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
 
 // Eight consecutive augmented samples n0 .. n0 + 7 (n0 a multiple of 8) of a clip of the resident split, the values aug_sample
 // gives one by one.  The source run starts at j0 = n0 - shift, aligned to 2 bytes only: the two ALIGNED 16-byte vectors that
@@ -279,12 +294,16 @@ __host__ __device__ inline size_t mfcc_wr_lds_bytes(const FrontendParams& p) {
 // G (kws_mfcc_dev.h): GeomAny reads the geometry from p, as every wavefront-resident kernel did before the type existed; GeomRef
 // is the reference configuration at compile time (kws_mfcc_i16_ref_kernel): the row pointer and the frames' LDS addresses
 // advance by constants, the frame bound is a lane mask, and the worklist code exists only in the instantiation that flags.
-template <bool AUG, class G = GeomAny>
+// RAGGED (kws_mfcc_i16_ragged_kernel): the clips are the recordings of rg, each with its own length, frame count, first row and
+// share of the launch's wavefronts; a wavefront finds its recording once, by a scalar binary search over the records' first
+// wavefronts, and from there on p.n_samples / p.num_frames are that recording's.  Every RAGGED branch is an if constexpr.
+template <bool AUG, class G = GeomAny, bool RAGGED = false>
 __device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t, const int16_t* __restrict__ wav,
                                              float* __restrict__ out, RefineList rl, int B, int chunks_per_wave,
-                                             AugmentArgs aug) {
+                                             AugmentArgs aug, RaggedArgs rg = RaggedArgs{}) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     static_assert(!(AUG && G::REF), "the fused loader keeps the generic geometry");
+    static_assert(!RAGGED || (!AUG && !G::REF), "the ragged kernel reads PCM at the generic geometry");
     const int nfp = (G::nfilt(p) + 3) & ~3;
     const int numcep = G::numcep(p), frame_step = G::frame_step(p);
     float* dctb = reinterpret_cast<float*>(smem);
@@ -306,14 +325,46 @@ __device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t,
     zero_scratch(scr, lane);
 
     // this wavefront's share: chunks [c, c_end) of clip `clip`
-    const int n_chunks = (p.num_frames + WR_FRAMES - 1) / WR_FRAMES;
-    const int waves_per_clip = (n_chunks + chunks_per_wave - 1) / chunks_per_wave;
-    const int gw = blockIdx.x * MFCC_WAVES + wv;
-    const int clip = gw / waves_per_clip, part = gw - clip * waves_per_clip;
-    int c = part * chunks_per_wave;
-    const int c_end = min(n_chunks, c + chunks_per_wave);
-    const bool active = clip < B && c < c_end;  // wave-uniform
-    const int16_t* __restrict__ x = AUG ? nullptr : wav + (size_t)(active ? clip : 0) * p.n_samples;
+    int n_chunks, clip, c, c_end_of, pair_base = 0, pad_floats = 0;
+    bool active_of;
+    size_t x_first;
+    if constexpr (RAGGED) {
+        const int gw = uniform_i(blockIdx.x * MFCC_WAVES + wv);
+        active_of = gw < B;  // B: the launch's wavefronts
+        int lo = 0, hi = rg.R;  // rec[lo].wave_off <= gw < rec[hi].wave_off (record R closes the table)
+        if (active_of)
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (rg.rec[mid].wave_off <= gw) lo = mid;
+                else hi = mid;
+            }
+        const RaggedRec rr = rg.rec[lo];
+        p.n_samples = uniform_i(rr.len);
+        p.num_frames = uniform_i(rr.frames);
+        n_chunks = (p.num_frames + WR_FRAMES - 1) / WR_FRAMES;
+        const int cpw = uniform_i(rr.cpw);
+        c = (gw - uniform_i(rr.wave_off)) * cpw;
+        c_end_of = min(n_chunks, c + cpw);
+        active_of = active_of && c < c_end_of;
+        clip = 0;  // rows and worklist entries count from the recording's own first row and pair
+        x_first = (size_t)rr.start;
+        out += (size_t)uniform_i(rr.frame_off) * numcep;
+        pair_base = uniform_i(rr.pair_off);
+        pad_floats = (uniform_i(rg.rec[lo + 1].frame_off) - uniform_i(rr.frame_off) - p.num_frames) * numcep;
+    } else {
+        n_chunks = (p.num_frames + WR_FRAMES - 1) / WR_FRAMES;
+        const int waves_per_clip = (n_chunks + chunks_per_wave - 1) / chunks_per_wave;
+        const int gw = blockIdx.x * MFCC_WAVES + wv;
+        clip = gw / waves_per_clip;
+        const int part = gw - clip * waves_per_clip;
+        c = part * chunks_per_wave;
+        c_end_of = min(n_chunks, c + chunks_per_wave);
+        active_of = clip < B && c < c_end_of;  // wave-uniform
+        x_first = (size_t)(active_of ? clip : 0) * p.n_samples;
+    }
+    const int c_end = c_end_of;
+    const bool active = active_of;
+    const int16_t* __restrict__ x = AUG ? nullptr : wav + x_first;
     AugClip ac{};
     if constexpr (AUG) ac = aug_clip(aug, active ? clip : 0, p.n_samples);  // wave-uniform: scalar registers
     const int chunk_step = WR_FRAMES * frame_step;  // samples from one chunk's span to the next (a multiple of 8: checked by the launcher)
@@ -324,8 +375,13 @@ __device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t,
     auto fetch = [&](int cc, int lane) {
         const int s0 = cc * chunk_step;
         const int n0 = s0 + 8 * lane, n1 = n0 + 512;
-        v0 = n0 + 8 <= p.n_samples ? *reinterpret_cast<const uint4*>(x + n0) : make_uint4(0, 0, 0, 0);
-        v1 = n1 + 8 <= p.n_samples ? *reinterpret_cast<const uint4*>(x + n1) : make_uint4(0, 0, 0, 0);
+        if constexpr (RAGGED) {
+            v0 = ragged_vec8(x, n0, p.n_samples);
+            v1 = ragged_vec8(x, n1, p.n_samples);
+        } else {
+            v0 = n0 + 8 <= p.n_samples ? *reinterpret_cast<const uint4*>(x + n0) : make_uint4(0, 0, 0, 0);
+            v1 = n1 + 8 <= p.n_samples ? *reinterpret_cast<const uint4*>(x + n1) : make_uint4(0, 0, 0, 0);
+        }
         before = s0 > 0 ? x[s0 - 1] : (int16_t)0;
     };
     __syncthreads();  // the only workgroup barrier: the shared tables are in place
@@ -354,7 +410,7 @@ __device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t,
                             (unsigned long long)__builtin_popcount(has) | ((unsigned long long)__builtin_popcount(fmask) << 32));   \
         const int at = __builtin_amdgcn_readfirstlane((int)(unsigned)old) + __builtin_popcount(has & ((1u << (lane & 31)) - 1u));   \
         if (fk != 0u && at < rl.cap)                                                                                                \
-            rl.list[at] = (int)((((unsigned)(rl.clip0 + clip) * (unsigned)((p.num_frames + 1) / 2) + (unsigned)(pair0 + lane)) << 2) | fk); \
+            rl.list[at] = (int)((((RAGGED ? (unsigned)pair_base : (unsigned)(rl.clip0 + clip) * (unsigned)((p.num_frames + 1) / 2)) + (unsigned)(pair0 + lane)) << 2) | fk); \
     }
     for (; c < c_end; ++c) {
         if constexpr (!AUG) fetch(c, lane);
@@ -413,6 +469,13 @@ __device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t,
                     if constexpr (G::REF) {
                         // past the clip the vector itself is zeros (fetch), so samples 1..7 are 0 - 0.97 * 0 = +0 already: one select, not eight
                         if (n + 8 > p.n_samples) y[0] = 0.f;
+                    } else if constexpr (RAGGED) {
+                        // a recording ends at any sample: the pre-emphasised signal is zero from len[r] on, also inside the vector
+                        // that straddles it (its first padded sample would otherwise be -preemph * x[len - 1])
+                        if (n + 8 > p.n_samples) {
+#pragma unroll
+                            for (int i = 0; i < 8; ++i) y[i] = n + i < p.n_samples ? y[i] : 0.f;
+                        }
                     } else if (n + 8 > p.n_samples) {  // past the clip: psf pads the PRE-EMPHASISED signal with zeros
 #pragma unroll
                         for (int i = 0; i < 8; ++i) y[i] = 0.f;
@@ -519,6 +582,14 @@ __device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t,
     }
     if constexpr (G::FLAGS) KWS_FLUSH_FLAGS()
 #undef KWS_FLUSH_FLAGS
+    if constexpr (RAGGED) {
+        // the wavefront that owns the recording's last chunk writes the zero rows that round its row count up
+        if (c_end == n_chunks) {
+            const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+            float* pad = out + (size_t)p.num_frames * numcep;
+            for (int i = lane; i < pad_floats; i += 64) pad[i] = 0.f;
+        }
+    }
 }
 
 __global__ __launch_bounds__(MFCC_THREADS) __attribute__((amdgpu_waves_per_eu(KWS_MFCC_EU, KWS_MFCC_EU))) void kws_mfcc_i16_kernel(
@@ -534,6 +605,11 @@ __global__ __launch_bounds__(MFCC_THREADS) __attribute__((amdgpu_waves_per_eu(KW
 __global__ __launch_bounds__(MFCC_THREADS) __attribute__((amdgpu_waves_per_eu(KWS_MFCC_EU, KWS_MFCC_EU))) void kws_mfcc_i16_ref_noflag_kernel(
     FrontendParams p, FrontendTables t, const int16_t* __restrict__ wav, float* __restrict__ out, RefineList rl, int B, int chunks_per_wave) {
     mfcc_wr_body<false, GeomRef<false>>(p, t, wav, out, rl, B, chunks_per_wave, AugmentArgs{});
+}
+// The generic kernel over the recordings of a ragged batch (kws_frames_ragged_i16); B: the launch's wavefronts.
+__global__ __launch_bounds__(MFCC_THREADS) __attribute__((amdgpu_waves_per_eu(KWS_MFCC_EU, KWS_MFCC_EU))) void kws_mfcc_i16_ragged_kernel(
+    FrontendParams p, FrontendTables t, const int16_t* __restrict__ pcm, float* __restrict__ out, RefineList rl, RaggedArgs rg, int n_waves) {
+    mfcc_wr_body<false, GeomAny, true>(p, t, pcm, out, rl, n_waves, 0, AugmentArgs{}, rg);
 }
 #ifndef KWS_MFCC_AUG_EU
 #define KWS_MFCC_AUG_EU 4
@@ -653,16 +729,17 @@ bool mfcc_reference_geometry(const FrontendParams& p) {
            p.append_energy != 0;
 }
 
-// Chunks per wavefront of the wavefront-resident kernels for a launch of nb clips.
+// Chunks per wavefront of the wavefront-resident kernels for a launch of total_chunks chunks (nb clips of n_chunks each, or the
+// recordings of a ragged batch together) and a clip of n_chunks.
 // ~5 chunks (20 frames) per wavefront, split evenly (99 frames = 25 chunks = 5 x 5): measured on 4096 clips, 1 / 5 / 25
 // chunks per wavefront take 0.219 / 0.183 / 0.201 ms -- short-lived wavefronts keep the CUs' phases mixed and the tail
 // short, an uneven split (6 + 6 + 6 + 6 + 1: 0.209 ms) wastes a wavefront's set-up on one chunk.  Small batches spread
 // a clip over more wavefronts, down to one chunk each, so that even one clip uses 25 wavefronts.
-static int mfcc_wr_chunks_per_wave(int nb, int n_chunks) {
+int mfcc_wr_chunks_per_wave(long total_chunks, int n_chunks) {
     int wpc = (n_chunks + 2) / 5;
     wpc = wpc < 1 ? 1 : wpc;
     int cpw = (n_chunks + wpc - 1) / wpc;
-    const int fill = (int)(((long)nb * n_chunks + 4095) / 4096);  // chunks per wavefront that still fill 256 CUs x 16 wavefronts
+    const int fill = (int)((total_chunks + 4095) / 4096);  // chunks per wavefront that still fill 256 CUs x 16 wavefronts
     cpw = cpw > fill ? (fill < 1 ? 1 : fill) : cpw;
     static const int cpw_env = [] {  // experiment hook, read once (profiles/r03_mfcc_ab.txt: the chunks-per-wavefront scan)
         const char* e = getenv("KWS_X_MFCC_CPW");
@@ -691,7 +768,7 @@ static hipError_t launch_mfcc_wr(K kernel, hipStream_t s, const FrontendParams& 
     const int n_chunks = (p.num_frames + WR_FRAMES - 1) / WR_FRAMES;
     for (int b0 = 0; b0 < B; b0 += (1 << 20)) {  // (grid.x limit: 2^31 workgroups; a million clips per launch keeps indices in 32 bits)
         const int nb = B - b0 < (1 << 20) ? B - b0 : (1 << 20);
-        const int cpw = mfcc_wr_chunks_per_wave(nb, n_chunks);
+        const int cpw = mfcc_wr_chunks_per_wave((long)nb * n_chunks, n_chunks);
         const int waves_per_clip = (n_chunks + cpw - 1) / cpw;
         const long waves = (long)nb * waves_per_clip;
         rl.clip0 = b0;
@@ -712,6 +789,13 @@ hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTab
     }
 #endif
     return launch_mfcc_t(mfcc_tail6(p) ? kws_mfcc_i16_tile_kernel : kws_mfcc_i16_any_kernel, s, p, t, d_wav, B, d_out, rl);
+}
+hipError_t launch_mfcc_ragged(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_pcm, const RaggedArgs& rg,
+                              int n_waves, float* d_out, const RefineList& rl) {
+    if (!mfcc_wave_resident_ok(p)) return hipErrorInvalidValue;  // refused by kws_frames_ragged_i16 before it gets here
+    hipLaunchKernelGGL(kws_mfcc_i16_ragged_kernel, dim3((unsigned)((n_waves + MFCC_WAVES - 1) / MFCC_WAVES)), dim3(MFCC_THREADS),
+                       mfcc_wr_lds_bytes(p), s, p, t, d_pcm, d_out, rl, rg, n_waves);
+    return hipGetLastError();
 }
 hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, int B, float* d_out,
                        const RefineList& rl, bool) {

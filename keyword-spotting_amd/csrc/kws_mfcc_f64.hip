@@ -131,7 +131,13 @@ constexpr int REFINE_WAVES = KWS_X_REFINE_WAVES;  // wavefronts per workgroup of
 // SrcOf: batch row -> the source of that clip's samples.  A pointer to them (int16 PCM or float32: the kernels of kws_mfcc_i16 /
 // kws_mfcc_f32), or the augmented view of a clip of the resident split (kws_mfcc_augment_i16): the refinement then re-creates
 // the float32 samples the fused kernel transformed through the same per-sample function, aug_sample.
-template <typename SrcOf>
+// RAGGED (kws_mfcc_refine_ragged_kernel): the entries count pairs in the packed numbering of a ragged batch, and src_of maps a
+// pair to its recording -- samples, length, frame count, first row and first pair (RaggedClip below).
+struct RaggedClip {
+    const int16_t* x;
+    int len, frames, row0, pair0;
+};
+template <bool RAGGED, typename SrcOf>
 __device__ __forceinline__ void mfcc_refine_body(const FrontendParams& p, const FrontendTables& t, float* __restrict__ out,
                                                  const RefineList& rl, SrcOf src_of) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem64[];
@@ -151,26 +157,40 @@ __device__ __forceinline__ void mfcc_refine_body(const FrontendParams& p, const 
         int e = wv * gridDim.x + blockIdx.x;
         int entry = 0, clip = 0, fa = 0;
         bool has_b = false, nza = false, nzb = false;
+        [[maybe_unused]] int row0 = 0;
         auto fetch = [&]() {
             entry = rl.list[e];
             const int pair = entry >> 2;
-            clip = pair / pairs_per_clip;
-            fa = 2 * (pair - clip * pairs_per_clip);
-            has_b = fa + 1 < p.num_frames;
-#ifdef KWS_X_REFINE_SINGLE
-            has_b = false;  // timing experiment: wrong rows for frame b
-#endif
-            const auto x = src_of(clip);
-            const long sa = (long)fa * p.frame_step;
-            if constexpr (std::is_pointer<decltype(x)>::value) {
-                f64_load_pair<typename std::remove_cv<typename std::remove_pointer<decltype(x)>::type>::type, NCT>(
-                    p, x, sa, x, sa + p.frame_step, has_b, X, NCT, n_used, lane, nza, nzb);
+            if constexpr (RAGGED) {
+                const RaggedClip rc = src_of(pair);
+                FrontendParams q = p;  // the recording as one clip: its own length decides the padding and the vector loads
+                q.n_samples = rc.len;
+                q.num_frames = rc.frames;
+                q.vec_ok = p.vec_ok && rc.len % 8 == 0;
+                row0 = rc.row0;
+                fa = 2 * (pair - rc.pair0);
+                has_b = fa + 1 < rc.frames;
+                const long sa = (long)fa * p.frame_step;
+                f64_load_pair<int16_t, NCT>(q, rc.x, sa, rc.x, sa + p.frame_step, has_b, X, NCT, n_used, lane, nza, nzb);
             } else {
-                nza = nzb = false;
-                f64_fill_pair<NCT>(p, x, sa, x, sa + p.frame_step, has_b, X, NCT, n_used, lane, nza, nzb);
-                nza = __any(nza);
-                nzb = __any(nzb);
-                wave_order();
+                clip = pair / pairs_per_clip;
+                fa = 2 * (pair - clip * pairs_per_clip);
+                has_b = fa + 1 < p.num_frames;
+#ifdef KWS_X_REFINE_SINGLE
+                has_b = false;  // timing experiment: wrong rows for frame b
+#endif
+                const auto x = src_of(clip);
+                const long sa = (long)fa * p.frame_step;
+                if constexpr (std::is_pointer<decltype(x)>::value) {
+                    f64_load_pair<typename std::remove_cv<typename std::remove_pointer<decltype(x)>::type>::type, NCT>(
+                        p, x, sa, x, sa + p.frame_step, has_b, X, NCT, n_used, lane, nza, nzb);
+                } else {
+                    nza = nzb = false;
+                    f64_fill_pair<NCT>(p, x, sa, x, sa + p.frame_step, has_b, X, NCT, n_used, lane, nza, nzb);
+                    nza = __any(nza);
+                    nzb = __any(nzb);
+                    wave_order();
+                }
             }
         };
 #ifndef KWS_X_REFINE_LATE_FETCH
@@ -183,7 +203,9 @@ __device__ __forceinline__ void mfcc_refine_body(const FrontendParams& p, const 
 #endif
         while (e < n) {
             spectrum_pair<true, NCT>(w.X, w.P, w.tb.tw, NCT, 9, n_used, 1.0 / (double)NCT, lane);
-            float* oa = out + ((size_t)clip * p.num_frames + fa) * p.numcep;
+            float* oa;
+            if constexpr (RAGGED) oa = out + (size_t)(row0 + fa) * p.numcep;
+            else oa = out + ((size_t)clip * p.num_frames + fa) * p.numcep;
             f64_tail<NCT / 2 + 1>(p, w.tb, NCT / 2 + 1, w.P, w.L, nza, nzb, has_b, (entry & 1) ? oa : nullptr,
                                   (entry & 2) ? oa + p.numcep : nullptr, nullptr, lane);
             e += gridDim.x * n_waves;
@@ -215,11 +237,26 @@ __device__ __forceinline__ void mfcc_refine_body(const FrontendParams& p, const 
 template <typename T>
 __global__ __launch_bounds__(REFINE_WAVES * 64) void kws_mfcc_refine_kernel(FrontendParams p, FrontendTables t, const T* __restrict__ wav,
                                                                          float* __restrict__ out, RefineList rl) {
-    mfcc_refine_body(p, t, out, rl, [&](int clip) -> const T* { return wav + (size_t)clip * p.n_samples; });
+    mfcc_refine_body<false>(p, t, out, rl, [&](int clip) -> const T* { return wav + (size_t)clip * p.n_samples; });
 }
 __global__ __launch_bounds__(REFINE_WAVES * 64) void kws_mfcc_refine_augment_kernel(FrontendParams p, FrontendTables t, AugmentArgs aug,
                                                                                  float* __restrict__ out, RefineList rl) {
-    mfcc_refine_body(p, t, out, rl, [&](int clip) { return aug_clip(aug, clip, p.n_samples); });
+    mfcc_refine_body<false>(p, t, out, rl, [&](int clip) { return aug_clip(aug, clip, p.n_samples); });
+}
+// The refinement of a ragged batch: a listed pair finds its recording by a binary search over the records' first pairs (a rare
+// path: a few loads per listed pair).
+__global__ __launch_bounds__(REFINE_WAVES * 64) void kws_mfcc_refine_ragged_kernel(FrontendParams p, FrontendTables t, const int16_t* __restrict__ pcm,
+                                                                                float* __restrict__ out, RefineList rl, RaggedArgs rg) {
+    mfcc_refine_body<true>(p, t, out, rl, [&](int pair) {
+        int lo = 0, hi = rg.R;  // rec[lo].pair_off <= pair < rec[hi].pair_off
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (rg.rec[mid].pair_off <= pair) lo = mid;
+            else hi = mid;
+        }
+        const RaggedRec rr = rg.rec[lo];
+        return RaggedClip{pcm + rr.start, rr.len, rr.frames, rr.frame_off, rr.pair_off};
+    });
 }
 
 template <typename T>
@@ -278,6 +315,17 @@ hipError_t launch_mfcc_refine(hipStream_t s, const FrontendParams& p, const Fron
 hipError_t launch_mfcc_refine(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const AugmentArgs& a, float* d_out,
                               const RefineList& rl, int B) {
     return launch_mfcc_refine_t(kws_mfcc_refine_augment_kernel, s, p, t, a, d_out, rl, B);
+}
+
+hipError_t launch_mfcc_refine_ragged(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_pcm,
+                                     const RaggedArgs& rg, float* d_out, const RefineList& rl, int B) {
+    const size_t lds = f64_layout(512, true, true, p.nfilt, p.numcep, REFINE_WAVES).total;
+    hipError_t e = raise_lds_limit(kws_mfcc_refine_ragged_kernel, lds);
+    if (e != hipSuccess) return e;
+    int grid = (B + 15) / 16;  // as launch_mfcc_refine_t sizes it, B = the batch in one-second clips
+    grid = grid < 32 ? 32 : (grid > REFINE_GRID ? REFINE_GRID : grid);
+    hipLaunchKernelGGL(kws_mfcc_refine_ragged_kernel, dim3(grid), dim3(REFINE_WAVES * 64), lds, s, p, t, d_pcm, d_out, rl, rg);
+    return hipGetLastError();
 }
 
 hipError_t launch_mfcc_f64(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_wav, int B, float* d_out) {

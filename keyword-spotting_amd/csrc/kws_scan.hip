@@ -7,15 +7,13 @@ using namespace kws;
 
 namespace {
 
-// Smoothed posteriors and candidates, one thread per window.  p: softmax rows [R * W][C] (launch_softmax).  s[c] = the sum of
-// p[v][c] over the last min(S, w + 1) windows, oldest first, divided by their number; k = first argmax.  cand[i] = k when k is
-// a keyword at or over the threshold, else -1; score[i] = s[k].
-__global__ __launch_bounds__(256) void kws_scan_smooth_kernel(const float* __restrict__ p, int n, int W, int C, int S, int first_keyword,
-                                                              float threshold, float* __restrict__ smoothed, int32_t* __restrict__ cand,
-                                                              float* __restrict__ score) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;  // r * W + w
-    if (i >= n) return;
-    const int w = i % W;
+// The smoothing rule for row i of p, window w of its recording (the history never reaches before the recording's window 0):
+// s[c] = the sum of p[v][c] over the last min(S, w + 1) windows, oldest first, divided by their number; k = first argmax.
+// cand[i] = k when k is a keyword at or over the threshold, else -1; score[i] = s[k].  Shared by the equal-length and the
+// ragged kernel.
+__device__ __forceinline__ void scan_smooth_window(const float* p, int i, int w, int C, int S, int first_keyword,
+                                                   float threshold, float* smoothed, int32_t* cand,
+                                                   float* score) {
     const int terms = w + 1 < S ? w + 1 : S;
     const float* first = p + (size_t)(i - terms + 1) * C;
     const float count = (float)terms;
@@ -35,15 +33,23 @@ __global__ __launch_bounds__(256) void kws_scan_smooth_kernel(const float* __res
     score[i] = best;
 }
 
+// Smoothed posteriors and candidates, one thread per window.  p: softmax rows [R * W][C] (launch_softmax).
+__global__ __launch_bounds__(256) void kws_scan_smooth_kernel(const float* __restrict__ p, int n, int W, int C, int S, int first_keyword,
+                                                              float threshold, float* __restrict__ smoothed, int32_t* __restrict__ cand,
+                                                              float* __restrict__ score) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;  // r * W + w
+    if (i >= n) return;
+    scan_smooth_window(p, i, i % W, C, S, first_keyword, threshold, smoothed, cand, score);
+}
+
 // The refractory walk, one wavefront per recording, 64 windows per step: the first candidate lane at or after `next` fires,
 // `next` moves `refractory` windows on, and the step repeats until no candidate lane is left.  Everything but the event stores
 // is wave-uniform; events land in window order with no atomics.
-__global__ __launch_bounds__(64) void kws_scan_events_kernel(const int32_t* __restrict__ cand, const float* __restrict__ score, int W,
-                                                             int refractory, int32_t* __restrict__ ev_window, int32_t* __restrict__ ev_label,
-                                                             float* __restrict__ ev_score, int max_events, int32_t* __restrict__ ev_count) {
-    const int r = blockIdx.x, lane = threadIdx.x;
-    const int32_t* cr = cand + (size_t)r * W;
-    const float* sr = score + (size_t)r * W;
+// cr / sr: the W candidates and scores of recording r (shared by the equal-length and the ragged kernel).
+__device__ __forceinline__ void scan_events_walk(const int32_t* cr, const float* sr, int W, int refractory,
+                                                 int32_t* ev_window, int32_t* ev_label,
+                                                 float* ev_score, int max_events, int32_t* ev_count, int r,
+                                                 int lane) {
     long long next = 0;
     int count = 0;
     for (int w0 = 0; w0 < W; w0 += 64) {
@@ -66,6 +72,43 @@ __global__ __launch_bounds__(64) void kws_scan_events_kernel(const int32_t* __re
         }
     }
     if (lane == 0) ev_count[r] = count;
+}
+__global__ __launch_bounds__(64) void kws_scan_events_kernel(const int32_t* __restrict__ cand, const float* __restrict__ score, int W,
+                                                             int refractory, int32_t* __restrict__ ev_window, int32_t* __restrict__ ev_label,
+                                                             float* __restrict__ ev_score, int max_events, int32_t* __restrict__ ev_count) {
+    const int r = blockIdx.x, lane = threadIdx.x;
+    scan_events_walk(cand + (size_t)r * W, score + (size_t)r * W, W, refractory, ev_window, ev_label, ev_score, max_events, ev_count, r,
+                     lane);
+}
+
+// The same two steps over the packed windows of a ragged batch (kws_scan_detect_ragged_f32).  span[r] = (first packed window,
+// windows) of recording r, first windows ascending; a packed row between two recordings' windows belongs to nobody and is
+// passed over.  One thread per packed row finds its recording by a binary search; one wavefront per recording walks.
+__global__ __launch_bounds__(256) void kws_scan_smooth_ragged_kernel(const float* __restrict__ p, int n, const int2* __restrict__ span, int R,
+                                                                     int C, int S, int first_keyword, float threshold,
+                                                                     float* __restrict__ smoothed, int32_t* __restrict__ cand,
+                                                                     float* __restrict__ score) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;  // packed window
+    if (i >= n) return;
+    int lo = 0, hi = R;  // span[lo].x <= i < span[hi].x (a row before span[0].x lands on recording 0 with w < 0)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (span[mid].x <= i) lo = mid;
+        else hi = mid;
+    }
+    const int2 sp = span[lo];
+    const int w = i - sp.x;
+    if (w < 0 || w >= sp.y) return;
+    scan_smooth_window(p, i, w, C, S, first_keyword, threshold, smoothed, cand, score);
+}
+__global__ __launch_bounds__(64) void kws_scan_events_ragged_kernel(const int32_t* __restrict__ cand, const float* __restrict__ score,
+                                                                    const int2* __restrict__ span, int refractory,
+                                                                    int32_t* __restrict__ ev_window, int32_t* __restrict__ ev_label,
+                                                                    float* __restrict__ ev_score, int max_events,
+                                                                    int32_t* __restrict__ ev_count) {
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const int2 sp = span[r];
+    scan_events_walk(cand + sp.x, score + sp.x, sp.y, refractory, ev_window, ev_label, ev_score, max_events, ev_count, r, lane);
 }
 
 }  // namespace
@@ -157,6 +200,60 @@ int kws_scan_detect_f32(kws_ctx* c, const float* d_logits, int R, int W, int C, 
     HIP_TRY(c, launch_scan_detect(c->stream, prob, R, W, C, smooth_window, first_keyword, threshold, refractory, d_smoothed, cand, score,
                                   d_event_window, d_event_label, d_event_score, max_events, d_event_count));
     return KWS_OK;
+}
+
+int kws_scan_detect_ragged_f32(kws_ctx* c, const float* d_logits, const int32_t* win_off, const int32_t* windows, int R, int C,
+                               int smooth_window, int first_keyword, float threshold, int refractory, float* d_smoothed,
+                               int32_t* d_event_window, int32_t* d_event_label, float* d_event_score, int max_events,
+                               int32_t* d_event_count) {
+    KWS_GUARD_BEGIN
+    if (!c) return KWS_EINVAL;
+    if (!d_logits || !d_event_count || !win_off || !windows)
+        return fail(c, KWS_EINVAL, "kws_scan_detect_ragged_f32: d_logits / d_event_count / win_off / windows is NULL");
+    if (max_events < 0 || (max_events > 0 && (!d_event_window || !d_event_label || !d_event_score)))
+        return fail(c, KWS_EINVAL, "kws_scan_detect_ragged_f32: max_events events need their three arrays");
+    if (R < 1 || C < 1 || C > MAX_CLASSES) return fail(c, KWS_EINVAL, "kws_scan_detect_ragged_f32: need R >= 1 and C in [1, 64]");
+    if (R > (1 << 20)) return fail(c, KWS_EUNSUPPORTED, "kws_scan_detect_ragged_f32: more than 2^20 recordings in one call");
+    if (smooth_window < 1 || smooth_window > 256) return fail(c, KWS_EINVAL, "kws_scan_detect_ragged_f32: smooth_window must be in [1, 256]");
+    if (refractory < 1 || first_keyword < 0)
+        return fail(c, KWS_EINVAL, "kws_scan_detect_ragged_f32: need refractory >= 1 and first_keyword >= 0");
+    std::vector<int2> span(R);
+    long long end = 0, total = 0;  // the packed rows in use end here
+    for (int r = 0; r < R; ++r) {
+        if (windows[r] < 0 || win_off[r] < end)
+            return fail(c, KWS_EINVAL, "kws_scan_detect_ragged_f32: windows must not be negative and the recordings' windows must not overlap "
+                                       "(win_off ascending, win_off[r] >= win_off[r - 1] + windows[r - 1])");
+        span[r] = make_int2(win_off[r], windows[r]);
+        end = (long long)win_off[r] + windows[r];
+        total += windows[r];
+        if (end > (1ll << 30)) return fail(c, KWS_EUNSUPPORTED, "kws_scan_detect_ragged_f32: more than 2^30 packed windows in one call");
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (total == 0) {  // no recording has a window: every count is 0
+        HIP_TRY(c, hipMemsetAsync(d_event_count, 0, sizeof(int32_t) * (size_t)R, c->stream));
+        return KWS_OK;
+    }
+    // packed rows [first, end) hold every recording's windows; context scratch as kws_scan_detect_f32 lays it out, indexed by packed row
+    const int first = win_off[0];
+    const size_t n = (size_t)end;
+    int rc = grow_device_buffer(c, c->d_conv_ws, c->conv_ws_floats, n * C + 2 * n, "kws_scan_detect_ragged_f32", "workspace");
+    if (rc) return rc;
+    const int2* d_span = nullptr;
+    if ((rc = upload_ragged_tables(c, span.data(), sizeof(int2) * span.size(), "kws_scan_detect_ragged_f32", reinterpret_cast<const void**>(&d_span))))
+        return rc;
+    float* prob = c->d_conv_ws;
+    float* score = prob + n * C;
+    int32_t* cand = reinterpret_cast<int32_t*>(score + n);
+    const int rows = (int)(end - first);
+    HIP_TRY(c, launch_softmax(c->stream, d_logits + (size_t)first * C, rows, C, prob + (size_t)first * C));
+    hipLaunchKernelGGL(kws_scan_smooth_ragged_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, prob, (int)n, d_span, R, C,
+                       smooth_window, first_keyword, threshold, d_smoothed, cand, score);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(kws_scan_events_ragged_kernel, dim3(R), dim3(64), 0, c->stream, cand, score, d_span, refractory, d_event_window,
+                       d_event_label, d_event_score, max_events, d_event_count);
+    HIP_TRY(c, hipGetLastError());
+    return KWS_OK;
+    KWS_GUARD_END(c, "kws_scan_detect_ragged_f32")
 }
 
 }  // extern "C"

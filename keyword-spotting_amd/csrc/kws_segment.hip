@@ -33,14 +33,13 @@ __device__ __forceinline__ int voiced_in_window(const unsigned long long* words,
 // windows as popcounts over at most 17 words and the wavefront's answers leave as two ballot words:
 //   open_ok[f]  = ep_opens(c_on[f], on_window),  close_ok[f] = ep_closes(c_off[f], off_window).
 // ok: [R][2][n_words], n_words = ceil(F / 64); bits at or beyond F are zero.
-__global__ __launch_bounds__(SEG_THREADS) void kws_segment_flags_kernel(const float* __restrict__ feat, int F, int numcep, float threshold,
-                                                                        int on_window, int off_window, int back, int n_words,
-                                                                        int groups_per_rec, unsigned long long* __restrict__ ok) {
-    __shared__ unsigned long long words[SEG_BACK_WORDS + SEG_WORDS];
-    const int r = blockIdx.x / groups_per_rec, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int f0 = (blockIdx.x % groups_per_rec) * SEG_THREADS;
+// segment_flags_group: the work of one workgroup -- frames f0 .. f0 + 255 of the recording whose F frames start at fr and whose
+// two rows of n_words ballot words start at o (shared by the equal-length and the ragged kernel).
+__device__ __forceinline__ void segment_flags_group(const float* fr, int F, int numcep, float threshold, int on_window,
+                                                    int off_window, int back, int n_words, int f0, unsigned long long* o,
+                                                    unsigned long long* words) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int base = f0 - back * 64;  // the frame of bit 0 of words[0]; may be negative
-    const float* fr = feat + (size_t)r * F * numcep;
     for (int j = wave; j < back + SEG_WORDS; j += SEG_WORDS) {  // wave-uniform
         const int g = base + j * 64 + lane;
         const bool voiced = g >= 0 && g < F && ep_voiced(fr[(size_t)g * numcep], threshold);
@@ -56,10 +55,39 @@ __global__ __launch_bounds__(SEG_THREADS) void kws_segment_flags_kernel(const fl
     const unsigned long long close_ok = __ballot(f < F && ep_closes(c_off, off_window));
     const int w = f0 / 64 + wave;
     if (lane == 0 && w < n_words) {
-        unsigned long long* o = ok + (size_t)r * 2 * n_words;
         o[w] = open_ok;
         o[n_words + w] = close_ok;
     }
+}
+__global__ __launch_bounds__(SEG_THREADS) void kws_segment_flags_kernel(const float* __restrict__ feat, int F, int numcep, float threshold,
+                                                                        int on_window, int off_window, int back, int n_words,
+                                                                        int groups_per_rec, unsigned long long* __restrict__ ok) {
+    __shared__ unsigned long long words[SEG_BACK_WORDS + SEG_WORDS];
+    const int r = blockIdx.x / groups_per_rec;
+    segment_flags_group(feat + (size_t)r * F * numcep, F, numcep, threshold, on_window, off_window, back, n_words,
+                        (blockIdx.x % groups_per_rec) * SEG_THREADS, ok + (size_t)r * 2 * n_words, words);
+}
+
+// A recording of a ragged batch as the two kernels see it (kws_segment_ragged_f32): rows [frame_off, frame_off + frames) of the
+// packed frame array, len samples, its ballot words at ok + 2 * word_off, its workgroups [group_off, next record's group_off) of
+// the flag launch.  R + 1 records; the last one closes the group table.
+struct SegRec {
+    int frame_off, frames, len, word_off, group_off;
+};
+__global__ __launch_bounds__(SEG_THREADS) void kws_segment_flags_ragged_kernel(const float* __restrict__ feat, const SegRec* __restrict__ rec,
+                                                                               int R, int numcep, float threshold, int on_window,
+                                                                               int off_window, int back, unsigned long long* __restrict__ ok) {
+    __shared__ unsigned long long words[SEG_BACK_WORDS + SEG_WORDS];
+    const int g = blockIdx.x;
+    int lo = 0, hi = R;  // rec[lo].group_off <= g < rec[hi].group_off (workgroup-uniform)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (rec[mid].group_off <= g) lo = mid;
+        else hi = mid;
+    }
+    const SegRec rr = rec[lo];
+    segment_flags_group(feat + (size_t)rr.frame_off * numcep, rr.frames, numcep, threshold, on_window, off_window, back,
+                        (rr.frames + 63) / 64, (g - rr.group_off) * SEG_THREADS, ok + 2 * (size_t)rr.word_off, words);
 }
 
 // The walk, one wavefront per recording.  Every lane holds one open_ok and one close_ok word of a chunk of 64 words (4096
@@ -67,11 +95,10 @@ __global__ __launch_bounds__(SEG_THREADS) void kws_segment_flags_kernel(const fl
 // open + max_frames - 1"; words without a bit are passed over through a ballot of the non-empty lanes, so a chunk costs a few
 // steps per utterance, not one per word.  f moves forward in every iteration, so the loop ends for any input.  Everything is
 // wave-uniform; lane 0 stores.  utt: [R][max_utts][5] = (start_sample, end_sample, open, close, reason).
-__global__ __launch_bounds__(64) void kws_segment_walk_kernel(const unsigned long long* __restrict__ ok, int F, int n_words, int n_total,
-                                                              int frame_len, int frame_step, int pre_roll, int max_frames,
-                                                              int32_t* __restrict__ utt, int max_utts, int32_t* __restrict__ count_out) {
-    const int r = blockIdx.x, lane = threadIdx.x;
-    const unsigned long long* o = ok + (size_t)r * 2 * n_words;
+// segment_walk: the walk of recording r, whose ballot words start at o (shared by the equal-length and the ragged kernel).
+__device__ __forceinline__ void segment_walk(const unsigned long long* o, int F, int n_words, int n_total, int frame_len,
+                                             int frame_step, int pre_roll, int max_frames, int32_t* utt, int max_utts,
+                                             int32_t* count_out, int r, int lane) {
     int32_t* ur = utt + (size_t)r * max_utts * 5;
     bool triggered = false;
     int open = 0, prev_close = -1, count = 0;
@@ -136,6 +163,21 @@ __global__ __launch_bounds__(64) void kws_segment_walk_kernel(const unsigned lon
     if (triggered) close_at(F - 1, 2);  // the recording ended inside an utterance
     if (lane == 0) count_out[r] = count;
 }
+__global__ __launch_bounds__(64) void kws_segment_walk_kernel(const unsigned long long* __restrict__ ok, int F, int n_words, int n_total,
+                                                              int frame_len, int frame_step, int pre_roll, int max_frames,
+                                                              int32_t* __restrict__ utt, int max_utts, int32_t* __restrict__ count_out) {
+    const int r = blockIdx.x, lane = threadIdx.x;
+    segment_walk(ok + (size_t)r * 2 * n_words, F, n_words, n_total, frame_len, frame_step, pre_roll, max_frames, utt, max_utts, count_out, r,
+                 lane);
+}
+__global__ __launch_bounds__(64) void kws_segment_walk_ragged_kernel(const unsigned long long* __restrict__ ok, const SegRec* __restrict__ rec,
+                                                                     int frame_len, int frame_step, int pre_roll, int max_frames,
+                                                                     int32_t* __restrict__ utt, int max_utts, int32_t* __restrict__ count_out) {
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const SegRec rr = rec[r];
+    segment_walk(ok + 2 * (size_t)rr.word_off, rr.frames, (rr.frames + 63) / 64, rr.len, frame_len, frame_step, pre_roll, max_frames, utt,
+                 max_utts, count_out, r, lane);
+}
 
 // normalize then fix_length (ep_cut_clip) of one span per workgroup.  A span starts at any sample: 2-byte loads.
 __global__ __launch_bounds__(CUT_THREADS) void kws_cut_i16_kernel(const int16_t* __restrict__ pcm, int R, int n_total,
@@ -199,6 +241,54 @@ int kws_segment_f32(kws_ctx* c, const float* d_feat, int R, int F_total, int n_t
                        c->fp.frame_step, pre_roll, max_frames, d_utt, max_utts, d_count);
     HIP_TRY(c, hipGetLastError());
     return KWS_OK;
+}
+
+int kws_segment_ragged_f32(kws_ctx* c, const float* d_feat, const int32_t* frame_off, const int32_t* frames, const int32_t* len, int R,
+                           float log_energy_threshold, int on_window, int off_window, int pre_roll, int max_frames, int32_t* d_utt,
+                           int max_utts, int32_t* d_count) {
+    KWS_GUARD_BEGIN
+    if (!c) return KWS_EINVAL;
+    if (!d_feat || !d_count || !frame_off || !frames || !len)
+        return fail(c, KWS_EINVAL, "kws_segment_ragged_f32: d_feat / d_count / frame_off / frames / len is NULL");
+    if (R < 1) return fail(c, KWS_EINVAL, "kws_segment_ragged_f32: R must be positive");
+    if (R > (1 << 20)) return fail(c, KWS_EUNSUPPORTED, "kws_segment_ragged_f32: more than 2^20 recordings in one call");
+    int rc = check_endpoint_windows(c, "kws_segment_ragged_f32", on_window, off_window);
+    if (rc) return rc;
+    if (pre_roll < 0 || (max_frames != 0 && max_frames < 2))
+        return fail(c, KWS_EINVAL, "kws_segment_ragged_f32: need pre_roll >= 0 and max_frames == 0 or >= 2");
+    if (max_utts < 0 || (max_utts > 0 && !d_utt)) return fail(c, KWS_EINVAL, "kws_segment_ragged_f32: max_utts utterances need d_utt");
+    if (!c->fe_ready) return fail(c, KWS_ESTATE, "kws_segment_ragged_f32: front end not configured");
+    if ((rc = check_append_energy(c, "kws_segment_ragged_f32"))) return rc;
+    std::vector<SegRec> rec(R + 1);
+    long long words = 0, groups = 0, rows_end = 0;
+    for (int r = 0; r < R; ++r) {
+        if (frames[r] < 1 || len[r] < 1 || frame_off[r] < rows_end)
+            return fail(c, KWS_EINVAL, "kws_segment_ragged_f32: frames and len must be positive and the recordings' rows must not overlap "
+                                       "(frame_off ascending)");
+        rows_end = (long long)frame_off[r] + frames[r];
+        if (rows_end > (1ll << 28)) return fail(c, KWS_EUNSUPPORTED, "kws_segment_ragged_f32: more than 2^28 rows in the packed frame array");
+        rec[r] = {frame_off[r], frames[r], len[r], (int)words, (int)groups};
+        words += (frames[r] + 63) / 64;
+        groups += (frames[r] + SEG_THREADS - 1) / SEG_THREADS;
+    }
+    rec[R] = {0, 0, 0, (int)words, (int)groups};
+    HIP_TRY(c, hipSetDevice(c->device));
+    // context scratch: per recording open_ok and close_ok as ballot words, [2][n_words_r] of 64 bits, one recording after another
+    rc = grow_device_buffer(c, c->d_conv_ws, c->conv_ws_floats, (size_t)words * 2 * 2, "kws_segment_ragged_f32", "workspace");
+    if (rc) return rc;
+    const SegRec* d_rec = nullptr;
+    if ((rc = upload_ragged_tables(c, rec.data(), sizeof(SegRec) * rec.size(), "kws_segment_ragged_f32", reinterpret_cast<const void**>(&d_rec))))
+        return rc;
+    unsigned long long* ok = reinterpret_cast<unsigned long long*>(c->d_conv_ws);
+    const int back = (off_window - 1 + 63) / 64;
+    hipLaunchKernelGGL(kws_segment_flags_ragged_kernel, dim3((unsigned)groups), dim3(SEG_THREADS), 0, c->stream, d_feat, d_rec, R,
+                       c->fp.numcep, log_energy_threshold, on_window, off_window, back, ok);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(kws_segment_walk_ragged_kernel, dim3(R), dim3(64), 0, c->stream, ok, d_rec, c->fp.frame_len, c->fp.frame_step, pre_roll,
+                       max_frames, d_utt, max_utts, d_count);
+    HIP_TRY(c, hipGetLastError());
+    return KWS_OK;
+    KWS_GUARD_END(c, "kws_segment_ragged_f32")
 }
 
 int kws_cut_i16(kws_ctx* c, const int16_t* d_pcm, int R, int n_total, const int32_t* d_span, int U, int normalize_to, int16_t* d_clips,

@@ -34,6 +34,7 @@ PW_DEFAULT = PW_PAIR_F16
 
 _c_ctx = C.c_void_p
 _i16p, _f32p, _i32p = C.c_void_p, C.c_void_p, C.c_void_p  # device pointers travel as integers
+_h_i32p, _h_i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)  # host tables of the ragged entries
 
 # name -> (restype, argtypes): every symbol include/kws_hip.h declares
 SIGNATURES = {
@@ -99,6 +100,12 @@ SIGNATURES = {
     "kws_segment_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, C.c_int,
                                   _i32p]),
     "kws_cut_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _i16p, C.c_int, _i32p]),
+    "kws_frames_ragged_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, _h_i64p, _h_i32p, C.c_int, C.c_int, _f32p]),
+    "kws_scan_ragged_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, _h_i64p, _h_i32p, C.c_int, C.c_int, _f32p, _i32p, _f32p]),
+    "kws_scan_detect_ragged_f32": (C.c_int, [_c_ctx, _f32p, _h_i32p, _h_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _f32p,
+                                             _i32p, _i32p, _f32p, C.c_int, _i32p]),
+    "kws_segment_ragged_f32": (C.c_int, [_c_ctx, _f32p, _h_i32p, _h_i32p, _h_i32p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         _i32p, C.c_int, _i32p]),
     "kws_host_stream_utt_history": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int)]),
     "kws_stream_utt_open": (C.c_int, [_c_ctx, C.c_float] + [C.c_int] * 6),
     "kws_stream_utt_close": (C.c_int, [_c_ctx]),
@@ -145,6 +152,8 @@ SIGNATURES = {
     "kws_host_cnn_trad_image": (C.c_int, [C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_uint32), C.c_size_t,
                                           C.POINTER(C.c_size_t), C.POINTER(C.c_float)]),
     "kws_host_scan_shape": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "kws_host_ragged_plan": (C.c_int, [_h_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _h_i32p, _h_i32p, _h_i32p, _h_i32p,
+                                       C.POINTER(C.c_int)]),
     "kws_host_resample_len": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "kws_host_resample_design": (C.c_int, [C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4 + [C.POINTER(C.c_double), C.c_size_t,
                                            C.POINTER(C.c_size_t)]),
@@ -479,6 +488,45 @@ class Context:
                                           int(normalize_to), _ptr(clips), int(clips.shape[1]), _ptr(peak) if peak is not None else None),
                     AudioProcessingError)
 
+    # -- batches of recordings of unequal length ---------------------------------------------------
+    def frames_ragged_i16(self, pcm, start, length, row_multiple, feat):
+        """``kws_frames_ragged_i16``: ``pcm`` int16 (any shape, contiguous) on the device holds recording r at samples
+        ``[start[r], start[r] + length[r])`` (host sequences; starts multiples of 8) -> ``feat`` float32 [F_pack, numcep], every
+        recording's rows rounded up to ``row_multiple`` (``host_ragged_plan(length, hop_frames=row_multiple)`` gives the rows)."""
+        st, ln = _host_i64(start), _host_i32(length)
+        self._check(self._lib.kws_frames_ragged_i16(self._h, _ptr(pcm), int(pcm.numel()), _as(st, C.c_int64), _as(ln, C.c_int32), len(ln),
+                                                    int(row_multiple), _ptr(feat)), AudioProcessingError)
+
+    def scan_ragged_i16(self, pcm, start, length, hop_frames, logits, label=None, feat=None):
+        """``kws_scan_ragged_i16``: the ragged front end, then the DS-CNN over the packed frame array as one recording ->
+        ``logits`` float32 [W_pack, C] (``label`` int32 [W_pack]); window w of recording r is row ``win_off[r] + w``."""
+        p = lambda t: _ptr(t) if t is not None else None
+        st, ln = _host_i64(start), _host_i32(length)
+        self._check(self._lib.kws_scan_ragged_i16(self._h, _ptr(pcm), int(pcm.numel()), _as(st, C.c_int64), _as(ln, C.c_int32), len(ln),
+                                                  int(hop_frames), _ptr(logits), p(label), p(feat)), ModelError)
+
+    def scan_detect_ragged_f32(self, logits, win_off, windows, smooth_window, first_keyword, threshold, refractory, event_count,
+                               event_window=None, event_label=None, event_score=None, max_events=0, smoothed=None):
+        """``kws_scan_detect_ragged_f32``: ``logits`` float32 [W_pack, C]; ``win_off`` / ``windows`` host sequences [R]; the
+        decisions of ``scan_detect_f32`` per recording.  ``event_count`` int32 [R]; the event arrays [R, max_events]."""
+        p = lambda t: _ptr(t) if t is not None else None
+        wo, wn = _host_i32(win_off), _host_i32(windows)
+        self._check(self._lib.kws_scan_detect_ragged_f32(self._h, _ptr(logits), _as(wo, C.c_int32), _as(wn, C.c_int32), len(wn),
+                                                         int(logits.shape[-1]), int(smooth_window), int(first_keyword), float(threshold),
+                                                         int(refractory), p(smoothed), p(event_window), p(event_label), p(event_score),
+                                                         int(max_events), _ptr(event_count)), ModelError)
+
+    def segment_ragged_f32(self, feat, frame_off, frames, length, threshold, count, utt=None, max_utts=0, on_window=40, off_window=80,
+                           pre_roll=60, max_frames=1000):
+        """``kws_segment_ragged_f32``: the endpointer of ``segment_f32`` per recording of the packed ``feat`` float32
+        [F_pack, numcep]; ``frame_off`` / ``frames`` / ``length`` host sequences [R].  ``count`` int32 [R]; ``utt`` int32
+        [R, max_utts, 5] with spans relative to each recording's own start."""
+        fo, fr, ln = _host_i32(frame_off)[:len(frames)], _host_i32(frames), _host_i32(length)
+        self._check(self._lib.kws_segment_ragged_f32(self._h, _ptr(feat), _as(np.ascontiguousarray(fo), C.c_int32), _as(fr, C.c_int32),
+                                                     _as(ln, C.c_int32), len(ln), float(threshold), int(on_window), int(off_window),
+                                                     int(pre_roll), int(max_frames), _ptr(utt) if utt is not None else None, int(max_utts),
+                                                     _ptr(count)), ModelError)
+
     # -- live utterances ---------------------------------------------------------------------------
     def stream_utt_open(self, threshold, on_window, off_window, pre_roll, max_frames, history_samples, max_events):
         """``kws_stream_utt_open``: arm the open stream set -- every push then appends its hop to a per-stream history, walks
@@ -785,6 +833,35 @@ def host_scan_shape(n_total, frame_len=400, frame_step=160, window_frames=99, ho
     if rc != KWS_OK:
         raise KWSError(f"kws_host_scan_shape failed ({rc}): sizes must be positive")
     return int(frames.value), int(windows.value)
+
+
+def _host_i32(v) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(v, dtype=np.int32).reshape(-1))
+
+
+def _host_i64(v) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(v, dtype=np.int64).reshape(-1))
+
+
+def _as(a: np.ndarray, ctype):
+    return a.ctypes.data_as(C.POINTER(ctype))
+
+
+def host_ragged_plan(lengths, frame_len=400, frame_step=160, window_frames=99, hop_frames=1):
+    """The plan of a ragged batch (``kws_host_ragged_plan``): ``(frames [R], frame_off [R + 1], windows [R], win_off [R], W_pack)``
+    as int32 arrays and an int -- each recording's frames and windows as ``host_scan_shape`` gives them, its first row in the
+    packed frame array (rows rounded up to ``hop_frames``; ``frame_off[R]`` = F_pack) and its first packed window."""
+    ln = _host_i32(lengths)
+    R = len(ln)
+    frames, frame_off = np.zeros(R, np.int32), np.zeros(R + 1, np.int32)
+    windows, win_off, w_pack = np.zeros(R, np.int32), np.zeros(R, np.int32), C.c_int(0)
+    rc = lib().kws_host_ragged_plan(_as(ln, C.c_int32), R, int(frame_len), int(frame_step), int(window_frames), int(hop_frames),
+                                    _as(frames, C.c_int32), _as(frame_off, C.c_int32), _as(windows, C.c_int32), _as(win_off, C.c_int32),
+                                    C.byref(w_pack))
+    if rc != KWS_OK:
+        raise KWSError(f"kws_host_ragged_plan failed ({rc}): need R >= 1, lengths >= 1 and positive sizes, at most 2^20 recordings "
+                       "and 2^28 packed rows")
+    return frames, frame_off, windows, win_off, int(w_pack.value)
 
 
 def host_stream_utt_history(frame_len=400, frame_step=160, pre_roll=60, max_frames=1000, slack_hops=8) -> int:

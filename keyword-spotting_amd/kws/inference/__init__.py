@@ -404,6 +404,223 @@ class KeywordSpotter:
             raise AudioProcessingError(f"{path}: {x.shape[1]} channels; segment_file takes mono files")
         return self.segment(x, **kwargs)[0]
 
+    # -- batches of recordings of unequal length ---------------------------------------------------------------------------
+    def _batch_recordings(self, recordings, sample_rate, what: str) -> Tuple[List[torch.Tensor], List[int]]:
+        """The argument checks of ``scan_batch`` / ``segment_batch`` (no device needed): a non-empty sequence of int16 ``[n_r]``
+        host arrays or tensors, none of them empty, and one rate or one rate per recording -> (1-D int16 tensors, rates)."""
+        if torch.is_tensor(recordings) or isinstance(recordings, np.ndarray):
+            recordings = list(recordings) if recordings.ndim == 2 else [recordings]
+        recs = list(recordings)
+        if not recs:
+            raise ModelError(f"{what}: no recordings were given")
+        out = []
+        for r, rec in enumerate(recs):
+            try:
+                x = self._recordings(rec, what)
+            except ModelError as e:
+                raise ModelError(f"{what}: recording {r}: {e.args[0]}") from None
+            if x.shape[0] != 1:
+                raise ModelError(f"{what}: recording {r} must be one int16 [n] array, got shape {tuple(x.shape)}")
+            if x.shape[1] < 1:
+                raise ModelError(f"{what}: recording {r} is empty")
+            out.append(x[0])
+        cfg = self.config
+        if sample_rate is None or np.ndim(sample_rate) == 0:
+            rates = [cfg.sample_rate if sample_rate is None else int(sample_rate)] * len(out)
+        else:
+            rates = [cfg.sample_rate if s is None else int(s) for s in sample_rate]
+            if len(rates) != len(out):
+                raise ModelError(f"{what}: {len(rates)} sample rates for {len(out)} recordings")
+        if any(s < 1 for s in rates):
+            raise ModelError(f"{what}: sample rates must be positive")
+        return out, rates
+
+    def _pack_batch(self, recs: List[torch.Tensor], rates: List[int]):
+        """Recordings -> ONE int16 device buffer at the configured rate: ``(buffer [n_pcm], start int64 [R], length int32 [R])``.
+        Recordings at the configured rate are packed one after another, each start rounded up to 8 samples.  The others are
+        grouped by rate; a group is padded to its longest, resampled with its true lengths in one launch (``kws_resample_i16``
+        with ``d_len``) straight into a rectangular block of the buffer whose rows are the group's recordings -- the natural
+        length of each (``kws_host_resample_len``) is its length."""
+        from kws import _native
+
+        cfg = self.config
+        R = len(recs)
+        up8 = lambda n: (int(n) + 7) & ~7
+        length = np.zeros(R, np.int32)
+        start = np.zeros(R, np.int64)
+        groups: dict = {}
+        at = 0
+        for r, (x, rate) in enumerate(zip(recs, rates)):
+            if rate == cfg.sample_rate:
+                length[r], start[r] = x.shape[0], at
+                at += up8(x.shape[0])
+            else:
+                length[r] = _native.host_resample_len(int(x.shape[0]), rate, cfg.sample_rate)
+                if length[r] < 1:
+                    raise ModelError(f"recording {r} is empty at the configured rate")
+                groups.setdefault(rate, []).append(r)
+        blocks = []
+        for rate, members in groups.items():
+            n_out = up8(max(int(length[r]) for r in members))
+            for i, r in enumerate(members):
+                start[r] = at + i * n_out
+            blocks.append((rate, members, at, n_out))
+            at += len(members) * n_out
+        buf = torch.empty((max(at, 8),), dtype=torch.int16, device=self.device)
+        native = [r for r in range(R) if rates[r] == cfg.sample_rate]
+        if native and not any(recs[r].is_cuda for r in native):  # host recordings: packed on the host, one upload
+            last = native[-1]
+            host = np.zeros(int(start[last]) + up8(int(length[last])), np.int16)
+            for r in native:
+                host[int(start[r]):int(start[r]) + int(length[r])] = recs[r].numpy()
+            buf[:host.shape[0]].copy_(torch.from_numpy(host))
+        else:
+            for r in native:
+                buf[int(start[r]):int(start[r]) + int(length[r])].copy_(recs[r])
+        ctx = self.model._context(self.device.index or 0)
+        for rate, members, first, n_out in blocks:
+            n_in = max(int(recs[r].shape[0]) for r in members)
+            src = torch.zeros((len(members), n_in), dtype=torch.int16, device=self.device)
+            for i, r in enumerate(members):
+                src[i, :recs[r].shape[0]].copy_(recs[r])
+            lengths = torch.tensor([int(recs[r].shape[0]) for r in members], dtype=torch.int32, device=self.device)
+            torch.cuda.current_stream(self.device).synchronize()  # a context may run on its own stream
+            ctx.resample_i16(src, rate, cfg.sample_rate, buf[first:first + len(members) * n_out].view(len(members), n_out), lengths)
+        torch.cuda.current_stream(self.device).synchronize()
+        return buf, start, length
+
+    def scan_batch(self, recordings, hop_frames: int = 1, smooth_window: int = 1, threshold: Optional[float] = None, refractory: int = 50,
+                   first_keyword: int = 2, max_events: int = 1024, sample_rate=None) -> List[ScanResult]:
+        """``scan`` for a batch of recordings of unequal length in one pass: ``recordings`` is a sequence of int16 ``[n_r]`` host
+        arrays or device tensors, ``sample_rate`` one rate or one rate per recording (``None``: the configured one).  Element
+        ``r`` of the result equals ``scan(recordings[r], ...)`` in every field -- labels ``[1, W_r]``, logits ``[1, W_r, C]``,
+        window start times, events -- bit for bit, except that a recording shorter than one window gives a result with zero
+        windows instead of raising.  An empty recording raises ``ModelError`` naming its index.
+
+        On the device: the recordings in one buffer (``_pack_batch``), the front end over all of them in one launch and the model
+        over the packed frame array as one recording (``kws_scan_ragged_i16``), the decisions per recording
+        (``kws_scan_detect_ragged_f32``).  The windows that straddle two recordings are computed and dropped."""
+        from kws import _native
+
+        recs, rates = self._batch_recordings(recordings, sample_rate, "scan_batch")
+        if int(hop_frames) < 1:
+            raise ModelError("scan_batch: hop_frames must be at least 1")
+        if threshold is not None:
+            if not 1 <= int(smooth_window) <= 256:
+                raise ModelError("scan_batch: smooth_window must be in [1, 256]")
+            if int(refractory) < 1 or int(first_keyword) < 0 or int(max_events) < 0:
+                raise ModelError("scan_batch: need refractory >= 1, first_keyword >= 0 and max_events >= 0")
+        cfg = self.config
+        frame_len, frame_step = _round_half_up(cfg.frame_length * cfg.sample_rate), _round_half_up(cfg.frame_step * cfg.sample_rate)
+        buf, start, length = self._pack_batch(recs, rates)
+        R, C, hop = len(recs), self.model.num_classes, int(hop_frames)
+        _, _, windows, win_off, W_pack = _native.host_ragged_plan(length, frame_len, frame_step, WINDOW_FRAMES, hop)
+        ctx = self.model._context(self.device.index or 0)
+        logits = torch.empty((max(W_pack, 1), C), dtype=torch.float32, device=self.device)
+        labels = torch.empty((max(W_pack, 1),), dtype=torch.int32, device=self.device)
+        ctx.scan_ragged_i16(buf, start, length, hop, logits, labels)
+        ev = None
+        if threshold is not None:
+            m = int(max_events)
+            count = torch.empty((R,), dtype=torch.int32, device=self.device)
+            ev_w = torch.empty((R, m), dtype=torch.int32, device=self.device)
+            ev_k = torch.empty((R, m), dtype=torch.int32, device=self.device)
+            ev_s = torch.empty((R, m), dtype=torch.float32, device=self.device)
+            ctx.scan_detect_ragged_f32(logits, win_off, windows, smooth_window, first_keyword, threshold, refractory, count,
+                                       ev_w if m else None, ev_k if m else None, ev_s if m else None, m)
+            ctx.sync()
+            ev = (count.cpu().numpy(), ev_w.cpu().numpy(), ev_k.cpu().numpy(), ev_s.cpu().numpy(), m)
+        ctx.sync()
+        labels_h, logits_h = labels.cpu().numpy(), logits.cpu().numpy()
+        out = []
+        for r in range(R):
+            W, o = int(windows[r]), int(win_off[r])
+            start_s, end_s = scan_window_times(W, hop, frame_len, frame_step, cfg.sample_rate, WINDOW_FRAMES, int(length[r]))
+            events = None
+            if ev is not None:
+                count, ev_w, ev_k, ev_s, m = ev
+                events = [[(float(end_s[ev_w[r, i]]), int(ev_k[r, i]), self.words[int(ev_k[r, i])], float(ev_s[r, i]))
+                           for i in range(min(int(count[r]), m))]]
+            out.append(ScanResult(labels_h[o:o + W][None, :].copy(), logits_h[o:o + W][None, :, :].copy(), start_s, events))
+        return out
+
+    def segment_batch(self, recordings, threshold: float, on_window: int = 40, off_window: int = 80, pre_roll: int = 60,
+                      max_seconds: float = 10.0, normalize: int = 16384, max_utterances: int = 1024, sample_rate=None,
+                      keep_unfinished: bool = True) -> List[List[Utterance]]:
+        """``segment`` for a batch of recordings of unequal length in one pass (``recordings`` and ``sample_rate`` as
+        ``scan_batch``).  Element ``r`` equals ``segment(recordings[r], ...)[0]`` with ``Utterance.recording = r``.
+
+        On the device: the recordings in one buffer, their frames in one launch (``kws_frames_ragged_i16``), the endpointer per
+        recording (``kws_segment_ragged_f32``), then the ONE device-to-host read of counts and spans, the cut over the whole
+        buffer as one recording with each recording's start added to its spans (``kws_cut_i16``) and the model once per clip."""
+        from kws import _native
+
+        recs, rates = self._batch_recordings(recordings, sample_rate, "segment_batch")
+        if not 1 <= int(on_window) <= int(off_window) <= 1024:
+            raise ModelError("segment_batch: need 1 <= on_window <= off_window <= 1024")
+        if int(pre_roll) < 0 or int(max_utterances) < 0 or not 0 <= int(normalize) <= 32767:
+            raise ModelError("segment_batch: need pre_roll >= 0, max_utterances >= 0 and normalize in [0, 32767]")
+        cfg = self.config
+        frame_len, frame_step = _round_half_up(cfg.frame_length * cfg.sample_rate), _round_half_up(cfg.frame_step * cfg.sample_rate)
+        max_frames = int(round(float(max_seconds) * cfg.sample_rate / frame_step))
+        if max_frames == 1 or max_frames < 0:
+            raise ModelError("segment_batch: max_seconds must be 0 (no limit) or at least two frames")
+        buf, start, length = self._pack_batch(recs, rates)
+        R, m = len(recs), int(max_utterances)
+        frames, frame_off, _, _, _ = _native.host_ragged_plan(length, frame_len, frame_step, WINDOW_FRAMES, 1)
+        ctx = self.model._context(self.device.index or 0)
+        feat = torch.empty((int(frame_off[R]), cfg.num_cepstral_coeffs), dtype=torch.float32, device=self.device)
+        found = torch.empty((R + 5 * R * m,), dtype=torch.int32, device=self.device)  # the counts [R], then the slots [R, m, 5]
+        ctx.frames_ragged_i16(buf, start, length, 1, feat)
+        ctx.segment_ragged_f32(feat, frame_off, frames, length, threshold, found[:R], found[R:] if m else None, m, on_window, off_window,
+                               pre_roll, max_frames)
+        ctx.sync()
+        host = found.cpu().numpy()  # the one device-to-host read: counts and spans together
+        counts, slots = host[:R], host[R:].reshape(R, m, 5)
+        rows = []
+        for r in range(R):
+            for i in range(min(int(counts[r]), m)):
+                s, e, opened, closed, reason = (int(v) for v in slots[r, i])
+                if reason == 2 and not keep_unfinished:
+                    continue
+                rows.append((r, s, e, opened, closed, reason))
+        out: List[List[Utterance]] = [[] for _ in range(R)]
+        if not rows:
+            return out
+        # the whole buffer as ONE recording: a span of recording r lies start[r] samples on
+        span = torch.tensor([(0, int(start[r]) + s, int(start[r]) + e) for r, s, e, _, _, _ in rows], dtype=torch.int32).to(self.device)
+        for utt in _classify_spans(ctx, self.device, self.words, self.model.num_classes, cfg.desired_samples, float(cfg.sample_rate), frame_step,
+                                   rows, lambda clips, peaks: ctx.cut_i16(buf[None, :], span, clips, int(normalize), peaks)):
+            out[utt.recording].append(utt)
+        return out
+
+    def _decode_file(self, path: str, resample: bool, what: str) -> Tuple[np.ndarray, int]:
+        """One wav file under the decode rules and error messages of ``scan_file`` / ``segment_file`` -> (int16 [n], rate)."""
+        if resample:
+            x, rate = read_wav(path)
+            if rate != self.config.sample_rate:
+                if x.dtype != np.int16:
+                    tail = " (there is no float32 scan)" if what == "scan_file" else ""
+                    raise AudioProcessingError(f"{path}: sample rate {rate} != {self.config.sample_rate} and the file is not 16-bit mono "
+                                               f"PCM; the device resampler of {what} takes int16 only{tail}")
+                return x, int(rate)
+        x = load_pcm16(path, self.config.sample_rate)
+        if x.ndim == 2:
+            raise AudioProcessingError(f"{path}: {x.shape[1]} channels; {what} takes mono files")
+        return x, self.config.sample_rate
+
+    def scan_files(self, paths: Sequence[str], resample: bool = False, **kwargs) -> List[ScanResult]:
+        """``scan_batch`` over whole wav files, one result per path: each file is decoded under the rules of ``scan_file`` (16-bit
+        mono PCM at the configured rate; with ``resample=True`` also 16-bit mono at another rate).  Files at other rates are
+        grouped by rate, resampled on the device with one launch per group, and scanned with the rest in one pass."""
+        decoded = [self._decode_file(p, resample, "scan_file") for p in paths]
+        return self.scan_batch([x for x, _ in decoded], sample_rate=[rate for _, rate in decoded], **kwargs)
+
+    def segment_files(self, paths: Sequence[str], resample: bool = False, **kwargs) -> List[List[Utterance]]:
+        """``segment_batch`` over whole wav files, one list of utterances per path (decode rules of ``segment_file``)."""
+        decoded = [self._decode_file(p, resample, "segment_file") for p in paths]
+        return self.segment_batch([x for x, _ in decoded], sample_rate=[rate for _, rate in decoded], **kwargs)
+
 
 _default: Optional[KeywordSpotter] = None
 
