@@ -665,6 +665,60 @@ int kws_stream_utt_read(kws_ctx* ctx, uint64_t first_seq, int n, int64_t* out_re
  * KWS_ESTATE.  Asynchronous, deterministic, not timed by kws_prof_*. */
 int kws_stream_utt_cut_i16(kws_ctx* ctx, uint64_t first_seq, int U, int normalize_to, int16_t* d_clips, int n_out, int32_t* d_peak);
 
+/* ---- live keyword events (the decision layer of kws_scan_detect_f32 for the streams of kws_stream_open: one decision per
+ * push, "keyword k fired on stream s at hop h" in a queue the host reads without a copy) -------------------------------------- */
+
+/* Arm the open stream set for detection: from here to kws_stream_detect_close (or kws_stream_open / kws_stream_close /
+ * kws_set_frontend, which drop it with the streams) every push that asks for logits -- kws_stream_push_i16,
+ * kws_stream_push_host_i16, kws_stream_push_rate_i16, kws_stream_push_host_rate_i16 -- enqueues ONE more launch behind its own
+ * (with use_graph: behind the replay, outside the captured graph): the decision step, one workgroup, fed with that push's
+ * d_logits [n_streams, C].  A push's logits and labels are the bits of an unarmed push; an unarmed context launches nothing new.
+ *   The rules are kws_scan_detect_f32's, with stream s as recording s and decision d as window d; decisions count d = 0, 1, ...
+ *   from this call.  (1) p = the softmax of the stream's logits (the bits of kws_softmax_f32), stored at slot d mod smooth_window
+ *   of a ring float32 [n_streams, smooth_window, C].  (2) s[c] = the sum of the last min(smooth_window, d + 1) posteriors,
+ *   oldest first, in float32, divided by their number as a float: a direct sum at every decision, no running sum -- the bits
+ *   of kws_scan_detect_f32's d_smoothed for the same logits (kws_stream_smooth_f32 keeps a running sum and gives other bits).
+ *   (3) k = the first argmax of s; the stream is a candidate when k >= first_keyword and s[k] >= threshold (a NaN row is none);
+ *   a candidate with d >= next[s] is an EVENT and sets next[s] = d + refractory (next starts at 0).  (4) EMIT: the streams that
+ *   fired at this step get consecutive sequence numbers in ascending stream order (wavefront ballots and a prefix over the
+ *   wavefronts; no atomics: the same bits run to run).  A record is int64 [5] = (stream, d, h, label k, score), the score being
+ *   the bits of the float s[k] in the low 32 bits; h is the context's hop count (kws_stream_state's hops, from 1) of the push
+ *   that decided, d for explicit steps.  Records are written at seq mod max_events to a device queue and to its mirror in
+ *   pinned, device-mapped host memory (system-scope stores; the totals and then a completion count are published behind them,
+ *   as kws_stream_utt_open describes).  The queue keeps the newest max_events records; older ones are overwritten.
+ *   first_hop: a push whose hop count h is below first_hop decides nothing and advances nothing.  With first_hop = num_frames +
+ *   K - 1 (K = ceil(frame_len / frame_step)) the windows that still hold zero rows are skipped, and decision d of a set armed
+ *   right after kws_stream_open is window d of kws_scan_i16 at hop_frames = 1; with 0 every push decides.
+ *   A push WITHOUT logits on an armed context, a push on a set that kws_stream_detect_step_f32 has stepped, and a push whose
+ *   model has another class count than C are refused (KWS_ESTATE, KWS_ESTATE, KWS_EINVAL) -- behind the push's own launches:
+ *   the hop has been taken, no decision is made.
+ *   Needs an open stream set (else KWS_ESTATE).  KWS_EINVAL: C outside [1, 64]; smooth_window outside [1, 256]; refractory < 1;
+ *   first_keyword < 0; first_hop < 0; max_events < n_streams (all streams may fire at one step).  n_streams > 1024:
+ *   KWS_EUNSUPPORTED.  Waits for the context stream, allocates; a second call replaces the first.  Independent of
+ *   kws_stream_smooth_f32, kws_stream_vad_f32 and kws_stream_utt_*, whose state it neither reads nor changes; armed together
+ *   with kws_stream_utt_open a push is followed by two step launches.  No entry below allocates. */
+int kws_stream_detect_open(kws_ctx* ctx, int C, int smooth_window, int first_keyword, float threshold, int refractory, int first_hop,
+                           int max_events);
+/* Waits for the context stream and releases what kws_stream_detect_open allocated; nothing when the context is not armed. */
+int kws_stream_detect_close(kws_ctx* ctx);
+/* The explicit step, for callers with their own model (and the tests): one decision per stream from d_logits float32
+ * [n_streams, C] (device), whatever first_hop says; the record's h is d.  KWS_EINVAL: a NULL pointer.  KWS_ESTATE: the context
+ * is not armed, or a push has stepped this armed set (the set has ONE decision counter; see above for the other direction). */
+int kws_stream_detect_step_f32(kws_ctx* ctx, const float* d_logits);
+/* Wait until the step of the newest enqueued push or explicit step has landed: spins on the completion count in host memory and
+ * falls back to the stream after ~2 ms (as kws_stream_utt_poll); returns at once on a set with nothing enqueued.
+ * *total_events: records emitted since kws_stream_detect_open; *decisions: decisions made (either may be NULL).  Not armed:
+ * KWS_ESTATE. */
+int kws_stream_detect_poll(kws_ctx* ctx, uint64_t* total_events, uint64_t* decisions);
+/* Copy records first_seq .. first_seq + n - 1 out of the host mirror: out_records int64 [n, 5] (host).  Waits for nothing:
+ * sequence numbers at or beyond the total that has landed, and ones no longer in the queue (seq + max_events < total, checked
+ * again after the copy), are KWS_EINVAL, as are n < 1 and a NULL pointer.  Not armed: KWS_ESTATE. */
+int kws_stream_detect_read(kws_ctx* ctx, uint64_t first_seq, int n, int64_t* out_records);
+/* The newest decision's smoothed posteriors and their first argmax (zeros before the first decision): d_smoothed float32
+ * [n_streams, C] and d_label int32 [n_streams] (device), two asynchronous copies on the context stream behind every earlier
+ * push.  For inspection; the events need neither.  KWS_EINVAL: a NULL pointer.  Not armed: KWS_ESTATE. */
+int kws_stream_detect_smoothed(kws_ctx* ctx, float* d_smoothed, int32_t* d_label);
+
 /* ---- sample-rate conversion on the device (replaces the resampling inside librosa.load(path, sr=...),
  * kws/libs/audio_processor.py:120,145; PARITY UNPINNED against librosa's soxr: what is pinned is the project's own host
  * definition, scipy.signal.resample_poly(x, up, down, window=("kaiser", 14.0)) with zero padding, in float64) ---------------- */

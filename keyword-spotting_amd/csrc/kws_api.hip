@@ -42,6 +42,7 @@ void stream_free(kws_ctx* c) {
     smooth_free(c);
     vad_free(c);
     stream_utt_free(c);  // live utterances (kws_live.hip)
+    stream_detect_free(c);  // live keyword events (kws_live_detect.hip)
     host_results_free(c);
     if (c->stream_graph) (void)hipGraphExecDestroy(c->stream_graph);
     if (c->d_pcm_ring) (void)hipFree(c->d_pcm_ring);
@@ -594,12 +595,14 @@ int kws_stream_push_i16(kws_ctx* c, const int16_t* d_hop, float* d_logits, int32
         }
         HIP_TRY(c, hipGraphLaunch(c->stream_graph, c->stream));
         c->pushes_enqueued += 1;
-        return stream_utt_pushed(c);  // armed: the step kernel, behind the replay and outside the graph
+        if (int rc = stream_utt_pushed(c)) return rc;  // armed: the step kernel, behind the replay and outside the graph
+        return stream_detect_pushed(c, d_logits);      // ... and the decision step (kws_live_detect.hip), likewise
     }
     HIP_TRY(c, stream_enqueue(c, d_hop, d_logits, d_label, true));
     c->pushes_enqueued += 1;
     if (c->last_push_host) c->host_push = c->pushes_enqueued;
-    return stream_utt_pushed(c);
+    if (int rc = stream_utt_pushed(c)) return rc;
+    return stream_detect_pushed(c, d_logits);
 }
 
 int kws_stream_state(kws_ctx* c, const float** d_feat_ring, int* hops) {

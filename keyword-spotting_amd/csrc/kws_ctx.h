@@ -1,6 +1,6 @@
 // The context behind the C ABI (include/kws_hip.h), the error plumbing and the device-memory helpers shared by the translation
 // units that implement it (kws_api.hip, kws_frontend.hip, kws_weights.hip, kws_ingest.hip, kws_scan.hip, kws_decide.hip,
-// kws_eval.hip, kws_resample.hip, kws_live.hip, kws_*_bwd.hip), and the event bracket of a timed launch.
+// kws_eval.hip, kws_resample.hip, kws_live.hip, kws_live_detect.hip, kws_*_bwd.hip), and the event bracket of a timed launch.
 #pragma once
 #include <new>
 
@@ -21,6 +21,9 @@ struct StreamUtt;               // live utterances: history ring, walk state, ev
 void stream_utt_free(kws_ctx* c);
 int stream_utt_push_check(kws_ctx* c, const char* fn);  // a push is refused once kws_stream_utt_step_i16 has stepped the set
 int stream_utt_pushed(kws_ctx* c);                      // the step behind a push's launches; nothing when the context is unarmed
+struct StreamDetect;            // live keyword events: posterior ring, refractory state, event queue and its host mirror (kws_live_detect.hip)
+void stream_detect_free(kws_ctx* c);
+int stream_detect_pushed(kws_ctx* c, const float* d_logits);  // the decision step behind a push, from that push's logits; nothing when unarmed
 }  // namespace kws
 
 using kws::FrontendParams; using kws::FrontendTables; using kws::DscnnWeights; using kws::CnnTradWeights; using kws::NFFT;
@@ -127,6 +130,8 @@ struct kws_ctx {
     kws::StreamResample* stream_resample = nullptr;
     // live utterances (kws_stream_utt_*): created by kws_stream_utt_open, dropped with the streams
     kws::StreamUtt* stream_utt = nullptr;
+    // live keyword events (kws_stream_detect_*): created by kws_stream_detect_open, dropped with the streams
+    kws::StreamDetect* stream_detect = nullptr;
 
     // host ingest (kws_infer_host_i16): staging rings, copy streams, pack threads -- created on first use
     kws::Ingest* ingest = nullptr;

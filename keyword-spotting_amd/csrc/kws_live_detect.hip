@@ -1,0 +1,346 @@
+// Live keyword events (include/kws_hip.h: kws_stream_detect_*) -- the decision layer of kws_scan_detect_f32 taken one decision
+// per push for the streams of kws_stream_open: softmax, a posterior ring per stream, the direct causal sum, threshold and
+// refractory, and an event queue mirrored in pinned host memory (the queue discipline of kws_live.hip).  Everything here is a new
+// kernel launched BEHIND a push; no other unit's kernel changes, and an unarmed context never gets here.
+#include <atomic>
+#include <chrono>
+#include <cstring>
+
+#include "kws_ctx.h"
+#include "kws_softmax_dev.h"
+
+namespace kws {
+
+constexpr int DETECT_MAX_STREAMS = 1024;  // one workgroup decides for every stream: one thread each
+constexpr int DETECT_REC = 5;             // int64 words per record
+constexpr int DETECT_MAX_WINDOW = 256;    // kws_scan_detect_f32's bound
+
+namespace {
+
+// What a step reads.  logits and ctx_hops are set per launch (detect_launch); the rest is filled once by
+// kws_stream_detect_open.  Device counters ctr[3] = decisions made, events so far, kernels finished; the host mirror h_ctr[3] =
+// events so far, decisions made, kernels finished (the flag kws_stream_detect_poll spins on).
+struct DetectArgs {
+    const float* logits;      // [S][C]
+    const int* ctx_hops;      // stepped by a push: the context's hop counter (already advanced); nullptr: explicit step
+    int S, C, W, first_keyword, refractory, first_hop, max_events;
+    float threshold;
+    float* ring;              // [S][W][C] posteriors, decision d at slot d mod W
+    float* smoothed;          // [S][C] of the newest decision, label [S] its first argmax
+    int32_t* label;
+    long long* next;          // [S]: the first decision at which stream s may fire again
+    unsigned long long* ctr;  // [3]
+    long long* queue;         // [max_events][5]
+    long long* h_queue;       // pinned, device-mapped mirror of queue
+    unsigned long long* h_ctr;  // pinned, device-mapped [3]
+};
+
+}  // namespace
+
+// Everything kws_stream_detect_open allocates, as the step kernel takes it.
+struct StreamDetect {
+    DetectArgs a{};
+    unsigned long long ticks_enqueued = 0;  // kernels enqueued so far: h_ctr[2] reads this once the newest has landed
+    int mode = 0;                           // 0: not stepped yet, 1: stepped by pushes, 2: stepped by kws_stream_detect_step_f32
+};
+
+namespace {
+
+__device__ __forceinline__ void store_host(long long* p, long long v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// One decision of every stream.  ONE workgroup.  (1) thread s = stream s: softmax_row of the stream's logits into slot d mod W of
+// its ring.  (2) behind a barrier the S * C sums are spread over ALL threads, one (stream, class) pair at a time with the class
+// fastest (a wavefront's loads of one term are contiguous runs of C floats): the mean over the last min(W, d + 1) slots,
+// oldest first -- scan_smooth_window's sum, no running sum.  The rule is restated here and not shared through a header: moving
+// it out of kws_scan.hip changed that unit's generated code (register allocation of both smooth kernels), which this unit must
+// not do; tests/test_live_detect_gpu.py holds the two to the same bits.  (3) behind another barrier thread s takes the first
+// argmax of its row, the threshold and the refractory rule.
+// Emit, exactly as kws_live_step_kernel: the wavefronts' ballots of "fired" give every firing stream its rank in ascending stream
+// order (popcount of the lower lanes + the counts of the lower wavefronts, through LDS): consecutive sequence numbers, no
+// atomics.  Records go to the device queue and, as system-scope stores, to the pinned host mirror; every wavefront waits for its
+// own stores (vmcnt 0), and behind the barrier thread 0 publishes the totals and, last, the kernel count the host spins on.
+// A push below first_hop decides nothing and advances nothing but the kernel count.
+__global__ __launch_bounds__(DETECT_MAX_STREAMS) void kws_live_detect_step_kernel(const DetectArgs a) {
+    __shared__ int wave_n[DETECT_MAX_STREAMS / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = (int)blockDim.x >> 6;
+    const unsigned long long d = a.ctr[0], total = a.ctr[1], ticks = a.ctr[2];
+    long long h = (long long)d;  // explicit steps: the record's hop is the decision
+    bool decide = true;          // workgroup-uniform
+    if (a.ctx_hops) {
+        h = a.ctx_hops[0];  // >= 1 behind a push
+        decide = h >= a.first_hop;
+    }
+    bool fired = false;
+    int arg = 0;
+    float best = -1.f;
+    if (decide) {
+        const int C = a.C, W = a.W;
+        const int slot = (int)(d % (unsigned long long)W);
+        if (tid < a.S) softmax_row(a.logits + (size_t)tid * C, C, a.ring + ((size_t)tid * W + slot) * C);
+        __syncthreads();
+        const int terms = d + 1 < (unsigned long long)W ? (int)d + 1 : W;
+        const int oldest = slot - terms + 1 + (slot - terms + 1 < 0 ? W : 0);
+        const float count = (float)terms;
+        for (int i = tid; i < a.S * C; i += (int)blockDim.x) {
+            const int s = i / C, c = i - s * C;
+            const float* row = a.ring + (size_t)s * W * C + c;
+            // scan_smooth_window's rule (kws_scan.hip), restated: float32 additions from 0, oldest first, then ONE division
+            // The ring's slots from `oldest` to its end, then from slot 0: two linear runs, each taken eight loads at a time so that
+            // a pair waits for memory once per eight terms (the additions stay one chain, in order).
+            float acc = 0.f;
+            auto run = [&](const float* p, int n) {
+                int v = 0;
+                for (; v + 8 <= n; v += 8) {
+                    float t[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) t[j] = p[(size_t)(v + j) * C];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) acc += t[j];
+                }
+                for (; v < n; ++v) acc += p[(size_t)v * C];
+            };
+            const int head = terms < W - oldest ? terms : W - oldest;
+            run(row + (size_t)oldest * C, head);
+            run(row, terms - head);
+            acc /= count;
+            a.smoothed[i] = acc;
+        }
+        __syncthreads();
+        if (tid < a.S) {
+            const float* sm = a.smoothed + (size_t)tid * C;
+            for (int c = 0; c < C; ++c) {
+                const float v = sm[c];
+                if (v > best) {
+                    best = v;
+                    arg = c;
+                }
+            }
+            a.label[tid] = arg;
+            if (arg >= a.first_keyword && best >= a.threshold && (long long)d >= a.next[tid]) {
+                fired = true;
+                a.next[tid] = (long long)d + a.refractory;
+            }
+        }
+    }
+    const unsigned long long b = __ballot(fired);
+    if (lane == 0) wave_n[wave] = __popcll(b);
+    __syncthreads();
+    int before = 0, all = 0;
+    for (int k = 0; k < n_waves; ++k) {
+        before += k < wave ? wave_n[k] : 0;
+        all += wave_n[k];
+    }
+    if (fired) {
+        const unsigned long long seq = total + (unsigned long long)before + (unsigned long long)__popcll(b & ((1ull << lane) - 1ull));
+        const size_t at = (size_t)(seq % (unsigned long long)a.max_events) * DETECT_REC;
+        const long long rec[DETECT_REC] = {(long long)tid, (long long)d, h, (long long)arg, (long long)__float_as_uint(best)};
+#pragma unroll
+        for (int k = 0; k < DETECT_REC; ++k) {
+            a.queue[at + k] = rec[k];
+            store_host(a.h_queue + at + k, rec[k]);
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wavefront's stores, the host's among them, are acknowledged
+    __syncthreads();                     // ... and so are every other wavefront's; all have read ctr[]
+    if (tid == 0) {
+        const unsigned long long decisions = d + (decide ? 1 : 0);
+        a.ctr[0] = decisions;
+        a.ctr[1] = total + (unsigned long long)all;
+        a.ctr[2] = ticks + 1;
+        store_host(reinterpret_cast<long long*>(a.h_ctr), (long long)(total + (unsigned long long)all));
+        store_host(reinterpret_cast<long long*>(a.h_ctr) + 1, (long long)decisions);
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+        store_host(reinterpret_cast<long long*>(a.h_ctr) + 2, (long long)(ticks + 1));
+    }
+}
+
+void detect_release(StreamDetect* u) {
+    if (!u) return;
+    for (void* d : {(void*)u->a.ring, (void*)u->a.smoothed, (void*)u->a.label, (void*)u->a.next, (void*)u->a.ctr, (void*)u->a.queue})
+        if (d) (void)hipFree(d);
+    if (u->a.h_queue) (void)hipHostFree(u->a.h_queue);
+    if (u->a.h_ctr) (void)hipHostFree(u->a.h_ctr);
+    delete u;
+}
+
+// One launch of the step kernel with the set's state.  Threads: one per stream at least, and up to one per (stream, class) pair
+// for the sums.
+int detect_launch(kws_ctx* c, const float* d_logits, const int* ctx_hops) {
+    StreamDetect* u = c->stream_detect;
+    DetectArgs a = u->a;
+    a.logits = d_logits;
+    a.ctx_hops = ctx_hops;
+    const long long pairs = (long long)a.S * a.C;
+    const int threads = pairs >= DETECT_MAX_STREAMS ? DETECT_MAX_STREAMS : (int)((pairs + 63) / 64 * 64);  // >= S rounded up: C >= 1
+    hipLaunchKernelGGL(kws_live_detect_step_kernel, dim3(1), dim3(threads), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    u->ticks_enqueued += 1;
+    return KWS_OK;
+}
+
+}  // namespace
+
+void stream_detect_free(kws_ctx* c) {
+    detect_release(c->stream_detect);
+    c->stream_detect = nullptr;
+}
+
+// The push entry's side (kws_api.hip): the step behind a push's launches, from that push's logits.
+int stream_detect_pushed(kws_ctx* c, const float* d_logits) {
+    StreamDetect* u = c->stream_detect;
+    if (!u) return KWS_OK;
+    if (!d_logits)
+        return fail(c, KWS_ESTATE, "kws_stream_push_i16: the context is armed for detection (kws_stream_detect_open) and this push asked for no logits; its hop was taken, no decision was made");
+    if (u->mode == 2)
+        return fail(c, KWS_ESTATE, "kws_stream_push_i16: this detection set was stepped by kws_stream_detect_step_f32; its hop was taken, no decision was made");
+    if (u->a.C != c->mw.num_classes)
+        return fail(c, KWS_EINVAL, "kws_stream_push_i16: kws_stream_detect_open was given another class count than the loaded model's; the hop was taken, no decision was made");
+    u->mode = 1;
+    return detect_launch(c, d_logits, c->d_hops);
+}
+
+}  // namespace kws
+
+using namespace kws;
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int kws_stream_detect_open(kws_ctx* c, int C, int smooth_window, int first_keyword, float threshold, int refractory, int first_hop,
+                           int max_events) {
+    KWS_GUARD_BEGIN
+    if (!c) return KWS_EINVAL;
+    if (!c->n_streams) return fail(c, KWS_ESTATE, "kws_stream_detect_open: call kws_stream_open first");
+    if (C < 1 || C > MAX_CLASSES) return fail(c, KWS_EINVAL, "kws_stream_detect_open: C must be in [1, 64]");
+    if (smooth_window < 1 || smooth_window > DETECT_MAX_WINDOW) return fail(c, KWS_EINVAL, "kws_stream_detect_open: smooth_window must be in [1, 256]");
+    if (refractory < 1 || first_keyword < 0 || first_hop < 0)
+        return fail(c, KWS_EINVAL, "kws_stream_detect_open: need refractory >= 1, first_keyword >= 0 and first_hop >= 0");
+    if (max_events < c->n_streams) return fail(c, KWS_EINVAL, "kws_stream_detect_open: max_events must be at least n_streams (all may fire at one step)");
+    if (c->n_streams > DETECT_MAX_STREAMS)
+        return fail(c, KWS_EUNSUPPORTED, "kws_stream_detect_open: more than 1024 streams (one workgroup decides for them all)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    stream_detect_free(c);
+    StreamDetect* u = new StreamDetect();
+    DetectArgs& a = u->a;
+    const size_t S = (size_t)c->n_streams;
+    a.S = c->n_streams;
+    a.C = C;
+    a.W = smooth_window;
+    a.first_keyword = first_keyword;
+    a.refractory = refractory;
+    a.first_hop = first_hop;
+    a.max_events = max_events;
+    a.threshold = threshold;
+    const size_t ring_b = sizeof(float) * S * (size_t)smooth_window * C, sm_b = sizeof(float) * S * C, label_b = sizeof(int32_t) * S,
+                 next_b = sizeof(long long) * S, ctr_b = sizeof(unsigned long long) * 4,
+                 queue_b = sizeof(long long) * (size_t)max_events * DETECT_REC;
+    const unsigned flags = hipHostMallocMapped | hipHostMallocCoherent;  // fine-grained: device stores are visible to the host as they land
+    if (hipMalloc(reinterpret_cast<void**>(&a.ring), ring_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&a.smoothed), sm_b) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&a.label), label_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&a.next), next_b) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&a.ctr), ctr_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&a.queue), queue_b) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void**>(&a.h_queue), queue_b, flags) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void**>(&a.h_ctr), 64, flags) != hipSuccess) {
+        detect_release(u);
+        return fail(c, KWS_ENOMEM, "kws_stream_detect_open: allocation failed");
+    }
+    memset(a.h_queue, 0, queue_b);
+    memset(a.h_ctr, 0, 64);
+    // the ring needs no clearing: a decision reads only slots written since the arming
+    hipError_t e = hipMemsetAsync(a.smoothed, 0, sm_b, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(a.label, 0, label_b, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(a.next, 0, next_b, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(a.ctr, 0, ctr_b, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(a.queue, 0, queue_b, c->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        detect_release(u);
+        return fail_hip(c, e, "kws_stream_detect_open: hipMemsetAsync");
+    }
+    c->stream_detect = u;
+    return KWS_OK;
+    KWS_GUARD_END(c, "kws_stream_detect_open")
+}
+
+int kws_stream_detect_close(kws_ctx* c) {
+    if (!c) return KWS_EINVAL;
+    if (!c->stream_detect) return KWS_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    stream_detect_free(c);
+    return KWS_OK;
+}
+
+int kws_stream_detect_step_f32(kws_ctx* c, const float* d_logits) {
+    if (!c) return KWS_EINVAL;
+    StreamDetect* u = c->stream_detect;
+    if (!u) return fail(c, KWS_ESTATE, "kws_stream_detect_step_f32: call kws_stream_detect_open first");
+    if (!d_logits) return fail(c, KWS_EINVAL, "kws_stream_detect_step_f32: d_logits is NULL");
+    if (u->mode == 1) return fail(c, KWS_ESTATE, "kws_stream_detect_step_f32: this detection set is stepped by the pushes");
+    HIP_TRY(c, hipSetDevice(c->device));
+    u->mode = 2;
+    return detect_launch(c, d_logits, nullptr);
+}
+
+int kws_stream_detect_poll(kws_ctx* c, uint64_t* total_events, uint64_t* decisions) {
+    if (!c) return KWS_EINVAL;
+    StreamDetect* u = c->stream_detect;
+    if (!u) return fail(c, KWS_ESTATE, "kws_stream_detect_poll: call kws_stream_detect_open first");
+    // spin on the count of finished kernels; bounded: after ~2 ms without it, fall back to the stream (kws_stream_utt_poll)
+    volatile unsigned long long* h = u->a.h_ctr;
+    const unsigned long long want = u->ticks_enqueued;
+    bool seen = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (long spin = 1;; ++spin) {
+        if (h[2] >= want) {
+            seen = true;
+            break;
+        }
+        __builtin_ia32_pause();
+        if ((spin & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
+    }
+    if (!seen) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (h[2] < want) return fail(c, KWS_EHIP, "kws_stream_detect_poll: the stream drained but the step's flag never arrived");
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    if (total_events) *total_events = h[0];
+    if (decisions) *decisions = h[1];
+    return KWS_OK;
+}
+
+int kws_stream_detect_read(kws_ctx* c, uint64_t first_seq, int n, int64_t* out_records) {
+    if (!c) return KWS_EINVAL;
+    StreamDetect* u = c->stream_detect;
+    if (!u) return fail(c, KWS_ESTATE, "kws_stream_detect_read: call kws_stream_detect_open first");
+    if (n < 1 || !out_records) return fail(c, KWS_EINVAL, "kws_stream_detect_read: n must be positive and out_records not NULL");
+    volatile unsigned long long* h = u->a.h_ctr;
+    unsigned long long total = h[0];
+    std::atomic_thread_fence(std::memory_order_acquire);
+    if (first_seq + (unsigned long long)n > total) return fail(c, KWS_EINVAL, "kws_stream_detect_read: sequence numbers beyond the events landed so far");
+    for (int i = 0; i < n; ++i) {
+        const volatile long long* rec = u->a.h_queue + (size_t)((first_seq + i) % (unsigned long long)u->a.max_events) * DETECT_REC;
+        for (int k = 0; k < DETECT_REC; ++k) out_records[(size_t)i * DETECT_REC + k] = rec[k];
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    total = h[0];  // again: a step that landed during the copy may have overwritten the oldest
+    if (first_seq + (unsigned long long)u->a.max_events < total) return fail(c, KWS_EINVAL, "kws_stream_detect_read: the sequence number is no longer in the queue");
+    return KWS_OK;
+}
+
+int kws_stream_detect_smoothed(kws_ctx* c, float* d_smoothed, int32_t* d_label) {
+    if (!c) return KWS_EINVAL;
+    StreamDetect* u = c->stream_detect;
+    if (!u) return fail(c, KWS_ESTATE, "kws_stream_detect_smoothed: call kws_stream_detect_open first");
+    if (!d_smoothed || !d_label) return fail(c, KWS_EINVAL, "kws_stream_detect_smoothed: d_smoothed / d_label is NULL");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(d_smoothed, u->a.smoothed, sizeof(float) * (size_t)u->a.S * u->a.C, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_label, u->a.label, sizeof(int32_t) * (size_t)u->a.S, hipMemcpyDeviceToDevice, c->stream));
+    return KWS_OK;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

@@ -114,6 +114,12 @@ SIGNATURES = {
     "kws_stream_utt_poll": (C.c_int, [_c_ctx, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "kws_stream_utt_read": (C.c_int, [_c_ctx, C.c_uint64, C.c_int, C.POINTER(C.c_int64)]),
     "kws_stream_utt_cut_i16": (C.c_int, [_c_ctx, C.c_uint64, C.c_int, C.c_int, _i16p, C.c_int, _i32p]),
+    "kws_stream_detect_open": (C.c_int, [_c_ctx, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int]),
+    "kws_stream_detect_close": (C.c_int, [_c_ctx]),
+    "kws_stream_detect_step_f32": (C.c_int, [_c_ctx, _f32p]),
+    "kws_stream_detect_poll": (C.c_int, [_c_ctx, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kws_stream_detect_read": (C.c_int, [_c_ctx, C.c_uint64, C.c_int, C.POINTER(C.c_int64)]),
+    "kws_stream_detect_smoothed": (C.c_int, [_c_ctx, _f32p, _i32p]),
     "kws_resample_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _i16p, C.c_int]),
     "kws_resample_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _f32p, C.c_int]),
     "kws_host_stream_resample_plan": (C.c_int, [C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4),
@@ -565,6 +571,40 @@ class Context:
         normalised and padded or trimmed into ``clips`` int16 [U, n_out]; ``peak`` int32 [U] or None."""
         self._check(self._lib.kws_stream_utt_cut_i16(self._h, C.c_uint64(int(first_seq)), int(clips.shape[0]), int(normalize_to), _ptr(clips),
                                                      int(clips.shape[1]), _ptr(peak) if peak is not None else None), AudioProcessingError)
+
+    # -- live keyword events -----------------------------------------------------------------------
+    def stream_detect_open(self, num_classes, smooth_window, first_keyword, threshold, refractory, first_hop, max_events):
+        """``kws_stream_detect_open``: arm the open stream set -- every push that asks for logits is then followed by one
+        decision per stream (softmax, causal mean over ``smooth_window`` decisions, threshold, refractory) and the events are
+        queued; pushes below hop ``first_hop`` decide nothing."""
+        self._check(self._lib.kws_stream_detect_open(self._h, int(num_classes), int(smooth_window), int(first_keyword), float(threshold),
+                                                     int(refractory), int(first_hop), int(max_events)), ModelError)
+
+    def stream_detect_close(self):
+        self._check(self._lib.kws_stream_detect_close(self._h), ModelError)
+
+    def stream_detect_step_f32(self, logits):
+        """``kws_stream_detect_step_f32``: the explicit step; ``logits`` float32 [S, C], a device tensor or a raw device address."""
+        self._check(self._lib.kws_stream_detect_step_f32(self._h, int(logits) if isinstance(logits, int) else _ptr(logits)), ModelError)
+
+    def stream_detect_poll(self):
+        """``kws_stream_detect_poll``: wait for the newest step; (events so far, decisions made)."""
+        total, decisions = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.kws_stream_detect_poll(self._h, C.byref(total), C.byref(decisions)), ModelError)
+        return int(total.value), int(decisions.value)
+
+    def stream_detect_read(self, first_seq: int, n: int) -> np.ndarray:
+        """``kws_stream_detect_read``: int64 [n, 5] = (stream, decision, hop, label, score bits) of the sequence numbers
+        ``first_seq`` .. ``first_seq + n - 1``, from the host mirror of the queue."""
+        out = np.empty((max(int(n), 0), 5), np.int64)
+        self._check(self._lib.kws_stream_detect_read(self._h, C.c_uint64(int(first_seq)), int(n), out.ctypes.data_as(C.POINTER(C.c_int64))),
+                    ModelError)
+        return out
+
+    def stream_detect_smoothed(self, smoothed, label):
+        """``kws_stream_detect_smoothed``: the newest decision's posteriors into ``smoothed`` float32 [S, C] and their argmax
+        into ``label`` int32 [S] (device), asynchronously on the context stream."""
+        self._check(self._lib.kws_stream_detect_smoothed(self._h, _ptr(smoothed), _ptr(label)), ModelError)
 
     # -- sample-rate conversion --------------------------------------------------------------------
     def _resample(self, fn, x, rate_in, rate_out, out, lengths):

@@ -103,6 +103,38 @@ class UtteranceConfig:
     slack_hops: int = 8
 
 
+@dataclass
+class DetectConfig:
+    """``StreamingSpotter(detect=...)``: the decision layer of ``KeywordSpotter.scan`` on the streams, one decision per push
+    (``kws_stream_detect_open``).  The posteriors of every hop are averaged over the last ``smooth_window`` decisions; a stream
+    fires when the top class is at least ``first_keyword`` (classes below it, _silence_ and _unknown_, never fire) and its
+    smoothed posterior at least ``threshold``, and then stays quiet for ``refractory`` decisions.  ``max_events``: records the
+    device queue keeps (None: ``max(n_streams, 64)``).  ``skip_partial_windows``: no decision before the one-second window holds
+    99 real frames -- decision d is then window d of ``scan(pcm, hop_frames=1)`` over the same audio; False: every push decides,
+    from the first."""
+    threshold: float
+    smooth_window: int = 1
+    refractory: int = 50
+    first_keyword: int = 2
+    max_events: Optional[int] = None
+    skip_partial_windows: bool = True
+
+
+@dataclass
+class KeywordEvent:
+    """One event of ``StreamingSpotter.pop_events``: class ``index`` (``word``) fired on ``stream`` with the smoothed posterior
+    ``score``.  ``time_s`` is the end of the window that fired, in seconds of the stream since the spotter was created at
+    ``config.sample_rate`` -- the convention of ``ScanResult.events``; ``decision`` counts the decisions since the arming and
+    ``hop`` the pushes (from 1)."""
+    stream: int
+    time_s: float
+    index: int
+    word: str
+    score: float
+    decision: int
+    hop: int
+
+
 class KeywordSpotter:
     """Holds a model on one GPU and maps wav files / PCM batches to (index, word)."""
 
@@ -656,6 +688,11 @@ class StreamingSpotter:
     queues the utterances that closed; ``pop_utterances()`` cuts, normalises and classifies them, ``flush()`` closes what is
     still open.  ``push`` keeps its signature, its results and its zero-copy path; at most 1024 streams.
 
+    ``detect``: a ``DetectConfig`` arms the scan's decision layer on the device (``kws_stream_detect_open``): every push is followed
+    by one more launch that takes its logits through softmax, a causal mean, threshold and refractory and queues the keyword
+    events; ``pop_events()`` returns them, ``smoothed()`` reads the newest decision's posteriors.  ``push`` keeps its signature,
+    its results (raw logits) and its zero-copy path; at most 1024 streams.  May be combined with ``utterances``.
+
     Attributes: ``hop`` -- samples per hop at ``config.sample_rate``; ``hop_in`` -- samples ``push`` takes per stream (``hop``
     without ``input_rate``); ``delay_samples`` -- the resampler's delay in samples at ``config.sample_rate`` (10 = 0.625 ms for
     every rate above 16 kHz, 20 for 8 kHz, 0 without ``input_rate``): what the streams hear lags the input by that much.
@@ -664,7 +701,8 @@ class StreamingSpotter:
     def __init__(self, n_streams: int, model: Optional[DepthwiseSeparableConv] = None, words: Sequence[str] = WANTED_WORDS,
                  config: Optional[AudioConfig] = None, device: int = 0, use_graph: bool = False, smooth_window: int = 0,
                  vad_log_energy: Optional[float] = None, vad_windows: Tuple[int, int] = (40, 80), host_results: bool = True,
-                 input_rate: Optional[int] = None, utterances: Optional[UtteranceConfig] = None):
+                 input_rate: Optional[int] = None, utterances: Optional[UtteranceConfig] = None,
+                 detect: Optional[DetectConfig] = None):
         from kws import _native
 
         self.config = config or AudioConfig()
@@ -728,6 +766,22 @@ class StreamingSpotter:
             self._utt_max_events = int(u.max_events) if u.max_events is not None else max(self.n_streams, 64)
             history = _native.host_stream_utt_history(frame_len, self.hop, int(u.pre_roll), max_frames, int(u.slack_hops))
             self._ctx.stream_utt_open(u.threshold, u.on_window, u.off_window, u.pre_roll, max_frames, history, self._utt_max_events)
+        # live keyword events (kws_stream_detect_*): armed, every push is also followed by one decision per stream on the device
+        # (softmax, causal mean, threshold, refractory) and the events are queued; push itself is unchanged, zero-copy path included
+        self.detect = detect
+        self._det_seq = 0  # the next sequence number pop_events hands out
+        if detect is not None:
+            d = detect
+            if not 1 <= int(d.smooth_window) <= 256:
+                raise ModelError("detect: smooth_window must be in [1, 256]")
+            if int(d.refractory) < 1 or int(d.first_keyword) < 0:
+                raise ModelError("detect: need refractory >= 1 and first_keyword >= 0")
+            self._det_lag = -(-frame_len // self.hop)  # K: hops a frame spans; push h completes frame h - K
+            self._det_frame_len = frame_len
+            self._det_max_events = int(d.max_events) if d.max_events is not None else max(self.n_streams, 64)
+            first_hop = WINDOW_FRAMES + self._det_lag - 1 if d.skip_partial_windows else 0
+            self._ctx.stream_detect_open(self.model.num_classes, d.smooth_window, d.first_keyword, d.threshold, d.refractory, first_hop,
+                                         self._det_max_events)
         torch.cuda.synchronize(self.device)
 
     def load_model(self, model: DepthwiseSeparableConv) -> None:
@@ -822,7 +876,39 @@ class StreamingSpotter:
         self._ctx.stream_utt_flush()
         return self.pop_utterances()
 
+    def pop_events(self) -> List[KeywordEvent]:
+        """The keyword events since the last call, in the order they fired (ascending stream within a hop).  Waits for the newest
+        push's decision step (``kws_stream_detect_poll``); with nothing new it returns ``[]`` without a launch or a read.
+        Otherwise one ``kws_stream_detect_read`` out of the queue's host mirror: no launch, no synchronise, no device copy.
+        Records the queue has already overwritten (more than ``max_events`` events between two calls) are skipped."""
+        if self.detect is None:
+            raise ModelError("pop_events: this StreamingSpotter was created without detect=DetectConfig(...)")
+        total, _ = self._ctx.stream_detect_poll()
+        first = max(self._det_seq, total - self._det_max_events)
+        if total - first <= 0:
+            return []
+        rec = self._ctx.stream_detect_read(first, total - first)
+        self._det_seq = total
+        score = (rec[:, 4] & 0xFFFFFFFF).astype(np.uint32).view(np.float32)
+        rate = float(self.config.sample_rate)
+        return [KeywordEvent(int(s), ((int(h) - self._det_lag) * self.hop + self._det_frame_len) / rate, int(k), self.words[int(k)],
+                             float(score[i]), int(d), int(h)) for i, (s, d, h, k, _) in enumerate(rec)]
+
+    def smoothed(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(labels int32 [S], posteriors float32 [S, C]) of the newest decision: the smoothed posteriors the events are decided
+        on and their argmax (zeros before the first decision).  A synchronising read, for inspection."""
+        if self.detect is None:
+            raise ModelError("smoothed: this StreamingSpotter was created without detect=DetectConfig(...)")
+        post = torch.empty((self.n_streams, self.model.num_classes), dtype=torch.float32, device=self.device)
+        labels = torch.empty((self.n_streams,), dtype=torch.int32, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()  # the context runs on its own stream
+        self._ctx.stream_detect_smoothed(post, labels)
+        self._ctx.sync()
+        return labels.cpu().numpy(), post.cpu().numpy()
+
     def close(self):
+        if self.detect is not None:
+            self._ctx.stream_detect_close()
         if self.utterances is not None:
             self._ctx.stream_utt_close()
         self._ctx.stream_close()
