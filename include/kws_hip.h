@@ -441,6 +441,18 @@ int kws_stream_smooth_f32(kws_ctx* ctx, const float* d_logits, int C, int window
 int kws_scan_i16(kws_ctx* ctx, const int16_t* d_pcm, int R, int n_total, int hop_frames, float* d_logits, int32_t* d_label,
                  float* d_feat_out);
 
+/* kws_scan_i16 over float32 samples: d_wav float32 [R, n_total] (device), taken as they are -- no scaling, no clamping, values
+ * beyond +-1 pass through as kws_mfcc_f32 passes them.  Same checks, error codes, limits, timing ids and stream behaviour.
+ *   Frames: those of kws_frames_f32 (below), refinement and KWS_FE_F64 included.  Windows: bit-identical to kws_forward_f32 on
+ *   the 99 gathered rows.  A recording of exactly n_samples samples gives the logits and label of kws_infer_f32, bit for bit.
+ *   Grid property: for d_wav[i] = (float)pcm[i] / 32768 (exact) the frames, logits and labels equal kws_scan_i16's on pcm bit for
+ *   bit -- the int16 entries' PCM scaling is that exact division.
+ *   What differs from the twin: the sample type, and the front-end route -- the wavefront-resident float32 kernel when n_total
+ *   is a multiple of 8, d_wav is 16-byte aligned and the geometry is that kernel's; the float32 tile kernel otherwise.  Both give
+ *   the same bits. */
+int kws_scan_f32(kws_ctx* ctx, const float* d_wav, int R, int n_total, int hop_frames, float* d_logits, int32_t* d_label,
+                 float* d_feat_out);
+
 /* Causal decisions over a scan's logits [R, W, C] (C <= 64) -- the decisions a stream would have made at each hop.
  *   p[r, w, :] = softmax(logits[r, w, :]) as kws_softmax_f32 computes it.
  *   Smoothing: s[r, w, c] = mean of p[r, v, c] over v = max(0, w - S + 1) .. w, S = smooth_window in [1, 256]: summed in
@@ -476,6 +488,14 @@ int kws_scan_detect_f32(kws_ctx* ctx, const float* d_logits, int R, int W, int C
  *   Timed under KWS_K_MFCC / KWS_K_MFCC_REFINE / KWS_K_MFCC_F64.  Asynchronous on the context stream; the refinement worklist
  *   grows with R * F_total, so the call may allocate and is not for stream capture. */
 int kws_frames_i16(kws_ctx* ctx, const int16_t* d_pcm, int R, int n_total, float* d_feat_out);
+
+/* kws_frames_i16 over float32 samples: d_wav float32 [R, n_total] (device), taken as they are.  Same checks, error codes, limits,
+ * timing ids and stream behaviour.
+ *   Equal, word for word, to kws_mfcc_f32 with B = R on a context configured with n_samples = n_total: the selective refinement
+ *   included, under KWS_FE_F32 and under KWS_FE_F64, and counted by kws_frontend_stats as that call counts.  For d_wav[i] =
+ *   (float)pcm[i] / 32768 the rows and the counts equal kws_frames_i16's on pcm (see kws_scan_f32).
+ *   What differs from the twin: the sample type and the front-end route (see kws_scan_f32). */
+int kws_frames_f32(kws_ctx* ctx, const float* d_wav, int R, int n_total, float* d_feat_out);
 
 /* The endpointer of kws_stream_vad_f32 walked over a whole frame array, with the reference's start point and time-out.
  *   d_feat: float32 [R, F_total, numcep] (kws_frames_i16, or the d_feat_out of kws_scan_i16); only column 0, the log frame
@@ -518,6 +538,21 @@ int kws_segment_f32(kws_ctx* ctx, const float* d_feat, int R, int F_total, int n
 int kws_cut_i16(kws_ctx* ctx, const int16_t* d_pcm, int R, int n_total, const int32_t* d_span, int U, int normalize_to,
                 int16_t* d_clips, int n_out, int32_t* d_peak);
 
+/* kws_cut_i16 over float32 samples.  d_wav: float32 [R, n_total].  d_clips: float32 [U, n_out]; every element is written.
+ * d_peak: float32 [U] or NULL.  d_span, its clamping and the recording index outside [0, R) (a zero clip, peak = -1) are
+ * kws_cut_i16's.
+ *   peak = the largest |x[i]| over the WHOLE span in float32, compared with m > peak, so a NaN never raises it; 0 for an empty
+ *   span.  normalize_to > 0 and peak > 0: times = (double)normalize_to / (double)peak and out[i] = (float)((double)x[start + i] *
+ *   times) for i < min(len, n_out) -- a float64 divide and multiply, then ONE round-to-nearest conversion.  peak == 0 writes
+ *   zeros.  normalize_to == 0 is a bitwise copy.  out[i] = 0 for i >= len.
+ *   What differs from the twin: no truncation step (there is no int() to reproduce), normalize_to and the peaks are floats in
+ *   full-scale units -- the reference's 16384 is normalize_to = 0.5.
+ *   KWS_EINVAL: normalize_to negative or not finite, U, R, n_total or n_out < 1, a NULL d_wav / d_span / d_clips.  Needs neither a
+ *   front end nor a model.  One launch, asynchronous on the context stream, deterministic; not timed by kws_prof_*.  A ragged float
+ *   batch is cut as ONE recording over the whole buffer, as the note below says for int16. */
+int kws_cut_f32(kws_ctx* ctx, const float* d_wav, int R, int n_total, const int32_t* d_span, int U, float normalize_to,
+                float* d_clips, int n_out, float* d_peak);
+
 /* Cutting the spans of a ragged batch (below) needs no entry of its own: kws_cut_i16 over the whole buffer as ONE recording
  * (R = 1, n_total = n_pcm, recording index 0), with start[r] added to each span of recording r on the host, gives the clips
  * and peaks kws_cut_i16 gives on that recording alone -- a span lies inside its recording, so the clamp to [0, n_pcm] never
@@ -556,6 +591,19 @@ int kws_cut_i16(kws_ctx* ctx, const int16_t* d_pcm, int R, int n_total, const in
 int kws_frames_ragged_i16(kws_ctx* ctx, const int16_t* d_pcm, int n_pcm, const int64_t* start, const int32_t* len, int R,
                           int row_multiple, float* d_feat_out);
 
+/* kws_frames_ragged_i16 over float32 samples: one device buffer d_wav of n_wav float32 samples, 16-byte aligned, recording r =
+ * samples [start[r], start[r] + len[r]) with start[r] % 8 == 0 (a packed buffer, or the rectangular output of kws_resample_f32
+ * with d_len and n_out % 8 == 0).  Same checks, error codes, limits, routes (KWS_FE_F64 and geometries outside the
+ * wavefront-resident kernel's: KWS_EUNSUPPORTED), timing ids and stream behaviour.
+ *   Rows frame_off[r] .. frame_off[r] + F_r - 1 equal, word for word, kws_frames_f32 on recording r alone, refinement included;
+ *   rounding rows are zeros.  Nothing past start[r] + len[r] is read as part of recording r: a vector is 8 samples (two 16-byte
+ *   loads) and the one that straddles the end is read sample by sample.  For d_wav[i] = (float)pcm[i] / 32768 the rows equal
+ *   kws_frames_ragged_i16's.  What differs from the twin: the sample type.
+ *   The decisions and the endpointer of a ragged float batch need nothing new: kws_scan_detect_ragged_f32 and
+ *   kws_segment_ragged_f32 take logits and frames. */
+int kws_frames_ragged_f32(kws_ctx* ctx, const float* d_wav, int n_wav, const int64_t* start, const int32_t* len, int R,
+                          int row_multiple, float* d_feat_out);
+
 /* kws_scan_i16 for a ragged batch: kws_frames_ragged_i16 with row_multiple = hop_frames, then the scan launch over the packed
  * frame array.  d_logits: float32 [W_pack, C]; d_label: int32 [W_pack] or NULL; d_feat_out: float32 [F_pack, numcep] or NULL
  * (a context workspace).  Rows win_off[r] + w, w < W_r, equal kws_scan_i16 on recording r alone (window w), bit for bit; the
@@ -563,6 +611,12 @@ int kws_frames_ragged_i16(kws_ctx* ctx, const int16_t* d_pcm, int n_pcm, const i
  * after the frames.  Scope, model and state checks as kws_scan_i16; argument checks and limits as kws_frames_ragged_i16, and
  * W_pack <= 2^30.  Timed under KWS_K_MFCC / KWS_K_MFCC_REFINE and KWS_K_DSCNN. */
 int kws_scan_ragged_i16(kws_ctx* ctx, const int16_t* d_pcm, int n_pcm, const int64_t* start, const int32_t* len, int R, int hop_frames,
+                        float* d_logits, int32_t* d_label, float* d_feat_out);
+
+/* kws_scan_ragged_i16 over float32 samples (the buffer of kws_frames_ragged_f32): rows win_off[r] + w, w < W_r, equal kws_scan_f32
+ * on recording r alone, bit for bit.  Same checks, error codes, limits, timing ids and stream behaviour; what differs from the
+ * twin is the sample type. */
+int kws_scan_ragged_f32(kws_ctx* ctx, const float* d_wav, int n_wav, const int64_t* start, const int32_t* len, int R, int hop_frames,
                         float* d_logits, int32_t* d_label, float* d_feat_out);
 
 /* kws_scan_detect_f32 per recording of a ragged scan.  d_logits: float32 [W_pack, C]; win_off, windows: HOST int32 [R]

@@ -154,9 +154,10 @@ int frames_for(int n_samples, int frame_len, int frame_step);  // 1 + ceil((n - 
 void set_clip_length(FrontendParams& p, int n_samples);
 int ensure_refine(kws_ctx* c, int B, int num_frames);  // the refinement worklist holds B clips of num_frames frames
 void stream_free(kws_ctx* c);                          // kws_api.hip: rings, hop counter, captured graph, smoothing and endpointer history
-// The MFCC launches of B clips read from src (const int16_t*, const float* or kws::AugmentArgs; instantiated in kws_frontend.hip)
+// The MFCC launches of B clips read from src (const int16_t*, const float* or kws::AugmentArgs; instantiated in kws_frontend.hip).
+// recording_f32: float32 samples may take the wavefront-resident kernel (kws_frames_f32, kws_scan_f32).
 template <typename Src>
-int run_frontend(kws_ctx* c, const FrontendParams& geometry, Src src, int B, float* d_out, int refine_clips);
+int run_frontend(kws_ctx* c, const FrontendParams& geometry, Src src, int B, float* d_out, int refine_clips, bool recording_f32 = false);
 
 inline thread_local std::string g_create_err;
 

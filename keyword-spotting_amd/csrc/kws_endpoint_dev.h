@@ -1,7 +1,7 @@
 // The energy endpointer's one statement on the device (the reference's live loop, kws/inference/inference_local.py:131-166):
 // what a voiced frame is, when an utterance opens and closes, the flag ring with O(1) window counts, where a span starts, and
 // normalize + fix_length of a span into a clip.  No kernels here: kws_stream_vad_kernel (kws_decide.hip), the flag and walk
-// kernels (kws_segment.hip), the live step (kws_live.hip) and the two cut kernels are the callers.
+// kernels (kws_segment.hip), the live step (kws_live.hip) and the cut kernels are the callers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -73,6 +73,39 @@ __device__ __forceinline__ void ep_cut_clip(At at, int len, bool ok, int normali
         for (unsigned i = tid; i < (unsigned)n_out; i += Threads) out[i] = i < (unsigned)body ? (int16_t)(int)((double)at(i) * times) : (int16_t)0;
     } else {
         for (unsigned i = tid; i < (unsigned)n_out; i += Threads) out[i] = i < (unsigned)body ? (int16_t)at(i) : (int16_t)0;
+    }
+}
+
+// The same for float32 samples (kws_cut_f32): peak = the largest |x| of the whole span in float32, compared with m > peak, so a NaN
+// never raises it; normalize_to > 0 and peak > 0: out[i] = (float)((double)x[i] * ((double)normalize_to / (double)peak)) -- a
+// float64 divide and multiply, one rounding to float32, no truncation; peak == 0: zeros; normalize_to == 0: the samples' own bits.
+// at(i): sample i of the span as float; peak_out[u] = the peak, -1 for a refused span.
+template <int Threads, typename At>
+__device__ __forceinline__ void ep_cut_clip_f32(At at, int len, bool ok, float normalize_to, float* out, int n_out, float* peak_out,
+                                                int u) {
+    __shared__ float wave_peak[Threads / 64];
+    const int tid = threadIdx.x;
+    float peak = 0.f;
+    for (unsigned i = tid; i < (unsigned)len; i += Threads) {
+        const float m = fabsf(at(i));
+        peak = m > peak ? m : peak;
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        const float other = __shfl_xor(peak, d);
+        peak = other > peak ? other : peak;
+    }
+    if ((tid & 63) == 0) wave_peak[tid >> 6] = peak;
+    __syncthreads();
+    peak = wave_peak[0];
+    for (int k = 1; k < Threads / 64; ++k) peak = wave_peak[k] > peak ? wave_peak[k] : peak;
+    if (tid == 0 && peak_out) peak_out[u] = ok ? peak : -1.f;
+    const int body = len < n_out ? len : n_out;
+    if (normalize_to > 0.f) {
+        const bool scale = peak > 0.f;
+        const double times = scale ? (double)normalize_to / (double)peak : 0.0;
+        for (unsigned i = tid; i < (unsigned)n_out; i += Threads) out[i] = scale && i < (unsigned)body ? (float)((double)at(i) * times) : 0.f;
+    } else {
+        for (unsigned i = tid; i < (unsigned)n_out; i += Threads) out[i] = i < (unsigned)body ? at(i) : 0.f;
     }
 }
 

@@ -49,11 +49,13 @@ int ensure_refine(kws_ctx* c, int B, int num_frames) {
 // from src: float64, or float32 with the flagged frames redone.  refine_clips sizes the refinement's grid: the batch in
 // one-second clips.  int16 PCM off a 16-byte boundary takes the kernels' scalar loads; kws_mfcc_augment_i16 refuses such a
 // split, and the float64 route, before it gets here.
+// recording_f32: float32 samples of a recording entry (kws_frames_f32, kws_scan_f32) ask for the wavefront-resident float kernel;
+// off a 16-byte boundary, or at a length that is no multiple of 8, the tile kernel serves them as it serves kws_mfcc_f32.
 template <typename Src>
-int run_frontend(kws_ctx* c, const FrontendParams& geometry, Src src, int B, float* d_out, int refine_clips) {
+int run_frontend(kws_ctx* c, const FrontendParams& geometry, Src src, int B, float* d_out, int refine_clips, bool recording_f32) {
     HIP_TRY(c, hipSetDevice(c->device));
     FrontendParams p = geometry;
-    if constexpr (std::is_same<Src, const int16_t*>::value)
+    if constexpr (std::is_pointer<Src>::value)  // (the float tile and float64 kernels read samples one by one and never ask)
         if ((reinterpret_cast<uintptr_t>(src) & 15) != 0) p.vec_ok = 0;
     if constexpr (std::is_pointer<Src>::value)
         if (c->fe_math == KWS_FE_F64 || !c->fe_fast_ok) {
@@ -62,7 +64,8 @@ int run_frontend(kws_ctx* c, const FrontendParams& geometry, Src src, int B, flo
             return KWS_OK;
         }
     c->frames_seen += (unsigned long long)B * p.num_frames;
-    const bool ref_route = c->fe_ref_geometry && c->fe_route == KWS_FE_ROUTE_AUTO;
+    // the launch's one routing flag: the reference-geometry kernel for int16 PCM, the wavefront-resident kernel for float32 samples
+    const bool ref_route = std::is_same<Src, const float*>::value ? recording_f32 : c->fe_ref_geometry && c->fe_route == KWS_FE_ROUTE_AUTO;
     if (p.refine_span > 0.f) {
         int rc = ensure_refine(c, B, p.num_frames);
         if (rc) return rc;
@@ -79,9 +82,9 @@ int run_frontend(kws_ctx* c, const FrontendParams& geometry, Src src, int B, flo
     HIP_TRY(c, launch_mfcc(c->stream, p, c->ft, src, B, d_out, RefineList{}, ref_route));
     return KWS_OK;
 }
-template int run_frontend(kws_ctx*, const FrontendParams&, const int16_t*, int, float*, int);
-template int run_frontend(kws_ctx*, const FrontendParams&, const float*, int, float*, int);
-template int run_frontend(kws_ctx*, const FrontendParams&, AugmentArgs, int, float*, int);
+template int run_frontend(kws_ctx*, const FrontendParams&, const int16_t*, int, float*, int, bool);
+template int run_frontend(kws_ctx*, const FrontendParams&, const float*, int, float*, int, bool);
+template int run_frontend(kws_ctx*, const FrontendParams&, AugmentArgs, int, float*, int, bool);
 
 #pragma GCC visibility push(default)
 extern "C" {

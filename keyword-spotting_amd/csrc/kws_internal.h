@@ -92,11 +92,13 @@ struct AugmentArgs;
 // The float32 MFCC of B clips read from int16 PCM, float32 samples, or the augmented view of a resident split (gather +
 // augment + MFCC in one launch, wavefront-resident geometry only).  Frames over p.refine_span are appended to rl; an empty rl
 // (ctr == nullptr) means no flagging.  ref_route: int16 PCM at the reference geometry takes the kernel compiled for it
-// (kws_mfcc_i16_ref_kernel: the same bits); the other sources have one route and ignore it.
+// (kws_mfcc_i16_ref_kernel: the same bits); the augmented source has one route and ignores it.  wr_route: float32 samples take
+// the wavefront-resident kernel where mfcc_wave_resident_ok holds (the recording entries ask; kws_mfcc_f32 / kws_infer_f32 do
+// not and stay on the tile kernels: the same bits either way).
 hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_wav, int B, float* d_out,
                        const RefineList& rl, bool ref_route);
 hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, int B, float* d_out,
-                       const RefineList& rl, bool ref_route);
+                       const RefineList& rl, bool wr_route);
 hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const AugmentArgs& a, int B, float* d_out,
                        const RefineList& rl, bool ref_route);
 // Float64 recomputation of the listed frames, in place in d_out (same source / d_out as the float32 launch before it).
@@ -126,6 +128,11 @@ struct RaggedArgs {
 hipError_t launch_mfcc_ragged(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_pcm, const RaggedArgs& rg,
                               int n_waves, float* d_out, const RefineList& rl);
 hipError_t launch_mfcc_refine_ragged(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_pcm,
+                                     const RaggedArgs& rg, float* d_out, const RefineList& rl, int B);
+// The same pair over float32 samples (kws_frames_ragged_f32): start % 8 == 0 and a 16-byte aligned buffer, as for int16.
+hipError_t launch_mfcc_ragged(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, const RaggedArgs& rg,
+                              int n_waves, float* d_out, const RefineList& rl);
+hipError_t launch_mfcc_refine_ragged(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav,
                                      const RaggedArgs& rg, float* d_out, const RefineList& rl, int B);
 // Chunks per wavefront of a wavefront-resident launch of total_chunks chunks in all, for a clip of n_chunks of them (host).
 int mfcc_wr_chunks_per_wave(long total_chunks, int n_chunks);

@@ -228,6 +228,27 @@ __device__ __forceinline__ uint4 ragged_vec8(const int16_t* __restrict__ x, int 
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
+// The same for float32 samples: a vector of 8 samples is two 16-byte loads (n0 a multiple of 8, x + n0 16-byte aligned), zeros past
+// len, and the one vector that straddles len sample by sample.  len = the clip's length for an equal-length batch, where
+// n_samples % 8 == 0 and no vector straddles.
+template <bool RAGGED>
+__device__ __forceinline__ void f32_vec8(const float* __restrict__ x, int n0, int len, float (&a)[8]) {
+    if (n0 + 8 <= len) {
+        const float4 lo = *reinterpret_cast<const float4*>(x + n0), hi = *reinterpret_cast<const float4*>(x + n0 + 4);
+        a[0] = lo.x, a[1] = lo.y, a[2] = lo.z, a[3] = lo.w, a[4] = hi.x, a[5] = hi.y, a[6] = hi.z, a[7] = hi.w;
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a[i] = 0.f;
+    if constexpr (RAGGED) {
+        if (n0 < len) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+                if (n0 + i < len) a[i] = x[n0 + i];
+        }
+    }
+}
+
 // Eight consecutive augmented samples n0 .. n0 + 7 (n0 a multiple of 8) of a clip of the resident split, the values aug_sample
 // gives one by one.  The source run starts at j0 = n0 - shift, aligned to 2 bytes only: the two ALIGNED 16-byte vectors that
 // hold it are read -- each lies wholly inside the clip's own row or is replaced by zeros (n_samples % 8 == 0), so nothing
@@ -297,11 +318,17 @@ __host__ __device__ inline size_t mfcc_wr_lds_bytes(const FrontendParams& p) {
 // RAGGED (kws_mfcc_i16_ragged_kernel): the clips are the recordings of rg, each with its own length, frame count, first row and
 // share of the launch's wavefronts; a wavefront finds its recording once, by a scalar binary search over the records' first
 // wavefronts, and from there on p.n_samples / p.num_frames are that recording's.  Every RAGGED branch is an if constexpr.
-template <bool AUG, class G = GeomAny, bool RAGGED = false>
-__device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t, const int16_t* __restrict__ wav,
+// T (kws_mfcc_f32_wr_kernel, kws_mfcc_f32_ragged_kernel): float32 samples, taken as they are.  A chunk's span is then four
+// 16-byte loads per lane, taken one half-span (two loads) at a time: load, pre-emphasise, store, and only then the other half --
+// both halves in registers at once would be the eight extra registers the dropped prefetch could not afford.  Every float branch
+// is an if constexpr: the int16 instantiations compile to the instructions they had.
+template <bool AUG, class G = GeomAny, bool RAGGED = false, typename T = int16_t>
+__device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t, const T* __restrict__ wav,
                                              float* __restrict__ out, RefineList rl, int B, int chunks_per_wave,
                                              AugmentArgs aug, RaggedArgs rg = RaggedArgs{}) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr bool F32 = sizeof(T) == 4;
+    static_assert(!F32 || (!AUG && !G::REF), "float32 samples take the generic geometry and no augmentation");
     static_assert(!(AUG && G::REF), "the fused loader keeps the generic geometry");
     static_assert(!RAGGED || (!AUG && !G::REF), "the ragged kernel reads PCM at the generic geometry");
     const int nfp = (G::nfilt(p) + 3) & ~3;
@@ -364,7 +391,7 @@ __device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t,
     }
     const int c_end = c_end_of;
     const bool active = active_of;
-    const int16_t* __restrict__ x = AUG ? nullptr : wav + x_first;
+    const T* __restrict__ x = AUG ? nullptr : wav + x_first;
     AugClip ac{};
     if constexpr (AUG) ac = aug_clip(aug, active ? clip : 0, p.n_samples);  // wave-uniform: scalar registers
     const int chunk_step = WR_FRAMES * frame_step;  // samples from one chunk's span to the next (a multiple of 8: checked by the launcher)
@@ -373,16 +400,18 @@ __device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t,
     uint4 v0 = make_uint4(0, 0, 0, 0), v1 = v0;
     int16_t before = 0;
     auto fetch = [&](int cc, int lane) {
-        const int s0 = cc * chunk_step;
-        const int n0 = s0 + 8 * lane, n1 = n0 + 512;
-        if constexpr (RAGGED) {
-            v0 = ragged_vec8(x, n0, p.n_samples);
-            v1 = ragged_vec8(x, n1, p.n_samples);
-        } else {
-            v0 = n0 + 8 <= p.n_samples ? *reinterpret_cast<const uint4*>(x + n0) : make_uint4(0, 0, 0, 0);
-            v1 = n1 + 8 <= p.n_samples ? *reinterpret_cast<const uint4*>(x + n1) : make_uint4(0, 0, 0, 0);
+        if constexpr (!F32) {
+            const int s0 = cc * chunk_step;
+            const int n0 = s0 + 8 * lane, n1 = n0 + 512;
+            if constexpr (RAGGED) {
+                v0 = ragged_vec8(x, n0, p.n_samples);
+                v1 = ragged_vec8(x, n1, p.n_samples);
+            } else {
+                v0 = n0 + 8 <= p.n_samples ? *reinterpret_cast<const uint4*>(x + n0) : make_uint4(0, 0, 0, 0);
+                v1 = n1 + 8 <= p.n_samples ? *reinterpret_cast<const uint4*>(x + n1) : make_uint4(0, 0, 0, 0);
+            }
+            before = s0 > 0 ? x[s0 - 1] : (int16_t)0;
         }
-        before = s0 > 0 ? x[s0 - 1] : (int16_t)0;
     };
     __syncthreads();  // the only workgroup barrier: the shared tables are in place
     if (!active) return;
@@ -413,7 +442,7 @@ __device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t,
             rl.list[at] = (int)((((RAGGED ? (unsigned)pair_base : (unsigned)(rl.clip0 + clip) * (unsigned)((p.num_frames + 1) / 2)) + (unsigned)(pair0 + lane)) << 2) | fk); \
     }
     for (; c < c_end; ++c) {
-        if constexpr (!AUG) fetch(c, lane);
+        if constexpr (!AUG && !F32) fetch(c, lane);
         // ---- registers -> float32, pre-emphasised, into this wavefront's span buffer -----------------------
         if constexpr (AUG) {
             const int s0 = c * chunk_step;
@@ -443,6 +472,34 @@ __device__ __forceinline__ void mfcc_wr_body(FrontendParams p, FrontendTables t,
             };
             emphasise(a0, lane == 0 ? before_a : w0, s0 + 8 * lane, ybuf + 8 * lane);
             emphasise(a1, lane == 0 ? last0 : w1, s0 + 512 + 8 * lane, ybuf + 512 + 8 * lane);
+        } else if constexpr (F32) {
+            const int s0 = c * chunk_step;
+            // one half-span at a time (see T above).  The sample before a lane's vector: the neighbouring lane's last one
+            // (wave_shr:1), lane 63's last of the first half for lane 0's second, the clip's sample s0 - 1 for lane 0's first
+            float carry = s0 > 0 ? x[s0 - 1] : 0.f;  // wave-uniform
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int n = s0 + 512 * h + 8 * lane;
+                float a[8], y[8];
+                f32_vec8<RAGGED>(x, n, p.n_samples, a);
+                const float w = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a[7]), 0x138, 0xf, 0xf, false));
+                float prev = lane == 0 ? carry : w;
+                if (h == 0) carry = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a[7]), 63));
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    y[i] = __fsub_rn(a[i], __fmul_rn(pre, prev));
+                    prev = a[i];
+                }
+                if (n == 0) y[0] = a[0];  // the clip's first sample is not pre-emphasised
+                if (n + 8 > p.n_samples) {  // past the end the PRE-EMPHASISED signal is zero, also inside a vector that straddles it
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) y[i] = (RAGGED && n + i < p.n_samples) ? y[i] : 0.f;
+                }
+                float* dst = ybuf + 512 * h + 8 * lane;
+                reinterpret_cast<float4*>(dst)[0] = make_float4(y[0], y[1], y[2], y[3]);
+                reinterpret_cast<float4*>(dst)[1] = make_float4(y[4], y[5], y[6], y[7]);
+                if (h == 0) asm volatile("" ::: "memory");  // the second half's loads stay behind the first half's stores
+            }
         } else {
             const int s0 = c * chunk_step;
             // the sample before a lane's vector: the last half-word of the neighbouring lane's vector (wave_shr:1), of lane 63's
@@ -611,12 +668,21 @@ __global__ __launch_bounds__(MFCC_THREADS) __attribute__((amdgpu_waves_per_eu(KW
     FrontendParams p, FrontendTables t, const int16_t* __restrict__ pcm, float* __restrict__ out, RefineList rl, RaggedArgs rg, int n_waves) {
     mfcc_wr_body<false, GeomAny, true>(p, t, pcm, out, rl, n_waves, 0, AugmentArgs{}, rg);
 }
+// float32 samples (kws_frames_f32, kws_scan_f32 and their ragged twins): the generic kernel and its ragged form, no GeomRef.
+__global__ __launch_bounds__(MFCC_THREADS) __attribute__((amdgpu_waves_per_eu(KWS_MFCC_EU, KWS_MFCC_EU))) void kws_mfcc_f32_wr_kernel(
+    FrontendParams p, FrontendTables t, const float* __restrict__ wav, float* __restrict__ out, RefineList rl, int B, int chunks_per_wave) {
+    mfcc_wr_body<false, GeomAny, false, float>(p, t, wav, out, rl, B, chunks_per_wave, AugmentArgs{});
+}
+__global__ __launch_bounds__(MFCC_THREADS) __attribute__((amdgpu_waves_per_eu(KWS_MFCC_EU, KWS_MFCC_EU))) void kws_mfcc_f32_ragged_kernel(
+    FrontendParams p, FrontendTables t, const float* __restrict__ wav, float* __restrict__ out, RefineList rl, RaggedArgs rg, int n_waves) {
+    mfcc_wr_body<false, GeomAny, true, float>(p, t, wav, out, rl, n_waves, 0, AugmentArgs{}, rg);
+}
 #ifndef KWS_MFCC_AUG_EU
 #define KWS_MFCC_AUG_EU 4
 #endif
 __global__ __launch_bounds__(MFCC_THREADS) __attribute__((amdgpu_waves_per_eu(KWS_MFCC_AUG_EU, KWS_MFCC_AUG_EU))) void kws_mfcc_augment_i16_kernel(
     FrontendParams p, FrontendTables t, AugmentArgs aug, float* __restrict__ out, RefineList rl, int B, int chunks_per_wave) {
-    mfcc_wr_body<true>(p, t, nullptr, out, rl, B, chunks_per_wave, aug);
+    mfcc_wr_body<true>(p, t, static_cast<const int16_t*>(nullptr), out, rl, B, chunks_per_wave, aug);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -751,6 +817,7 @@ int mfcc_wr_chunks_per_wave(long total_chunks, int n_chunks) {
 
 // A launch's source from its first clip b0 on: the PCM pointer moves by whole clips, the fused loader's per-clip arrays by b0.
 static const int16_t* clips_from(const int16_t* d_wav, int b0, const FrontendParams& p) { return d_wav + (size_t)b0 * p.n_samples; }
+static const float* clips_from(const float* d_wav, int b0, const FrontendParams& p) { return d_wav + (size_t)b0 * p.n_samples; }
 static AugmentArgs clips_from(AugmentArgs a, int b0, const FrontendParams&) {
     a.index += b0;
     if (a.shift) a.shift += b0;
@@ -797,8 +864,20 @@ hipError_t launch_mfcc_ragged(hipStream_t s, const FrontendParams& p, const Fron
                        mfcc_wr_lds_bytes(p), s, p, t, d_pcm, d_out, rl, rg, n_waves);
     return hipGetLastError();
 }
+hipError_t launch_mfcc_ragged(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, const RaggedArgs& rg,
+                              int n_waves, float* d_out, const RefineList& rl) {
+    if (!mfcc_wave_resident_ok(p)) return hipErrorInvalidValue;  // refused by kws_frames_ragged_f32 before it gets here
+    hipLaunchKernelGGL(kws_mfcc_f32_ragged_kernel, dim3((unsigned)((n_waves + MFCC_WAVES - 1) / MFCC_WAVES)), dim3(MFCC_THREADS),
+                       mfcc_wr_lds_bytes(p), s, p, t, d_wav, d_out, rl, rg, n_waves);
+    return hipGetLastError();
+}
+// wr_route: the recording entries (kws_frames_f32, kws_scan_f32) ask for the wavefront-resident kernel where the recording's length
+// and pointer allow it; kws_mfcc_f32 / kws_infer_f32 do not ask and stay on the tile kernels.
 hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav, int B, float* d_out,
-                       const RefineList& rl, bool) {
+                       const RefineList& rl, bool wr_route) {
+#ifndef KWS_X_MFCC_TILE_KERNEL
+    if (wr_route && mfcc_wave_resident_ok(p)) return launch_mfcc_wr(kws_mfcc_f32_wr_kernel, s, p, t, d_wav, B, d_out, rl);
+#endif
     return launch_mfcc_t(mfcc_tail6(p) ? kws_mfcc_f32_kernel : kws_mfcc_f32_any_kernel, s, p, t, d_wav, B, d_out, rl);
 }
 hipError_t launch_mfcc(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const AugmentArgs& a, int B, float* d_out,

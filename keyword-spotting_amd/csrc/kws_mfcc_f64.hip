@@ -133,8 +133,9 @@ constexpr int REFINE_WAVES = KWS_X_REFINE_WAVES;  // wavefronts per workgroup of
 // the float32 samples the fused kernel transformed through the same per-sample function, aug_sample.
 // RAGGED (kws_mfcc_refine_ragged_kernel): the entries count pairs in the packed numbering of a ragged batch, and src_of maps a
 // pair to its recording -- samples, length, frame count, first row and first pair (RaggedClip below).
+template <typename T>  // int16 PCM or float32 samples
 struct RaggedClip {
-    const int16_t* x;
+    const T* x;
     int len, frames, row0, pair0;
 };
 template <bool RAGGED, typename SrcOf>
@@ -162,7 +163,7 @@ __device__ __forceinline__ void mfcc_refine_body(const FrontendParams& p, const 
             entry = rl.list[e];
             const int pair = entry >> 2;
             if constexpr (RAGGED) {
-                const RaggedClip rc = src_of(pair);
+                const auto rc = src_of(pair);
                 FrontendParams q = p;  // the recording as one clip: its own length decides the padding and the vector loads
                 q.n_samples = rc.len;
                 q.num_frames = rc.frames;
@@ -171,7 +172,8 @@ __device__ __forceinline__ void mfcc_refine_body(const FrontendParams& p, const 
                 fa = 2 * (pair - rc.pair0);
                 has_b = fa + 1 < rc.frames;
                 const long sa = (long)fa * p.frame_step;
-                f64_load_pair<int16_t, NCT>(q, rc.x, sa, rc.x, sa + p.frame_step, has_b, X, NCT, n_used, lane, nza, nzb);
+                f64_load_pair<typename std::remove_cv<typename std::remove_pointer<decltype(rc.x)>::type>::type, NCT>(
+                    q, rc.x, sa, rc.x, sa + p.frame_step, has_b, X, NCT, n_used, lane, nza, nzb);
             } else {
                 clip = pair / pairs_per_clip;
                 fa = 2 * (pair - clip * pairs_per_clip);
@@ -245,18 +247,25 @@ __global__ __launch_bounds__(REFINE_WAVES * 64) void kws_mfcc_refine_augment_ker
 }
 // The refinement of a ragged batch: a listed pair finds its recording by a binary search over the records' first pairs (a rare
 // path: a few loads per listed pair).
+template <typename T>
+__device__ __forceinline__ RaggedClip<T> ragged_clip_of(const T* __restrict__ pcm, const RaggedArgs& rg, int pair) {
+    int lo = 0, hi = rg.R;  // rec[lo].pair_off <= pair < rec[hi].pair_off
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (rg.rec[mid].pair_off <= pair) lo = mid;
+        else hi = mid;
+    }
+    const RaggedRec rr = rg.rec[lo];
+    return RaggedClip<T>{pcm + rr.start, rr.len, rr.frames, rr.frame_off, rr.pair_off};
+}
 __global__ __launch_bounds__(REFINE_WAVES * 64) void kws_mfcc_refine_ragged_kernel(FrontendParams p, FrontendTables t, const int16_t* __restrict__ pcm,
                                                                                 float* __restrict__ out, RefineList rl, RaggedArgs rg) {
-    mfcc_refine_body<true>(p, t, out, rl, [&](int pair) {
-        int lo = 0, hi = rg.R;  // rec[lo].pair_off <= pair < rec[hi].pair_off
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (rg.rec[mid].pair_off <= pair) lo = mid;
-            else hi = mid;
-        }
-        const RaggedRec rr = rg.rec[lo];
-        return RaggedClip{pcm + rr.start, rr.len, rr.frames, rr.frame_off, rr.pair_off};
-    });
+    mfcc_refine_body<true>(p, t, out, rl, [&](int pair) { return ragged_clip_of(pcm, rg, pair); });
+}
+// The same over float32 samples (kws_frames_ragged_f32): the scalar loads of kws_mfcc_refine_kernel<float>, bounded by the recording.
+__global__ __launch_bounds__(REFINE_WAVES * 64) void kws_mfcc_refine_ragged_f32_kernel(FrontendParams p, FrontendTables t, const float* __restrict__ wav,
+                                                                                    float* __restrict__ out, RefineList rl, RaggedArgs rg) {
+    mfcc_refine_body<true>(p, t, out, rl, [&](int pair) { return ragged_clip_of(wav, rg, pair); });
 }
 
 template <typename T>
@@ -317,15 +326,24 @@ hipError_t launch_mfcc_refine(hipStream_t s, const FrontendParams& p, const Fron
     return launch_mfcc_refine_t(kws_mfcc_refine_augment_kernel, s, p, t, a, d_out, rl, B);
 }
 
-hipError_t launch_mfcc_refine_ragged(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_pcm,
-                                     const RaggedArgs& rg, float* d_out, const RefineList& rl, int B) {
+template <typename K, typename T>
+static hipError_t launch_mfcc_refine_ragged_t(K kernel, hipStream_t s, const FrontendParams& p, const FrontendTables& t, const T* d_pcm,
+                                              const RaggedArgs& rg, float* d_out, const RefineList& rl, int B) {
     const size_t lds = f64_layout(512, true, true, p.nfilt, p.numcep, REFINE_WAVES).total;
-    hipError_t e = raise_lds_limit(kws_mfcc_refine_ragged_kernel, lds);
+    hipError_t e = raise_lds_limit(kernel, lds);
     if (e != hipSuccess) return e;
     int grid = (B + 15) / 16;  // as launch_mfcc_refine_t sizes it, B = the batch in one-second clips
     grid = grid < 32 ? 32 : (grid > REFINE_GRID ? REFINE_GRID : grid);
-    hipLaunchKernelGGL(kws_mfcc_refine_ragged_kernel, dim3(grid), dim3(REFINE_WAVES * 64), lds, s, p, t, d_pcm, d_out, rl, rg);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(REFINE_WAVES * 64), lds, s, p, t, d_pcm, d_out, rl, rg);
     return hipGetLastError();
+}
+hipError_t launch_mfcc_refine_ragged(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_pcm,
+                                     const RaggedArgs& rg, float* d_out, const RefineList& rl, int B) {
+    return launch_mfcc_refine_ragged_t(kws_mfcc_refine_ragged_kernel, s, p, t, d_pcm, rg, d_out, rl, B);
+}
+hipError_t launch_mfcc_refine_ragged(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const float* d_wav,
+                                     const RaggedArgs& rg, float* d_out, const RefineList& rl, int B) {
+    return launch_mfcc_refine_ragged_t(kws_mfcc_refine_ragged_f32_kernel, s, p, t, d_wav, rg, d_out, rl, B);
 }
 
 hipError_t launch_mfcc_f64(hipStream_t s, const FrontendParams& p, const FrontendTables& t, const int16_t* d_wav, int B, float* d_out) {

@@ -1,4 +1,4 @@
-// Batches of recordings of unequal length (include/kws_hip.h: kws_host_ragged_plan, kws_frames_ragged_i16, kws_scan_ragged_i16):
+// Batches of recordings of unequal length (include/kws_hip.h: kws_host_ragged_plan, kws_frames_ragged_i16 / _f32, kws_scan_ragged_i16 / _f32):
 // the plan of a packed batch on the host, the ragged front end (kws_mfcc_i16_ragged_kernel, kws_mfcc.hip, and the refinement of
 // its flagged frames, kws_mfcc_f64.hip) and the scan of the packed frame array as ONE recording by the strided DS-CNN launch.
 // The decisions and the endpointer of a ragged batch are beside their equal-length families (kws_scan.hip, kws_segment.hip).
@@ -27,26 +27,30 @@ long long ragged_rows(const int32_t* len, int R, int frame_len, int frame_step, 
 }
 
 // The argument checks of the two device entries; nothing is launched before they pass.
-int check_ragged_batch(kws_ctx* c, const char* fn, const int16_t* d_pcm, int n_pcm, const int64_t* start, const int32_t* len, int R) {
-    const std::string f(fn);
-    if (!d_pcm || !start || !len) return fail(c, KWS_EINVAL, f + ": d_pcm / start / len is NULL");
-    if (R < 1 || n_pcm < 1) return fail(c, KWS_EINVAL, f + ": R and n_pcm must be positive");
+// src: the buffer's name in the entry's prototype ("pcm" for int16, "wav" for float32: d_pcm / n_pcm, d_wav / n_wav).
+int check_ragged_batch(kws_ctx* c, const char* fn, const char* src, const void* d_pcm, int n_pcm, const int64_t* start, const int32_t* len,
+                       int R) {
+    const std::string f(fn), d_src = std::string("d_") + src, n_src = std::string("n_") + src;
+    if (!d_pcm || !start || !len) return fail(c, KWS_EINVAL, f + ": " + d_src + " / start / len is NULL");
+    if (R < 1 || n_pcm < 1) return fail(c, KWS_EINVAL, f + ": R and " + n_src + " must be positive");
     if (R > RAGGED_MAX_R) return fail(c, KWS_EUNSUPPORTED, f + ": more than 2^20 recordings in one call");
     if (n_pcm > RAGGED_MAX_PCM) return fail(c, KWS_EUNSUPPORTED, f + ": more than 2^30 samples in the buffer");
-    if ((reinterpret_cast<uintptr_t>(d_pcm) & 15) != 0) return fail(c, KWS_EINVAL, f + ": d_pcm must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_pcm) & 15) != 0) return fail(c, KWS_EINVAL, f + ": " + d_src + " must be 16-byte aligned");
     for (int r = 0; r < R; ++r) {
         if (len[r] < 1) return fail(c, KWS_EINVAL, f + ": recording " + std::to_string(r) + " has no samples");
         if (start[r] < 0 || start[r] % 8 != 0)
             return fail(c, KWS_EINVAL, f + ": start of recording " + std::to_string(r) + " must be a non-negative multiple of 8 samples");
         if (start[r] + (int64_t)len[r] > (int64_t)n_pcm)
-            return fail(c, KWS_EINVAL, f + ": recording " + std::to_string(r) + " runs past the buffer's n_pcm samples");
+            return fail(c, KWS_EINVAL, f + ": recording " + std::to_string(r) + " runs past the buffer's " + n_src + " samples");
     }
     return KWS_OK;
 }
 
 // The ragged front end: plan, tables into context scratch, the float32 kernel and the refinement of what it flagged.
 // frames_total (may be NULL) receives the sum of the recordings' own frame counts.
-int frames_ragged(kws_ctx* c, const char* fn, const int16_t* d_pcm, const int64_t* start, const int32_t* len, int R, int row_multiple,
+// T: int16 PCM or float32 samples -- the same plan, records and launches (launch_mfcc_ragged / launch_mfcc_refine_ragged overloads).
+template <typename T>
+int frames_ragged(kws_ctx* c, const char* fn, const T* d_pcm, const int64_t* start, const int32_t* len, int R, int row_multiple,
                   float* d_feat_out, long long* frames_total) {
     const std::string f(fn);
     FrontendParams p = c->fp;
@@ -109,6 +113,64 @@ int upload_ragged_tables(kws_ctx* c, const void* host, size_t bytes, const char*
     return KWS_OK;
 }
 
+// The device entries, shared by the int16 and the float32 source (fn / src: the entry's and its buffer's names in the error text).
+template <typename T>
+static int frames_ragged_entry(kws_ctx* c, const char* fn, const char* src, const T* d_pcm, int n_pcm, const int64_t* start, const int32_t* len,
+                               int R, int row_multiple, float* d_feat_out) {
+    const std::string f(fn);
+    if (!c) return KWS_EINVAL;
+    int rc = check_ragged_batch(c, fn, src, d_pcm, n_pcm, start, len, R);
+    if (rc) return rc;
+    if (!d_feat_out) return fail(c, KWS_EINVAL, f + ": d_feat_out is NULL");
+    if (row_multiple < 1) return fail(c, KWS_EINVAL, f + ": row_multiple must be positive");
+    if (!c->fe_ready) return fail(c, KWS_ESTATE, f + ": front end not configured");
+    return frames_ragged(c, fn, d_pcm, start, len, R, row_multiple, d_feat_out, nullptr);
+}
+
+template <typename Sample>
+static int scan_ragged_entry(kws_ctx* c, const char* fn, const char* src, const Sample* d_pcm, int n_pcm, const int64_t* start, const int32_t* len,
+                             int R, int hop_frames, float* d_logits, int32_t* d_label, float* d_feat_out) {
+    const std::string f(fn);
+    if (!c) return KWS_EINVAL;
+    int rc = check_ragged_batch(c, fn, src, d_pcm, n_pcm, start, len, R);
+    if (rc) return rc;
+    if (!d_logits) return fail(c, KWS_EINVAL, f + ": d_logits is NULL");
+    if (hop_frames < 1) return fail(c, KWS_EINVAL, f + ": hop_frames must be positive");
+    if (!c->fe_ready || !c->model_ready) return fail(c, KWS_ESTATE, f + ": front end or model not configured");
+    if (c->fp.num_frames != IN_T || c->fp.numcep != IN_F)
+        return fail(c, KWS_EUNSUPPORTED, f + ": the strided DS-CNN kernel is built for windows of 99 x 10 features");
+    if (c->mw.in_channels != 1)
+        return fail(c, KWS_EUNSUPPORTED, f + ": the MFCC front end yields one channel; the model was loaded with more");
+    if (c->pw_math != KWS_PW_PAIR_F16 && c->pw_math != KWS_PW_SPLIT_BF16)
+        return fail(c, KWS_EUNSUPPORTED, f + ": needs KWS_PW_PAIR_F16 or KWS_PW_SPLIT_BF16");
+    const int T = c->fp.num_frames;
+    std::vector<int32_t> windows(R);
+    std::vector<int32_t> frame_off(R + 1);
+    int W_pack = 0;
+    rc = kws_host_ragged_plan(len, R, c->fp.frame_len, c->fp.frame_step, T, hop_frames, nullptr, frame_off.data(), windows.data(), nullptr, &W_pack);
+    if (rc) return fail(c, rc, f + ": more than 2^28 rows in the packed frame array");
+    const long long F_pack = frame_off[R];
+    if ((long long)W_pack > RAGGED_MAX_WINDOWS) return fail(c, KWS_EUNSUPPORTED, f + ": more than 2^30 packed windows");
+    long long any_window = 0;
+    for (int r = 0; r < R; ++r) any_window += windows[r];
+    HIP_TRY(c, hipSetDevice(c->device));
+    float* feat = d_feat_out;
+    if (!feat) {
+        rc = grow_device_buffer(c, c->d_scan_ws, c->scan_ws_floats, (size_t)F_pack * c->fp.numcep, fn, "frame workspace");
+        if (rc) return rc;
+        feat = c->d_scan_ws;
+    }
+    rc = frames_ragged(c, fn, d_pcm, start, len, R, hop_frames, feat, nullptr);
+    if (rc) return rc;
+    if (any_window == 0) return KWS_OK;  // every recording is shorter than a window: the frames are all there is
+    // the packed frame array as ONE recording of F_pack frames: window win_off[r] + w is window w of recording r
+    const ScanWindows sw = {(unsigned)W_pack, W_pack == 1 ? 0xffffffffu : (unsigned)((1ull << 32) / (unsigned)W_pack),
+                            (unsigned)F_pack * (unsigned)IN_F, (unsigned)hop_frames * (unsigned)IN_F};
+    ProfScope ps(c, KWS_K_DSCNN);
+    HIP_TRY(c, launch_dscnn_scan(c->stream, c->mw, feat, W_pack, d_logits, d_label, c->pw_math, c->n_cu, sw));
+    return KWS_OK;
+}
+
 #pragma GCC visibility push(default)
 extern "C" {
 
@@ -137,58 +199,29 @@ int kws_host_ragged_plan(const int32_t* len, int R, int frame_len, int frame_ste
 int kws_frames_ragged_i16(kws_ctx* c, const int16_t* d_pcm, int n_pcm, const int64_t* start, const int32_t* len, int R, int row_multiple,
                           float* d_feat_out) {
     KWS_GUARD_BEGIN
-    if (!c) return KWS_EINVAL;
-    int rc = check_ragged_batch(c, "kws_frames_ragged_i16", d_pcm, n_pcm, start, len, R);
-    if (rc) return rc;
-    if (!d_feat_out) return fail(c, KWS_EINVAL, "kws_frames_ragged_i16: d_feat_out is NULL");
-    if (row_multiple < 1) return fail(c, KWS_EINVAL, "kws_frames_ragged_i16: row_multiple must be positive");
-    if (!c->fe_ready) return fail(c, KWS_ESTATE, "kws_frames_ragged_i16: front end not configured");
-    return frames_ragged(c, "kws_frames_ragged_i16", d_pcm, start, len, R, row_multiple, d_feat_out, nullptr);
+    return frames_ragged_entry(c, "kws_frames_ragged_i16", "pcm", d_pcm, n_pcm, start, len, R, row_multiple, d_feat_out);
     KWS_GUARD_END(c, "kws_frames_ragged_i16")
+}
+
+int kws_frames_ragged_f32(kws_ctx* c, const float* d_wav, int n_wav, const int64_t* start, const int32_t* len, int R, int row_multiple,
+                          float* d_feat_out) {
+    KWS_GUARD_BEGIN
+    return frames_ragged_entry(c, "kws_frames_ragged_f32", "wav", d_wav, n_wav, start, len, R, row_multiple, d_feat_out);
+    KWS_GUARD_END(c, "kws_frames_ragged_f32")
 }
 
 int kws_scan_ragged_i16(kws_ctx* c, const int16_t* d_pcm, int n_pcm, const int64_t* start, const int32_t* len, int R, int hop_frames,
                         float* d_logits, int32_t* d_label, float* d_feat_out) {
     KWS_GUARD_BEGIN
-    if (!c) return KWS_EINVAL;
-    int rc = check_ragged_batch(c, "kws_scan_ragged_i16", d_pcm, n_pcm, start, len, R);
-    if (rc) return rc;
-    if (!d_logits) return fail(c, KWS_EINVAL, "kws_scan_ragged_i16: d_logits is NULL");
-    if (hop_frames < 1) return fail(c, KWS_EINVAL, "kws_scan_ragged_i16: hop_frames must be positive");
-    if (!c->fe_ready || !c->model_ready) return fail(c, KWS_ESTATE, "kws_scan_ragged_i16: front end or model not configured");
-    if (c->fp.num_frames != IN_T || c->fp.numcep != IN_F)
-        return fail(c, KWS_EUNSUPPORTED, "kws_scan_ragged_i16: the strided DS-CNN kernel is built for windows of 99 x 10 features");
-    if (c->mw.in_channels != 1)
-        return fail(c, KWS_EUNSUPPORTED, "kws_scan_ragged_i16: the MFCC front end yields one channel; the model was loaded with more");
-    if (c->pw_math != KWS_PW_PAIR_F16 && c->pw_math != KWS_PW_SPLIT_BF16)
-        return fail(c, KWS_EUNSUPPORTED, "kws_scan_ragged_i16: needs KWS_PW_PAIR_F16 or KWS_PW_SPLIT_BF16");
-    const int T = c->fp.num_frames;
-    std::vector<int32_t> windows(R);
-    std::vector<int32_t> frame_off(R + 1);
-    int W_pack = 0;
-    rc = kws_host_ragged_plan(len, R, c->fp.frame_len, c->fp.frame_step, T, hop_frames, nullptr, frame_off.data(), windows.data(), nullptr, &W_pack);
-    if (rc) return fail(c, rc, "kws_scan_ragged_i16: more than 2^28 rows in the packed frame array");
-    const long long F_pack = frame_off[R];
-    if ((long long)W_pack > RAGGED_MAX_WINDOWS) return fail(c, KWS_EUNSUPPORTED, "kws_scan_ragged_i16: more than 2^30 packed windows");
-    long long any_window = 0;
-    for (int r = 0; r < R; ++r) any_window += windows[r];
-    HIP_TRY(c, hipSetDevice(c->device));
-    float* feat = d_feat_out;
-    if (!feat) {
-        rc = grow_device_buffer(c, c->d_scan_ws, c->scan_ws_floats, (size_t)F_pack * c->fp.numcep, "kws_scan_ragged_i16", "frame workspace");
-        if (rc) return rc;
-        feat = c->d_scan_ws;
-    }
-    rc = frames_ragged(c, "kws_scan_ragged_i16", d_pcm, start, len, R, hop_frames, feat, nullptr);
-    if (rc) return rc;
-    if (any_window == 0) return KWS_OK;  // every recording is shorter than a window: the frames are all there is
-    // the packed frame array as ONE recording of F_pack frames: window win_off[r] + w is window w of recording r
-    const ScanWindows sw = {(unsigned)W_pack, W_pack == 1 ? 0xffffffffu : (unsigned)((1ull << 32) / (unsigned)W_pack),
-                            (unsigned)F_pack * (unsigned)IN_F, (unsigned)hop_frames * (unsigned)IN_F};
-    ProfScope ps(c, KWS_K_DSCNN);
-    HIP_TRY(c, launch_dscnn_scan(c->stream, c->mw, feat, W_pack, d_logits, d_label, c->pw_math, c->n_cu, sw));
-    return KWS_OK;
+    return scan_ragged_entry(c, "kws_scan_ragged_i16", "pcm", d_pcm, n_pcm, start, len, R, hop_frames, d_logits, d_label, d_feat_out);
     KWS_GUARD_END(c, "kws_scan_ragged_i16")
+}
+
+int kws_scan_ragged_f32(kws_ctx* c, const float* d_wav, int n_wav, const int64_t* start, const int32_t* len, int R, int hop_frames,
+                        float* d_logits, int32_t* d_label, float* d_feat_out) {
+    KWS_GUARD_BEGIN
+    return scan_ragged_entry(c, "kws_scan_ragged_f32", "wav", d_wav, n_wav, start, len, R, hop_frames, d_logits, d_label, d_feat_out);
+    KWS_GUARD_END(c, "kws_scan_ragged_f32")
 }
 
 }  // extern "C"

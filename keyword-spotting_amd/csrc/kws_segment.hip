@@ -1,4 +1,4 @@
-// Utterances from recordings (include/kws_hip.h: kws_frames_i16, kws_segment_f32, kws_cut_i16) -- the device side of the
+// Utterances from recordings (include/kws_hip.h: kws_frames_i16 / _f32, kws_segment_f32, kws_cut_i16 / _f32) -- the device side of the
 // reference's record-then-classify loop (kws/inference/inference_local.py:114-192): the MFCC pass of a scan on its own, the
 // energy endpointer walked over a whole frame array with the reference's start point and time-out, and normalize + fix_length
 // for a list of sample spans.  What follows a clip (kws_infer_i16) is elsewhere; nothing here touches another unit's kernels.
@@ -179,38 +179,73 @@ __global__ __launch_bounds__(64) void kws_segment_walk_ragged_kernel(const unsig
                  max_utts, count_out, r, lane);
 }
 
+// Span u of d_span = (recording, start, end), as both cut kernels read it: start and end clamped to [0, n_total], a recording
+// index outside [0, R) refused (workgroup-uniform); returns the span's first sample in the [R, n_total] buffer x.
+template <typename T>
+__device__ __forceinline__ const T* cut_span(const T* __restrict__ x, const int32_t* __restrict__ span, int u, int R, int n_total, bool& in_range,
+                                             int& len) {
+    const int r = span[3 * (size_t)u];
+    int start = span[3 * (size_t)u + 1], end = span[3 * (size_t)u + 2];
+    start = start < 0 ? 0 : (start > n_total ? n_total : start);
+    end = end < 0 ? 0 : (end > n_total ? n_total : end);
+    in_range = r >= 0 && r < R;  // workgroup-uniform
+    len = in_range && end > start ? end - start : 0;
+    return x + (in_range ? (size_t)r * n_total + start : 0);
+}
+
 // normalize then fix_length (ep_cut_clip) of one span per workgroup.  A span starts at any sample: 2-byte loads.
 __global__ __launch_bounds__(CUT_THREADS) void kws_cut_i16_kernel(const int16_t* __restrict__ pcm, int R, int n_total,
                                                                   const int32_t* __restrict__ span, int normalize_to,
                                                                   int16_t* __restrict__ clips, int n_out, int32_t* __restrict__ peak_out) {
     const int u = blockIdx.x;
-    const int r = span[3 * (size_t)u];
-    int start = span[3 * (size_t)u + 1], end = span[3 * (size_t)u + 2];
-    start = start < 0 ? 0 : (start > n_total ? n_total : start);
-    end = end < 0 ? 0 : (end > n_total ? n_total : end);
-    const bool in_range = r >= 0 && r < R;  // workgroup-uniform
-    const int len = in_range && end > start ? end - start : 0;
-    const int16_t* x = pcm + (in_range ? (size_t)r * n_total + start : 0);
+    bool in_range;
+    int len;
+    const int16_t* x = cut_span(pcm, span, u, R, n_total, in_range, len);
     ep_cut_clip<CUT_THREADS>([&](unsigned i) -> int { return x[i]; }, len, in_range, normalize_to, clips + (size_t)u * n_out, n_out, peak_out, u);
+}
+// The same over float32 samples (ep_cut_clip_f32: a float32 peak, a float64 scale, one rounding to float32 and no truncation).
+__global__ __launch_bounds__(CUT_THREADS) void kws_cut_f32_kernel(const float* __restrict__ wav, int R, int n_total,
+                                                                  const int32_t* __restrict__ span, float normalize_to,
+                                                                  float* __restrict__ clips, int n_out, float* __restrict__ peak_out) {
+    const int u = blockIdx.x;
+    bool in_range;
+    int len;
+    const float* x = cut_span(wav, span, u, R, n_total, in_range, len);
+    ep_cut_clip_f32<CUT_THREADS>([&](unsigned i) -> float { return x[i]; }, len, in_range, normalize_to, clips + (size_t)u * n_out, n_out, peak_out, u);
 }
 
 }  // namespace
+
+// kws_frames_i16 / kws_frames_f32: the same checks, limits and launches over int16 PCM or float32 samples; f names the entry in
+// the error text, src_name its source pointer.
+template <typename T>
+static int frames_recordings(kws_ctx* c, const std::string& f, const char* src_name, const T* d_pcm, int R, int n_total, float* d_feat_out) {
+    if (!c) return KWS_EINVAL;
+    if (!d_pcm || !d_feat_out) return fail(c, KWS_EINVAL, f + ": " + src_name + " / d_feat_out is NULL");
+    if (R < 1 || n_total < 1) return fail(c, KWS_EINVAL, f + ": R and n_total must be positive");
+    if (!c->fe_ready) return fail(c, KWS_ESTATE, f + ": front end not configured");
+    if (n_total > (1 << 30)) return fail(c, KWS_EUNSUPPORTED, f + ": more than 2^30 samples per recording");
+    FrontendParams p = c->fp;  // the context's geometry and arithmetic; the recording is one clip of n_total samples
+    set_clip_length(p, n_total);
+    const int F = p.num_frames;
+    if ((unsigned long long)R * F > (1ull << 28)) return fail(c, KWS_EUNSUPPORTED, f + ": more than 2^28 frames in one call");
+    // the refinement's grid: the batch in clips of the context's own length, as kws_scan_i16 sizes it
+    return run_frontend(c, p, d_pcm, R, d_feat_out, (int)((unsigned long long)R * F / c->fp.num_frames + 1), /*recording_f32=*/true);
+}
 
 #pragma GCC visibility push(default)
 extern "C" {
 
 int kws_frames_i16(kws_ctx* c, const int16_t* d_pcm, int R, int n_total, float* d_feat_out) {
-    if (!c) return KWS_EINVAL;
-    if (!d_pcm || !d_feat_out) return fail(c, KWS_EINVAL, "kws_frames_i16: d_pcm / d_feat_out is NULL");
-    if (R < 1 || n_total < 1) return fail(c, KWS_EINVAL, "kws_frames_i16: R and n_total must be positive");
-    if (!c->fe_ready) return fail(c, KWS_ESTATE, "kws_frames_i16: front end not configured");
-    if (n_total > (1 << 30)) return fail(c, KWS_EUNSUPPORTED, "kws_frames_i16: more than 2^30 samples per recording");
-    FrontendParams p = c->fp;  // the context's geometry and arithmetic; the recording is one clip of n_total samples
-    set_clip_length(p, n_total);
-    const int F = p.num_frames;
-    if ((unsigned long long)R * F > (1ull << 28)) return fail(c, KWS_EUNSUPPORTED, "kws_frames_i16: more than 2^28 frames in one call");
-    // the refinement's grid: the batch in clips of the context's own length, as kws_scan_i16 sizes it
-    return run_frontend(c, p, d_pcm, R, d_feat_out, (int)((unsigned long long)R * F / c->fp.num_frames + 1));
+    KWS_GUARD_BEGIN
+    return frames_recordings(c, "kws_frames_i16", "d_pcm", d_pcm, R, n_total, d_feat_out);
+    KWS_GUARD_END(c, "kws_frames_i16")
+}
+
+int kws_frames_f32(kws_ctx* c, const float* d_wav, int R, int n_total, float* d_feat_out) {
+    KWS_GUARD_BEGIN
+    return frames_recordings(c, "kws_frames_f32", "d_wav", d_wav, R, n_total, d_feat_out);
+    KWS_GUARD_END(c, "kws_frames_f32")
 }
 
 int kws_segment_f32(kws_ctx* c, const float* d_feat, int R, int F_total, int n_total, float log_energy_threshold, int on_window,
@@ -299,6 +334,19 @@ int kws_cut_i16(kws_ctx* c, const int16_t* d_pcm, int R, int n_total, const int3
     if (int rc = check_normalize_to(c, "kws_cut_i16", normalize_to)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     hipLaunchKernelGGL(kws_cut_i16_kernel, dim3(U), dim3(CUT_THREADS), 0, c->stream, d_pcm, R, n_total, d_span, normalize_to, d_clips,
+                       n_out, d_peak);
+    HIP_TRY(c, hipGetLastError());
+    return KWS_OK;
+}
+
+int kws_cut_f32(kws_ctx* c, const float* d_wav, int R, int n_total, const int32_t* d_span, int U, float normalize_to, float* d_clips,
+                int n_out, float* d_peak) {
+    if (!c) return KWS_EINVAL;
+    if (!d_wav || !d_span || !d_clips) return fail(c, KWS_EINVAL, "kws_cut_f32: d_wav / d_span / d_clips is NULL");
+    if (U < 1 || R < 1 || n_total < 1 || n_out < 1) return fail(c, KWS_EINVAL, "kws_cut_f32: U, R, n_total and n_out must be positive");
+    if (!(normalize_to >= 0.f) || normalize_to > 3.402823466e38f) return fail(c, KWS_EINVAL, "kws_cut_f32: normalize_to must be finite and not negative");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(kws_cut_f32_kernel, dim3(U), dim3(CUT_THREADS), 0, c->stream, d_wav, R, n_total, d_span, normalize_to, d_clips,
                        n_out, d_peak);
     HIP_TRY(c, hipGetLastError());
     return KWS_OK;

@@ -94,14 +94,19 @@ SIGNATURES = {
     "kws_softmax_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, _f32p]),
     "kws_stream_smooth_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, _f32p, _i32p]),
     "kws_scan_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, _f32p]),
+    "kws_scan_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, _f32p]),
     "kws_scan_detect_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _f32p, _i32p, _i32p,
                                       _f32p, C.c_int, _i32p]),
     "kws_frames_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, C.c_int, _f32p]),
+    "kws_frames_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, _f32p]),
     "kws_segment_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, C.c_int,
                                   _i32p]),
     "kws_cut_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _i16p, C.c_int, _i32p]),
+    "kws_cut_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, _i32p, C.c_int, C.c_float, _f32p, C.c_int, _f32p]),
     "kws_frames_ragged_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, _h_i64p, _h_i32p, C.c_int, C.c_int, _f32p]),
     "kws_scan_ragged_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, _h_i64p, _h_i32p, C.c_int, C.c_int, _f32p, _i32p, _f32p]),
+    "kws_frames_ragged_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, _h_i64p, _h_i32p, C.c_int, C.c_int, _f32p]),
+    "kws_scan_ragged_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, _h_i64p, _h_i32p, C.c_int, C.c_int, _f32p, _i32p, _f32p]),
     "kws_scan_detect_ragged_f32": (C.c_int, [_c_ctx, _f32p, _h_i32p, _h_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _f32p,
                                              _i32p, _i32p, _f32p, C.c_int, _i32p]),
     "kws_segment_ragged_f32": (C.c_int, [_c_ctx, _f32p, _h_i32p, _h_i32p, _h_i32p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -462,6 +467,12 @@ class Context:
         self._check(self._lib.kws_scan_i16(self._h, _ptr(pcm), int(pcm.shape[0]), int(pcm.shape[1]), int(hop_frames), _ptr(logits),
                                            p(label), p(feat)), ModelError)
 
+    def scan_f32(self, wav, hop_frames, logits, label=None, feat=None):
+        """``kws_scan_f32``: ``scan_i16`` over ``wav`` float32 [R, n_total] on the device, the samples taken as they are."""
+        p = lambda t: _ptr(t) if t is not None else None
+        self._check(self._lib.kws_scan_f32(self._h, _ptr(wav), int(wav.shape[0]), int(wav.shape[1]), int(hop_frames), _ptr(logits),
+                                           p(label), p(feat)), ModelError)
+
     def scan_detect_f32(self, logits, smooth_window, first_keyword, threshold, refractory, event_count, event_window=None,
                         event_label=None, event_score=None, max_events=0, smoothed=None):
         """``kws_scan_detect_f32``: ``logits`` float32 [R, W, C] -> smoothed posteriors, candidates and events with a refractory
@@ -477,6 +488,10 @@ class Context:
         """``kws_frames_i16``: ``pcm`` int16 [R, n_total] on the device -> ``feat`` float32 [R, F_total, numcep], each recording
         one clip of the context's front end (``host_scan_shape`` gives F_total)."""
         self._check(self._lib.kws_frames_i16(self._h, _ptr(pcm), int(pcm.shape[0]), int(pcm.shape[1]), _ptr(feat)), AudioProcessingError)
+
+    def frames_f32(self, wav, feat):
+        """``kws_frames_f32``: ``frames_i16`` over ``wav`` float32 [R, n_total] on the device."""
+        self._check(self._lib.kws_frames_f32(self._h, _ptr(wav), int(wav.shape[0]), int(wav.shape[1]), _ptr(feat)), AudioProcessingError)
 
     def segment_f32(self, feat, n_total, threshold, count, utt=None, max_utts=0, on_window=40, off_window=80, pre_roll=60,
                     max_frames=1000):
@@ -494,6 +509,13 @@ class Context:
                                           int(normalize_to), _ptr(clips), int(clips.shape[1]), _ptr(peak) if peak is not None else None),
                     AudioProcessingError)
 
+    def cut_f32(self, wav, span, clips, normalize_to=0.5, peak=None):
+        """``kws_cut_f32``: ``cut_i16`` over ``wav`` float32 [R, n_total] into ``clips`` float32 [U, n_out]; ``normalize_to`` and
+        ``peak`` (float32 [U] or None) are in full-scale units (0.5 is the reference's 16384), and nothing is truncated."""
+        self._check(self._lib.kws_cut_f32(self._h, _ptr(wav), int(wav.shape[0]), int(wav.shape[1]), _ptr(span), int(span.shape[0]),
+                                          float(normalize_to), _ptr(clips), int(clips.shape[1]), _ptr(peak) if peak is not None else None),
+                    AudioProcessingError)
+
     # -- batches of recordings of unequal length ---------------------------------------------------
     def frames_ragged_i16(self, pcm, start, length, row_multiple, feat):
         """``kws_frames_ragged_i16``: ``pcm`` int16 (any shape, contiguous) on the device holds recording r at samples
@@ -509,6 +531,19 @@ class Context:
         p = lambda t: _ptr(t) if t is not None else None
         st, ln = _host_i64(start), _host_i32(length)
         self._check(self._lib.kws_scan_ragged_i16(self._h, _ptr(pcm), int(pcm.numel()), _as(st, C.c_int64), _as(ln, C.c_int32), len(ln),
+                                                  int(hop_frames), _ptr(logits), p(label), p(feat)), ModelError)
+
+    def frames_ragged_f32(self, wav, start, length, row_multiple, feat):
+        """``kws_frames_ragged_f32``: ``frames_ragged_i16`` over ``wav`` float32 (any shape, contiguous) on the device."""
+        st, ln = _host_i64(start), _host_i32(length)
+        self._check(self._lib.kws_frames_ragged_f32(self._h, _ptr(wav), int(wav.numel()), _as(st, C.c_int64), _as(ln, C.c_int32), len(ln),
+                                                    int(row_multiple), _ptr(feat)), AudioProcessingError)
+
+    def scan_ragged_f32(self, wav, start, length, hop_frames, logits, label=None, feat=None):
+        """``kws_scan_ragged_f32``: ``scan_ragged_i16`` over ``wav`` float32 (any shape, contiguous) on the device."""
+        p = lambda t: _ptr(t) if t is not None else None
+        st, ln = _host_i64(start), _host_i32(length)
+        self._check(self._lib.kws_scan_ragged_f32(self._h, _ptr(wav), int(wav.numel()), _as(st, C.c_int64), _as(ln, C.c_int32), len(ln),
                                                   int(hop_frames), _ptr(logits), p(label), p(feat)), ModelError)
 
     def scan_detect_ragged_f32(self, logits, win_off, windows, smooth_window, first_keyword, threshold, refractory, event_count,

@@ -53,7 +53,7 @@ class Utterance:
     """One utterance ``KeywordSpotter.segment`` found: where it lies in its recording (seconds), why it closed and what the
     model says about its normalised, one-second clip.  ``start_s`` is ``pre_roll`` frames before ``open_s``, the frame at which
     the endpointer triggered; ``end_s`` is the end of the closing frame ``close_s`` starts; ``peak`` is the largest sample
-    magnitude of the span before normalisation."""
+    magnitude of the span before normalisation: an int for int16 PCM, a float in full-scale units for float32 samples."""
     recording: int
     start_s: float
     end_s: float
@@ -63,25 +63,32 @@ class Utterance:
     label: int
     word: str
     logits: np.ndarray  # float32 [C]
-    peak: int
+    peak: float  # int for int16 PCM
 
 
-def _classify_spans(ctx, device, words, num_classes: int, clip_samples: int, rate: float, frame_step: int, rows, cut) -> List[Utterance]:
+def _classify_spans(ctx, device, words, num_classes: int, clip_samples: int, rate: float, frame_step: int, rows, cut,
+                    f32: bool = False) -> List[Utterance]:
     """The tail ``segment`` and ``pop_utterances`` share: ``rows`` of ``(recording, start, end, open, close, reason)``, samples
     and frames; ``cut(clips, peaks)`` launches the cut of row ``u`` into ``clips[u]`` and ``peaks[u]``.  Then the model once per
-    clip and ONE read of logits, labels and peaks."""
+    clip and ONE read of logits, labels and peaks.  ``f32``: float32 clips and peaks (``kws_cut_f32``, ``kws_infer_f32``)."""
     U, C = len(rows), num_classes
-    clips = torch.empty((U, clip_samples), dtype=torch.int16, device=device)
-    out = torch.empty((U * (C + 2),), dtype=torch.float32, device=device)  # logits [U, C], then labels [U] and peaks [U] as int32
+    clips = torch.empty((U, clip_samples), dtype=torch.float32 if f32 else torch.int16, device=device)
+    out = torch.empty((U * (C + 2),), dtype=torch.float32, device=device)  # logits [U, C], then labels [U] (int32) and peaks [U]
     logits, ints = out[:U * C].view(U, C), out[U * C:].view(torch.int32)
     torch.cuda.current_stream(device).synchronize()  # a context may run on its own stream
-    cut(clips, ints[U:])
-    ctx.infer_i16(clips, logits, ints[:U])
+    if f32:
+        cut(clips, out[U * C + U:])
+        ctx.infer_f32(clips, logits, ints[:U])
+    else:
+        cut(clips, ints[U:])
+        ctx.infer_i16(clips, logits, ints[:U])
     ctx.sync()
     host = out.cpu()  # the one read
     logits, ints = host[:U * C].view(U, C).numpy(), host[U * C:].view(torch.int32).numpy()
+    peaks = host[U * C + U:].numpy() if f32 else ints[U:]
     return [Utterance(int(r), int(start) / rate, int(end) / rate, int(opened) * frame_step / rate, int(closed) * frame_step / rate,
-                      UTTERANCE_REASONS[int(reason)], int(ints[u]), words[int(ints[u])], logits[u].copy(), int(ints[U + u]))
+                      UTTERANCE_REASONS[int(reason)], int(ints[u]), words[int(ints[u])], logits[u].copy(),
+                      float(peaks[u]) if f32 else int(peaks[u]))
             for u, (r, start, end, opened, closed, reason) in enumerate(rows)]
 
 
@@ -275,29 +282,43 @@ class KeywordSpotter:
         are returned.  A recording shorter than one window raises ``ModelError``.  ``sample_rate``: the rate of ``pcm`` when it
         is not the configured one; the recordings are then resampled on the device to their natural length at the configured
         rate (``kws_resample_i16``) and the result is scanned, so window and event times stay in seconds of the recording."""
+        return self._scan(self._recordings(pcm, "scan"), "scan", hop_frames, smooth_window, threshold, refractory, first_keyword,
+                          max_events, sample_rate)
+
+    def scan_f32(self, signal, hop_frames: int = 1, smooth_window: int = 1, threshold: Optional[float] = None, refractory: int = 50,
+                 first_keyword: int = 2, max_events: int = 1024, sample_rate: Optional[int] = None) -> ScanResult:
+        """``scan`` for float32 samples in [-1, 1], the reference's native sample type: ``signal`` float32 ``[n]`` or ``[R, n]``, a
+        host array or a device tensor, taken as it is -- nothing is quantised (``kws_scan_f32``; ``sample_rate`` goes through
+        ``kws_resample_f32``).  For ``signal = pcm / 32768`` the result equals ``scan(pcm)`` bit for bit.  Anything that is not
+        float32 raises ``ModelError``."""
+        return self._scan(self._recordings(signal, "scan_f32", f32=True), "scan_f32", hop_frames, smooth_window, threshold, refractory,
+                          first_keyword, max_events, sample_rate)
+
+    def _scan(self, x: torch.Tensor, what: str, hop_frames, smooth_window, threshold, refractory, first_keyword, max_events,
+              sample_rate) -> ScanResult:
+        """``scan`` / ``scan_f32`` behind their argument's type check; the sample type of ``x`` picks the entries."""
         from kws import _native
 
-        x = self._recordings(pcm, "scan")
         if int(hop_frames) < 1:
-            raise ModelError("scan: hop_frames must be at least 1")
+            raise ModelError(f"{what}: hop_frames must be at least 1")
         if threshold is not None:
             if not 1 <= int(smooth_window) <= 256:
-                raise ModelError("scan: smooth_window must be in [1, 256]")
+                raise ModelError(f"{what}: smooth_window must be in [1, 256]")
             if int(refractory) < 1 or int(first_keyword) < 0 or int(max_events) < 0:
-                raise ModelError("scan: need refractory >= 1, first_keyword >= 0 and max_events >= 0")
+                raise ModelError(f"{what}: need refractory >= 1, first_keyword >= 0 and max_events >= 0")
         cfg = self.config
-        x = self._at_configured_rate(x, sample_rate, "scan")
+        x = self._at_configured_rate(x, sample_rate, what)
         frame_len, frame_step = _round_half_up(cfg.frame_length * cfg.sample_rate), _round_half_up(cfg.frame_step * cfg.sample_rate)
         R, n = int(x.shape[0]), int(x.shape[1])
         frames, W = (0, 0) if n < 1 else _native.host_scan_shape(n, frame_len, frame_step, WINDOW_FRAMES, int(hop_frames))
         if W < 1:
-            raise ModelError(f"scan: a recording of {n} samples ({frames} frames) is shorter than one window of {WINDOW_FRAMES} frames")
+            raise ModelError(f"{what}: a recording of {n} samples ({frames} frames) is shorter than one window of {WINDOW_FRAMES} frames")
         ctx = self.model._context(self.device.index or 0)
         x = x.to(self.device).contiguous()
         C = self.model.num_classes
         logits = torch.empty((R, W, C), dtype=torch.float32, device=self.device)
         labels = torch.empty((R, W), dtype=torch.int32, device=self.device)
-        ctx.scan_i16(x, int(hop_frames), logits, labels)
+        (ctx.scan_f32 if x.dtype == torch.float32 else ctx.scan_i16)(x, int(hop_frames), logits, labels)
         start_s, end_s = scan_window_times(W, int(hop_frames), frame_len, frame_step, cfg.sample_rate, WINDOW_FRAMES, n)
         events = None
         if threshold is not None:
@@ -313,11 +334,18 @@ class KeywordSpotter:
                        for i in range(min(int(count[r]), m))] for r in range(R)]
         return ScanResult(labels.cpu().numpy(), logits.cpu().numpy(), start_s, events)
 
-    def scan_file(self, path: str, resample: bool = False, **kwargs) -> ScanResult:
+    def scan_file(self, path: str, resample: bool = False, decode: str = "pcm16", **kwargs) -> ScanResult:
         """``scan`` over a whole wav file (no trimming or padding to a clip).  The file must be 16-bit mono PCM at the
         configured rate: anything else raises ``AudioProcessingError`` with the reason.  With ``resample=True`` a 16-bit mono
         file at another rate is uploaded at its own rate and resampled on the device (``scan`` with ``sample_rate``); any other
-        encoding at another rate is still refused -- ``kws_scan_i16`` takes int16 and there is no float32 scan."""
+        encoding at another rate is still refused under this default ``decode``, in the words it always had.
+
+        ``decode="any"``: ``read_wav`` decodes the file.  16-bit mono goes down the int16 path unchanged; every other encoding
+        (24-bit, 32-bit, float, stereo) is float32 mono and goes down the float path (``scan_f32``), and with ``resample=True`` the
+        rate change runs on the device in the file's own sample type."""
+        if self._decode_mode(decode, "scan_file"):
+            x, rate = self._decode_any(path, resample, "scan_file")
+            return (self.scan if x.dtype == np.int16 else self.scan_f32)(x, sample_rate=rate, **kwargs)
         if resample:
             x, rate = read_wav(path)
             if rate != self.config.sample_rate:
@@ -330,26 +358,43 @@ class KeywordSpotter:
             raise AudioProcessingError(f"{path}: {x.shape[1]} channels; scan_file takes mono files")
         return self.scan(x, **kwargs)
 
-    def _recordings(self, pcm, what: str) -> torch.Tensor:
-        """int16 ``[n]`` or ``[R, n]``, host array or device tensor -> an int16 tensor ``[R, n]`` (the checks of ``scan``)."""
+    def _recordings(self, pcm, what: str, f32: bool = False) -> torch.Tensor:
+        """int16 ``[n]`` or ``[R, n]``, host array or device tensor -> an int16 tensor ``[R, n]`` (the checks of ``scan``);
+        ``f32``: the same for float32 samples (the checks of ``scan_f32``)."""
+        kind, t_dtype, n_dtype = ("float32 samples", torch.float32, np.float32) if f32 else ("int16 PCM", torch.int16, np.int16)
         if torch.is_tensor(pcm):
-            if pcm.dtype != torch.int16:
-                raise ModelError(f"{what} expects int16 PCM, got {pcm.dtype}")
+            if pcm.dtype != t_dtype:
+                raise ModelError(f"{what} expects {kind}, got {pcm.dtype}")
             x = pcm
         else:
             a = np.asarray(pcm)
-            if a.dtype != np.int16:
-                raise ModelError(f"{what} expects int16 PCM, got {a.dtype}")
+            if a.dtype != n_dtype:
+                raise ModelError(f"{what} expects {kind}, got {a.dtype}")
             x = torch.from_numpy(np.ascontiguousarray(a))
         if x.dim() == 1:
             x = x[None, :]
         if x.dim() != 2 or x.shape[0] < 1:
-            raise ModelError(f"{what} expects int16 [n] or [R, n], got shape {tuple(x.shape)}")
+            raise ModelError(f"{what} expects {'float32' if f32 else 'int16'} [n] or [R, n], got shape {tuple(x.shape)}")
         return x
+
+    @staticmethod
+    def _decode_mode(decode: str, what: str) -> bool:
+        """The ``decode`` argument of the file methods -> True for ``"any"``, False for ``"pcm16"`` (today's rules)."""
+        if decode not in ("pcm16", "any"):
+            raise AudioProcessingError(f"{what}: decode must be 'pcm16' or 'any', got {decode!r}")
+        return decode == "any"
+
+    def _decode_any(self, path: str, resample: bool, what: str) -> Tuple[np.ndarray, int]:
+        """One wav file under ``decode="any"`` -> (int16 [n] for 16-bit mono, else float32 [n] mono; its rate)."""
+        x, rate = read_wav(path)
+        if int(rate) != self.config.sample_rate and not resample:
+            raise AudioProcessingError(f"{path}: sample rate {rate} != {self.config.sample_rate}; pass resample=True to {what} to "
+                                       "resample on the device")
+        return x, int(rate)
 
     def _at_configured_rate(self, x: torch.Tensor, sample_rate: Optional[int], what: str) -> torch.Tensor:
         """Recordings at ``sample_rate`` -> the same at the configured rate, resampled on the device to their natural length
-        (``kws_resample_i16``); ``x`` itself when the rate is the configured one."""
+        (``kws_resample_i16``, ``kws_resample_f32`` for float32 samples); ``x`` itself when the rate is the configured one."""
         from kws import _native
 
         cfg = self.config
@@ -358,9 +403,10 @@ class KeywordSpotter:
         if x.shape[1] < 1:
             raise ModelError(f"{what}: the recording is empty")
         src = x.to(self.device).contiguous()
-        y = torch.empty((src.shape[0], _native.host_resample_len(src.shape[1], sample_rate, cfg.sample_rate)), dtype=torch.int16,
+        y = torch.empty((src.shape[0], _native.host_resample_len(src.shape[1], sample_rate, cfg.sample_rate)), dtype=src.dtype,
                         device=self.device)
-        self.model._context(self.device.index or 0).resample_i16(src, sample_rate, cfg.sample_rate, y)
+        ctx = self.model._context(self.device.index or 0)
+        (ctx.resample_f32 if src.dtype == torch.float32 else ctx.resample_i16)(src, sample_rate, cfg.sample_rate, y)
         return y
 
     def segment(self, pcm, threshold: float, on_window: int = 40, off_window: int = 80, pre_roll: int = 60, max_seconds: float = 10.0,
@@ -379,29 +425,46 @@ class KeywordSpotter:
         they are) and padded or trimmed to a clip (``kws_cut_i16``); and the model once per clip (``kws_infer_i16``).  With no
         utterance nothing further is launched.  At most ``max_utterances`` per recording are returned;
         ``keep_unfinished=False`` drops those the end of the recording closed."""
+        return self._segment(self._recordings(pcm, "segment"), "segment", threshold, on_window, off_window, pre_roll, max_seconds,
+                             normalize, max_utterances, sample_rate, keep_unfinished)
+
+    def segment_f32(self, signal, threshold: float, on_window: int = 40, off_window: int = 80, pre_roll: int = 60,
+                    max_seconds: float = 10.0, normalize: int = 16384, max_utterances: int = 1024, sample_rate: Optional[int] = None,
+                    keep_unfinished: bool = True) -> List[List[Utterance]]:
+        """``segment`` for float32 samples in [-1, 1]: ``signal`` float32 ``[n]`` or ``[R, n]``, a host array or a device tensor
+        (``kws_frames_f32``, ``kws_cut_f32``, ``kws_infer_f32``).  ``normalize`` stays in int16 units -- 16384 scales a span to a
+        peak of 16384 / 32768 = 0.5 in float64 with one rounding to float32 and no truncation -- and ``Utterance.peak`` is a float
+        in full-scale units.  With ``normalize=0`` and ``signal = pcm / 32768`` the spans, labels and logits are those of
+        ``segment(pcm, normalize=0)``.  Anything that is not float32 raises ``ModelError``."""
+        return self._segment(self._recordings(signal, "segment_f32", f32=True), "segment_f32", threshold, on_window, off_window, pre_roll,
+                             max_seconds, normalize, max_utterances, sample_rate, keep_unfinished)
+
+    def _segment(self, x: torch.Tensor, what: str, threshold, on_window, off_window, pre_roll, max_seconds, normalize, max_utterances,
+                 sample_rate, keep_unfinished) -> List[List[Utterance]]:
+        """``segment`` / ``segment_f32`` behind their argument's type check; the sample type of ``x`` picks the entries."""
         from kws import _native
 
-        x = self._recordings(pcm, "segment")
         if not 1 <= int(on_window) <= int(off_window) <= 1024:
-            raise ModelError("segment: need 1 <= on_window <= off_window <= 1024")
+            raise ModelError(f"{what}: need 1 <= on_window <= off_window <= 1024")
         if int(pre_roll) < 0 or int(max_utterances) < 0 or not 0 <= int(normalize) <= 32767:
-            raise ModelError("segment: need pre_roll >= 0, max_utterances >= 0 and normalize in [0, 32767]")
+            raise ModelError(f"{what}: need pre_roll >= 0, max_utterances >= 0 and normalize in [0, 32767]")
         cfg = self.config
-        x = self._at_configured_rate(x, sample_rate, "segment")
+        x = self._at_configured_rate(x, sample_rate, what)
         frame_len, frame_step = _round_half_up(cfg.frame_length * cfg.sample_rate), _round_half_up(cfg.frame_step * cfg.sample_rate)
         max_frames = int(round(float(max_seconds) * cfg.sample_rate / frame_step))
         if max_frames == 1 or max_frames < 0:
-            raise ModelError("segment: max_seconds must be 0 (no limit) or at least two frames")
+            raise ModelError(f"{what}: max_seconds must be 0 (no limit) or at least two frames")
         R, n = int(x.shape[0]), int(x.shape[1])
         if n < 1:
-            raise ModelError("segment: the recording is empty")
+            raise ModelError(f"{what}: the recording is empty")
         F, _ = _native.host_scan_shape(n, frame_len, frame_step, WINDOW_FRAMES, 1)
         ctx = self.model._context(self.device.index or 0)
         x = x.to(self.device).contiguous()
         m = int(max_utterances)
         feat = torch.empty((R, F, cfg.num_cepstral_coeffs), dtype=torch.float32, device=self.device)
         found = torch.empty((R + 5 * R * m,), dtype=torch.int32, device=self.device)  # the counts [R], then the slots [R, m, 5]
-        ctx.frames_i16(x, feat)
+        f32 = x.dtype == torch.float32
+        (ctx.frames_f32 if f32 else ctx.frames_i16)(x, feat)
         ctx.segment_f32(feat, n, threshold, found[:R], found[R:] if m else None, m, on_window, off_window, pre_roll, max_frames)
         host = found.cpu().numpy()  # the one device-to-host read (it waits for the stream): counts and spans together
         counts, slots = host[:R], host[R:].reshape(R, m, 5)
@@ -416,14 +479,20 @@ class KeywordSpotter:
         if not rows:
             return out
         span = torch.tensor([row[:3] for row in rows], dtype=torch.int32).to(self.device)
+        cut = (lambda clips, peaks: ctx.cut_f32(x, span, clips, int(normalize) / 32768.0, peaks)) if f32 else \
+              (lambda clips, peaks: ctx.cut_i16(x, span, clips, int(normalize), peaks))
         for utt in _classify_spans(ctx, self.device, self.words, self.model.num_classes, cfg.desired_samples, float(cfg.sample_rate), frame_step,
-                                   rows, lambda clips, peaks: ctx.cut_i16(x, span, clips, int(normalize), peaks)):
+                                   rows, cut, f32):
             out[utt.recording].append(utt)
         return out
 
-    def segment_file(self, path: str, resample: bool = False, **kwargs) -> List[Utterance]:
+    def segment_file(self, path: str, resample: bool = False, decode: str = "pcm16", **kwargs) -> List[Utterance]:
         """``segment`` over a whole wav file; the file's utterances.  The file must be 16-bit mono PCM at the configured rate;
-        with ``resample=True`` a 16-bit mono file at another rate is resampled on the device (as ``scan_file``)."""
+        with ``resample=True`` a 16-bit mono file at another rate is resampled on the device (as ``scan_file``).
+        ``decode="any"``: every encoding ``read_wav`` decodes, as ``scan_file`` routes it."""
+        if self._decode_mode(decode, "segment_file"):
+            x, rate = self._decode_any(path, resample, "segment_file")
+            return (self.segment if x.dtype == np.int16 else self.segment_f32)(x, sample_rate=rate, **kwargs)[0]
         if resample:
             x, rate = read_wav(path)
             if rate != self.config.sample_rate:
@@ -437,9 +506,10 @@ class KeywordSpotter:
         return self.segment(x, **kwargs)[0]
 
     # -- batches of recordings of unequal length ---------------------------------------------------------------------------
-    def _batch_recordings(self, recordings, sample_rate, what: str) -> Tuple[List[torch.Tensor], List[int]]:
+    def _batch_recordings(self, recordings, sample_rate, what: str, f32: bool = False) -> Tuple[List[torch.Tensor], List[int]]:
         """The argument checks of ``scan_batch`` / ``segment_batch`` (no device needed): a non-empty sequence of int16 ``[n_r]``
-        host arrays or tensors, none of them empty, and one rate or one rate per recording -> (1-D int16 tensors, rates)."""
+        host arrays or tensors, none of them empty, and one rate or one rate per recording -> (1-D int16 tensors, rates).
+        ``f32``: float32 ``[n_r]`` members (``scan_batch_f32`` / ``segment_batch_f32``)."""
         if torch.is_tensor(recordings) or isinstance(recordings, np.ndarray):
             recordings = list(recordings) if recordings.ndim == 2 else [recordings]
         recs = list(recordings)
@@ -448,11 +518,11 @@ class KeywordSpotter:
         out = []
         for r, rec in enumerate(recs):
             try:
-                x = self._recordings(rec, what)
+                x = self._recordings(rec, what, f32)
             except ModelError as e:
                 raise ModelError(f"{what}: recording {r}: {e.args[0]}") from None
             if x.shape[0] != 1:
-                raise ModelError(f"{what}: recording {r} must be one int16 [n] array, got shape {tuple(x.shape)}")
+                raise ModelError(f"{what}: recording {r} must be one {'float32' if f32 else 'int16'} [n] array, got shape {tuple(x.shape)}")
             if x.shape[1] < 1:
                 raise ModelError(f"{what}: recording {r} is empty")
             out.append(x[0])
@@ -468,9 +538,10 @@ class KeywordSpotter:
         return out, rates
 
     def _pack_batch(self, recs: List[torch.Tensor], rates: List[int]):
-        """Recordings -> ONE int16 device buffer at the configured rate: ``(buffer [n_pcm], start int64 [R], length int32 [R])``.
+        """Recordings -> ONE device buffer of their sample type (int16 or float32) at the configured rate: ``(buffer [n_pcm], start
+        int64 [R], length int32 [R])``.
         Recordings at the configured rate are packed one after another, each start rounded up to 8 samples.  The others are
-        grouped by rate; a group is padded to its longest, resampled with its true lengths in one launch (``kws_resample_i16``
+        grouped by rate; a group is padded to its longest, resampled with its true lengths in one launch (``kws_resample_i16`` / ``kws_resample_f32``
         with ``d_len``) straight into a rectangular block of the buffer whose rows are the group's recordings -- the natural
         length of each (``kws_host_resample_len``) is its length."""
         from kws import _native
@@ -498,11 +569,12 @@ class KeywordSpotter:
                 start[r] = at + i * n_out
             blocks.append((rate, members, at, n_out))
             at += len(members) * n_out
-        buf = torch.empty((max(at, 8),), dtype=torch.int16, device=self.device)
+        dtype = recs[0].dtype  # one sample type per batch (_batch_recordings)
+        buf = torch.empty((max(at, 8),), dtype=dtype, device=self.device)
         native = [r for r in range(R) if rates[r] == cfg.sample_rate]
         if native and not any(recs[r].is_cuda for r in native):  # host recordings: packed on the host, one upload
             last = native[-1]
-            host = np.zeros(int(start[last]) + up8(int(length[last])), np.int16)
+            host = np.zeros(int(start[last]) + up8(int(length[last])), np.float32 if dtype == torch.float32 else np.int16)
             for r in native:
                 host[int(start[r]):int(start[r]) + int(length[r])] = recs[r].numpy()
             buf[:host.shape[0]].copy_(torch.from_numpy(host))
@@ -512,12 +584,13 @@ class KeywordSpotter:
         ctx = self.model._context(self.device.index or 0)
         for rate, members, first, n_out in blocks:
             n_in = max(int(recs[r].shape[0]) for r in members)
-            src = torch.zeros((len(members), n_in), dtype=torch.int16, device=self.device)
+            src = torch.zeros((len(members), n_in), dtype=dtype, device=self.device)
             for i, r in enumerate(members):
                 src[i, :recs[r].shape[0]].copy_(recs[r])
             lengths = torch.tensor([int(recs[r].shape[0]) for r in members], dtype=torch.int32, device=self.device)
             torch.cuda.current_stream(self.device).synchronize()  # a context may run on its own stream
-            ctx.resample_i16(src, rate, cfg.sample_rate, buf[first:first + len(members) * n_out].view(len(members), n_out), lengths)
+            (ctx.resample_f32 if dtype == torch.float32 else ctx.resample_i16)(
+                src, rate, cfg.sample_rate, buf[first:first + len(members) * n_out].view(len(members), n_out), lengths)
         torch.cuda.current_stream(self.device).synchronize()
         return buf, start, length
 
@@ -532,16 +605,28 @@ class KeywordSpotter:
         On the device: the recordings in one buffer (``_pack_batch``), the front end over all of them in one launch and the model
         over the packed frame array as one recording (``kws_scan_ragged_i16``), the decisions per recording
         (``kws_scan_detect_ragged_f32``).  The windows that straddle two recordings are computed and dropped."""
+        return self._scan_batch(recordings, "scan_batch", False, hop_frames, smooth_window, threshold, refractory, first_keyword,
+                                max_events, sample_rate)
+
+    def scan_batch_f32(self, recordings, hop_frames: int = 1, smooth_window: int = 1, threshold: Optional[float] = None,
+                       refractory: int = 50, first_keyword: int = 2, max_events: int = 1024, sample_rate=None) -> List[ScanResult]:
+        """``scan_batch`` for a sequence of float32 ``[n_r]`` recordings (``kws_scan_ragged_f32``): element ``r`` equals
+        ``scan_f32(recordings[r], ...)``.  A member that is not float32 raises ``ModelError`` naming its index."""
+        return self._scan_batch(recordings, "scan_batch_f32", True, hop_frames, smooth_window, threshold, refractory, first_keyword,
+                                max_events, sample_rate)
+
+    def _scan_batch(self, recordings, what: str, f32: bool, hop_frames, smooth_window, threshold, refractory, first_keyword, max_events,
+                    sample_rate) -> List[ScanResult]:
         from kws import _native
 
-        recs, rates = self._batch_recordings(recordings, sample_rate, "scan_batch")
+        recs, rates = self._batch_recordings(recordings, sample_rate, what, f32)
         if int(hop_frames) < 1:
-            raise ModelError("scan_batch: hop_frames must be at least 1")
+            raise ModelError(f"{what}: hop_frames must be at least 1")
         if threshold is not None:
             if not 1 <= int(smooth_window) <= 256:
-                raise ModelError("scan_batch: smooth_window must be in [1, 256]")
+                raise ModelError(f"{what}: smooth_window must be in [1, 256]")
             if int(refractory) < 1 or int(first_keyword) < 0 or int(max_events) < 0:
-                raise ModelError("scan_batch: need refractory >= 1, first_keyword >= 0 and max_events >= 0")
+                raise ModelError(f"{what}: need refractory >= 1, first_keyword >= 0 and max_events >= 0")
         cfg = self.config
         frame_len, frame_step = _round_half_up(cfg.frame_length * cfg.sample_rate), _round_half_up(cfg.frame_step * cfg.sample_rate)
         buf, start, length = self._pack_batch(recs, rates)
@@ -550,7 +635,7 @@ class KeywordSpotter:
         ctx = self.model._context(self.device.index or 0)
         logits = torch.empty((max(W_pack, 1), C), dtype=torch.float32, device=self.device)
         labels = torch.empty((max(W_pack, 1),), dtype=torch.int32, device=self.device)
-        ctx.scan_ragged_i16(buf, start, length, hop, logits, labels)
+        (ctx.scan_ragged_f32 if f32 else ctx.scan_ragged_i16)(buf, start, length, hop, logits, labels)
         ev = None
         if threshold is not None:
             m = int(max_events)
@@ -585,25 +670,38 @@ class KeywordSpotter:
         On the device: the recordings in one buffer, their frames in one launch (``kws_frames_ragged_i16``), the endpointer per
         recording (``kws_segment_ragged_f32``), then the ONE device-to-host read of counts and spans, the cut over the whole
         buffer as one recording with each recording's start added to its spans (``kws_cut_i16``) and the model once per clip."""
+        return self._segment_batch(recordings, "segment_batch", False, threshold, on_window, off_window, pre_roll, max_seconds, normalize,
+                                   max_utterances, sample_rate, keep_unfinished)
+
+    def segment_batch_f32(self, recordings, threshold: float, on_window: int = 40, off_window: int = 80, pre_roll: int = 60,
+                          max_seconds: float = 10.0, normalize: int = 16384, max_utterances: int = 1024, sample_rate=None,
+                          keep_unfinished: bool = True) -> List[List[Utterance]]:
+        """``segment_batch`` for a sequence of float32 ``[n_r]`` recordings (``kws_frames_ragged_f32``, ``kws_cut_f32`` over the
+        buffer as one recording): element ``r`` equals ``segment_f32(recordings[r], ...)[0]`` with ``Utterance.recording = r``."""
+        return self._segment_batch(recordings, "segment_batch_f32", True, threshold, on_window, off_window, pre_roll, max_seconds,
+                                   normalize, max_utterances, sample_rate, keep_unfinished)
+
+    def _segment_batch(self, recordings, what: str, f32: bool, threshold, on_window, off_window, pre_roll, max_seconds, normalize,
+                       max_utterances, sample_rate, keep_unfinished) -> List[List[Utterance]]:
         from kws import _native
 
-        recs, rates = self._batch_recordings(recordings, sample_rate, "segment_batch")
+        recs, rates = self._batch_recordings(recordings, sample_rate, what, f32)
         if not 1 <= int(on_window) <= int(off_window) <= 1024:
-            raise ModelError("segment_batch: need 1 <= on_window <= off_window <= 1024")
+            raise ModelError(f"{what}: need 1 <= on_window <= off_window <= 1024")
         if int(pre_roll) < 0 or int(max_utterances) < 0 or not 0 <= int(normalize) <= 32767:
-            raise ModelError("segment_batch: need pre_roll >= 0, max_utterances >= 0 and normalize in [0, 32767]")
+            raise ModelError(f"{what}: need pre_roll >= 0, max_utterances >= 0 and normalize in [0, 32767]")
         cfg = self.config
         frame_len, frame_step = _round_half_up(cfg.frame_length * cfg.sample_rate), _round_half_up(cfg.frame_step * cfg.sample_rate)
         max_frames = int(round(float(max_seconds) * cfg.sample_rate / frame_step))
         if max_frames == 1 or max_frames < 0:
-            raise ModelError("segment_batch: max_seconds must be 0 (no limit) or at least two frames")
+            raise ModelError(f"{what}: max_seconds must be 0 (no limit) or at least two frames")
         buf, start, length = self._pack_batch(recs, rates)
         R, m = len(recs), int(max_utterances)
         frames, frame_off, _, _, _ = _native.host_ragged_plan(length, frame_len, frame_step, WINDOW_FRAMES, 1)
         ctx = self.model._context(self.device.index or 0)
         feat = torch.empty((int(frame_off[R]), cfg.num_cepstral_coeffs), dtype=torch.float32, device=self.device)
         found = torch.empty((R + 5 * R * m,), dtype=torch.int32, device=self.device)  # the counts [R], then the slots [R, m, 5]
-        ctx.frames_ragged_i16(buf, start, length, 1, feat)
+        (ctx.frames_ragged_f32 if f32 else ctx.frames_ragged_i16)(buf, start, length, 1, feat)
         ctx.segment_ragged_f32(feat, frame_off, frames, length, threshold, found[:R], found[R:] if m else None, m, on_window, off_window,
                                pre_roll, max_frames)
         ctx.sync()
@@ -621,8 +719,10 @@ class KeywordSpotter:
             return out
         # the whole buffer as ONE recording: a span of recording r lies start[r] samples on
         span = torch.tensor([(0, int(start[r]) + s, int(start[r]) + e) for r, s, e, _, _, _ in rows], dtype=torch.int32).to(self.device)
+        cut = (lambda clips, peaks: ctx.cut_f32(buf[None, :], span, clips, int(normalize) / 32768.0, peaks)) if f32 else \
+              (lambda clips, peaks: ctx.cut_i16(buf[None, :], span, clips, int(normalize), peaks))
         for utt in _classify_spans(ctx, self.device, self.words, self.model.num_classes, cfg.desired_samples, float(cfg.sample_rate), frame_step,
-                                   rows, lambda clips, peaks: ctx.cut_i16(buf[None, :], span, clips, int(normalize), peaks)):
+                                   rows, cut, f32):
             out[utt.recording].append(utt)
         return out
 
@@ -641,15 +741,42 @@ class KeywordSpotter:
             raise AudioProcessingError(f"{path}: {x.shape[1]} channels; {what} takes mono files")
         return x, self.config.sample_rate
 
-    def scan_files(self, paths: Sequence[str], resample: bool = False, **kwargs) -> List[ScanResult]:
+    def _files_by_type(self, paths: Sequence[str], resample: bool, what: str, run_i16, run_f32) -> list:
+        """The plural file methods under ``decode="any"``: the files decoded by ``read_wav``, ONE ragged pass per sample type
+        (``run_i16`` / ``run_f32``: recordings, rates -> one result per recording), the results in input order."""
+        decoded = [self._decode_any(p, resample, what) for p in paths]
+        out: list = [None] * len(decoded)
+        for is_i16, run in ((True, run_i16), (False, run_f32)):
+            members = [i for i, (x, _) in enumerate(decoded) if (x.dtype == np.int16) == is_i16]
+            if members:
+                for i, res in zip(members, run([decoded[i][0] for i in members], [decoded[i][1] for i in members])):
+                    out[i] = res
+        return out
+
+    def scan_files(self, paths: Sequence[str], resample: bool = False, decode: str = "pcm16", **kwargs) -> List[ScanResult]:
         """``scan_batch`` over whole wav files, one result per path: each file is decoded under the rules of ``scan_file`` (16-bit
         mono PCM at the configured rate; with ``resample=True`` also 16-bit mono at another rate).  Files at other rates are
-        grouped by rate, resampled on the device with one launch per group, and scanned with the rest in one pass."""
+        grouped by rate, resampled on the device with one launch per group, and scanned with the rest in one pass.
+        ``decode="any"``: every encoding ``read_wav`` decodes; 16-bit mono files go through ``scan_batch`` and the others, as
+        float32, through ``scan_batch_f32`` -- one ragged pass per sample type, results in the order of ``paths``."""
+        if self._decode_mode(decode, "scan_files"):
+            return self._files_by_type(paths, resample, "scan_files",
+                                       lambda recs, rates: self.scan_batch(recs, sample_rate=rates, **kwargs),
+                                       lambda recs, rates: self.scan_batch_f32(recs, sample_rate=rates, **kwargs))
         decoded = [self._decode_file(p, resample, "scan_file") for p in paths]
         return self.scan_batch([x for x, _ in decoded], sample_rate=[rate for _, rate in decoded], **kwargs)
 
-    def segment_files(self, paths: Sequence[str], resample: bool = False, **kwargs) -> List[List[Utterance]]:
-        """``segment_batch`` over whole wav files, one list of utterances per path (decode rules of ``segment_file``)."""
+    def segment_files(self, paths: Sequence[str], resample: bool = False, decode: str = "pcm16", **kwargs) -> List[List[Utterance]]:
+        """``segment_batch`` over whole wav files, one list of utterances per path (decode rules of ``segment_file``;
+        ``decode="any"`` as ``scan_files``, ``Utterance.recording`` being the index into ``paths``)."""
+        if self._decode_mode(decode, "segment_files"):
+            out = self._files_by_type(paths, resample, "segment_files",
+                                      lambda recs, rates: self.segment_batch(recs, sample_rate=rates, **kwargs),
+                                      lambda recs, rates: self.segment_batch_f32(recs, sample_rate=rates, **kwargs))
+            for i, utts in enumerate(out):
+                for u in utts:
+                    u.recording = i
+            return out
         decoded = [self._decode_file(p, resample, "segment_file") for p in paths]
         return self.segment_batch([x for x, _ in decoded], sample_rate=[rate for _, rate in decoded], **kwargs)
 
