@@ -2,13 +2,12 @@
 // per-kernel event timing.  The front end's entries are in kws_frontend.hip, the weight images in kws_weights.hip.  No torch
 // types, no exceptions across the boundary, no CPU fallback.
 #include <atomic>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <new>
 
-#include "kws_ctx.h"
+#include "kws_event_queue.h"  // spin_until
 
 namespace kws {
 
@@ -374,17 +373,7 @@ int kws_stream_wait_host(kws_ctx* c, const float** h_logits, const int32_t** h_l
         return fail(c, KWS_ESTATE, "kws_stream_wait_host: the newest push did not deliver to host memory (it asked for no logits, or took a multi-launch route)");
     volatile int* flag = c->h_stream_flag;
     const int want = c->host_push;
-    bool seen = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (long spin = 1;; ++spin) {
-        if (*flag - want >= 0) {
-            seen = true;
-            break;
-        }
-        __builtin_ia32_pause();
-        if ((spin & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-    }
-    if (!seen) {
+    if (!spin_until([&] { return *flag - want >= 0; })) {
         HIP_TRY(c, hipSetDevice(c->device));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         if (*flag - want < 0) return fail(c, KWS_EHIP, "kws_stream_wait_host: the stream drained but the results flag never arrived");

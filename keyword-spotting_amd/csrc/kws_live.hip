@@ -1,25 +1,24 @@
 // Live utterances (include/kws_hip.h: kws_stream_utt_*) -- the reference's one live loop (kws/inference/inference_local.py:
 // 114-192) for the streams of kws_stream_open: a per-stream PCM history ring, the walk of kws_segment_f32 taken one frame per
-// hop with O(1) window counts, an event queue mirrored in pinned host memory, and kws_cut_i16 with a ring origin.  Everything
-// here is new kernels launched BEHIND a push; no other unit's kernel changes, and an unarmed context never gets here.
-#include <atomic>
-#include <chrono>
+// hop with O(1) window counts, an event queue mirrored in pinned host memory (kws_event_queue.h), and kws_cut_i16 with a ring
+// origin.  Everything here is new kernels launched BEHIND a push; no other unit's kernel changes, and an unarmed context never
+// gets here.
 #include <climits>
-#include <cstring>
 
-#include "kws_ctx.h"
+#include "kws_event_queue.h"
 
 namespace kws {
 
 constexpr int LIVE_MAX_STREAMS = 1024;  // one workgroup walks every stream: one thread each
 constexpr int LIVE_REC = 6;             // int64 words per record
 constexpr int LIVE_CUT_THREADS = 256;
+static_assert(LIVE_MAX_STREAMS <= EQ_MAX_THREADS, "eq_emit counts one ballot per wavefront of the step's workgroup");
 
 namespace {
 
 // What a step reads.  The first group is set per launch (utt_launch); the set's own size, rules and buffers below it are filled
-// once by kws_stream_utt_open.  Device counters ctr[4] = frames walked, hops appended, events so far, kernels finished; the host
-// mirror h_ctr[3] = events so far, frames walked, kernels finished (the flag kws_stream_utt_poll spins on).
+// once by kws_stream_utt_open.  The unit's device counters q.unit()[2] = frames walked, hops appended; the queue's progress word
+// (h_ctr[1]) is the frames walked.
 struct LiveArgs {
     const int16_t* hop;       // append source (nullptr: no append): stream s at hop + s * hop_stride (+ the ring offset with ctx_hops)
     long long hop_stride;
@@ -27,7 +26,7 @@ struct LiveArgs {
     int ring_len;             // of the context's PCM ring
     const float* energy;      // explicit step: [S] (nullptr: no walk); push: the context's feature ring
     int num_frames, numcep, K;
-    int S, step, frame_len, H, max_events;
+    int S, step, frame_len, H;
     int on_window, off_window, pre_roll, max_frames;
     float threshold;
     int vec;                  // the hop may be copied 16 bytes at a time
@@ -35,10 +34,7 @@ struct LiveArgs {
     unsigned long long* bits; // [S][EP_BIT_WORDS], counts [S][4] = c_on, c_off, triggered, unused: ep_ring_push's state
     int* counts;
     long long* pos;           // [S][2]: open, prev_close
-    unsigned long long* ctr;  // [4]
-    long long* queue;         // [max_events][6]
-    long long* h_queue;       // pinned, device-mapped mirror of queue
-    unsigned long long* h_ctr;  // pinned, device-mapped [3]
+    EventQueue q;             // records of LIVE_REC words
 };
 
 }  // namespace
@@ -46,29 +42,20 @@ struct LiveArgs {
 // Everything kws_stream_utt_open allocates, as the step kernel takes it.
 struct StreamUtt {
     LiveArgs a{};
-    unsigned long long ticks_enqueued = 0; // kernels enqueued so far: h_ctr[2] reads this once the newest has landed
-    int mode = 0;                          // 0: not stepped yet, 1: stepped by pushes, 2: stepped by kws_stream_utt_step_i16
+    int mode = 0;  // 0: not stepped yet, 1: stepped by pushes, 2: stepped by kws_stream_utt_step_i16
 };
 
 namespace {
 
-__device__ __forceinline__ void store_host(long long* p, long long v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // One hop of every stream: append, walk one frame, emit.  ONE workgroup, thread s = stream s (threads at or beyond S only
 // help with the copy, the ballots and the barriers).  FLUSH: no append and no walk -- every stream inside an utterance closes
-// at the newest walked frame with reason 2.
-// Emit: the wavefronts' ballots of "closed at this step" give every closing stream its rank in ascending stream order (popcount
-// of the lower lanes + the counts of the lower wavefronts, through LDS): consecutive sequence numbers, no atomics.  Records go
-// to the device queue and, as system-scope stores, to the pinned host mirror; every wavefront waits for its own stores to be
-// acknowledged (vmcnt 0: they are on their way, in order), and behind the barrier thread 0 publishes the totals and, last, the
-// kernel count the host spins on -- the discipline of the push's zero-copy results (kws_dscnn.hip), in one workgroup.
+// at the newest walked frame with reason 2.  The streams that closed at this step emit their records and thread 0 publishes
+// the totals as kws_event_queue.h lays down (eq_emit, eq_publish).
 template <bool FLUSH>
 __global__ __launch_bounds__(LIVE_MAX_STREAMS) void kws_live_step_kernel(const LiveArgs a) {
-    __shared__ int wave_n[LIVE_MAX_STREAMS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = (int)blockDim.x >> 6;
-    const unsigned long long frames = a.ctr[0], appended = a.ctr[1], total = a.ctr[2], ticks = a.ctr[3];
+    const int tid = threadIdx.x;
+    const EqCounts was = eq_counts(a.q);
+    const unsigned long long frames = was.unit[0], appended = was.unit[1];
     bool do_append = false, do_walk = false;
     const int16_t* src = a.hop;
     const float* energy = a.energy;
@@ -145,56 +132,31 @@ __global__ __launch_bounds__(LIVE_MAX_STREAMS) void kws_live_step_kernel(const L
             cnt[2] = 0;
         }
     }
-    const unsigned long long b = __ballot(closed);
-    if (lane == 0) wave_n[wave] = __popcll(b);
-    __syncthreads();
-    int before = 0, all = 0;
-    for (int k = 0; k < n_waves; ++k) {
-        before += k < wave ? wave_n[k] : 0;
-        all += wave_n[k];
-    }
-    if (closed) {
-        const unsigned long long seq = total + (unsigned long long)before + (unsigned long long)__popcll(b & ((1ull << lane) - 1ull));
-        const size_t at = (size_t)(seq % (unsigned long long)a.max_events) * LIVE_REC;
-        const long long rec[LIVE_REC] = {(long long)tid, start_frame * a.step, close_frame * a.step + a.frame_len, open, close_frame, (long long)reason};
-#pragma unroll
-        for (int k = 0; k < LIVE_REC; ++k) {
-            a.queue[at + k] = rec[k];
-            store_host(a.h_queue + at + k, rec[k]);
-        }
-    }
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wavefront's stores, the host's among them, are acknowledged
-    __syncthreads();                     // ... and so are every other wavefront's; all have read ctr[]
+    const long long rec[LIVE_REC] = {(long long)tid, start_frame * a.step, close_frame * a.step + a.frame_len, open, close_frame, (long long)reason};
+    const int all = eq_emit(a.q, was, closed, rec);
+    const unsigned long long frames_now = frames + (do_walk ? 1 : 0);
+    eq_publish(a.q, was, all, frames_now);
     if (tid == 0) {
-        const unsigned long long frames_now = frames + (do_walk ? 1 : 0);
-        a.ctr[0] = frames_now;
-        a.ctr[1] = appended + (do_append ? 1 : 0);
-        a.ctr[2] = total + (unsigned long long)all;
-        a.ctr[3] = ticks + 1;
-        store_host(reinterpret_cast<long long*>(a.h_ctr), (long long)(total + (unsigned long long)all));
-        store_host(reinterpret_cast<long long*>(a.h_ctr) + 1, (long long)frames_now);
-        __builtin_amdgcn_s_waitcnt(0x0F70);
-        store_host(reinterpret_cast<long long*>(a.h_ctr) + 2, (long long)(ticks + 1));
+        a.q.unit()[0] = frames_now;
+        a.q.unit()[1] = appended + (do_append ? 1 : 0);
     }
 }
 
 // kws_cut_i16_kernel (kws_segment.hip) with a ring origin: one workgroup per sequence number, the record read from the device
-// queue.  The span [start, end) of stream r lies in the history ring from start mod H on and crosses the seam at most once
-// (end - start <= H): element i is at p0 + i, minus H from the seam on.  The cut itself is the linear kernel's (ep_cut_clip).
-// Refused (zero clip, peak -1): a sequence number not issued yet
-// or already overwritten in the queue, a span whose start has left the ring, a span that ends beyond what was appended.
+// queue (q.ctr[0]: events so far; q.unit()[1]: hops appended).  The span [start, end) of stream r lies in the history ring from
+// start mod H on and crosses the seam at most once (end - start <= H): element i is at p0 + i, minus H from the seam on.  The
+// cut itself is the linear kernel's (ep_cut_clip).  Refused (zero clip, peak -1): a sequence number not issued yet or already
+// overwritten in the queue, a span whose start has left the ring, a span that ends beyond what was appended.
 __global__ __launch_bounds__(LIVE_CUT_THREADS) void kws_live_cut_kernel(const int16_t* __restrict__ hist, int S, int H, int step,
-                                                                        const long long* __restrict__ queue, int max_events,
-                                                                        const unsigned long long* __restrict__ ctr,
-                                                                        unsigned long long first_seq, int normalize_to,
+                                                                        const EventQueue q, unsigned long long first_seq, int normalize_to,
                                                                         int16_t* __restrict__ clips, int n_out, int32_t* __restrict__ peak_out) {
     const int u = blockIdx.x;
-    const unsigned long long seq = first_seq + (unsigned long long)u, total = ctr[2];
-    const long long have = (long long)(ctr[1] * (unsigned long long)step);  // samples appended so far
-    bool ok = seq < total && seq + (unsigned long long)max_events >= total;  // workgroup-uniform throughout
+    const unsigned long long seq = first_seq + (unsigned long long)u, total = q.ctr[0];
+    const long long have = (long long)(q.unit()[1] * (unsigned long long)step);  // samples appended so far
+    bool ok = seq < total && seq + (unsigned long long)q.max_events >= total;  // workgroup-uniform throughout
     long long r = 0, start = 0, end = 0;
     if (ok) {
-        const long long* rec = queue + (size_t)(seq % (unsigned long long)max_events) * LIVE_REC;
+        const long long* rec = q.queue + (size_t)(seq % (unsigned long long)q.max_events) * LIVE_REC;
         r = rec[0];
         start = rec[1];
         end = rec[2];
@@ -220,10 +182,9 @@ int history_for(int frame_len, int frame_step, int pre_roll, int max_frames, int
 
 void utt_release(StreamUtt* u) {
     if (!u) return;
-    for (void* d : {(void*)u->a.hist, (void*)u->a.bits, (void*)u->a.counts, (void*)u->a.pos, (void*)u->a.ctr, (void*)u->a.queue})
+    for (void* d : {(void*)u->a.hist, (void*)u->a.bits, (void*)u->a.counts, (void*)u->a.pos})
         if (d) (void)hipFree(d);
-    if (u->a.h_queue) (void)hipHostFree(u->a.h_queue);
-    if (u->a.h_ctr) (void)hipHostFree(u->a.h_ctr);
+    eq_release(u->a.q);
     delete u;
 }
 
@@ -250,7 +211,7 @@ int utt_launch(kws_ctx* c, const int16_t* hop, long long hop_stride, const int* 
     if (hop && threads < 256) threads = 256;  // the copy is the workgroup's bulk
     hipLaunchKernelGGL(kws_live_step_kernel<FLUSH>, dim3(1), dim3(threads), 0, c->stream, a);
     HIP_TRY(c, hipGetLastError());
-    u->ticks_enqueued += 1;
+    eq_enqueued(u->a.q);
     return KWS_OK;
 }
 
@@ -314,30 +275,21 @@ int kws_stream_utt_open(kws_ctx* c, float log_energy_threshold, int on_window, i
     const size_t S = (size_t)c->n_streams;
     a.S = c->n_streams;
     a.H = history_samples;
-    a.max_events = max_events;
     a.on_window = on_window;
     a.off_window = off_window;
     a.pre_roll = pre_roll;
     a.max_frames = max_frames;
     a.threshold = log_energy_threshold;
-    const size_t hist_b = sizeof(int16_t) * S * (size_t)a.H, pos_b = sizeof(long long) * S * 2, ctr_b = sizeof(unsigned long long) * 4,
-                 queue_b = sizeof(long long) * (size_t)max_events * LIVE_REC;
-    const unsigned flags = hipHostMallocMapped | hipHostMallocCoherent;  // fine-grained: device stores are visible to the host as they land
-    if (hipMalloc(reinterpret_cast<void**>(&a.hist), hist_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&a.pos), pos_b) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&a.ctr), ctr_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&a.queue), queue_b) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&a.h_queue), queue_b, flags) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&a.h_ctr), 64, flags) != hipSuccess) {
+    const size_t hist_b = sizeof(int16_t) * S * (size_t)a.H, pos_b = sizeof(long long) * S * 2;
+    if (hipMalloc(reinterpret_cast<void**>(&a.hist), hist_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&a.pos), pos_b) != hipSuccess) {
         utt_release(u);
         return fail(c, KWS_ENOMEM, "kws_stream_utt_open: allocation failed");
     }
-    memset(a.h_queue, 0, queue_b);
-    memset(a.h_ctr, 0, 64);
     auto drop = [&](int code) { (void)hipStreamSynchronize(c->stream); utt_release(u); return code; };
+    if ((rc = eq_open(c, "kws_stream_utt_open", a.q, LIVE_REC, max_events))) return drop(rc);
     if ((rc = alloc_endpoint_state(c, "kws_stream_utt_open", S, a.bits, a.counts))) return drop(rc);
     hipError_t e = hipMemsetAsync(a.hist, 0, hist_b, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(a.pos, 0xFF, pos_b, c->stream);  // open = prev_close = -1
-    if (e == hipSuccess) e = hipMemsetAsync(a.ctr, 0, ctr_b, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(a.queue, 0, queue_b, c->stream);
     if (e != hipSuccess) return drop(fail_hip(c, e, "kws_stream_utt_open: hipMemsetAsync"));
     c->stream_utt = u;
     return KWS_OK;
@@ -375,47 +327,14 @@ int kws_stream_utt_poll(kws_ctx* c, uint64_t* total_events, uint64_t* steps) {
     if (!c) return KWS_EINVAL;
     StreamUtt* u = c->stream_utt;
     if (!u) return fail(c, KWS_ESTATE, "kws_stream_utt_poll: call kws_stream_utt_open first");
-    // spin on the count of finished kernels; bounded: after ~2 ms without it, fall back to the stream (kws_stream_wait_host)
-    volatile unsigned long long* h = u->a.h_ctr;
-    const unsigned long long want = u->ticks_enqueued;
-    bool seen = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (long spin = 1;; ++spin) {
-        if (h[2] >= want) {
-            seen = true;
-            break;
-        }
-        __builtin_ia32_pause();
-        if ((spin & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-    }
-    if (!seen) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (h[2] < want) return fail(c, KWS_EHIP, "kws_stream_utt_poll: the stream drained but the step's flag never arrived");
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    if (total_events) *total_events = h[0];
-    if (steps) *steps = h[1];
-    return KWS_OK;
+    return eq_wait(c, "kws_stream_utt_poll", u->a.q, total_events, steps);
 }
 
 int kws_stream_utt_read(kws_ctx* c, uint64_t first_seq, int n, int64_t* out_records) {
     if (!c) return KWS_EINVAL;
     StreamUtt* u = c->stream_utt;
     if (!u) return fail(c, KWS_ESTATE, "kws_stream_utt_read: call kws_stream_utt_open first");
-    if (n < 1 || !out_records) return fail(c, KWS_EINVAL, "kws_stream_utt_read: n must be positive and out_records not NULL");
-    volatile unsigned long long* h = u->a.h_ctr;
-    unsigned long long total = h[0];
-    std::atomic_thread_fence(std::memory_order_acquire);
-    if (first_seq + (unsigned long long)n > total) return fail(c, KWS_EINVAL, "kws_stream_utt_read: sequence numbers beyond the events landed so far");
-    for (int i = 0; i < n; ++i) {
-        const volatile long long* rec = u->a.h_queue + (size_t)((first_seq + i) % (unsigned long long)u->a.max_events) * LIVE_REC;
-        for (int k = 0; k < LIVE_REC; ++k) out_records[(size_t)i * LIVE_REC + k] = rec[k];
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    total = h[0];  // again: a step that landed during the copy may have overwritten the oldest
-    if (first_seq + (unsigned long long)u->a.max_events < total) return fail(c, KWS_EINVAL, "kws_stream_utt_read: the sequence number is no longer in the queue");
-    return KWS_OK;
+    return eq_read(c, "kws_stream_utt_read", u->a.q, LIVE_REC, first_seq, n, out_records);
 }
 
 int kws_stream_utt_cut_i16(kws_ctx* c, uint64_t first_seq, int U, int normalize_to, int16_t* d_clips, int n_out, int32_t* d_peak) {
@@ -427,7 +346,7 @@ int kws_stream_utt_cut_i16(kws_ctx* c, uint64_t first_seq, int U, int normalize_
     if (int rc = check_normalize_to(c, "kws_stream_utt_cut_i16", normalize_to)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     hipLaunchKernelGGL(kws_live_cut_kernel, dim3(U), dim3(LIVE_CUT_THREADS), 0, c->stream, u->a.hist, u->a.S, u->a.H, c->fp.frame_step,
-                       u->a.queue, u->a.max_events, u->a.ctr, (unsigned long long)first_seq, normalize_to, d_clips, n_out, d_peak);
+                       u->a.q, (unsigned long long)first_seq, normalize_to, d_clips, n_out, d_peak);
     HIP_TRY(c, hipGetLastError());
     return KWS_OK;
 }

@@ -1,12 +1,8 @@
 // Live keyword events (include/kws_hip.h: kws_stream_detect_*) -- the decision layer of kws_scan_detect_f32 taken one decision
 // per push for the streams of kws_stream_open: softmax, a posterior ring per stream, the direct causal sum, threshold and
-// refractory, and an event queue mirrored in pinned host memory (the queue discipline of kws_live.hip).  Everything here is a new
-// kernel launched BEHIND a push; no other unit's kernel changes, and an unarmed context never gets here.
-#include <atomic>
-#include <chrono>
-#include <cstring>
-
-#include "kws_ctx.h"
+// refractory, and an event queue mirrored in pinned host memory (kws_event_queue.h).  Everything here is a new kernel launched
+// BEHIND a push; no other unit's kernel changes, and an unarmed context never gets here.
+#include "kws_event_queue.h"
 #include "kws_softmax_dev.h"
 
 namespace kws {
@@ -14,25 +10,23 @@ namespace kws {
 constexpr int DETECT_MAX_STREAMS = 1024;  // one workgroup decides for every stream: one thread each
 constexpr int DETECT_REC = 5;             // int64 words per record
 constexpr int DETECT_MAX_WINDOW = 256;    // kws_scan_detect_f32's bound
+static_assert(DETECT_MAX_STREAMS <= EQ_MAX_THREADS, "eq_emit counts one ballot per wavefront of the step's workgroup");
 
 namespace {
 
 // What a step reads.  logits and ctx_hops are set per launch (detect_launch); the rest is filled once by
-// kws_stream_detect_open.  Device counters ctr[3] = decisions made, events so far, kernels finished; the host mirror h_ctr[3] =
-// events so far, decisions made, kernels finished (the flag kws_stream_detect_poll spins on).
+// kws_stream_detect_open.  The unit's device counter q.unit()[0] = decisions made, which is also the queue's progress word
+// (h_ctr[1]).
 struct DetectArgs {
     const float* logits;      // [S][C]
     const int* ctx_hops;      // stepped by a push: the context's hop counter (already advanced); nullptr: explicit step
-    int S, C, W, first_keyword, refractory, first_hop, max_events;
+    int S, C, W, first_keyword, refractory, first_hop;
     float threshold;
     float* ring;              // [S][W][C] posteriors, decision d at slot d mod W
     float* smoothed;          // [S][C] of the newest decision, label [S] its first argmax
     int32_t* label;
     long long* next;          // [S]: the first decision at which stream s may fire again
-    unsigned long long* ctr;  // [3]
-    long long* queue;         // [max_events][5]
-    long long* h_queue;       // pinned, device-mapped mirror of queue
-    unsigned long long* h_ctr;  // pinned, device-mapped [3]
+    EventQueue q;             // records of DETECT_REC words
 };
 
 }  // namespace
@@ -40,15 +34,10 @@ struct DetectArgs {
 // Everything kws_stream_detect_open allocates, as the step kernel takes it.
 struct StreamDetect {
     DetectArgs a{};
-    unsigned long long ticks_enqueued = 0;  // kernels enqueued so far: h_ctr[2] reads this once the newest has landed
-    int mode = 0;                           // 0: not stepped yet, 1: stepped by pushes, 2: stepped by kws_stream_detect_step_f32
+    int mode = 0;  // 0: not stepped yet, 1: stepped by pushes, 2: stepped by kws_stream_detect_step_f32
 };
 
 namespace {
-
-__device__ __forceinline__ void store_host(long long* p, long long v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 
 // One decision of every stream.  ONE workgroup.  (1) thread s = stream s: softmax_row of the stream's logits into slot d mod W of
 // its ring.  (2) behind a barrier the S * C sums are spread over ALL threads, one (stream, class) pair at a time with the class
@@ -57,15 +46,12 @@ __device__ __forceinline__ void store_host(long long* p, long long v) {
 // it out of kws_scan.hip changed that unit's generated code (register allocation of both smooth kernels), which this unit must
 // not do; tests/test_live_detect_gpu.py holds the two to the same bits.  (3) behind another barrier thread s takes the first
 // argmax of its row, the threshold and the refractory rule.
-// Emit, exactly as kws_live_step_kernel: the wavefronts' ballots of "fired" give every firing stream its rank in ascending stream
-// order (popcount of the lower lanes + the counts of the lower wavefronts, through LDS): consecutive sequence numbers, no
-// atomics.  Records go to the device queue and, as system-scope stores, to the pinned host mirror; every wavefront waits for its
-// own stores (vmcnt 0), and behind the barrier thread 0 publishes the totals and, last, the kernel count the host spins on.
-// A push below first_hop decides nothing and advances nothing but the kernel count.
+// The streams that fired emit their records and thread 0 publishes the totals as kws_event_queue.h lays down (eq_emit,
+// eq_publish).  A push below first_hop decides nothing and advances nothing but the kernel count.
 __global__ __launch_bounds__(DETECT_MAX_STREAMS) void kws_live_detect_step_kernel(const DetectArgs a) {
-    __shared__ int wave_n[DETECT_MAX_STREAMS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = (int)blockDim.x >> 6;
-    const unsigned long long d = a.ctr[0], total = a.ctr[1], ticks = a.ctr[2];
+    const int tid = threadIdx.x;
+    const EqCounts was = eq_counts(a.q);
+    const unsigned long long d = was.unit[0];
     long long h = (long long)d;  // explicit steps: the record's hop is the decision
     bool decide = true;          // workgroup-uniform
     if (a.ctx_hops) {
@@ -124,44 +110,18 @@ __global__ __launch_bounds__(DETECT_MAX_STREAMS) void kws_live_detect_step_kerne
             }
         }
     }
-    const unsigned long long b = __ballot(fired);
-    if (lane == 0) wave_n[wave] = __popcll(b);
-    __syncthreads();
-    int before = 0, all = 0;
-    for (int k = 0; k < n_waves; ++k) {
-        before += k < wave ? wave_n[k] : 0;
-        all += wave_n[k];
-    }
-    if (fired) {
-        const unsigned long long seq = total + (unsigned long long)before + (unsigned long long)__popcll(b & ((1ull << lane) - 1ull));
-        const size_t at = (size_t)(seq % (unsigned long long)a.max_events) * DETECT_REC;
-        const long long rec[DETECT_REC] = {(long long)tid, (long long)d, h, (long long)arg, (long long)__float_as_uint(best)};
-#pragma unroll
-        for (int k = 0; k < DETECT_REC; ++k) {
-            a.queue[at + k] = rec[k];
-            store_host(a.h_queue + at + k, rec[k]);
-        }
-    }
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wavefront's stores, the host's among them, are acknowledged
-    __syncthreads();                     // ... and so are every other wavefront's; all have read ctr[]
-    if (tid == 0) {
-        const unsigned long long decisions = d + (decide ? 1 : 0);
-        a.ctr[0] = decisions;
-        a.ctr[1] = total + (unsigned long long)all;
-        a.ctr[2] = ticks + 1;
-        store_host(reinterpret_cast<long long*>(a.h_ctr), (long long)(total + (unsigned long long)all));
-        store_host(reinterpret_cast<long long*>(a.h_ctr) + 1, (long long)decisions);
-        __builtin_amdgcn_s_waitcnt(0x0F70);
-        store_host(reinterpret_cast<long long*>(a.h_ctr) + 2, (long long)(ticks + 1));
-    }
+    const long long rec[DETECT_REC] = {(long long)tid, (long long)d, h, (long long)arg, (long long)__float_as_uint(best)};
+    const int all = eq_emit(a.q, was, fired, rec);
+    const unsigned long long decisions = d + (decide ? 1 : 0);
+    eq_publish(a.q, was, all, decisions);
+    if (tid == 0) a.q.unit()[0] = decisions;
 }
 
 void detect_release(StreamDetect* u) {
     if (!u) return;
-    for (void* d : {(void*)u->a.ring, (void*)u->a.smoothed, (void*)u->a.label, (void*)u->a.next, (void*)u->a.ctr, (void*)u->a.queue})
+    for (void* d : {(void*)u->a.ring, (void*)u->a.smoothed, (void*)u->a.label, (void*)u->a.next})
         if (d) (void)hipFree(d);
-    if (u->a.h_queue) (void)hipHostFree(u->a.h_queue);
-    if (u->a.h_ctr) (void)hipHostFree(u->a.h_ctr);
+    eq_release(u->a.q);
     delete u;
 }
 
@@ -176,7 +136,7 @@ int detect_launch(kws_ctx* c, const float* d_logits, const int* ctx_hops) {
     const int threads = pairs >= DETECT_MAX_STREAMS ? DETECT_MAX_STREAMS : (int)((pairs + 63) / 64 * 64);  // >= S rounded up: C >= 1
     hipLaunchKernelGGL(kws_live_detect_step_kernel, dim3(1), dim3(threads), 0, c->stream, a);
     HIP_TRY(c, hipGetLastError());
-    u->ticks_enqueued += 1;
+    eq_enqueued(u->a.q);
     return KWS_OK;
 }
 
@@ -232,33 +192,21 @@ int kws_stream_detect_open(kws_ctx* c, int C, int smooth_window, int first_keywo
     a.first_keyword = first_keyword;
     a.refractory = refractory;
     a.first_hop = first_hop;
-    a.max_events = max_events;
     a.threshold = threshold;
     const size_t ring_b = sizeof(float) * S * (size_t)smooth_window * C, sm_b = sizeof(float) * S * C, label_b = sizeof(int32_t) * S,
-                 next_b = sizeof(long long) * S, ctr_b = sizeof(unsigned long long) * 4,
-                 queue_b = sizeof(long long) * (size_t)max_events * DETECT_REC;
-    const unsigned flags = hipHostMallocMapped | hipHostMallocCoherent;  // fine-grained: device stores are visible to the host as they land
+                 next_b = sizeof(long long) * S;
     if (hipMalloc(reinterpret_cast<void**>(&a.ring), ring_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&a.smoothed), sm_b) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&a.label), label_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&a.next), next_b) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&a.ctr), ctr_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&a.queue), queue_b) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&a.h_queue), queue_b, flags) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&a.h_ctr), 64, flags) != hipSuccess) {
+        hipMalloc(reinterpret_cast<void**>(&a.label), label_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&a.next), next_b) != hipSuccess) {
         detect_release(u);
         return fail(c, KWS_ENOMEM, "kws_stream_detect_open: allocation failed");
     }
-    memset(a.h_queue, 0, queue_b);
-    memset(a.h_ctr, 0, 64);
+    auto drop = [&](int code) { (void)hipStreamSynchronize(c->stream); detect_release(u); return code; };
+    if (int rc = eq_open(c, "kws_stream_detect_open", a.q, DETECT_REC, max_events)) return drop(rc);
     // the ring needs no clearing: a decision reads only slots written since the arming
     hipError_t e = hipMemsetAsync(a.smoothed, 0, sm_b, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(a.label, 0, label_b, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(a.next, 0, next_b, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(a.ctr, 0, ctr_b, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(a.queue, 0, queue_b, c->stream);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(c->stream);
-        detect_release(u);
-        return fail_hip(c, e, "kws_stream_detect_open: hipMemsetAsync");
-    }
+    if (e != hipSuccess) return drop(fail_hip(c, e, "kws_stream_detect_open: hipMemsetAsync"));
     c->stream_detect = u;
     return KWS_OK;
     KWS_GUARD_END(c, "kws_stream_detect_open")
@@ -288,47 +236,14 @@ int kws_stream_detect_poll(kws_ctx* c, uint64_t* total_events, uint64_t* decisio
     if (!c) return KWS_EINVAL;
     StreamDetect* u = c->stream_detect;
     if (!u) return fail(c, KWS_ESTATE, "kws_stream_detect_poll: call kws_stream_detect_open first");
-    // spin on the count of finished kernels; bounded: after ~2 ms without it, fall back to the stream (kws_stream_utt_poll)
-    volatile unsigned long long* h = u->a.h_ctr;
-    const unsigned long long want = u->ticks_enqueued;
-    bool seen = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (long spin = 1;; ++spin) {
-        if (h[2] >= want) {
-            seen = true;
-            break;
-        }
-        __builtin_ia32_pause();
-        if ((spin & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-    }
-    if (!seen) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (h[2] < want) return fail(c, KWS_EHIP, "kws_stream_detect_poll: the stream drained but the step's flag never arrived");
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    if (total_events) *total_events = h[0];
-    if (decisions) *decisions = h[1];
-    return KWS_OK;
+    return eq_wait(c, "kws_stream_detect_poll", u->a.q, total_events, decisions);
 }
 
 int kws_stream_detect_read(kws_ctx* c, uint64_t first_seq, int n, int64_t* out_records) {
     if (!c) return KWS_EINVAL;
     StreamDetect* u = c->stream_detect;
     if (!u) return fail(c, KWS_ESTATE, "kws_stream_detect_read: call kws_stream_detect_open first");
-    if (n < 1 || !out_records) return fail(c, KWS_EINVAL, "kws_stream_detect_read: n must be positive and out_records not NULL");
-    volatile unsigned long long* h = u->a.h_ctr;
-    unsigned long long total = h[0];
-    std::atomic_thread_fence(std::memory_order_acquire);
-    if (first_seq + (unsigned long long)n > total) return fail(c, KWS_EINVAL, "kws_stream_detect_read: sequence numbers beyond the events landed so far");
-    for (int i = 0; i < n; ++i) {
-        const volatile long long* rec = u->a.h_queue + (size_t)((first_seq + i) % (unsigned long long)u->a.max_events) * DETECT_REC;
-        for (int k = 0; k < DETECT_REC; ++k) out_records[(size_t)i * DETECT_REC + k] = rec[k];
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    total = h[0];  // again: a step that landed during the copy may have overwritten the oldest
-    if (first_seq + (unsigned long long)u->a.max_events < total) return fail(c, KWS_EINVAL, "kws_stream_detect_read: the sequence number is no longer in the queue");
-    return KWS_OK;
+    return eq_read(c, "kws_stream_detect_read", u->a.q, DETECT_REC, first_seq, n, out_records);
 }
 
 int kws_stream_detect_smoothed(kws_ctx* c, float* d_smoothed, int32_t* d_label) {

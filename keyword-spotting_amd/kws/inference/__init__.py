@@ -973,6 +973,17 @@ class StreamingSpotter:
         head = (hops - k + 1) % t
         return np.roll(host, -head, axis=1), hops
 
+    def _drain(self, which: str, poll, read):
+        """What a host-mirrored event queue (``"_utt"`` or ``"_det"``) holds beyond this spotter's sequence counter: ``(first,
+        records)``, the counter advanced past them, or ``None`` with nothing new.  Records already overwritten are skipped."""
+        total = poll()[0]
+        first = max(getattr(self, which + "_seq"), total - getattr(self, which + "_max_events"))
+        if total <= first:
+            return None
+        rec = read(first, total - first)
+        setattr(self, which + "_seq", total)
+        return first, rec
+
     def pop_utterances(self) -> List[Utterance]:
         """The utterances that closed since the last call, in the order they closed (ascending stream within a hop).  Waits for
         the newest push's step (``kws_stream_utt_poll``); with nothing new it returns ``[]`` and launches nothing.  Otherwise, on
@@ -984,13 +995,9 @@ class StreamingSpotter:
         hops after it closed has left the history and comes back with ``peak`` -1 and a silent clip's logits."""
         if self.utterances is None:
             raise ModelError("pop_utterances: this StreamingSpotter was created without utterances=UtteranceConfig(...)")
-        total, _ = self._ctx.stream_utt_poll()
-        first = max(self._utt_seq, total - self._utt_max_events)
-        U = total - first
-        if U <= 0:
+        if (new := self._drain("_utt", self._ctx.stream_utt_poll, self._ctx.stream_utt_read)) is None:
             return []
-        rec = self._ctx.stream_utt_read(first, U)
-        self._utt_seq = total
+        first, rec = new
         return _classify_spans(self._ctx, self.device, self.words, self.model.num_classes, self.config.desired_samples,
                                float(self.config.sample_rate), self.hop, rec,
                                lambda clips, peaks: self._ctx.stream_utt_cut_i16(first, clips, int(self.utterances.normalize), peaks))
@@ -1010,12 +1017,9 @@ class StreamingSpotter:
         Records the queue has already overwritten (more than ``max_events`` events between two calls) are skipped."""
         if self.detect is None:
             raise ModelError("pop_events: this StreamingSpotter was created without detect=DetectConfig(...)")
-        total, _ = self._ctx.stream_detect_poll()
-        first = max(self._det_seq, total - self._det_max_events)
-        if total - first <= 0:
+        if (new := self._drain("_det", self._ctx.stream_detect_poll, self._ctx.stream_detect_read)) is None:
             return []
-        rec = self._ctx.stream_detect_read(first, total - first)
-        self._det_seq = total
+        rec = new[1]
         score = (rec[:, 4] & 0xFFFFFFFF).astype(np.uint32).view(np.float32)
         rate = float(self.config.sample_rate)
         return [KeywordEvent(int(s), ((int(h) - self._det_lag) * self.hop + self._det_frame_len) / rate, int(k), self.words[int(k)],

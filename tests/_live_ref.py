@@ -74,6 +74,27 @@ def whole_signal_records(flags, on_window, off_window, pre_roll, max_frames, **g
     return sorted(rows, key=lambda r: (r[4], r[5] == 2, r[0]))
 
 
+def rows(rec):
+    """Records as the queue returns them (int64 [n, 6]) -> the tuples of the two functions above."""
+    return [tuple(int(v) for v in r) for r in rec]
+
+
+def energies(flags, threshold=0.0):
+    """flags [S, F] -> float32 [F, S] at threshold +- 1: one contiguous [S] row of energies per explicit step."""
+    return np.ascontiguousarray(np.where(np.asarray(flags).T > 0, threshold + 1.0, threshold - 1.0).astype(np.float32))
+
+
+def count_flags(S):
+    """Stream s: a first run [2 + d, 8 + d), d = s mod 7, that closes by endpoint at 12 + d, then a run from 16 + d up to frame 40
+    for everyone: all streams close at step 44."""
+    v = np.zeros((S, 46), np.int64)
+    for s in range(S):
+        d = s % 7
+        v[s, 2 + d:8 + d] = 1
+        v[s, 16 + d:40] = 1
+    return v
+
+
 # ---- the walk sweep -----------------------------------------------------------------------------------------------------
 SWEEP_FRAMES = [1, 63, 64, 65, 129, 700]
 SWEEP_PRE_ROLLS = [0, 60, 10000]

@@ -220,6 +220,39 @@ def test_queue_keeps_the_newest_max_events(bare):
     assert time.perf_counter() - t0 < 1e-3
 
 
+def test_both_sets_on_one_context_keep_their_own_queues(bare):
+    """Utterances and detection armed on ONE context and stepped alternately, never waiting: both queues go through the same
+    code (kws_event_queue.h), each with its own counters, slots and kernel count.  The utterance queue (max_events = S) wraps --
+    2 S records, the last S closing in one step, the rules and flags of test_live_gpu.test_sequence_numbers_across_stream_counts
+    --, the detection queue (46 S slots) never does and holds the bytes of the same steps with detection armed alone.  On the
+    CPU (_live_detect_ref.LiveDetectRef, float64) these logits fire 834 events, every one of the 65 streams among them."""
+    S, W, Cn = 65, 46, N_CLASSES
+    flags = lr.count_flags(S)
+    want_utt = lr.whole_signal_records(flags, 3, 5, 2, 1000)
+    assert len(want_utt) == 2 * S and {r[4] for r in want_utt[S:]} == {44}
+    z = ref.detect_logits(W, Cn, range(1200, 1200 + S))
+    _, _, alone, n_alone, _ = _live_steps(bare, z, 2, 2, 0.5, 3, watch=False)
+    assert n_alone > S
+    bare.stream_open(S)
+    bare.stream_utt_open(0.0, 3, 5, 2, 1000, _native.host_stream_utt_history(ref.FRAME_LEN, STEP, 2, 1000, 0), S)
+    bare.stream_detect_open(Cn, 2, 2, 0.5, 3, 0, W * S)
+    e = torch.from_numpy(lr.energies(flags)).to(DEV)                           # one contiguous [S] row per step
+    zt = torch.from_numpy(np.ascontiguousarray(z.transpose(1, 0, 2))).to(DEV)  # one contiguous [S, C] block per step
+    torch.cuda.synchronize()
+    for t in range(W):
+        bare.stream_utt_step_i16(None, e.data_ptr() + 4 * S * t)
+        bare.stream_detect_step_f32(zt.data_ptr() + 4 * S * Cn * t)
+    bare.stream_utt_flush()
+    assert bare.stream_utt_poll() == (2 * S, W)
+    assert lr.rows(bare.stream_utt_read(S, S)) == want_utt[S:]
+    out = (C.c_int64 * 6)()
+    assert bare._lib.kws_stream_utt_read(bare._h, S - 1, 1, out) == EINVAL  # overwritten
+    total, decisions = bare.stream_detect_poll()
+    assert (total, decisions) == (n_alone, W)
+    assert bare.stream_detect_read(0, total).tobytes() == alone.tobytes()
+    bare.sync()
+
+
 # ---- 4. armed pushes, real front end -------------------------------------------------------------------------------------------------
 PUSH_S, PUSH_HOPS = 5, 130
 # Chosen on the CPU with oracle_scan + smooth_ref over mixed_recordings(5, 130 hops): at a window of 5 the complete windows' top

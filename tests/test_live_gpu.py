@@ -48,12 +48,10 @@ def _arm(c, on, off, pre_roll, max_frames, slack_hops=0, max_events=4096, thresh
 
 def _energies(flags, threshold=0.0):
     """flags [S, F] -> float32 [F, S] on the device at threshold +- 1: one contiguous [S] row per step."""
-    e = np.where(np.asarray(flags).T > 0, threshold + 1.0, threshold - 1.0).astype(np.float32)
-    return torch.from_numpy(np.ascontiguousarray(e)).to(DEV)
+    return torch.from_numpy(lr.energies(flags, threshold)).to(DEV)
 
 
-def _rows(rec):
-    return [tuple(int(v) for v in r) for r in rec]
+_rows = lr.rows
 
 
 def _all_records(c):
@@ -130,20 +128,9 @@ def test_threshold_is_strict_and_a_nan_is_unvoiced(bare):
 
 
 # ---- 6. stream counts ---------------------------------------------------------------------------------------------------------
-def _count_flags(S):
-    """Stream s: a first run [2 + d, 8 + d), d = s mod 7, that closes by endpoint at 12 + d, then a run from 16 + d up to frame 40
-    for everyone: all streams close at step 44."""
-    v = np.zeros((S, 46), np.int64)
-    for s in range(S):
-        d = s % 7
-        v[s, 2 + d:8 + d] = 1
-        v[s, 16 + d:40] = 1
-    return v
-
-
 @pytest.mark.parametrize("S", [1, 63, 64, 65, 130, 1024])
 def test_sequence_numbers_across_stream_counts(bare, S):
-    flags = _count_flags(S)
+    flags = lr.count_flags(S)
     want = lr.whole_signal_records(flags, 3, 5, 2, 1000)
     assert len(want) == 2 * S and [r[0] for r in want[S:]] == list(range(S)) and {r[4] for r in want[S:]} == {44}
     runs = []
