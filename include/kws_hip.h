@@ -1023,6 +1023,14 @@ int kws_host_dscnn_image(const float* blob, size_t n_floats, int num_classes, in
                          size_t cap_words, size_t* need_words, float* scalars);
 int kws_host_cnn_trad_image(const float* blob, size_t n_floats, int num_classes, uint32_t* out_words, size_t cap_words,
                             size_t* need_words, float* scalars);
+/* The unit descriptor table every DS-CNN load places behind the device image, for the persistent batched forward (more clips
+ * than CUs): the per-lane geometry of each (block, tile) unit of the four depthwise-separable blocks on the [1,99,10] map, read
+ * by the f16-pair kernel instead of being recomputed for every clip.  It depends on the map geometry alone, not on the weights.  Words
+ * [unit][part 2][lane 64][4], unit = unit_base[block - 1] + tile; part 0 = the LDS float indices of the lane's own-column taps in
+ * rows h-1, h, h+1 (channel pair 8 * (lane >> 5)) and the store mask (all ones / all zeros); part 1 = the left and right
+ * neighbour masks (1.0f / 0.0f) and two zero words.  Size protocol of kws_host_dscnn_image; unit_base (may be NULL) receives
+ * five ints: the first unit of blocks 1..4 and the number of units. */
+int kws_host_dscnn_units(uint32_t* out_words, size_t cap_words, size_t* need_words, int* unit_base);
 
 /* Frames of a recording of n_total samples taken as one clip (*frames_total = 1 + ceil((n_total - frame_len) / frame_step),
  * 1 when n_total <= frame_len) and windows of a scan over it (*n_windows = (frames_total - window_frames) / hop_frames + 1,

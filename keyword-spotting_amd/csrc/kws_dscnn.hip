@@ -251,6 +251,9 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
     };
 
     constexpr bool SPLIT = MODE >= 4;
+    // unit descriptors (block_phase, UT): the persistent f16-pair kernels.  The bf16 triple, three pieces per operand, has no
+    // registers for a descriptor in flight (it spilled more and ran 0.9 % slower) and keeps computing its geometry.
+    constexpr bool UT = PERSIST && PAIR;
     // PERSIST: block 1's tables are the same for every clip (3 registers for the whole loop); conv1's operands are reloaded in
     // every block-4 tail, after the pool sums have left the registers.  The first clip is staged here.
     BlockTables t1p{};
@@ -266,7 +269,11 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
     for (;;) {  // one pass unless PERSIST (the body keeps its one-clip indentation)
     // PERSIST: every weight load of the body is clip-invariant; hoisted out of the loop they would pin hundreds of registers
     // for the workgroup's whole life (spills).  Opaque weight pointers per clip keep each load where it is.
-    const DscnnWeights w = PERSIST ? weights_for_this_clip() : w_arg;
+    // The same per PHASE: one copy for the whole clip keeps every pointer and bound of DscnnWeights live in scalar registers from
+    // the clip's head to block 4 (they spill into vector lanes); each phase reads what it uses again, ahead of the barrier it
+    // starts behind.
+    auto weights_now = [&]() -> DscnnWeights { return PERSIST ? weights_for_this_clip() : w_arg; };
+    const DscnnWeights w = weights_now();
     int tid = tid_k;
     if constexpr (PERSIST) {
         // the same for the thread index: every LDS address and mask is derived from it, and hoisted they spill.  The wavefront
@@ -281,6 +288,7 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
     stamp();  // 0: start (PERSIST: features already staged)
 
     PwOperands<MODE> wa;            // pointwise operands of the running block
+    UnitDesc ud{};                  // PERSIST: the descriptor of this wavefront's next block-phase unit (block_phase, UT)
     int hops_before = 0;            // STREAM: pushes before this one
     // PAIR: exponents of the clip's scales.  kx: features; ky[n]: block n's depthwise output (true units) * 2^ky[n] < 2^15;
     // sg[n]: the units stage n's accumulators and stored output are in (sg[0]: conv1), = ky[n] + the layer's weight exponent
@@ -307,6 +315,8 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
             pool_fc_wave(w, lds, lane, prev_clip, logits, label, a_prev);
             if (stamps && lane == 0) stamps[(size_t)prev_clip * KWS_DSCNN_STAMPS + 13] = __builtin_amdgcn_s_memtime();
         }
+        // block 1's first unit: tile wv, or (wavefronts 4-7) a quarter of the leftover tile
+        if constexpr (UT) load_unit_desc(w, 1, wv < Leftover<1>::TILE ? wv : Leftover<1>::TILE, lane, ud);
         load_afrag(w, 1, wv >= 4 ? wv - 4 : 0, lane, wa.ring[0]);  // wavefronts 4-7: their k-block of block 1's leftover tile
     } else if constexpr (PRECONV) {
         static_assert(!PRECONV || MODE >= 4, "the pre-convolved entry exists for the product (split) path only");
@@ -454,6 +464,7 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
     }
     }
     stamp();  // 2: conv1 units of wave 0 done
+    const DscnnWeights w1 = weights_now();
     __syncthreads();
     stamp();  // 3: conv1 barrier
     float* a = act ? act + (size_t)clip * KWS_ACT_FLOATS_PER_CLIP : nullptr;
@@ -467,9 +478,9 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
     PairCtx pc;
     if constexpr (PAIR && PRECONV) {
         const float mz0 = read_stage_max(lds, 1, 1);  // true units
-        const float by1 = (w.dw_abs[0] * mz0 + w.dw_bmax[0]) * 1.001f;
+        const float by1 = (w1.dw_abs[0] * mz0 + w1.dw_bmax[0]) * 1.001f;
         ky[1] = pow2_exp_for(by1);
-        cap_units(ky[1], sg[1], w.k_pw[0], (w.pw_abs[0] * by1 + w.pw_bmax[0]) * 1.001f);
+        cap_units(ky[1], sg[1], w1.k_pw[0], (w1.pw_abs[0] * by1 + w1.pw_bmax[0]) * 1.001f);
         store_block_tables(lds, 1, tid, t1_pre, pow2f(ky[1]), pow2f(sg[1]), pow2f(ky[1]));
         __syncthreads();
     }
@@ -477,16 +488,17 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
         // conv1's largest output is known now: it bounds block 1's output, which fixes block 2's operand scale and units --
         // two layers ahead, so that block 2's tables can be stored (scaled) while block 1 runs
         const float mz = read_stage_max(lds, 1, 1) * pow2f(-sg[0]);
-        const float bz = (w.pw_abs[0] * ((w.dw_abs[0] * mz + w.dw_bmax[0]) * 1.001f) + w.pw_bmax[0]) * 1.001f;
-        const float by = (w.dw_abs[1] * bz + w.dw_bmax[1]) * 1.001f;
+        const float bz = (w1.pw_abs[0] * ((w1.dw_abs[0] * mz + w1.dw_bmax[0]) * 1.001f) + w1.pw_bmax[0]) * 1.001f;
+        const float by = (w1.dw_abs[1] * bz + w1.dw_bmax[1]) * 1.001f;
         ky[2] = pow2_exp_for(by);
-        cap_units(ky[2], sg[2], w.k_pw[1], (w.pw_abs[1] * by + w.pw_bmax[1]) * 1.001f);
+        cap_units(ky[2], sg[2], w1.k_pw[1], (w1.pw_abs[1] * by + w1.pw_bmax[1]) * 1.001f);
         pc.s_dww = pow2f(ky[2] - sg[1]);
         pc.s_dwb = pow2f(ky[2]);
         pc.s_pwb = pow2f(sg[2]);
     }
-    block_phase<1, MODE, CLUSTER>(w, lds, tid, wa, nullptr, rg1, pc);
+    block_phase<1, MODE, CLUSTER, UT>(w1, lds, tid, wa, ud, nullptr, rg1, pc);
     stamp();  // 4: block 1 units of wave 0 done
+    const DscnnWeights w2 = weights_now();
     __syncthreads();
     if constexpr (Leftover<1>::HAS && KSL_ON) {
         leftover_combine<1, PAIR>(lds, tid);
@@ -501,17 +513,18 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
     }
     if constexpr (PAIR) {
         // block 2 reads block 1's interior and its ring (relu(bias) <= pw_bmax)
-        const float mz = fmaxf(read_stage_max(lds, 2, (Leftover<1>::HAS && KSL_ON) ? 2 : 1) * pow2f(-sg[1]), w.pw_bmax[0]);
-        const float bz = (w.pw_abs[1] * ((w.dw_abs[1] * mz + w.dw_bmax[1]) * 1.001f) + w.pw_bmax[1]) * 1.001f;
-        const float by = (w.dw_abs[2] * bz + w.dw_bmax[2]) * 1.001f;
+        const float mz = fmaxf(read_stage_max(lds, 2, (Leftover<1>::HAS && KSL_ON) ? 2 : 1) * pow2f(-sg[1]), w2.pw_bmax[0]);
+        const float bz = (w2.pw_abs[1] * ((w2.dw_abs[1] * mz + w2.dw_bmax[1]) * 1.001f) + w2.pw_bmax[1]) * 1.001f;
+        const float by = (w2.dw_abs[2] * bz + w2.dw_bmax[2]) * 1.001f;
         ky[3] = pow2_exp_for(by);
-        cap_units(ky[3], sg[3], w.k_pw[2], (w.pw_abs[2] * by + w.pw_bmax[2]) * 1.001f);
+        cap_units(ky[3], sg[3], w2.k_pw[2], (w2.pw_abs[2] * by + w2.pw_bmax[2]) * 1.001f);
         pc.s_dww = pow2f(ky[3] - sg[2]);
         pc.s_dwb = pow2f(ky[3]);
         pc.s_pwb = pow2f(sg[3]);
     }
-    block_phase<2, MODE, CLUSTER>(w, lds, tid, wa, nullptr, rg2, pc);
+    block_phase<2, MODE, CLUSTER, UT>(w2, lds, tid, wa, ud, nullptr, rg2, pc);
     stamp();  // 6
+    const DscnnWeights w3 = weights_now();
     __syncthreads();
     if constexpr (Leftover<2>::HAS && KSL_ON) {
         leftover_combine<2, PAIR>(lds, tid);
@@ -525,17 +538,18 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
         a += CH * Blk<2>::POUT;
     }
     if constexpr (PAIR) {
-        const float mz = fmaxf(read_stage_max(lds, 0, (Leftover<2>::HAS && KSL_ON) ? 2 : 1) * pow2f(-sg[2]), w.pw_bmax[1]);
-        const float bz = (w.pw_abs[2] * ((w.dw_abs[2] * mz + w.dw_bmax[2]) * 1.001f) + w.pw_bmax[2]) * 1.001f;
-        const float by = (w.dw_abs[3] * bz + w.dw_bmax[3]) * 1.001f;
+        const float mz = fmaxf(read_stage_max(lds, 0, (Leftover<2>::HAS && KSL_ON) ? 2 : 1) * pow2f(-sg[2]), w3.pw_bmax[1]);
+        const float bz = (w3.pw_abs[2] * ((w3.dw_abs[2] * mz + w3.dw_bmax[2]) * 1.001f) + w3.pw_bmax[2]) * 1.001f;
+        const float by = (w3.dw_abs[3] * bz + w3.dw_bmax[3]) * 1.001f;
         ky[4] = pow2_exp_for(by);
-        cap_units(ky[4], sg[4], w.k_pw[3], (w.pw_abs[3] * by + w.pw_bmax[3]) * 1.001f);
+        cap_units(ky[4], sg[4], w3.k_pw[3], (w3.pw_abs[3] * by + w3.pw_bmax[3]) * 1.001f);
         pc.s_dww = pow2f(ky[4] - sg[3]);
         pc.s_dwb = pow2f(ky[4]);
         pc.s_pwb = pow2f(sg[4]);
     }
-    block_phase<3, MODE, CLUSTER>(w, lds, tid, wa, nullptr, rg3, pc);
+    block_phase<3, MODE, CLUSTER, UT>(w3, lds, tid, wa, ud, nullptr, rg3, pc);
     stamp();  // 8
+    const DscnnWeights w4 = weights_now();
     __syncthreads();
     stamp();  // 9
     if (a) {
@@ -547,8 +561,8 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
     if constexpr (PAIR) {
         pc.inv_out = pow2f(-sg[4]);
     }
-    block_phase<4, MODE, CLUSTER>(w, lds, tid, wa, a ? a + CH : nullptr, rg4, pc,  // block 4's output follows the pooled means
-                                  PERSIST ? OFF_POOLBUF_P : OFF_POOLBUF);
+    block_phase<4, MODE, CLUSTER, UT>(w4, lds, tid, wa, ud, a ? a + CH : nullptr, rg4, pc,  // block 4's output follows the pooled means
+                                      PERSIST ? OFF_POOLBUF_P : OFF_POOLBUF);
     stamp();  // 10
     if constexpr (PERSIST) {
         // block 4's tail: the pool partials are stored; wavefronts 0-3 stage the next clip while 4-7 finish their units, and
@@ -559,7 +573,7 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
         const ScanWindows sw_next = SCAN ? scan_windows_now() : ScanWindows{};  // (outside the branch: a uniform scalar read)
         if (wv < STAGE_WAVES && next < B) stage_features_persist<PAIR, SCAN>(lds, feat, next, tid, sw_next);
         stamp();  // 11: next clip staged (wavefront 0)
-        load_conv1_frags(w, wv, lane, c1p);  // (unconditional: a conditional reload keeps the old copy live through the whole loop)
+        load_conv1_frags(w4, wv, lane, c1p);  // (unconditional: a conditional reload keeps the old copy live through the whole loop)
         __syncthreads();
         stamp();  // 12: block 4 barrier
         if (stamps && tid == KWS_X_DSCNN_STAMP_TID) stamps[(size_t)clip * KWS_DSCNN_STAMPS + KWS_DSCNN_STAMPS - 1] = __builtin_amdgcn_s_memrealtime();
@@ -572,16 +586,16 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
     // The classifier row of lane c (wavefront 0) and the ring bias of channel tid are requested BEFORE the barrier:
     // their L2 round trips pass while the workgroup waits for its slowest wavefront, instead of sitting exposed at
     // the very end of the clip (the CU cannot take its next clip before this wavefront is done).
-    const int C = w.num_classes;
+    const int C = w4.num_classes;
     float4 fcw[CH / 4];
     float fcb = 0.f, ring_b = 0.f;
     if (wv == 0 && lane < C) {
-        const float4* wr = reinterpret_cast<const float4*>(w.fc_w + lane * CH);
+        const float4* wr = reinterpret_cast<const float4*>(w4.fc_w + lane * CH);
 #pragma unroll
         for (int c = 0; c < CH / 4; ++c) fcw[c] = wr[c];
-        fcb = w.fc_b[lane];
+        fcb = w4.fc_b[lane];
     }
-    if (tid < CH) ring_b = w.pw_b[3 * CH + tid];
+    if (tid < CH) ring_b = w4.pw_b[3 * CH + tid];
     __syncthreads();
     stamp();  // 11
 

@@ -41,7 +41,7 @@ static_assert(CH * 12 <= 2 * NT, "table staging assumes at most two elements per
 // planes hold S floats lives at (c >> 1) * 2S + 2p + (c & 1).  One ds_read_b64 then fetches a column's value for
 // two consecutive channels (the split path walks channels two at a time) and the epilogue stores two output
 // channels with one ds_write_b64: half the tap reads and stores, at twice the bytes per LDS cycle.
-__device__ __forceinline__ constexpr int pidx(int c, int p, int S) { return (c >> 1) * 2 * S + 2 * p + (c & 1); }
+__host__ __device__ __forceinline__ constexpr int pidx(int c, int p, int S) { return (c >> 1) * 2 * S + 2 * p + (c & 1); }
 
 // Geometry of block N (1..4): output plane H x W (all of it is the next block's interior).
 template <int N>

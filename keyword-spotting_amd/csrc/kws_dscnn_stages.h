@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "kws_dscnn_geom.h"
+#include "kws_dscnn_units.h"
 #include "kws_mfcc_dev.h"
 #include "kws_split_mfma.h"
 
@@ -176,6 +177,19 @@ __device__ __forceinline__ void load_afrag(const DscnnWeights& w, int n, int m, 
 __device__ __forceinline__ void load_block_head(const DscnnWeights& w, int n, int lane, PwRegsF32& o) { load_pointwise(w, n, lane, o); }
 template <int NP>
 __device__ __forceinline__ void load_block_head(const DscnnWeights& w, int n, int lane, PwRing<NP>& o) { load_afrag(w, n, 0, lane, o.ring[0]); }
+
+// The descriptor of a block-phase unit as its lane holds it (kws_dscnn_units.h): requested where the unit's first A operands
+// are requested -- a unit ahead -- so it returns in order with them, and read at the unit's head in place of the geometry
+// arithmetic.  The persistent batched f16-pair kernels only (UT); every other route computes its geometry.
+struct UnitDesc {
+    uintx4 a;  // tlo[0..2], valid
+    uint2 m;   // mask_l, mask_r
+};
+__device__ __forceinline__ void load_unit_desc(const DscnnWeights& w, int n, int tile, int lane, UnitDesc& d) {
+    const uint32_t* src = w.units + ((size_t)(ds_unit_base(n - 1) + tile) * 2 * 64 + lane) * 4;
+    d.a = *reinterpret_cast<const uintx4*>(src);
+    d.m = *reinterpret_cast<const uint2*>(src + 64 * 4);
+}
 
 // ------------------------------------------------------------------------------------------------
 // conv1: D[cout][pos] = sum_k W[cout][k] * im2col[k][pos], k = kh*10 + kw, as 50 MFMA k-steps.
@@ -533,27 +547,37 @@ __device__ __forceinline__ void conv1_phase_split(const DscnnWeights& w, float* 
 // A quarter of the leftover tile of block N (see Leftover): k-block M (input channels 16M .. 16M+15) of tile Leftover<N>::TILE
 // for both output-channel tiles.  Eight stencil steps, one split, twelve MFMAs, the raw partial sums (no bias, no ReLU) of the
 // tile's valid columns to part[M][cout][position in tile].  af: the pre-split weights of k-block M (requested long before).
-template <int N, int NP>
-__device__ __forceinline__ void leftover_partial_unit(float* lds, int lane, int M, const uintx4 (&af)[2][NP]) {
+// UT: the tile's geometry from its unit descriptor ud (else ud is not read).
+template <int N, int NP, bool UT = false>
+__device__ __forceinline__ void leftover_partial_unit(float* lds, int lane, int M, const uintx4 (&af)[2][NP], const UnitDesc& ud) {
     using G = Blk<N>;
     using L = Leftover<N>;
     const int half = lane >> 5, col = lane & 31;
     const float* dwtab = lds + OFF_DWTAB + G::BUF * 768;
     const float4* dwt4 = reinterpret_cast<const float4*>(dwtab) + half * 24;
-    const int pos = L::P0T - 1 + col;
-    const bool valid = col >= 1 && col <= TW && pos < G::POUT;
-    const int posc = pos < G::POUT ? pos : G::POUT - 1;  // (pos >= P0T - 1 >= 0)
-    const int h = posc / G::W, x = posc % G::W;
-    const float mask_l = x > 0 ? 1.f : 0.f, mask_r = x < G::W - 1 ? 1.f : 0.f;
+    bool valid;
+    float mask_l, mask_r;
     int ta[3];  // own-column tap addresses (rows h-1, h, h+1) of channel pair 8 * half, as float indices into lds
+    if constexpr (UT) {
+        valid = ud.a[3] != 0u;
+        mask_l = __builtin_bit_cast(float, ud.m.x), mask_r = __builtin_bit_cast(float, ud.m.y);
 #pragma unroll
-    for (int dh = -1; dh <= 1; ++dh) {
-        const int o = G::RING ? 1 : 0;
-        const int hh = h + dh - o, xx = x - o;
-        const bool inside = (unsigned)hh < (unsigned)G::HI && (unsigned)xx < (unsigned)G::WI;
-        const bool in_map = (unsigned)(h + dh) < (unsigned)G::H;
-        const int a = inside ? hh * G::WI + xx : ((G::RING && in_map) ? G::PIN : G::PIN + 1);
-        ta[dh + 1] = G::OFF_IN + pidx(half * 8, a, G::SIN);
+        for (int i = 0; i < 3; ++i) ta[i] = (int)ud.a[i];
+    } else {
+        const int pos = L::P0T - 1 + col;
+        valid = col >= 1 && col <= TW && pos < G::POUT;
+        const int posc = pos < G::POUT ? pos : G::POUT - 1;  // (pos >= P0T - 1 >= 0)
+        const int h = posc / G::W, x = posc % G::W;
+        mask_l = x > 0 ? 1.f : 0.f, mask_r = x < G::W - 1 ? 1.f : 0.f;
+#pragma unroll
+        for (int dh = -1; dh <= 1; ++dh) {
+            const int o = G::RING ? 1 : 0;
+            const int hh = h + dh - o, xx = x - o;
+            const bool inside = (unsigned)hh < (unsigned)G::HI && (unsigned)xx < (unsigned)G::WI;
+            const bool in_map = (unsigned)(h + dh) < (unsigned)G::H;
+            const int a = inside ? hh * G::WI + xx : ((G::RING && in_map) ? G::PIN : G::PIN + 1);
+            ta[dh + 1] = G::OFF_IN + pidx(half * 8, a, G::SIN);
+        }
     }
     float y[8];
 #pragma unroll
@@ -629,10 +653,15 @@ __device__ __forceinline__ void leftover_combine(float* lds, int tid) {
 // act4 (diagnostics instantiation only, block 4): global [64][53*9] that receives the block's output, which the product
 // path never stores (it is pooled in registers).
 // RANGED: only the positions rg.lo .. rg.hi - 1 (whole rows) are computed -- one time tile of a workgroup cluster.
-template <int N, int MODE, bool RANGED = false>
-__device__ __forceinline__ void block_phase(const DscnnWeights& w, float* lds, int tid, PwOperands<MODE>& pwo,
+// UT (persistent batched kernel, whole maps): a unit's geometry comes from its descriptor.  ud: on entry the descriptor of this
+// wavefront's FIRST unit of this block (a tile, or its quarter of block 1's leftover tile), requested by the caller or by the
+// previous block; on exit (N < 4) the request for its first unit of the next block.  Every later unit's descriptor is
+// requested beside the A operands of that unit, in front of them.  Not read or written without UT.
+template <int N, int MODE, bool RANGED = false, bool UT = false>
+__device__ __forceinline__ void block_phase(const DscnnWeights& w, float* lds, int tid, PwOperands<MODE>& pwo, UnitDesc& ud,
                                             float* __restrict__ act4 = nullptr, PosRange rg = PosRange{0, 0}, PairCtx pc = PairCtx{},
                                             int off_poolbuf = OFF_POOLBUF) {
+    static_assert(!UT || ((MODE == 4 || MODE == 5) && !RANGED && Leftover<1>::HAS), "unit descriptors: product paths on whole maps");
     using G = Blk<N>;
     constexpr bool PAIR = MODE == 5;          // f16 pairs: three products per k-block, activations in per-clip scaled units
     constexpr int NP = PAIR ? 2 : 3;
@@ -686,26 +715,44 @@ __device__ __forceinline__ void block_phase(const DscnnWeights& w, float* lds, i
         // range's ends is clamped into it: a range ends on a row end, where the neighbour's contribution is masked anyway,
         // and the clamp keeps the lane's own reads on rows this workgroup has computed.
         const int pos = p_lo + t * TW - 1 + col;
-        const bool valid = col >= 1 && col <= TW && pos < p_hi;
-        const int posc = pos < p_lo ? p_lo : (pos < p_hi ? pos : p_hi - 1);
-        const int h = posc / G::W, x = posc % G::W;
-        const float mask_l = x > 0 ? 1.f : 0.f, mask_r = x < G::W - 1 ? 1.f : 0.f;
+        bool valid;
+        uint32_t keep;  // valid as all ones / all zeros
+        float mask_l, mask_r;
         // own-column tap addresses (rows h-1, h, h+1), as float indices into lds, for channel pairs
         // 0..15 (lo) and 16..31 (hi): two bases keep every ds_read inside the 64 KiB immediate window;
         // the empty asm stops the compiler from re-deriving one base register per step.
         int tlo[3], thi[3];
+        if constexpr (UT) {
+            keep = ud.a[3];
+            valid = keep != 0u;
+            mask_l = __builtin_bit_cast(float, ud.m.x), mask_r = __builtin_bit_cast(float, ud.m.y);
 #pragma unroll
-        for (int dh = -1; dh <= 1; ++dh) {
-            const int o = G::RING ? 1 : 0;
-            const int hh = h + dh - o, xx = x - o;
-            const bool inside = (unsigned)hh < (unsigned)G::HI && (unsigned)xx < (unsigned)G::WI;
-            const bool in_map = (unsigned)(h + dh) < (unsigned)G::H;
-            const int a = inside ? hh * G::WI + xx : ((G::RING && in_map) ? G::PIN : G::PIN + 1);
-            tlo[dh + 1] = G::OFF_IN + pidx(half * 8, a, G::SIN);
-            thi[dh + 1] = tlo[dh + 1] + 32 * G::SIN;
-            asm volatile("" : "+v"(tlo[dh + 1]));
-            asm volatile("" : "+v"(thi[dh + 1]));
+            for (int i = 0; i < 3; ++i) {
+                tlo[i] = (int)ud.a[i];
+                thi[i] = tlo[i] + 32 * G::SIN;
+                asm volatile("" : "+v"(tlo[i]));
+                asm volatile("" : "+v"(thi[i]));
+            }
+        } else {
+            valid = col >= 1 && col <= TW && pos < p_hi;
+            keep = valid ? 0xffffffffu : 0u;
+            const int posc = pos < p_lo ? p_lo : (pos < p_hi ? pos : p_hi - 1);
+            const int h = posc / G::W, x = posc % G::W;
+            mask_l = x > 0 ? 1.f : 0.f, mask_r = x < G::W - 1 ? 1.f : 0.f;
+#pragma unroll
+            for (int dh = -1; dh <= 1; ++dh) {
+                const int o = G::RING ? 1 : 0;
+                const int hh = h + dh - o, xx = x - o;
+                const bool inside = (unsigned)hh < (unsigned)G::HI && (unsigned)xx < (unsigned)G::WI;
+                const bool in_map = (unsigned)(h + dh) < (unsigned)G::H;
+                const int a = inside ? hh * G::WI + xx : ((G::RING && in_map) ? G::PIN : G::PIN + 1);
+                tlo[dh + 1] = G::OFF_IN + pidx(half * 8, a, G::SIN);
+                thi[dh + 1] = tlo[dh + 1] + 32 * G::SIN;
+                asm volatile("" : "+v"(tlo[dh + 1]));
+                asm volatile("" : "+v"(thi[dh + 1]));
+            }
         }
+        UnitDesc ud_next = ud;  // UT: the descriptor this wavefront reads next, requested in the last k-block
 
         auto cs_of = [](int s) { return 16 * (s >> 3) + (s & 7); };  // channel of step s minus the half's offset 8*half
         // the own-column inputs of channels (cs, cs+1), cs even, in three 8-byte reads (pair-interleaved planes)
@@ -798,15 +845,21 @@ __device__ __forceinline__ void block_phase(const DscnnWeights& w, float* lds, i
                     __builtin_amdgcn_sched_barrier(0);
                     if (j == 6) {
                         // the products of k-block m-1 are done: its ring slot takes k-block m+1, or k-block 0 of
-                        // this wave's next unit / of the next block
-                        if (m < 3)
+                        // this wave's next unit / of the next block (UT: that unit's descriptor in front of it -- the tap
+                        // addresses of this unit were last read four steps ago)
+                        if (m < 3) {
                             load_afrag(w, N, m + 1, lane, pwo.ring[(m + 1) & 1]);
-                        else if (t + NW < n_tiles)
+                        } else if (t + NW < n_tiles) {
+                            if constexpr (UT) load_unit_desc(w, N, t + NW, lane, ud_next);
                             load_afrag(w, N, 0, lane, pwo.ring[0]);
-                        else if (KSL && N == 2 && wv < 4)
+                        } else if (KSL && N == 2 && wv < 4) {
+                            if constexpr (UT) load_unit_desc(w, N, Leftover<N>::TILE, lane, ud_next);
                             load_afrag(w, N, wv, lane, pwo.ring[0]);  // this wavefront's quarter of the leftover tile comes next
-                        else if (N < 4)
+                        } else if (N < 4) {
+                            // (blocks 2 - 4 have a tile for every wavefront: its first unit there is tile wv)
+                            if constexpr (UT) load_unit_desc(w, N < 4 ? N + 1 : N, wv, lane, ud_next);
                             load_afrag(w, N < 4 ? N + 1 : N, 0, lane, pwo.ring[0]);
+                        }
                         __builtin_amdgcn_sched_barrier(0);
                     }
                     if (j == 7) {
@@ -895,7 +948,6 @@ __device__ __forceinline__ void block_phase(const DscnnWeights& w, float* lds, i
                     // relu is an asm statement: written as `valid ? relu(x) : 0` every element became its own exec-masked
                     // branch region (16 per unit).  An AND with an all-ones / all-zeros mask selects without a branch -- and,
                     // unlike a 0/1 factor, also if a halo lane ever held a NaN.
-                    const uint32_t keep = valid ? 0xffffffffu : 0u;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         psum[0][r] += __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, relu(acc0[r])) & keep);
@@ -922,6 +974,7 @@ __device__ __forceinline__ void block_phase(const DscnnWeights& w, float* lds, i
                 }
             }
             epilogue();
+            if constexpr (UT) ud = ud_next;
         } else {
             // VALU cross-check of the pointwise GEMM: each half sums its 32 input channels, halves are
             // combined with a lane exchange.
@@ -959,8 +1012,9 @@ __device__ __forceinline__ void block_phase(const DscnnWeights& w, float* lds, i
     if constexpr (KSL) {
         using L = Leftover<N>;
         if (wv >= L::WAVE0 && wv < L::WAVE0 + 4) {
-            leftover_partial_unit<N, NP>(lds, lane, wv - L::WAVE0, pwo.ring[0]);
+            leftover_partial_unit<N, NP, UT>(lds, lane, wv - L::WAVE0, pwo.ring[0], ud);
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (UT) load_unit_desc(w, N + 1, wv, lane, ud);  // (block 2 has a tile for every wavefront, block 3 too)
             load_afrag(w, N + 1, 0, lane, pwo.ring[0]);  // the next block's first operands fly across the barrier
         }
     }

@@ -226,6 +226,7 @@ struct DscnnWeights {
     // |depthwise out| <= dw_abs max|in| + dw_bmax, |pointwise out| <= pw_abs max|depthwise out| + pw_bmax (row sums of |w|,
     // maximised over output channels, rounded up)
     float c1_abs, c1_bmax, dw_abs[4], dw_bmax[4], pw_abs[4], pw_bmax[4];
+    const uint32_t* units;     // [unit 42][part 2][lane 64][4]  unit descriptors of the block phases (kws_dscnn_units.h; persistent launch)
 };
 
 hipError_t dscnn_init_device();

@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "kws_ctx.h"
+#include "kws_dscnn_units.h"
 #include "kws_pack.h"
 
 using namespace kws;
@@ -110,12 +111,20 @@ static void dscnn_scalars_out(const DscnnWeights& mw, float* scalars) {
         for (int b = 0; b < 4; ++b) *scalars++ = p[b];
 }
 
-// The host image h of a checked blob and the members DscnnWeights carries by value (its pointers stay null).
+// The device allocation of a DS-CNN model: the image (L.total words, what the exports return) and behind it the unit descriptor
+// table of the persistent forward kernel (kws_dscnn_units.h), which no export returns.
+static size_t ds_alloc_words(const DscnnLayout& L) {
+    static_assert(DS_UNIT_WORDS % 4 == 0, "whole 16-byte rows");
+    return L.total + DS_UNIT_WORDS;  // (L.total is a multiple of four words: the table is 16-byte aligned)
+}
+
+// The host image h of a checked blob with the unit table behind it, and the members DscnnWeights carries by value (its pointers
+// stay null).
 static void build_dscnn_image(const float* blob, const DscnnLayout& L, std::vector<float>& h, DscnnWeights& mw) {
     const int input_channels = L.in_channels;
     DscnnScales sw;
     mw = ds_scalars(dscnn_host_stats(blob, L), L, sw);
-    h.assign(L.total, 0.f);
+    h.assign(ds_alloc_words(L), 0.f);
     const float* src = blob;
     memcpy(&h[L.o_raw], blob, L.n_floats * sizeof(float));  // torch layouts, for the composed any-map path (kws_forward_map_f32)
     // conv1.weight [64][C][10][10] -> [ci][tap][cout] (kws_conv1_general_kernel for C > 1, kws_conv1_any_kernel for any map)
@@ -146,6 +155,7 @@ static void build_dscnn_image(const float* blob, const DscnnLayout& L, std::vect
     // conv1 and the pointwise layers as MFMA A operands, both arithmetics (kws_pack.h)
     uint32_t* const img = reinterpret_cast<uint32_t*>(h.data());
     for (size_t i = 0; i < L.n_frag; ++i) ds_pack_fragment(L, blob, i, sw, img);
+    for (size_t i = 0; i < DS_UNIT_WORDS; ++i) img[L.total + i] = ds_unit_word(i);
 }
 
 // Point the context at a complete device image d (layout L); mw holds the values DscnnWeights carries by value.
@@ -166,6 +176,7 @@ static void install_dscnn(kws_ctx* c, float* d, const DscnnLayout& L, DscnnWeigh
     mw.fc_b = d + L.o_fcb;
     mw.c1_general = d + L.o_c1g;
     mw.raw = d + L.o_raw;
+    mw.units = reinterpret_cast<const uint32_t*>(d + L.total);
     c->mw = mw;
     c->model_ready = true;
 }
@@ -223,11 +234,14 @@ extern "C" __global__ __launch_bounds__(256) void kws_ds_load_pack_kernel(const 
 }
 
 // One thread per image word outside the fragment blocks the pack kernel writes: the transposed, interleaved and copied float32
-// sections of build_dscnn_image, gathered from the blob, and zero wherever the host image keeps its initial zero -- the depthwise
+// sections of build_dscnn_image, gathered from the blob, the unit table behind the image, and zero wherever the host image keeps its initial zero -- the depthwise
 // pad floats, the alignment padding, and for more than one input channel c1_w and conv1's fragment blocks.
 extern "C" __global__ __launch_bounds__(256) void kws_ds_load_fill_kernel(const float* __restrict__ blob, DscnnLayout L, uint32_t* __restrict__ img) {
     const size_t w = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (w >= L.total) return;
+    if (w >= L.total) {  // the unit descriptor table behind the image
+        if (w - L.total < DS_UNIT_WORDS) img[w] = ds_unit_word(w - L.total);
+        return;
+    }
     constexpr size_t ZERO = ~(size_t)0;
     const bool one = L.in_channels == 1;
     const size_t cin = (size_t)L.in_channels;
@@ -418,7 +432,9 @@ int kws_load_dscnn_ex(kws_ctx* c, const float* blob, size_t n_floats, int num_cl
     build_dscnn_image(blob, L, h, mw);
 
     HIP_TRY(c, hipSetDevice(c->device));
-    rc = replace_device_image(c, c->d_model, h.data(), L.total * sizeof(float), "kws_load_dscnn");
+    static_assert(sizeof(float) == sizeof(uint32_t), "image words");
+    if (L.total % 4) return fail(c, KWS_EINVAL, "kws_load_dscnn: image size is not a multiple of 16 bytes");
+    rc = replace_device_image(c, c->d_model, h.data(), ds_alloc_words(L) * sizeof(float), "kws_load_dscnn");
     if (rc) return rc;
     drop_stream_graph(c);  // a captured push holds the old weight pointers by value
     install_dscnn(c, c->d_model, L, mw);
@@ -450,7 +466,7 @@ int kws_load_dscnn_device(kws_ctx* c, const float* d_blob, size_t n_floats, int 
     // the stream has drained: rewrite an image of this size where it lies, else allocate (install_dscnn frees the old one)
     float* d = c->d_model;
     const bool in_place = d && c->ds_image_words == L.total;
-    if (!in_place && hipMalloc(reinterpret_cast<void**>(&d), L.total * sizeof(float)) != hipSuccess)
+    if (!in_place && hipMalloc(reinterpret_cast<void**>(&d), ds_alloc_words(L) * sizeof(float)) != hipSuccess)
         return fail(c, KWS_ENOMEM, std::string(fn) + ": device allocation failed");
     drop_stream_graph(c);  // a captured push holds the old weight pointers and scalars by value
     uint32_t* img = reinterpret_cast<uint32_t*>(d);
@@ -462,7 +478,7 @@ int kws_load_dscnn_device(kws_ctx* c, const float* d_blob, size_t n_floats, int 
     }
     if (e == hipSuccess) {
         ProfScope ps(c, KWS_K_DSCNN_LOAD_FILL);
-        hipLaunchKernelGGL(kws_ds_load_fill_kernel, dim3((unsigned)((L.total + 255) / 256)), dim3(256), 0, s, d_blob, L, img);
+        hipLaunchKernelGGL(kws_ds_load_fill_kernel, dim3((unsigned)((ds_alloc_words(L) + 255) / 256)), dim3(256), 0, s, d_blob, L, img);
         e = hipGetLastError();
     }
     if (e != hipSuccess) {  // no mixed image is served: the context's own image may be half rewritten, a fresh one is dropped
@@ -562,6 +578,17 @@ int kws_host_dscnn_image(const float* blob, size_t n_floats, int num_classes, in
     if (scalars) dscnn_scalars_out(mw, scalars);
     return KWS_OK;
     KWS_GUARD_END(nullptr, "kws_host_dscnn_image")
+}
+
+int kws_host_dscnn_units(uint32_t* out_words, size_t cap_words, size_t* need_words, int* unit_base) {
+    KWS_GUARD_BEGIN
+    int rc = export_room(DS_UNIT_WORDS, out_words, cap_words, need_words);
+    if (unit_base)
+        for (int n = 0; n <= 4; ++n) unit_base[n] = ds_unit_base(n);
+    if (rc || !out_words) return rc;
+    for (size_t i = 0; i < DS_UNIT_WORDS; ++i) out_words[i] = ds_unit_word(i);
+    return KWS_OK;
+    KWS_GUARD_END(nullptr, "kws_host_dscnn_units")
 }
 
 int kws_host_cnn_trad_image(const float* blob, size_t n_floats, int num_classes, uint32_t* out_words, size_t cap_words,

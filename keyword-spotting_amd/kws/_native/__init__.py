@@ -162,6 +162,7 @@ SIGNATURES = {
                                        C.POINTER(C.c_size_t), C.POINTER(C.c_float)]),
     "kws_host_cnn_trad_image": (C.c_int, [C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_uint32), C.c_size_t,
                                           C.POINTER(C.c_size_t), C.POINTER(C.c_float)]),
+    "kws_host_dscnn_units": (C.c_int, [C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "kws_host_scan_shape": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "kws_host_ragged_plan": (C.c_int, [_h_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _h_i32p, _h_i32p, _h_i32p, _h_i32p,
                                        C.POINTER(C.c_int)]),
@@ -1010,6 +1011,21 @@ def host_dscnn_image(blob: np.ndarray, num_classes: int, input_channels: int = 1
     """(words uint32, scalars float32[23]): the device image ``Context.load_dscnn`` uploads for this blob and the values the context
     keeps by value -- k_c1, k_pw[4], c1_abs, c1_bmax, dw_abs[4], dw_bmax[4], pw_abs[4], pw_bmax[4] (``kws_host_dscnn_image``)."""
     return _host_image(lib().kws_host_dscnn_image, 23, blob, int(num_classes), int(input_channels))
+
+
+def host_dscnn_units():
+    """(words uint32 [units, 2, 64, 4], unit_base int32[5]): the unit descriptor table a DS-CNN load places behind the device image
+    for the persistent batched forward, and the first unit of blocks 1..4 followed by the unit count (``kws_host_dscnn_units``)."""
+    need, base = C.c_size_t(0), np.zeros(5, np.int32)
+    bp = base.ctypes.data_as(C.POINTER(C.c_int))
+    rc = lib().kws_host_dscnn_units(None, 0, C.byref(need), bp)
+    if rc != KWS_OK:
+        raise KWSError(f"kws_host_dscnn_units failed ({rc})")
+    words = np.empty(need.value, np.uint32)
+    rc = lib().kws_host_dscnn_units(words.ctypes.data_as(C.POINTER(C.c_uint32)), words.size, None, bp)
+    if rc != KWS_OK:
+        raise KWSError(f"kws_host_dscnn_units failed ({rc})")
+    return words.reshape(-1, 2, 64, 4), base
 
 
 def host_cnn_trad_image(blob: np.ndarray, num_classes: int):
