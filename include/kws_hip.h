@@ -333,7 +333,14 @@ int kws_stream_cluster(kws_ctx* ctx, int workgroups_per_stream);
  * host memory.  kws_stream_wait_host spins on that flag (falling back to the stream after ~2 ms) and returns the host
  * arrays (owned by the context, overwritten by the next push): the caller has the results in hand without a
  * hipStreamSynchronize round trip and without a device-to-host copy.  d_logits / d_label of kws_stream_push_i16 are still
- * written.  Call after kws_stream_open and kws_load_dscnn; kws_stream_open / kws_stream_close / enable == 0 release it. */
+ * written.  Call after kws_stream_open and kws_load_dscnn; kws_stream_open / kws_stream_close / enable == 0 release it.
+ *   The arrays hold n_streams x C floats for the C LOADED AT THIS CALL, and kws_load_dscnn / kws_load_dscnn_device leave them
+ *   alone.  After a load with another class count they are stale: kws_stream_push_i16 still takes the hop and writes the caller's
+ *   d_logits / d_label (sized by the caller for the new C), delivers NOTHING to the host arrays, and kws_stream_wait_host returns
+ *   KWS_ESTATE with a message that names the class-count change until kws_stream_host_results(ctx, 1) is called again.
+ *   kws_stream_push_host_i16 and kws_stream_push_host_rate_i16 own their outputs, so they make the arrays again by themselves
+ *   (one stream synchronise, as this call) and deliver the new model's results; the hop counter runs on.  No entry hands a
+ *   kernel an output array made for another class count. */
 int kws_stream_host_results(kws_ctx* ctx, int enable);
 int kws_stream_wait_host(kws_ctx* ctx, const float** h_logits, const int32_t** h_label);
 /* The whole hop from host memory to host memory in one call: h_hop int16 [n_streams, frame_step] (pageable is fine) is copied

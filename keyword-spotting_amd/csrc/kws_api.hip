@@ -368,6 +368,10 @@ int kws_stream_host_results(kws_ctx* c, int enable) {
 int kws_stream_wait_host(kws_ctx* c, const float** h_logits, const int32_t** h_label) {
     if (!c) return KWS_EINVAL;
     if (!c->h_stream_flag) return fail(c, KWS_ESTATE, "kws_stream_wait_host: call kws_stream_host_results(ctx, 1) first");
+    // the pinned arrays hold the class count loaded when they were made: a push under another model delivered nothing to them
+    if (c->host_results_classes != c->mw.num_classes)
+        return fail(c, KWS_ESTATE, "kws_stream_wait_host: the class count changed (" + std::to_string(c->host_results_classes) + " -> " +
+                                       std::to_string(c->mw.num_classes) + ") since kws_stream_host_results; call it again, or push with kws_stream_push_host_i16");
     // spin on the flag the last workgroup of the newest push raises; bounded: after ~2 ms without it, fall back to the stream
     if (c->host_push != c->pushes_enqueued)
         return fail(c, KWS_ESTATE, "kws_stream_wait_host: the newest push did not deliver to host memory (it asked for no logits, or took a multi-launch route)");
@@ -388,10 +392,7 @@ int kws_stream_push_host_i16(kws_ctx* c, const int16_t* h_hop, const float** h_l
     if (!c) return KWS_EINVAL;
     if (!c->n_streams) return fail(c, KWS_ESTATE, "kws_stream_push_host_i16: call kws_stream_open first");
     if (!h_hop) return fail(c, KWS_EINVAL, "kws_stream_push_host_i16: h_hop is NULL");
-    if (!c->h_stream_flag) {
-        int rc = kws_stream_host_results(c, 1);
-        if (rc) return rc;
-    }
+    if (int rc = host_results_ensure(c)) return rc;
     // the hop goes into pinned, device-mapped memory and the kernel reads it from there (one PCIe read of 320 bytes per stream
     // on the frame wavefront's path) -- no H2D submission in front of the launch.  One slot: this call returns after the
     // kernel's last workgroup has raised the flag, i.e. after every read of it.

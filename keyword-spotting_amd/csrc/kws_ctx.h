@@ -171,6 +171,13 @@ inline int fail(kws_ctx* c, int code, const std::string& msg) {
 inline int fail_hip(kws_ctx* c, hipError_t e, const char* what) {
     return fail(c, KWS_EHIP, std::string(what) + ": " + hipGetErrorString(e));
 }
+// The zero-copy arrays of kws_stream_host_results (c->d_hr_logits among them) hold n_streams x the class count loaded when they
+// were made, and neither DS-CNN loader retires them.  The host pushes call this before they hand c->d_hr_logits to a kernel:
+// the arrays are made when absent and made again when the loaded model has another class count.
+inline int host_results_ensure(kws_ctx* c) {
+    if (c->h_stream_flag && c->host_results_classes == c->mw.num_classes) return KWS_OK;
+    return kws_stream_host_results(c, 1);
+}
 inline int check_batch(kws_ctx* c, const void* in, int B, const char* fn) {
     if (!c) return KWS_EINVAL;
     if (!in) return fail(c, KWS_EINVAL, std::string(fn) + ": input pointer is NULL");

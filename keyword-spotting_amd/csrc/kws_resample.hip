@@ -725,10 +725,8 @@ int kws_stream_push_host_rate_i16(kws_ctx* c, const int16_t* h_in, int n_in, con
     int rc = stream_push_rate_check(c, h_in, n_in, "kws_stream_push_host_rate_i16");
     if (rc) return rc;
     StreamResample* st = c->stream_resample;
-    if (!c->h_stream_flag) {
-        rc = kws_stream_host_results(c, 1);
-        if (rc) return rc;
-    }
+    rc = host_results_ensure(c);
+    if (rc) return rc;
     if (!st->h_in) {
         HIP_TRY(c, hipSetDevice(c->device));
         if (hipHostMalloc(reinterpret_cast<void**>(&st->h_in), sizeof(int16_t) * (size_t)st->n_streams * st->max_in,

@@ -764,10 +764,11 @@ class Context:
         return self._host_views_of(pl, py, n_streams)
 
     def _host_views_of(self, pl, py, n_streams):
-        if getattr(self, "_host_views", None) is None or self._host_views[0] != (pl.value, py.value, n_streams):
+        key = (pl.value, py.value, n_streams, self.num_classes)  # a reload with another class count may get the old addresses back
+        if getattr(self, "_host_views", None) is None or self._host_views[0] != key:
             lg = np.ctypeslib.as_array(C.cast(pl, C.POINTER(C.c_float)), shape=(n_streams, self.num_classes))
             lb = np.ctypeslib.as_array(C.cast(py, C.POINTER(C.c_int32)), shape=(n_streams,))
-            self._host_views = ((pl.value, py.value, n_streams), lg, lb)
+            self._host_views = (key, lg, lb)
         return self._host_views[1], self._host_views[2]
 
     def stream_close(self):
