@@ -260,6 +260,9 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
     uintx4 c1p[PERSIST ? 7 : 1][NP];
     int prev_clip = -1;         // PERSIST: the clip whose pool + fc is still to run (on wavefront NW - 1)
     float* a_prev = nullptr;    // its pooled-means slot in the activation dump (diagnostics)
+    // the arrival counter of the K-split leftover tiles: zeroed once per workgroup (conv1's barrier, at the latest, lies between
+    // this store and block 1); whoever combines a tile leaves it at zero again (leftover_arrive)
+    if ((MODE == 4 || MODE == 5) && !CLUSTER && tid_k == 0) lds[OFF_ARRIVE] = 0.f;
     if constexpr (PERSIST) {
         fetch_block_tables(w_arg, 1, tid_k, t1p);
         if (wv_k < STAGE_WAVES) stage_features_persist<PAIR, SCAN>(lds, feat, clip, tid_k, sp.scan);
@@ -468,7 +471,6 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
     __syncthreads();
     stamp();  // 3: conv1 barrier
     float* a = act ? act + (size_t)clip * KWS_ACT_FLOATS_PER_CLIP : nullptr;
-    constexpr bool KSL_ON = (MODE == 4 || MODE == 5) && !CLUSTER;  // the leftover tiles of blocks 1 / 2 are K-split
     // PAIR: the planes hold activations * 2^sg[n]; the dumps (diagnostics) go out in true units
     if (a) {
         const float u = PAIR ? pow2f(-sg[0]) : 1.f;
@@ -499,11 +501,7 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
     block_phase<1, MODE, CLUSTER, UT>(w1, lds, tid, wa, ud, nullptr, rg1, pc);
     stamp();  // 4: block 1 units of wave 0 done
     const DscnnWeights w2 = weights_now();
-    __syncthreads();
-    if constexpr (Leftover<1>::HAS && KSL_ON) {
-        leftover_combine<1, PAIR>(lds, tid);
-        __syncthreads();
-    }
+    __syncthreads();  // (the K-split leftover tile was combined ahead of it: leftover_arrive)
     stamp();  // 5: block 1 barrier
     if (a) {
         const float u = PAIR ? pow2f(-sg[1]) : 1.f;
@@ -513,7 +511,7 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
     }
     if constexpr (PAIR) {
         // block 2 reads block 1's interior and its ring (relu(bias) <= pw_bmax)
-        const float mz = fmaxf(read_stage_max(lds, 2, (Leftover<1>::HAS && KSL_ON) ? 2 : 1) * pow2f(-sg[1]), w2.pw_bmax[0]);
+        const float mz = fmaxf(read_stage_max(lds, 2, 1) * pow2f(-sg[1]), w2.pw_bmax[0]);
         const float bz = (w2.pw_abs[1] * ((w2.dw_abs[1] * mz + w2.dw_bmax[1]) * 1.001f) + w2.pw_bmax[1]) * 1.001f;
         const float by = (w2.dw_abs[2] * bz + w2.dw_bmax[2]) * 1.001f;
         ky[3] = pow2_exp_for(by);
@@ -526,10 +524,6 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
     stamp();  // 6
     const DscnnWeights w3 = weights_now();
     __syncthreads();
-    if constexpr (Leftover<2>::HAS && KSL_ON) {
-        leftover_combine<2, PAIR>(lds, tid);
-        __syncthreads();
-    }
     stamp();  // 7
     if (a) {
         const float u = PAIR ? pow2f(-sg[2]) : 1.f;
@@ -538,7 +532,7 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
         a += CH * Blk<2>::POUT;
     }
     if constexpr (PAIR) {
-        const float mz = fmaxf(read_stage_max(lds, 0, (Leftover<2>::HAS && KSL_ON) ? 2 : 1) * pow2f(-sg[2]), w3.pw_bmax[1]);
+        const float mz = fmaxf(read_stage_max(lds, 0, 1) * pow2f(-sg[2]), w3.pw_bmax[1]);
         const float bz = (w3.pw_abs[2] * ((w3.dw_abs[2] * mz + w3.dw_bmax[2]) * 1.001f) + w3.pw_bmax[2]) * 1.001f;
         const float by = (w3.dw_abs[3] * bz + w3.dw_bmax[3]) * 1.001f;
         ky[4] = pow2_exp_for(by);

@@ -28,11 +28,13 @@ constexpr int OFF_DWTAB = 38784;                 // [2][64][12]  double-buffered
 constexpr int OFF_PWB = OFF_DWTAB + 2 * 768;     // [2][64]      pointwise bias, double-buffered
 constexpr int OFF_POOLED = OFF_PWB + 2 * 64;     // [64]
 constexpr int OFF_POOLBUF = OFF_DWTAB;           // [NW][64] aliases depthwise buffer 0 (idle during block 4)
-constexpr int OFF_WMAX = OFF_POOLED + 64 + 8;    // [4][NW] f16-pair arithmetic: per-wavefront maxima of a stage's stored output.  Sets: features 0,
-                                                 // conv1 1, block 1 2 (+ its leftover combine 3), block 2 0 (+ combine 1): a set is
-                                                 // rewritten two barriers after its last reader at the earliest
+constexpr int OFF_WMAX = OFF_POOLED + 64 + 8;    // [3][NW] f16-pair arithmetic: per-wavefront maxima of a stage's stored output.  Sets: features 0,
+                                                 // conv1 1, block 1 2, block 2 0 (a leftover tile's maximum is folded into the slot of the
+                                                 // wavefront that combined it): a set is rewritten two barriers after its last reader at the earliest
+constexpr int OFF_ARRIVE = OFF_WMAX + 3 * NW;    // one dword: how many quarter wavefronts of the running block's K-split leftover tile have
+                                                 // stored their partial sums (leftover_arrive); zero outside blocks 1 and 2
 constexpr int LDS_FLOATS = 40960;                // 160 KiB
-static_assert(OFF_WMAX + 4 * NW <= LDS_FLOATS, "LDS overflow");
+static_assert(OFF_ARRIVE + 1 <= LDS_FLOATS, "LDS overflow");
 static_assert(NW * 64 <= 768, "pool scratch must fit one depthwise buffer");
 static_assert(OFF_FEAT + FEAT_H * FEAT_W <= OFF_Z2, "feature pad overlaps Z2");
 static_assert(CH * 12 <= 2 * NT, "table staging assumes at most two elements per thread");
@@ -60,10 +62,10 @@ struct Blk {
 // Leftover tiles (round 3).  Block 1 has 5 tiles and block 2 has 9 for 8 wavefronts: the fifth / ninth tile costs a whole
 // extra unit on one wavefront while others idle (block 2: 12.5 k cycles for 9 tiles, block 3: 13 k for 12).  With
 // KWS_DSCNN_KSPLIT_LEFTOVER that tile is cut along K instead: four wavefronts take one k-block (16 input channels, 8 steps)
-// each, write their 64 x positions partial sums to a dead region of LDS, and after the block's barrier all threads add the
-// four partials in a fixed order, add the bias, apply ReLU and store (leftover_combine; one more barrier).  Block 1: tiles
-// 0-3 on wavefronts 0-3, the leftover on 4-7 (one per SIMD); block 2: tiles 0-7 on all eight, the leftover as a second,
-// quarter-size unit of the older wavefronts 0-3.
+// each and write their 64 x positions partial sums to a dead region of LDS; the one of the four that stores its partials last
+// (an arrival counter at OFF_ARRIVE, nobody waits) adds the four partials in a fixed order, adds the bias, applies ReLU and
+// stores, ahead of the block's one barrier (leftover_arrive).  Block 1: tiles 0-3 on wavefronts 0-3, the leftover on 4-7 (one
+// per SIMD); block 2: tiles 0-7 on all eight, the leftover as a second, quarter-size unit of the older wavefronts 0-3.
 #ifndef KWS_DSCNN_KSPLIT_LEFTOVER
 #define KWS_DSCNN_KSPLIT_LEFTOVER 1
 #endif
@@ -74,10 +76,14 @@ struct Leftover {
     static constexpr int P0T = TILE * TW;                           // its first position
     static constexpr int NP = HAS ? Blk<N>::POUT - P0T : 1;         // its positions: 21 (block 1), 5 (block 2)
     static constexpr int WAVE0 = N == 1 ? 4 : 0;                    // wavefronts WAVE0 .. WAVE0 + 3 take k-blocks 0 .. 3
-    static constexpr int OFF_PART = N == 1 ? OFF_Z2 : OFF_Z0;       // [4][64][NP] partial sums, in a plane that is dead during block N
+    static constexpr int OFF_PART = N == 1 ? OFF_Z2 : OFF_Z0;       // [4][NP][CSTRIDE] partial sums, in a plane that is dead during block N
+    static constexpr int CSTRIDE = CH + 4;                          // floats per position: the 64 channels as float4s, padded so that the
+                                                                    // 16-byte stores of neighbouring columns fall into different banks
+    static constexpr int PART = NP * CSTRIDE;                       // floats per k-block
 };
 static_assert(Blk<1>::TILES == 5 && Blk<2>::TILES == 9, "the leftover tiles are the fifth of block 1 and the ninth of block 2");
-static_assert(4 * CH * Leftover<1>::NP <= 38784 - OFF_Z2 && OFF_Z0 + 4 * CH * Leftover<2>::NP <= OFF_FEAT, "partial sums fit their dead planes");
+static_assert(4 * Leftover<1>::PART <= 38784 - OFF_Z2 && OFF_Z0 + 4 * Leftover<2>::PART <= OFF_FEAT, "partial sums fit their dead planes");
+static_assert(Leftover<1>::OFF_PART % 4 == 0 && Leftover<2>::OFF_PART % 4 == 0 && Leftover<1>::CSTRIDE % 4 == 0, "partial sums move as float4s");
 
 // Persistent batched launch (PERSIST, kws_dscnn_fwd_kernel): a workgroup carries clips g, g + grid, ... one after another and
 // the next clip is staged in block 4's tail.  Block 4 reads only Z3 and the odd table buffer, so the Z2 plane is dead from

@@ -546,7 +546,7 @@ __device__ __forceinline__ void conv1_phase_split(const DscnnWeights& w, float* 
 // ------------------------------------------------------------------------------------------------
 // A quarter of the leftover tile of block N (see Leftover): k-block M (input channels 16M .. 16M+15) of tile Leftover<N>::TILE
 // for both output-channel tiles.  Eight stencil steps, one split, twelve MFMAs, the raw partial sums (no bias, no ReLU) of the
-// tile's valid columns to part[M][cout][position in tile].  af: the pre-split weights of k-block M (requested long before).
+// tile's valid columns to part[M][position in tile][cout] (Leftover<N>::CSTRIDE floats per position).  af: the pre-split weights of k-block M (requested long before).
 // UT: the tile's geometry from its unit descriptor ud (else ud is not read).
 template <int N, int NP, bool UT = false>
 __device__ __forceinline__ void leftover_partial_unit(float* lds, int lane, int M, const uintx4 (&af)[2][NP], const UnitDesc& ud) {
@@ -614,33 +614,71 @@ __device__ __forceinline__ void leftover_partial_unit(float* lds, int lane, int 
             acc1 = mfma_bf16(af[1][pa], b, acc1);
         }
     }
-    float* part = lds + L::OFF_PART + M * (CH * L::NP);
+    // accumulator registers 4q .. 4q+3 are output channels 8q + 4 * half + (0..3) (row_of): one 16-byte store each
     if (valid) {  // (plain stores of the accumulators: the compiler waits out the matrix-core write itself)
+        float4* part4 = reinterpret_cast<float4*>(lds + L::OFF_PART + M * L::PART + (col - 1) * L::CSTRIDE) + half;  // (valid: 1 <= col <= NP)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            part[row_of(r, half) * L::NP + (col - 1)] = acc0[r];
-            part[(32 + row_of(r, half)) * L::NP + (col - 1)] = acc1[r];
+        for (int q = 0; q < 4; ++q) {
+            part4[2 * q] = make_float4(acc0[4 * q], acc0[4 * q + 1], acc0[4 * q + 2], acc0[4 * q + 3]);
+            part4[8 + 2 * q] = make_float4(acc1[4 * q], acc1[4 * q + 1], acc1[4 * q + 2], acc1[4 * q + 3]);
         }
     }
 }
 
-// After the block's barrier: the leftover tile's output = relu(bias + the four k-block partials, added in a fixed order).
-template <int N, bool PAIR = false>
-__device__ __forceinline__ void leftover_combine(float* lds, int tid) {
+// A quarter wavefront of block N's leftover tile, behind leftover_partial_unit: it counts itself in at OFF_ARRIVE, and the one of
+// the four that counts in last (it reads 3) combines the tile alone, 64 lanes striding over it four channels at a time: output = relu(bias + the four
+// k-block partials, added in a fixed order).  Nobody waits for another wavefront.  The LDS instructions of a wavefront execute in
+// order, so a wavefront's partial stores are done when its count is, and whoever reads 3 reads finished partials.  The waits are
+// on lgkmcnt alone: the requests for the next block's operands, issued by the caller, stay in flight.  The combining wavefront
+// leaves the counter at zero, for block 2 and for the next clip.  Returns the largest value stored (zero on the other three).
+template <int N>
+__device__ __forceinline__ float leftover_arrive(float* lds, int lane) {
     using G = Blk<N>;
     using L = Leftover<N>;
-    const float* part = lds + L::OFF_PART;
-    const float* pwb = lds + OFF_PWB + G::BUF * 64;
-    float* zout = lds + G::OFF_OUT;
+    int* arrived = reinterpret_cast<int*>(lds + OFF_ARRIVE);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wavefront's partial stores
+    int before = 0;
+    if (lane == 0) before = __hip_atomic_fetch_add(arrived, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    before = __builtin_amdgcn_readfirstlane(before);
+    asm volatile("" ::: "memory");  // (no partial is read ahead of the count)
     float mx = 0.f;
-    for (int i = tid; i < CH * L::NP; i += NT) {
-        const int co = i / L::NP, j = i - co * L::NP;
-        const float s = (part[i] + part[CH * L::NP + i]) + (part[2 * CH * L::NP + i] + part[3 * CH * L::NP + i]);
-        const float v = relu(s + pwb[co]);
-        zout[pidx(co, L::P0T + j, G::SOUT)] = v;
-        mx = fmaxf(mx, v);
+    if (before == 3) {
+        // An item is four consecutive output channels of one position: four 16-byte reads (one per k-block), two 8-byte stores
+        // (the planes are interleaved in channel pairs).  Lane l takes the channels 4 (l & 15) .. + 3 of position (l >> 4) + 4 r
+        // in round r; RB rounds' reads are in flight before the first of their stores.
+        const float4* part4 = reinterpret_cast<const float4*>(lds + L::OFF_PART);
+        float* zout = lds + G::OFF_OUT;
+        const int cq = lane & 15;
+        const float4 b = reinterpret_cast<const float4*>(lds + OFF_PWB + G::BUF * 64)[cq];  // (pwb is stored in the accumulators' units)
+        constexpr int ROUNDS = (L::NP + 3) / 4, RB = 2;
+        static_assert(ROUNDS % RB == 0, "whole batches");
+        auto comb = [&](float p0, float p1, float p2, float p3, float bias) { return relu(((p0 + p1) + (p2 + p3)) + bias); };
+#pragma unroll 1
+        for (int r0 = 0; r0 < ROUNDS; r0 += RB) {
+            float4 p[RB][4];
+#pragma unroll
+            for (int r = 0; r < RB; ++r) {
+                const int j = (lane >> 4) + 4 * (r0 + r);
+                const int jc = j < L::NP ? j : L::NP - 1;  // (a lane past the tile reads its last position and stores nothing)
+#pragma unroll
+                for (int m = 0; m < 4; ++m) p[r][m] = part4[(m * L::PART + jc * L::CSTRIDE) / 4 + cq];
+            }
+#pragma unroll
+            for (int r = 0; r < RB; ++r) {
+                const int j = (lane >> 4) + 4 * (r0 + r);
+                const float4(&q)[4] = p[r];
+                const float v0 = comb(q[0].x, q[1].x, q[2].x, q[3].x, b.x), v1 = comb(q[0].y, q[1].y, q[2].y, q[3].y, b.y);
+                const float v2 = comb(q[0].z, q[1].z, q[2].z, q[3].z, b.z), v3 = comb(q[0].w, q[1].w, q[2].w, q[3].w, b.w);
+                if (j < L::NP) {
+                    *reinterpret_cast<float2*>(zout + pidx(4 * cq, L::P0T + j, G::SOUT)) = make_float2(v0, v1);
+                    *reinterpret_cast<float2*>(zout + pidx(4 * cq + 2, L::P0T + j, G::SOUT)) = make_float2(v2, v3);
+                    mx = fmaxf(mx, fmaxf(fmaxf(v0, v1), fmaxf(v2, v3)));
+                }
+            }
+        }
+        if (lane == 0) *arrived = 0;
     }
-    if constexpr (PAIR) publish_wave_max(lds, N == 1 ? 3 : 1, tid >> 6, tid & 63, mx);  // (pwb is stored in the accumulators' units)
+    return mx;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1016,6 +1054,9 @@ __device__ __forceinline__ void block_phase(const DscnnWeights& w, float* lds, i
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (UT) load_unit_desc(w, N + 1, wv, lane, ud);  // (block 2 has a tile for every wavefront, block 3 too)
             load_afrag(w, N + 1, 0, lane, pwo.ring[0]);  // the next block's first operands fly across the barrier
+            __builtin_amdgcn_sched_barrier(0);
+            // the last of the four to get here combines the tile; its maximum joins this wavefront's (a maximum is exact in any order)
+            stage_max = fmaxf(stage_max, leftover_arrive<N>(lds, lane));
         }
     }
     if constexpr (N < 4) store_block_tables(lds, N + 1, tid, next_tables, pc.s_dwb, pc.s_pwb, pc.s_dww);
