@@ -401,6 +401,45 @@ int kws_forward_cnn_trad_debug_f32(kws_ctx* ctx, const float* d_feat, int B, flo
 /* Fused wav -> label for this model (BASELINE.json configs[2]): kws_mfcc_i16 into the context workspace, then
  * kws_forward_cnn_trad_f32, on the context's stream.  Same arguments and errors as kws_infer_i16. */
 int kws_infer_cnn_trad_i16(kws_ctx* ctx, const int16_t* d_wav, int B, float* d_logits, int32_t* d_label);
+/* The float32 twin: kws_mfcc_f32 into the context workspace, then kws_forward_cnn_trad_f32.  Same arguments and errors as
+ * kws_infer_f32; samples of int16 PCM / 32768 give the bits of kws_infer_cnn_trad_i16. */
+int kws_infer_cnn_trad_f32(kws_ctx* ctx, const float* d_wav, int B, float* d_logits, int32_t* d_label);
+
+/* ---- cnn-trad-fpool3 on recordings and streams: windows read in place ----
+ * Windows per launch pair of kws_forward_cnn_trad_windows_f32 (host only): a positive multiple of 16, the clips the dense kernel
+ * takes per workgroup.  The context workspace holds one chunk's convolution output (76 KB per window). */
+int kws_host_cnn_trad_window_chunk(void);
+/* The model over the strided 99-frame windows of R recordings' frame arrays, read where they lie: d_frames float32 [R][F][10]
+ * (kws_frames_i16 / kws_frames_f32 write it), W = (F - 99) / hop_frames + 1 windows per recording, window w of recording r =
+ * rows [w * hop_frames, w * hop_frames + 99) -> d_logits float32 [R][W][C] and d_label int32 [R][W] (may be NULL).  Every window's
+ * result is bit-identical to kws_forward_cnn_trad_f32 on the same 99 rows handed over as a contiguous clip, under either
+ * arithmetic (the f16 pair's scales are per window).  Runs in chunks of kws_host_cnn_trad_window_chunk() windows, one convolution
+ * and one dense launch each, on the context's stream.  Needs a loaded model (kws_load_cnn_trad) and nothing of the front end.
+ * KWS_EINVAL: NULL d_frames / d_logits, R < 1, hop_frames < 1, F < 99.  KWS_ESTATE: no model loaded.  KWS_EUNSUPPORTED: more than
+ * 2^28 frames or 2^30 windows in one call (the limits of kws_scan_i16). */
+int kws_forward_cnn_trad_windows_f32(kws_ctx* ctx, const float* d_frames, int R, int F, int hop_frames, float* d_logits,
+                                     int32_t* d_label);
+/* kws_scan_i16 / kws_scan_f32 for this model: one MFCC pass per recording, then kws_forward_cnn_trad_windows_f32 over the frame
+ * array.  Same arguments, shapes and limits; KWS_ESTATE without a front end or a cnn-trad-fpool3 model, KWS_EUNSUPPORTED for a
+ * front end whose clip is not 99 x 10. */
+int kws_scan_cnn_trad_i16(kws_ctx* ctx, const int16_t* d_pcm, int R, int n_total, int hop_frames, float* d_logits, int32_t* d_label,
+                          float* d_feat_out);
+int kws_scan_cnn_trad_f32(kws_ctx* ctx, const float* d_wav, int R, int n_total, int hop_frames, float* d_logits, int32_t* d_label,
+                          float* d_feat_out);
+/* kws_scan_ragged_i16 / kws_scan_ragged_f32 for this model: the ragged front end, then the packed frame array scanned as ONE
+ * recording.  Same arguments, plan (kws_host_ragged_plan) and limits; the model's errors as for kws_scan_cnn_trad_i16. */
+int kws_scan_ragged_cnn_trad_i16(kws_ctx* ctx, const int16_t* d_pcm, int n_pcm, const int64_t* start, const int32_t* len, int R,
+                                 int hop_frames, float* d_logits, int32_t* d_label, float* d_feat_out);
+int kws_scan_ragged_cnn_trad_f32(kws_ctx* ctx, const float* d_wav, int n_wav, const int64_t* start, const int32_t* len, int R,
+                                 int hop_frames, float* d_logits, int32_t* d_label, float* d_feat_out);
+/* kws_stream_push_i16 for this model: d_hop int16 [n_streams][frame_step] -> one new frame per stream in the rings, then every
+ * stream's current window classified from the feature ring in place -> d_logits float32 [n_streams][C] (required) and d_label
+ * int32 [n_streams] (may be NULL).  Three launches on the context's stream (frame, convolution, dense); a context armed with
+ * kws_stream_utt_open / kws_stream_detect_open runs its step behind them, and the detection set's class count must be this
+ * model's.  There is no graph replay, no one-launch push and no zero-copy delivery for this model: read the device arrays
+ * after kws_sync.  KWS_ESTATE: no open stream set or no model loaded; KWS_EINVAL: NULL d_hop / d_logits; KWS_EUNSUPPORTED: a
+ * front end whose clip is not 99 x 10. */
+int kws_stream_push_cnn_trad_i16(kws_ctx* ctx, const int16_t* d_hop, float* d_logits, int32_t* d_label);
 
 /* ---- posteriors (build-defined: the reference's scripts stop at argmax of the logits,
  * kws/libs/training.py:371) ------------------------------------------------------------------------------ */

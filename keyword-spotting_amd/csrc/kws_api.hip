@@ -461,6 +461,15 @@ static int forward_cnn_trad(kws_ctx* c, const float* d_feat, int B, float* d_log
     return KWS_OK;
 }
 
+// cnn-trad-fpool3 behind the recording flows (kws_scan_cnn_trad_*, kws_scan_ragged_cnn_trad_*; ScanModel, kws_ctx.h)
+static int cnntrad_windows_launch(kws_ctx* c, const std::string& fn, const float* d_frames, int R, int F, int W, int hop_frames,
+                                  float* d_logits, int32_t* d_label);
+static int cnntrad_scan_check(kws_ctx* c, const std::string& f) {
+    if (!c->fe_ready || !c->cnntrad_ready) return fail(c, KWS_ESTATE, f + ": front end or model not configured (kws_load_cnn_trad)");
+    if (c->fp.num_frames != IN_T || c->fp.numcep != IN_F)
+        return fail(c, KWS_EUNSUPPORTED, f + ": the kernels are built for a 99 x 10 feature map");
+    return KWS_OK;
+}
 int kws_forward_cnn_trad_f32(kws_ctx* c, const float* d_feat, int B, float* d_logits, int32_t* d_label) {
     return forward_cnn_trad(c, d_feat, B, d_logits, d_label, "kws_forward_cnn_trad_f32");
 }
@@ -497,6 +506,96 @@ int kws_infer_cnn_trad_i16(kws_ctx* c, const int16_t* d_wav, int B, float* d_log
     rc = kws_mfcc_i16(c, d_wav, B, c->d_feat_ws);
     if (rc) return rc;
     return kws_forward_cnn_trad_f32(c, c->d_feat_ws, B, d_logits, d_label);
+}
+
+int kws_infer_cnn_trad_f32(kws_ctx* c, const float* d_wav, int B, float* d_logits, int32_t* d_label) {
+    int rc = check_batch(c, d_wav, B, "kws_infer_cnn_trad_f32");
+    if (rc) return rc;
+    if (!c->fe_ready || !c->cnntrad_ready)
+        return fail(c, KWS_ESTATE, "kws_infer_cnn_trad_f32: front end or model not configured (kws_load_cnn_trad)");
+    if (c->fp.num_frames != IN_T || c->fp.numcep != IN_F)
+        return fail(c, KWS_EUNSUPPORTED, "kws_infer_cnn_trad_f32: the kernels are built for a 99 x 10 feature map");
+    rc = kws_reserve(c, B);
+    if (rc) return rc;
+    rc = kws_mfcc_f32(c, d_wav, B, c->d_feat_ws);
+    if (rc) return rc;
+    return forward_cnn_trad(c, c->d_feat_ws, B, d_logits, d_label, "kws_infer_cnn_trad_f32");
+}
+
+int kws_host_cnn_trad_window_chunk(void) { return CT_WINDOW_CHUNK; }
+
+// The R * W windows of a frame array [R][F][10], read in place, in chunks of CT_WINDOW_CHUNK: per chunk one conv launch into the
+// context workspace (a chunk's 19008 floats + 1 scale per window) and one dense launch that writes logits and labels at the
+// chunk's offset.  The caller has checked the arguments and the limits (R * F <= 2^28, R * W <= 2^30).
+static int cnntrad_windows_launch(kws_ctx* c, const std::string& fn, const float* d_frames, int R, int F, int W, int hop_frames,
+                                  float* d_logits, int32_t* d_label) {
+    const long long n = (long long)R * W;
+    const int chunk = n < CT_WINDOW_CHUNK ? (int)n : CT_WINDOW_CHUNK;
+    int rc = grow_conv_ws(c, (size_t)chunk * 64 * 297 + (size_t)chunk, fn);
+    if (rc) return rc;
+    const bool pair = c->cnntrad_math == KWS_CT_F16_PAIR;
+    const int C = c->tw.num_classes;
+    for (long long i0 = 0; i0 < n; i0 += chunk) {
+        const int nb = n - i0 < chunk ? (int)(n - i0) : chunk;
+        const CtWindows sw = {(unsigned)i0, (unsigned)W, (unsigned)F * (unsigned)IN_F, (unsigned)hop_frames * (unsigned)IN_F};
+        {
+            ProfScope ps(c, KWS_K_CNNTRAD_CONV);
+            HIP_TRY(c, launch_cnntrad_conv_windows(c->stream, c->tw, d_frames, sw, nb, c->d_conv_ws, pair));
+        }
+        {
+            ProfScope ps(c, KWS_K_CNNTRAD_DENSE);
+            HIP_TRY(c, launch_cnntrad_dense(c->stream, c->tw, c->d_conv_ws, nb, d_logits + (size_t)i0 * C, d_label ? d_label + i0 : nullptr, pair));
+        }
+    }
+    return KWS_OK;
+}
+
+int kws_forward_cnn_trad_windows_f32(kws_ctx* c, const float* d_frames, int R, int F, int hop_frames, float* d_logits, int32_t* d_label) {
+    const std::string fn = "kws_forward_cnn_trad_windows_f32";
+    if (!c) return KWS_EINVAL;
+    if (!d_frames || !d_logits) return fail(c, KWS_EINVAL, fn + ": d_frames / d_logits is NULL");
+    if (R < 1 || hop_frames < 1) return fail(c, KWS_EINVAL, fn + ": R and hop_frames must be positive");
+    if (F < IN_T) return fail(c, KWS_EINVAL, fn + ": a recording of fewer than 99 frames has no window");
+    if (!c->cnntrad_ready) return fail(c, KWS_ESTATE, fn + ": no model loaded (kws_load_cnn_trad)");
+    const int W = (F - IN_T) / hop_frames + 1;
+    if ((unsigned long long)R * F > (1ull << 28) || (unsigned long long)R * W > (1ull << 30))
+        return fail(c, KWS_EUNSUPPORTED, fn + ": more than 2^28 frames or 2^30 windows in one call");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return cnntrad_windows_launch(c, fn, d_frames, R, F, W, hop_frames, d_logits, d_label);
+}
+
+// The push of a cnn-trad-fpool3 context: the frame kernel advances the rings and the hop counter, the conv kernel reads every
+// stream's window from the feature ring in place (RING), the dense kernel writes logits and labels.  Three launches, no graph,
+// no zero-copy delivery; the armed steps run behind them as behind kws_stream_push_i16.
+int kws_stream_push_cnn_trad_i16(kws_ctx* c, const int16_t* d_hop, float* d_logits, int32_t* d_label) {
+    const char* fn = "kws_stream_push_cnn_trad_i16";
+    if (!c) return KWS_EINVAL;
+    if (!c->n_streams) return fail(c, KWS_ESTATE, std::string(fn) + ": call kws_stream_open first");
+    if (!d_hop || !d_logits) return fail(c, KWS_EINVAL, std::string(fn) + ": d_hop / d_logits is NULL");
+    if (!c->cnntrad_ready) return fail(c, KWS_ESTATE, std::string(fn) + ": no model loaded (kws_load_cnn_trad)");
+    if (c->fp.num_frames != IN_T || c->fp.numcep != IN_F)
+        return fail(c, KWS_EUNSUPPORTED, std::string(fn) + ": the kernels are built for a 99 x 10 feature map");
+    if (int rc = stream_utt_push_check(c, fn)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int S = c->n_streams;
+    if (int rc = grow_conv_ws(c, (size_t)S * 64 * 297 + (size_t)S, fn)) return rc;
+    const bool pair = c->cnntrad_math == KWS_CT_F16_PAIR;
+    c->last_push_host = false;
+    {
+        ProfScope ps(c, KWS_K_STREAM_FRAME);
+        HIP_TRY(c, launch_stream_frame(c->stream, c->fp, c->ft, d_hop, S, c->d_pcm_ring, c->ring_len, c->d_feat_ring, c->d_hops, c->d_refine));
+    }
+    {
+        ProfScope ps(c, KWS_K_CNNTRAD_CONV);
+        HIP_TRY(c, launch_cnntrad_conv_ring(c->stream, c->tw, c->d_feat_ring, c->d_hops, frames_lag(c->fp), S, c->d_conv_ws, pair));
+    }
+    {
+        ProfScope ps(c, KWS_K_CNNTRAD_DENSE);
+        HIP_TRY(c, launch_cnntrad_dense(c->stream, c->tw, c->d_conv_ws, S, d_logits, d_label, pair));
+    }
+    c->pushes_enqueued += 1;
+    if (int rc = stream_utt_pushed(c)) return rc;
+    return stream_detect_pushed(c, d_logits, fn, c->tw.num_classes);
 }
 
 int kws_stream_close(kws_ctx* c) {
@@ -586,13 +685,13 @@ int kws_stream_push_i16(kws_ctx* c, const int16_t* d_hop, float* d_logits, int32
         HIP_TRY(c, hipGraphLaunch(c->stream_graph, c->stream));
         c->pushes_enqueued += 1;
         if (int rc = stream_utt_pushed(c)) return rc;  // armed: the step kernel, behind the replay and outside the graph
-        return stream_detect_pushed(c, d_logits);      // ... and the decision step (kws_live_detect.hip), likewise
+        return stream_detect_pushed(c, d_logits, "kws_stream_push_i16", c->mw.num_classes);  // ... and the decision step (kws_live_detect.hip), likewise
     }
     HIP_TRY(c, stream_enqueue(c, d_hop, d_logits, d_label, true));
     c->pushes_enqueued += 1;
     if (c->last_push_host) c->host_push = c->pushes_enqueued;
     if (int rc = stream_utt_pushed(c)) return rc;
-    return stream_detect_pushed(c, d_logits);
+    return stream_detect_pushed(c, d_logits, "kws_stream_push_i16", c->mw.num_classes);
 }
 
 int kws_stream_state(kws_ctx* c, const float** d_feat_ring, int* hops) {
@@ -662,3 +761,7 @@ int kws_prof_read(kws_ctx* c, int kernel_id, double* total_ms, int* launches) {
 
 }  // extern "C"
 #pragma GCC visibility pop
+
+namespace kws {
+ScanModel scan_model_cnn_trad() { return {cnntrad_scan_check, cnntrad_windows_launch}; }
+}  // namespace kws

@@ -23,7 +23,19 @@ int stream_utt_push_check(kws_ctx* c, const char* fn);  // a push is refused onc
 int stream_utt_pushed(kws_ctx* c);                      // the step behind a push's launches; nothing when the context is unarmed
 struct StreamDetect;            // live keyword events: posterior ring, refractory state, event queue and its host mirror (kws_live_detect.hip)
 void stream_detect_free(kws_ctx* c);
-int stream_detect_pushed(kws_ctx* c, const float* d_logits);  // the decision step behind a push, from that push's logits; nothing when unarmed
+// the decision step behind a push, from that push's logits; nothing when unarmed.  fn: the push entry, named in the errors;
+// model_classes: the class count of the model that made the logits (the DS-CNN's or cnn-trad-fpool3's)
+int stream_detect_pushed(kws_ctx* c, const float* d_logits, const char* fn, int model_classes);
+// What the recording flows (scan_recordings, kws_scan.hip; scan_ragged_entry, kws_ragged.hip) need of a model: its readiness and
+// geometry checks in the entry's words (f names the entry), and the launch over the R * W strided 99-frame windows of a frame
+// array [R][F][10] -- logits [R * W][C] and labels [R * W] (or NULL) in window order.
+struct ScanModel {
+    int (*check)(kws_ctx* c, const std::string& f);
+    int (*launch)(kws_ctx* c, const std::string& f, const float* d_frames, int R, int F, int W, int hop_frames, float* d_logits,
+                  int32_t* d_label);
+};
+ScanModel scan_model_dscnn();     // kws_scan.hip: kws_dscnn_fwd_kernel, SCAN
+ScanModel scan_model_cnn_trad();  // kws_api.hip: kws_cnntrad_conv_windows_kernel + the dense kernel, in chunks
 }  // namespace kws
 
 using kws::FrontendParams; using kws::FrontendTables; using kws::DscnnWeights; using kws::CnnTradWeights; using kws::NFFT;

@@ -302,6 +302,21 @@ hipError_t cnntrad_init_device();
 hipError_t launch_cnntrad_conv(hipStream_t s, const CnnTradWeights& w, const float* d_feat, int B, float* d_conv_ws, bool f16_pair);
 hipError_t launch_cnntrad_dense(hipStream_t s, const CnnTradWeights& w, const float* d_conv_ws, int B, float* d_logits,
                                 int32_t* d_label, bool f16_pair);
+// Windows of recordings read in place (kws_cnntrad_conv_windows_kernel): window i of the call is window i % wpr of recording
+// i / wpr, 99 consecutive rows of the recording's [F][10] frame array from row (i % wpr) * hop_frames on.  A launch takes the n
+// windows from `first` on and writes workspace slots 0 .. n - 1, which the dense launch reads as n clips.
+struct CtWindows {
+    unsigned first;        // the chunk's first window
+    unsigned wpr;          // windows per recording
+    unsigned row_floats;   // one recording's frames: F * 10
+    unsigned win_floats;   // from one window to the next: hop_frames * 10
+};
+constexpr int CT_WINDOW_CHUNK = 4096;  // windows per launch pair: the workspace of kws_forward_cnn_trad_f32 at the bench batch (311 MB)
+hipError_t launch_cnntrad_conv_windows(hipStream_t s, const CnnTradWeights& w, const float* d_frames, const CtWindows& sw, int n,
+                                       float* d_conv_ws, bool f16_pair);
+// The streaming push's conv launch: stream s's window is the ring's 99 rows from ((*d_hops + 1 - frames_lag) mod 99 + 99) mod 99 on.
+hipError_t launch_cnntrad_conv_ring(hipStream_t s, const CnnTradWeights& w, const float* d_feat_ring, const int* d_hops, int frames_lag,
+                                    int S, float* d_conv_ws, bool f16_pair);
 
 // Standalone depthwise-separable block on an arbitrary [B, C_in, H, W] map (kws_dsblock.hip); d_ws: B*C_in*Ho*Wo floats.
 hipError_t launch_dsblock(hipStream_t s, const float* d_x, int B, int C_in, int H, int W, const float* d_dw_w, const float* d_dw_b,

@@ -148,15 +148,16 @@ void stream_detect_free(kws_ctx* c) {
 }
 
 // The push entry's side (kws_api.hip): the step behind a push's launches, from that push's logits.
-int stream_detect_pushed(kws_ctx* c, const float* d_logits) {
+int stream_detect_pushed(kws_ctx* c, const float* d_logits, const char* fn, int model_classes) {
     StreamDetect* u = c->stream_detect;
     if (!u) return KWS_OK;
+    const std::string f(fn);
     if (!d_logits)
-        return fail(c, KWS_ESTATE, "kws_stream_push_i16: the context is armed for detection (kws_stream_detect_open) and this push asked for no logits; its hop was taken, no decision was made");
+        return fail(c, KWS_ESTATE, f + ": the context is armed for detection (kws_stream_detect_open) and this push asked for no logits; its hop was taken, no decision was made");
     if (u->mode == 2)
-        return fail(c, KWS_ESTATE, "kws_stream_push_i16: this detection set was stepped by kws_stream_detect_step_f32; its hop was taken, no decision was made");
-    if (u->a.C != c->mw.num_classes)
-        return fail(c, KWS_EINVAL, "kws_stream_push_i16: kws_stream_detect_open was given another class count than the loaded model's; the hop was taken, no decision was made");
+        return fail(c, KWS_ESTATE, f + ": this detection set was stepped by kws_stream_detect_step_f32; its hop was taken, no decision was made");
+    if (u->a.C != model_classes)
+        return fail(c, KWS_EINVAL, f + ": kws_stream_detect_open was given another class count than the loaded model's; the hop was taken, no decision was made");
     u->mode = 1;
     return detect_launch(c, d_logits, c->d_hops);
 }

@@ -91,6 +91,14 @@ SIGNATURES = {
     "kws_forward_cnn_trad_debug_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, _f32p, _i32p, _f32p, _f32p]),
     "kws_set_cnn_trad_math": (C.c_int, [_c_ctx, C.c_int]),
     "kws_infer_cnn_trad_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, _f32p, _i32p]),
+    "kws_infer_cnn_trad_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, _f32p, _i32p]),
+    "kws_host_cnn_trad_window_chunk": (C.c_int, []),
+    "kws_forward_cnn_trad_windows_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _i32p]),
+    "kws_scan_cnn_trad_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, _f32p]),
+    "kws_scan_cnn_trad_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, _f32p]),
+    "kws_scan_ragged_cnn_trad_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, _h_i64p, _h_i32p, C.c_int, C.c_int, _f32p, _i32p, _f32p]),
+    "kws_scan_ragged_cnn_trad_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, _h_i64p, _h_i32p, C.c_int, C.c_int, _f32p, _i32p, _f32p]),
+    "kws_stream_push_cnn_trad_i16": (C.c_int, [_c_ctx, _i16p, _f32p, _i32p]),
     "kws_softmax_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, _f32p]),
     "kws_stream_smooth_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, _f32p, _i32p]),
     "kws_scan_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, _f32p]),
@@ -449,6 +457,51 @@ class Context:
         self._check(self._lib.kws_infer_host_submit_i16(self._h, C.c_void_p(src), B, C.c_void_p(logits.ctypes.data),
                                                         C.c_void_p(label.ctypes.data), C.byref(ticket)), ModelError)
         return logits, label, int(ticket.value), wav
+
+    # -- cnn-trad-fpool3 on recordings and streams ---------------------------------------------------
+    def infer_cnn_trad_f32(self, wav, logits, label=None):
+        """``kws_infer_cnn_trad_f32``: ``infer_cnn_trad_i16`` over ``wav`` float32 [B, n_samples] on the device."""
+        self._check(self._lib.kws_infer_cnn_trad_f32(self._h, _ptr(wav), int(wav.shape[0]), _ptr(logits),
+                                                     _ptr(label) if label is not None else None), ModelError)
+
+    def forward_cnn_trad_windows_f32(self, frames, hop_frames, logits, label=None):
+        """``kws_forward_cnn_trad_windows_f32``: ``frames`` float32 [R, F, 10] on the device -> ``logits`` float32 [R, W, C] (and
+        ``label`` int32 [R, W]) for every window of 99 frames, ``hop_frames`` apart, read in place; W = (F - 99) // hop_frames + 1."""
+        self._check(self._lib.kws_forward_cnn_trad_windows_f32(self._h, _ptr(frames), int(frames.shape[0]), int(frames.shape[1]),
+                                                               int(hop_frames), _ptr(logits), _ptr(label) if label is not None else None),
+                    ModelError)
+
+    def scan_cnn_trad_i16(self, pcm, hop_frames, logits, label=None, feat=None):
+        """``kws_scan_cnn_trad_i16``: ``scan_i16`` with cnn-trad-fpool3 over the windows."""
+        p = lambda t: _ptr(t) if t is not None else None
+        self._check(self._lib.kws_scan_cnn_trad_i16(self._h, _ptr(pcm), int(pcm.shape[0]), int(pcm.shape[1]), int(hop_frames), _ptr(logits),
+                                                    p(label), p(feat)), ModelError)
+
+    def scan_cnn_trad_f32(self, wav, hop_frames, logits, label=None, feat=None):
+        """``kws_scan_cnn_trad_f32``: ``scan_f32`` with cnn-trad-fpool3 over the windows."""
+        p = lambda t: _ptr(t) if t is not None else None
+        self._check(self._lib.kws_scan_cnn_trad_f32(self._h, _ptr(wav), int(wav.shape[0]), int(wav.shape[1]), int(hop_frames), _ptr(logits),
+                                                    p(label), p(feat)), ModelError)
+
+    def scan_ragged_cnn_trad_i16(self, pcm, start, length, hop_frames, logits, label=None, feat=None):
+        """``kws_scan_ragged_cnn_trad_i16``: ``scan_ragged_i16`` with cnn-trad-fpool3 over the packed windows."""
+        p = lambda t: _ptr(t) if t is not None else None
+        st, ln = _host_i64(start), _host_i32(length)
+        self._check(self._lib.kws_scan_ragged_cnn_trad_i16(self._h, _ptr(pcm), int(pcm.numel()), _as(st, C.c_int64), _as(ln, C.c_int32),
+                                                           len(ln), int(hop_frames), _ptr(logits), p(label), p(feat)), ModelError)
+
+    def scan_ragged_cnn_trad_f32(self, wav, start, length, hop_frames, logits, label=None, feat=None):
+        """``kws_scan_ragged_cnn_trad_f32``: ``scan_ragged_f32`` with cnn-trad-fpool3 over the packed windows."""
+        p = lambda t: _ptr(t) if t is not None else None
+        st, ln = _host_i64(start), _host_i32(length)
+        self._check(self._lib.kws_scan_ragged_cnn_trad_f32(self._h, _ptr(wav), int(wav.numel()), _as(st, C.c_int64), _as(ln, C.c_int32),
+                                                           len(ln), int(hop_frames), _ptr(logits), p(label), p(feat)), ModelError)
+
+    def stream_push_cnn_trad_i16(self, hop, logits, label=None):
+        """``kws_stream_push_cnn_trad_i16``: one hop per stream, then cnn-trad-fpool3 over every stream's window of the feature
+        ring; ``logits`` float32 [n_streams, C] is required.  Three launches; read the results after ``sync``."""
+        self._check(self._lib.kws_stream_push_cnn_trad_i16(self._h, _ptr(hop), _ptr(logits), _ptr(label) if label is not None else None),
+                    ModelError)
 
     def ingest_config(self, chunk_clips: int = 0, n_slots: int = 0, pack_threads: int = 0):
         self._check(self._lib.kws_ingest_config(self._h, int(chunk_clips), int(n_slots), int(pack_threads)), ModelError)
@@ -1027,6 +1080,11 @@ def host_dscnn_units():
     if rc != KWS_OK:
         raise KWSError(f"kws_host_dscnn_units failed ({rc})")
     return words.reshape(-1, 2, 64, 4), base
+
+
+def host_cnn_trad_window_chunk() -> int:
+    """Windows per launch pair of ``Context.forward_cnn_trad_windows_f32`` (``kws_host_cnn_trad_window_chunk``)."""
+    return int(lib().kws_host_cnn_trad_window_chunk())
 
 
 def host_cnn_trad_image(blob: np.ndarray, num_classes: int):

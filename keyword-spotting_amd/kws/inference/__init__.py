@@ -12,7 +12,7 @@ import torch
 from kws.common.errors import AudioProcessingError, ModelError
 from kws.datasets.speech_commands import DEFAULT_WORDS, SpeechCommandDataset
 from kws.libs.audio_processor import AudioConfig, fix_length, load_audio, load_pcm16, read_wav
-from kws.libs.models import DepthwiseSeparableConv
+from kws.libs.models import DepthwiseSeparableConv, KeywordSpottingModel
 
 WANTED_WORDS = [SpeechCommandDataset.SILENCE_LABEL, SpeechCommandDataset.UNKNOWN_LABEL] + DEFAULT_WORDS
 
@@ -66,11 +66,12 @@ class Utterance:
     peak: float  # int for int16 PCM
 
 
-def _classify_spans(ctx, device, words, num_classes: int, clip_samples: int, rate: float, frame_step: int, rows, cut,
+def _classify_spans(ctx, model, device, words, num_classes: int, clip_samples: int, rate: float, frame_step: int, rows, cut,
                     f32: bool = False) -> List[Utterance]:
     """The tail ``segment`` and ``pop_utterances`` share: ``rows`` of ``(recording, start, end, open, close, reason)``, samples
     and frames; ``cut(clips, peaks)`` launches the cut of row ``u`` into ``clips[u]`` and ``peaks[u]``.  Then the model once per
-    clip and ONE read of logits, labels and peaks.  ``f32``: float32 clips and peaks (``kws_cut_f32``, ``kws_infer_f32``)."""
+    clip (``model``'s fused entry, through its hooks) and ONE read of logits, labels and peaks.  ``f32``: float32 clips and peaks
+    (``kws_cut_f32``, ``kws_infer_f32`` / ``kws_infer_cnn_trad_f32``)."""
     U, C = len(rows), num_classes
     clips = torch.empty((U, clip_samples), dtype=torch.float32 if f32 else torch.int16, device=device)
     out = torch.empty((U * (C + 2),), dtype=torch.float32, device=device)  # logits [U, C], then labels [U] (int32) and peaks [U]
@@ -78,10 +79,10 @@ def _classify_spans(ctx, device, words, num_classes: int, clip_samples: int, rat
     torch.cuda.current_stream(device).synchronize()  # a context may run on its own stream
     if f32:
         cut(clips, out[U * C + U:])
-        ctx.infer_f32(clips, logits, ints[:U])
+        model._native_infer_f32(ctx, clips, logits, ints[:U])
     else:
         cut(clips, ints[U:])
-        ctx.infer_i16(clips, logits, ints[:U])
+        model._native_infer_i16(ctx, clips, logits, ints[:U])
     ctx.sync()
     host = out.cpu()  # the one read
     logits, ints = host[:U * C].view(U, C).numpy(), host[U * C:].view(torch.int32).numpy()
@@ -143,9 +144,11 @@ class KeywordEvent:
 
 
 class KeywordSpotter:
-    """Holds a model on one GPU and maps wav files / PCM batches to (index, word)."""
+    """Holds a model on one GPU and maps wav files / PCM batches to (index, word).  ``model``: a ``DepthwiseSeparableConv`` (the
+    default), a ``DepthwiseSeparableConvBN`` (served by its fold) or a ``CnnTradFpool3``; every method runs the model through its
+    hooks (``kws/libs/models.py``), so clips, files, ``scan*`` and ``segment*`` work for all three."""
 
-    def __init__(self, model: Optional[DepthwiseSeparableConv] = None, words: Sequence[str] = WANTED_WORDS,
+    def __init__(self, model: Optional[KeywordSpottingModel] = None, words: Sequence[str] = WANTED_WORDS,
                  config: Optional[AudioConfig] = None, device: int = 0):
         self.config = config or AudioConfig()
         self.words = list(words)
@@ -159,11 +162,25 @@ class KeywordSpotter:
 
     def infer_pcm16(self, pcm: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
         """``int16[B,n]`` host array -> (labels int32[B], logits float32[B,C]) through the library's host-ingest
-        pipeline (``kws_infer_host_i16``: pack into pinned staging, H2D, MFCC + DS-CNN and D2H overlapped chunk by chunk)."""
+        pipeline (``kws_infer_host_i16``: pack into pinned staging, H2D, MFCC + DS-CNN and D2H overlapped chunk by chunk).
+        A ``CnnTradFpool3`` has no such pipeline: the batch is uploaded and classified by ``kws_infer_cnn_trad_i16``, with the same
+        results and nothing overlapped."""
         clips = fix_length(np.atleast_2d(np.asarray(pcm, dtype=np.int16)), self.config.desired_samples)
         ctx = self.model._context(self.device.index or 0)
+        if not self.model._host_ingest:
+            return self._infer_uploaded(ctx, torch.from_numpy(np.ascontiguousarray(clips)))
         logits, labels = ctx.infer_host_i16(np.ascontiguousarray(clips))
         return labels, logits
+
+    def _infer_uploaded(self, ctx, clips: torch.Tensor) -> Tuple[np.ndarray, np.ndarray]:
+        """One int16 (or float32) ``[B, n]`` batch: upload, the model's fused entry, read back -> (labels, logits)."""
+        x = clips.to(self.device).contiguous()
+        logits = torch.empty((x.shape[0], self.model.num_classes), dtype=torch.float32, device=self.device)
+        labels = torch.empty((x.shape[0],), dtype=torch.int32, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()  # a context may run on its own stream
+        (self.model._native_infer_f32 if x.dtype == torch.float32 else self.model._native_infer_i16)(ctx, x, logits, labels)
+        ctx.sync()
+        return labels.cpu().numpy(), logits.cpu().numpy()
 
     def infer_batches(self, batches: Iterable[np.ndarray], max_batch: Optional[int] = None
                       ) -> Iterator[Tuple[np.ndarray, np.ndarray]]:
@@ -174,9 +191,18 @@ class KeywordSpotter:
         full ACROSS batches: batch k+1 is submitted (``kws_infer_host_submit_i16``) before batch k's results are waited
         for, so its pack and H2D run under batch k's kernels -- with the reference's own batch size (1028, ``train.py:110``)
         a batch is also cut into as many chunks as the ring has slots.  Yields ``(labels int32[B], logits float32[B,C])``
-        per batch, in order.  ``max_batch``: clips per chunk of the staging ring (default 1024)."""
+        per batch, in order.  ``max_batch``: clips per chunk of the staging ring (default 1024).
+
+        A ``CnnTradFpool3`` has no host-ingest pipeline: every batch is uploaded and classified by ``kws_infer_cnn_trad_i16``
+        before the next one is touched -- the same results in the same order, no pipelining; ``max_batch`` is ignored."""
         n = self.config.desired_samples
         ctx = self.model._context(self.device.index or 0)
+        if not self.model._host_ingest:
+            for batch in batches:
+                src = batch if torch.is_tensor(batch) and batch.dtype == torch.int16 and batch.dim() == 2 and batch.shape[1] == n \
+                    else torch.from_numpy(np.ascontiguousarray(fix_length(np.atleast_2d(np.asarray(batch, dtype=np.int16)), n)))
+                yield self._infer_uploaded(ctx, src)
+            return
         if max_batch:
             ctx.infer_host_wait(0)
             ctx.ingest_config(chunk_clips=int(max_batch))
@@ -254,21 +280,22 @@ class KeywordSpotter:
             labels = torch.empty((len(clips),), dtype=torch.int32, device=self.device)
             if is_i16:
                 ctx.resample_i16(x, rate, cfg.sample_rate, y, lengths)
-                ctx.infer_i16(y, logits, labels)
+                self.model._native_infer_i16(ctx, y, logits, labels)
             else:
                 ctx.resample_f32(x, rate, cfg.sample_rate, y, lengths)
-                ctx.infer_f32(y, logits, labels)
+                self.model._native_infer_f32(ctx, y, logits, labels)
             result[members] = labels.cpu().numpy()
         return [(int(i), self.words[int(i)]) for i in result]
 
     def infer_f32(self, signals: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
-        """``float32[B,n]`` host signals in [-1, 1] -> (labels int32[B], logits float32[B,C]) (``kws_infer_f32``)."""
+        """``float32[B,n]`` host signals in [-1, 1] -> (labels int32[B], logits float32[B,C]) (``kws_infer_f32``, for a
+        ``CnnTradFpool3`` ``kws_infer_cnn_trad_f32``)."""
         x = torch.from_numpy(np.ascontiguousarray(fix_length(np.atleast_2d(np.asarray(signals, dtype=np.float32)),
                                                              self.config.desired_samples))).to(self.device)
         ctx = self.model._context(self.device.index or 0)
         logits = torch.empty((x.shape[0], self.model.num_classes), dtype=torch.float32, device=self.device)
         labels = torch.empty((x.shape[0],), dtype=torch.int32, device=self.device)
-        ctx.infer_f32(x, logits, labels)
+        self.model._native_infer_f32(ctx, x, logits, labels)
         return labels.cpu().numpy(), logits.cpu().numpy()
 
 
@@ -318,7 +345,7 @@ class KeywordSpotter:
         C = self.model.num_classes
         logits = torch.empty((R, W, C), dtype=torch.float32, device=self.device)
         labels = torch.empty((R, W), dtype=torch.int32, device=self.device)
-        (ctx.scan_f32 if x.dtype == torch.float32 else ctx.scan_i16)(x, int(hop_frames), logits, labels)
+        self.model._native_scan(ctx, x, int(hop_frames), logits, labels)
         start_s, end_s = scan_window_times(W, int(hop_frames), frame_len, frame_step, cfg.sample_rate, WINDOW_FRAMES, n)
         events = None
         if threshold is not None:
@@ -481,7 +508,7 @@ class KeywordSpotter:
         span = torch.tensor([row[:3] for row in rows], dtype=torch.int32).to(self.device)
         cut = (lambda clips, peaks: ctx.cut_f32(x, span, clips, int(normalize) / 32768.0, peaks)) if f32 else \
               (lambda clips, peaks: ctx.cut_i16(x, span, clips, int(normalize), peaks))
-        for utt in _classify_spans(ctx, self.device, self.words, self.model.num_classes, cfg.desired_samples, float(cfg.sample_rate), frame_step,
+        for utt in _classify_spans(ctx, self.model, self.device, self.words, self.model.num_classes, cfg.desired_samples, float(cfg.sample_rate), frame_step,
                                    rows, cut, f32):
             out[utt.recording].append(utt)
         return out
@@ -635,7 +662,7 @@ class KeywordSpotter:
         ctx = self.model._context(self.device.index or 0)
         logits = torch.empty((max(W_pack, 1), C), dtype=torch.float32, device=self.device)
         labels = torch.empty((max(W_pack, 1),), dtype=torch.int32, device=self.device)
-        (ctx.scan_ragged_f32 if f32 else ctx.scan_ragged_i16)(buf, start, length, hop, logits, labels)
+        self.model._native_scan_ragged(ctx, buf, start, length, hop, logits, labels)
         ev = None
         if threshold is not None:
             m = int(max_events)
@@ -721,7 +748,7 @@ class KeywordSpotter:
         span = torch.tensor([(0, int(start[r]) + s, int(start[r]) + e) for r, s, e, _, _, _ in rows], dtype=torch.int32).to(self.device)
         cut = (lambda clips, peaks: ctx.cut_f32(buf[None, :], span, clips, int(normalize) / 32768.0, peaks)) if f32 else \
               (lambda clips, peaks: ctx.cut_i16(buf[None, :], span, clips, int(normalize), peaks))
-        for utt in _classify_spans(ctx, self.device, self.words, self.model.num_classes, cfg.desired_samples, float(cfg.sample_rate), frame_step,
+        for utt in _classify_spans(ctx, self.model, self.device, self.words, self.model.num_classes, cfg.desired_samples, float(cfg.sample_rate), frame_step,
                                    rows, cut, f32):
             out[utt.recording].append(utt)
         return out
@@ -823,9 +850,16 @@ class StreamingSpotter:
     Attributes: ``hop`` -- samples per hop at ``config.sample_rate``; ``hop_in`` -- samples ``push`` takes per stream (``hop``
     without ``input_rate``); ``delay_samples`` -- the resampler's delay in samples at ``config.sample_rate`` (10 = 0.625 ms for
     every rate above 16 kHz, 20 for 8 kHz, 0 without ``input_rate``): what the streams hear lags the input by that much.
+
+    ``model``: a ``DepthwiseSeparableConv`` (the default), a ``DepthwiseSeparableConvBN`` (served by its fold) or a
+    ``CnnTradFpool3``.  With a ``CnnTradFpool3`` a push is three launches (``kws_stream_push_cnn_trad_i16``: the frame, the
+    convolutions over every stream's window of the feature ring read in place, the dense tail), the results are read from the
+    device -- one synchronise and one read per push, ``host_results`` is off -- ``use_graph=True`` raises ``ModelError``, and
+    ``input_rate`` resamples into the hop buffer (``kws_stream_resample_i16``) in front of the push.  ``utterances``, ``detect``,
+    ``smooth_window`` and ``vad_log_energy`` work as for the DS-CNN.
     """
 
-    def __init__(self, n_streams: int, model: Optional[DepthwiseSeparableConv] = None, words: Sequence[str] = WANTED_WORDS,
+    def __init__(self, n_streams: int, model: Optional[KeywordSpottingModel] = None, words: Sequence[str] = WANTED_WORDS,
                  config: Optional[AudioConfig] = None, device: int = 0, use_graph: bool = False, smooth_window: int = 0,
                  vad_log_energy: Optional[float] = None, vad_windows: Tuple[int, int] = (40, 80), host_results: bool = True,
                  input_rate: Optional[int] = None, utterances: Optional[UtteranceConfig] = None,
@@ -848,6 +882,8 @@ class StreamingSpotter:
             self.hop_in = self.hop * down // up
         self.device = torch.device("cuda", device)
         self.use_graph = use_graph
+        if use_graph and not self.model._stream_graph:
+            raise ModelError(f"use_graph=True: {type(self.model).__name__} has no captured-graph push (it is DS-CNN only)")
         self._ctx = _native.Context(device, ModelError)
         cfg = self.config
         frame_len = int(round(cfg.frame_length * cfg.sample_rate))
@@ -855,11 +891,14 @@ class StreamingSpotter:
                 (16000, 16000, 400, 160, 512, 26, 10):  # a non-default AudioConfig: tell the front end (nfft as audio_processor.py:268 derives it)
             self._ctx.set_frontend(cfg.sample_rate, cfg.desired_samples, frame_len, self.hop, max(cfg.fft_size, frame_len),
                                    cfg.num_mel_filters, cfg.num_cepstral_coeffs)
-        self._ctx.load_dscnn(self.model.packed_weights(), self.model.num_classes)
+        self.model._native_stream_load(self._ctx)
         self._ctx.stream_open(self.n_streams)
         if self._resample:
             self._ctx.stream_resample_open(self.n_streams, self.input_rate, cfg.sample_rate, self.hop_in)
         self._hop_buf = torch.zeros((self.n_streams, self.hop_in), dtype=torch.int16, device=self.device)
+        # a model without the DS-CNN's rate push: the resampler writes the hop here and the model's own push takes it
+        self._hop16 = torch.zeros((self.n_streams, self.hop), dtype=torch.int16, device=self.device) \
+            if self._resample and not self.model._stream_zero_copy else None
         self._logits = torch.zeros((self.n_streams, self.model.num_classes), dtype=torch.float32, device=self.device)
         self._labels = torch.zeros((self.n_streams,), dtype=torch.int32, device=self.device)
         # posterior smoothing: softmax of every hop's logits averaged over the last
@@ -875,7 +914,7 @@ class StreamingSpotter:
         self.vad_state: Optional[np.ndarray] = None
         # zero-copy delivery (kws_stream_host_results): the push's own kernel writes logits and labels to pinned host memory
         # and raises a flag there, so a plain push returns without a stream synchronise or a device-to-host copy
-        self._host = bool(host_results) and self.smooth_window == 0 and self._vad is None
+        self._host = bool(host_results) and self.smooth_window == 0 and self._vad is None and self.model._stream_zero_copy
         if self._host:
             self._ctx.stream_host_results(True)
         # live utterances (kws_stream_utt_*): armed, every push also appends its hop to a per-stream history on the device, walks
@@ -911,13 +950,17 @@ class StreamingSpotter:
                                          self._det_max_events)
         torch.cuda.synchronize(self.device)
 
-    def load_model(self, model: DepthwiseSeparableConv) -> None:
+    def load_model(self, model: KeywordSpottingModel) -> None:
         """Swap the classifier while the streams keep running (their PCM and feature rings are untouched); a captured
-        hipGraph is re-captured on the next push (``kws_load_dscnn`` retires it: it holds the old weights)."""
+        hipGraph is re-captured on the next push (``kws_load_dscnn`` retires it: it holds the old weights).  The new model must be
+        of the family the spotter was created with (DS-CNN, folded BatchNorm DS-CNN included, or cnn-trad-fpool3)."""
+        if model._family != self.model._family:
+            raise ModelError(f"load_model: the streams run {type(self.model).__name__}; a {type(model).__name__} is another model "
+                             "family -- create a new StreamingSpotter for it")
         if model.num_classes != self.model.num_classes:
             raise ModelError(f"the streams were opened for {self.model.num_classes} classes, the new model has {model.num_classes}")
         self.model = model
-        self._ctx.load_dscnn(model.packed_weights(), model.num_classes)
+        model._native_stream_load(self._ctx)
 
     def push(self, samples) -> Tuple[np.ndarray, np.ndarray]:
         """``int16[n_streams, hop_in]`` (host array or device tensor) -> (labels int32[S], logits float32[S,C]);
@@ -938,10 +981,14 @@ class StreamingSpotter:
             raise ModelError(f"push expects int16 [{self.n_streams}, {self.hop_in}]")
         self._hop_buf.copy_(x, non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()  # the context runs on its own stream
-        if self._resample:
+        if self._hop16 is not None:
+            if self._ctx.stream_resample_i16(self._hop_buf, self._hop16) != self.hop:
+                raise ModelError(f"push: the resampler did not emit a hop of {self.hop} samples")
+            self.model._native_stream_push(self._ctx, self._hop16, self._logits, self._labels, False)
+        elif self._resample:
             self._ctx.stream_push_rate_i16(self._hop_buf, self._logits, self._labels)
         else:
-            self._ctx.stream_push_i16(self._hop_buf, self._logits, self._labels, use_graph=self.use_graph)
+            self.model._native_stream_push(self._ctx, self._hop_buf, self._logits, self._labels, self.use_graph)
         if self._host:
             lg, lb = self._ctx.stream_wait_host(self.n_streams)
             return lb.copy(), lg.copy()
@@ -988,7 +1035,7 @@ class StreamingSpotter:
         """The utterances that closed since the last call, in the order they closed (ascending stream within a hop).  Waits for
         the newest push's step (``kws_stream_utt_poll``); with nothing new it returns ``[]`` and launches nothing.  Otherwise, on
         the device: the spans cut out of the history rings, normalised and padded or trimmed to a clip
-        (``kws_stream_utt_cut_i16``), the model once per clip (``kws_infer_i16``), then ONE read of logits, labels and peaks.
+        (``kws_stream_utt_cut_i16``), the model once per clip (``kws_infer_i16`` or the model's own fused entry), then ONE read of logits, labels and peaks.
         ``recording`` is the stream index; times are seconds of the stream since this spotter was armed, at ``config.sample_rate``
         (with ``input_rate`` that is the resampled timeline, ``delay_samples`` behind the input).  Records the queue has already
         overwritten (more than ``max_events`` closes between two calls) are skipped; an utterance cut more than ``slack_hops``
@@ -998,7 +1045,7 @@ class StreamingSpotter:
         if (new := self._drain("_utt", self._ctx.stream_utt_poll, self._ctx.stream_utt_read)) is None:
             return []
         first, rec = new
-        return _classify_spans(self._ctx, self.device, self.words, self.model.num_classes, self.config.desired_samples,
+        return _classify_spans(self._ctx, self.model, self.device, self.words, self.model.num_classes, self.config.desired_samples,
                                float(self.config.sample_rate), self.hop, rec,
                                lambda clips, peaks: self._ctx.stream_utt_cut_i16(first, clips, int(self.utterances.normalize), peaks))
 

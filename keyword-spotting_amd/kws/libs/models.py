@@ -155,7 +155,9 @@ class _TrainableNative(KeywordSpottingModel):
     """A model whose forward and backward are HIP entries of a ``_native.Context``: the context with its parameter refresh, the
     switch between the plain forward and ``_NativeTrainFunction``, the output tensors and the checks of ``infer_pcm16``.  A model
     supplies ``_name``, ``_backward_entry``, ``_pcm16_is`` and the hooks ``_check_features``, ``_load_host``, ``_load_device``,
-    ``_native_forward``, ``_native_backward``, ``_native_infer_i16``."""
+    ``_native_forward``, ``_native_backward``, and what ``KeywordSpotter`` / ``StreamingSpotter`` run a model through:
+    ``_native_infer_i16``, ``_native_infer_f32``, ``_native_scan``, ``_native_scan_ragged``, ``_native_stream_load``,
+    ``_native_stream_push``."""
 
     _name = ""            # the class name in messages
     _backward_entry = ""  # the C entry behind loss.backward()
@@ -163,6 +165,12 @@ class _TrainableNative(KeywordSpottingModel):
     # the parameter refresh of ``_context`` for parameters on the GPU: True = on the device (``kws_load_*_device``), False =
     # through the host as for CPU-resident parameters (an instance of ``DepthwiseSeparableConv`` sets it to compare the routes)
     _device_refresh = True
+    # what the spotters may use with this model: ``_family`` names the kernels (a StreamingSpotter swaps models within one
+    # family only); the host-ingest pipeline, the captured-graph push and the zero-copy result delivery exist for the DS-CNN
+    _family = ""
+    _host_ingest = False
+    _stream_graph = False
+    _stream_zero_copy = False
 
     def __init__(self, num_classes: int):
         super().__init__(num_classes)
@@ -280,6 +288,10 @@ class DepthwiseSeparableConv(_TrainableNative):
 
     _name = "DepthwiseSeparableConv"
     _backward_entry = "kws_dscnn_backward_f32"
+    _family = "dscnn"
+    _host_ingest = True
+    _stream_graph = True
+    _stream_zero_copy = True
 
     def __init__(self, num_classes: int = 12, input_channels: int = 1):
         super().__init__(num_classes)
@@ -331,6 +343,21 @@ class DepthwiseSeparableConv(_TrainableNative):
 
     def _native_infer_i16(self, ctx, wav, logits, labels):
         ctx.infer_i16(wav, logits, labels)
+
+    def _native_infer_f32(self, ctx, wav, logits, labels):
+        ctx.infer_f32(wav, logits, labels)
+
+    def _native_scan(self, ctx, x, hop, logits, labels):
+        (ctx.scan_f32 if x.dtype == torch.float32 else ctx.scan_i16)(x, hop, logits, labels)
+
+    def _native_scan_ragged(self, ctx, buf, start, length, hop, logits, labels):
+        (ctx.scan_ragged_f32 if buf.dtype == torch.float32 else ctx.scan_ragged_i16)(buf, start, length, hop, logits, labels)
+
+    def _native_stream_load(self, ctx):
+        ctx.load_dscnn(self.packed_weights(), self.num_classes)
+
+    def _native_stream_push(self, ctx, hop, logits, labels, use_graph=False):
+        ctx.stream_push_i16(hop, logits, labels, use_graph=use_graph)
 
 
 class DepthwiseSeparableConvBN(KeywordSpottingModel):
@@ -393,6 +420,36 @@ class DepthwiseSeparableConvBN(KeywordSpottingModel):
     def infer_pcm16(self, wav: torch.Tensor):
         return self.fold().infer_pcm16(wav)
 
+    # what the spotters run a model through: the fold is an ordinary DS-CNN, so its context, its packed weights and its hooks serve
+    _family = DepthwiseSeparableConv._family
+    _host_ingest = DepthwiseSeparableConv._host_ingest
+    _stream_graph = DepthwiseSeparableConv._stream_graph
+    _stream_zero_copy = DepthwiseSeparableConv._stream_zero_copy
+
+    def _context(self, device_index: int, params=None):
+        return self.fold()._context(device_index, params)
+
+    def packed_weights(self) -> np.ndarray:
+        return self.fold().packed_weights()
+
+    def _native_infer_i16(self, ctx, wav, logits, labels):
+        self.fold()._native_infer_i16(ctx, wav, logits, labels)
+
+    def _native_infer_f32(self, ctx, wav, logits, labels):
+        self.fold()._native_infer_f32(ctx, wav, logits, labels)
+
+    def _native_scan(self, ctx, x, hop, logits, labels):
+        self.fold()._native_scan(ctx, x, hop, logits, labels)
+
+    def _native_scan_ragged(self, ctx, buf, start, length, hop, logits, labels):
+        self.fold()._native_scan_ragged(ctx, buf, start, length, hop, logits, labels)
+
+    def _native_stream_load(self, ctx):
+        self.fold()._native_stream_load(ctx)
+
+    def _native_stream_push(self, ctx, hop, logits, labels, use_graph=False):
+        self.fold()._native_stream_push(ctx, hop, logits, labels, use_graph)
+
 
 class CnnTradFpool3(_TrainableNative):
     """Build-defined model-zoo member: Sainath & Parada's cnn-trad-fpool3 on the reference's
@@ -413,6 +470,7 @@ class CnnTradFpool3(_TrainableNative):
 
     _name = "CnnTradFpool3"
     _backward_entry = "kws_cnn_trad_backward_f32"
+    _family = "cnn_trad"
     _pcm16_is = "the path is HIP kernels"
 
     def __init__(self, num_classes: int = 12):
@@ -441,3 +499,21 @@ class CnnTradFpool3(_TrainableNative):
 
     def _native_infer_i16(self, ctx, wav, logits, labels):
         ctx.infer_cnn_trad_i16(wav, logits, labels)
+
+    def _native_infer_f32(self, ctx, wav, logits, labels):
+        ctx.infer_cnn_trad_f32(wav, logits, labels)
+
+    def _native_scan(self, ctx, x, hop, logits, labels):
+        (ctx.scan_cnn_trad_f32 if x.dtype == torch.float32 else ctx.scan_cnn_trad_i16)(x, hop, logits, labels)
+
+    def _native_scan_ragged(self, ctx, buf, start, length, hop, logits, labels):
+        (ctx.scan_ragged_cnn_trad_f32 if buf.dtype == torch.float32 else ctx.scan_ragged_cnn_trad_i16)(buf, start, length, hop, logits,
+                                                                                                     labels)
+
+    def _native_stream_load(self, ctx):
+        ctx.load_cnn_trad(self.packed_weights(), self.num_classes)
+
+    def _native_stream_push(self, ctx, hop, logits, labels, use_graph=False):
+        if use_graph:
+            raise ModelError("CnnTradFpool3: the streaming push has no captured-graph variant (kws_stream_push_cnn_trad_i16)")
+        ctx.stream_push_cnn_trad_i16(hop, logits, labels)
