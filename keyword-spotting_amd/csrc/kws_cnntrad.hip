@@ -14,9 +14,10 @@
 // input channels of one input position -- is a single aligned ds_read_b128 per piece with no VALU work in the
 // loop.  Taps that fall into the padding read a zero region.  conv2's pre-split weights (983 KB) stream from L2.
 // Kernel B: the dense tail, 16 clips per workgroup; its 19008 -> 32 layer is a GEMM on the same matrix-pipe path.
+// Behind the kernels and their launchers: the one conv + dense host sequence, the model's ModelOps and its C entry points.
 #include <type_traits>
 
-#include "kws_internal.h"
+#include "kws_ctx.h"
 #include "kws_split_mfma.h"
 
 namespace kws {
@@ -259,37 +260,24 @@ hipError_t cnntrad_init_device() {
     return hipSuccess;
 }
 
-// d_conv_ws: B * 19008 floats of conv2 output, then B floats of per-clip scales (f16-pair arithmetic only)
-hipError_t launch_cnntrad_conv(hipStream_t s, const CnnTradWeights& w, const float* d_feat, int B, float* d_conv_ws, bool f16_pair) {
-    float* scale = d_conv_ws + (size_t)B * CT_FLAT;
-    if (f16_pair)
-        hipLaunchKernelGGL(kws_cnntrad_conv_kernel<true>, dim3(B), dim3(CT_NT), CT_LDS_BYTES_H2, s, w, d_feat, B, d_conv_ws, scale);
+// One launch per source kind and arithmetic: the six instantiations cnntrad_init_device has prepared.
+template <bool H2>
+static void conv_launch(hipStream_t s, const CnnTradWeights& w, const CtSource& src, int n, float* d_conv_ws, float* scale) {
+    constexpr int lds = H2 ? CT_LDS_BYTES_H2 : CT_LDS_BYTES;
+    const dim3 grid(n), block(CT_NT);
+    if (src.kind == CtSource::CLIPS)
+        hipLaunchKernelGGL(kws_cnntrad_conv_kernel<H2>, grid, block, lds, s, w, src.maps, n, d_conv_ws, scale);
+    else if (src.kind == CtSource::WINDOWS)
+        hipLaunchKernelGGL(kws_cnntrad_conv_windows_kernel<H2>, grid, block, lds, s, w, src.maps, src.windows, n, d_conv_ws, scale);
     else
-        hipLaunchKernelGGL(kws_cnntrad_conv_kernel<false>, dim3(B), dim3(CT_NT), CT_LDS_BYTES, s, w, d_feat, B, d_conv_ws, scale);
-    return hipGetLastError();
+        hipLaunchKernelGGL(kws_cnntrad_conv_ring_kernel<H2>, grid, block, lds, s, w, src.maps, src.hops, src.lag, n, d_conv_ws, scale);
 }
-
-// n windows from sw.first on -> slots 0 .. n - 1 of d_conv_ws (n * 19008 floats, then n scales)
-hipError_t launch_cnntrad_conv_windows(hipStream_t s, const CnnTradWeights& w, const float* d_frames, const CtWindows& sw, int n,
-                                       float* d_conv_ws, bool f16_pair) {
+hipError_t launch_cnntrad_conv(hipStream_t s, const CnnTradWeights& w, const CtSource& src, int n, float* d_conv_ws, bool f16_pair) {
     float* scale = d_conv_ws + (size_t)n * CT_FLAT;
     if (f16_pair)
-        hipLaunchKernelGGL(kws_cnntrad_conv_windows_kernel<true>, dim3(n), dim3(CT_NT), CT_LDS_BYTES_H2, s, w, d_frames, sw, n, d_conv_ws, scale);
+        conv_launch<true>(s, w, src, n, d_conv_ws, scale);
     else
-        hipLaunchKernelGGL(kws_cnntrad_conv_windows_kernel<false>, dim3(n), dim3(CT_NT), CT_LDS_BYTES, s, w, d_frames, sw, n, d_conv_ws, scale);
-    return hipGetLastError();
-}
-
-// the S streams' windows of the feature ring, rotated by the hop counter the frame kernel has advanced
-hipError_t launch_cnntrad_conv_ring(hipStream_t s, const CnnTradWeights& w, const float* d_feat_ring, const int* d_hops, int frames_lag,
-                                    int S, float* d_conv_ws, bool f16_pair) {
-    float* scale = d_conv_ws + (size_t)S * CT_FLAT;
-    if (f16_pair)
-        hipLaunchKernelGGL(kws_cnntrad_conv_ring_kernel<true>, dim3(S), dim3(CT_NT), CT_LDS_BYTES_H2, s, w, d_feat_ring, d_hops, frames_lag, S,
-                           d_conv_ws, scale);
-    else
-        hipLaunchKernelGGL(kws_cnntrad_conv_ring_kernel<false>, dim3(S), dim3(CT_NT), CT_LDS_BYTES, s, w, d_feat_ring, d_hops, frames_lag, S,
-                           d_conv_ws, scale);
+        conv_launch<false>(s, w, src, n, d_conv_ws, scale);
     return hipGetLastError();
 }
 
@@ -305,3 +293,121 @@ hipError_t launch_cnntrad_dense(hipStream_t s, const CnnTradWeights& w, const fl
 }
 
 }  // namespace kws
+
+using namespace kws;
+
+// ---- behind the C ABI: conv from `src`, then dense, over n slots of the context workspace: n * 19008 floats of conv2 output, then one scale per slot
+// (f16-pair arithmetic).  Logits [n][C] and labels [n] (or NULL); fn names the caller in the allocation's refusal.
+static int ct_reserve(kws_ctx* c, const char* fn, int n) { return grow_conv_ws(c, (size_t)n * 64 * 297 + (size_t)n, fn); }
+static int ct_conv_dense(kws_ctx* c, const char* fn, const CtSource& src, int n, float* d_logits, int32_t* d_label) {
+    int rc = ct_reserve(c, fn, n);
+    if (rc) return rc;
+    const bool pair = c->cnntrad_math == KWS_CT_F16_PAIR;
+    {
+        ProfScope ps(c, KWS_K_CNNTRAD_CONV);
+        HIP_TRY(c, launch_cnntrad_conv(c->stream, c->tw, src, n, c->d_conv_ws, pair));
+    }
+    {
+        ProfScope ps(c, KWS_K_CNNTRAD_DENSE);
+        HIP_TRY(c, launch_cnntrad_dense(c->stream, c->tw, c->d_conv_ws, n, d_logits, d_label, pair));
+    }
+    return KWS_OK;
+}
+
+// The model as the host flows see it (ModelOps, kws_ctx.h); the recording flows and the fused clip entries ask the same of it.
+static int ct_scan_check(kws_ctx* c, const char* fn) {
+    if (!c->fe_ready || !c->cnntrad_ready) return fail(c, KWS_ESTATE, std::string(fn) + ": front end or model not configured (kws_load_cnn_trad)");
+    return check_ref_map(c, fn, ": the kernels are built for a 99 x 10 feature map");
+}
+static int ct_model_check(kws_ctx* c, const char* fn) {
+    return c->cnntrad_ready ? KWS_OK : fail(c, KWS_ESTATE, std::string(fn) + ": no model loaded (kws_load_cnn_trad)");
+}
+static int ct_push_check(kws_ctx* c, const char* fn) {
+    if (int rc = ct_model_check(c, fn)) return rc;
+    return check_ref_map(c, fn, ": the kernels are built for a 99 x 10 feature map");
+}
+static int ct_classes(const kws_ctx* c) { return c->tw.num_classes; }
+
+// B contiguous clips: the product entry, its parity aid and the fused clip entries.
+static int ct_forward(kws_ctx* c, const float* d_feat, int B, float* d_logits, int32_t* d_label, const char* fn) {
+    int rc = check_batch(c, d_feat, B, fn);
+    if (rc) return rc;
+    if (!d_logits) return fail(c, KWS_EINVAL, std::string(fn) + ": d_logits is NULL");
+    if ((rc = ct_model_check(c, fn))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return ct_conv_dense(c, fn, {CtSource::CLIPS, d_feat, {}, nullptr, 0}, B, d_logits, d_label);
+}
+
+// The R * W windows of a frame array [R][F][10], read in place, in chunks of CT_WINDOW_CHUNK: per chunk one conv and one dense launch
+// that writes logits and labels at the chunk's offset.  The caller has checked the arguments and the limits (2^28 frames, 2^30 windows).
+static int ct_windows(kws_ctx* c, const char* fn, const float* d_frames, int R, int F, int W, int hop_frames, float* d_logits,
+                      int32_t* d_label) {
+    const long long n = (long long)R * W;
+    const int C = c->tw.num_classes;
+    for (long long i0 = 0; i0 < n; i0 += CT_WINDOW_CHUNK) {
+        const int nb = n - i0 < CT_WINDOW_CHUNK ? (int)(n - i0) : CT_WINDOW_CHUNK;
+        const CtWindows sw = {(unsigned)i0, (unsigned)W, (unsigned)F * (unsigned)IN_F, (unsigned)hop_frames * (unsigned)IN_F};
+        int rc = ct_conv_dense(c, fn, {CtSource::WINDOWS, d_frames, sw, nullptr, 0}, nb, d_logits + (size_t)i0 * C, d_label ? d_label + i0 : nullptr);
+        if (rc) return rc;
+    }
+    return KWS_OK;
+}
+
+// The launches of a push: the frame kernel, then every stream's window of the feature ring, rotated by the hop counter it has
+// advanced.  The workspace is there before the frame launch: a push that cannot allocate leaves the set as it was.
+static int ct_ring_push(kws_ctx* c, const char* fn, const int16_t* d_hop, float* d_logits, int32_t* d_label) {
+    if (int rc = ct_reserve(c, fn, c->n_streams)) return rc;
+    HIP_TRY(c, stream_enqueue_frame(c, d_hop, true));
+    return ct_conv_dense(c, fn, {CtSource::RING, c->d_feat_ring, {}, c->d_hops, frames_lag(c->fp)}, c->n_streams, d_logits, d_label);
+}
+
+static const ModelOps kCnnTradOps = {ct_scan_check, ct_scan_check, ct_push_check, ct_classes, ct_forward, ct_windows, ct_ring_push};
+namespace kws {
+const ModelOps& model_ops_cnn_trad() { return kCnnTradOps; }
+}  // namespace kws
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int kws_forward_cnn_trad_f32(kws_ctx* c, const float* d_feat, int B, float* d_logits, int32_t* d_label) {
+    return ct_forward(c, d_feat, B, d_logits, d_label, "kws_forward_cnn_trad_f32");
+}
+
+int kws_forward_cnn_trad_debug_f32(kws_ctx* c, const float* d_feat, int B, float* d_logits, int32_t* d_label, float* d_conv2,
+                                   float* d_clip_scale) {
+    const char* fn = "kws_forward_cnn_trad_debug_f32";
+    if (c && !d_conv2) return fail(c, KWS_EINVAL, std::string(fn) + ": d_conv2 is NULL");
+    int rc = ct_forward(c, d_feat, B, d_logits, d_label, fn);
+    if (rc) return rc;
+    const size_t n = (size_t)B * 64 * 297;
+    HIP_TRY(c, hipMemcpyAsync(d_conv2, c->d_conv_ws, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
+    if (d_clip_scale && c->cnntrad_math == KWS_CT_F16_PAIR)
+        HIP_TRY(c, hipMemcpyAsync(d_clip_scale, c->d_conv_ws + n, sizeof(float) * (size_t)B, hipMemcpyDeviceToDevice, c->stream));
+    return KWS_OK;
+}
+
+int kws_set_cnn_trad_math(kws_ctx* c, int math) {
+    if (!c) return KWS_EINVAL;
+    if (math != KWS_CT_F16_PAIR && math != KWS_CT_BF16_TRIPLE) return fail(c, KWS_EINVAL, "kws_set_cnn_trad_math: unknown arithmetic");
+    c->cnntrad_math = math;
+    return KWS_OK;
+}
+
+int kws_host_cnn_trad_window_chunk(void) { return CT_WINDOW_CHUNK; }
+
+int kws_forward_cnn_trad_windows_f32(kws_ctx* c, const float* d_frames, int R, int F, int hop_frames, float* d_logits, int32_t* d_label) {
+    const char* fn = "kws_forward_cnn_trad_windows_f32";
+    if (!c) return KWS_EINVAL;
+    if (!d_frames || !d_logits) return fail(c, KWS_EINVAL, std::string(fn) + ": d_frames / d_logits is NULL");
+    if (R < 1 || hop_frames < 1) return fail(c, KWS_EINVAL, std::string(fn) + ": R and hop_frames must be positive");
+    if (F < IN_T) return fail(c, KWS_EINVAL, std::string(fn) + ": a recording of fewer than 99 frames has no window");
+    if (int rc = ct_model_check(c, fn)) return rc;
+    const int W = (F - IN_T) / hop_frames + 1;
+    if ((unsigned long long)R * F > (1ull << 28) || (unsigned long long)R * W > (1ull << 30))
+        return fail(c, KWS_EUNSUPPORTED, std::string(fn) + ": more than 2^28 frames or 2^30 windows in one call");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return ct_windows(c, fn, d_frames, R, F, W, hop_frames, d_logits, d_label);
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

@@ -1,6 +1,7 @@
 // The context behind the C ABI (include/kws_hip.h), the error plumbing and the device-memory helpers shared by the translation
-// units that implement it (kws_api.hip, kws_frontend.hip, kws_weights.hip, kws_ingest.hip, kws_scan.hip, kws_decide.hip,
-// kws_eval.hip, kws_resample.hip, kws_live.hip, kws_live_detect.hip, kws_*_bwd.hip), and the event bracket of a timed launch.
+// units that implement it (kws_api.hip, kws_stream.hip, kws_cnntrad.hip, kws_frontend.hip, kws_weights.hip, kws_ingest.hip,
+// kws_scan.hip, kws_ragged.hip, kws_decide.hip, kws_eval.hip, kws_resample.hip, kws_live.hip, kws_live_detect.hip, kws_*_bwd.hip),
+// the table of what the host flows need of a model, and the event bracket of a timed launch.
 #pragma once
 #include <new>
 
@@ -26,16 +27,25 @@ void stream_detect_free(kws_ctx* c);
 // the decision step behind a push, from that push's logits; nothing when unarmed.  fn: the push entry, named in the errors;
 // model_classes: the class count of the model that made the logits (the DS-CNN's or cnn-trad-fpool3's)
 int stream_detect_pushed(kws_ctx* c, const float* d_logits, const char* fn, int model_classes);
-// What the recording flows (scan_recordings, kws_scan.hip; scan_ragged_entry, kws_ragged.hip) need of a model: its readiness and
-// geometry checks in the entry's words (f names the entry), and the launch over the R * W strided 99-frame windows of a frame
-// array [R][F][10] -- logits [R * W][C] and labels [R * W] (or NULL) in window order.
-struct ScanModel {
-    int (*check)(kws_ctx* c, const std::string& f);
-    int (*launch)(kws_ctx* c, const std::string& f, const float* d_frames, int R, int F, int W, int hop_frames, float* d_logits,
-                  int32_t* d_label);
+// What the host flows need of a model.  The recording flows (scan_recordings, kws_scan.hip; scan_ragged_entry, kws_ragged.hip), the
+// fused clip entries (infer_clips, kws_api.hip) and the stream push (stream_push, kws_stream.hip) are each written once and take one
+// of these.  fn names the entry: a refusal starts with it, in that model's words, and is composed on the failing branch only.
+struct ModelOps {
+    // readiness and geometry: front end and model for the recording flows and the clip entries, the model alone for a push with logits
+    int (*scan_check)(kws_ctx* c, const char* fn);
+    int (*clip_check)(kws_ctx* c, const char* fn);
+    int (*push_check)(kws_ctx* c, const char* fn);
+    int (*classes)(const kws_ctx* c);  // of the loaded model
+    // B contiguous maps of the front end's geometry (cnn-trad-fpool3: 99 x 10 only) -> logits [B][C], labels [B] or NULL
+    int (*forward)(kws_ctx* c, const float* d_feat, int B, float* d_logits, int32_t* d_label, const char* fn);
+    // the R * W strided 99-frame windows of a frame array [R][F][10] -> logits [R * W][C], labels or NULL, in window order
+    int (*windows)(kws_ctx* c, const char* fn, const float* d_frames, int R, int F, int W, int hop_frames, float* d_logits, int32_t* d_label);
+    // the launches of a push through the feature ring: what can fail on the host, stream_enqueue_frame, the model over every stream's
+    // window.  nullptr for the DS-CNN: its product push computes the frame inside the model kernel (stream_enqueue, kws_stream.hip)
+    int (*ring_push)(kws_ctx* c, const char* fn, const int16_t* d_hop, float* d_logits, int32_t* d_label);
 };
-ScanModel scan_model_dscnn();     // kws_scan.hip: kws_dscnn_fwd_kernel, SCAN
-ScanModel scan_model_cnn_trad();  // kws_api.hip: kws_cnntrad_conv_windows_kernel + the dense kernel, in chunks
+const ModelOps& model_ops_dscnn();     // kws_api.hip
+const ModelOps& model_ops_cnn_trad();  // kws_cnntrad.hip
 }  // namespace kws
 
 using kws::FrontendParams; using kws::FrontendTables; using kws::DscnnWeights; using kws::CnnTradWeights; using kws::NFFT;
@@ -165,7 +175,8 @@ struct kws_ctx {
 int frames_for(int n_samples, int frame_len, int frame_step);  // 1 + ceil((n - L) / step), 1 for n <= L (sigproc.py:31-35)
 void set_clip_length(FrontendParams& p, int n_samples);
 int ensure_refine(kws_ctx* c, int B, int num_frames);  // the refinement worklist holds B clips of num_frames frames
-void stream_free(kws_ctx* c);                          // kws_api.hip: rings, hop counter, captured graph, smoothing and endpointer history
+hipError_t stream_enqueue_frame(kws_ctx* c, const int16_t* d_hop, bool timed);  // kws_stream.hip: the frame kernel of a multi-launch push
+void stream_free(kws_ctx* c);                          // kws_stream.hip: rings, hop counter, captured graph, smoothing and endpointer history
 // The MFCC launches of B clips read from src (const int16_t*, const float* or kws::AugmentArgs; instantiated in kws_frontend.hip).
 // recording_f32: float32 samples may take the wavefront-resident kernel (kws_frames_f32, kws_scan_f32).
 template <typename Src>
@@ -189,6 +200,11 @@ inline int fail_hip(kws_ctx* c, hipError_t e, const char* what) {
 inline int host_results_ensure(kws_ctx* c) {
     if (c->h_stream_flag && c->host_results_classes == c->mw.num_classes) return KWS_OK;
     return kws_stream_host_results(c, 1);
+}
+// The fused kernels' one geometry; `what` is the rest of the refusal, in the words of the model and the flow.
+inline int check_ref_map(kws_ctx* c, const char* fn, const char* what) {
+    if (c->fp.num_frames == kws::IN_T && c->fp.numcep == kws::IN_F) return KWS_OK;
+    return fail(c, KWS_EUNSUPPORTED, std::string(fn) + what);
 }
 inline int check_batch(kws_ctx* c, const void* in, int B, const char* fn) {
     if (!c) return KWS_EINVAL;
@@ -235,13 +251,13 @@ inline int alloc_endpoint_state(kws_ctx* c, const char* fn, size_t S, unsigned l
 // Host-built plan tables of a ragged call -> context scratch (kws_ragged.hip); may wait for the stream.
 int upload_ragged_tables(kws_ctx* c, const void* host, size_t bytes, const char* fn, const void** d_tables);
 
-// Bracket a kernel launch with events when profiling is on.
+// Bracket a kernel launch with events when profiling is on (timed = false: never, e.g. inside a stream capture).
 struct ProfScope {
     kws_ctx* c;
     int id;
     hipEvent_t stop = nullptr;
-    ProfScope(kws_ctx* c_, int id_) : c(c_), id(id_) {
-        if (!c->prof) return;
+    ProfScope(kws_ctx* c_, int id_, bool timed = true) : c(c_), id(id_) {
+        if (!c->prof || !timed) return;
         if (c->prof_seen[id]++ % (unsigned)c->prof_every != 0) return;  // sampling: events around every launch cost ~7 us of stream time each
         if (c->ev_used[id] == c->ev[id].size()) {
             kws_ctx::EvPair p{};
@@ -262,6 +278,14 @@ inline void drop_stream_graph(kws_ctx* c) {
     if (c->stream_graph) (void)hipGraphExecDestroy(c->stream_graph);
     c->stream_graph = nullptr;
     c->graph_key[0] = c->graph_key[1] = c->graph_key[2] = nullptr;
+}
+
+// ... once the stream is idle, if there is one: what a change of anything the graph holds by value does first.
+inline int retire_captured_push(kws_ctx* c) {
+    if (!c->stream_graph) return KWS_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    drop_stream_graph(c);
+    return KWS_OK;
 }
 
 // Swap a device allocation for a fresh copy of `bytes` host bytes: drain the stream (kernels may be reading the old one),
@@ -294,4 +318,8 @@ int grow_device_buffer(kws_ctx* c, T*& buf, size_t& cap, size_t need, const char
     buf = d;
     cap = need;
     return KWS_OK;
+}
+// Grow the context's float scratch (convolution outputs between two kernels of one call) to at least `need` floats.
+inline int grow_conv_ws(kws_ctx* c, size_t need, const char* fn) {
+    return grow_device_buffer(c, c->d_conv_ws, c->conv_ws_floats, need, fn, "workspace");
 }

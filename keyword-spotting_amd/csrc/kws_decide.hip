@@ -114,7 +114,7 @@ hipError_t launch_smooth_posteriors(hipStream_t s, const float* d_logits, int S,
     return hipGetLastError();
 }
 
-// The histories of the two streaming entry points below; stream_free (kws_api.hip) drops them with the streams.
+// The histories of the two streaming entry points below; stream_free (kws_stream.hip) drops them with the streams.
 void smooth_free(kws_ctx* c) {
     if (c->d_post_ring) (void)hipFree(c->d_post_ring);
     if (c->d_post_sum) (void)hipFree(c->d_post_sum);

@@ -1,7 +1,7 @@
 // The host-mirrored event queue of the live units (kws_live.hip: utterances, kws_live_detect.hip: keyword events): a step kernel
 // of ONE workgroup numbers the events of its step, writes them to a device queue and to a pinned host mirror, and raises a
 // kernel count the host spins on.  Inline functions only: the device half is the tail of both step kernels, the host half what
-// their open, release, poll and read entries do with the queue; kws_stream_wait_host (kws_api.hip) shares the bounded spin.
+// their open, release, poll and read entries do with the queue; kws_stream_wait_host (kws_stream.hip) shares the bounded spin.
 // What the two halves keep, and what every change here must keep:
 //  1. Every thread reads the counters at the top of the kernel (eq_counts); thread 0 overwrites them only behind the last
 //     barrier (eq_publish, and the unit's own words after it).

@@ -164,11 +164,7 @@ int kws_set_frontend_refine(kws_ctx* c, float log_span) {
     if (!(log_span == log_span)) return fail(c, KWS_EINVAL, "kws_set_frontend_refine: log_span is NaN");
     c->refine_span = log_span > 0.f ? log_span : 0.f;
     c->fp.refine_span = c->refine_span;
-    if (c->stream_graph) {  // a captured push holds the front-end parameters by value
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        drop_stream_graph(c);
-    }
-    return KWS_OK;
+    return retire_captured_push(c);  // a captured push holds the front-end parameters by value
 }
 
 int kws_frontend_stats(kws_ctx* c, uint64_t* frames_total, uint64_t* frames_refined, int* last_call_refined) {

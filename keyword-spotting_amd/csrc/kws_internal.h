@@ -1,4 +1,4 @@
-// Internal declarations shared by the C-ABI translation unit and the gfx950 kernels.
+// Internal declarations shared by the translation units of the C ABI (kws_ctx.h lists them) and the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -299,7 +299,6 @@ struct CnnTradWeights {
     float w2_abs, b2_max;      // the same for conv2
 };
 hipError_t cnntrad_init_device();
-hipError_t launch_cnntrad_conv(hipStream_t s, const CnnTradWeights& w, const float* d_feat, int B, float* d_conv_ws, bool f16_pair);
 hipError_t launch_cnntrad_dense(hipStream_t s, const CnnTradWeights& w, const float* d_conv_ws, int B, float* d_logits,
                                 int32_t* d_label, bool f16_pair);
 // Windows of recordings read in place (kws_cnntrad_conv_windows_kernel): window i of the call is window i % wpr of recording
@@ -312,11 +311,17 @@ struct CtWindows {
     unsigned win_floats;   // from one window to the next: hop_frames * 10
 };
 constexpr int CT_WINDOW_CHUNK = 4096;  // windows per launch pair: the workspace of kws_forward_cnn_trad_f32 at the bench batch (311 MB)
-hipError_t launch_cnntrad_conv_windows(hipStream_t s, const CnnTradWeights& w, const float* d_frames, const CtWindows& sw, int n,
-                                       float* d_conv_ws, bool f16_pair);
-// The streaming push's conv launch: stream s's window is the ring's 99 rows from ((*d_hops + 1 - frames_lag) mod 99 + 99) mod 99 on.
-hipError_t launch_cnntrad_conv_ring(hipStream_t s, const CnnTradWeights& w, const float* d_feat_ring, const int* d_hops, int frames_lag,
-                                    int S, float* d_conv_ws, bool f16_pair);
+// Where the conv kernel finds the n maps of a launch: n contiguous clips [n][99][10] (kws_cnntrad_conv_kernel), n windows of a frame
+// array [R][F][10] from windows.first on (kws_cnntrad_conv_windows_kernel), or the n streams' windows of the feature ring
+// [n][99][10] (kws_cnntrad_conv_ring_kernel): stream s's window is the ring's 99 rows from ((*hops + 1 - lag) mod 99 + 99) mod 99 on.
+struct CtSource {
+    enum Kind { CLIPS, WINDOWS, RING } kind;
+    const float* maps;
+    CtWindows windows;  // WINDOWS
+    const int* hops; int lag;  // RING: the hop counter the frame kernel has advanced, and frames_lag
+};
+// conv1 + pool + conv2 of n maps -> slots 0 .. n - 1 of d_conv_ws (n * 19008 floats, then n per-clip scales: f16-pair arithmetic only)
+hipError_t launch_cnntrad_conv(hipStream_t s, const CnnTradWeights& w, const CtSource& src, int n, float* d_conv_ws, bool f16_pair);
 
 // Standalone depthwise-separable block on an arbitrary [B, C_in, H, W] map (kws_dsblock.hip); d_ws: B*C_in*Ho*Wo floats.
 hipError_t launch_dsblock(hipStream_t s, const float* d_x, int B, int C_in, int H, int W, const float* d_dw_w, const float* d_dw_b,

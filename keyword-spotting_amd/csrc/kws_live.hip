@@ -222,7 +222,7 @@ void stream_utt_free(kws_ctx* c) {
     c->stream_utt = nullptr;
 }
 
-// The push entries' side (kws_api.hip): the check in front of a push's launches, the step behind them.
+// The push entries' side (kws_stream.hip): the check in front of a push's launches, the step behind them.
 int stream_utt_push_check(kws_ctx* c, const char* fn) {
     if (c->stream_utt && c->stream_utt->mode == 2)
         return fail(c, KWS_ESTATE, std::string(fn) + ": this utterance set was stepped by kws_stream_utt_step_i16; a push would let its two counters drift apart");

@@ -147,7 +147,7 @@ void stream_detect_free(kws_ctx* c) {
     c->stream_detect = nullptr;
 }
 
-// The push entry's side (kws_api.hip): the step behind a push's launches, from that push's logits.
+// The push entries' side (kws_stream.hip): the step behind a push's launches, from that push's logits.
 int stream_detect_pushed(kws_ctx* c, const float* d_logits, const char* fn, int model_classes) {
     StreamDetect* u = c->stream_detect;
     if (!u) return KWS_OK;

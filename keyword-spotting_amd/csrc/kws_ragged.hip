@@ -128,7 +128,7 @@ static int frames_ragged_entry(kws_ctx* c, const char* fn, const char* src, cons
 }
 
 template <typename Sample>
-static int scan_ragged_entry(kws_ctx* c, const ScanModel& m, const char* fn, const char* src, const Sample* d_pcm, int n_pcm, const int64_t* start, const int32_t* len,
+static int scan_ragged_entry(kws_ctx* c, const ModelOps& m, const char* fn, const char* src, const Sample* d_pcm, int n_pcm, const int64_t* start, const int32_t* len,
                              int R, int hop_frames, float* d_logits, int32_t* d_label, float* d_feat_out) {
     const std::string f(fn);
     if (!c) return KWS_EINVAL;
@@ -136,7 +136,7 @@ static int scan_ragged_entry(kws_ctx* c, const ScanModel& m, const char* fn, con
     if (rc) return rc;
     if (!d_logits) return fail(c, KWS_EINVAL, f + ": d_logits is NULL");
     if (hop_frames < 1) return fail(c, KWS_EINVAL, f + ": hop_frames must be positive");
-    if ((rc = m.check(c, f))) return rc;
+    if ((rc = m.scan_check(c, fn))) return rc;
     const int T = c->fp.num_frames;
     std::vector<int32_t> windows(R);
     std::vector<int32_t> frame_off(R + 1);
@@ -158,7 +158,7 @@ static int scan_ragged_entry(kws_ctx* c, const ScanModel& m, const char* fn, con
     if (rc) return rc;
     if (any_window == 0) return KWS_OK;  // every recording is shorter than a window: the frames are all there is
     // the packed frame array as ONE recording of F_pack frames: window win_off[r] + w is window w of recording r
-    return m.launch(c, f, feat, 1, (int)F_pack, W_pack, hop_frames, d_logits, d_label);
+    return m.windows(c, fn, feat, 1, (int)F_pack, W_pack, hop_frames, d_logits, d_label);
 }
 
 #pragma GCC visibility push(default)
@@ -203,21 +203,21 @@ int kws_frames_ragged_f32(kws_ctx* c, const float* d_wav, int n_wav, const int64
 int kws_scan_ragged_i16(kws_ctx* c, const int16_t* d_pcm, int n_pcm, const int64_t* start, const int32_t* len, int R, int hop_frames,
                         float* d_logits, int32_t* d_label, float* d_feat_out) {
     KWS_GUARD_BEGIN
-    return scan_ragged_entry(c, scan_model_dscnn(), "kws_scan_ragged_i16", "pcm", d_pcm, n_pcm, start, len, R, hop_frames, d_logits, d_label, d_feat_out);
+    return scan_ragged_entry(c, model_ops_dscnn(), "kws_scan_ragged_i16", "pcm", d_pcm, n_pcm, start, len, R, hop_frames, d_logits, d_label, d_feat_out);
     KWS_GUARD_END(c, "kws_scan_ragged_i16")
 }
 
 int kws_scan_ragged_f32(kws_ctx* c, const float* d_wav, int n_wav, const int64_t* start, const int32_t* len, int R, int hop_frames,
                         float* d_logits, int32_t* d_label, float* d_feat_out) {
     KWS_GUARD_BEGIN
-    return scan_ragged_entry(c, scan_model_dscnn(), "kws_scan_ragged_f32", "wav", d_wav, n_wav, start, len, R, hop_frames, d_logits, d_label, d_feat_out);
+    return scan_ragged_entry(c, model_ops_dscnn(), "kws_scan_ragged_f32", "wav", d_wav, n_wav, start, len, R, hop_frames, d_logits, d_label, d_feat_out);
     KWS_GUARD_END(c, "kws_scan_ragged_f32")
 }
 
 int kws_scan_ragged_cnn_trad_i16(kws_ctx* c, const int16_t* d_pcm, int n_pcm, const int64_t* start, const int32_t* len, int R, int hop_frames,
                                  float* d_logits, int32_t* d_label, float* d_feat_out) {
     KWS_GUARD_BEGIN
-    return scan_ragged_entry(c, scan_model_cnn_trad(), "kws_scan_ragged_cnn_trad_i16", "pcm", d_pcm, n_pcm, start, len, R, hop_frames, d_logits, d_label,
+    return scan_ragged_entry(c, model_ops_cnn_trad(), "kws_scan_ragged_cnn_trad_i16", "pcm", d_pcm, n_pcm, start, len, R, hop_frames, d_logits, d_label,
                              d_feat_out);
     KWS_GUARD_END(c, "kws_scan_ragged_cnn_trad_i16")
 }
@@ -225,7 +225,7 @@ int kws_scan_ragged_cnn_trad_i16(kws_ctx* c, const int16_t* d_pcm, int n_pcm, co
 int kws_scan_ragged_cnn_trad_f32(kws_ctx* c, const float* d_wav, int n_wav, const int64_t* start, const int32_t* len, int R, int hop_frames,
                                  float* d_logits, int32_t* d_label, float* d_feat_out) {
     KWS_GUARD_BEGIN
-    return scan_ragged_entry(c, scan_model_cnn_trad(), "kws_scan_ragged_cnn_trad_f32", "wav", d_wav, n_wav, start, len, R, hop_frames, d_logits, d_label,
+    return scan_ragged_entry(c, model_ops_cnn_trad(), "kws_scan_ragged_cnn_trad_f32", "wav", d_wav, n_wav, start, len, R, hop_frames, d_logits, d_label,
                              d_feat_out);
     KWS_GUARD_END(c, "kws_scan_ragged_cnn_trad_f32")
 }

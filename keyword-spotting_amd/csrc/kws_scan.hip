@@ -129,37 +129,15 @@ hipError_t launch_scan_detect(hipStream_t s, const float* d_prob, int R, int W, 
 
 }  // namespace kws
 
-// The DS-CNN behind the recording flows (ScanModel, kws_ctx.h): its checks, and kws_dscnn_fwd_kernel (SCAN) over the strided windows.
-static int dscnn_scan_check(kws_ctx* c, const std::string& f) {
-    if (!c->fe_ready || !c->model_ready) return fail(c, KWS_ESTATE, f + ": front end or model not configured");
-    if (c->fp.num_frames != IN_T || c->fp.numcep != IN_F)
-        return fail(c, KWS_EUNSUPPORTED, f + ": the strided DS-CNN kernel is built for windows of 99 x 10 features");
-    if (c->mw.in_channels != 1) return fail(c, KWS_EUNSUPPORTED, f + ": the MFCC front end yields one channel; the model was loaded with more");
-    if (c->pw_math != KWS_PW_PAIR_F16 && c->pw_math != KWS_PW_SPLIT_BF16)
-        return fail(c, KWS_EUNSUPPORTED, f + ": needs KWS_PW_PAIR_F16 or KWS_PW_SPLIT_BF16");
-    return KWS_OK;
-}
-static int dscnn_scan_launch(kws_ctx* c, const std::string&, const float* d_frames, int R, int F, int W, int hop_frames, float* d_logits,
-                             int32_t* d_label) {
-    const ScanWindows sw = {(unsigned)W, W == 1 ? 0xffffffffu : (unsigned)((1ull << 32) / (unsigned)W), (unsigned)F * (unsigned)IN_F,
-                            (unsigned)hop_frames * (unsigned)IN_F};
-    ProfScope ps(c, KWS_K_DSCNN);
-    HIP_TRY(c, launch_dscnn_scan(c->stream, c->mw, d_frames, R * W, d_logits, d_label, c->pw_math, c->n_cu, sw));
-    return KWS_OK;
-}
-namespace kws {
-ScanModel scan_model_dscnn() { return {dscnn_scan_check, dscnn_scan_launch}; }
-}  // namespace kws
-
 // kws_scan_i16 / kws_scan_f32 and their cnn-trad-fpool3 twins: the same checks, limits and launches over int16 PCM or float32
 // samples; f names the entry in the error text, src_name its source pointer, m is the model that classifies the windows.
 template <typename Sample>
-static int scan_recordings(kws_ctx* c, const ScanModel& m, const std::string& f, const char* src_name, const Sample* d_pcm, int R, int n_total,
+static int scan_recordings(kws_ctx* c, const ModelOps& m, const std::string& f, const char* src_name, const Sample* d_pcm, int R, int n_total,
                            int hop_frames, float* d_logits, int32_t* d_label, float* d_feat_out) {
     if (!c) return KWS_EINVAL;
     if (!d_pcm || !d_logits) return fail(c, KWS_EINVAL, f + ": " + src_name + " / d_logits is NULL");
     if (R < 1 || n_total < 1 || hop_frames < 1) return fail(c, KWS_EINVAL, f + ": R, n_total and hop_frames must be positive");
-    if (int rc = m.check(c, f)) return rc;
+    if (int rc = m.scan_check(c, f.c_str())) return rc;
     if (n_total > (1 << 30)) return fail(c, KWS_EUNSUPPORTED, f + ": more than 2^30 samples per recording");
     FrontendParams p = c->fp;  // the context's geometry and arithmetic; the recording is one clip of n_total samples
     set_clip_length(p, n_total);
@@ -178,7 +156,7 @@ static int scan_recordings(kws_ctx* c, const ScanModel& m, const std::string& f,
     // the refinement's grid: the batch in one-second clips (R * F <= 2^28 was checked above)
     int rc = run_frontend(c, p, d_pcm, R, feat, (int)((unsigned long long)R * F / T + 1), /*recording_f32=*/true);
     if (rc) return rc;
-    return m.launch(c, f, feat, R, F, W, hop_frames, d_logits, d_label);
+    return m.windows(c, f.c_str(), feat, R, F, W, hop_frames, d_logits, d_label);
 }
 
 #pragma GCC visibility push(default)
@@ -196,28 +174,28 @@ int kws_host_scan_shape(int n_total, int frame_len, int frame_step, int window_f
 int kws_scan_i16(kws_ctx* c, const int16_t* d_pcm, int R, int n_total, int hop_frames, float* d_logits, int32_t* d_label,
                  float* d_feat_out) {
     KWS_GUARD_BEGIN
-    return scan_recordings(c, scan_model_dscnn(), "kws_scan_i16", "d_pcm", d_pcm, R, n_total, hop_frames, d_logits, d_label, d_feat_out);
+    return scan_recordings(c, model_ops_dscnn(), "kws_scan_i16", "d_pcm", d_pcm, R, n_total, hop_frames, d_logits, d_label, d_feat_out);
     KWS_GUARD_END(c, "kws_scan_i16")
 }
 
 int kws_scan_f32(kws_ctx* c, const float* d_wav, int R, int n_total, int hop_frames, float* d_logits, int32_t* d_label,
                  float* d_feat_out) {
     KWS_GUARD_BEGIN
-    return scan_recordings(c, scan_model_dscnn(), "kws_scan_f32", "d_wav", d_wav, R, n_total, hop_frames, d_logits, d_label, d_feat_out);
+    return scan_recordings(c, model_ops_dscnn(), "kws_scan_f32", "d_wav", d_wav, R, n_total, hop_frames, d_logits, d_label, d_feat_out);
     KWS_GUARD_END(c, "kws_scan_f32")
 }
 
 int kws_scan_cnn_trad_i16(kws_ctx* c, const int16_t* d_pcm, int R, int n_total, int hop_frames, float* d_logits, int32_t* d_label,
                           float* d_feat_out) {
     KWS_GUARD_BEGIN
-    return scan_recordings(c, scan_model_cnn_trad(), "kws_scan_cnn_trad_i16", "d_pcm", d_pcm, R, n_total, hop_frames, d_logits, d_label, d_feat_out);
+    return scan_recordings(c, model_ops_cnn_trad(), "kws_scan_cnn_trad_i16", "d_pcm", d_pcm, R, n_total, hop_frames, d_logits, d_label, d_feat_out);
     KWS_GUARD_END(c, "kws_scan_cnn_trad_i16")
 }
 
 int kws_scan_cnn_trad_f32(kws_ctx* c, const float* d_wav, int R, int n_total, int hop_frames, float* d_logits, int32_t* d_label,
                           float* d_feat_out) {
     KWS_GUARD_BEGIN
-    return scan_recordings(c, scan_model_cnn_trad(), "kws_scan_cnn_trad_f32", "d_wav", d_wav, R, n_total, hop_frames, d_logits, d_label, d_feat_out);
+    return scan_recordings(c, model_ops_cnn_trad(), "kws_scan_cnn_trad_f32", "d_wav", d_wav, R, n_total, hop_frames, d_logits, d_label, d_feat_out);
     KWS_GUARD_END(c, "kws_scan_cnn_trad_f32")
 }
 
