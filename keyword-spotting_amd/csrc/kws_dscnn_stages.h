@@ -12,49 +12,53 @@
 namespace kws {
 namespace {
 
+// The depthwise table is interleaved in channel PAIRS: a record is ten (channel c, channel c + 1) pairs -- nine taps and the
+// bias -- in 96 bytes.  The record is the same for all 32 lanes of a half-wave, and a ds_read_b128 costs its four LDS-array
+// cycles whether or not the addresses coincide, so no lane reads the whole record: lane l reads the ONE pair at
+// 8 * (l & 15) bytes into it (dw_row_offset), the 16 lanes of a row then hold the record between them, and every tap reaches
+// its multiply-add through row_newbcast.  One ds_read_b64 and two registers per step pair where whole records took five
+// ds_read_b128 and twenty.  Lanes 10 - 15 of a row read the pad and the head of the next record (the last record: the head of
+// the pointwise bias); those values are never selected.  (`tools/experiments/dscnn_unit_ablations.patch`: without the weight
+// reloads the kernel runs 9.5 % faster; DESIGN 4.2, "Depthwise weights by row broadcast".)
+struct DwPair {
+    float2 w;  // in lane l: element l & 15 of (w0 .. w8, b, pad ...), as the (channel c, channel c + 1) pair
+};
+static_assert((2 * 768 - 24) * 4 + 8 * 15 + 8 <= (OFF_PWB + 2 * 64 - OFF_DWTAB) * 4,
+              "a row's read of the last record of the second table buffer ends inside the pointwise biases that follow it");
+__device__ __forceinline__ int dw_row_offset(int lane) { return 2 * (lane & 15); }  // in floats
 // Depthwise 3x3 (+bias) at this lane's column from its three own-column inputs: nine multiply-adds and two
 // fused DPP multiply-adds that pull the neighbouring lanes' column sums across the wavefront (0 shifted in at the
-// ends).  Written as one asm block so that (a) the shift and the multiply-add are one instruction each
-// (v_fmac_f32_dpp; the compiler emits v_mov_b32_dpp + v_fmac), and (b) each DPP source is written three
-// instructions before it is read -- the VALU-write -> DPP-read hazard needs two wait states and the hazard
-// recognizer does not look inside inline asm.  w0..w8 row-major taps, b bias.  TO_MFMA: the result is fed straight
-// to a matrix-core instruction (f32 path), which needs two more wait states after the last VALU write.
+// ends).  w: one channel's element of the row-resident record (DwPair); tap k is row_newbcast:k, the bias row_newbcast:9
+// (v_mov_b32_dpp into c, then c = w1 * up + c in one v_fmac: the fused w1 * up + b).  Written as one asm block so that (a) the
+// shift or broadcast and the multiply-add are one instruction each (v_fmac_f32_dpp; the compiler emits v_mov_b32_dpp +
+// v_fmac), and (b) each DPP source a VALU writes (to_right, to_left) is written three instructions before it is read -- the
+// VALU-write -> DPP-read hazard needs two wait states and the hazard recognizer does not look inside inline asm; w comes
+// from an LDS read, which the compiler waits for.  All 64 lanes must be active: a source lane that EXEC disables reads as
+// invalid.  TO_MFMA: the result is fed straight to a matrix-core instruction (f32 path), which needs two more wait states
+// after the last VALU write.
 template <bool TO_MFMA = false>
-__device__ __forceinline__ float stencil3x3(float w0, float w1, float w2, float w3, float w4, float w5, float w6,
-                                            float w7, float w8, float b, float up, float mid, float dn, float mask_l,
-                                            float mask_r) {
+__device__ __forceinline__ float stencil3x3(float w, float up, float mid, float dn, float mask_l, float mask_r) {
     float c, to_right, to_left;
-    asm("v_mul_f32 %1, %3, %13\n\t"          // to_right = w0*up   (what lane+1 needs: its (.., -1) taps)
-        "v_mul_f32 %2, %5, %13\n\t"          // to_left  = w2*up   (what lane-1 needs: its (.., +1) taps)
-        "v_fma_f32 %0, %4, %13, %12\n\t"     // c = w1*up + b
-        "v_fmac_f32 %1, %6, %14\n\t"         // to_right += w3*mid
-        "v_fmac_f32 %2, %8, %14\n\t"         // to_left  += w5*mid
-        "v_fmac_f32 %0, %7, %14\n\t"         // c += w4*mid
-        "v_fmac_f32 %1, %9, %15\n\t"         // to_right += w6*dn
-        "v_fmac_f32 %2, %11, %15\n\t"        // to_left  += w8*dn
-        "v_fmac_f32 %0, %10, %15\n\t"        // c += w7*dn
-        "v_fmac_f32_dpp %0, %1, %16 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"   // c += to_right[lane-1]*mask_l
-        "v_fmac_f32_dpp %0, %2, %17 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"        // c += to_left[lane+1]*mask_r
+    asm("v_mov_b32_dpp %0, %3 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"        // c = b
+        "v_mul_f32_dpp %1, %3, %4 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"    // to_right = w0*up   (what lane+1 needs: its (.., -1) taps)
+        "v_mul_f32_dpp %2, %3, %4 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"    // to_left  = w2*up   (what lane-1 needs: its (.., +1) taps)
+        "v_fmac_f32_dpp %0, %3, %4 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"   // c = w1*up + b
+        "v_fmac_f32_dpp %1, %3, %5 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"   // to_right += w3*mid
+        "v_fmac_f32_dpp %2, %3, %5 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"   // to_left  += w5*mid
+        "v_fmac_f32_dpp %0, %3, %5 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"   // c += w4*mid
+        "v_fmac_f32_dpp %1, %3, %6 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"   // to_right += w6*dn
+        "v_fmac_f32_dpp %2, %3, %6 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"   // to_left  += w8*dn
+        "v_fmac_f32_dpp %0, %3, %6 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"   // c += w7*dn
+        "v_fmac_f32_dpp %0, %1, %7 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"   // c += to_right[lane-1]*mask_l
+        "v_fmac_f32_dpp %0, %2, %8 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"        // c += to_left[lane+1]*mask_r
         : "=&v"(c), "=&v"(to_right), "=&v"(to_left)
-        : "v"(w0), "v"(w1), "v"(w2), "v"(w3), "v"(w4), "v"(w5), "v"(w6), "v"(w7), "v"(w8), "v"(b), "v"(up), "v"(mid),
-          "v"(dn), "v"(mask_l), "v"(mask_r));
+        : "v"(w), "v"(up), "v"(mid), "v"(dn), "v"(mask_l), "v"(mask_r));
     if constexpr (TO_MFMA) asm volatile("s_nop 1" : "+v"(c));
     return c;
 }
-// The depthwise table is interleaved in channel PAIRS: ten (channel c, channel c + 1) pairs -- nine taps and the bias -- are 80
-// bytes, FIVE ds_read_b128 for two stencil steps where a table per channel took six.  (A wavefront's issue slots are what
-// this kernel is made of; `tools/experiments/dscnn_unit_ablations.patch`: without the weight reloads it runs 9.5 % faster.)
-struct DwPair {
-    float4 l[5];  // (w0, w1) (w2, w3) (w4, w5) (w6, w7) (w8, b), each a (channel c, channel c + 1) pair
-};
 template <bool TO_MFMA, int E>  // E: which channel of the pair
 __device__ __forceinline__ float stencil3x3_of_pair(const DwPair& w, float up, float mid, float dn, float mask_l, float mask_r) {
-    if constexpr (E == 0)
-        return stencil3x3<TO_MFMA>(w.l[0].x, w.l[0].z, w.l[1].x, w.l[1].z, w.l[2].x, w.l[2].z, w.l[3].x, w.l[3].z, w.l[4].x, w.l[4].z, up, mid, dn,
-                                   mask_l, mask_r);
-    else
-        return stencil3x3<TO_MFMA>(w.l[0].y, w.l[0].w, w.l[1].y, w.l[1].w, w.l[2].y, w.l[2].w, w.l[3].y, w.l[3].w, w.l[4].y, w.l[4].w, up, mid, dn,
-                                   mask_l, mask_r);
+    return stencil3x3<TO_MFMA>(E == 0 ? w.w.x : w.w.y, up, mid, dn, mask_l, mask_r);
 }
 // Sum over each 32-lane half of the wavefront without touching LDS: inclusive scan inside the 16-lane rows
 // (row_shr 1,2,4,8), then row 0 -> row 1 and row 2 -> row 3 (row_bcast:15).  Lanes 31 and 63 hold the totals.
@@ -554,7 +558,7 @@ __device__ __forceinline__ void leftover_partial_unit(float* lds, int lane, int 
     using L = Leftover<N>;
     const int half = lane >> 5, col = lane & 31;
     const float* dwtab = lds + OFF_DWTAB + G::BUF * 768;
-    const float4* dwt4 = reinterpret_cast<const float4*>(dwtab) + half * 24;
+    const float* dwrow = dwtab + half * 96 + dw_row_offset(lane);  // (channel pair 4 * half; this lane's element of a record)
     bool valid;
     float mask_l, mask_r;
     int ta[3];  // own-column tap addresses (rows h-1, h, h+1) of channel pair 8 * half, as float indices into lds
@@ -588,8 +592,7 @@ __device__ __forceinline__ void leftover_partial_unit(float* lds, int lane, int 
         const float2 mid = *reinterpret_cast<const float2*>(lds + ta[1] + o);
         const float2 dn = *reinterpret_cast<const float2*>(lds + ta[2] + o);
         DwPair wp;
-#pragma unroll
-        for (int i = 0; i < 5; ++i) wp.l[i] = dwt4[(cs >> 1) * 6 + i];
+        wp.w = *reinterpret_cast<const float2*>(dwrow + (cs >> 1) * 24);
         y[j] = stencil3x3_of_pair<false, 0>(wp, up.x, mid.x, dn.x, mask_l, mask_r);
         y[j + 1] = stencil3x3_of_pair<false, 1>(wp, up.y, mid.y, dn.y, mask_l, mask_r);
     }
@@ -740,7 +743,7 @@ __device__ __forceinline__ void block_phase(const DscnnWeights& w, float* lds, i
     // accumulator rows 4q..4q+3 of tile ct are output channels ct*32 + 8q + 4*half + (0..3): one float4
     const float4* bias4 = reinterpret_cast<const float4*>(pwb) + half;
     // lane (column, half) walks the input channels 16m + 8*half + j (m = 0..3, j = 0..7) in 32 steps s = 8m + j
-    const float4* dwt4 = reinterpret_cast<const float4*>(dwtab) + half * 24;  // (channel pair 4 * half; six float4 per pair, five of them read)
+    const float* dwrow = dwtab + half * 96 + dw_row_offset(lane);  // (channel pair 4 * half; this lane's element of a record of 24 floats)
     float psum[2][16];
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
@@ -807,11 +810,10 @@ __device__ __forceinline__ void block_phase(const DscnnWeights& w, float* lds, i
             }
             tp.mid = *reinterpret_cast<const float2*>(lds + ta[1] + o);
         };
-        // the depthwise weights of the step pair's two channels: five 16-byte reads (DwPair)
+        // the depthwise weights of the step pair's two channels: one 8-byte read, a row of lanes holds the record (DwPair)
         auto wts_pair_load = [&](int sp, DwPair& wp) {
             const int cs = cs_of(2 * sp);
-#pragma unroll
-            for (int i = 0; i < 5; ++i) wp.l[i] = dwt4[(cs >> 1) * 6 + i];
+            wp.w = *reinterpret_cast<const float2*>(dwrow + (cs >> 1) * 24);
         };
         // depthwise 3x3 (+bias) of step 2sp + odd at this lane's column -> one MFMA B operand element
         auto dw_eval = [&](const DwPair& wp, const TapPair& tq, auto odd) -> float {
