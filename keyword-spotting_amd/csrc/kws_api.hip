@@ -29,9 +29,9 @@ static int forward_impl(kws_ctx* c, const float* d_feat, int B, float* d_logits,
             return fail(c, KWS_EUNSUPPORTED, std::string(fn) + ": input_channels > 1 runs on the product kernels only");
         rc = grow_conv_ws(c, (size_t)B * 64 * 141, fn);
         if (rc) return rc;
-        HIP_TRY(c, launch_conv1_general(c->stream, d_feat, B, c->mw.in_channels, c->mw.c1_general, c->mw.c1_b, c->d_conv_ws));
+        HIP_TRY(c, launch_conv1_general(c->stream, d_feat, B, c->mw.in_channels, c->mw.c1_general, c->mw.c1_b, c->d_conv_ws.get()));
         ProfScope ps(c, KWS_K_DSCNN);
-        HIP_TRY(c, launch_dscnn(c->stream, c->mw, c->d_conv_ws, B, d_logits, d_label, nullptr, mode, nullptr, nullptr, true));
+        HIP_TRY(c, launch_dscnn(c->stream, c->mw, c->d_conv_ws.get(), B, d_logits, d_label, nullptr, mode, nullptr, nullptr, true));
         return KWS_OK;
     }
     ProfScope ps(c, KWS_K_DSCNN);
@@ -59,8 +59,8 @@ static int forward_map_impl(kws_ctx* c, const float* d_feat, int B, int T, int F
     const int chunk = B < COMPOSED_MAX_CLIPS ? B : COMPOSED_MAX_CLIPS;     // a bounded workspace
     rc = grow_conv_ws(c, (size_t)chunk * (2 * per_clip_max + dw_max), fn);
     if (rc) return rc;
-    float* bufs[2] = {c->d_conv_ws, c->d_conv_ws + (size_t)chunk * per_clip_max};
-    float* dw_ws = c->d_conv_ws + 2 * (size_t)chunk * per_clip_max;
+    float* bufs[2] = {c->d_conv_ws.get(), c->d_conv_ws.get() + (size_t)chunk * per_clip_max};
+    float* dw_ws = c->d_conv_ws.get() + 2 * (size_t)chunk * per_clip_max;
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int nb = B - b0 < chunk ? B - b0 : chunk;
         // the stages ping-pong between the two buffers; the diagnostics entry keeps them in d_layers instead, stage-major with the
@@ -130,8 +130,8 @@ static int infer_clips(kws_ctx* c, const ModelOps& m, const char* fn, int (*mfcc
     if (rc) return rc;
     if ((rc = m.clip_check(c, fn))) return rc;
     if ((rc = kws_reserve(c, B))) return rc;
-    if ((rc = mfcc(c, d_wav, B, c->d_feat_ws))) return rc;
-    return m.forward(c, c->d_feat_ws, B, d_logits, d_label, forward_fn ? forward_fn : fn);
+    if ((rc = mfcc(c, d_wav, B, c->d_feat_ws.get()))) return rc;
+    return m.forward(c, c->d_feat_ws.get(), B, d_logits, d_label, forward_fn ? forward_fn : fn);
 }
 
 #pragma GCC visibility push(default)
@@ -191,26 +191,16 @@ void kws_destroy(kws_ctx* c) {
             (void)hipEventDestroy(p.a);
             (void)hipEventDestroy(p.b);
         }
-    if (c->d_fe) (void)hipFree(c->d_fe);
-    if (c->d_spec_tw64) (void)hipFree(c->d_spec_tw64);
-    if (c->d_refine) (void)hipFree(c->d_refine);
-    if (c->d_model) (void)hipFree(c->d_model);
-    if (c->d_cnntrad) (void)hipFree(c->d_cnntrad);
-    if (c->d_ct_stats) (void)hipFree(c->d_ct_stats);
-    if (c->d_ds_stats) (void)hipFree(c->d_ds_stats);
-    if (c->d_conv_ws) (void)hipFree(c->d_conv_ws);
-    if (c->d_train_ws) (void)hipFree(c->d_train_ws);
-    if (c->d_feat_ws) (void)hipFree(c->d_feat_ws);
-    if (c->d_scan_ws) (void)hipFree(c->d_scan_ws);
-    if (c->d_ragged) (void)hipFree(c->d_ragged);
-    stream_free(c);     // rings, hop counter, captured graph, smoothing and endpointer history (kws_decide.hip)
-    eval_free(c);        // evaluation accumulators (kws_eval.hip)
+    stream_free(c);     // the stream set and what is armed on it: counters, captured graph, live utterances and events
+    eval_free(c);        // evaluation state (kws_eval.hip)
     stream_resample_free(c);  // streaming resampler: history, hop buffer, pinned input (kws_resample.hip)
     resample_free(c);    // tap tables of the rate pairs (kws_resample.hip)
     ingest_free(c);      // staging rings, copy streams, pack threads
-    if (c->order_ev) (void)hipEventDestroy(c->order_ev);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    const hipEvent_t order_ev = c->order_ev;
+    const hipStream_t own_stream = c->own_stream;
+    delete c;            // every buffer the context still owns goes here: the device is current, the stream drained and still alive
+    if (order_ev) (void)hipEventDestroy(order_ev);
+    if (own_stream) (void)hipStreamDestroy(own_stream);
 }
 
 // The workspaces and tables of a context are shared by everything it enqueues, so work enqueued on the new stream must
@@ -308,7 +298,7 @@ int kws_dsblock_forward_f32(kws_ctx* c, const float* d_x, int B, int C_in, int H
     rc = grow_conv_ws(c, (size_t)B * C_in * Ho * Wo, "kws_dsblock_forward_f32");
     if (rc) return rc;
     HIP_TRY(c, launch_dsblock(c->stream, d_x, B, C_in, H, W, d_dw_w, d_dw_b, d_pw_w, d_pw_b, C_out, kernel_size, stride, padding,
-                              c->d_conv_ws, d_out));
+                              c->d_conv_ws.get(), d_out));
     return KWS_OK;
 }
 

@@ -305,11 +305,11 @@ static int ct_conv_dense(kws_ctx* c, const char* fn, const CtSource& src, int n,
     const bool pair = c->cnntrad_math == KWS_CT_F16_PAIR;
     {
         ProfScope ps(c, KWS_K_CNNTRAD_CONV);
-        HIP_TRY(c, launch_cnntrad_conv(c->stream, c->tw, src, n, c->d_conv_ws, pair));
+        HIP_TRY(c, launch_cnntrad_conv(c->stream, c->tw, src, n, c->d_conv_ws.get(), pair));
     }
     {
         ProfScope ps(c, KWS_K_CNNTRAD_DENSE);
-        HIP_TRY(c, launch_cnntrad_dense(c->stream, c->tw, c->d_conv_ws, n, d_logits, d_label, pair));
+        HIP_TRY(c, launch_cnntrad_dense(c->stream, c->tw, c->d_conv_ws.get(), n, d_logits, d_label, pair));
     }
     return KWS_OK;
 }
@@ -358,7 +358,7 @@ static int ct_windows(kws_ctx* c, const char* fn, const float* d_frames, int R, 
 static int ct_ring_push(kws_ctx* c, const char* fn, const int16_t* d_hop, float* d_logits, int32_t* d_label) {
     if (int rc = ct_reserve(c, fn, c->n_streams)) return rc;
     HIP_TRY(c, stream_enqueue_frame(c, d_hop, true));
-    return ct_conv_dense(c, fn, {CtSource::RING, c->d_feat_ring, {}, c->d_hops, frames_lag(c->fp)}, c->n_streams, d_logits, d_label);
+    return ct_conv_dense(c, fn, {CtSource::RING, c->d_feat_ring.get(), {}, c->d_hops.get(), frames_lag(c->fp)}, c->n_streams, d_logits, d_label);
 }
 
 static const ModelOps kCnnTradOps = {ct_scan_check, ct_scan_check, ct_push_check, ct_classes, ct_forward, ct_windows, ct_ring_push};
@@ -380,9 +380,9 @@ int kws_forward_cnn_trad_debug_f32(kws_ctx* c, const float* d_feat, int B, float
     int rc = ct_forward(c, d_feat, B, d_logits, d_label, fn);
     if (rc) return rc;
     const size_t n = (size_t)B * 64 * 297;
-    HIP_TRY(c, hipMemcpyAsync(d_conv2, c->d_conv_ws, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_conv2, c->d_conv_ws.get(), sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
     if (d_clip_scale && c->cnntrad_math == KWS_CT_F16_PAIR)
-        HIP_TRY(c, hipMemcpyAsync(d_clip_scale, c->d_conv_ws + n, sizeof(float) * (size_t)B, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d_clip_scale, c->d_conv_ws.get() + n, sizeof(float) * (size_t)B, hipMemcpyDeviceToDevice, c->stream));
     return KWS_OK;
 }
 

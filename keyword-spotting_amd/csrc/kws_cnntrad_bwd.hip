@@ -606,9 +606,9 @@ int run(kws_ctx* c, const char* fn, const float* d_feat, int B, const float* d_d
     Carver need(chunk);
     carve(need);
     // the training workspace is shared with kws_dscnn_backward_f32
-    int rc = grow_device_buffer(c, c->d_train_ws, c->train_ws_floats, need.floats(), fn, "workspace");
+    int rc = grow_device_buffer(c, c->d_train_ws, need.floats(), fn, "workspace");
     if (rc) return rc;
-    Carver ws(chunk, c->d_train_ws);
+    Carver ws(chunk, c->d_train_ws.get());
     carve(ws);
     const float* raw = c->ct_raw;
     hipStream_t s = c->stream;

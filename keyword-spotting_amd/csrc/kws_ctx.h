@@ -2,9 +2,14 @@
 // units that implement it (kws_api.hip, kws_stream.hip, kws_cnntrad.hip, kws_frontend.hip, kws_weights.hip, kws_ingest.hip,
 // kws_scan.hip, kws_ragged.hip, kws_decide.hip, kws_eval.hip, kws_resample.hip, kws_live.hip, kws_live_detect.hip, kws_*_bwd.hip),
 // the table of what the host flows need of a model, and the event bracket of a timed launch.
+// Memory: every device or pinned allocation of the context is a DeviceBuffer / PinnedBuffer member (kws_buffer.h) of kws_ctx or of
+// a sub-state the context points to, and is freed by that member's destructor.  The *_free functions below reset what is not
+// memory (counters, modes, the captured graph, threads and streams) and delete their sub-state; nothing frees a buffer by name.
 #pragma once
+#include <memory>
 #include <new>
 
+#include "kws_buffer.h"
 #include "kws_endpoint_dev.h"
 #include "kws_internal.h"
 
@@ -49,7 +54,10 @@ const ModelOps& model_ops_cnn_trad();  // kws_cnntrad.hip
 }  // namespace kws
 
 using kws::FrontendParams; using kws::FrontendTables; using kws::DscnnWeights; using kws::CnnTradWeights; using kws::NFFT;
+using kws::DeviceBuffer; using kws::PinnedBuffer;
 
+// The buffers below are freed when the context is deleted: kws_destroy does that with the device current and the stream drained,
+// and destroys own_stream only afterwards.
 struct kws_ctx {
     int device = 0;
     int n_cu = 0;                   // compute units of the device (hipDeviceProp_t::multiProcessorCount): the persistent DS-CNN grid
@@ -66,62 +74,58 @@ struct kws_ctx {
     bool fe_ref_geometry = false; // frame length, hop, filters and cepstra are the reference's: int16 PCM may take kws_mfcc_i16_ref_kernel
     int fe_route = KWS_FE_ROUTE_AUTO;  // kws_set_frontend_route (diagnostics): KWS_FE_ROUTE_GENERIC keeps such calls on the generic kernel
     int fe_math = KWS_FE_F32;     // requested arithmetic (kws_set_frontend_math); geometries without a fast kernel run in float64 anyway
-    void* d_fe = nullptr;  // one allocation holding all front-end tables
+    DeviceBuffer<unsigned char> d_fe;  // one allocation holding all front-end tables
     FrontendTables ft{};
-    double* d_spec_tw64 = nullptr;  // float64 twiddles of kws_spec_f32's last transform length
+    DeviceBuffer<double> d_spec_tw64;  // float64 twiddles of kws_spec_f32's last transform length
     int spec_nfft = 0;
     // selective float64 refinement of the float32 front end (kws_set_frontend_refine): worklist + counters
     float refine_span = KWS_FE_REFINE_SPAN_DEFAULT;
-    int* d_refine = nullptr;          // int[8] counters followed by the list, one allocation
+    DeviceBuffer<int> d_refine;       // int[8] counters followed by the list, one allocation
     int refine_cap = 0;               // frames the list holds
     unsigned long long frames_seen = 0;  // frames through the float32 kernels since kws_create
 
     // model
-    float* d_model = nullptr;
+    DeviceBuffer<float> d_model;
     DscnnWeights mw{};
     bool model_ready = false;
-    size_t ds_image_words = 0;        // size of d_model (kws_load_dscnn_device refreshes it in place when the size matches)
-    void* d_ds_stats = nullptr;       // kws_load_dscnn_device: the weight statistics read back to the host
+    size_t ds_image_words = 0;        // image words in d_model, without the unit table behind them (kws_load_dscnn_device refreshes
+                                      // the image in place when this matches)
+    DeviceBuffer<unsigned char> d_ds_stats;  // kws_load_dscnn_device: the weight statistics read back to the host
     int pw_math = KWS_PW_PAIR_F16;    // kernel variant of the product entry points
     // cnn-trad-fpool3
-    void* d_cnntrad = nullptr;
+    DeviceBuffer<uint32_t> d_cnntrad;
     CnnTradWeights tw{};
     bool cnntrad_ready = false;
     int cnntrad_math = KWS_CT_F16_PAIR;
     const float* ct_raw = nullptr;  // the loaded blob as float32 (state_dict layouts), inside d_cnntrad: kws_cnn_trad_backward_f32's weights
     size_t ct_image_words = 0;      // size of d_cnntrad (kws_load_cnn_trad_device refreshes it in place when the size matches)
-    float* d_ct_stats = nullptr;    // kws_load_cnn_trad_device: the weight statistics read back to the host
-    float* d_conv_ws = nullptr;
-    size_t conv_ws_floats = 0;
+    DeviceBuffer<float> d_ct_stats;  // kws_load_cnn_trad_device: the weight statistics read back to the host
+    DeviceBuffer<float> d_conv_ws;  // scratch between two kernels of one call (grow_conv_ws)
     // training (kws_dscnn_backward_f32, kws_dscnn_bwd.hip; kws_cnn_trad_backward_f32, kws_cnntrad_bwd.hip): recomputed activations, gradients, per-workgroup partials
-    float* d_train_ws = nullptr;
-    size_t train_ws_floats = 0;
+    DeviceBuffer<float> d_train_ws;
 
     // workspace (MFCC features between the two kernels of kws_infer_i16)
-    float* d_feat_ws = nullptr;
-    size_t feat_ws_floats = 0;
+    DeviceBuffer<float> d_feat_ws;
     // kws_scan_i16: a recording's frames when the caller keeps none (kws_scan_detect_f32's scratch is d_conv_ws)
-    float* d_scan_ws = nullptr;
-    size_t scan_ws_floats = 0;
+    DeviceBuffer<float> d_scan_ws;
     // the ragged entries' plan tables (records, per-recording offsets and counts), derived on the host per call
-    unsigned char* d_ragged = nullptr;
-    size_t ragged_bytes = 0;
+    DeviceBuffer<unsigned char> d_ragged;
 
     // streaming state (kws_stream_*): per-stream PCM ring, feature ring, hop counter, optional graph
     int n_streams = 0, ring_len = 0;
-    int16_t* d_pcm_ring = nullptr;
-    float* d_feat_ring = nullptr;
-    int* d_hops = nullptr;
+    DeviceBuffer<int16_t> d_pcm_ring;
+    DeviceBuffer<float> d_feat_ring;
+    DeviceBuffer<int> d_hops;
     int stream_cluster = 0;           // workgroups per stream of the fused push (kws_stream_cluster; 0 = by stream count)
-    float* d_cl_part = nullptr;       // [n_streams][4][64] pooled partial sums of a stream's time tiles
-    int* d_cl_count = nullptr;        // [n_streams]
+    DeviceBuffer<float> d_cl_part;    // [n_streams][4][64] pooled partial sums of a stream's time tiles
+    DeviceBuffer<int> d_cl_count;     // [n_streams]
     // zero-copy result delivery of the one-launch push (kws_stream_host_results): pinned, device-mapped host memory
-    float* h_stream_logits = nullptr;  // [n_streams][num_classes at enable time]
-    int32_t* h_stream_label = nullptr;
-    int* h_stream_flag = nullptr;
-    int16_t* h_stream_hop = nullptr;   // [n_streams][frame_step]: the hop of kws_stream_push_host_i16, read by the kernel over PCIe
-    float* d_hr_logits = nullptr;      // device-side outputs of kws_stream_push_host_i16 (the kernel writes both copies)
-    int32_t* d_hr_label = nullptr;
+    PinnedBuffer<float> h_stream_logits;  // [n_streams][num_classes at enable time]
+    PinnedBuffer<int32_t> h_stream_label;
+    PinnedBuffer<int> h_stream_flag;
+    PinnedBuffer<int16_t> h_stream_hop;  // [n_streams][frame_step]: the hop of kws_stream_push_host_i16, read by the kernel over PCIe
+    DeviceBuffer<float> d_hr_logits;   // device-side outputs of kws_stream_push_host_i16 (the kernel writes both copies)
+    DeviceBuffer<int32_t> d_hr_label;
     int host_results_classes = 0;
     int pushes_enqueued = 0;           // pushes since kws_stream_open = the device's hop counter once the stream has drained
     int host_push = 0;                 // the newest push that delivers to host memory (the flag reads this when it is done)
@@ -129,22 +133,20 @@ struct kws_ctx {
     hipGraphExec_t stream_graph = nullptr;
     const void* graph_key[3] = {nullptr, nullptr, nullptr};
     // posterior smoothing history (kws_stream_smooth_f32): ring [n_streams][window][C], sum [n_streams][C], hop count
-    float* d_post_ring = nullptr;
-    float* d_post_sum = nullptr;
-    int* d_post_count = nullptr;
+    DeviceBuffer<float> d_post_ring, d_post_sum;
+    DeviceBuffer<int> d_post_count;
     int post_window = 0, post_classes = 0;
     // energy endpointer (kws_stream_vad_f32): ep_ring_push's state, bits [n_streams][EP_BIT_WORDS] and counts [n_streams][4] =
     // (c_on, c_off, triggered, cursor)
-    unsigned long long* d_vad_bits = nullptr;
-    int* d_vad_counts = nullptr;
+    DeviceBuffer<unsigned long long> d_vad_bits;
+    DeviceBuffer<int> d_vad_counts;
     int vad_on = 0, vad_off = 0;
 
     // evaluation statistics (kws_eval_*, kws_eval.hip): one allocation of 64-bit words -- counts[4], loss_sum (a double),
     // confusion [C][C], hist_pos [C][K], hist_neg [C][K] -- and the per-workgroup float64 loss partials of one update
-    unsigned long long* d_eval = nullptr;
+    DeviceBuffer<unsigned long long> d_eval;
     int eval_classes = 0, eval_bins = 0;  // eval_classes > 0: open
-    double* d_eval_part = nullptr;
-    size_t eval_part_cap = 0;
+    DeviceBuffer<double> d_eval_part;
 
     // sample-rate conversion (kws_resample_*): the tap tables of the rate pairs used so far -- created on first use
     kws::ResampleCache* resample = nullptr;
@@ -238,13 +240,11 @@ inline int check_normalize_to(kws_ctx* c, const char* fn, int v) {
     } while (0)
 
 // ep_ring_push's state for S streams, zeroed on the context's stream (history before the first frame is unvoiced).  On an
-// error the caller frees whatever was allocated.
-inline int alloc_endpoint_state(kws_ctx* c, const char* fn, size_t S, unsigned long long*& bits, int*& counts) {
-    const size_t bits_b = sizeof(unsigned long long) * S * kws::EP_BIT_WORDS, counts_b = sizeof(int) * S * 4;
-    if (hipMalloc(reinterpret_cast<void**>(&bits), bits_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&counts), counts_b) != hipSuccess)
-        return fail(c, KWS_ENOMEM, std::string(fn) + ": device allocation failed");
-    hipError_t e = hipMemsetAsync(bits, 0, bits_b, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(counts, 0, counts_b, c->stream);
+// error the caller resets the two (or lets them go).
+inline int alloc_endpoint_state(kws_ctx* c, const char* fn, size_t S, DeviceBuffer<unsigned long long>& bits, DeviceBuffer<int>& counts) {
+    if (!(bits.alloc(S * kws::EP_BIT_WORDS) && counts.alloc(S * 4))) return fail(c, KWS_ENOMEM, std::string(fn) + ": device allocation failed");
+    hipError_t e = hipMemsetAsync(bits.get(), 0, sizeof(unsigned long long) * bits.size(), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(counts.get(), 0, sizeof(int) * counts.size(), c->stream);
     return e == hipSuccess ? KWS_OK : fail_hip(c, e, (std::string(fn) + ": hipMemsetAsync").c_str());
 }
 
@@ -288,38 +288,31 @@ inline int retire_captured_push(kws_ctx* c) {
     return KWS_OK;
 }
 
-// Swap a device allocation for a fresh copy of `bytes` host bytes: drain the stream (kernels may be reading the old one),
-// allocate, copy, free the old allocation, store the pointer.  On failure the context keeps what it had.
+// Swap a device allocation for a fresh copy of `bytes` host bytes (a multiple of sizeof(T)): drain the stream (kernels may be
+// reading the old one), allocate, copy, and only then let the old allocation go.  On failure the context keeps what it had.
 template <class T>
-int replace_device_image(kws_ctx* c, T*& slot, const void* host, size_t bytes, const char* fn) {
+int replace_device_image(kws_ctx* c, DeviceBuffer<T>& buf, const void* host, size_t bytes, const char* fn) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    void* d = nullptr;
-    if (hipMalloc(&d, bytes) != hipSuccess) return fail(c, KWS_ENOMEM, std::string(fn) + ": device allocation failed");
-    hipError_t e = hipMemcpy(d, host, bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return fail_hip(c, e, (std::string(fn) + ": hipMemcpy").c_str());
-    }
-    if (slot) (void)hipFree(slot);
-    slot = static_cast<T*>(d);
+    DeviceBuffer<T> d;
+    if (!d.alloc(bytes / sizeof(T))) return fail(c, KWS_ENOMEM, std::string(fn) + ": device allocation failed");
+    hipError_t e = hipMemcpy(d.get(), host, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail_hip(c, e, (std::string(fn) + ": hipMemcpy").c_str());
+    buf = std::move(d);
     return KWS_OK;
 }
 
 // Grow a workspace to at least `need` elements (contents are not kept): nothing when it is large enough, else drain the
-// stream, allocate, free the old one, store pointer and capacity.  KWS_ENOMEM reads "<fn>: <what> allocation failed".
+// stream, allocate, and only then let the old one go: a failed grow keeps it.  KWS_ENOMEM reads "<fn>: <what> allocation failed".
 template <class T>
-int grow_device_buffer(kws_ctx* c, T*& buf, size_t& cap, size_t need, const char* fn, const char* what) {
-    if (need <= cap) return KWS_OK;
+int grow_device_buffer(kws_ctx* c, DeviceBuffer<T>& buf, size_t need, const char* fn, const char* what) {
+    if (need <= buf.size()) return KWS_OK;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    T* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), need * sizeof(T)) != hipSuccess)
-        return fail(c, KWS_ENOMEM, std::string(fn) + ": " + what + " allocation failed");
-    if (buf) (void)hipFree(buf);
-    buf = d;
-    cap = need;
+    DeviceBuffer<T> d;
+    if (!d.alloc(need)) return fail(c, KWS_ENOMEM, std::string(fn) + ": " + what + " allocation failed");
+    buf = std::move(d);
     return KWS_OK;
 }
 // Grow the context's float scratch (convolution outputs between two kernels of one call) to at least `need` floats.
 inline int grow_conv_ws(kws_ctx* c, size_t need, const char* fn) {
-    return grow_device_buffer(c, c->d_conv_ws, c->conv_ws_floats, need, fn, "workspace");
+    return grow_device_buffer(c, c->d_conv_ws, need, fn, "workspace");
 }

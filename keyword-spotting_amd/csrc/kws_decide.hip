@@ -114,21 +114,18 @@ hipError_t launch_smooth_posteriors(hipStream_t s, const float* d_logits, int S,
     return hipGetLastError();
 }
 
-// The histories of the two streaming entry points below; stream_free (kws_stream.hip) drops them with the streams.
+// The histories of the two streaming entry points below; stream_free (kws_stream.hip) drops them with the streams.  The window
+// sizes say whether a history is running.
 void smooth_free(kws_ctx* c) {
-    if (c->d_post_ring) (void)hipFree(c->d_post_ring);
-    if (c->d_post_sum) (void)hipFree(c->d_post_sum);
-    if (c->d_post_count) (void)hipFree(c->d_post_count);
-    c->d_post_ring = c->d_post_sum = nullptr;
-    c->d_post_count = nullptr;
+    c->d_post_ring.reset();
+    c->d_post_sum.reset();
+    c->d_post_count.reset();
     c->post_window = c->post_classes = 0;
 }
 
 void vad_free(kws_ctx* c) {
-    if (c->d_vad_bits) (void)hipFree(c->d_vad_bits);
-    if (c->d_vad_counts) (void)hipFree(c->d_vad_counts);
-    c->d_vad_bits = nullptr;
-    c->d_vad_counts = nullptr;
+    c->d_vad_bits.reset();
+    c->d_vad_counts.reset();
     c->vad_on = c->vad_off = 0;
 }
 
@@ -157,9 +154,9 @@ int kws_stream_vad_f32(kws_ctx* c, float log_energy_threshold, int on_window, in
         c->vad_on = on_window;
         c->vad_off = off_window;
     }
-    hipLaunchKernelGGL(kws_stream_vad_kernel, dim3((c->n_streams + 63) / 64), dim3(64), 0, c->stream, c->d_feat_ring, c->d_hops, c->n_streams,
-                       c->fp.num_frames, c->fp.numcep, frames_lag(c->fp), log_energy_threshold, on_window, off_window, c->d_vad_bits,
-                       c->d_vad_counts, d_state);
+    hipLaunchKernelGGL(kws_stream_vad_kernel, dim3((c->n_streams + 63) / 64), dim3(64), 0, c->stream, c->d_feat_ring.get(), c->d_hops.get(),
+                       c->n_streams, c->fp.num_frames, c->fp.numcep, frames_lag(c->fp), log_energy_threshold, on_window, off_window,
+                       c->d_vad_bits.get(), c->d_vad_counts.get(), d_state);
     HIP_TRY(c, hipGetLastError());
     return KWS_OK;
 }
@@ -184,21 +181,19 @@ int kws_stream_smooth_f32(kws_ctx* c, const float* d_logits, int C, int window, 
     if (window != c->post_window || C != c->post_classes) {  // (re)start the history
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         smooth_free(c);
-        const size_t ring_b = sizeof(float) * (size_t)c->n_streams * window * C, sum_b = sizeof(float) * (size_t)c->n_streams * C;
-        if (hipMalloc(reinterpret_cast<void**>(&c->d_post_ring), ring_b) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&c->d_post_sum), sum_b) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&c->d_post_count), 2 * sizeof(int)) != hipSuccess) {
+        const size_t sums = (size_t)c->n_streams * C;
+        if (!(c->d_post_ring.alloc(sums * window) && c->d_post_sum.alloc(sums) && c->d_post_count.alloc(2))) {
             smooth_free(c);
             return fail(c, KWS_ENOMEM, "kws_stream_smooth_f32: device allocation failed");
         }
-        HIP_TRY(c, hipMemsetAsync(c->d_post_ring, 0, ring_b, c->stream));
-        HIP_TRY(c, hipMemsetAsync(c->d_post_sum, 0, sum_b, c->stream));
-        HIP_TRY(c, hipMemsetAsync(c->d_post_count, 0, 2 * sizeof(int), c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_post_ring.get(), 0, sizeof(float) * sums * window, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_post_sum.get(), 0, sizeof(float) * sums, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_post_count.get(), 0, 2 * sizeof(int), c->stream));
         c->post_window = window;
         c->post_classes = C;
     }
-    HIP_TRY(c, launch_smooth_posteriors(c->stream, d_logits, c->n_streams, C, window, c->d_post_ring, c->d_post_sum,
-                                        c->d_post_count, d_smoothed, d_label));
+    HIP_TRY(c, launch_smooth_posteriors(c->stream, d_logits, c->n_streams, C, window, c->d_post_ring.get(), c->d_post_sum.get(),
+                                        c->d_post_count.get(), d_smoothed, d_label));
     return KWS_OK;
 }
 

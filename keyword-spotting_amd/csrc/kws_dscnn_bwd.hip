@@ -363,9 +363,9 @@ int kws_dscnn_backward_f32(kws_ctx* c, const float* d_feat, int B, int T, int F,
     const int chunk = (int)std::min<size_t>({(size_t)B, COMPOSED_MAX_CLIPS, by_budget});
     Carver need(chunk);
     carve(need);
-    rc = grow_device_buffer(c, c->d_train_ws, c->train_ws_floats, need.floats(), fn, "workspace");
+    rc = grow_device_buffer(c, c->d_train_ws, need.floats(), fn, "workspace");
     if (rc) return rc;
-    Carver ws(chunk, c->d_train_ws);
+    Carver ws(chunk, c->d_train_ws.get());
     carve(ws);
     const float* raw = c->mw.raw;
     hipStream_t s = c->stream;

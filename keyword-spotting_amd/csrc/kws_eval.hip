@@ -128,11 +128,8 @@ __global__ __launch_bounds__(EVAL_BLOCK) void kws_eval_loss_kernel(const double*
 }  // namespace
 
 void eval_free(kws_ctx* c) {
-    if (c->d_eval) (void)hipFree(c->d_eval);
-    if (c->d_eval_part) (void)hipFree(c->d_eval_part);
-    c->d_eval = nullptr;
-    c->d_eval_part = nullptr;
-    c->eval_part_cap = 0;
+    c->d_eval.reset();
+    c->d_eval_part.reset();
     c->eval_classes = c->eval_bins = 0;
 }
 
@@ -151,16 +148,14 @@ int kws_eval_open(kws_ctx* c, int num_classes, int n_bins) {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // an update of the state being replaced may still be running
     eval_free(c);
-    const size_t bytes = eval_words(num_classes, n_bins) * sizeof(unsigned long long);
-    if (hipMalloc(reinterpret_cast<void**>(&c->d_eval), bytes) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->d_eval_part), EVAL_PART_RESERVE * sizeof(double)) != hipSuccess) {
+    const size_t words = eval_words(num_classes, n_bins);
+    if (!(c->d_eval.alloc(words) && c->d_eval_part.alloc(EVAL_PART_RESERVE))) {
         eval_free(c);
         return fail(c, KWS_ENOMEM, "kws_eval_open: device allocation failed");
     }
-    c->eval_part_cap = EVAL_PART_RESERVE;
     c->eval_classes = num_classes;
     c->eval_bins = n_bins;
-    HIP_TRY(c, hipMemsetAsync(c->d_eval, 0, bytes, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_eval.get(), 0, words * sizeof(unsigned long long), c->stream));
     return KWS_OK;
 }
 
@@ -168,7 +163,7 @@ int kws_eval_reset(kws_ctx* c) {
     if (!c) return KWS_EINVAL;
     if (!c->eval_classes) return fail(c, KWS_ESTATE, "kws_eval_reset: call kws_eval_open first");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemsetAsync(c->d_eval, 0, eval_words(c->eval_classes, c->eval_bins) * sizeof(unsigned long long), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_eval.get(), 0, eval_words(c->eval_classes, c->eval_bins) * sizeof(unsigned long long), c->stream));
     return KWS_OK;
 }
 
@@ -190,18 +185,18 @@ int kws_eval_update_f32(kws_ctx* c, const float* d_logits, const int32_t* d_trut
     HIP_TRY(c, hipSetDevice(c->device));
     const int C = c->eval_classes, K = c->eval_bins;
     const int blocks = (B + EVAL_BLOCK - 1) / EVAL_BLOCK;
-    int rc = grow_device_buffer(c, c->d_eval_part, c->eval_part_cap, (size_t)blocks, "kws_eval_update_f32", "loss partial");
+    int rc = grow_device_buffer(c, c->d_eval_part, (size_t)blocks, "kws_eval_update_f32", "loss partial");
     if (rc) return rc;
     const float scale = d_dlogits ? grad_scale : 0.f;
     const int counters = 2 * C * K;
     if (K > 0 && counters <= EVAL_LDS_COUNTERS)
         hipLaunchKernelGGL(kws_eval_update_kernel<true>, dim3(blocks), dim3(EVAL_BLOCK), counters * sizeof(unsigned int), c->stream,
-                           d_logits, d_truth, B, C, K, scale, d_dlogits, d_loss_rows, c->d_eval, c->d_eval_part);
+                           d_logits, d_truth, B, C, K, scale, d_dlogits, d_loss_rows, c->d_eval.get(), c->d_eval_part.get());
     else
         hipLaunchKernelGGL(kws_eval_update_kernel<false>, dim3(blocks), dim3(EVAL_BLOCK), 0, c->stream, d_logits, d_truth, B, C, K,
-                           scale, d_dlogits, d_loss_rows, c->d_eval, c->d_eval_part);
+                           scale, d_dlogits, d_loss_rows, c->d_eval.get(), c->d_eval_part.get());
     HIP_TRY(c, hipGetLastError());
-    hipLaunchKernelGGL(kws_eval_loss_kernel, dim3(1), dim3(EVAL_BLOCK), 0, c->stream, c->d_eval_part, blocks, c->d_eval);
+    hipLaunchKernelGGL(kws_eval_loss_kernel, dim3(1), dim3(EVAL_BLOCK), 0, c->stream, c->d_eval_part.get(), blocks, c->d_eval.get());
     HIP_TRY(c, hipGetLastError());
     return KWS_OK;
 }
@@ -214,7 +209,7 @@ int kws_eval_read(kws_ctx* c, uint64_t* counts, double* loss_sum, uint64_t* conf
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     const size_t C = (size_t)c->eval_classes, K = (size_t)c->eval_bins;
     std::vector<unsigned long long> h(eval_words((int)C, (int)K));
-    HIP_TRY(c, hipMemcpy(h.data(), c->d_eval, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(h.data(), c->d_eval.get(), h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     const unsigned long long* conf = h.data() + EVAL_CONFUSION;
     if (counts) std::memcpy(counts, h.data() + EVAL_COUNTS, 4 * sizeof(uint64_t));
     if (loss_sum) std::memcpy(loss_sum, h.data() + EVAL_LOSS, sizeof(double));

@@ -1,7 +1,8 @@
 // The host-mirrored event queue of the live units (kws_live.hip: utterances, kws_live_detect.hip: keyword events): a step kernel
 // of ONE workgroup numbers the events of its step, writes them to a device queue and to a pinned host mirror, and raises a
 // kernel count the host spins on.  Inline functions only: the device half is the tail of both step kernels, the host half what
-// their open, release, poll and read entries do with the queue; kws_stream_wait_host (kws_stream.hip) shares the bounded spin.
+// their open, poll and read entries do with the queue; kws_stream_wait_host (kws_stream.hip) shares the bounded spin.  The queue's
+// memory is owned by an EventQueueMem beside the EventQueue that travels to the kernels, and goes with its unit.
 // What the two halves keep, and what every change here must keep:
 //  1. Every thread reads the counters at the top of the kernel (eq_counts); thread 0 overwrites them only behind the last
 //     barrier (eq_publish, and the unit's own words after it).
@@ -108,25 +109,27 @@ inline bool spin_until(Seen seen) {
     }
 }
 
-inline void eq_release(EventQueue& q) {
-    if (q.queue) (void)hipFree(q.queue);
-    if (q.ctr) (void)hipFree(q.ctr);
-    if (q.h_queue) (void)hipHostFree(q.h_queue);
-    if (q.h_ctr) (void)hipHostFree(q.h_ctr);
-    q = EventQueue{};
-}
+// What an EventQueue points into.
+struct EventQueueMem {
+    DeviceBuffer<unsigned long long> ctr;
+    DeviceBuffer<long long> queue;
+    PinnedBuffer<long long> h_queue;
+    PinnedBuffer<unsigned long long> h_ctr;
+};
 
-// Allocate a queue of max_events records of `rec` words; the mirror zeroed here, the device side on the context's stream.  On
-// a failure the caller releases (eq_release), after the stream has drained.
-inline int eq_open(kws_ctx* c, const char* fn, EventQueue& q, int rec, int max_events) {
+// Allocate a queue of max_events records of `rec` words into m and point q at it; the mirror zeroed here, the device side on the
+// context's stream.  On a failure the caller lets m go, after the stream has drained.
+inline int eq_open(kws_ctx* c, const char* fn, EventQueueMem& m, EventQueue& q, int rec, int max_events) {
     q = EventQueue{};
-    q.max_events = max_events;
-    const size_t queue_b = sizeof(long long) * (size_t)max_events * rec;
+    const size_t words = (size_t)max_events * rec, queue_b = sizeof(long long) * words;
     const unsigned flags = hipHostMallocMapped | hipHostMallocCoherent;  // fine-grained: device stores are visible to the host as they land
-    if (hipMalloc(reinterpret_cast<void**>(&q.ctr), 64) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&q.queue), queue_b) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&q.h_queue), queue_b, flags) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&q.h_ctr), 64, flags) != hipSuccess)
+    if (!(m.ctr.alloc(8) && m.queue.alloc(words) && m.h_queue.alloc(words, flags) && m.h_ctr.alloc(8, flags)))
         return fail(c, KWS_ENOMEM, std::string(fn) + ": allocation failed");
+    q.ctr = m.ctr.get();
+    q.queue = m.queue.get();
+    q.h_queue = m.h_queue.get();
+    q.h_ctr = m.h_ctr.get();
+    q.max_events = max_events;
     memset(q.h_queue, 0, queue_b);
     memset(q.h_ctr, 0, 64);
     hipError_t e = hipMemsetAsync(q.ctr, 0, 64, c->stream);

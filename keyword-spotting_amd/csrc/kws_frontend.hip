@@ -31,16 +31,13 @@ int ensure_refine(kws_ctx* c, int B, int num_frames) {
     if (frames > 0x1fffffffu) return fail(c, KWS_EUNSUPPORTED, "refinement worklist: more than 2^29 frame pairs in one call");
     if (c->d_refine && (int)frames <= c->refine_cap) return KWS_OK;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    int* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), sizeof(int) * (8 + frames)) != hipSuccess)
-        return fail(c, KWS_ENOMEM, "refinement worklist: device allocation failed");
-    hipError_t e = c->d_refine ? hipMemcpy(d, c->d_refine, sizeof(int) * 8, hipMemcpyDeviceToDevice) : hipMemset(d, 0, sizeof(int) * 8);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return fail_hip(c, e, "refinement worklist");
-    }
-    if (c->d_refine) (void)hipFree(c->d_refine);
-    c->d_refine = d;
+    // not grow_device_buffer: the eight counters in front of the list (kws_frontend_stats reads them) move to the new allocation
+    DeviceBuffer<int> d;
+    if (!d.alloc(8 + frames)) return fail(c, KWS_ENOMEM, "refinement worklist: device allocation failed");
+    hipError_t e = c->d_refine ? hipMemcpy(d.get(), c->d_refine.get(), sizeof(int) * 8, hipMemcpyDeviceToDevice)
+                               : hipMemset(d.get(), 0, sizeof(int) * 8);
+    if (e != hipSuccess) return fail_hip(c, e, "refinement worklist");
+    c->d_refine = std::move(d);
     c->refine_cap = (int)frames;
     return KWS_OK;
 }
@@ -69,7 +66,7 @@ int run_frontend(kws_ctx* c, const FrontendParams& geometry, Src src, int B, flo
     if (p.refine_span > 0.f) {
         int rc = ensure_refine(c, B, p.num_frames);
         if (rc) return rc;
-        const RefineList rl = {c->d_refine, c->d_refine + 8, c->refine_cap, 0};
+        const RefineList rl = {c->d_refine.get(), c->d_refine.get() + 8, c->refine_cap, 0};
         {
             ProfScope ps(c, KWS_K_MFCC);
             HIP_TRY(c, launch_mfcc(c->stream, p, c->ft, src, B, d_out, rl, ref_route));
@@ -111,7 +108,7 @@ int kws_set_frontend(kws_ctx* c, int sample_rate, int n_samples, int frame_len, 
     if (c->n_streams) stream_free(c);             // ring geometry depends on the front end
     int rc = replace_device_image(c, c->d_fe, im.bytes.data(), im.bytes.size(), "kws_set_frontend");
     if (rc) return rc;
-    c->ft = im.tables(c->d_fe);
+    c->ft = im.tables(c->d_fe.get());
 
     FrontendParams& p = c->fp;
     p.frame_len = frame_len;
@@ -172,7 +169,7 @@ int kws_frontend_stats(kws_ctx* c, uint64_t* frames_total, uint64_t* frames_refi
     int ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->d_refine) HIP_TRY(c, hipMemcpy(ctr, c->d_refine, sizeof ctr, hipMemcpyDeviceToHost));
+    if (c->d_refine) HIP_TRY(c, hipMemcpy(ctr, c->d_refine.get(), sizeof ctr, hipMemcpyDeviceToHost));
     if (frames_total) *frames_total = c->frames_seen;
     if (frames_refined) *frames_refined = ((uint64_t)(uint32_t)ctr[3] << 32 | (uint32_t)ctr[2]) + (uint64_t)(uint32_t)ctr[5];
     if (last_call_refined) *last_call_refined = ctr[4];
@@ -196,9 +193,9 @@ int kws_reserve(kws_ctx* c, int max_batch) {
         if (rc) return rc;
     }
     const size_t need = (size_t)max_batch * c->fp.num_frames * c->fp.numcep;
-    if (need <= c->feat_ws_floats) return KWS_OK;
+    if (need <= c->d_feat_ws.size()) return KWS_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    return grow_device_buffer(c, c->d_feat_ws, c->feat_ws_floats, need, "kws_reserve", "device");
+    return grow_device_buffer(c, c->d_feat_ws, need, "kws_reserve", "device");
 }
 
 int kws_mfcc_i16(kws_ctx* c, const int16_t* d_wav, int B, float* d_out) {
@@ -314,7 +311,7 @@ int kws_spec_f32(kws_ctx* c, const float* d_frames, int num_frames, int frame_le
         if (rc) return rc;
         c->spec_nfft = nfft;
     }
-    HIP_TRY(c, launch_spec_f64(c->stream, c->d_spec_tw64, d_frames, num_frames, frame_len, nfft, log2n, power, d_spec));
+    HIP_TRY(c, launch_spec_f64(c->stream, c->d_spec_tw64.get(), d_frames, num_frames, frame_len, nfft, log2n, power, d_spec));
     return KWS_OK;
     KWS_GUARD_END(c, "kws_spec_f32")
 }

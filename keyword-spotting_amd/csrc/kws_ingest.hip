@@ -100,12 +100,12 @@ class PackPool {
 };
 
 struct IngestSlot {
-    int16_t* h_in = nullptr;      // pinned [chunk][n_samples]
-    int16_t* d_in = nullptr;      // device
-    float* d_logits = nullptr;    // device [chunk][C]
-    int32_t* d_label = nullptr;   // device [chunk]
-    float* h_logits = nullptr;    // pinned
-    int32_t* h_label = nullptr;   // pinned
+    PinnedBuffer<int16_t> h_in;      // pinned [chunk][n_samples]
+    DeviceBuffer<int16_t> d_in;      // device
+    DeviceBuffer<float> d_logits;    // device [chunk][C]
+    DeviceBuffer<int32_t> d_label;   // device [chunk]
+    PinnedBuffer<float> h_logits;    // pinned
+    PinnedBuffer<int32_t> h_label;   // pinned
     hipEvent_t staged = nullptr, computed = nullptr, drained = nullptr;
     int count = 0;                // clips this slot currently carries (0: free)
     float* dst_logits = nullptr;  // where its results go in the submitting call's host arrays (already offset to the chunk)
@@ -128,17 +128,11 @@ struct Ingest {
 static void ingest_release(Ingest* g) {
     if (!g) return;
     for (auto& s : g->slots) {
-        if (s.h_in) (void)hipHostFree(s.h_in);
-        if (s.d_in) (void)hipFree(s.d_in);
-        if (s.d_logits) (void)hipFree(s.d_logits);
-        if (s.d_label) (void)hipFree(s.d_label);
-        if (s.h_logits) (void)hipHostFree(s.h_logits);
-        if (s.h_label) (void)hipHostFree(s.h_label);
         if (s.staged) (void)hipEventDestroy(s.staged);
         if (s.computed) (void)hipEventDestroy(s.computed);
         if (s.drained) (void)hipEventDestroy(s.drained);
     }
-    g->slots.clear();
+    g->slots.clear();  // the slots' staging memory goes with them
     for (auto& st : g->copy_in) {
         if (st) (void)hipStreamDestroy(st);
         st = nullptr;
@@ -182,15 +176,10 @@ static int ingest_prepare(kws_ctx* c) {
     HIP_TRY(c, hipStreamCreateWithFlags(&g->copy_in[1], hipStreamNonBlocking));
     HIP_TRY(c, hipStreamCreateWithFlags(&g->copy_out, hipStreamNonBlocking));
     g->slots.resize(n_slots);
-    const size_t in_b = sizeof(int16_t) * (size_t)chunk * n_samples, lg_b = sizeof(float) * (size_t)chunk * classes,
-                 lb_b = sizeof(int32_t) * (size_t)chunk;
+    const size_t in_n = (size_t)chunk * n_samples, lg_n = (size_t)chunk * classes, lb_n = (size_t)chunk;
     for (auto& s : g->slots) {
-        if (hipHostMalloc(reinterpret_cast<void**>(&s.h_in), in_b, hipHostMallocDefault) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&s.d_in), in_b) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&s.d_logits), lg_b) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&s.d_label), lb_b) != hipSuccess ||
-            hipHostMalloc(reinterpret_cast<void**>(&s.h_logits), lg_b, hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc(reinterpret_cast<void**>(&s.h_label), lb_b, hipHostMallocDefault) != hipSuccess ||
+        if (!(s.h_in.alloc(in_n, hipHostMallocDefault) && s.d_in.alloc(in_n) && s.d_logits.alloc(lg_n) && s.d_label.alloc(lb_n) &&
+              s.h_logits.alloc(lg_n, hipHostMallocDefault) && s.h_label.alloc(lb_n, hipHostMallocDefault)) ||
             hipEventCreateWithFlags(&s.staged, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&s.computed, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&s.drained, hipEventDisableTiming) != hipSuccess) {
@@ -210,8 +199,8 @@ static int ingest_collect(kws_ctx* c, IngestSlot& s) {
     if (s.count == 0) return KWS_OK;
     HIP_TRY(c, hipEventSynchronize(s.drained));
     const int C = c->ingest->classes;
-    memcpy(s.dst_logits, s.h_logits, sizeof(float) * (size_t)s.count * C);
-    if (s.dst_label) memcpy(s.dst_label, s.h_label, sizeof(int32_t) * (size_t)s.count);
+    memcpy(s.dst_logits, s.h_logits.get(), sizeof(float) * (size_t)s.count * C);
+    if (s.dst_label) memcpy(s.dst_label, s.h_label.get(), sizeof(int32_t) * (size_t)s.count);
     s.count = 0;
     return KWS_OK;
 }
@@ -279,18 +268,18 @@ static int ingest_submit(kws_ctx* c, const int16_t* h_wav, int B, float* h_logit
         const size_t bytes = sizeof(int16_t) * (size_t)count * n;
         const int16_t* src = h_wav + (size_t)first * n;
         if (!direct) {
-            g->pool->copy(s.h_in, src, bytes);
-            src = s.h_in;
+            g->pool->copy(s.h_in.get(), src, bytes);
+            src = s.h_in.get();
         }
-        HIP_TRY(c, hipMemcpyAsync(s.d_in, src, bytes, hipMemcpyHostToDevice, g->copy_in[g->lane]));
+        HIP_TRY(c, hipMemcpyAsync(s.d_in.get(), src, bytes, hipMemcpyHostToDevice, g->copy_in[g->lane]));
         HIP_TRY(c, hipEventRecord(s.staged, g->copy_in[g->lane]));
         HIP_TRY(c, hipStreamWaitEvent(c->stream, s.staged, 0));
-        rc = kws_infer_i16(c, s.d_in, count, s.d_logits, s.d_label);
+        rc = kws_infer_i16(c, s.d_in.get(), count, s.d_logits.get(), s.d_label.get());
         if (rc) return rc;
         HIP_TRY(c, hipEventRecord(s.computed, c->stream));
         HIP_TRY(c, hipStreamWaitEvent(g->copy_out, s.computed, 0));
-        HIP_TRY(c, hipMemcpyAsync(s.h_logits, s.d_logits, sizeof(float) * (size_t)count * C, hipMemcpyDeviceToHost, g->copy_out));
-        HIP_TRY(c, hipMemcpyAsync(s.h_label, s.d_label, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, g->copy_out));
+        HIP_TRY(c, hipMemcpyAsync(s.h_logits.get(), s.d_logits.get(), sizeof(float) * (size_t)count * C, hipMemcpyDeviceToHost, g->copy_out));
+        HIP_TRY(c, hipMemcpyAsync(s.h_label.get(), s.d_label.get(), sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, g->copy_out));
         HIP_TRY(c, hipEventRecord(s.drained, g->copy_out));
         s.dst_logits = h_logits + (size_t)first * C;
         s.dst_label = h_label ? h_label + first : nullptr;

@@ -39,10 +39,15 @@ struct LiveArgs {
 
 }  // namespace
 
-// Everything kws_stream_utt_open allocates, as the step kernel takes it.
+// Everything kws_stream_utt_open allocates: as the step kernel takes it (a), and the owners a's pointers are filled from.
 struct StreamUtt {
     LiveArgs a{};
     int mode = 0;  // 0: not stepped yet, 1: stepped by pushes, 2: stepped by kws_stream_utt_step_i16
+    DeviceBuffer<int16_t> hist;
+    DeviceBuffer<unsigned long long> bits;
+    DeviceBuffer<int> counts;
+    DeviceBuffer<long long> pos;
+    EventQueueMem queue;
 };
 
 namespace {
@@ -180,14 +185,6 @@ int history_for(int frame_len, int frame_step, int pre_roll, int max_frames, int
     return *out > INT_MAX ? KWS_EINVAL : KWS_OK;
 }
 
-void utt_release(StreamUtt* u) {
-    if (!u) return;
-    for (void* d : {(void*)u->a.hist, (void*)u->a.bits, (void*)u->a.counts, (void*)u->a.pos})
-        if (d) (void)hipFree(d);
-    eq_release(u->a.q);
-    delete u;
-}
-
 // One launch of the step or flush kernel with the set's state; hop / energy / ctx_hops as LiveArgs describes them.
 template <bool FLUSH>
 int utt_launch(kws_ctx* c, const int16_t* hop, long long hop_stride, const int* ctx_hops, const float* energy) {
@@ -218,7 +215,7 @@ int utt_launch(kws_ctx* c, const int16_t* hop, long long hop_stride, const int* 
 }  // namespace
 
 void stream_utt_free(kws_ctx* c) {
-    utt_release(c->stream_utt);
+    delete c->stream_utt;
     c->stream_utt = nullptr;
 }
 
@@ -232,7 +229,7 @@ int stream_utt_push_check(kws_ctx* c, const char* fn) {
 int stream_utt_pushed(kws_ctx* c) {
     if (!c->stream_utt) return KWS_OK;
     c->stream_utt->mode = 1;
-    return utt_launch<false>(c, c->d_pcm_ring, c->ring_len, c->d_hops, c->d_feat_ring);
+    return utt_launch<false>(c, c->d_pcm_ring.get(), c->ring_len, c->d_hops.get(), c->d_feat_ring.get());
 }
 
 }  // namespace kws
@@ -270,7 +267,7 @@ int kws_stream_utt_open(kws_ctx* c, float log_energy_threshold, int on_window, i
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     stream_utt_free(c);
-    StreamUtt* u = new StreamUtt();
+    std::unique_ptr<StreamUtt> u(new StreamUtt());
     LiveArgs& a = u->a;
     const size_t S = (size_t)c->n_streams;
     a.S = c->n_streams;
@@ -281,17 +278,23 @@ int kws_stream_utt_open(kws_ctx* c, float log_energy_threshold, int on_window, i
     a.max_frames = max_frames;
     a.threshold = log_energy_threshold;
     const size_t hist_b = sizeof(int16_t) * S * (size_t)a.H, pos_b = sizeof(long long) * S * 2;
-    if (hipMalloc(reinterpret_cast<void**>(&a.hist), hist_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&a.pos), pos_b) != hipSuccess) {
-        utt_release(u);
-        return fail(c, KWS_ENOMEM, "kws_stream_utt_open: allocation failed");
+    if (!(u->hist.alloc(S * (size_t)a.H) && u->pos.alloc(S * 2))) return fail(c, KWS_ENOMEM, "kws_stream_utt_open: allocation failed");
+    a.hist = u->hist.get();
+    a.pos = u->pos.get();
+    rc = eq_open(c, "kws_stream_utt_open", u->queue, a.q, LIVE_REC, max_events);
+    if (!rc) rc = alloc_endpoint_state(c, "kws_stream_utt_open", S, u->bits, u->counts);
+    if (!rc) {
+        a.bits = u->bits.get();
+        a.counts = u->counts.get();
+        hipError_t e = hipMemsetAsync(a.hist, 0, hist_b, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(a.pos, 0xFF, pos_b, c->stream);  // open = prev_close = -1
+        if (e != hipSuccess) rc = fail_hip(c, e, "kws_stream_utt_open: hipMemsetAsync");
     }
-    auto drop = [&](int code) { (void)hipStreamSynchronize(c->stream); utt_release(u); return code; };
-    if ((rc = eq_open(c, "kws_stream_utt_open", a.q, LIVE_REC, max_events))) return drop(rc);
-    if ((rc = alloc_endpoint_state(c, "kws_stream_utt_open", S, a.bits, a.counts))) return drop(rc);
-    hipError_t e = hipMemsetAsync(a.hist, 0, hist_b, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(a.pos, 0xFF, pos_b, c->stream);  // open = prev_close = -1
-    if (e != hipSuccess) return drop(fail_hip(c, e, "kws_stream_utt_open: hipMemsetAsync"));
-    c->stream_utt = u;
+    if (rc) {  // the clears enqueued so far finish before u's memory goes
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    c->stream_utt = u.release();
     return KWS_OK;
     KWS_GUARD_END(c, "kws_stream_utt_open")
 }

@@ -31,10 +31,14 @@ struct DetectArgs {
 
 }  // namespace
 
-// Everything kws_stream_detect_open allocates, as the step kernel takes it.
+// Everything kws_stream_detect_open allocates: as the step kernel takes it (a), and the owners a's pointers are filled from.
 struct StreamDetect {
     DetectArgs a{};
     int mode = 0;  // 0: not stepped yet, 1: stepped by pushes, 2: stepped by kws_stream_detect_step_f32
+    DeviceBuffer<float> ring, smoothed;
+    DeviceBuffer<int32_t> label;
+    DeviceBuffer<long long> next;
+    EventQueueMem queue;
 };
 
 namespace {
@@ -117,14 +121,6 @@ __global__ __launch_bounds__(DETECT_MAX_STREAMS) void kws_live_detect_step_kerne
     if (tid == 0) a.q.unit()[0] = decisions;
 }
 
-void detect_release(StreamDetect* u) {
-    if (!u) return;
-    for (void* d : {(void*)u->a.ring, (void*)u->a.smoothed, (void*)u->a.label, (void*)u->a.next})
-        if (d) (void)hipFree(d);
-    eq_release(u->a.q);
-    delete u;
-}
-
 // One launch of the step kernel with the set's state.  Threads: one per stream at least, and up to one per (stream, class) pair
 // for the sums.
 int detect_launch(kws_ctx* c, const float* d_logits, const int* ctx_hops) {
@@ -143,7 +139,7 @@ int detect_launch(kws_ctx* c, const float* d_logits, const int* ctx_hops) {
 }  // namespace
 
 void stream_detect_free(kws_ctx* c) {
-    detect_release(c->stream_detect);
+    delete c->stream_detect;
     c->stream_detect = nullptr;
 }
 
@@ -159,7 +155,7 @@ int stream_detect_pushed(kws_ctx* c, const float* d_logits, const char* fn, int 
     if (u->a.C != model_classes)
         return fail(c, KWS_EINVAL, f + ": kws_stream_detect_open was given another class count than the loaded model's; the hop was taken, no decision was made");
     u->mode = 1;
-    return detect_launch(c, d_logits, c->d_hops);
+    return detect_launch(c, d_logits, c->d_hops.get());
 }
 
 }  // namespace kws
@@ -184,7 +180,7 @@ int kws_stream_detect_open(kws_ctx* c, int C, int smooth_window, int first_keywo
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     stream_detect_free(c);
-    StreamDetect* u = new StreamDetect();
+    std::unique_ptr<StreamDetect> u(new StreamDetect());
     DetectArgs& a = u->a;
     const size_t S = (size_t)c->n_streams;
     a.S = c->n_streams;
@@ -194,21 +190,26 @@ int kws_stream_detect_open(kws_ctx* c, int C, int smooth_window, int first_keywo
     a.refractory = refractory;
     a.first_hop = first_hop;
     a.threshold = threshold;
-    const size_t ring_b = sizeof(float) * S * (size_t)smooth_window * C, sm_b = sizeof(float) * S * C, label_b = sizeof(int32_t) * S,
-                 next_b = sizeof(long long) * S;
-    if (hipMalloc(reinterpret_cast<void**>(&a.ring), ring_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&a.smoothed), sm_b) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&a.label), label_b) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&a.next), next_b) != hipSuccess) {
-        detect_release(u);
+    const size_t sm_b = sizeof(float) * S * C, label_b = sizeof(int32_t) * S, next_b = sizeof(long long) * S;
+    if (!(u->ring.alloc(S * (size_t)smooth_window * C) && u->smoothed.alloc(S * C) && u->label.alloc(S) && u->next.alloc(S)))
         return fail(c, KWS_ENOMEM, "kws_stream_detect_open: allocation failed");
+    a.ring = u->ring.get();
+    a.smoothed = u->smoothed.get();
+    a.label = u->label.get();
+    a.next = u->next.get();
+    int rc = eq_open(c, "kws_stream_detect_open", u->queue, a.q, DETECT_REC, max_events);
+    if (!rc) {
+        // the ring needs no clearing: a decision reads only slots written since the arming
+        hipError_t e = hipMemsetAsync(a.smoothed, 0, sm_b, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(a.label, 0, label_b, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(a.next, 0, next_b, c->stream);
+        if (e != hipSuccess) rc = fail_hip(c, e, "kws_stream_detect_open: hipMemsetAsync");
     }
-    auto drop = [&](int code) { (void)hipStreamSynchronize(c->stream); detect_release(u); return code; };
-    if (int rc = eq_open(c, "kws_stream_detect_open", a.q, DETECT_REC, max_events)) return drop(rc);
-    // the ring needs no clearing: a decision reads only slots written since the arming
-    hipError_t e = hipMemsetAsync(a.smoothed, 0, sm_b, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(a.label, 0, label_b, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(a.next, 0, next_b, c->stream);
-    if (e != hipSuccess) return drop(fail_hip(c, e, "kws_stream_detect_open: hipMemsetAsync"));
-    c->stream_detect = u;
+    if (rc) {  // the clears enqueued so far finish before u's memory goes
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    c->stream_detect = u.release();
     return KWS_OK;
     KWS_GUARD_END(c, "kws_stream_detect_open")
 }

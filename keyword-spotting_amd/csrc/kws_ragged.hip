@@ -86,7 +86,7 @@ int frames_ragged(kws_ctx* c, const char* fn, const T* d_pcm, const int64_t* sta
     RefineList rl{};
     if (p.refine_span > 0.f) {
         if ((rc = ensure_refine(c, 1, (int)(2 * pairs)))) return rc;  // one entry per frame pair of the packed numbering
-        rl = {c->d_refine, c->d_refine + 8, c->refine_cap, 0};
+        rl = {c->d_refine.get(), c->d_refine.get() + 8, c->refine_cap, 0};
     }
     {
         ProfScope ps(c, KWS_K_MFCC);
@@ -105,11 +105,11 @@ int frames_ragged(kws_ctx* c, const char* fn, const T* d_pcm, const int64_t* sta
 // Host-built tables of a ragged call -> context scratch.  The copy is ordered on the context's stream behind the kernels that
 // still read the previous tables, and the stream is drained before the host's copy may go.
 int upload_ragged_tables(kws_ctx* c, const void* host, size_t bytes, const char* fn, const void** d_tables) {
-    int rc = grow_device_buffer(c, c->d_ragged, c->ragged_bytes, bytes, fn, "plan table");
+    int rc = grow_device_buffer(c, c->d_ragged, bytes, fn, "plan table");
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->d_ragged, host, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_ragged.get(), host, bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    *d_tables = c->d_ragged;
+    *d_tables = c->d_ragged.get();
     return KWS_OK;
 }
 
@@ -150,9 +150,9 @@ static int scan_ragged_entry(kws_ctx* c, const ModelOps& m, const char* fn, cons
     HIP_TRY(c, hipSetDevice(c->device));
     float* feat = d_feat_out;
     if (!feat) {
-        rc = grow_device_buffer(c, c->d_scan_ws, c->scan_ws_floats, (size_t)F_pack * c->fp.numcep, fn, "frame workspace");
+        rc = grow_device_buffer(c, c->d_scan_ws, (size_t)F_pack * c->fp.numcep, fn, "frame workspace");
         if (rc) return rc;
-        feat = c->d_scan_ws;
+        feat = c->d_scan_ws.get();
     }
     rc = frames_ragged(c, fn, d_pcm, start, len, R, hop_frames, feat, nullptr);
     if (rc) return rc;

@@ -49,7 +49,7 @@ struct ResamplePlan {
 
 struct ResampleDesign {
     ResamplePlan plan;
-    double* d_taps = nullptr;  // [rows * up]: h, then zeros
+    DeviceBuffer<double> d_taps;  // [rows * up]: h, then zeros
     unsigned long long used = 0;
 };
 
@@ -69,11 +69,10 @@ struct StreamResample : StreamPlan {
     int rate_in = 0, rate_out = 0;
     int n_streams = 0, max_in = 0;
     unsigned long long pos = 0;  // samples received, first_sample included
-    int16_t* d_hist = nullptr;   // [2][n_streams][hist]: a push reads one half and writes the other
+    DeviceBuffer<int16_t> d_hist;  // [2][n_streams][hist]: a push reads one half and writes the other
     int cur = 0;
-    int16_t* d_hop = nullptr;    // [n_streams][frame_step]: the resampled hop of the fused push
-    size_t hop_cap = 0;
-    int16_t* h_in = nullptr;     // [n_streams][max_in], pinned and device-mapped: the input of kws_stream_push_host_rate_i16
+    DeviceBuffer<int16_t> d_hop;   // [n_streams][frame_step]: the resampled hop of the fused push
+    PinnedBuffer<int16_t> h_in;    // [n_streams][max_in], pinned and device-mapped: the input of kws_stream_push_host_rate_i16
 };
 
 namespace {
@@ -263,15 +262,14 @@ int get_design(kws_ctx* c, const ResamplePlan& plan, const char* fn, const Resam
     int rc = replace_device_image(c, fresh.d_taps, h.data(), n * sizeof(double), fn);  // drains the stream
     if (rc) return rc;
     if (cache.designs.size() < (size_t)RS_CACHE_PAIRS) {
-        cache.designs.push_back(fresh);
+        cache.designs.push_back(std::move(fresh));
         out = &cache.designs.back();
         return KWS_OK;
     }
     size_t oldest = 0;
     for (size_t i = 1; i < cache.designs.size(); ++i)
         if (cache.designs[i].used < cache.designs[oldest].used) oldest = i;
-    (void)hipFree(cache.designs[oldest].d_taps);
-    cache.designs[oldest] = fresh;
+    cache.designs[oldest] = std::move(fresh);  // frees the oldest pair's table
     out = &cache.designs[oldest];
     return KWS_OK;
 }
@@ -314,11 +312,11 @@ int resample(kws_ctx* c, const S* d_in, int R, int n_in, const int32_t* d_len, i
     const ResampleArgs a = {n_in, n_out, plan.up, plan.down, plan.half, plan.rows, plan.span, tiles};
     ProfScope ps(c, KWS_K_RESAMPLE);
     if (!plan.staged)
-        launch_resample<S, false, false>(c->stream, plan, d_in, d_len, d_out, d->d_taps, a, R);
+        launch_resample<S, false, false>(c->stream, plan, d_in, d_len, d_out, d->d_taps.get(), a, R);
     else if (plan.up == 1)
-        launch_resample<S, true, true>(c->stream, plan, d_in, d_len, d_out, d->d_taps, a, R);
+        launch_resample<S, true, true>(c->stream, plan, d_in, d_len, d_out, d->d_taps.get(), a, R);
     else
-        launch_resample<S, false, true>(c->stream, plan, d_in, d_len, d_out, d->d_taps, a, R);
+        launch_resample<S, false, true>(c->stream, plan, d_in, d_len, d_out, d->d_taps.get(), a, R);
     HIP_TRY(c, hipGetLastError());
     return KWS_OK;
     KWS_GUARD_END(c, "kws_resample")
@@ -470,14 +468,6 @@ int make_stream_plan(int rate_in, int rate_out, StreamPlan& sp) {
     return KWS_OK;
 }
 
-void stream_resample_release(StreamResample* st) {
-    if (!st) return;
-    if (st->d_hist) (void)hipFree(st->d_hist);
-    if (st->d_hop) (void)hipFree(st->d_hop);
-    if (st->h_in) (void)hipHostFree(st->h_in);
-    delete st;
-}
-
 // The checks every push shares; *n_out = what this push emits.  Nothing is touched.
 int stream_resample_check(kws_ctx* c, const void* in, int n_in, const std::string& name, int* n_out) {
     StreamResample* st = c->stream_resample;
@@ -500,7 +490,7 @@ int stream_resample_enqueue(kws_ctx* c, const int16_t* d_in, int n_in, int16_t* 
         const ResampleDesign* d = nullptr;
         const int rc = get_design(c, p, fn, d);  // the cache may have dropped the pair since the open: designed again then
         if (rc) return rc;
-        d_taps = d->d_taps;
+        d_taps = d->d_taps.get();
         // the first output's newest sample and phase, from the 64-bit position
         const __int128 k0 = (__int128)outputs_before(st->pos, p) - st->delay;
         const __int128 c0 = (__int128)p.half + k0 * p.down;
@@ -512,8 +502,8 @@ int stream_resample_enqueue(kws_ctx* c, const int16_t* d_in, int n_in, int16_t* 
             return fail(c, KWS_EHIP, std::string(fn) + ": internal error, an output's span leaves history || input");
         a.e0 = n_out > 0 ? (int)e0 : p.rows - 1;
     }
-    const int16_t* const h_old = st->d_hist + (size_t)st->cur * st->n_streams * st->hist;
-    int16_t* const h_new = st->d_hist + (size_t)(st->cur ^ 1) * st->n_streams * st->hist;
+    const int16_t* const h_old = st->d_hist.get() + (size_t)st->cur * st->n_streams * st->hist;
+    int16_t* const h_new = st->d_hist.get() + (size_t)(st->cur ^ 1) * st->n_streams * st->hist;
     const size_t lds = st->copy ? 0 : (size_t)(st->hist + n_in) * sizeof(double);
     if (!st->copy && p.up == 1)
         hipLaunchKernelGGL(kws_stream_resample_kernel<true>, dim3((unsigned)(st->n_streams * a.tiles)), dim3(SRS_THREADS), lds, c->stream, d_in,
@@ -545,20 +535,17 @@ int stream_push_rate_check(kws_ctx* c, const void* in, int n_in, const std::stri
     if (rc) return rc;
     if (n_out != c->fp.frame_step)
         return fail(c, KWS_EINVAL, name + ": this push would emit " + std::to_string(n_out) + " samples, a hop is " + std::to_string(c->fp.frame_step));
-    return grow_device_buffer(c, st->d_hop, st->hop_cap, (size_t)st->n_streams * c->fp.frame_step, name.c_str(), "hop buffer");
+    return grow_device_buffer(c, st->d_hop, (size_t)st->n_streams * c->fp.frame_step, name.c_str(), "hop buffer");
 }
 
 }  // namespace
 
 void stream_resample_free(kws_ctx* c) {
-    stream_resample_release(c->stream_resample);
+    delete c->stream_resample;
     c->stream_resample = nullptr;
 }
 
 void resample_free(kws_ctx* c) {
-    if (!c->resample) return;
-    for (ResampleDesign& d : c->resample->designs)
-        if (d.d_taps) (void)hipFree(d.d_taps);
     delete c->resample;
     c->resample = nullptr;
 }
@@ -658,27 +645,21 @@ int kws_stream_resample_open(kws_ctx* c, int n_streams, int rate_in, int rate_ou
         if (rc) return rc;
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // the state being replaced may still be read
-    StreamResample* st = new StreamResample();
+    std::unique_ptr<StreamResample> st(new StreamResample());
     static_cast<StreamPlan&>(*st) = sp;
     st->rate_in = rate_in;
     st->rate_out = rate_out;
     st->n_streams = n_streams;
     st->max_in = max_in;
     st->pos = first_sample;
-    const size_t hist_b = sizeof(int16_t) * 2 * (size_t)n_streams * sp.hist;
-    if (hist_b) {
-        if (hipMalloc(reinterpret_cast<void**>(&st->d_hist), hist_b) != hipSuccess) {
-            stream_resample_release(st);
-            return fail(c, KWS_ENOMEM, name + ": device allocation failed");
-        }
-        const hipError_t e = hipMemsetAsync(st->d_hist, 0, hist_b, c->stream);
-        if (e != hipSuccess) {
-            stream_resample_release(st);
-            return fail_hip(c, e, "kws_stream_resample_open: hipMemsetAsync");
-        }
+    const size_t hist_n = 2 * (size_t)n_streams * sp.hist;
+    if (hist_n) {
+        if (!st->d_hist.alloc(hist_n)) return fail(c, KWS_ENOMEM, name + ": device allocation failed");
+        const hipError_t e = hipMemsetAsync(st->d_hist.get(), 0, sizeof(int16_t) * hist_n, c->stream);
+        if (e != hipSuccess) return fail_hip(c, e, "kws_stream_resample_open: hipMemsetAsync");
     }
     stream_resample_free(c);
-    c->stream_resample = st;
+    c->stream_resample = st.release();
     return KWS_OK;
     KWS_GUARD_END(c, "kws_stream_resample_open")
 }
@@ -711,9 +692,9 @@ int kws_stream_push_rate_i16(kws_ctx* c, const int16_t* d_in, int n_in, float* d
     int rc = stream_push_rate_check(c, d_in, n_in, "kws_stream_push_rate_i16");
     if (rc) return rc;
     StreamResample* st = c->stream_resample;
-    rc = stream_resample_enqueue(c, d_in, n_in, st->d_hop, c->fp.frame_step, c->fp.frame_step, "kws_stream_push_rate_i16");
+    rc = stream_resample_enqueue(c, d_in, n_in, st->d_hop.get(), c->fp.frame_step, c->fp.frame_step, "kws_stream_push_rate_i16");
     if (rc) return rc;
-    rc = kws_stream_push_i16(c, st->d_hop, d_logits, d_label, 0);
+    rc = kws_stream_push_i16(c, st->d_hop.get(), d_logits, d_label, 0);
     if (rc) stream_resample_undo(st, n_in);
     return rc;
     KWS_GUARD_END(c, "kws_stream_push_rate_i16")
@@ -729,17 +710,14 @@ int kws_stream_push_host_rate_i16(kws_ctx* c, const int16_t* h_in, int n_in, con
     if (rc) return rc;
     if (!st->h_in) {
         HIP_TRY(c, hipSetDevice(c->device));
-        if (hipHostMalloc(reinterpret_cast<void**>(&st->h_in), sizeof(int16_t) * (size_t)st->n_streams * st->max_in,
-                          hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-            st->h_in = nullptr;
+        if (!st->h_in.alloc((size_t)st->n_streams * st->max_in, hipHostMallocMapped | hipHostMallocCoherent))
             return fail(c, KWS_ENOMEM, "kws_stream_push_host_rate_i16: pinned host allocation failed");
-        }
     }
     // one slot, as in kws_stream_push_host_i16: this call returns after the push kernel's flag, i.e. after the resampler's reads
-    memcpy(st->h_in, h_in, sizeof(int16_t) * (size_t)st->n_streams * n_in);
-    rc = stream_resample_enqueue(c, st->h_in, n_in, st->d_hop, c->fp.frame_step, c->fp.frame_step, "kws_stream_push_host_rate_i16");
+    memcpy(st->h_in.get(), h_in, sizeof(int16_t) * (size_t)st->n_streams * n_in);
+    rc = stream_resample_enqueue(c, st->h_in.get(), n_in, st->d_hop.get(), c->fp.frame_step, c->fp.frame_step, "kws_stream_push_host_rate_i16");
     if (rc) return rc;
-    rc = kws_stream_push_i16(c, st->d_hop, c->d_hr_logits, c->d_hr_label, 0);
+    rc = kws_stream_push_i16(c, st->d_hop.get(), c->d_hr_logits.get(), c->d_hr_label.get(), 0);
     if (rc) {
         stream_resample_undo(st, n_in);
         return rc;

@@ -149,9 +149,9 @@ static int scan_recordings(kws_ctx* c, const ModelOps& m, const std::string& f, 
     HIP_TRY(c, hipSetDevice(c->device));
     float* feat = d_feat_out;
     if (!feat) {
-        int rc = grow_device_buffer(c, c->d_scan_ws, c->scan_ws_floats, (size_t)R * F * p.numcep, f.c_str(), "frame workspace");
+        int rc = grow_device_buffer(c, c->d_scan_ws, (size_t)R * F * p.numcep, f.c_str(), "frame workspace");
         if (rc) return rc;
-        feat = c->d_scan_ws;
+        feat = c->d_scan_ws.get();
     }
     // the refinement's grid: the batch in one-second clips (R * F <= 2^28 was checked above)
     int rc = run_frontend(c, p, d_pcm, R, feat, (int)((unsigned long long)R * F / T + 1), /*recording_f32=*/true);
@@ -213,9 +213,9 @@ int kws_scan_detect_f32(kws_ctx* c, const float* d_logits, int R, int W, int C, 
     HIP_TRY(c, hipSetDevice(c->device));
     // context scratch: posteriors [R W][C], then per window the candidate label and its score
     const size_t n = (size_t)R * W;
-    int rc = grow_device_buffer(c, c->d_conv_ws, c->conv_ws_floats, n * C + 2 * n, "kws_scan_detect_f32", "workspace");
+    int rc = grow_device_buffer(c, c->d_conv_ws, n * C + 2 * n, "kws_scan_detect_f32", "workspace");
     if (rc) return rc;
-    float* prob = c->d_conv_ws;
+    float* prob = c->d_conv_ws.get();
     float* score = prob + n * C;
     int32_t* cand = reinterpret_cast<int32_t*>(score + n);
     HIP_TRY(c, launch_softmax(c->stream, d_logits, (int)n, C, prob));
@@ -258,12 +258,12 @@ int kws_scan_detect_ragged_f32(kws_ctx* c, const float* d_logits, const int32_t*
     // packed rows [first, end) hold every recording's windows; context scratch as kws_scan_detect_f32 lays it out, indexed by packed row
     const int first = win_off[0];
     const size_t n = (size_t)end;
-    int rc = grow_device_buffer(c, c->d_conv_ws, c->conv_ws_floats, n * C + 2 * n, "kws_scan_detect_ragged_f32", "workspace");
+    int rc = grow_device_buffer(c, c->d_conv_ws, n * C + 2 * n, "kws_scan_detect_ragged_f32", "workspace");
     if (rc) return rc;
     const int2* d_span = nullptr;
     if ((rc = upload_ragged_tables(c, span.data(), sizeof(int2) * span.size(), "kws_scan_detect_ragged_f32", reinterpret_cast<const void**>(&d_span))))
         return rc;
-    float* prob = c->d_conv_ws;
+    float* prob = c->d_conv_ws.get();
     float* score = prob + n * C;
     int32_t* cand = reinterpret_cast<int32_t*>(score + n);
     const int rows = (int)(end - first);

@@ -264,9 +264,9 @@ int kws_segment_f32(kws_ctx* c, const float* d_feat, int R, int F_total, int n_t
     HIP_TRY(c, hipSetDevice(c->device));
     // context scratch: open_ok and close_ok as ballot words, [R][2][n_words] of 64 bits
     const int n_words = (F_total + 63) / 64;
-    rc = grow_device_buffer(c, c->d_conv_ws, c->conv_ws_floats, (size_t)R * 2 * n_words * 2, "kws_segment_f32", "workspace");
+    rc = grow_device_buffer(c, c->d_conv_ws, (size_t)R * 2 * n_words * 2, "kws_segment_f32", "workspace");
     if (rc) return rc;
-    unsigned long long* ok = reinterpret_cast<unsigned long long*>(c->d_conv_ws);
+    unsigned long long* ok = reinterpret_cast<unsigned long long*>(c->d_conv_ws.get());
     const int back = (off_window - 1 + 63) / 64;  // words of history before a workgroup's first frame: <= 16
     const int groups_per_rec = (F_total + SEG_THREADS - 1) / SEG_THREADS;  // R * groups_per_rec <= 2^28 / 256 + R workgroups
     hipLaunchKernelGGL(kws_segment_flags_kernel, dim3((unsigned)R * (unsigned)groups_per_rec), dim3(SEG_THREADS), 0, c->stream, d_feat,
@@ -309,12 +309,12 @@ int kws_segment_ragged_f32(kws_ctx* c, const float* d_feat, const int32_t* frame
     rec[R] = {0, 0, 0, (int)words, (int)groups};
     HIP_TRY(c, hipSetDevice(c->device));
     // context scratch: per recording open_ok and close_ok as ballot words, [2][n_words_r] of 64 bits, one recording after another
-    rc = grow_device_buffer(c, c->d_conv_ws, c->conv_ws_floats, (size_t)words * 2 * 2, "kws_segment_ragged_f32", "workspace");
+    rc = grow_device_buffer(c, c->d_conv_ws, (size_t)words * 2 * 2, "kws_segment_ragged_f32", "workspace");
     if (rc) return rc;
     const SegRec* d_rec = nullptr;
     if ((rc = upload_ragged_tables(c, rec.data(), sizeof(SegRec) * rec.size(), "kws_segment_ragged_f32", reinterpret_cast<const void**>(&d_rec))))
         return rc;
-    unsigned long long* ok = reinterpret_cast<unsigned long long*>(c->d_conv_ws);
+    unsigned long long* ok = reinterpret_cast<unsigned long long*>(c->d_conv_ws.get());
     const int back = (off_window - 1 + 63) / 64;
     hipLaunchKernelGGL(kws_segment_flags_ragged_kernel, dim3((unsigned)groups), dim3(SEG_THREADS), 0, c->stream, d_feat, d_rec, R,
                        c->fp.numcep, log_energy_threshold, on_window, off_window, back, ok);

@@ -10,18 +10,14 @@
 using namespace kws;
 
 // Streaming state: the zero-copy result buffers, then everything kws_stream_open allocates (kws_set_frontend retires it too).
-template <class T>
-static void release(T*& p, bool pinned = false) {
-    if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
-    p = nullptr;
-}
+// The buffers are the context's own (kws_ctx.h); what is reset here with them are the counts that say a set is open.
 static void host_results_free(kws_ctx* c) {
-    release(c->h_stream_logits, true);
-    release(c->h_stream_label, true);
-    release(c->h_stream_flag, true);
-    release(c->h_stream_hop, true);
-    release(c->d_hr_logits);
-    release(c->d_hr_label);
+    c->h_stream_logits.reset();
+    c->h_stream_label.reset();
+    c->h_stream_flag.reset();
+    c->h_stream_hop.reset();
+    c->d_hr_logits.reset();
+    c->d_hr_label.reset();
     c->host_results_classes = 0;
 }
 
@@ -32,18 +28,19 @@ void stream_free(kws_ctx* c) {
     stream_detect_free(c);  // live keyword events (kws_live_detect.hip)
     host_results_free(c);
     drop_stream_graph(c);
-    release(c->d_pcm_ring);
-    release(c->d_feat_ring);
-    release(c->d_hops);
-    release(c->d_cl_part);
-    release(c->d_cl_count);
+    c->d_pcm_ring.reset();
+    c->d_feat_ring.reset();
+    c->d_hops.reset();
+    c->d_cl_part.reset();
+    c->d_cl_count.reset();
     c->n_streams = 0;
 }
 
 // The frame kernel of a multi-launch push: every stream's rings and the hop counter advance by one hop.
 hipError_t stream_enqueue_frame(kws_ctx* c, const int16_t* d_hop, bool timed) {
     ProfScope ps(c, KWS_K_STREAM_FRAME, timed);
-    return launch_stream_frame(c->stream, c->fp, c->ft, d_hop, c->n_streams, c->d_pcm_ring, c->ring_len, c->d_feat_ring, c->d_hops, c->d_refine);
+    return launch_stream_frame(c->stream, c->fp, c->ft, d_hop, c->n_streams, c->d_pcm_ring.get(), c->ring_len, c->d_feat_ring.get(),
+                               c->d_hops.get(), c->d_refine.get());
 }
 
 // The route of a DS-CNN push: logits from one of the product kernels.
@@ -61,17 +58,18 @@ static hipError_t stream_enqueue(kws_ctx* c, const int16_t* d_hop, float* d_logi
         // time-tile clusters while there are CUs to spare: 4 workgroups per stream up to 64 streams, 2 up to 128 (256 CUs)
         const int cluster = c->stream_cluster ? c->stream_cluster : (c->n_streams <= 64 ? 4 : (c->n_streams <= 128 ? 2 : 1));
         const bool host = c->h_stream_flag && c->host_results_classes == c->mw.num_classes;
-        const StreamPush sp = {c->fp, c->ft, d_hop, c->d_pcm_ring, c->ring_len, c->d_hops, c->d_refine, 0, cluster, c->d_cl_part, c->d_cl_count,
-                               host ? c->h_stream_logits : nullptr, host ? c->h_stream_label : nullptr, host ? c->h_stream_flag : nullptr};
+        const StreamPush sp = {c->fp, c->ft, d_hop, c->d_pcm_ring.get(), c->ring_len, c->d_hops.get(), c->d_refine.get(), 0, cluster,
+                               c->d_cl_part.get(), c->d_cl_count.get(), host ? c->h_stream_logits.get() : nullptr,
+                               host ? c->h_stream_label.get() : nullptr, host ? c->h_stream_flag.get() : nullptr};
         c->last_push_host = host;
-        return launch_dscnn_stream(c->stream, c->mw, sp, c->d_feat_ring, c->n_streams, d_logits, d_label, c->pw_math == KWS_PW_PAIR_F16);
+        return launch_dscnn_stream(c->stream, c->mw, sp, c->d_feat_ring.get(), c->n_streams, d_logits, d_label, c->pw_math == KWS_PW_PAIR_F16);
     }
     c->last_push_host = false;
     hipError_t e = stream_enqueue_frame(c, d_hop, timed);
     if (e == hipSuccess && d_logits) {
         ProfScope ps(c, KWS_K_DSCNN, timed);
-        e = launch_dscnn(c->stream, c->mw, c->d_feat_ring, c->n_streams, d_logits, d_label, nullptr, c->pw_math, nullptr, c->d_hops, false,
-                         frames_lag(c->fp));
+        e = launch_dscnn(c->stream, c->mw, c->d_feat_ring.get(), c->n_streams, d_logits, d_label, nullptr, c->pw_math, nullptr,
+                         c->d_hops.get(), false, frames_lag(c->fp));
     }
     return e;
 }
@@ -133,13 +131,9 @@ int kws_stream_open(kws_ctx* c, int n_streams) {
     stream_free(c);
     const FrontendParams& p = c->fp;
     c->ring_len = (frames_lag(p) + 1) * p.frame_step;
-    const size_t pcm_b = sizeof(int16_t) * (size_t)n_streams * c->ring_len;
-    const size_t feat_b = sizeof(float) * (size_t)n_streams * p.num_frames * p.numcep;
-    if (hipMalloc(reinterpret_cast<void**>(&c->d_pcm_ring), pcm_b) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->d_feat_ring), feat_b) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->d_hops), 2 * sizeof(int)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->d_cl_part), sizeof(float) * (size_t)n_streams * 4 * 64) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->d_cl_count), sizeof(int) * (size_t)n_streams) != hipSuccess) {
+    const size_t n = (size_t)n_streams;
+    if (!(c->d_pcm_ring.alloc(n * c->ring_len) && c->d_feat_ring.alloc(n * p.num_frames * p.numcep) && c->d_hops.alloc(2) &&
+          c->d_cl_part.alloc(n * 4 * 64) && c->d_cl_count.alloc(n))) {
         stream_free(c);
         return fail(c, KWS_ENOMEM, "kws_stream_open: device allocation failed");
     }
@@ -151,10 +145,10 @@ int kws_stream_open(kws_ctx* c, int n_streams) {
         int rc = ensure_refine(c, 1, c->fp.num_frames);
         if (rc) return rc;
     }
-    HIP_TRY(c, hipMemsetAsync(c->d_pcm_ring, 0, pcm_b, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_feat_ring, 0, feat_b, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_hops, 0, 2 * sizeof(int), c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_cl_count, 0, sizeof(int) * (size_t)n_streams, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_pcm_ring.get(), 0, sizeof(int16_t) * c->d_pcm_ring.size(), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_feat_ring.get(), 0, sizeof(float) * c->d_feat_ring.size(), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_hops.get(), 0, 2 * sizeof(int), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_cl_count.get(), 0, sizeof(int) * n, c->stream));
     return KWS_OK;
 }
 
@@ -168,21 +162,18 @@ int kws_stream_host_results(kws_ctx* c, int enable) {
     if (!c->model_ready) return fail(c, KWS_ESTATE, "kws_stream_host_results: no model loaded (kws_load_dscnn)");
     const int C = c->mw.num_classes;
     const unsigned flags = hipHostMallocMapped | hipHostMallocCoherent;  // fine-grained: device stores are visible to the host as they land
-    if (hipHostMalloc(reinterpret_cast<void**>(&c->h_stream_logits), sizeof(float) * (size_t)c->n_streams * C, flags) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&c->h_stream_label), sizeof(int32_t) * (size_t)c->n_streams, flags) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&c->h_stream_flag), 64, flags) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&c->h_stream_hop), sizeof(int16_t) * (size_t)c->n_streams * c->fp.frame_step, flags) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->d_hr_logits), sizeof(float) * (size_t)c->n_streams * C) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->d_hr_label), sizeof(int32_t) * (size_t)c->n_streams) != hipSuccess) {
+    const size_t n = (size_t)c->n_streams;
+    if (!(c->h_stream_logits.alloc(n * C, flags) && c->h_stream_label.alloc(n, flags) && c->h_stream_flag.alloc(64 / sizeof(int), flags) &&
+          c->h_stream_hop.alloc(n * c->fp.frame_step, flags) && c->d_hr_logits.alloc(n * C) && c->d_hr_label.alloc(n))) {
         host_results_free(c);
         return fail(c, KWS_ENOMEM, "kws_stream_host_results: pinned host allocation failed");
     }
-    memset(c->h_stream_logits, 0, sizeof(float) * (size_t)c->n_streams * C);
-    memset(c->h_stream_label, 0, sizeof(int32_t) * (size_t)c->n_streams);
+    memset(c->h_stream_logits.get(), 0, sizeof(float) * n * C);
+    memset(c->h_stream_label.get(), 0, sizeof(int32_t) * n);
     // the flag holds the device's push count: start it where the device stands
     int hops = 0;
-    HIP_TRY(c, hipMemcpy(&hops, c->d_hops, sizeof(int), hipMemcpyDeviceToHost));
-    *c->h_stream_flag = hops;
+    HIP_TRY(c, hipMemcpy(&hops, c->d_hops.get(), sizeof(int), hipMemcpyDeviceToHost));
+    *c->h_stream_flag.get() = hops;
     c->pushes_enqueued = hops;
     c->host_push = hops;
     c->host_results_classes = C;
@@ -199,7 +190,7 @@ int kws_stream_wait_host(kws_ctx* c, const float** h_logits, const int32_t** h_l
     // spin on the flag the last workgroup of the newest push raises; bounded: after ~2 ms without it, fall back to the stream
     if (c->host_push != c->pushes_enqueued)
         return fail(c, KWS_ESTATE, "kws_stream_wait_host: the newest push did not deliver to host memory (it asked for no logits, or took a multi-launch route)");
-    volatile int* flag = c->h_stream_flag;
+    volatile int* flag = c->h_stream_flag.get();
     const int want = c->host_push;
     if (!spin_until([&] { return *flag - want >= 0; })) {
         HIP_TRY(c, hipSetDevice(c->device));
@@ -207,8 +198,8 @@ int kws_stream_wait_host(kws_ctx* c, const float** h_logits, const int32_t** h_l
         if (*flag - want < 0) return fail(c, KWS_EHIP, "kws_stream_wait_host: the stream drained but the results flag never arrived");
     }
     std::atomic_thread_fence(std::memory_order_acquire);
-    if (h_logits) *h_logits = c->h_stream_logits;
-    if (h_label) *h_label = c->h_stream_label;
+    if (h_logits) *h_logits = c->h_stream_logits.get();
+    if (h_label) *h_label = c->h_stream_label.get();
     return KWS_OK;
 }
 
@@ -220,8 +211,8 @@ int kws_stream_push_host_i16(kws_ctx* c, const int16_t* h_hop, const float** h_l
     // the hop goes into pinned, device-mapped memory and the kernel reads it from there (one PCIe read of 320 bytes per stream
     // on the frame wavefront's path) -- no H2D submission in front of the launch.  One slot: this call returns after the
     // kernel's last workgroup has raised the flag, i.e. after every read of it.
-    memcpy(c->h_stream_hop, h_hop, sizeof(int16_t) * (size_t)c->n_streams * c->fp.frame_step);
-    int rc = kws_stream_push_i16(c, c->h_stream_hop, c->d_hr_logits, c->d_hr_label, 0);
+    memcpy(c->h_stream_hop.get(), h_hop, sizeof(int16_t) * (size_t)c->n_streams * c->fp.frame_step);
+    int rc = kws_stream_push_i16(c, c->h_stream_hop.get(), c->d_hr_logits.get(), c->d_hr_label.get(), 0);
     if (rc) return rc;
     return kws_stream_wait_host(c, h_logits, h_label);
 }
@@ -273,8 +264,8 @@ int kws_stream_state(kws_ctx* c, const float** d_feat_ring, int* hops) {
     if (!c->n_streams) return fail(c, KWS_ESTATE, "kws_stream_state: no open stream set");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (d_feat_ring) *d_feat_ring = c->d_feat_ring;
-    if (hops) HIP_TRY(c, hipMemcpy(hops, c->d_hops, sizeof(int), hipMemcpyDeviceToHost));
+    if (d_feat_ring) *d_feat_ring = c->d_feat_ring.get();
+    if (hops) HIP_TRY(c, hipMemcpy(hops, c->d_hops.get(), sizeof(int), hipMemcpyDeviceToHost));
     return KWS_OK;
 }
 
@@ -283,7 +274,7 @@ int kws_stream_copy_features(kws_ctx* c, float* d_out) {
     if (!c->n_streams) return fail(c, KWS_ESTATE, "kws_stream_copy_features: no open stream set");
     if (!d_out) return fail(c, KWS_EINVAL, "kws_stream_copy_features: d_out is NULL");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(d_out, c->d_feat_ring, sizeof(float) * (size_t)c->n_streams * c->fp.num_frames * c->fp.numcep,
+    HIP_TRY(c, hipMemcpyAsync(d_out, c->d_feat_ring.get(), sizeof(float) * (size_t)c->n_streams * c->fp.num_frames * c->fp.numcep,
                               hipMemcpyDeviceToDevice, c->stream));
     return KWS_OK;
 }

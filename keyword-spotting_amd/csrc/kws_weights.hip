@@ -158,10 +158,9 @@ static void build_dscnn_image(const float* blob, const DscnnLayout& L, std::vect
     for (size_t i = 0; i < DS_UNIT_WORDS; ++i) img[L.total + i] = ds_unit_word(i);
 }
 
-// Point the context at a complete device image d (layout L); mw holds the values DscnnWeights carries by value.
-static void install_dscnn(kws_ctx* c, float* d, const DscnnLayout& L, DscnnWeights mw) {
-    if (c->d_model && c->d_model != d) (void)hipFree(c->d_model);
-    c->d_model = d;
+// Point the context at the complete device image in c->d_model (layout L); mw holds the values DscnnWeights carries by value.
+static void install_dscnn(kws_ctx* c, const DscnnLayout& L, DscnnWeights mw) {
+    float* const d = c->d_model.get();
     c->ds_image_words = L.total;
     mw.c1_w = d + L.o_c1w;
     mw.c1_b = d + L.o_c1b;
@@ -322,10 +321,9 @@ static void build_cnntrad_image(const float* blob, const CtLayout& L, int num_cl
                    max_abs(blob + L.b_b2, CtLayout::CO));
 }
 
-// Point the context at a complete device image d (layout L); w holds the values CnnTradWeights carries by value.
-static void install_cnntrad(kws_ctx* c, uint32_t* d, const CtLayout& L, const CnnTradWeights& w) {
-    if (c->d_cnntrad && c->d_cnntrad != d) (void)hipFree(c->d_cnntrad);
-    c->d_cnntrad = d;
+// Point the context at the complete device image in c->d_cnntrad (layout L); w holds the values CnnTradWeights carries by value.
+static void install_cnntrad(kws_ctx* c, const CtLayout& L, const CnnTradWeights& w) {
+    uint32_t* const d = c->d_cnntrad.get();
     c->ct_image_words = L.total;
     const float* df = reinterpret_cast<const float*>(d);
     c->tw = w;
@@ -437,7 +435,7 @@ int kws_load_dscnn_ex(kws_ctx* c, const float* blob, size_t n_floats, int num_cl
     rc = replace_device_image(c, c->d_model, h.data(), ds_alloc_words(L) * sizeof(float), "kws_load_dscnn");
     if (rc) return rc;
     drop_stream_graph(c);  // a captured push holds the old weight pointers by value
-    install_dscnn(c, c->d_model, L, mw);
+    install_dscnn(c, L, mw);
     return KWS_OK;
     KWS_GUARD_END(c, "kws_load_dscnn")
 }
@@ -451,23 +449,24 @@ int kws_load_dscnn_device(kws_ctx* c, const float* d_blob, size_t n_floats, int 
     if (rc) return rc;
     const DscnnLayout L(num_classes, input_channels);
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->d_ds_stats) HIP_TRY(c, hipMalloc(&c->d_ds_stats, sizeof(DscnnStats)));
+    if (!c->d_ds_stats && !c->d_ds_stats.alloc(sizeof(DscnnStats)))  // (the words this refusal has always had)
+        return fail_hip(c, hipGetLastError(), "hipMalloc(&c->d_ds_stats, sizeof(DscnnStats))");
     hipStream_t s = c->stream;
     {
         ProfScope ps(c, KWS_K_DSCNN_LOAD_STATS);
-        hipLaunchKernelGGL(kws_ds_load_stats_kernel, dim3(14 + 9), dim3(256), 0, s, d_blob, L, static_cast<DscnnStats*>(c->d_ds_stats));
+        hipLaunchKernelGGL(kws_ds_load_stats_kernel, dim3(14 + 9), dim3(256), 0, s, d_blob, L, reinterpret_cast<DscnnStats*>(c->d_ds_stats.get()));
     }
     HIP_TRY(c, hipGetLastError());
     DscnnStats st;
-    HIP_TRY(c, hipMemcpyAsync(&st, c->d_ds_stats, sizeof st, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&st, c->d_ds_stats.get(), sizeof st, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     DscnnScales sw;
     const DscnnWeights mw = ds_scalars(st, L, sw);
-    // the stream has drained: rewrite an image of this size where it lies, else allocate (install_dscnn frees the old one)
-    float* d = c->d_model;
-    const bool in_place = d && c->ds_image_words == L.total;
-    if (!in_place && hipMalloc(reinterpret_cast<void**>(&d), ds_alloc_words(L) * sizeof(float)) != hipSuccess)
-        return fail(c, KWS_ENOMEM, std::string(fn) + ": device allocation failed");
+    // the stream has drained: rewrite an image of this size where it lies, else build a fresh one beside it and swap after success
+    DeviceBuffer<float> fresh;
+    const bool in_place = c->d_model && c->ds_image_words == L.total;
+    if (!in_place && !fresh.alloc(ds_alloc_words(L))) return fail(c, KWS_ENOMEM, std::string(fn) + ": device allocation failed");
+    float* const d = in_place ? c->d_model.get() : fresh.get();
     drop_stream_graph(c);  // a captured push holds the old weight pointers and scalars by value
     uint32_t* img = reinterpret_cast<uint32_t*>(d);
     hipError_t e;
@@ -481,14 +480,12 @@ int kws_load_dscnn_device(kws_ctx* c, const float* d_blob, size_t n_floats, int 
         hipLaunchKernelGGL(kws_ds_load_fill_kernel, dim3((unsigned)((ds_alloc_words(L) + 255) / 256)), dim3(256), 0, s, d_blob, L, img);
         e = hipGetLastError();
     }
-    if (e != hipSuccess) {  // no mixed image is served: the context's own image may be half rewritten, a fresh one is dropped
-        if (in_place)
-            c->model_ready = false;
-        else
-            (void)hipFree(d);
+    if (e != hipSuccess) {  // no mixed image is served: the context's own image may be half rewritten, a fresh one goes with `fresh`
+        if (in_place) c->model_ready = false;
         return fail_hip(c, e, fn);
     }
-    install_dscnn(c, d, L, mw);
+    if (!in_place) c->d_model = std::move(fresh);  // frees the old image
+    install_dscnn(c, L, mw);
     return KWS_OK;
     KWS_GUARD_END(c, "kws_load_dscnn_device")
 }
@@ -501,7 +498,7 @@ int kws_dscnn_image_read(kws_ctx* c, uint32_t* out_words, size_t cap_words, size
     if (rc) return fail(c, rc, "kws_dscnn_image_read: cap_words is below the image's size");
     if (!out_words) return KWS_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(out_words, c->d_model, c->ds_image_words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out_words, c->d_model.get(), c->ds_image_words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (scalars) dscnn_scalars_out(c->mw, scalars);
     return KWS_OK;
@@ -521,7 +518,7 @@ int kws_load_cnn_trad(kws_ctx* c, const float* blob, size_t n_floats, int num_cl
     HIP_TRY(c, hipSetDevice(c->device));
     rc = replace_device_image(c, c->d_cnntrad, h.data(), L.total * sizeof(uint32_t), "kws_load_cnn_trad");
     if (rc) return rc;
-    install_cnntrad(c, static_cast<uint32_t*>(c->d_cnntrad), L, w);
+    install_cnntrad(c, L, w);
     return KWS_OK;
     KWS_GUARD_END(c, "kws_load_cnn_trad")
 }
@@ -535,19 +532,21 @@ int kws_load_cnn_trad_device(kws_ctx* c, const float* d_blob, size_t n_floats, i
     if (rc) return rc;
     const CtLayout L(num_classes);
     HIP_TRY(c, hipSetDevice(c->device));
-    uint32_t* d = static_cast<uint32_t*>(c->d_cnntrad);
-    if (!d || c->ct_image_words != L.total) {
+    // same size: write into the live image; else build a fresh one beside it and swap after success (a failure lets it go)
+    DeviceBuffer<uint32_t> fresh;
+    const bool in_place = c->d_cnntrad && c->ct_image_words == L.total;
+    if (!in_place) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        d = nullptr;
-        if (hipMalloc(reinterpret_cast<void**>(&d), L.total * sizeof(uint32_t)) != hipSuccess)
-            return fail(c, KWS_ENOMEM, std::string(fn) + ": device allocation failed");
+        if (!fresh.alloc(L.total)) return fail(c, KWS_ENOMEM, std::string(fn) + ": device allocation failed");
     }
-    if (!c->d_ct_stats) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_ct_stats), 16 * sizeof(float)));
+    uint32_t* const d = in_place ? c->d_cnntrad.get() : fresh.get();
+    if (!c->d_ct_stats && !c->d_ct_stats.alloc(16))  // (the words this refusal has always had)
+        return fail_hip(c, hipGetLastError(), "hipMalloc(reinterpret_cast<void**>(&c->d_ct_stats), 16 * sizeof(float))");
     hipStream_t s = c->stream;
-    hipLaunchKernelGGL(kws_ct_load_stats_kernel, dim3(6), dim3(1024), 0, s, d_blob, L, c->d_ct_stats);
+    hipLaunchKernelGGL(kws_ct_load_stats_kernel, dim3(6), dim3(1024), 0, s, d_blob, L, c->d_ct_stats.get());
     HIP_TRY(c, hipGetLastError());
     float st[10];
-    HIP_TRY(c, hipMemcpyAsync(st, c->d_ct_stats, sizeof st, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(st, c->d_ct_stats.get(), sizeof st, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     double rows[2];
     memcpy(rows, st + 6, sizeof rows);
@@ -556,7 +555,8 @@ int kws_load_cnn_trad_device(kws_ctx* c, const float* d_blob, size_t n_floats, i
     HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(kws_ct_load_copy_kernel, dim3((unsigned)((n_floats + 255) / 256)), dim3(256), 0, s, d_blob, L, d);
     HIP_TRY(c, hipGetLastError());
-    install_cnntrad(c, d, L, ct_scalars(num_classes, sw1, sw2, swl, rows[0], rows[1], st[3], st[4]));
+    if (!in_place) c->d_cnntrad = std::move(fresh);  // frees the old image
+    install_cnntrad(c, L, ct_scalars(num_classes, sw1, sw2, swl, rows[0], rows[1], st[3], st[4]));
     return KWS_OK;
     KWS_GUARD_END(c, "kws_load_cnn_trad_device")
 }
