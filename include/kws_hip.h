@@ -689,6 +689,50 @@ int kws_segment_ragged_f32(kws_ctx* ctx, const float* d_feat, const int32_t* fra
                            float log_energy_threshold, int on_window, int off_window, int pre_roll, int max_frames, int32_t* d_utt,
                            int max_utts, int32_t* d_count);
 
+/* ---- scoring a scan against annotations over a threshold sweep: event-level hits, false alarms, duplicates and latency per
+ * class and threshold, on the device, with one read-back of K * C * 4 counters ------------------------------------------- */
+
+/* Events.  For recording r and threshold t the events are exactly those kws_scan_detect_f32 fires with the same smooth_window,
+ * first_keyword, refractory and threshold = t: the same softmax, float32 smoothing sums, first argmax, score >= t comparison in
+ * float32 and walk -- bit for bit, for any float t (0, above 1; NaN: no events).  The smoothing runs once, not per threshold.
+ * Annotations.  truth: HOST int32 [N][4], rows (recording, label, first_window, last_window) in any order, windows relative to
+ * the recording's own.  A row is valid when 0 <= recording < R, first_keyword <= label < C and 0 <= first_window <=
+ * last_window (last_window may lie beyond the recording's last window: nothing fires there).  Two rows of one recording and
+ * one label must not overlap (sharing one window is overlapping); rows of different labels may.
+ * Matching.  Per recording and threshold the events are taken in window order.  For an event (w, k) let j be the annotation of
+ * that recording with label k and first_window <= w <= last_window (at most one).  No j: a false alarm of class k (also inside
+ * an annotation of another label).  j not matched yet at this threshold: a hit of class k, j becomes matched, w - first_window
+ * is added to class k's latency sum.  j matched already: a duplicate of class k, neither hit nor false alarm.
+ * Counts.  d_counts: uint64 [K][C][4] (device) = hits, false alarms, duplicates, latency sum in windows, summed over the call's
+ * recordings; overwritten, not accumulated.  Misses are annotations minus hits.  Integer atomics: deterministic. */
+
+/* Host only: the annotation table validated and sorted.  sorted: int32 [N][4], the rows by (recording, label, first_window);
+ * off: int32 [R * C + 1], rows off[r * C + k] .. off[r * C + k + 1] - 1 of sorted are recording r's label k (off[R * C] = N).
+ * truth is not modified; nothing is written unless KWS_OK.  N = 0 is valid (truth and sorted may be NULL; off is all zeros).
+ *   KWS_EINVAL: a row that is not valid, two overlapping rows of one recording and label, R < 1, C outside [1, 64],
+ *   first_keyword < 0, N < 0, a NULL off, or a NULL truth / sorted with N > 0.  N > 2^24 or R > 2^20: KWS_EUNSUPPORTED. */
+int kws_host_score_plan(const int32_t* truth, int N, int R, int C, int first_keyword, int32_t* sorted, int32_t* off);
+
+/* The counts above for d_logits float32 [R][W][C] (device) at thresholds HOST float [K], K in [1, 1024], any values in any
+ * order, each scored on its own.  truth: HOST, through kws_host_score_plan (its codes pass through).  Launches: softmax, the
+ * smoothing kernel of kws_scan_detect_f32 at a threshold of -inf, a memset of d_counts, one sweep (a wavefront per recording
+ * and threshold).  Asynchronous on the context stream behind the upload of the tables, which waits for the stream's earlier
+ * work; not timed.  Scratch in the context: R * W * (C + 2) floats as kws_scan_detect_f32, and the tables.
+ *   KWS_EINVAL: as kws_scan_detect_f32 for what they share (R or W < 1, C outside [1, 64], S outside [1, 256], refractory < 1,
+ *   first_keyword < 0, a NULL d_logits), a NULL thresholds / d_counts, K outside [1, 1024], N < 0.  R * W > 2^30:
+ *   KWS_EUNSUPPORTED.  A refused call launches nothing and leaves d_counts as it was. */
+int kws_scan_score_f32(kws_ctx* ctx, const float* d_logits, int R, int W, int C, int smooth_window, int first_keyword, int refractory,
+                       const float* thresholds, int K, const int32_t* truth, int N, uint64_t* d_counts);
+
+/* kws_scan_score_f32 per recording of a packed scan: d_logits float32 [W_pack, C], win_off / windows HOST int32 [R] with the
+ * checks and limits of kws_scan_detect_ragged_f32.  The history never crosses a recording's first window, annotations carry
+ * window indices relative to their own recording, rows of no recording change nothing, a recording without windows
+ * contributes nothing, and when no recording has a window d_counts is zeroed.  The counts equal the sum of kws_scan_score_f32
+ * over each recording alone. */
+int kws_scan_score_ragged_f32(kws_ctx* ctx, const float* d_logits, const int32_t* win_off, const int32_t* windows, int R, int C,
+                              int smooth_window, int first_keyword, int refractory, const float* thresholds, int K, const int32_t* truth,
+                              int N, uint64_t* d_counts);
+
 /* ---- live utterances (the same loop, :114-192, for the streams of kws_stream_open: the walk of kws_segment_f32 taken one
  * frame per hop, a PCM history per stream to cut from, events in a queue the host reads without a copy) ------------------ */
 

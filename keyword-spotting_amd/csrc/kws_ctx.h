@@ -1,6 +1,6 @@
 // The context behind the C ABI (include/kws_hip.h), the error plumbing and the device-memory helpers shared by the translation
 // units that implement it (kws_api.hip, kws_stream.hip, kws_cnntrad.hip, kws_frontend.hip, kws_weights.hip, kws_ingest.hip,
-// kws_scan.hip, kws_ragged.hip, kws_decide.hip, kws_eval.hip, kws_resample.hip, kws_live.hip, kws_live_detect.hip, kws_*_bwd.hip),
+// kws_scan.hip, kws_score.hip, kws_ragged.hip, kws_decide.hip, kws_eval.hip, kws_resample.hip, kws_live.hip, kws_live_detect.hip, kws_*_bwd.hip),
 // the table of what the host flows need of a model, and the event bracket of a timed launch.
 // Memory: every device or pinned allocation of the context is a DeviceBuffer / PinnedBuffer member (kws_buffer.h) of kws_ctx or of
 // a sub-state the context points to, and is freed by that member's destructor.  The *_free functions below reset what is not
@@ -250,6 +250,10 @@ inline int alloc_endpoint_state(kws_ctx* c, const char* fn, size_t S, DeviceBuff
 
 // Host-built plan tables of a ragged call -> context scratch (kws_ragged.hip); may wait for the stream.
 int upload_ragged_tables(kws_ctx* c, const void* host, size_t bytes, const char* fn, const void** d_tables);
+// The window tables of a ragged decision call, checked (kws_scan.hip): span[r] = (first packed window, windows), *end = where the
+// packed rows in use end, *total = the windows of all recordings.  fn names the entry in the refusal.
+int scan_ragged_spans(kws_ctx* c, const char* fn, const int32_t* win_off, const int32_t* windows, int R, std::vector<int2>& span,
+                      long long* end, long long* total);
 
 // Bracket a kernel launch with events when profiling is on (timed = false: never, e.g. inside a stream capture).
 struct ProfScope {

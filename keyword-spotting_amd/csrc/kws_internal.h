@@ -367,6 +367,13 @@ hipError_t launch_scan_detect(hipStream_t s, const float* d_logits, int R, int W
                               float threshold, int refractory, float* d_smoothed, int32_t* d_cand, float* d_score,
                               int32_t* d_event_window, int32_t* d_event_label, float* d_event_score, int max_events,
                               int32_t* d_event_count);
+// The first of the two on its own, for the equal-length and the ragged layout (span[r] = (first packed window, windows), n packed
+// rows): what kws_scan_score_f32 shares with the decisions.  A threshold of -inf leaves in d_cand the argmax of every window whose
+// argmax is a keyword, whatever its score.
+hipError_t launch_scan_smooth(hipStream_t s, const float* d_prob, int R, int W, int C, int smooth_window, int first_keyword,
+                              float threshold, float* d_smoothed, int32_t* d_cand, float* d_score);
+hipError_t launch_scan_smooth_ragged(hipStream_t s, const float* d_prob, int n, const int2* d_span, int R, int C, int smooth_window,
+                                     int first_keyword, float threshold, float* d_smoothed, int32_t* d_cand, float* d_score);
 
 extern const char* const kKernelNames[KWS_K_COUNT];
 

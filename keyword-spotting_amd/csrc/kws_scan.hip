@@ -2,6 +2,7 @@
 // pass over each recording as one long clip, the DS-CNN over strided 99-frame windows of the frame array (kws_dscnn_fwd_kernel,
 // SCAN), and the causal decision layer that turns the windows' logits into a short list of events.
 #include "kws_ctx.h"
+#include "kws_scan_dev.h"
 
 using namespace kws;
 
@@ -42,35 +43,31 @@ __global__ __launch_bounds__(256) void kws_scan_smooth_kernel(const float* __res
     scan_smooth_window(p, i, i % W, C, S, first_keyword, threshold, smoothed, cand, score);
 }
 
-// The refractory walk, one wavefront per recording, 64 windows per step: the first candidate lane at or after `next` fires,
-// `next` moves `refractory` windows on, and the step repeats until no candidate lane is left.  Everything but the event stores
-// is wave-uniform; events land in window order with no atomics.
+// The refractory walk (scan_walk, kws_scan_dev.h), one wavefront per recording: a candidate is a window whose cand is a label;
+// events land in window order with no atomics, and everything but the event stores is wave-uniform.
 // cr / sr: the W candidates and scores of recording r (shared by the equal-length and the ragged kernel).
 __device__ __forceinline__ void scan_events_walk(const int32_t* cr, const float* sr, int W, int refractory,
                                                  int32_t* ev_window, int32_t* ev_label,
                                                  float* ev_score, int max_events, int32_t* ev_count, int r,
                                                  int lane) {
-    long long next = 0;
-    int count = 0;
-    for (int w0 = 0; w0 < W; w0 += 64) {
-        const int w = w0 + lane;
-        const int k = w < W ? cr[w] : -1;
-        const float sc = w < W ? sr[w] : 0.f;
-        unsigned long long left = __ballot(k >= 0);
-        while (left) {
-            const int f = __builtin_ctzll(left);
-            left &= left - 1;  // lanes below f are gone already
-            if (w0 + f < next) continue;
-            if (lane == f && count < max_events) {
-                const size_t at = (size_t)r * max_events + count;
-                ev_window[at] = w;
+    int k = -1;
+    float sc = 0.f;
+    const int count = scan_walk(
+        W, refractory,
+        [&](int w0) {
+            const int w = w0 + lane;
+            k = w < W ? cr[w] : -1;
+            sc = w < W ? sr[w] : 0.f;
+            return __ballot(k >= 0);
+        },
+        [&](int w0, int f, int n) {
+            if (lane == f && n < max_events) {
+                const size_t at = (size_t)r * max_events + n;
+                ev_window[at] = w0 + lane;
                 ev_label[at] = k;
                 ev_score[at] = sc;
             }
-            ++count;
-            next = (long long)w0 + f + refractory;
-        }
-    }
+        });
     if (lane == 0) ev_count[r] = count;
 }
 __global__ __launch_bounds__(64) void kws_scan_events_kernel(const int32_t* __restrict__ cand, const float* __restrict__ score, int W,
@@ -115,19 +112,54 @@ __global__ __launch_bounds__(64) void kws_scan_events_ragged_kernel(const int32_
 
 namespace kws {
 
+hipError_t launch_scan_smooth(hipStream_t s, const float* d_prob, int R, int W, int C, int smooth_window, int first_keyword,
+                              float threshold, float* d_smoothed, int32_t* d_cand, float* d_score) {
+    const int n = R * W;
+    hipLaunchKernelGGL(kws_scan_smooth_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_prob, n, W, C, smooth_window, first_keyword,
+                       threshold, d_smoothed, d_cand, d_score);
+    return hipGetLastError();
+}
+
+hipError_t launch_scan_smooth_ragged(hipStream_t s, const float* d_prob, int n, const int2* d_span, int R, int C, int smooth_window,
+                                     int first_keyword, float threshold, float* d_smoothed, int32_t* d_cand, float* d_score) {
+    hipLaunchKernelGGL(kws_scan_smooth_ragged_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_prob, n, d_span, R, C,
+                       smooth_window, first_keyword, threshold, d_smoothed, d_cand, d_score);
+    return hipGetLastError();
+}
+
 hipError_t launch_scan_detect(hipStream_t s, const float* d_prob, int R, int W, int C, int smooth_window, int first_keyword,
                               float threshold, int refractory, float* d_smoothed, int32_t* d_cand, float* d_score,
                               int32_t* d_event_window, int32_t* d_event_label, float* d_event_score, int max_events,
                               int32_t* d_event_count) {
-    const int n = R * W;
-    hipLaunchKernelGGL(kws_scan_smooth_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_prob, n, W, C, smooth_window, first_keyword,
-                       threshold, d_smoothed, d_cand, d_score);
+    hipError_t e = launch_scan_smooth(s, d_prob, R, W, C, smooth_window, first_keyword, threshold, d_smoothed, d_cand, d_score);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kws_scan_events_kernel, dim3(R), dim3(64), 0, s, d_cand, d_score, W, refractory, d_event_window, d_event_label,
                        d_event_score, max_events, d_event_count);
     return hipGetLastError();
 }
 
 }  // namespace kws
+
+// The window tables of a ragged decision call (kws_scan_detect_ragged_f32, kws_scan_score_ragged_f32) -> span[r] = (first packed
+// window, windows); *end: where the packed rows in use end, *total: the windows of all recordings.  fn names the entry.
+int scan_ragged_spans(kws_ctx* c, const char* fn, const int32_t* win_off, const int32_t* windows, int R, std::vector<int2>& span,
+                      long long* end_out, long long* total_out) {
+    const std::string f(fn);
+    span.resize(R);
+    long long end = 0, total = 0;
+    for (int r = 0; r < R; ++r) {
+        if (windows[r] < 0 || win_off[r] < end)
+            return fail(c, KWS_EINVAL, f + ": windows must not be negative and the recordings' windows must not overlap "
+                                       "(win_off ascending, win_off[r] >= win_off[r - 1] + windows[r - 1])");
+        span[r] = make_int2(win_off[r], windows[r]);
+        end = (long long)win_off[r] + windows[r];
+        total += windows[r];
+        if (end > (1ll << 30)) return fail(c, KWS_EUNSUPPORTED, f + ": more than 2^30 packed windows in one call");
+    }
+    *end_out = end;
+    *total_out = total;
+    return KWS_OK;
+}
 
 // kws_scan_i16 / kws_scan_f32 and their cnn-trad-fpool3 twins: the same checks, limits and launches over int16 PCM or float32
 // samples; f names the entry in the error text, src_name its source pointer, m is the model that classifies the windows.
@@ -239,17 +271,9 @@ int kws_scan_detect_ragged_f32(kws_ctx* c, const float* d_logits, const int32_t*
     if (smooth_window < 1 || smooth_window > 256) return fail(c, KWS_EINVAL, "kws_scan_detect_ragged_f32: smooth_window must be in [1, 256]");
     if (refractory < 1 || first_keyword < 0)
         return fail(c, KWS_EINVAL, "kws_scan_detect_ragged_f32: need refractory >= 1 and first_keyword >= 0");
-    std::vector<int2> span(R);
+    std::vector<int2> span;
     long long end = 0, total = 0;  // the packed rows in use end here
-    for (int r = 0; r < R; ++r) {
-        if (windows[r] < 0 || win_off[r] < end)
-            return fail(c, KWS_EINVAL, "kws_scan_detect_ragged_f32: windows must not be negative and the recordings' windows must not overlap "
-                                       "(win_off ascending, win_off[r] >= win_off[r - 1] + windows[r - 1])");
-        span[r] = make_int2(win_off[r], windows[r]);
-        end = (long long)win_off[r] + windows[r];
-        total += windows[r];
-        if (end > (1ll << 30)) return fail(c, KWS_EUNSUPPORTED, "kws_scan_detect_ragged_f32: more than 2^30 packed windows in one call");
-    }
+    if (int rc = scan_ragged_spans(c, "kws_scan_detect_ragged_f32", win_off, windows, R, span, &end, &total)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     if (total == 0) {  // no recording has a window: every count is 0
         HIP_TRY(c, hipMemsetAsync(d_event_count, 0, sizeof(int32_t) * (size_t)R, c->stream));
@@ -268,9 +292,7 @@ int kws_scan_detect_ragged_f32(kws_ctx* c, const float* d_logits, const int32_t*
     int32_t* cand = reinterpret_cast<int32_t*>(score + n);
     const int rows = (int)(end - first);
     HIP_TRY(c, launch_softmax(c->stream, d_logits + (size_t)first * C, rows, C, prob + (size_t)first * C));
-    hipLaunchKernelGGL(kws_scan_smooth_ragged_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, prob, (int)n, d_span, R, C,
-                       smooth_window, first_keyword, threshold, d_smoothed, cand, score);
-    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, launch_scan_smooth_ragged(c->stream, prob, (int)n, d_span, R, C, smooth_window, first_keyword, threshold, d_smoothed, cand, score));
     hipLaunchKernelGGL(kws_scan_events_ragged_kernel, dim3(R), dim3(64), 0, c->stream, cand, score, d_span, refractory, d_event_window,
                        d_event_label, d_event_score, max_events, d_event_count);
     HIP_TRY(c, hipGetLastError());

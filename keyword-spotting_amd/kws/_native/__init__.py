@@ -117,6 +117,11 @@ SIGNATURES = {
     "kws_scan_ragged_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, _h_i64p, _h_i32p, C.c_int, C.c_int, _f32p, _i32p, _f32p]),
     "kws_scan_detect_ragged_f32": (C.c_int, [_c_ctx, _f32p, _h_i32p, _h_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _f32p,
                                              _i32p, _i32p, _f32p, C.c_int, _i32p]),
+    "kws_host_score_plan": (C.c_int, [_h_i32p, C.c_int, C.c_int, C.c_int, C.c_int, _h_i32p, _h_i32p]),
+    "kws_scan_score_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int,
+                                     _h_i32p, C.c_int, C.c_void_p]),
+    "kws_scan_score_ragged_f32": (C.c_int, [_c_ctx, _f32p, _h_i32p, _h_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.POINTER(C.c_float), C.c_int, _h_i32p, C.c_int, C.c_void_p]),
     "kws_segment_ragged_f32": (C.c_int, [_c_ctx, _f32p, _h_i32p, _h_i32p, _h_i32p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int,
                                          _i32p, C.c_int, _i32p]),
     "kws_host_stream_utt_history": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int)]),
@@ -611,6 +616,27 @@ class Context:
                                                          int(refractory), p(smoothed), p(event_window), p(event_label), p(event_score),
                                                          int(max_events), _ptr(event_count)), ModelError)
 
+    # -- scoring against annotations ---------------------------------------------------------------
+    def scan_score_f32(self, logits, smooth_window, first_keyword, refractory, thresholds, truth, counts):
+        """``kws_scan_score_f32``: ``logits`` float32 [R, W, C] on the device scored against ``truth`` (host, int32 [N, 4] rows
+        (recording, label, first_window, last_window), or None / empty) at every one of ``thresholds`` (host, float32 [K]):
+        ``counts`` int64 [K, C, 4] on the device = hits, false alarms, duplicates, latency sum.  Read it after ``sync``."""
+        R, W, Cn = (int(v) for v in logits.shape)
+        th, tr = _host_f32(thresholds), _host_truth(truth)
+        self._check(self._lib.kws_scan_score_f32(self._h, _ptr(logits), R, W, Cn, int(smooth_window), int(first_keyword), int(refractory),
+                                                 _as(th, C.c_float), len(th), _as(tr, C.c_int32) if len(tr) else None, len(tr),
+                                                 _ptr(counts)), ModelError)
+
+    def scan_score_ragged_f32(self, logits, win_off, windows, smooth_window, first_keyword, refractory, thresholds, truth, counts):
+        """``kws_scan_score_ragged_f32``: ``scan_score_f32`` per recording of the packed ``logits`` float32 [W_pack, C];
+        ``win_off`` / ``windows`` host sequences [R]; the windows of ``truth`` are relative to their own recording."""
+        wo, wn = _host_i32(win_off), _host_i32(windows)
+        th, tr = _host_f32(thresholds), _host_truth(truth)
+        self._check(self._lib.kws_scan_score_ragged_f32(self._h, _ptr(logits), _as(wo, C.c_int32), _as(wn, C.c_int32), len(wn),
+                                                        int(logits.shape[-1]), int(smooth_window), int(first_keyword), int(refractory),
+                                                        _as(th, C.c_float), len(th), _as(tr, C.c_int32) if len(tr) else None, len(tr),
+                                                        _ptr(counts)), ModelError)
+
     def segment_ragged_f32(self, feat, frame_off, frames, length, threshold, count, utt=None, max_utts=0, on_window=40, off_window=80,
                            pre_roll=60, max_frames=1000):
         """``kws_segment_ragged_f32``: the endpointer of ``segment_f32`` per recording of the packed ``feat`` float32
@@ -975,6 +1001,37 @@ def _host_i64(v) -> np.ndarray:
 
 def _as(a: np.ndarray, ctype):
     return a.ctypes.data_as(C.POINTER(ctype))
+
+
+def _host_f32(v) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(v, dtype=np.float32).reshape(-1))
+
+
+def _host_truth(truth) -> np.ndarray:
+    """An annotation table (or None) as a contiguous int32 [N, 4] copy."""
+    t = np.zeros((0, 4), np.int32) if truth is None else np.array(truth, dtype=np.int32)
+    if t.size == 0:
+        return np.zeros((0, 4), np.int32)
+    if t.ndim != 2 or t.shape[1] != 4:
+        raise KWSError(f"an annotation table is int32 [N, 4] = (recording, label, first_window, last_window), got shape {t.shape}")
+    return np.ascontiguousarray(t)
+
+
+def host_score_plan(truth, n_recordings, num_classes, first_keyword=2):
+    """``kws_host_score_plan``: the annotation table ``truth`` int32 [N, 4] = (recording, label, first_window, last_window)
+    validated -> ``(sorted [N, 4], off [R * C + 1])``: the rows by (recording, label, first_window) and where each (recording,
+    label) list begins.  ``KWSError`` for a bad row, overlapping rows of one recording and label, or sizes out of range."""
+    t = _host_truth(truth)
+    n = len(t)
+    srt = np.zeros((n, 4), np.int32)
+    off = np.zeros(max(int(n_recordings) * int(num_classes), 0) + 1, np.int32)
+    rc = lib().kws_host_score_plan(_as(t, C.c_int32) if n else None, n, int(n_recordings), int(num_classes), int(first_keyword),
+                                   _as(srt, C.c_int32) if n else None, _as(off, C.c_int32))
+    if rc != KWS_OK:
+        raise KWSError(f"kws_host_score_plan failed ({rc}): rows need 0 <= recording < R, first_keyword <= label < C <= 64, "
+                       "0 <= first_window <= last_window and no overlap within one recording and label; at most 2^24 rows and 2^20 "
+                       "recordings")
+    return srt, off
 
 
 def host_ragged_plan(lengths, frame_len=400, frame_step=160, window_frames=99, hop_frames=1):

@@ -361,6 +361,89 @@ class KeywordSpotter:
                        for i in range(min(int(count[r]), m))] for r in range(R)]
         return ScanResult(labels.cpu().numpy(), logits.cpu().numpy(), start_s, events)
 
+    def score(self, pcm, truth, thresholds, hop_frames: int = 1, smooth_window: int = 1, refractory: int = 50, first_keyword: int = 2,
+              tolerance_s: float = 1.0, sample_rate: Optional[int] = None):
+        """How many keywords would ``scan`` find, miss and invent at each of ``thresholds``?  ``pcm`` as ``scan`` takes it;
+        ``truth``: per recording a list of ``(word_or_index, t0, t1)`` in seconds (for one recording ``[n]`` the list itself),
+        mapped to windows by ``kws.libs.evaluation.truth_windows`` with ``tolerance_s``.  Returns a ``DetectionReport``: per
+        threshold and class the hits, false alarms and duplicates of exactly the events ``scan(threshold=t, smooth_window=...,
+        refractory=..., first_keyword=...)`` fires, matched in time order against the annotations, and the hits' latency.
+
+        On the device: the scan (``kws_scan_i16``), then ``kws_scan_score_f32`` -- the smoothing once, one walk per recording and
+        threshold.  The logits stay on the device; the one read-back is the ``K * C * 4`` counters."""
+        return self._score(self._recordings(pcm, "score"), "score", truth, thresholds, hop_frames, smooth_window, refractory,
+                           first_keyword, tolerance_s, sample_rate)
+
+    def score_f32(self, signal, truth, thresholds, hop_frames: int = 1, smooth_window: int = 1, refractory: int = 50,
+                  first_keyword: int = 2, tolerance_s: float = 1.0, sample_rate: Optional[int] = None):
+        """``score`` for float32 samples in [-1, 1] (``scan_f32``): for ``signal = pcm / 32768`` the counts equal ``score(pcm)``'s."""
+        return self._score(self._recordings(signal, "score_f32", f32=True), "score_f32", truth, thresholds, hop_frames, smooth_window,
+                           refractory, first_keyword, tolerance_s, sample_rate)
+
+    @staticmethod
+    def _score_args(what: str, thresholds, hop_frames, smooth_window, refractory, first_keyword) -> np.ndarray:
+        """The argument checks ``score`` and ``score_batch`` share (no device needed) -> the thresholds as float32 [K]."""
+        th = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float32).reshape(-1))
+        if not 1 <= len(th) <= 1024:
+            raise ModelError(f"{what}: between 1 and 1024 thresholds are needed, got {len(th)}")
+        if int(hop_frames) < 1:
+            raise ModelError(f"{what}: hop_frames must be at least 1")
+        if not 1 <= int(smooth_window) <= 256:
+            raise ModelError(f"{what}: smooth_window must be in [1, 256]")
+        if int(refractory) < 1 or int(first_keyword) < 0:
+            raise ModelError(f"{what}: need refractory >= 1 and first_keyword >= 0")
+        return th
+
+    @staticmethod
+    def _truth_lists(what: str, truth, R: int) -> list:
+        """``truth`` -> one list of annotations per recording; a single recording may give its list directly."""
+        lists = list(truth) if truth is not None else []
+        if R == 1 and (not lists or (len(lists[0]) == 3 and (isinstance(lists[0][0], str) or np.ndim(lists[0][0]) == 0))):
+            lists = [lists]
+        if len(lists) != R:
+            raise ModelError(f"{what}: {len(lists)} annotation lists for {R} recordings")
+        return [list(t) for t in lists]
+
+    def _score_report(self, ctx, score_call, th, truths, end_times, tolerance_s, hours, hop_frames, frame_step):
+        """Annotations -> the window table, the native call, the one read-back, the report."""
+        from kws.libs.evaluation import DetectionReport, truth_windows
+
+        C = self.model.num_classes
+        n_truth, undetectable, rows = np.zeros(C, np.int64), np.zeros(C, np.int64), []
+        for r, (t, end_s) in enumerate(zip(truths, end_times)):
+            table, n, u = truth_windows(t, end_s, tolerance_s, self.words, C, r)
+            rows.append(table)
+            n_truth += n
+            undetectable += u
+        counts = torch.empty((len(th), C, 4), dtype=torch.int64, device=self.device)
+        score_call(np.concatenate(rows) if rows else None, counts)
+        ctx.sync()
+        return DetectionReport(counts.cpu().numpy(), n_truth, undetectable, th, hours, int(hop_frames) * frame_step / self.config.sample_rate,
+                               self.words)
+
+    def _score(self, x: torch.Tensor, what: str, truth, thresholds, hop_frames, smooth_window, refractory, first_keyword, tolerance_s,
+               sample_rate):
+        """``score`` / ``score_f32`` behind their argument's type check; the sample type of ``x`` picks the entries."""
+        from kws import _native
+
+        th = self._score_args(what, thresholds, hop_frames, smooth_window, refractory, first_keyword)
+        cfg = self.config
+        truths = self._truth_lists(what, truth, int(x.shape[0]))
+        hours = float(x.shape[0]) * float(x.shape[1]) / float(sample_rate or cfg.sample_rate) / 3600.0
+        x = self._at_configured_rate(x, sample_rate, what)
+        frame_len, frame_step = _round_half_up(cfg.frame_length * cfg.sample_rate), _round_half_up(cfg.frame_step * cfg.sample_rate)
+        R, n = int(x.shape[0]), int(x.shape[1])
+        frames, W = (0, 0) if n < 1 else _native.host_scan_shape(n, frame_len, frame_step, WINDOW_FRAMES, int(hop_frames))
+        if W < 1:
+            raise ModelError(f"{what}: a recording of {n} samples ({frames} frames) is shorter than one window of {WINDOW_FRAMES} frames")
+        ctx = self.model._context(self.device.index or 0)
+        x = x.to(self.device).contiguous()
+        logits = torch.empty((R, W, self.model.num_classes), dtype=torch.float32, device=self.device)
+        self.model._native_scan(ctx, x, int(hop_frames), logits, None)
+        _, end_s = scan_window_times(W, int(hop_frames), frame_len, frame_step, cfg.sample_rate, WINDOW_FRAMES, n)
+        call = lambda table, counts: ctx.scan_score_f32(logits, smooth_window, first_keyword, refractory, th, table, counts)
+        return self._score_report(ctx, call, th, truths, [end_s] * R, tolerance_s, hours, hop_frames, frame_step)
+
     def scan_file(self, path: str, resample: bool = False, decode: str = "pcm16", **kwargs) -> ScanResult:
         """``scan`` over a whole wav file (no trimming or padding to a clip).  The file must be 16-bit mono PCM at the
         configured rate: anything else raises ``AudioProcessingError`` with the reason.  With ``resample=True`` a 16-bit mono
@@ -687,6 +770,45 @@ class KeywordSpotter:
                            for i in range(min(int(count[r]), m))]]
             out.append(ScanResult(labels_h[o:o + W][None, :].copy(), logits_h[o:o + W][None, :, :].copy(), start_s, events))
         return out
+
+    def score_batch(self, recordings, truths, thresholds, hop_frames: int = 1, smooth_window: int = 1, refractory: int = 50,
+                    first_keyword: int = 2, tolerance_s: float = 1.0, sample_rate=None):
+        """``score`` for a batch of recordings of unequal length in one pass (``recordings`` and ``sample_rate`` as ``scan_batch``;
+        ``truths``: one annotation list per recording).  The report's counts equal the sum of ``score(recordings[r], truths[r],
+        ...)`` over the recordings; a recording shorter than one window has no windows, so its annotations are undetectable
+        (``kws_scan_ragged_i16``, ``kws_scan_score_ragged_f32``)."""
+        return self._score_batch(recordings, "score_batch", False, truths, thresholds, hop_frames, smooth_window, refractory, first_keyword,
+                                 tolerance_s, sample_rate)
+
+    def score_batch_f32(self, recordings, truths, thresholds, hop_frames: int = 1, smooth_window: int = 1, refractory: int = 50,
+                        first_keyword: int = 2, tolerance_s: float = 1.0, sample_rate=None):
+        """``score_batch`` for a sequence of float32 ``[n_r]`` recordings (``kws_scan_ragged_f32``)."""
+        return self._score_batch(recordings, "score_batch_f32", True, truths, thresholds, hop_frames, smooth_window, refractory,
+                                 first_keyword, tolerance_s, sample_rate)
+
+    def _score_batch(self, recordings, what: str, f32: bool, truths, thresholds, hop_frames, smooth_window, refractory, first_keyword,
+                     tolerance_s, sample_rate):
+        from kws import _native
+
+        recs, rates = self._batch_recordings(recordings, sample_rate, what, f32)
+        th = self._score_args(what, thresholds, hop_frames, smooth_window, refractory, first_keyword)
+        lists = [list(t) if t is not None else [] for t in (truths if truths is not None else [[]] * len(recs))]
+        if len(lists) != len(recs):
+            raise ModelError(f"{what}: {len(lists)} annotation lists for {len(recs)} recordings")
+        cfg = self.config
+        hours = sum(float(x.shape[0]) / float(rate) for x, rate in zip(recs, rates)) / 3600.0
+        frame_len, frame_step = _round_half_up(cfg.frame_length * cfg.sample_rate), _round_half_up(cfg.frame_step * cfg.sample_rate)
+        buf, start, length = self._pack_batch(recs, rates)
+        R, hop = len(recs), int(hop_frames)
+        _, _, windows, win_off, W_pack = _native.host_ragged_plan(length, frame_len, frame_step, WINDOW_FRAMES, hop)
+        ctx = self.model._context(self.device.index or 0)
+        logits = torch.empty((max(W_pack, 1), self.model.num_classes), dtype=torch.float32, device=self.device)
+        self.model._native_scan_ragged(ctx, buf, start, length, hop, logits, None)
+        ends = [scan_window_times(int(windows[r]), hop, frame_len, frame_step, cfg.sample_rate, WINDOW_FRAMES, int(length[r]))[1]
+                for r in range(R)]
+        call = lambda table, counts: ctx.scan_score_ragged_f32(logits, win_off, windows, smooth_window, first_keyword, refractory, th, table,
+                                                               counts)
+        return self._score_report(ctx, call, th, lists, ends, tolerance_s, hours, hop, frame_step)
 
     def segment_batch(self, recordings, threshold: float, on_window: int = 40, off_window: int = 80, pre_roll: int = 60,
                       max_seconds: float = 10.0, normalize: int = 16384, max_utterances: int = 1024, sample_rate=None,

@@ -10,6 +10,10 @@ Here ``Evaluator.update(logits, labels)`` enqueues ``kws_eval_update_f32`` on to
 device memory take the batch (and the call optionally returns the cross-entropy gradient, so a training step has its loss and
 accuracy without a synchronisation); ``Evaluator.report()`` synchronises once and returns an ``EvalReport``, plain NumPy, which
 derives every figure from the counts.  ``evaluate(model, loader)`` is the validation pass around it.
+
+Recordings are judged at the event level: ``KeywordSpotter.score`` scores a scan against annotations over a threshold sweep on the
+device (``kws_scan_score_f32``) and returns a ``DetectionReport`` -- false alarms per hour against miss rate per threshold;
+``truth_windows`` turns annotations in seconds into the window ranges it takes.
 """
 from __future__ import annotations
 
@@ -195,6 +199,144 @@ class EvalReport:
     def far_micro_mean(self) -> float:
         """``np.average(fpr["micro"])`` (``test.py:58``)."""
         return float(np.mean(self.roc_micro()[0]))
+
+
+def truth_windows(truth, end_s, tolerance_s: float = 1.0, words: Optional[Sequence[str]] = None, num_classes: Optional[int] = None,
+                  recording: int = 0):
+    """Annotations in seconds -> rows of the table ``kws_scan_score_f32`` takes, for ONE recording.
+
+    ``truth``: a sequence of ``(word_or_index, t0, t1)``, a keyword spoken from ``t0`` to ``t1`` seconds; a word is looked up in
+    ``words``.  ``end_s``: the end time of every window of the recording, ascending (``scan_window_times``) -- the time
+    ``ScanResult.events`` reports for an event.  A truth maps to the windows whose end time lies in ``[t0, t1 + tolerance_s]``.
+    The default ``tolerance_s = 1.0`` is one window length: a detector that fires once the whole word is inside its window fires
+    up to a window after the word began, and an API choice, not a measured figure.
+
+    Returns ``(rows int32 [N, 4], n_truth int64 [C], undetectable int64 [C])``, rows ``(recording, label, first_window,
+    last_window)``.  A truth whose range holds no window (before the first window ends, after the last) is *undetectable*: it
+    is counted in ``n_truth`` and in ``undetectable`` and left out of the rows.  Where two ranges of one label would overlap,
+    the earlier one ends one window before the later one begins (and is undetectable if nothing is left of it)."""
+    C = int(num_classes) if num_classes is not None else (len(words) if words is not None else None)
+    if C is None:
+        raise ModelError("truth_windows: give words or num_classes")
+    end_s = np.asarray(end_s, dtype=np.float64).reshape(-1)
+    n_truth, undetectable = np.zeros(C, np.int64), np.zeros(C, np.int64)
+    ranges: dict = {}
+    for item in truth:
+        k, t0, t1 = item
+        if isinstance(k, str):
+            if words is None or k not in list(words):
+                raise ModelError(f"truth_windows: {k!r} is not one of the model's words")
+            k = list(words).index(k)
+        k = int(k)
+        if not 0 <= k < C or not float(t0) <= float(t1):
+            raise ModelError(f"truth_windows: {item!r} needs a label in [0, {C}) and t0 <= t1")
+        n_truth[k] += 1
+        first = int(np.searchsorted(end_s, float(t0), "left"))
+        last = int(np.searchsorted(end_s, float(t1) + float(tolerance_s), "right")) - 1
+        if first > last:
+            undetectable[k] += 1
+        else:
+            ranges.setdefault(k, []).append([first, last])
+    rows = []
+    for k in sorted(ranges):
+        lst = sorted(ranges[k])
+        for i, (first, last) in enumerate(lst):
+            if i + 1 < len(lst):
+                last = min(last, lst[i + 1][0] - 1)
+            if first > last:
+                undetectable[k] += 1
+            else:
+                rows.append((int(recording), k, first, last))
+    return np.asarray(rows, np.int32).reshape(-1, 4), n_truth, undetectable
+
+
+class DetectionReport:
+    """Event-level detection figures over a threshold sweep, from the counters of ``kws_scan_score_f32``.  Plain NumPy.
+
+    ``counts`` int64 [K, C, 4] = per threshold and class the hits, false alarms, duplicates and the hits' latency sum in windows;
+    ``n_truth`` [C]: the annotations per class, the ``undetectable`` [C] among them included (they can only be missed);
+    ``thresholds`` [K]; ``hours``: the audio scanned; ``hop_s``: seconds between two windows; ``words``: one per class.
+    Reports of the same sweep over different audio add (``a + b``): the library does not accumulate across calls.
+
+    With ``c=None`` a figure is over all classes together (sums, then the ratio), else of class ``c``; each is an array [K].
+    A ratio with a zero denominator is 0."""
+
+    def __init__(self, counts, n_truth, undetectable, thresholds, hours: float, hop_s: float, words: Optional[Sequence[str]] = None):
+        self.counts = np.asarray(counts).astype(np.int64)
+        if self.counts.ndim != 3 or self.counts.shape[2] != 4:
+            raise ModelError("DetectionReport: counts must be [K, C, 4]")
+        K, C = self.counts.shape[:2]
+        self.n_truth = np.asarray(n_truth).astype(np.int64).reshape(-1)
+        self.undetectable = np.asarray(undetectable).astype(np.int64).reshape(-1)
+        self.thresholds = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+        if self.n_truth.shape != (C,) or self.undetectable.shape != (C,) or self.thresholds.shape != (K,):
+            raise ModelError("DetectionReport: n_truth and undetectable must be [C], thresholds [K]")
+        self.hours, self.hop_s = float(hours), float(hop_s)
+        self.words = list(words) if words is not None else [str(c) for c in range(C)]
+        if len(self.words) != C:
+            raise ModelError("DetectionReport: one word per class is required")
+
+    def __add__(self, other: "DetectionReport") -> "DetectionReport":
+        if self.counts.shape != other.counts.shape or not np.array_equal(self.thresholds, other.thresholds, equal_nan=True) \
+                or self.hop_s != other.hop_s:
+            raise ModelError("DetectionReport: only reports of the same thresholds, classes and hop add")
+        return DetectionReport(self.counts + other.counts, self.n_truth + other.n_truth, self.undetectable + other.undetectable,
+                               self.thresholds, self.hours + other.hours, self.hop_s, self.words)
+
+    @property
+    def hits(self) -> np.ndarray:
+        return self.counts[:, :, 0]
+
+    @property
+    def false_alarms(self) -> np.ndarray:
+        return self.counts[:, :, 1]
+
+    @property
+    def duplicates(self) -> np.ndarray:
+        return self.counts[:, :, 2]
+
+    @property
+    def misses(self) -> np.ndarray:
+        """[K, C]: the annotations no event hit, the undetectable ones among them."""
+        return self.n_truth[None, :] - self.hits
+
+    def _of(self, a: np.ndarray, c) -> np.ndarray:
+        return a.sum(axis=-1) if c is None else a[..., int(c)]
+
+    def miss_rate(self, c=None) -> np.ndarray:
+        return _ratio(self._of(self.misses, c), self._of(self.n_truth, c))
+
+    def false_alarms_per_hour(self, c=None) -> np.ndarray:
+        return _ratio(self._of(self.false_alarms, c), self.hours)
+
+    def mean_latency_s(self, c=None) -> np.ndarray:
+        """The mean, over the hits, of the time from the annotation's first window to the window that hit it."""
+        return _ratio(self._of(self.counts[:, :, 3], c), self._of(self.hits, c)) * self.hop_s
+
+    def det_curve(self, c=None) -> Curve:
+        """(false alarms per hour, miss rate, thresholds), by ascending threshold (a NaN threshold last)."""
+        order = np.argsort(self.thresholds, kind="stable")
+        return self.false_alarms_per_hour(c)[order], self.miss_rate(c)[order], self.thresholds[order]
+
+    def threshold_for(self, max_false_alarms_per_hour: float, c=None) -> Optional[float]:
+        """The threshold with the lowest miss rate among those with at most ``max_false_alarms_per_hour``; of several, the one
+        with the fewest false alarms, then the highest.  ``None`` when no threshold of the sweep meets the bound."""
+        fa, mr = self.false_alarms_per_hour(c), self.miss_rate(c)
+        ok = [i for i in range(len(self.thresholds)) if fa[i] <= float(max_false_alarms_per_hour) and not np.isnan(self.thresholds[i])]
+        if not ok:
+            return None
+        return float(self.thresholds[min(ok, key=lambda i: (mr[i], fa[i], -self.thresholds[i]))])
+
+    def format(self, digits: int = 3) -> str:
+        """A text table, one row per threshold in ascending order, over all classes together."""
+        head = " ".join(f"{h:>10}" for h in ("threshold", "hits", "misses", "false_al", "dupl", "miss_rate", "fa_per_h", "latency_s"))
+        lines = [f"{int(self.n_truth.sum())} annotations ({int(self.undetectable.sum())} undetectable), {self.hours:.{digits}f} h", head]
+        mr, fa, lat = self.miss_rate(), self.false_alarms_per_hour(), self.mean_latency_s()
+        for i in np.argsort(self.thresholds, kind="stable"):
+            lines.append(f"{self.thresholds[i]:>10.{digits}f} {int(self.hits[i].sum()):>10d} {int(self.misses[i].sum()):>10d} "
+                         f"{int(self.false_alarms[i].sum()):>10d} {int(self.duplicates[i].sum()):>10d} {mr[i]:>10.{digits}f} "
+                         f"{fa[i]:>10.{digits}f} {lat[i]:>10.{digits}f}")
+        return "\n".join(lines) + "\n"
 
 
 class Evaluator:
