@@ -250,10 +250,29 @@ inline int alloc_endpoint_state(kws_ctx* c, const char* fn, size_t S, DeviceBuff
 
 // Host-built plan tables of a ragged call -> context scratch (kws_ragged.hip); may wait for the stream.
 int upload_ragged_tables(kws_ctx* c, const void* host, size_t bytes, const char* fn, const void** d_tables);
-// The window tables of a ragged decision call, checked (kws_scan.hip): span[r] = (first packed window, windows), *end = where the
-// packed rows in use end, *total = the windows of all recordings.  fn names the entry in the refusal.
-int scan_ragged_spans(kws_ctx* c, const char* fn, const int32_t* win_off, const int32_t* windows, int R, std::vector<int2>& span,
-                      long long* end, long long* total);
+// What the four decision entries (kws_scan_detect_f32, kws_scan_score_f32, their ragged twins) share on the host, kws_scan.hip.
+struct WindowBatch {          // the windows of R recordings among the rows of a logits array
+    int R = 0;
+    int W = 0;                // equal length: windows per recording; ragged: unused
+    std::vector<int2> span;   // ragged: (first packed row, windows) per recording; empty for equal length
+    long long first = 0, end = 0, total = 0;   // rows in use [first, end), windows of all recordings
+    bool ragged() const { return !span.empty(); }
+};
+constexpr int MAX_RAGGED_RECORDINGS = 1 << 20;
+// The two makers, each with its layout's own refusals (R >= 1 is decision_check's); fn names the entry in every refusal.
+int scan_equal_windows(kws_ctx* c, const char* fn, int R, int W, WindowBatch& b);
+int scan_ragged_spans(kws_ctx* c, const char* fn, const int32_t* win_off, const int32_t* windows, int R, WindowBatch& b);
+// R and C, smooth_window, then refractory and first_keyword.  W: kws_scan_detect_f32 alone names its W in the first sentence (the
+// score entry refuses W later, scan_equal_windows); recordings_first: kws_scan_detect_ragged_f32 alone refuses more than 2^20
+// recordings ahead of smooth_window (the score entry later, scan_ragged_spans).
+int decision_check(kws_ctx* c, const char* fn, int R, int C, int smooth_window, int first_keyword, int refractory, const int* W = nullptr,
+                   bool recordings_first = false);
+// Softmax over rows [first, end) into the context's scratch, then the layout's smoothing kernel -> per row of the logits array the
+// smoothed top score and the candidate label (-1: none; at a threshold of -inf the argmax wherever it is a keyword).  d_span: b.span
+// on the device -- the caller uploads it, alone or among its other tables -- or NULL for equal length.
+struct ScanScratch { float* score; int32_t* cand; };
+int scan_posteriors(kws_ctx* c, const char* fn, const WindowBatch& b, const int2* d_span, const float* d_logits, int C, int smooth_window,
+                    int first_keyword, float threshold, float* d_smoothed, ScanScratch& out);
 
 // Bracket a kernel launch with events when profiling is on (timed = false: never, e.g. inside a stream capture).
 struct ProfScope {

@@ -361,19 +361,8 @@ constexpr int COMPOSED_MAX_CLIPS = 16384;
 hipError_t launch_softmax(hipStream_t s, const float* d_logits, int B, int C, float* d_prob);
 hipError_t launch_smooth_posteriors(hipStream_t s, const float* d_logits, int S, int C, int window, float* d_ring,
                                     float* d_sum, int* d_count, float* d_smoothed, int32_t* d_label);
-// Decisions over a scan's logits (kws_scan_detect_f32, kws_scan.hip): smoothed posteriors + candidates per window, then the
-// refractory walk per recording.  d_cand: int32 [R * W] scratch (candidate label or -1), d_score: float32 [R * W] scratch.
-hipError_t launch_scan_detect(hipStream_t s, const float* d_logits, int R, int W, int C, int smooth_window, int first_keyword,
-                              float threshold, int refractory, float* d_smoothed, int32_t* d_cand, float* d_score,
-                              int32_t* d_event_window, int32_t* d_event_label, float* d_event_score, int max_events,
-                              int32_t* d_event_count);
-// The first of the two on its own, for the equal-length and the ragged layout (span[r] = (first packed window, windows), n packed
-// rows): what kws_scan_score_f32 shares with the decisions.  A threshold of -inf leaves in d_cand the argmax of every window whose
-// argmax is a keyword, whatever its score.
-hipError_t launch_scan_smooth(hipStream_t s, const float* d_prob, int R, int W, int C, int smooth_window, int first_keyword,
-                              float threshold, float* d_smoothed, int32_t* d_cand, float* d_score);
-hipError_t launch_scan_smooth_ragged(hipStream_t s, const float* d_prob, int n, const int2* d_span, int R, int C, int smooth_window,
-                                     int first_keyword, float threshold, float* d_smoothed, int32_t* d_cand, float* d_score);
+// Decisions over a scan's logits (kws_scan_detect_f32, kws_scan_score_f32 and their ragged twins): kws_ctx.h, WindowBatch and
+// scan_posteriors -- they take the context, whose scratch they carve.
 
 extern const char* const kKernelNames[KWS_K_COUNT];
 

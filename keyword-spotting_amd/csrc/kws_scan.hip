@@ -110,54 +110,92 @@ __global__ __launch_bounds__(64) void kws_scan_events_ragged_kernel(const int32_
 
 }  // namespace
 
-namespace kws {
-
-hipError_t launch_scan_smooth(hipStream_t s, const float* d_prob, int R, int W, int C, int smooth_window, int first_keyword,
-                              float threshold, float* d_smoothed, int32_t* d_cand, float* d_score) {
-    const int n = R * W;
-    hipLaunchKernelGGL(kws_scan_smooth_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_prob, n, W, C, smooth_window, first_keyword,
-                       threshold, d_smoothed, d_cand, d_score);
-    return hipGetLastError();
+static int events_check(kws_ctx* c, const char* fn, int max_events, const int32_t* d_event_window, const int32_t* d_event_label, const float* d_event_score) {
+    if (max_events < 0 || (max_events > 0 && (!d_event_window || !d_event_label || !d_event_score)))
+        return fail(c, KWS_EINVAL, std::string(fn) + ": max_events events need their three arrays");
+    return KWS_OK;
 }
 
-hipError_t launch_scan_smooth_ragged(hipStream_t s, const float* d_prob, int n, const int2* d_span, int R, int C, int smooth_window,
-                                     int first_keyword, float threshold, float* d_smoothed, int32_t* d_cand, float* d_score) {
-    hipLaunchKernelGGL(kws_scan_smooth_ragged_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_prob, n, d_span, R, C,
-                       smooth_window, first_keyword, threshold, d_smoothed, d_cand, d_score);
-    return hipGetLastError();
-}
-
-hipError_t launch_scan_detect(hipStream_t s, const float* d_prob, int R, int W, int C, int smooth_window, int first_keyword,
-                              float threshold, int refractory, float* d_smoothed, int32_t* d_cand, float* d_score,
-                              int32_t* d_event_window, int32_t* d_event_label, float* d_event_score, int max_events,
-                              int32_t* d_event_count) {
-    hipError_t e = launch_scan_smooth(s, d_prob, R, W, C, smooth_window, first_keyword, threshold, d_smoothed, d_cand, d_score);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kws_scan_events_kernel, dim3(R), dim3(64), 0, s, d_cand, d_score, W, refractory, d_event_window, d_event_label,
-                       d_event_score, max_events, d_event_count);
-    return hipGetLastError();
-}
-
-}  // namespace kws
-
-// The window tables of a ragged decision call (kws_scan_detect_ragged_f32, kws_scan_score_ragged_f32) -> span[r] = (first packed
-// window, windows); *end: where the packed rows in use end, *total: the windows of all recordings.  fn names the entry.
-int scan_ragged_spans(kws_ctx* c, const char* fn, const int32_t* win_off, const int32_t* windows, int R, std::vector<int2>& span,
-                      long long* end_out, long long* total_out) {
+int decision_check(kws_ctx* c, const char* fn, int R, int C, int smooth_window, int first_keyword, int refractory, const int* W,
+                   bool recordings_first) {
     const std::string f(fn);
-    span.resize(R);
-    long long end = 0, total = 0;
+    if (R < 1 || (W && *W < 1) || C < 1 || C > MAX_CLASSES)
+        return fail(c, KWS_EINVAL, f + (W ? ": need R >= 1, W >= 1 and C in [1, 64]" : ": need R >= 1 and C in [1, 64]"));
+    if (recordings_first && R > MAX_RAGGED_RECORDINGS) return fail(c, KWS_EUNSUPPORTED, f + ": more than 2^20 recordings in one call");
+    if (smooth_window < 1 || smooth_window > 256) return fail(c, KWS_EINVAL, f + ": smooth_window must be in [1, 256]");
+    if (refractory < 1 || first_keyword < 0) return fail(c, KWS_EINVAL, f + ": need refractory >= 1 and first_keyword >= 0");
+    return KWS_OK;
+}
+
+int scan_equal_windows(kws_ctx* c, const char* fn, int R, int W, WindowBatch& b) {
+    if (W < 1) return fail(c, KWS_EINVAL, std::string(fn) + ": need W >= 1");
+    if ((unsigned long long)R * W > (1ull << 30)) return fail(c, KWS_EUNSUPPORTED, std::string(fn) + ": more than 2^30 windows in one call");
+    b.R = R;
+    b.W = W;
+    b.end = b.total = (long long)R * W;
+    return KWS_OK;
+}
+
+int scan_ragged_spans(kws_ctx* c, const char* fn, const int32_t* win_off, const int32_t* windows, int R, WindowBatch& b) {
+    const std::string f(fn);
+    if (R > MAX_RAGGED_RECORDINGS) return fail(c, KWS_EUNSUPPORTED, f + ": more than 2^20 recordings in one call");
+    b.R = R;
+    b.span.resize(R);
     for (int r = 0; r < R; ++r) {
-        if (windows[r] < 0 || win_off[r] < end)
+        if (windows[r] < 0 || win_off[r] < b.end)
             return fail(c, KWS_EINVAL, f + ": windows must not be negative and the recordings' windows must not overlap "
                                        "(win_off ascending, win_off[r] >= win_off[r - 1] + windows[r - 1])");
-        span[r] = make_int2(win_off[r], windows[r]);
-        end = (long long)win_off[r] + windows[r];
-        total += windows[r];
-        if (end > (1ll << 30)) return fail(c, KWS_EUNSUPPORTED, f + ": more than 2^30 packed windows in one call");
+        b.span[r] = make_int2(win_off[r], windows[r]);
+        b.end = (long long)win_off[r] + windows[r];
+        b.total += windows[r];
+        if (b.end > (1ll << 30)) return fail(c, KWS_EUNSUPPORTED, f + ": more than 2^30 packed windows in one call");
     }
-    *end_out = end;
-    *total_out = total;
+    b.first = win_off[0];
+    return KWS_OK;
+}
+
+// Context scratch, indexed by row of the logits array: posteriors [end][C], then per row the score and the candidate label.
+int scan_posteriors(kws_ctx* c, const char* fn, const WindowBatch& b, const int2* d_span, const float* d_logits, int C, int smooth_window,
+                    int first_keyword, float threshold, float* d_smoothed, ScanScratch& out) {
+    const size_t n = (size_t)b.end;
+    if (int rc = grow_device_buffer(c, c->d_conv_ws, n * C + 2 * n, fn, "workspace")) return rc;
+    float* prob = c->d_conv_ws.get();
+    float* score = prob + n * C;
+    int32_t* cand = reinterpret_cast<int32_t*>(score + n);
+    HIP_TRY(c, launch_softmax(c->stream, d_logits + (size_t)b.first * C, (int)(b.end - b.first), C, prob + (size_t)b.first * C));
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (b.ragged())
+        hipLaunchKernelGGL(kws_scan_smooth_ragged_kernel, grid, dim3(256), 0, c->stream, prob, (int)n, d_span, b.R, C, smooth_window,
+                           first_keyword, threshold, d_smoothed, cand, score);
+    else
+        hipLaunchKernelGGL(kws_scan_smooth_kernel, grid, dim3(256), 0, c->stream, prob, (int)n, b.W, C, smooth_window, first_keyword, threshold,
+                           d_smoothed, cand, score);
+    HIP_TRY(c, hipGetLastError());
+    out = {score, cand};
+    return KWS_OK;
+}
+
+// The refractory walk of every recording over what scan_posteriors left.
+static hipError_t launch_scan_events(hipStream_t s, const WindowBatch& b, const int2* d_span, const int32_t* d_cand, const float* d_score,
+                                     int refractory, int32_t* d_event_window, int32_t* d_event_label, float* d_event_score, int max_events,
+                                     int32_t* d_event_count) {
+    if (b.ragged())
+        hipLaunchKernelGGL(kws_scan_events_ragged_kernel, dim3(b.R), dim3(64), 0, s, d_cand, d_score, d_span, refractory, d_event_window,
+                           d_event_label, d_event_score, max_events, d_event_count);
+    else
+        hipLaunchKernelGGL(kws_scan_events_kernel, dim3(b.R), dim3(64), 0, s, d_cand, d_score, b.W, refractory, d_event_window,
+                           d_event_label, d_event_score, max_events, d_event_count);
+    return hipGetLastError();
+}
+
+// kws_scan_detect_f32 and its ragged twin behind their own pointer checks and the making of b; d_span: b.span on the device.
+static int scan_detect(kws_ctx* c, const char* fn, const WindowBatch& b, const int2* d_span, const float* d_logits, int C, int smooth_window,
+                       int first_keyword, float threshold, int refractory, float* d_smoothed, int32_t* d_event_window,
+                       int32_t* d_event_label, float* d_event_score, int max_events, int32_t* d_event_count) {
+    ScanScratch ws;
+    if (int rc = scan_posteriors(c, fn, b, d_span, d_logits, C, smooth_window, first_keyword, threshold, d_smoothed, ws)) return rc;
+    HIP_TRY(c, launch_scan_events(c->stream, b, d_span, ws.cand, ws.score, refractory, d_event_window, d_event_label, d_event_score, max_events,
+                                  d_event_count));
     return KWS_OK;
 }
 
@@ -234,69 +272,42 @@ int kws_scan_cnn_trad_f32(kws_ctx* c, const float* d_wav, int R, int n_total, in
 int kws_scan_detect_f32(kws_ctx* c, const float* d_logits, int R, int W, int C, int smooth_window, int first_keyword, float threshold,
                         int refractory, float* d_smoothed, int32_t* d_event_window, int32_t* d_event_label, float* d_event_score,
                         int max_events, int32_t* d_event_count) {
+    const char* fn = "kws_scan_detect_f32";
+    KWS_GUARD_BEGIN
     if (!c) return KWS_EINVAL;
     if (!d_logits || !d_event_count) return fail(c, KWS_EINVAL, "kws_scan_detect_f32: d_logits / d_event_count is NULL");
-    if (max_events < 0 || (max_events > 0 && (!d_event_window || !d_event_label || !d_event_score)))
-        return fail(c, KWS_EINVAL, "kws_scan_detect_f32: max_events events need their three arrays");
-    if (R < 1 || W < 1 || C < 1 || C > MAX_CLASSES) return fail(c, KWS_EINVAL, "kws_scan_detect_f32: need R >= 1, W >= 1 and C in [1, 64]");
-    if (smooth_window < 1 || smooth_window > 256) return fail(c, KWS_EINVAL, "kws_scan_detect_f32: smooth_window must be in [1, 256]");
-    if (refractory < 1 || first_keyword < 0) return fail(c, KWS_EINVAL, "kws_scan_detect_f32: need refractory >= 1 and first_keyword >= 0");
-    if ((unsigned long long)R * W > (1ull << 30)) return fail(c, KWS_EUNSUPPORTED, "kws_scan_detect_f32: more than 2^30 windows in one call");
+    if (int rc = events_check(c, fn, max_events, d_event_window, d_event_label, d_event_score)) return rc;
+    if (int rc = decision_check(c, fn, R, C, smooth_window, first_keyword, refractory, &W)) return rc;
+    WindowBatch b;
+    if (int rc = scan_equal_windows(c, fn, R, W, b)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    // context scratch: posteriors [R W][C], then per window the candidate label and its score
-    const size_t n = (size_t)R * W;
-    int rc = grow_device_buffer(c, c->d_conv_ws, n * C + 2 * n, "kws_scan_detect_f32", "workspace");
-    if (rc) return rc;
-    float* prob = c->d_conv_ws.get();
-    float* score = prob + n * C;
-    int32_t* cand = reinterpret_cast<int32_t*>(score + n);
-    HIP_TRY(c, launch_softmax(c->stream, d_logits, (int)n, C, prob));
-    HIP_TRY(c, launch_scan_detect(c->stream, prob, R, W, C, smooth_window, first_keyword, threshold, refractory, d_smoothed, cand, score,
-                                  d_event_window, d_event_label, d_event_score, max_events, d_event_count));
-    return KWS_OK;
+    return scan_detect(c, fn, b, nullptr, d_logits, C, smooth_window, first_keyword, threshold, refractory, d_smoothed, d_event_window,
+                       d_event_label, d_event_score, max_events, d_event_count);
+    KWS_GUARD_END(c, "kws_scan_detect_f32")
 }
 
 int kws_scan_detect_ragged_f32(kws_ctx* c, const float* d_logits, const int32_t* win_off, const int32_t* windows, int R, int C,
                                int smooth_window, int first_keyword, float threshold, int refractory, float* d_smoothed,
                                int32_t* d_event_window, int32_t* d_event_label, float* d_event_score, int max_events,
                                int32_t* d_event_count) {
+    const char* fn = "kws_scan_detect_ragged_f32";
     KWS_GUARD_BEGIN
     if (!c) return KWS_EINVAL;
     if (!d_logits || !d_event_count || !win_off || !windows)
         return fail(c, KWS_EINVAL, "kws_scan_detect_ragged_f32: d_logits / d_event_count / win_off / windows is NULL");
-    if (max_events < 0 || (max_events > 0 && (!d_event_window || !d_event_label || !d_event_score)))
-        return fail(c, KWS_EINVAL, "kws_scan_detect_ragged_f32: max_events events need their three arrays");
-    if (R < 1 || C < 1 || C > MAX_CLASSES) return fail(c, KWS_EINVAL, "kws_scan_detect_ragged_f32: need R >= 1 and C in [1, 64]");
-    if (R > (1 << 20)) return fail(c, KWS_EUNSUPPORTED, "kws_scan_detect_ragged_f32: more than 2^20 recordings in one call");
-    if (smooth_window < 1 || smooth_window > 256) return fail(c, KWS_EINVAL, "kws_scan_detect_ragged_f32: smooth_window must be in [1, 256]");
-    if (refractory < 1 || first_keyword < 0)
-        return fail(c, KWS_EINVAL, "kws_scan_detect_ragged_f32: need refractory >= 1 and first_keyword >= 0");
-    std::vector<int2> span;
-    long long end = 0, total = 0;  // the packed rows in use end here
-    if (int rc = scan_ragged_spans(c, "kws_scan_detect_ragged_f32", win_off, windows, R, span, &end, &total)) return rc;
+    if (int rc = events_check(c, fn, max_events, d_event_window, d_event_label, d_event_score)) return rc;
+    if (int rc = decision_check(c, fn, R, C, smooth_window, first_keyword, refractory, nullptr, /*recordings_first=*/true)) return rc;
+    WindowBatch b;
+    if (int rc = scan_ragged_spans(c, fn, win_off, windows, R, b)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (total == 0) {  // no recording has a window: every count is 0
+    if (b.total == 0) {  // no recording has a window: every count is 0
         HIP_TRY(c, hipMemsetAsync(d_event_count, 0, sizeof(int32_t) * (size_t)R, c->stream));
         return KWS_OK;
     }
-    // packed rows [first, end) hold every recording's windows; context scratch as kws_scan_detect_f32 lays it out, indexed by packed row
-    const int first = win_off[0];
-    const size_t n = (size_t)end;
-    int rc = grow_device_buffer(c, c->d_conv_ws, n * C + 2 * n, "kws_scan_detect_ragged_f32", "workspace");
-    if (rc) return rc;
     const int2* d_span = nullptr;
-    if ((rc = upload_ragged_tables(c, span.data(), sizeof(int2) * span.size(), "kws_scan_detect_ragged_f32", reinterpret_cast<const void**>(&d_span))))
-        return rc;
-    float* prob = c->d_conv_ws.get();
-    float* score = prob + n * C;
-    int32_t* cand = reinterpret_cast<int32_t*>(score + n);
-    const int rows = (int)(end - first);
-    HIP_TRY(c, launch_softmax(c->stream, d_logits + (size_t)first * C, rows, C, prob + (size_t)first * C));
-    HIP_TRY(c, launch_scan_smooth_ragged(c->stream, prob, (int)n, d_span, R, C, smooth_window, first_keyword, threshold, d_smoothed, cand, score));
-    hipLaunchKernelGGL(kws_scan_events_ragged_kernel, dim3(R), dim3(64), 0, c->stream, cand, score, d_span, refractory, d_event_window,
+    if (int rc = upload_ragged_tables(c, b.span.data(), sizeof(int2) * b.span.size(), fn, reinterpret_cast<const void**>(&d_span))) return rc;
+    return scan_detect(c, fn, b, d_span, d_logits, C, smooth_window, first_keyword, threshold, refractory, d_smoothed, d_event_window,
                        d_event_label, d_event_score, max_events, d_event_count);
-    HIP_TRY(c, hipGetLastError());
-    return KWS_OK;
     KWS_GUARD_END(c, "kws_scan_detect_ragged_f32")
 }
 

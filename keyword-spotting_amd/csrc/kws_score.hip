@@ -123,14 +123,10 @@ int score_plan(const int32_t* truth, int N, int R, int C, int first_keyword, std
     return KWS_OK;
 }
 
-// What the two entries share with kws_scan_detect_f32's arguments, and their own.
-int score_check(kws_ctx* c, const std::string& f, const float* d_logits, int R, int C, int smooth_window, int first_keyword, int refractory,
-                const float* thresholds, int K, int N, const uint64_t* d_counts) {
+// The two entries' own arguments, ahead of those they share with kws_scan_detect_f32 (decision_check).
+int score_check(kws_ctx* c, const std::string& f, const float* d_logits, const float* thresholds, int K, int N, const uint64_t* d_counts) {
     if (!d_logits || !d_counts || !thresholds) return fail(c, KWS_EINVAL, f + ": d_logits / thresholds / d_counts is NULL");
     if (K < 1 || K > 1024 || N < 0) return fail(c, KWS_EINVAL, f + ": need K in [1, 1024] and N >= 0");
-    if (R < 1 || C < 1 || C > MAX_CLASSES) return fail(c, KWS_EINVAL, f + ": need R >= 1 and C in [1, 64]");
-    if (smooth_window < 1 || smooth_window > 256) return fail(c, KWS_EINVAL, f + ": smooth_window must be in [1, 256]");
-    if (refractory < 1 || first_keyword < 0) return fail(c, KWS_EINVAL, f + ": need refractory >= 1 and first_keyword >= 0");
     return KWS_OK;
 }
 
@@ -167,14 +163,18 @@ int score_tables(kws_ctx* c, const std::string& f, const std::vector<int2>* span
     return KWS_OK;
 }
 
-hipError_t launch_score_sweep(hipStream_t s, const int32_t* cand, const float* score, const ScoreTables& tb, int R, int W, int C, int refractory,
-                              int K, uint64_t* d_counts) {
+// The smoothing at a threshold of -inf over the batch, then the sweep.
+int score_windows(kws_ctx* c, const std::string& f, const WindowBatch& b, const ScoreTables& tb, const float* d_logits, int C, int smooth_window,
+                  int first_keyword, int refractory, int K, uint64_t* d_counts) {
+    ScanScratch ws;
+    if (int rc = scan_posteriors(c, f.c_str(), b, tb.span, d_logits, C, smooth_window, first_keyword, -std::numeric_limits<float>::infinity(), nullptr, ws))
+        return rc;
     unsigned long long* counts = reinterpret_cast<unsigned long long*>(d_counts);
-    hipError_t e = hipMemsetAsync(counts, 0, sizeof(unsigned long long) * (size_t)K * C * 4, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kws_score_sweep_kernel, dim3(R, (K + SWEEP_WAVES - 1) / SWEEP_WAVES), dim3(64 * SWEEP_WAVES), 0, s, cand, score, tb.span,
-                       W, C, refractory, tb.thr, K, tb.ival, tb.off, counts);
-    return hipGetLastError();
+    HIP_TRY(c, hipMemsetAsync(counts, 0, sizeof(unsigned long long) * (size_t)K * C * 4, c->stream));
+    hipLaunchKernelGGL(kws_score_sweep_kernel, dim3(b.R, (K + SWEEP_WAVES - 1) / SWEEP_WAVES), dim3(64 * SWEEP_WAVES), 0, c->stream, ws.cand, ws.score,
+                       tb.span, b.W, C, refractory, tb.thr, K, tb.ival, tb.off, counts);
+    HIP_TRY(c, hipGetLastError());
+    return KWS_OK;
 }
 
 }  // namespace
@@ -202,23 +202,14 @@ int kws_scan_score_f32(kws_ctx* c, const float* d_logits, int R, int W, int C, i
     KWS_GUARD_BEGIN
     if (!c) return KWS_EINVAL;
     const std::string f = "kws_scan_score_f32";
-    if (int rc = score_check(c, f, d_logits, R, C, smooth_window, first_keyword, refractory, thresholds, K, N, d_counts)) return rc;
-    if (W < 1) return fail(c, KWS_EINVAL, f + ": need W >= 1");
-    if ((unsigned long long)R * W > (1ull << 30)) return fail(c, KWS_EUNSUPPORTED, f + ": more than 2^30 windows in one call");
+    if (int rc = score_check(c, f, d_logits, thresholds, K, N, d_counts)) return rc;
+    if (int rc = decision_check(c, f.c_str(), R, C, smooth_window, first_keyword, refractory)) return rc;
+    WindowBatch b;
+    if (int rc = scan_equal_windows(c, f.c_str(), R, W, b)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     ScoreTables tb;
     if (int rc = score_tables(c, f, nullptr, truth, N, R, C, first_keyword, thresholds, K, &tb)) return rc;
-    // context scratch as kws_scan_detect_f32 lays it out: posteriors [R W][C], then per window the score and the candidate label
-    const size_t n = (size_t)R * W;
-    if (int rc = grow_device_buffer(c, c->d_conv_ws, n * C + 2 * n, f.c_str(), "workspace")) return rc;
-    float* prob = c->d_conv_ws.get();
-    float* score = prob + n * C;
-    int32_t* cand = reinterpret_cast<int32_t*>(score + n);
-    HIP_TRY(c, launch_softmax(c->stream, d_logits, (int)n, C, prob));
-    HIP_TRY(c, launch_scan_smooth(c->stream, prob, R, W, C, smooth_window, first_keyword, -std::numeric_limits<float>::infinity(), nullptr, cand,
-                                  score));
-    HIP_TRY(c, launch_score_sweep(c->stream, cand, score, tb, R, W, C, refractory, K, d_counts));
-    return KWS_OK;
+    return score_windows(c, f, b, tb, d_logits, C, smooth_window, first_keyword, refractory, K, d_counts);
     KWS_GUARD_END(c, "kws_scan_score_f32")
 }
 
@@ -228,30 +219,19 @@ int kws_scan_score_ragged_f32(kws_ctx* c, const float* d_logits, const int32_t* 
     KWS_GUARD_BEGIN
     if (!c) return KWS_EINVAL;
     const std::string f = "kws_scan_score_ragged_f32";
-    if (int rc = score_check(c, f, d_logits, R, C, smooth_window, first_keyword, refractory, thresholds, K, N, d_counts)) return rc;
+    if (int rc = score_check(c, f, d_logits, thresholds, K, N, d_counts)) return rc;
+    if (int rc = decision_check(c, f.c_str(), R, C, smooth_window, first_keyword, refractory)) return rc;
     if (!win_off || !windows) return fail(c, KWS_EINVAL, f + ": win_off / windows is NULL");
-    if (R > (1 << 20)) return fail(c, KWS_EUNSUPPORTED, f + ": more than 2^20 recordings in one call");
-    std::vector<int2> span;
-    long long end = 0, total = 0;
-    if (int rc = scan_ragged_spans(c, f.c_str(), win_off, windows, R, span, &end, &total)) return rc;
+    WindowBatch b;
+    if (int rc = scan_ragged_spans(c, f.c_str(), win_off, windows, R, b)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     ScoreTables tb;  // also when nothing has a window: a bad table is refused all the same
-    if (int rc = score_tables(c, f, &span, truth, N, R, C, first_keyword, thresholds, K, &tb)) return rc;
-    if (total == 0) {  // no recording has a window: nothing fires
+    if (int rc = score_tables(c, f, &b.span, truth, N, R, C, first_keyword, thresholds, K, &tb)) return rc;
+    if (b.total == 0) {  // no recording has a window: nothing fires
         HIP_TRY(c, hipMemsetAsync(d_counts, 0, sizeof(uint64_t) * (size_t)K * C * 4, c->stream));
         return KWS_OK;
     }
-    const int first = win_off[0];
-    const size_t n = (size_t)end;
-    if (int rc = grow_device_buffer(c, c->d_conv_ws, n * C + 2 * n, f.c_str(), "workspace")) return rc;
-    float* prob = c->d_conv_ws.get();
-    float* score = prob + n * C;
-    int32_t* cand = reinterpret_cast<int32_t*>(score + n);
-    HIP_TRY(c, launch_softmax(c->stream, d_logits + (size_t)first * C, (int)(end - first), C, prob + (size_t)first * C));
-    HIP_TRY(c, launch_scan_smooth_ragged(c->stream, prob, (int)n, tb.span, R, C, smooth_window, first_keyword,
-                                         -std::numeric_limits<float>::infinity(), nullptr, cand, score));
-    HIP_TRY(c, launch_score_sweep(c->stream, cand, score, tb, R, 0, C, refractory, K, d_counts));
-    return KWS_OK;
+    return score_windows(c, f, b, tb, d_logits, C, smooth_window, first_keyword, refractory, K, d_counts);
     KWS_GUARD_END(c, "kws_scan_score_ragged_f32")
 }
 

@@ -233,6 +233,17 @@ static int frames_recordings(kws_ctx* c, const std::string& f, const char* src_n
     return run_frontend(c, p, d_pcm, R, d_feat_out, (int)((unsigned long long)R * F / c->fp.num_frames + 1), /*recording_f32=*/true);
 }
 
+// What kws_segment_f32 and its ragged twin check alike, behind their own pointer and count checks and ahead of their size limits.
+static int segment_check(kws_ctx* c, const char* fn, int on_window, int off_window, int pre_roll, int max_frames, const int32_t* d_utt,
+                         int max_utts) {
+    const std::string f(fn);
+    if (int rc = check_endpoint_windows(c, fn, on_window, off_window)) return rc;
+    if (pre_roll < 0 || (max_frames != 0 && max_frames < 2)) return fail(c, KWS_EINVAL, f + ": need pre_roll >= 0 and max_frames == 0 or >= 2");
+    if (max_utts < 0 || (max_utts > 0 && !d_utt)) return fail(c, KWS_EINVAL, f + ": max_utts utterances need d_utt");
+    if (!c->fe_ready) return fail(c, KWS_ESTATE, f + ": front end not configured");
+    return check_append_energy(c, fn);
+}
+
 #pragma GCC visibility push(default)
 extern "C" {
 
@@ -253,13 +264,8 @@ int kws_segment_f32(kws_ctx* c, const float* d_feat, int R, int F_total, int n_t
     if (!c) return KWS_EINVAL;
     if (!d_feat || !d_count) return fail(c, KWS_EINVAL, "kws_segment_f32: d_feat / d_count is NULL");
     if (R < 1 || F_total < 1 || n_total < 1) return fail(c, KWS_EINVAL, "kws_segment_f32: R, F_total and n_total must be positive");
-    int rc = check_endpoint_windows(c, "kws_segment_f32", on_window, off_window);
+    int rc = segment_check(c, "kws_segment_f32", on_window, off_window, pre_roll, max_frames, d_utt, max_utts);
     if (rc) return rc;
-    if (pre_roll < 0 || (max_frames != 0 && max_frames < 2))
-        return fail(c, KWS_EINVAL, "kws_segment_f32: need pre_roll >= 0 and max_frames == 0 or >= 2");
-    if (max_utts < 0 || (max_utts > 0 && !d_utt)) return fail(c, KWS_EINVAL, "kws_segment_f32: max_utts utterances need d_utt");
-    if (!c->fe_ready) return fail(c, KWS_ESTATE, "kws_segment_f32: front end not configured");
-    if ((rc = check_append_energy(c, "kws_segment_f32"))) return rc;
     if ((unsigned long long)R * F_total > (1ull << 28)) return fail(c, KWS_EUNSUPPORTED, "kws_segment_f32: more than 2^28 frames in one call");
     HIP_TRY(c, hipSetDevice(c->device));
     // context scratch: open_ok and close_ok as ballot words, [R][2][n_words] of 64 bits
@@ -287,13 +293,8 @@ int kws_segment_ragged_f32(kws_ctx* c, const float* d_feat, const int32_t* frame
         return fail(c, KWS_EINVAL, "kws_segment_ragged_f32: d_feat / d_count / frame_off / frames / len is NULL");
     if (R < 1) return fail(c, KWS_EINVAL, "kws_segment_ragged_f32: R must be positive");
     if (R > (1 << 20)) return fail(c, KWS_EUNSUPPORTED, "kws_segment_ragged_f32: more than 2^20 recordings in one call");
-    int rc = check_endpoint_windows(c, "kws_segment_ragged_f32", on_window, off_window);
+    int rc = segment_check(c, "kws_segment_ragged_f32", on_window, off_window, pre_roll, max_frames, d_utt, max_utts);
     if (rc) return rc;
-    if (pre_roll < 0 || (max_frames != 0 && max_frames < 2))
-        return fail(c, KWS_EINVAL, "kws_segment_ragged_f32: need pre_roll >= 0 and max_frames == 0 or >= 2");
-    if (max_utts < 0 || (max_utts > 0 && !d_utt)) return fail(c, KWS_EINVAL, "kws_segment_ragged_f32: max_utts utterances need d_utt");
-    if (!c->fe_ready) return fail(c, KWS_ESTATE, "kws_segment_ragged_f32: front end not configured");
-    if ((rc = check_append_energy(c, "kws_segment_ragged_f32"))) return rc;
     std::vector<SegRec> rec(R + 1);
     long long words = 0, groups = 0, rows_end = 0;
     for (int r = 0; r < R; ++r) {

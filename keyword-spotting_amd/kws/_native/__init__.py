@@ -216,6 +216,11 @@ def _ptr(t) -> int:
     return int(t.data_ptr())
 
 
+def _opt(t):
+    """An optional device tensor -> its address or NULL."""
+    return _ptr(t) if t is not None else None
+
+
 class Context:
     """One kws_ctx: a GPU, its stream, front-end tables, model weights, workspace."""
 
@@ -478,29 +483,19 @@ class Context:
 
     def scan_cnn_trad_i16(self, pcm, hop_frames, logits, label=None, feat=None):
         """``kws_scan_cnn_trad_i16``: ``scan_i16`` with cnn-trad-fpool3 over the windows."""
-        p = lambda t: _ptr(t) if t is not None else None
-        self._check(self._lib.kws_scan_cnn_trad_i16(self._h, _ptr(pcm), int(pcm.shape[0]), int(pcm.shape[1]), int(hop_frames), _ptr(logits),
-                                                    p(label), p(feat)), ModelError)
+        self._scan_equal(self._lib.kws_scan_cnn_trad_i16, pcm, hop_frames, logits, label, feat)
 
     def scan_cnn_trad_f32(self, wav, hop_frames, logits, label=None, feat=None):
         """``kws_scan_cnn_trad_f32``: ``scan_f32`` with cnn-trad-fpool3 over the windows."""
-        p = lambda t: _ptr(t) if t is not None else None
-        self._check(self._lib.kws_scan_cnn_trad_f32(self._h, _ptr(wav), int(wav.shape[0]), int(wav.shape[1]), int(hop_frames), _ptr(logits),
-                                                    p(label), p(feat)), ModelError)
+        self._scan_equal(self._lib.kws_scan_cnn_trad_f32, wav, hop_frames, logits, label, feat)
 
     def scan_ragged_cnn_trad_i16(self, pcm, start, length, hop_frames, logits, label=None, feat=None):
         """``kws_scan_ragged_cnn_trad_i16``: ``scan_ragged_i16`` with cnn-trad-fpool3 over the packed windows."""
-        p = lambda t: _ptr(t) if t is not None else None
-        st, ln = _host_i64(start), _host_i32(length)
-        self._check(self._lib.kws_scan_ragged_cnn_trad_i16(self._h, _ptr(pcm), int(pcm.numel()), _as(st, C.c_int64), _as(ln, C.c_int32),
-                                                           len(ln), int(hop_frames), _ptr(logits), p(label), p(feat)), ModelError)
+        self._scan_packed(self._lib.kws_scan_ragged_cnn_trad_i16, pcm, start, length, hop_frames, logits, label, feat)
 
     def scan_ragged_cnn_trad_f32(self, wav, start, length, hop_frames, logits, label=None, feat=None):
         """``kws_scan_ragged_cnn_trad_f32``: ``scan_ragged_f32`` with cnn-trad-fpool3 over the packed windows."""
-        p = lambda t: _ptr(t) if t is not None else None
-        st, ln = _host_i64(start), _host_i32(length)
-        self._check(self._lib.kws_scan_ragged_cnn_trad_f32(self._h, _ptr(wav), int(wav.numel()), _as(st, C.c_int64), _as(ln, C.c_int32),
-                                                           len(ln), int(hop_frames), _ptr(logits), p(label), p(feat)), ModelError)
+        self._scan_packed(self._lib.kws_scan_ragged_cnn_trad_f32, wav, start, length, hop_frames, logits, label, feat)
 
     def stream_push_cnn_trad_i16(self, hop, logits, label=None):
         """``kws_stream_push_cnn_trad_i16``: one hop per stream, then cnn-trad-fpool3 over every stream's window of the feature
@@ -518,28 +513,33 @@ class Context:
         )
 
     # -- scanning --------------------------------------------------------------------------------
+    def _scan_equal(self, fn, src, hop_frames, logits, label, feat):
+        """One of the four ``kws_scan_*`` entries over ``src`` [R, n_total] on the device."""
+        self._check(fn(self._h, _ptr(src), int(src.shape[0]), int(src.shape[1]), int(hop_frames), _ptr(logits), _opt(label), _opt(feat)), ModelError)
+
+    def _scan_packed(self, fn, src, start, length, hop_frames, logits, label, feat):
+        """One of the four ``kws_scan_ragged_*`` entries over the packed ``src`` on the device; ``start`` / ``length`` host sequences."""
+        st, ln = _host_i64(start), _host_i32(length)
+        self._check(fn(self._h, _ptr(src), int(src.numel()), _as(st, C.c_int64), _as(ln, C.c_int32), len(ln), int(hop_frames), _ptr(logits),
+                       _opt(label), _opt(feat)), ModelError)
+
     def scan_i16(self, pcm, hop_frames, logits, label=None, feat=None):
         """``kws_scan_i16``: ``pcm`` int16 [R, n_total] on the device -> ``logits`` float32 [R, W, C] (and ``label`` int32 [R, W])
         for every window of 99 frames, ``hop_frames`` frames apart, of each recording's one MFCC pass; ``feat`` float32
         [R, F_total, numcep] keeps the frames (``host_scan_shape`` gives F_total and W)."""
-        p = lambda t: _ptr(t) if t is not None else None
-        self._check(self._lib.kws_scan_i16(self._h, _ptr(pcm), int(pcm.shape[0]), int(pcm.shape[1]), int(hop_frames), _ptr(logits),
-                                           p(label), p(feat)), ModelError)
+        self._scan_equal(self._lib.kws_scan_i16, pcm, hop_frames, logits, label, feat)
 
     def scan_f32(self, wav, hop_frames, logits, label=None, feat=None):
         """``kws_scan_f32``: ``scan_i16`` over ``wav`` float32 [R, n_total] on the device, the samples taken as they are."""
-        p = lambda t: _ptr(t) if t is not None else None
-        self._check(self._lib.kws_scan_f32(self._h, _ptr(wav), int(wav.shape[0]), int(wav.shape[1]), int(hop_frames), _ptr(logits),
-                                           p(label), p(feat)), ModelError)
+        self._scan_equal(self._lib.kws_scan_f32, wav, hop_frames, logits, label, feat)
 
     def scan_detect_f32(self, logits, smooth_window, first_keyword, threshold, refractory, event_count, event_window=None,
                         event_label=None, event_score=None, max_events=0, smoothed=None):
         """``kws_scan_detect_f32``: ``logits`` float32 [R, W, C] -> smoothed posteriors, candidates and events with a refractory
         gap.  ``event_count`` int32 [R]; the three event arrays [R, max_events]; ``smoothed`` float32 [R, W, C] or None."""
-        p = lambda t: _ptr(t) if t is not None else None
         R, W, Cn = (int(v) for v in logits.shape)
         self._check(self._lib.kws_scan_detect_f32(self._h, _ptr(logits), R, W, Cn, int(smooth_window), int(first_keyword), float(threshold),
-                                                  int(refractory), p(smoothed), p(event_window), p(event_label), p(event_score),
+                                                  int(refractory), _opt(smoothed), _opt(event_window), _opt(event_label), _opt(event_score),
                                                   int(max_events), _ptr(event_count)), ModelError)
 
     # -- utterances --------------------------------------------------------------------------------
@@ -587,10 +587,7 @@ class Context:
     def scan_ragged_i16(self, pcm, start, length, hop_frames, logits, label=None, feat=None):
         """``kws_scan_ragged_i16``: the ragged front end, then the DS-CNN over the packed frame array as one recording ->
         ``logits`` float32 [W_pack, C] (``label`` int32 [W_pack]); window w of recording r is row ``win_off[r] + w``."""
-        p = lambda t: _ptr(t) if t is not None else None
-        st, ln = _host_i64(start), _host_i32(length)
-        self._check(self._lib.kws_scan_ragged_i16(self._h, _ptr(pcm), int(pcm.numel()), _as(st, C.c_int64), _as(ln, C.c_int32), len(ln),
-                                                  int(hop_frames), _ptr(logits), p(label), p(feat)), ModelError)
+        self._scan_packed(self._lib.kws_scan_ragged_i16, pcm, start, length, hop_frames, logits, label, feat)
 
     def frames_ragged_f32(self, wav, start, length, row_multiple, feat):
         """``kws_frames_ragged_f32``: ``frames_ragged_i16`` over ``wav`` float32 (any shape, contiguous) on the device."""
@@ -600,20 +597,16 @@ class Context:
 
     def scan_ragged_f32(self, wav, start, length, hop_frames, logits, label=None, feat=None):
         """``kws_scan_ragged_f32``: ``scan_ragged_i16`` over ``wav`` float32 (any shape, contiguous) on the device."""
-        p = lambda t: _ptr(t) if t is not None else None
-        st, ln = _host_i64(start), _host_i32(length)
-        self._check(self._lib.kws_scan_ragged_f32(self._h, _ptr(wav), int(wav.numel()), _as(st, C.c_int64), _as(ln, C.c_int32), len(ln),
-                                                  int(hop_frames), _ptr(logits), p(label), p(feat)), ModelError)
+        self._scan_packed(self._lib.kws_scan_ragged_f32, wav, start, length, hop_frames, logits, label, feat)
 
     def scan_detect_ragged_f32(self, logits, win_off, windows, smooth_window, first_keyword, threshold, refractory, event_count,
                                event_window=None, event_label=None, event_score=None, max_events=0, smoothed=None):
         """``kws_scan_detect_ragged_f32``: ``logits`` float32 [W_pack, C]; ``win_off`` / ``windows`` host sequences [R]; the
         decisions of ``scan_detect_f32`` per recording.  ``event_count`` int32 [R]; the event arrays [R, max_events]."""
-        p = lambda t: _ptr(t) if t is not None else None
         wo, wn = _host_i32(win_off), _host_i32(windows)
         self._check(self._lib.kws_scan_detect_ragged_f32(self._h, _ptr(logits), _as(wo, C.c_int32), _as(wn, C.c_int32), len(wn),
                                                          int(logits.shape[-1]), int(smooth_window), int(first_keyword), float(threshold),
-                                                         int(refractory), p(smoothed), p(event_window), p(event_label), p(event_score),
+                                                         int(refractory), _opt(smoothed), _opt(event_window), _opt(event_label), _opt(event_score),
                                                          int(max_events), _ptr(event_count)), ModelError)
 
     # -- scoring against annotations ---------------------------------------------------------------
@@ -794,9 +787,8 @@ class Context:
         """``kws_eval_update_f32``: ``logits`` float32 [B, C] and ``truth`` int32 [B] on the device into the statistics;
         ``dlogits`` float32 [B, C] (the cross-entropy gradient times ``grad_scale``) and ``loss_rows`` float32 [B] are optional
         outputs.  Asynchronous on the context's stream."""
-        p = lambda t: _ptr(t) if t is not None else None
-        self._check(self._lib.kws_eval_update_f32(self._h, _ptr(logits), _ptr(truth), int(logits.shape[0]), float(grad_scale), p(dlogits),
-                                                  p(loss_rows)), ModelError)
+        self._check(self._lib.kws_eval_update_f32(self._h, _ptr(logits), _ptr(truth), int(logits.shape[0]), float(grad_scale), _opt(dlogits),
+                                                  _opt(loss_rows)), ModelError)
 
     def eval_read(self):
         """``kws_eval_read``: wait for the stream, then (counts uint64[4], loss_sum float, confusion uint64[C, C], hist_pos
@@ -871,21 +863,19 @@ class Context:
 
     # -- augmentation ----------------------------------------------------------------------------
     def augment_i16(self, wav, out, shift=None, bg=None, bg_off=None, bg_vol=None, silence=None):
-        p = lambda t: _ptr(t) if t is not None else None
         self._check(
-            self._lib.kws_augment_i16(self._h, _ptr(wav), int(wav.shape[0]), p(shift), p(bg), int(bg.numel()) if bg is not None else 0,
-                                      p(bg_off), p(bg_vol), p(silence), _ptr(out)),
+            self._lib.kws_augment_i16(self._h, _ptr(wav), int(wav.shape[0]), _opt(shift), _opt(bg), int(bg.numel()) if bg is not None else 0,
+                                      _opt(bg_off), _opt(bg_vol), _opt(silence), _ptr(out)),
             AudioProcessingError,
         )
 
     def augment_draw(self, seed, epoch, index, shift, bg_off, bg_vol, silence, labels=None, time_shift=0, bg_start=None, bg_len=None,
                      bg_volume=0.0, bg_frequency=0.0, use_background=True, n_samples=16000):
         """The training transform's random draws for the dataset indices ``index`` (int32, device), made on the device."""
-        p = lambda t: _ptr(t) if t is not None else None
         self._check(
             self._lib.kws_augment_draw(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF, _ptr(index), int(index.numel()),
-                                       p(labels), int(labels.numel()) if labels is not None else 0, int(time_shift), p(bg_start),
-                                       p(bg_len), int(bg_start.numel()) if bg_start is not None else 0, float(bg_volume),
+                                       _opt(labels), int(labels.numel()) if labels is not None else 0, int(time_shift), _opt(bg_start),
+                                       _opt(bg_len), int(bg_start.numel()) if bg_start is not None else 0, float(bg_volume),
                                        float(bg_frequency), int(bool(use_background)), int(n_samples), _ptr(shift), _ptr(bg_off),
                                        _ptr(bg_vol), _ptr(silence)),
             AudioProcessingError,
@@ -894,9 +884,8 @@ class Context:
     def mfcc_augment_i16(self, pcm, index, out, shift=None, bg=None, bg_off=None, bg_vol=None, silence=None) -> int:
         """Gather + augment + MFCC in one launch.  Returns ``KWS_OK``, or ``KWS_EUNSUPPORTED`` when the configured front end
         has no fused kernel (the caller composes ``augment_i16`` and ``mfcc_f32``); every other code raises."""
-        p = lambda t: _ptr(t) if t is not None else None
-        rc = self._lib.kws_mfcc_augment_i16(self._h, _ptr(pcm), int(pcm.shape[0]), _ptr(index), int(index.numel()), p(shift), p(bg),
-                                            int(bg.numel()) if bg is not None else 0, p(bg_off), p(bg_vol), p(silence), _ptr(out))
+        rc = self._lib.kws_mfcc_augment_i16(self._h, _ptr(pcm), int(pcm.shape[0]), _ptr(index), int(index.numel()), _opt(shift), _opt(bg),
+                                            int(bg.numel()) if bg is not None else 0, _opt(bg_off), _opt(bg_vol), _opt(silence), _ptr(out))
         if rc != KWS_EUNSUPPORTED:
             self._check(rc, AudioProcessingError)
         return rc

@@ -321,44 +321,68 @@ class KeywordSpotter:
         return self._scan(self._recordings(signal, "scan_f32", f32=True), "scan_f32", hop_frames, smooth_window, threshold, refractory,
                           first_keyword, max_events, sample_rate)
 
-    def _scan(self, x: torch.Tensor, what: str, hop_frames, smooth_window, threshold, refractory, first_keyword, max_events,
-              sample_rate) -> ScanResult:
-        """``scan`` / ``scan_f32`` behind their argument's type check; the sample type of ``x`` picks the entries."""
-        from kws import _native
+    def _frame_geometry(self) -> Tuple[int, int]:
+        """(frame_len, frame_step) in samples at the configured rate."""
+        cfg = self.config
+        return _round_half_up(cfg.frame_length * cfg.sample_rate), _round_half_up(cfg.frame_step * cfg.sample_rate)
 
+    @staticmethod
+    def _decision_args(what: str, hop_frames, smooth_window, refractory, first_keyword, max_events=None, decide: bool = True) -> None:
+        """The argument checks the scan and score methods share (no device needed): the hop, then -- when decisions are asked
+        for -- the rules; ``max_events`` joins the last sentence for the methods that take it."""
         if int(hop_frames) < 1:
             raise ModelError(f"{what}: hop_frames must be at least 1")
-        if threshold is not None:
-            if not 1 <= int(smooth_window) <= 256:
-                raise ModelError(f"{what}: smooth_window must be in [1, 256]")
-            if int(refractory) < 1 or int(first_keyword) < 0 or int(max_events) < 0:
-                raise ModelError(f"{what}: need refractory >= 1, first_keyword >= 0 and max_events >= 0")
-        cfg = self.config
+        if not decide:
+            return
+        if not 1 <= int(smooth_window) <= 256:
+            raise ModelError(f"{what}: smooth_window must be in [1, 256]")
+        if int(refractory) < 1 or int(first_keyword) < 0 or (max_events is not None and int(max_events) < 0):
+            rest = " and first_keyword >= 0" if max_events is None else ", first_keyword >= 0 and max_events >= 0"
+            raise ModelError(f"{what}: need refractory >= 1{rest}")
+
+    def _scan_logits(self, x: torch.Tensor, what: str, hop_frames, sample_rate, want_labels: bool):
+        """Recordings ``[R, n]`` -> (ctx, logits [R, W, C] and labels [R, W] (or None) on the device, window start and end times,
+        frame_step): the resampling, the shape refusal and the scan ``scan`` and ``score`` share."""
+        from kws import _native
+
+        cfg, hop = self.config, int(hop_frames)
         x = self._at_configured_rate(x, sample_rate, what)
-        frame_len, frame_step = _round_half_up(cfg.frame_length * cfg.sample_rate), _round_half_up(cfg.frame_step * cfg.sample_rate)
+        frame_len, frame_step = self._frame_geometry()
         R, n = int(x.shape[0]), int(x.shape[1])
-        frames, W = (0, 0) if n < 1 else _native.host_scan_shape(n, frame_len, frame_step, WINDOW_FRAMES, int(hop_frames))
+        frames, W = (0, 0) if n < 1 else _native.host_scan_shape(n, frame_len, frame_step, WINDOW_FRAMES, hop)
         if W < 1:
             raise ModelError(f"{what}: a recording of {n} samples ({frames} frames) is shorter than one window of {WINDOW_FRAMES} frames")
         ctx = self.model._context(self.device.index or 0)
         x = x.to(self.device).contiguous()
-        C = self.model.num_classes
-        logits = torch.empty((R, W, C), dtype=torch.float32, device=self.device)
-        labels = torch.empty((R, W), dtype=torch.int32, device=self.device)
-        self.model._native_scan(ctx, x, int(hop_frames), logits, labels)
-        start_s, end_s = scan_window_times(W, int(hop_frames), frame_len, frame_step, cfg.sample_rate, WINDOW_FRAMES, n)
+        logits = torch.empty((R, W, self.model.num_classes), dtype=torch.float32, device=self.device)
+        labels = torch.empty((R, W), dtype=torch.int32, device=self.device) if want_labels else None
+        self.model._native_scan(ctx, x, hop, logits, labels)
+        start_s, end_s = scan_window_times(W, hop, frame_len, frame_step, cfg.sample_rate, WINDOW_FRAMES, n)
+        return ctx, logits, labels, start_s, end_s, frame_step
+
+    def _events(self, detect, end_times, max_events) -> List[List[Tuple[float, int, str, float]]]:
+        """The count and the three event arrays of R = ``len(end_times)`` recordings, ``detect(count, window, label, score,
+        max_events)`` over them, the read-back, and per recording its events as ``(time_s, index, word, score)``;
+        ``end_times[r]``: the end of each window of recording ``r`` in seconds."""
+        R, m = len(end_times), int(max_events)
+        count = torch.empty((R,), dtype=torch.int32, device=self.device)
+        ev_w = torch.empty((R, m), dtype=torch.int32, device=self.device)
+        ev_k = torch.empty((R, m), dtype=torch.int32, device=self.device)
+        ev_s = torch.empty((R, m), dtype=torch.float32, device=self.device)
+        detect(count, ev_w if m else None, ev_k if m else None, ev_s if m else None, m)
+        count, ev_w, ev_k, ev_s = count.cpu().numpy(), ev_w.cpu().numpy(), ev_k.cpu().numpy(), ev_s.cpu().numpy()
+        return [[(float(end_times[r][ev_w[r, i]]), int(ev_k[r, i]), self.words[int(ev_k[r, i])], float(ev_s[r, i]))
+                 for i in range(min(int(count[r]), m))] for r in range(R)]
+
+    def _scan(self, x: torch.Tensor, what: str, hop_frames, smooth_window, threshold, refractory, first_keyword, max_events,
+              sample_rate) -> ScanResult:
+        """``scan`` / ``scan_f32`` behind their argument's type check; the sample type of ``x`` picks the entries."""
+        self._decision_args(what, hop_frames, smooth_window, refractory, first_keyword, max_events, decide=threshold is not None)
+        ctx, logits, labels, start_s, end_s, _ = self._scan_logits(x, what, hop_frames, sample_rate, True)
         events = None
         if threshold is not None:
-            m = int(max_events)
-            count = torch.empty((R,), dtype=torch.int32, device=self.device)
-            ev_w = torch.empty((R, m), dtype=torch.int32, device=self.device)
-            ev_k = torch.empty((R, m), dtype=torch.int32, device=self.device)
-            ev_s = torch.empty((R, m), dtype=torch.float32, device=self.device)
-            ctx.scan_detect_f32(logits, smooth_window, first_keyword, threshold, refractory, count,
-                                ev_w if m else None, ev_k if m else None, ev_s if m else None, m)
-            count, ev_w, ev_k, ev_s = count.cpu().numpy(), ev_w.cpu().numpy(), ev_k.cpu().numpy(), ev_s.cpu().numpy()
-            events = [[(float(end_s[ev_w[r, i]]), int(ev_k[r, i]), self.words[int(ev_k[r, i])], float(ev_s[r, i]))
-                       for i in range(min(int(count[r]), m))] for r in range(R)]
+            events = self._events(lambda *out: ctx.scan_detect_f32(logits, smooth_window, first_keyword, threshold, refractory, *out),
+                                  [end_s] * logits.shape[0], max_events)
         return ScanResult(labels.cpu().numpy(), logits.cpu().numpy(), start_s, events)
 
     def score(self, pcm, truth, thresholds, hop_frames: int = 1, smooth_window: int = 1, refractory: int = 50, first_keyword: int = 2,
@@ -386,12 +410,7 @@ class KeywordSpotter:
         th = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float32).reshape(-1))
         if not 1 <= len(th) <= 1024:
             raise ModelError(f"{what}: between 1 and 1024 thresholds are needed, got {len(th)}")
-        if int(hop_frames) < 1:
-            raise ModelError(f"{what}: hop_frames must be at least 1")
-        if not 1 <= int(smooth_window) <= 256:
-            raise ModelError(f"{what}: smooth_window must be in [1, 256]")
-        if int(refractory) < 1 or int(first_keyword) < 0:
-            raise ModelError(f"{what}: need refractory >= 1 and first_keyword >= 0")
+        KeywordSpotter._decision_args(what, hop_frames, smooth_window, refractory, first_keyword)
         return th
 
     @staticmethod
@@ -424,23 +443,11 @@ class KeywordSpotter:
     def _score(self, x: torch.Tensor, what: str, truth, thresholds, hop_frames, smooth_window, refractory, first_keyword, tolerance_s,
                sample_rate):
         """``score`` / ``score_f32`` behind their argument's type check; the sample type of ``x`` picks the entries."""
-        from kws import _native
-
         th = self._score_args(what, thresholds, hop_frames, smooth_window, refractory, first_keyword)
-        cfg = self.config
-        truths = self._truth_lists(what, truth, int(x.shape[0]))
-        hours = float(x.shape[0]) * float(x.shape[1]) / float(sample_rate or cfg.sample_rate) / 3600.0
-        x = self._at_configured_rate(x, sample_rate, what)
-        frame_len, frame_step = _round_half_up(cfg.frame_length * cfg.sample_rate), _round_half_up(cfg.frame_step * cfg.sample_rate)
-        R, n = int(x.shape[0]), int(x.shape[1])
-        frames, W = (0, 0) if n < 1 else _native.host_scan_shape(n, frame_len, frame_step, WINDOW_FRAMES, int(hop_frames))
-        if W < 1:
-            raise ModelError(f"{what}: a recording of {n} samples ({frames} frames) is shorter than one window of {WINDOW_FRAMES} frames")
-        ctx = self.model._context(self.device.index or 0)
-        x = x.to(self.device).contiguous()
-        logits = torch.empty((R, W, self.model.num_classes), dtype=torch.float32, device=self.device)
-        self.model._native_scan(ctx, x, int(hop_frames), logits, None)
-        _, end_s = scan_window_times(W, int(hop_frames), frame_len, frame_step, cfg.sample_rate, WINDOW_FRAMES, n)
+        R = int(x.shape[0])
+        truths = self._truth_lists(what, truth, R)
+        hours = float(R) * float(x.shape[1]) / float(sample_rate or self.config.sample_rate) / 3600.0
+        ctx, logits, _, _, end_s, frame_step = self._scan_logits(x, what, hop_frames, sample_rate, False)
         call = lambda table, counts: ctx.scan_score_f32(logits, smooth_window, first_keyword, refractory, th, table, counts)
         return self._score_report(ctx, call, th, truths, [end_s] * R, tolerance_s, hours, hop_frames, frame_step)
 
@@ -453,20 +460,9 @@ class KeywordSpotter:
         ``decode="any"``: ``read_wav`` decodes the file.  16-bit mono goes down the int16 path unchanged; every other encoding
         (24-bit, 32-bit, float, stereo) is float32 mono and goes down the float path (``scan_f32``), and with ``resample=True`` the
         rate change runs on the device in the file's own sample type."""
-        if self._decode_mode(decode, "scan_file"):
-            x, rate = self._decode_any(path, resample, "scan_file")
-            return (self.scan if x.dtype == np.int16 else self.scan_f32)(x, sample_rate=rate, **kwargs)
-        if resample:
-            x, rate = read_wav(path)
-            if rate != self.config.sample_rate:
-                if x.dtype != np.int16:
-                    raise AudioProcessingError(f"{path}: sample rate {rate} != {self.config.sample_rate} and the file is not 16-bit mono "
-                                               "PCM; the device resampler of scan_file takes int16 only (there is no float32 scan)")
-                return self.scan(x, sample_rate=rate, **kwargs)
-        x = load_pcm16(path, self.config.sample_rate)
-        if x.ndim == 2:
-            raise AudioProcessingError(f"{path}: {x.shape[1]} channels; scan_file takes mono files")
-        return self.scan(x, **kwargs)
+        decode_one = self._decode_any if self._decode_mode(decode, "scan_file") else self._decode_file
+        x, rate = decode_one(path, resample, "scan_file")
+        return (self.scan if x.dtype == np.int16 else self.scan_f32)(x, sample_rate=rate, **kwargs)
 
     def _recordings(self, pcm, what: str, f32: bool = False) -> torch.Tensor:
         """int16 ``[n]`` or ``[R, n]``, host array or device tensor -> an int16 tensor ``[R, n]`` (the checks of ``scan``);
@@ -549,36 +545,25 @@ class KeywordSpotter:
         return self._segment(self._recordings(signal, "segment_f32", f32=True), "segment_f32", threshold, on_window, off_window, pre_roll,
                              max_seconds, normalize, max_utterances, sample_rate, keep_unfinished)
 
-    def _segment(self, x: torch.Tensor, what: str, threshold, on_window, off_window, pre_roll, max_seconds, normalize, max_utterances,
-                 sample_rate, keep_unfinished) -> List[List[Utterance]]:
-        """``segment`` / ``segment_f32`` behind their argument's type check; the sample type of ``x`` picks the entries."""
-        from kws import _native
-
+    def _segment_args(self, what: str, on_window, off_window, pre_roll, max_seconds, normalize, max_utterances) -> int:
+        """The argument checks ``segment`` and ``segment_batch`` share (no device needed) -> ``max_frames``."""
         if not 1 <= int(on_window) <= int(off_window) <= 1024:
             raise ModelError(f"{what}: need 1 <= on_window <= off_window <= 1024")
         if int(pre_roll) < 0 or int(max_utterances) < 0 or not 0 <= int(normalize) <= 32767:
             raise ModelError(f"{what}: need pre_roll >= 0, max_utterances >= 0 and normalize in [0, 32767]")
-        cfg = self.config
-        x = self._at_configured_rate(x, sample_rate, what)
-        frame_len, frame_step = _round_half_up(cfg.frame_length * cfg.sample_rate), _round_half_up(cfg.frame_step * cfg.sample_rate)
-        max_frames = int(round(float(max_seconds) * cfg.sample_rate / frame_step))
+        max_frames = int(round(float(max_seconds) * self.config.sample_rate / self._frame_geometry()[1]))
         if max_frames == 1 or max_frames < 0:
             raise ModelError(f"{what}: max_seconds must be 0 (no limit) or at least two frames")
-        R, n = int(x.shape[0]), int(x.shape[1])
-        if n < 1:
-            raise ModelError(f"{what}: the recording is empty")
-        F, _ = _native.host_scan_shape(n, frame_len, frame_step, WINDOW_FRAMES, 1)
-        ctx = self.model._context(self.device.index or 0)
-        x = x.to(self.device).contiguous()
-        m = int(max_utterances)
-        feat = torch.empty((R, F, cfg.num_cepstral_coeffs), dtype=torch.float32, device=self.device)
-        found = torch.empty((R + 5 * R * m,), dtype=torch.int32, device=self.device)  # the counts [R], then the slots [R, m, 5]
-        f32 = x.dtype == torch.float32
-        (ctx.frames_f32 if f32 else ctx.frames_i16)(x, feat)
-        ctx.segment_f32(feat, n, threshold, found[:R], found[R:] if m else None, m, on_window, off_window, pre_roll, max_frames)
-        host = found.cpu().numpy()  # the one device-to-host read (it waits for the stream): counts and spans together
-        counts, slots = host[:R], host[R:].reshape(R, m, 5)
-        rows = []  # (recording, start, end, open, close, reason): the compact list, in recording and time order
+        return max_frames
+
+    def _utterances(self, ctx, found: np.ndarray, R: int, m: int, keep_unfinished: bool, source: torch.Tensor, sample_off, normalize
+                    ) -> List[List[Utterance]]:
+        """The host copy of the endpointer's answer -- the counts [R], then the slots [R, m, 5] -- -> one list of ``Utterance``
+        per recording: the compact rows in recording and time order, their spans cut from ``source`` and classified
+        (``_classify_spans``; nothing is launched without a row).  ``source`` is ``[R, n]`` with ``sample_off`` None, or the whole
+        buffer of a batch as ONE recording ``[1, n_pcm]``, where a span of recording ``r`` lies ``sample_off[r]`` samples on."""
+        counts, slots = found[:R], found[R:].reshape(R, m, 5)
+        rows = []  # (recording, start, end, open, close, reason)
         for r in range(R):
             for i in range(min(int(counts[r]), m)):
                 start, end, opened, closed, reason = (int(v) for v in slots[r, i])
@@ -588,32 +573,45 @@ class KeywordSpotter:
         out: List[List[Utterance]] = [[] for _ in range(R)]
         if not rows:
             return out
-        span = torch.tensor([row[:3] for row in rows], dtype=torch.int32).to(self.device)
-        cut = (lambda clips, peaks: ctx.cut_f32(x, span, clips, int(normalize) / 32768.0, peaks)) if f32 else \
-              (lambda clips, peaks: ctx.cut_i16(x, span, clips, int(normalize), peaks))
-        for utt in _classify_spans(ctx, self.model, self.device, self.words, self.model.num_classes, cfg.desired_samples, float(cfg.sample_rate), frame_step,
-                                   rows, cut, f32):
+        span = torch.tensor([(r, s, e) if sample_off is None else (0, int(sample_off[r]) + s, int(sample_off[r]) + e)
+                             for r, s, e, _, _, _ in rows], dtype=torch.int32).to(self.device)
+        f32 = source.dtype == torch.float32
+        cut = (lambda clips, peaks: ctx.cut_f32(source, span, clips, int(normalize) / 32768.0, peaks)) if f32 else \
+              (lambda clips, peaks: ctx.cut_i16(source, span, clips, int(normalize), peaks))
+        cfg = self.config
+        for utt in _classify_spans(ctx, self.model, self.device, self.words, self.model.num_classes, cfg.desired_samples, float(cfg.sample_rate),
+                                   self._frame_geometry()[1], rows, cut, f32):
             out[utt.recording].append(utt)
         return out
+
+    def _segment(self, x: torch.Tensor, what: str, threshold, on_window, off_window, pre_roll, max_seconds, normalize, max_utterances,
+                 sample_rate, keep_unfinished) -> List[List[Utterance]]:
+        """``segment`` / ``segment_f32`` behind their argument's type check; the sample type of ``x`` picks the entries."""
+        from kws import _native
+
+        max_frames = self._segment_args(what, on_window, off_window, pre_roll, max_seconds, normalize, max_utterances)
+        x = self._at_configured_rate(x, sample_rate, what)
+        R, n = int(x.shape[0]), int(x.shape[1])
+        if n < 1:
+            raise ModelError(f"{what}: the recording is empty")
+        F, _ = _native.host_scan_shape(n, *self._frame_geometry(), WINDOW_FRAMES, 1)
+        ctx = self.model._context(self.device.index or 0)
+        x = x.to(self.device).contiguous()
+        m = int(max_utterances)
+        feat = torch.empty((R, F, self.config.num_cepstral_coeffs), dtype=torch.float32, device=self.device)
+        found = torch.empty((R + 5 * R * m,), dtype=torch.int32, device=self.device)  # the counts [R], then the slots [R, m, 5]
+        (ctx.frames_f32 if x.dtype == torch.float32 else ctx.frames_i16)(x, feat)
+        ctx.segment_f32(feat, n, threshold, found[:R], found[R:] if m else None, m, on_window, off_window, pre_roll, max_frames)
+        host = found.cpu().numpy()  # the one device-to-host read (it waits for the stream): counts and spans together
+        return self._utterances(ctx, host, R, m, keep_unfinished, x, None, normalize)
 
     def segment_file(self, path: str, resample: bool = False, decode: str = "pcm16", **kwargs) -> List[Utterance]:
         """``segment`` over a whole wav file; the file's utterances.  The file must be 16-bit mono PCM at the configured rate;
         with ``resample=True`` a 16-bit mono file at another rate is resampled on the device (as ``scan_file``).
         ``decode="any"``: every encoding ``read_wav`` decodes, as ``scan_file`` routes it."""
-        if self._decode_mode(decode, "segment_file"):
-            x, rate = self._decode_any(path, resample, "segment_file")
-            return (self.segment if x.dtype == np.int16 else self.segment_f32)(x, sample_rate=rate, **kwargs)[0]
-        if resample:
-            x, rate = read_wav(path)
-            if rate != self.config.sample_rate:
-                if x.dtype != np.int16:
-                    raise AudioProcessingError(f"{path}: sample rate {rate} != {self.config.sample_rate} and the file is not 16-bit mono "
-                                               "PCM; the device resampler of segment_file takes int16 only")
-                return self.segment(x, sample_rate=rate, **kwargs)[0]
-        x = load_pcm16(path, self.config.sample_rate)
-        if x.ndim == 2:
-            raise AudioProcessingError(f"{path}: {x.shape[1]} channels; segment_file takes mono files")
-        return self.segment(x, **kwargs)[0]
+        decode_one = self._decode_any if self._decode_mode(decode, "segment_file") else self._decode_file
+        x, rate = decode_one(path, resample, "segment_file")
+        return (self.segment if x.dtype == np.int16 else self.segment_f32)(x, sample_rate=rate, **kwargs)[0]
 
     # -- batches of recordings of unequal length ---------------------------------------------------------------------------
     def _batch_recordings(self, recordings, sample_rate, what: str, f32: bool = False) -> Tuple[List[torch.Tensor], List[int]]:
@@ -725,50 +723,41 @@ class KeywordSpotter:
         return self._scan_batch(recordings, "scan_batch_f32", True, hop_frames, smooth_window, threshold, refractory, first_keyword,
                                 max_events, sample_rate)
 
-    def _scan_batch(self, recordings, what: str, f32: bool, hop_frames, smooth_window, threshold, refractory, first_keyword, max_events,
-                    sample_rate) -> List[ScanResult]:
+    def _scan_logits_batch(self, recs, rates, hop: int, want_labels: bool):
+        """Recordings of a batch -> (ctx, packed logits [W_pack, C] and labels [W_pack] (or None) on the device, windows [R],
+        win_off [R], length [R], per recording its window (start, end) times, frame_step): the packing, the plan and the ragged
+        scan ``scan_batch`` and ``score_batch`` share."""
         from kws import _native
 
-        recs, rates = self._batch_recordings(recordings, sample_rate, what, f32)
-        if int(hop_frames) < 1:
-            raise ModelError(f"{what}: hop_frames must be at least 1")
-        if threshold is not None:
-            if not 1 <= int(smooth_window) <= 256:
-                raise ModelError(f"{what}: smooth_window must be in [1, 256]")
-            if int(refractory) < 1 or int(first_keyword) < 0 or int(max_events) < 0:
-                raise ModelError(f"{what}: need refractory >= 1, first_keyword >= 0 and max_events >= 0")
-        cfg = self.config
-        frame_len, frame_step = _round_half_up(cfg.frame_length * cfg.sample_rate), _round_half_up(cfg.frame_step * cfg.sample_rate)
+        frame_len, frame_step = self._frame_geometry()
         buf, start, length = self._pack_batch(recs, rates)
-        R, C, hop = len(recs), self.model.num_classes, int(hop_frames)
         _, _, windows, win_off, W_pack = _native.host_ragged_plan(length, frame_len, frame_step, WINDOW_FRAMES, hop)
         ctx = self.model._context(self.device.index or 0)
-        logits = torch.empty((max(W_pack, 1), C), dtype=torch.float32, device=self.device)
-        labels = torch.empty((max(W_pack, 1),), dtype=torch.int32, device=self.device)
+        logits = torch.empty((max(W_pack, 1), self.model.num_classes), dtype=torch.float32, device=self.device)
+        labels = torch.empty((max(W_pack, 1),), dtype=torch.int32, device=self.device) if want_labels else None
         self.model._native_scan_ragged(ctx, buf, start, length, hop, logits, labels)
-        ev = None
+        times = [scan_window_times(int(windows[r]), hop, frame_len, frame_step, self.config.sample_rate, WINDOW_FRAMES, int(length[r]))
+                 for r in range(len(recs))]
+        return ctx, logits, labels, windows, win_off, times, frame_step
+
+    def _scan_batch(self, recordings, what: str, f32: bool, hop_frames, smooth_window, threshold, refractory, first_keyword, max_events,
+                    sample_rate) -> List[ScanResult]:
+        recs, rates = self._batch_recordings(recordings, sample_rate, what, f32)
+        self._decision_args(what, hop_frames, smooth_window, refractory, first_keyword, max_events, decide=threshold is not None)
+        ctx, logits, labels, windows, win_off, times, _ = self._scan_logits_batch(recs, rates, int(hop_frames), True)
+        events = None
         if threshold is not None:
-            m = int(max_events)
-            count = torch.empty((R,), dtype=torch.int32, device=self.device)
-            ev_w = torch.empty((R, m), dtype=torch.int32, device=self.device)
-            ev_k = torch.empty((R, m), dtype=torch.int32, device=self.device)
-            ev_s = torch.empty((R, m), dtype=torch.float32, device=self.device)
-            ctx.scan_detect_ragged_f32(logits, win_off, windows, smooth_window, first_keyword, threshold, refractory, count,
-                                       ev_w if m else None, ev_k if m else None, ev_s if m else None, m)
-            ctx.sync()
-            ev = (count.cpu().numpy(), ev_w.cpu().numpy(), ev_k.cpu().numpy(), ev_s.cpu().numpy(), m)
+            def detect(*out):
+                ctx.scan_detect_ragged_f32(logits, win_off, windows, smooth_window, first_keyword, threshold, refractory, *out)
+                ctx.sync()
+            events = self._events(detect, [end_s for _, end_s in times], max_events)
         ctx.sync()
         labels_h, logits_h = labels.cpu().numpy(), logits.cpu().numpy()
         out = []
-        for r in range(R):
+        for r, (start_s, _) in enumerate(times):
             W, o = int(windows[r]), int(win_off[r])
-            start_s, end_s = scan_window_times(W, hop, frame_len, frame_step, cfg.sample_rate, WINDOW_FRAMES, int(length[r]))
-            events = None
-            if ev is not None:
-                count, ev_w, ev_k, ev_s, m = ev
-                events = [[(float(end_s[ev_w[r, i]]), int(ev_k[r, i]), self.words[int(ev_k[r, i])], float(ev_s[r, i]))
-                           for i in range(min(int(count[r]), m))]]
-            out.append(ScanResult(labels_h[o:o + W][None, :].copy(), logits_h[o:o + W][None, :, :].copy(), start_s, events))
+            out.append(ScanResult(labels_h[o:o + W][None, :].copy(), logits_h[o:o + W][None, :, :].copy(), start_s,
+                                  None if events is None else [events[r]]))
         return out
 
     def score_batch(self, recordings, truths, thresholds, hop_frames: int = 1, smooth_window: int = 1, refractory: int = 50,
@@ -788,27 +777,16 @@ class KeywordSpotter:
 
     def _score_batch(self, recordings, what: str, f32: bool, truths, thresholds, hop_frames, smooth_window, refractory, first_keyword,
                      tolerance_s, sample_rate):
-        from kws import _native
-
         recs, rates = self._batch_recordings(recordings, sample_rate, what, f32)
         th = self._score_args(what, thresholds, hop_frames, smooth_window, refractory, first_keyword)
         lists = [list(t) if t is not None else [] for t in (truths if truths is not None else [[]] * len(recs))]
         if len(lists) != len(recs):
             raise ModelError(f"{what}: {len(lists)} annotation lists for {len(recs)} recordings")
-        cfg = self.config
         hours = sum(float(x.shape[0]) / float(rate) for x, rate in zip(recs, rates)) / 3600.0
-        frame_len, frame_step = _round_half_up(cfg.frame_length * cfg.sample_rate), _round_half_up(cfg.frame_step * cfg.sample_rate)
-        buf, start, length = self._pack_batch(recs, rates)
-        R, hop = len(recs), int(hop_frames)
-        _, _, windows, win_off, W_pack = _native.host_ragged_plan(length, frame_len, frame_step, WINDOW_FRAMES, hop)
-        ctx = self.model._context(self.device.index or 0)
-        logits = torch.empty((max(W_pack, 1), self.model.num_classes), dtype=torch.float32, device=self.device)
-        self.model._native_scan_ragged(ctx, buf, start, length, hop, logits, None)
-        ends = [scan_window_times(int(windows[r]), hop, frame_len, frame_step, cfg.sample_rate, WINDOW_FRAMES, int(length[r]))[1]
-                for r in range(R)]
+        ctx, logits, _, windows, win_off, times, frame_step = self._scan_logits_batch(recs, rates, int(hop_frames), False)
         call = lambda table, counts: ctx.scan_score_ragged_f32(logits, win_off, windows, smooth_window, first_keyword, refractory, th, table,
                                                                counts)
-        return self._score_report(ctx, call, th, lists, ends, tolerance_s, hours, hop, frame_step)
+        return self._score_report(ctx, call, th, lists, [end_s for _, end_s in times], tolerance_s, hours, int(hop_frames), frame_step)
 
     def segment_batch(self, recordings, threshold: float, on_window: int = 40, off_window: int = 80, pre_roll: int = 60,
                       max_seconds: float = 10.0, normalize: int = 16384, max_utterances: int = 1024, sample_rate=None,
@@ -835,45 +813,19 @@ class KeywordSpotter:
         from kws import _native
 
         recs, rates = self._batch_recordings(recordings, sample_rate, what, f32)
-        if not 1 <= int(on_window) <= int(off_window) <= 1024:
-            raise ModelError(f"{what}: need 1 <= on_window <= off_window <= 1024")
-        if int(pre_roll) < 0 or int(max_utterances) < 0 or not 0 <= int(normalize) <= 32767:
-            raise ModelError(f"{what}: need pre_roll >= 0, max_utterances >= 0 and normalize in [0, 32767]")
-        cfg = self.config
-        frame_len, frame_step = _round_half_up(cfg.frame_length * cfg.sample_rate), _round_half_up(cfg.frame_step * cfg.sample_rate)
-        max_frames = int(round(float(max_seconds) * cfg.sample_rate / frame_step))
-        if max_frames == 1 or max_frames < 0:
-            raise ModelError(f"{what}: max_seconds must be 0 (no limit) or at least two frames")
+        max_frames = self._segment_args(what, on_window, off_window, pre_roll, max_seconds, normalize, max_utterances)
         buf, start, length = self._pack_batch(recs, rates)
         R, m = len(recs), int(max_utterances)
-        frames, frame_off, _, _, _ = _native.host_ragged_plan(length, frame_len, frame_step, WINDOW_FRAMES, 1)
+        frames, frame_off, _, _, _ = _native.host_ragged_plan(length, *self._frame_geometry(), WINDOW_FRAMES, 1)
         ctx = self.model._context(self.device.index or 0)
-        feat = torch.empty((int(frame_off[R]), cfg.num_cepstral_coeffs), dtype=torch.float32, device=self.device)
+        feat = torch.empty((int(frame_off[R]), self.config.num_cepstral_coeffs), dtype=torch.float32, device=self.device)
         found = torch.empty((R + 5 * R * m,), dtype=torch.int32, device=self.device)  # the counts [R], then the slots [R, m, 5]
         (ctx.frames_ragged_f32 if f32 else ctx.frames_ragged_i16)(buf, start, length, 1, feat)
         ctx.segment_ragged_f32(feat, frame_off, frames, length, threshold, found[:R], found[R:] if m else None, m, on_window, off_window,
                                pre_roll, max_frames)
         ctx.sync()
         host = found.cpu().numpy()  # the one device-to-host read: counts and spans together
-        counts, slots = host[:R], host[R:].reshape(R, m, 5)
-        rows = []
-        for r in range(R):
-            for i in range(min(int(counts[r]), m)):
-                s, e, opened, closed, reason = (int(v) for v in slots[r, i])
-                if reason == 2 and not keep_unfinished:
-                    continue
-                rows.append((r, s, e, opened, closed, reason))
-        out: List[List[Utterance]] = [[] for _ in range(R)]
-        if not rows:
-            return out
-        # the whole buffer as ONE recording: a span of recording r lies start[r] samples on
-        span = torch.tensor([(0, int(start[r]) + s, int(start[r]) + e) for r, s, e, _, _, _ in rows], dtype=torch.int32).to(self.device)
-        cut = (lambda clips, peaks: ctx.cut_f32(buf[None, :], span, clips, int(normalize) / 32768.0, peaks)) if f32 else \
-              (lambda clips, peaks: ctx.cut_i16(buf[None, :], span, clips, int(normalize), peaks))
-        for utt in _classify_spans(ctx, self.model, self.device, self.words, self.model.num_classes, cfg.desired_samples, float(cfg.sample_rate), frame_step,
-                                   rows, cut, f32):
-            out[utt.recording].append(utt)
-        return out
+        return self._utterances(ctx, host, R, m, keep_unfinished, buf[None, :], start, normalize)
 
     def _decode_file(self, path: str, resample: bool, what: str) -> Tuple[np.ndarray, int]:
         """One wav file under the decode rules and error messages of ``scan_file`` / ``segment_file`` -> (int16 [n], rate)."""

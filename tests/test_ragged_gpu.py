@@ -456,7 +456,90 @@ def test_cut_over_the_shared_buffer_equals_the_cut_per_recording(ctx):
         assert torch.equal(clips[u], c1[0]) and int(peaks[u]) == int(p1[0]), f"span {u}"
 
 
-# ---- 6. refusals ---------------------------------------------------------------------------------------------------------------
+# ---- 6. one host path, two layouts ---------------------------------------------------------------------------------------------
+LAY_R, LAY_W, LAY_F = 3, 130, 300            # 130 windows: two chunks of 64 of the walk and two more; 300 frames: past one 256-frame workgroup
+LAY_SEG = dict(on=3, off=5, pre_roll=2, max_frames=40, max_utts=8)
+
+
+def layout_flags():
+    """Voiced flags [3, 300]: a short utterance and one longer than the time-out; one that runs to the end; one of each."""
+    v = np.zeros((LAY_R, LAY_F), np.int64)
+    v[0, 20:50] = v[0, 100:200] = 1
+    v[1, 250:] = 1
+    v[2, 60:70] = v[2, 280:] = 1
+    return v
+
+
+def test_the_layout_flags_close_for_every_reason_on_the_cpu():
+    n = n_for_frames(LAY_F)
+    reasons = [{u[4] for u in gref.walk_ref(v, LAY_SEG["on"], LAY_SEG["off"], LAY_SEG["pre_roll"], LAY_SEG["max_frames"], n)} for v in layout_flags()]
+    assert reasons[0] >= {0, 1} and 2 in reasons[1] and reasons[2] == {0, 2}, reasons
+
+
+def packed_rows(per_rec, first, gap, tail=4):
+    """[R, n, ...] -> (packed [rows, ...] with NaN rows ahead of, between and behind the recordings, the first row of each)."""
+    R, n = per_rec.shape[:2]
+    off = [first + r * (n + gap) for r in range(R)]
+    packed = torch.full((off[-1] + n + tail,) + tuple(per_rec.shape[2:]), float("nan"), device=DEV)
+    for r, o in enumerate(off):
+        packed[o:o + n] = per_rec[r]
+    return packed, off
+
+
+@pytest.mark.parametrize("S", [1, 7])
+@pytest.mark.parametrize("Cn", [12, 64])
+def test_equal_and_ragged_layouts_agree(ctx, Cn, S):
+    """The same values through the equal-length entry and, packed with first != 0 and NaN rows between the recordings, through
+    its ragged twin: every output equal bit for bit, no row of no recording written."""
+    R, W, M = LAY_R, LAY_W, 8
+    gen = torch.Generator().manual_seed(100 * Cn + S)
+    z = (3.0 * torch.randn((R, W, Cn), generator=gen)).to(DEV)
+    packed, off = packed_rows(z, 5, 9)
+    assert off == [5, 5 + 130 + 9, 5 + 2 * (130 + 9)]
+    windows = [W] * R
+    ints = lambda *shape: torch.full(shape, -1, dtype=torch.int32, device=DEV)
+    # decisions
+    a = dict(count=ints(R), w=ints(R, M), k=ints(R, M), s=torch.zeros((R, M), device=DEV), sm=torch.full((R, W, Cn), float("nan"), device=DEV))
+    b = dict(count=ints(R), w=ints(R, M), k=ints(R, M), s=torch.zeros((R, M), device=DEV), sm=torch.full_like(packed, float("nan")))
+    ctx.scan_detect_f32(z, S, 2, 1.5 / Cn, 4, a["count"], a["w"], a["k"], a["s"], M, a["sm"])
+    ctx.scan_detect_ragged_f32(packed, off, windows, S, 2, 1.5 / Cn, 4, b["count"], b["w"], b["k"], b["s"], M, b["sm"])
+    torch.cuda.synchronize()
+    assert int(a["count"].min()) > M, "every recording fires more often than max_events"
+    for key in ("count", "w", "k"):
+        assert torch.equal(a[key], b[key]), key
+    assert torch.equal(a["s"].view(torch.int32), b["s"].view(torch.int32))
+    owned = torch.zeros(packed.shape[0], dtype=torch.bool, device=DEV)
+    for r, o in enumerate(off):
+        owned[o:o + W] = True
+        assert torch.equal(a["sm"][r].view(torch.int32), b["sm"][o:o + W].view(torch.int32)), f"recording {r}: smoothed posteriors differ"
+    assert torch.isnan(b["sm"][~owned]).all(), "a row of no recording was written"
+    # scores: five thresholds, the one above among them, and a dozen annotations around the first four events of each recording
+    # (events lie 4 windows apart, so no two rows overlap): hits at the third threshold, false alarms everywhere
+    th = (np.array([0.5, 1.0, 1.5, 2.0, 3.0]) / Cn).astype(np.float32)
+    ev_w, ev_k = a["w"].cpu().numpy(), a["k"].cpu().numpy()
+    truth = np.array([(r, ev_k[r, i], max(ev_w[r, i] - 1, 0), ev_w[r, i] + 1) for r in range(R) for i in range(4)], np.int32)
+    ca = torch.full((5, Cn, 4), -7, dtype=torch.int64, device=DEV)
+    cb = torch.full((5, Cn, 4), -7, dtype=torch.int64, device=DEV)
+    ctx.scan_score_f32(z, S, 2, 4, th, truth, ca)
+    ctx.scan_score_ragged_f32(packed, off, windows, S, 2, 4, th, truth, cb)
+    torch.cuda.synchronize()
+    assert torch.equal(ca, cb) and int(ca[..., 0].sum()) > 0 and int(ca[..., 1].sum()) > 0, "hits and false alarms, the same"
+    # utterances
+    p = LAY_SEG
+    n = n_for_frames(LAY_F)
+    feat = torch.from_numpy(gref.frames_from_flags(layout_flags(), N_CEP, seed=Cn + S)).to(DEV)
+    assert feat.shape == (R, LAY_F, N_CEP)
+    fpacked, foff = packed_rows(feat, 4, 7)
+    ua, ub = (ints(R), ints(R, p["max_utts"], 5)), (ints(R), ints(R, p["max_utts"], 5))
+    ctx.segment_f32(feat, n, 0.0, ua[0], ua[1], p["max_utts"], p["on"], p["off"], p["pre_roll"], p["max_frames"])
+    ctx.segment_ragged_f32(fpacked, foff, [LAY_F] * R, [n] * R, 0.0, ub[0], ub[1], p["max_utts"], p["on"], p["off"], p["pre_roll"], p["max_frames"])
+    torch.cuda.synchronize()
+    assert torch.equal(ua[0], ub[0]) and torch.equal(ua[1], ub[1])
+    counts, slots = ua[0].cpu().numpy(), ua[1].cpu().numpy()
+    assert {int(slots[r, i, 4]) for r in range(R) for i in range(min(int(counts[r]), p["max_utts"]))} == {0, 1, 2}
+
+
+# ---- 7. refusals ---------------------------------------------------------------------------------------------------------------
 def test_refusals_launch_nothing(ctx, e2e_golden):
     import ctypes as Ct
 

@@ -117,6 +117,41 @@ def test_defaults_are_unchanged_and_decode_is_checked(spotter, tmp_path):
         spotter.segment_files([slow], decode="any", threshold=0.0)
 
 
+def test_the_file_methods_refuse_in_their_own_words(spotter, tmp_path):
+    """The full message of every decode refusal of the four file methods, before any device call.  Under decode="pcm16" the
+    plural methods speak with the singular method's name; under decode="any" with their own."""
+    def write(name, rate, width, channels=1):
+        path = str(tmp_path / name)
+        with wave.open(path, "wb") as w:
+            w.setnchannels(channels)
+            w.setsampwidth(width)
+            w.setframerate(rate)
+            w.writeframes(b"\0" * (width * channels * 64))
+        return path
+
+    slow, slow24, stereo = write("slow.wav", 8000, 2), write("slow24.wav", 8000, 3), write("stereo.wav", 16000, 2, channels=2)
+    methods = {"scan_file": (spotter.scan_file, "scan_file", " (there is no float32 scan)"),
+               "segment_file": (lambda p, **kw: spotter.segment_file(p, threshold=0.0, **kw), "segment_file", ""),
+               "scan_files": (lambda p, **kw: spotter.scan_files([p], **kw), "scan_file", " (there is no float32 scan)"),
+               "segment_files": (lambda p, **kw: spotter.segment_files([p], threshold=0.0, **kw), "segment_file", "")}
+    for name, (call, singular, tail) in methods.items():
+        def message(path, **kw):
+            with pytest.raises(AudioProcessingError) as e:
+                call(path, **kw)
+            assert e.value.args[0].startswith("Audio processing error: ")
+            return e.value.args[0][len("Audio processing error: "):]
+
+        assert message(slow) == f"{slow}: sample rate 8000 != 16000; resampling is not implemented"
+        assert message(slow, decode="any") == f"{slow}: sample rate 8000 != 16000; pass resample=True to {name} to resample on the device"
+        assert message(slow24, resample=True) == (f"{slow24}: sample rate 8000 != 16000 and the file is not 16-bit mono PCM; the device "
+                                                  f"resampler of {singular} takes int16 only{tail}")
+        assert message(slow24) == f"{slow24}: only 16-bit PCM WAV is supported (sample width 3)"
+        assert message(stereo) == f"{stereo}: 2 channels; {singular} takes mono files"
+        assert message(stereo, resample=True) == f"{stereo}: 2 channels; {singular} takes mono files"
+        assert message(slow, decode="float") == f"{name}: decode must be 'pcm16' or 'any', got 'float'"
+        assert message(slow, decode=None, resample=True) == f"{name}: decode must be 'pcm16' or 'any', got None"
+
+
 def test_the_restatement_of_the_float_cut_on_a_hand_made_case():
     x = np.array([[0.25, -0.5, np.nan, 0.125, 0.0, 1.5, -2.0, 0.0625]], np.float32)
     spans = [(0, 0, 4), (0, 3, 5), (0, 4, 5), (0, 5, 99), (0, 2, 2), (1, 0, 4), (-1, 0, 4), (0, -3, 2)]
