@@ -226,6 +226,43 @@ int kws_cnn_trad_backward_f32(kws_ctx* ctx, const float* d_feat, int B, const fl
 int kws_cnn_trad_train_debug_f32(kws_ctx* ctx, const float* d_feat, int B, float* d_conv1, int32_t* d_winner, float* d_conv2,
                                  float* d_hidden);
 
+/* Training the BatchNorm DS-CNN (DepthwiseSeparableConvBN, kws/libs/models.py: conv -> BatchNorm2d -> ReLU after conv1 and after
+ * every pointwise convolution, conv -> BatchNorm2d after every depthwise one).  The three entries below take the parameters as a
+ * DEVICE blob d_params float32 [n_floats] in DepthwiseSeparableConvBN.parameters() order -- the 20 tensors of kws_load_dscnn (one
+ * input channel), then weight [64] | bias [64] of bn_conv1, bn_dw.0 .. 3, bn_pw.0 .. 3: n_floats = 25664 + 65*num_classes + 1152 --
+ * and neither need nor touch the context's loaded model.  d_feat float32 [B, 1, T, F], any map kws_forward_map_f32 accepts.
+ *
+ * Train-mode forward: every BatchNorm normalises with the mean and the biased variance of its input over the batch and all
+ * positions, y = gamma (z - mean) / sqrt(var + eps) + beta; the ring a padded pointwise convolution puts around its output equals
+ * its bias and counts in that layer's statistics.  d_logits float32 [B, num_classes]; d_label int32 [B] or NULL; d_stats float32
+ * [9][2][64] or NULL: batch mean and UNBIASED batch variance (var N / (N - 1), what nn.BatchNorm2d's running_var takes) per layer,
+ * in the order conv1, dw1, pw1, dw2, pw2, dw3, pw3, dw4, pw4.  The sums are taken in float64 over per-workgroup partials reduced in
+ * a fixed order (no float atomics): logits and statistics are bit-identical from call to call.
+ * Statistics span the batch, so the batch is not chunked: B above kws_host_dscnn_bn_max_batch(T, F) is KWS_EUNSUPPORTED, refused
+ * on the host before any allocation or launch.  B * H1 * W1 < 2 (one value per channel in the first layer; torch raises there too),
+ * a NULL pointer, B <= 0, an n_floats other than the layout's, eps not positive and finite: KWS_EINVAL.  num_classes outside
+ * [1, 64]: KWS_EUNSUPPORTED.  Map limits as kws_forward_map_f32.  Asynchronous on the context stream; the context keeps a workspace
+ * of about 1.8 MB per clip (99 x 10). */
+int kws_dscnn_bn_train_forward_f32(kws_ctx* ctx, const float* d_params, size_t n_floats, int num_classes, const float* d_feat, int B,
+                                   int T, int F, float eps, float* d_logits, int32_t* d_label, float* d_stats);
+/* Gradient of a scalar loss through that forward, given d_dlogits = dloss/dlogits float32 [B, num_classes]: d_grad float32
+ * [n_floats] in the layout of d_params, overwritten.  Recompute, not save: the call redoes the train-mode forward into the
+ * context's training workspace (it is deterministic, so the backward sees the bits the forward call produced), then per BatchNorm
+ * layer S1 = sum dy^ and S2 = sum dy^ x^ in float64 (dy^: the incoming gradient, masked by output > 0 where a ReLU follows),
+ * g_beta = S1, g_gamma = S2, dz = gamma / sigma (dy^ - S1 / N - x^ S2 / N), and dz through the convolution's backward of
+ * kws_dscnn_backward_f32.  Deterministic as that entry.  Arguments, limits and errors as kws_dscnn_bn_train_forward_f32; the
+ * gradient with respect to the features is not computed. */
+int kws_dscnn_bn_backward_f32(kws_ctx* ctx, const float* d_params, size_t n_floats, int num_classes, const float* d_feat, int B, int T,
+                              int F, float eps, const float* d_dlogits, float* d_grad);
+/* Parity aid: kws_dscnn_bn_train_forward_f32 that also stores the five post-ReLU activations a0 .. a4 to d_layers, in the layout
+ * of kws_forward_map_debug_f32 (conv1, then blocks 1..4 with their rings, each [B][64][H][W]).  Tests pin their references' ReLU
+ * decisions to these. */
+int kws_dscnn_bn_train_debug_f32(kws_ctx* ctx, const float* d_params, size_t n_floats, int num_classes, const float* d_feat, int B, int T,
+                                 int F, float eps, float* d_logits, int32_t* d_label, float* d_layers, float* d_stats);
+/* Host only: the largest B the three entries above take on a T x F map -- what fits 2^31 floats of workspace, at most 16384; 0 for
+ * a map they refuse.  4747 at 99 x 10. */
+int kws_host_dscnn_bn_max_batch(int T, int F);
+
 /* One depthwise-separable block on an arbitrary map -- replaces DepthwiseSeparableConvBlock.forward
  * (kws/libs/models.py:108-119) used on its own: depthwise Conv2d(C_in, C_in, kernel_size, stride, padding, groups=C_in)
  * + bias, then pointwise Conv2d(C_in, C_out, 1, padding=padding) + bias, then ReLU.  d_x float32 [B,C_in,H,W]; d_dw_w

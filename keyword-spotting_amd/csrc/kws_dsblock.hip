@@ -11,6 +11,9 @@
 //   kws_dsblock_pointwise_kernel   64 positions x 64 output channels per workgroup, the depthwise tile staged through
 //                                  LDS in slabs of 16 input channels, 4 x 4 outputs per thread, f32 FMA in channel
 //                                  order; ring positions are written by the same kernel (relu(bias), no arithmetic)
+// kws_dsblock_pointwise_pre_kernel and kws_conv1_any_pre_kernel are the pointwise and the conv1 kernel without the ReLU (the ring
+// is then the bias): the pre-activations of the train-mode BatchNorm path (kws_dscnn_bn.hip).  Each pair shares one body, included
+// as text (kws_dsblock_pointwise_body.h, kws_conv1_any_body.h).
 #include <algorithm>
 
 #include "kws_ctx.h"
@@ -50,66 +53,15 @@ constexpr int TP = 64, TC = 64, TK = 16;  // positions x output channels per wor
 __global__ __launch_bounds__(256) void kws_dsblock_pointwise_kernel(const float* __restrict__ dw, int C_in, int P /*Ho*Wo*/,
                                                                     const float* __restrict__ w, const float* __restrict__ bias,
                                                                     int C_out, int Ho, int Wo, int pad, float* __restrict__ out) {
-    __shared__ float s_x[TK][TP + 1];
-    __shared__ float s_w[TK][TC + 1];
-    const int tid = threadIdx.x;
-    const int b = blockIdx.z, p0 = blockIdx.x * TP, c0 = blockIdx.y * TC;
-    const int tp = tid & 15, tc = tid >> 4;  // this thread: positions tp + 16 i, output channels tc + 16 j
-    const int Hp = Ho + 2 * pad, Wp = Wo + 2 * pad;
-    float acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-    const float* dwb = dw + (long)b * C_in * P;
-    for (int k0 = 0; k0 < C_in; k0 += TK) {
-        for (int e = tid; e < TK * TP; e += 256) {
-            const int kk = e / TP, pp = e % TP;
-            s_x[kk][pp] = (k0 + kk < C_in && p0 + pp < P) ? dwb[(long)(k0 + kk) * P + p0 + pp] : 0.f;
-        }
-        for (int e = tid; e < TK * TC; e += 256) {
-            const int cc = e / TK, kk = e % TK;
-            s_w[kk][cc] = (k0 + kk < C_in && c0 + cc < C_out) ? w[(long)(c0 + cc) * C_in + k0 + kk] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < TK; ++kk) {
-            float xv[4], wv[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) xv[i] = s_x[kk][tp + 16 * i];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) wv[j] = s_w[kk][tc + 16 * j];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(wv[j], xv[i], acc[i][j]);
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int co = c0 + tc + 16 * j;
-        if (co >= C_out) continue;
-        const float bv = bias[co];
-        float* op = out + ((long)b * C_out + co) * Hp * Wp;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int p = p0 + tp + 16 * i;
-            if (p < P) op[(long)(p / Wo + pad) * Wp + (p % Wo) + pad] = relu(acc[i][j] + bv);
-        }
-    }
-    // the ring: the 1x1 convolution sees only zero padding there, so its value is relu(bias); written once per
-    // (batch, channel tile) by the workgroup of the first position tile
-    if (pad > 0 && blockIdx.x == 0) {
-        for (int cc = 0; cc < TC && c0 + cc < C_out; ++cc) {
-            const float rv = relu(bias[c0 + cc]);
-            float* op = out + ((long)b * C_out + c0 + cc) * Hp * Wp;
-            for (int e = tid; e < Hp * Wp; e += 256) {
-                const int h = e / Wp, x = e % Wp;
-                if (h < pad || h >= Ho + pad || x < pad || x >= Wo + pad) op[e] = rv;
-            }
-        }
-    }
+    constexpr bool RELU_OUT = true;
+#include "kws_dsblock_pointwise_body.h"
+}
+// no ReLU: conv + bias, the ring equal to the bias
+__global__ __launch_bounds__(256) void kws_dsblock_pointwise_pre_kernel(const float* __restrict__ dw, int C_in, int P /*Ho*Wo*/,
+                                                                    const float* __restrict__ w, const float* __restrict__ bias,
+                                                                    int C_out, int Ho, int Wo, int pad, float* __restrict__ out) {
+    constexpr bool RELU_OUT = false;
+#include "kws_dsblock_pointwise_body.h"
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -125,40 +77,14 @@ __global__ __launch_bounds__(256) void kws_dsblock_pointwise_kernel(const float*
 constexpr int C1A_POS = 64, C1A_PER = C1A_POS / 4;
 __global__ __launch_bounds__(256) void kws_conv1_any_kernel(const float* __restrict__ x, int C_in, int T, int F, const float* __restrict__ wt,
                                                             const float* __restrict__ bias, int Ho, int Wo, float* __restrict__ out) {
-    extern __shared__ float plane[];  // (T + 4) x (F + 4)
-    const int tid = threadIdx.x, co = tid & 63, pg = tid >> 6;
-    const int Hp = T + 4, Wp = F + 4, P = Ho * Wo, p0 = blockIdx.x * C1A_POS;
-    float acc[C1A_PER];
-    int base[C1A_PER];  // plane offset of the position's top-left tap (position p: rows 2*(p / Wo) .., columns 2*(p % Wo) ..)
-#pragma unroll
-    for (int k = 0; k < C1A_PER; ++k) {
-        acc[k] = 0.f;
-        const int p = min(p0 + pg + 4 * k, P - 1);
-        base[k] = 2 * (p / Wo) * Wp + 2 * (p % Wo);
-    }
-    const float* xc = x + (size_t)blockIdx.y * C_in * T * F;
-    for (int ci = 0; ci < C_in; ++ci) {
-        __syncthreads();
-        for (int i = tid; i < Hp * Wp; i += 256) {
-            const int r = i / Wp - 2, c = i % Wp - 2;
-            plane[i] = ((unsigned)r < (unsigned)T && (unsigned)c < (unsigned)F) ? xc[(size_t)ci * T * F + r * F + c] : 0.f;
-        }
-        __syncthreads();
-        const float* wc = wt + (size_t)ci * 100 * 64 + co;
-        for (int tap = 0; tap < 100; ++tap) {
-            const float wv = wc[(size_t)tap * 64];
-            const int off = (tap / 10) * Wp + tap % 10;
-#pragma unroll
-            for (int k = 0; k < C1A_PER; ++k) acc[k] = fmaf(wv, plane[base[k] + off], acc[k]);
-        }
-    }
-    float* o = out + ((size_t)blockIdx.y * 64 + co) * P;
-    const float bv = bias[co];
-#pragma unroll
-    for (int k = 0; k < C1A_PER; ++k) {
-        const int p = p0 + pg + 4 * k;
-        if (p < P) o[p] = relu(acc[k] + bv);
-    }
+    constexpr bool RELU_OUT = true;
+#include "kws_conv1_any_body.h"
+}
+// no ReLU: conv1 + bias
+__global__ __launch_bounds__(256) void kws_conv1_any_pre_kernel(const float* __restrict__ x, int C_in, int T, int F, const float* __restrict__ wt,
+                                                            const float* __restrict__ bias, int Ho, int Wo, float* __restrict__ out) {
+    constexpr bool RELU_OUT = false;
+#include "kws_conv1_any_body.h"
 }
 
 // conv1 for input_channels > 1 on the 99 x 10 map, in front of the fused kernel's PRECONV entry (kws_dscnn.hip; reference
@@ -237,15 +163,15 @@ __global__ __launch_bounds__(256) void kws_pool_fc_kernel(const float* __restric
 }  // namespace
 
 hipError_t launch_conv1_any(hipStream_t s, const float* d_x, int B, int C_in, int T, int F, const float* d_wt, const float* d_bias,
-                            float* d_out) {
+                            float* d_out, bool relu_out) {
     const int Ho = (T + 4 - 10) / 2 + 1, Wo = (F + 4 - 10) / 2 + 1;
     const size_t lds = sizeof(float) * (size_t)(T + 4) * (F + 4);
+    const auto kernel = relu_out ? kws_conv1_any_kernel : kws_conv1_any_pre_kernel;
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kws_conv1_any_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kws_conv1_any_kernel, dim3((Ho * Wo + C1A_POS - 1) / C1A_POS, B), dim3(256), lds, s, d_x, C_in, T, F, d_wt, d_bias,
-                       Ho, Wo, d_out);
+    hipLaunchKernelGGL(kernel, dim3((Ho * Wo + C1A_POS - 1) / C1A_POS, B), dim3(256), lds, s, d_x, C_in, T, F, d_wt, d_bias, Ho, Wo, d_out);
     return hipGetLastError();
 }
 
@@ -260,20 +186,32 @@ hipError_t launch_pool_fc(hipStream_t s, const float* d_x, int B, int HW, const 
     return hipGetLastError();
 }
 
-hipError_t launch_dsblock(hipStream_t s, const float* d_x, int B, int C_in, int H, int W, const float* d_dw_w, const float* d_dw_b,
-                          const float* d_pw_w, const float* d_pw_b, int C_out, int k, int stride, int pad, float* d_ws,
-                          float* d_out) {
+hipError_t launch_dsblock_depthwise(hipStream_t s, const float* d_x, int B, int C_in, int H, int W, const float* d_dw_w,
+                                    const float* d_dw_b, int k, int stride, int pad, float* d_out) {
     const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
     const long total = (long)B * C_in * Ho * Wo;
     const int blocks = (int)std::min<long>((total + 255) / 256, 1 << 20);
     hipLaunchKernelGGL(kws_dsblock_depthwise_kernel, dim3(blocks), dim3(256), 0, s, d_x, C_in, H, W, d_dw_w, d_dw_b, k, stride, pad,
-                       Ho, Wo, d_ws, total);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    const int P = Ho * Wo;
-    hipLaunchKernelGGL(kws_dsblock_pointwise_kernel, dim3((P + TP - 1) / TP, (C_out + TC - 1) / TC, B), dim3(256), 0, s, d_ws, C_in,
-                       P, d_pw_w, d_pw_b, C_out, Ho, Wo, pad, d_out);
+                       Ho, Wo, d_out, total);
     return hipGetLastError();
+}
+
+hipError_t launch_dsblock_pointwise(hipStream_t s, const float* d_dw, int B, int C_in, int Ho, int Wo, const float* d_pw_w,
+                                    const float* d_pw_b, int C_out, int pad, float* d_out, bool relu_out) {
+    const int P = Ho * Wo;
+    hipLaunchKernelGGL(relu_out ? kws_dsblock_pointwise_kernel : kws_dsblock_pointwise_pre_kernel,
+                       dim3((P + TP - 1) / TP, (C_out + TC - 1) / TC, B), dim3(256), 0, s, d_dw, C_in, P, d_pw_w, d_pw_b, C_out, Ho, Wo, pad,
+                       d_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_dsblock(hipStream_t s, const float* d_x, int B, int C_in, int H, int W, const float* d_dw_w, const float* d_dw_b,
+                          const float* d_pw_w, const float* d_pw_b, int C_out, int k, int stride, int pad, float* d_ws,
+                          float* d_out) {
+    const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
+    hipError_t e = launch_dsblock_depthwise(s, d_x, B, C_in, H, W, d_dw_w, d_dw_b, k, stride, pad, d_ws);
+    if (e != hipSuccess) return e;
+    return launch_dsblock_pointwise(s, d_ws, B, C_in, Ho, Wo, d_pw_w, d_pw_b, C_out, pad, d_out, true);
 }
 
 int check_dscnn_map(kws_ctx* c, const char* fn, int T, int F) {

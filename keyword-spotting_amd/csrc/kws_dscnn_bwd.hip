@@ -22,6 +22,10 @@
 //   kws_bwd_conv1_kernel       dZ1 = dA0 [A0 > 0]; g_c1_b = sum dZ1, g_c1_w as an implicit GEMM (M = 64, N = 100, K = B H1 W1)
 //                              on the VALU; no input gradient
 //   kws_bwd_reduce_kernel      fixed-order sum of the per-workgroup partials into d_grad
+//   kws_bwd_pointwise_dz_kernel, kws_bwd_conv1_dz_kernel   the same two kernels fed with a finished dZ instead of dY and the mask
+//                              Y > 0: what a BatchNorm between the convolution and its ReLU hands back (kws_dscnn_bn.hip, through
+//                              the launch_bwd_* functions of kws_train.h).  Each pair shares one body, included as text
+//                              (kws_bwd_pointwise_body.h, kws_bwd_conv1_body.h).
 //
 // Deterministic: no float atomics, but the clip groups of kws_train.h with at most 1024 groups per chunk (chunks after the first
 // add onto d_grad in chunk order).  G, cpg and the chunking depend on B and the map only, so the same inputs and B give
@@ -36,12 +40,7 @@ namespace kws {
 namespace {
 
 using DL = DscnnLayout;
-constexpr int BWD_MAX_GROUPS = 1024;          // partial rows per stage and chunk
 constexpr int PW_TP = 64;                     // interior positions per tile of the pointwise backward
-constexpr int PW_PART = DL::PW_W + DL::CO;    // pointwise.weight [co][ci] | pointwise.bias
-constexpr int DW_PART = DL::DW_W + DL::CO;    // depthwise.weight [c][3][3] | depthwise.bias
-constexpr int C1_PART = DL::C1_W + DL::CO;    // conv1.weight [co][10][10] | conv1.bias
-constexpr int fc_part(int C) { return C * DL::CO + C; }  // fc.weight [C][64] | fc.bias
 
 // ---- global average pool + fc ---------------------------------------------------------------------------------------------
 // One workgroup per clip group.  Per clip: pooled = mean of the block-4 output over its Q4 positions (ring included),
@@ -105,91 +104,16 @@ __global__ __launch_bounds__(256) void kws_bwd_pointwise_kernel(const float* __r
                                                                 const float* __restrict__ y, const float* __restrict__ xdw,
                                                                 const float* __restrict__ w, int H, int W, int nb, int cpg,
                                                                 float* __restrict__ dxdw, float* __restrict__ part) {
-    __shared__ float s_w[64][65];        // W[co][ci]
-    __shared__ float s_dz[64][PW_TP + 1];  // dZ[co][p]
-    __shared__ float s_x[64][PW_TP + 1];   // X_dw[ci][p]
-    __shared__ float s_b[4][64];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = blockIdx.x;
-    const int P = H * W, Wq = W + 2, Q = (H + 2) * Wq;
-    for (int e = tid; e < DL::PW_W; e += 256) s_w[e >> 6][e & 63] = w[e];
-    __syncthreads();
-    const int co0 = 32 * (wv >> 1), ci0 = 32 * (wv & 1), pt0 = 32 * (wv >> 1);
-    // A operand of dX_dw = W^T dZ (32x32x2: A[i = l & 31][k = l >> 5]): A[ci][co] = W[co][ci], k-step s covers co 2s, 2s + 1
-    float wa[32];
-#pragma unroll
-    for (int s = 0; s < 32; ++s) wa[s] = s_w[2 * s + (lane >> 5)][ci0 + (lane & 31)];
-    // the MFMA calls, zero fills and D rows stay spelled out in this kernel: through kws_train.h's mfma32 / zero16 / drow it
-    // took 176 VGPRs for 168
-    f32x16 gw;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) gw[r] = 0.f;
-    float bsum = 0.f;
-    const int b_end = group_end(g, cpg, nb);
-    for (int b = g * cpg; b < b_end; ++b) {
-        const float* dyb = dy + (size_t)b * dy_clip;
-        const float* yb = y + (size_t)b * 64 * Q;
-        const float* xb = xdw + (size_t)b * 64 * P;
-        {
-            const float* yc = yb + (size_t)lane * Q;
-            const float* dc = dyb + (size_t)lane * dy_plane;
-            for (int r0 = wv; r0 < Q; r0 += 4 * RUN) {  // runs of RUN positions, each summed from zero
-                const int r1 = min(Q, r0 + 4 * RUN);
-                float t = 0.f;
-                for (int q = r0; q < r1; q += 4)
-                    if (yc[q] > 0.f) t += dc[(size_t)q * dy_qstep];
-                bsum += t;
-            }
-        }
-        for (int p0 = 0; p0 < P; p0 += PW_TP) {
-            for (int e = tid; e < 64 * PW_TP; e += 256) {
-                const int row = e / PW_TP, pp = e % PW_TP, p = p0 + pp;
-                float dz = 0.f, xv = 0.f;
-                if (p < P) {
-                    const int q = (p / W + 1) * Wq + p % W + 1;
-                    const float yv = yb[(size_t)row * Q + q];
-                    dz = yv > 0.f ? dyb[(size_t)row * dy_plane + (size_t)q * dy_qstep] : 0.f;
-                    xv = xb[(size_t)row * P + p];
-                }
-                s_dz[row][pp] = dz;
-                s_x[row][pp] = xv;
-            }
-            __syncthreads();
-            // g_pw_w: A[i = co][k = p] = dZ, B[k = p][j = ci] = X_dw (32x32x2: lane l holds k = l >> 5); the tile's sum starts
-            // from zero and is added to the running one, so no f32 chain runs longer than 64 positions
-            f32x16 gt;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) gt[r] = 0.f;
-#pragma unroll
-            for (int s = 0; s < PW_TP / 2; ++s) {
-                const float a = s_dz[co0 + (lane & 31)][2 * s + (lane >> 5)];
-                const float bb = s_x[ci0 + (lane & 31)][2 * s + (lane >> 5)];
-                gt = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bb, gt, 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) gw[r] += gt[r];
-            // dX_dw: B[k = co][j = p] = dZ
-            f32x16 d;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) d[r] = 0.f;
-#pragma unroll
-            for (int s = 0; s < 32; ++s) d = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[s], s_dz[2 * s + (lane >> 5)][pt0 + (lane & 31)], d, 0, 0, 0);
-            // C/D: col = l & 31 (position), row = (r & 3) + 8 (r >> 2) + 4 (l >> 5) (input channel)
-            const int p = p0 + pt0 + (lane & 31);
-            if (p < P) {
-                float* o = dxdw + (size_t)b * 64 * P + (size_t)ci0 * P + p;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[(size_t)((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * P] = d[r];
-            }
-            __syncthreads();
-        }
-    }
-    float* pg = part + (size_t)g * PW_PART;
-    // C/D of 32x32: col = l & 31 (ci), row = (r & 3) + 8 (r >> 2) + 4 (l >> 5) (co)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) pg[(co0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 64 + ci0 + (lane & 31)] = gw[r];
-    s_b[wv][lane] = bsum;
-    __syncthreads();
-    if (tid < 64) pg[DL::PW_W + tid] = (s_b[0][tid] + s_b[1][tid]) + (s_b[2][tid] + s_b[3][tid]);
+    constexpr bool MASK = true;
+#include "kws_bwd_pointwise_body.h"
+}
+// dy = the finished dZ [nb][64][Q] (dy_clip = 64 Q, dy_plane = Q, dy_qstep = 1); y is not read
+__global__ __launch_bounds__(256) void kws_bwd_pointwise_dz_kernel(const float* __restrict__ dy, long dy_clip, int dy_plane, int dy_qstep,
+                                                                const float* __restrict__ y, const float* __restrict__ xdw,
+                                                                const float* __restrict__ w, int H, int W, int nb, int cpg,
+                                                                float* __restrict__ dxdw, float* __restrict__ part) {
+    constexpr bool MASK = false;
+#include "kws_bwd_pointwise_body.h"
 }
 
 // ---- depthwise 3x3 (padding 1, groups 64) --------------------------------------------------------------------------------
@@ -250,63 +174,15 @@ constexpr int C1B_TP = 64;
 __global__ __launch_bounds__(256) void kws_bwd_conv1_kernel(const float* __restrict__ da, const float* __restrict__ a,
                                                             const float* __restrict__ x, int T, int F, int H1, int W1, int nb,
                                                             int cpg, float* __restrict__ part) {
-    __shared__ float s_dz[C1B_TP][65];
-    __shared__ float s_b[4][64];
-    const int tid = threadIdx.x, co = tid & 63, r0 = tid >> 6, g = blockIdx.x;
-    const int P = H1 * W1;
-    float acc[3][10];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int k = 0; k < 10; ++k) acc[i][k] = 0.f;
-    float bsum = 0.f;
-    const int b_end = group_end(g, cpg, nb);
-    for (int b = g * cpg; b < b_end; ++b) {
-        const float* dab = da + (size_t)b * 64 * P;
-        const float* ab = a + (size_t)b * 64 * P;
-        const float* xb = x + (size_t)b * T * F;
-        for (int p0 = 0; p0 < P; p0 += C1B_TP) {
-            for (int e = tid; e < 64 * C1B_TP; e += 256) {
-                const int ch = e / C1B_TP, pp = e % C1B_TP, p = p0 + pp;
-                float dz = 0.f;
-                if (p < P && ab[(size_t)ch * P + p] > 0.f) dz = dab[(size_t)ch * P + p];
-                s_dz[pp][ch] = dz;
-            }
-            __syncthreads();
-            const int n = min(C1B_TP, P - p0);
-            for (int pp = 0; pp < n; ++pp) {
-                const int p = p0 + pp, oh = p / W1, ow = p % W1;
-                const float dz = s_dz[pp][co];
-                if (r0 == 0) bsum += dz;
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    const int kh = r0 + 4 * i;
-                    const int ih = 2 * oh - 2 + kh;
-                    if (kh < 10 && (unsigned)ih < (unsigned)T) {
-                        const float* xr = xb + (size_t)ih * F;
-#pragma unroll
-                        for (int kw = 0; kw < 10; ++kw) {
-                            const int iw = 2 * ow - 2 + kw;
-                            if ((unsigned)iw < (unsigned)F) acc[i][kw] = fmaf(dz, xr[iw], acc[i][kw]);
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    float* pg = part + (size_t)g * C1_PART;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const int kh = r0 + 4 * i;
-        if (kh < 10) {
-#pragma unroll
-            for (int kw = 0; kw < 10; ++kw) pg[co * DL::C1_TAPS + kh * 10 + kw] = acc[i][kw];
-        }
-    }
-    s_b[r0][co] = bsum;
-    __syncthreads();
-    if (tid < 64) pg[DL::C1_W + tid] = s_b[0][tid];
+    constexpr bool MASK = true;
+#include "kws_bwd_conv1_body.h"
+}
+// da = the finished dZ1; a is not read
+__global__ __launch_bounds__(256) void kws_bwd_conv1_dz_kernel(const float* __restrict__ da, const float* __restrict__ a,
+                                                            const float* __restrict__ x, int T, int F, int H1, int W1, int nb,
+                                                            int cpg, float* __restrict__ part) {
+    constexpr bool MASK = false;
+#include "kws_bwd_conv1_body.h"
 }
 
 // out[i] (+)= sum over g = 0 .. G-1 of part[g][i], in the fixed order of reduce_partials (kws_train.h)
@@ -321,6 +197,33 @@ hipError_t reduce(hipStream_t s, const float* part, int G, int n, float* out, bo
 }
 
 }  // namespace
+
+// The launches the train-mode BatchNorm backward (kws_dscnn_bn.hip) shares with this unit; `part` holds G rows of the stage's
+// partials, reduced in fixed order into `out` (bwd_reduce).
+hipError_t bwd_reduce(hipStream_t s, const float* part, int G, int n, float* out) { return reduce(s, part, G, n, out, false); }
+hipError_t launch_bwd_fc(hipStream_t s, const float* y4, const float* dl, const float* fc_w, int Q4, int C, int nb, int cpg, int G,
+                         float* dy4, float* part) {
+    hipLaunchKernelGGL(kws_bwd_fc_kernel, dim3(G), dim3(256), 0, s, y4, dl, fc_w, Q4, C, nb, cpg, dy4, part);
+    return hipGetLastError();
+}
+hipError_t launch_bwd_pointwise_dz(hipStream_t s, const float* dz, const float* xdw, const float* w, int H, int W, int nb, int cpg, int G,
+                                   float* dxdw, float* part) {
+    const int Q = (H + 2) * (W + 2);
+    hipLaunchKernelGGL(kws_bwd_pointwise_dz_kernel, dim3(G), dim3(256), 0, s, dz, (long)CH * Q, Q, 1, (const float*)nullptr, xdw, w, H, W, nb, cpg,
+                       dxdw, part);
+    return hipGetLastError();
+}
+hipError_t launch_bwd_depthwise(hipStream_t s, const float* dxdw, const float* xin, const float* w, int H, int W, int nb, int cpg, int G,
+                                float* dxin, float* part) {
+    hipLaunchKernelGGL(kws_bwd_depthwise_kernel, dim3(CH / 4, G), dim3(256), 0, s, dxdw, xin, w, H, W, nb, cpg, dxin, part);
+    return hipGetLastError();
+}
+hipError_t launch_bwd_conv1_dz(hipStream_t s, const float* dz, const float* x, int T, int F, int H1, int W1, int nb, int cpg, int G,
+                               float* part) {
+    hipLaunchKernelGGL(kws_bwd_conv1_dz_kernel, dim3(G), dim3(256), 0, s, dz, (const float*)nullptr, x, T, F, H1, W1, nb, cpg, part);
+    return hipGetLastError();
+}
+
 }  // namespace kws
 
 using namespace kws;

@@ -327,11 +327,18 @@ hipError_t launch_cnntrad_conv(hipStream_t s, const CnnTradWeights& w, const CtS
 hipError_t launch_dsblock(hipStream_t s, const float* d_x, int B, int C_in, int H, int W, const float* d_dw_w, const float* d_dw_b,
                           const float* d_pw_w, const float* d_pw_b, int C_out, int k, int stride, int pad, float* d_ws,
                           float* d_out);
+// Its two kernels on their own: the depthwise convolution + bias -> [B][C_in][Ho][Wo], and the pointwise one on such a map ->
+// [B][C_out][Ho + 2 pad][Wo + 2 pad] with ReLU, or (relu_out = false) as the pre-activation whose ring is the bias.
+hipError_t launch_dsblock_depthwise(hipStream_t s, const float* d_x, int B, int C_in, int H, int W, const float* d_dw_w,
+                                    const float* d_dw_b, int k, int stride, int pad, float* d_out);
+hipError_t launch_dsblock_pointwise(hipStream_t s, const float* d_dw, int B, int C_in, int Ho, int Wo, const float* d_pw_w,
+                                    const float* d_pw_b, int C_out, int pad, float* d_out, bool relu_out);
 
 // DS-CNN on a feature map other than 99 x 10 (composed, HBM-resident): conv1 for any [B][C_in][T][F] (d_wt: [ci][tap][co]) and
 // global average pool + fc + argmax over [B][64][HW].
+// relu_out = false (the train-mode BatchNorm path, kws_dscnn_bn.hip): the pre-activation conv1 + bias.
 hipError_t launch_conv1_any(hipStream_t s, const float* d_x, int B, int C_in, int T, int F, const float* d_wt, const float* d_bias,
-                            float* d_out);
+                            float* d_out, bool relu_out = true);
 hipError_t launch_pool_fc(hipStream_t s, const float* d_x, int B, int HW, const float* d_fc_w, const float* d_fc_b, int C,
                           float* d_logits, int32_t* d_label);
 // The composed path's geometry on a T x F map: conv1's output is H1 x W1; block k (0-based) takes H(k) x W(k) = P(k) positions,

@@ -81,6 +81,20 @@ struct DscnnLayout {
     __host__ __device__ size_t block(int k) const { return b_blk + (size_t)k * BLK; }  // blob offset of block k (0-based)
 };
 
+// DepthwiseSeparableConvBN's parameters() as one blob (kws_dscnn_bn.hip): the plain model's 20 tensors (DscnnLayout, one input
+// channel), then weight [64] | bias [64] of bn_conv1, bn_dw.0 .. 3, bn_pw.0 .. 3.  A BatchNorm LAYER is counted in data-flow order,
+// as d_stats is: 0 = conv1, 2k + 1 = the depthwise and 2k + 2 = the pointwise convolution of block k (0-based).
+struct DscnnBnLayout {
+    static constexpr int N_BN = 9, CO = DscnnLayout::CO, BN_FLOATS = N_BN * 2 * CO;
+    DscnnLayout plain;
+    size_t b_bn, n_floats;
+    __host__ __device__ explicit DscnnBnLayout(int num_classes) : plain(num_classes, 1), b_bn(plain.n_floats), n_floats(plain.n_floats + BN_FLOATS) {}
+    // the layer's module in blob order: bn_conv1, the four bn_dw, the four bn_pw
+    __host__ __device__ static int module_of(int layer) { return layer == 0 ? 0 : (layer & 1) ? 1 + (layer - 1) / 2 : 5 + (layer - 2) / 2; }
+    __host__ __device__ size_t gamma(int layer) const { return b_bn + (size_t)module_of(layer) * 2 * CO; }
+    __host__ __device__ size_t beta(int layer) const { return gamma(layer) + CO; }
+};
+
 // The layers' power-of-two weight scales of the f16-pair images (pow2_scale_of_max of max|w|): conv1, the four pointwise layers.
 struct DscnnScales {
     float c1, pw[4];

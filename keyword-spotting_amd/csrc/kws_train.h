@@ -1,6 +1,7 @@
-// The scaffold the two training back ends share (kws_dscnn_bwd.hip, kws_cnntrad_bwd.hip): the conventions of their long sums,
-// the clip-group plan behind the deterministic reduction and its reduce body, the f32 MFMA helpers, the workspace carver and the
-// argument check of the backward entries.  The state_dict layouts come from kws_pack.h.
+// The scaffold the training back ends share (kws_dscnn_bwd.hip, kws_cnntrad_bwd.hip, kws_dscnn_bn.hip): the conventions of their
+// long sums, the clip-group plan behind the deterministic reduction and its reduce body, the f32 MFMA helpers, the DS-CNN's
+// backward launches as the BatchNorm path calls them, the workspace carver and the argument check of the backward entries.  The
+// state_dict layouts come from kws_pack.h.
 #pragma once
 #include <algorithm>
 #include <string>
@@ -63,6 +64,24 @@ __device__ __forceinline__ void reduce_partials(const float* __restrict__ part, 
         out[i] = accumulate ? out[i] + s : s;
     }
 }
+
+// ---- the DS-CNN's backward launches (kws_dscnn_bwd.hip), shared with the train-mode BatchNorm path (kws_dscnn_bn.hip) -----------
+constexpr int BWD_MAX_GROUPS = 1024;                                   // partial rows per stage and chunk
+constexpr int PW_PART = DscnnLayout::PW_W + DscnnLayout::CO;           // pointwise.weight [co][ci] | pointwise.bias
+constexpr int DW_PART = DscnnLayout::DW_W + DscnnLayout::CO;           // depthwise.weight [c][3][3] | depthwise.bias
+constexpr int C1_PART = DscnnLayout::C1_W + DscnnLayout::CO;           // conv1.weight [co][10][10] | conv1.bias
+constexpr int fc_part(int C) { return C * DscnnLayout::CO + C; }       // fc.weight [C][64] | fc.bias
+// Each writes G = clip_groups(nb, BWD_MAX_GROUPS).G partial rows to `part`; bwd_reduce sums them in fixed order into `out`.
+// The *_dz launches take a finished dloss/d(pre-activation) where the plain model's kernels mask dloss/d(output) by output > 0.
+hipError_t bwd_reduce(hipStream_t s, const float* part, int G, int n, float* out);
+hipError_t launch_bwd_fc(hipStream_t s, const float* y4, const float* dl, const float* fc_w, int Q4, int C, int nb, int cpg, int G,
+                         float* dy4, float* part);
+hipError_t launch_bwd_pointwise_dz(hipStream_t s, const float* dz, const float* xdw, const float* w, int H, int W, int nb, int cpg, int G,
+                                   float* dxdw, float* part);
+hipError_t launch_bwd_depthwise(hipStream_t s, const float* dxdw, const float* xin, const float* w, int H, int W, int nb, int cpg, int G,
+                                float* dxin, float* part);
+hipError_t launch_bwd_conv1_dz(hipStream_t s, const float* dz, const float* x, int T, int F, int H1, int W1, int nb, int cpg, int G,
+                               float* part);
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
 // Hands out consecutive float ranges of a workspace for `clips` clips.  Run the same carving lines twice: without a base they

@@ -63,6 +63,12 @@ SIGNATURES = {
     "kws_forward_map_debug_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, _f32p]),
     "kws_infer_i16": (C.c_int, [_c_ctx, _i16p, C.c_int, _f32p, _i32p]),
     "kws_dscnn_backward_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _f32p]),
+    "kws_dscnn_bn_train_forward_f32": (C.c_int, [_c_ctx, _f32p, C.c_size_t, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, C.c_float, _f32p, _i32p,
+                                                 _f32p]),
+    "kws_dscnn_bn_backward_f32": (C.c_int, [_c_ctx, _f32p, C.c_size_t, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, C.c_float, _f32p, _f32p]),
+    "kws_dscnn_bn_train_debug_f32": (C.c_int, [_c_ctx, _f32p, C.c_size_t, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, C.c_float, _f32p, _i32p,
+                                               _f32p, _f32p]),
+    "kws_host_dscnn_bn_max_batch": (C.c_int, [C.c_int, C.c_int]),
     "kws_dsblock_forward_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int,
                                           C.c_int, C.c_int, _f32p]),
     "kws_infer_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, _f32p, _i32p]),
@@ -353,6 +359,25 @@ class Context:
         [n_floats] (the kws_load_dscnn blob layout) is overwritten.  Asynchronous on the context's stream."""
         self._check(self._lib.kws_dscnn_backward_f32(self._h, _ptr(feat), int(feat.shape[0]), int(T), int(F), _ptr(dlogits), _ptr(grad)),
                     ModelError)
+
+    def dscnn_bn_train_forward_f32(self, params, num_classes, feat, eps, logits, label=None, stats=None, layers=None):
+        """Train-mode forward of the BatchNorm DS-CNN at the device blob ``params`` (``DepthwiseSeparableConvBN.parameters()`` order;
+        ``kws_dscnn_bn_train_forward_f32``): ``feat`` float32 [B, 1, T, F] -> ``logits``, ``label`` (optional), ``stats`` float32
+        [9, 2, 64] (optional: batch mean and unbiased batch variance per layer).  ``layers`` (diagnostics): the five post-ReLU
+        activations, stage after stage (``kws_dscnn_bn_train_debug_f32``)."""
+        B, _, T, F = (int(v) for v in feat.shape)
+        head = (self._h, _ptr(params), int(params.numel()), int(num_classes), _ptr(feat), B, T, F, float(eps), _ptr(logits), _opt(label))
+        if layers is None:
+            self._check(self._lib.kws_dscnn_bn_train_forward_f32(*head, _opt(stats)), ModelError)
+        else:
+            self._check(self._lib.kws_dscnn_bn_train_debug_f32(*head, _ptr(layers), _opt(stats)), ModelError)
+
+    def dscnn_bn_backward_f32(self, params, num_classes, feat, eps, dlogits, grad):
+        """Gradient of a scalar loss with respect to the 38 tensors of ``params`` (``kws_dscnn_bn_backward_f32``): ``dlogits`` float32
+        [B, num_classes]; ``grad`` float32 [params.numel()] in the blob's layout is overwritten.  Asynchronous on the context's stream."""
+        B, _, T, F = (int(v) for v in feat.shape)
+        self._check(self._lib.kws_dscnn_bn_backward_f32(self._h, _ptr(params), int(params.numel()), int(num_classes), _ptr(feat), B, T, F,
+                                                        float(eps), _ptr(dlogits), _ptr(grad)), ModelError)
 
     def load_cnn_trad(self, blob: np.ndarray, num_classes: int):
         blob = np.ascontiguousarray(blob, dtype=np.float32)
@@ -1126,6 +1151,28 @@ def host_dscnn_units():
     if rc != KWS_OK:
         raise KWSError(f"kws_host_dscnn_units failed ({rc})")
     return words.reshape(-1, 2, 64, 4), base
+
+
+def dscnn_bn_blob_layout(num_classes: int):
+    """The blob of the BatchNorm DS-CNN's training entries as ``[(name, offset, floats)]`` in blob order (the mirror of
+    ``DscnnBnLayout``, csrc/kws_pack.h): ``DepthwiseSeparableConvBN.named_parameters()``."""
+    sizes = [("plain.conv1.weight", 6400), ("plain.conv1.bias", 64)]
+    for k in range(1, 5):
+        sizes += [(f"plain.dsconv{k}.depthwise.weight", 576), (f"plain.dsconv{k}.depthwise.bias", 64),
+                  (f"plain.dsconv{k}.pointwise.weight", 4096), (f"plain.dsconv{k}.pointwise.bias", 64)]
+    sizes += [("plain.fc.weight", 64 * int(num_classes)), ("plain.fc.bias", int(num_classes))]
+    for mod in ["bn_conv1"] + [f"bn_dw.{i}" for i in range(4)] + [f"bn_pw.{i}" for i in range(4)]:
+        sizes += [(f"{mod}.weight", 64), (f"{mod}.bias", 64)]
+    out, off = [], 0
+    for name, n in sizes:
+        out.append((name, off, n))
+        off += n
+    return out
+
+
+def host_dscnn_bn_max_batch(T: int, F: int) -> int:
+    """The largest batch the BatchNorm DS-CNN's training entries take on a ``T x F`` map (``kws_host_dscnn_bn_max_batch``)."""
+    return int(lib().kws_host_dscnn_bn_max_batch(int(T), int(F)))
 
 
 def host_cnn_trad_window_chunk() -> int:

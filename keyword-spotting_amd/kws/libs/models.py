@@ -9,8 +9,8 @@ names, shapes and initialisation, so reference checkpoints (bare ``state_dict`` 
 VALU, pointwise 1x1 and conv1 on the matrix cores.  ``DepthwiseSeparableConv`` also trains: after ``model.train()`` (which
 the reference trainers call every epoch), with grad mode on and a parameter that requires grad, its forward is a
 ``torch.autograd.Function`` (``_NativeTrainFunction``) whose backward is ``kws_dscnn_backward_f32``, so the trainer's ``loss.backward()`` /
-``optimizer.step()`` work unchanged.  ``CnnTradFpool3`` trains the same way (``kws_cnn_trad_backward_f32``); the other models
-are inference only.
+``optimizer.step()`` work unchanged.  ``CnnTradFpool3`` trains the same way (``kws_cnn_trad_backward_f32``), and so does
+``DepthwiseSeparableConvBN`` with batch statistics (``kws_dscnn_bn_train_forward_f32`` / ``kws_dscnn_bn_backward_f32``).
 """
 from __future__ import annotations
 
@@ -143,7 +143,7 @@ class _NativeTrainFunction(torch.autograd.Function):
         if fctx.needs_input_grad[1]:
             raise ModelError(f"{model._name}: the gradient with respect to the input features is not provided "
                              f"({model._backward_entry} computes parameter gradients only); detach the input")
-        ctx = model._context(x.device.index or 0, params)
+        ctx = model._train_context(x.device.index or 0, params)
         x = x.detach().to(torch.float32).contiguous()
         dl = dlogits.detach().to(x.device, torch.float32).contiguous()
         grad = torch.empty(sum(p.numel() for p in params), dtype=torch.float32, device=x.device)
@@ -227,6 +227,10 @@ class _TrainableNative(KeywordSpottingModel):
             self._uploaded = fp
         self._ctx.use_torch_stream()
         return self._ctx
+
+    def _train_context(self, device_index: int, params):
+        """What ``_NativeTrainFunction.backward`` hands to ``_native_backward``: the context holding the saved ``params``."""
+        return self._context(device_index, params)
 
     def _outputs(self, like: torch.Tensor):
         return (torch.empty((like.shape[0], self.num_classes), dtype=torch.float32, device=like.device),
@@ -362,12 +366,29 @@ class DepthwiseSeparableConv(_TrainableNative):
 
 class DepthwiseSeparableConvBN(KeywordSpottingModel):
     """Build-defined model-zoo member (the reference has no BatchNorm): the same DS-CNN
-    with an inference-mode BatchNorm2d after conv1, after every depthwise and after every pointwise convolution
-    (conv -> BN -> ReLU where the plain model has conv -> ReLU).  ``fold()`` folds every BatchNorm into the
-    convolution before it -- w' = w * g / sqrt(var + eps), b' = (b - mean) * g / sqrt(var + eps) + beta -- which
-    yields an ordinary ``DepthwiseSeparableConv`` whose forward is the fused kernel.  The relu(bias) ring of the
-    padded 1x1 convolutions stays exact: a BatchNorm acts per channel, ring included.  Inference only: the fold is
-    detached, so no gradient reaches this model's parameters (training covers the plain ``DepthwiseSeparableConv``)."""
+    with a BatchNorm2d after conv1, after every depthwise and after every pointwise convolution
+    (conv -> BN -> ReLU where the plain model has conv -> ReLU; conv -> BN after a depthwise convolution).
+
+    Inference -- a model never switched with ``train()``, or switched back with ``eval()`` / ``train(False)`` -- runs on the
+    fold: ``fold()`` folds every BatchNorm, at its running statistics, into the convolution before it -- w' = w * g /
+    sqrt(var + eps), b' = (b - mean) * g / sqrt(var + eps) + beta -- which yields an ordinary ``DepthwiseSeparableConv`` whose
+    forward is the fused kernel.  The relu(bias) ring of the padded 1x1 convolutions stays exact: a BatchNorm acts per channel,
+    ring included.  The fold is detached; ``KeywordSpotter`` / ``StreamingSpotter`` take the model through it.
+
+    Training: after an explicit ``model.train()`` (as for ``_TrainableNative``: ``nn.Module.training`` alone, True by default,
+    switches nothing), ``forward`` on a GPU tensor ``[B,1,T,F]`` is the train-mode forward in HIP
+    (``kws_dscnn_bn_train_forward_f32``): every BatchNorm normalises with the statistics of the batch, with or without grad mode,
+    as torch's does, and the ring of a pointwise convolution (equal to its bias) counts in them.  Each such forward updates the
+    nine modules' ``running_mean`` / ``running_var`` (the unbiased batch variance, momentum as ``nn.BatchNorm2d``) and
+    ``num_batches_tracked`` on the device without a host synchronisation; the in-place updates bump the buffers' versions, so the
+    next ``eval()`` forward rebuilds the fold.  Under grad mode with a parameter that requires grad the forward runs through
+    ``_NativeTrainFunction``, whose backward (``kws_dscnn_bn_backward_f32``: recompute, fp32 with float64 batch sums,
+    deterministic) yields all 38 parameter gradients; a frozen parameter simply receives none.  No gradient with respect to the
+    input (``ModelError`` in backward).  The batch is not chunked: ``B`` above ``_native.host_dscnn_bn_max_batch(T, F)`` (4747
+    at 99 x 10) and ``B * H1 * W1 < 2`` raise ``ModelError``, as do ``momentum=None`` and ``track_running_stats=False``."""
+
+    _name = "DepthwiseSeparableConvBN"
+    _backward_entry = "kws_dscnn_bn_backward_f32"
 
     def __init__(self, num_classes: int = 12, eps: float = 1e-5):
         super().__init__(num_classes)
@@ -377,6 +398,8 @@ class DepthwiseSeparableConvBN(KeywordSpottingModel):
         self.bn_pw = nn.ModuleList([nn.BatchNorm2d(64, eps=eps) for _ in range(4)])
         object.__setattr__(self, "_folded", None)  # kept out of nn.Module's child registry: not a parameter holder
         self._folded_key = None
+        self._autograd = False  # set by an explicit train(), cleared by eval() / train(False)
+        self._train_ctx = None  # the context of the training entries (the fold has its own)
 
     @staticmethod
     def _fold(conv: nn.Conv2d, bn: nn.BatchNorm2d):
@@ -414,8 +437,86 @@ class DepthwiseSeparableConvBN(KeywordSpottingModel):
         """Drop the cached fold (needed only after edits through ``.data``, which do not bump ``_version``)."""
         self._folded_key = None
 
+    def train(self, mode: bool = True):
+        """``nn.Module.train``; an explicit ``train()`` also switches ``forward`` from the fold to the train-mode HIP forward (see
+        the class docstring), ``eval()`` / ``train(False)`` switches it back."""
+        super().train(mode)
+        self._autograd = bool(mode)
+        return self
+
+    def bn_layers(self):
+        """The nine BatchNorm modules in data-flow order (the layer order of ``kws_dscnn_bn_train_forward_f32``'s statistics):
+        conv1, then depthwise and pointwise of block 1 .. 4."""
+        return [self.bn_conv1] + [m for i in range(4) for m in (self.bn_dw[i], self.bn_pw[i])]
+
     def forward(self, x: torch.Tensor, return_labels: bool = False):
-        return self.fold().forward(x, return_labels)
+        if not self._autograd:
+            return self.fold().forward(x, return_labels)
+        if not x.is_cuda:
+            raise ModelError(f"{self._name}.forward needs a CUDA/ROCm tensor: the train-mode forward is HIP kernels and has no CPU "
+                             "fallback")
+        if x.dim() != 4 or x.shape[1] != 1:
+            raise ModelError(f"expected input [B,1,T,F], got {tuple(x.shape)}")
+        params = tuple(self.parameters())
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            logits, labels = _NativeTrainFunction.apply(self, x, *params)
+        else:
+            logits, labels = self._forward_native(x)
+        return (logits, labels) if return_labels else logits
+
+    def _eps(self) -> float:
+        layers = self.bn_layers()
+        if any(m.eps != layers[0].eps for m in layers):
+            raise ModelError(f"{self._name}: the nine BatchNorm modules must share one eps")
+        for m in layers:
+            if m.momentum is None or not m.track_running_stats or m.running_mean is None:
+                raise ModelError(f"{self._name}: training needs running statistics with a fixed momentum "
+                                 "(momentum=None and track_running_stats=False are not supported)")
+        return float(layers[0].eps)
+
+    def _train_context(self, device_index: int, params=None):
+        """(context of the training entries on ``device_index``, ``params`` -- default: the current parameters -- as one float32
+        blob on that device in ``parameters()`` order)."""
+        from kws import _native
+
+        if self._train_ctx is None or self._train_ctx.device != device_index:
+            self._train_ctx = _native.Context(device_index, ModelError)
+        self._train_ctx.use_torch_stream()
+        dev = torch.device("cuda", device_index)
+        params = tuple(self.parameters()) if params is None else tuple(params)
+        return self._train_ctx, torch.cat([p.detach().to(dev, torch.float32).reshape(-1) for p in params])
+
+    def _forward_native(self, x: torch.Tensor):
+        """The train-mode forward on ``x`` (checked by the caller) -> (logits, labels), and the update of the running statistics;
+        no autograd graph."""
+        eps = self._eps()
+        ctx, blob = self._train_context(x.device.index or 0)
+        x = x.detach().to(torch.float32).contiguous()
+        logits = torch.empty((x.shape[0], self.num_classes), dtype=torch.float32, device=x.device)
+        labels = torch.empty((x.shape[0],), dtype=torch.int32, device=x.device)
+        stats = torch.empty((9, 2, 64), dtype=torch.float32, device=x.device)
+        ctx.dscnn_bn_train_forward_f32(blob, self.num_classes, x, eps, logits, labels, stats)
+        self._update_running(stats)
+        return logits, labels
+
+    @torch.no_grad()
+    def _update_running(self, stats: torch.Tensor) -> None:
+        """running <- (1 - momentum) * running + momentum * batch for the 18 buffers, num_batches_tracked += 1: one fused launch
+        per distinct momentum (one by default), no host synchronisation."""
+        layers = self.bn_layers()
+        by_momentum = {}
+        for i, m in enumerate(layers):
+            bufs, srcs = by_momentum.setdefault(float(m.momentum), ([], []))
+            for j, buf in enumerate((m.running_mean, m.running_var)):
+                bufs.append(buf)
+                srcs.append(stats[i, j].to(buf.device, buf.dtype))
+        for momentum, (bufs, srcs) in by_momentum.items():
+            torch._foreach_lerp_(bufs, srcs, momentum)
+        torch._foreach_add_([m.num_batches_tracked for m in layers], 1)
+
+    def _native_backward(self, ctx, x, dl, grad):
+        native, blob = ctx
+        native.dscnn_bn_backward_f32(blob, self.num_classes, x, self._eps(), dl, grad)
 
     def infer_pcm16(self, wav: torch.Tensor):
         return self.fold().infer_pcm16(wav)

@@ -8,6 +8,11 @@ zero_grad -> forward -> CrossEntropyLoss -> loss.backward() -> Adam(lr=1e-3) (tr
     python tools/bench_train.py --backward-only --batches 1028     # only the kws_dscnn_backward_f32 loop (for rocprofv3)
     python tools/bench_train.py --model cnn-trad-fpool3 [--batches 1024,4096]   # the same step on CnnTradFpool3
                                    (oracle.cnn_trad.forward for torch eager; kws_cnn_trad_backward_f32; --backward-only as above)
+    python tools/bench_train.py --model ds-cnn-bn [--batches 1028,4096] --out profiles/train_bn_bench.json
+                                   the same step on DepthwiseSeparableConvBN in train mode (kws_dscnn_bn_train_forward_f32 +
+                                   kws_dscnn_bn_backward_f32, batch statistics, running statistics updated) against torch eager on an
+                                   unfolded nn definition of the same model (nn.Conv2d / nn.BatchNorm2d in train mode);
+                                   --backward-only loops kws_dscnn_bn_backward_f32 alone
 
 Prints one JSON line.  Per batch size B:
   hip.step_ms            device-event time of a whole step (median, p10, p90 over --steps steps), clips/s at the median
@@ -300,14 +305,131 @@ def run_cnntrad(B, steps, warmup, dev, backward_only=False):
     }
 
 
+class EagerDscnnBN(torch.nn.Module):
+    """DepthwiseSeparableConvBN unfolded, as plain torch modules: what a user trains in eager mode to obtain a BatchNorm checkpoint."""
+
+    def __init__(self, num_classes=C, eps=1e-5):
+        super().__init__()
+        nn = torch.nn
+        self.conv1, self.bn_conv1 = nn.Conv2d(1, 64, 10, stride=2, padding=2), nn.BatchNorm2d(64, eps=eps)
+        self.dw = nn.ModuleList([nn.Conv2d(64, 64, 3, padding=1, groups=64) for _ in range(4)])
+        self.pw = nn.ModuleList([nn.Conv2d(64, 64, 1, padding=1) for _ in range(4)])
+        self.bn_dw = nn.ModuleList([nn.BatchNorm2d(64, eps=eps) for _ in range(4)])
+        self.bn_pw = nn.ModuleList([nn.BatchNorm2d(64, eps=eps) for _ in range(4)])
+        self.fc = nn.Linear(64, num_classes)
+
+    def forward(self, x):
+        h = torch.relu(self.bn_conv1(self.conv1(x)))
+        for k in range(4):
+            h = self.bn_dw[k](self.dw[k](h))
+            h = torch.relu(self.bn_pw[k](self.pw[k](h)))
+        return self.fc(h.mean(dim=(2, 3)))
+
+    def load_from(self, model):
+        """The parameters of a DepthwiseSeparableConvBN, tensor by tensor."""
+        with torch.no_grad():
+            pairs = [(self.conv1, model.plain.conv1), (self.fc, model.plain.fc), (self.bn_conv1, model.bn_conv1)]
+            for k in range(4):
+                blk = getattr(model.plain, f"dsconv{k + 1}")
+                pairs += [(self.dw[k], blk.depthwise), (self.pw[k], blk.pointwise), (self.bn_dw[k], model.bn_dw[k]), (self.bn_pw[k], model.bn_pw[k])]
+            for mine, theirs in pairs:
+                mine.weight.copy_(theirs.weight)
+                mine.bias.copy_(theirs.bias)
+        return self
+
+
+def run_bn(B, steps, warmup, dev, backward_only=False):
+    from kws.libs.models import DepthwiseSeparableConvBN
+
+    torch.manual_seed(0)
+    model = DepthwiseSeparableConvBN().to(dev).train()
+    with torch.no_grad():  # off the default init's degenerate point (every beta and bias zero puts the rings on the ReLU threshold)
+        for name, p in model.named_parameters():
+            if name.startswith("bn_") or name.endswith("bias"):
+                p.add_(torch.randn_like(p) * 0.1)
+    eager = EagerDscnnBN().load_from(model).to(dev).train()
+    gen = torch.Generator().manual_seed(B)
+    x = torch.randn(B, 1, T_IN, F_IN, generator=gen).to(dev)
+    y = torch.randint(0, C, (B,), generator=gen).to(dev)
+    crit = torch.nn.CrossEntropyLoss()
+    opt = torch.optim.Adam(model.parameters(), lr=1e-3)
+    opt_t = torch.optim.Adam(eager.parameters(), lr=1e-3)
+
+    def ev():
+        return torch.cuda.Event(enable_timing=True)
+
+    def calls(n):
+        ctx, blob = model._train_context(dev.index or 0)
+        evs = []
+        for _ in range(n):
+            a, b = ev(), ev()
+            a.record()
+            ctx.dscnn_bn_backward_f32(blob, C, x, model._eps(), dl, grad)
+            b.record()
+            evs.append((a, b))
+        torch.cuda.synchronize()
+        return [a.elapsed_time(b) for a, b in evs]
+
+    dl = torch.randn(B, C, generator=gen).to(dev) / B
+    grad = torch.empty(sum(p.numel() for p in model.parameters()), dtype=torch.float32, device=dev)
+    if backward_only:
+        calls(warmup)
+        return {"B": B, "backward_call_ms": stats(calls(steps))}
+
+    def hip_step():
+        e = [ev() for _ in range(4)]
+        e[0].record()
+        opt.zero_grad()
+        logits = model(x)
+        e[1].record()
+        crit(logits, y).backward()
+        e[2].record()
+        opt.step()
+        e[3].record()
+        return e
+
+    def torch_step():
+        e = [ev(), ev()]
+        e[0].record()
+        opt_t.zero_grad()
+        crit(eager(x), y).backward()
+        opt_t.step()
+        e[1].record()
+        return e
+
+    for _ in range(warmup):
+        hip_step()
+        torch_step()
+    torch.cuda.synchronize()
+    hip_ev, t_ev = [], []
+    for _ in range(steps):  # alternated: both see the same clocks and neighbours
+        hip_ev.append(hip_step())
+        t_ev.append(torch_step())
+    torch.cuda.synchronize()
+    step = [e[0].elapsed_time(e[3]) for e in hip_ev]
+    split = {name: stats([e[i].elapsed_time(e[i + 1]) for e in hip_ev])["median"]
+             for i, name in enumerate(["forward", "backward", "optimizer"])}
+    t_step = [e[0].elapsed_time(e[1]) for e in t_ev]
+    calls(warmup)
+    call_ms = stats(calls(steps))
+    hs, ts = stats(step), stats(t_step)
+    return {
+        "B": B,
+        "hip": {"step_ms": hs, "clips_per_s": round(B / hs["median"] * 1e3), "split_ms": split},
+        "backward_call_ms": call_ms,
+        "torch_eager": {"step_ms": ts, "clips_per_s": round(B / ts["median"] * 1e3)},
+        "speedup": round(ts["median"] / hs["median"], 3),
+    }
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--model", default="ds-cnn", choices=["ds-cnn", "cnn-trad-fpool3"])
+    ap.add_argument("--model", default="ds-cnn", choices=["ds-cnn", "cnn-trad-fpool3", "ds-cnn-bn"])
     ap.add_argument("--batches", default=None, help="comma-separated batch sizes (default 1028,4096; cnn-trad-fpool3: 1024,4096)")
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
-    ap.add_argument("--backward-only", action="store_true", help="time only the kws_dscnn_backward_f32 call")
+    ap.add_argument("--backward-only", action="store_true", help="time only the model's backward entry")
     args = ap.parse_args(argv)
     if args.steps < 50:
         ap.error("--steps must be at least 50")
@@ -316,10 +438,10 @@ def main(argv=None):
     dev = torch.device("cuda", 0)
     cnntrad = args.model == "cnn-trad-fpool3"
     batches = args.batches or ("1024,4096" if cnntrad else "1028,4096")
-    fn = run_cnntrad if cnntrad else run
+    fn = run_cnntrad if cnntrad else run_bn if args.model == "ds-cnn-bn" else run
     res = {"tool": "bench_train", "device": torch.cuda.get_device_name(0), "features": [1, T_IN, F_IN], "num_classes": C,
            "steps": args.steps, "warmup": args.warmup, "f32_matrix_peak_tf": F32_MATRIX_PEAK_TF}
-    if cnntrad:
+    if args.model != "ds-cnn":
         res = {"tool": "bench_train", "model": args.model, **{k: v for k, v in res.items() if k != "tool"}}
     res["results"] = [fn(int(b), args.steps, args.warmup, dev, args.backward_only) for b in batches.split(",")]
     line = json.dumps(res)
