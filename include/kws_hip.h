@@ -983,6 +983,36 @@ int kws_stream_resample_i16(kws_ctx* ctx, const int16_t* d_in, int n_in, int16_t
 int kws_stream_push_rate_i16(kws_ctx* ctx, const int16_t* d_in, int n_in, float* d_logits, int32_t* d_label);
 int kws_stream_push_host_rate_i16(kws_ctx* ctx, const int16_t* h_in, int n_in, const float** h_logits, const int32_t** h_label);
 
+/* ---- resetting single streams of a live set (build-defined: the reference handles ONE microphone, one capture at a time --
+ * kws/inference/inference_local.py:114-192 opens the device, records until the VAD closes, classifies and starts over; it has no
+ * set of streams whose members come and go) -----------------------------------------------------------------------------------
+ * streams: host int32 [n], indices into the open set; duplicates are allowed.  Enqueued on the context's stream between two
+ * pushes: no host synchronisation, no device allocation after the set's first reset, and the indices travel inside the launch
+ * (a 1024-bit mask per 1024 streams), so the array may be reused as soon as the call returns.
+ * From the next push on, each named stream behaves AS IF IT HAD RECEIVED DIGITAL SILENCE (all-zero samples) EVER SINCE
+ * kws_stream_open; what is armed on the set starts over for it.  Every other stream is untouched, bit for bit, and the set's
+ * counters run on (hops, frames walked, decisions made, samples appended): records stay in set coordinates, and a stream's own
+ * time is the set's minus the hop count at its reset.  Per layer, h0 = pushes so far, K = ceil(frame_len / frame_step):
+ *   PCM ring, both halves of the streaming resampler's history: zeros (the resampler's position and phase are the set's and stay).
+ *   feature ring: the rows of the frames a silent stream would hold -- frames 0 .. h0 - K, frame f in row f mod num_frames -- get the
+ *     row the streaming frame kernel writes for an all-zero frame (taken from that kernel, once per open set, on a scratch set
+ *     of one stream; kws_frontend_stats does not move); every other row is zero.  The frames that straddle the reset then come
+ *     out of the unchanged frame code as "silence, then the new audio".
+ *   kws_stream_utt_*: an utterance open on the stream closes at the newest walked frame with reason 2, as kws_stream_utt_flush
+ *     closes it, and is queued (one more step of that queue for kws_stream_utt_poll); flags, window counts and the open frame are
+ *     cleared and the previous close is set to hops appended - 1, so no later utterance of the stream starts before the first
+ *     sample pushed after the reset.  The history ring stays: utterances closed before the reset remain cuttable.
+ *   kws_stream_detect_*: the stream's causal mean runs over the decisions since the reset only (at most smooth_window of them,
+ *     same order of addition), its refractory wait is cleared; first_hop stays a gate of the set; queued events stay.
+ *   kws_stream_vad_f32: the stream's flags and window counts are cleared.
+ *   kws_stream_smooth_f32: while its history is live the reset is REFUSED with KWS_EUNSUPPORTED before anything changes -- that
+ *     smoother keeps a running sum and one hop count for all streams; use kws_stream_detect_*.
+ * Nothing to reset: the zero-copy result arrays, the time-tile partial sums, the refinement counters, a captured push graph (the
+ * reset is a launch outside it; the next replay works on the reset rings).
+ * n == 0: KWS_OK, nothing is launched.  KWS_EINVAL, nothing changed: an index outside [0, n_streams), streams == NULL with
+ * n > 0, n < 0.  KWS_ESTATE: no open set. */
+int kws_stream_reset(kws_ctx* ctx, const int32_t* streams, int n);
+
 /* ---- evaluation statistics on the device (build-defined: the reference computes them on the host, with a
  * round trip per batch -- running_loss += loss.item(), torch.max(outputs, 1), (predicted == labels).sum().item() in
  * train.py:51-54,79-98 and kws/libs/training.py:300-303,347-393 -- and test.py:27-58 derives the per-class report, the

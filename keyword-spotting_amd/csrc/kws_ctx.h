@@ -1,6 +1,6 @@
 // The context behind the C ABI (include/kws_hip.h), the error plumbing and the device-memory helpers shared by the translation
 // units that implement it (kws_api.hip, kws_stream.hip, kws_cnntrad.hip, kws_frontend.hip, kws_weights.hip, kws_ingest.hip,
-// kws_scan.hip, kws_score.hip, kws_ragged.hip, kws_decide.hip, kws_eval.hip, kws_resample.hip, kws_live.hip, kws_live_detect.hip, kws_*_bwd.hip),
+// kws_scan.hip, kws_score.hip, kws_ragged.hip, kws_decide.hip, kws_eval.hip, kws_resample.hip, kws_live.hip, kws_live_detect.hip, kws_stream_reset.hip, kws_*_bwd.hip),
 // the table of what the host flows need of a model, and the event bracket of a timed launch.
 // Memory: every device or pinned allocation of the context is a DeviceBuffer / PinnedBuffer member (kws_buffer.h) of kws_ctx or of
 // a sub-state the context points to, and is freed by that member's destructor.  The *_free functions below reset what is not
@@ -32,6 +32,23 @@ void stream_detect_free(kws_ctx* c);
 // the decision step behind a push, from that push's logits; nothing when unarmed.  fn: the push entry, named in the errors;
 // model_classes: the class count of the model that made the logits (the DS-CNN's or cnn-trad-fpool3's)
 int stream_detect_pushed(kws_ctx* c, const float* d_logits, const char* fn, int model_classes);
+// A per-stream reset (kws_stream_reset, kws_stream_reset.hip) names its streams BY VALUE: bit s % 64 of word s / 64 of a chunk of
+// 1024 streams travels inside the kernel arguments, so no later call can overtake a copy of the selection.
+constexpr int RESET_CHUNK = 1024;
+struct ResetMask {
+    unsigned long long w[RESET_CHUNK / 64];
+    __host__ __device__ bool has(int s) const { return (w[s >> 6] >> (s & 63)) & 1ull; }
+};
+// What the reset's ring kernel clears of the other units, each handed out by its owner: the streaming resampler's two history
+// halves (kws_resample.hip), the live events' refractory word and epoch with the decision counter the epoch is read from
+// (kws_live_detect.hip; from this call on the set launches the epoch instantiation of its step).  All nullptr when the unit is off.
+struct ResampleResetView { int16_t* hist; long long half; int len; };  // stream s: hist + h * half + s * len, h = 0, 1
+ResampleResetView stream_resample_reset_view(kws_ctx* c);
+struct DetectResetView { long long* next; long long* epoch; const unsigned long long* decisions; };
+DetectResetView stream_detect_reset_view(kws_ctx* c);
+// live utterances: close what is open on the named streams with reason 2 and start their endpointer over -- one more tick of the
+// unit's queue (kws_live.hip); nothing when the context is unarmed
+int stream_utt_reset(kws_ctx* c, const ResetMask& m);
 // What the host flows need of a model.  The recording flows (scan_recordings, kws_scan.hip; scan_ragged_entry, kws_ragged.hip), the
 // fused clip entries (infer_clips, kws_api.hip) and the stream push (stream_push, kws_stream.hip) are each written once and take one
 // of these.  fn names the entry: a refusal starts with it, in that model's words, and is composed on the failing branch only.
@@ -141,6 +158,10 @@ struct kws_ctx {
     DeviceBuffer<unsigned long long> d_vad_bits;
     DeviceBuffer<int> d_vad_counts;
     int vad_on = 0, vad_off = 0;
+    // per-stream reset (kws_stream_reset): the frame kernel's scratch set of ONE stream, made at the set's first reset -- its
+    // feature ring's row 0 is the row of an all-zero frame -- then the hop counter, the PCM ring and the zero hop of that run
+    DeviceBuffer<float> d_reset_scratch;
+    bool reset_row_ready = false;
 
     // evaluation statistics (kws_eval_*, kws_eval.hip): one allocation of 64-bit words -- counts[4], loss_sum (a double),
     // confusion [C][C], hist_pos [C][K], hist_neg [C][K] -- and the per-workgroup float64 loss partials of one update

@@ -147,6 +147,39 @@ __global__ __launch_bounds__(LIVE_MAX_STREAMS) void kws_live_step_kernel(const L
     }
 }
 
+// kws_stream_reset's step: the FLUSH of the streams `m` names alone -- an utterance open on one of them closes at the newest walked
+// frame with reason 2 and is queued, one more tick of the queue --, which then start over: flag ring, window counts and the open
+// frame as kws_stream_utt_open leaves them, prev_close = hops appended - 1, so that ep_span_start keeps a later utterance of the
+// stream from starting before the first sample pushed after the reset.  The history ring stays: what closed before the reset
+// remains cuttable.  A kernel of its own, not a third instantiation of the one above: with the mask folded into that body the
+// compiler scheduled the plain flush differently, and the step and the flush keep the code they had.
+__global__ __launch_bounds__(LIVE_MAX_STREAMS) void kws_live_reset_kernel(const LiveArgs a, const ResetMask m) {
+    const int tid = threadIdx.x;
+    const EqCounts was = eq_counts(a.q);
+    const unsigned long long frames = was.unit[0], appended = was.unit[1];
+    bool closed = false;
+    long long open = 0, start_frame = 0, close_frame = 0;
+    if (tid < a.S && m.has(tid)) {
+        int* cnt = a.counts + 4 * tid;
+        long long* ps = a.pos + 2 * tid;
+        open = ps[0];
+        if (cnt[2]) {  // triggered: at least one frame was walked
+            closed = true;
+            close_frame = (long long)frames - 1;
+            start_frame = ep_span_start(open, a.pre_roll, ps[1]);
+        }
+        ulonglong2* row = reinterpret_cast<ulonglong2*>(a.bits + (size_t)tid * EP_BIT_WORDS);
+#pragma unroll
+        for (int k = 0; k < EP_BIT_WORDS / 2; ++k) row[k] = make_ulonglong2(0ull, 0ull);
+        cnt[0] = cnt[1] = cnt[2] = 0;
+        ps[0] = -1;
+        ps[1] = (long long)appended - 1;
+    }
+    const long long rec[LIVE_REC] = {(long long)tid, start_frame * a.step, close_frame * a.step + a.frame_len, open, close_frame, 2};
+    const int all = eq_emit(a.q, was, closed, rec);
+    eq_publish(a.q, was, all, frames);  // the unit's own counters stand
+}
+
 // kws_cut_i16_kernel (kws_segment.hip) with a ring origin: one workgroup per sequence number, the record read from the device
 // queue (q.ctr[0]: events so far; q.unit()[1]: hops appended).  The span [start, end) of stream r lies in the history ring from
 // start mod H on and crosses the seam at most once (end - start <= H): element i is at p0 + i, minus H from the seam on.  The
@@ -185,12 +218,10 @@ int history_for(int frame_len, int frame_step, int pre_roll, int max_frames, int
     return *out > INT_MAX ? KWS_EINVAL : KWS_OK;
 }
 
-// One launch of the step or flush kernel with the set's state; hop / energy / ctx_hops as LiveArgs describes them.
-template <bool FLUSH>
-int utt_launch(kws_ctx* c, const int16_t* hop, long long hop_stride, const int* ctx_hops, const float* energy) {
-    StreamUtt* u = c->stream_utt;
+// The set's state with a launch's own fields; hop / energy / ctx_hops as LiveArgs describes them.
+LiveArgs utt_args(kws_ctx* c, const int16_t* hop, long long hop_stride, const int* ctx_hops, const float* energy) {
     const FrontendParams& p = c->fp;
-    LiveArgs a = u->a;
+    LiveArgs a = c->stream_utt->a;
     a.hop = hop;
     a.hop_stride = hop_stride;
     a.ctx_hops = ctx_hops;
@@ -204,6 +235,14 @@ int utt_launch(kws_ctx* c, const int16_t* hop, long long hop_stride, const int* 
     // 16-byte copies: whole hops of 8 samples, every stream's hop and ring row on a 16-byte boundary (the ring offset and the
     // ring's write position are multiples of step)
     a.vec = hop && p.frame_step % 8 == 0 && hop_stride % 8 == 0 && reinterpret_cast<uintptr_t>(hop) % 16 == 0;
+    return a;
+}
+
+// One launch of the step or flush kernel.
+template <bool FLUSH>
+int utt_launch(kws_ctx* c, const int16_t* hop, long long hop_stride, const int* ctx_hops, const float* energy) {
+    StreamUtt* u = c->stream_utt;
+    const LiveArgs a = utt_args(c, hop, hop_stride, ctx_hops, energy);
     int threads = (a.S + 63) / 64 * 64;
     if (hop && threads < 256) threads = 256;  // the copy is the workgroup's bulk
     hipLaunchKernelGGL(kws_live_step_kernel<FLUSH>, dim3(1), dim3(threads), 0, c->stream, a);
@@ -223,6 +262,15 @@ void stream_utt_free(kws_ctx* c) {
 int stream_utt_push_check(kws_ctx* c, const char* fn) {
     if (c->stream_utt && c->stream_utt->mode == 2)
         return fail(c, KWS_ESTATE, std::string(fn) + ": this utterance set was stepped by kws_stream_utt_step_i16; a push would let its two counters drift apart");
+    return KWS_OK;
+}
+
+int stream_utt_reset(kws_ctx* c, const ResetMask& m) {
+    StreamUtt* u = c->stream_utt;
+    if (!u) return KWS_OK;
+    hipLaunchKernelGGL(kws_live_reset_kernel, dim3(1), dim3((u->a.S + 63) / 64 * 64), 0, c->stream, utt_args(c, nullptr, 0, nullptr, nullptr), m);
+    HIP_TRY(c, hipGetLastError());
+    eq_enqueued(u->a.q);
     return KWS_OK;
 }
 

@@ -38,6 +38,8 @@ struct StreamDetect {
     DeviceBuffer<float> ring, smoothed;
     DeviceBuffer<int32_t> label;
     DeviceBuffer<long long> next;
+    DeviceBuffer<long long> epoch;  // [S]: decisions made when stream s was last reset (kws_stream_reset); 0 in a fresh set
+    bool was_reset = false;         // a reset was issued on this set: its steps launch the epoch instantiation from then on
     EventQueueMem queue;
 };
 
@@ -52,7 +54,12 @@ namespace {
 // argmax of its row, the threshold and the refractory rule.
 // The streams that fired emit their records and thread 0 publishes the totals as kws_event_queue.h lays down (eq_emit,
 // eq_publish).  A push below first_hop decides nothing and advances nothing but the kernel count.
-__global__ __launch_bounds__(DETECT_MAX_STREAMS) void kws_live_detect_step_kernel(const DetectArgs a) {
+// EPOCH (a set on which kws_stream_reset was called): stream s's mean runs over the last min(W, d - epoch[s] + 1) slots -- the
+// decisions since its reset --, same order of addition, same single division; the term count is then the pair's own, no longer
+// the workgroup's.  The body of two kernels: a set that was never reset launches kws_live_detect_step_kernel, under the name and
+// with the code it had before there was a reset (DESIGN 4.32 holds its listing to that).
+template <bool EPOCH>
+__device__ __forceinline__ void detect_step(const DetectArgs& a, const long long* __restrict__ epoch) {
     const int tid = threadIdx.x;
     const EqCounts was = eq_counts(a.q);
     const unsigned long long d = was.unit[0];
@@ -70,11 +77,17 @@ __global__ __launch_bounds__(DETECT_MAX_STREAMS) void kws_live_detect_step_kerne
         const int slot = (int)(d % (unsigned long long)W);
         if (tid < a.S) softmax_row(a.logits + (size_t)tid * C, C, a.ring + ((size_t)tid * W + slot) * C);
         __syncthreads();
-        const int terms = d + 1 < (unsigned long long)W ? (int)d + 1 : W;
-        const int oldest = slot - terms + 1 + (slot - terms + 1 < 0 ? W : 0);
-        const float count = (float)terms;
+        int terms = d + 1 < (unsigned long long)W ? (int)d + 1 : W;
+        int oldest = slot - terms + 1 + (slot - terms + 1 < 0 ? W : 0);
+        float count = (float)terms;
         for (int i = tid; i < a.S * C; i += (int)blockDim.x) {
             const int s = i / C, c = i - s * C;
+            if constexpr (EPOCH) {
+                const long long since = (long long)d - epoch[s] + 1;  // >= 1: an epoch is a decision count already reached
+                terms = since < (long long)W ? (int)since : W;
+                oldest = slot - terms + 1 + (slot - terms + 1 < 0 ? W : 0);
+                count = (float)terms;
+            }
             const float* row = a.ring + (size_t)s * W * C + c;
             // scan_smooth_window's rule (kws_scan.hip), restated: float32 additions from 0, oldest first, then ONE division
             // The ring's slots from `oldest` to its end, then from slot 0: two linear runs, each taken eight loads at a time so that
@@ -121,6 +134,14 @@ __global__ __launch_bounds__(DETECT_MAX_STREAMS) void kws_live_detect_step_kerne
     if (tid == 0) a.q.unit()[0] = decisions;
 }
 
+__global__ __launch_bounds__(DETECT_MAX_STREAMS) void kws_live_detect_step_kernel(const DetectArgs a) {
+    detect_step<false>(a, nullptr);
+}
+
+__global__ __launch_bounds__(DETECT_MAX_STREAMS) void kws_live_detect_step_epoch_kernel(const DetectArgs a, const long long* __restrict__ epoch) {
+    detect_step<true>(a, epoch);
+}
+
 // One launch of the step kernel with the set's state.  Threads: one per stream at least, and up to one per (stream, class) pair
 // for the sums.
 int detect_launch(kws_ctx* c, const float* d_logits, const int* ctx_hops) {
@@ -130,7 +151,10 @@ int detect_launch(kws_ctx* c, const float* d_logits, const int* ctx_hops) {
     a.ctx_hops = ctx_hops;
     const long long pairs = (long long)a.S * a.C;
     const int threads = pairs >= DETECT_MAX_STREAMS ? DETECT_MAX_STREAMS : (int)((pairs + 63) / 64 * 64);  // >= S rounded up: C >= 1
-    hipLaunchKernelGGL(kws_live_detect_step_kernel, dim3(1), dim3(threads), 0, c->stream, a);
+    if (u->was_reset)
+        hipLaunchKernelGGL(kws_live_detect_step_epoch_kernel, dim3(1), dim3(threads), 0, c->stream, a, (const long long*)u->epoch.get());
+    else
+        hipLaunchKernelGGL(kws_live_detect_step_kernel, dim3(1), dim3(threads), 0, c->stream, a);
     HIP_TRY(c, hipGetLastError());
     eq_enqueued(u->a.q);
     return KWS_OK;
@@ -141,6 +165,15 @@ int detect_launch(kws_ctx* c, const float* d_logits, const int* ctx_hops) {
 void stream_detect_free(kws_ctx* c) {
     delete c->stream_detect;
     c->stream_detect = nullptr;
+}
+
+// kws_stream_reset's side: what its kernel writes for the streams it names (next = 0, epoch = decisions made), and the switch
+// of this set's steps to the epoch instantiation.
+DetectResetView stream_detect_reset_view(kws_ctx* c) {
+    StreamDetect* u = c->stream_detect;
+    if (!u) return {nullptr, nullptr, nullptr};
+    u->was_reset = true;
+    return {u->a.next, u->epoch.get(), u->a.q.unit()};
 }
 
 // The push entries' side (kws_stream.hip): the step behind a push's launches, from that push's logits.
@@ -191,7 +224,7 @@ int kws_stream_detect_open(kws_ctx* c, int C, int smooth_window, int first_keywo
     a.first_hop = first_hop;
     a.threshold = threshold;
     const size_t sm_b = sizeof(float) * S * C, label_b = sizeof(int32_t) * S, next_b = sizeof(long long) * S;
-    if (!(u->ring.alloc(S * (size_t)smooth_window * C) && u->smoothed.alloc(S * C) && u->label.alloc(S) && u->next.alloc(S)))
+    if (!(u->ring.alloc(S * (size_t)smooth_window * C) && u->smoothed.alloc(S * C) && u->label.alloc(S) && u->next.alloc(S) && u->epoch.alloc(S)))
         return fail(c, KWS_ENOMEM, "kws_stream_detect_open: allocation failed");
     a.ring = u->ring.get();
     a.smoothed = u->smoothed.get();
@@ -203,6 +236,7 @@ int kws_stream_detect_open(kws_ctx* c, int C, int smooth_window, int first_keywo
         hipError_t e = hipMemsetAsync(a.smoothed, 0, sm_b, c->stream);
         if (e == hipSuccess) e = hipMemsetAsync(a.label, 0, label_b, c->stream);
         if (e == hipSuccess) e = hipMemsetAsync(a.next, 0, next_b, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(u->epoch.get(), 0, next_b, c->stream);
         if (e != hipSuccess) rc = fail_hip(c, e, "kws_stream_detect_open: hipMemsetAsync");
     }
     if (rc) {  // the clears enqueued so far finish before u's memory goes

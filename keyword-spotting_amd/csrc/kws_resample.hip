@@ -540,6 +540,15 @@ int stream_push_rate_check(kws_ctx* c, const void* in, int n_in, const std::stri
 
 }  // namespace
 
+// kws_stream_reset's side: both halves of a stream's history are cleared, whichever the next push reads.  The set's position and
+// phase are shared by its streams and stay.  Nothing when there is no resampler, when it keeps no history (equal rates), or when
+// it was opened for another stream count (kws_stream_push_rate_i16 refuses that pairing anyway).
+ResampleResetView stream_resample_reset_view(kws_ctx* c) {
+    StreamResample* st = c->stream_resample;
+    if (!st || !st->d_hist || st->n_streams != c->n_streams) return {nullptr, 0, 0};
+    return {st->d_hist.get(), (long long)st->n_streams * st->hist, st->hist};
+}
+
 void stream_resample_free(kws_ctx* c) {
     delete c->stream_resample;
     c->stream_resample = nullptr;

@@ -33,6 +33,8 @@ void stream_free(kws_ctx* c) {
     c->d_hops.reset();
     c->d_cl_part.reset();
     c->d_cl_count.reset();
+    c->d_reset_scratch.reset();
+    c->reset_row_ready = false;
     c->n_streams = 0;
 }
 

@@ -81,6 +81,7 @@ SIGNATURES = {
     "kws_forward_debug_f32": (C.c_int, [_c_ctx, _f32p, C.c_int, _f32p, _i32p, _f32p, C.c_int]),
     "kws_stream_open": (C.c_int, [_c_ctx, C.c_int]),
     "kws_stream_close": (C.c_int, [_c_ctx]),
+    "kws_stream_reset": (C.c_int, [_c_ctx, C.c_void_p, C.c_int]),
     "kws_stream_cluster": (C.c_int, [_c_ctx, C.c_int]),
     "kws_stream_host_results": (C.c_int, [_c_ctx, C.c_int]),
     "kws_stream_wait_host": (C.c_int, [_c_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
@@ -869,6 +870,16 @@ class Context:
 
     def stream_close(self):
         self._check(self._lib.kws_stream_close(self._h))
+
+    def stream_reset(self, streams):
+        """``kws_stream_reset``: from the next push on the named streams (an int or a sequence of indices, host) behave as if they
+        had received silence ever since ``stream_open``; what is armed on the set starts over for them, every other stream is
+        untouched.  Enqueued on the context's stream; the indices travel inside the launch."""
+        idx = np.ascontiguousarray(np.atleast_1d(np.asarray(streams, dtype=np.int64)).ravel())
+        if idx.size and (idx.min() < -2**31 or idx.max() >= 2**31):
+            raise ModelError("stream_reset: a stream index does not fit int32")
+        idx = idx.astype(np.int32)
+        self._check(self._lib.kws_stream_reset(self._h, idx.ctypes.data if idx.size else None, int(idx.size)), ModelError)
 
     def stream_push_i16(self, hop, logits=None, label=None, use_graph=False):
         self._check(

@@ -921,7 +921,14 @@ class StreamingSpotter:
     events; ``pop_events()`` returns them, ``smoothed()`` reads the newest decision's posteriors.  ``push`` keeps its signature,
     its results (raw logits) and its zero-copy path; at most 1024 streams.  May be combined with ``utterances``.
 
-    Attributes: ``hop`` -- samples per hop at ``config.sample_rate``; ``hop_in`` -- samples ``push`` takes per stream (``hop``
+    ``reset(streams)`` hands single slots of the set to new callers while the others run on (``kws_stream_reset``): from the next
+    push on a reset stream behaves as if it had heard silence ever since the spotter was created -- its rings, its resampler
+    history, its endpointer and its posterior window start over, an utterance open on it closes with ``"end_of_recording"`` --
+    and every other stream keeps its bits.  Times and hop numbers of ``Utterance`` and ``KeywordEvent`` stay in set coordinates;
+    ``stream_origin`` turns them into a stream's own.  Not with ``smooth_window`` > 0 (one hop count for all streams): use ``detect``.
+
+    Attributes: ``stream_origin`` -- ``np.int64[S]``, the hop count at each stream's last ``reset`` (zeros at creation);
+    ``hop`` -- samples per hop at ``config.sample_rate``; ``hop_in`` -- samples ``push`` takes per stream (``hop``
     without ``input_rate``); ``delay_samples`` -- the resampler's delay in samples at ``config.sample_rate`` (10 = 0.625 ms for
     every rate above 16 kHz, 20 for 8 kHz, 0 without ``input_rate``): what the streams hear lags the input by that much.
 
@@ -975,6 +982,8 @@ class StreamingSpotter:
             if self._resample and not self.model._stream_zero_copy else None
         self._logits = torch.zeros((self.n_streams, self.model.num_classes), dtype=torch.float32, device=self.device)
         self._labels = torch.zeros((self.n_streams,), dtype=torch.int32, device=self.device)
+        self._pushes = 0  # hops pushed so far: the origin the next reset records
+        self.stream_origin = np.zeros(self.n_streams, dtype=np.int64)
         # posterior smoothing: softmax of every hop's logits averaged over the last
         # `smooth_window` hops per stream on the device (kws_stream_smooth_f32); 0 = raw logits / argmax
         self.smooth_window = int(smooth_window)
@@ -1049,6 +1058,7 @@ class StreamingSpotter:
                 lg, lb = self._ctx.stream_push_host_rate_i16(h, self.n_streams)
             else:
                 lg, lb = self._ctx.stream_push_host_i16(h, self.n_streams)
+            self._pushes += 1
             return lb.copy(), lg.copy()
         x = samples if isinstance(samples, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(samples, dtype=np.int16))
         if tuple(x.shape) != (self.n_streams, self.hop_in) or x.dtype != torch.int16:
@@ -1063,6 +1073,7 @@ class StreamingSpotter:
             self._ctx.stream_push_rate_i16(self._hop_buf, self._logits, self._labels)
         else:
             self.model._native_stream_push(self._ctx, self._hop_buf, self._logits, self._labels, self.use_graph)
+        self._pushes += 1
         if self._host:
             lg, lb = self._ctx.stream_wait_host(self.n_streams)
             return lb.copy(), lg.copy()
@@ -1076,6 +1087,28 @@ class StreamingSpotter:
         self._ctx.sync()
         self._fetch_vad()
         return self._labels.cpu().numpy(), self._logits.cpu().numpy()
+
+    def reset(self, streams) -> int:
+        """Start ``streams`` (an index or a sequence of indices; duplicates are fine) over between two pushes, in one call of
+        ``kws_stream_reset``: nothing waits for the device and every other stream is untouched.  Returns the number of hops pushed
+        so far, the reset's origin, and records it in ``stream_origin`` for the named streams.  The set's clock runs on, so for
+        stream ``s`` a ``KeywordEvent.hop`` is hop ``hop - stream_origin[s]`` of the stream's own audio, and an ``Utterance`` or
+        ``KeywordEvent`` time ``t`` (seconds) is ``t - stream_origin[s] * hop / config.sample_rate`` seconds after the stream's
+        first sample.  An utterance open on a reset stream is returned by the next ``pop_utterances`` with reason
+        ``"end_of_recording"``; events already queued stay.  With ``smooth_window`` > 0 the device refuses and this raises
+        ``ModelError``."""
+        idx = np.atleast_1d(np.asarray(streams))
+        if idx.ndim != 1 or (idx.size and not np.issubdtype(idx.dtype, np.integer)):
+            raise ModelError("reset expects a stream index or a sequence of stream indices")
+        if idx.size and (idx.min() < 0 or idx.max() >= self.n_streams):
+            raise ModelError(f"reset: stream indices must be in [0, {self.n_streams})")
+        idx = idx.astype(np.int64)
+        if self.smooth_window > 0 and self._pushes == 0:  # the device refuses once the smoother's history is live: the same answer before it
+            raise ModelError("kws_stream_reset: kws_stream_smooth_f32 (smooth_window > 0) keeps a running sum and one hop count for all "
+                             "streams, which no single stream can leave; smooth with detect=DetectConfig(...) on spotters that reset streams")
+        self._ctx.stream_reset(idx)
+        self.stream_origin[idx] = self._pushes
+        return self._pushes
 
     def _fetch_vad(self):
         if self._vad is not None:
