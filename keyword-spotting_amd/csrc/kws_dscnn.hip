@@ -203,7 +203,9 @@ __device__ __forceinline__ void pool_fc_wave(const DscnnWeights& w, const float*
 // g + grid, ... and overlaps consecutive ones.  Wavefronts 0-3, which finish block 4 first, stage the next clip's features
 // (OFF_FEAT_P) while 4-7 finish their units; one barrier closes both.  The pool + fc + argmax of the finished clip then runs
 // on wavefront NW - 1 beside the next clip's conv1, in which it has no unit.  Same units, orders and sums as one clip per
-// workgroup: the results are bit-identical.
+// workgroup: the results are bit-identical.  Its block phases run under a per-block wavefront-priority schedule (s_setprio at
+// unit boundaries, kws_dscnn_stages.h "Wavefront priority"), which moves issue slots between the two wavefronts of a SIMD
+// and nothing else.
 // SCAN (kws_scan_i16, launch_dscnn_scan): "clip" i is a window of a long recording's frame array -- only the address its
 // features are fetched from changes (clip_features); logits and labels stay indexed by i.
 // The parameter list is mirrored by FwdKernelArgs / FwdKernelFn (the persistent kernels read arguments from the segment).
@@ -498,7 +500,7 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
         pc.s_dwb = pow2f(ky[2]);
         pc.s_pwb = pow2f(sg[2]);
     }
-    block_phase<1, MODE, CLUSTER, UT>(w1, lds, tid, wa, ud, nullptr, rg1, pc);
+    block_phase<1, MODE, CLUSTER, UT, PERSIST>(w1, lds, tid, wa, ud, nullptr, rg1, pc);
     stamp();  // 4: block 1 units of wave 0 done
     const DscnnWeights w2 = weights_now();
     __syncthreads();  // (the K-split leftover tile was combined ahead of it: leftover_arrive)
@@ -520,7 +522,7 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
         pc.s_dwb = pow2f(ky[3]);
         pc.s_pwb = pow2f(sg[3]);
     }
-    block_phase<2, MODE, CLUSTER, UT>(w2, lds, tid, wa, ud, nullptr, rg2, pc);
+    block_phase<2, MODE, CLUSTER, UT, PERSIST>(w2, lds, tid, wa, ud, nullptr, rg2, pc);
     stamp();  // 6
     const DscnnWeights w3 = weights_now();
     __syncthreads();
@@ -541,7 +543,7 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
         pc.s_dwb = pow2f(ky[4]);
         pc.s_pwb = pow2f(sg[4]);
     }
-    block_phase<3, MODE, CLUSTER, UT>(w3, lds, tid, wa, ud, nullptr, rg3, pc);
+    block_phase<3, MODE, CLUSTER, UT, PERSIST>(w3, lds, tid, wa, ud, nullptr, rg3, pc);
     stamp();  // 8
     const DscnnWeights w4 = weights_now();
     __syncthreads();
@@ -555,7 +557,7 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
     if constexpr (PAIR) {
         pc.inv_out = pow2f(-sg[4]);
     }
-    block_phase<4, MODE, CLUSTER, UT>(w4, lds, tid, wa, ud, a ? a + CH : nullptr, rg4, pc,  // block 4's output follows the pooled means
+    block_phase<4, MODE, CLUSTER, UT, PERSIST>(w4, lds, tid, wa, ud, a ? a + CH : nullptr, rg4, pc,  // block 4's output follows the pooled means
                                       PERSIST ? OFF_POOLBUF_P : OFF_POOLBUF);
     stamp();  // 10
     if constexpr (PERSIST) {

@@ -628,13 +628,44 @@ __device__ __forceinline__ void leftover_partial_unit(float* lds, int lane, int 
     }
 }
 
+// Wavefront priority in the block phases (PRIO: the persistent batched kernels).  A SIMD carries two wavefronts, w and w + 4;
+// VALU issue between them goes by priority, then age, so at equal priority the older one (0-3) runs a unit at its lone speed and
+// the younger gets the leftover slots -- and whenever one of the two runs out of work first the SIMD spends the rest of the
+// block with one busy wavefront, at about two thirds of its throughput ("Wavefront priority per block").  s_setprio
+// moves issue slots and nothing else: the results are the same bits.  It changes only at a wavefront's own unit boundaries and
+// is 0 again in front of every barrier.
+//   block 1 (f16 pairs): whichever of the quarter wavefronts 4-7 combines the leftover tile does so at 1 -- the combine was the
+//            block's tail, done in the slots the tile of 0-3 left over
+//   block 2: 0-3 at 2 for their tile and at 0 for their quarter, 4-7 at 1 throughout: both halves end together
+//   block 4: 4-7 at 1 for their first unit and at 0 for their second: 0-3 still finish first and stage the next clip, but
+//            under a shorter lone tail of 4-7
+// Blocks 3 and conv1 are balanced as they are.  KWS_DSCNN_PRIO_BLOCKS: bit n - 1 set = block n runs its schedule (A/B builds).
+// s_setprio is a scalar instruction and ignores EXEC: every raise sits under a condition formed through readfirstlane, so that
+// it lowers to a scalar branch and not to an exec mask around an unconditional s_setprio, which would raise every wavefront
+// and change nothing (tests/test_dscnn_priority_isa.py holds the device assembly to that).
+#ifndef KWS_DSCNN_PRIO_BLOCKS
+#define KWS_DSCNN_PRIO_BLOCKS 0xb
+#endif
+template <int N>
+constexpr bool kPrioBlock = ((KWS_DSCNN_PRIO_BLOCKS >> (N - 1)) & 1) != 0;
+__device__ __forceinline__ void set_wave_priority(int p) {  // p: a compile-time constant at every call
+    __builtin_amdgcn_sched_barrier(0);
+    if (p == 0)
+        __builtin_amdgcn_s_setprio(0);
+    else if (p == 1)
+        __builtin_amdgcn_s_setprio(1);
+    else
+        __builtin_amdgcn_s_setprio(2);
+    __builtin_amdgcn_sched_barrier(0);
+}
+
 // A quarter wavefront of block N's leftover tile, behind leftover_partial_unit: it counts itself in at OFF_ARRIVE, and the one of
 // the four that counts in last (it reads 3) combines the tile alone, 64 lanes striding over it four channels at a time: output = relu(bias + the four
 // k-block partials, added in a fixed order).  Nobody waits for another wavefront.  The LDS instructions of a wavefront execute in
 // order, so a wavefront's partial stores are done when its count is, and whoever reads 3 reads finished partials.  The waits are
 // on lgkmcnt alone: the requests for the next block's operands, issued by the caller, stay in flight.  The combining wavefront
 // leaves the counter at zero, for block 2 and for the next clip.  Returns the largest value stored (zero on the other three).
-template <int N>
+template <int N, int RAISE = 0>  // RAISE: the priority the combining wavefront takes for the combine (0: it keeps its own)
 __device__ __forceinline__ float leftover_arrive(float* lds, int lane) {
     using G = Blk<N>;
     using L = Leftover<N>;
@@ -646,6 +677,7 @@ __device__ __forceinline__ float leftover_arrive(float* lds, int lane) {
     asm volatile("" ::: "memory");  // (no partial is read ahead of the count)
     float mx = 0.f;
     if (before == 3) {
+        if constexpr (RAISE != 0) set_wave_priority(RAISE);
         // An item is four consecutive output channels of one position: four 16-byte reads (one per k-block), two 8-byte stores
         // (the planes are interleaved in channel pairs).  Lane l takes the channels 4 (l & 15) .. + 3 of position (l >> 4) + 4 r
         // in round r; RB rounds' reads are in flight before the first of their stores.
@@ -698,7 +730,8 @@ __device__ __forceinline__ float leftover_arrive(float* lds, int lane) {
 // wavefront's FIRST unit of this block (a tile, or its quarter of block 1's leftover tile), requested by the caller or by the
 // previous block; on exit (N < 4) the request for its first unit of the next block.  Every later unit's descriptor is
 // requested beside the A operands of that unit, in front of them.  Not read or written without UT.
-template <int N, int MODE, bool RANGED = false, bool UT = false>
+// PRIO (persistent batched kernel, whole maps): the block's wavefront-priority schedule, see above.
+template <int N, int MODE, bool RANGED = false, bool UT = false, bool PRIO = false>
 __device__ __forceinline__ void block_phase(const DscnnWeights& w, float* lds, int tid, PwOperands<MODE>& pwo, UnitDesc& ud,
                                             float* __restrict__ act4 = nullptr, PosRange rg = PosRange{0, 0}, PairCtx pc = PairCtx{},
                                             int off_poolbuf = OFF_POOLBUF) {
@@ -725,6 +758,17 @@ __device__ __forceinline__ void block_phase(const DscnnWeights& w, float* lds, i
     const float* dwtab = lds + OFF_DWTAB + G::BUF * 768;
     const float* pwb = lds + OFF_PWB + G::BUF * 64;
     float* poolbuf = lds + off_poolbuf;  // block 4's pool partials (PERSIST: OFF_POOLBUF_P)
+    static_assert(!PRIO || ((MODE == 4 || MODE == 5) && !RANGED && NW == 8), "priority schedules: product paths on whole maps, two wavefronts per SIMD");
+    constexpr bool PR = PRIO && kPrioBlock<N> && (N == 2 || N == 4);                 // the block's units run under a schedule
+    constexpr int COMBINE_AT = (PRIO && kPrioBlock<N> && N == 1 && MODE == 5) ? 1 : 0;  // the leftover tile's combine is raised
+    // the wavefront index as a scalar the compiler knows to be one: the conditions around s_setprio must be scalar branches
+    const int wv_s = PR ? __builtin_amdgcn_readfirstlane(wv) : 0;
+    if constexpr (PR) {
+        if constexpr (N == 2) {
+            if (wv_s < 4) set_wave_priority(2);
+        }
+        if (wv_s >= 4) set_wave_priority(1);
+    }
 
     // The other table buffer is idle during this block: the next block's tables are fetched now and
     // stored after the units.  Ring and zero slots of the output planes.  No barrier needed before the
@@ -1015,6 +1059,10 @@ __device__ __forceinline__ void block_phase(const DscnnWeights& w, float* lds, i
             }
             epilogue();
             if constexpr (UT) ud = ud_next;
+#ifndef KWS_X_DSCNN_PRIO_STATIC4  // diagnostics builds: wavefronts 4-7 keep priority 1 for the whole of block 4 (the test that the
+                                  // hardware honours it: the halves swap roles)
+            if constexpr (PR && N == 4) set_wave_priority(0);  // a unit boundary: the second unit of 4-7 runs at 0, behind the older partner
+#endif
         } else {
             // VALU cross-check of the pointwise GEMM: each half sums its 32 input channels, halves are
             // combined with a lane exchange.
@@ -1052,15 +1100,17 @@ __device__ __forceinline__ void block_phase(const DscnnWeights& w, float* lds, i
     if constexpr (KSL) {
         using L = Leftover<N>;
         if (wv >= L::WAVE0 && wv < L::WAVE0 + 4) {
+            if constexpr (PR && N == 2) set_wave_priority(0);  // the quarter of 0-3 runs behind the tile of 4-7 (still at 1)
             leftover_partial_unit<N, NP, UT>(lds, lane, wv - L::WAVE0, pwo.ring[0], ud);
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (UT) load_unit_desc(w, N + 1, wv, lane, ud);  // (block 2 has a tile for every wavefront, block 3 too)
             load_afrag(w, N + 1, 0, lane, pwo.ring[0]);  // the next block's first operands fly across the barrier
             __builtin_amdgcn_sched_barrier(0);
             // the last of the four to get here combines the tile; its maximum joins this wavefront's (a maximum is exact in any order)
-            stage_max = fmaxf(stage_max, leftover_arrive<N>(lds, lane));
+            stage_max = fmaxf(stage_max, leftover_arrive<N, COMBINE_AT>(lds, lane));
         }
     }
+    if constexpr (PR || COMBINE_AT != 0) set_wave_priority(0);  // the units are done: everyone is at 0 again in front of the block's barrier
     if constexpr (N < 4) store_block_tables(lds, N + 1, tid, next_tables, pc.s_dwb, pc.s_pwb, pc.s_dww);
     if constexpr (PAIR && N <= 2) publish_wave_max(lds, N == 1 ? 2 : 0, wv, lane, stage_max);
     if constexpr (MFMA) {
