@@ -1013,6 +1013,40 @@ int kws_stream_push_host_rate_i16(kws_ctx* ctx, const int16_t* h_in, int n_in, c
  * n > 0, n < 0.  KWS_ESTATE: no open set. */
 int kws_stream_reset(kws_ctx* ctx, const int32_t* streams, int n);
 
+/* ---- sparse live sets: streams that leave the set and join it again (build-defined, as the reset above) ------------------------
+ * After kws_stream_open every stream is ACTIVE, and a set in which no stream was ever deactivated launches exactly what it
+ * launched before these entries existed.  An INACTIVE stream takes no part in anything a push does: its row of the hop buffer
+ * is not read (its content may be anything) -- EXCEPT by kws_stream_push_rate_i16 / kws_stream_push_host_rate_i16, whose
+ * resampler kernel keeps running over every slot and so READS the idle rows of its input (they must be readable memory; what
+ * they hold does not matter, an idle stream's resampler history is zeroed when it is activated) --; its PCM ring, feature ring,
+ * endpointer state and posterior ring are not written; its rows of d_logits, d_label and of the zero-copy host arrays are not
+ * written and keep what they held; it emits no utterance and no event.  The set's clocks run on: the hop counter, the push
+ * count, the utterance unit's frame and append counters, the event unit's decision counter.  The fused push then launches
+ * workgroups for the active streams alone, and unless kws_stream_cluster pinned it the default time-tile cluster follows the
+ * ACTIVE count (4 up to 64, 2 up to 128, else 1).  A push with no active stream is legal: the hop counter advances, the
+ * zero-copy flag is raised, the armed steps tick.
+ * kws_stream_deactivate: an utterance open on a named stream closes with reason 2, exactly as kws_stream_reset closes it (its
+ *   span stays cuttable); the stream then leaves the set.  Naming an inactive stream is a no-op.
+ * kws_stream_activate: the named streams get the whole of kws_stream_reset -- rings, silence rows, resampler history, endpointer
+ *   state, the utterance start-over with the previous close at hops appended - 1, the event epoch and refractory wait -- and
+ *   then join.  On an active stream it is a plain reset.
+ * Both are enqueued on the context's stream between two pushes, with no host synchronisation and no allocation after the set's
+ * first deactivation; streams (host int32 [n], duplicates allowed) travels inside the launches.  Checks and codes are
+ * kws_stream_reset's: n == 0 KWS_OK; KWS_EINVAL with nothing changed for an index outside [0, n_streams), NULL with n > 0,
+ * n < 0; KWS_ESTATE without an open set; KWS_EUNSUPPORTED, before anything changes, while kws_stream_smooth_f32's history is live.
+ * kws_stream_active: the host's own record -- no device work, no wait.  out: uint8 [n_streams], 1 = active, or NULL;
+ *   n_active: the count, or NULL.
+ * Served while some stream is inactive: kws_stream_push_i16 with logits on the product maths (KWS_PW_SPLIT_BF16,
+ * KWS_PW_PAIR_F16) without use_graph, kws_stream_push_host_i16, kws_stream_wait_host, both rate pushes, live utterances and live
+ * events armed on the set with their poll / read / cut / flush / smoothed entries, kws_stream_state, kws_stream_copy_features,
+ * and kws_stream_reset (a no-op on an inactive stream).  REFUSED with KWS_EUNSUPPORTED while any stream is inactive, before any
+ * launch and with no hop taken: features-only pushes (d_logits == NULL) and the diagnostic pointwise maths, use_graph,
+ * kws_stream_push_cnn_trad_i16, kws_stream_vad_f32, kws_stream_utt_step_i16, kws_stream_detect_step_f32 -- each is a kernel of
+ * its own over every slot.  kws_stream_open and kws_stream_close restore "all active". */
+int kws_stream_deactivate(kws_ctx* ctx, const int32_t* streams, int n);
+int kws_stream_activate(kws_ctx* ctx, const int32_t* streams, int n);
+int kws_stream_active(kws_ctx* ctx, uint8_t* out, int* n_active);
+
 /* ---- evaluation statistics on the device (build-defined: the reference computes them on the host, with a
  * round trip per batch -- running_loss += loss.item(), torch.max(outputs, 1), (predicted == labels).sum().item() in
  * train.py:51-54,79-98 and kws/libs/training.py:300-303,347-393 -- and test.py:27-58 derives the per-class report, the

@@ -1,6 +1,6 @@
 // The context behind the C ABI (include/kws_hip.h), the error plumbing and the device-memory helpers shared by the translation
 // units that implement it (kws_api.hip, kws_stream.hip, kws_cnntrad.hip, kws_frontend.hip, kws_weights.hip, kws_ingest.hip,
-// kws_scan.hip, kws_score.hip, kws_ragged.hip, kws_decide.hip, kws_eval.hip, kws_resample.hip, kws_live.hip, kws_live_detect.hip, kws_stream_reset.hip, kws_*_bwd.hip),
+// kws_scan.hip, kws_score.hip, kws_ragged.hip, kws_decide.hip, kws_eval.hip, kws_resample.hip, kws_live.hip, kws_live_detect.hip, kws_stream_reset.hip, kws_stream_active.hip, kws_*_bwd.hip),
 // the table of what the host flows need of a model, and the event bracket of a timed launch.
 // Memory: every device or pinned allocation of the context is a DeviceBuffer / PinnedBuffer member (kws_buffer.h) of kws_ctx or of
 // a sub-state the context points to, and is freed by that member's destructor.  The *_free functions below reset what is not
@@ -49,6 +49,16 @@ DetectResetView stream_detect_reset_view(kws_ctx* c);
 // live utterances: close what is open on the named streams with reason 2 and start their endpointer over -- one more tick of the
 // unit's queue (kws_live.hip); nothing when the context is unarmed
 int stream_utt_reset(kws_ctx* c, const ResetMask& m);
+// kws_stream_reset's checks under the name `fn` of the entry that makes them (kws_stream_reset.hip; kws_stream_activate and
+// kws_stream_deactivate share them, kws_stream_active.hip).  KWS_OK with *nothing = true: n == 0, the call is done.
+int stream_reset_check(kws_ctx* c, const char* fn, const int32_t* streams, int n, bool* nothing);
+// ... and its launches over the checked list.  only_active: inactive streams are skipped; utt_only: the rings and the other units
+// stay, only what is open in the live utterances closes (a deactivation)
+int stream_reset_launch(kws_ctx* c, const int32_t* streams, int n, bool only_active, bool utt_only);
+// Sparse sets (kws_stream_active.hip): the launch of a push that finds no active stream -- the hop counter advances, the zero-copy
+// flag follows it --, and the release of what the first deactivation allocated
+hipError_t launch_stream_tick(hipStream_t s, int* d_hops, int* h_flag);
+void stream_active_free(kws_ctx* c);
 // What the host flows need of a model.  The recording flows (scan_recordings, kws_scan.hip; scan_ragged_entry, kws_ragged.hip), the
 // fused clip entries (infer_clips, kws_api.hip) and the stream push (stream_push, kws_stream.hip) are each written once and take one
 // of these.  fn names the entry: a refusal starts with it, in that model's words, and is composed on the failing branch only.
@@ -162,6 +172,21 @@ struct kws_ctx {
     // feature ring's row 0 is the row of an all-zero frame -- then the hop counter, the PCM ring and the zero hop of that run
     DeviceBuffer<float> d_reset_scratch;
     bool reset_row_ready = false;
+    // sparse sets (kws_stream_activate / kws_stream_deactivate, kws_stream_active.hip).  The host mirror decides everything a launch
+    // needs -- the count is the grid, the bits travel by value --; the device list is rebuilt from it at every change.
+    int n_active = 0;                              // == n_streams until a stream is deactivated
+    std::vector<unsigned long long> active_bits;   // bit s % 64 of word s / 64; empty until the set's first deactivation = all active
+    DeviceBuffer<int32_t> d_active_list;           // [n_streams]: the first n_active entries are the active streams, ascending
+    bool sparse() const { return n_active < n_streams; }
+    bool is_active(int s) const { return active_bits.empty() || ((active_bits[(size_t)s >> 6] >> (s & 63)) & 1ull); }
+    kws::ResetMask active_chunk(int first) const {  // the mask of streams first .. first + RESET_CHUNK - 1 (first a multiple of RESET_CHUNK)
+        kws::ResetMask m{};
+        for (int k = 0; k < kws::RESET_CHUNK / 64; ++k) {
+            const size_t w = (size_t)first / 64 + k;
+            m.w[k] = active_bits.empty() ? ~0ull : (w < active_bits.size() ? active_bits[w] : 0ull);
+        }
+        return m;
+    }
 
     // evaluation statistics (kws_eval_*, kws_eval.hip): one allocation of 64-bit words -- counts[4], loss_sum (a double),
     // confusion [C][C], hist_pos [C][K], hist_neg [C][K] -- and the per-workgroup float64 loss partials of one update
@@ -246,6 +271,13 @@ inline int check_append_energy(kws_ctx* c, const char* fn) {
 }
 inline int check_normalize_to(kws_ctx* c, const char* fn, int v) {
     return v >= 0 && v <= 32767 ? KWS_OK : fail(c, KWS_EINVAL, std::string(fn) + ": normalize_to must be in [0, 32767]");
+}
+// While a stream of the set is inactive (kws_stream_deactivate) only the fused push and the steps armed behind it are served: every
+// other per-hop entry is a kernel of its own over all slots, which would need the list.  `what`: the route, in the entry's words.
+inline int refuse_sparse(kws_ctx* c, const char* fn, const char* what) {
+    if (!c->sparse()) return KWS_OK;
+    return fail(c, KWS_EUNSUPPORTED, std::string(fn) + ": " + what + " run over every slot of the set, and " + std::to_string(c->n_streams - c->n_active) +
+                                         " of its streams are inactive (kws_stream_deactivate); kws_stream_activate them first");
 }
 // No exception may cross the C ABI (ctypes would terminate the process): entry points that allocate host containers or
 // start threads run their body between these two.

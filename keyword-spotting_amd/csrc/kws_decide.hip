@@ -142,6 +142,7 @@ int kws_stream_vad_f32(kws_ctx* c, float log_energy_threshold, int on_window, in
     if (!d_state) return fail(c, KWS_EINVAL, "kws_stream_vad_f32: d_state is NULL");
     int rc = check_endpoint_windows(c, "kws_stream_vad_f32", on_window, off_window);
     if (!rc) rc = check_append_energy(c, "kws_stream_vad_f32");
+    if (!rc) rc = refuse_sparse(c, "kws_stream_vad_f32", "the endpointer's frames");
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     if (on_window != c->vad_on || off_window != c->vad_off) {  // (re)start the history

@@ -208,9 +208,13 @@ __device__ __forceinline__ void pool_fc_wave(const DscnnWeights& w, const float*
 // and nothing else.
 // SCAN (kws_scan_i16, launch_dscnn_scan): "clip" i is a window of a long recording's frame array -- only the address its
 // features are fetched from changes (clip_features); logits and labels stay indexed by i.
+// ACTIVE (with STREAM; a set with deactivated streams, kws_stream_active.hip): the grid holds the ACTIVE streams' workgroups only and
+// workgroup slot i serves stream ring_hops[i] -- the set's device list of active streams, ascending, in the argument the fused push
+// does not otherwise read, so that the kernel-argument segment of every instantiation stays as it was.  Everything else, the
+// finishers count among it (gridDim.x / cluster), is the body below: rings, partial sums, results and labels are addressed by `clip`.
 // The parameter list is mirrored by FwdKernelArgs / FwdKernelFn (the persistent kernels read arguments from the segment).
 template <int MODE, bool DIAG = true, bool PRECONV = false, bool STREAM = false, bool CLUSTER = false, bool PERSIST = false,
-          bool SCAN = false>
+          bool SCAN = false, bool ACTIVE = false>
 __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, const float* __restrict__ feat, int B,
                                                            float* __restrict__ logits, int32_t* __restrict__ label,
                                                            float* __restrict__ act_arg,
@@ -223,6 +227,7 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
     constexpr int NP = PAIR ? 2 : 3;
     BlockTables t1_pre{};              // PRECONV: block 1's tables between their fetch and their (PAIR: scaled) store
     static_assert(!CLUSTER || STREAM, "time-tile clusters exist for the streaming push only");
+    static_assert(!ACTIVE || STREAM, "a list of active streams exists for the streaming push only");
     float* const act = DIAG ? act_arg : nullptr;
     unsigned long long* const stamps = DIAG ? stamps_arg : nullptr;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -235,6 +240,7 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
     const int cl_n = CLUSTER ? sp.cluster : 1;
     int clip = CLUSTER ? (int)blockIdx.x / cl_n : (int)blockIdx.x;  // PERSIST: the running clip
     const int cl_tile = CLUSTER ? (int)blockIdx.x - clip * cl_n : 0;
+    if constexpr (ACTIVE) clip = ring_hops[clip];  // workgroup-uniform: slot -> stream
     if (clip >= B) return;
     // Rows of each stage this workgroup computes (CLUSTER; otherwise everything).  Block 4's output rows [j0, j1) need block
     // 3's rows [j0 - 2, j1) (a 3-row stencil, and block 3's stored plane is block 4's input without its ring: row index - 1),
@@ -704,15 +710,25 @@ __global__ __launch_bounds__(NT) void kws_dscnn_fwd_kernel(DscnnWeights w_arg, c
 
 // The instantiations of kws_dscnn_fwd_kernel the host can launch.  This table is the one place that names them:
 // dscnn_init_device walks it, launch_variant looks a launch up in it.
-enum : unsigned { F_DIAG = 1, F_PRECONV = 2, F_STREAM = 4, F_CLUSTER = 8, F_PERSIST = 16, F_SCAN = 32 };
+enum : unsigned { F_DIAG = 1, F_PRECONV = 2, F_STREAM = 4, F_CLUSTER = 8, F_PERSIST = 16, F_SCAN = 32, F_ACTIVE = 64 };
 struct FwdVariant {
     int mode;
-    unsigned flags;  // the six template booleans below as one word: what launch_variant is asked for
-    bool diag, preconv, stream, cluster, persist, scan;
+    unsigned flags;  // the seven template booleans below as one word: what launch_variant is asked for
+    bool diag, preconv, stream, cluster, persist, scan, active;
     constexpr FwdVariant(int m, unsigned f)
-        : mode(m), flags(f), diag(f & F_DIAG), preconv(f & F_PRECONV), stream(f & F_STREAM), cluster(f & F_CLUSTER), persist(f & F_PERSIST), scan(f & F_SCAN) {}
+        : mode(m), flags(f), diag(f & F_DIAG), preconv(f & F_PRECONV), stream(f & F_STREAM), cluster(f & F_CLUSTER), persist(f & F_PERSIST), scan(f & F_SCAN),
+          active(f & F_ACTIVE) {}
 };
+// The ACTIVE instantiations are compiled in a unit of their own (kws_dscnn_active.hip, which includes this file with
+// KWS_DSCNN_ACTIVE_UNIT defined): instantiated beside the others they gave the stages' templates a second caller each, and the
+// compiler then laid out the two cluster kernels differently.
 constexpr FwdVariant kFwdVariants[] = {
+#ifdef KWS_DSCNN_ACTIVE_UNIT
+    {4, F_STREAM | F_ACTIVE},              // launch_dscnn_stream_active: split-bf16, one workgroup per active stream
+    {4, F_STREAM | F_CLUSTER | F_ACTIVE},  // ... sp.cluster > 1 workgroups per active stream
+    {5, F_STREAM | F_ACTIVE},              // launch_dscnn_stream_active: f16 pairs, one workgroup per active stream
+    {5, F_STREAM | F_CLUSTER | F_ACTIVE},  // ... sp.cluster > 1 workgroups per active stream
+#else
     {0, F_DIAG},                       // launch_dscnn: VALU cross-check of the GEMMs (diagnostics entry)
     {1, F_DIAG},                       // launch_dscnn: f32 MFMA, and every mode number without a case of its own
     {2, F_DIAG},                       // launch_dscnn: timing ablation, matrix core only
@@ -736,12 +752,13 @@ constexpr FwdVariant kFwdVariants[] = {
     {4, F_PERSIST | F_SCAN},           // launch_dscnn_scan: split-bf16, B > n_cu
     {5, F_SCAN},                       // launch_dscnn_scan: f16 pairs, one window per workgroup
     {5, F_PERSIST | F_SCAN},           // launch_dscnn_scan: f16 pairs, B > n_cu
+#endif
 };
 constexpr size_t N_FWD_VARIANTS = sizeof(kFwdVariants) / sizeof(kFwdVariants[0]);
 
 template <size_t I>
 constexpr auto kFwdKernel = &kws_dscnn_fwd_kernel<kFwdVariants[I].mode, kFwdVariants[I].diag, kFwdVariants[I].preconv, kFwdVariants[I].stream,
-                                                  kFwdVariants[I].cluster, kFwdVariants[I].persist, kFwdVariants[I].scan>;
+                                                  kFwdVariants[I].cluster, kFwdVariants[I].persist, kFwdVariants[I].scan, kFwdVariants[I].active>;
 template <size_t... I>
 constexpr std::array<FwdKernelFn, sizeof...(I)> fwd_kernel_table(std::index_sequence<I...>) {
     return {{kFwdKernel<I>...}};
@@ -765,15 +782,30 @@ hipError_t launch_variant(int mode, unsigned flags, int grid, hipStream_t s, con
     return hipErrorInvalidValue;
 }
 
-}  // namespace
-
 // The kernel needs the CU's whole 160 KiB of LDS as dynamic shared memory: opt in once per device.
-hipError_t dscnn_init_device() {
+hipError_t init_variants() {
     for (FwdKernelFn k : kFwdKernels) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_FLOATS * (int)sizeof(float));
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+}  // namespace
+
+#ifdef KWS_DSCNN_ACTIVE_UNIT
+hipError_t dscnn_active_init_device() { return init_variants(); }
+
+hipError_t launch_dscnn_stream_active(hipStream_t s, const DscnnWeights& w, const StreamPush& sp, float* d_feat_ring, int n_streams, float* d_logits,
+                                      int32_t* d_label, bool pair, const int32_t* d_active, int n_active) {
+    const bool tiles = sp.cluster > 1;  // time tiles: sp.cluster workgroups per active stream
+    return launch_variant(pair ? 5 : 4, (tiles ? F_STREAM | F_CLUSTER : F_STREAM) | F_ACTIVE, tiles ? n_active * sp.cluster : n_active, s, w, d_feat_ring,
+                          n_streams, d_logits, d_label, nullptr, nullptr, d_active, sp);
+}
+#else
+hipError_t dscnn_init_device() {
+    const hipError_t e = init_variants();
+    return e == hipSuccess ? dscnn_active_init_device() : e;
 }
 
 hipError_t launch_dscnn_stream(hipStream_t s, const DscnnWeights& w, const StreamPush& sp, float* d_feat_ring, int n_streams,
@@ -813,5 +845,6 @@ hipError_t launch_dscnn_scan(hipStream_t s, const DscnnWeights& w, const float* 
     return launch_variant(mode, persist ? F_PERSIST | F_SCAN : F_SCAN, persist ? n_cu : B, s, w, d_feat, B, d_logits, d_label, nullptr, nullptr,
                           nullptr, sp);
 }
+#endif  // KWS_DSCNN_ACTIVE_UNIT
 
 }  // namespace kws

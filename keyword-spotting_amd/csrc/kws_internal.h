@@ -265,6 +265,11 @@ struct StreamPush {
 };
 hipError_t launch_dscnn_stream(hipStream_t s, const DscnnWeights& w, const StreamPush& sp, float* d_feat_ring, int n_streams,
                                float* d_logits, int32_t* d_label, bool pair);
+// The same for a set with deactivated streams (kws_dscnn_active.hip): d_active is the device list of the n_active >= 1 active
+// streams, ascending; the grid holds their workgroups alone and no other stream's state or result row is touched.
+hipError_t launch_dscnn_stream_active(hipStream_t s, const DscnnWeights& w, const StreamPush& sp, float* d_feat_ring, int n_streams, float* d_logits,
+                                      int32_t* d_label, bool pair, const int32_t* d_active, int n_active);
+hipError_t dscnn_active_init_device();  // called by dscnn_init_device
 hipError_t launch_dscnn(hipStream_t s, const DscnnWeights& w, const float* d_feat, int B, float* d_logits,
                         int32_t* d_label, float* d_act, int mode, unsigned long long* d_stamps = nullptr,
                         const int* d_ring_hops = nullptr, bool preconv = false, int frames_lag = 3, int n_cu = 0);

@@ -180,6 +180,78 @@ __global__ __launch_bounds__(LIVE_MAX_STREAMS) void kws_live_reset_kernel(const 
     eq_publish(a.q, was, all, frames);  // the unit's own counters stand
 }
 
+// The step behind a push of a set with inactive streams (kws_stream_deactivate; `m`: the active ones, by value): the step of
+// kws_live_step_kernel<false> for the active streams -- the same append, walk and rules, so an active stream's records are those of
+// a dense set -- while an inactive stream's thread appends nothing, pushes no flag, walks nothing and emits nothing, but takes part
+// in the ballots and the barriers.  The unit's two counters run on for the whole set.  Only ever stepped by a push (explicit steps
+// are refused while a stream is inactive).  A kernel of its own for the reason kws_live_reset_kernel is one.
+__global__ __launch_bounds__(LIVE_MAX_STREAMS) void kws_live_step_masked_kernel(const LiveArgs a, const ResetMask m) {
+    const int tid = threadIdx.x;
+    const EqCounts was = eq_counts(a.q);
+    const unsigned long long frames = was.unit[0], appended = was.unit[1];
+    const int h = a.ctx_hops[0];  // >= 1 behind a push
+    const bool do_append = h >= 1;
+    const bool do_walk = do_append && appended + 1 >= (unsigned long long)a.K && h >= a.K;
+    if (do_append) {  // workgroup-uniform
+        const int16_t* src = a.hop + (int)(((long long)(h - 1) * a.step) % a.ring_len);
+        const int at = (int)((appended * (unsigned long long)a.step) % (unsigned long long)a.H);
+        if (a.vec) {
+            const int per = a.step >> 3;
+            for (int i = tid; i < a.S * per; i += (int)blockDim.x) {
+                const int s = i / per, j = i - s * per;
+                if (m.has(s)) reinterpret_cast<uint4*>(a.hist + (size_t)s * a.H + at)[j] = reinterpret_cast<const uint4*>(src + (size_t)s * a.hop_stride)[j];
+            }
+        } else {
+            for (int i = tid; i < a.S * a.step; i += (int)blockDim.x) {
+                const int s = i / a.step, j = i - s * a.step;
+                if (m.has(s)) a.hist[(size_t)s * a.H + at + j] = src[(size_t)s * a.hop_stride + j];
+            }
+        }
+    }
+    bool closed = false;
+    long long open = 0, start_frame = 0, close_frame = 0;
+    int reason = 0;
+    if (tid < a.S && do_walk && m.has(tid)) {
+        int* cnt = a.counts + 4 * tid;
+        long long* ps = a.pos + 2 * tid;
+        int trig = cnt[2];
+        open = ps[0];
+        const long long prev_close = ps[1];
+        const long long f = (long long)frames;
+        const float* energy = a.energy + (size_t)((h - a.K) % a.num_frames) * a.numcep;
+        const int v = ep_voiced(energy[(size_t)tid * ((size_t)a.num_frames * a.numcep)], a.threshold) ? 1 : 0;
+        const EpCounts n = ep_ring_push(a.bits + (size_t)tid * EP_BIT_WORDS, cnt, f, v, a.on_window, a.off_window);
+        if (!trig) {
+            if (ep_opens(n.on, a.on_window)) {  // the utterance opens; nothing else happens at this frame
+                open = f;
+                ps[0] = f;
+                cnt[2] = 1;
+            }
+        } else if (ep_closes(n.off, a.off_window)) {
+            closed = true;
+            reason = 0;
+            close_frame = f;
+        } else if (f - open + 1 >= a.max_frames) {
+            closed = true;
+            reason = 1;
+            close_frame = f;
+        }
+        if (closed) {
+            start_frame = ep_span_start(open, a.pre_roll, prev_close);
+            ps[1] = close_frame;
+            cnt[2] = 0;
+        }
+    }
+    const long long rec[LIVE_REC] = {(long long)tid, start_frame * a.step, close_frame * a.step + a.frame_len, open, close_frame, (long long)reason};
+    const int all = eq_emit(a.q, was, closed, rec);
+    const unsigned long long frames_now = frames + (do_walk ? 1 : 0);
+    eq_publish(a.q, was, all, frames_now);
+    if (tid == 0) {
+        a.q.unit()[0] = frames_now;
+        a.q.unit()[1] = appended + (do_append ? 1 : 0);
+    }
+}
+
 // kws_cut_i16_kernel (kws_segment.hip) with a ring origin: one workgroup per sequence number, the record read from the device
 // queue (q.ctr[0]: events so far; q.unit()[1]: hops appended).  The span [start, end) of stream r lies in the history ring from
 // start mod H on and crosses the seam at most once (end - start <= H): element i is at p0 + i, minus H from the seam on.  The
@@ -277,6 +349,15 @@ int stream_utt_reset(kws_ctx* c, const ResetMask& m) {
 int stream_utt_pushed(kws_ctx* c) {
     if (!c->stream_utt) return KWS_OK;
     c->stream_utt->mode = 1;
+    if (c->sparse()) {  // some stream is inactive: the masked step, its active streams by value (the unit holds at most one chunk)
+        StreamUtt* u = c->stream_utt;
+        const LiveArgs a = utt_args(c, c->d_pcm_ring.get(), c->ring_len, c->d_hops.get(), c->d_feat_ring.get());
+        const int threads = a.S <= 256 ? 256 : (a.S + 63) / 64 * 64;  // utt_launch's rule for a step that copies
+        hipLaunchKernelGGL(kws_live_step_masked_kernel, dim3(1), dim3(threads), 0, c->stream, a, c->active_chunk(0));
+        HIP_TRY(c, hipGetLastError());
+        eq_enqueued(u->a.q);
+        return KWS_OK;
+    }
     return utt_launch<false>(c, c->d_pcm_ring.get(), c->ring_len, c->d_hops.get(), c->d_feat_ring.get());
 }
 
@@ -362,6 +443,7 @@ int kws_stream_utt_step_i16(kws_ctx* c, const int16_t* d_hop, const float* d_ene
     if (!u) return fail(c, KWS_ESTATE, "kws_stream_utt_step_i16: call kws_stream_utt_open first");
     if (!d_hop && !d_energy) return fail(c, KWS_EINVAL, "kws_stream_utt_step_i16: d_hop and d_energy are both NULL");
     if (u->mode == 1) return fail(c, KWS_ESTATE, "kws_stream_utt_step_i16: this utterance set is stepped by the pushes");
+    if (int rc = refuse_sparse(c, "kws_stream_utt_step_i16", "explicit steps")) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     u->mode = 2;
     return utt_launch<false>(c, d_hop, c->fp.frame_step, nullptr, d_energy);

@@ -58,8 +58,13 @@ namespace {
 // decisions since its reset --, same order of addition, same single division; the term count is then the pair's own, no longer
 // the workgroup's.  The body of two kernels: a set that was never reset launches kws_live_detect_step_kernel, under the name and
 // with the code it had before there was a reset (DESIGN 4.32 holds its listing to that).
-template <bool EPOCH>
-__device__ __forceinline__ void detect_step(const DetectArgs& a, const long long* __restrict__ epoch) {
+// MASKED (a set with inactive streams, kws_stream_deactivate; `active`: the active ones): the epoch step in which an inactive
+// stream writes no posterior, gets no mean, takes no decision and emits nothing; the decision counter runs on for the whole set.  A
+// stream that joins again has its epoch at the decision count of its activation, so no mean reads a slot of its idle time.  A third
+// kernel: the two above keep their code.
+template <bool EPOCH, bool MASKED = false>
+__device__ __forceinline__ void detect_step(const DetectArgs& a, const long long* __restrict__ epoch, const ResetMask* active = nullptr) {
+    auto mine = [&](int s) { return !MASKED || active->has(s); };
     const int tid = threadIdx.x;
     const EqCounts was = eq_counts(a.q);
     const unsigned long long d = was.unit[0];
@@ -75,13 +80,15 @@ __device__ __forceinline__ void detect_step(const DetectArgs& a, const long long
     if (decide) {
         const int C = a.C, W = a.W;
         const int slot = (int)(d % (unsigned long long)W);
-        if (tid < a.S) softmax_row(a.logits + (size_t)tid * C, C, a.ring + ((size_t)tid * W + slot) * C);
+        if (tid < a.S && mine(tid)) softmax_row(a.logits + (size_t)tid * C, C, a.ring + ((size_t)tid * W + slot) * C);
         __syncthreads();
         int terms = d + 1 < (unsigned long long)W ? (int)d + 1 : W;
         int oldest = slot - terms + 1 + (slot - terms + 1 < 0 ? W : 0);
         float count = (float)terms;
         for (int i = tid; i < a.S * C; i += (int)blockDim.x) {
             const int s = i / C, c = i - s * C;
+            if constexpr (MASKED)
+                if (!mine(s)) continue;
             if constexpr (EPOCH) {
                 const long long since = (long long)d - epoch[s] + 1;  // >= 1: an epoch is a decision count already reached
                 terms = since < (long long)W ? (int)since : W;
@@ -111,7 +118,7 @@ __device__ __forceinline__ void detect_step(const DetectArgs& a, const long long
             a.smoothed[i] = acc;
         }
         __syncthreads();
-        if (tid < a.S) {
+        if (tid < a.S && mine(tid)) {
             const float* sm = a.smoothed + (size_t)tid * C;
             for (int c = 0; c < C; ++c) {
                 const float v = sm[c];
@@ -142,6 +149,11 @@ __global__ __launch_bounds__(DETECT_MAX_STREAMS) void kws_live_detect_step_epoch
     detect_step<true>(a, epoch);
 }
 
+__global__ __launch_bounds__(DETECT_MAX_STREAMS) void kws_live_detect_step_masked_kernel(const DetectArgs a, const long long* __restrict__ epoch,
+                                                                                         const ResetMask active) {
+    detect_step<true, true>(a, epoch, &active);
+}
+
 // One launch of the step kernel with the set's state.  Threads: one per stream at least, and up to one per (stream, class) pair
 // for the sums.
 int detect_launch(kws_ctx* c, const float* d_logits, const int* ctx_hops) {
@@ -151,7 +163,9 @@ int detect_launch(kws_ctx* c, const float* d_logits, const int* ctx_hops) {
     a.ctx_hops = ctx_hops;
     const long long pairs = (long long)a.S * a.C;
     const int threads = pairs >= DETECT_MAX_STREAMS ? DETECT_MAX_STREAMS : (int)((pairs + 63) / 64 * 64);  // >= S rounded up: C >= 1
-    if (u->was_reset)
+    if (c->sparse())  // (an epoch of 0, where no stream was reset yet, is the plain step's term count)
+        hipLaunchKernelGGL(kws_live_detect_step_masked_kernel, dim3(1), dim3(threads), 0, c->stream, a, (const long long*)u->epoch.get(), c->active_chunk(0));
+    else if (u->was_reset)
         hipLaunchKernelGGL(kws_live_detect_step_epoch_kernel, dim3(1), dim3(threads), 0, c->stream, a, (const long long*)u->epoch.get());
     else
         hipLaunchKernelGGL(kws_live_detect_step_kernel, dim3(1), dim3(threads), 0, c->stream, a);
@@ -263,6 +277,7 @@ int kws_stream_detect_step_f32(kws_ctx* c, const float* d_logits) {
     if (!u) return fail(c, KWS_ESTATE, "kws_stream_detect_step_f32: call kws_stream_detect_open first");
     if (!d_logits) return fail(c, KWS_EINVAL, "kws_stream_detect_step_f32: d_logits is NULL");
     if (u->mode == 1) return fail(c, KWS_ESTATE, "kws_stream_detect_step_f32: this detection set is stepped by the pushes");
+    if (int rc = refuse_sparse(c, "kws_stream_detect_step_f32", "explicit steps")) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     u->mode = 2;
     return detect_launch(c, d_logits, nullptr);

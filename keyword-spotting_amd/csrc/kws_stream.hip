@@ -35,6 +35,7 @@ void stream_free(kws_ctx* c) {
     c->d_cl_count.reset();
     c->d_reset_scratch.reset();
     c->reset_row_ready = false;
+    stream_active_free(c);  // every stream of the next set is active (kws_stream_active.hip)
     c->n_streams = 0;
 }
 
@@ -58,12 +59,18 @@ static hipError_t stream_enqueue(kws_ctx* c, const int16_t* d_hop, float* d_logi
     if (one_launch_push(c, d_logits)) {
         ProfScope ps(c, KWS_K_DSCNN, timed);
         // time-tile clusters while there are CUs to spare: 4 workgroups per stream up to 64 streams, 2 up to 128 (256 CUs)
-        const int cluster = c->stream_cluster ? c->stream_cluster : (c->n_streams <= 64 ? 4 : (c->n_streams <= 128 ? 2 : 1));
+        // (n_active == n_streams unless streams were deactivated: a sparse set gets the cluster of the streams it serves)
+        const int cluster = c->stream_cluster ? c->stream_cluster : (c->n_active <= 64 ? 4 : (c->n_active <= 128 ? 2 : 1));
         const bool host = c->h_stream_flag && c->host_results_classes == c->mw.num_classes;
         const StreamPush sp = {c->fp, c->ft, d_hop, c->d_pcm_ring.get(), c->ring_len, c->d_hops.get(), c->d_refine.get(), 0, cluster,
                                c->d_cl_part.get(), c->d_cl_count.get(), host ? c->h_stream_logits.get() : nullptr,
                                host ? c->h_stream_label.get() : nullptr, host ? c->h_stream_flag.get() : nullptr};
         c->last_push_host = host;
+        if (c->sparse()) {  // the active streams' workgroups alone, their stream index from the set's list; none: the clock runs on
+            if (!c->n_active) return launch_stream_tick(c->stream, sp.hops, sp.h_flag);
+            return launch_dscnn_stream_active(c->stream, c->mw, sp, c->d_feat_ring.get(), c->n_streams, d_logits, d_label, c->pw_math == KWS_PW_PAIR_F16,
+                                              c->d_active_list.get(), c->n_active);
+        }
         return launch_dscnn_stream(c->stream, c->mw, sp, c->d_feat_ring.get(), c->n_streams, d_logits, d_label, c->pw_math == KWS_PW_PAIR_F16);
     }
     c->last_push_host = false;
@@ -140,6 +147,7 @@ int kws_stream_open(kws_ctx* c, int n_streams) {
         return fail(c, KWS_ENOMEM, "kws_stream_open: device allocation failed");
     }
     c->n_streams = n_streams;
+    c->n_active = n_streams;
     c->pushes_enqueued = 0;
     c->host_push = 0;
     c->last_push_host = false;
@@ -213,7 +221,15 @@ int kws_stream_push_host_i16(kws_ctx* c, const int16_t* h_hop, const float** h_l
     // the hop goes into pinned, device-mapped memory and the kernel reads it from there (one PCIe read of 320 bytes per stream
     // on the frame wavefront's path) -- no H2D submission in front of the launch.  One slot: this call returns after the
     // kernel's last workgroup has raised the flag, i.e. after every read of it.
-    memcpy(c->h_stream_hop.get(), h_hop, sizeof(int16_t) * (size_t)c->n_streams * c->fp.frame_step);
+    if (c->sparse()) {  // the rows of inactive streams are not read, here either
+        const size_t row = (size_t)c->fp.frame_step;
+        for (size_t w = 0; w < c->active_bits.size(); ++w)
+            for (unsigned long long bits = c->active_bits[w]; bits; bits &= bits - 1) {
+                const size_t s = 64 * w + (size_t)__builtin_ctzll(bits);
+                memcpy(c->h_stream_hop.get() + s * row, h_hop + s * row, sizeof(int16_t) * row);
+            }
+    } else
+        memcpy(c->h_stream_hop.get(), h_hop, sizeof(int16_t) * (size_t)c->n_streams * c->fp.frame_step);
     int rc = kws_stream_push_i16(c, c->h_stream_hop.get(), c->d_hr_logits.get(), c->d_hr_label.get(), 0);
     if (rc) return rc;
     return kws_stream_wait_host(c, h_logits, h_label);
@@ -243,6 +259,11 @@ int kws_stream_push_i16(kws_ctx* c, const int16_t* d_hop, float* d_logits, int32
         // takes 6.9 us of host time against 3.0 us for the plain launch, and completion is observed 8 us later in all
         // (tools/graph_overhead.hip: 20.6 vs 12.3 us launch -> hipStreamSynchronize for a trivial kernel; still 23.6 vs 20.3 us at
         // four kernels).  use_graph is honoured for the multi-launch routes only, where it saves host time per push.
+        if (c->sparse()) {  // the fused push alone takes its streams from the list
+            if (use_graph) return refuse_sparse(c, "kws_stream_push_i16", "use_graph replays launches captured earlier, which");
+            if (!one_launch_push(c, d_logits))
+                return refuse_sparse(c, "kws_stream_push_i16", "features-only pushes and the diagnostic pointwise maths take the frame kernel and the two-launch route, which");
+        }
         if (use_graph && !one_launch_push(c, d_logits)) return stream_enqueue_graph(c, d_hop, d_logits, d_label);
         HIP_TRY(c, stream_enqueue(c, d_hop, d_logits, d_label, true));
         return KWS_OK;
@@ -256,6 +277,7 @@ int kws_stream_push_cnn_trad_i16(kws_ctx* c, const int16_t* d_hop, float* d_logi
     const char* fn = "kws_stream_push_cnn_trad_i16";
     const ModelOps& m = model_ops_cnn_trad();
     return stream_push(c, m, fn, d_hop, d_logits, true, [&]() -> int {
+        if (int rc = refuse_sparse(c, fn, "cnn-trad-fpool3's three launches")) return rc;
         c->last_push_host = false;
         return m.ring_push(c, fn, d_hop, d_logits, d_label);
     });

@@ -116,27 +116,30 @@ int ensure_silence_row(kws_ctx* c) {
 }
 
 }  // namespace
-}  // namespace kws
 
-using namespace kws;
-
-#pragma GCC visibility push(default)
-extern "C" {
-
-int kws_stream_reset(kws_ctx* c, const int32_t* streams, int n) {
-    KWS_GUARD_BEGIN
+int stream_reset_check(kws_ctx* c, const char* fn, const int32_t* streams, int n, bool* nothing) {
+    *nothing = false;
     if (!c) return KWS_EINVAL;
-    if (!c->n_streams) return fail(c, KWS_ESTATE, "kws_stream_reset: call kws_stream_open first");
-    if (n < 0) return fail(c, KWS_EINVAL, "kws_stream_reset: n must not be negative");
-    if (n == 0) return KWS_OK;
-    if (!streams) return fail(c, KWS_EINVAL, "kws_stream_reset: streams is NULL");
+    const std::string f(fn);
+    if (!c->n_streams) return fail(c, KWS_ESTATE, f + ": call kws_stream_open first");
+    if (n < 0) return fail(c, KWS_EINVAL, f + ": n must not be negative");
+    if (n == 0) {
+        *nothing = true;
+        return KWS_OK;
+    }
+    if (!streams) return fail(c, KWS_EINVAL, f + ": streams is NULL");
     for (int i = 0; i < n; ++i)
         if (streams[i] < 0 || streams[i] >= c->n_streams)
-            return fail(c, KWS_EINVAL, "kws_stream_reset: stream " + std::to_string(streams[i]) + " is outside [0, " + std::to_string(c->n_streams) + ")");
+            return fail(c, KWS_EINVAL, f + ": stream " + std::to_string(streams[i]) + " is outside [0, " + std::to_string(c->n_streams) + ")");
     if (c->post_window)
-        return fail(c, KWS_EUNSUPPORTED, "kws_stream_reset: kws_stream_smooth_f32 keeps a running sum and ONE hop count for all streams, which no single stream can leave; smooth with kws_stream_detect_* (a ring and an epoch per stream) on sets that reset streams");
+        return fail(c, KWS_EUNSUPPORTED, f + ": kws_stream_smooth_f32 keeps a running sum and ONE hop count for all streams, which no single stream can leave; smooth with kws_stream_detect_* (a ring and an epoch per stream) on sets that reset streams");
+    return KWS_OK;
+}
+
+int stream_reset_launch(kws_ctx* c, const int32_t* streams, int n, bool only_active, bool utt_only) {
     HIP_TRY(c, hipSetDevice(c->device));
-    if (int rc = ensure_silence_row(c)) return rc;
+    if (!utt_only)
+        if (int rc = ensure_silence_row(c)) return rc;
 
     ResetArgs a{};
     a.n_streams = c->n_streams;
@@ -151,24 +154,42 @@ int kws_stream_reset(kws_ctx* c, const int32_t* streams, int n) {
     a.rs = stream_resample_reset_view(c);
     a.vad_bits = c->d_vad_bits.get();
     a.vad_counts = c->d_vad_counts.get();
-    a.dv = stream_detect_reset_view(c);
+    if (!utt_only) a.dv = stream_detect_reset_view(c);  // (switches the set's event steps to their epoch instantiation)
     for (int first = 0; first < c->n_streams; first += RESET_CHUNK) {
         memset(&a.m, 0, sizeof a.m);
         int named = 0;
         for (int i = 0; i < n; ++i) {
             const int r = streams[i] - first;
             if (r < 0 || r >= RESET_CHUNK || a.m.has(r)) continue;  // another chunk's, or a duplicate
+            if (only_active && !c->is_active(streams[i])) continue;  // left alone until it is activated, which resets it
             a.m.w[r >> 6] |= 1ull << (r & 63);
             named += 1;
         }
         if (!named) continue;
         a.first = first;
-        hipLaunchKernelGGL(kws_stream_reset_kernel, dim3(named), dim3(RESET_THREADS), 0, c->stream, a);
-        HIP_TRY(c, hipGetLastError());
+        if (!utt_only) {
+            hipLaunchKernelGGL(kws_stream_reset_kernel, dim3(named), dim3(RESET_THREADS), 0, c->stream, a);
+            HIP_TRY(c, hipGetLastError());
+        }
         if (first == 0)  // the live units hold at most 1024 streams: theirs are all in the first chunk
             if (int rc = stream_utt_reset(c, a.m)) return rc;
     }
     return KWS_OK;
+}
+
+}  // namespace kws
+
+using namespace kws;
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int kws_stream_reset(kws_ctx* c, const int32_t* streams, int n) {
+    KWS_GUARD_BEGIN
+    bool nothing = false;
+    if (int rc = stream_reset_check(c, "kws_stream_reset", streams, n, &nothing)) return rc;
+    if (nothing) return KWS_OK;
+    return stream_reset_launch(c, streams, n, true, false);
     KWS_GUARD_END(c, "kws_stream_reset")
 }
 

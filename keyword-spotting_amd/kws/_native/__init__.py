@@ -82,6 +82,9 @@ SIGNATURES = {
     "kws_stream_open": (C.c_int, [_c_ctx, C.c_int]),
     "kws_stream_close": (C.c_int, [_c_ctx]),
     "kws_stream_reset": (C.c_int, [_c_ctx, C.c_void_p, C.c_int]),
+    "kws_stream_deactivate": (C.c_int, [_c_ctx, C.c_void_p, C.c_int]),
+    "kws_stream_activate": (C.c_int, [_c_ctx, C.c_void_p, C.c_int]),
+    "kws_stream_active": (C.c_int, [_c_ctx, C.c_void_p, C.POINTER(C.c_int)]),
     "kws_stream_cluster": (C.c_int, [_c_ctx, C.c_int]),
     "kws_stream_host_results": (C.c_int, [_c_ctx, C.c_int]),
     "kws_stream_wait_host": (C.c_int, [_c_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
@@ -880,6 +883,31 @@ class Context:
             raise ModelError("stream_reset: a stream index does not fit int32")
         idx = idx.astype(np.int32)
         self._check(self._lib.kws_stream_reset(self._h, idx.ctypes.data if idx.size else None, int(idx.size)), ModelError)
+
+    def _stream_indices(self, streams, what):
+        idx = np.ascontiguousarray(np.atleast_1d(np.asarray(streams, dtype=np.int64)).ravel())
+        if idx.size and (idx.min() < -2**31 or idx.max() >= 2**31):
+            raise ModelError(f"{what}: a stream index does not fit int32")
+        return idx.astype(np.int32)
+
+    def stream_deactivate(self, streams):
+        """``kws_stream_deactivate``: the named streams (an int or a sequence of indices, host) leave the set -- from the next push
+        on their hop rows are not read and nothing of theirs is written; an utterance open on one closes with reason 2.  Enqueued
+        on the context's stream; the indices travel inside the launch."""
+        idx = self._stream_indices(streams, "stream_deactivate")
+        self._check(self._lib.kws_stream_deactivate(self._h, idx.ctypes.data if idx.size else None, int(idx.size)), ModelError)
+
+    def stream_activate(self, streams):
+        """``kws_stream_activate``: the named streams get the whole of ``stream_reset`` and (re)join the set."""
+        idx = self._stream_indices(streams, "stream_activate")
+        self._check(self._lib.kws_stream_activate(self._h, idx.ctypes.data if idx.size else None, int(idx.size)), ModelError)
+
+    def stream_active(self, n_streams):
+        """``kws_stream_active``: (bool [n_streams], active count) from the host's own record; no device work, no wait."""
+        out = np.zeros(int(n_streams), np.uint8)
+        n = C.c_int(0)
+        self._check(self._lib.kws_stream_active(self._h, out.ctypes.data, C.byref(n)), ModelError)
+        return out.astype(np.bool_), int(n.value)
 
     def stream_push_i16(self, hop, logits=None, label=None, use_graph=False):
         self._check(

@@ -927,6 +927,15 @@ class StreamingSpotter:
     and every other stream keeps its bits.  Times and hop numbers of ``Utterance`` and ``KeywordEvent`` stay in set coordinates;
     ``stream_origin`` turns them into a stream's own.  Not with ``smooth_window`` > 0 (one hop count for all streams): use ``detect``.
 
+    ``deactivate(streams)`` / ``activate(streams)`` take slots out of the set and bring them back (``kws_stream_deactivate``,
+    ``kws_stream_activate``), ``active`` (``np.bool_[S]``) says which are in, and the ``active=`` argument (bool ``[S]``) sets the
+    initial set.  A push launches, reads and writes for the active streams alone: ``push`` keeps its signature and takes full
+    ``[S, hop_in]`` arrays, but the rows of inactive streams are NOT READ (with ``input_rate`` the resampler still reads them; what
+    they hold does not matter) and their rows of the returned labels and logits are STALE -- whatever the stream's last active push
+    left.  An inactive stream yields no utterance and no event.  A stream that is activated starts over as after ``reset``.  A set sized
+    for its peak then costs what its active streams cost.  DS-CNN models only, and not with ``use_graph=True``, ``smooth_window`` > 0 or
+    ``vad_log_energy``: those raise ``ModelError``.
+
     Attributes: ``stream_origin`` -- ``np.int64[S]``, the hop count at each stream's last ``reset`` (zeros at creation);
     ``hop`` -- samples per hop at ``config.sample_rate``; ``hop_in`` -- samples ``push`` takes per stream (``hop``
     without ``input_rate``); ``delay_samples`` -- the resampler's delay in samples at ``config.sample_rate`` (10 = 0.625 ms for
@@ -944,7 +953,7 @@ class StreamingSpotter:
                  config: Optional[AudioConfig] = None, device: int = 0, use_graph: bool = False, smooth_window: int = 0,
                  vad_log_energy: Optional[float] = None, vad_windows: Tuple[int, int] = (40, 80), host_results: bool = True,
                  input_rate: Optional[int] = None, utterances: Optional[UtteranceConfig] = None,
-                 detect: Optional[DetectConfig] = None):
+                 detect: Optional[DetectConfig] = None, active=None):
         from kws import _native
 
         self.config = config or AudioConfig()
@@ -1031,6 +1040,14 @@ class StreamingSpotter:
             first_hop = WINDOW_FRAMES + self._det_lag - 1 if d.skip_partial_windows else 0
             self._ctx.stream_detect_open(self.model.num_classes, d.smooth_window, d.first_keyword, d.threshold, d.refractory, first_hop,
                                          self._det_max_events)
+        # sparse sets (kws_stream_deactivate / kws_stream_activate): which streams the pushes serve; all of them unless told otherwise
+        self._active = np.ones(self.n_streams, dtype=np.bool_)
+        if active is not None:
+            initial = np.asarray(active)
+            if initial.shape != (self.n_streams,) or initial.dtype != np.bool_:
+                raise ModelError(f"active expects bool [{self.n_streams}]")
+            if not initial.all():
+                self.deactivate(np.flatnonzero(~initial))
         torch.cuda.synchronize(self.device)
 
     def load_model(self, model: KeywordSpottingModel) -> None:
@@ -1107,8 +1124,51 @@ class StreamingSpotter:
             raise ModelError("kws_stream_reset: kws_stream_smooth_f32 (smooth_window > 0) keeps a running sum and one hop count for all "
                              "streams, which no single stream can leave; smooth with detect=DetectConfig(...) on spotters that reset streams")
         self._ctx.stream_reset(idx)
+        self.stream_origin[idx[self._active[idx]]] = self._pushes  # (on an inactive stream the reset is a no-op)
+        return self._pushes
+
+    def _sparse_indices(self, streams, what: str) -> np.ndarray:
+        """The checks ``activate`` and ``deactivate`` share: the indices, and what the spotter already knows the device refuses."""
+        idx = np.atleast_1d(np.asarray(streams))
+        if idx.ndim != 1 or (idx.size and not np.issubdtype(idx.dtype, np.integer)):
+            raise ModelError(f"{what} expects a stream index or a sequence of stream indices")
+        if idx.size and (idx.min() < 0 or idx.max() >= self.n_streams):
+            raise ModelError(f"{what}: stream indices must be in [0, {self.n_streams})")
+        if not self.model._stream_zero_copy:
+            raise ModelError(f"{what}: a {type(self.model).__name__} push is three launches over every slot of the set "
+                             "(kws_stream_push_cnn_trad_i16); only the DS-CNN's one-launch push serves a set with inactive streams")
+        if self.use_graph:
+            raise ModelError(f"{what}: use_graph=True replays launches captured for every slot of the set; create the spotter without it")
+        if self.smooth_window > 0:
+            raise ModelError(f"kws_stream_{what}: kws_stream_smooth_f32 (smooth_window > 0) keeps a running sum and one hop count for all "
+                             "streams, which no single stream can leave; smooth with detect=DetectConfig(...) on spotters whose streams come and go")
+        if self._vad is not None:
+            raise ModelError(f"{what}: vad_log_energy steps kws_stream_vad_f32 over every slot of the set; use utterances=UtteranceConfig(...)")
+        return idx.astype(np.int64)
+
+    def deactivate(self, streams) -> None:
+        """Take ``streams`` (an index or a sequence; duplicates are fine) out of the set between two pushes
+        (``kws_stream_deactivate``): an utterance open on one closes with ``"end_of_recording"``, and from the next push on nothing
+        is launched, read or written for them -- their rows of ``push``'s input may hold anything and their result rows go stale.
+        Naming an inactive stream does nothing.  Nothing waits for the device."""
+        idx = self._sparse_indices(streams, "deactivate")
+        self._ctx.stream_deactivate(idx)
+        self._active[idx] = False
+
+    def activate(self, streams) -> int:
+        """(Re)join ``streams`` to the set between two pushes (``kws_stream_activate``): each gets the whole of ``reset`` -- it
+        starts as a stream that has heard silence ever since the spotter was created -- and is served from the next push on.  On
+        an active stream this is ``reset``.  Returns the number of hops pushed so far and records it in ``stream_origin``."""
+        idx = self._sparse_indices(streams, "activate")
+        self._ctx.stream_activate(idx)
+        self._active[idx] = True
         self.stream_origin[idx] = self._pushes
         return self._pushes
+
+    @property
+    def active(self) -> np.ndarray:
+        """``np.bool_[S]``: which streams the pushes serve (the device library's own record, ``kws_stream_active``)."""
+        return self._ctx.stream_active(self.n_streams)[0]
 
     def _fetch_vad(self):
         if self._vad is not None:
