@@ -297,7 +297,15 @@ int kws_infer_host_i16(kws_ctx* ctx, const int16_t* h_wav, int B, float* h_logit
  * the wait -- and hands back a ticket; kws_infer_host_wait(ctx, ticket) blocks until every batch up to that ticket has its
  * results in its h_logits / h_label (ticket 0: everything in flight).  Submitting batch k+1 before waiting for batch k lets
  * k+1's pack and H2D run under k's kernels.  Results of older batches are also delivered whenever a later submit needs
- * their staging slot.  kws_infer_host_i16 == submit + wait. */
+ * their staging slot.  kws_infer_host_i16 == submit + wait.
+ * A submit that is REFUSED -- KWS_EINVAL (B <= 0, a NULL or a device pointer) or KWS_ESTATE (no front end or model; the class
+ * count or n_samples changed while batches are in flight) -- has enqueued nothing and leaves the ring, its slots and every
+ * ticket in flight exactly as they were: their results still arrive (it may use up a ticket NUMBER, never one handed out).
+ * A submit that FAILS after enqueuing chunks of its own (a HIP error mid-batch) first delivers the chunks of every older
+ * ticket, then drops its own chunks only, and writes its ticket number to *ticket.  kws_infer_host_wait never returns KWS_OK
+ * over rows nobody filled: a wait that covers a dropped ticket (its number, a later one, or 0) -- dropped by such a submit or
+ * because its results failed to return -- delivers what it can of the OTHER tickets, returns the code of the failure and
+ * names the dropped ticket(s) in kws_last_error, once. */
 int kws_infer_host_submit_i16(kws_ctx* ctx, const int16_t* h_wav, int B, float* h_logits, int32_t* h_label, uint64_t* ticket);
 int kws_infer_host_wait(kws_ctx* ctx, uint64_t ticket);
 /* Pipeline shape of kws_infer_host_i16: clips per chunk (default 1024), staging slots in flight (default 3, 2..16), host

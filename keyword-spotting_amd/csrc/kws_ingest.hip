@@ -14,90 +14,14 @@
 // pin_memory) skips the pack stage: the DMA reads it directly.  The PCIe-inclusive rate of this path is reported by
 // tools/bench_ingest.py, never as bench.py's `value`.
 #include <algorithm>
-#include <condition_variable>
 #include <cstring>
-#include <mutex>
 #include <new>
-#include <system_error>
 #include <thread>
 
 #include "kws_ctx.h"
+#include "kws_pack_pool.h"
 
 namespace kws {
-
-// A fixed set of host threads that copy one chunk in parallel (a single memcpy moves ~10-20 GB/s; the PCIe DMA behind it
-// takes ~50): job = (dst, src, bytes), cut into equal 4 KiB-aligned slices.
-class PackPool {
-  public:
-    explicit PackPool(int n) {
-        // a host that refuses more threads (cgroup pids limit, RLIMIT_NPROC) still gets a pool: of the threads that did start,
-        // or of none -- copy() then runs on the calling thread.  Nothing is thrown across the C ABI.
-        try {
-            for (int i = 0; i < n; ++i) workers_.emplace_back([this, i] { run(i); });
-        } catch (const std::system_error&) {
-        }
-        n_started_ = workers_.size();
-    }
-    ~PackPool() {
-        {
-            std::lock_guard<std::mutex> g(m_);
-            stop_ = true;
-        }
-        cv_.notify_all();
-        for (auto& t : workers_) t.join();
-    }
-    int size() const { return (int)workers_.size(); }
-    // blocks until the whole copy is done (the caller enqueues the DMA right after)
-    void copy(void* dst, const void* src, size_t bytes) {
-        if (workers_.empty() || bytes < (1u << 20)) {
-            memcpy(dst, src, bytes);
-            return;
-        }
-        std::unique_lock<std::mutex> g(m_);
-        dst_ = static_cast<unsigned char*>(dst);
-        src_ = static_cast<const unsigned char*>(src);
-        bytes_ = bytes;
-        pending_ = (int)n_started_;
-        ++gen_;
-        cv_.notify_all();
-        done_.wait(g, [this] { return pending_ == 0; });
-    }
-
-  private:
-    void run(int idx) {
-        unsigned long seen = 0;
-        for (;;) {
-            unsigned char* dst;
-            const unsigned char* src;
-            size_t bytes;
-            {
-                std::unique_lock<std::mutex> g(m_);
-                cv_.wait(g, [&] { return stop_ || gen_ != seen; });
-                if (stop_) return;
-                seen = gen_;
-                dst = dst_, src = src_, bytes = bytes_;
-            }
-            const size_t n = n_started_;
-            const size_t slice = ((bytes + n - 1) / n + 4095) & ~(size_t)4095;
-            const size_t lo = std::min(bytes, slice * idx), hi = std::min(bytes, lo + slice);
-            if (hi > lo) memcpy(dst + lo, src + lo, hi - lo);
-            {
-                std::lock_guard<std::mutex> g(m_);
-                if (--pending_ == 0) done_.notify_one();
-            }
-        }
-    }
-    std::vector<std::thread> workers_;
-    size_t n_started_ = 0;  // fixed before any job is posted (workers_.size() must not be read while the vector may still grow)
-    std::mutex m_;
-    std::condition_variable cv_, done_;
-    unsigned char* dst_ = nullptr;
-    const unsigned char* src_ = nullptr;
-    size_t bytes_ = 0;
-    int pending_ = 0;
-    unsigned long gen_ = 0;
-    bool stop_ = false;
-};
 
 struct IngestSlot {
     PinnedBuffer<int16_t> h_in;      // pinned [chunk][n_samples]
@@ -121,6 +45,13 @@ struct Ingest {
     int pool_threads = 0;
     uint64_t next_ticket = 1;
     int next_slot = 0, lane = 0;   // ring position and H2D stream of the next chunk (they persist across submit calls)
+    // tickets whose chunks were dropped after a HIP failure and that no kws_infer_host_wait has reported yet, with the code of
+    // the failure: their callers' arrays are incomplete, and a wait that covers one must say so
+    struct Dropped {
+        uint64_t ticket;
+        int code;
+    };
+    std::vector<Dropped> dropped;
     // configuration requested through kws_ingest_config (0 = default)
     int want_chunk = 0, want_slots = 0, want_threads = 0;
 };
@@ -217,6 +148,60 @@ static int host_pointer_kind(const void* p) {
     return 0;  // unregistered / managed: treated as pageable
 }
 
+// Let the pipeline's own streams run dry before chunks are forgotten: a forgotten slot's staging memory is packed into by the
+// host and its device buffers are written by the next chunk that takes it, on whichever H2D stream comes next.
+static void ingest_quiesce(kws_ctx* c) {
+    Ingest* g = c->ingest;
+    for (hipStream_t st : {g->copy_in[0], g->copy_in[1], c->stream, g->copy_out}) (void)hipStreamSynchronize(st);
+    (void)hipGetLastError();
+}
+
+// Forget every chunk of `ticket` that the ring still carries and remember the ticket, so that kws_infer_host_wait reports it
+// instead of returning KWS_OK over rows nobody filled.  (The streams have been quiesced by the caller.)
+static void ingest_drop(Ingest* g, uint64_t ticket, int code) {
+    for (auto& s : g->slots)
+        if (s.count && s.ticket == ticket) s.count = 0;
+    for (const auto& d : g->dropped)
+        if (d.ticket == ticket) return;
+    g->dropped.push_back({ticket, code});
+}
+
+// Deliver every chunk of the tickets up to `limit`, oldest first.  A chunk whose D2H failed takes its whole ticket with it
+// (ingest_drop) -- and only that ticket: the chunks of the others are still delivered.
+static void ingest_drain(kws_ctx* c, uint64_t limit) {
+    Ingest* g = c->ingest;
+    bool quiet = false;
+    for (int i = 0; i < g->n_slots; ++i) {
+        IngestSlot& s = g->slots[(g->next_slot + i) % g->n_slots];
+        if (!s.count || s.ticket > limit) continue;
+        const int rc = ingest_collect(c, s);
+        if (rc == KWS_OK) continue;
+        if (!quiet) ingest_quiesce(c);
+        quiet = true;
+        ingest_drop(g, s.ticket, rc);
+    }
+}
+
+// The unreported dropped tickets up to `limit`: none -> KWS_OK; else they are taken off the list and named in the error text,
+// with the code of the first one's failure.
+static int ingest_report_dropped(kws_ctx* c, uint64_t limit) {
+    Ingest* g = c->ingest;
+    std::string names;
+    int code = KWS_OK, n = 0;
+    for (size_t i = 0; i < g->dropped.size();) {
+        if (g->dropped[i].ticket > limit) {
+            ++i;
+            continue;
+        }
+        if (!n++) code = g->dropped[i].code;
+        names += (names.empty() ? "" : ", ") + std::to_string(g->dropped[i].ticket);
+        g->dropped.erase(g->dropped.begin() + (std::ptrdiff_t)i);
+    }
+    if (!n) return KWS_OK;
+    return fail(c, code, std::string("kws_infer_host_wait: the results of ") + (n > 1 ? "tickets " : "ticket ") + names +
+                             " were dropped after a failure (code " + std::to_string(code) + "): their h_logits / h_label are incomplete");
+}
+
 }  // namespace kws
 
 using namespace kws;
@@ -241,18 +226,21 @@ int kws_ingest_config(kws_ctx* c, int chunk_clips, int n_slots, int pack_threads
 
 // Enqueue one host batch: every chunk is packed (pageable input), sent, computed and its results started on their way back;
 // slots still carrying an older chunk are collected (results copied to THAT chunk's destination) as the ring comes round.
-static int ingest_submit(kws_ctx* c, const int16_t* h_wav, int B, float* h_logits, int32_t* h_label, uint64_t* ticket_out) {
+// Every argument and state check comes before the call takes its ticket, and a call refused by one has touched nothing: the
+// ring, the slots and the tickets in flight are as they were.  *began is the call's ticket once it has one (0 before): an
+// error with *began != 0 may have left chunks of this call in the ring (ingest_abandon).
+static int ingest_submit(kws_ctx* c, const int16_t* h_wav, int B, float* h_logits, int32_t* h_label, uint64_t* ticket_out, uint64_t* began) {
     if (!h_wav || !h_logits) return fail(c, KWS_EINVAL, "kws_infer_host_submit_i16: h_wav and h_logits must not be NULL");
     if (B <= 0) return fail(c, KWS_EINVAL, "kws_infer_host_submit_i16: B must be positive");
     if (!c->fe_ready || !c->model_ready) return fail(c, KWS_ESTATE, "kws_infer_host_submit_i16: front end or model not configured");
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = ingest_prepare(c);
-    if (rc) return rc;
-    Ingest* g = c->ingest;
-    const int n = g->n_samples, C = g->classes;
     const int kind = host_pointer_kind(h_wav);
     if (kind < 0 || host_pointer_kind(h_logits) < 0 || (h_label && host_pointer_kind(h_label) < 0))
         return fail(c, KWS_EINVAL, "kws_infer_host_submit_i16: h_wav / h_logits / h_label must be HOST pointers (device tensors go to kws_infer_i16)");
+    int rc = ingest_prepare(c);  // rebuilds the ring only when nothing is in flight, refuses (KWS_ESTATE) otherwise
+    if (rc) return rc;
+    Ingest* g = c->ingest;
+    const int n = g->n_samples, C = g->classes;
     const bool direct = kind == 1;  // the DMA can read the caller's buffer: no pack stage
     // Chunk size of THIS batch: a batch smaller than the ring (the reference's own batch_size = 1028, train.py:110, against
     // 3 x 1024) would otherwise be one chunk plus a tail, its pack / H2D / compute / D2H strictly one after the other; cut
@@ -260,6 +248,7 @@ static int ingest_submit(kws_ctx* c, const int16_t* h_wav, int B, float* h_logit
     int chunk = (B + g->n_slots - 1) / g->n_slots;
     chunk = std::min(g->chunk, std::max(chunk, std::min(B, 128)));  // never above what the staging slots hold
     const uint64_t ticket = g->next_ticket++;
+    *began = ticket;
     for (int first = 0; first < B; first += chunk, g->next_slot = (g->next_slot + 1) % g->n_slots, g->lane ^= 1) {
         IngestSlot& s = g->slots[g->next_slot];
         rc = ingest_collect(c, s);  // blocks only if this slot's previous chunk is still in flight
@@ -290,38 +279,51 @@ static int ingest_submit(kws_ctx* c, const int16_t* h_wav, int B, float* h_logit
     return KWS_OK;
 }
 
-// Collect every chunk of the batches up to `ticket` (0: everything in flight), oldest first.
+// A submit failed with `code` after it took `ticket` (a HIP error mid-batch): the callers of the OLDER tickets get their
+// results first, then the streams run dry and only this call's own chunks are forgotten; the ticket is remembered as dropped.
+// The error text of the failure itself is kept.
+static void ingest_abandon(kws_ctx* c, uint64_t ticket, int code) {
+    const std::string err = c->err;
+    ingest_drain(c, ticket - 1);
+    ingest_quiesce(c);
+    ingest_drop(c->ingest, ticket, code);
+    c->err = err;
+}
+
+// Collect every chunk of the batches up to `ticket` (0: everything in flight), oldest first, then report the tickets among
+// them whose chunks were dropped: never KWS_OK over rows nobody filled.
 static int ingest_wait(kws_ctx* c, uint64_t ticket) {
     Ingest* g = c->ingest;
-    if (!g || g->slots.empty()) return KWS_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    for (int i = 0; i < g->n_slots; ++i) {
-        IngestSlot& s = g->slots[(g->next_slot + i) % g->n_slots];
-        if (s.count && (ticket == 0 || s.ticket <= ticket)) {
-            int rc = ingest_collect(c, s);
-            if (rc) {  // a failed D2H: let the device finish, then forget what was in flight (the caller's arrays stay partial)
-                (void)hipDeviceSynchronize();
-                for (auto& t : g->slots) t.count = 0;
-                return rc;
-            }
-        }
+    if (!g) return KWS_OK;
+    const uint64_t limit = ticket ? ticket : UINT64_MAX;
+    if (!g->slots.empty()) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        ingest_drain(c, limit);
     }
-    return KWS_OK;
+    return ingest_report_dropped(c, limit);
 }
 
 int kws_infer_host_submit_i16(kws_ctx* c, const int16_t* h_wav, int B, float* h_logits, int32_t* h_label, uint64_t* ticket) {
     if (!c) return KWS_EINVAL;
-    try {
-        int rc = ingest_submit(c, h_wav, B, h_logits, h_label, ticket);
-        if (rc) {  // a call that failed half-way may have left chunks in flight: let them finish, then forget them
-            (void)hipDeviceSynchronize();
-            if (c->ingest)
-                for (auto& t : c->ingest->slots) t.count = 0;
+    uint64_t began = 0;
+    // failed half-way: chunks of this call may be in flight (a refusal, began == 0, has touched nothing)
+    auto failed = [&](int code) noexcept {
+        if (!began) return;
+        try {
+            ingest_abandon(c, began, code);
+        } catch (...) {
         }
+        if (ticket) *ticket = began;  // the number kws_infer_host_wait will name
+    };
+    try {
+        const int rc = ingest_submit(c, h_wav, B, h_logits, h_label, ticket, &began);
+        if (rc) failed(rc);
         return rc;
     } catch (const std::bad_alloc&) {
+        failed(KWS_ENOMEM);
         return fail(c, KWS_ENOMEM, "kws_infer_host_submit_i16: out of host memory");
     } catch (...) {
+        failed(KWS_EHIP);
         return fail(c, KWS_EHIP, "kws_infer_host_submit_i16: unexpected C++ exception");
     }
 }
@@ -339,7 +341,13 @@ int kws_infer_host_i16(kws_ctx* c, const int16_t* h_wav, int B, float* h_logits,
     if (!c) return KWS_EINVAL;
     uint64_t ticket = 0;
     int rc = kws_infer_host_submit_i16(c, h_wav, B, h_logits, h_label, &ticket);
-    if (rc) return rc;
+    if (rc) {  // this return reports the failure: a dropped ticket of this very call is not reported to a later wait again
+        if (ticket && c->ingest) {
+            auto& d = c->ingest->dropped;
+            d.erase(std::remove_if(d.begin(), d.end(), [&](const Ingest::Dropped& x) { return x.ticket == ticket; }), d.end());
+        }
+        return rc;
+    }
     return kws_infer_host_wait(c, ticket);
 }
 

@@ -244,12 +244,16 @@ class Context:
             raise error_cls(f"kws_create failed ({rc}): {msg}")
         self.device = int(device)
         self.num_classes = None
+        # {ticket: (logits, label, source)} of the host batches in flight: the library holds raw pointers to them until
+        # infer_host_wait retires the ticket, whatever the caller does with the tuple infer_host_submit_i16 returned
+        self._host_inflight = {}
 
     # -- plumbing -------------------------------------------------------------------------------
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             self._lib.kws_destroy(self._h)
             self._h = _c_ctx()
+            self._host_inflight.clear()
 
     def __del__(self):  # best effort
         try:
@@ -469,12 +473,18 @@ class Context:
 
     def infer_host_wait(self, ticket: int = 0):
         """Block until every submitted batch up to ``ticket`` (0: all) has its results in its host arrays."""
-        self._check(self._lib.kws_infer_host_wait(self._h, C.c_uint64(int(ticket))), ModelError)
+        ticket = int(ticket)
+        self._check(self._lib.kws_infer_host_wait(self._h, C.c_uint64(ticket)), ModelError)
+        # retired: the library has let go of every batch up to the ticket (after an error the arrays stay referenced, which is
+        # always safe, until a later wait succeeds or the context closes)
+        for t in [t for t in self._host_inflight if ticket == 0 or t <= ticket]:
+            del self._host_inflight[t]
 
     def infer_host_submit_i16(self, wav: np.ndarray, logits: np.ndarray = None, label: np.ndarray = None):
         """Enqueue one host batch without waiting for its results (``kws_infer_host_submit_i16``).  Returns (logits, label,
         ticket, keepalive): the arrays are filled once ``infer_host_wait(ticket)`` has returned; keep ``keepalive`` (the
-        source buffer -- a pinned one is read by the DMA until then) referenced until that wait."""
+        source buffer -- a pinned one is read by the DMA until then) referenced until that wait.  The context itself also keeps
+        the three referenced until ``infer_host_wait`` retires the ticket: the library holds raw pointers to them."""
         if self.num_classes is None:
             raise ModelError("no model loaded (kws_load_dscnn)")
         if hasattr(wav, "data_ptr"):  # CPU torch tensor (possibly pinned)
@@ -495,6 +505,7 @@ class Context:
         ticket = C.c_uint64(0)
         self._check(self._lib.kws_infer_host_submit_i16(self._h, C.c_void_p(src), B, C.c_void_p(logits.ctypes.data),
                                                         C.c_void_p(label.ctypes.data), C.byref(ticket)), ModelError)
+        self._host_inflight[int(ticket.value)] = (logits, label, wav)
         return logits, label, int(ticket.value), wav
 
     # -- cnn-trad-fpool3 on recordings and streams ---------------------------------------------------
