@@ -16,7 +16,7 @@ static_assert(LIVE_MAX_STREAMS <= EQ_MAX_THREADS, "eq_emit counts one ballot per
 
 namespace {
 
-// What a step reads.  The first group is set per launch (utt_launch); the set's own size, rules and buffers below it are filled
+// What a step reads.  The first group is set per launch (utt_args); the set's own size, rules and buffers below it are filled
 // once by kws_stream_utt_open.  The unit's device counters q.unit()[2] = frames walked, hops appended; the queue's progress word
 // (h_ctr[1]) is the frames walked.
 struct LiveArgs {
@@ -52,16 +52,27 @@ struct StreamUtt {
 
 namespace {
 
-// One hop of every stream: append, walk one frame, emit.  ONE workgroup, thread s = stream s (threads at or beyond S only
-// help with the copy, the ballots and the barriers).  FLUSH: no append and no walk -- every stream inside an utterance closes
-// at the newest walked frame with reason 2.  The streams that closed at this step emit their records and thread 0 publishes
-// the totals as kws_event_queue.h lays down (eq_emit, eq_publish).
-template <bool FLUSH>
-__global__ __launch_bounds__(LIVE_MAX_STREAMS) void kws_live_step_kernel(const LiveArgs a) {
+// One hop of every stream: append, walk one frame of the endpointer, close and emit, publish -- the body of the four step kernels
+// below.  ONE workgroup, thread s = stream s (threads at or beyond S only help with the copy, the ballots and the barriers).  The
+// streams that closed at this step emit their records and thread 0 publishes the totals as kws_event_queue.h lays down (eq_emit,
+// eq_publish): every thread gets there in every instantiation -- no early return, and the mask below gates only the copy, the
+// walk and `closed`.
+// FLUSH: no append and no walk -- every stream inside an utterance closes at the newest walked frame with reason 2.
+// MASKED: `m` names the streams that take part; a stream outside it appends nothing, pushes no flag, walks nothing and emits
+// nothing, while its thread takes part in the ballots and the barriers.  The unit's two counters run on for the whole set.
+// RESET (a masked flush): the named streams then start over -- flag ring, window counts and the open frame as
+// kws_stream_utt_open leaves them, prev_close = hops appended - 1, so that ep_span_start keeps a later utterance of the stream
+// from starting before the first sample pushed after the reset.  The history ring stays: what closed before the reset remains
+// cuttable.  The unit's own counters stand.
+// `a` by value: by reference the compiler schedules the dense step differently.
+template <bool FLUSH, bool MASKED, bool RESET = false>
+__device__ __forceinline__ void live_step(const LiveArgs a, const ResetMask* m = nullptr) {
+    static_assert(!RESET || (FLUSH && MASKED), "a reset is the flush of the streams a mask names");
+    auto mine = [&](int s) { return !MASKED || m->has(s); };
     const int tid = threadIdx.x;
     const EqCounts was = eq_counts(a.q);
     const unsigned long long frames = was.unit[0], appended = was.unit[1];
-    bool do_append = false, do_walk = false;
+    bool do_append = false, do_walk = false;  // workgroup-uniform
     const int16_t* src = a.hop;
     const float* energy = a.energy;
     long long e_stride = 1;
@@ -80,25 +91,25 @@ __global__ __launch_bounds__(LIVE_MAX_STREAMS) void kws_live_step_kernel(const L
             do_walk = a.energy != nullptr;
         }
     }
-    if (do_append) {  // workgroup-uniform; a hop never straddles the seam: H is a multiple of step
+    if (do_append) {  // a hop never straddles the seam: H is a multiple of step
         const int at = (int)((appended * (unsigned long long)a.step) % (unsigned long long)a.H);
         if (a.vec) {
             const int per = a.step >> 3;
             for (int i = tid; i < a.S * per; i += (int)blockDim.x) {
                 const int s = i / per, j = i - s * per;
-                reinterpret_cast<uint4*>(a.hist + (size_t)s * a.H + at)[j] = reinterpret_cast<const uint4*>(src + (size_t)s * a.hop_stride)[j];
+                if (mine(s)) reinterpret_cast<uint4*>(a.hist + (size_t)s * a.H + at)[j] = reinterpret_cast<const uint4*>(src + (size_t)s * a.hop_stride)[j];
             }
         } else {
             for (int i = tid; i < a.S * a.step; i += (int)blockDim.x) {
                 const int s = i / a.step, j = i - s * a.step;
-                a.hist[(size_t)s * a.H + at + j] = src[(size_t)s * a.hop_stride + j];
+                if (mine(s)) a.hist[(size_t)s * a.H + at + j] = src[(size_t)s * a.hop_stride + j];
             }
         }
     }
     bool closed = false;
     long long open = 0, start_frame = 0, close_frame = 0;
     int reason = 0;
-    if (tid < a.S && (FLUSH || do_walk)) {
+    if (tid < a.S && (FLUSH || do_walk) && mine(tid)) {
         int* cnt = a.counts + 4 * tid;
         long long* ps = a.pos + 2 * tid;
         int trig = cnt[2];
@@ -136,120 +147,42 @@ __global__ __launch_bounds__(LIVE_MAX_STREAMS) void kws_live_step_kernel(const L
             ps[1] = close_frame;
             cnt[2] = 0;
         }
-    }
-    const long long rec[LIVE_REC] = {(long long)tid, start_frame * a.step, close_frame * a.step + a.frame_len, open, close_frame, (long long)reason};
-    const int all = eq_emit(a.q, was, closed, rec);
-    const unsigned long long frames_now = frames + (do_walk ? 1 : 0);
-    eq_publish(a.q, was, all, frames_now);
-    if (tid == 0) {
-        a.q.unit()[0] = frames_now;
-        a.q.unit()[1] = appended + (do_append ? 1 : 0);
-    }
-}
-
-// kws_stream_reset's step: the FLUSH of the streams `m` names alone -- an utterance open on one of them closes at the newest walked
-// frame with reason 2 and is queued, one more tick of the queue --, which then start over: flag ring, window counts and the open
-// frame as kws_stream_utt_open leaves them, prev_close = hops appended - 1, so that ep_span_start keeps a later utterance of the
-// stream from starting before the first sample pushed after the reset.  The history ring stays: what closed before the reset
-// remains cuttable.  A kernel of its own, not a third instantiation of the one above: with the mask folded into that body the
-// compiler scheduled the plain flush differently, and the step and the flush keep the code they had.
-__global__ __launch_bounds__(LIVE_MAX_STREAMS) void kws_live_reset_kernel(const LiveArgs a, const ResetMask m) {
-    const int tid = threadIdx.x;
-    const EqCounts was = eq_counts(a.q);
-    const unsigned long long frames = was.unit[0], appended = was.unit[1];
-    bool closed = false;
-    long long open = 0, start_frame = 0, close_frame = 0;
-    if (tid < a.S && m.has(tid)) {
-        int* cnt = a.counts + 4 * tid;
-        long long* ps = a.pos + 2 * tid;
-        open = ps[0];
-        if (cnt[2]) {  // triggered: at least one frame was walked
-            closed = true;
-            close_frame = (long long)frames - 1;
-            start_frame = ep_span_start(open, a.pre_roll, ps[1]);
-        }
-        ulonglong2* row = reinterpret_cast<ulonglong2*>(a.bits + (size_t)tid * EP_BIT_WORDS);
+        if constexpr (RESET) {
+            ulonglong2* row = reinterpret_cast<ulonglong2*>(a.bits + (size_t)tid * EP_BIT_WORDS);
 #pragma unroll
-        for (int k = 0; k < EP_BIT_WORDS / 2; ++k) row[k] = make_ulonglong2(0ull, 0ull);
-        cnt[0] = cnt[1] = cnt[2] = 0;
-        ps[0] = -1;
-        ps[1] = (long long)appended - 1;
-    }
-    const long long rec[LIVE_REC] = {(long long)tid, start_frame * a.step, close_frame * a.step + a.frame_len, open, close_frame, 2};
-    const int all = eq_emit(a.q, was, closed, rec);
-    eq_publish(a.q, was, all, frames);  // the unit's own counters stand
-}
-
-// The step behind a push of a set with inactive streams (kws_stream_deactivate; `m`: the active ones, by value): the step of
-// kws_live_step_kernel<false> for the active streams -- the same append, walk and rules, so an active stream's records are those of
-// a dense set -- while an inactive stream's thread appends nothing, pushes no flag, walks nothing and emits nothing, but takes part
-// in the ballots and the barriers.  The unit's two counters run on for the whole set.  Only ever stepped by a push (explicit steps
-// are refused while a stream is inactive).  A kernel of its own for the reason kws_live_reset_kernel is one.
-__global__ __launch_bounds__(LIVE_MAX_STREAMS) void kws_live_step_masked_kernel(const LiveArgs a, const ResetMask m) {
-    const int tid = threadIdx.x;
-    const EqCounts was = eq_counts(a.q);
-    const unsigned long long frames = was.unit[0], appended = was.unit[1];
-    const int h = a.ctx_hops[0];  // >= 1 behind a push
-    const bool do_append = h >= 1;
-    const bool do_walk = do_append && appended + 1 >= (unsigned long long)a.K && h >= a.K;
-    if (do_append) {  // workgroup-uniform
-        const int16_t* src = a.hop + (int)(((long long)(h - 1) * a.step) % a.ring_len);
-        const int at = (int)((appended * (unsigned long long)a.step) % (unsigned long long)a.H);
-        if (a.vec) {
-            const int per = a.step >> 3;
-            for (int i = tid; i < a.S * per; i += (int)blockDim.x) {
-                const int s = i / per, j = i - s * per;
-                if (m.has(s)) reinterpret_cast<uint4*>(a.hist + (size_t)s * a.H + at)[j] = reinterpret_cast<const uint4*>(src + (size_t)s * a.hop_stride)[j];
-            }
-        } else {
-            for (int i = tid; i < a.S * a.step; i += (int)blockDim.x) {
-                const int s = i / a.step, j = i - s * a.step;
-                if (m.has(s)) a.hist[(size_t)s * a.H + at + j] = src[(size_t)s * a.hop_stride + j];
-            }
-        }
-    }
-    bool closed = false;
-    long long open = 0, start_frame = 0, close_frame = 0;
-    int reason = 0;
-    if (tid < a.S && do_walk && m.has(tid)) {
-        int* cnt = a.counts + 4 * tid;
-        long long* ps = a.pos + 2 * tid;
-        int trig = cnt[2];
-        open = ps[0];
-        const long long prev_close = ps[1];
-        const long long f = (long long)frames;
-        const float* energy = a.energy + (size_t)((h - a.K) % a.num_frames) * a.numcep;
-        const int v = ep_voiced(energy[(size_t)tid * ((size_t)a.num_frames * a.numcep)], a.threshold) ? 1 : 0;
-        const EpCounts n = ep_ring_push(a.bits + (size_t)tid * EP_BIT_WORDS, cnt, f, v, a.on_window, a.off_window);
-        if (!trig) {
-            if (ep_opens(n.on, a.on_window)) {  // the utterance opens; nothing else happens at this frame
-                open = f;
-                ps[0] = f;
-                cnt[2] = 1;
-            }
-        } else if (ep_closes(n.off, a.off_window)) {
-            closed = true;
-            reason = 0;
-            close_frame = f;
-        } else if (f - open + 1 >= a.max_frames) {
-            closed = true;
-            reason = 1;
-            close_frame = f;
-        }
-        if (closed) {
-            start_frame = ep_span_start(open, a.pre_roll, prev_close);
-            ps[1] = close_frame;
-            cnt[2] = 0;
+            for (int k = 0; k < EP_BIT_WORDS / 2; ++k) row[k] = make_ulonglong2(0ull, 0ull);
+            cnt[0] = cnt[1] = cnt[2] = 0;
+            ps[0] = -1;
+            ps[1] = (long long)appended - 1;
         }
     }
     const long long rec[LIVE_REC] = {(long long)tid, start_frame * a.step, close_frame * a.step + a.frame_len, open, close_frame, (long long)reason};
     const int all = eq_emit(a.q, was, closed, rec);
     const unsigned long long frames_now = frames + (do_walk ? 1 : 0);
     eq_publish(a.q, was, all, frames_now);
-    if (tid == 0) {
-        a.q.unit()[0] = frames_now;
-        a.q.unit()[1] = appended + (do_append ? 1 : 0);
+    if constexpr (!RESET) {
+        if (tid == 0) {
+            a.q.unit()[0] = frames_now;
+            a.q.unit()[1] = appended + (do_append ? 1 : 0);
+        }
     }
+}
+
+// The step of a dense set (a push, kws_stream_utt_step_i16) and kws_stream_utt_flush.
+template <bool FLUSH>
+__global__ __launch_bounds__(LIVE_MAX_STREAMS) void kws_live_step_kernel(const LiveArgs a) {
+    live_step<FLUSH, false>(a);
+}
+
+// kws_stream_reset's step (and a deactivation's): one more tick of the queue.
+__global__ __launch_bounds__(LIVE_MAX_STREAMS) void kws_live_reset_kernel(const LiveArgs a, const ResetMask m) {
+    live_step<true, true, true>(a, &m);
+}
+
+// The step behind a push of a set with inactive streams (kws_stream_deactivate; `m`: the active ones, by value): an active
+// stream's records are those of a dense set.  Only ever stepped by a push (explicit steps are refused while a stream is inactive).
+__global__ __launch_bounds__(LIVE_MAX_STREAMS) void kws_live_step_masked_kernel(const LiveArgs a, const ResetMask m) {
+    live_step<false, true>(a, &m);
 }
 
 // kws_cut_i16_kernel (kws_segment.hip) with a ring origin: one workgroup per sequence number, the record read from the device
@@ -310,16 +243,14 @@ LiveArgs utt_args(kws_ctx* c, const int16_t* hop, long long hop_stride, const in
     return a;
 }
 
-// One launch of the step or flush kernel.
-template <bool FLUSH>
-int utt_launch(kws_ctx* c, const int16_t* hop, long long hop_stride, const int* ctx_hops, const float* energy) {
-    StreamUtt* u = c->stream_utt;
-    const LiveArgs a = utt_args(c, hop, hop_stride, ctx_hops, energy);
+// One launch of a step kernel, with its mask where it takes one, and the queue's tick.  Threads: one per stream, in whole wavefronts.
+template <class... Mask>
+int utt_launch(kws_ctx* c, void (*kernel)(LiveArgs, Mask...), const LiveArgs& a, const Mask&... m) {
     int threads = (a.S + 63) / 64 * 64;
-    if (hop && threads < 256) threads = 256;  // the copy is the workgroup's bulk
-    hipLaunchKernelGGL(kws_live_step_kernel<FLUSH>, dim3(1), dim3(threads), 0, c->stream, a);
+    if (a.hop && threads < 256) threads = 256;  // the copy is the workgroup's bulk
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(threads), 0, c->stream, a, m...);
     HIP_TRY(c, hipGetLastError());
-    eq_enqueued(u->a.q);
+    eq_enqueued(c->stream_utt->a.q);
     return KWS_OK;
 }
 
@@ -338,27 +269,16 @@ int stream_utt_push_check(kws_ctx* c, const char* fn) {
 }
 
 int stream_utt_reset(kws_ctx* c, const ResetMask& m) {
-    StreamUtt* u = c->stream_utt;
-    if (!u) return KWS_OK;
-    hipLaunchKernelGGL(kws_live_reset_kernel, dim3(1), dim3((u->a.S + 63) / 64 * 64), 0, c->stream, utt_args(c, nullptr, 0, nullptr, nullptr), m);
-    HIP_TRY(c, hipGetLastError());
-    eq_enqueued(u->a.q);
-    return KWS_OK;
+    if (!c->stream_utt) return KWS_OK;
+    return utt_launch(c, kws_live_reset_kernel, utt_args(c, nullptr, 0, nullptr, nullptr), m);
 }
 
 int stream_utt_pushed(kws_ctx* c) {
     if (!c->stream_utt) return KWS_OK;
     c->stream_utt->mode = 1;
-    if (c->sparse()) {  // some stream is inactive: the masked step, its active streams by value (the unit holds at most one chunk)
-        StreamUtt* u = c->stream_utt;
-        const LiveArgs a = utt_args(c, c->d_pcm_ring.get(), c->ring_len, c->d_hops.get(), c->d_feat_ring.get());
-        const int threads = a.S <= 256 ? 256 : (a.S + 63) / 64 * 64;  // utt_launch's rule for a step that copies
-        hipLaunchKernelGGL(kws_live_step_masked_kernel, dim3(1), dim3(threads), 0, c->stream, a, c->active_chunk(0));
-        HIP_TRY(c, hipGetLastError());
-        eq_enqueued(u->a.q);
-        return KWS_OK;
-    }
-    return utt_launch<false>(c, c->d_pcm_ring.get(), c->ring_len, c->d_hops.get(), c->d_feat_ring.get());
+    const LiveArgs a = utt_args(c, c->d_pcm_ring.get(), c->ring_len, c->d_hops.get(), c->d_feat_ring.get());
+    // some stream is inactive: the masked step, its active streams by value (the unit holds at most one chunk)
+    return c->sparse() ? utt_launch(c, kws_live_step_masked_kernel, a, c->active_chunk(0)) : utt_launch(c, kws_live_step_kernel<false>, a);
 }
 
 }  // namespace kws
@@ -446,14 +366,14 @@ int kws_stream_utt_step_i16(kws_ctx* c, const int16_t* d_hop, const float* d_ene
     if (int rc = refuse_sparse(c, "kws_stream_utt_step_i16", "explicit steps")) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     u->mode = 2;
-    return utt_launch<false>(c, d_hop, c->fp.frame_step, nullptr, d_energy);
+    return utt_launch(c, kws_live_step_kernel<false>, utt_args(c, d_hop, c->fp.frame_step, nullptr, d_energy));
 }
 
 int kws_stream_utt_flush(kws_ctx* c) {
     if (!c) return KWS_EINVAL;
     if (!c->stream_utt) return fail(c, KWS_ESTATE, "kws_stream_utt_flush: call kws_stream_utt_open first");
     HIP_TRY(c, hipSetDevice(c->device));
-    return utt_launch<true>(c, nullptr, 0, nullptr, nullptr);
+    return utt_launch(c, kws_live_step_kernel<true>, utt_args(c, nullptr, 0, nullptr, nullptr));
 }
 
 int kws_stream_utt_poll(kws_ctx* c, uint64_t* total_events, uint64_t* steps) {

@@ -151,10 +151,16 @@ def test_more_than_1024_streams_are_refused(bare):
 
 
 # ---- 8. (and 7.) the ring cut -----------------------------------------------------------------------------------------------
-def _hops_dev(pcm, step=STEP):
-    """int16 [S, hops * step] on the host -> [hops, S, step] on the device, one contiguous [S, step] block per push."""
+def _hops_dev(pcm, step=STEP, skew=0):
+    """int16 [S, hops * step] on the host -> [hops, S, step] on the device, one contiguous [S, step] block per push.  skew: the
+    block starts that many int16 past a 16-byte boundary (an allocation starts on one)."""
     S = pcm.shape[0]
-    return torch.from_numpy(np.ascontiguousarray(pcm.reshape(S, -1, step).transpose(1, 0, 2))).to(DEV)
+    hops = torch.from_numpy(np.ascontiguousarray(pcm.reshape(S, -1, step).transpose(1, 0, 2)))
+    buf = torch.empty(hops.numel() + skew, dtype=torch.int16, device=DEV)
+    assert buf.data_ptr() % 16 == 0
+    out = buf[skew:].view(hops.shape)
+    out.copy_(hops)
+    return out
 
 
 def _cut_step(c, t, hops_dev, e_base, S, K):
@@ -162,10 +168,11 @@ def _cut_step(c, t, hops_dev, e_base, S, K):
     c.stream_utt_step_i16(hops_dev[t], e_base + 4 * S * (t - (K - 1)) if t >= K - 1 else None)
 
 
-@pytest.mark.parametrize("name", list(lr.CUT_GEOMETRIES))
-def test_ring_cut_equals_the_linear_cut(name):
+@pytest.mark.parametrize("name, skew", [pytest.param(n, 0, id=n) for n in lr.CUT_GEOMETRIES] + [pytest.param("400/160", 1, id="400/160-skewed")])
+def test_ring_cut_equals_the_linear_cut(name, skew):
     """History at the slack_hops = 0 minimum, wrapping many times; every record is cut at once after its close, under every
-    normalize_to and n_out; clips and peaks are the bits of cut_ref on the linear signal."""
+    normalize_to and n_out; clips and peaks are the bits of cut_ref on the linear signal.  skewed: every hop is handed over from
+    an address one int16 past a 16-byte boundary, so the step appends it sample by sample and not 16 bytes at a time."""
     frame_len, step, _ = lr.CUT_GEOMETRIES[name]
     K = -(-frame_len // step)
     flags, pcm, records, H, facts = lr.cut_case(name)
@@ -177,7 +184,8 @@ def test_ring_cut_equals_the_linear_cut(name):
         c.stream_open(S)
         assert _arm(c, lr.CUT_ON, lr.CUT_OFF, lr.CUT_PRE_ROLL, lr.CUT_MAX_FRAMES, frame=(frame_len, step)) == H
         assert pcm.shape[1] >= 3 * H
-        hops_dev, e = _hops_dev(pcm, step), _energies(flags)
+        hops_dev, e = _hops_dev(pcm, step, skew), _energies(flags)
+        assert all(hops_dev[t].data_ptr() % 16 == 2 * skew for t in (0, 1, lr.CUT_HOPS - 1))
         clips = [torch.full((N + 1, n_out), 77, dtype=torch.int16, device=DEV) for _, n_out in combos]
         peaks = torch.full((len(combos), N + 1), -7, dtype=torch.int32, device=DEV)
         torch.cuda.synchronize()
